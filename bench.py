@@ -28,6 +28,17 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
                  single-thread processes, each on its 1/P row slab of X -- timed on the host (N=1 only)
 With no flags: N = 1 and 500 timed steps (about 2.3 s of GPU time).
 
+A plain run does only what its headline figure needs: set up, warm up, time the --steps steps, write the outputs if
+--dump-outputs is given, print the line (N > 1 still A/Bs the exchange in the warm-up: the winner is what the timed region
+uses).  Everything else listed above -- roofline(s), kernels, the held clock, sustained, bf16x6, bf16_stored_x, the
+multi_gpu compute-only and allreduce-alone legs, cpu_baseline, reference_example_swim and configs -- is measured only
+with --full; the --no-* switches then leave single parts of it out.
+
+--dump-outputs DIR: after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy
+(float32 / float64, rank 0): the factors W and H of config 3 / 4 (rank 0's share), the estimated rank of config 5.  An
+array over its share of the 48 MiB budget is written as a fixed, seeded sample of its rows (W) or columns (H), with the
+indices kept in DIR/<name>_index.npy.  Inputs depend only on the arguments, so two builds can be compared file by file.
+
 --config {2,3,4,5} (round 4) selects the BASELINE configuration that is measured; 3 (the headline) is the default and is
 unchanged.  2 = MU/FRO 65536 x 4096, k = 32 (the same step on the smaller problem).  4 = MU/KL 131072 x 65536, k = 128 on the
 2D grid the rank count gives (8 ranks: 4 x 2) through nmf_algorithms_2D -- `--emulate-ranks 8` runs ONE rank's 32768 x 32768
@@ -43,15 +54,15 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from benchlib.common import (CONFIGS, PEAK_CLOCK_GHZ, PEAK_FP32_MFMA_TFLOPS, PEAK_HBM_GBS, Job, event_time_ms, flush_c_stdio,  # noqa: E402
-                             parse_grid, pmc_traffic, rccl_record)
+from benchlib.common import (CONFIGS, PEAK_CLOCK_GHZ, PEAK_FP32_MFMA_TFLOPS, PEAK_HBM_GBS, Job, dump_outputs, event_time_ms,  # noqa: E402
+                             flush_c_stdio, parse_grid, pmc_traffic, rccl_record)
 from benchlib.config4 import run_config4  # noqa: E402
 from benchlib.config5 import run_config5, swim_example  # noqa: E402
 from benchlib.cpu_baseline import (_cpu_hals_rank, _cpu_kl_rank, _cpu_pool, cpu_baseline, cpu_baseline_allcores,  # noqa: E402
                                    host_cpu)
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--config", type=int, default=3, choices=[2, 3, 4, 5],
@@ -97,12 +108,24 @@ def parse_args():
     ap.add_argument("--overlap-chunks", default="auto",
                     help="N > 1: column chunks of the H phase's overlapped exchange; 'auto' (default) times 1 / 2 / 4 in "
                          "the warm-up and uses the fastest")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="measure everything beside the headline too (rooflines, kernels, held clock, "
+                    "sustained, bf16x6, bf16-stored X, the multi_gpu breakdown, cpu_baseline, the swim example, the other configs); "
+                    "a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
+    a = ap.parse_args(argv)
     dflt = CONFIGS[a.config]
     for key in ("m", "n", "k", "norm", "steps", "warmup"):
         if getattr(a, key) is None:
             setattr(a, key, dflt[key])
+    if not a.full:
+        for key in LEAN_SKIPS:
+            setattr(a, key, True)
     return a
+
+
+# what a plain run leaves out (--full measures them, each still switchable off with its --no-* flag)
+LEAN_SKIPS = ("no_cpu_baseline", "no_kernel_timing", "no_sustained", "no_bf16x6", "no_configs", "no_swim")
 
 
 # BASELINE.json `configs` (1 = the reference's own CPU case: a parity test, tests/test_gpu_parity.py, not a bench line)
@@ -130,7 +153,7 @@ def other_configs():
     for name, args in runs.items():
         t0 = time.time()
         try:
-            res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-configs"] + args, capture_output=True, text=True,
+            res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-configs"] + args, capture_output=True, text=True,
                                  timeout=120, env=env)
             line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
             if res.returncode != 0 or not line:
@@ -442,6 +465,8 @@ def main():
     torch.cuda.synchronize()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     assert torch.isfinite(W).all() and torch.isfinite(H).all()
+    if a.dump_outputs and rank == 0:                              # before anything below steps W and H again
+        dump_outputs(a.dump_outputs, [("W", W, 0), ("H", H, 1)])
     if multi and mg.get("exchange_used") == "native-direct":
         # a direct allreduce that gave up on a peer inside the timed loop would have timed garbage: fatal on every rank together
         if max_over_ranks(1.0 if p._native_comm.direct_timed_out() else 0.0) > 0:
@@ -450,7 +475,7 @@ def main():
     # N > 1: where the step's time goes.  (a) the same step with the exchange stubbed out (NullExchange: every allreduce
     # returns at once, so H diverges between ranks -- timing only; H is re-broadcast afterwards): per-rank compute-only
     # ms; exposed_comm_ms = full step - slowest rank's compute-only step.  (b) the packed [W^T A | W^T W] allreduce alone.
-    if multi:
+    if multi and a.full:
         from pydnmfk_amd.dist_comm import NullExchange
         pn = parse()
         pn.__dict__.update(vars(p))

@@ -44,6 +44,36 @@ def event_time_ms(fn, reps=5, warm=2):
     return sum(ts) / len(ts), ts[0]
 
 
+DUMP_BUDGET_BYTES = 48 << 20     # --dump-outputs: all arrays together (the sample indices come on top: 8 B per kept slice)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES):
+    """bench.py --dump-outputs: write `arrays` = [(name, tensor or array, axis)] as <outdir>/<name>.npy, float64 kept, every other
+    dtype as float32.  An array larger than its equal share of `budget` is written as a fixed sample of its slices along `axis`:
+    DUMP_SEED picks them (sorted, the same for a given shape on every run) and <outdir>/<name>_index.npy (float64) lists them."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, x, axis in arrays:
+        if isinstance(x, torch.Tensor):
+            x = x.detach()
+            x = (x if x.dtype == torch.float64 else x.float()).cpu().numpy()
+        x = np.asarray(x)
+        if x.dtype != np.float64:
+            x = x.astype(np.float32)
+        count = x.shape[axis] if x.ndim else 1
+        keep = share // max(1, x.nbytes // max(1, count))
+        if x.ndim and count > keep:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(count, size=keep, replace=False))
+            x = np.take(x, idx, axis=axis)
+            np.save(os.path.join(outdir, name + "_index.npy"), idx.astype(np.float64))
+        elif os.path.exists(os.path.join(outdir, name + "_index.npy")):      # (left by an earlier run into the same directory)
+            os.remove(os.path.join(outdir, name + "_index.npy"))
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(x))
+
+
 def pmc_traffic(role, workload="bench"):
     """HBM bytes per launch of a kernel from the NEWEST committed PMC pass of the given profiled workload
     (profiles/<tag>_<workload>_pmc.json: separate --pmc runs of tools/collect_profiles.sh, FETCH_SIZE doubled per

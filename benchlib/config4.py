@@ -4,7 +4,8 @@ import os
 import sys
 import time
 
-from .common import CONFIGS, PEAK_CLOCK_GHZ, PEAK_FP32_MFMA_TFLOPS, PEAK_HBM_GBS, ROOT, event_time_ms, parse_grid, pmc_traffic, rccl_record
+from .common import (CONFIGS, PEAK_CLOCK_GHZ, PEAK_FP32_MFMA_TFLOPS, PEAK_HBM_GBS, ROOT, dump_outputs, event_time_ms, parse_grid, pmc_traffic,
+                     rccl_record)
 from .cpu_baseline import _cpu_kl_rank, _cpu_pool, host_cpu
 
 
@@ -123,9 +124,11 @@ def run_config4(a, job):
         step(it)
     elapsed = job.timed(a.steps, step)
     assert torch.isfinite(W).all() and torch.isfinite(H).all()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, [("W", W, 0), ("H", H, 1)])
     ms = elapsed / a.steps * 1e3
 
-    if multi:      # the same step with every exchange stubbed out (timing only): this rank's compute
+    if multi and a.full:      # the same step with every exchange stubbed out (timing only): this rank's compute
         pn = parse()
         pn.__dict__.update(vars(p))
         native_used = p.exchange == "native"

@@ -5,7 +5,8 @@ import os
 import sys
 import time
 
-from .common import CONFIGS, PEAK_CLOCK_GHZ, PEAK_FP32_MFMA_TFLOPS, PEAK_HBM_GBS, ROOT, event_time_ms, parse_grid, pmc_traffic, rccl_record
+from .common import (CONFIGS, PEAK_CLOCK_GHZ, PEAK_FP32_MFMA_TFLOPS, PEAK_HBM_GBS, ROOT, dump_outputs, event_time_ms, parse_grid, pmc_traffic,
+                     rccl_record)
 from .cpu_baseline import _cpu_hals_rank, _cpu_pool, host_cpu
 
 
@@ -118,6 +119,8 @@ def run_config5(a, job):
     for i in range(max(1, a.warmup)):
         sweep(i, small=True)                                           # loads every kernel class of the sweep; not a full sweep
     elapsed = job.timed(a.steps, sweep)
+    if a.dump_outputs and rank == 0:                                   # what PyNMFk.fit returns: the estimated rank
+        dump_outputs(a.dump_outputs, [("estimated_k", [float(nopt[0])], 0)])
     nk = a.end_k - a.start_k + 1
     fits = nk * a.perturbations
     ms = elapsed / a.steps * 1e3

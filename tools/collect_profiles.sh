@@ -10,7 +10,7 @@ WL=${@:-bench kl hals16 hals64 k16 bf16 elt c2}
 cd /tmp && export TMPDIR=/tmp
 prog() {   # the command line of a workload: "full" (stats pass) or "short" (PMC passes)
   case $1 in
-    bench)  if [ "$2" = full ]; then echo "$R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-sustained --no-configs"; else echo "$R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-sustained --no-configs"; fi ;;
+    bench)  if [ "$2" = full ]; then echo "$R/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-sustained --no-configs"; else echo "$R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-sustained --no-configs"; fi ;;
     kl)     echo "$R/tools/klbench.py 32768 32768 128" ;;
     kl16)   echo "$R/tools/klbench.py 32768 16384 16" ;;
     kl32)   echo "$R/tools/klbench.py 32768 16384 32" ;;
@@ -21,8 +21,8 @@ prog() {   # the command line of a workload: "full" (stats pass) or "short" (PMC
     bf16)   echo "$R/tools/kbench.py 262144 8192 64 --bf16" ;;
     elt)    echo "$R/tools/eltbench.py 64" ;;
     elt128) echo "$R/tools/eltbench.py 128" ;;
-    c4)     echo "$R/bench.py --config 4 --emulate-ranks 8 --steps 10 --warmup 2 --no-cpu-baseline" ;;
-    c5)     echo "$R/bench.py --config 5 --no-cpu-baseline" ;;
+    c4)     echo "$R/bench.py --config 4 --emulate-ranks 8 --steps 10 --warmup 2 --full --no-cpu-baseline" ;;
+    c5)     echo "$R/bench.py --config 5 --full --no-cpu-baseline" ;;
     c5s)    echo "$R/bench.py --config 5 --rows 1024 --cols 256 --no-cpu-baseline --no-kernel-timing" ;;
     c5s1)   echo "$R/bench.py --config 5 --rows 1024 --cols 256 --no-cpu-baseline --no-kernel-timing --nmfk-batch 1" ;;
     f64)    echo "$R/tools/f64bench.py 65536 4096 64" ;;
