@@ -11,7 +11,6 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libdnmf_hip.so")
-TUNE_LIB = os.path.join(ROOT, "tools", "_build", "libdnmf_hip_tune.so")   # -DDNMF_TUNING: experiment switches (tools only)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # per-unit compiler flags.  dnmf_kl16: MFMA accumulators in VGPRs (no v_accvgpr copies around the division of the KL
 # products -- on gfx950 every fp32 vector instruction costs matrix-pipe time, csrc/dnmf_kl16.h)
@@ -26,25 +25,17 @@ def _stale():
     return any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps)
 
 
-def build_lib(force=False, report=False, tuning=False):
+def build_lib(force=False, report=False):
     """Compile the translation units csrc/*.hip (dnmf, dnmf_kl, dnmf_hals, dnmf_split; kernels in csrc/dnmf_*.h) side by side and link them into
-    libdnmf_hip.so.  Returns the library path.
-    `tuning=True` builds tools/_build/libdnmf_hip_tune.so instead: the same sources with -DDNMF_TUNING, in which the
-    DNMF_* environment switches and the extra kernel variants of the A/B runs exist (tools/README.md); the shipped
-    library reads no environment."""
+    libdnmf_hip.so.  Returns the library path."""
     import glob
     from concurrent.futures import ThreadPoolExecutor
-    out = TUNE_LIB if tuning else LIB
-    if not tuning and not force and not report and not _stale():
+    if not force and not report and not _stale():
         return LIB
-    objdir = os.path.join(ROOT, "tools", "_build", "obj_tune" if tuning else "obj")
+    objdir = os.path.join(ROOT, "tools", "_build", "obj")
     os.makedirs(objdir, exist_ok=True)
-    os.makedirs(os.path.dirname(out), exist_ok=True)
     flags = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
              "-I" + os.path.join(HERE, "csrc")]
-    if tuning:
-        flags.append("-DDNMF_TUNING")
-        flags += os.environ.get("DNMF_EXTRA_FLAGS", "").split()      # experiments: extra -D switches for the tuning build only
     if report:
         flags.append("-Rpass-analysis=kernel-resource-usage")
     srcs = sorted(glob.glob(os.path.join(HERE, "csrc", "*.hip")))
@@ -64,13 +55,13 @@ def build_lib(force=False, report=False, tuning=False):
 
     with ThreadPoolExecutor(max_workers=len(srcs)) as ex:
         logs = list(ex.map(compile_one, zip(srcs, objs)))
-    res = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs, capture_output=True, text=True)
+    res = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs, capture_output=True, text=True)
     if res.returncode != 0:
         sys.stderr.write(res.stderr)
         raise RuntimeError("hipcc link failed (%d)" % res.returncode)
     if report:
         print(resource_report("".join(logs)))
-    return out
+    return LIB
 
 
 def resource_report(log):
@@ -95,4 +86,4 @@ def resource_report(log):
 
 
 if __name__ == "__main__":
-    print(build_lib(force=True, report="--report" in sys.argv, tuning="--tuning" in sys.argv))
+    print(build_lib(force=True, report="--report" in sys.argv))

@@ -59,11 +59,11 @@ int launch_nt_pf(const NtArgs& a, int nsplit, hipStream_t st) {
 
 template <int KT, int MT, int NW, int KS, bool FAST, int MODE, typename TX>
 int launch_nt_inst(const NtArgs& a, int nsplit, hipStream_t st) {
-    // PF code (switch DNMF_NT_PF for A/B runs) -- what the interior tiles of the streamed operand do:
+    // PF code -- what the interior tiles of the streamed operand do:
     //   1  loads of k-tile t+1 issued at the top of tile t, tiles in order (also the generic / edge path)
-    //   5  1 + every workgroup starts at a different k-tile (rotated order) + nontemporal loads of A
-    //   7  5 with LDS-DMA staging (global_load_lds: no staging VGPRs, no ds_write)
-    //  10  5 with TWO k-tiles in flight and a branch-free loop (nt_mainloop_p2) -- the default; grids of at most one
+    //   5  1 + every workgroup starts at a different k-tile (rotated order) + nontemporal loads of A (bf16 X)
+    //   7  5 with LDS-DMA staging (global_load_lds: no staging VGPRs, no ds_write) -- measured, not kept
+    //  10  5 with TWO k-tiles in flight and a branch-free loop (nt_mainloop_p2) -- fp32 X; grids of at most one
     //      workgroup per CU take three tiles in flight (nt_mainloop_p3t, code 13)
     // Measured on MI355X (tools/kbench.py, k = 64, n = 8192; ms at 262144 / 65536 / 32768 rows):
     //   1: 2.54 / 0.82 / -     5: 2.42-2.49 / 0.76 / 0.44     7: +-2 % of 5     10: 2.43-2.47 / 0.76 / 0.40
@@ -81,22 +81,15 @@ int launch_nt_inst(const NtArgs& a, int nsplit, hipStream_t st) {
     // kernel reaches 103 / 118 / 128 TFLOP/s at 32768 / 65536 / 262144 rows against 82-89 / 91 / 113 from HBM -- with
     // IDENTICAL cycle counts (PMC): the difference is the core clock the chip holds (1.8-2.0 GHz with the HBM stream,
     // 2.2-2.4 GHz without), i.e. power, not the instruction schedule (measured ceilings).
-    static const int pf = (int)tune("DNMF_NT_PF", 10);
     if constexpr (FAST && KS == 1) if (MODE == NT_FUSED_W || !a.store_all) {
-#ifdef DNMF_TUNING      // the A/B variants are only instantiated in the tuning build
-        if (pf == 5) return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 5, TX>(a, nsplit, st);
-        if constexpr (std::is_same<TX, float>::value)
-            if (pf == 7) return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 7, TX>(a, nsplit, st);
-#endif
         if constexpr (std::is_same<TX, float>::value) {
             // 13 = 10 with three tiles in flight: chosen when the grid has at most one workgroup per CU (a 32768-row
             // shard = the per-GPU work of the 8-GPU configuration), where a single wave per SIMD has to cover the HBM latency
             constexpr int BM = 32 * MT * (NW / KS);
-            if (pf == 13 || (pf == 10 && cdiv(a.nrows, BM) * nsplit <= 256))
-                return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 13, TX>(a, nsplit, st);
-            if (pf == 10) return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 10, TX>(a, nsplit, st);
+            if (cdiv(a.nrows, BM) * nsplit <= 256) return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 13, TX>(a, nsplit, st);
+            return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 10, TX>(a, nsplit, st);
         } else {
-            if (pf == 10) return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 5, TX>(a, nsplit, st);   // bf16 X: one 64-wide tile in flight
+            return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 5, TX>(a, nsplit, st);   // bf16 X: one 64-wide tile in flight
         }
     }
     return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 1, TX>(a, nsplit, st);
@@ -110,14 +103,8 @@ int launch_nt(int kt, bool fast, const NtArgs& a, int nsplit, hipStream_t st) {
     return fast ? launch_nt_inst<KT_, MT_, NW_, KS_, true, MODE, TX>(a, nsplit, st)                \
                 : launch_nt_inst<KT_, MT_, NW_, KS_, false, MODE, TX>(a, nsplit, st);
     // 128-row tiles for every rank.  (k <= 32 used 256-row tiles, MT = 2, in an earlier version: equal at 262144 rows,
-    // 1.8x slower at 32768 rows where it left half the CUs without a workgroup.)
-#ifdef DNMF_TUNING
-    if (kt == 2 && tune("DNMF_NT_MT", 1) == 2) { NT_CASE(2, 2, 4, 1) }     // 256-row tiles at k = 64 (A/B runs)
-    // 32-row workgroups (4 waves = 4 contraction slices of one row group): fills the GPU on an 8192-row slab, for the
-    // slab-wise one-pass experiment of tools/onepass.py
-    if constexpr (std::is_same<TX, float>::value)
-        if (kt == 1 && tune("DNMF_NT_KS4", 0) != 0) { NT_CASE(1, 1, 4, 4) }
-#endif
+    // 1.8x slower at 32768 rows where it left half the CUs without a workgroup.  256-row tiles at k = 64, and 32-row
+    // workgroups for the slab-wise one-pass experiment of round 2, were measured and not kept: docs/history/DESIGN_r01-r05.md.)
     if (kt == 1) { NT_CASE(1, 1, 4, 1) }
     if (kt == 2) { NT_CASE(2, 1, 4, 1) }
     if (kt == 4) { NT_CASE(4, 1, 4, 1) }
@@ -132,12 +119,10 @@ int launch_tn(int kt, bool fast, const TnArgs& a, hipStream_t st) {
     const long waves = (long)a.nchunks * a.ncolblk;
     const dim3 grid((unsigned)cdiv(waves, 4)), block(256);
     // nontemporal loads of the streamed operand (A): +2 % at 262144 rows, +7 % at 65536 rows, slightly less HBM
-    // traffic (the reused W rows stay in L2).  DNMF_TN_NT=0 switches them off for A/B runs.
-    static const bool nty = tune("DNMF_TN_NT", 1) != 0;
+    // traffic (the reused W rows stay in L2).
 #define TN_CASE(KT_, NT_)                                                                                \
     if (kt == KT_) {                                                                                     \
-        if (fast && nty) DNMF_LAUNCH((tn_kernel<KT_, NT_, true, MODE, true, TY>), grid, block, 0, st, a); \
-        else if (fast) DNMF_LAUNCH((tn_kernel<KT_, NT_, true, MODE, false, TY>), grid, block, 0, st, a);  \
+        if (fast) DNMF_LAUNCH((tn_kernel<KT_, NT_, true, MODE, true, TY>), grid, block, 0, st, a);       \
         else DNMF_LAUNCH((tn_kernel<KT_, NT_, false, MODE, false, TY>), grid, block, 0, st, a);          \
         return check_launch("tn_kernel");                                                                \
     }
@@ -178,9 +163,8 @@ int launch_ew(float* X, long rows, long cols, long ldx, const float* Sm, long ld
         const dim3 grid((unsigned)cdiv(cvecs, 256 * U), (unsigned)rows);
         // a matrix that cannot stay in the caches until it is touched again (>= 256 MiB) is streamed with nontemporal
         // loads and stores: 5.5 -> 6.1 TB/s on the 1 GiB operands of the isolation pass; smaller factors (the W and H of a
-        // step are re-read by the next kernel) keep the default policy.  DNMF_EW_NT = 0 / 1 forces it in the tuning build.
-        const long ntp_dflt = (double)rows * cols * sizeof(float) >= 256.0 * (1 << 20);
-        if (vec && tune("DNMF_EW_NT", ntp_dflt)) {
+        // step are re-read by the next kernel) keep the default policy.
+        if (vec && (double)rows * cols * sizeof(float) >= 256.0 * (1 << 20)) {
             DNMF_LAUNCH((ew_kernel<OP, 4, true, true>), grid, dim3(256), 0, st, X, rows, cols, ldx, Sm, lds_, x, eps, clamp, 0);
             return check_launch(what);
         }
@@ -193,7 +177,7 @@ int launch_ew(float* X, long rows, long cols, long ldx, const float* Sm, long ld
     while (txs < 8 && (1L << txs) < cvecs) ++txs;
     const long TY = 256 >> txs;
     const dim3 grid((unsigned)cdiv(rows, TY * U));
-    if (vec && tune("DNMF_EW_NT", (double)rows * cols * sizeof(float) >= 256.0 * (1 << 20))) {
+    if (vec && (double)rows * cols * sizeof(float) >= 256.0 * (1 << 20)) {
         DNMF_LAUNCH((ew_kernel<OP, 4, false, true>), grid, dim3(256), 0, st, X, rows, cols, ldx, Sm, lds_, x, eps, clamp, txs);
         return check_launch(what);
     }
@@ -402,7 +386,7 @@ namespace {
 template <int MODE, typename TA>
 int try_nt16(const NtArgs& a, bool fast, long n, int k, hipStream_t st) {
     constexpr bool b16 = std::is_same<TA, bf16_t>::value;
-    if (!(k <= 16 && fast && k16_on() && n % (b16 ? BKH : BK) == 0)) return 1;
+    if (!(k <= 16 && fast && n % (b16 ? BKH : BK) == 0)) return 1;
     DNMF_LAUNCH((nt16_kernel<TA, MODE>), dim3((unsigned)cdiv(a.nrows, 128)), dim3(256), nt16_lds_bytes(b16), st, a);
     return check_launch("nt16_kernel");
 }
@@ -439,7 +423,7 @@ int aht_update_w_impl(const TA* A, long m, long n, long lda, const float* H, int
                       float* W, long ldw, float eps, void* stream) {
     REQUIRE(!wide_k(k), "aht_update_w: the fused form takes k <= %d (dnmf_aht followed by dnmf_mu_update_w beyond it)", DNMF_TUNED_MAX_K);
     const int kt = kt_of(k);
-    REQUIRE(kt > 0 && A && H && G && W && m >= 1 && n >= 1 && (lda >= n || alias_ok(lda)) && ldh >= n && ldw >= k, "aht_update_w: bad arguments");
+    REQUIRE(kt > 0 && A && H && G && W && m >= 1 && n >= 1 && lda >= n && ldh >= n && ldw >= k, "aht_update_w: bad arguments");
     NtArgs a{};
     a.X = A; a.ldx = lda; a.nrows = m; a.ncols = n;
     a.Y = H; a.ldy = ldh; a.yrows = k;
@@ -507,19 +491,18 @@ int dnmf_mu_update_w(float* W, long m, int k, long ldw, const float* AH, long ld
     const bool fast = aligned16(W) && aligned16(AH) && ldw % 4 == 0 && ldah % 4 == 0 && k % 4 == 0;
     hipStream_t st = S(stream);
     {   // 16-row wave tiles (update_w16_kernel; round 5): full ranks, whole tiles, aligned rows, 2 GiB descriptor windows.  Measured on
-        // the isolation pass (k x 2^22, tools/dbg/w16_ab.sh): k = 32: 0.346 -> 0.310 ms (0.58 -> 0.65 of HBM), k = 64: 0.759 -> 0.632
+        // the isolation pass (k x 2^22): k = 32: 0.346 -> 0.310 ms (0.58 -> 0.65 of HBM), k = 64: 0.759 -> 0.632
         // (0.53 -> 0.64), k = 128: 1.49 -> 1.40 (0.54 -> 0.58: the matrix work of 2 n k^2 flops bounds that one).  Workgroups walk
         // their tiles grid-stride; capped at 1024 workgroups from k = 64 on (G staged once per several tiles: 0.648 -> 0.632 at
-        // k = 64), one tile per wave at k = 32.  DNMF_UPD_W16 = 0 (tuning build): the 32-row kernel; > 1: that cap.
-        static const long w16 = tune("DNMF_UPD_W16", 1);
-        if (w16 && fast && k == 32 * kt && m % 16 == 0 && 16 * ldw * 4 + k * 4 < 0x7fffffffL && 16 * ldah * 4 + k * 4 < 0x7fffffffL) {
+        // k = 64), one tile per wave at k = 32.
+        if (fast && k == 32 * kt && m % 16 == 0 && 16 * ldw * 4 + k * 4 < 0x7fffffffL && 16 * ldah * 4 + k * 4 < 0x7fffffffL) {
             const long tiles = m / 16;
             auto run = [&](auto kt_c, auto nwv_c, auto occ_c) {
                 constexpr int KT_ = decltype(kt_c)::value, NWV_ = decltype(nwv_c)::value, OCC_ = decltype(occ_c)::value;
                 constexpr size_t lds = (size_t)(32 * KT_) * (32 * KT_ + 4) * sizeof(float);
                 static bool once = false;
                 if (!once) { allow_lds(update_w16_kernel<KT_, NWV_, OCC_>, lds); once = true; }
-                const long cap = w16 > 1 ? w16 : (KT_ == 1 ? (1L << 30) : 1024L);
+                const long cap = KT_ == 1 ? (1L << 30) : 1024L;
                 const unsigned grid = (unsigned)std::min<long>(cdiv(tiles, NWV_), cap);
                 DNMF_LAUNCH((update_w16_kernel<KT_, NWV_, OCC_>), dim3(grid), dim3(64 * NWV_), lds, st, W, m, ldw, AH, ldah, G, eps);
                 return check_launch("mu_update_w(16)");
@@ -532,25 +515,9 @@ int dnmf_mu_update_w(float* W, long m, int k, long ldw, const float* AH, long ld
     }
     // waves per SIMD requested from the compiler (3.2 GB pass, k = 64: 3 / 4 / 5 / 6 -> 4.68 / 4.72 / 4.76 / 4.67 TB/s;
     // k = 128 holds 120 registers: 4)
-    static const int var0 = (int)tune("DNMF_UPD_W", 0);
-    const int var = var0 ? var0 : (kt == 4 ? 4 : 5);
-#define UWS(KT_, OCC_)                                                                                            \
-    if (kt == KT_ && var == OCC_)                                                                                 \
-        return fast ? launch_update_w_seq<KT_, 4, OCC_>(W, m, k, ldw, AH, ldah, G, eps, st)                       \
-                    : launch_update_w_seq<KT_, 1, OCC_>(W, m, k, ldw, AH, ldah, G, eps, st);
-    UWS(1, 5) UWS(2, 5) UWS(4, 4)
-#ifdef DNMF_TUNING
-    if (var == 35 && kt == 2 && fast && k == 64 && m % 32 == 0) {      // nontemporal loads and stores (A/B)
-        constexpr size_t lds = 64 * 68 * sizeof(float);
-        static bool once = false;
-        if (!once) { allow_lds(update_w_seq_kernel<2, 4, 5, false, UW_MU, 2>, lds); once = true; }
-        DNMF_LAUNCH((update_w_seq_kernel<2, 4, 5, false, UW_MU, 2>), dim3((unsigned)cdiv(cdiv(m, 32), 4)), dim3(256), lds, st, W, m, k, ldw, AH, ldah, G, eps, (float*)nullptr, 0L);
-        return check_launch("mu_update_w(nt)");
-    }
-    UWS(1, 3) UWS(2, 3) UWS(4, 3) UWS(1, 4) UWS(2, 4) UWS(4, 5) UWS(1, 6) UWS(2, 6) UWS(1, 8) UWS(2, 2) UWS(4, 2)
-#endif
-#undef UWS
-    return fail(DNMF_EINVAL, "mu_update_w: no kernel for k tile %d / variant %d", kt, var);
+    if (kt == 1) return fast ? launch_update_w_seq<1, 4, 5>(W, m, k, ldw, AH, ldah, G, eps, st) : launch_update_w_seq<1, 1, 5>(W, m, k, ldw, AH, ldah, G, eps, st);
+    if (kt == 2) return fast ? launch_update_w_seq<2, 4, 5>(W, m, k, ldw, AH, ldah, G, eps, st) : launch_update_w_seq<2, 1, 5>(W, m, k, ldw, AH, ldah, G, eps, st);
+    return fast ? launch_update_w_seq<4, 4, 4>(W, m, k, ldw, AH, ldah, G, eps, st) : launch_update_w_seq<4, 1, 4>(W, m, k, ldw, AH, ldah, G, eps, st);
 }
 
 }  // extern "C"
@@ -567,13 +534,12 @@ int wta_impl(const TA* A, long m, long n, long lda, const float* W, int k, long 
         return wta_impl<TA>(A, m, n, lda, W + WIDE_PANEL, k - WIDE_PANEL, ldw, AtW + (long)WIDE_PANEL * ldatw, ldatw, ws, ws_bytes, stream, nullptr);
     }
     const int kt = kt_of(k);
-    REQUIRE(kt > 0 && A && W && AtW && ws && m >= 1 && n >= 1 && (lda >= n || alias_ok(lda)) && ldw >= k && ldatw >= n, "wta: bad arguments");
+    REQUIRE(kt > 0 && A && W && AtW && ws && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldatw >= n, "wta: bad arguments");
     const int kp = 32 * kt;
-    static const bool gram_ride = tune("DNMF_WTA_GRAM", 1) != 0;
     auto gram_first = [&]() { return G ? dnmf_gram_wtw(W, m, k, ldw, G, ws, ws_bytes, stream) : DNMF_OK; };
     {   // rank k <= 16: 16-wide kernel (16-byte aligned rows of A, whole column blocks, workspace permitting)
         constexpr int V = std::is_same<TA, bf16_t>::value ? 8 : 4;
-        if (k <= 16 && k16_on() && a_rows16(A, lda) && n % (16 * V) == 0 && lda != 0) {
+        if (k <= 16 && a_rows16(A, lda) && n % (16 * V) == 0) {
             const Tn16Plan q = plan_tn16(m, n, V);
             const size_t pb = (size_t)q.nchunks * 16 * n * sizeof(float);
             if (pb + reduce_scratch_bytes(q.nchunks, k, n) <= ws_bytes) {
@@ -582,7 +548,7 @@ int wta_impl(const TA* A, long m, long n, long lda, const float* W, int k, long 
                 a.nrows = m; a.rows_per_chunk = q.rows_per_chunk; a.nchunks = q.nchunks; a.ncolblk = q.ncolblk;
                 a.P = (float*)ws; a.chunk_stride = 16 * n; a.ldp = n;
                 const size_t gb = (size_t)q.nchunks * 256 * sizeof(float);            // partial Gram tiles behind the slabs
-                const bool ride = G && gram_ride && reduce_slices(q.nchunks) == 1 && pb + gb <= ws_bytes;
+                const bool ride = G && reduce_slices(q.nchunks) == 1 && pb + gb <= ws_bytes;
                 int rc;
                 if (!ride && (rc = gram_first())) return rc;
                 hipStream_t st = S(stream);
@@ -659,8 +625,8 @@ int launch_update_h_seq(float* H, int k, long n, long ldh, const float* AtW, lon
         // and loses a factor of two with the same hint, so it keeps the default policy)
         if (k == 32 * KT && n % (32 * NT) == 0 && (double)k * n * sizeof(float) >= 64.0 * (1 << 20)) {
             static bool once2 = false;
-            if (!once2) { allow_lds(update_h_seq_kernel<KT, NT, OCC, false, true, 2, 2>, lds); once2 = true; }
-            DNMF_LAUNCH((update_h_seq_kernel<KT, NT, OCC, false, true, 2, 2>), dim3(grid), dim3(T), lds, st, H, k, n, ldh, AtW, ldatw, G, eps, clamp);
+            if (!once2) { allow_lds(update_h_seq_kernel<KT, NT, OCC, false, 2, 2>, lds); once2 = true; }
+            DNMF_LAUNCH((update_h_seq_kernel<KT, NT, OCC, false, 2, 2>), dim3(grid), dim3(T), lds, st, H, k, n, ldh, AtW, ldatw, G, eps, clamp);
             return check_launch("mu_update_h");
         }
     }
@@ -689,36 +655,17 @@ int dnmf_mu_update_h(float* H, int k, long n, long ldh, const float* AtW, long l
     // (k x 2^22): k = 64: 14 / 16 -> 4.76 / 4.78 TB/s, 23 -> 4.97, 24 (spills) -> 4.0; k = 32: 14 -> 4.93, 23 -> 5.26;
     // k = 128: 14 -> 3.44, 23 -> 2.58.  Two columns per lane (256 B per row and wave) stream better but need 8-byte
     // aligned rows, and a short H (fewer than 1024 such tiles: a latency chain on a few CUs) keeps 32-column tiles.
-    static const int var0 = (int)tune("DNMF_UPD_H", 0);
     // k = 128 (round 4): LDS holds two workgroups per CU there whatever the registers allow (66 KiB of G each), so the two-column
     // tile at TWO waves per SIMD (200 registers, no spills) costs no occupancy and halves the accesses per byte: 4.25 -> 4.5 TB/s on
     // the 6.4 GB pass (variant 23 spills there: 2.4 TB/s)
-    int var = var0 ? var0 : ((even && k == 32 * kt && n % 64 == 0 && n / 64 >= 1024) ? (kt == 4 ? 22 : 23) : 14);
-    if (var >= 20 && !even) var = 14;
-#define UHS(KT_, NT_, OCC_)                                                                                       \
-    if (kt == KT_ && var == 10 * NT_ + OCC_)                                                                      \
-        return launch_update_h_seq<KT_, NT_, OCC_>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
-    UHS(1, 1, 4) UHS(2, 1, 4) UHS(4, 1, 4) UHS(1, 2, 3) UHS(2, 2, 3) UHS(4, 2, 2)
-#ifdef DNMF_TUNING
-    if (var >= 91 && var <= 93 && kt == 2 && k == 64 && n % 64 == 0 && even) {   // cache-policy variants of the k = 64, NT = 2 kernel
-        constexpr size_t lds = 64 * 68 * sizeof(float);
-        const unsigned grid = (unsigned)cdiv(cdiv(n, 64), 4);
-        if (var == 91) DNMF_LAUNCH((update_h_seq_kernel<2, 2, 3, false, true, 2, 0>), dim3(grid), dim3(256), lds, st, H, k, n, ldh, AtW, ldatw, G, eps, clamp);
-        if (var == 92) DNMF_LAUNCH((update_h_seq_kernel<2, 2, 3, false, true, 0, 2>), dim3(grid), dim3(256), lds, st, H, k, n, ldh, AtW, ldatw, G, eps, clamp);
-        if (var == 93) DNMF_LAUNCH((update_h_seq_kernel<2, 2, 3, false, true, 2, 2>), dim3(grid), dim3(256), lds, st, H, k, n, ldh, AtW, ldatw, G, eps, clamp);
-        return check_launch("mu_update_h(aux)");
+    if (even && k == 32 * kt && n % 64 == 0 && n / 64 >= 1024) {
+        if (kt == 1) return launch_update_h_seq<1, 2, 3>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
+        if (kt == 2) return launch_update_h_seq<2, 2, 3>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
+        return launch_update_h_seq<4, 2, 2>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
     }
-    if (var == 99 && kt == 2 && k == 64 && n % 32 == 0) {   // memory pattern of the k = 64 kernel without its matrix work
-        constexpr size_t lds = 64 * 68 * sizeof(float);
-        const unsigned grid = (unsigned)std::min<long>(cdiv(cdiv(n, 32), 4), tune("DNMF_UPD_GRID", 1024L));
-        DNMF_LAUNCH((update_h_seq_kernel<2, 1, 4, false, false>), dim3(grid), dim3(256), lds, st, H, k, n, ldh, AtW, ldatw, G, eps, clamp);
-        return check_launch("mu_update_h(nomma)");
-    }
-    UHS(1, 1, 5) UHS(2, 1, 5) UHS(1, 1, 6) UHS(2, 1, 6) UHS(1, 1, 8) UHS(4, 1, 3) UHS(4, 1, 5)
-    UHS(1, 2, 4) UHS(2, 2, 4) UHS(4, 2, 3) UHS(1, 2, 5) UHS(1, 2, 6)
-#endif
-#undef UHS
-    return fail(DNMF_EINVAL, "mu_update_h: no kernel for k tile %d / variant %d", kt, var);
+    if (kt == 1) return launch_update_h_seq<1, 1, 4>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
+    if (kt == 2) return launch_update_h_seq<2, 1, 4>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
+    return launch_update_h_seq<4, 1, 4>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
 }
 
 int dnmf_clamp_min(float* X, long rows, long cols, long ldx, float eps, void* stream) {

@@ -118,14 +118,6 @@ int check_launch(const char* what) {
     return DNMF_OK;
 }
 
-// Experiment switches exist only in the tuning build (-DDNMF_TUNING -> tools/_build/libdnmf_hip_tune.so, tools/README.md);
-// the shipped library has the defaults compiled in and never reads the environment.
-#ifdef DNMF_TUNING
-inline long tune(const char* name, long dflt) { const char* v = getenv(name); return v ? atol(v) : dflt; }
-#else
-constexpr long tune(const char*, long dflt) { return dflt; }
-#endif
-
 // host twins of `rebase`: problem z's copy of a pointer laid out for problem 0, and a memset of every problem's copy
 inline void* batch_ptr(const void* p, int z) {
     const BatchCtx* bc = dnmf_batch_();

@@ -576,9 +576,7 @@ TnPlan64 plan_tn64(long m, long n, int k) {
     return p;
 }
 long nt_splits(long m, long n) {
-    if (m <= 1024) return std::max<long>(1, std::min<long>(256, n / 512));
-    const long forced = tune("DNMF_F64_NT_SPLIT", 0);
-    return forced > 0 ? std::min<long>(forced, std::max<long>(1, n / 512)) : 1;
+    return m <= 1024 ? std::max<long>(1, std::min<long>(256, n / 512)) : 1;
 }
 
 int sum_all(bool sq, const double* X, long rows, long cols, long ldx, double* out, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -680,7 +678,6 @@ int dnmf_f64_aht(const double* X, long m, long n, long ldx, const double* Y, int
     const bool vec = n % 4 == 0;
     const int nt = tiles16(kc);
     int rt = (m >= 16 * 4 * 256 && nt <= 4) ? 4 : (m >= 16 * 2 * 256 ? 2 : 1);     // row tiles per wave: 16 accumulators at most
-    if (tune("DNMF_F64_NT_RT", 0)) rt = (int)tune("DNMF_F64_NT_RT", 0);
     while (rt > 1 && !buf_ok(ldx, 16 * rt)) rt >>= 1;
 // (three register sets in flight for k <= 16, where the kernel is a stream of A: 0.565 -> 0.509 ms at 65536 x 4096; two beyond)
 #define NT_LAUNCH(RT_, NT_, VEC_) hipLaunchKernelGGL((f64_nt_kernel<RT_, NT_, VEC_, (NT_ == 1 ? 3 : 2)>), dim3((unsigned)cdiv(cdiv(m, 16 * RT_), 4), (unsigned)nsplit), dim3(256), 0, st, \
@@ -754,14 +751,13 @@ int dnmf_f64_kl_quot(const double* A, long m, long n, long lda, const double* W,
 int dnmf_f64_kl_uht(const double* A, long m, long n, long lda, const double* W, long ldw, const double* H, long ldh, int k, double eps,
                     double* S, long lds_, double* U, void* ws, size_t ws_bytes, void* stream) {
     REQ(A && W && H && S && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K && lda >= n && ldw >= k && ldh >= n && lds_ >= k, "f64 kl_uht: bad arguments");
-    if (k > KL64_MAX_K || tune("DNMF_F64_KL_IMAGE", 0) || !kl64_buf_ok(lda, ldw, ldh, k)) {
+    if (k > KL64_MAX_K || !kl64_buf_ok(lda, ldw, ldh, k)) {
         REQ(U, "f64 kl_uht: k = %d > %d needs the m x n image U", k, KL64_MAX_K);
         int rc = dnmf_f64_kl_quot(A, m, n, lda, W, ldw, H, ldh, k, eps, U, n, stream);
         return rc ? rc : dnmf_f64_aht(U, m, n, n, H, k, ldh, S, lds_, ws, ws_bytes, stream);
     }
     hipStream_t st = ST(stream);
     KlUhtPlan p = plan_kl_uht(m, n, k);
-    if (tune("DNMF_F64_KL_RT", 0)) { p.rt = (int)tune("DNMF_F64_KL_RT", 0); }
     const int kp = 16 * tiles16(k);
     double* out = S; long ldo = lds_, sstride = 0;
     if (p.nsplit > 1) {
@@ -790,7 +786,7 @@ int dnmf_f64_kl_uht(const double* A, long m, long n, long lda, const double* W, 
 int dnmf_f64_kl_wtu(const double* A, long m, long n, long lda, const double* W, long ldw, const double* H, long ldh, int k, double eps,
                     double* S, long lds_, double* U, void* ws, size_t ws_bytes, void* stream) {
     REQ(A && W && H && S && ws && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K && lda >= n && ldw >= k && ldh >= n && lds_ >= n, "f64 kl_wtu: bad arguments");
-    if (k > KL64_MAX_K || tune("DNMF_F64_KL_IMAGE", 0) || !kl64_buf_ok(lda, ldw, ldh, k)) {
+    if (k > KL64_MAX_K || !kl64_buf_ok(lda, ldw, ldh, k)) {
         REQ(U, "f64 kl_wtu: k = %d > %d needs the m x n image U", k, KL64_MAX_K);
         int rc = dnmf_f64_kl_quot(A, m, n, lda, W, ldw, H, ldh, k, eps, U, n, stream);
         return rc ? rc : dnmf_f64_wta(U, m, n, n, W, k, ldw, S, lds_, ws, ws_bytes, stream);
@@ -901,8 +897,7 @@ int dnmf_f64_fit(int method, const double* A, long m, long n, long lda, double* 
             ldw >= k && ldh >= n, "f64 fit: bad arguments");
     const size_t need = dnmf_f64_ws_bytes_fit(m, n, k);
     if (ws_bytes < need) return fail(DNMF_EWS, "f64 fit: workspace %zu < %zu", ws_bytes, need);
-    static const bool tiny_on = tune("DNMF_F64_TINY", 1) != 0;     // (tuning build: 0 = the chain of primitives, for the before / after timing)
-    if (itr >= 1 && tiny_on) {      // tiny problems (the reference's own test sizes): the whole fit as ONE single-workgroup launch (csrc/dnmf_f64_tiny.hip)
+    if (itr >= 1) {      // tiny problems (the reference's own test sizes): the whole fit as ONE single-workgroup launch (csrc/dnmf_f64_tiny.hip)
         const int rc_tiny = dnmf_f64_tiny_fit_(method, A, m, n, lda, 0, W, ldw, 0, H, ldh, 0, k, eps, w_update, itr, 1, sq_out, 2, stream);
         if (rc_tiny != 1) return rc_tiny;
     }

@@ -22,7 +22,7 @@ inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 struct SmallPlan { int kp, nw, P; bool alds; long ns; size_t lds, part_floats, bytes; bool ok; };
 SmallPlan small_kl_plan(long m, long n, int k) {
     SmallPlan s{};
-    if (k < 1 || k > 32 || n > 4096 || tune("DNMF_SMALL_FIT", 1) == 0) return s;
+    if (k < 1 || k > 32 || n > 4096) return s;
     s.kp = k <= 16 ? 16 : 32;
     s.ns = round_up(n, 16);
     // geometry by shape alone (a batched fit must equal single fits bit for bit): 128-row slabs with A in LDS when that fits; else 96-row
@@ -30,8 +30,7 @@ SmallPlan small_kl_plan(long m, long n, int k) {
     // of the 256 CUs where 8 slabs covered 160); else 128-row slabs with A streamed from the L2 (H and the slab's W in LDS); else 64-row
     // slabs with A in LDS, or streamed (short, wide problems)
     struct Try { int nw; bool alds; };
-    Try tries[5] = {{8, true}, {6, true}, {8, false}, {4, true}, {4, false}};
-    if (tune("DNMF_SMALL_NW6", 0)) std::swap(tries[0], tries[1]);      // (tuning build: 96-row slabs first)
+    const Try tries[5] = {{8, true}, {6, true}, {8, false}, {4, true}, {4, false}};
     for (const auto& t : tries) {
         const size_t lds = small_kl_lds(s.kp, t.nw, n, t.alds);
         const long P = cdiv(m, 16L * t.nw);
@@ -50,7 +49,7 @@ SmallPlan small_kl_plan(long m, long n, int k) {
 struct HalsPlan { int kp, nw, P, cw; long ns; size_t lds, lds_bf16_resident, part_floats, slot_words, bytes; bool ok; };
 HalsPlan small_hals_plan(long m, long n, int k) {
     HalsPlan s{};
-    if (k < 1 || k > 32 || n > 4096 || tune("DNMF_SMALL_FIT", 1) == 0) return s;
+    if (k < 1 || k > 32 || n > 4096) return s;
     s.kp = k <= 16 ? 16 : 32;
     s.ns = round_up(n, 16);
     for (int nw : {8, 4}) {
@@ -77,7 +76,7 @@ HalsPlan small_hals_plan(long m, long n, int k) {
 struct FroBfPlan { int kp, nw, P; bool alds; long ns; size_t lds, part_floats, bytes; bool ok; };
 FroBfPlan small_fro_bf16_plan(long m, long n, int k) {
     FroBfPlan s{};
-    if (k < 1 || k > 32 || n > 4096 || tune("DNMF_SMALL_FIT", 1) == 0) return s;
+    if (k < 1 || k > 32 || n > 4096) return s;
     s.kp = k <= 16 ? 16 : 32;
     s.ns = round_up(n, 16);
     const struct { int nw; bool alds; } tries[4] = {{8, true}, {8, false}, {4, true}, {4, false}};
@@ -192,9 +191,6 @@ int small_fit(bool fro, const float* A, long m, long n, long lda, float* W, long
     a.part = (float*)(ws + f.small_off); a.part_stride = (long)(f.total / sizeof(float));
     a.bar = (unsigned*)(ws + f.small_off + sp.bytes - 256); a.bar_stride = (long)(f.total / sizeof(unsigned));
     a.hg = a.part + sp.part_floats; a.hg_stride = a.part_stride;                       // [kp][ns] granules {H element, step}: zeroed below
-#ifdef DNMF_TUNING
-    a.w_update |= (int)tune("DNMF_SMALL_ABL", 0) << 8;
-#endif
     a.patience = g_small_patience;                                     // ticks of the 100 MHz wall clock (2 s unless dnmf_fit_set_timeout)
     if (batch == 1) { a.a_stride = a.w_stride = a.h_stride = 0; }
     if (!fro && !w_update) {

@@ -244,7 +244,7 @@ __device__ __forceinline__ double hals_poll(const unsigned long long* col, int n
 template <int KP, int KK>
 __device__ __forceinline__ void hals_col_step(float (&t)[KP], float& u, int k, bool live, float eps, const float* gs,
                                               unsigned long long* __restrict__ slab, double* __restrict__ ss2_out,
-                                              double* red, int nwg, int dbg, const HalsPeers& pe) {
+                                              double* red, int nwg, const HalsPeers& pe) {
     asm volatile("" ::: "memory");
     if (KK >= k) return;                                  // uniform
     const double sq = live ? (double)u * (double)u : 0.0;
@@ -278,9 +278,7 @@ __device__ __forceinline__ void hals_col_step(float (&t)[KP], float& u, int k, b
     }
     // the first four waves of the workgroup fetch the slots of this column (wave w: slots 256 w .. 256 w + 255)
     double mine = 0.0;
-    if (dbg & 1) {                                         // tuning build only: no exchange (each workgroup on its own)
-        if (threadIdx.x == 0) mine = part;
-    } else if (threadIdx.x < 256) {
+    if (threadIdx.x < 256) {
         const int base = (threadIdx.x >> 6) * 256, cnt = nwg - base;
         if (cnt > 0) {
             const unsigned long long pat = pe.P ? pe.patience : 0ull;
@@ -303,8 +301,8 @@ __device__ __forceinline__ void hals_col_step(float (&t)[KP], float& u, int k, b
 template <int KP, int... Ks>
 __device__ __forceinline__ void hals_sweep_all(float (&t)[KP], float& u, int k, bool live, float eps, const float* gs,
                                                unsigned long long* __restrict__ slab, double* __restrict__ ss2_out,
-                                               double* red, int nwg, int dbg, const HalsPeers& pe, std::integer_sequence<int, Ks...>) {
-    (hals_col_step<KP, Ks>(t, u, k, live, eps, gs, slab, ss2_out, red, nwg, dbg, pe), ...);
+                                               double* red, int nwg, const HalsPeers& pe, std::integer_sequence<int, Ks...>) {
+    (hals_col_step<KP, Ks>(t, u, k, live, eps, gs, slab, ss2_out, red, nwg, pe), ...);
 }
 
 // waves per SIMD: what the row (KP registers) + the fp64 reductions + the slot polling hold; 8-wave workgroups, so the device keeps 4 / 4 / 2 x 256 CUs x 4 SIMDs x 64 rows = 262144 / 262144 / 131072 rows
@@ -312,7 +310,7 @@ __device__ __forceinline__ void hals_sweep_all(float (&t)[KP], float& u, int k, 
 template <int KP, bool VEC>
 __global__ __launch_bounds__(HALS_WG, KP <= 64 ? 4 : 2) void hals_w_sweep_kernel(
     float* __restrict__ W, long m, int k, long ldw, const float* __restrict__ T, long ldt, const float* __restrict__ G,
-    float eps, unsigned long long* __restrict__ slab, double* __restrict__ ss2_out, int dbg, HalsPeers pe, BatchTab bt) {
+    float eps, unsigned long long* __restrict__ slab, double* __restrict__ ss2_out, HalsPeers pe, BatchTab bt) {
     REBASE(W); REBASE(T); REBASE(G); REBASE(slab); REBASE(ss2_out);
     __shared__ double red[HALS_WG / 64];
     // G (KP x KP, zero padded, symmetric) staged once per workgroup: every use is a row segment G[r][c0 .. c0+3] at a
@@ -341,7 +339,7 @@ __global__ __launch_bounds__(HALS_WG, KP <= 64 ? 4 : 2) void hals_w_sweep_kernel
     }
     // 2. the column sweep
     float u = fmaxf(t[0], eps);
-    hals_sweep_all<KP>(t, u, k, live, eps, gs, slab, ss2_out, red, nwg, dbg, pe, std::make_integer_sequence<int, KP>{});
+    hals_sweep_all<KP>(t, u, k, live, eps, gs, slab, ss2_out, red, nwg, pe, std::make_integer_sequence<int, KP>{});
     // 3. store the row
     if (live) {
         float* orow = W + i * ldw;

@@ -127,13 +127,12 @@ int launch_hals_sweep(float* W, long m, int k, long ldw, const float* AH, long l
         int rc = check_launch("hals_sweep_w(transform)");
         if (rc) return rc;
     }
-    static const int dbg = (int)tune("DNMF_HALS_DBG", 0);     // tuning build: 1 = no grid exchange (timing experiment, wrong norms)
     int rc_sweep = DNMF_OK;
     for (int z0 = 0; z0 < B && !rc_sweep; z0 += per) {
         bc->B = std::min(per, B - z0);
         bc->tab.z0 = z0;
-        if (vec) DNMF_LAUNCH((hals_w_sweep_kernel<KP, HASVEC>), dim3((unsigned)grid), dim3(HALS_WG), lds, st, W, m, k, ldw, (const float*)T, ldt, G, eps, slab, ss2, dbg, peers);
-        else DNMF_LAUNCH((hals_w_sweep_kernel<KP, false>), dim3((unsigned)grid), dim3(HALS_WG), lds, st, W, m, k, ldw, (const float*)T, ldt, G, eps, slab, ss2, dbg, peers);
+        if (vec) DNMF_LAUNCH((hals_w_sweep_kernel<KP, HASVEC>), dim3((unsigned)grid), dim3(HALS_WG), lds, st, W, m, k, ldw, (const float*)T, ldt, G, eps, slab, ss2, peers);
+        else DNMF_LAUNCH((hals_w_sweep_kernel<KP, false>), dim3((unsigned)grid), dim3(HALS_WG), lds, st, W, m, k, ldw, (const float*)T, ldt, G, eps, slab, ss2, peers);
         rc_sweep = check_launch("hals_sweep_w");
     }
     bc->B = B;
@@ -159,9 +158,8 @@ int dnmf_hals_sweep_w(float* W, long m, int k, long ldw, const float* AH, long l
     unsigned long long* slab = (unsigned long long*)ws;
     double* ss2 = (double*)((char*)ws + slab_bytes);
     float* T = (float*)((char*)ws + t_off);
-    static const int mode = (int)tune("DNMF_HALS_SWEEP", 1);     // 0: always the column-per-launch path (A/B runs)
     int rc = 1;
-    if (mode && kt > 0 && ws_bytes >= t_off + (size_t)m * kp * sizeof(float)) {
+    if (kt > 0 && ws_bytes >= t_off + (size_t)m * kp * sizeof(float)) {
         hipStream_t st = S(stream);
         if (kt == 1) rc = launch_hals_sweep<1>(W, m, k, ldw, AH, ldah, G, eps, slab, ss2, T, st);
         else if (kt == 2) rc = launch_hals_sweep<2>(W, m, k, ldw, AH, ldah, G, eps, slab, ss2, T, st);

@@ -16,10 +16,6 @@ inline bool wide_k(int k) { return k > DNMF_TUNED_MAX_K && k <= DNMF_MAX_K; }
 inline int kp_of(int k) { return wide_k(k) ? 256 : (kt_of(k) < 0 ? -1 : 32 * kt_of(k)); }
 constexpr int WIDE_PANEL = 128;          // the panels a wide rank is cut into
 
-// lda == 0 (every row of A aliases one row: A becomes cache resident) is an experiment of the tuning build only
-// (tools/kbench.py ALIAS=1); the shipped library requires lda >= n everywhere, as include/dnmf.h says
-inline bool alias_ok(long lda) { return lda == 0 && tune("DNMF_ALLOW_ALIAS", 0) != 0; }
-
 hipStream_t S(void* s) {
     clear_hip_error();
     return reinterpret_cast<hipStream_t>(s);
@@ -57,8 +53,7 @@ int launch_reduce(const float* P, long stride, long ldp, int nsplit, float* out,
     const GramTail gt = gram ? *gram : GramTail{nullptr, nullptr, 0, 0, 0, 0};
     const unsigned extra = gram ? (unsigned)gram_tail_blocks(gram->k) : 0u;
     if (gram && ny != 1) return fail(DNMF_EINVAL, "reduce: a Gram tail needs a single-stage reduction (%d partials)", nsplit);
-    static const bool wide = tune("DNMF_REDUCE_WIDE", 1) != 0;
-    if (wide && ny == 1 && rows == rows_out && cols == cols_out && cols % 4 == 0 && cols >= 4096 && ldo % 4 == 0 &&
+    if (ny == 1 && rows == rows_out && cols == cols_out && cols % 4 == 0 && cols >= 4096 && ldo % 4 == 0 &&
         aligned16(out) && aligned16(P) && ldp % 4 == 0 && stride % 4 == 0) {
         DNMF_LAUNCH(reduce_partials_wide_kernel, dim3((unsigned)cdiv(total, 256) + extra), dim3(256), 0, st, P, stride, ldp,
                            nsplit, out, ldo, rows, cols, gt);
@@ -84,8 +79,7 @@ struct TnPlan { int ncolblk; int nchunks; long rows_per_chunk; long ldp; long ch
 TnPlan plan_tn(long nrows, long ycols, int kt, int nt, long min_rows = 256, long waves = 0) {
     TnPlan p;
     p.ncolblk = (int)cdiv(ycols, 32 * nt);
-    static const long forced = tune("DNMF_TN_WAVES", 0);           // (experiments of the tuning build)
-    const long target_waves = forced ? forced : waves ? waves : 2048;   // default: one resident round, 256 CUs x 2 waves/SIMD
+    const long target_waves = waves ? waves : 2048;   // default: one resident round, 256 CUs x 2 waves/SIMD
     long nchunks = std::max<long>(1, target_waves / p.ncolblk);
     nchunks = std::min<long>(nchunks, std::max<long>(1, cdiv(nrows, min_rows)));
     p.rows_per_chunk = round_up(cdiv(nrows, nchunks), 16);
@@ -103,11 +97,6 @@ inline long wta_waves(long m, long n, int kt, size_t elt) {
     return (kt == 1 && elt == 4 && (double)m * (double)n < (double)(1L << 30)) ? 1024 : 0;
 }
 
-// k <= 16 kernels (dnmf_k16.h): DNMF_K16=0 switches them off (A/B runs)
-inline bool k16_on() {
-    static const bool on = tune("DNMF_K16", 1) != 0;
-    return on;
-}
 // row chunking of tn16_kernel: waves = nchunks x (n / (16 V)), 16-row partial slabs of ld = n
 struct Tn16Plan { int ncolblk; int nchunks; long rows_per_chunk; };
 Tn16Plan plan_tn16(long m, long n, int v) {
@@ -115,8 +104,7 @@ Tn16Plan plan_tn16(long m, long n, int v) {
     p.ncolblk = (int)(n / (16 * v));
     // 2 waves per SIMD.  (4 until round 3: 0.195 -> 0.170 ms at 65536 x 4096, 0.343 -> 0.324 at 32768 x 16384, 1.307 -> 1.285 at
     // 262144 x 8192, k = 16 -- half the partial slabs to write and reduce, and the HBM stream does not need the waves.)
-    static const long target = tune("DNMF_TN16_WAVES", 2048);
-    long nchunks = std::max<long>(1, target / std::max(1, p.ncolblk));
+    long nchunks = std::max<long>(1, 2048 / std::max(1, p.ncolblk));
     nchunks = std::min<long>(nchunks, std::max<long>(1, cdiv(m, 256)));
     p.rows_per_chunk = round_up(cdiv(m, nchunks), 16);
     p.nchunks = (int)cdiv(m, p.rows_per_chunk);
@@ -141,10 +129,7 @@ Tn16Plan plan_wtu16(long m, long n) {
 
 inline int tn_nt(int kt) { return kt == 4 ? 2 : 4; }  // column sets per wave in TN form
 
-inline int kl_nt(int kt) {   // column sets per wave in kl_wtu (three live tiles: out, S/U, A)
-    static const int nt1 = (int)tune("DNMF_WTU_NT1", 4);
-    return kt == 1 ? nt1 : 2;
-}
+inline int kl_nt(int kt) { return kt == 1 ? 4 : 2; }   // column sets per wave in kl_wtu (three live tiles: out, S/U, A)
 
 // Row chunking of kl_wtu_kernel: plan_tn's round of waves, with the chunk capped so that ONE 2 GiB buffer descriptor covers a
 // chunk's rows of A (the pipelined path of the kernel addresses a chunk through MUBUF; a chunk beyond the window fell back to
@@ -205,7 +190,7 @@ __global__ __launch_bounds__(256) void pad_factors_kernel(const float* __restric
 bool pad_factors(const float*& W, long& ldw, const float*& H, long& ldh, int& k, long m, long n, int kp, void* ws,
                         size_t ws_bytes, size_t own_need, hipStream_t st) {
     const bool friendly = k == kp && aligned16(W) && ldw % 4 == 0 && aligned16(H) && ldh % 4 == 0;
-    if (friendly || tune("DNMF_KL_PAD", 1) == 0) return false;
+    if (friendly) return false;
     const size_t pb = pad_bytes(m, n, kp);
     if (!ws || ws_bytes < align256(own_need) + pb) return false;
     char* base = (char*)ws + align256(own_need);

@@ -53,8 +53,6 @@ static NnArgs nn_args(const float* A, long m, long n, long lda, const float* W, 
     a.A = A; a.lda = lda; a.m = m; a.n = n; a.W = W; a.ldw = ldw; a.H = H; a.ldh = ldh; a.k = k; a.eps = eps;
     a.nrowblk = cdiv(m, 32); a.ncolblk = (int)cdiv(n, 128);
     a.kreal = k;
-    static const int kl_pipe = (int)tune("DNMF_KL_PIPE", 1);
-    a.pipe = kl_pipe;
     return a;
 }
 
@@ -89,8 +87,7 @@ int resid_sqnorm_impl(const TA* A, long m, long n, long lda, const float* W, lon
     hipStream_t stq = st;
     // H staged through LDS, waves walking row chunks (resid_lds_kernel) when the block is big enough to give every wave a
     // chunk of several row blocks; small blocks keep one tile per wave (resid_kernel)
-    static const int lds_on = (int)tune("DNMF_RESID_LDS", 1);
-    if (lds_on && fast && k % 32 == 0 && n >= 128 && m >= 4096) {
+    if (fast && k % 32 == 0 && n >= 128 && m >= 4096) {
         const int nt = 4;
         TnPlan pl = plan_tn(m, n, kt, nt);
         {                                                          // one wave per SIMD (1024 waves): half of plan_tn's round
@@ -251,10 +248,9 @@ int kl_uht_impl(const float* A, long m, long n, long lda, const float* W, long l
     // Whole 128-row tiles of a friendly problem (aligned rows, k = KP or padded to it, whole 32-column tiles, 2 GiB descriptor
     // windows) go to the software-pipelined kernel; a ragged last row tile -- or everything else -- to kl_uht_kernel.  Same
     // arithmetic in the same order: the two are bit identical.
-    static const int pipe_on = (int)tune("DNMF_KLUHT_PIPE", 1);
     auto window = [](long rows, long ld, long cols) { return (rows * ld + cols) * 4 < 0x7fffffffL; };
     long rowtile0 = 0;
-    if (pipe_on && fast && k == kp && m >= 128 && n % BK == 0 && u.cols_per_split % BK == 0 && out_cols >= kp &&
+    if (fast && k == kp && m >= 128 && n % BK == 0 && u.cols_per_split % BK == 0 && out_cols >= kp &&
         window(128, lda, u.cols_per_split) && window(kp, ldh, u.cols_per_split)) {
         rowtile0 = m / 128;
         if (int rcp = dnmf_kl_uht_pipe_(A, rowtile0, n, lda, W, ldw, H, ldh, hblk, a.hextra, kt, eps, out, ldout, (long)m * kp,
@@ -338,16 +334,7 @@ int dnmf_kl_wtu(const float* A, long m, long n, long lda, const float* W, long l
         if (fast) DNMF_LAUNCH((kl_wtu_kernel<KT_, NT_, true>), grid, block, lds, st, a, rowblks_per_chunk); \
         else DNMF_LAUNCH((kl_wtu_kernel<KT_, NT_, false>), grid, block, lds, st, a, rowblks_per_chunk);    \
     }
-#ifdef DNMF_TUNING
-    static const long wvar = tune("DNMF_WTU_VAR", 0);          // A/B: 10 * nt + waves per SIMD for kt = 1; 100 + waves per SIMD for kt = 2
-#define WV(KT_, NT_, OCC_, VAR_) if (kt == KT_ && nt == NT_ && wvar == VAR_ && fast) { \
-        DNMF_LAUNCH((kl_wtu_kernel<KT_, NT_, true, OCC_>), grid, block, lds, st, a, rowblks_per_chunk); } else
-    WV(1, 2, 2, 22) WV(1, 2, 3, 23) WV(1, 4, 1, 41) WV(2, 2, 1, 101) WV(2, 2, 2, 102)
-#undef WV
-#endif
-    {
     WU_CASE(1, 4) WU_CASE(2, 2) WU_CASE(4, 2)
-    }
 #undef WU_CASE
     int rc = check_launch("kl_wtu");
     if (rc) return rc;

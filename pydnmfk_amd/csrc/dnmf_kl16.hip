@@ -24,7 +24,7 @@ constexpr long WINDOW = 0x7fffffffL;          // the kernels address a tile / a 
 // (other ranks go to the caller's block-aware padding and come back as one matrix)
 int dnmf_kl16_uht_(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, long hblk, int k,
                    float eps, float* UHT, long ldo, void* ws, size_t ws_bytes, void* stream) {
-    if (!(k <= 16 && k16_on() && aligned16(A) && lda % 4 == 0 && n % BK == 0 && m <= 0x7fffffffL)) return 1;
+    if (!(k <= 16 && aligned16(A) && lda % 4 == 0 && n % BK == 0 && m <= 0x7fffffffL)) return 1;
     if (hblk && !friendly16(W, ldw, H, ldh, k)) return 1;
     const long ldh_img = friendly16(W, ldw, H, ldh, k) ? ldh : round_up(n, 4);
     if (128 * lda * 4 + n * 4 >= WINDOW || 16 * ldh_img * 4 + n * 4 >= WINDOW) return 1;
@@ -66,7 +66,7 @@ int dnmf_kl16_uht_(const float* A, long m, long n, long lda, const float* W, lon
 
 int dnmf_kl16_wtu_(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
                    float eps, float* WTU, long ldo, void* ws, size_t ws_bytes, void* stream) {
-    if (!(k <= 16 && k16_on() && aligned16(A) && lda % 4 == 0 && n % 64 == 0)) return 1;
+    if (!(k <= 16 && aligned16(A) && lda % 4 == 0 && n % 64 == 0)) return 1;
     hipStream_t st = S(stream);
     const Tn16Plan q = plan_wtu16(m, n);
     const long ldw_img = friendly16(W, ldw, H, ldh, k) ? ldw : 16;

@@ -40,39 +40,39 @@ __device__ __forceinline__ float klu_quot(float a, float d) { return a * __built
 // waves per SIMD the register budget is cut for (KT = 4: out 64 + W row 64 + S^T 16 + A 16 + H stage 16 + fragments 16)
 template <int KT> struct KlUhtOcc { static constexpr int value = KT == 4 ? 2 : (KT == 2 ? 3 : 4); };
 
-// AUXA: cache policy of the A loads.  A lane reads 16 bytes of ITS row, so one instruction touches 32 rows x 32 bytes and a
-// row's 128-byte line is completed by four instructions: with the nontemporal hint every one of them went to L2 as its own
-// 32-byte request (TCP_TCC_READ_REQ: 7.2e7 per launch = 30 B per request at 32768 x 16384, k = 32); plain loads merge in L1
-// (0.69 -> 0.65 ms there, +2.5 % at k = 64, nothing at k = 128).
+// The A loads keep the default cache policy.  A lane reads 16 bytes of ITS row, so one instruction touches 32 rows x 32 bytes
+// and a row's 128-byte line is completed by four instructions: with the nontemporal hint every one of them went to L2 as its
+// own 32-byte request (TCP_TCC_READ_REQ: 7.2e7 per launch = 30 B per request at 32768 x 16384, k = 32); plain loads merge in
+// L1 (0.69 -> 0.65 ms there, +2.5 % at k = 64, nothing at k = 128).
 // A2: the A pieces of tile t+1 land in a second register set requested at the top of tile t (a whole tile of latency);
 // otherwise they refill the one set right after the quotient consumed it (second product + next first product of latency).
-// ABL (tuning build only, tools/kluht_ab.py): ablations that give wrong results but tell where the time goes -- 1: no
-// barrier, 2: no quotient, 4: A pieces loaded once, 8: H tile loaded / staged once, 16: no second product, 32: no first product, 64: line-coalesced A requests, 128: one LDS read per product and tile
-// MR (round 5): 32-row groups per wave.  MR = 2: a wave owns 64 rows -- two S^T tiles, two out strips, two sets of A
-// pieces -- and every H fragment read from LDS (both products) feeds TWO MFMAs: half the LDS reads per matrix instruction, the
-// one term of the k <= 64 kernels' instruction mix that a wider tile can shrink.  Same arithmetic per element in the same order:
-// bit identical to MR = 1.  The workgroup then covers 256 rows.
-template <int KT, bool A2, int OCC = KlUhtOcc<KT>::value, int ABL = 0, int AUXA = 0, int MR = 1>
-__global__ __launch_bounds__(256, OCC) void kl_uht_pipe_kernel(KlUhtArgs p, BatchTab bt) {
-    static_assert(MR == 1 || ABL == 0, "the ablations exist for the one-group kernel");
+// Measured and not kept (round 5; profiles/r05_kluht_mr_pmc.txt): 64-row wave tiles (256-row workgroups)
+// for k <= 64, in which every H fragment read from LDS feeds two MFMAs -- bit identical, LDS instructions per MFMA
+// 0.41 -> 0.20, LDS wait cycles -70 %, and the same time at k = 32 (0.655 -> 0.645 ms) and +25..50 % at k = 64 (250
+// registers: two waves per SIMD).  The LDS reads were not what holds these products back.  The ablations that located the
+// time (no barrier, no quotient, no first or second product, ...) are recorded in docs/history/DESIGN_r01-r05.md.
+template <int KT, bool A2>
+__global__ __launch_bounds__(256, KlUhtOcc<KT>::value) void kl_uht_pipe_kernel(KlUhtArgs p, BatchTab bt) {
     rebase_args(p, bt);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int KP = 32 * KT, STAGE = KP * BK, NY = KP / 32, NG = 4 * KT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
-    const long arow0 = (long)blockIdx.x * 128 * MR;
-    const long arow = arow0 + wave * 32 * MR + li;                 // the lane's row of group 0; group r: + 32 r
+    const long arow0 = (long)blockIdx.x * 128;
+    const long arow = arow0 + wave * 32 + li;                       // the lane's row
     const long cbeg = (long)blockIdx.y * p.cols_per_split;
     long cend = cbeg + p.cols_per_split;
     if (cend > p.n) cend = p.n;
     const int nt = (int)((cend - cbeg) / BK);
     const float* Hb = p.H + (p.hblk ? (cbeg / p.hblk) * p.hextra : 0);    // this split's column block of H (block uniform)
     const i32x4 rsa = buf_rsrc(p.A + arow0 * p.lda + cbeg), rsh = buf_rsrc(Hb + cbeg);
-    const int va = (ABL & 64) ? (int)((wave * 32 + (lane >> 3)) * p.lda * 4) + 16 * (lane & 7)    // (ablation: line-coalesced requests, wrong data)
-                              : (int)((wave * 32 * MR + li) * p.lda * 4) + 16 * h;     // A[arow][c0 + 8 g + 4 h ..+3] at va + 32 g (+ tile offset)
-    int vam[MR];                                                    // group r: 32 r rows further down
+    // A[arow][c0 + 8 g + 4 h ..+3] at va + 32 g (+ tile offset).  The offset goes through a one-element array filled by a one-trip loop,
+    // the form it had when a wave could own several 32-row groups: hipcc then emits the code the kernel was measured with (the plain
+    // scalar form allocates the registers of the whole kernel differently).
+    const int va0 = (int)((wave * 32 + li) * p.lda * 4) + 16 * h;
+    int vg[1];
 #pragma unroll
-    for (int r = 0; r < MR; ++r) vam[r] = va + (int)(32 * r * p.lda * 4);
-    const int lda32 = (int)(p.lda * 32);
+    for (int r = 0; r < 1; ++r) vg[r] = va0 + (int)(32 * r * p.lda * 4);
+    const int va = vg[0];
     int vh[NY];
     stage_offsets<KP, 256>(vh, p.ldh, tid);
 
@@ -88,31 +88,23 @@ __global__ __launch_bounds__(256, OCC) void kl_uht_pipe_kernel(KlUhtArgs p, Batc
     // staging: thread t owns chunk t & 7 of rows (t >> 3) + 32 it
     const int aw = (tid >> 3) * BK + (((tid & 7) ^ ((tid >> 4) & 7)) << 2);
 
-    f32x16 out[MR][KT];  // (U H^T)^T tile: rows j (KT tiles of 32), lanes i
+    f32x16 out[KT];  // (U H^T)^T tile: rows j (KT tiles of 32), lanes i
 #pragma unroll
-    for (int m = 0; m < MR; ++m)
+    for (int jt = 0; jt < KT; ++jt)
 #pragma unroll
-        for (int jt = 0; jt < KT; ++jt)
+        for (int r = 0; r < 16; ++r) out[jt][r] = 0.f;
+    float wreg[NG][4];   // W[arow][8 s + 4 h + e]: the lane's own row, B operand of the first product for the whole kernel
 #pragma unroll
-            for (int r = 0; r < 16; ++r) out[m][jt][r] = 0.f;
-    float wreg[MR][NG][4];   // W[arow + 32 m][8 s + 4 h + e]: the lane's own rows, B operand of the first product for the whole kernel
-#pragma unroll
-    for (int m = 0; m < MR; ++m)
-#pragma unroll
-        for (int s = 0; s < NG; ++s) load_vec_raw<4>(wreg[m][s], p.W + (arow + 32 * m) * p.ldw + 8 * s + 4 * h);
+    for (int s = 0; s < NG; ++s) load_vec_raw<4>(wreg[s], p.W + arow * p.ldw + 8 * s + 4 * h);
 
     f32x4 hst[NY];
-    float a0[MR][4][4], a1[A2 ? MR : 1][A2 ? 4 : 1][4];
+    float a0[4][4], a1[A2 ? 4 : 1][4];
     float hv[2][4];
     f32x4 hh[2];
 
     auto load_a = [&](auto& a, int so) {
 #pragma unroll
-        for (int m = 0; m < MR; ++m)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                if constexpr ((ABL & 64) != 0) buf_load<4, AUXA>(a[m][g], rsa, va, so + g * lda32);
-                else buf_load<4, AUXA>(a[m][g], rsa, vam[m] + 32 * g, so);
+        for (int g = 0; g < 4; ++g) buf_load<4>(a[g], rsa, va + 32 * g, so);
     };
     auto store_h = [&](float* stage) {
 #pragma unroll
@@ -120,13 +112,11 @@ __global__ __launch_bounds__(256, OCC) void kl_uht_pipe_kernel(KlUhtArgs p, Batc
     };
     auto read_hv = [&](float (&v)[4], const float* Hs, auto S) {
         constexpr int s = decltype(S)::value;
-        if constexpr ((ABL & 128) != 0) { if (s != 0) return; }        // (ablation: the first step's values for every step)
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = Hs[ax[2 * (s & 1) + (e >> 1)] + (8 * s + e) * BK];
     };
     auto read_hh = [&](f32x4& v, const float* Hs, auto Q) {
         constexpr int q = decltype(Q)::value, g = q / KT, jt = q % KT;
-        if constexpr ((ABL & 128) != 0) { if (q != 0) return; }
         v = *reinterpret_cast<const f32x4*>(&Hs[ay[g] + jt * 32 * BK]);
     };
 
@@ -137,53 +127,40 @@ __global__ __launch_bounds__(256, OCC) void kl_uht_pipe_kernel(KlUhtArgs p, Batc
         const float* Hs = smem + cur * STAGE;
         float* Hn = smem + (cur ^ 1) * STAGE;
         const int so = tn * (BK * 4);                       // wave uniform
-        if constexpr (!(ABL & 8)) stage_load_buf<NY, false>(hst, rsh, vh, so);
-        if constexpr (A2 && !(ABL & 4)) load_a(an, so);
-        f32x16 st[MR];   // S^T tiles (rows c, lanes i), eps = initial value: S + eps costs nothing
+        stage_load_buf<NY, false>(hst, rsh, vh, so);
+        if constexpr (A2) load_a(an, so);
+        f32x16 st;   // S^T tile (rows c, lanes i), eps = initial value: S + eps costs nothing
 #pragma unroll
-        for (int m = 0; m < MR; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[m][r] = p.eps;
+        for (int r = 0; r < 16; ++r) st[r] = p.eps;
         static_for<0, NG>([&](auto S) {
             constexpr int s = decltype(S)::value;
             if constexpr (s + 1 < NG) read_hv(hv[(s + 1) & 1], Hs, std::integral_constant<int, s + 1>{});
             else read_hh(hh[0], Hs, std::integral_constant<int, 0>{});
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int m = 0; m < MR; ++m)                    // (group by group: four MFMAs on one chain behind its eps block, HAZARD 2)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if constexpr (!(ABL & 32)) st[m] = MFMA32(hv[s & 1][e], wreg[m][s][e], st[m]);
-                    else st[m][e] += hv[s & 1][e] * wreg[m][s][e];
+            for (int e = 0; e < 4; ++e) st = MFMA32(hv[s & 1][e], wreg[s][e], st);   // (four MFMAs on one chain behind its eps block, HAZARD 2)
             __builtin_amdgcn_sched_barrier(0);
         });
 #pragma unroll
-        for (int m = 0; m < MR; ++m)
+        for (int g = 0; g < 4; ++g)
 #pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; e += 2)
-                    if constexpr (!(ABL & 2)) {                                   // U^T (dist_nmf.py:806): two reciprocals, ONE packed multiply
-                        const f32x2 r = {__builtin_amdgcn_rcpf(st[m][4 * g + e]), __builtin_amdgcn_rcpf(st[m][4 * g + e + 1])};
-                        const f32x2 q = f32x2{ac[m][g][e], ac[m][g][e + 1]} * r;
-                        st[m][4 * g + e] = q[0]; st[m][4 * g + e + 1] = q[1];
-                    } else if (g == 0 && e == 0) st[m][0] += ac[m][0][0] + ac[m][1][1] + ac[m][2][2] + ac[m][3][3];
-        if constexpr (!A2 && !(ABL & 4)) load_a(ac, so);
+            for (int e = 0; e < 4; e += 2) {                                 // U^T (dist_nmf.py:806): two reciprocals, ONE packed multiply
+                const f32x2 r = {__builtin_amdgcn_rcpf(st[4 * g + e]), __builtin_amdgcn_rcpf(st[4 * g + e + 1])};
+                const f32x2 q = f32x2{ac[g][e], ac[g][e + 1]} * r;
+                st[4 * g + e] = q[0]; st[4 * g + e + 1] = q[1];
+            }
+        if constexpr (!A2) load_a(ac, so);
         static_for<0, NG>([&](auto Q) {
             constexpr int q = decltype(Q)::value, g = q / KT, jt = q % KT;
             if constexpr (q + 1 < NG) read_hh(hh[(q + 1) & 1], Hs, std::integral_constant<int, q + 1>{});
-            if constexpr (q == NG - 2 && !(ABL & 8)) store_h(Hn);
+            if constexpr (q == NG - 2) store_h(Hn);
             if constexpr (q == NG - 1) {
-                if constexpr (!(ABL & 1)) __syncthreads();
+                __syncthreads();
                 read_hv(hv[0], Hn, std::integral_constant<int, 0>{});
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int m = 0; m < MR; ++m)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if constexpr (!(ABL & 16)) out[m][jt] = MFMA32(hh[q & 1][e], st[m][4 * g + e], out[m][jt]);
-                    else out[m][jt][e] += hh[q & 1][e] * st[m][4 * g + e];
+            for (int e = 0; e < 4; ++e) out[jt] = MFMA32(hh[q & 1][e], st[4 * g + e], out[jt]);
             __builtin_amdgcn_sched_barrier(0);
         });
     };
@@ -196,7 +173,6 @@ __global__ __launch_bounds__(256, OCC) void kl_uht_pipe_kernel(KlUhtArgs p, Batc
     const int last = nt - 1;
     int t = 0;
     if constexpr (A2) {
-        if constexpr ((ABL & 4) != 0) load_a(a1, 0);
         for (; t + 2 <= nt; t += 2) {
             tile(std::integral_constant<int, 0>{}, a0, a1, t + 1);
             tile(std::integral_constant<int, 1>{}, a1, a0, t + 2 < nt ? t + 2 : last);
@@ -211,16 +187,13 @@ __global__ __launch_bounds__(256, OCC) void kl_uht_pipe_kernel(KlUhtArgs p, Batc
     }
 
     // out[jt] (reg, lane): j = jt*32 + crow(reg, h), i = arow; registers 4g..4g+3 are 4 consecutive j
+    float* dst = p.out + (long)blockIdx.y * p.split_stride + arow * p.ldo;
 #pragma unroll
-    for (int m = 0; m < MR; ++m) {
-        float* dst = p.out + (long)blockIdx.y * p.split_stride + (arow + 32 * m) * p.ldo;
+    for (int jt = 0; jt < KT; ++jt)
 #pragma unroll
-        for (int jt = 0; jt < KT; ++jt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<f32x4*>(dst + jt * 32 + 8 * g + 4 * h) =
-                    f32x4{out[m][jt][4 * g], out[m][jt][4 * g + 1], out[m][jt][4 * g + 2], out[m][jt][4 * g + 3]};
-    }
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<f32x4*>(dst + jt * 32 + 8 * g + 4 * h) =
+                f32x4{out[jt][4 * g], out[jt][4 * g + 1], out[jt][4 * g + 2], out[jt][4 * g + 3]};
 }
 
 }  // namespace

@@ -19,7 +19,6 @@ struct NnArgs {
     float eps; double* out;                          // NN_RESID
     float* P; long chunk_stride; long ldp;           // NN_KL_WTU partials [rowblk][KP][ldp]
     long nrowblk; int ncolblk;
-    int pipe;                                        // NN_KL_*: software-pipelined interior path (DNMF_KL_PIPE=0 switches it off)
     long hblk; long hextra;                          // kl_uht: H given as column blocks [n / hblk][k][hblk] (an allgather's receive
                                                      // buffer): columns [q hblk, (q+1) hblk) live at H + q hextra with ldh = hblk;
                                                      // hblk = 0: one k x n matrix.  A column split never straddles a block.
@@ -401,8 +400,8 @@ __device__ __forceinline__ void kl_wtu_chunk_pipe(f32x16 (&out)[KT][NT], const N
     }
 }
 
-template <int KT, int NT, bool FAST, int OCC = (KT == 2 ? 2 : 1)>
-__global__ __launch_bounds__(256, OCC) void kl_wtu_kernel(NnArgs p, long rowblks_per_chunk, BatchTab bt) {
+template <int KT, int NT, bool FAST>
+__global__ __launch_bounds__(256, KT == 2 ? 2 : 1) void kl_wtu_kernel(NnArgs p, long rowblks_per_chunk, BatchTab bt) {
     rebase_args(p, bt);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int KP = 32 * KT, CW = 32 * NT;
@@ -435,7 +434,7 @@ __global__ __launch_bounds__(256, OCC) void kl_wtu_kernel(NnArgs p, long rowblks
     // (A merely branch-free block, its 16 A loads issued as one VMEM block ahead of the MFMAs, was 8-20 % slower than
     // the predicated one.)
     const long rb0 = chunk * rowblks_per_chunk;
-    if (FAST && p.pipe && p.k == KP && col0 + CW <= p.n && rb1 * 32 <= p.m &&
+    if (FAST && p.k == KP && col0 + CW <= p.n && rb1 * 32 <= p.m &&
         buf_window_ok((rb1 - rb0 + 1) * 32, p.lda, CW) && buf_window_ok((rb1 - rb0 + 1) * 32, p.ldw, KP)) {   // (one descriptor per chunk)
         if (KT == 1 && p.kreal <= 24) kl_wtu_chunk_pipe<KT, NT, KT == 1>(out, p, smem, rb0, rb1, col0, li, h);
         else kl_wtu_chunk_pipe<KT, NT, false>(out, p, smem, rb0, rb1, col0, li, h);

@@ -20,7 +20,7 @@
 // Two barriers per step among the <= 64 workgroups of ONE problem (an arrival counter per problem; the exchanged data move as
 // device-scope atomic stores / loads, see st_dev); waits are bounded by the wall clock and report through a sticky word, as the
 // persistent HALS sweep does.
-// Measured (20 problems of 1024 x 256, k <= 16, 8 workgroups of 8 waves each; tuning build with phases switched off): a step is 19 us
+// Measured (20 problems of 1024 x 256, k <= 16, 8 workgroups of 8 waves each; with phases switched off in an ablation build): a step is 19 us
 // = W phase 6-7 us + H phase 6-7 us (4.2 MFLOP per workgroup and step on one CU's matrix pipe: 160 of the 256 CUs are in use) + 6 us
 // of H update, re-read of H and row / column sums + 2 us for the two barriers; the per-step path needs 90 us for the same step.
 // The sums are fp32 MFMA accumulations in a different association than the big kernels' (dnmf_kl16.h): results agree with the step
@@ -137,7 +137,7 @@ __device__ __forceinline__ void hs_row_sums(const float (&rs)[RB], float* xs, in
 // (the rows [k, KP) are zeroed once, before the first step).  Wave wv takes the rows wv, wv + NW, ..., a lane four consecutive columns;
 // every load of a pass is in flight before the first value is used and no index is divided (round 6: the element-indexed copy, eight
 // loads in flight and a division per element, was 2.4 us of an 18.7 us step at k <= 16 and 5.6 of 29.3 at k = 17, tools/swimbench.py
-// under DNMF_SMALL_ABL).
+// on an ablation build).
 // xs != nullptr: also the row sums of H (a wave owns whole rows: lane partials, then the wave's reduction) -> xs[j], j < k.
 template <int NW, int KP>
 __device__ __forceinline__ void hs_fill(const float* H, long ldh, int k, int n, int NS, int LDH, float* Hs, int wv, int lane, float* xs = nullptr) {
@@ -235,12 +235,6 @@ __global__ __launch_bounds__(64 * NW, 1) void small_kl_fit_kernel(SmallKlArgs a)
     const int m = a.m, n = a.n, k = a.k;
     const float eps = a.eps;
     const int ksteps = (k + 3) >> 2;                      // contraction steps of 4 that hold real columns of W
-#ifdef DNMF_TUNING
-    const int abl = a.w_update >> 8;                       // ablations (WRONG results, timing only): 1 H without waiting for its granules, 2 no barrier before the H update, 4 no reload of H, 8 no H update
-    a.w_update &= 1;
-#else
-    constexpr int abl = 0;
-#endif
     const int NS = (n + 15) & ~15, nct = NS / 16, LDA = NS + 4, LDH = NS + 4;
     float* pcs = part + (long)P * KP * NS;                 // [P][KP] column sums of W per slab
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -451,9 +445,9 @@ __global__ __launch_bounds__(64 * NW, 1) void small_kl_fit_kernel(SmallKlArgs a)
                 for (int r = 0; r < 4; ++r)
                     if (16 * jt + 4 * q + r < k) st_dev(&part[((long)p * KP + 16 * jt + 4 * q + r) * NS + c0 + i], acc3[0][jt][r] + acc3[1][jt][r]);   // (only the k real rows are read)
         }
-        if (!(abl & 2)) small_barrier(bar, (unsigned)P * ++gen, a.patience);
+        small_barrier(bar, (unsigned)P * ++gen, a.patience);
         // -------------------------------------------------------------------- H update: this workgroup's share of the elements
-        for (int e = p * T + tid; e < ((abl & 8) ? 0 : k * NS); e += P * T) {      // (the rows [k, KP) of H do not exist)
+        for (int e = p * T + tid; e < k * NS; e += P * T) {      // (the rows [k, KP) of H do not exist)
             const int j = e / NS, c = e - j * NS;
             float sum = 0.f, x = 0.f;                      // W^T U and the column sum of W over all slabs, slab order
             auto add = [&](auto wide, int g0) __attribute__((always_inline)) {      // `wide` partials of each in flight
@@ -478,7 +472,7 @@ __global__ __launch_bounds__(64 * NW, 1) void small_kl_fit_kernel(SmallKlArgs a)
             }
         }
         __syncthreads();                                   // (every thread has read its old elements of Hs)
-        if (!(abl & 4)) load_h((abl & 1) ? 0.f : (float)(it + 1));                              // (no device-wide barrier: the granules carry their step)
+        load_h((float)(it + 1));                                   // (no device-wide barrier: the granules carry their step)
         if (clamp) {                                       // W = max(W, eps) after both updates (pyDNMF.py:155)
 #pragma unroll
             for (int s = 0; s < KS; ++s) {

@@ -167,14 +167,14 @@ __device__ __forceinline__ void tile_store(char* tile, const u32x4 (&v)[3 * 32 *
 // free, tile t + 1 (loaded NSET - 1 tiles ago) goes to the other LDS stage after the MFMAs of tile t.
 constexpr int XT = 32;                                                   // contraction indices per NT tile
 
-template <int KT, bool INTERIOR, bool NTX, int NSET, typename TX, int NW = 4>
+template <int KT, bool INTERIOR, bool NTX, int NSET, typename TX>
 __device__ __forceinline__ void ntx_mainloop(f32x16 (&acc)[1][KT], const TX* __restrict__ X, long ldx, long nrows, long row0,
                                              const SplitOperand& ys, long cbeg, long cend, float* smem) {
     // bf16-stored X: a tile is the same 128 bytes of every row = 64 contraction indices, kept in LDS as it lies in HBM; a
     // fragment read IS the MFMA operand (no cutting), and a product is three MFMAs (the pieces of H only).
     constexpr bool B16 = std::is_same<TX, bf16_t>::value;
     constexpr int XTI = B16 ? 64 : XT, CR = XTI / 8;                 // indices per tile, 16-byte chunks per H-tile row
-    constexpr int BM = 32 * NW, T = 64 * NW;                       // rows and threads of the workgroup
+    constexpr int BM = 128, T = 256;                               // rows and threads of the workgroup
     constexpr int XB = BM * 128, HB = 3 * 32 * KT * CR * 16, STAGE = XB + HB;      // bytes
     char* lds = reinterpret_cast<char*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, h = lane >> 5;
@@ -296,16 +296,16 @@ __device__ __forceinline__ void ntx_mainloop(f32x16 (&acc)[1][KT], const TX* __r
 
 // tiles in flight: 4 register sets at KP = 64 with fp32 A (28 registers a set), 2 where a set is 40-64 registers (KP = 128, or
 // bf16 A with its 64-index H tiles); bf16 A at KP = 128 stages 128 KiB, i.e. one workgroup per CU, and may use its registers
-// NW = waves (32-row groups) per workgroup: 4 in the shipped library.  NW = 6 (192 rows, 166 registers with two register sets
-// in flight, three waves per SIMD) exists for A/B runs: it is slower (2.16 vs 1.91 ms at the headline shape).
+// Workgroups of 4 waves (32-row groups).  Six waves (192 rows, 166 registers with two register sets in flight, three waves per
+// SIMD) were measured slower: 2.16 vs 1.91 ms at the headline shape -- more resident waves do not fill the idle issue slots.
 // (A second main loop -- A cut before LDS into wave-private piece tiles, two tiles in flight, 182 registers -- gave the same bits, 3 %
 // faster timed alone and 1 % slower inside the iteration: the pass is bound by the power limit, not by its schedule.  Measured in
 // rounds 3 / 4 (profiles/r03d_ntxproto.txt) and removed.)
-template <int KT, int MODE, int AUX, typename TX = float, int NW = 4,
-          int NSET = ((KT == 2 && std::is_same<TX, float>::value && NW == 4) ? 4 : 2)>
-__global__ __launch_bounds__(64 * NW, (KT == 4 && std::is_same<TX, bf16_t>::value) ? 1 : 2) void ntx_kernel(NtArgs p, SplitOperand ys) {
+template <int KT, int MODE, int AUX, typename TX = float>
+__global__ __launch_bounds__(256, (KT == 4 && std::is_same<TX, bf16_t>::value) ? 1 : 2) void ntx_kernel(NtArgs p, SplitOperand ys) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int BM = 32 * NW;
+    constexpr int NW = 4, BM = 32 * NW;
+    constexpr int NSET = (KT == 2 && std::is_same<TX, float>::value) ? 4 : 2;
     const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long row0 = (long)blockIdx.x * BM;
@@ -321,8 +321,8 @@ __global__ __launch_bounds__(64 * NW, (KT == 4 && std::is_same<TX, bf16_t>::valu
 
     const TX* X = static_cast<const TX*>(p.X);
     if (row0 + BM <= p.nrows) {
-        ntx_mainloop<KT, true, AUX != 0, NSET, TX, NW>(acc, X, p.ldx, p.nrows, row0, ys, cbeg, cend, smem);
-    } else ntx_mainloop<KT, false, false, 2, TX, NW>(acc, X, p.ldx, p.nrows, row0, ys, cbeg, cend, smem);
+        ntx_mainloop<KT, true, AUX != 0, NSET, TX>(acc, X, p.ldx, p.nrows, row0, ys, cbeg, cend, smem);
+    } else ntx_mainloop<KT, false, false, 2, TX>(acc, X, p.ldx, p.nrows, row0, ys, cbeg, cend, smem);
 
     if constexpr (MODE == NT_STORE) {
         float* out = p.out + (long)blockIdx.y * p.split_stride;

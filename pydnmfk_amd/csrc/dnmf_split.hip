@@ -21,7 +21,7 @@ bool split_shape(const TA* A, long m, long n, long lda, int k) {
     // 16-wide fp32 kernels are as fast (1.39-1.43 ms vs 1.43-1.46 ms) and stay.
     const int kmin = std::is_same<TA, bf16_t>::value ? 17 : 33;
     return k >= kmin && k <= DNMF_TUNED_MAX_K && n % 128 == 0 && lda % V == 0 && aligned16(A) && lda >= n && lda <= 4 * n && m >= 1 &&
-           n < (1L << 19) && tune("DNMF_SPLIT", 1) != 0;
+           n < (1L << 19);
 }
 
 struct TnxPlan { int nt, ncolblk, nchunks; long rows_per_chunk, ldp, chunk_stride; };
@@ -31,8 +31,7 @@ TnxPlan plan_tnx(long m, long n, int kt) {
     p.nt = kt == 4 ? 2 : 4;
     p.ncolblk = (int)(n / (32 * p.nt));
     const long cb4 = cdiv(p.ncolblk, 4);
-    static const long target = tune("DNMF_TNX_WGS", 512);           // one resident round: 256 CUs x 2 workgroups
-    long nchunks = std::max<long>(1, target / cb4);
+    long nchunks = std::max<long>(1, 512 / cb4);                    // one resident round: 256 CUs x 2 workgroups
     nchunks = std::min<long>(nchunks, cdiv(m, 256));
     // a chunk is addressed with 32-bit offsets from its first row: rows_per_chunk * lda * 4 < 2^31 for every lda <= 4 n that
     // split_shape admits (column slices of a wider matrix: the overlapped H phase of dist_nmf.py works on halves of A)
@@ -71,17 +70,18 @@ int cut_wt(const float* W, long m, int k, int kp, long ldw, bf16_t* img, SplitOp
     return check_launch("split3_cols");
 }
 
-template <int KT, int MODE, typename TX, int NW = 4>
+template <int KT, int MODE, typename TX>
 int launch_ntx_kt(const NtArgs& a, const SplitOperand& ys, hipStream_t st) {
+    constexpr int NW = 4;
     // two stages [A tile, 32 NW rows x 128 bytes | H tile bf16 pieces (32 indices per row for fp32 A, 64 for bf16 A)]; >= the W.G loop's LDS
     constexpr size_t lds = 2 * (32 * NW * 128 + 3 * 32 * KT * (std::is_same<TX, bf16_t>::value ? 128 : 64));
     static bool once = false;
     // A is touched once: stream it past the caches when it cannot stay in them anyway
-    const bool nt = (double)a.nrows * a.ncols * sizeof(TX) >= 256.0 * (1 << 20) && tune("DNMF_SPLIT_NT", 1) != 0;
-    if (!once) { allow_lds(ntx_kernel<KT, MODE, 0, TX, NW>, lds); allow_lds(ntx_kernel<KT, MODE, 2, TX, NW>, lds); once = true; }
+    const bool nt = (double)a.nrows * a.ncols * sizeof(TX) >= 256.0 * (1 << 20);
+    if (!once) { allow_lds(ntx_kernel<KT, MODE, 0, TX>, lds); allow_lds(ntx_kernel<KT, MODE, 2, TX>, lds); once = true; }
     const dim3 grid((unsigned)cdiv(a.nrows, 32 * NW), 1);
-    if (nt) hipLaunchKernelGGL((ntx_kernel<KT, MODE, 2, TX, NW>), grid, dim3(64 * NW), lds, st, a, ys);
-    else hipLaunchKernelGGL((ntx_kernel<KT, MODE, 0, TX, NW>), grid, dim3(64 * NW), lds, st, a, ys);
+    if (nt) hipLaunchKernelGGL((ntx_kernel<KT, MODE, 2, TX>), grid, dim3(64 * NW), lds, st, a, ys);
+    else hipLaunchKernelGGL((ntx_kernel<KT, MODE, 0, TX>), grid, dim3(64 * NW), lds, st, a, ys);
     return check_launch("ntx_kernel");
 }
 
@@ -90,12 +90,6 @@ int launch_ntx(const NtArgs& a, const SplitOperand& ys, int kt, hipStream_t st) 
     if constexpr (std::is_same<TX, bf16_t>::value) {
         if (kt == 1) return launch_ntx_kt<1, MODE, TX>(a, ys, st);
     }
-#ifdef DNMF_TUNING
-    // 192-row workgroups = three waves per SIMD (166 registers, two register sets in flight): measured 2.16 ms against 1.91 ms
-    // for the 128-row form on 262144 x 8192 -- more resident waves do not fill the idle issue slots.  A/B runs only.
-    if constexpr (std::is_same<TX, float>::value)
-        if (kt == 2 && tune("DNMF_SPLIT_NW6", 0) != 0) return launch_ntx_kt<2, MODE, TX, 6>(a, ys, st);
-#endif
     return kt == 2 ? launch_ntx_kt<2, MODE, TX>(a, ys, st) : launch_ntx_kt<4, MODE, TX>(a, ys, st);
 }
 
@@ -104,7 +98,7 @@ int launch_tnx(const TnArgs& a, const SplitOperand& wsplit, const TnxPlan& p, lo
     constexpr size_t lds = 2 * 3 * 32 * KT * (XKT / 8) * 16;
     static bool once = false;
     if (!once) { allow_lds(tnx_kernel<KT, NT, XKT, 0, TX>, lds); allow_lds(tnx_kernel<KT, NT, XKT, 2, TX>, lds); once = true; }
-    const bool nt = (double)m * n * sizeof(TX) >= 256.0 * (1 << 20) && tune("DNMF_SPLIT_NT", 1) != 0;
+    const bool nt = (double)m * n * sizeof(TX) >= 256.0 * (1 << 20);
     const dim3 grid((unsigned)(cdiv(p.ncolblk, 4) * p.nchunks));
     if (nt) hipLaunchKernelGGL((tnx_kernel<KT, NT, XKT, 2, TX>), grid, dim3(256), lds, st, a, wsplit);
     else hipLaunchKernelGGL((tnx_kernel<KT, NT, XKT, 0, TX>), grid, dim3(256), lds, st, a, wsplit);
@@ -192,7 +186,7 @@ int wta_x6(const TA* A, long m, long n, long lda, const float* W, int k, long ld
 // whole 128-column blocks, 16-byte aligned rows of A; other shapes run the fp32 kernels.
 bool klx_shape(const float* A, long m, long n, long lda, int k) {
     return k >= 1 && k <= DNMF_TUNED_MAX_K && n % 128 == 0 && lda % 4 == 0 && aligned16(A) && lda >= n && lda <= 4 * n && m >= 1 &&
-           n < (1L << 19) && tune("DNMF_SPLIT_KL", 1) != 0;
+           n < (1L << 19);
 }
 
 struct KlxImages { SplitOperand wp, ht; };

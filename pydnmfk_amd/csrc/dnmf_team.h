@@ -72,10 +72,11 @@ struct TeamArgs {
     int T, tpx;                          // members per team, teams per XCD-residue class (grid = 8 tpx T)
     long rpt;                            // rows per team (a multiple of 16)
     unsigned long long patience;         // ticks of the 100 MHz wall clock a wait may last
-    int xflags;                          // tuning build only (0 in the shipped library): 1 = take granules as they are, 2 = no exchange at all (timing ablations, wrong results)
 };
 
-// SD: slabs in flight in registers ahead of the LDS ring (1, 2 or 3); NT: cache policy bits of the loads of A (2 = streaming)
+// SD = 2 slabs in flight in registers ahead of the LDS ring, loads of A with the streaming cache policy (NT = 2).  SD = 1 / 3, default-policy
+// loads of A, plain (not write-through) granule stores and the timing ablations (granules taken as they are, no exchange at all) were
+// measured while the kernel was built: profiles/r06_team_ab.txt.
 //
 // Memory instructions and the in-order counter.  A wave's loads and stores retire in issue order (s_waitcnt vmcnt(N) = "all but my N
 // youngest"), and this kernel has three streams per wave with very different latencies: the slab pieces of A (HBM, SD stages ahead),
@@ -92,8 +93,9 @@ struct TeamArgs {
 // ring fills the LDS), 3 at k <= 16 -- there a stage is short (0.9 us of MFMA) and one stage did not cover the fabric round trip: the
 // exchange cost 0.074 of 0.29 ms (profiles/r06_team_ab.txt)
 // MT = members per team the register sets are sized for: 8 (n <= 4096); 16 at k <= 16 only (n <= 8192: the registers allow it there)
-template <int SD, int NT, int KT = 2, int LA = 2, int MT = TM_MAXT>
+template <int KT, int LA, int MT = TM_MAXT>
 __global__ __launch_bounds__(64 * TM_NW, 2) void team_fro_kernel(TeamArgs a) {
+    constexpr int SD = 2, NT = 2;
     extern __shared__ __attribute__((aligned(16))) float tm_smem[];
     constexpr int TM_LDW = tm_ldw(16 * KT);
     constexpr int KP = 16 * KT, NB = LA + 1, NG = LA - 1, PER = NB % 2 ? 2 * NB : NB;   // ring slots, granule register sets, stages per unrolled group
@@ -190,7 +192,6 @@ __global__ __launch_bounds__(64 * TM_NW, 2) void team_fro_kernel(TeamArgs a) {
     for (int tk = 0; tk < KT; ++tk)
 #pragma unroll
         for (int j = 0; j < 4; ++j) qacc[tk][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const bool plain = (a.xflags & 4) != 0;
     // W_new^T W_new (the Gram matrix of the H phase, dist_nmf.py:748) rides along: the new rows of a slab are in every member's LDS, and as
     // the A operand of Q they ARE both operands of the product -- the slab's owner adds its 16 MFMAs (KT = 2, two per wave: tile (wv >> 1 & 1,
     // wv & 1), contraction steps 2 (wv >> 2), + 1; KT = 1: four MFMAs, one in each of the waves 0-3: step wv), no loads
@@ -300,7 +301,7 @@ __global__ __launch_bounds__(64 * TM_NW, 2) void team_fro_kernel(TeamArgs a) {
             unsigned tsum = __float_as_uint(gcur[0][1]);
 #pragma unroll
             for (int j = 1; j < MT + 2; ++j) tsum += __float_as_uint(gcur[j][1]);
-            if (eon && tsum != (MT + 2) * want && !(a.xflags & 1)) regather(s, gcur);
+            if (eon && tsum != (MT + 2) * want) regather(s, gcur);
             float ah = gcur[0][0];
 #pragma unroll
             for (int j = 1; j < MT; ++j) ah = fmaf(tmask[j], gcur[j][0], ah);     // planes j >= T: x 0 (a re-read of plane T - 1)
@@ -365,19 +366,13 @@ __global__ __launch_bounds__(64 * TM_NW, 2) void team_fro_kernel(TeamArgs a) {
             const float den = (((dd[0] + dd[1]) + dd[2]) + dd[3]) + a.eps;
             const float tag = __uint_as_float((unsigned)(s + LA + 1));
             const int slot = __builtin_amdgcn_readfirstlane(((s + LA) & (TM_D - 1)) * slotb);
-            const int ov = (o2 == member && !(a.xflags & 2)) ? gvoff : BUF_OOB;
-            if (plain) {        // the whole team on one XCD: its L2 is the point of coherence, the granules need not leave it
-                buf_st_f32x2(f32x2{v, tag}, rrsrc, (a.xflags & 2) ? BUF_OOB : gvoff, slot + member * PLANE, 0);
-                buf_st_f32x2(f32x2{wold[(U + LA) & 1], tag}, rrsrc, ov, slot + T * PLANE, 0);
-                buf_st_f32x2(f32x2{den, tag}, rrsrc, ov, slot + (T + 1) * PLANE, 0);
-            } else {
-                buf_st_f32x2(f32x2{v, tag}, rrsrc, (a.xflags & 2) ? BUF_OOB : gvoff, slot + member * PLANE, 16);
-                buf_st_f32x2(f32x2{wold[(U + LA) & 1], tag}, rrsrc, ov, slot + T * PLANE, 16);
-                buf_st_f32x2(f32x2{den, tag}, rrsrc, ov, slot + (T + 1) * PLANE, 16);
-            }
+            const int ov = o2 == member ? gvoff : BUF_OOB;
+            buf_st_f32x2(f32x2{v, tag}, rrsrc, gvoff, slot + member * PLANE, 16);
+            buf_st_f32x2(f32x2{wold[(U + LA) & 1], tag}, rrsrc, ov, slot + T * PLANE, 16);
+            buf_st_f32x2(f32x2{den, tag}, rrsrc, ov, slot + (T + 1) * PLANE, 16);
         }
         // the reads of slab s + LA - 1's granules (published a stage ago, used LA - 1 stages from now) into the set slab s has just left
-        if ((!GD || (s + LA - 1 >= 0 && s + LA - 1 < nsl)) && !(a.xflags & 2)) {
+        if (!GD || (s + LA - 1 >= 0 && s + LA - 1 < nsl)) {
             const int slot = __builtin_amdgcn_readfirstlane(((s + LA - 1) & (TM_D - 1)) * slotb);
 #pragma unroll
             for (int j = 0; j < MT + 2; ++j) {

@@ -2,9 +2,6 @@
 // csrc/dnmf.hip (mu_fro_step_impl) asks dnmf_team_plan_ whether a step of this shape takes it, sizes the workspace with
 // dnmf_team_ws_bytes_ and calls dnmf_team_fro_; the reduction of the teams' partials and the H update stay where they were.
 #include "dnmf_team.h"
-#ifdef DNMF_TUNING
-#include "dnmf_team2.h"       // the role-split variant: measured slower (profiles/r06b_team2_*), kept for the A/B only
-#endif
 #include "dnmf_host.h"
 
 namespace {
@@ -29,7 +26,7 @@ int team_cus() {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= TEAM_MAX_DEVICES) { clear_hip_error(); return 0; }
     if (have[dev]) return cus_of[dev];
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { clear_hip_error(); return 0; }
-    const auto kern = team_fro_kernel<2, 2, 2, 2>;
+    const auto kern = team_fro_kernel<2, 2>;
     allow_lds(kern, TM_LDS_BYTES + 64);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 64 * TM_NW, TM_LDS_BYTES) != hipSuccess || nb < 1) { clear_hip_error(); cus = 0; }
     cus_of[dev] = cus;
@@ -114,46 +111,17 @@ __attribute__((visibility("hidden"))) int dnmf_team_fro_(const float* A, long m,
     a.T = p.T; a.tpx = p.tpx; a.rpt = p.rpt;
     a.patience = g_team_patience;
     if (hipMemsetAsync(base + p.ctl_off, 0, p.total - p.ctl_off, st) != hipSuccess) return fail(DNMF_EHIP, "team: memset of the granule ring failed");
-    static const int sd = (int)tune("DNMF_TEAM_SD", 2), nt = (int)tune("DNMF_TEAM_NT", 2);
     const dim3 grid((unsigned)(8 * p.tpx * p.T)), block(64 * TM_NW);
-#ifdef DNMF_TUNING
-#define TEAM2_LAUNCH(SD, NT)                                                         \
-    do {                                                                             \
-        static bool once = false;                                                    \
-        if (!once) { allow_lds(team_split_kernel<SD, NT>, TM2_LDS_BYTES + 64); once = true; } \
-        hipLaunchKernelGGL((team_split_kernel<SD, NT>), grid, block, TM2_LDS_BYTES, st, a); \
-    } while (0)
-#endif
-#define TEAM_LAUNCH(SD, NT)                                                          \
-    do {                                                                             \
-        constexpr int SD16 = (SD) == 3 ? 2 : (SD);       /* the k <= 16 kernel's group is four stages long */ \
-        static bool once = false;                                                    \
-        if (!once) {                                                                 \
-            allow_lds(team_fro_kernel<SD, NT, 2, 2>, TM_LDS_BYTES + 64);             \
-            allow_lds(team_fro_kernel<SD16, NT, 1, 3>, tm_lds_bytes(16) + 64);       \
-            allow_lds(team_fro_kernel<SD16, NT, 1, 3, 2 * TM_MAXT>, tm_lds_bytes(16) + 64); \
-            once = true;                                                             \
-        }                                                                            \
-        if (p.kp == 16 && p.T > TM_MAXT) hipLaunchKernelGGL((team_fro_kernel<SD16, NT, 1, 3, 2 * TM_MAXT>), grid, block, tm_lds_bytes(16), st, a); \
-        else if (p.kp == 16) hipLaunchKernelGGL((team_fro_kernel<SD16, NT, 1, 3>), grid, block, tm_lds_bytes(16), st, a); \
-        else hipLaunchKernelGGL((team_fro_kernel<SD, NT, 2, 2>), grid, block, TM_LDS_BYTES, st, a); \
-    } while (0)
-#ifdef DNMF_TUNING
-    a.xflags = (int)tune("DNMF_TEAM_X", 0);
-    static const int ver = (int)tune("DNMF_TEAM_V", 1);
-    if (ver == 2) {
-        if (sd == 1) TEAM2_LAUNCH(1, 2);
-        else if (sd == 3) TEAM2_LAUNCH(3, 2);
-        else TEAM2_LAUNCH(2, 2);
-    } else
-    if (sd == 1 && nt == 2) TEAM_LAUNCH(1, 2);
-    else if (sd == 3 && nt == 2) TEAM_LAUNCH(3, 2);
-    else if (sd == 2 && nt == 0) TEAM_LAUNCH(2, 0);
-    else
-#endif
-        TEAM_LAUNCH(2, 2);
-#undef TEAM_LAUNCH
-    (void)sd; (void)nt;
+    static bool once = false;
+    if (!once) {
+        allow_lds(team_fro_kernel<2, 2>, TM_LDS_BYTES + 64);
+        allow_lds(team_fro_kernel<1, 3>, tm_lds_bytes(16) + 64);
+        allow_lds(team_fro_kernel<1, 3, 2 * TM_MAXT>, tm_lds_bytes(16) + 64);
+        once = true;
+    }
+    if (p.kp == 16 && p.T > TM_MAXT) hipLaunchKernelGGL((team_fro_kernel<1, 3, 2 * TM_MAXT>), grid, block, tm_lds_bytes(16), st, a);
+    else if (p.kp == 16) hipLaunchKernelGGL((team_fro_kernel<1, 3>), grid, block, tm_lds_bytes(16), st, a);
+    else hipLaunchKernelGGL((team_fro_kernel<2, 2>), grid, block, TM_LDS_BYTES, st, a);
     if (int rc = check_launch("team_fro_kernel")) return rc;
     }
     *P_out = (const float*)part;                                      // problem 0's (the reduction launch moves to its own problem by blockIdx.z)

@@ -45,7 +45,7 @@ constexpr int edge_occ(int kt, int occ) { return kt == 4 ? 2 : (occ < 4 ? occ : 
 // Step (jb, r) of output block ob: A operand lane (li, h) = G[32 ob + li][32 jb + crow(r, h)], read four at a time
 // (r = 4g .. 4g+3 are four consecutive columns of G starting at 32 jb + 8g + 4h).
 // NT = 1 needs no alignment at all (dword accesses); NT = 2 needs 8-byte aligned rows and an even n.
-template <int KT, int NT, bool INTERIOR, bool MMA = true, int AUXL = 0, int AUXS = 0>
+template <int KT, int NT, bool INTERIOR, int AUXL = 0, int AUXS = 0>
 __device__ __forceinline__ void update_h_seq_tile(float* __restrict__ H, int k, long n, long ldh, const float* __restrict__ Sm,
                                                   long lds_, const float* gs, float eps, int clamp, long col0, int li, int h) {
     constexpr int KP = 32 * KT, GP = KP + 4;
@@ -96,10 +96,7 @@ __device__ __forceinline__ void update_h_seq_tile(float* __restrict__ H, int k, 
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
 #pragma unroll
-                    for (int ne = 0; ne < NT; ++ne) {
-                        if constexpr (MMA) acc[ne] = MFMA32(a[e], hreg[jb][4 * g + e][ne], acc[ne]);
-                        else acc[ne][4 * g + e] += a[e] * hreg[jb][4 * g + e][ne];   // tuning build: same traffic, no matrix work
-                    }
+                    for (int ne = 0; ne < NT; ++ne) acc[ne] = MFMA32(a[e], hreg[jb][4 * g + e][ne], acc[ne]);
             }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -130,11 +127,10 @@ __device__ __forceinline__ void update_h_seq_tile(float* __restrict__ H, int k, 
 constexpr int upd_waves(int /*kt*/) { return 4; }
 // workgroups for `tiles` wave tiles: one tile per wave at k <= 64 (measured best: G is at most 16 KiB), capped at k = 128
 inline unsigned upd_grid(long tiles, int kt) {
-    const long cap = tune("DNMF_UPD_GRID", kt == 4 ? 1024 : (1L << 30));
-    return (unsigned)std::min<long>(cdiv(tiles, upd_waves(kt)), cap);
+    return (unsigned)std::min<long>(cdiv(tiles, upd_waves(kt)), kt == 4 ? 1024 : (1L << 30));
 }
 
-template <int KT, int NT, int OCC, bool EDGE, bool MMA = true, int AUXL = 0, int AUXS = 0, int NWV = upd_waves(KT)>
+template <int KT, int NT, int OCC, bool EDGE, int AUXL = 0, int AUXS = 0, int NWV = upd_waves(KT)>
 __global__ __launch_bounds__(64 * NWV, EDGE ? edge_occ(KT, OCC) : OCC) void update_h_seq_kernel(float* __restrict__ H, int k, long n, long ldh,
                                                                 const float* __restrict__ Sm, long lds_,
                                                                 const float* __restrict__ G, float eps, int clamp, BatchTab bt) {
@@ -151,7 +147,7 @@ __global__ __launch_bounds__(64 * NWV, EDGE ? edge_occ(KT, OCC) : OCC) void upda
     const long ntiles = cdiv(n, 32 * NT);
     for (long t = (long)blockIdx.x * NWV + wid; t < ntiles; t += (long)gridDim.x * NWV) {
         const long col0 = t * 32 * NT;
-        if constexpr (!EDGE) update_h_seq_tile<KT, NT, true, MMA, AUXL, AUXS>(H, k, n, ldh, Sm, lds_, gs, eps, clamp, col0, li, h);
+        if constexpr (!EDGE) update_h_seq_tile<KT, NT, true, AUXL, AUXS>(H, k, n, ldh, Sm, lds_, gs, eps, clamp, col0, li, h);
         else if (k == KP && col0 + 32 * NT <= n) update_h_seq_tile<KT, NT, true>(H, k, n, ldh, Sm, lds_, gs, eps, clamp, col0, li, h);
         else update_h_seq_tile<KT, NT, false>(H, k, n, ldh, Sm, lds_, gs, eps, clamp, col0, li, h);
     }
@@ -166,7 +162,7 @@ __global__ __launch_bounds__(64 * NWV, EDGE ? edge_occ(KT, OCC) : OCC) void upda
 // written to a separate buffer; W is only read.
 enum { UW_MU = 0, UW_HALS_T = 1 };
 
-template <int KT, int V, bool INTERIOR, int MODE = UW_MU, int AUX = 0>
+template <int KT, int V, bool INTERIOR, int MODE = UW_MU>
 __device__ __forceinline__ void update_w_seq_tile(float* __restrict__ W, long m, int k, long ldw, const float* __restrict__ Sm,
                                                   long lds_, const float* gs, float eps, long row0, int li, int h,
                                                   float* __restrict__ T = nullptr, long ldt = 0) {
@@ -191,7 +187,7 @@ __device__ __forceinline__ void update_w_seq_tile(float* __restrict__ W, long m,
     // (measured: lanes 12-15 / 28-31 of a store picked up the following group's denominators).
     auto ld4 = [&](float (&d)[4], i32x4 rs, int off, int s) {
         if constexpr (V == 4) {
-            buf_load<4, AUX>(d, rs, ((INTERIOR || 8 * s + 4 * h < k) ? off : BUF_OOB) + 32 * s, 0);
+            buf_load<4>(d, rs, ((INTERIOR || 8 * s + 4 * h < k) ? off : BUF_OOB) + 32 * s, 0);
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) d[e] = buf_ld_f32(rs, ((8 * s + 4 * h + e < k) ? off : BUF_OOB) + 32 * s + 4 * e, 0, 0);
@@ -199,7 +195,7 @@ __device__ __forceinline__ void update_w_seq_tile(float* __restrict__ W, long m,
     };
     auto st4 = [&](const float (&d)[4], i32x4 rs, int off, int s) {
         if constexpr (V == 4) {
-            buf_store<4, AUX>(d, rs, ((INTERIOR || 8 * s + 4 * h < k) ? off : BUF_OOB) + 32 * s, 0);
+            buf_store<4>(d, rs, ((INTERIOR || 8 * s + 4 * h < k) ? off : BUF_OOB) + 32 * s, 0);
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) buf_st_f32(d[e], rs, ((8 * s + 4 * h + e < k) ? off : BUF_OOB) + 32 * s + 4 * e, 0, 0);
@@ -236,7 +232,7 @@ __device__ __forceinline__ void update_w_seq_tile(float* __restrict__ W, long m,
     }
 }
 
-template <int KT, int V, int OCC, bool EDGE, int MODE = UW_MU, int AUX = 0, int NWV = upd_waves(KT)>
+template <int KT, int V, int OCC, bool EDGE, int MODE = UW_MU, int NWV = upd_waves(KT)>
 __global__ __launch_bounds__(64 * NWV, (EDGE || V == 1) ? edge_occ(KT, OCC) : OCC) void update_w_seq_kernel(float* __restrict__ W, long m, int k, long ldw,
                                                                 const float* __restrict__ Sm, long lds_,
                                                                 const float* __restrict__ G, float eps,
@@ -259,7 +255,7 @@ __global__ __launch_bounds__(64 * NWV, (EDGE || V == 1) ? edge_occ(KT, OCC) : OC
     const long ntiles = cdiv(m, 32);
     for (long t = (long)blockIdx.x * NWV + wid; t < ntiles; t += (long)gridDim.x * NWV) {
         const long row0 = t * 32;
-        if constexpr (!EDGE) update_w_seq_tile<KT, V, true, MODE, AUX>(W, m, k, ldw, Sm, lds_, gs, eps, row0, li, h, T, ldt);
+        if constexpr (!EDGE) update_w_seq_tile<KT, V, true, MODE>(W, m, k, ldw, Sm, lds_, gs, eps, row0, li, h, T, ldt);
         else if (k == KP && row0 + 32 <= m) update_w_seq_tile<KT, V, true, MODE>(W, m, k, ldw, Sm, lds_, gs, eps, row0, li, h, T, ldt);
         else update_w_seq_tile<KT, V, false, MODE>(W, m, k, ldw, Sm, lds_, gs, eps, row0, li, h, T, ldt);
     }

@@ -13,8 +13,7 @@ probe = ctypes.CDLL(os.path.join(here, "_build", "libclockprobe.so"))
 probe.clockprobe_launch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
 dev = torch.device("cuda", 0)
 g = torch.Generator(device=dev).manual_seed(1)
-# ALIAS=1 (tuning build + DNMF_ALLOW_ALIAS=1): every row of A is the same row -> A is cache resident, no HBM traffic, same instructions
-A = torch.rand(m, n, device=dev, generator=g) if not os.environ.get("ALIAS") else torch.rand(1, n, device=dev, generator=g).expand(m, n)
+A = torch.rand(m, n, device=dev, generator=g)
 W = torch.rand(m, k, device=dev, generator=g)
 H = torch.rand(k, n, device=dev, generator=g)
 AH = torch.empty(m, k, device=dev)
@@ -60,8 +59,6 @@ trace("A H^T + W update (fp32 MFMA)", lambda: f32.aht_update_w(A, H, G, Wc, 1e-7
 trace("W^T A (fp32 MFMA)", lambda: f32.wta(A, W, WtA), win)
 trace("A H^T (fp32 MFMA, plain)", lambda: f32.aht(A, H, AH), win)
 trace("||A||^2 (loads only)", lambda: f32.sqnorm(A) if hasattr(f32, "sqnorm") else A.sum(), win)
-if os.environ.get("ALIAS"):
-    sys.exit(0)
 Wc = W.clone()
 trace("A H^T + W update (bf16x6)", lambda: x6.aht_update_w(A, H, G, Wc, 1e-7), win)
 trace("W^T A (bf16x6)", lambda: x6.wta(A, W, WtA), win)

@@ -1,8 +1,6 @@
 """The reference's own test recipe (tests/test_dist_nmf_1d.py:14-46: 24 x 12 float64 data of exact rank 2, k = 2, 2000 iterations, mu-fro /
-mu-kl / hals) through PyNMF.fit on one rank: wall time per fit.  With the tuning build, DNMF_F64_TINY=0 shows the chain of float64
-primitives the single-workgroup kernel (csrc/dnmf_f64_tiny.hip) replaced:
-    python tools/f64tiny.py
-    DNMF_LIB_PATH=tools/_build/libdnmf_hip_tune.so DNMF_F64_TINY=0 python tools/f64tiny.py"""
+mu-kl / hals) through PyNMF.fit on one rank: wall time per fit (the single-workgroup kernel of csrc/dnmf_f64_tiny.hip):
+    python tools/f64tiny.py"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -16,7 +14,7 @@ np.random.seed(100)
 m, k, n = 24, 2, 12
 A = np.random.rand(m, k) @ np.random.rand(k, n)
 comms = MPI_comm(None, 1, 1)
-out = {"shape": [m, n, k], "itr": 2000, "tiny_kernel": bool(lib.dnmf_f64_fit_tiny(m, n, k, 0)) and os.environ.get("DNMF_F64_TINY", "1") != "0"}
+out = {"shape": [m, n, k], "itr": 2000, "tiny_kernel": bool(lib.dnmf_f64_fit_tiny(m, n, k, 0))}
 for mthd, norm in (("mu", "fro"), ("mu", "kl"), ("hals", "fro")):
     ts, err = [], None
     for rep in range(4):

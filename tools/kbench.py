@@ -7,7 +7,7 @@ m, n, k = (int(x) for x in sys.argv[1:4]) if len(sys.argv) > 3 else (262144, 819
 if "--bf16" in sys.argv: os.environ["BF16"] = "1"
 dev = torch.device("cuda", 0)
 g = torch.Generator(device=dev); g.manual_seed(1)
-A = torch.rand(m, n, device=dev, generator=g) if not os.environ.get("ALIAS") else torch.rand(1, n, device=dev, generator=g).expand(m, n); W = torch.rand(m, k, device=dev, generator=g); H = torch.rand(k, n, device=dev, generator=g)
+A = torch.rand(m, n, device=dev, generator=g); W = torch.rand(m, k, device=dev, generator=g); H = torch.rand(k, n, device=dev, generator=g)
 if os.environ.get("BF16"): A = A.to(torch.bfloat16)   # bf16 storage of A
 abytes = A.element_size() * m * n
 G = ops.gram_hht(H, new_gram(k, dev)); AtW = torch.empty(k, n, device=dev); Wt = W.clone()

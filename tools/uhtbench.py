@@ -1,4 +1,4 @@
-"""U H^T alone: python tools/uhtbench.py m n k   (tuning build: DNMF_KLUHT_VAR / DNMF_KLUHT_ABL / DNMF_KLUHT_PIPE select variants)"""
+"""One KL product alone: python tools/uhtbench.py m n k   (KB=uht / KB=wtu)"""
 import sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,5 +18,5 @@ for s, e in ev:
 torch.cuda.synchronize()
 x = sorted(s.elapsed_time(e) for s, e in ev)
 ms = x[len(x) // 2]
-print(json.dumps({"which": which, "m": m, "n": n, "k": k, "var": os.environ.get("DNMF_KLUHT_VAR", ""), "abl": os.environ.get("DNMF_KLUHT_ABL", ""),
+print(json.dumps({"which": which, "m": m, "n": n, "k": k,
                   "ms": round(ms, 4), "min_ms": round(x[0], 4), "tf": round(4.0 * m * n * k / ms / 1e9, 1)}))
