@@ -96,7 +96,9 @@ __attribute__((visibility("hidden"))) int dnmf_team_fro_(const float* A, long m,
     // after the other -- each exactly as a fit of its own (bit-identical, as the batched entry points promise)
     const int B = dnmf_batch_()->B;
     if (!(aligned16(A) && lda % 4 == 0 && lda >= n && aligned16(H) && ldh % 4 == 0 && ldh >= n && ldw >= k && aligned16(part))) return 1;
-    if ((double)p.rpt * lda * 4.0 >= 2147483648.0 || part_bytes < p.total) return 1;
+    // the A and the W descriptors are based at the team's first row and span 2 GiB: a team's rows must fit in both windows (beyond,
+    // the loads would read zeros and the stores of W would be dropped, silently)
+    if ((double)p.rpt * lda * 4.0 >= 2147483648.0 || (double)p.rpt * ldw * 4.0 >= 2147483648.0 || part_bytes < p.total) return 1;
     hipStream_t st = S(stream);
     for (int z = 0; z < B; ++z) {
     char* base = (char*)batch_ptr(part, z);

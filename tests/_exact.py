@@ -1,0 +1,195 @@
+"""Exact-by-construction operands for the kernel tests (tests/test_exact_cpu.py proves them, tests/test_gpu_exact.py uses them).
+
+Every product the kernels form on these operands is exact in fp32 -- small non-negative integers, or dyadic rationals with few
+significant bits -- so the sums come out the same in every summation order, split-K plan and MFMA shape, and a product is compared
+with float64 bit for bit.  Where a kernel divides, the numerator and the denominator are still exact and each element is held to
+an ulp bound against the float64 quotient (`assert_ulp`).  Every generator asserts its own range bound: all terms are non-negative
+multiples of a common power of two, so a total below 2^24 of those units bounds every partial sum as well.
+
+`Poisoned` places an operand inside a larger buffer whose padding, the elements before the view and a guard band after it hold
+NaN (a legal PyTorch view); outputs sit in a buffer filled with a sentinel.  `check()` asserts that nothing outside the view changed.
+"""
+import numpy as np
+
+MANT = {np.float32: 24, np.float64: 53}
+
+
+def _bound(total, unit, dtype, what):
+    """all terms non-negative multiples of `unit`: every partial sum is exact when the total is below 2^mantissa units"""
+    top = float(np.max(total)) if np.size(total) else 0.0
+    lim = float(unit) * 2.0 ** MANT[np.dtype(dtype).type]
+    assert top < lim, "%s: total %g reaches 2^%d units of %g -- the shape is too large for exact operands" % (what, top, MANT[np.dtype(dtype).type], unit)
+
+
+def products(m, n, k, dtype=np.float32, seed=0):
+    """A in 0..7, W and H in 1..3 with some zero rows / columns: A H^T, W^T A, the Grams, and the MU denominators W (H H^T),
+    (W^T W) H are integers.  The denominators are 0 (a zero row of W / column of H: that factor element stays 0) or >= 2 and
+    below 2^22, so eps is absorbed in every order (an integer below 2^22 is an even number of its own ulps)."""
+    rs = np.random.RandomState(seed + 1009 * m + 17 * n + k)
+    A = rs.randint(0, 8, size=(m, n)).astype(dtype)
+    A[rs.rand(m, n) < 0.2] = 0
+    W = rs.randint(1, 4, size=(m, k)).astype(dtype)
+    H = rs.randint(1, 4, size=(k, n)).astype(dtype)
+    W[rs.rand(m) < 0.05] = 0
+    H[:, rs.rand(n) < 0.05] = 0
+    A64, W64, H64 = (x.astype(np.float64) for x in (A, W, H))
+    G, GW = H64 @ H64.T, W64.T @ W64
+    dw, dh = W64 @ G, GW @ H64
+    for tot, what in ((A64 @ H64.T, "A H^T"), (W64.T @ A64, "W^T A"), (G, "H H^T"), (GW, "W^T W")):
+        _bound(tot, 1.0, dtype, what)
+    for d, what in ((dw, "W HH^T"), (dh, "W^TW H")):
+        _bound(d, 0.25, np.float32, what)           # below 2^22
+        assert np.all((d == 0) | (d >= 2)), what
+    return A, W, H
+
+
+def _groups(n, k, tmax):
+    """k power-of-two group widths 2^t (t <= tmax) that tile the first columns of n; the columns after the last group stay zero in H"""
+    t = [0] * k
+    used = k
+    while used < n:
+        j = min(range(k), key=lambda i: t[i])
+        if t[j] >= tmax or used + (1 << t[j]) > n:
+            break
+        used += 1 << t[j]
+        t[j] += 1
+    assert used <= n, (n, k)
+    return t
+
+
+def fro_step(m, n, k, dtype=np.float32, seed=0, tmax=6):
+    """One MU/Frobenius step with an exact W phase: H has one nonzero per column, 2^-t_j in the 2^t_j columns of group j (G = H H^T
+    is diag(2^-t_j)); W[r][j] = 2^(t_j + 1 + s), s in 0..2 (W G = 2^(1 + s) >= 2); A in {0, 2^a}.  The new W is then 2^a times the
+    count of nonzeros of A's row in group j, exactly.  The H phase has exact numerators 2^2a sum_r cnt A/2^a and single-term
+    denominators 2^2a (cnt^T cnt)[j][g] 2^-t_g >= 2 (a chosen for that), below 2^22 units, so only its quotient rounds.
+    Returns A, W, H and the expected new W (exact) and the float64 quotient of the new H."""
+    assert n >= k
+    rs = np.random.RandomState(seed + 31 * m + 7 * n + k)
+    t = _groups(n, k, tmax)
+    a = (max(t) + 2) // 2
+    H = np.zeros((k, n), dtype=np.float64)
+    grp = np.full(n, -1)
+    c = 0
+    for j in range(k):
+        w = 1 << t[j]
+        H[j, c:c + w] = 2.0 ** -t[j]
+        grp[c:c + w] = j
+        c += w
+    p = min(0.5, max(0.05, 40.0 / max(m, 1) ** 0.5 / 2 ** (max(t) / 2)))
+    A = np.where(rs.rand(m, n) < p, 2.0 ** a, 0.0)
+    W = np.stack([2.0 ** (t[j] + 1 + rs.randint(0, 3, size=m)) for j in range(k)], axis=1)
+    G = H @ H.T
+    assert np.array_equal(G, np.diag(np.diag(G)))
+    AH = A @ H.T
+    Wn = W * AH / (W @ G)
+    cnt = AH / 2.0 ** a * 2.0 ** np.array(t)                     # nonzeros of A per row and group
+    assert np.array_equal(Wn, 2.0 ** a * cnt)
+    num, den = Wn.T @ A, (Wn.T @ Wn) @ H
+    _bound(cnt.T @ cnt, 0.25, np.float32, "H-phase denominators")                 # below 2^22 units of 2^(2a - t_g) >= 2
+    _bound(num, 2.0 ** (2 * a), dtype, "W_new^T A")
+    assert np.all((den == 0) | (den >= 2)), "an H-phase denominator in (0, 2): raise a"
+    Hq = np.where(den > 0, H * num / np.where(den > 0, den, 1.0), 0.0)
+    return A.astype(dtype), W.astype(dtype), H.astype(dtype), Wn, Hq
+
+
+def kl(m, n, k, dtype=np.float32, seed=0, qmax=3):
+    """KL operands with an exact quotient U = A / (W H + eps): W has one nonzero per row, a power of two 2^(0..2) in column j(r);
+    H[j][c] = 2^q, q in 1..qmax.  (W H)[r][c] = W[r][j(r)] H[j(r)][c] is a power of two >= 2, so eps is absorbed and U is A times a
+    power of two; U H^T and W^T U are sums of multiples of 2^-(2 + qmax), A in 0..7.  rowsum(H) >= 2 and colsum(W) are integers
+    (a colsum of 0 or 1 does not absorb eps: the reference of the KL H update rounds colsum + eps to float32 as the kernel does)."""
+    rs = np.random.RandomState(seed + 13 * m + 5 * n + 3 * k)
+    A = rs.randint(0, 8, size=(m, n)).astype(np.float64)
+    A[rs.rand(m, n) < 0.2] = 0
+    jr = rs.randint(0, k, size=m)
+    W = np.zeros((m, k))
+    W[np.arange(m), jr] = 2.0 ** rs.randint(0, 3, size=m)
+    H = 2.0 ** rs.randint(1, qmax + 1, size=(k, n))
+    WH = W @ H
+    assert np.all(WH >= 2) and np.array_equal(np.log2(WH), np.round(np.log2(WH)))
+    U = A / WH
+    unit = 2.0 ** -(2 + qmax)
+    _bound(U @ H.T, unit, dtype, "U H^T")
+    _bound(W.T @ U, unit, dtype, "W^T U")
+    _bound(H.sum(1), 1.0, np.float32, "rowsum(H)")
+    return A.astype(dtype), W.astype(dtype), H.astype(dtype), U
+
+
+# ---------------------------------------------------------------------------------------------------------- per-element comparison
+def assert_ulp(got, q, c, what="", tile=(16, 32), q_hi=None):
+    """|got - q| <= c * spacing(q in got's type) per element, q the float64 reference; q == 0 must be exactly 0 and c == 0 means
+    bit-equal.  q_hi: the reference is only known to lie between q and q_hi (an order-dependent input such as a sum that may or may
+    not absorb eps terms); got must be within c ulps of that interval.  On failure: the first bad (row, col), both bit patterns, the
+    tile it falls in and whether that is an edge tile."""
+    got = np.asarray(got)
+    q = np.asarray(q, dtype=np.float64)
+    assert got.shape == q.shape, "%s: shape %s, expected %s" % (what, got.shape, q.shape)
+    ft = got.dtype.type
+    g64 = got.astype(np.float64)
+    lo, hi = (q, q) if q_hi is None else (np.minimum(q, q_hi), np.maximum(q, q_hi))
+    if c == 0:
+        bad = ~((g64 >= lo) & (g64 <= hi))
+    else:
+        tol = c * np.spacing(np.maximum(np.abs(lo), np.abs(hi)).astype(ft)).astype(np.float64)
+        bad = ~((g64 >= lo - tol) & (g64 <= hi + tol)) | ((lo == 0) & (hi == 0) & (g64 != 0))
+    if not bad.any():
+        return
+    idx = tuple(int(i) for i in np.argwhere(bad)[0])
+    it = {np.float32: np.uint32, np.float64: np.uint64}[ft]
+    exp = ft(q[idx])
+    where = ""
+    if got.ndim == 2:
+        r, col = idx
+        tr, tc = r // tile[0], col // tile[1]
+        last_r, last_c = (got.shape[0] - 1) // tile[0], (got.shape[1] - 1) // tile[1]
+        where = " in tile (%d, %d) of (%d, %d)%s%s" % (tr, tc, last_r + 1, last_c + 1, " [last row tile]" if tr == last_r else "",
+                                                      " [last column tile]" if tc == last_c else "")
+    raise AssertionError("%s: %d of %d elements off by more than %g ulp; first at %s%s: got %r (0x%x), expected %r (0x%x), float64 %r"
+                         % (what, int(bad.sum()), bad.size, c, idx, where, got[idx].item(), got[idx].view(it).item(),
+                            exp.item(), np.array(exp).view(it).item(), q[idx]))
+
+
+# ---------------------------------------------------------------------------------------------------------- poisoned views
+SENTINEL = -12345.6875
+
+
+class Poisoned:
+    """A rows x cols view -- or a stack [B][rows][cols] of them, problem b at b rows ld -- inside a buffer: `lead` elements before it,
+    pitch ld >= cols, `guard` elements after it; everything outside the view holds `fill` (NaN for operands, SENTINEL for outputs).
+    aligned: lead and ld multiples of 4 (the vector paths); otherwise an odd start and pitch (the generic paths).  packed: ld = cols
+    (a contiguous view, for the entry points that require one)."""
+
+    def __init__(self, torch, x, dtype=None, fill=float("nan"), aligned=True, guard=67, device="cuda", packed=False):
+        x = np.asarray(x)
+        x3 = x if x.ndim == 3 else x[None]
+        B, rows, cols = x3.shape
+        self.torch = torch
+        self.dtype = dtype or {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}[x.dtype]
+        self.lead = 8 if aligned else 3
+        self.ld = cols if packed else (-(-cols // 4) * 4 + 4) if aligned else cols + 3
+        self.rows, self.cols, self.fill = rows, cols, fill
+        bs = rows * self.ld
+        self.buf = torch.full((self.lead + B * bs + guard,), fill, dtype=self.dtype, device=device)
+        v3 = self.buf.as_strided((B, rows, cols), (bs, self.ld, 1), self.lead)
+        v3.copy_(torch.from_numpy(np.ascontiguousarray(x3)).to(self.dtype))
+        self.view = v3 if x.ndim == 3 else v3[0]
+        self.mask = np.zeros(self.buf.numel(), dtype=bool)
+        self.mask[(self.lead + np.arange(B)[:, None, None] * bs + np.arange(rows)[None, :, None] * self.ld
+                   + np.arange(cols)[None, None, :]).ravel()] = True
+
+    @classmethod
+    def out(cls, torch, rows, cols, dtype, aligned=True):
+        npd = {torch.float32: np.float32, torch.float64: np.float64}[dtype]
+        return cls(torch, np.full((rows, cols), SENTINEL, dtype=npd), dtype, fill=SENTINEL, aligned=aligned)
+
+    def check(self, what=""):
+        """nothing outside the view changed; no NaN inside it.  Returns the view as numpy."""
+        b = self.buf.float().cpu().numpy() if self.dtype == self.torch.bfloat16 else self.buf.cpu().numpy()
+        out = b[~self.mask]
+        ok = np.isnan(out) if np.isnan(self.fill) else out == np.asarray(self.fill, dtype=b.dtype)
+        if not ok.all():
+            i = int(np.flatnonzero(~self.mask)[np.argmin(ok)])
+            raise AssertionError("%s: element %d of the buffer outside the view (view starts at %d, pitch %d) was written: %r"
+                                 % (what, i, self.lead, self.ld, b[i]))
+        v = self.view.cpu().numpy() if self.dtype != self.torch.bfloat16 else self.view.float().cpu().numpy()
+        assert not np.isnan(v).any(), "%s: NaN inside the view at %s" % (what, tuple(np.argwhere(np.isnan(v))[0]))
+        return v

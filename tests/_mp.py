@@ -361,3 +361,66 @@ def run_nmfk_golden(fixture, use_hip=False, timeout=600, extra=None, world=None)
     for rank, out, err in res:
         assert err is None, "rank %d failed:\n%s" % (rank, err)
     return [out for _, out, _ in sorted(res, key=lambda r: r[0])]
+
+
+def run_exact_rank(rank, world, port, grid, shape, q, exchange=None):
+    """One MU/Frobenius step of PyNMF's update() on a p_r x p_c grid with the exact operands of tests/_exact.py (fro_step): every
+    partial sum that crosses ranks is exact, so each rank's block of the new W must EQUAL the whole-matrix reference and its block of
+    the new H be within 3 ulps of the float64 quotient, element by element.  `exchange`: None (the Python choreography) or
+    'native-hosted' (the step sequenced inside the library, collectives handed to gloo)."""
+    try:
+        import torch.distributed as dist
+        from oracle import nmf_oracle as orc
+        from pydnmfk_amd.dist_comm import MPI_comm
+        from pydnmfk_amd.dist_nmf import nmf_algorithms_1D, nmf_algorithms_2D
+        from pydnmfk_amd.pyDNMF import PyNMF
+        from pydnmfk_amd.utils import determine_block_params, parse
+        from tests import _exact as ex
+
+        torch.set_num_threads(1)
+        torch.cuda.set_device(0)
+        os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        p_r, p_c = grid
+        m, n, k = shape
+        A, W0, H0, Wn, Hq = ex.fro_step(m, n, k)
+        comms = MPI_comm(None, p_r, p_c)
+        args = parse()
+        args.comm1, args.comm, args.p_r, args.p_c, args.k = comms.comm, comms, p_r, p_c, k
+        args.row_comm, args.col_comm = comms.cart_1d_row(), comms.cart_1d_column()
+        args.itr, args.init, args.verbose, args.prune = 1, "rand", False, False
+        args.norm, args.method, args.W_update = "fro", "mu", True
+        if exchange:
+            args.exchange = exchange
+        s, e = determine_block_params(rank, (p_r, p_c), A.shape).determine_block_index_range_asymm()
+        (w0, w1), (h0, h1) = orc.factor_ranges(rank, p_r, p_c, m, n)
+        nmf = PyNMF(A[s[0]:e[0] + 1, s[1]:e[1] + 1], factors=[W0[w0:w1], H0[:, h0:h1]], params=args, ops=None)
+        if nmf.topo == "2d":
+            W1, H1 = nmf_algorithms_2D(nmf.A_ij, nmf.W_ij, nmf.H_ij, params=nmf.params, ops=nmf._ops()).update()
+        else:
+            W1, H1 = nmf_algorithms_1D(nmf.A_ij, nmf.W_i, nmf.H_j, params=nmf.params, ops=nmf._ops()).update()
+        import pydnmfk_amd.engine as _eng
+        if exchange and not getattr(_eng, "_downgraded", False):         # the step really ran inside the library
+            assert getattr(args, "_native_comm", None) is not None and args._native_comm.steps == 1, getattr(args, "_native_comm", None)
+        ex.assert_ulp(W1.cpu().numpy(), Wn[w0:w1], 0, "rank %d W rows %d:%d (exact)" % (rank, w0, w1))
+        ex.assert_ulp(H1.cpu().numpy(), Hq[:, h0:h1], 3, "rank %d H columns %d:%d" % (rank, h0, h1))
+        q.put((rank, None))
+        dist.barrier()
+        dist.destroy_process_group()
+    except Exception:  # noqa: BLE001
+        q.put((rank, traceback.format_exc()))
+
+
+def run_exact(grid, shape, exchange=None, timeout=240):
+    world = grid[0] * grid[1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = free_port()
+    procs = [ctx.Process(target=run_exact_rank, args=(r, world, port, grid, shape, q, exchange)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=timeout) for _ in procs]
+    for p in procs:
+        p.join(timeout=60)
+    for rank, err in res:
+        assert err is None, "rank %d failed:\n%s" % (rank, err)
