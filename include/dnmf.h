@@ -300,6 +300,55 @@ int dnmf_hals_fro_fit_bf16a(const void* A, long m, long n, long lda, float* W, l
                             int w_update, int itr, int column_sweep, int batch, long a_stride, long w_stride, long h_stride,
                             double* sq_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- BCD: accelerated block coordinate descent for the Frobenius objective (method = 'bcd'; dist_nmf.py:940-1047 in 1D,
+ * :474-579 in 2D, pyDNMF.py:151-152).  One update() runs `itr` iterations of: a projected-gradient W step with the Lipschitz
+ * bound Lw = ||H H^T||_F, W divided by its column sums, the H step with Lh = ||W^T W||_F, the objective 1/2 ||A - W H||^2, then a
+ * Nesterov extrapolation of W and H or, when the objective did not decrease, a restart from the last accepted pair.  float32
+ * data and factors; rank 1 <= k <= DNMF_MAX_K.  Every scalar of the method (norms, Lipschitz bounds, t, the accept decision,
+ * the extrapolation weights) lives in a device STATE BLOCK of 16 doubles `st` that these calls read and write: no call
+ * returns a value to the host, so a host that sequences them (with its grid exchanges in between) never synchronises inside
+ * an iteration.  The big products are the entry points above: dnmf_gram_hht / dnmf_aht (H H^T, A H^T), dnmf_wta_gram
+ * (W^T A, W^T W), dnmf_resid_sqnorm_ws and dnmf_sqnorm.  The restart takes H H^T and A H^T of the last accepted H from a copy
+ * kept by dnmf_bcd_extrapolate (the products are deterministic: the copy is what recomputing them would give). */
+/* st from sq = {sum A^2, sum W0^2, sum H0^2} (device doubles, each summed over the ranks holding disjoint pieces):
+ * obj_old = sum A^2 / 2, t_old = 1, Lw = Lh = 1 (initWandH, dist_nmf.py:947-965, :485-499) */
+int dnmf_bcd_state_init(double* st, const double* sq, void* stream);
+/* X_old = X_m = X0 / sqrt(sum X0^2) * sqrt(sqrt(sum A^2)) for W (which = 0) or H (which = 1) (dist_nmf.py:958-961) */
+int dnmf_bcd_init_factor(const float* X0, long rows, long cols, long ld0, float* Xold, long ldo, float* Xm, long ldm, const double* st,
+                         int which, void* stream);
+/* L_old = L; L = ||G[:k, :k]||_F for the W bound (which = 0, G = H H^T, dist_nmf.py:998) or the H bound (which = 1, G = W^T W,
+ * :1011); G is the KP x KP Gram buffer */
+int dnmf_bcd_lipschitz(const float* G, int k, double* st, int which, void* stream);
+/* scratch of dnmf_bcd_update_w on m rows (its column-sum partials) */
+size_t dnmf_bcd_ws_bytes_w(long m, int k);
+/* W = max(0, Wm - (Wm G - AHT) / Lw) for G = H H^T (KP x KP), and s[k] = the column sums of the new W over these m rows
+ * (dist_nmf.py:999-1004; a host allreduces s when p_r != 1, :1006-1008).  W must not alias Wm.  ws >= dnmf_bcd_ws_bytes_w(m, k) */
+int dnmf_bcd_update_w(const float* Wm, long ldwm, const float* AHT, long ldaht, const float* G, long m, int k, const double* st, float* W,
+                      long ldw, float* s, void* ws, size_t ws_bytes, void* stream);
+/* W[i][c] /= s[c], no eps (dist_nmf.py:1009) */
+int dnmf_bcd_scale_cols(float* W, long m, int k, long ldw, const float* s, void* stream);
+/* H = max(0, Hm - (G Hm - WTA) / Lh) for G = W^T W (KP x KP) (dist_nmf.py:1012-1015).  H must not alias Hm. */
+int dnmf_bcd_update_h(const float* Hm, long ldhm, const float* WTA, long ldwta, const float* G, int k, long n, const double* st, float* H,
+                      long ldh, void* stream);
+/* the decision from sq[0] = sum (A - W H)^2 (global): obj = sq / 2, t = (1 + sqrt(1 + 4 t_old^2)) / 2; obj >= obj_old: restart,
+ * else accept with ww = min((t_old - 1) / t, sqrt(Lw_old / Lw)), wh likewise, t_old = t, obj_old = obj (dist_nmf.py:1024-1047).  One lane. */
+int dnmf_bcd_decide(double* st, const double* sq, void* stream);
+/* the pass after the decision, one launch: accepted -> Wm = W + ww (W - W_old), W_old = W, the same for H, and AHTk / Gk keep
+ * AHT / G (the products of the new H_old); restart -> Wm = W_old, Hm = H_old, AHT = AHTk, G = Gk (dist_nmf.py:1026-1047).
+ * W, H are left as they are (the last iterate is what update() returns, accepted or not).  AHT / AHTk are m x k, G / Gk KP x KP. */
+int dnmf_bcd_extrapolate(float* W, long ldw, float* Wold, long ldwo, float* Wm, long ldwm, long m, float* H, long ldh, float* Hold,
+                         long ldho, float* Hm, long ldhm, long n, int k, float* AHT, long ldaht, float* AHTk, long ldahtk, float* G,
+                         float* Gk, const double* st, void* stream);
+/* workspace of dnmf_bcd_fro_fit (0 for an unsupported shape) */
+size_t dnmf_bcd_ws_bytes(long m, long n, int k);
+/* A whole BCD fit on one rank (PyNMF.fit with method = 'bcd', pyDNMF.py:151-182): ONE update() of `itr` iterations, the clamp to
+ * eps iff (itr - 1) % 10 == 0 (the fit's single trip has i = itr - 1), normalize_features and sq_out = {sum (A - W H)^2, sum A^2},
+ * conventions of dnmf_mu_fro_fit.  w_update is ignored (the reference always updates W, dist_nmf.py:967); batch must be 1 (the
+ * strides are ignored).  The same primitives in the order a host choreography issues them: bit-identical to that sequence. */
+int dnmf_bcd_fro_fit(const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int w_update,
+                     int itr, int batch, long a_stride, long w_stride, long h_stride, double* sq_out, void* ws, size_t ws_bytes,
+                     void* stream);
+
 /* ---- The update path in float64.  The reference computes in the dtype of A_ij (pyDNMF.py:68; its own tests feed float64,
  * tests/test_dist_nmf_1d.py:14-20): these are the float64 twins of the primitives above, on the fp64 matrix cores
  * (v_mfma_f64_16x16x4_f64), one tile shape each (0.61 / 0.72 of the fp64 MFMA peak per MU/FRO / MU/KL step at 65536 x 4096, k = 64).  Everything is `double`

@@ -41,7 +41,7 @@ FLAGS = [
     ('init', str, 'rand', False, 'factor initialisation: rand / nnsvd'),
     ('itr', int, 5000, False, 'update iterations'),
     ('norm', str, 'kl', False, 'objective: kl / fro'),
-    ('method', str, 'mu', False, 'update rule: mu / hals'),
+    ('method', str, 'mu', False, 'update rule: mu / hals / bcd (bcd: Frobenius, float32 data)'),
     ('verbose', _flag, False, False, 'print the relative error of every fit'),
     ('results_path', str, 'results/', False, 'output directory'),
     ('checkpoint', _flag, False, False, 'keep a coarse NMFk checkpoint'),

@@ -10,8 +10,9 @@ module only sequences kernels and the grid exchanges, placed exactly where the r
 mpi4py (allreduce / allgather / Reduce_scatter), minus its barriers.  There is no CPU path: `ops`
 exists as a parameter so the choreography can be exercised by tests with a checker back end.
 
-Methods: 'mu' (Frobenius and KL) and 'hals' (Frobenius; dist_nmf.py:411-470, :873-934 -- the same contractions, with
-the multiply-divide replaced by column-sequential sweeps).  BCD (dist_nmf.py:474-579, :939-1047) is out of scope.
+Methods: 'mu' (Frobenius and KL), 'hals' (Frobenius; dist_nmf.py:411-470, :873-934 -- the same contractions, with
+the multiply-divide replaced by column-sequential sweeps) and 'bcd' (Frobenius; dist_nmf.py:474-579, :940-1047 -- accelerated
+block coordinate descent: `params.itr` iterations per update(), float32 data; csrc/dnmf_bcd.h).
 """
 import torch
 
@@ -63,7 +64,11 @@ class _Base:
             elif method == 'HALS':
                 self.FRO_HALS_update(self.W_update, clamp)
             elif method == 'BCD':
-                raise NotImplementedError("method 'bcd' is not part of the MI355X engine (mu / hals)")
+                self.FRO_BCD_update(self.W_update, itr=int(self.params.itr))
+                if clamp:                                                      # pyDNMF.py:155-157 after the fit's one trip
+                    W, H = self._bcd_factors()
+                    self.ops.clamp_min(H, self.eps)
+                    self.ops.clamp_min(W, self.eps)
             else:
                 raise Exception('Not a valid method: Choose (mu/hals/bcd)')    # dist_nmf.py:84,652
         elif norm == 'KL':
@@ -74,6 +79,50 @@ class _Base:
         else:
             raise Exception('Not a valid norm: Choose (fro/kl)')               # dist_nmf.py:91,659
 
+
+    # ---- BCD / Frobenius (dist_nmf.py:940-1047 in 1D, :474-579 in 2D).  The grid-specific pieces are the `_bcd_*` hooks of each
+    # class: the exchanges sit exactly where the reference allreduces / gathers.  Every scalar of the method stays in the device state
+    # block `st` (csrc/dnmf_bcd.h): no value comes back to the host inside the loop, the restart decision included.
+    def FRO_BCD_update(self, W_update=True, itr=1000):
+        """`itr` BCD iterations on this rank's blocks; W and H (updated in place) end as the LAST iterate, accepted or not (the
+        reference returns self.W_i / self.H_j, which the restart does not reset).  `W_update` is ignored: the reference always
+        updates W (dist_nmf.py:967, :499)."""
+        ops, A, k = self.ops, self.A_ij, self.k
+        W, H = self._bcd_factors()
+        if not hasattr(ops, "bcd_update_w") or getattr(ops, "name", "") in ("hip-bf16x6", "hip-f64") or \
+                A.dtype not in (torch.float32,) or W.dtype != torch.float32:
+            raise NotImplementedError("method 'bcd' runs on float32 data with the product's fp32 operator set; not provided for %s data "
+                                      "with the '%s' operator set (float64, bf16-stored A and --gemm bf16x6 are out of scope)"
+                                      % (str(A.dtype).replace("torch.", ""), getattr(ops, "name", "?")))
+        kp = _kp(k)
+        st = ops.bcd_state(A)
+        sq = torch.cat([ops.sqnorm(A), ops.sqnorm(W), ops.sqnorm(H)])          # initWandH :947-957
+        self._bcd_exchange_init(sq)
+        ops.bcd_state_init(st, sq)
+        Wo, Wm, Ho, Hm = (torch.empty_like(W), torch.empty_like(W), torch.empty_like(H), torch.empty_like(H))
+        ops.bcd_init_factor(W, Wo, Wm, st, 0)                                  # :958-961
+        ops.bcd_init_factor(H, Ho, Hm, st, 1)
+        G = ops.zeros((kp, kp), A)
+        AH = ops.empty(tuple(W.shape), A)
+        self._bcd_hht(Ho, G)                                                   # :962
+        self._bcd_aht(Ho, AH)                                                  # :963
+        Gk, AHk = G.clone(), AH.clone()                                        # the products of H_old, for a restart
+        Gw = ops.zeros((kp, kp), A)
+        s = ops.zeros((k,), A)
+        for _ in range(int(itr)):
+            ops.bcd_lipschitz(G, k, st, 0)                                     # :998
+            ops.bcd_update_w(Wm, AH, G, st, W, s)                              # :999-1004
+            self._bcd_colsum_exchange(s)                                       # :1005-1008
+            ops.bcd_scale_cols(W, s)                                           # :1009
+            AtW = self._bcd_wta(W, Gw)                                         # :1010, :1013
+            ops.bcd_lipschitz(Gw, k, st, 1)                                    # :1011
+            ops.bcd_update_h(Hm, AtW, Gw, st, H)                               # :1012-1015
+            self._bcd_hht(H, G)                                                # :1016
+            self._bcd_aht(H, AH)                                               # :1017
+            r = self._bcd_resid(W, H)                                          # :1018-1019
+            ops.bcd_decide(st, r)                                              # :1024-1047
+            ops.bcd_extrapolate(W, Wo, Wm, H, Ho, Hm, AH, AHk, G, Gk, st)
+        self._bcd_st = st                                                      # (tests read the state block)
 
     def _hals_w_sweep(self, W, AH, G, allreduce_norm):
         """Column-sequential W sweep (dist_nmf.py:884-891 / :428-434).  Without a cross-rank norm it is one library
@@ -150,6 +199,49 @@ class nmf_algorithms_1D(_Base):
         nc.step_1d(self.norm, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, clamp)
         nc.steps += 1
         return True
+
+    # ---- BCD hooks (dist_nmf.py:940-1047): W_i rows are disjoint across ranks iff p_r != 1, H_j columns iff p_c != 1
+    def _bcd_factors(self):
+        return self.W_i, self.H_j
+
+    def _bcd_exchange_init(self, sq):
+        """globalSqNorm (:940-950): ||A||^2 always over the grid, ||W0||^2 iff p_r != 1, ||H0||^2 iff p_c != 1"""
+        if self.p == 1:
+            return
+        self.comm1.allreduce_(sq[0:1])
+        if self.p_r != 1:
+            self.comm1.allreduce_(sq[1:2])
+        if self.p_c != 1:
+            self.comm1.allreduce_(sq[2:3])
+
+    def _bcd_hht(self, H, G):
+        self.ops.gram_hht(H, G)                                    # global_gram(H.T, p=self.p_c) :962, :1016
+        if self.p_c != 1:
+            self.comm1.allreduce_(G)
+
+    def _bcd_aht(self, H, out):
+        self.ops.aht(self.A_ij, H, out)                            # global_mm(A, H.T, p=self.p_c) :963, :1017
+        if self.p_c != 1:
+            self.comm1.allreduce_(out)
+
+    def _bcd_colsum_exchange(self, s):
+        if self.p_r != 1:                                          # :1006-1008
+            self.comm1.allreduce_(s)
+
+    def _bcd_wta(self, W, G):
+        k, n_l = self.k, self.A_ij.shape[1]
+        AtW = _buf(("bcd_atw", k, n_l), k * n_l, self.A_ij)[: k * n_l].view(k, n_l)
+        self.ops.wta_gram(self.A_ij, W, AtW, G)                    # global_gram(W, p=p_r) :1010, global_mm(W.T, A, p=p_r) :1013
+        if self.p_r != 1:
+            self.comm1.allreduce_(G)
+            self.comm1.allreduce_(AtW)
+        return AtW
+
+    def _bcd_resid(self, W, H):
+        r = self.ops.resid_sqnorm(self.A_ij, W, H)                 # globalSqNorm(A - W H) :1018, always over the grid
+        if self.p != 1:
+            self.comm1.allreduce_(r)
+        return r
 
     # ---- Frobenius (dist_nmf.py:716-771)
     def Fro_MU_update(self, W_update=True, clamp=False):
@@ -444,6 +536,45 @@ class nmf_algorithms_2D(_Base):
         for q in range(p):
             product(q * nh, (q + 1) * nh, buf[q * k * nh: (q + 1) * k * nh].view(k, nh))
         return self.cartesian1d_row.reduce_scatter_rows(buf.view(p * k, nh), [k] * p)
+
+    # ---- BCD hooks (dist_nmf.py:474-579): every reduction is over the whole grid (comm1); A H^T and W^T A as AH_glob / ATW_glob
+    def _bcd_factors(self):
+        return self.W_ij, self.H_ij
+
+    def _bcd_exchange_init(self, sq):
+        self.comm1.allreduce_(sq)                                  # globalSqNorm(comm1, .) :478-484, :487-491
+
+    def _bcd_hht(self, H, G):
+        self.ops.gram_hht(H, G)                                    # global_gram(H_ij.T) :496, :548
+        self.comm1.allreduce_(G)
+
+    def _bcd_gather_h(self, H):
+        blocks = self.cartesian1d_row.allgather_blocks(H, [(self.k, c) for c in self.h_counts])
+        return blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
+
+    def _bcd_aht(self, H, out):
+        """AH_glob(H) (:175-205): allgather of the H slices over the row group, A H_j^T, reduce-scatter over the column group"""
+        m_l = self.A_ij.shape[0]
+        V = _buf(("V", m_l, self.k), m_l * self.k, self.A_ij)[: m_l * self.k].view(m_l, self.k)
+        self.ops.aht(self.A_ij, self._bcd_gather_h(H), V)
+        out.copy_(self._scatter_to_W(V))
+
+    def _bcd_colsum_exchange(self, s):
+        self.comm1.allreduce_(s)                                   # :537-538
+
+    def _bcd_wta(self, W, G):
+        """global_gram(W_ij) (:541) and ATW_glob (:545): allgather of W over the column group, W_i^T A, reduce-scatter"""
+        ops, A = self.ops, self.A_ij
+        ops.gram_wtw(W, G)
+        self.comm1.allreduce_(G)
+        W_i = self.gather_W()
+        return self._product_scattered_to_H(lambda c0, c1, out: ops.wta(A[:, c0:c1], W_i, out)).contiguous()
+
+    def _bcd_resid(self, W, H):
+        W_i, H_j = self.gather_W(), self._bcd_gather_h(H)         # gather_W_H :550
+        r = self.ops.resid_sqnorm(self.A_ij, W_i, H_j)             # globalSqNorm(comm1, A - W_i H_j) :551
+        self.comm1.allreduce_(r)
+        return r
 
     # ---- Frobenius (dist_nmf.py:207-263)
     def Fro_MU_update(self, W_update=True, clamp=False):

@@ -424,7 +424,73 @@ class HipOps:
                                   W.shape[1], out[0].data_ptr(), out[1].data_ptr(), _stream()))
         return out[0], out[1]
 
-    # ---- whole fits (csrc/dnmf_fit.hip)
+    # ---- BCD primitives (csrc/dnmf_bcd.hip; the choreography is dist_nmf._Base._bcd).  `st` is the method's float64 state block
+    # (16 device doubles): every scalar of an iteration stays in it, nothing here returns a value to the host.
+    def bcd_state(self, like):
+        return torch.zeros(16, dtype=torch.float64, device=like.device)
+
+    @staticmethod
+    def _req_d(t, name, numel):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() >= numel):
+            raise TypeError("%s: expected a contiguous float64 CUDA tensor of at least %d elements" % (name, numel))
+        _same_device(t, name)
+
+    def bcd_state_init(self, st, sq):
+        self._req_d(st, "st", 16); self._req_d(sq, "sq", 3)
+        check(lib.dnmf_bcd_state_init(st.data_ptr(), sq.data_ptr(), _stream()))
+
+    def bcd_init_factor(self, X0, Xold, Xm, st, which):
+        _req(X0, "X0"); _req(Xold, "X_old"); _req(Xm, "X_m"); self._req_d(st, "st", 16)
+        r, c = X0.shape
+        if Xold.shape != X0.shape or Xm.shape != X0.shape:
+            raise ValueError("bcd_init_factor: shapes differ")
+        check(lib.dnmf_bcd_init_factor(X0.data_ptr(), r, c, _ld(X0), Xold.data_ptr(), _ld(Xold), Xm.data_ptr(), _ld(Xm), st.data_ptr(),
+                                       int(which), _stream()))
+
+    def bcd_lipschitz(self, G, k, st, which):
+        _req_g(G, k); self._req_d(st, "st", 16)
+        check(lib.dnmf_bcd_lipschitz(G.data_ptr(), int(k), st.data_ptr(), int(which), _stream()))
+
+    def bcd_update_w(self, Wm, AH, G, st, W, s):
+        _req(Wm, "Wm"); _req(AH, "AH"); _req(W, "W"); _req(s, "s", 1); self._req_d(st, "st", 16)
+        m, k = W.shape
+        _req_g(G, k)
+        if Wm.shape != W.shape or AH.shape != W.shape or s.numel() < k:
+            raise ValueError("bcd_update_w: shapes W %s, Wm %s, AH %s, s %s" % (tuple(W.shape), tuple(Wm.shape), tuple(AH.shape), tuple(s.shape)))
+        ws = _scratch(lib.dnmf_bcd_ws_bytes_w(int(m), int(k)), W.device)
+        check(lib.dnmf_bcd_update_w(Wm.data_ptr(), _ld(Wm), AH.data_ptr(), _ld(AH), G.data_ptr(), m, k, st.data_ptr(), W.data_ptr(), _ld(W),
+                                    s.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+
+    def bcd_scale_cols(self, W, s):
+        _req(W, "W"); _req(s, "s", 1)
+        check(lib.dnmf_bcd_scale_cols(W.data_ptr(), W.shape[0], W.shape[1], _ld(W), s.data_ptr(), _stream()))
+
+    def bcd_update_h(self, Hm, AtW, G, st, H):
+        _req(Hm, "Hm"); _req(AtW, "AtW"); _req(H, "H"); self._req_d(st, "st", 16)
+        k, n = H.shape
+        _req_g(G, k)
+        if Hm.shape != H.shape or AtW.shape != H.shape:
+            raise ValueError("bcd_update_h: shapes H %s, Hm %s, AtW %s" % (tuple(H.shape), tuple(Hm.shape), tuple(AtW.shape)))
+        check(lib.dnmf_bcd_update_h(Hm.data_ptr(), _ld(Hm), AtW.data_ptr(), _ld(AtW), G.data_ptr(), k, n, st.data_ptr(), H.data_ptr(), _ld(H),
+                                    _stream()))
+
+    def bcd_decide(self, st, sq):
+        self._req_d(st, "st", 16); self._req_d(sq, "sq", 1)
+        check(lib.dnmf_bcd_decide(st.data_ptr(), sq.data_ptr(), _stream()))
+
+    def bcd_extrapolate(self, W, Wold, Wm, H, Hold, Hm, AH, AHk, G, Gk, st):
+        for t, nm in ((W, "W"), (Wold, "W_old"), (Wm, "Wm"), (H, "H"), (Hold, "H_old"), (Hm, "Hm"), (AH, "AH"), (AHk, "AH kept")):
+            _req(t, nm)
+        m, k = W.shape
+        n = H.shape[1]
+        _req_g(G, k); _req_g(Gk, k); self._req_d(st, "st", 16)
+        if not (Wold.shape == Wm.shape == AH.shape == AHk.shape == W.shape and Hold.shape == Hm.shape == H.shape and H.shape[0] == k):
+            raise ValueError("bcd_extrapolate: shapes do not match")
+        check(lib.dnmf_bcd_extrapolate(W.data_ptr(), _ld(W), Wold.data_ptr(), _ld(Wold), Wm.data_ptr(), _ld(Wm), m, H.data_ptr(), _ld(H),
+                                       Hold.data_ptr(), _ld(Hold), Hm.data_ptr(), _ld(Hm), n, k, AH.data_ptr(), _ld(AH), AHk.data_ptr(),
+                                       _ld(AHk), G.data_ptr(), Gk.data_ptr(), st.data_ptr(), _stream()))
+
+    # ---- whole fits (csrc/dnmf_fit.hip, csrc/dnmf_bcd.hip)
     def fit(self, method, norm, A, W, H, eps, w_update, itr, column_sweep=False):
         """`itr` update steps (clamp after the steps i % 10 == 0), normalize_features and the squared norms of relative_err in
         ONE library call (dnmf_{mu_fro,mu_kl,hals_fro}_fit; pyDNMF.py:138-182 on one rank).  A, W, H are matrices -- one
@@ -441,6 +507,8 @@ class HipOps:
         k = W3.shape[2]
         if W3.shape != (B, m, k) or H3.shape != (B, k, n):
             raise ValueError("fit: shapes A %s, W %s, H %s do not match" % (tuple(A3.shape), tuple(W3.shape), tuple(H3.shape)))
+        if (norm, method) == ("fro", "bcd"):
+            return self._bcd_fit(A3, W3, H3, eps, w_update, itr, sfx, batched)
         if (norm, method) == ("kl", "mu"):
             if sfx:
                 raise TypeError("fit: KL needs float32 data")
@@ -462,6 +530,27 @@ class HipOps:
         check(fn(A3.data_ptr(), m, n, _ld(A3[0]), W3.data_ptr(), _ld(W3[0]), H3.data_ptr(), _ld(H3[0]), k, float(eps),
                  int(bool(w_update)), int(itr), *extra, int(B), A3.stride(0), W3.stride(0), H3.stride(0), sq.data_ptr(),
                  ws.data_ptr(), ws.numel(), _stream()))
+        return sq
+
+    def _bcd_fit(self, A3, W3, H3, eps, w_update, itr, sfx, batched):
+        """method 'bcd' (dnmf_bcd_fro_fit): float32 data, one problem per call -- a stack is fitted one problem after another
+        (no batched BCD kernels; each problem is the single fit it would be on its own)."""
+        if sfx:
+            raise NotImplementedError("method 'bcd' with bfloat16-stored A is not provided (float32 data only)")
+        B, m, n = A3.shape
+        k = W3.shape[2]
+        nbytes = lib.dnmf_bcd_ws_bytes(int(m), int(n), int(k))
+        if nbytes == 0:
+            raise ValueError("fit: bad problem shape m=%d n=%d k=%d for method 'bcd'" % (m, n, k))
+        ws = _scratch(nbytes, A3.device)
+        sq = torch.empty(B, 2, dtype=torch.float64, device=A3.device)
+        for b in range(B):
+            A, W, H = A3[b], W3[b], H3[b]
+            for t, name in ((A, "A"), (W, "W"), (H, "H")):
+                if t.stride(1) != 1 and t.numel():
+                    raise ValueError("fit: %s must have unit inner stride" % name)
+            check(lib.dnmf_bcd_fro_fit(A.data_ptr(), m, n, _ld(A), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), k, float(eps),
+                                       int(bool(w_update)), int(itr), 1, 0, 0, 0, sq[b].data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
         return sq
 
     # ---- allocation helpers used by the choreography

@@ -13,7 +13,8 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
     cores, engine.HipOpsF64: correctness first, one plain tile shape); `params.precision = 'bfloat16'` (or a
     bfloat16 tensor) keeps the data block in HBM as bf16 -- storage only, Frobenius mu / hals -- with W, H and every
     product in float32: the fit equals the float32 fit of the bf16-rounded data (BASELINE config 5);
-  * method is 'mu' (fro / kl) or 'hals' (fro); 'bcd' is not provided; init is 'rand' or 'nnsvd' (1D grids);
+  * method is 'mu' (fro / kl), 'hals' (fro) or 'bcd' (fro; float32 data with the fp32 operator set -- float64, bf16-stored A and
+    --gemm bf16x6 raise NotImplementedError); init is 'rand' or 'nnsvd' (1D grids);
   * `prune=True` (the reference's default when the attribute is absent) drops all-zero rows / columns before the
     iterations and scatters the factors back afterwards.  numpy callers get float64 factors back in that case, exactly
     as from the reference (its unprune scatters into np.zeros, utils.py:195,198); tensor callers keep float32 on the GPU.
@@ -52,7 +53,7 @@ def storage_dtype(A_ij, params):
 
 
 _MASKS = ("row_zero_idx_x", "col_zero_idx_x", "row_zero_idx_w", "col_zero_idx_h")
-_NATIVE_FITS = (("mu", "fro"), ("mu", "kl"), ("hals", "fro"))
+_NATIVE_FITS = (("mu", "fro"), ("mu", "kl"), ("hals", "fro"), ("bcd", "fro"))
 
 
 class PyNMF:
@@ -233,8 +234,8 @@ class PyNMF:
                 delattr(self, name)
 
     def _fit_once(self):
-        if self.method.lower() not in ('mu', 'hals'):
-            raise NotImplementedError("method '%s' is not part of the MI355X engine (mu / hals)" % self.method)
+        if self.method.lower() not in ('mu', 'hals', 'bcd'):
+            raise NotImplementedError("method '%s' is not part of the MI355X engine (mu / hals / bcd)" % self.method)
         ops = self._ops()
         if self._whole_fit_ok(ops):
             # one rank: the whole loop below -- steps, clamps, normalisation, both squared norms -- is ONE library call
@@ -242,7 +243,9 @@ class PyNMF:
             sq = ops.fit(self.method, self.norm, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr,
                          column_sweep=(getattr(self.params, "hals_sweep", None) == "columns"))
             return self._finish(sq[0])
-        for i in range(self.itr):
+        # bcd: ONE trip with i = itr - 1 (pyDNMF.py:152) -- its update() runs all itr iterations (dist_nmf.py:83, params.itr)
+        trips = range(self.itr - 1, self.itr) if self.method.lower() == 'bcd' else range(self.itr)
+        for i in trips:
             clamp = (i % 10 == 0)                                   # :155 / :170, fused into the step
             if self.topo == '2d':
                 self.W_ij, self.H_ij = nmf_algorithms_2D(self.A_ij, self.W_ij, self.H_ij, params=self.params,
@@ -264,6 +267,7 @@ class PyNMF:
         return (self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") in ("hip", "hip-f64") and hasattr(ops, "fit")
                 and not (getattr(ops, "name", "") == "hip-f64" and self.k > 128)
                 and (str(self.method).lower(), str(self.norm).lower()) in _NATIVE_FITS
+                and not (str(self.method).lower() == "bcd" and (getattr(ops, "name", "") != "hip" or self.a_dtype != torch.float32))
                 and getattr(self.params, "fit_loop", None) != "python"
                 and not getattr(self.params, "native_always", False))
 
@@ -323,7 +327,8 @@ class PyNMF:
                     and f.A_ij.dtype == f0.A_ij.dtype and f.A_ij.device == f0.A_ij.device and f.W_i.shape == f0.W_i.shape
                     and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k) ==
                     (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k))
-        if len(fits) < 2 or not all(same(f) for f in fits):
+        # (no batched BCD fits: each one is the single-problem library call, one after another)
+        if len(fits) < 2 or str(f0.method).lower() == 'bcd' or not all(same(f) for f in fits):
             return [f.fit() for f in fits]
         if f0.method.lower() not in ('mu', 'hals'):
             raise NotImplementedError("method '%s' is not part of the MI355X engine (mu / hals)" % f0.method)
