@@ -339,12 +339,18 @@ int dnmf_bcd_decide(double* st, const double* sq, void* stream);
 int dnmf_bcd_extrapolate(float* W, long ldw, float* Wold, long ldwo, float* Wm, long ldwm, long m, float* H, long ldh, float* Hold,
                          long ldho, float* Hm, long ldhm, long n, int k, float* AHT, long ldaht, float* AHTk, long ldahtk, float* G,
                          float* Gk, const double* st, void* stream);
-/* workspace of dnmf_bcd_fro_fit (0 for an unsupported shape) */
+/* workspace of dnmf_bcd_fro_fit for one problem (0 for an unsupported shape) */
 size_t dnmf_bcd_ws_bytes(long m, long n, int k);
+/* workspace of dnmf_bcd_fro_fit for `batch` problems: batch slices of dnmf_bcd_ws_bytes(m, n, k), slice z = problem z (0 for an
+ * unsupported shape or batch < 1) */
+size_t dnmf_bcd_ws_bytes_fit(long m, long n, int k, int batch);
 /* A whole BCD fit on one rank (PyNMF.fit with method = 'bcd', pyDNMF.py:151-182): ONE update() of `itr` iterations, the clamp to
  * eps iff (itr - 1) % 10 == 0 (the fit's single trip has i = itr - 1), normalize_features and sq_out = {sum (A - W H)^2, sum A^2},
- * conventions of dnmf_mu_fro_fit.  w_update is ignored (the reference always updates W, dist_nmf.py:967); batch must be 1 (the
- * strides are ignored).  The same primitives in the order a host choreography issues them: bit-identical to that sequence. */
+ * conventions of dnmf_mu_fro_fit.  w_update is ignored (the reference always updates W, dist_nmf.py:967).  batch >= 1 same-shape
+ * problems, a_stride / w_stride / h_stride elements apart (ignored when batch == 1), sq_out[batch][2], ws >=
+ * dnmf_bcd_ws_bytes_fit(m, n, k, batch): every launch covers all problems, each problem keeps its own state block, so the problems
+ * of a batch accept or restart independently, and the results are bit-identical to fitting them one by one.  The same primitives in
+ * the order a host choreography issues them: bit-identical to that sequence. */
 int dnmf_bcd_fro_fit(const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int w_update,
                      int itr, int batch, long a_stride, long w_stride, long h_stride, double* sq_out, void* ws, size_t ws_bytes,
                      void* stream);

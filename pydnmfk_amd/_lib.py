@@ -170,10 +170,11 @@ SIGNATURES["dnmf_bcd_extrapolate"] = [c_void_p, c_long, c_void_p, c_long, c_void
                                       c_void_p, c_long, c_long, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
                                       c_void_p]
 SIGNATURES["dnmf_bcd_ws_bytes"] = [c_long, c_long, c_int]
+SIGNATURES["dnmf_bcd_ws_bytes_fit"] = [c_long, c_long, c_int, c_int]
 SIGNATURES["dnmf_bcd_fro_fit"] = SIGNATURES["dnmf_mu_fro_fit"]
 _RESTYPES = {"dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
              "dnmf_ws_bytes_1d": c_size_t, "dnmf_ws_bytes_hblocks": c_size_t, "dnmf_ws_bytes_2d": c_size_t,
-             "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t}
+             "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t, "dnmf_bcd_ws_bytes_fit": c_size_t}
 
 
 def load():

@@ -32,6 +32,11 @@ constexpr int BCD_ROWS = 64;      // rows (W step) / columns (H step) of a workg
 constexpr int BCD_CG = 16;        // output columns of one wave
 constexpr int BCD_LT = 32;        // contraction slab staged in LDS
 
+// Batched launches (csrc/dnmf_common.h): every kernel below takes the BatchTab and moves its pointers into its problem first thing.
+// The move is guarded by `bt.n` (0 outside a batched fit, where it would add zero anyway): the family search is some 25 scalar
+// instructions per pointer on the CU's one scalar unit, and the element-wise kernels here run workgroups of a few hundred cycles --
+// unguarded, bcd_extrapolate_kernel of a single 65536 x 16 fit went from 9.4 to 15.6 us (rocprofv3 --kernel-trace --stats).
+
 // ---- the projected-gradient step (dist_nmf.py:999-1003 / :1011-1015, 2D :531-535 / :543-547):
 //   W side (HS = false): W = max(0, Wm - (Wm G - P) / L),  Wm, P, W [R x k], G = H H^T,  L = ||G||_F
 //   H side (HS = true):  H = max(0, Hm - (G Hm - P) / L),  Hm, P, H [k x R], G = W^T W
@@ -46,8 +51,9 @@ template <bool HS>
 __global__ __launch_bounds__(256) void bcd_pg_kernel(const float* __restrict__ Xm, long ldx, const float* __restrict__ P, long ldp,
                                                      const float* __restrict__ G, int ldg, long R, int k,
                                                      const double* __restrict__ st, int lslot, float* __restrict__ X, long ldo,
-                                                     float* __restrict__ part) {
+                                                     float* __restrict__ part, BatchTab bt) {
 #pragma clang fp contract(off)
+    if (bt.n) { REBASE(Xm); REBASE(P); REBASE(G); REBASE(st); REBASE(X); REBASE(part); }      // (part == null falls in no family: stays null)
     __shared__ float sx[BCD_ROWS][BCD_LT + 1];
     const int lane = threadIdx.x & 63;
     const int cg = __builtin_amdgcn_readfirstlane((int)blockIdx.y * 4 + (int)(threadIdx.x >> 6));
@@ -122,7 +128,8 @@ __global__ __launch_bounds__(256) void bcd_pg_kernel(const float* __restrict__ X
 }
 
 // s[c] = sum over the nb workgroup partials of column c, in float64 and a fixed order (one workgroup per column)
-__global__ __launch_bounds__(256) void bcd_colsum_kernel(const float* __restrict__ part, long nb, int k, float* __restrict__ s) {
+__global__ __launch_bounds__(256) void bcd_colsum_kernel(const float* __restrict__ part, long nb, int k, float* __restrict__ s, BatchTab bt) {
+    if (bt.n) { REBASE(part); REBASE(s); }
     __shared__ double red[256];
     const int c = blockIdx.x;
     double v = 0.0;
@@ -137,7 +144,9 @@ __global__ __launch_bounds__(256) void bcd_colsum_kernel(const float* __restrict
 }
 
 // W[i][c] /= s[c] (dist_nmf.py:1005-1009, 2D :537-540): no eps -- a zero column sum gives inf / NaN, as in the reference
-__global__ __launch_bounds__(256) void bcd_scale_cols_kernel(float* __restrict__ W, long m, int k, long ldw, const float* __restrict__ s) {
+__global__ __launch_bounds__(256) void bcd_scale_cols_kernel(float* __restrict__ W, long m, int k, long ldw, const float* __restrict__ s,
+                                                             BatchTab bt) {
+    if (bt.n) { REBASE(W); REBASE(s); }
     const long total = m * (long)k;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const long i = e / k;
@@ -147,7 +156,9 @@ __global__ __launch_bounds__(256) void bcd_scale_cols_kernel(float* __restrict__
 }
 
 // L_old = L; L = ||G[:k, :k]||_F (np.linalg.norm of the float32 Gram: the value is kept rounded to float32).  One workgroup.
-__global__ __launch_bounds__(256) void bcd_lipschitz_kernel(const float* __restrict__ G, int ldg, int k, double* __restrict__ st, int slot) {
+__global__ __launch_bounds__(256) void bcd_lipschitz_kernel(const float* __restrict__ G, int ldg, int k, double* __restrict__ st, int slot,
+                                                            BatchTab bt) {
+    if (bt.n) { REBASE(G); REBASE(st); }
     __shared__ double red[256];
     double v = 0.0;
     for (int e = threadIdx.x; e < k * k; e += 256) {
@@ -167,7 +178,8 @@ __global__ __launch_bounds__(256) void bcd_lipschitz_kernel(const float* __restr
 }
 
 // state init (initWandH, dist_nmf.py:947-965 / 2D :485-499): from sq = {sum A^2, sum W0^2, sum H0^2}
-__global__ void bcd_state_init_kernel(double* __restrict__ st, const double* __restrict__ sq) {
+__global__ void bcd_state_init_kernel(double* __restrict__ st, const double* __restrict__ sq, BatchTab bt) {
+    if (bt.n) { REBASE(st); REBASE(sq); }
     if (threadIdx.x != 0) return;
     for (int i = 0; i < BCD_NSLOTS; ++i) st[i] = 0.0;
     st[BCD_XN] = sq[0];
@@ -181,8 +193,9 @@ __global__ void bcd_state_init_kernel(double* __restrict__ st, const double* __r
 
 // X_old = X_m = X0 / sqrt(sum X0^2) * sqrt(sqrt(Xnorm)), in float32 as numpy evaluates it (two roundings)
 __global__ __launch_bounds__(256) void bcd_init_factor_kernel(const float* __restrict__ X0, long rows, long cols, long ld0, float* __restrict__ Xo,
-                                                              long ldo, float* __restrict__ Xm, long ldm, const double* __restrict__ st, int slot) {
+                                                              long ldo, float* __restrict__ Xm, long ldm, const double* __restrict__ st, int slot, BatchTab bt) {
 #pragma clang fp contract(off)
+    if (bt.n) { REBASE(X0); REBASE(Xo); REBASE(Xm); REBASE(st); }
     const float a = (float)sqrt(st[slot]);
     const float b = (float)sqrt(sqrt(st[BCD_XN]));
     const long total = rows * cols;
@@ -196,8 +209,9 @@ __global__ __launch_bounds__(256) void bcd_init_factor_kernel(const float* __res
 
 // the decision (dist_nmf.py:1024-1047 / 2D :556-579): obj = sq / 2; t = (1 + sqrt(1 + 4 t_old^2)) / 2; obj >= obj_old: restart;
 // else w = (t_old - 1) / t, ww = min(w, sqrt(Lw_old / Lw)), wh = min(w, sqrt(Lh_old / Lh)), t_old = t, obj_old = obj.  One lane.
-__global__ void bcd_decide_kernel(double* __restrict__ st, const double* __restrict__ sq) {
+__global__ void bcd_decide_kernel(double* __restrict__ st, const double* __restrict__ sq, BatchTab bt) {
 #pragma clang fp contract(off)
+    if (bt.n) { REBASE(st); REBASE(sq); }
     if (threadIdx.x != 0) return;
     const double obj = 0.5 * sq[0];
     const double t_old = st[BCD_T_OLD];
@@ -227,10 +241,14 @@ __global__ void bcd_decide_kernel(double* __restrict__ st, const double* __restr
 struct BcdJob { float* x; float* o; float* p; long rows, cols, ldx, ldo, ldp; int kind, wslot; };
 struct BcdJobs { BcdJob j[4]; int n; };
 
-__global__ __launch_bounds__(256) void bcd_extrapolate_kernel(BcdJobs jobs, const double* __restrict__ st) {
+// Batched: blockIdx.y stays the job, blockIdx.z is the problem; each job's pointers are moved into the problem here (they
+// arrive inside the struct), as rebase_args does for NtArgs in dnmf_nt.h.
+__global__ __launch_bounds__(256) void bcd_extrapolate_kernel(BcdJobs jobs, const double* __restrict__ st, BatchTab bt) {
 #pragma clang fp contract(off)
     if ((int)blockIdx.y >= jobs.n) return;
-    const BcdJob J = jobs.j[blockIdx.y];
+    if (bt.n) { REBASE(st); }
+    BcdJob J = jobs.j[blockIdx.y];
+    if (bt.n) { rebase(J.x, bt); rebase(J.o, bt); rebase(J.p, bt); }             // (p == null in the kind-1 jobs: no family, stays null)
     const bool acc = st[BCD_ACC] != 0.0;
     const float w = J.kind == 0 ? (float)st[J.wslot] : 0.f;
     const long total = J.rows * J.cols;

@@ -8,7 +8,8 @@ namespace {
 
 inline unsigned ew_grid(long total) { return (unsigned)std::max<long>(1, std::min<long>(cdiv(total, 256), 256L * 32)); }
 
-// per-fit workspace: [ step workspace (dnmf_ws_bytes) | W_old | Wm | AHT | AHT kept | H_old | Hm | W^T A | G_h | G_h kept | G_w |
+// per-problem workspace slice (a batched fit holds `batch` of them, slice z = problem z):
+//                    [ step workspace (dnmf_ws_bytes) | W_old | Wm | AHT | AHT kept | H_old | Hm | W^T A | G_h | G_h kept | G_w |
 //                      s (KP floats) | column-sum partials | state block | squared norms ]
 // m x k buffers have ld = k, k x n buffers ld = n, Gram buffers are KP x KP
 struct BcdWs { size_t step, wo, wm, aht, ahtk, ho, hm, wta, gh, ghk, gw, s, part, st, sq, total; };
@@ -42,8 +43,8 @@ int pg_launch(bool hs, const float* Xm, long ldx, const float* P, long ldp, cons
               long ldo, float* part, hipStream_t s) {
     const dim3 grid((unsigned)cdiv(R, BCD_ROWS), (unsigned)cdiv(cdiv(k, BCD_CG), 4));
     const int kp = dnmf_kp(k);
-    if (hs) hipLaunchKernelGGL(bcd_pg_kernel<true>, grid, dim3(256), 0, s, Xm, ldx, P, ldp, G, kp, R, k, st, (int)BCD_LH, X, ldo, part);
-    else hipLaunchKernelGGL(bcd_pg_kernel<false>, grid, dim3(256), 0, s, Xm, ldx, P, ldp, G, kp, R, k, st, (int)BCD_LW, X, ldo, part);
+    if (hs) DNMF_LAUNCH(bcd_pg_kernel<true>, grid, dim3(256), 0, s, Xm, ldx, P, ldp, G, kp, R, k, st, (int)BCD_LH, X, ldo, part);
+    else DNMF_LAUNCH(bcd_pg_kernel<false>, grid, dim3(256), 0, s, Xm, ldx, P, ldp, G, kp, R, k, st, (int)BCD_LW, X, ldo, part);
     return check_launch(hs ? "bcd_update_h" : "bcd_update_w");
 }
 
@@ -61,9 +62,14 @@ size_t dnmf_bcd_ws_bytes(long m, long n, int k) {
     return bcd_layout(m, n, k).total;
 }
 
+size_t dnmf_bcd_ws_bytes_fit(long m, long n, int k, int batch) {
+    if (batch < 1) return 0;
+    return (size_t)batch * dnmf_bcd_ws_bytes(m, n, k);
+}
+
 int dnmf_bcd_state_init(double* st, const double* sq, void* stream) {
     REQUIRE(st && sq, "bcd_state_init: null pointer");
-    hipLaunchKernelGGL(bcd_state_init_kernel, dim3(1), dim3(64), 0, S(stream), st, sq);
+    DNMF_LAUNCH(bcd_state_init_kernel, dim3(1), dim3(64), 0, S(stream), st, sq);
     return check_launch("bcd_state_init");
 }
 
@@ -71,7 +77,7 @@ int dnmf_bcd_init_factor(const float* X0, long rows, long cols, long ld0, float*
                          int which, void* stream) {
     REQUIRE(X0 && Xold && Xm && st && rows >= 1 && cols >= 1 && ld0 >= cols && ldo >= cols && ldm >= cols && (which == 0 || which == 1),
             "bcd_init_factor: bad arguments");
-    hipLaunchKernelGGL(bcd_init_factor_kernel, dim3(ew_grid(rows * cols)), dim3(256), 0, S(stream), X0, rows, cols, ld0, Xold, ldo, Xm, ldm,
+    DNMF_LAUNCH(bcd_init_factor_kernel, dim3(ew_grid(rows * cols)), dim3(256), 0, S(stream), X0, rows, cols, ld0, Xold, ldo, Xm, ldm,
                        st, which == 0 ? (int)BCD_SW : (int)BCD_SH);
     return check_launch("bcd_init_factor");
 }
@@ -79,7 +85,7 @@ int dnmf_bcd_init_factor(const float* X0, long rows, long cols, long ld0, float*
 int dnmf_bcd_lipschitz(const float* G, int k, double* st, int which, void* stream) {
     const int kp = dnmf_kp(k);
     REQUIRE(G && st && kp > 0 && (which == 0 || which == 1), "bcd_lipschitz: bad arguments (k %d)", k);
-    hipLaunchKernelGGL(bcd_lipschitz_kernel, dim3(1), dim3(256), 0, S(stream), G, kp, k, st, which == 0 ? (int)BCD_LW : (int)BCD_LH);
+    DNMF_LAUNCH(bcd_lipschitz_kernel, dim3(1), dim3(256), 0, S(stream), G, kp, k, st, which == 0 ? (int)BCD_LW : (int)BCD_LH);
     return check_launch("bcd_lipschitz");
 }
 
@@ -93,13 +99,13 @@ int dnmf_bcd_update_w(const float* Wm, long ldwm, const float* AHT, long ldaht, 
     float* part = (float*)ws;
     int rc;
     if ((rc = pg_launch(false, Wm, ldwm, AHT, ldaht, G, m, k, st, W, ldw, part, st_))) return rc;
-    hipLaunchKernelGGL(bcd_colsum_kernel, dim3((unsigned)k), dim3(256), 0, st_, part, cdiv(m, BCD_ROWS), k, s);
+    DNMF_LAUNCH(bcd_colsum_kernel, dim3((unsigned)k), dim3(256), 0, st_, part, cdiv(m, BCD_ROWS), k, s);
     return check_launch("bcd_colsum");
 }
 
 int dnmf_bcd_scale_cols(float* W, long m, int k, long ldw, const float* s, void* stream) {
     REQUIRE(W && s && m >= 1 && k >= 1 && ldw >= k, "bcd_scale_cols: bad arguments");
-    hipLaunchKernelGGL(bcd_scale_cols_kernel, dim3(ew_grid(m * (long)k)), dim3(256), 0, S(stream), W, m, k, ldw, s);
+    DNMF_LAUNCH(bcd_scale_cols_kernel, dim3(ew_grid(m * (long)k)), dim3(256), 0, S(stream), W, m, k, ldw, s);
     return check_launch("bcd_scale_cols");
 }
 
@@ -113,7 +119,7 @@ int dnmf_bcd_update_h(const float* Hm, long ldhm, const float* WTA, long ldwta, 
 
 int dnmf_bcd_decide(double* st, const double* sq, void* stream) {
     REQUIRE(st && sq, "bcd_decide: null pointer");
-    hipLaunchKernelGGL(bcd_decide_kernel, dim3(1), dim3(64), 0, S(stream), st, sq);
+    DNMF_LAUNCH(bcd_decide_kernel, dim3(1), dim3(64), 0, S(stream), st, sq);
     return check_launch("bcd_decide");
 }
 
@@ -130,22 +136,30 @@ int dnmf_bcd_extrapolate(float* W, long ldw, float* Wold, long ldwo, float* Wm, 
     J.j[3] = BcdJob{G, Gk, nullptr, kp, kp, kp, kp, 0, 1, 0};
     J.n = 4;
     const long big = std::max(m * (long)k, (long)k * n);
-    hipLaunchKernelGGL(bcd_extrapolate_kernel, dim3(ew_grid(big), 4), dim3(256), 0, S(stream), J, st);
+    DNMF_LAUNCH(bcd_extrapolate_kernel, dim3(ew_grid(big), 4), dim3(256), 0, S(stream), J, st);
     return check_launch("bcd_extrapolate");
 }
 
 // One rank: `itr` BCD iterations (one update(), dist_nmf.py:967-1047), then the clamp iff (itr - 1) % 10 == 0 (PyNMF.fit runs ONE
 // trip with i = itr - 1, pyDNMF.py:151-156), normalize_features (:185-194) and the squared norms of relative_err (:205-218).
+// batch > 1: the same launch sequence, laid out for problem 0, with every launch covering all problems (blockIdx.z = problem; csrc/
+// dnmf_common.h "batched launches").  Each problem's state block and squared norms sit in its own workspace slice, so the problems
+// of one batch accept or restart independently in the same iteration: nothing the host issues depends on a decision.
 int dnmf_bcd_fro_fit(const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int w_update,
                      int itr, int batch, long a_stride, long w_stride, long h_stride, double* sq_out, void* ws, size_t ws_bytes,
                      void* stream) {
-    (void)w_update; (void)a_stride; (void)w_stride; (void)h_stride;          // (W is always updated: dist_nmf.py:967 ignores W_update)
-    REQUIRE(A && W && H && sq_out && ws && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_MAX_K && lda >= n && ldw >= k && ldh >= n && itr >= 1,
-            "bcd_fro_fit: bad arguments (m %ld, n %ld, k %d, itr %d)", m, n, k, itr);
-    REQUIRE(batch == 1, "bcd_fro_fit: batch %d -- batched BCD fits are not provided (fit the problems one by one)", batch);
+    (void)w_update;                                                          // (W is always updated: dist_nmf.py:967 ignores W_update)
+    REQUIRE(A && W && H && sq_out && ws && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_MAX_K && lda >= n && ldw >= k && ldh >= n && itr >= 1 &&
+            batch >= 1, "bcd_fro_fit: bad arguments (m %ld, n %ld, k %d, itr %d, batch %d)", m, n, k, itr, batch);
     const size_t need = dnmf_bcd_ws_bytes(m, n, k);
-    if (ws_bytes < need) return fail(DNMF_EWS, "bcd_fro_fit: workspace %zu < %zu", ws_bytes, need);
+    REQUIRE(need != 0, "bcd_fro_fit: unsupported shape (m %ld, n %ld, k %d)", m, n, k);
+    if (ws_bytes < (size_t)batch * need) return fail(DNMF_EWS, "bcd_fro_fit: workspace %zu < %d x %zu", ws_bytes, batch, need);
     const BcdWs L = bcd_layout(m, n, k);
+    BatchCtx* ctx = dnmf_batch_();
+    if (ctx->B != 1) return fail(DNMF_EINVAL, "bcd_fro_fit: called inside a batched fit");
+    BatchGuard guard(ctx);
+    if (int frc = batch_families(ctx, "bcd_fro_fit", batch, A, sizeof(float), m, n, lda, a_stride, W, ldw, w_stride, H, ldh, h_stride, k, ws,
+                                 L.total)) return frc;
     char* b = (char*)ws;
     const int kp = dnmf_kp(k);
     float *Wo = (float*)(b + L.wo), *Wm = (float*)(b + L.wm), *AHT = (float*)(b + L.aht), *AHTk = (float*)(b + L.ahtk);
@@ -166,8 +180,12 @@ int dnmf_bcd_fro_fit(const float* A, long m, long n, long lda, float* W, long ld
     if ((rc = dnmf_bcd_init_factor(H, k, n, ldh, Ho, n, Hm, n, st, 1, stream))) return rc;
     if ((rc = dnmf_gram_hht(Ho, k, n, n, Gh, ws, step, stream))) return rc;
     if ((rc = dnmf_aht(A, m, n, lda, Ho, k, n, AHT, k, stream))) return rc;
-    if (hipMemcpyAsync(Ghk, Gh, (size_t)kp * kp * sizeof(float), hipMemcpyDeviceToDevice, hs) != hipSuccess ||
-        hipMemcpyAsync(AHTk, AHT, (size_t)m * k * sizeof(float), hipMemcpyDeviceToDevice, hs) != hipSuccess)
+    // the kept products of every problem: one copy each, the slices `L.total` apart as the rows of a two-dimensional copy
+    const size_t gbytes = (size_t)kp * kp * sizeof(float), ahtbytes = (size_t)m * k * sizeof(float);
+    if (batch == 1 ? (hipMemcpyAsync(Ghk, Gh, gbytes, hipMemcpyDeviceToDevice, hs) != hipSuccess ||
+                      hipMemcpyAsync(AHTk, AHT, ahtbytes, hipMemcpyDeviceToDevice, hs) != hipSuccess)
+                   : (hipMemcpy2DAsync(Ghk, L.total, Gh, L.total, gbytes, (size_t)batch, hipMemcpyDeviceToDevice, hs) != hipSuccess ||
+                      hipMemcpy2DAsync(AHTk, L.total, AHT, L.total, ahtbytes, (size_t)batch, hipMemcpyDeviceToDevice, hs) != hipSuccess))
         return fail(DNMF_EHIP, "bcd_fro_fit: copy of the kept products failed");
     for (int i = 0; i < itr; ++i) {                                                              // :977-1047
         if ((rc = dnmf_bcd_lipschitz(Gh, k, st, 0, stream))) return rc;
@@ -190,8 +208,15 @@ int dnmf_bcd_fro_fit(const float* A, long m, long n, long lda, float* W, long ld
     if ((rc = dnmf_colsum(W, m, k, ldw, s, ws, step, stream))) return rc;
     if ((rc = dnmf_scale_cols_div(W, m, k, ldw, s, eps, stream))) return rc;
     if ((rc = dnmf_scale_rows_mul(H, k, n, ldh, s, stream))) return rc;
-    if ((rc = dnmf_resid_sqnorm_ws(A, m, n, lda, W, ldw, H, ldh, k, sq_out, ws, step, stream))) return rc;
-    return dnmf_sqnorm(A, m, n, lda, sq_out + 1, stream);
+    // a single fit writes its pair where the caller wants it; the problems of a batch write theirs in their slices (sq[4], sq[5]), gathered
+    // into sq_out[z][2] by one copy
+    double* fin = batch == 1 ? sq_out : sq + 4;
+    if ((rc = dnmf_resid_sqnorm_ws(A, m, n, lda, W, ldw, H, ldh, k, fin, ws, step, stream))) return rc;
+    if ((rc = dnmf_sqnorm(A, m, n, lda, fin + 1, stream))) return rc;
+    if (batch > 1 && hipMemcpy2DAsync(sq_out, 2 * sizeof(double), fin, L.total, 2 * sizeof(double), (size_t)batch, hipMemcpyDeviceToDevice,
+                                      hs) != hipSuccess)
+        return fail(DNMF_EHIP, "bcd_fro_fit: copy of the squared norms failed");
+    return DNMF_OK;
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 // of the per-step entry points, in the order the per-step callers issue them -- problem z of a batch runs the instructions
 // a single fit runs, on the same operands (csrc/dnmf_common.h "batched launches").
 #include "dnmf_common.h"
+#include "dnmf_host.h"
 #include "dnmf_small.h"
 
 // csrc/dnmf.hip: offsets of the step workspace {G, S, x, partials, total}
@@ -113,13 +114,6 @@ FitWs fit_layout(long m, long n, int k) {
     return f;
 }
 
-struct BatchGuard {      // the batch state of this thread is set for the duration of one fit call, whatever the exit path
-    BatchCtx* c;
-    explicit BatchGuard(BatchCtx* ctx) : c(ctx) {}
-    ~BatchGuard() { c->B = 1; c->tab.n = 0; c->tab.z0 = 0; }
-};
-
-bool overlap(const BatchFam& a, const BatchFam& b) { return a.lo < b.hi && b.lo < a.hi; }
 inline bool wide_fit_k(int k) { return k > DNMF_TUNED_MAX_K; }
 
 template <bool BF>
@@ -294,22 +288,8 @@ int fit_impl(int method, bool bf, const void* A, long m, long n, long lda, float
     if (ctx->B != 1) return fail(DNMF_EINVAL, "fit: called inside a batched fit");
     BatchGuard guard(ctx);
     const size_t ea = bf ? 2 : 4;
-    if (batch > 1) {
-        BatchFam fam[4] = {{(unsigned long)A, (unsigned long)A + ((size_t)(m - 1) * lda + n) * ea, (long)(a_stride * (long)ea)},
-                           {(unsigned long)W, (unsigned long)W + ((size_t)(m - 1) * ldw + k) * 4, w_stride * 4},
-                           {(unsigned long)H, (unsigned long)H + ((size_t)(k - 1) * ldh + n) * 4, h_stride * 4},
-                           {(unsigned long)ws, (unsigned long)ws + f.total, (long)f.total}};
-        for (int i = 0; i < 4; ++i) {
-            if (fam[i].stride % 16 != 0 || (unsigned long)(fam[i].stride < 0 ? -fam[i].stride : fam[i].stride) < fam[i].hi - fam[i].lo)
-                return fail(DNMF_EINVAL, "fit: stride of operand %d (%ld bytes) must be a multiple of 16 bytes and span one problem (%lu bytes)",
-                            i, fam[i].stride, fam[i].hi - fam[i].lo);
-            for (int j = 0; j < i; ++j)
-                if (overlap(fam[i], fam[j])) return fail(DNMF_EINVAL, "fit: operands %d and %d overlap", j, i);
-            ctx->tab.f[i] = fam[i];
-        }
-        ctx->tab.n = 4;
-        ctx->B = batch;
-    }
+    // (the family set-up and the guard: csrc/dnmf_host.h)
+    if (int frc = batch_families(ctx, "fit", batch, A, ea, m, n, lda, a_stride, W, ldw, w_stride, H, ldh, h_stride, k, ws, f.total)) return frc;
     char* base = (char*)ws;
     int rc = DNMF_OK;
     bool small = false;

@@ -31,6 +31,40 @@ inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 #define REQUIRE(cond, ...) \
     do { if (!(cond)) return fail(DNMF_EINVAL, __VA_ARGS__); } while (0)
 
+// ---- the batch state of a whole fit (csrc/dnmf_fit.hip, csrc/dnmf_bcd.hip; csrc/dnmf_common.h "batched launches")
+struct BatchGuard {      // the batch state of this thread is set for the duration of one fit call, whatever the exit path
+    BatchCtx* c;
+    explicit BatchGuard(BatchCtx* ctx) : c(ctx) {}
+    ~BatchGuard() { c->B = 1; c->tab.n = 0; c->tab.z0 = 0; }
+};
+
+inline bool overlap(const BatchFam& a, const BatchFam& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// The four operand families of `batch` > 1 same-shape problems -- the data blocks (`ea` bytes per element), the W factors, the H
+// factors, the workspace slices of `ws_slice` bytes -- checked (strides multiples of 16 bytes that span one problem, no two
+// families overlapping) and installed in the calling thread's batch state; batch = 1 leaves the state alone.  The caller holds a
+// BatchGuard on `ctx`.  `who` prefixes the messages.
+inline int batch_families(BatchCtx* ctx, const char* who, int batch, const void* A, size_t ea, long m, long n, long lda, long a_stride,
+                          const float* W, long ldw, long w_stride, const float* H, long ldh, long h_stride, int k, const void* ws,
+                          size_t ws_slice) {
+    if (batch <= 1) return DNMF_OK;
+    BatchFam fam[4] = {{(unsigned long)A, (unsigned long)A + ((size_t)(m - 1) * lda + n) * ea, (long)(a_stride * (long)ea)},
+                       {(unsigned long)W, (unsigned long)W + ((size_t)(m - 1) * ldw + k) * 4, w_stride * 4},
+                       {(unsigned long)H, (unsigned long)H + ((size_t)(k - 1) * ldh + n) * 4, h_stride * 4},
+                       {(unsigned long)ws, (unsigned long)ws + ws_slice, (long)ws_slice}};
+    for (int i = 0; i < 4; ++i) {
+        if (fam[i].stride % 16 != 0 || (unsigned long)(fam[i].stride < 0 ? -fam[i].stride : fam[i].stride) < fam[i].hi - fam[i].lo)
+            return fail(DNMF_EINVAL, "%s: stride of operand %d (%ld bytes) must be a multiple of 16 bytes and span one problem (%lu bytes)",
+                        who, i, fam[i].stride, fam[i].hi - fam[i].lo);
+        for (int j = 0; j < i; ++j)
+            if (overlap(fam[i], fam[j])) return fail(DNMF_EINVAL, "%s: operands %d and %d overlap", who, j, i);
+        ctx->tab.f[i] = fam[i];
+    }
+    ctx->tab.n = 4;
+    ctx->B = batch;
+    return DNMF_OK;
+}
+
 // two-stage when there are many partials per output (gram of a tall W): slices of 32 splits, then one more pass
 constexpr int REDUCE_SLICE = 32;
 inline int reduce_slices(int nsplit) { return nsplit > 2 * REDUCE_SLICE ? (int)cdiv(nsplit, REDUCE_SLICE) : 1; }

@@ -533,24 +533,24 @@ class HipOps:
         return sq
 
     def _bcd_fit(self, A3, W3, H3, eps, w_update, itr, sfx, batched):
-        """method 'bcd' (dnmf_bcd_fro_fit): float32 data, one problem per call -- a stack is fitted one problem after another
-        (no batched BCD kernels; each problem is the single fit it would be on its own)."""
+        """method 'bcd' (dnmf_bcd_fro_fit): float32 data; a stack of B problems is ONE library call in which every launch
+        covers all of them.  Each problem keeps its own state block in its workspace slice, so the problems accept or restart
+        independently; bit-identical to B single fits."""
         if sfx:
             raise NotImplementedError("method 'bcd' with bfloat16-stored A is not provided (float32 data only)")
         B, m, n = A3.shape
         k = W3.shape[2]
-        nbytes = lib.dnmf_bcd_ws_bytes(int(m), int(n), int(k))
+        nbytes = lib.dnmf_bcd_ws_bytes_fit(int(m), int(n), int(k), int(B))
         if nbytes == 0:
-            raise ValueError("fit: bad problem shape m=%d n=%d k=%d for method 'bcd'" % (m, n, k))
+            raise ValueError("fit: bad problem shape m=%d n=%d k=%d batch=%d for method 'bcd'" % (m, n, k, B))
         ws = _scratch(nbytes, A3.device)
         sq = torch.empty(B, 2, dtype=torch.float64, device=A3.device)
-        for b in range(B):
-            A, W, H = A3[b], W3[b], H3[b]
-            for t, name in ((A, "A"), (W, "W"), (H, "H")):
-                if t.stride(1) != 1 and t.numel():
-                    raise ValueError("fit: %s must have unit inner stride" % name)
-            check(lib.dnmf_bcd_fro_fit(A.data_ptr(), m, n, _ld(A), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), k, float(eps),
-                                       int(bool(w_update)), int(itr), 1, 0, 0, 0, sq[b].data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        for t, name in ((A3, "A"), (W3, "W"), (H3, "H")):
+            if t.stride(2) != 1 and t.numel():
+                raise ValueError("fit: %s must have unit inner stride" % name)
+        check(lib.dnmf_bcd_fro_fit(A3.data_ptr(), m, n, _ld(A3[0]), W3.data_ptr(), _ld(W3[0]), H3.data_ptr(), _ld(H3[0]), k, float(eps),
+                                   int(bool(w_update)), int(itr), int(B), A3.stride(0), W3.stride(0), H3.stride(0), sq.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), _stream()))
         return sq
 
     # ---- allocation helpers used by the choreography

@@ -327,11 +327,10 @@ class PyNMF:
                     and f.A_ij.dtype == f0.A_ij.dtype and f.A_ij.device == f0.A_ij.device and f.W_i.shape == f0.W_i.shape
                     and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k) ==
                     (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k))
-        # (no batched BCD fits: each one is the single-problem library call, one after another)
-        if len(fits) < 2 or str(f0.method).lower() == 'bcd' or not all(same(f) for f in fits):
+        if len(fits) < 2 or not all(same(f) for f in fits):
             return [f.fit() for f in fits]
-        if f0.method.lower() not in ('mu', 'hals'):
-            raise NotImplementedError("method '%s' is not part of the MI355X engine (mu / hals)" % f0.method)
+        if f0.method.lower() not in ('mu', 'hals', 'bcd'):
+            raise NotImplementedError("method '%s' is not part of the MI355X engine (mu / hals / bcd)" % f0.method)
         A = getattr(f0, "_stack", None)
         if A is None or A.shape[0] != len(fits) or any(getattr(f, "_stack", None) is not A or f.A_ij.data_ptr() != A[b].data_ptr()
                                                        for b, f in enumerate(fits)):

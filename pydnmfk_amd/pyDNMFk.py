@@ -315,6 +315,14 @@ class PyNMFk:
         # stay on the safe side), the factors and their workspaces
         esz = self.A_ij.element_size() if isinstance(self.A_ij, torch.Tensor) else int(np.dtype(getattr(self.A_ij, "dtype", np.float32)).itemsize)
         per = m * n * esz * (2.25 if esz == 8 else 1.25) + (m + n) * max(int(self.end_k), 1) * esz * 8 + (64 << 20)
+        if str(getattr(self.params, "method", "mu")).lower() == "bcd" and esz == 4:
+            # a BCD problem's workspace slice holds four m x k and three k x n buffers next to the step workspace: ask the library
+            # (the largest rank of the sweep) instead of trusting the estimate above
+            from ._lib import lib
+            kmax = max(int(self.end_k), 1)
+            slice_bytes = lib.dnmf_bcd_ws_bytes_fit(int(m), int(n), kmax, 1)
+            if slice_bytes:
+                per = m * n * esz * 1.25 + (m + n) * kmax * esz * 2 + slice_bytes + (16 << 20)
         return int(max(1, min(cap, self.perturbations, (0.6 * free) // per)))
 
     def pvalueAnalysis(self):
