@@ -578,6 +578,47 @@ int dnmf_hals_fro_step_1d_bf16a(const void* A, long m_l, long n_l, long lda, flo
 int dnmf_hals_fro_step_2d_bf16a(const void* A, long m_l, long n_l, long lda, float* W, long m_w, long ldw, float* H, long n_h, long ldh,
                                 int k, float eps, int w_update, int clamp, void* ws, size_t ws_bytes, dnmf_comm_t* comm, void* stream);
 
+/* ---- Sparse data: the block as CSR (no counterpart in the reference, whose data block is a dense numpy array) ----
+ * The one exception to "every matrix is dense" above.  A block of m x n with nnz stored entries is handed over as TWO CSR
+ * images in device memory, both built once by the caller: the block itself (row pointers int32 [m + 1], column indices int32
+ * [nnz], values float32 [nnz]) and its transpose (row pointers [n + 1], the ROW indices of the block as its column indices,
+ * the values in that order).  Layout contract: nnz < 2^31, m, n < 2^31, indices in range, column indices strictly increasing
+ * inside a row (no duplicates), no stored zeros needed.  An update rule touches A only through products in which a zero of
+ * A contributes exactly zero (dist_nmf.py:705 via :730, :749, :883, :902; the KL quotient :806-810 is zero wherever A is), so a
+ * sparse step is the dense step on the densified block up to summation order; the k x k work, the update kernels, Gram
+ * matrices, clamps and normalisation are the dense entry points above, which never see A.
+ * Factors enter these kernels as PACKED images [rows x KPAD], KPAD = dnmf_csr_kpad(k) = 16 / 32 / 64 / 128 / 256 floats, zero
+ * padded and 16-byte aligned (dnmf_csr_pack): a gathered row is one float4 per lane whatever k is.
+ * Rows with more than dnmf_csr_seg() stored entries ("long rows") are named by the caller, once per image: `long_rows`
+ * [n_long] (ascending row numbers) and `long_segptr` [n_long + 1] (running count of their segments of dnmf_csr_seg() entries,
+ * long_segptr[0] = 0, long_segptr[n_long] = nseg); such a row is computed segment by segment and its partial rows are added in
+ * segment order.  n_long = 0: both may be NULL.  No sum is formed with atomics: results are bit-reproducible.
+ * `ws`: dnmf_csr_ws_bytes(m, n, k, nseg) bytes (the larger nseg of the two images), 16-byte aligned. */
+int dnmf_csr_kpad(int k);
+int dnmf_csr_seg(void);
+size_t dnmf_csr_ws_bytes(long m, long n, int k, int nseg);
+/* P = the packed image of a factor.  transpose == 0: X is [rows x cols], cols = k (W): P[rows x KPAD].  transpose != 0: X is
+ * [rows x cols], rows = k (H): P[cols x KPAD] = X^T.  (H_j.T of dist_nmf.py:730, materialised.) */
+int dnmf_csr_pack(const float* X, long rows, long cols, long ldx, int transpose, float* P, void* stream);
+/* out[r][0:k] = sum over the stored entries p of row r of val[p] * Fp[col[p]][0:k].  On the block's CSR with Fp = packed H^T:
+ * A H^T [m x k] (global_mm(A_ij, H_j.T), dist_nmf.py:730, :883).  On the transpose's CSR with Fp = packed W and out_trans != 0
+ * (out[c][r], ldo >= rows): W^T A [k x n] (global_mm(W_i.T, A_ij), :749, :902).  Empty rows give exact zeros. */
+int dnmf_csr_mm(const int* rowptr, const int* col, const float* val, long rows, const float* Fp, int k, float* out, long ldo,
+                int out_trans, const int* long_rows, const int* long_segptr, int n_long, int nseg, void* ws, size_t ws_bytes,
+                void* stream);
+/* The KL products with the quotient fused (dist_nmf.py:806-810): per stored entry d = <Lp[r], Fp[col[p]]>, q = val[p] / (d + eps),
+ * out[r] += q * Fp[col[p]].  Block's CSR, Lp = packed W, Fp = packed H^T: U H^T [m x k] (:810).  Transpose's CSR, Lp = packed
+ * H^T, Fp = packed W, out_trans != 0: W^T U [k x n] (:808). */
+int dnmf_csr_kl_mm(const int* rowptr, const int* col, const float* val, long rows, const float* Lp, const float* Fp, int k,
+                   float eps, float* out, long ldo, int out_trans, const int* long_rows, const int* long_segptr, int n_long,
+                   int nseg, void* ws, size_t ws_bytes, void* stream);
+/* sq[0] = ||A - W H||_F^2 (pyDNMF.py:205-218) without a dense image: sum over the stored entries of a (a - 2 d), d = <W[i], H[:, j]>,
+ * plus <W^T W, H H^T> (= ||W H||^2 over ALL entries).  The two terms cancel when the fit is good, so d, the stored-entry sum, both
+ * Gram matrices and their contraction are float64.  Block's CSR, Wp = packed W [m x KPAD], HTp = packed H^T [n x KPAD]. */
+int dnmf_csr_resid_sqnorm(const int* rowptr, const int* col, const float* val, long m, long n, const float* Wp, const float* HTp,
+                          int k, const int* long_rows, const int* long_segptr, int n_long, int nseg, double* sq, void* ws,
+                          size_t ws_bytes, void* stream);
+
 /* ---- measurement aid (no counterpart in the reference) ----
  * Which shader clock does the GPU hold right now?  Launches ONE wave on `stream` that writes `n` pairs {s_memtime (shader
  * cycles), wall_clock64 (the constant 100 MHz reference)} into samples[2 n], sleeping `naps` x ~4 us between two pairs, and

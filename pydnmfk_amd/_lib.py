@@ -172,7 +172,18 @@ SIGNATURES["dnmf_bcd_extrapolate"] = [c_void_p, c_long, c_void_p, c_long, c_void
 SIGNATURES["dnmf_bcd_ws_bytes"] = [c_long, c_long, c_int]
 SIGNATURES["dnmf_bcd_ws_bytes_fit"] = [c_long, c_long, c_int, c_int]
 SIGNATURES["dnmf_bcd_fro_fit"] = SIGNATURES["dnmf_mu_fro_fit"]
-_RESTYPES = {"dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
+# sparse data block (csrc/dnmf_csr.hip): rowptr col val rows ... long_rows long_segptr n_long nseg ws ws_bytes stream
+SIGNATURES["dnmf_csr_kpad"] = [c_int]
+SIGNATURES["dnmf_csr_seg"] = []
+SIGNATURES["dnmf_csr_ws_bytes"] = [c_long, c_long, c_int, c_int]
+SIGNATURES["dnmf_csr_pack"] = [c_void_p, c_long, c_long, c_long, c_int, c_void_p, c_void_p]
+SIGNATURES["dnmf_csr_mm"] = [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_int,
+                             c_void_p, c_size_t, c_void_p]
+SIGNATURES["dnmf_csr_kl_mm"] = [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int, c_float, c_void_p, c_long, c_int, c_void_p,
+                                c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]
+SIGNATURES["dnmf_csr_resid_sqnorm"] = [c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                       c_void_p, c_void_p, c_size_t, c_void_p]
+_RESTYPES = {"dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
              "dnmf_ws_bytes_1d": c_size_t, "dnmf_ws_bytes_hblocks": c_size_t, "dnmf_ws_bytes_2d": c_size_t,
              "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t, "dnmf_bcd_ws_bytes_fit": c_size_t}
 

@@ -1,0 +1,270 @@
+// dnmf_csr.h -- kernels for a data block held as CSR (int32 row pointers and column indices, float32 values, columns sorted
+// within a row) next to the CSR of its transpose.  Every update rule touches A only through products in which a zero of A
+// contributes exactly zero, so a step needs three kinds of pass over the stored entries:
+//     mm      Out[r] = sum_p val[p] F[col[p]]                                   (A H^T on the block, (W^T A)^T on the transpose)
+//     kl_mm   Out[r] = sum_p val[p] / (<L[r], F[col[p]]> + eps) F[col[p]]       (the KL products, quotient fused)
+//     resid   sum_p val[p] (val[p] - 2 <L[r], F[col[p]]>) in float64           (||A - W H||^2 minus the Gram term)
+// F and L are PACKED factor images [rows x KPAD] (csr_pack_kernel / csr_pack_t_kernel): KPAD = 16 / 32 / 64 / 128 / 256 floats,
+// zero padded, so that a gathered row is 64 B (inside one 128-byte line) or whole 128-byte lines and is read as one float4 per
+// lane, whatever k is.
+//
+// Work split (template parameter G = KPAD / 4 lanes per stored entry): a wave owns a row; it reads 64 (col, val) pairs coalesced,
+// hands entry j to lane group j % (64 / G) by cross-lane reads, every group accumulates its entries in order, and the groups are
+// folded once per row by an xor butterfly.  Nothing in this file is accumulated with atomics: the order of every sum is
+// fixed by the matrix and G alone, so these kernels are bit-reproducible.
+// Long rows (more than CSR_SEG entries; listed at construction of the block): cut into segments of CSR_SEG entries, one wave per
+// segment writing a partial row, and one small launch that adds a row's partials in segment order.
+#pragma once
+#include "dnmf_common.h"
+
+namespace {
+
+constexpr int CSR_SEG = 1024;            // entries of one segment of a long row; rows up to this length are one wave's work
+constexpr int CSR_RESID_WAVES = 8192;    // waves of the residual pass over the rows (each leaves one float64 partial)
+
+template <int G, typename T>
+__device__ inline T csr_sum_in_group(T v) {
+#pragma unroll
+    for (int off = 1; off < G; off <<= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+template <int G, typename T>
+__device__ inline T csr_sum_over_groups(T v) {
+#pragma unroll
+    for (int off = G; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+template <int G>
+__device__ inline f32x4 csr_fold(f32x4 a) {
+    a.x = csr_sum_over_groups<G>(a.x);
+    a.y = csr_sum_over_groups<G>(a.y);
+    a.z = csr_sum_over_groups<G>(a.z);
+    a.w = csr_sum_over_groups<G>(a.w);
+    return a;
+}
+
+// MODE 0: mm, 1: kl_mm, 2: resid.  The stored entries [p0, p1) of one row; `lrow` = this lane's float4 of the packed row L[r].
+template <int G, int MODE>
+__device__ inline void csr_span(const int* __restrict__ col, const float* __restrict__ val, int p0, int p1,
+                                const float* __restrict__ F, const f32x4 lrow, float eps, f32x4& acc, double& dacc) {
+    constexpr int NG = 64 / G, KPAD = 4 * G;
+    const int lane = threadIdx.x & 63, grp = lane / G, l = lane % G;
+    for (int base = p0; base < p1; base += 64) {
+        const int p = base + lane;
+        const bool in = p < p1;
+        const int c = in ? col[p] : 0;
+        const float v = in ? val[p] : 0.f;
+        const int cnt = min(64, p1 - base);
+#pragma unroll 2
+        for (int j0 = 0; j0 < cnt; j0 += NG) {
+            const int j = j0 + grp;                               // (< 64: j0 <= 64 - NG)
+            const int cj = __shfl(c, j, 64);
+            const float vj = __shfl(v, j, 64);
+            const bool ok = j < cnt;                              // uniform inside a lane group
+            f32x4 f = {0.f, 0.f, 0.f, 0.f};
+            if (ok) f = *reinterpret_cast<const f32x4*>(F + (size_t)cj * KPAD + 4 * l);
+            if (MODE == 0) {
+                if (ok) {
+                    acc.x = fmaf(vj, f.x, acc.x); acc.y = fmaf(vj, f.y, acc.y);
+                    acc.z = fmaf(vj, f.z, acc.z); acc.w = fmaf(vj, f.w, acc.w);
+                }
+            } else if (MODE == 1) {
+                float t = lrow.x * f.x;
+                t = fmaf(lrow.y, f.y, t); t = fmaf(lrow.z, f.z, t); t = fmaf(lrow.w, f.w, t);
+                const float d = csr_sum_in_group<G>(t);
+                if (ok) {
+                    const float q = vj / (d + eps);
+                    acc.x = fmaf(q, f.x, acc.x); acc.y = fmaf(q, f.y, acc.y);
+                    acc.z = fmaf(q, f.z, acc.z); acc.w = fmaf(q, f.w, acc.w);
+                }
+            } else {
+                double t = (double)lrow.x * (double)f.x;
+                t = fma((double)lrow.y, (double)f.y, t); t = fma((double)lrow.z, (double)f.z, t); t = fma((double)lrow.w, (double)f.w, t);
+                const double d = csr_sum_in_group<G>(t);
+                if (ok && l == 0) dacc += (double)vj * ((double)vj - 2.0 * d);
+            }
+        }
+    }
+}
+
+__device__ inline void csr_store(float* __restrict__ out, long ldo, int out_trans, long r, int c0, const f32x4 a, int k) {
+    const float e[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (c0 + i < k) {
+            if (out_trans) out[(size_t)(c0 + i) * ldo + r] = e[i];
+            else out[(size_t)r * ldo + c0 + i] = e[i];
+        }
+}
+
+// one wave per row, four rows per workgroup; rows longer than CSR_SEG are left to the segment kernels
+template <int G, int MODE>
+__global__ __launch_bounds__(256) void csr_rows_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                       const float* __restrict__ val, long rows, const float* __restrict__ L,
+                                                       const float* __restrict__ F, int k, float eps, float* __restrict__ out,
+                                                       long ldo, int out_trans) {
+    constexpr int KPAD = 4 * G;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int lane = threadIdx.x & 63, l = lane % G;
+    const int p0 = rowptr[r], p1 = rowptr[r + 1];
+    if (p1 - p0 > CSR_SEG) return;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, lrow = {0.f, 0.f, 0.f, 0.f};
+    double dacc = 0.0;
+    if (MODE != 0 && p1 > p0) lrow = *reinterpret_cast<const f32x4*>(L + (size_t)r * KPAD + 4 * l);
+    csr_span<G, MODE>(col, val, p0, p1, F, lrow, eps, acc, dacc);
+    acc = csr_fold<G>(acc);
+    if (lane < G) csr_store(out, ldo, out_trans, r, 4 * l, acc, k);
+}
+
+// the residual's pass over the rows: a fixed number of waves, wave w takes rows w, w + nw, ... and leaves ONE float64 partial
+template <int G>
+__global__ __launch_bounds__(256) void csr_resid_rows_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                             const float* __restrict__ val, long rows, const float* __restrict__ L,
+                                                             const float* __restrict__ F, double* __restrict__ dpart) {
+    constexpr int KPAD = 4 * G;
+    const long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (long)gridDim.x * 4;
+    const int lane = threadIdx.x & 63, l = lane % G;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    double dacc = 0.0;
+    for (long r = w; r < rows; r += nw) {
+        const int p0 = rowptr[r], p1 = rowptr[r + 1];
+        if (p1 == p0 || p1 - p0 > CSR_SEG) continue;
+        const f32x4 lrow = *reinterpret_cast<const f32x4*>(L + (size_t)r * KPAD + 4 * l);
+        csr_span<G, 2>(col, val, p0, p1, F, lrow, 0.f, acc, dacc);
+    }
+    dacc = csr_sum_over_groups<G>(dacc);
+    if (lane == 0) dpart[w] = dacc;
+}
+
+// one wave per segment of a long row: partial rows [nseg][KPAD] (MODE 0, 1) or one float64 per segment (MODE 2)
+template <int G, int MODE>
+__global__ __launch_bounds__(256) void csr_long_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                       const float* __restrict__ val, const float* __restrict__ L,
+                                                       const float* __restrict__ F, float eps, const int* __restrict__ long_rows,
+                                                       const int* __restrict__ long_segptr, int n_long, float* __restrict__ part,
+                                                       double* __restrict__ dpart) {
+    constexpr int KPAD = 4 * G;
+    const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= long_segptr[n_long]) return;
+    int lo = 0, hi = n_long;                                       // the long row whose segments include s
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (long_segptr[mid] <= s) lo = mid; else hi = mid;
+    }
+    const long r = long_rows[lo];
+    const int lane = threadIdx.x & 63, l = lane % G;
+    const int p0 = rowptr[r] + (s - long_segptr[lo]) * CSR_SEG, p1 = min(p0 + CSR_SEG, rowptr[r + 1]);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, lrow = {0.f, 0.f, 0.f, 0.f};
+    double dacc = 0.0;
+    if (MODE != 0) lrow = *reinterpret_cast<const f32x4*>(L + (size_t)r * KPAD + 4 * l);
+    csr_span<G, MODE>(col, val, p0, p1, F, lrow, eps, acc, dacc);
+    if (MODE == 2) {
+        dacc = csr_sum_over_groups<G>(dacc);
+        if (lane == 0) dpart[s] = dacc;
+    } else {
+        acc = csr_fold<G>(acc);
+        if (lane < G) *reinterpret_cast<f32x4*>(part + (size_t)s * KPAD + 4 * l) = acc;
+    }
+}
+
+// a long row's partial rows added in segment order: one workgroup of `kpad` threads per long row
+__global__ void csr_long_reduce_kernel(const float* __restrict__ part, int kpad, const int* __restrict__ long_rows,
+                                       const int* __restrict__ long_segptr, int k, float* __restrict__ out, long ldo, int out_trans) {
+    const int i = blockIdx.x, c = threadIdx.x;
+    const long r = long_rows[i];
+    float a = 0.f;
+    for (int s = long_segptr[i]; s < long_segptr[i + 1]; ++s) a += part[(size_t)s * kpad + c];
+    if (c < k) {
+        if (out_trans) out[(size_t)c * ldo + r] = a;
+        else out[(size_t)r * ldo + c] = a;
+    }
+}
+
+// ---- packed factor images
+// P[rows x kpad] = X[rows x k], zero padded (W)
+__global__ __launch_bounds__(256) void csr_pack_kernel(const float* __restrict__ X, long rows, int k, long ldx, float* __restrict__ P,
+                                                       int kpad) {
+    const int q = kpad / 4;
+    const long total = rows * q;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long r = idx / q;
+        const int c = (int)(idx % q) * 4;
+        float d[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = c + e < k ? X[r * ldx + c + e] : 0.f;
+        *reinterpret_cast<f32x4*>(P + r * kpad + c) = f32x4{d[0], d[1], d[2], d[3]};
+    }
+}
+
+// P[n x kpad] = X[k x n]^T, zero padded (H): 32 x 32 tiles through LDS, reads and writes both along rows
+__global__ __launch_bounds__(256) void csr_pack_t_kernel(const float* __restrict__ X, int k, long n, long ldx, float* __restrict__ P,
+                                                         int kpad) {
+    __shared__ float tile[32][33];
+    const long n0 = (long)blockIdx.x * 32;
+    const int k0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int kk = k0 + ty + 8 * i;
+        tile[ty + 8 * i][tx] = (kk < k && n0 + tx < n) ? X[(size_t)kk * ldx + n0 + tx] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int cc = ty + 8 * i;
+        if (n0 + cc < n && k0 + tx < kpad) P[(size_t)(n0 + cc) * kpad + k0 + tx] = tile[tx][cc];
+    }
+}
+
+// ---- float64 Gram partials of a packed image: part[chunk][k x k] = sum over the chunk's rows of X[r][i] X[r][j]
+__global__ __launch_bounds__(256) void csr_gram_f64_kernel(const float* __restrict__ X, long rows, int kpad, int k, long rows_per_chunk,
+                                                           double* __restrict__ part) {
+    __shared__ float sa[64][17], sb[64][17];
+    const int nt = (k + 15) / 16;
+    const int ti = blockIdx.y / nt, tj = blockIdx.y % nt, tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const long r0 = (long)blockIdx.x * rows_per_chunk, r1 = min(rows, r0 + rows_per_chunk);
+    double acc = 0.0;
+    for (long rb = r0; rb < r1; rb += 64) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int idx = threadIdx.x + 256 * e, rr = idx >> 4, cc = idx & 15;
+            const long row = rb + rr;
+            sa[rr][cc] = row < r1 ? X[(size_t)row * kpad + ti * 16 + cc] : 0.f;
+            sb[rr][cc] = row < r1 ? X[(size_t)row * kpad + tj * 16 + cc] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int rr = 0; rr < 64; ++rr) acc = fma((double)sa[rr][ty], (double)sb[rr][tx], acc);
+        __syncthreads();
+    }
+    const int i = ti * 16 + ty, j = tj * 16 + tx;
+    if (i < k && j < k) part[(size_t)blockIdx.x * k * k + i * k + j] = acc;
+}
+
+// sq[0] = max(0, sum_e (sum_c gw[c][e]) (sum_c gh[c][e]) + sum dpart): one workgroup, every sum in a fixed order
+__global__ __launch_bounds__(256) void csr_resid_final_kernel(const double* __restrict__ gw, int ncw, const double* __restrict__ gh,
+                                                              int nch, int k, const double* __restrict__ dpart, long ndpart,
+                                                              double* __restrict__ sq) {
+    __shared__ double sh[256];
+    const int kk = k * k;
+    double t = 0.0;
+    for (int e = threadIdx.x; e < kk; e += 256) {
+        double a = 0.0, b = 0.0;
+        for (int c = 0; c < ncw; ++c) a += gw[(size_t)c * kk + e];
+        for (int c = 0; c < nch; ++c) b += gh[(size_t)c * kk + e];
+        t = fma(a, b, t);
+    }
+    double u = 0.0;
+    for (long e = threadIdx.x; e < ndpart; e += 256) u += dpart[e];
+    sh[threadIdx.x] = t + u;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) sq[0] = sh[0] > 0.0 ? sh[0] : 0.0;
+}
+
+}  // namespace

@@ -1,0 +1,169 @@
+// dnmf_csr.hip -- C ABI of the sparse (CSR) data block: packed factor images, the gather products, the KL products with the
+// quotient fused, and the residual's closed form (csrc/dnmf_csr.h).  A translation unit of its own (see csrc/dnmf_kl.hip).
+// Plain launch chains: no workgroup waits for another one.
+#include "dnmf_common.h"
+#include "dnmf_host.h"
+#include "dnmf_csr.h"
+
+namespace {
+
+inline int csr_kpad_of(int k) {
+    if (k < 1 || k > DNMF_MAX_K) return -1;
+    return k <= 16 ? 16 : (k <= 32 ? 32 : (k <= 64 ? 64 : (k <= 128 ? 128 : 256)));
+}
+
+inline int gram_chunks(long rows, int k) {
+    const long nt = cdiv(k, 16) * cdiv(k, 16);
+    return (int)std::max<long>(1, std::min<long>(cdiv(rows, 512), std::max<long>(8, 256 / nt)));
+}
+
+inline long resid_waves(long rows) { return std::min<long>(round_up(std::max<long>(rows, 1), 4), CSR_RESID_WAVES); }
+
+struct ResidWs { size_t gw, gh, dpart, total; int ncw, nch; long nw; };
+
+ResidWs resid_layout(long rows, long cols, int k, long nseg) {
+    ResidWs L{};
+    L.ncw = gram_chunks(rows, k);
+    L.nch = gram_chunks(cols, k);
+    L.nw = resid_waves(rows);
+    size_t o = 0;
+    L.gw = o; o += align256((size_t)L.ncw * k * k * sizeof(double));
+    L.gh = o; o += align256((size_t)L.nch * k * k * sizeof(double));
+    L.dpart = o; o += align256((size_t)(L.nw + nseg) * sizeof(double));
+    L.total = o;
+    return L;
+}
+
+struct CsrArgs {
+    const int* rowptr; const int* col; const float* val; long rows;
+    const float* L; const float* F; int k; float eps; float* out; long ldo; int out_trans;
+    const int* long_rows; const int* long_segptr; int n_long; int nseg; float* part;
+};
+
+template <int G, int MODE>
+int csr_launch(const CsrArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL((csr_rows_kernel<G, MODE>), dim3((unsigned)cdiv(a.rows, 4)), dim3(256), 0, st, a.rowptr, a.col, a.val, a.rows, a.L,
+                       a.F, a.k, a.eps, a.out, a.ldo, a.out_trans);
+    if (a.n_long > 0) {
+        hipLaunchKernelGGL((csr_long_kernel<G, MODE>), dim3((unsigned)cdiv(a.nseg, 4)), dim3(256), 0, st, a.rowptr, a.col, a.val, a.L, a.F,
+                           a.eps, a.long_rows, a.long_segptr, a.n_long, a.part, (double*)nullptr);
+        hipLaunchKernelGGL(csr_long_reduce_kernel, dim3((unsigned)a.n_long), dim3(4 * G), 0, st, (const float*)a.part, 4 * G, a.long_rows,
+                           a.long_segptr, a.k, a.out, a.ldo, a.out_trans);
+    }
+    return check_launch(MODE ? "csr_kl_mm" : "csr_mm");
+}
+
+template <int MODE>
+int csr_dispatch(const CsrArgs& a, hipStream_t st) {
+    switch (csr_kpad_of(a.k)) {
+        case 16: return csr_launch<4, MODE>(a, st);
+        case 32: return csr_launch<8, MODE>(a, st);
+        case 64: return csr_launch<16, MODE>(a, st);
+        case 128: return csr_launch<32, MODE>(a, st);
+        default: return csr_launch<64, MODE>(a, st);
+    }
+}
+
+template <int G>
+int resid_launch(const int* rowptr, const int* col, const float* val, long rows, const float* Wp, const float* HTp, const int* long_rows,
+                 const int* long_segptr, int n_long, int nseg, double* dpart, long nw, hipStream_t st) {
+    hipLaunchKernelGGL((csr_resid_rows_kernel<G>), dim3((unsigned)(nw / 4)), dim3(256), 0, st, rowptr, col, val, rows, Wp, HTp, dpart);
+    if (n_long > 0)
+        hipLaunchKernelGGL((csr_long_kernel<G, 2>), dim3((unsigned)cdiv(nseg, 4)), dim3(256), 0, st, rowptr, col, val, Wp, HTp, 0.f, long_rows,
+                           long_segptr, n_long, (float*)nullptr, dpart + nw);
+    return check_launch("csr_resid_sqnorm");
+}
+
+int check_common(const char* who, const int* rowptr, const int* col, const float* val, long rows, int k, const int* long_rows,
+                 const int* long_segptr, int n_long, int nseg) {
+    if (!rowptr || rows < 1 || rows >= (1L << 31)) return fail(DNMF_EINVAL, "%s: null row pointers or bad row count %ld (1 <= rows < 2^31)", who, rows);
+    if (csr_kpad_of(k) < 0) return fail(DNMF_EINVAL, "%s: rank k=%d unsupported (1 <= k <= %d)", who, k, DNMF_MAX_K);
+    if (n_long < 0 || nseg < 0 || (n_long > 0 && (!long_rows || !long_segptr || nseg < n_long)))
+        return fail(DNMF_EINVAL, "%s: bad long-row lists (n_long=%d, segments=%d)", who, n_long, nseg);
+    (void)col; (void)val;        // (null for a block without stored entries: never dereferenced then)
+    return DNMF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dnmf_csr_kpad(int k) { return csr_kpad_of(k); }
+
+int dnmf_csr_seg(void) { return CSR_SEG; }
+
+size_t dnmf_csr_ws_bytes(long rows, long cols, int k, int nseg) {
+    if (rows < 1 || cols < 1 || nseg < 0 || csr_kpad_of(k) < 0) return 0;
+    const size_t part = align256((size_t)nseg * csr_kpad_of(k) * sizeof(float));
+    return std::max<size_t>(256, std::max(part, resid_layout(rows, cols, k, nseg).total));
+}
+
+int dnmf_csr_pack(const float* X, long rows, long cols, long ldx, int transpose, float* P, void* stream) {
+    REQUIRE(X && P && rows >= 1 && cols >= 1 && ldx >= cols && aligned16(P), "csr_pack: null / misaligned pointer or bad shape");
+    const int k = (int)(transpose ? rows : cols);
+    REQUIRE((transpose ? rows : cols) <= DNMF_MAX_K, "csr_pack: rank %ld unsupported (1 <= k <= %d)", transpose ? rows : cols, DNMF_MAX_K);
+    const int kpad = csr_kpad_of(k);
+    if (transpose) {
+        REQUIRE(cols < (1L << 31), "csr_pack: %ld columns (must be < 2^31)", cols);
+        hipLaunchKernelGGL(csr_pack_t_kernel, dim3((unsigned)cdiv(cols, 32), (unsigned)cdiv(kpad, 32)), dim3(256), 0, S(stream), X, k, cols,
+                           ldx, P, kpad);
+    } else {
+        const long quads = rows * (kpad / 4);
+        hipLaunchKernelGGL(csr_pack_kernel, dim3((unsigned)std::min<long>(cdiv(quads, 256), 8192)), dim3(256), 0, S(stream), X, rows, k, ldx,
+                           P, kpad);
+    }
+    return check_launch("csr_pack");
+}
+
+int dnmf_csr_mm(const int* rowptr, const int* col, const float* val, long rows, const float* Fp, int k, float* out, long ldo, int out_trans,
+                const int* long_rows, const int* long_segptr, int n_long, int nseg, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_common("csr_mm", rowptr, col, val, rows, k, long_rows, long_segptr, n_long, nseg)) return rc;
+    REQUIRE(Fp && out && aligned16(Fp) && ldo >= (out_trans ? rows : (long)k), "csr_mm: null / misaligned operand or ld too small");
+    const size_t need = (size_t)nseg * csr_kpad_of(k) * sizeof(float);
+    if (n_long > 0 && (!ws || ws_bytes < need || !aligned16(ws))) return fail(DNMF_EWS, "csr_mm: workspace %zu < %zu bytes", ws_bytes, need);
+    const CsrArgs a{rowptr, col, val, rows, nullptr, Fp, k, 0.f, out, ldo, out_trans, long_rows, long_segptr, n_long, nseg, (float*)ws};
+    return csr_dispatch<0>(a, S(stream));
+}
+
+int dnmf_csr_kl_mm(const int* rowptr, const int* col, const float* val, long rows, const float* Lp, const float* Fp, int k, float eps,
+                   float* out, long ldo, int out_trans, const int* long_rows, const int* long_segptr, int n_long, int nseg, void* ws,
+                   size_t ws_bytes, void* stream) {
+    if (int rc = check_common("csr_kl_mm", rowptr, col, val, rows, k, long_rows, long_segptr, n_long, nseg)) return rc;
+    REQUIRE(Lp && Fp && out && aligned16(Lp) && aligned16(Fp) && ldo >= (out_trans ? rows : (long)k),
+            "csr_kl_mm: null / misaligned operand or ld too small");
+    const size_t need = (size_t)nseg * csr_kpad_of(k) * sizeof(float);
+    if (n_long > 0 && (!ws || ws_bytes < need || !aligned16(ws))) return fail(DNMF_EWS, "csr_kl_mm: workspace %zu < %zu bytes", ws_bytes, need);
+    const CsrArgs a{rowptr, col, val, rows, Lp, Fp, k, eps, out, ldo, out_trans, long_rows, long_segptr, n_long, nseg, (float*)ws};
+    return csr_dispatch<1>(a, S(stream));
+}
+
+int dnmf_csr_resid_sqnorm(const int* rowptr, const int* col, const float* val, long rows, long cols, const float* Wp, const float* HTp,
+                          int k, const int* long_rows, const int* long_segptr, int n_long, int nseg, double* sq, void* ws, size_t ws_bytes,
+                          void* stream) {
+    if (int rc = check_common("csr_resid_sqnorm", rowptr, col, val, rows, k, long_rows, long_segptr, n_long, nseg)) return rc;
+    REQUIRE(Wp && HTp && sq && cols >= 1 && cols < (1L << 31) && aligned16(Wp) && aligned16(HTp), "csr_resid_sqnorm: null / misaligned operand or bad shape");
+    const ResidWs L = resid_layout(rows, cols, k, nseg);
+    if (!ws || ws_bytes < L.total || !aligned16(ws)) return fail(DNMF_EWS, "csr_resid_sqnorm: workspace %zu < %zu bytes", ws_bytes, L.total);
+    hipStream_t st = S(stream);
+    const int kpad = csr_kpad_of(k);
+    double* gw = (double*)((char*)ws + L.gw);
+    double* gh = (double*)((char*)ws + L.gh);
+    double* dpart = (double*)((char*)ws + L.dpart);
+    const unsigned tiles = (unsigned)(cdiv(k, 16) * cdiv(k, 16));
+    hipLaunchKernelGGL(csr_gram_f64_kernel, dim3((unsigned)L.ncw, tiles), dim3(256), 0, st, Wp, rows, kpad, k, cdiv(rows, L.ncw), gw);
+    hipLaunchKernelGGL(csr_gram_f64_kernel, dim3((unsigned)L.nch, tiles), dim3(256), 0, st, HTp, cols, kpad, k, cdiv(cols, L.nch), gh);
+    int rc;
+    switch (kpad) {
+        case 16: rc = resid_launch<4>(rowptr, col, val, rows, Wp, HTp, long_rows, long_segptr, n_long, nseg, dpart, L.nw, st); break;
+        case 32: rc = resid_launch<8>(rowptr, col, val, rows, Wp, HTp, long_rows, long_segptr, n_long, nseg, dpart, L.nw, st); break;
+        case 64: rc = resid_launch<16>(rowptr, col, val, rows, Wp, HTp, long_rows, long_segptr, n_long, nseg, dpart, L.nw, st); break;
+        case 128: rc = resid_launch<32>(rowptr, col, val, rows, Wp, HTp, long_rows, long_segptr, n_long, nseg, dpart, L.nw, st); break;
+        default: rc = resid_launch<64>(rowptr, col, val, rows, Wp, HTp, long_rows, long_segptr, n_long, nseg, dpart, L.nw, st); break;
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(csr_resid_final_kernel, dim3(1), dim3(256), 0, st, (const double*)gw, L.ncw, (const double*)gh, L.nch, k,
+                       (const double*)dpart, L.nw + (n_long > 0 ? nseg : 0), sq);
+    return check_launch("csr_resid_sqnorm");
+}
+
+}  // extern "C"

@@ -41,7 +41,12 @@ def release_buffers():
 
 def _default_ops(params=None, like=None):
     from .engine import ops_for
-    return ops_for(params, like.dtype if like is not None else None)
+    return ops_for(params, like.dtype if like is not None else None, sparse=_is_sparse(like))
+
+
+def _is_sparse(A):
+    """the data block is a pydnmfk_amd.sparse.SparseBlock: no fused local step, no library-sequenced step, no column slices"""
+    return bool(getattr(A, "is_sparse_block", False))
 
 
 def _kp(k):
@@ -176,6 +181,8 @@ class nmf_algorithms_1D(_Base):
         the RCCL communicator inside libdnmf_hip.so) -- same kernels in the same order as the choreography below, no Python
         between the launches.  float32 data, the product's own operator set, more than one rank."""
         hals = self.method.upper() == 'HALS' and self.norm.upper() == 'FRO'
+        if _is_sparse(self.A_ij):
+            return False            # (sparse data: the host sequences the sparse primitives)
         if (self.p == 1 and not getattr(self.params, "native_always", False)) or self.k > 128 or \
                 not (hals or (self.method.upper() == 'MU' and self.norm.upper() in ('FRO', 'KL'))):
             return False            # (k > 128: the library-sequenced steps stop at the tuned kernels' rank; the choreography below does not)
@@ -246,7 +253,7 @@ class nmf_algorithms_1D(_Base):
     # ---- Frobenius (dist_nmf.py:716-771)
     def Fro_MU_update(self, W_update=True, clamp=False):
         ops, A, W, H, eps, k = self.ops, self.A_ij, self.W_i, self.H_j, self.eps, self.k
-        if self.p == 1 and hasattr(ops, "mu_fro_step"):
+        if self.p == 1 and hasattr(ops, "mu_fro_step") and not _is_sparse(A):
             ops.mu_fro_step(A, W, H, eps, W_update, clamp)         # whole local step, one library call
             return
         kp = _kp(k)
@@ -287,8 +294,8 @@ class nmf_algorithms_1D(_Base):
         Compute-side cost of the chunks on the 8-GPU shard (32768 x 8192, k = 64, tools/chunkbench.py, no exchange):
         1 / 2 / 4 / 8 chunks = 0.654 / 0.668 / 0.752 / 0.816 ms per step -- two chunks cost 13 us and hide about half of
         the exchange, four cost more than a 2 MiB allreduce is expected to take, hence the default."""
-        if self.p_c != 1 or self.p_r < 2:
-            return 1
+        if self.p_c != 1 or self.p_r < 2 or _is_sparse(self.A_ij):
+            return 1                                               # (a sparse block is not sliced by columns)
         nch = getattr(self.params, "overlap_chunks", None)
         if nch is None:                                            # default: two ranks keep the single packed allreduce
             nch = 2 if self.p_r > 2 else 1
@@ -351,7 +358,7 @@ class nmf_algorithms_1D(_Base):
     # ---- KL (dist_nmf.py:776-869)
     def KL_MU_update(self, W_update=True, clamp=False):
         ops, A, W, H, eps, k = self.ops, self.A_ij, self.W_i, self.H_j, self.eps, self.k
-        if self.p == 1 and hasattr(ops, "mu_kl_step"):
+        if self.p == 1 and hasattr(ops, "mu_kl_step") and not _is_sparse(A):
             ops.mu_kl_step(A, W, H, eps, W_update, clamp)
             return
         m_l, n_l = A.shape
@@ -390,6 +397,9 @@ class nmf_algorithms_2D(_Base):
         self.p = self.p_r * self.p_c
         self.W_update = params.W_update
         self.norm, self.method = params.norm, params.method
+        if _is_sparse(A_ij):
+            raise NotImplementedError("sparse data on a 2D grid (p_r = %d, p_c = %d) are not provided: the 2D choreography slices and "
+                                      "gathers column blocks of A; use a 1D grid" % (self.p_r, self.p_c))
         self.rank = self.comm1.rank
         self.local_W_m = self.W_ij.shape[0]
         self.local_H_n = self.H_ij.shape[1]

@@ -652,6 +652,168 @@ HIP_OPS_BF16X6 = HipOpsBf16x6()
 
 
 
+class HipCsrOps(HipOps):
+    """The operator set for a SPARSE data block (pydnmfk_amd.sparse.SparseBlock): the eight operations that touch A run on its
+    CSR images (csrc/dnmf_csr.h, `dnmf_csr_*`); everything else of a step -- update kernels, Gram matrices, clamps,
+    normalisation -- is the fp32 code of HipOps, which never sees A.  There is no fused local step and no whole fit for sparse
+    data (`mu_fro_step`, `mu_kl_step`, `fit` refuse it): the host's choreography sequences the primitives.  A dense tensor
+    in A's place (BCD asks for the squared norms of W and H) takes the dense kernels."""
+
+    name = "hip-csr"
+    kl_uht_hblocks = None
+    aht_hblocks = None
+
+    def __init__(self):
+        super().__init__()
+        self._bufs = {}
+
+    def _buf(self, role, numel, device, dtype=torch.float32):
+        """one persistent buffer per role and device, grown on demand: a step allocates nothing once it has run"""
+        key = (device, role, dtype)
+        t = self._bufs.get(key)
+        if t is None or t.numel() < numel:
+            t = torch.empty(max(int(numel), 1), dtype=dtype, device=device)
+            self._bufs[key] = t
+        return t
+
+    @staticmethod
+    def _sp(A):
+        return getattr(A, "is_sparse_block", False)
+
+    def _ws(self, A, k):
+        m, n = A.shape
+        nbytes = lib.dnmf_csr_ws_bytes(int(m), int(n), int(k), int(max(A.nseg, A.t_nseg)))
+        if nbytes == 0:
+            raise ValueError("sparse block: bad problem shape m=%d n=%d k=%d" % (m, n, k))
+        return _scratch(nbytes, A.device)
+
+    def _pack(self, X, transpose, role):
+        """the packed image [rows x KPAD] of W (transpose=False) or of H^T (transpose=True) in this operator set's buffer `role`"""
+        _req(X, role)
+        r, c = X.shape
+        k = r if transpose else c
+        kpad = lib.dnmf_csr_kpad(int(k))
+        if kpad < 0:
+            raise ValueError("rank k=%d unsupported (1 <= k <= 256)" % k)
+        P = self._buf(role, (c if transpose else r) * kpad, X.device)
+        check(lib.dnmf_csr_pack(X.data_ptr(), r, c, _ld(X), int(bool(transpose)), P.data_ptr(), _stream()))
+        return P
+
+    @staticmethod
+    def _req_sp(A):
+        if not A.val.is_cuda:
+            raise TypeError("sparse block is on %s; the engine only runs on the GPU (no CPU fallback)" % A.device)
+        _same_device(A.val, "A")
+
+    def _mm(self, A, transposed, Fp, k, out, L=None, eps=0.0):
+        self._req_sp(A)
+        if transposed:
+            crow, col, val, rows = A.t_crow, A.t_col, A.t_val, A.shape[1]
+            lr, ls, nl, ns = A.t_long_rows, A.t_long_segptr, A.t_n_long, A.t_nseg
+        else:
+            crow, col, val, rows = A.crow, A.col, A.val, A.shape[0]
+            lr, ls, nl, ns = A.long_rows, A.long_segptr, A.n_long, A.nseg
+        ws = self._ws(A, k)
+        tail = (lr.data_ptr() if nl else None, ls.data_ptr() if nl else None, nl, ns, ws.data_ptr(), ws.numel(), _stream())
+        if L is None:
+            check(lib.dnmf_csr_mm(crow.data_ptr(), col.data_ptr(), val.data_ptr(), rows, Fp.data_ptr(), int(k), out.data_ptr(), _ld(out),
+                                  int(transposed), *tail))
+        else:
+            check(lib.dnmf_csr_kl_mm(crow.data_ptr(), col.data_ptr(), val.data_ptr(), rows, L.data_ptr(), Fp.data_ptr(), int(k), float(eps),
+                                     out.data_ptr(), _ld(out), int(transposed), *tail))
+        return out
+
+    def aht(self, A, H, out):
+        if not self._sp(A):
+            return super().aht(A, H, out)
+        _req(out, "AH")
+        return self._mm(A, False, self._pack(H, True, "HT"), H.shape[0], out)
+
+    def wta(self, A, W, out):
+        if not self._sp(A):
+            return super().wta(A, W, out)
+        _req(out, "AtW")
+        return self._mm(A, True, self._pack(W, False, "W"), W.shape[1], out)
+
+    def wta_gram(self, A, W, out, G):
+        if not self._sp(A):
+            self.gram_wtw(W, G)
+            return super().wta(A, W, out)
+        self.gram_wtw(W, G)
+        return self.wta(A, W, out)
+
+    def aht_update_w(self, A, H, G, W, eps):
+        if not self._sp(A):
+            return super().aht_update_w(A, H, G, W, eps)
+        m, k = W.shape
+        AH = self._buf("AH", m * k, W.device)[: m * k].view(m, k)
+        self.aht(A, H, AH)
+        return self.mu_update_w(W, AH, G, eps)
+
+    def kl_uht(self, A, W, H, eps, out):
+        if not self._sp(A):
+            return super().kl_uht(A, W, H, eps, out)
+        _req(out, "UHT")
+        Wp, HTp = self._pack(W, False, "W"), self._pack(H, True, "HT")
+        return self._mm(A, False, HTp, W.shape[1], out, L=Wp, eps=eps)
+
+    def kl_wtu(self, A, W, H, eps, out):
+        if not self._sp(A):
+            return super().kl_wtu(A, W, H, eps, out)
+        _req(out, "WTU")
+        Wp, HTp = self._pack(W, False, "W"), self._pack(H, True, "HT")
+        return self._mm(A, True, Wp, W.shape[1], out, L=HTp, eps=eps)
+
+    def sqnorm(self, A):
+        if not self._sp(A):
+            return super().sqnorm(A)
+        self._req_sp(A)
+        if A.nnz == 0:
+            return torch.zeros(1, dtype=torch.float64, device=A.device)
+        # the value array as a 1 x nnz matrix.  dnmf_sqnorm ends in a float64 atomic sum whose order varies between runs, and
+        # ||A||^2 never changes during a fit (BCD asks for it per fit, relative_err per fit): evaluated once per block and kept
+        if getattr(A, "_sqnorm", None) is None:
+            A._sqnorm = super().sqnorm(A.val.view(1, -1))
+        return A._sqnorm.clone()
+
+    def resid_sqnorm(self, A, W, H):
+        if not self._sp(A):
+            return super().resid_sqnorm(A, W, H)
+        self._req_sp(A)
+        m, n = A.shape
+        k = W.shape[1]
+        Wp, HTp = self._pack(W, False, "W"), self._pack(H, True, "HT")
+        out = torch.empty(1, dtype=torch.float64, device=A.device)
+        ws = self._ws(A, k)
+        check(lib.dnmf_csr_resid_sqnorm(A.crow.data_ptr(), A.col.data_ptr(), A.val.data_ptr(), m, n, Wp.data_ptr(), HTp.data_ptr(), int(k),
+                                        A.long_rows.data_ptr() if A.n_long else None, A.long_segptr.data_ptr() if A.n_long else None,
+                                        A.n_long, A.nseg, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        return out
+
+    def _dense_only(self, what, A):
+        if self._sp(A):
+            raise NotImplementedError("%s is not provided for sparse data (the choreography sequences the sparse primitives)" % what)
+
+    def mu_fro_step(self, A, W, H, eps, w_update=True, clamp=False):
+        self._dense_only("the fused local MU/FRO step", A)
+        return super().mu_fro_step(A, W, H, eps, w_update, clamp)
+
+    def mu_kl_step(self, A, W, H, eps, w_update=True, clamp=False):
+        self._dense_only("the fused local MU/KL step", A)
+        return super().mu_kl_step(A, W, H, eps, w_update, clamp)
+
+    def fit(self, method, norm, A, W, H, eps, w_update, itr, column_sweep=False):
+        self._dense_only("a whole-fit entry point", A)
+        return super().fit(method, norm, A, W, H, eps, w_update, itr, column_sweep=column_sweep)
+
+    def column_err_sums(self, A, W, H):
+        self._dense_only("the per-column error of NMFk", A)
+        return super().column_err_sums(A, W, H)
+
+
+HIP_CSR_OPS = HipCsrOps()
+
+
 class HipOpsF64:
     """The operator set in float64 (csrc/dnmf_f64.hip: the fp64 matrix cores, one plain tile shape per kernel family).  The
     reference computes in the dtype of A_ij (pyDNMF.py:68): float64 data are factorised in float64, eps = 2.22e-16.  The same
@@ -1289,9 +1451,14 @@ def native_comm_for(params):
     return nc
 
 
-def ops_for(params=None, dtype=None):
+def ops_for(params=None, dtype=None, sparse=False):
     """The operator set `params` asks for: `params.gemm` = 'fp32' (default: the fp32-MFMA contractions, the parity
-    reference) or 'bf16x6' (HipOpsBf16x6); float64 data (`dtype`) take the float64 set whatever `gemm` says."""
+    reference) or 'bf16x6' (HipOpsBf16x6); float64 data (`dtype`) take the float64 set whatever `gemm` says.  `sparse`: the
+    data block is a SparseBlock -- HipCsrOps (float32 values, fp32 arithmetic only)."""
+    if sparse:
+        if (getattr(params, "gemm", None) or "fp32") != "fp32":
+            raise NotImplementedError("params.gemm = %r is not provided for sparse data (fp32 arithmetic only)" % (params.gemm,))
+        return HIP_CSR_OPS
     if dtype is torch.float64:
         return HIP_OPS_F64
     mode = getattr(params, "gemm", None) or "fp32"

@@ -60,25 +60,36 @@ class PyNMF:
     """Reference pyDNMF.py:6-239 (the MU path of it)."""
 
     def __init__(self, A_ij, factors=None, save_factors=False, params=None, ops=None):
-        self._numpy_io = not isinstance(A_ij, torch.Tensor)
+        from .sparse import is_sparse_input
+        self._sparse = is_sparse_input(A_ij)
+        # (sparse data: scipy input is numpy I/O, torch sparse tensors and SparseBlocks get CUDA tensors back)
+        self._numpy_io = not (isinstance(A_ij, torch.Tensor) or getattr(A_ij, "is_sparse_block", False))
         self.ops = ops
         if ops is None:
-            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda:
+            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda and not self._sparse:
                 raise TypeError("PyNMF: A_ij is a CPU tensor; pass a CUDA tensor or a numpy array (no CPU fallback)")
             if not torch.cuda.is_available():
                 raise RuntimeError("PyNMF: no GPU visible; the MI355X engine has no CPU fallback")
-            device = A_ij.device if isinstance(A_ij, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+            device = A_ij.device if isinstance(A_ij, torch.Tensor) and A_ij.is_cuda or getattr(A_ij, "is_sparse_block", False) \
+                else torch.device("cuda", torch.cuda.current_device())
         else:
-            device = A_ij.device if isinstance(A_ij, torch.Tensor) else torch.device("cpu")
+            device = A_ij.device if isinstance(A_ij, torch.Tensor) or getattr(A_ij, "is_sparse_block", False) else torch.device("cpu")
         self.device = device
         if ops is None and getattr(params, "shared_gpu", False):
             # (main.py --shared_gpu / params.shared_gpu = True) the launch-chain kernels from the start: no kernel of this process waits
             # for co-resident workgroups, so none can time out behind a co-tenant
             from ._lib import lib
             lib.dnmf_set_persistent(0)
-        self.a_dtype = storage_dtype(A_ij, params)
+        if self._sparse:
+            self.a_dtype = self._sparse_checks(A_ij, params)
+        else:
+            self.a_dtype = storage_dtype(A_ij, params)
         self.c_dtype = torch.float64 if self.a_dtype == torch.float64 else torch.float32      # factors, products, eps
-        self.A_ij = _to_device(A_ij, device, self.a_dtype)
+        if self._sparse:
+            from .sparse import SparseBlock
+            self.A_ij = SparseBlock.from_any(A_ij, device)
+        else:
+            self.A_ij = _to_device(A_ij, device, self.a_dtype)
         self.params = params
         self.m_loc, self.n_loc = self.A_ij.shape
         self.init = self.params.init if getattr(self.params, "init", None) else 'rand'
@@ -136,9 +147,27 @@ class PyNMF:
         elif hasattr(self.params, "_slice_counts"):
             del self.params._slice_counts
 
+    @staticmethod
+    def _sparse_checks(A_ij, params):
+        """What is refused for sparse data, each by name (float32 values, fp32 arithmetic, 1D grids, init='rand' or factors)."""
+        prec = getattr(params, "precision", None)
+        if isinstance(prec, str) and prec.lower() in ("bfloat16", "bf16") or prec is torch.bfloat16:
+            raise NotImplementedError("precision='bfloat16' is not provided for sparse data (float32 values only)")
+        dt = getattr(A_ij, "dtype", None)
+        if dt in (torch.float64, np.dtype("float64")):
+            raise NotImplementedError("float64 sparse data are not provided (float32 values only); cast the values to float32")
+        if (getattr(params, "gemm", None) or "fp32") != "fp32":
+            raise NotImplementedError("--gemm %s is not provided for sparse data (fp32 arithmetic only)" % params.gemm)
+        grid = getattr(params, "grid", None) or (getattr(params, "p_r", 1), getattr(params, "p_c", 1))
+        if grid[0] != 1 and grid[1] != 1:
+            raise NotImplementedError("sparse data on a 2D grid (%d x %d) are not provided: use a 1D grid (p_r = 1 or p_c = 1)" % (grid[0], grid[1]))
+        return torch.float32
+
     def init_factors(self):
         """pyDNMF.py:107-135, init='rand': uniform [0,1) from the process-global numpy RNG (so seeding numpy
         reproduces the reference's draw order), cast to float32; the replicated factor is broadcast from rank 0."""
+        if self.init == 'nnsvd' and self._sparse:
+            raise NotImplementedError("init='nnsvd' is not provided for sparse data: init='rand' or factors=...")
         if self.init == 'nnsvd':                                    # pyDNMF.py:130-135
             if self.topo != '1d':
                 raise Exception('NNSVD init only available for 1D topology, please try with 1d topo.')
@@ -190,7 +219,7 @@ class PyNMF:
     def _ops(self):
         if self.ops is None:
             from .engine import ops_for
-            self.ops = ops_for(self.params, self.c_dtype)
+            self.ops = ops_for(self.params, self.c_dtype, sparse=self._sparse)
         return self.ops
 
     def _out(self, t):
@@ -264,7 +293,7 @@ class PyNMF:
         """One rank, the product's own fp32-MFMA operator set, a method / norm pair the library has a whole-fit entry point for
         (anything else keeps the step loop, which raises the reference's messages for invalid pairs).  `params.fit_loop =
         'python'` keeps the step loop (A/B runs, tests of the per-step API)."""
-        return (self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") in ("hip", "hip-f64") and hasattr(ops, "fit")
+        return (not self._sparse and self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") in ("hip", "hip-f64") and hasattr(ops, "fit")
                 and not (getattr(ops, "name", "") == "hip-f64" and self.k > 128)
                 and (str(self.method).lower(), str(self.norm).lower()) in _NATIVE_FITS
                 and not (str(self.method).lower() == "bcd" and (getattr(ops, "name", "") != "hip" or self.a_dtype != torch.float32))

@@ -82,6 +82,10 @@ class PyNMFk:
     """pyDNMFk.py:70-299."""
 
     def __init__(self, A_ij, factors=None, params=None, ops=None):
+        from .sparse import is_sparse_input
+        if is_sparse_input(A_ij):
+            raise NotImplementedError("PyNMFk on sparse data is not provided: the perturbation kernel is keyed by dense element "
+                                      "position (PyNMF factorises sparse data at a given k)")
         self.A_ij = A_ij
         self.ops = ops
         self.local_m, self.local_n = self.A_ij.shape
