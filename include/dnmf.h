@@ -619,6 +619,37 @@ int dnmf_csr_resid_sqnorm(const int* rowptr, const int* col, const float* val, l
                           int k, const int* long_rows, const int* long_segptr, int n_long, int nseg, double* sq, void* ws,
                           size_t ws_bytes, void* stream);
 
+/* ---- A sparse block whose UNSTORED entries are MISSING (not observed; no reference counterpart: the reference's rules with every sum
+ * restricted to the stored positions Omega of the block).  A stored zero is an observation.  Objective 'fro': sum over Omega of
+ * (a - (W H))^2; 'kl': the quotient rule with both sums over Omega.  With d = <Lp[r], Fp[col[p]]> formed per stored entry p of row r:
+ *     kl == 0:  num[r] = sum_p val[p] Fp[col[p]]             den[r] = sum_p d Fp[col[p]]       (A H^T and P_Omega(W H) H^T)
+ *     kl != 0:  num[r] = sum_p val[p] / (d + eps) Fp[col[p]]   den[r] = sum_p Fp[col[p]]
+ * On the block's CSR with Lp = packed W, Fp = packed H^T these are the two sides of the W rule (dist_nmf.py:729-732, KL :806-810 and
+ * :827-830); on the transpose's CSR with Lp = packed H^T, Fp = packed W and out_trans != 0, of the H rule (:748-751, KL :846-849).  On a
+ * fully stored block they are the reference's rules up to summation order.  Rows without a stored entry give exact zeros.  Same CSR,
+ * packed-image and long-row arguments as dnmf_csr_kl_mm; no atomics: bit-reproducible.
+ * `ws`: dnmf_csr_masked_ws_bytes(m, n, k, nseg) bytes (the larger nseg of the two images; long rows leave PAIRS of partial rows). */
+size_t dnmf_csr_masked_ws_bytes(long m, long n, int k, int nseg);
+/* the pair stored: num and den [rows x k] (out_trans != 0: [k x rows]) with the same leading dimension ldo -- the two halves of one
+ * contiguous buffer where the sums cross ranks (one allreduce, then dnmf_csr_ratio_update) */
+int dnmf_csr_masked_mm(const int* rowptr, const int* col, const float* val, long rows, const float* Lp, const float* Fp, int k,
+                       float eps, int kl, float* num, float* den, long ldo, int out_trans, const int* long_rows,
+                       const int* long_segptr, int n_long, int nseg, void* ws, size_t ws_bytes, void* stream);
+/* the pair applied where nothing crosses ranks: X[r] = Lp[r] * num[r] / (den[r] + eps), max(., eps) if clamp != 0 (pyDNMF.py:170-172).
+ * X is the factor itself (W [rows x k], or H [k x rows] with out_trans != 0) and Lp its packed copy: X is written, never read. */
+int dnmf_csr_masked_update(const int* rowptr, const int* col, const float* val, long rows, const float* Lp, const float* Fp, int k,
+                           float eps, int kl, int clamp, float* X, long ldx, int out_trans, const int* long_rows,
+                           const int* long_segptr, int n_long, int nseg, void* ws, size_t ws_bytes, void* stream);
+/* X <- X * num / (den + eps), max(., eps) if clamp != 0: the multiply-divide of dist_nmf.py:731-732, :750-751, :828-830, :847-849 on a
+ * summed pair.  X [rows x cols], ldx; num, den [rows x cols], ldp. */
+int dnmf_csr_ratio_update(float* X, long rows, long cols, long ldx, const float* num, const float* den, long ldp, float eps,
+                          int clamp, void* stream);
+/* sq[0] = ||P_Omega(A - W H)||_F^2 (pyDNMF.py:205-218 over the stored positions): sum of (a - d)^2 with d and the sum in float64, a
+ * fixed number of waves and one workgroup adding their partials in a fixed order.  Block's CSR, Wp = packed W, HTp = packed H^T. */
+int dnmf_csr_masked_resid_sqnorm(const int* rowptr, const int* col, const float* val, long m, long n, const float* Wp,
+                                 const float* HTp, int k, const int* long_rows, const int* long_segptr, int n_long, int nseg,
+                                 double* sq, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- measurement aid (no counterpart in the reference) ----
  * Which shader clock does the GPU hold right now?  Launches ONE wave on `stream` that writes `n` pairs {s_memtime (shader
  * cycles), wall_clock64 (the constant 100 MHz reference)} into samples[2 n], sleeping `naps` x ~4 us between two pairs, and

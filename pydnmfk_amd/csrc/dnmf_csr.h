@@ -4,6 +4,13 @@
 //     mm      Out[r] = sum_p val[p] F[col[p]]                                   (A H^T on the block, (W^T A)^T on the transpose)
 //     kl_mm   Out[r] = sum_p val[p] / (<L[r], F[col[p]]> + eps) F[col[p]]       (the KL products, quotient fused)
 //     resid   sum_p val[p] (val[p] - 2 <L[r], F[col[p]]>) in float64           (||A - W H||^2 minus the Gram term)
+// A block whose UNSTORED entries are missing (not observed) restricts the objective to the stored positions: its passes have the
+// same shape but leave TWO k-vectors per row, the numerator and the denominator of the multiplicative rule,
+//     m_fro   num[r] = sum_p val[p] F[col[p]],                      den[r] = sum_p <L[r], F[col[p]]> F[col[p]]
+//     m_kl    num[r] = sum_p val[p] / (<L[r], F[col[p]]> + eps) F[col[p]],   den[r] = sum_p F[col[p]]
+//     m_resid sum_p (val[p] - <L[r], F[col[p]]>)^2 in float64        (no Gram term: nothing outside the stored positions counts)
+// and end either by storing the pair (the sides whose sums cross ranks) or, the wave holding L[r] in registers, by writing
+// X[r] = L[r] * num / (den + eps) straight into the factor (it reads the packed copy, so nothing is updated under a reader).
 // F and L are PACKED factor images [rows x KPAD] (csr_pack_kernel / csr_pack_t_kernel): KPAD = 16 / 32 / 64 / 128 / 256 floats,
 // zero padded, so that a gathered row is 64 B (inside one 128-byte line) or whole 128-byte lines and is read as one float4 per
 // lane, whatever k is.
@@ -45,10 +52,14 @@ __device__ inline f32x4 csr_fold(f32x4 a) {
     return a;
 }
 
-// MODE 0: mm, 1: kl_mm, 2: resid.  The stored entries [p0, p1) of one row; `lrow` = this lane's float4 of the packed row L[r].
+enum { CSR_MM = 0, CSR_KL_MM = 1, CSR_RESID = 2, CSR_M_FRO = 3, CSR_M_KL = 4, CSR_M_RESID = 5 };
+enum { CSR_END_STORE = 0, CSR_END_UPDATE = 1 };     // masked passes: store [num | den], or write L[r] * num / (den + eps)
+
+// MODE 0: mm, 1: kl_mm, 2: resid, 3: m_fro, 4: m_kl, 5: m_resid.  The stored entries [p0, p1) of one row; `lrow` = this lane's
+// float4 of the packed row L[r]; `acc2` = the denominator's k-vector of the masked passes (untouched by the others).
 template <int G, int MODE>
 __device__ inline void csr_span(const int* __restrict__ col, const float* __restrict__ val, int p0, int p1,
-                                const float* __restrict__ F, const f32x4 lrow, float eps, f32x4& acc, double& dacc) {
+                                const float* __restrict__ F, const f32x4 lrow, float eps, f32x4& acc, f32x4& acc2, double& dacc) {
     constexpr int NG = 64 / G, KPAD = 4 * G;
     const int lane = threadIdx.x & 63, grp = lane / G, l = lane % G;
     for (int base = p0; base < p1; base += 64) {
@@ -79,11 +90,33 @@ __device__ inline void csr_span(const int* __restrict__ col, const float* __rest
                     acc.x = fmaf(q, f.x, acc.x); acc.y = fmaf(q, f.y, acc.y);
                     acc.z = fmaf(q, f.z, acc.z); acc.w = fmaf(q, f.w, acc.w);
                 }
+            } else if (MODE == 3 || MODE == 4) {
+                float t = lrow.x * f.x;
+                t = fmaf(lrow.y, f.y, t); t = fmaf(lrow.z, f.z, t); t = fmaf(lrow.w, f.w, t);
+                const float d = csr_sum_in_group<G>(t);
+                if (ok) {
+                    if (MODE == 3) {
+                        acc.x = fmaf(vj, f.x, acc.x); acc.y = fmaf(vj, f.y, acc.y);
+                        acc.z = fmaf(vj, f.z, acc.z); acc.w = fmaf(vj, f.w, acc.w);
+                        acc2.x = fmaf(d, f.x, acc2.x); acc2.y = fmaf(d, f.y, acc2.y);
+                        acc2.z = fmaf(d, f.z, acc2.z); acc2.w = fmaf(d, f.w, acc2.w);
+                    } else {
+                        const float q = vj / (d + eps);             // (a stored zero: q = 0, and it counts in the denominator)
+                        acc.x = fmaf(q, f.x, acc.x); acc.y = fmaf(q, f.y, acc.y);
+                        acc.z = fmaf(q, f.z, acc.z); acc.w = fmaf(q, f.w, acc.w);
+                        acc2.x += f.x; acc2.y += f.y; acc2.z += f.z; acc2.w += f.w;
+                    }
+                }
             } else {
                 double t = (double)lrow.x * (double)f.x;
                 t = fma((double)lrow.y, (double)f.y, t); t = fma((double)lrow.z, (double)f.z, t); t = fma((double)lrow.w, (double)f.w, t);
                 const double d = csr_sum_in_group<G>(t);
-                if (ok && l == 0) dacc += (double)vj * ((double)vj - 2.0 * d);
+                if (MODE == 2) {
+                    if (ok && l == 0) dacc += (double)vj * ((double)vj - 2.0 * d);
+                } else if (ok && l == 0) {
+                    const double e = (double)vj - d;
+                    dacc = fma(e, e, dacc);
+                }
             }
         }
     }
@@ -99,47 +132,85 @@ __device__ inline void csr_store(float* __restrict__ out, long ldo, int out_tran
         }
 }
 
-// one wave per row, four rows per workgroup; rows longer than CSR_SEG are left to the segment kernels
-template <int G, int MODE>
+// the masked passes' pair: num -> out, den -> out2 at the same offsets.  (One loop for both: two csr_store calls in a row crash
+// hipcc 7.2's optimizer at G = 64, where every lane stores.)
+__device__ inline void csr_store_pair(float* __restrict__ out, float* __restrict__ out2, long ldo, int out_trans, long r, int c0,
+                                      const f32x4 a, const f32x4 b, int k) {
+    const float e[4] = {a.x, a.y, a.z, a.w}, g[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (c0 + i < k) {
+            const size_t o = out_trans ? (size_t)(c0 + i) * ldo + r : (size_t)r * ldo + c0 + i;
+            out[o] = e[i];
+            out2[o] = g[i];
+        }
+}
+
+// the multiplicative rule on this lane's float4: x * num / (den + eps), optionally clamped from below (0 / (0 + eps) = 0 stays finite)
+__device__ inline float csr_ratio1(float x, float num, float den, float eps, int clamp) {
+    const float y = x * (num / (den + eps));
+    return clamp ? fmaxf(y, eps) : y;
+}
+
+__device__ inline f32x4 csr_ratio(const f32x4 x, const f32x4 num, const f32x4 den, float eps, int clamp) {
+    return f32x4{csr_ratio1(x.x, num.x, den.x, eps, clamp), csr_ratio1(x.y, num.y, den.y, eps, clamp),
+                 csr_ratio1(x.z, num.z, den.z, eps, clamp), csr_ratio1(x.w, num.w, den.w, eps, clamp)};
+}
+
+// one wave per row, four rows per workgroup; rows longer than CSR_SEG are left to the segment kernels.  Masked passes (MODE 3, 4):
+// END = CSR_END_STORE writes num -> out, den -> out2 (same ld and orientation); CSR_END_UPDATE writes L[r] * num / (den + eps) -> out
+template <int G, int MODE, int END = CSR_END_STORE>
 __global__ __launch_bounds__(256) void csr_rows_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                        const float* __restrict__ val, long rows, const float* __restrict__ L,
                                                        const float* __restrict__ F, int k, float eps, float* __restrict__ out,
-                                                       long ldo, int out_trans) {
+                                                       long ldo, int out_trans, float* __restrict__ out2, int clamp) {
     constexpr int KPAD = 4 * G;
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
     const int lane = threadIdx.x & 63, l = lane % G;
     const int p0 = rowptr[r], p1 = rowptr[r + 1];
     if (p1 - p0 > CSR_SEG) return;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, lrow = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f}, lrow = {0.f, 0.f, 0.f, 0.f};
     double dacc = 0.0;
     if (MODE != 0 && p1 > p0) lrow = *reinterpret_cast<const f32x4*>(L + (size_t)r * KPAD + 4 * l);
-    csr_span<G, MODE>(col, val, p0, p1, F, lrow, eps, acc, dacc);
+    csr_span<G, MODE>(col, val, p0, p1, F, lrow, eps, acc, acc2, dacc);
     acc = csr_fold<G>(acc);
-    if (lane < G) csr_store(out, ldo, out_trans, r, 4 * l, acc, k);
+    if (MODE == 3 || MODE == 4) {
+        acc2 = csr_fold<G>(acc2);
+        if (lane < G) {
+            if (END == CSR_END_STORE) {
+                csr_store_pair(out, out2, ldo, out_trans, r, 4 * l, acc, acc2, k);
+            } else {                                              // (a row without a stored entry: num = 0, the row becomes 0)
+                csr_store(out, ldo, out_trans, r, 4 * l, csr_ratio(lrow, acc, acc2, eps, clamp), k);
+            }
+        }
+    } else if (lane < G) {
+        csr_store(out, ldo, out_trans, r, 4 * l, acc, k);
+    }
 }
 
 // the residual's pass over the rows: a fixed number of waves, wave w takes rows w, w + nw, ... and leaves ONE float64 partial
-template <int G>
+template <int G, int MODE = 2>
 __global__ __launch_bounds__(256) void csr_resid_rows_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                              const float* __restrict__ val, long rows, const float* __restrict__ L,
                                                              const float* __restrict__ F, double* __restrict__ dpart) {
     constexpr int KPAD = 4 * G;
     const long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (long)gridDim.x * 4;
     const int lane = threadIdx.x & 63, l = lane % G;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
     double dacc = 0.0;
     for (long r = w; r < rows; r += nw) {
         const int p0 = rowptr[r], p1 = rowptr[r + 1];
         if (p1 == p0 || p1 - p0 > CSR_SEG) continue;
         const f32x4 lrow = *reinterpret_cast<const f32x4*>(L + (size_t)r * KPAD + 4 * l);
-        csr_span<G, 2>(col, val, p0, p1, F, lrow, 0.f, acc, dacc);
+        csr_span<G, MODE>(col, val, p0, p1, F, lrow, 0.f, acc, acc2, dacc);
     }
     dacc = csr_sum_over_groups<G>(dacc);
     if (lane == 0) dpart[w] = dacc;
 }
 
-// one wave per segment of a long row: partial rows [nseg][KPAD] (MODE 0, 1) or one float64 per segment (MODE 2)
+// one wave per segment of a long row: partial rows [nseg][KPAD] (MODE 0, 1), partial pairs [nseg][num | den][KPAD] (MODE 3, 4) or one
+// float64 per segment (MODE 2, 5)
 template <int G, int MODE>
 __global__ __launch_bounds__(256) void csr_long_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                        const float* __restrict__ val, const float* __restrict__ L,
@@ -157,13 +228,20 @@ __global__ __launch_bounds__(256) void csr_long_kernel(const int* __restrict__ r
     const long r = long_rows[lo];
     const int lane = threadIdx.x & 63, l = lane % G;
     const int p0 = rowptr[r] + (s - long_segptr[lo]) * CSR_SEG, p1 = min(p0 + CSR_SEG, rowptr[r + 1]);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, lrow = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f}, lrow = {0.f, 0.f, 0.f, 0.f};
     double dacc = 0.0;
     if (MODE != 0) lrow = *reinterpret_cast<const f32x4*>(L + (size_t)r * KPAD + 4 * l);
-    csr_span<G, MODE>(col, val, p0, p1, F, lrow, eps, acc, dacc);
-    if (MODE == 2) {
+    csr_span<G, MODE>(col, val, p0, p1, F, lrow, eps, acc, acc2, dacc);
+    if (MODE == 2 || MODE == 5) {
         dacc = csr_sum_over_groups<G>(dacc);
         if (lane == 0) dpart[s] = dacc;
+    } else if (MODE == 3 || MODE == 4) {
+        acc = csr_fold<G>(acc);
+        acc2 = csr_fold<G>(acc2);
+        if (lane < G) {
+            *reinterpret_cast<f32x4*>(part + ((size_t)s * 2) * KPAD + 4 * l) = acc;
+            *reinterpret_cast<f32x4*>(part + ((size_t)s * 2 + 1) * KPAD + 4 * l) = acc2;
+        }
     } else {
         acc = csr_fold<G>(acc);
         if (lane < G) *reinterpret_cast<f32x4*>(part + (size_t)s * KPAD + 4 * l) = acc;
@@ -180,6 +258,49 @@ __global__ void csr_long_reduce_kernel(const float* __restrict__ part, int kpad,
     if (c < k) {
         if (out_trans) out[(size_t)c * ldo + r] = a;
         else out[(size_t)r * ldo + c] = a;
+    }
+}
+
+// a long row's partial pairs [num | den] added in segment order, then stored as a pair (END = CSR_END_STORE: num -> out, den ->
+// out2) or applied (CSR_END_UPDATE: L[r] * num / (den + eps) -> out): one workgroup of `kpad` threads per long row
+template <int END>
+__global__ void csr_long_reduce_pair_kernel(const float* __restrict__ part, int kpad, const int* __restrict__ long_rows,
+                                            const int* __restrict__ long_segptr, const float* __restrict__ L, int k, float eps, int clamp,
+                                            float* __restrict__ out, float* __restrict__ out2, long ldo, int out_trans) {
+    const int i = blockIdx.x, c = threadIdx.x;
+    const long r = long_rows[i];
+    float a = 0.f, b = 0.f;
+    for (int s = long_segptr[i]; s < long_segptr[i + 1]; ++s) {
+        a += part[((size_t)s * 2) * kpad + c];
+        b += part[((size_t)s * 2 + 1) * kpad + c];
+    }
+    if (c < k) {
+        const size_t o = out_trans ? (size_t)c * ldo + r : (size_t)r * ldo + c;
+        if (END == CSR_END_STORE) {
+            out[o] = a;
+            out2[o] = b;
+        } else {
+            out[o] = csr_ratio1(L[(size_t)r * kpad + c], a, b, eps, clamp);
+        }
+    }
+}
+
+// X = X * num / (den + eps), optionally clamped from below: the multiplicative rule after the pair has been summed over the ranks.
+// X [rows x cols] with leading dimension ldx; num and den [rows x cols] with leading dimension ldp.  V = 4: 16-byte accesses.
+template <int V>
+__global__ __launch_bounds__(256) void csr_ratio_kernel(float* __restrict__ X, long rows, long cols, long ldx, const float* __restrict__ num,
+                                                        const float* __restrict__ den, long ldp, float eps, int clamp) {
+    const long cv = cols / V, total = rows * cv;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long r = idx / cv, c = (idx % cv) * V;
+        if (V == 4) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(X + r * ldx + c);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(num + r * ldp + c);
+            const f32x4 b = *reinterpret_cast<const f32x4*>(den + r * ldp + c);
+            *reinterpret_cast<f32x4*>(X + r * ldx + c) = csr_ratio(x, a, b, eps, clamp);
+        } else {
+            X[r * ldx + c] = csr_ratio1(X[r * ldx + c], num[r * ldp + c], den[r * ldp + c], eps, clamp);
+        }
     }
 }
 

@@ -1,5 +1,5 @@
 // dnmf_csr.hip -- C ABI of the sparse (CSR) data block: packed factor images, the gather products, the KL products with the
-// quotient fused, and the residual's closed form (csrc/dnmf_csr.h).  A translation unit of its own (see csrc/dnmf_kl.hip).
+// quotient fused, the residual's closed form, and the passes of a block whose unstored entries are missing (csrc/dnmf_csr.h).  A translation unit of its own (see csrc/dnmf_kl.hip).
 // Plain launch chains: no workgroup waits for another one.
 #include "dnmf_common.h"
 #include "dnmf_host.h"
@@ -38,12 +38,13 @@ struct CsrArgs {
     const int* rowptr; const int* col; const float* val; long rows;
     const float* L; const float* F; int k; float eps; float* out; long ldo; int out_trans;
     const int* long_rows; const int* long_segptr; int n_long; int nseg; float* part;
+    float* out2 = nullptr; int clamp = 0;              // masked passes: the denominator's half of the pair / the clamp of the fused ending
 };
 
 template <int G, int MODE>
 int csr_launch(const CsrArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((csr_rows_kernel<G, MODE>), dim3((unsigned)cdiv(a.rows, 4)), dim3(256), 0, st, a.rowptr, a.col, a.val, a.rows, a.L,
-                       a.F, a.k, a.eps, a.out, a.ldo, a.out_trans);
+                       a.F, a.k, a.eps, a.out, a.ldo, a.out_trans, (float*)nullptr, 0);
     if (a.n_long > 0) {
         hipLaunchKernelGGL((csr_long_kernel<G, MODE>), dim3((unsigned)cdiv(a.nseg, 4)), dim3(256), 0, st, a.rowptr, a.col, a.val, a.L, a.F,
                            a.eps, a.long_rows, a.long_segptr, a.n_long, a.part, (double*)nullptr);
@@ -51,6 +52,48 @@ int csr_launch(const CsrArgs& a, hipStream_t st) {
                            a.long_segptr, a.k, a.out, a.ldo, a.out_trans);
     }
     return check_launch(MODE ? "csr_kl_mm" : "csr_mm");
+}
+
+// masked passes (MODE 3: Frobenius, 4: KL): the pair [num | den] is stored (END = CSR_END_STORE) or applied to the factor `out`
+template <int G, int MODE, int END>
+int csr_masked_launch(const CsrArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL((csr_rows_kernel<G, MODE, END>), dim3((unsigned)cdiv(a.rows, 4)), dim3(256), 0, st, a.rowptr, a.col, a.val, a.rows, a.L,
+                       a.F, a.k, a.eps, a.out, a.ldo, a.out_trans, a.out2, a.clamp);
+    if (a.n_long > 0) {
+        hipLaunchKernelGGL((csr_long_kernel<G, MODE>), dim3((unsigned)cdiv(a.nseg, 4)), dim3(256), 0, st, a.rowptr, a.col, a.val, a.L, a.F,
+                           a.eps, a.long_rows, a.long_segptr, a.n_long, a.part, (double*)nullptr);
+        hipLaunchKernelGGL((csr_long_reduce_pair_kernel<END>), dim3((unsigned)a.n_long), dim3(4 * G), 0, st, (const float*)a.part, 4 * G,
+                           a.long_rows, a.long_segptr, a.L, a.k, a.eps, a.clamp, a.out, a.out2, a.ldo, a.out_trans);
+    }
+    return check_launch(END == CSR_END_STORE ? "csr_masked_mm" : "csr_masked_update");
+}
+
+template <int MODE, int END>
+int csr_masked_dispatch(const CsrArgs& a, hipStream_t st) {
+    switch (csr_kpad_of(a.k)) {
+        case 16: return csr_masked_launch<4, MODE, END>(a, st);
+        case 32: return csr_masked_launch<8, MODE, END>(a, st);
+        case 64: return csr_masked_launch<16, MODE, END>(a, st);
+        case 128: return csr_masked_launch<32, MODE, END>(a, st);
+        default: return csr_masked_launch<64, MODE, END>(a, st);
+    }
+}
+
+template <int G>
+int masked_resid_launch(const int* rowptr, const int* col, const float* val, long rows, const float* Wp, const float* HTp, const int* long_rows,
+                        const int* long_segptr, int n_long, int nseg, double* dpart, long nw, hipStream_t st) {
+    hipLaunchKernelGGL((csr_resid_rows_kernel<G, CSR_M_RESID>), dim3((unsigned)(nw / 4)), dim3(256), 0, st, rowptr, col, val, rows, Wp, HTp, dpart);
+    if (n_long > 0)
+        hipLaunchKernelGGL((csr_long_kernel<G, CSR_M_RESID>), dim3((unsigned)cdiv(nseg, 4)), dim3(256), 0, st, rowptr, col, val, Wp, HTp, 0.f,
+                           long_rows, long_segptr, n_long, (float*)nullptr, dpart + nw);
+    return check_launch("csr_masked_resid_sqnorm");
+}
+
+// workspace of the masked passes: the partial PAIRS of the long rows, or the residual's float64 partials
+inline size_t masked_ws_need(long rows, int k, long nseg) {
+    const size_t pairs = align256((size_t)nseg * 2 * csr_kpad_of(k) * sizeof(float));
+    const size_t dparts = align256((size_t)(resid_waves(rows) + nseg) * sizeof(double));
+    return std::max<size_t>(256, std::max(pairs, dparts));
 }
 
 template <int MODE>
@@ -164,6 +207,81 @@ int dnmf_csr_resid_sqnorm(const int* rowptr, const int* col, const float* val, l
     hipLaunchKernelGGL(csr_resid_final_kernel, dim3(1), dim3(256), 0, st, (const double*)gw, L.ncw, (const double*)gh, L.nch, k,
                        (const double*)dpart, L.nw + (n_long > 0 ? nseg : 0), sq);
     return check_launch("csr_resid_sqnorm");
+}
+
+size_t dnmf_csr_masked_ws_bytes(long rows, long cols, int k, int nseg) {
+    if (rows < 1 || cols < 1 || nseg < 0 || csr_kpad_of(k) < 0) return 0;
+    return masked_ws_need(std::max(rows, cols), k, nseg);
+}
+
+// The Frobenius rule W <- W * (A H^T) / (W H H^T + eps) (dist_nmf.py:729-732; H: :748-751) and the KL rule W <- W * (U H^T) / (rowsum(H) + eps)
+// with U = A / (W H + eps) (dist_nmf.py:806-810, :827-830; H: :846-849), both sums of the numerator AND of the denominator restricted to
+// the stored positions: num and den of a row, stored as a pair
+int dnmf_csr_masked_mm(const int* rowptr, const int* col, const float* val, long rows, const float* Lp, const float* Fp, int k, float eps,
+                       int kl, float* num, float* den, long ldo, int out_trans, const int* long_rows, const int* long_segptr, int n_long,
+                       int nseg, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_common("csr_masked_mm", rowptr, col, val, rows, k, long_rows, long_segptr, n_long, nseg)) return rc;
+    REQUIRE(Lp && Fp && num && den && aligned16(Lp) && aligned16(Fp) && ldo >= (out_trans ? rows : (long)k),
+            "csr_masked_mm: null / misaligned operand or ld too small");
+    const size_t need = (size_t)nseg * 2 * csr_kpad_of(k) * sizeof(float);
+    if (n_long > 0 && (!ws || ws_bytes < need || !aligned16(ws))) return fail(DNMF_EWS, "csr_masked_mm: workspace %zu < %zu bytes", ws_bytes, need);
+    CsrArgs a{rowptr, col, val, rows, Lp, Fp, k, eps, num, ldo, out_trans, long_rows, long_segptr, n_long, nseg, (float*)ws};
+    a.out2 = den;
+    return kl ? csr_masked_dispatch<CSR_M_KL, CSR_END_STORE>(a, S(stream)) : csr_masked_dispatch<CSR_M_FRO, CSR_END_STORE>(a, S(stream));
+}
+
+// The same two rules (dist_nmf.py:729-732 / :748-751; :827-830 / :846-849) applied where nothing crosses ranks: the wave that owns row r
+// holds Lp[r] (the packed copy of the factor's row) and writes X[r] = Lp[r] * num / (den + eps), max(., eps) with `clamp` (pyDNMF.py:170-172)
+int dnmf_csr_masked_update(const int* rowptr, const int* col, const float* val, long rows, const float* Lp, const float* Fp, int k, float eps,
+                           int kl, int clamp, float* X, long ldx, int out_trans, const int* long_rows, const int* long_segptr, int n_long,
+                           int nseg, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_common("csr_masked_update", rowptr, col, val, rows, k, long_rows, long_segptr, n_long, nseg)) return rc;
+    REQUIRE(Lp && Fp && X && aligned16(Lp) && aligned16(Fp) && ldx >= (out_trans ? rows : (long)k),
+            "csr_masked_update: null / misaligned operand or ld too small");
+    const size_t need = (size_t)nseg * 2 * csr_kpad_of(k) * sizeof(float);
+    if (n_long > 0 && (!ws || ws_bytes < need || !aligned16(ws))) return fail(DNMF_EWS, "csr_masked_update: workspace %zu < %zu bytes", ws_bytes, need);
+    CsrArgs a{rowptr, col, val, rows, Lp, Fp, k, eps, X, ldx, out_trans, long_rows, long_segptr, n_long, nseg, (float*)ws};
+    a.clamp = clamp != 0;
+    return kl ? csr_masked_dispatch<CSR_M_KL, CSR_END_UPDATE>(a, S(stream)) : csr_masked_dispatch<CSR_M_FRO, CSR_END_UPDATE>(a, S(stream));
+}
+
+// X <- X * num / (den + eps) (the multiply-divide of dist_nmf.py:731-732, :750-751, :828-830, :847-849) after the pair was summed over ranks
+int dnmf_csr_ratio_update(float* X, long rows, long cols, long ldx, const float* num, const float* den, long ldp, float eps, int clamp,
+                          void* stream) {
+    REQUIRE(X && num && den && rows >= 1 && cols >= 1 && ldx >= cols && ldp >= cols, "csr_ratio_update: null pointer or bad shape");
+    const bool vec = aligned16(X) && aligned16(num) && aligned16(den) && cols % 4 == 0 && ldx % 4 == 0 && ldp % 4 == 0;
+    const long total = rows * (vec ? cols / 4 : cols);
+    const unsigned grid = (unsigned)std::min<long>(cdiv(total, 256), 8192);
+    if (vec) hipLaunchKernelGGL((csr_ratio_kernel<4>), dim3(grid), dim3(256), 0, S(stream), X, rows, cols, ldx, num, den, ldp, eps, clamp != 0);
+    else hipLaunchKernelGGL((csr_ratio_kernel<1>), dim3(grid), dim3(256), 0, S(stream), X, rows, cols, ldx, num, den, ldp, eps, clamp != 0);
+    return check_launch("csr_ratio_update");
+}
+
+// sq[0] = ||P_Omega(A - W H)||_F^2 (pyDNMF.py:205-218 with the sum restricted to the stored positions): sum of (a - d)^2 in float64
+int dnmf_csr_masked_resid_sqnorm(const int* rowptr, const int* col, const float* val, long rows, long cols, const float* Wp, const float* HTp,
+                                 int k, const int* long_rows, const int* long_segptr, int n_long, int nseg, double* sq, void* ws,
+                                 size_t ws_bytes, void* stream) {
+    if (int rc = check_common("csr_masked_resid_sqnorm", rowptr, col, val, rows, k, long_rows, long_segptr, n_long, nseg)) return rc;
+    REQUIRE(Wp && HTp && sq && cols >= 1 && cols < (1L << 31) && aligned16(Wp) && aligned16(HTp),
+            "csr_masked_resid_sqnorm: null / misaligned operand or bad shape");
+    const long nw = resid_waves(rows);
+    const size_t need = (size_t)(nw + nseg) * sizeof(double);
+    if (!ws || ws_bytes < need || !aligned16(ws)) return fail(DNMF_EWS, "csr_masked_resid_sqnorm: workspace %zu < %zu bytes", ws_bytes, need);
+    hipStream_t st = S(stream);
+    double* dpart = (double*)ws;
+    int rc;
+    switch (csr_kpad_of(k)) {
+        case 16: rc = masked_resid_launch<4>(rowptr, col, val, rows, Wp, HTp, long_rows, long_segptr, n_long, nseg, dpart, nw, st); break;
+        case 32: rc = masked_resid_launch<8>(rowptr, col, val, rows, Wp, HTp, long_rows, long_segptr, n_long, nseg, dpart, nw, st); break;
+        case 64: rc = masked_resid_launch<16>(rowptr, col, val, rows, Wp, HTp, long_rows, long_segptr, n_long, nseg, dpart, nw, st); break;
+        case 128: rc = masked_resid_launch<32>(rowptr, col, val, rows, Wp, HTp, long_rows, long_segptr, n_long, nseg, dpart, nw, st); break;
+        default: rc = masked_resid_launch<64>(rowptr, col, val, rows, Wp, HTp, long_rows, long_segptr, n_long, nseg, dpart, nw, st); break;
+    }
+    if (rc) return rc;
+    // (no Gram term: zero chunks of both Gram matrices, k = 0)
+    hipLaunchKernelGGL(csr_resid_final_kernel, dim3(1), dim3(256), 0, st, (const double*)nullptr, 0, (const double*)nullptr, 0, 0,
+                       (const double*)dpart, nw + (n_long > 0 ? nseg : 0), sq);
+    return check_launch("csr_masked_resid_sqnorm");
 }
 
 }  // extern "C"

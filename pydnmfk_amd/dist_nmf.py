@@ -49,6 +49,12 @@ def _is_sparse(A):
     return bool(getattr(A, "is_sparse_block", False))
 
 
+def _is_masked(A):
+    """the sparse block's UNSTORED entries are missing (SparseBlock.missing == 'unstored'): objective, rules and error over the stored
+    positions only"""
+    return _is_sparse(A) and getattr(A, "missing", None) == "unstored"
+
+
 def _kp(k):
     """the padded rank of the k x k buffers (dnmf_kp): 32 / 64 / 128, and 256 for the wide ranks 128 < k <= 256 (csrc/dnmf_wide.hip)"""
     if k < 1 or k > 256:
@@ -63,6 +69,9 @@ def _pad64(x):
 class _Base:
     def _dispatch(self, clamp):
         norm, method = self.norm.upper(), self.method.upper()
+        if _is_masked(self.A_ij) and method in ('HALS', 'BCD'):
+            raise NotImplementedError("missing='unstored' is provided for method 'mu' (fro / kl) only, not for '%s': HALS and BCD "
+                                      "contract with Gram matrices, which count every position" % self.method)
         if norm == 'FRO':
             if method == 'MU':
                 self.Fro_MU_update(self.W_update, clamp)
@@ -250,9 +259,36 @@ class nmf_algorithms_1D(_Base):
             self.comm1.allreduce_(r)
         return r
 
+    # ---- a block whose unstored entries are missing: the rules of :716-751 (fro) and :806-849 (kl) with every sum over the stored
+    # positions.  Numerator AND denominator then depend on the pattern, so what crosses ranks is the pair [num | den]
+    def _masked_MU_update(self, norm, W_update=True, clamp=False):
+        ops, A, W, H, eps, k = self.ops, self.A_ij, self.W_i, self.H_j, self.eps, self.k
+        if not hasattr(ops, "masked_update_w"):
+            raise NotImplementedError("missing='unstored': the '%s' operator set has no masked operations" % getattr(ops, "name", "?"))
+        m_l, n_l = A.shape
+        if W_update:
+            if self.p_c == 1:                                      # the reference exchanges nothing here: the pass writes W
+                ops.masked_update_w(A, W, H, eps, norm)
+            else:
+                buf = _buf(("mnd_w", m_l, k), 2 * m_l * k, A)[: 2 * m_l * k]
+                num, den = ops.masked_aht_pair(A, W, H, eps, norm, buf)
+                self.comm1.allreduce_(buf)                         # where :707 sums A H^T (fro) / :797 sums U H^T (kl)
+                ops.ratio_update(W, num, den, eps)
+        if self.p_r == 1:
+            ops.masked_update_h(A, W, H, eps, norm, clamp)
+        else:
+            buf = _buf(("mnd_h", k, n_l), 2 * k * n_l, A)[: 2 * k * n_l]
+            num, den = ops.masked_wta_pair(A, W, H, eps, norm, buf)
+            self.comm1.allreduce_(buf)
+            ops.ratio_update(H, num, den, eps, clamp)
+        if clamp:
+            ops.clamp_min(W, eps)
+
     # ---- Frobenius (dist_nmf.py:716-771)
     def Fro_MU_update(self, W_update=True, clamp=False):
         ops, A, W, H, eps, k = self.ops, self.A_ij, self.W_i, self.H_j, self.eps, self.k
+        if _is_masked(A):
+            return self._masked_MU_update('fro', W_update, clamp)
         if self.p == 1 and hasattr(ops, "mu_fro_step") and not _is_sparse(A):
             ops.mu_fro_step(A, W, H, eps, W_update, clamp)         # whole local step, one library call
             return
@@ -358,6 +394,8 @@ class nmf_algorithms_1D(_Base):
     # ---- KL (dist_nmf.py:776-869)
     def KL_MU_update(self, W_update=True, clamp=False):
         ops, A, W, H, eps, k = self.ops, self.A_ij, self.W_i, self.H_j, self.eps, self.k
+        if _is_masked(A):                                          # (no rowsum / colsum vector: the sums run over the stored positions)
+            return self._masked_MU_update('kl', W_update, clamp)
         if self.p == 1 and hasattr(ops, "mu_kl_step") and not _is_sparse(A):
             ops.mu_kl_step(A, W, H, eps, W_update, clamp)
             return

@@ -657,7 +657,11 @@ class HipCsrOps(HipOps):
     CSR images (csrc/dnmf_csr.h, `dnmf_csr_*`); everything else of a step -- update kernels, Gram matrices, clamps,
     normalisation -- is the fp32 code of HipOps, which never sees A.  There is no fused local step and no whole fit for sparse
     data (`mu_fro_step`, `mu_kl_step`, `fit` refuse it): the host's choreography sequences the primitives.  A dense tensor
-    in A's place (BCD asks for the squared norms of W and H) takes the dense kernels."""
+    in A's place (BCD asks for the squared norms of W and H) takes the dense kernels.
+    A block whose unstored entries are MISSING (`A.missing == 'unstored'`) takes the masked operations: `masked_aht_pair` /
+    `masked_wta_pair` (numerator and denominator of the rule over the stored positions, as one contiguous [num | den] buffer for
+    ONE allreduce), `ratio_update` after it, and `masked_update_w` / `masked_update_h` where nothing crosses ranks (the pass writes
+    the factor itself); `resid_sqnorm` then sums over the stored positions only."""
 
     name = "hip-csr"
     kl_uht_hblocks = None
@@ -723,6 +727,77 @@ class HipCsrOps(HipOps):
                                      out.data_ptr(), _ld(out), int(transposed), *tail))
         return out
 
+    # ---- a block whose unstored entries are missing (dnmf_csr_masked_*): `norm` = 'fro' or 'kl'
+    def _masked_ws(self, A, k):
+        m, n = A.shape
+        nbytes = lib.dnmf_csr_masked_ws_bytes(int(m), int(n), int(k), int(max(A.nseg, A.t_nseg)))
+        if nbytes == 0:
+            raise ValueError("sparse block: bad problem shape m=%d n=%d k=%d" % (m, n, k))
+        return _scratch(nbytes, A.device)
+
+    def _masked(self, A, transposed, W, H, eps, norm, pair=None, X=None, clamp=False):
+        """one masked pass over the block's image (the W side) or the transpose's (the H side): the pair stored, or applied to X"""
+        self._req_sp(A)
+        if str(norm).lower() not in ("fro", "kl"):
+            raise ValueError("masked update: norm %r (fro / kl)" % (norm,))
+        kl = int(str(norm).lower() == "kl")
+        _req(W, "W")
+        _req(H, "H")
+        k = W.shape[1]
+        Wp, HTp = self._pack(W, False, "W"), self._pack(H, True, "HT")
+        if transposed:
+            crow, col, val, rows = A.t_crow, A.t_col, A.t_val, A.shape[1]
+            lr, ls, nl, ns = A.t_long_rows, A.t_long_segptr, A.t_n_long, A.t_nseg
+            Lp, Fp = HTp, Wp
+        else:
+            crow, col, val, rows = A.crow, A.col, A.val, A.shape[0]
+            lr, ls, nl, ns = A.long_rows, A.long_segptr, A.n_long, A.nseg
+            Lp, Fp = Wp, HTp
+        ws = self._masked_ws(A, k)
+        tail = (lr.data_ptr() if nl else None, ls.data_ptr() if nl else None, nl, ns, ws.data_ptr(), ws.numel(), _stream())
+        head = (crow.data_ptr(), col.data_ptr(), val.data_ptr(), rows, Lp.data_ptr(), Fp.data_ptr(), int(k), float(eps), kl)
+        if X is None:
+            num, den = pair
+            check(lib.dnmf_csr_masked_mm(*head, num.data_ptr(), den.data_ptr(), _ld(num), int(transposed), *tail))
+            return num, den
+        check(lib.dnmf_csr_masked_update(*head, int(bool(clamp)), X.data_ptr(), _ld(X), int(transposed), *tail))
+        return X
+
+    @staticmethod
+    def _halves(buf, shape):
+        r, c = shape
+        if buf.numel() < 2 * r * c or not buf.is_contiguous() or buf.dtype != torch.float32:
+            raise ValueError("masked pair: a contiguous float32 buffer of 2 x %d x %d elements is expected" % (r, c))
+        return buf[: r * c].view(r, c), buf[r * c: 2 * r * c].view(r, c)
+
+    def masked_aht_pair(self, A, W, H, eps, norm, buf):
+        """buf = [num | den], each m x k: A H^T and P(W H) H^T ('fro'), or U H^T and the stored-position row sums of H ('kl')"""
+        return self._masked(A, False, W, H, eps, norm, pair=self._halves(buf, tuple(W.shape)))
+
+    def masked_wta_pair(self, A, W, H, eps, norm, buf):
+        """buf = [num | den], each k x n: W^T A and W^T P(W H) ('fro'), or W^T U and the stored-position column sums of W ('kl')"""
+        return self._masked(A, True, W, H, eps, norm, pair=self._halves(buf, tuple(H.shape)))
+
+    def masked_update_w(self, A, W, H, eps, norm):
+        """W <- W * num / (den + eps) in the pass itself (the W rows of this rank see all their columns)"""
+        return self._masked(A, False, W, H, eps, norm, X=W)
+
+    def masked_update_h(self, A, W, H, eps, norm, clamp=False):
+        """H <- H * num / (den + eps), max(., eps) with `clamp`, in the pass itself (the H columns of this rank see all their rows)"""
+        return self._masked(A, True, W, H, eps, norm, X=H, clamp=clamp)
+
+    def ratio_update(self, X, num, den, eps, clamp=False):
+        """X <- X * num / (den + eps), max(., eps) with `clamp`: the rule on a pair that was summed over the ranks"""
+        _req(X, "X")
+        _req(num, "num")
+        _req(den, "den")
+        if tuple(num.shape) != tuple(X.shape) or tuple(den.shape) != tuple(X.shape) or _ld(num) != _ld(den):
+            raise ValueError("ratio_update: X %s, num %s, den %s" % (tuple(X.shape), tuple(num.shape), tuple(den.shape)))
+        r, c = X.shape
+        check(lib.dnmf_csr_ratio_update(X.data_ptr(), r, c, _ld(X), num.data_ptr(), den.data_ptr(), _ld(num), float(eps), int(bool(clamp)),
+                                        _stream()))
+        return X
+
     def aht(self, A, H, out):
         if not self._sp(A):
             return super().aht(A, H, out)
@@ -784,10 +859,12 @@ class HipCsrOps(HipOps):
         k = W.shape[1]
         Wp, HTp = self._pack(W, False, "W"), self._pack(H, True, "HT")
         out = torch.empty(1, dtype=torch.float64, device=A.device)
-        ws = self._ws(A, k)
-        check(lib.dnmf_csr_resid_sqnorm(A.crow.data_ptr(), A.col.data_ptr(), A.val.data_ptr(), m, n, Wp.data_ptr(), HTp.data_ptr(), int(k),
-                                        A.long_rows.data_ptr() if A.n_long else None, A.long_segptr.data_ptr() if A.n_long else None,
-                                        A.n_long, A.nseg, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        masked = getattr(A, "missing", None) == "unstored"       # ||P(A - W H)||^2 over the stored positions
+        ws = self._masked_ws(A, k) if masked else self._ws(A, k)
+        fn = lib.dnmf_csr_masked_resid_sqnorm if masked else lib.dnmf_csr_resid_sqnorm
+        check(fn(A.crow.data_ptr(), A.col.data_ptr(), A.val.data_ptr(), m, n, Wp.data_ptr(), HTp.data_ptr(), int(k),
+                 A.long_rows.data_ptr() if A.n_long else None, A.long_segptr.data_ptr() if A.n_long else None,
+                 A.n_long, A.nseg, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
         return out
 
     def _dense_only(self, what, A):

@@ -15,6 +15,8 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
     product in float32: the fit equals the float32 fit of the bf16-rounded data (BASELINE config 5);
   * method is 'mu' (fro / kl), 'hals' (fro) or 'bcd' (fro; float32 data with the fp32 operator set -- float64, bf16-stored A and
     --gemm bf16x6 raise NotImplementedError); init is 'rand' or 'nnsvd' (1D grids);
+  * sparse data (pydnmfk_amd.sparse) with `params.missing = 'unstored'`: an unstored entry is NOT OBSERVED instead of zero -- objective,
+    MU rules (fro / kl) and the reported error run over the stored positions only (1D grids, method 'mu'; DESIGN.md "Sparse data");
   * `prune=True` (the reference's default when the attribute is absent) drops all-zero rows / columns before the
     iterations and scatters the factors back afterwards.  numpy callers get float64 factors back in that case, exactly
     as from the reference (its unprune scatters into np.zeros, utils.py:195,198); tensor callers keep float32 on the GPU.
@@ -80,6 +82,7 @@ class PyNMF:
             # for co-resident workgroups, so none can time out behind a co-tenant
             from ._lib import lib
             lib.dnmf_set_persistent(0)
+        missing = self._missing_checks(A_ij, params, self._sparse)
         if self._sparse:
             self.a_dtype = self._sparse_checks(A_ij, params)
         else:
@@ -87,7 +90,8 @@ class PyNMF:
         self.c_dtype = torch.float64 if self.a_dtype == torch.float64 else torch.float32      # factors, products, eps
         if self._sparse:
             from .sparse import SparseBlock
-            self.A_ij = SparseBlock.from_any(A_ij, device)
+            # (missing='unstored': a stored zero is an observation and stays stored; the block carries the meaning from here on)
+            self.A_ij = SparseBlock.from_any(A_ij, device, keep_zeros=(missing == "unstored"), missing=missing)
         else:
             self.A_ij = _to_device(A_ij, device, self.a_dtype)
         self.params = params
@@ -146,6 +150,26 @@ class PyNMF:
                     [int(c) for c in self.cart_1d_row.allgather(int(self.H_ij.shape[1]))])
         elif hasattr(self.params, "_slice_counts"):
             del self.params._slice_counts
+
+    @staticmethod
+    def _missing_checks(A_ij, params, sparse):
+        """`params.missing`: None (an unstored entry of sparse data is a zero) or 'unstored' (it is not observed).  The latter is
+        provided for sparse data with method 'mu' (fro / kl) on one rank and 1D grids."""
+        missing = getattr(params, "missing", None)
+        if missing not in (None, "unstored"):
+            raise ValueError("params.missing = %r is not known: None (unstored entries are zeros) or 'unstored' (not observed)" % (missing,))
+        if getattr(A_ij, "is_sparse_block", False) and getattr(A_ij, "missing", None) != missing:
+            raise ValueError("params.missing = %r, but the SparseBlock handed over was built with missing = %r: build the block with "
+                             "the meaning (and keep_zeros) the fit is to use" % (missing, getattr(A_ij, "missing", None)))
+        if missing is None:
+            return None
+        if not sparse:
+            raise NotImplementedError("missing='unstored' is not provided for dense data (no mask, no NaN convention): hand the observed "
+                                      "entries over as a sparse matrix")
+        method = str(getattr(params, "method", None) or "mu").lower()
+        if method != "mu":
+            raise NotImplementedError("missing='unstored' is provided for method 'mu' (fro / kl) only, not for '%s'" % method)
+        return missing
 
     @staticmethod
     def _sparse_checks(A_ij, params):

@@ -4,11 +4,15 @@
     W, H, err = PyNMF(scipy_or_torch_sparse_matrix, params=args).fit()        # PyNMF builds the block itself
 
 The block lives on the device as CSR (int32 row pointers and column indices, float32 values, columns sorted inside a row,
-duplicates summed, explicit zeros dropped) AND as the CSR of its transpose, built once here: A H^T gathers rows of H^T along
-the block's rows, W^T A gathers rows of W along the transpose's rows (csrc/dnmf_csr.h).  Rows with more than
+duplicates summed, explicit zeros dropped unless `keep_zeros`) AND as the CSR of its transpose, built once here: A H^T gathers
+rows of H^T along the block's rows, W^T A gathers rows of W along the transpose's rows (csrc/dnmf_csr.h).  Rows with more than
 `dnmf_csr_seg()` stored entries are listed per image (`long_rows`, `long_segptr`): the kernels cut those into segments.
 Building uses torch ops (sort / bincount / cumsum): set-up, not the hot path.  There is no dense image anywhere except in
 `to_dense()`, which tests use.
+
+What an UNSTORED entry means is an attribute of the block, `missing`: None (the default) -- a zero that W H must reproduce; 'unstored'
+-- not observed: the objective, the update rules and the reported error run over the stored positions only (PyNMF sets it
+from `params.missing`).  A stored zero is an observation under that meaning, so such a block is built with `keep_zeros=True`.
 
 Limits: nnz < 2^31, m, n < 2^31 (ValueError); float32 values only (float64 sparse data: NotImplementedError).
 """
@@ -36,7 +40,7 @@ def _is_scipy_sparse(x):
 
 
 class _StoredPattern:
-    """`block != 0`: what utils.data_operations sums along an axis to find all-zero rows / columns"""
+    """`block != 0`: what utils.data_operations sums along an axis to find all-zero rows / columns (counts of stored entries)"""
 
     def __init__(self, blk):
         self.blk = blk
@@ -70,14 +74,27 @@ def _check_dtype(dt):
         raise NotImplementedError("sparse data block: %s sparse data are not provided (float32 values only)" % (dt,))
 
 
+MISSING = (None, "unstored")
+
+
+def _check_missing(missing):
+    if missing not in MISSING:
+        raise ValueError("sparse data block: missing=%r is not known (None: unstored entries are zeros; 'unstored': they are "
+                         "not observed)" % (missing,))
+    return missing
+
+
 class SparseBlock:
     is_sparse_block = True
     dtype = torch.float32
+    missing = None
 
-    def __init__(self, crow, col, val, shape, _trusted=False):
+    def __init__(self, crow, col, val, shape, _trusted=False, keep_zeros=False, missing=None):
         """Raw device arrays of a CSR block: `crow` [m + 1], `col` [nnz], `val` [nnz], `shape` = (m, n).  Unless they come from
-        this module's own builders the arrays are re-normalised (columns sorted, duplicates summed, zeros dropped)."""
+        this module's own builders the arrays are re-normalised (columns sorted, duplicates summed, zeros dropped unless
+        `keep_zeros`).  `missing`: what an unstored entry means (module docstring)."""
         m, n = int(shape[0]), int(shape[1])
+        self.missing = _check_missing(missing)
         _check_dims(m, n, int(col.numel()))
         _check_dtype(val.dtype)
         if crow.numel() != m + 1 or col.numel() != val.numel():
@@ -85,7 +102,7 @@ class SparseBlock:
         if not _trusted:
             counts = (crow[1:] - crow[:-1]).long()
             rows = torch.repeat_interleave(torch.arange(m, device=col.device), counts)
-            blk = SparseBlock.from_coo(rows, col, val, (m, n))
+            blk = SparseBlock.from_coo(rows, col, val, (m, n), keep_zeros=keep_zeros, missing=missing)
             self.__dict__.update(blk.__dict__)
             return
         self.shape = (m, n)
@@ -97,9 +114,10 @@ class SparseBlock:
 
     # ---- builders
     @classmethod
-    def from_coo(cls, rows, cols, vals, shape):
+    def from_coo(cls, rows, cols, vals, shape, keep_zeros=False, missing=None):
         """Entries (rows[i], cols[i]) = vals[i] in any order on one device; duplicates are summed (in float64, rounded once),
-        entries that are or sum to zero are dropped."""
+        entries that are or sum to zero are dropped -- or, with `keep_zeros`, stay stored (observed zeros of a block whose
+        unstored entries are missing)."""
         m, n = int(shape[0]), int(shape[1])
         _check_dims(m, n, int(vals.numel()))
         _check_dtype(vals.dtype)
@@ -124,22 +142,25 @@ class SparseBlock:
                 vals = acc.float()
                 del acc
             del first
-        keep = vals != 0
-        if not bool(keep.all()):
-            key, vals = key[keep], vals[keep]
-        del keep
+        if not keep_zeros:
+            keep = vals != 0
+            if not bool(keep.all()):
+                key, vals = key[keep], vals[keep]
+            del keep
         r = torch.div(key, n, rounding_mode="floor")
         col = (key - r * n).to(torch.int32)
         del key
         crow = torch.zeros(m + 1, dtype=torch.int64, device=dev)
         torch.cumsum(torch.bincount(r, minlength=m), 0, out=crow[1:])
         del r
-        return cls(crow.to(torch.int32), col, vals, (m, n), _trusted=True)
+        return cls(crow.to(torch.int32), col, vals, (m, n), _trusted=True, missing=missing)
 
     @classmethod
-    def from_any(cls, x, device):
-        """A SparseBlock on `device` from a SparseBlock, a scipy.sparse matrix of any format, or a torch sparse tensor."""
+    def from_any(cls, x, device, keep_zeros=False, missing=None):
+        """A SparseBlock on `device` from a SparseBlock, a scipy.sparse matrix of any format, or a torch sparse tensor.  A
+        SparseBlock is taken as it was built: its stored entries and its `missing` attribute are its builder's."""
         device = torch.device(device)
+        _check_missing(missing)
         if getattr(x, "is_sparse_block", False):
             return x if x.device == device else x.to(device)
         if isinstance(x, torch.Tensor):
@@ -151,18 +172,19 @@ class SparseBlock:
                 crow, col, val = x.crow_indices().to(device), x.col_indices().to(device), x.values().to(device)
                 counts = crow[1:] - crow[:-1]
                 rows = torch.repeat_interleave(torch.arange(x.shape[0], device=device), counts)
-                return cls.from_coo(rows, col, val, x.shape)
+                return cls.from_coo(rows, col, val, x.shape, keep_zeros=keep_zeros, missing=missing)
             if x.layout == torch.sparse_csc:
                 x = x.to_sparse_coo()
             idx = x._indices().to(device)
-            return cls.from_coo(idx[0], idx[1], x._values().to(device), x.shape)
+            return cls.from_coo(idx[0], idx[1], x._values().to(device), x.shape, keep_zeros=keep_zeros, missing=missing)
         if _is_scipy_sparse(x):
             _check_dtype(np.dtype(x.dtype))
             _check_dims(int(x.shape[0]), int(x.shape[1]), int(x.nnz))
             c = x.tocoo()
             return cls.from_coo(torch.from_numpy(np.ascontiguousarray(c.row).astype(np.int64)).to(device),
                                 torch.from_numpy(np.ascontiguousarray(c.col).astype(np.int64)).to(device),
-                                torch.from_numpy(np.ascontiguousarray(c.data).astype(np.float32)).to(device), x.shape)
+                                torch.from_numpy(np.ascontiguousarray(c.data).astype(np.float32)).to(device), x.shape,
+                                keep_zeros=keep_zeros, missing=missing)
         raise TypeError("sparse data block: cannot be built from %s" % type(x))
 
     def _build_transpose(self):
@@ -212,7 +234,9 @@ class SparseBlock:
 
     def compact(self, row_keep, col_keep):
         """The block without the rows / columns whose keep-mask is False (pruning, utils.py:156-172): an index remap.  Rows and
-        columns that go hold no stored entry here (the masks are non-zero counts over the whole grid)."""
+        columns that go hold no stored entry here (the masks are counts of STORED entries over the whole grid: all of them
+        non-zero by default; under missing='unstored' a stored zero is an observation and counts, so what is pruned is a row or
+        column without any observation)."""
         m, n = self.shape
         row_keep, col_keep = row_keep.to(self.device), col_keep.to(self.device)
         counts = self.nnz_per_row()
@@ -221,13 +245,16 @@ class SparseBlock:
         colmap = (torch.cumsum(col_keep.long(), 0) - 1).to(torch.int32)
         crow = torch.zeros(int(row_keep.sum()) + 1, dtype=torch.int64, device=self.device)
         torch.cumsum(counts[row_keep], 0, out=crow[1:])
-        return SparseBlock(crow.to(torch.int32), colmap[self.col.long()], self.val, (int(row_keep.sum()), int(col_keep.sum())), _trusted=True)
+        return SparseBlock(crow.to(torch.int32), colmap[self.col.long()], self.val, (int(row_keep.sum()), int(col_keep.sum())), _trusted=True,
+                           missing=self.missing)
 
     # ---- the three expressions utils.data_operations applies to a data block when it prunes (utils.py:117-172), so that its
     # dense lines serve a sparse block unchanged: `ten != 0` -> .sum(1) / .sum(0); `ten[rows][:, cols].contiguous()`
     def __ne__(self, other):
         if isinstance(other, (int, float)) and other == 0:
-            return _StoredPattern(self)                 # (stored entries are non-zero by construction)
+            # (the stored pattern: non-zero by construction unless the block was built with keep_zeros -- then a stored zero is an
+            # observation, and a row / column counts as empty only when nothing of it was observed)
+            return _StoredPattern(self)
         return NotImplemented
 
     __hash__ = object.__hash__
@@ -254,4 +281,5 @@ class SparseBlock:
         return out
 
     def __repr__(self):
-        return "SparseBlock(%d x %d, nnz=%d, %s)" % (self.shape[0], self.shape[1], self.nnz, self.device)
+        return "SparseBlock(%d x %d, nnz=%d, %s%s)" % (self.shape[0], self.shape[1], self.nnz, self.device,
+                                                       ", missing=%r" % self.missing if self.missing else "")
