@@ -171,7 +171,7 @@ def run_bcd_rank(rank, world, port, name, q, use_hip, extra=None):
 def run_bcd(name, use_hip=False, timeout=240, extra=None):
     """Runs the fixture on its grid (one process per rank, gloo) and returns {rank: {key: (dW, dH, derr)}}; raises on a rank's error."""
     import torch.multiprocessing as mp
-    from tests._mp import free_port
+    from tests._mp import collect, free_port
     meta = load_bcd(name)[0]
     world = meta["grid"][0] * meta["grid"][1]
     ctx = mp.get_context("spawn")
@@ -180,9 +180,7 @@ def run_bcd(name, use_hip=False, timeout=240, extra=None):
     procs = [ctx.Process(target=run_bcd_rank, args=(r, world, port, name, q, use_hip, extra)) for r in range(world)]
     for p in procs:
         p.start()
-    res = [q.get(timeout=timeout) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
+    res = collect(procs, q, timeout)
     out = {}
     for rank, o, err in res:
         assert err is None, "rank %d failed:\n%s" % (rank, err)
@@ -228,7 +226,7 @@ def run_acceptance_rank(rank, world, port, grid, itr, q):
 
 def run_acceptance(grid, itr, timeout=240):
     import torch.multiprocessing as mp
-    from tests._mp import free_port
+    from tests._mp import collect, free_port
     world = grid[0] * grid[1]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
@@ -236,9 +234,7 @@ def run_acceptance(grid, itr, timeout=240):
     procs = [ctx.Process(target=run_acceptance_rank, args=(r, world, port, grid, itr, q)) for r in range(world)]
     for p in procs:
         p.start()
-    res = [q.get(timeout=timeout) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
+    res = collect(procs, q, timeout)
     for rank, err, tb in res:
         assert tb is None, "rank %d failed:\n%s" % (rank, tb)
     return [err for _, err, _ in res]

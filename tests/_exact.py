@@ -114,6 +114,110 @@ def kl(m, n, k, dtype=np.float32, seed=0, qmax=3):
     return A.astype(dtype), W.astype(dtype), H.astype(dtype), U
 
 
+# ---------------------------------------------------------------------------------------------------------- sparse (CSR) blocks
+# Row lengths on both sides of every structural boundary of csrc/dnmf_csr.h: the lane-group counts NG = 256 / KPAD = 16, 8, 4, 2, 1,
+# the 64 (col, val) pairs a wave reads per step, and the segment length 1024 of a long row (one, two and three segments, a ragged
+# fourth).  27 rows (not a multiple of a workgroup's 4 waves), an empty row right after the longest one, a short last row.
+LENS = [0, 1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 2047, 2048, 2049, 3073, 0, 2]
+LENS_N = 3100
+
+
+def sparse_pattern(lengths, n, seed=0, empty_cols=0):
+    """A boolean len(lengths) x n mask: row r holds exactly lengths[r] stored positions, at random columns; `empty_cols` random
+    columns hold none (rows of the transposed image without a stored entry)."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    assert lengths.min(initial=0) >= 0 and lengths.max(initial=0) <= n - empty_cols, "a row cannot hold that many entries"
+    rs = np.random.RandomState(seed + 7 * len(lengths) + n)
+    score = rs.rand(len(lengths), n)
+    score[:, rs.choice(n, size=empty_cols, replace=False)] = 2.0               # ranked last in every row
+    mask = score.argsort(1).argsort(1) < lengths[:, None]
+    assert np.array_equal(mask.sum(1), lengths) and (mask.sum(0) == 0).sum() >= empty_cols
+    return mask
+
+
+def lens_pattern(seed=0):
+    """the standard pattern: LENS x LENS_N with two empty columns"""
+    return sparse_pattern(LENS, LENS_N, seed, empty_cols=2)
+
+
+def sparse_exact(A, mask, W, H, kl=False):
+    """float64 answers of every pass over a block whose stored positions are `mask` (A is zero elsewhere), D = W H:
+    aht = A H^T, wta = W^T A; Frobenius pairs (aht, P(D) H^T), (wta, W^T P(D)); resid = ||A - D||^2, resid_masked = sum over the
+    mask of (a - d)^2.  kl=True: U = P(A / D) (the generators make D a power of two >= 2 there: eps is absorbed), uht = U H^T,
+    wtu = W^T U, and the KL denominators P(1) H^T (stored-position sums of H rows), W^T P(1) (of W columns)."""
+    A64, W64, H64, M = A.astype(np.float64), W.astype(np.float64), H.astype(np.float64), mask.astype(np.float64)
+    D = W64 @ H64
+    PD = M * D
+    out = {"aht": A64 @ H64.T, "wta": W64.T @ A64, "den_w": PD @ H64.T, "den_h": W64.T @ PD, "gram_w": W64.T @ W64,
+           "resid": float(np.sum((A64 - D) ** 2)), "resid_masked": float(np.sum(M * (A64 - D) ** 2))}
+    if kl:
+        U = np.where(mask, A64 / np.where(mask, D, 1.0), 0.0)
+        out.update(U=U, uht=U @ H64.T, wtu=W64.T @ U, klden_w=M @ H64.T, klden_h=W64.T @ M)
+    return out
+
+
+def sparse_products(mask, k, seed=0, stored_zeros=False):
+    """A in 1..7 on the mask (with `stored_zeros` a few observed positions hold 0: `keep_zeros` / missing='unstored'), W and H in
+    1..3 with some zero rows of W / columns of H.  Integers below 2^24, exact in fp32 in any order: A H^T, W^T A, W^T W, every
+    <W_r, H_c> (<= 9 k), and the masked pairs' denominators P(W H) H^T, W^T P(W H).  Integers below 2^53, exact in float64: the
+    stored-entry sum of squares, <W^T W, H H^T>, the cross term sum v d, sum over the mask of (a - d)^2."""
+    m, n = mask.shape
+    rs = np.random.RandomState(seed + 1009 * m + 17 * n + k)
+    A = np.where(mask, rs.randint(1, 8, size=(m, n)), 0).astype(np.float32)
+    if stored_zeros:
+        r, c = np.nonzero(mask)
+        z = rs.choice(r.size, size=max(3, r.size // 50), replace=False)
+        A[r[z], c[z]] = 0
+    W = rs.randint(1, 4, size=(m, k)).astype(np.float32)
+    H = rs.randint(1, 4, size=(k, n)).astype(np.float32)
+    W[rs.rand(m) < 0.05] = 0
+    W[rs.randint(m)] = 0                                        # (a small block has a zero row / column too)
+    H[:, rs.rand(n) < 0.05] = 0
+    H[:, rs.randint(n)] = 0
+    ref = sparse_exact(A, mask, W, H)
+    W64, H64, A64 = W.astype(np.float64), H.astype(np.float64), A.astype(np.float64)
+    for what in ("aht", "wta", "den_w", "den_h", "gram_w"):
+        _bound(ref[what], 1.0, np.float32, what)
+    _bound(H64 @ H64.T, 1.0, np.float32, "H H^T")
+    _bound(9.0 * k, 1.0, np.float32, "<W_r, H_c>")
+    cross = float(np.sum(A64 * (W64 @ H64)))
+    for tot, what in ((np.sum(A64 * A64), "sum a^2"), (np.sum(ref["gram_w"] * (H64 @ H64.T)), "<W^T W, H H^T>"), (2.0 * cross, "2 sum a d"),
+                      (np.sum(A64 * A64) + 2.0 * cross, "sum |a (a - 2 d)|"), (ref["resid_masked"], "sum (a - d)^2")):
+        _bound(tot, 1.0, np.float64, what)
+    return A, W, H
+
+
+def sparse_kl(mask, k, seed=0, stored_zeros=False, qmax=3):
+    """The structure of `kl` on a stored pattern: W one-hot per row with 2^(0..2), H = 2^(1..qmax), A in 1..7 on the mask (a few
+    observed zeros with `stored_zeros`).  <W_r, H_c> is a power of two >= 2 (one non-zero product, so the dot is exact whichever
+    side is the lane-dense one; eps is absorbed) and val / (d + eps) is exact; U H^T and W^T U are sums of multiples of
+    2^-(2 + qmax); the stored-position sums of H rows and of W columns are integers."""
+    m, n = mask.shape
+    rs = np.random.RandomState(seed + 13 * m + 5 * n + 3 * k)
+    A = np.where(mask, rs.randint(1, 8, size=(m, n)), 0).astype(np.float32)
+    if stored_zeros:
+        r, c = np.nonzero(mask)
+        z = rs.choice(r.size, size=max(3, r.size // 50), replace=False)
+        A[r[z], c[z]] = 0
+    W = np.zeros((m, k), dtype=np.float32)
+    W[np.arange(m), rs.randint(0, k, size=m)] = 2.0 ** rs.randint(0, 3, size=m)
+    H = (2.0 ** rs.randint(1, qmax + 1, size=(k, n))).astype(np.float32)
+    WH = W.astype(np.float64) @ H.astype(np.float64)
+    assert np.all(WH >= 2) and np.array_equal(np.log2(WH), np.round(np.log2(WH)))
+    ref = sparse_exact(A, mask, W, H, kl=True)
+    unit = 2.0 ** -(2 + qmax)
+    _bound(ref["uht"], unit, np.float32, "U H^T")
+    _bound(ref["wtu"], unit, np.float32, "W^T U")
+    _bound(ref["klden_w"], 1.0, np.float32, "stored-position sums of H rows")
+    _bound(ref["klden_h"], 1.0, np.float32, "stored-position sums of W columns")
+    return A, W, H
+
+
+def transposed(A, mask, W, H):
+    """the same problem seen from A^T: (A^T, mask^T) with the factor roles swapped to (H^T, W^T)"""
+    return tuple(np.ascontiguousarray(x) for x in (A.T, mask.T, H.T, W.T))
+
+
 # ---------------------------------------------------------------------------------------------------------- per-element comparison
 def assert_ulp(got, q, c, what="", tile=(16, 32), q_hi=None):
     """|got - q| <= c * spacing(q in got's type) per element, q the float64 reference; q == 0 must be exactly 0 and c == 0 means

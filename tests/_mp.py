@@ -18,6 +18,32 @@ def free_port():
     return port
 
 
+def collect(procs, q, timeout):
+    """One result per rank from `q` (each within `timeout`), then the ranks joined.  A rank that is still alive when this returns or
+    raises is terminated: a rank stuck in a collective whose peer has gone would otherwise outlive the test and, being a
+    non-daemonic child, keep the interpreter from exiting.  A missing result fails with every rank's state and what the others sent."""
+    import queue
+    res = []
+    try:
+        for _ in procs:
+            res.append(q.get(timeout=timeout))
+        for p in procs:
+            p.join(timeout=60)
+    except queue.Empty:
+        state = ["alive" if getattr(p, "exitcode", 0) is None else "exit code %r" % getattr(p, "exitcode", 0) for p in procs]
+        sent = "\n".join("rank %d sent:\n%s" % (r[0], r[-1]) for r in res if r[-1] is not None)
+        raise AssertionError("%d of %d ranks sent a result within %g s; ranks: %s\n%s" % (len(res), len(procs), timeout, ", ".join(state), sent))
+    finally:
+        for p in procs:
+            if getattr(p, "is_alive", lambda: False)():
+                p.terminate()
+                p.join(timeout=10)
+                if p.is_alive():
+                    p.kill()
+                    p.join(timeout=10)
+    return res
+
+
 def run_case_rank(rank, world, port, name, q, use_hip, extra=None):
     try:
         import torch.distributed as dist
@@ -108,9 +134,7 @@ def run_case(name, use_hip=False, timeout=240, extra=None, tols=None):
     procs = [ctx.Process(target=run_case_rank, args=(r, world, port, name, q, use_hip, extra)) for r in range(world)]
     for p in procs:
         p.start()
-    res = [q.get(timeout=timeout) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
+    res = collect(procs, q, timeout)
     for rank, out, err in res:
         assert err is None, "rank %d failed:\n%s" % (rank, err)
         hals = meta.get("method") == "hals"
@@ -194,9 +218,7 @@ def run_bf16(grid, method, use_hip=False, timeout=240, cfg=None):
     procs = [ctx.Process(target=run_bf16_rank, args=(r, world, port, grid, method, q, use_hip, cfg)) for r in range(world)]
     for p in procs:
         p.start()
-    res = [q.get(timeout=timeout) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
+    res = collect(procs, q, timeout)
     tol = 2e-3 if method == "hals" else 1e-4
     for rank, out, err in res:
         assert err is None, "rank %d failed:\n%s" % (rank, err)
@@ -267,9 +289,7 @@ def run_swim_nmfk(cfg, use_hip=True, timeout=3600):
     procs = [ctx.Process(target=run_swim_nmfk_rank, args=(r, 4, port, cfg, q, use_hip)) for r in range(4)]
     for p in procs:
         p.start()
-    res = [q.get(timeout=timeout) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
+    res = collect(procs, q, timeout)
     for rank, out, err in res:
         assert err is None, "rank %d failed:\n%s" % (rank, err)
     return [out for _, out, _ in sorted(res, key=lambda r: r[0])]
@@ -355,9 +375,7 @@ def run_nmfk_golden(fixture, use_hip=False, timeout=600, extra=None, world=None)
     procs = [ctx.Process(target=run_nmfk_golden_rank, args=(r, world, port, fixture, q, use_hip, extra)) for r in range(world)]
     for p in procs:
         p.start()
-    res = [q.get(timeout=timeout) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
+    res = collect(procs, q, timeout)
     for rank, out, err in res:
         assert err is None, "rank %d failed:\n%s" % (rank, err)
     return [out for _, out, _ in sorted(res, key=lambda r: r[0])]
@@ -419,8 +437,6 @@ def run_exact(grid, shape, exchange=None, timeout=240):
     procs = [ctx.Process(target=run_exact_rank, args=(r, world, port, grid, shape, q, exchange)) for r in range(world)]
     for p in procs:
         p.start()
-    res = [q.get(timeout=timeout) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
+    res = collect(procs, q, timeout)
     for rank, err in res:
         assert err is None, "rank %d failed:\n%s" % (rank, err)

@@ -90,3 +90,111 @@ def test_ulp_comparator_reports_the_first_bad_element():
     q2[0, 0] = 0.0
     with pytest.raises(AssertionError, match=r"first at \(0, 0\)"):
         ex.assert_ulp(z, q2, 3)                                             # a zero must be exactly zero
+
+
+# ---------------------------------------------------------------------------------------------------------- sparse (CSR) blocks
+SPARSE_KS = (1, 17, 64, 129, 256)
+SEG = 1024                                                                  # entries of one segment of a long row (csrc/dnmf_csr.h)
+
+
+def _kpad(k):
+    return next(p for p in (16, 32, 64, 128, 256) if k <= p)
+
+
+def _gather_orders(mask, coef, F, ng, dtype=np.float32):
+    """out[r] = sum over the stored c of row r of coef[r][c] F[c], in `dtype`, three ways: the stored entries front to back, back to
+    front, and as the kernels do it -- entry j of a segment of SEG entries goes to lane group j % ng, every group sums its entries in
+    order, the groups are folded by an xor butterfly (neighbours first), the segments are added in order.  coef is zero off the mask,
+    and adding an exact zero changes nothing, so the dense loop over c IS the sparse sum."""
+    m, n = mask.shape
+    k = F.shape[1]
+    coef, F = coef.astype(dtype), F.astype(dtype)
+    rank = np.where(mask, np.cumsum(mask, 1) - 1, 0)
+    nseg = int(rank.max(initial=0)) // SEG + 1
+    fwd, rev = np.zeros((m, k), dtype), np.zeros((m, k), dtype)
+    parts = np.zeros((nseg, ng, m, k), dtype)
+    rows = np.arange(m)
+    for c in range(n):
+        t = coef[:, c, None] * F[c]
+        fwd += t
+        parts[rank[:, c] // SEG, rank[:, c] % ng, rows] += t
+    for c in range(n - 1, -1, -1):
+        rev += coef[:, c, None] * F[c]
+    while parts.shape[1] > 1:
+        parts = parts[:, 0::2] + parts[:, 1::2]
+    ker = np.zeros((m, k), dtype)
+    for s in range(nseg):
+        ker += parts[s, 0]
+    return fwd, rev, ker
+
+
+def _exact_in_all_orders(mask, coef, F, ng, ref, what, dtype=np.float32):
+    for got, how in zip(_gather_orders(mask, coef, F, ng, dtype), ("forward", "reversed", "lane groups")):
+        assert np.array_equal(got.astype(np.float64), ref), "%s (%s, %d lane groups) is not exact in %s" % (what, how, ng, np.dtype(dtype))
+
+
+@pytest.fixture(scope="module")
+def lens_mask():
+    return ex.lens_pattern()
+
+
+def test_sparse_pattern_has_the_prescribed_rows(lens_mask):
+    assert lens_mask.shape == (27, 3100) and lens_mask.dtype == bool
+    assert lens_mask.sum(1).tolist() == ex.LENS
+    assert np.array_equal(lens_mask, ex.lens_pattern())                                # the same pattern every time
+    assert lens_mask.sum(0).max() <= 27 and (lens_mask.sum(0) == 0).any()              # the transpose has short and empty rows
+    many = ex.sparse_pattern(np.arange(2 * 8192 + 5) % 6, 70, seed=1)
+    assert np.array_equal(many.sum(1), np.arange(2 * 8192 + 5) % 6)
+
+
+@pytest.mark.parametrize("k", SPARSE_KS)
+def test_sparse_products_are_exact(lens_mask, k):
+    """every pass of the Frobenius side on `sparse_products` operands, on the block and on its transpose, in every order"""
+    eps = np.float32(np.finfo(np.float32).eps)
+    ng = 256 // _kpad(k)
+    prob = ex.sparse_products(lens_mask, k, stored_zeros=True)
+    assert ((prob[0] == 0) & lens_mask).sum() >= 3                                     # observed zeros
+    assert (prob[1].sum(1) == 0).any() and (prob[2].sum(0) == 0).any()                 # a zero row of W, a zero column of H
+    for A, mask, W, H in ((prob[0], lens_mask) + prob[1:], ex.transposed(prob[0], lens_mask, *prob[1:])):
+        ref = ex.sparse_exact(A, mask, W, H)
+        D = _all_orders(W, H, "W H")
+        PD = np.where(mask, D, 0.0)
+        _exact_in_all_orders(mask, A, H.T, ng, ref["aht"], "A H^T")
+        _exact_in_all_orders(mask, PD, H.T, ng, ref["den_w"], "P(W H) H^T")
+        _exact_in_all_orders(mask.T, A.T, W, ng, ref["wta"].T, "W^T A")
+        _exact_in_all_orders(mask.T, PD.T, W, ng, ref["den_h"].T, "W^T P(W H)")
+        _all_orders(W.T, W, "W^T W")
+        for den in (ref["den_w"], ref["den_h"]):                                       # what the fused ending divides by is one rounding
+            d32 = den.astype(np.float32)
+            assert np.array_equal(d32.astype(np.float64), den) and np.all(np.isfinite(prob[0].max() * d32.max() / eps))
+        # the residuals: float64 sums of integers, against integer arithmetic
+        Ai, Di = A.astype(np.int64), W.astype(np.int64) @ H.astype(np.int64)
+        Mi = mask.astype(np.int64)
+        gram = int(np.sum((W.astype(np.int64).T @ W.astype(np.int64)) * (H.astype(np.int64) @ H.astype(np.int64).T)))
+        cross, sq = Ai * (Ai - 2 * Di), Mi * (Ai - Di) ** 2
+        assert gram + int(cross.sum()) == int(((Ai - Di) ** 2).sum()) == int(ref["resid"]) and float(int(ref["resid"])) == ref["resid"]
+        assert int(sq.sum()) == int(ref["resid_masked"]) and float(int(ref["resid_masked"])) == ref["resid_masked"]
+        one = np.ones((mask.shape[1], 1))
+        _exact_in_all_orders(mask, cross, one, ng, cross.sum(1, keepdims=True).astype(np.float64), "sum a (a - 2 d)", np.float64)
+        _exact_in_all_orders(mask, sq, one, ng, sq.sum(1, keepdims=True).astype(np.float64), "sum (a - d)^2", np.float64)
+        assert abs(cross).sum() < 2 ** 53 and gram < 2 ** 53
+
+
+@pytest.mark.parametrize("k", SPARSE_KS)
+def test_sparse_kl_is_exact(lens_mask, k):
+    """the KL passes on `sparse_kl` operands: the fused quotient is exact, and so are both products and both denominators"""
+    eps = np.float32(np.finfo(np.float32).eps)
+    ng = 256 // _kpad(k)
+    prob = ex.sparse_kl(lens_mask, k, stored_zeros=True)
+    assert ((prob[0] == 0) & lens_mask).sum() >= 3
+    for A, mask, W, H in ((prob[0], lens_mask) + prob[1:], ex.transposed(prob[0], lens_mask, *prob[1:])):
+        ref = ex.sparse_exact(A, mask, W, H, kl=True)
+        D = _all_orders(W, H, "W H").astype(np.float32)
+        assert np.array_equal(D + eps, D)                                               # eps is absorbed
+        U32 = np.where(mask, A / (D + eps), np.float32(0))
+        assert U32.dtype == np.float32 and np.array_equal(U32.astype(np.float64), ref["U"])
+        Mf = mask.astype(np.float32)
+        _exact_in_all_orders(mask, U32, H.T, ng, ref["uht"], "U H^T")
+        _exact_in_all_orders(mask, Mf, H.T, ng, ref["klden_w"], "stored-position sums of H rows")
+        _exact_in_all_orders(mask.T, U32.T, W, ng, ref["wtu"].T, "W^T U")
+        _exact_in_all_orders(mask.T, Mf.T, W, ng, ref["klden_h"].T, "stored-position sums of W columns")
