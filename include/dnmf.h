@@ -650,6 +650,28 @@ int dnmf_csr_masked_resid_sqnorm(const int* rowptr, const int* col, const float*
                                  const float* HTp, int k, const int* long_rows, const int* long_segptr, int n_long, int nseg,
                                  double* sq, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- NMFk on a sparse block: the perturbed copy and the per-column error ----
+ * val_out[p] = val[p] * (1 + nv + 2 nv u) (pyDNMFk.py:42-44) on ONE CSR image of the block.  u is the uniform dnmf_perturb_uniform
+ * gives the entry's position in the DENSE block: linear index L = r * ncols + c, the splitmix64 finaliser of (seed, L >> 1), its high
+ * 24 bits for even L and its low 24 bits for odd L -- so the result equals dnmf_perturb_uniform on the densified block at the stored
+ * positions, bit for bit, and depends on (seed, position) only.  transposed == 0: the block's own image (row index r, column index
+ * c).  transposed != 0: the transpose's image (its row index is c, its column index r; rows must equal ncols); the two outputs
+ * describe the same matrix.  `ncols`: the dense block's column count.  Rows of any length; no workspace. */
+int dnmf_csr_perturb_uniform(const int* rowptr, const int* col, const float* val, long rows, long ncols, int transposed,
+                             float noise_var, unsigned long long seed, float* val_out, void* stream);
+/* num[c], den[c] (float64, c < rows) of pyDNMF.py:221-239 (`column_err`) over this rank's rows, from the TRANSPOSE's image: rows = the
+ * block's column count n, cols = its row count m, Lp = packed H^T [n x KPAD], Fp = packed W [m x KPAD]; d = <H^T[c], W[r]> in float64.
+ *     masked == 0:  num[c] = sum_stored a (a - 2 d) + h_c^T (W^T W) h_c,  den[c] = sum_stored a^2   (W^T W: this rank's float64 Gram
+ *                   matrix, partials added in a fixed order, read through L2)
+ *     masked != 0:  num[c] = sum_stored (a - d)^2,                        den[c] = sum_stored a^2   (missing='unstored')
+ * A column without a stored entry gives den = 0 and num = the Gram term (masked: 0).  Long rows of the image go through segment
+ * partials added in segment order; no atomics: bit-reproducible.
+ * `ws`: dnmf_csr_column_err_ws_bytes(n, m, k, masked, nseg) bytes (nseg of the transpose's image), 16-byte aligned. */
+size_t dnmf_csr_column_err_ws_bytes(long rows, long cols, int k, int masked, int nseg);
+int dnmf_csr_column_err(const int* rowptr, const int* col, const float* val, long rows, long cols, const float* Lp, const float* Fp,
+                        int k, int masked, const int* long_rows, const int* long_segptr, int n_long, int nseg, double* num,
+                        double* den, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- measurement aid (no counterpart in the reference) ----
  * Which shader clock does the GPU hold right now?  Launches ONE wave on `stream` that writes `n` pairs {s_memtime (shader
  * cycles), wall_clock64 (the constant 100 MHz reference)} into samples[2 n], sleeping `naps` x ~4 us between two pairs, and

@@ -36,7 +36,7 @@ FLAGS = [
     ('p_c', int, None, True, 'process-grid columns'),
     ('k', int, 4, False, 'rank of the factorisation'),
     ('fpath', str, 'data/', False, 'directory of the input (with trailing slash)'),
-    ('ftype', str, 'mat', False, 'input format: mat / npy / csv / txt / folder'),
+    ('ftype', str, 'mat', False, 'input format: mat / npy / csv / txt / folder, or spnpz (a scipy.sparse.save_npz file <fname>.npz: the block stays sparse)'),
     ('fname', str, 'swim', False, 'input file name without extension'),
     ('init', str, 'rand', False, 'factor initialisation: rand / nnsvd'),
     ('itr', int, 5000, False, 'update iterations'),
@@ -54,6 +54,7 @@ FLAGS = [
     ('direct_allreduce', _flag, False, False, 'with --exchange native on one node: the packed allreduce of a 1D step goes through IPC-mapped peer buffers (two-shot, rank-ordered sums) instead of RCCL, and the HALS W sweep on p_r > 1 runs as ONE persistent launch whose column norms cross the ranks through slots in those buffers; checked against RCCL on first contact, all ranks fall back together'),
     ('shared_gpu', _flag, False, False, 'the GPU is shared with other processes or streams: never use the kernels whose workgroups wait for each other (whole fits of small problems, the one-launch HALS W sweep, the one-pass MU/FRO step) -- dnmf_set_persistent(0); without it a fit that loses its residency is detected and fitted again on the launch-chain kernels, at the cost of one time-out'),
     ('hals_sweep', str, 'persistent', False, 'W sweep of method hals on a rank with local norms: persistent (one launch; needs the GPU to itself) or columns'),
+    ('missing', str, None, False, 'what an unstored entry of sparse input means: omitted = a zero; unstored = not observed (method mu, 1D grids)'),
     # NMFk
     ('perturbations', int, 20, False, 'perturbed copies per rank'),
     ('noise_var', float, 0.015, False, 'perturbation amplitude'),
@@ -110,7 +111,18 @@ def main():
         args.size, args.rank, args.comm1 = whole.size, whole.rank, whole      # PyNMFk builds the fits' one-rank bag from here
     if args.rank == 0:
         print('Starting ', args.process, '...')
-    if args.rng == 'device':
+    from pydnmfk_amd.sparse import is_sparse_input
+    if args.missing is None:
+        del args.missing                                   # (the choreography reads params.missing only when it is set)
+    elif args.missing != 'unstored':
+        raise SystemExit("--missing must be unstored (or omitted: unstored entries are zeros)")
+    if is_sparse_input(A_ij):
+        if args.rng == 'device':                           # the block's CSR arrays go to the GPU once; perturbations are drawn there
+            A_ij = torch.sparse_csr_tensor(torch.from_numpy(A_ij.indptr.astype(np.int64)), torch.from_numpy(A_ij.indices.astype(np.int64)),
+                                           torch.from_numpy(A_ij.data), size=A_ij.shape).to(torch.device("cuda", torch.cuda.current_device()))
+        elif args.rng != 'numpy':
+            raise SystemExit("--rng must be device or numpy")
+    elif args.rng == 'device':
         # the rank's block goes to the GPU ONCE (bf16 storage is rounded here); PyNMF / PyNMFk then work on device tensors:
         # perturbations and the rand init are drawn on the GPU, factors stay there between the fits of an NMFk sweep
         from pydnmfk_amd.pyDNMF import storage_dtype

@@ -191,7 +191,12 @@ SIGNATURES["dnmf_csr_masked_update"] = [c_void_p, c_void_p, c_void_p, c_long, c_
                                         c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]
 SIGNATURES["dnmf_csr_ratio_update"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_void_p, c_long, c_float, c_int, c_void_p]
 SIGNATURES["dnmf_csr_masked_resid_sqnorm"] = SIGNATURES["dnmf_csr_resid_sqnorm"]
-_RESTYPES = {"dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
+# NMFk on a sparse block: rowptr col val rows ncols transposed noise_var seed val_out stream
+SIGNATURES["dnmf_csr_perturb_uniform"] = [c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_float, ctypes.c_ulonglong, c_void_p, c_void_p]
+SIGNATURES["dnmf_csr_column_err_ws_bytes"] = [c_long, c_long, c_int, c_int, c_int]
+SIGNATURES["dnmf_csr_column_err"] = [c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+_RESTYPES = {"dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
              "dnmf_ws_bytes_1d": c_size_t, "dnmf_ws_bytes_hblocks": c_size_t, "dnmf_ws_bytes_2d": c_size_t,
              "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t, "dnmf_bcd_ws_bytes_fit": c_size_t}
 

@@ -9,7 +9,9 @@
 //     m_fro   num[r] = sum_p val[p] F[col[p]],                      den[r] = sum_p <L[r], F[col[p]]> F[col[p]]
 //     m_kl    num[r] = sum_p val[p] / (<L[r], F[col[p]]> + eps) F[col[p]],   den[r] = sum_p F[col[p]]
 //     m_resid sum_p (val[p] - <L[r], F[col[p]]>)^2 in float64        (no Gram term: nothing outside the stored positions counts)
-// and end either by storing the pair (the sides whose sums cross ranks) or, the wave holding L[r] in registers, by writing
+// An NMFk sweep adds two passes outside the fits (end of this file): the perturbed copy of a CSR image keyed by dense position, and
+//     col_err num[c], den[c] in float64 per column from the transpose's image (the residual of modes 2 / 5, kept per row)
+// The masked passes end either by storing the pair (the sides whose sums cross ranks) or, the wave holding L[r] in registers, by writing
 // X[r] = L[r] * num / (den + eps) straight into the factor (it reads the packed copy, so nothing is updated under a reader).
 // F and L are PACKED factor images [rows x KPAD] (csr_pack_kernel / csr_pack_t_kernel): KPAD = 16 / 32 / 64 / 128 / 256 floats,
 // zero padded, so that a gathered row is 64 B (inside one 128-byte line) or whole 128-byte lines and is read as one float4 per
@@ -23,6 +25,7 @@
 // segment writing a partial row, and one small launch that adds a row's partials in segment order.
 #pragma once
 #include "dnmf_common.h"
+#include "dnmf_stream.h"
 
 namespace {
 
@@ -386,6 +389,167 @@ __global__ __launch_bounds__(256) void csr_resid_final_kernel(const double* __re
         __syncthreads();
     }
     if (threadIdx.x == 0) sq[0] = sh[0] > 0.0 ? sh[0] : 0.0;
+}
+
+// ---- NMFk on a sparse block: the perturbed copy and the per-column error
+// val_out[p] = val[p] * (1 + nv + 2 nv u), u the uniform the dense kernels of csrc/dnmf_stream.h give the element's position in the
+// DENSE block (perturb_factor: one definition of the stream), so the perturbed block is the dense kernels' output at the stored
+// positions, bit for bit.  One kernel for both images: on the block's own image a stored entry (ir, ic) sits at dense position
+// (ir, ic), on the transpose's image (`transposed`) at (ic, ir); `ncols` = the dense block's column count.  A wave takes rows
+// w, w + nw, ... and walks each 64 entries at a time, however long the row is; a value depends on (seed, position) only.
+__global__ __launch_bounds__(256) void csr_perturb_uniform_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                                  const float* __restrict__ val, long rows, long ncols, int transposed,
+                                                                  float nv, unsigned long long seed, float* __restrict__ val_out) {
+    const long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (long)gridDim.x * 4;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long key = perturb_key(seed);
+    for (long ir = w; ir < rows; ir += nw) {
+        const int p1 = rowptr[ir + 1];
+        for (int p = rowptr[ir] + lane; p < p1; p += 64) {
+            const unsigned long long ic = (unsigned long long)col[p];
+            const unsigned long long L = transposed ? ic * (unsigned long long)ncols + (unsigned long long)ir
+                                                    : (unsigned long long)ir * (unsigned long long)ncols + ic;
+            val_out[p] = val[p] * perturb_factor(key, L, nv);
+        }
+    }
+}
+
+// The stored entries [p0, p1) of one row of the TRANSPOSE's image (a column c of the block), `lrow` = this lane's float4 of the
+// packed H^T[c], F = packed W: per entry d = <H^T[c], W[r]> in float64 as in csr_span modes 2 and 5, then
+//     zero meaning:  num += a (a - 2 d)      missing='unstored':  num += (a - d)^2      both:  den += a^2
+// accumulated by lane 0 of every lane group (the caller folds the groups).
+template <int G, bool MASKED>
+__device__ inline void csr_span_err(const int* __restrict__ col, const float* __restrict__ val, int p0, int p1, const float* __restrict__ F,
+                                    const f32x4 lrow, double& num, double& den) {
+    constexpr int NG = 64 / G, KPAD = 4 * G;
+    const int lane = threadIdx.x & 63, grp = lane / G, l = lane % G;
+    for (int base = p0; base < p1; base += 64) {
+        const int p = base + lane;
+        const bool in = p < p1;
+        const int c = in ? col[p] : 0;
+        const float v = in ? val[p] : 0.f;
+        const int cnt = min(64, p1 - base);
+#pragma unroll 2
+        for (int j0 = 0; j0 < cnt; j0 += NG) {
+            const int j = j0 + grp;
+            const int cj = __shfl(c, j, 64);
+            const double vj = (double)__shfl(v, j, 64);
+            const bool ok = j < cnt;                              // uniform inside a lane group
+            f32x4 f = {0.f, 0.f, 0.f, 0.f};
+            if (ok) f = *reinterpret_cast<const f32x4*>(F + (size_t)cj * KPAD + 4 * l);
+            double t = (double)lrow.x * (double)f.x;
+            t = fma((double)lrow.y, (double)f.y, t); t = fma((double)lrow.z, (double)f.z, t); t = fma((double)lrow.w, (double)f.w, t);
+            const double d = csr_sum_in_group<G>(t);
+            if (ok && l == 0) {
+                if (MASKED) {
+                    const double e = vj - d;
+                    num = fma(e, e, num);
+                } else {
+                    num += vj * (vj - 2.0 * d);
+                }
+                den = fma(vj, vj, den);
+            }
+        }
+    }
+}
+
+// h^T Gm h in float64 for one packed row h and the symmetric k x k matrix Gm = W^T W (row-major; read through L2: 512 KB at k = 256
+// do not fit LDS).  Lane i takes rows i, i + 64, ... (column i of Gm read along the lanes: Gm is symmetric), the lanes' sums are
+// folded by an xor butterfly: every lane of the wave returns the total, in an order fixed by k alone.
+__device__ inline double csr_gram_quad(const double* __restrict__ Gm, const float* __restrict__ h, int k) {
+    double t = 0.0;
+    for (int i = threadIdx.x & 63; i < k; i += 64) {
+        double s = 0.0;
+        for (int j = 0; j < k; ++j) s = fma(Gm[(size_t)j * k + i], (double)h[j], s);
+        t = fma((double)h[i], s, t);
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) t += __shfl_xor(t, off, 64);
+    return t;
+}
+
+// one wave per row of the transpose's image (a column of the block), four per workgroup: num[c], den[c].  Gm = nullptr under
+// missing='unstored' (no Gram term).  A row without a stored entry: den = 0, num = the Gram term or 0.  Rows longer than CSR_SEG
+// are left to the two kernels below.
+template <int G, bool MASKED>
+__global__ __launch_bounds__(256) void csr_colerr_rows_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                              const float* __restrict__ val, long rows, const float* __restrict__ L,
+                                                              const float* __restrict__ F, int k, const double* __restrict__ Gm,
+                                                              double* __restrict__ num, double* __restrict__ den) {
+    constexpr int KPAD = 4 * G;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int lane = threadIdx.x & 63, l = lane % G;
+    const int p0 = rowptr[r], p1 = rowptr[r + 1];
+    if (p1 - p0 > CSR_SEG) return;
+    double a = 0.0, b = 0.0;
+    if (p1 > p0) {
+        const f32x4 lrow = *reinterpret_cast<const f32x4*>(L + (size_t)r * KPAD + 4 * l);
+        csr_span_err<G, MASKED>(col, val, p0, p1, F, lrow, a, b);
+        a = csr_sum_over_groups<G>(a);
+        b = csr_sum_over_groups<G>(b);
+    }
+    if (!MASKED) a += csr_gram_quad(Gm, L + (size_t)r * KPAD, k);
+    if (lane == 0) {
+        num[r] = a;
+        den[r] = b;
+    }
+}
+
+// one wave per segment of a long row: the pair of float64 partials dpart[2 s], dpart[2 s + 1]
+template <int G, bool MASKED>
+__global__ __launch_bounds__(256) void csr_colerr_long_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                              const float* __restrict__ val, const float* __restrict__ L,
+                                                              const float* __restrict__ F, const int* __restrict__ long_rows,
+                                                              const int* __restrict__ long_segptr, int n_long, double* __restrict__ dpart) {
+    constexpr int KPAD = 4 * G;
+    const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= long_segptr[n_long]) return;
+    int lo = 0, hi = n_long;                                       // the long row whose segments include s
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (long_segptr[mid] <= s) lo = mid; else hi = mid;
+    }
+    const long r = long_rows[lo];
+    const int lane = threadIdx.x & 63, l = lane % G;
+    const int p0 = rowptr[r] + (s - long_segptr[lo]) * CSR_SEG, p1 = min(p0 + CSR_SEG, rowptr[r + 1]);
+    const f32x4 lrow = *reinterpret_cast<const f32x4*>(L + (size_t)r * KPAD + 4 * l);
+    double a = 0.0, b = 0.0;
+    csr_span_err<G, MASKED>(col, val, p0, p1, F, lrow, a, b);
+    a = csr_sum_over_groups<G>(a);
+    b = csr_sum_over_groups<G>(b);
+    if (lane == 0) {
+        dpart[2 * (size_t)s] = a;
+        dpart[2 * (size_t)s + 1] = b;
+    }
+}
+
+// a long row's partial pairs added in segment order, then the Gram term (Gm != nullptr): one wave per long row
+__global__ __launch_bounds__(64) void csr_colerr_long_reduce_kernel(const double* __restrict__ dpart, const int* __restrict__ long_rows,
+                                                                    const int* __restrict__ long_segptr, const float* __restrict__ L,
+                                                                    int kpad, int k, const double* __restrict__ Gm,
+                                                                    double* __restrict__ num, double* __restrict__ den) {
+    const int i = blockIdx.x;
+    const long r = long_rows[i];
+    double a = 0.0, b = 0.0;
+    for (int s = long_segptr[i]; s < long_segptr[i + 1]; ++s) {
+        a += dpart[2 * (size_t)s];
+        b += dpart[2 * (size_t)s + 1];
+    }
+    if (Gm) a += csr_gram_quad(Gm, L + (size_t)r * kpad, k);
+    if (threadIdx.x == 0) {
+        num[r] = a;
+        den[r] = b;
+    }
+}
+
+// Gm[e] = sum over the chunks of csr_gram_f64_kernel's partials, in chunk order
+__global__ __launch_bounds__(256) void csr_gram_sum_kernel(const double* __restrict__ part, int nchunks, int kk, double* __restrict__ Gm) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= kk) return;
+    double a = 0.0;
+    for (int c = 0; c < nchunks; ++c) a += part[(size_t)c * kk + e];
+    Gm[e] = a;
 }
 
 }  // namespace

@@ -1,6 +1,8 @@
 // dnmf_csr.hip -- C ABI of the sparse (CSR) data block: packed factor images, the gather products, the KL products with the
-// quotient fused, the residual's closed form, and the passes of a block whose unstored entries are missing (csrc/dnmf_csr.h).  A translation unit of its own (see csrc/dnmf_kl.hip).
+// quotient fused, the residual's closed form, the passes of a block whose unstored entries are missing, and NMFk's perturbed copy and
+// per-column error (csrc/dnmf_csr.h).  A translation unit of its own (see csrc/dnmf_kl.hip).
 // Plain launch chains: no workgroup waits for another one.
+#include <cmath>
 #include "dnmf_common.h"
 #include "dnmf_host.h"
 #include "dnmf_csr.h"
@@ -115,6 +117,45 @@ int resid_launch(const int* rowptr, const int* col, const float* val, long rows,
         hipLaunchKernelGGL((csr_long_kernel<G, 2>), dim3((unsigned)cdiv(nseg, 4)), dim3(256), 0, st, rowptr, col, val, Wp, HTp, 0.f, long_rows,
                            long_segptr, n_long, (float*)nullptr, dpart + nw);
     return check_launch("csr_resid_sqnorm");
+}
+
+// workspace of dnmf_csr_column_err: the Gram partials of W and their sum (zero meaning only), then one float64 PAIR per segment
+struct ColerrWs { size_t gpart, gram, dpart, total; int nc; };
+
+ColerrWs colerr_layout(long frows, int k, long nseg, bool masked) {
+    ColerrWs L{};
+    L.nc = masked ? 0 : gram_chunks(frows, k);
+    size_t o = 0;
+    L.gpart = o; o += align256((size_t)L.nc * k * k * sizeof(double));
+    L.gram = o; o += masked ? 0 : align256((size_t)k * k * sizeof(double));
+    L.dpart = o; o += align256((size_t)nseg * 2 * sizeof(double));
+    L.total = std::max<size_t>(256, o);
+    return L;
+}
+
+template <int G, bool MASKED>
+int colerr_launch(const int* rowptr, const int* col, const float* val, long rows, const float* Lp, const float* Fp, int k, const double* Gm,
+                  const int* long_rows, const int* long_segptr, int n_long, int nseg, double* dpart, double* num, double* den, hipStream_t st) {
+    hipLaunchKernelGGL((csr_colerr_rows_kernel<G, MASKED>), dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, st, rowptr, col, val, rows, Lp, Fp, k,
+                       Gm, num, den);
+    if (n_long > 0) {
+        hipLaunchKernelGGL((csr_colerr_long_kernel<G, MASKED>), dim3((unsigned)cdiv(nseg, 4)), dim3(256), 0, st, rowptr, col, val, Lp, Fp,
+                           long_rows, long_segptr, n_long, dpart);
+        hipLaunchKernelGGL(csr_colerr_long_reduce_kernel, dim3((unsigned)n_long), dim3(64), 0, st, (const double*)dpart, long_rows,
+                           long_segptr, Lp, 4 * G, k, Gm, num, den);
+    }
+    return check_launch("csr_column_err");
+}
+
+template <bool MASKED, typename... Args>
+int colerr_dispatch(int kpad, Args... a) {
+    switch (kpad) {
+        case 16: return colerr_launch<4, MASKED>(a...);
+        case 32: return colerr_launch<8, MASKED>(a...);
+        case 64: return colerr_launch<16, MASKED>(a...);
+        case 128: return colerr_launch<32, MASKED>(a...);
+        default: return colerr_launch<64, MASKED>(a...);
+    }
 }
 
 int check_common(const char* who, const int* rowptr, const int* col, const float* val, long rows, int k, const int* long_rows,
@@ -282,6 +323,55 @@ int dnmf_csr_masked_resid_sqnorm(const int* rowptr, const int* col, const float*
     hipLaunchKernelGGL(csr_resid_final_kernel, dim3(1), dim3(256), 0, st, (const double*)nullptr, 0, (const double*)nullptr, 0, 0,
                        (const double*)dpart, nw + (n_long > 0 ? nseg : 0), sq);
     return check_launch("csr_masked_resid_sqnorm");
+}
+
+// ---- NMFk on a sparse block
+// The perturbed copy of pyDNMFk.py:42-44 (`sample.randM`: X * (1 + nv + 2 nv U)) on ONE CSR image: val_out[p] = val[p] * factor of the
+// entry's position in the dense block, the factor of dnmf_perturb_uniform (csrc/dnmf_stream.h).  `transposed`: the image is the
+// transpose's (its row index is the block's column); `ncols`: the dense block's column count.
+int dnmf_csr_perturb_uniform(const int* rowptr, const int* col, const float* val, long rows, long ncols, int transposed, float noise_var,
+                             unsigned long long seed, float* val_out, void* stream) {
+    REQUIRE(rowptr && rows >= 1 && rows < (1L << 31), "csr_perturb_uniform: null row pointers or bad row count %ld (1 <= rows < 2^31)", rows);
+    REQUIRE(ncols >= 1 && ncols < (1L << 31), "csr_perturb_uniform: %ld columns of the dense block (1 <= ncols < 2^31)", ncols);
+    REQUIRE(!transposed || rows == ncols, "csr_perturb_uniform: the transpose's image has %ld rows, the dense block %ld columns", rows, ncols);
+    REQUIRE(val_out, "csr_perturb_uniform: null destination");
+    REQUIRE(std::isfinite(noise_var) && noise_var >= 0.f, "csr_perturb_uniform: noise_var %g (finite, >= 0)", (double)noise_var);
+    (void)col; (void)val;        // (null for a block without stored entries: never dereferenced then)
+    hipLaunchKernelGGL(csr_perturb_uniform_kernel, dim3((unsigned)std::min<long>(cdiv(rows, 4), 1L << 16)), dim3(256), 0, S(stream), rowptr,
+                       col, val, rows, ncols, transposed != 0, noise_var, seed, val_out);
+    return check_launch("csr_perturb_uniform");
+}
+
+size_t dnmf_csr_column_err_ws_bytes(long rows, long cols, int k, int masked, int nseg) {
+    if (rows < 1 || cols < 1 || nseg < 0 || csr_kpad_of(k) < 0) return 0;
+    return colerr_layout(cols, k, nseg, masked != 0).total;
+}
+
+// The per-column sums of pyDNMF.py:221-239 (`column_err`) over this rank's rows, on the TRANSPOSE's image (rows = the block's
+// columns, cols = the block's rows): Lp = packed H^T [rows x KPAD], Fp = packed W [cols x KPAD].
+int dnmf_csr_column_err(const int* rowptr, const int* col, const float* val, long rows, long cols, const float* Lp, const float* Fp, int k,
+                        int masked, const int* long_rows, const int* long_segptr, int n_long, int nseg, double* num, double* den, void* ws,
+                        size_t ws_bytes, void* stream) {
+    if (int rc = check_common("csr_column_err", rowptr, col, val, rows, k, long_rows, long_segptr, n_long, nseg)) return rc;
+    REQUIRE(Lp && Fp && num && den && cols >= 1 && cols < (1L << 31) && aligned16(Lp) && aligned16(Fp),
+            "csr_column_err: null / misaligned operand or bad shape");
+    const ColerrWs L = colerr_layout(cols, k, nseg, masked != 0);
+    const size_t need = masked ? (size_t)nseg * 2 * sizeof(double) : L.total;
+    if ((need > 0 || n_long > 0) && (!ws || ws_bytes < need || !aligned16(ws)))
+        return fail(DNMF_EWS, "csr_column_err: workspace %zu < %zu bytes", ws_bytes, need);
+    hipStream_t st = S(stream);
+    const int kpad = csr_kpad_of(k);
+    double* dpart = ws ? (double*)((char*)ws + L.dpart) : nullptr;
+    if (masked)
+        return colerr_dispatch<true>(kpad, rowptr, col, val, rows, Lp, Fp, k, (const double*)nullptr, long_rows, long_segptr, n_long, nseg,
+                                     dpart, num, den, st);
+    double* gpart = (double*)((char*)ws + L.gpart);
+    double* Gm = (double*)((char*)ws + L.gram);
+    const unsigned tiles = (unsigned)(cdiv(k, 16) * cdiv(k, 16));
+    hipLaunchKernelGGL(csr_gram_f64_kernel, dim3((unsigned)L.nc, tiles), dim3(256), 0, st, Fp, cols, kpad, k, cdiv(cols, L.nc), gpart);
+    hipLaunchKernelGGL(csr_gram_sum_kernel, dim3((unsigned)cdiv(k * k, 256)), dim3(256), 0, st, (const double*)gpart, L.nc, k * k, Gm);
+    return colerr_dispatch<false>(kpad, rowptr, col, val, rows, Lp, Fp, k, (const double*)Gm, long_rows, long_segptr, n_long, nseg, dpart, num,
+                                  den, st);
 }
 
 }  // extern "C"

@@ -19,6 +19,21 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
     return x;
 }
 
+// THE definition of the stream, element by element: the key of a seed, and the factor 1 + nv + 2 nv u of the element with linear
+// index L = r cols + c of the dense block -- u = the high (L even) or low (L odd) 24 bits of the hash of pair L >> 1.  The
+// one-element dense kernel and the CSR kernel (csrc/dnmf_csr.h) call it; the vector kernel below hashes once per pair and must
+// give every element this value.
+__device__ __forceinline__ unsigned long long perturb_key(unsigned long long seed) {
+    return mix64(seed * 0x9E3779B97F4A7C15ull + 0x632BE59BD9B4E019ull);
+}
+
+__device__ __forceinline__ float perturb_factor(unsigned long long key, unsigned long long L, float nv) {
+    const unsigned long long h = mix64(key + (L >> 1) * 0x9E3779B97F4A7C15ull);
+    const float u = (L & 1) ? (float)((unsigned)(h >> 8) & 0xffffffu) * (1.0f / 16777216.0f)
+                            : (float)((unsigned)(h >> 40)) * (1.0f / 16777216.0f);
+    return fmaf(2.0f * nv, u, 1.0f + nv);
+}
+
 template <typename TA>
 __global__ __launch_bounds__(256) void perturb_uniform_kernel(const TA* __restrict__ X, TA* __restrict__ out, long rows, long cols,
                                                               long ldx, long ldo, float nv, unsigned long long seed) {
@@ -64,16 +79,14 @@ template <typename TA>
 __global__ __launch_bounds__(256) void perturb_uniform_any_kernel(const TA* __restrict__ X, TA* __restrict__ out, long rows, long cols,
                                                                   long ldx, long ldo, float nv, unsigned long long seed) {
     const long total = rows * cols;
-    const unsigned long long key = mix64(seed * 0x9E3779B97F4A7C15ull + 0x632BE59BD9B4E019ull);
+    const unsigned long long key = perturb_key(seed);
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const long r = idx / cols, c = idx % cols;
-        const unsigned long long h = mix64(key + ((unsigned long long)idx >> 1) * 0x9E3779B97F4A7C15ull);
-        const float u = (idx & 1) ? (float)((unsigned)(h >> 8) & 0xffffffu) * (1.0f / 16777216.0f)
-                                  : (float)((unsigned)(h >> 40)) * (1.0f / 16777216.0f);
+        const float f = perturb_factor(key, (unsigned long long)idx, nv);
         if constexpr (std::is_same<TA, float>::value) {
-            out[r * ldo + c] = X[r * ldx + c] * fmaf(2.0f * nv, u, 1.0f + nv);
+            out[r * ldo + c] = X[r * ldx + c] * f;
         } else {
-            const float v = bf16_lo((unsigned int)X[r * ldx + c]) * fmaf(2.0f * nv, u, 1.0f + nv);
+            const float v = bf16_lo((unsigned int)X[r * ldx + c]) * f;
             const unsigned int w = __float_as_uint(v);
             out[r * ldo + c] = (bf16_t)((w + 0x7fffu + ((w >> 16) & 1u)) >> 16);
         }

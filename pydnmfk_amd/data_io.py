@@ -20,16 +20,23 @@ def _load_mat(path):
     return loadmat(path)['X']
 
 
+def _load_spnpz(path):
+    import scipy.sparse as sp
+    return sp.load_npz(path).tocsr()
+
+
 # ftype -> (reader, the file holds the WHOLE matrix: cut this rank's block out of it)
 _READERS = {'npy': (_load_npy, True), 'csv': (_load_text, True), 'txt': (_load_text, True), 'mat': (_load_mat, True),
-            'folder': (_load_npy, False)}
+            'folder': (_load_npy, False), 'spnpz': (_load_spnpz, True)}
+_EXT = {'spnpz': 'npz'}                                      # a scipy.sparse.save_npz file: <fname>.npz
 
 
 class data_read:
     """This rank's block of a dense matrix on disk -- what reference data_io.py:12-105 returns.
 
     File: args.fpath + args.fname + '.' + args.ftype for ftype in {npy, csv, txt, mat}; ftype == 'folder' names the pre-split
-    block fpath + fname + <rank> + '.npy', taken as is.  Whole-matrix files are cut by determine_block_params(rank, [p_r, p_c],
+    block fpath + fname + <rank> + '.npy', taken as is.  ftype == 'spnpz': fpath + fname + '.npz' written by scipy.sparse.save_npz
+    (the whole matrix); the rank's block is cut as CSR and comes back as a scipy.sparse matrix -- nothing is densified.  Whole-matrix files are cut by determine_block_params(rank, [p_r, p_c],
     shape) (data_io.py:81-83); the block is cast to args.precision (default float32).  Like the reference every rank opens the
     file; .npy files are memory-mapped here (the reference loads the whole matrix on every rank, data_io.py:57)."""
 
@@ -37,12 +44,12 @@ class data_read:
         opts = vars(args)
         self.ftype = args.ftype
         if self.ftype not in _READERS:
-            raise ValueError("unknown ftype '%s' (npy/csv/txt/mat/folder)" % self.ftype)
+            raise ValueError("unknown ftype '%s' (npy/csv/txt/mat/folder/spnpz)" % self.ftype)
         self.pgrid = opts.get("grid") or [args.p_r, args.p_c]
         self.rank = args.comm1.rank
         self.precision = opts.get("precision") or 'float32'
         whole = _READERS[self.ftype][1]
-        self.file_path = args.fpath + args.fname + ('.' + self.ftype if whole else '%d.npy' % self.rank)
+        self.file_path = args.fpath + args.fname + ('.' + _EXT.get(self.ftype, self.ftype) if whole else '%d.npy' % self.rank)
 
     def read(self):
         load, whole = _READERS[self.ftype]
@@ -51,6 +58,8 @@ class data_read:
             s, e = determine_block_params(self.rank, self.pgrid, data.shape).determine_block_index_range_asymm()
             data = data[s[0]:e[0] + 1, s[1]:e[1] + 1]
         prec = 'float32' if str(self.precision).lower() in ('bfloat16', 'bf16') else self.precision
+        if self.ftype == 'spnpz':                            # the rank's block stays sparse: a scipy CSR matrix for PyNMF / PyNMFk
+            return data.tocsr().astype(prec)
         return np.ascontiguousarray(data).astype(prec)       # bf16: numpy has no such dtype; PyNMF rounds on upload
 
     read_dat = read                                          # (the reference's name for the same call)

@@ -661,7 +661,8 @@ class HipCsrOps(HipOps):
     A block whose unstored entries are MISSING (`A.missing == 'unstored'`) takes the masked operations: `masked_aht_pair` /
     `masked_wta_pair` (numerator and denominator of the rule over the stored positions, as one contiguous [num | den] buffer for
     ONE allreduce), `ratio_update` after it, and `masked_update_w` / `masked_update_h` where nothing crosses ranks (the pass writes
-    the factor itself); `resid_sqnorm` then sums over the stored positions only."""
+    the factor itself); `resid_sqnorm` then sums over the stored positions only.
+    An NMFk sweep adds `perturb_uniform` (a new block with the source's pattern) and `column_err_sums` on a block (`sparse_nmfk`)."""
 
     name = "hip-csr"
     kl_uht_hblocks = None
@@ -883,9 +884,46 @@ class HipCsrOps(HipOps):
         self._dense_only("a whole-fit entry point", A)
         return super().fit(method, norm, A, W, H, eps, w_update, itr, column_sweep=column_sweep)
 
+    # ---- NMFk on a sparse block: the two operations of the sweep that touch A outside a fit
+    sparse_nmfk = True
+
+    def perturb_uniform(self, X, noise_var, seed, out=None):
+        """A SparseBlock: a NEW block with X's pattern (index arrays and long-row lists shared, `SparseBlock.with_values`) whose
+        values are X's times (1 + nv + 2 nv U) -- U keyed by (seed, position in the dense block), so both images hold what
+        HipOps.perturb_uniform gives the densified block at the stored positions, bit for bit.  Dense tensors: the inherited path."""
+        if not self._sp(X):
+            return super().perturb_uniform(X, noise_var, seed, out=out)
+        self._req_sp(X)
+        m, n = X.shape
+        val, t_val = torch.empty_like(X.val), torch.empty_like(X.t_val)
+        if X.nnz:
+            sd = int(seed) & (2**64 - 1)
+            check(lib.dnmf_csr_perturb_uniform(X.crow.data_ptr(), X.col.data_ptr(), X.val.data_ptr(), m, n, 0, float(noise_var), sd,
+                                               val.data_ptr(), _stream()))
+            check(lib.dnmf_csr_perturb_uniform(X.t_crow.data_ptr(), X.t_col.data_ptr(), X.t_val.data_ptr(), n, n, 1, float(noise_var), sd,
+                                               t_val.data_ptr(), _stream()))
+        return X.with_values(val, t_val)
+
     def column_err_sums(self, A, W, H):
-        self._dense_only("the per-column error of NMFk", A)
-        return super().column_err_sums(A, W, H)
+        """(num, den) per column over this rank's rows, float64 [n]: sum (A - W H)^2 and sum A^2 -- or, under missing='unstored', both
+        over the stored positions only -- from the transpose's image (dnmf_csr_column_err); a dense tensor takes the dense kernel."""
+        if not self._sp(A):
+            return super().column_err_sums(A, W, H)
+        self._req_sp(A)
+        m, n = A.shape
+        k = W.shape[1]
+        Wp, HTp = self._pack(W, False, "W"), self._pack(H, True, "HT")
+        masked = int(getattr(A, "missing", None) == "unstored")
+        nbytes = lib.dnmf_csr_column_err_ws_bytes(int(n), int(m), int(k), masked, int(A.t_nseg))
+        if nbytes == 0:
+            raise ValueError("sparse block: bad problem shape m=%d n=%d k=%d" % (m, n, k))
+        ws = _scratch(nbytes, A.device)
+        out = torch.empty(2, n, dtype=torch.float64, device=A.device)
+        nl = A.t_n_long
+        check(lib.dnmf_csr_column_err(A.t_crow.data_ptr(), A.t_col.data_ptr(), A.t_val.data_ptr(), n, m, HTp.data_ptr(), Wp.data_ptr(), int(k),
+                                      masked, A.t_long_rows.data_ptr() if nl else None, A.t_long_segptr.data_ptr() if nl else None, nl,
+                                      A.t_nseg, out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        return out[0], out[1]
 
 
 HIP_CSR_OPS = HipCsrOps()

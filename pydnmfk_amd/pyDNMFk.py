@@ -31,9 +31,11 @@ class sample:
     CUDA tensors are perturbed on the device with a torch generator seeded the same way (same distribution,
     different stream)."""
 
-    def __init__(self, data, noise_var, method, seed=None, out=None):
+    def __init__(self, data, noise_var, method, seed=None, out=None, sparse=None):
         self.X = data
         self.out = out          # optional destination of the perturbed copy (a slice of the stack an NMFk batch is fitted from)
+        # a SparseBlock: what the sweep keeps about it between the perturbations (SparseSweep; built here when the caller has none)
+        self.sparse = sparse if sparse is not None or not getattr(data, "is_sparse_block", False) else SparseSweep(data)
         self.noise_var = noise_var
         self.seed = seed
         if self.seed is not None:
@@ -43,6 +45,9 @@ class sample:
 
     def randM(self):
         nv = self.noise_var
+        if self.sparse is not None:
+            self.X_per = self.sparse.uniform(nv, self.seed)
+            return
         if isinstance(self.X, torch.Tensor):
             if self.X.is_cuda:      # one fused pass with a counter-based generator (dnmf_perturb_uniform): 1 GB of traffic per fit at
                 from .engine import HIP_OPS        # 65536 x 4096 bf16 where the torch expression below moves about 9 GB
@@ -59,6 +64,9 @@ class sample:
             self.X_per = np.multiply(self.X, M + 1)
 
     def poisson(self):
+        if self.sparse is not None:
+            self.X_per = self.sparse.poisson(self.seed)
+            return
         if isinstance(self.X, torch.Tensor):
             g = torch.Generator(device=self.X.device)
             g.manual_seed(0 if self.seed is None else int(self.seed))
@@ -74,6 +82,68 @@ class sample:
         return self.X_per
 
 
+def host_uniform_values(crow, col, val, shape, nv, chunk_rows=None):
+    """The reference's perturbation (pyDNMFk.py:42-44) of a CSR block from the process-global numpy stream: the values of
+    np.multiply(dense, M + 1), M = 2 nv random_sample(dense.shape).astype(float32) + nv, at the stored positions.  The uniforms are
+    drawn over the DENSE shape, `chunk_rows` rows at a time (random_sample fills row-major, so chunking by rows leaves the stream
+    as it is), and only the draws at stored positions are kept: O(m n) time, O(chunk_rows n) memory, and the generator ends in
+    the state the dense path leaves it in.  `crow`, `col`, `val`: numpy CSR arrays (columns in any order inside a row)."""
+    m, n = int(shape[0]), int(shape[1])
+    chunk_rows = int(chunk_rows) if chunk_rows else max(1, (1 << 22) // n)            # about 4 M draws (32 MB of float64) at a time
+    out = np.empty_like(val)
+    for r0 in range(0, m, chunk_rows):
+        r1 = min(m, r0 + chunk_rows)
+        M = 2 * nv * np.random.random_sample((r1 - r0, n)).astype(val.dtype) + nv
+        p0, p1 = int(crow[r0]), int(crow[r1])
+        rows = np.repeat(np.arange(r1 - r0), np.diff(crow[r0:r1 + 1]))
+        out[p0:p1] = np.multiply(val[p0:p1], M[rows, col[p0:p1]] + 1)
+    return out
+
+
+class SparseSweep:
+    """What an NMFk sweep over a SparseBlock keeps between its perturbations: the block, the permutation that carries the values
+    from the block's image to the transpose's (computed once, not kept on every block) and, for numpy I/O, the host copy of the
+    CSR arrays.  A perturbed copy is `block.with_values(...)`: it shares the pattern -- index arrays, long-row lists -- with the
+    source, so `prune=True` sees the source's all-empty rows / columns in every copy.
+
+    uniform: a block on the GPU that did not come from numpy I/O takes the keyed kernel (`ops.perturb_uniform`: the dense device
+    path's values at the stored positions, bit for bit).  numpy I/O (scipy input) and CPU blocks reproduce the reference's numpy
+    stream (host_uniform_values: O(m n) time on the host, O(chunk n) memory -- device input is the path that scales); PyNMF's rand
+    init then continues that stream, as for dense numpy input.
+    poisson: torch.poisson on the stored values with a generator seeded per perturbation; Poisson(0) = 0, so unstored zeros stay
+    zero, and a draw of 0 stays stored and contributes zero."""
+
+    def __init__(self, blk, numpy_io=False, ops=None):
+        self.blk, self.numpy_io, self.ops = blk, numpy_io, ops
+        self._perm = self._host = None
+
+    @property
+    def perm(self):
+        if self._perm is None:
+            self._perm = self.blk.transpose_perm()
+        return self._perm
+
+    def _with(self, val):
+        return self.blk.with_values(val, val[self.perm])
+
+    def uniform(self, nv, seed):
+        blk = self.blk
+        if blk.device.type == "cuda" and not self.numpy_io:
+            ops = self.ops
+            if ops is None:
+                from .engine import HIP_CSR_OPS as ops
+            return ops.perturb_uniform(blk, nv, 0 if seed is None else int(seed))
+        if self._host is None:
+            self._host = tuple(t.cpu().numpy() for t in (blk.crow, blk.col, blk.val))
+        val = host_uniform_values(*self._host, blk.shape, nv)
+        return self._with(torch.from_numpy(val).to(blk.device))
+
+    def poisson(self, seed):
+        g = torch.Generator(device=self.blk.device)
+        g.manual_seed(0 if seed is None else int(seed))
+        return self._with(torch.poisson(self.blk.val, generator=g))
+
+
 def _np(x):
     return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
@@ -83,9 +153,17 @@ class PyNMFk:
 
     def __init__(self, A_ij, factors=None, params=None, ops=None):
         from .sparse import is_sparse_input
-        if is_sparse_input(A_ij):
-            raise NotImplementedError("PyNMFk on sparse data is not provided: the perturbation kernel is keyed by dense element "
-                                      "position (PyNMF factorises sparse data at a given k)")
+        self._sparse = is_sparse_input(A_ij)
+        if self._sparse:
+            # the sweep touches A outside PyNMF.fit in two operations: the perturbed copy and the per-column error
+            if ops is None:
+                from .engine import HIP_CSR_OPS as opset
+            else:
+                opset = ops
+            if not (getattr(opset, "sparse_nmfk", False) and hasattr(opset, "column_err_sums")):
+                raise NotImplementedError("PyNMFk on sparse data is not provided by operator set %r: it has no per-column error and no "
+                                          "perturbed copy of a sparse block (PyNMF factorises sparse data at a given k)"
+                                          % (getattr(opset, "name", type(opset).__name__),))
         self.A_ij = A_ij
         self.ops = ops
         self.local_m, self.local_n = self.A_ij.shape
@@ -140,6 +218,27 @@ class PyNMFk:
         self.params.flag = 0   # 1: all perturbations factorised, 2: clustered, 3: results saved (pyDNMFk.py:165)
         self.cp = Checkpoint(checkpoint_save=self.params.checkpoint, params=self.params)
         self.stats = {}        # k -> cluster statistics (also written to disk per k)
+        self.sweep = None
+        if self._sparse:
+            self._sparse_setup(A_ij)
+
+    def _sparse_setup(self, A_ij):
+        """The SparseBlock of the sweep, built ONCE (keep_zeros and the meaning of an unstored entry from params.missing) and handed
+        to every PyNMF, which takes a block as it is; what PyNMF refuses for sparse data is refused here, in its words."""
+        from .sparse import SparseBlock
+        missing = PyNMF._missing_checks(A_ij, self.params, True)
+        PyNMF._sparse_checks(A_ij, self.params)
+        on_dev = isinstance(A_ij, torch.Tensor) or getattr(A_ij, "is_sparse_block", False)
+        if self.ops is None:
+            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda:
+                raise TypeError("PyNMFk: A_ij is a CPU tensor; pass a CUDA tensor or a scipy.sparse matrix (no CPU fallback)")
+            if not torch.cuda.is_available():
+                raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
+            device = A_ij.device if on_dev else torch.device("cuda", torch.cuda.current_device())
+        else:
+            device = A_ij.device if on_dev else torch.device("cpu")
+        self.A_ij = SparseBlock.from_any(A_ij, device, keep_zeros=(missing == "unstored"), missing=missing)
+        self.sweep = SparseSweep(self.A_ij, numpy_io=not on_dev, ops=self.ops)
 
     def fit(self):
         """pyDNMFk.py:169-215.  Returns the estimated number of latent features (same on every rank)."""
@@ -193,7 +292,7 @@ class PyNMFk:
                     stack = stack_alloc(len(chunk), self.A_ij.shape[0], self.A_ij.shape[1], self.A_ij.dtype,
                                         self.A_ij.device)            # the perturbed copies are written straight into it
                 data = sample(data=self.A_ij, noise_var=self.noise_var, method=self.sampling, seed=perturbation * 1000,
-                              out=None if stack is None else stack[b]).fit()
+                              out=None if stack is None else stack[b], sparse=self.sweep).fit()
                 self.params.W_update = True
                 if getattr(self.params, "rng", None) == "device":       # device-drawn init: one seed per (perturbation, k)
                     self.params.init_seed = perturbation * 1000 + self.k
@@ -248,13 +347,13 @@ class PyNMFk:
         self.AvgW = centroids
         self.params.W_update = False                                                                    # :245
         self.params.init_seed = None
-        numpy_io = not isinstance(self.A_ij, torch.Tensor)
+        numpy_io = self.sweep.numpy_io if self._sparse else not isinstance(self.A_ij, torch.Tensor)
         f0 = [_np(self.AvgW), _np(self.AvgH)] if numpy_io else [self.AvgW, self.AvgH]
         regressH = PyNMF(self.A_ij, factors=f0, params=self.params, ops=self.ops)
         self.AvgW, self.AvgH, self.L_errDist = regressH.fit()                                           # :246-247
         self.col_err = regressH.column_err()                                                            # :248
         self.avgErr = float(np.mean(self.recon_err))
-        mn = self.params.m * self.params.n
+        mn = self.params.m * self.params.n      # (sparse data too, under both meanings of an unstored entry: DESIGN.md "Sparse data")
         self.AIC = 2 * self.k + mn * np.log(self.avgErr / mn)                                           # :250
         cluster_stats = {'clusterSilhouetteCoefficients': self.clusterSilhouetteCoefficients,
                          'avgSilhouetteCoefficients': self.avgSilhouetteCoefficients, 'L_errDist': self.L_errDist,
@@ -306,6 +405,8 @@ class PyNMFk:
         operators -- as many as fit next to each other in the GPU's free memory (each holds its perturbed copy of the data) --
         else 1.  `params.nmfk_batch` = False / 0 / 1 keeps the one-by-one fits, an integer caps the batch."""
         want = getattr(self.params, "nmfk_batch", True)
+        if self._sparse:          # no batched sparse entry point: the fits run one by one and no stack is allocated
+            return 1
         if want is False or self.p != 1 or self.ops is not None or not torch.cuda.is_available():
             return 1
         cap = self.perturbations if want is True else max(1, int(want))

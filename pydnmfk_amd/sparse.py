@@ -226,6 +226,21 @@ class SparseBlock:
         out.__dict__.update({k_: (v.to(device) if isinstance(v, torch.Tensor) else v) for k_, v in self.__dict__.items()})
         return out
 
+    def with_values(self, val, t_val):
+        """A block with this block's pattern and new values (NMFk's perturbed copies): `crow` / `col` / `t_crow` / `t_col` and the
+        long-row lists are SHARED with this block, `val` (row-image order) and `t_val` (the same entries in the transpose's order)
+        are the new block's own.  `missing` carries over; nothing cached from the old values does."""
+        if val.shape != self.val.shape or t_val.shape != self.t_val.shape or val.dtype != torch.float32 or t_val.dtype != torch.float32:
+            raise ValueError("sparse data block: with_values() takes two float32 arrays of %d values" % self.nnz)
+        out = object.__new__(SparseBlock)
+        out.__dict__.update({k_: v for k_, v in self.__dict__.items() if k_ != "_sqnorm"})
+        out.val, out.t_val = val.contiguous(), t_val.contiguous()
+        return out
+
+    def transpose_perm(self):
+        """perm with t_val == val[perm]: the stable sort by column that _build_transpose applies (int64, on the block's device)"""
+        return torch.sort(self.col, stable=True)[1]
+
     def nnz_per_row(self):
         return (self.crow[1:] - self.crow[:-1]).long()
 

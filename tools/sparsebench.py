@@ -2,6 +2,7 @@
 dense step of the same build on the densified matrix where that fits.
 
     python tools/sparsebench.py [--json out.json] [--quick]
+    python tools/sparsebench.py --nmfk [--json out.json]        # NMFk on a sparse block: the two kernels and one small sweep
 
 Matrices: uniformly placed entries and power-law rows AND columns (Zipf exponent 1 over a random permutation), values uniform in
 [0.05, 1.05).  k = 16 and 64.  Every figure is the median (min / max next to it) of --steps timed steps after --warmup steps, each
@@ -100,14 +101,62 @@ def bench_block(blk, k, steps, warmup, dense=False):
     return out
 
 
+def bench_nmfk(steps, warmup):
+    """--nmfk: the perturbed copy (both images) and the per-column error of a sparse block, per call, under both meanings of an
+    unstored entry, and the wall time of one small sweep through PyNMFk.  Reported only: nothing here is a pass / fail condition."""
+    import tempfile
+    import time
+    from pydnmfk_amd.pyDNMFk import PyNMFk
+    ops = HIP_CSR_OPS
+    rows = []
+    for kind, m, n, nnz in (("uniform 0.01", 65536, 4096, int(0.01 * 65536 * 4096)), ("powerlaw", 2 ** 20, 2 ** 16, 20_000_000)):
+        blk = make_block(m, n, nnz, "uniform" if kind.startswith("uniform") else "powerlaw")
+        r = {"kind": kind, "m": m, "n": n, "nnz": blk.nnz, "long_cols": blk.t_n_long}
+        r["perturb_uniform"] = timed(lambda: ops.perturb_uniform(blk, 0.03, 1000), steps, warmup)
+        for k in (16, 64, 256):
+            W, H = torch.rand(m, k, device=blk.device), torch.rand(k, n, device=blk.device)
+            for missing in (None, "unstored"):
+                blk.missing = missing
+                r["column_err k=%d %s" % (k, missing or "zero")] = timed(lambda: ops.column_err_sums(blk, W, H), steps, warmup)
+            blk.missing = None
+            del W, H
+        rows.append(r)
+        del blk
+    blk = make_block(8192, 1024, int(0.02 * 8192 * 1024), "uniform")
+    a = _args(8192, 1024, 2, "fro")
+    a.fpath, a.fname, a.ftype, a.results_path = "", "sparsebench", None, tempfile.mkdtemp() + "/"
+    a.start_k, a.end_k, a.step_k, a.perturbations, a.noise_var, a.itr, a.checkpoint, a.rng = 2, 4, 1, 8, 0.03, 100, False, "device"
+    torch.cuda.synchronize()
+    t0 = time.time()
+    nopt = PyNMFk(blk, params=a).fit()
+    torch.cuda.synchronize()
+    sweep = {"m": 8192, "n": 1024, "nnz": blk.nnz, "k": "2..4", "perturbations": 8, "itr": 100, "seconds": time.time() - t0, "nopt": int(nopt)}
+    print("| matrix | m x n | nnz | long columns | perturb (both images) ms | " + " | ".join(
+        "col err k=%d %s ms" % (k, w) for k in (16, 64, 256) for w in ("zero", "unstored")) + " |")
+    print("|---|---|---|---|---|" + "---|" * 6)
+    for r in rows:
+        print("| %s | %d x %d | %d | %d | %.3f | " % (r["kind"], r["m"], r["n"], r["nnz"], r["long_cols"], r["perturb_uniform"]["median_ms"])
+              + " | ".join("%.3f" % r["column_err k=%d %s" % (k, w)]["median_ms"] for k in (16, 64, 256) for w in ("zero", "unstored")) + " |")
+    print("sweep: %(m)d x %(n)d, nnz %(nnz)d, k = %(k)s, %(perturbations)d perturbations x %(itr)d iterations (mu / fro, rng = device): "
+          "%(seconds).2f s, estimate %(nopt)d" % sweep)
+    return {"rows": rows, "sweep": sweep}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--nmfk", action="store_true", help="time the two kernels of NMFk on a sparse block and one small sweep (reported only)")
     ap.add_argument("--json")
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--quick", action="store_true", help="the crossover table only")
     opt = ap.parse_args()
     torch.cuda.set_device(0)
+    if opt.nmfk:
+        res = bench_nmfk(opt.steps, opt.warmup)
+        if opt.json:
+            with open(opt.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return 0
     rows = []
     m, n = 65536, 4096
     for dens in (0.001, 0.01, 0.05, 0.2):
