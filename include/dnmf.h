@@ -672,6 +672,35 @@ int dnmf_csr_column_err(const int* rowptr, const int* col, const float* val, lon
                         int k, int masked, const int* long_rows, const int* long_segptr, int n_long, int nseg, double* num,
                         double* den, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- dense data with missing entries: NaN = not observed (csrc/dnmf_masked.h) ----
+ * A [m x n] (lda) is float32 and stays as handed over; an entry is observed iff it is not NaN (a zero is an observation) -- there is no
+ * mask array.  With Omega the observed positions, S = W H and F = H^T (W side) or W (H side), the masked MU rules are pairs
+ *     kl == 0:  num = P_Omega(A) F,              den = P_Omega(S) F       dist_nmf.py:729-732 (W), :748-751 (H), sums over Omega
+ *     kl != 0:  num = P_Omega(A / (S + eps)) F,  den = P_Omega(1) F       dist_nmf.py:806-810 (the quotient), :827-849 (the rules)
+ * formed tile by tile on the matrix cores: S in accumulators, one compare and two selects per element, two second products.  On a block
+ * without a NaN they are the reference's rules up to summation order.  A row (column) without an observation gives exact zeros in
+ * both halves.  1 <= k <= DNMF_TUNED_MAX_K; any shape and any leading dimensions (NaN in the padding is never read as data).  Partial
+ * sums are added in a fixed order, no float atomics: bit-reproducible.
+ * `ws`: dnmf_masked_ws_bytes(m, n, k) bytes, 16-byte aligned (0: bad shape or rank). */
+size_t dnmf_masked_ws_bytes(long m, long n, int k);
+/* the pair stored: num, den [m x k] (W side) or [k x n] (H side) with the same leading dimension ldo -- the two halves of one contiguous
+ * buffer where the sums cross ranks (one allreduce, then dnmf_csr_ratio_update) */
+int dnmf_masked_aht_pair(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,
+                         int kl, float* num, float* den, long ldo, void* ws, size_t ws_bytes, void* stream);
+int dnmf_masked_wta_pair(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,
+                         int kl, float* num, float* den, long ldo, void* ws, size_t ws_bytes, void* stream);
+/* the pair applied where nothing crosses ranks: W <- W * num / (den + eps) (dist_nmf.py:731-732, :828-830), H alike (:750-751,
+ * :847-849) with max(., eps) if clamp != 0 (pyDNMF.py:170-172); the factor is updated in place after the pass has read it */
+int dnmf_masked_update_w(const float* A, long m, long n, long lda, float* W, long ldw, const float* H, long ldh, int k, float eps, int kl,
+                         void* ws, size_t ws_bytes, void* stream);
+int dnmf_masked_update_h(const float* A, long m, long n, long lda, const float* W, long ldw, float* H, long ldh, int k, float eps, int kl,
+                         int clamp, void* ws, size_t ws_bytes, void* stream);
+/* sq[0] = ||P_Omega(A - W H)||_F^2 (pyDNMF.py:205-218 over the observed positions), float64 (summed like dnmf_resid_sqnorm) */
+int dnmf_masked_resid_sqnorm(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
+                             double* sq, void* stream);
+/* out[0] = ||P_Omega(A)||_F^2, out[1] = |Omega| (the count of observed entries), both float64 */
+int dnmf_masked_sqnorm(const float* A, long m, long n, long lda, double* out, void* stream);
+
 /* ---- measurement aid (no counterpart in the reference) ----
  * Which shader clock does the GPU hold right now?  Launches ONE wave on `stream` that writes `n` pairs {s_memtime (shader
  * cycles), wall_clock64 (the constant 100 MHz reference)} into samples[2 n], sleeping `naps` x ~4 us between two pairs, and

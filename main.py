@@ -54,7 +54,7 @@ FLAGS = [
     ('direct_allreduce', _flag, False, False, 'with --exchange native on one node: the packed allreduce of a 1D step goes through IPC-mapped peer buffers (two-shot, rank-ordered sums) instead of RCCL, and the HALS W sweep on p_r > 1 runs as ONE persistent launch whose column norms cross the ranks through slots in those buffers; checked against RCCL on first contact, all ranks fall back together'),
     ('shared_gpu', _flag, False, False, 'the GPU is shared with other processes or streams: never use the kernels whose workgroups wait for each other (whole fits of small problems, the one-launch HALS W sweep, the one-pass MU/FRO step) -- dnmf_set_persistent(0); without it a fit that loses its residency is detected and fitted again on the launch-chain kernels, at the cost of one time-out'),
     ('hals_sweep', str, 'persistent', False, 'W sweep of method hals on a rank with local norms: persistent (one launch; needs the GPU to itself) or columns'),
-    ('missing', str, None, False, 'what an unstored entry of sparse input means: omitted = a zero; unstored = not observed (method mu, 1D grids)'),
+    ('missing', str, None, False, 'missing data (method mu, 1D grids): omitted = none (an unstored entry of sparse input is a zero, dense input is not scanned for NaN); unstored = an unstored entry of sparse input (--ftype spnpz) is not observed; nan = a NaN entry of dense input (mat / npy / csv / txt / folder, float32) is not observed'),
     # NMFk
     ('perturbations', int, 20, False, 'perturbed copies per rank'),
     ('noise_var', float, 0.015, False, 'perturbation amplitude'),
@@ -77,8 +77,23 @@ def build_parser():
     return ap
 
 
+_MISSING_NAN_SPARSE = ("--missing nan marks the missing entries of DENSE input; with --ftype spnpz the unstored entries are the missing "
+                       "ones: --missing unstored")
+
+
+def check_missing_flag(args):
+    """--missing: omitted, unstored (sparse input) or nan (the dense file types); decided from the flags alone, before any device is touched"""
+    if args.missing not in (None, 'unstored', 'nan'):
+        raise SystemExit("--missing must be unstored (sparse input) or nan (dense input), or omitted")
+    if args.missing == 'nan' and args.ftype == 'spnpz':
+        raise SystemExit(_MISSING_NAN_SPARSE)
+    if args.missing == 'nan' and args.process == 'pyDNMFk':
+        raise SystemExit("--missing nan is provided for --process pyDNMF (rank estimation over NaN-marked data is not)")
+
+
 def main():
     args = build_parser().parse_args()
+    check_missing_flag(args)
     import torch
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -114,8 +129,8 @@ def main():
     from pydnmfk_amd.sparse import is_sparse_input
     if args.missing is None:
         del args.missing                                   # (the choreography reads params.missing only when it is set)
-    elif args.missing != 'unstored':
-        raise SystemExit("--missing must be unstored (or omitted: unstored entries are zeros)")
+    elif args.missing == 'nan' and is_sparse_input(A_ij):
+        raise SystemExit(_MISSING_NAN_SPARSE)
     if is_sparse_input(A_ij):
         if args.rng == 'device':                           # the block's CSR arrays go to the GPU once; perturbations are drawn there
             A_ij = torch.sparse_csr_tensor(torch.from_numpy(A_ij.indptr.astype(np.int64)), torch.from_numpy(A_ij.indices.astype(np.int64)),

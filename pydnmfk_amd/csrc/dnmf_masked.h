@@ -1,0 +1,301 @@
+// dnmf_masked.h -- dense data with missing entries (NaN = not observed): the masked MU rules on the matrix cores.
+// Part of libdnmf_hip.so (kernels live in anonymous namespaces of the headers; the translation units csrc/*.hip include what they launch).
+//
+// With Omega the observed positions (a == a), S = W H and eps the float32 machine epsilon, both sides of a step are a pair
+//     fro:  num = P(A) F,          den = P(S) F                      (dist_nmf.py:729-732 for W, :748-751 for H, sums over Omega)
+//     kl:   num = P(A / (S + eps)) F,  den = P(1) F                  (dist_nmf.py:806-810, :827-849)
+// with F = H^T on the W side and W on the H side.  These are the two products of the dense KL kernels (csrc/dnmf_nn.h: a tile of S in
+// MFMA accumulators, an element-wise step against A, a second MFMA product) with another element-wise step -- one compare and two
+// selects per element -- and TWO second products that share their F fragments.  The data stay as handed over: there is no mask array,
+// the compare is the mask.
+//
+// No NaN reaches an MFMA operand: the selects come BEFORE the second product (0 * NaN is NaN), and the first product never sees A.
+// An A load outside the block returns 0, which reads as an OBSERVED zero: u_n = 0 either way, and u_d (S for fro, 1 for kl) meets a
+// zero of F there by construction -- a column c >= n is a zero column of the staged H tile (so is S), a row r >= m is a zero W row (the
+// predicated W loads) -- so it adds exactly nothing.  The padded contraction indices j >= k are zero rows of the staged H and zero
+// columns of the loaded W.  A row or column without an observation has u_n = u_d = 0 throughout: exact zeros in both halves.
+//
+// Every kernel here is generic: bounds by predication, any shape, any leading dimension (FAST = 16-byte rows, vector loads).  Sums
+// over column splits (W side) and row chunks (H side) are left as partials and added in split / chunk order by masked_reduce_kernel --
+// no float atomics, so a fit's factors are bit-reproducible.  Plain launch chains: no workgroup waits for another one.
+#pragma once
+#include "dnmf_common.h"
+#include "dnmf_nt.h"
+#include "dnmf_stream.h"
+#include "dnmf_nn.h"
+
+namespace {
+
+// the element-wise step: (u_n, u_d) of one element from its datum `a` and its model value s = <W[r], H[:, c]>
+template <bool KL>
+__device__ __forceinline__ void masked_pair(float a, float s, float eps, float& un, float& ud) {
+    const bool obs = a == a;
+    if constexpr (KL) {
+        un = obs ? kl_quot(a, s + eps) : 0.f;
+        ud = obs ? 1.f : 0.f;
+    } else {
+        un = obs ? a : 0.f;
+        ud = obs ? s : 0.f;
+    }
+}
+
+// ---- W side: P[split][half][m][KP], half 0 = num, 1 = den, over the columns of this split (row tiling of kl_uht_kernel: a workgroup
+// owns 128 rows, a lane the W row of its A row; S is formed transposed so that the contraction index of the second products is in
+// registers).  Two output accumulator sets do not fit next to the W row at KP = 128, so a workgroup owns JT of the KT 32-wide tiles of
+// output columns (blockIdx.z picks them; JT = KT up to KP = 64, JT = 2 at KP = 128 where S is formed twice).
+template <int KT, int JT, bool FAST, bool KL>
+__global__ __launch_bounds__(256, KT == 4 ? 1 : 2) void masked_uht_kernel(NnArgs p, float* __restrict__ P, long split_stride,
+                                                                          long half_stride, long cols_per_split) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int KP = 32 * KT, T = 256, STAGE = KP * BK, NY = KP / (T / 8);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
+    const long arow = (long)blockIdx.x * 128 + wave * 32 + li;
+    const bool rok = arow < p.m;
+    const long cbeg = (long)blockIdx.y * cols_per_split;
+    long cend = cbeg + cols_per_split;
+    if (cend > p.n) cend = p.n;
+    const long nt = (cend - cbeg + BK - 1) / BK;
+    const int jt0 = (int)blockIdx.z * JT;
+
+    f32x16 on[JT], od[JT];  // (num)^T and (den)^T tiles: rows j, lanes i
+#pragma unroll
+    for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { on[jt][r] = 0.f; od[jt][r] = 0.f; }
+    float wreg[4 * KT][4];   // W[arow][8s + 4h + e]; zero for j >= k and for rows >= m
+#pragma unroll
+    for (int s = 0; s < 4 * KT; ++s) load_vec<4, FAST>(wreg[s], p.W + arow * p.ldw, 8 * s + 4 * h, p.k, rok);
+
+    f32x4 hst[NY];
+    float a_cur[4][4];
+    if (nt > 0) {
+        stage_load<KP, T, FAST, false>(hst, p.H, p.ldh, p.k, cend, 0, cbeg, tid);     // zero outside k x [.., cend)
+        stage_store<KP, T>(smem, hst, tid);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) load_vec<4, FAST>(a_cur[g], p.A + arow * p.lda, cbeg + 8 * g + 4 * h, cend, rok);
+    }
+    __syncthreads();
+    for (long t = 0; t < nt; ++t) {
+        const int cur = t & 1;
+        const bool more = t + 1 < nt;
+        const long c1 = cbeg + (t + 1) * BK;
+        const float* Hs = smem + cur * STAGE;
+        f32x16 st;  // S^T tile: rows c, lanes i.  Starts from zero (an inline constant: HAZARD 2 of dnmf_common.h does not arise)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) st[r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < 4 * KT; ++s)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) st = MFMA32(Hs[lds_idx(8 * s + 4 * h + e, li >> 2) + (li & 3)], wreg[s][e], st);
+        f32x16 un, ud;
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float x, y;
+                masked_pair<KL>(a_cur[g][e], st[4 * g + e], p.eps, x, y);
+                un[4 * g + e] = x;
+                ud[4 * g + e] = y;
+            }
+        if (more) {   // the A registers are free now: the next tile's pieces (and the next H tile) under the second products
+            stage_load<KP, T, FAST, false>(hst, p.H, p.ldh, p.k, cend, 0, c1, tid);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) load_vec<4, FAST>(a_cur[g], p.A + arow * p.lda, c1 + 8 * g + 4 * h, cend, rok);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int jt = 0; jt < JT; ++jt) {
+                const f32x4 hh = *reinterpret_cast<const f32x4*>(&Hs[lds_idx((jt0 + jt) * 32 + li, 2 * g + h)]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    on[jt] = MFMA32(hh[e], un[4 * g + e], on[jt]);
+                    od[jt] = MFMA32(hh[e], ud[4 * g + e], od[jt]);
+                }
+            }
+        if (more) stage_store<KP, T>(smem + (cur ^ 1) * STAGE, hst, tid);
+        __syncthreads();
+    }
+    // on[jt] (reg, lane): j = (jt0 + jt) * 32 + crow(reg, h), i = arow; registers 4g..4g+3 are 4 consecutive j.  The slab rows are
+    // KP floats at a 256-byte aligned base: every store is a whole aligned vector inside the slab
+    if (rok) {
+        float* dn = P + (long)blockIdx.y * split_stride + arow * KP;
+        float* dd = dn + half_stride;
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int j = (jt0 + jt) * 32 + 8 * g + 4 * h;
+                *reinterpret_cast<f32x4*>(dn + j) = f32x4{on[jt][4 * g], on[jt][4 * g + 1], on[jt][4 * g + 2], on[jt][4 * g + 3]};
+                *reinterpret_cast<f32x4*>(dd + j) = f32x4{od[jt][4 * g], od[jt][4 * g + 1], od[jt][4 * g + 2], od[jt][4 * g + 3]};
+            }
+    }
+}
+
+// ---- H side: P[chunk][half][KP][ldp] over the rows of this chunk (the scheme of kl_wtu_kernel: a workgroup = 4 waves that share one
+// block of CW = 32 NT columns, whose KP x CW block of H is staged once; a wave walks a chunk of 32-row blocks, forms S, turns it into
+// (u_n, u_d) in place and feeds both as B operands of W^T u with the same W fragments).  ldp = ncolblk * CW: every store is in the slab.
+template <int KT, int NT, bool FAST, bool KL>
+__global__ __launch_bounds__(256, 1) void masked_wtu_kernel(NnArgs p, long half_stride, long rowblks_per_chunk) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int KP = 32 * KT, CW = 32 * NT;
+    const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, h = lane >> 5;
+    const int wid = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const long nchunks = cdiv(p.nrowblk, rowblks_per_chunk);
+    const long colblk = blockIdx.x % p.ncolblk;
+    const long chunk = (blockIdx.x / p.ncolblk) * 4 + wid;
+    const long col0 = colblk * CW;
+    for (int idx = tid; idx < KP * (CW / 4); idx += 256) {     // stage H[0:KP][col0:col0+CW] (zero outside k x n)
+        const int jj = idx / (CW / 4), c4 = (idx % (CW / 4)) * 4;
+        float d[4];
+        load_vec<4, FAST>(d, p.H + (long)jj * p.ldh, col0 + c4, p.n, jj < p.k);
+        *reinterpret_cast<f32x4*>(&smem[jj * CW + c4]) = f32x4{d[0], d[1], d[2], d[3]};
+    }
+    __syncthreads();
+    if (chunk >= nchunks) return;
+
+    f32x16 outn[KT][NT], outd[KT][NT];
+#pragma unroll
+    for (int ke = 0; ke < KT; ++ke)
+#pragma unroll
+        for (int ne = 0; ne < NT; ++ne)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { outn[ke][ne][r] = 0.f; outd[ke][ne][r] = 0.f; }
+    long rb1 = (chunk + 1) * rowblks_per_chunk;
+    if (rb1 > p.nrowblk) rb1 = p.nrowblk;
+    for (long rb = chunk * rowblks_per_chunk; rb < rb1; ++rb) {
+        const long row0 = rb * 32;
+        float areg[16][NT];   // A[row0 + crow(r,h)][col0 + NT*li + ne], requested first; becomes u_n
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const long row = row0 + crow(r, h);
+            load_vec<NT, FAST>(areg[r], p.A + row * p.lda, col0 + NT * li, p.n, row < p.m);
+        }
+        f32x16 acc[NT];       // S, then u_d
+#pragma unroll
+        for (int ne = 0; ne < NT; ++ne)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ne][r] = 0.f;
+        const long wrow = row0 + li;
+#pragma unroll
+        for (int s = 0; s < 4 * KT; ++s) {  // S = W H: contraction jj = 8s + 4h + e
+            float a[4];
+            load_vec<4, FAST>(a, p.W + wrow * p.ldw, 8 * s + 4 * h, p.k, wrow < p.m);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int jj = 8 * s + 4 * h + e;
+                float b[NT];
+                load_vec_raw<NT>(b, &smem[jj * CW + NT * li]);
+#pragma unroll
+                for (int ne = 0; ne < NT; ++ne) acc[ne] = MFMA32(a[e], b[ne], acc[ne]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+            for (int ne = 0; ne < NT; ++ne) {
+                float x, y;
+                masked_pair<KL>(areg[r][ne], acc[ne][r], p.eps, x, y);
+                areg[r][ne] = x;
+                acc[ne][r] = y;
+            }
+        // out[ke][ne] += sum_i W[i][KT*li + ke] * u[i][c]: A-operand lane (li, h) holds W[row0 + crow(r,h)][KT*li + ke]
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const long row = row0 + crow(r, h);
+            float w[KT];
+            load_vec<KT, FAST>(w, p.W + row * p.ldw, (long)KT * li, p.k, row < p.m);
+#pragma unroll
+            for (int ke = 0; ke < KT; ++ke)
+#pragma unroll
+                for (int ne = 0; ne < NT; ++ne) {
+                    outn[ke][ne] = MFMA32(w[ke], areg[r][ne], outn[ke][ne]);
+                    outd[ke][ne] = MFMA32(w[ke], acc[ne][r], outd[ke][ne]);
+                }
+        }
+    }
+    float* Pn = p.P + chunk * p.chunk_stride;
+    float* Pd = Pn + half_stride;
+#pragma unroll
+    for (int ke = 0; ke < KT; ++ke)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int j = KT * crow(r, h) + ke;
+            float dn[NT], dd[NT];
+#pragma unroll
+            for (int ne = 0; ne < NT; ++ne) { dn[ne] = outn[ke][ne][r]; dd[ne] = outd[ke][ne][r]; }
+            store_vec<NT, true>(dn, Pn + (long)j * p.ldp, col0 + (long)NT * li, p.ldp, true);
+            store_vec<NT, true>(dd, Pd + (long)j * p.ldp, col0 + (long)NT * li, p.ldp, true);
+        }
+}
+
+// ---- the endings: the partials added in part order, then either the pair stored (num, den with leading dimension ldo: the two halves
+// of one contiguous buffer where the sums cross ranks) or the rule applied, X <- X * (num / (den + eps)), max(., eps) with clamp
+// (the expression of dnmf_csr_ratio_update, which follows an allreduce of the stored pair)
+__global__ __launch_bounds__(256) void masked_reduce_kernel(const float* __restrict__ P, long part_stride, long half_stride, long ldp,
+                                                            int nparts, long rows, long cols, float* __restrict__ num,
+                                                            float* __restrict__ den, long ldo, float* __restrict__ X, long ldx, float eps,
+                                                            int clamp) {
+    const long total = rows * cols;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long r = idx / cols, c = idx % cols;
+        const float* q = P + r * ldp + c;
+        float a = q[0], b = q[half_stride];
+        for (int s = 1; s < nparts; ++s) {
+            a += q[s * part_stride];
+            b += q[s * part_stride + half_stride];
+        }
+        if (X) {
+            const float y = X[r * ldx + c] * (a / (b + eps));
+            X[r * ldx + c] = clamp ? fmaxf(y, eps) : y;
+        } else {
+            num[r * ldo + c] = a;
+            den[r * ldo + c] = b;
+        }
+    }
+}
+
+// ---- sum over Omega of (a - d)^2 (pyDNMF.py:205-218 over the observed positions): resid_kernel's tiles with the select; fp32 per tile
+// and lane (64 terms), float64 from there on, ending the way the dense residual does
+template <int KT, bool FAST>
+__global__ __launch_bounds__(256) void masked_resid_kernel(NnArgs p) {
+    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long gw = (long)blockIdx.x * 4 + wid;
+    double total = 0.0;
+    if (gw < p.nrowblk * p.ncolblk) {
+        const long row0 = (gw / p.ncolblk) * 32, col0 = (gw % p.ncolblk) * 128;
+        f32x16 acc[4];
+        nn_tile<KT, 4, FAST, false>(acc, p.W, p.ldw, p.m, p.k, p.H, p.ldh, p.n, row0, col0, li, h);
+        float part = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const long row = row0 + crow(r, h);
+            float a[4];
+            load_vec<4, FAST>(a, p.A + row * p.lda, col0 + 4 * li, p.n, row < p.m);
+#pragma unroll
+            for (int ne = 0; ne < 4; ++ne) {
+                // outside the block a = 0 and acc = 0 (zero-filled operands): an observed zero that is reproduced exactly
+                const float d = (a[ne] == a[ne]) ? a[ne] - acc[ne][r] : 0.f;
+                part = fmaf(d, d, part);
+            }
+        }
+        total = (double)part;
+    }
+    block_atomic_sum(total, p.out);
+}
+
+// out[0] = sum over Omega of a^2, out[1] = |Omega| (both float64; the count is exact below 2^53)
+__global__ __launch_bounds__(256) void masked_sqnorm_kernel(const float* __restrict__ A, long m, long n, long lda, double* __restrict__ out) {
+    double s = 0.0, cnt = 0.0;
+    const long total = m * n;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const float a = A[(idx / n) * lda + idx % n];
+        if (a == a) { s += (double)a * (double)a; cnt += 1.0; }
+    }
+    block_atomic_sum(s, out);
+    __syncthreads();                       // (block_atomic_sum's shared slots are read by thread 0 after its barrier)
+    block_atomic_sum(cnt, out + 1);
+}
+
+}  // namespace

@@ -1,0 +1,180 @@
+// dnmf_masked.hip -- C ABI of the masked MU rules on DENSE data whose missing entries are NaN (csrc/dnmf_masked.h).  A translation unit
+// of its own (see csrc/dnmf_kl.hip).  Plain launch chains: no workgroup waits for another one; no float atomics in the products.
+#include "dnmf_common.h"
+#include "dnmf_host.h"
+#include "dnmf_masked.h"
+
+namespace {
+
+// W side: 128-row tiles x column splits (x 2 halves of the output columns at KP = 128); splits are whole 32-column tiles
+struct MaskedUhtPlan { long rowtiles; int zdim; long cols_per_split; int nsplit; size_t bytes; };
+MaskedUhtPlan plan_masked_uht(long m, long n, int kt) {
+    MaskedUhtPlan u{};
+    u.rowtiles = cdiv(m, 128);
+    u.zdim = kt == 4 ? 2 : 1;
+    const long tiles = cdiv(n, BK);
+    long ns = std::max<long>(1, 512 / (u.rowtiles * u.zdim));       // about two workgroups per CU
+    ns = std::min<long>(std::min<long>(ns, tiles), 32);
+    u.cols_per_split = cdiv(tiles, ns) * BK;
+    u.nsplit = (int)cdiv(n, u.cols_per_split);
+    u.bytes = (size_t)u.nsplit * 2 * m * (32 * kt) * sizeof(float);
+    return u;
+}
+
+// H side: column blocks of CW = 32 NT columns x row chunks (a wave per chunk)
+struct MaskedWtuPlan { int nt; int ncolblk; long ldp; long nrowblk; long rowblks_per_chunk; long nchunks; size_t bytes; };
+MaskedWtuPlan plan_masked_wtu(long m, long n, int kt) {
+    MaskedWtuPlan w{};
+    w.nt = kt == 1 ? 4 : (kt == 2 ? 2 : 1);
+    w.ncolblk = (int)cdiv(n, 32 * w.nt);
+    w.ldp = (long)w.ncolblk * 32 * w.nt;
+    w.nrowblk = cdiv(m, 32);
+    const long want = std::min<long>(std::max<long>(1, 1024 / w.ncolblk), 64);   // about a wave per SIMD
+    w.rowblks_per_chunk = std::max<long>(1, cdiv(w.nrowblk, want));
+    w.nchunks = cdiv(w.nrowblk, w.rowblks_per_chunk);
+    w.bytes = (size_t)w.nchunks * 2 * (32 * kt) * w.ldp * sizeof(float);
+    return w;
+}
+
+NnArgs masked_args(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps) {
+    NnArgs a{};
+    a.A = A; a.lda = lda; a.m = m; a.n = n; a.W = W; a.ldw = ldw; a.H = H; a.ldh = ldh; a.k = k; a.eps = eps; a.kreal = k;
+    a.nrowblk = cdiv(m, 32); a.ncolblk = (int)cdiv(n, 128);
+    return a;
+}
+
+bool masked_fast(const float* A, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k) {
+    return aligned16(A) && aligned16(W) && aligned16(H) && lda % 4 == 0 && n % 4 == 0 && ldw % 4 == 0 && k % 4 == 0 && ldh % 4 == 0;
+}
+
+int masked_reduce(const float* P, long part_stride, long half_stride, long ldp, int nparts, long rows, long cols, float* num, float* den,
+                  long ldo, float* X, long ldx, float eps, int clamp, hipStream_t st, const char* who) {
+    const unsigned grid = (unsigned)std::min<long>(cdiv(rows * cols, 256), 8192);
+    hipLaunchKernelGGL(masked_reduce_kernel, dim3(grid), dim3(256), 0, st, P, part_stride, half_stride, ldp, nparts, rows, cols, num, den, ldo,
+                       X, ldx, eps, clamp);
+    return check_launch(who);
+}
+
+// the W side into partial slabs, then the ending: (num, den) stored, or X = W updated in place
+int masked_w_side(const char* who, const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
+                  float eps, int kl, float* num, float* den, long ldo, float* X, void* ws, size_t ws_bytes, void* stream) {
+    const int kt = kt_of(k);
+    REQUIRE(kt > 0, "%s: rank k=%d unsupported (1 <= k <= %d for masked dense data)", who, k, DNMF_TUNED_MAX_K);
+    REQUIRE(A && W && H && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n && (X || (num && den && ldo >= k)),
+            "%s: null pointer or bad shape", who);
+    const MaskedUhtPlan u = plan_masked_uht(m, n, kt);
+    if (!ws || ws_bytes < u.bytes || !aligned16(ws)) return fail(DNMF_EWS, "%s: workspace %zu < %zu bytes", who, ws_bytes, u.bytes);
+    const int kp = 32 * kt;
+    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
+    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
+    const long half = m * kp, split = 2 * half;
+    const dim3 grid((unsigned)u.rowtiles, (unsigned)u.nsplit, (unsigned)u.zdim), block(256);
+    const size_t lds = 2ul * kp * BK * sizeof(float);
+    hipStream_t st = S(stream);
+    float* P = (float*)ws;
+#define MU_CASE(KT_, JT_)                                                                                                    \
+    if (kt == KT_) {                                                                                                         \
+        if (fast && kl) hipLaunchKernelGGL((masked_uht_kernel<KT_, JT_, true, true>), grid, block, lds, st, a, P, split, half, u.cols_per_split);   \
+        else if (fast) hipLaunchKernelGGL((masked_uht_kernel<KT_, JT_, true, false>), grid, block, lds, st, a, P, split, half, u.cols_per_split);   \
+        else if (kl) hipLaunchKernelGGL((masked_uht_kernel<KT_, JT_, false, true>), grid, block, lds, st, a, P, split, half, u.cols_per_split);     \
+        else hipLaunchKernelGGL((masked_uht_kernel<KT_, JT_, false, false>), grid, block, lds, st, a, P, split, half, u.cols_per_split);            \
+    }
+    MU_CASE(1, 1) MU_CASE(2, 2) MU_CASE(4, 2)
+#undef MU_CASE
+    if (int rc = check_launch(who)) return rc;
+    return masked_reduce(P, split, half, kp, u.nsplit, m, k, num, den, ldo, X, ldw, eps, 0, st, who);
+}
+
+int masked_h_side(const char* who, const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
+                  float eps, int kl, float* num, float* den, long ldo, float* X, int clamp, void* ws, size_t ws_bytes, void* stream) {
+    const int kt = kt_of(k);
+    REQUIRE(kt > 0, "%s: rank k=%d unsupported (1 <= k <= %d for masked dense data)", who, k, DNMF_TUNED_MAX_K);
+    REQUIRE(A && W && H && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n && (X || (num && den && ldo >= n)),
+            "%s: null pointer or bad shape", who);
+    const MaskedWtuPlan w = plan_masked_wtu(m, n, kt);
+    if (!ws || ws_bytes < w.bytes || !aligned16(ws)) return fail(DNMF_EWS, "%s: workspace %zu < %zu bytes", who, ws_bytes, w.bytes);
+    const int kp = 32 * kt;
+    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
+    a.ncolblk = w.ncolblk;
+    const long half = (long)kp * w.ldp;
+    a.P = (float*)ws; a.ldp = w.ldp; a.chunk_stride = 2 * half;
+    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
+    const dim3 grid((unsigned)(cdiv(w.nchunks, 4) * w.ncolblk)), block(256);     // 4 row chunks (waves) per workgroup
+    const size_t lds = (size_t)kp * 32 * w.nt * sizeof(float);
+    hipStream_t st = S(stream);
+#define MH_CASE(KT_, NT_)                                                                                                    \
+    if (kt == KT_) {                                                                                                         \
+        if (fast && kl) hipLaunchKernelGGL((masked_wtu_kernel<KT_, NT_, true, true>), grid, block, lds, st, a, half, w.rowblks_per_chunk);    \
+        else if (fast) hipLaunchKernelGGL((masked_wtu_kernel<KT_, NT_, true, false>), grid, block, lds, st, a, half, w.rowblks_per_chunk);    \
+        else if (kl) hipLaunchKernelGGL((masked_wtu_kernel<KT_, NT_, false, true>), grid, block, lds, st, a, half, w.rowblks_per_chunk);      \
+        else hipLaunchKernelGGL((masked_wtu_kernel<KT_, NT_, false, false>), grid, block, lds, st, a, half, w.rowblks_per_chunk);             \
+    }
+    MH_CASE(1, 4) MH_CASE(2, 2) MH_CASE(4, 1)
+#undef MH_CASE
+    if (int rc = check_launch(who)) return rc;
+    return masked_reduce(a.P, a.chunk_stride, half, w.ldp, (int)w.nchunks, k, n, num, den, ldo, X, ldh, eps, clamp, st, who);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dnmf_masked_ws_bytes(long m, long n, int k) {
+    const int kt = kt_of(k);
+    if (kt < 0 || m < 1 || n < 1) return 0;
+    return align256(std::max(plan_masked_uht(m, n, kt).bytes, plan_masked_wtu(m, n, kt).bytes));
+}
+
+int dnmf_masked_aht_pair(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,
+                         int kl, float* num, float* den, long ldo, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE(num && den, "masked_aht_pair: null pointer or bad shape");
+    return masked_w_side("masked_aht_pair", A, m, n, lda, W, ldw, H, ldh, k, eps, kl, num, den, ldo, nullptr, ws, ws_bytes, stream);
+}
+
+int dnmf_masked_wta_pair(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,
+                         int kl, float* num, float* den, long ldo, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE(num && den, "masked_wta_pair: null pointer or bad shape");
+    return masked_h_side("masked_wta_pair", A, m, n, lda, W, ldw, H, ldh, k, eps, kl, num, den, ldo, nullptr, 0, ws, ws_bytes, stream);
+}
+
+int dnmf_masked_update_w(const float* A, long m, long n, long lda, float* W, long ldw, const float* H, long ldh, int k, float eps, int kl,
+                         void* ws, size_t ws_bytes, void* stream) {
+    return masked_w_side("masked_update_w", A, m, n, lda, W, ldw, H, ldh, k, eps, kl, nullptr, nullptr, 0, W, ws, ws_bytes, stream);
+}
+
+int dnmf_masked_update_h(const float* A, long m, long n, long lda, const float* W, long ldw, float* H, long ldh, int k, float eps, int kl,
+                         int clamp, void* ws, size_t ws_bytes, void* stream) {
+    return masked_h_side("masked_update_h", A, m, n, lda, W, ldw, H, ldh, k, eps, kl, nullptr, nullptr, 0, H, clamp != 0, ws, ws_bytes, stream);
+}
+
+int dnmf_masked_resid_sqnorm(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
+                             double* sq, void* stream) {
+    const int kt = kt_of(k);
+    REQUIRE(kt > 0, "masked_resid_sqnorm: rank k=%d unsupported (1 <= k <= %d for masked dense data)", k, DNMF_TUNED_MAX_K);
+    REQUIRE(A && W && H && sq && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n, "masked_resid_sqnorm: null pointer or bad shape");
+    hipStream_t st = S(stream);
+    if (hipMemsetAsync(sq, 0, sizeof(double), st) != hipSuccess) return fail(DNMF_EHIP, "masked_resid_sqnorm: memset failed");
+    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, 0.f);
+    a.out = sq;
+    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
+    const dim3 grid((unsigned)cdiv(a.nrowblk * a.ncolblk, 4)), block(256);
+#define MR_CASE(KT_)                                                                                     \
+    if (kt == KT_) {                                                                                     \
+        if (fast) hipLaunchKernelGGL((masked_resid_kernel<KT_, true>), grid, block, 0, st, a);           \
+        else hipLaunchKernelGGL((masked_resid_kernel<KT_, false>), grid, block, 0, st, a);               \
+    }
+    MR_CASE(1) MR_CASE(2) MR_CASE(4)
+#undef MR_CASE
+    return check_launch("masked_resid_sqnorm");
+}
+
+int dnmf_masked_sqnorm(const float* A, long m, long n, long lda, double* out, void* stream) {
+    REQUIRE(A && out && m >= 1 && n >= 1 && lda >= n, "masked_sqnorm: null pointer or bad shape");
+    hipStream_t st = S(stream);
+    if (hipMemsetAsync(out, 0, 2 * sizeof(double), st) != hipSuccess) return fail(DNMF_EHIP, "masked_sqnorm: memset failed");
+    const unsigned grid = (unsigned)std::min<long>(cdiv(m * n, 1024), 4096);
+    hipLaunchKernelGGL(masked_sqnorm_kernel, dim3(grid), dim3(256), 0, st, A, m, n, lda, out);
+    return check_launch("masked_sqnorm");
+}
+
+}  // extern "C"

@@ -41,7 +41,7 @@ def release_buffers():
 
 def _default_ops(params=None, like=None):
     from .engine import ops_for
-    return ops_for(params, like.dtype if like is not None else None, sparse=_is_sparse(like))
+    return ops_for(params, like.dtype if like is not None else None, sparse=_is_sparse(like), masked=_is_masked_dense(like))
 
 
 def _is_sparse(A):
@@ -49,10 +49,16 @@ def _is_sparse(A):
     return bool(getattr(A, "is_sparse_block", False))
 
 
+def _is_masked_dense(A):
+    """the data block is a pydnmfk_amd.masked.MaskedDenseBlock (dense float32, NaN = not observed): never handed to a kernel that reads A
+    as numbers -- no fused local step, no whole fit, no library-sequenced step, no column slices"""
+    return bool(getattr(A, "is_masked_dense", False))
+
+
 def _is_masked(A):
-    """the sparse block's UNSTORED entries are missing (SparseBlock.missing == 'unstored'): objective, rules and error over the stored
-    positions only"""
-    return _is_sparse(A) and getattr(A, "missing", None) == "unstored"
+    """objective, rules and error run over the OBSERVED positions only: a sparse block whose unstored entries are missing
+    (SparseBlock.missing == 'unstored'), or a dense block whose NaN entries are (MaskedDenseBlock, missing == 'nan')"""
+    return (_is_sparse(A) and getattr(A, "missing", None) == "unstored") or _is_masked_dense(A)
 
 
 def _kp(k):
@@ -70,8 +76,8 @@ class _Base:
     def _dispatch(self, clamp):
         norm, method = self.norm.upper(), self.method.upper()
         if _is_masked(self.A_ij) and method in ('HALS', 'BCD'):
-            raise NotImplementedError("missing='unstored' is provided for method 'mu' (fro / kl) only, not for '%s': HALS and BCD "
-                                      "contract with Gram matrices, which count every position" % self.method)
+            raise NotImplementedError("missing='%s' is provided for method 'mu' (fro / kl) only, not for '%s': HALS and BCD "
+                                      "contract with Gram matrices, which count every position" % (self.A_ij.missing, self.method))
         if norm == 'FRO':
             if method == 'MU':
                 self.Fro_MU_update(self.W_update, clamp)
@@ -190,8 +196,8 @@ class nmf_algorithms_1D(_Base):
         the RCCL communicator inside libdnmf_hip.so) -- same kernels in the same order as the choreography below, no Python
         between the launches.  float32 data, the product's own operator set, more than one rank."""
         hals = self.method.upper() == 'HALS' and self.norm.upper() == 'FRO'
-        if _is_sparse(self.A_ij):
-            return False            # (sparse data: the host sequences the sparse primitives)
+        if _is_sparse(self.A_ij) or _is_masked_dense(self.A_ij):
+            return False            # (sparse data, NaN-marked dense data: the host sequences the primitives)
         if (self.p == 1 and not getattr(self.params, "native_always", False)) or self.k > 128 or \
                 not (hals or (self.method.upper() == 'MU' and self.norm.upper() in ('FRO', 'KL'))):
             return False            # (k > 128: the library-sequenced steps stop at the tuned kernels' rank; the choreography below does not)
@@ -264,7 +270,7 @@ class nmf_algorithms_1D(_Base):
     def _masked_MU_update(self, norm, W_update=True, clamp=False):
         ops, A, W, H, eps, k = self.ops, self.A_ij, self.W_i, self.H_j, self.eps, self.k
         if not hasattr(ops, "masked_update_w"):
-            raise NotImplementedError("missing='unstored': the '%s' operator set has no masked operations" % getattr(ops, "name", "?"))
+            raise NotImplementedError("missing='%s': the '%s' operator set has no masked operations" % (A.missing, getattr(ops, "name", "?")))
         m_l, n_l = A.shape
         if W_update:
             if self.p_c == 1:                                      # the reference exchanges nothing here: the pass writes W
@@ -289,7 +295,7 @@ class nmf_algorithms_1D(_Base):
         ops, A, W, H, eps, k = self.ops, self.A_ij, self.W_i, self.H_j, self.eps, self.k
         if _is_masked(A):
             return self._masked_MU_update('fro', W_update, clamp)
-        if self.p == 1 and hasattr(ops, "mu_fro_step") and not _is_sparse(A):
+        if self.p == 1 and hasattr(ops, "mu_fro_step") and not _is_sparse(A) and not _is_masked_dense(A):
             ops.mu_fro_step(A, W, H, eps, W_update, clamp)         # whole local step, one library call
             return
         kp = _kp(k)
@@ -330,8 +336,8 @@ class nmf_algorithms_1D(_Base):
         Compute-side cost of the chunks on the 8-GPU shard (32768 x 8192, k = 64, tools/chunkbench.py, no exchange):
         1 / 2 / 4 / 8 chunks = 0.654 / 0.668 / 0.752 / 0.816 ms per step -- two chunks cost 13 us and hide about half of
         the exchange, four cost more than a 2 MiB allreduce is expected to take, hence the default."""
-        if self.p_c != 1 or self.p_r < 2 or _is_sparse(self.A_ij):
-            return 1                                               # (a sparse block is not sliced by columns)
+        if self.p_c != 1 or self.p_r < 2 or _is_sparse(self.A_ij) or _is_masked_dense(self.A_ij):
+            return 1                                               # (a sparse block or a NaN-marked block is not sliced by columns)
         nch = getattr(self.params, "overlap_chunks", None)
         if nch is None:                                            # default: two ranks keep the single packed allreduce
             nch = 2 if self.p_r > 2 else 1
@@ -396,7 +402,7 @@ class nmf_algorithms_1D(_Base):
         ops, A, W, H, eps, k = self.ops, self.A_ij, self.W_i, self.H_j, self.eps, self.k
         if _is_masked(A):                                          # (no rowsum / colsum vector: the sums run over the stored positions)
             return self._masked_MU_update('kl', W_update, clamp)
-        if self.p == 1 and hasattr(ops, "mu_kl_step") and not _is_sparse(A):
+        if self.p == 1 and hasattr(ops, "mu_kl_step") and not _is_sparse(A) and not _is_masked_dense(A):
             ops.mu_kl_step(A, W, H, eps, W_update, clamp)
             return
         m_l, n_l = A.shape
@@ -438,6 +444,9 @@ class nmf_algorithms_2D(_Base):
         if _is_sparse(A_ij):
             raise NotImplementedError("sparse data on a 2D grid (p_r = %d, p_c = %d) are not provided: the 2D choreography slices and "
                                       "gathers column blocks of A; use a 1D grid" % (self.p_r, self.p_c))
+        if _is_masked_dense(A_ij):
+            raise NotImplementedError("missing='nan' on a 2D grid (p_r = %d, p_c = %d) is not provided: the 2D choreography slices and "
+                                      "gathers column blocks of A for the unmasked products; use a 1D grid" % (self.p_r, self.p_c))
         self.rank = self.comm1.rank
         self.local_W_m = self.W_ij.shape[0]
         self.local_H_n = self.H_ij.shape[1]

@@ -929,6 +929,134 @@ class HipCsrOps(HipOps):
 HIP_CSR_OPS = HipCsrOps()
 
 
+class HipMaskedOps(HipOps):
+    """The operator set for a DENSE data block whose missing entries are NaN (pydnmfk_amd.masked.MaskedDenseBlock, `params.missing =
+    'nan'`): the operations that touch A are the masked ones of csrc/dnmf_masked.h (`dnmf_masked_*`: S = W H tiles in MFMA accumulators,
+    one compare and two selects per element, two second products) -- `masked_aht_pair` / `masked_wta_pair` (numerator and denominator
+    over the observed positions as one contiguous [num | den] buffer for ONE allreduce), `ratio_update` after it, `masked_update_w` /
+    `masked_update_h` where nothing crosses ranks, `resid_sqnorm` and `sqnorm` over the observed positions.  Everything that never
+    sees A -- clamps, normalisation, scaling -- is the fp32 code of HipOps.  Every dense operation that would read A as numbers (the
+    fused local steps, the whole fits, the plain products) refuses the block: those kernels would consume the NaNs."""
+
+    name = "hip-masked"
+    kl_uht_hblocks = None
+    aht_hblocks = None
+    _halves = staticmethod(HipCsrOps._halves)
+    ratio_update = HipCsrOps.ratio_update
+
+    @staticmethod
+    def _blk(A):
+        return getattr(A, "is_masked_dense", False)
+
+    def _masked(self, side, A, W, H, eps, norm, pair=None, X=None, clamp=False):
+        if not self._blk(A):
+            raise TypeError("masked update: the data must be a MaskedDenseBlock, got %s" % (type(A),))
+        if str(norm).lower() not in ("fro", "kl"):
+            raise ValueError("masked update: norm %r (fro / kl)" % (norm,))
+        kl = int(str(norm).lower() == "kl")
+        T = _req(A.tensor, "A")
+        _req(W, "W")
+        _req(H, "H")
+        m, n = T.shape
+        k = W.shape[1]
+        if tuple(W.shape) != (m, k) or tuple(H.shape) != (k, n):
+            raise ValueError("masked update: shapes A %s, W %s, H %s do not match" % (tuple(T.shape), tuple(W.shape), tuple(H.shape)))
+        nbytes = lib.dnmf_masked_ws_bytes(int(m), int(n), int(k))
+        if nbytes == 0:
+            raise NotImplementedError("missing='nan' with k = %d: the masked dense kernels serve 1 <= k <= 128" % k)
+        ws = _scratch(nbytes, T.device)
+        head = (T.data_ptr(), m, n, _ld(T), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), int(k), float(eps), kl)
+        tail = (ws.data_ptr(), ws.numel(), _stream())
+        if X is None:
+            num, den = pair
+            _req(num, "num")
+            _req(den, "den")
+            want = (m, k) if side == "w" else (k, n)
+            if tuple(num.shape) != want or tuple(den.shape) != want or _ld(num) != _ld(den):
+                raise ValueError("masked pair: num %s and den %s must both be %s with one leading dimension" % (tuple(num.shape), tuple(den.shape), want))
+            fn = lib.dnmf_masked_aht_pair if side == "w" else lib.dnmf_masked_wta_pair
+            check(fn(*head, num.data_ptr(), den.data_ptr(), _ld(num), *tail))
+            return num, den
+        if side == "w":
+            check(lib.dnmf_masked_update_w(*head, *tail))
+        else:
+            check(lib.dnmf_masked_update_h(*head, int(bool(clamp)), *tail))
+        return X
+
+    def masked_aht_pair(self, A, W, H, eps, norm, buf):
+        """buf = [num | den], each m x k: P(A) H^T and P(W H) H^T ('fro'), or P(A / (W H + eps)) H^T and P(1) H^T ('kl')"""
+        return self._masked("w", A, W, H, eps, norm, pair=self._halves(buf, tuple(W.shape)))
+
+    def masked_wta_pair(self, A, W, H, eps, norm, buf):
+        """buf = [num | den], each k x n: W^T P(A) and W^T P(W H) ('fro'), or W^T P(A / (W H + eps)) and W^T P(1) ('kl')"""
+        return self._masked("h", A, W, H, eps, norm, pair=self._halves(buf, tuple(H.shape)))
+
+    def masked_pair_into(self, side, A, W, H, eps, norm, num, den):
+        """the same pair into two views of the caller's (one leading dimension, any pitch): side 'w' (m x k) or 'h' (k x n)"""
+        return self._masked(side, A, W, H, eps, norm, pair=(num, den))
+
+    def masked_update_w(self, A, W, H, eps, norm):
+        """W <- W * num / (den + eps): the pass, then the rule on its partial sums (this rank's W rows see all their columns)"""
+        return self._masked("w", A, W, H, eps, norm, X=W)
+
+    def masked_update_h(self, A, W, H, eps, norm, clamp=False):
+        """H <- H * num / (den + eps), max(., eps) with `clamp` (this rank's H columns see all their rows)"""
+        return self._masked("h", A, W, H, eps, norm, X=H, clamp=clamp)
+
+    def _observed_sums(self, A):
+        """(||P(A)||^2, |Omega|) as two device doubles, evaluated once per block: the sum ends in float64 atomics whose order varies
+        between runs, and neither value changes during a fit"""
+        if A._sqnorm is None:
+            T = _req(A.tensor, "A")
+            out = torch.empty(2, dtype=torch.float64, device=T.device)
+            check(lib.dnmf_masked_sqnorm(T.data_ptr(), T.shape[0], T.shape[1], _ld(T), out.data_ptr(), _stream()))
+            A._sqnorm = out
+        return A._sqnorm
+
+    def sqnorm(self, A):
+        if not self._blk(A):
+            return super().sqnorm(A)
+        return self._observed_sums(A)[:1].clone()
+
+    def resid_sqnorm(self, A, W, H):
+        if not self._blk(A):
+            return super().resid_sqnorm(A, W, H)
+        T = _req(A.tensor, "A"); _req(W, "W"); _req(H, "H")
+        out = torch.empty(1, dtype=torch.float64, device=T.device)
+        check(lib.dnmf_masked_resid_sqnorm(T.data_ptr(), T.shape[0], T.shape[1], _ld(T), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H),
+                                           int(W.shape[1]), out.data_ptr(), _stream()))
+        return out
+
+    def _refuse(self, what, A):
+        if self._blk(A):
+            raise NotImplementedError("%s is not provided under missing='nan': it would read the NaNs of the block as data (the "
+                                      "choreography sequences the masked operations)" % what)
+
+
+def _masked_refusal(name, what):
+    def method(self, A, *args, **kwargs):
+        self._refuse(what, A)
+        return getattr(HipOps, name)(self, A, *args, **kwargs)
+    method.__name__ = name
+    return method
+
+
+for _name, _what in (("aht", "the product A H^T"), ("wta", "the product W^T A"), ("wta_gram", "the product W^T A"),
+                     ("aht_update_w", "the fused A H^T update"), ("mu_fro_step", "the fused local MU/FRO step"),
+                     ("mu_kl_step", "the fused local MU/KL step"), ("kl_uht", "the dense KL product U H^T"),
+                     ("kl_wtu", "the dense KL product W^T U"), ("column_err_sums", "the per-column error (NMFk)")):
+    setattr(HipMaskedOps, _name, _masked_refusal(_name, _what))
+
+
+def _masked_fit(self, method, norm, A, *args, **kwargs):
+    self._refuse("a whole-fit entry point", A)
+    return HipOps.fit(self, method, norm, A, *args, **kwargs)
+
+
+HipMaskedOps.fit = _masked_fit
+HIP_MASKED_OPS = HipMaskedOps()
+
+
 class HipOpsF64:
     """The operator set in float64 (csrc/dnmf_f64.hip: the fp64 matrix cores, one plain tile shape per kernel family).  The
     reference computes in the dtype of A_ij (pyDNMF.py:68): float64 data are factorised in float64, eps = 2.22e-16.  The same
@@ -1566,10 +1694,15 @@ def native_comm_for(params):
     return nc
 
 
-def ops_for(params=None, dtype=None, sparse=False):
+def ops_for(params=None, dtype=None, sparse=False, masked=False):
     """The operator set `params` asks for: `params.gemm` = 'fp32' (default: the fp32-MFMA contractions, the parity
     reference) or 'bf16x6' (HipOpsBf16x6); float64 data (`dtype`) take the float64 set whatever `gemm` says.  `sparse`: the
-    data block is a SparseBlock -- HipCsrOps (float32 values, fp32 arithmetic only)."""
+    data block is a SparseBlock -- HipCsrOps (float32 values, fp32 arithmetic only).  `masked`: it is a MaskedDenseBlock (dense
+    float32 data, NaN = not observed) -- HipMaskedOps."""
+    if masked:
+        if (getattr(params, "gemm", None) or "fp32") != "fp32":
+            raise NotImplementedError("missing='nan' with params.gemm = %r is not provided (fp32 arithmetic only)" % (params.gemm,))
+        return HIP_MASKED_OPS
     if sparse:
         if (getattr(params, "gemm", None) or "fp32") != "fp32":
             raise NotImplementedError("params.gemm = %r is not provided for sparse data (fp32 arithmetic only)" % (params.gemm,))

@@ -17,6 +17,9 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
     --gemm bf16x6 raise NotImplementedError); init is 'rand' or 'nnsvd' (1D grids);
   * sparse data (pydnmfk_amd.sparse) with `params.missing = 'unstored'`: an unstored entry is NOT OBSERVED instead of zero -- objective,
     MU rules (fro / kl) and the reported error run over the stored positions only (1D grids, method 'mu'; DESIGN.md "Sparse data");
+  * dense float32 data with `params.missing = 'nan'`: an entry is observed iff it is not NaN (a zero is an observation) -- the same
+    masked objective, rules and error on the matrix cores (pydnmfk_amd.masked, csrc/dnmf_masked.h; method 'mu', 1D grids, k <= 128).
+    Without `params.missing` dense data are not scanned for NaN;
   * `prune=True` (the reference's default when the attribute is absent) drops all-zero rows / columns before the
     iterations and scatters the factors back afterwards.  numpy callers get float64 factors back in that case, exactly
     as from the reference (its unprune scatters into np.zeros, utils.py:195,198); tensor callers keep float32 on the GPU.
@@ -88,10 +91,15 @@ class PyNMF:
         else:
             self.a_dtype = storage_dtype(A_ij, params)
         self.c_dtype = torch.float64 if self.a_dtype == torch.float64 else torch.float32      # factors, products, eps
+        self._masked_dense = (missing == "nan")
         if self._sparse:
             from .sparse import SparseBlock
             # (missing='unstored': a stored zero is an observation and stays stored; the block carries the meaning from here on)
             self.A_ij = SparseBlock.from_any(A_ij, device, keep_zeros=(missing == "unstored"), missing=missing)
+        elif self._masked_dense:
+            from .masked import MaskedDenseBlock
+            # (the data stay as handed over, NaN at the missing positions: the block carries the meaning from here on)
+            self.A_ij = MaskedDenseBlock(_to_device(A_ij, device, self.a_dtype))
         else:
             self.A_ij = _to_device(A_ij, device, self.a_dtype)
         self.params = params
@@ -113,6 +121,12 @@ class PyNMF:
         if self.a_dtype == torch.bfloat16 and str(self.norm).lower() == 'kl':
             raise TypeError("PyNMF: bfloat16 storage of A is provided for the Frobenius updates (mu / hals) only")
         self.prune = var_init(self.params, 'prune', default=True)
+        if self._masked_dense and self.prune:
+            raise NotImplementedError("missing='nan' with prune=True is not provided (pruning drops all-ZERO rows and columns; under "
+                                      "missing='nan' a row without an observation keeps its place and its factor row goes to zero): set "
+                                      "params.prune = False")
+        if self._masked_dense and self.params.k > 128:
+            raise NotImplementedError("missing='nan' with k = %d is not provided: the masked dense kernels serve 1 <= k <= 128" % self.params.k)
         self.save_factors = save_factors
         self.params.itr = var_init(self.params, 'itr', default=5000)
         self.itr = self.params.itr
@@ -153,23 +167,50 @@ class PyNMF:
 
     @staticmethod
     def _missing_checks(A_ij, params, sparse):
-        """`params.missing`: None (an unstored entry of sparse data is a zero) or 'unstored' (it is not observed).  The latter is
-        provided for sparse data with method 'mu' (fro / kl) on one rank and 1D grids."""
+        """`params.missing`: None (an unstored entry of sparse data is a zero; dense data are not scanned for NaN), 'unstored' (sparse
+        data: an unstored entry is not observed) or 'nan' (dense float32 data: a NaN entry is not observed).  Both meanings are provided
+        with method 'mu' (fro / kl) on one rank and 1D grids."""
         missing = getattr(params, "missing", None)
-        if missing not in (None, "unstored"):
-            raise ValueError("params.missing = %r is not known: None (unstored entries are zeros) or 'unstored' (not observed)" % (missing,))
+        if missing not in (None, "unstored", "nan"):
+            raise ValueError("params.missing = %r is not known: None (unstored entries are zeros), 'unstored' (sparse data: not observed) "
+                             "or 'nan' (dense data: NaN entries are not observed)" % (missing,))
+        if missing == "nan" and sparse:
+            raise ValueError("params.missing = 'nan' marks the missing entries of DENSE data; for sparse data the unstored entries are the "
+                             "missing ones: params.missing = 'unstored'")
         if getattr(A_ij, "is_sparse_block", False) and getattr(A_ij, "missing", None) != missing:
             raise ValueError("params.missing = %r, but the SparseBlock handed over was built with missing = %r: build the block with "
                              "the meaning (and keep_zeros) the fit is to use" % (missing, getattr(A_ij, "missing", None)))
         if missing is None:
             return None
-        if not sparse:
-            raise NotImplementedError("missing='unstored' is not provided for dense data (no mask, no NaN convention): hand the observed "
-                                      "entries over as a sparse matrix")
+        if missing == "unstored" and not sparse:
+            raise NotImplementedError("missing='unstored' is not provided for dense data: mark the missing entries of a dense array with "
+                                      "NaN and pass missing='nan', or hand the observed entries over as a sparse matrix")
         method = str(getattr(params, "method", None) or "mu").lower()
         if method != "mu":
-            raise NotImplementedError("missing='unstored' is provided for method 'mu' (fro / kl) only, not for '%s'" % method)
+            raise NotImplementedError("missing='%s' is provided for method 'mu' (fro / kl) only, not for '%s'" % (missing, method))
+        if missing == "nan":
+            PyNMF._masked_dense_checks(A_ij, params)
         return missing
+
+    @staticmethod
+    def _masked_dense_checks(A_ij, params):
+        """What is refused under missing='nan', each by name (dense float32 data, fp32 arithmetic, 1D grids, init='rand' or factors)."""
+        prec = getattr(params, "precision", None)
+        dt = getattr(A_ij, "dtype", None)
+        if isinstance(prec, str) and prec.lower() in ("bfloat16", "bf16") or prec is torch.bfloat16 or dt is torch.bfloat16:
+            raise NotImplementedError("missing='nan' with bfloat16 storage of the data is not provided (float32 data only)")
+        if dt in (torch.float64, np.dtype("float64")):
+            raise NotImplementedError("missing='nan' with float64 data is not provided (float32 data only); cast the block to float32")
+        if dt not in (torch.float32, np.dtype("float32")):
+            raise NotImplementedError("missing='nan' is provided for dense float32 data (a numpy array or a torch tensor), not for %s"
+                                      % (dt if dt is not None else type(A_ij).__name__,))
+        if (getattr(params, "gemm", None) or "fp32") != "fp32":
+            raise NotImplementedError("missing='nan' with --gemm %s is not provided (fp32 arithmetic only)" % params.gemm)
+        grid = getattr(params, "grid", None) or (getattr(params, "p_r", 1), getattr(params, "p_c", 1))
+        if grid[0] != 1 and grid[1] != 1:
+            raise NotImplementedError("missing='nan' on a 2D grid (%d x %d) is not provided: use a 1D grid (p_r = 1 or p_c = 1)" % (grid[0], grid[1]))
+        if getattr(params, "init", None) == "nnsvd":
+            raise NotImplementedError("missing='nan' with init='nnsvd' is not provided (the SVD would read the NaNs): init='rand' or factors=...")
 
     @staticmethod
     def _sparse_checks(A_ij, params):
@@ -243,7 +284,7 @@ class PyNMF:
     def _ops(self):
         if self.ops is None:
             from .engine import ops_for
-            self.ops = ops_for(self.params, self.c_dtype, sparse=self._sparse)
+            self.ops = ops_for(self.params, self.c_dtype, sparse=self._sparse, masked=self._masked_dense)
         return self.ops
 
     def _out(self, t):
@@ -317,7 +358,7 @@ class PyNMF:
         """One rank, the product's own fp32-MFMA operator set, a method / norm pair the library has a whole-fit entry point for
         (anything else keeps the step loop, which raises the reference's messages for invalid pairs).  `params.fit_loop =
         'python'` keeps the step loop (A/B runs, tests of the per-step API)."""
-        return (not self._sparse and self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") in ("hip", "hip-f64") and hasattr(ops, "fit")
+        return (not self._sparse and not self._masked_dense and self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") in ("hip", "hip-f64") and hasattr(ops, "fit")
                 and not (getattr(ops, "name", "") == "hip-f64" and self.k > 128)
                 and (str(self.method).lower(), str(self.norm).lower()) in _NATIVE_FITS
                 and not (str(self.method).lower() == "bcd" and (getattr(ops, "name", "") != "hip" or self.a_dtype != torch.float32))

@@ -154,6 +154,9 @@ class PyNMFk:
     def __init__(self, A_ij, factors=None, params=None, ops=None):
         from .sparse import is_sparse_input
         self._sparse = is_sparse_input(A_ij)
+        if getattr(params, "missing", None) == "nan" and not self._sparse:
+            raise NotImplementedError("PyNMFk with missing='nan' is not provided: rank estimation over NaN-marked data needs a masked "
+                                      "per-column error (PyNMF factorises such data at a given k)")
         if self._sparse:
             # the sweep touches A outside PyNMF.fit in two operations: the perturbed copy and the per-column error
             if ops is None:
