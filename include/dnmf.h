@@ -683,6 +683,15 @@ int dnmf_csr_column_err(const int* rowptr, const int* col, const float* val, lon
  * sums are added in a fixed order, no float atomics: bit-reproducible.
  * `ws`: dnmf_masked_ws_bytes(m, n, k) bytes, 16-byte aligned (0: bad shape or rank). */
 size_t dnmf_masked_ws_bytes(long m, long n, int k);
+/* The launch plans for an m x n block at rank k, host arithmetic only (nothing is launched): out = {tiles_per_split, nsplit, zdim,
+ * rowblks_per_chunk, nchunks, nrowblk}.  W side: nsplit column splits of tiles_per_split 32-column tiles each (the last split holds
+ * the rest), zdim halves of the output columns; its partial slabs take nsplit * 2 * m * KP floats.  H side: nrowblk 32-row blocks in
+ * nchunks chunks of rowblks_per_chunk (the last chunk holds the rest); its slabs take nchunks * 2 * KP * ldp floats, ldp = n rounded
+ * up to the column block of 4096 / KP columns.  KP = dnmf_kp(k).  Non-zero for an unsupported k, m or n < 1, or a null `out`. */
+int dnmf_masked_plan(long m, long n, int k, long out[6]);
+/* Workgroups (of 256 threads, one output element per thread and grid-stride trip) of the ending that adds the partial slabs, for a
+ * rows x cols output: m x k on the W side, k x n on the H side.  Host arithmetic only; 0 for rows or cols < 1. */
+long dnmf_masked_reduce_grid(long rows, long cols);
 /* the pair stored: num, den [m x k] (W side) or [k x n] (H side) with the same leading dimension ldo -- the two halves of one contiguous
  * buffer where the sums cross ranks (one allreduce, then dnmf_csr_ratio_update) */
 int dnmf_masked_aht_pair(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,

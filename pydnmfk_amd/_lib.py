@@ -198,6 +198,8 @@ SIGNATURES["dnmf_csr_column_err"] = [c_void_p, c_void_p, c_void_p, c_long, c_lon
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
 # dense data with NaN = not observed (csrc/dnmf_masked.hip): A m n lda W ldw H ldh k eps kl [clamp] [num den ldo] ws ws_bytes stream
 SIGNATURES["dnmf_masked_ws_bytes"] = [c_long, c_long, c_int]
+SIGNATURES["dnmf_masked_plan"] = [c_long, c_long, c_int, c_void_p]      # out: long[6]
+SIGNATURES["dnmf_masked_reduce_grid"] = [c_long, c_long]
 SIGNATURES["dnmf_masked_aht_pair"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_int, c_void_p, c_void_p,
                                       c_long, c_void_p, c_size_t, c_void_p]
 SIGNATURES["dnmf_masked_wta_pair"] = SIGNATURES["dnmf_masked_aht_pair"]
@@ -207,7 +209,7 @@ SIGNATURES["dnmf_masked_update_h"] = [c_void_p, c_long, c_long, c_long, c_void_p
                                       c_size_t, c_void_p]
 SIGNATURES["dnmf_masked_resid_sqnorm"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_void_p, c_void_p]
 SIGNATURES["dnmf_masked_sqnorm"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_void_p]
-_RESTYPES = {"dnmf_masked_ws_bytes": c_size_t, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
+_RESTYPES = {"dnmf_masked_ws_bytes": c_size_t, "dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
              "dnmf_ws_bytes_1d": c_size_t, "dnmf_ws_bytes_hblocks": c_size_t, "dnmf_ws_bytes_2d": c_size_t,
              "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t, "dnmf_bcd_ws_bytes_fit": c_size_t}
 

@@ -47,9 +47,12 @@ bool masked_fast(const float* A, long n, long lda, const float* W, long ldw, con
     return aligned16(A) && aligned16(W) && aligned16(H) && lda % 4 == 0 && n % 4 == 0 && ldw % 4 == 0 && k % 4 == 0 && ldh % 4 == 0;
 }
 
+// workgroups of masked_reduce_kernel (256 output elements each per grid-stride trip) for rows x cols outputs
+long masked_reduce_grid(long rows, long cols) { return std::min<long>(cdiv(rows * cols, 256), 8192); }
+
 int masked_reduce(const float* P, long part_stride, long half_stride, long ldp, int nparts, long rows, long cols, float* num, float* den,
                   long ldo, float* X, long ldx, float eps, int clamp, hipStream_t st, const char* who) {
-    const unsigned grid = (unsigned)std::min<long>(cdiv(rows * cols, 256), 8192);
+    const unsigned grid = (unsigned)masked_reduce_grid(rows, cols);
     hipLaunchKernelGGL(masked_reduce_kernel, dim3(grid), dim3(256), 0, st, P, part_stride, half_stride, ldp, nparts, rows, cols, num, den, ldo,
                        X, ldx, eps, clamp);
     return check_launch(who);
@@ -123,6 +126,30 @@ size_t dnmf_masked_ws_bytes(long m, long n, int k) {
     const int kt = kt_of(k);
     if (kt < 0 || m < 1 || n < 1) return 0;
     return align256(std::max(plan_masked_uht(m, n, kt).bytes, plan_masked_wtu(m, n, kt).bytes));
+}
+
+// the launch plans of both sides as numbers (host arithmetic, no GPU): what the launches above use, for callers and tests that must
+// know which loops of the kernels a shape enters
+int dnmf_masked_plan(long m, long n, int k, long out[6]) {
+    const int kt = kt_of(k);
+    REQUIRE(kt > 0, "masked_plan: rank k=%d unsupported (1 <= k <= %d for masked dense data)", k, DNMF_TUNED_MAX_K);
+    REQUIRE(out && m >= 1 && n >= 1, "masked_plan: null pointer or bad shape");
+    const MaskedUhtPlan u = plan_masked_uht(m, n, kt);
+    const MaskedWtuPlan w = plan_masked_wtu(m, n, kt);
+    out[0] = u.cols_per_split / BK;     // 32-column tiles a workgroup of the W side walks (the last split may hold fewer)
+    out[1] = u.nsplit;
+    out[2] = u.zdim;
+    out[3] = w.rowblks_per_chunk;       // 32-row blocks a wave of the H side walks (the last chunk may hold fewer)
+    out[4] = w.nchunks;
+    out[5] = w.nrowblk;
+    return DNMF_OK;
+}
+
+// the grid of the ending (masked_reduce_kernel) for a rows x cols output, as the launches size it: rows x cols = m x k on the W side,
+// k x n on the H side; the kernel takes cdiv(rows * cols, 256 * grid) grid-stride trips.  0 for rows or cols < 1.
+long dnmf_masked_reduce_grid(long rows, long cols) {
+    if (rows < 1 || cols < 1) return 0;
+    return masked_reduce_grid(rows, cols);
 }
 
 int dnmf_masked_aht_pair(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,

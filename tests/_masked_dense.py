@@ -197,13 +197,9 @@ EXACT_SHAPES = ((130, 97), (257, 70), (132, 96))          # (the third: rows and
 EXACT_KS = (3, 32, 64, 128)
 
 
-def exact_problem(m, n, k):
-    """tests/_exact.py::products(m, n, k) -- A in 0..7, W and H in 0..3, every unmasked product an integer below 2^24 -- under a 50 %
-    mask in which a few rows and columns keep exactly ONE observation (where a sum is a single term) and one row and one column keep
-    none.  Returns A, mask, W, H and the float64 answers: the four `fro` arrays and the two `kl` denominators (integers), the `kl`
-    numerators (float64 quotient sums) and the observation counts per row and column."""
-    A, W, H = E.products(m, n, k)
-    rs = np.random.RandomState(7 * m + n + k)
+def _exact_mask(rs, m, n):
+    """a 50 % mask in which rows 5, 64, m - 1 and columns 9, 40, n - 1 keep exactly ONE observation (where a sum is a single term) and
+    row 2 and column 3 keep none"""
     mask = rs.rand(m, n) < 0.5
     mask[2, :] = False                                                   # no observation at all
     mask[:, 3] = False
@@ -217,10 +213,105 @@ def exact_problem(m, n, k):
         free = [r for r in range(m) if r not in (2, 5, 64, m - 1)]
         if not keep.any():
             mask[free[rs.randint(len(free))], c] = True
+    return mask
+
+
+def _exact_ref(A, mask, W, H):
+    """the float64 answers of the masked pairs: the four `fro` arrays, the `kl` numerators (float64 quotient sums) and denominators,
+    the unmasked `fro` sums (which bound the masked ones: all terms are non-negative) and the observation counts per row and column"""
     A64, W64, H64, Mk = A.astype(np.float64), W.astype(np.float64), H.astype(np.float64), mask.astype(np.float64)
     D = W64 @ H64
     PA, PD = Mk * A64, Mk * D
     Q = Mk * A64 / (D + EPS)
-    ref = {"fro": (PA @ H64.T, PD @ H64.T, W64.T @ PA, W64.T @ PD), "kl": (Q @ H64.T, Mk @ H64.T, W64.T @ Q, W64.T @ Mk),
-           "unmasked_fro": (A64 @ H64.T, D @ H64.T, W64.T @ A64, W64.T @ D), "row_obs": mask.sum(1), "col_obs": mask.sum(0)}
+    return {"fro": (PA @ H64.T, PD @ H64.T, W64.T @ PA, W64.T @ PD), "kl": (Q @ H64.T, Mk @ H64.T, W64.T @ Q, W64.T @ Mk),
+            "unmasked_fro": (A64 @ H64.T, D @ H64.T, W64.T @ A64, W64.T @ D), "row_obs": mask.sum(1), "col_obs": mask.sum(0)}
+
+
+def exact_problem(m, n, k):
+    """tests/_exact.py::products(m, n, k) -- A in 0..7, W and H in 0..3, every unmasked product an integer below 2^24 -- under the mask
+    of `_exact_mask`.  Returns A, mask, W, H and the float64 answers of `_exact_ref`."""
+    A, W, H = E.products(m, n, k)
+    mask = _exact_mask(np.random.RandomState(7 * m + n + k), m, n)
+    return A, mask, W, H, _exact_ref(A, mask, W, H)
+
+
+def exact_problem_01(m, n, k):
+    """The same under a tall block, where the Gram denominators of tests/_exact.py::products pass its 2^22: A in 0..7, W and H in
+    {0, 1} with W[:, 0] = H[0, :] = 1, so that every model value <W_r, H_c> is an integer in 1..k.  Every unmasked sum is asserted
+    below 2^24 (and bounds the masked one: all terms are non-negative), the `kl` denominators as well."""
+    rs = np.random.RandomState(31 * m + 7 * n + k)
+    A = rs.randint(0, 8, size=(m, n)).astype(np.float32)
+    W = rs.randint(0, 2, size=(m, k)).astype(np.float32)
+    H = rs.randint(0, 2, size=(k, n)).astype(np.float32)
+    W[:, 0] = 1
+    H[0, :] = 1
+    mask = _exact_mask(rs, m, n)
+    ref = _exact_ref(A, mask, W, H)
+    for tot, what in zip(ref["unmasked_fro"], ("A H^T", "(W H) H^T", "W^T A", "W^T (W H)")):
+        E._bound(tot, 1.0, np.float32, what)
+    E._bound(np.float64(max(m, n)), 1.0, np.float32, "observation counts")
     return A, mask, W, H, ref
+
+
+# ---- exact operands at the smallest shapes whose launch plans (dnmf_masked_plan) enter the tile loop of masked_uht_kernel, the
+# row-block loop of masked_wtu_kernel and the grid-stride trip of masked_reduce_kernel; EXACT_SHAPES above stay at one trip of each.
+# Per case: shape, ranks, generator, whether the operands qualify for the 16-byte vector (FAST) kernels at k % 4 == 0, and what
+# tests/test_capi_masked.py must find in the plan at EVERY one of its ranks.  Derived there from the plan's six numbers:
+#   last_split_tiles  tiles of the last column split         last_tile_cols   width of its last tile (< 32: ragged, and not the first)
+#   last_chunk_blks   row blocks of the last row chunk       last_blk_rows    rows of its last block
+#   w_reduce_trips    grid-stride trips of the W side's ending, from dnmf_masked_reduce_grid(m, k) workgroups of 256 threads
+EXACT_LOOP_CASES = (
+    {"shape": (70, 2085), "ks": EXACT_KS, "gen": "products", "fast": False,          # W side, generic: cur goes 0, 1, 0
+     "reach": {"tiles_per_split": 3, "nsplit": 22, "last_split_tiles": 3, "last_tile_cols": 5}},
+    {"shape": (68, 2084), "ks": EXACT_KS, "gen": "products", "fast": True,           # W side through the vector loads
+     "reach": {"tiles_per_split": 3, "nsplit": 22, "last_split_tiles": 3, "last_tile_cols": 4}},
+    {"shape": (2130, 70), "ks": EXACT_KS, "gen": "products", "fast": False,          # H side, generic: a short last chunk
+     "reach": {"nrowblk": 67, "rowblks_per_chunk": 2, "nchunks": 34, "last_chunk_blks": 1, "last_blk_rows": 18}},
+    {"shape": (2132, 96), "ks": EXACT_KS, "gen": "products", "fast": True,           # H side through the vector paths
+     "reach": {"nrowblk": 67, "rowblks_per_chunk": 2, "nchunks": 34, "last_chunk_blks": 1, "last_blk_rows": 20}},
+    {"shape": (16400, 41), "ks": (128,), "gen": "01", "fast": False,                 # m k elements: a second trip of the reduce
+     "reach": {"tiles_per_split": 2, "nsplit": 1, "zdim": 2, "last_split_tiles": 2, "last_tile_cols": 9,
+               "nrowblk": 513, "rowblks_per_chunk": 9, "nchunks": 57, "last_chunk_blks": 9, "last_blk_rows": 16,
+               "w_reduce_trips": 2}},
+)
+EXACT_LOOP_SHAPES = tuple(c["shape"] for c in EXACT_LOOP_CASES)
+PLAN_FIELDS = ("tiles_per_split", "nsplit", "zdim", "rowblks_per_chunk", "nchunks", "nrowblk")
+
+
+def loop_case(shape):
+    return next(c for c in EXACT_LOOP_CASES if c["shape"] == tuple(shape))
+
+
+def plan_reach(m, n, k, plan, reduce_grid):
+    """the six numbers of dnmf_masked_plan as a dict, with the derived entries the table above names; `reduce_grid` is the library's
+    dnmf_masked_reduce_grid"""
+    d = dict(zip(PLAN_FIELDS, (int(x) for x in plan)))
+    last_cols = n - (d["nsplit"] - 1) * d["tiles_per_split"] * 32
+    d["last_split_tiles"] = -(-last_cols // 32)
+    d["last_tile_cols"] = last_cols - (d["last_split_tiles"] - 1) * 32
+    d["last_chunk_blks"] = d["nrowblk"] - (d["nchunks"] - 1) * d["rowblks_per_chunk"]
+    d["last_blk_rows"] = m - (d["nrowblk"] - 1) * 32
+    d["w_reduce_trips"] = -(-m * k // (256 * int(reduce_grid(m, k))))
+    d["h_reduce_trips"] = -(-k * n // (256 * int(reduce_grid(k, n))))
+    return d
+
+
+_LOOP_PROBLEMS = {}
+
+
+def loop_problem(m, n, k):
+    """(A, mask, W, H, ref) of a case of EXACT_LOOP_CASES from its generator, built once per process and shared: no test writes to them"""
+    key = (m, n, k)
+    if key not in _LOOP_PROBLEMS:
+        gen = exact_problem_01 if loop_case((m, n))["gen"] == "01" else exact_problem
+        _LOOP_PROBLEMS[key] = gen(m, n, k)
+    return _LOOP_PROBLEMS[key]
+
+
+def exact_resid_block(A, mask, W, H):
+    """(block, r): W H + r at the observed positions with r in {0, 1, 2}, NaN elsewhere -- integers, so the kernel's differences are
+    exactly r and the masked residual is sum(mask * r^2)"""
+    m, n = mask.shape
+    r = np.random.RandomState(3 * m + n).randint(0, 3, size=(m, n))
+    D = W.astype(np.float64) @ H.astype(np.float64)
+    return nan_marked((D + r).astype(np.float32), mask), r

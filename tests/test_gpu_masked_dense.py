@@ -112,6 +112,58 @@ def test_masked_dense_kernels_against_float64_and_csr(shape):
 
 
 # ---- 3. exact operands, element by element, on padded views
+def _pairs_on_views(blk, Wp, Hp, k, norm, aligned=True):
+    """both pairs of one objective into poisoned, pitched output views: (num_w, den_w, num_h, den_h) as numpy, after the check that
+    nothing outside a view was written and no NaN came through"""
+    ops = _ops()
+    m, n = blk.shape
+    out = []
+    for side, (r, c) in (("w", (m, k)), ("h", (k, n))):
+        num, den = E.Poisoned.out(torch, r, c, torch.float32, aligned=aligned), E.Poisoned.out(torch, r, c, torch.float32, aligned=aligned)
+        assert num.ld == den.ld > c
+        ops.masked_pair_into(side, blk, Wp.view, Hp.view, EPS, norm, num.view, den.view)
+        out += [num.check("%s %s num k=%d" % (norm, side, k)), den.check("%s %s den k=%d" % (norm, side, k))]   # nothing outside, no NaN
+    return tuple(out)
+
+
+def _exact_pair_checks(A, mask, W, H, ref, aligned=True):
+    """the checks of test_masked_dense_exact_operands on one problem; returns the views, the block and {norm: the four arrays}.
+    aligned=False: every view starts at an odd element and has an odd pitch (tests/_exact.py::Poisoned)"""
+    from pydnmfk_amd.masked import MaskedDenseBlock
+    m, n = A.shape
+    k = W.shape[1]
+    Ap = E.Poisoned(torch, D.nan_marked(A, mask), aligned=aligned)
+    Wp, Hp = E.Poisoned(torch, W, aligned=aligned), E.Poisoned(torch, H, aligned=aligned)
+    assert Ap.ld > n and Wp.ld > k and Hp.ld > n and not Ap.view.is_contiguous()
+    blk = MaskedDenseBlock(Ap.view)
+    got = {}
+    for norm in ("fro", "kl"):
+        nw, dw, nh, dh = got[norm] = _pairs_on_views(blk, Wp, Hp, k, norm, aligned)
+        rnw, rdw, rnh, rdh = ref[norm]
+        E.assert_ulp(dw, rdw, 0, "%s den_w k=%d" % (norm, k))
+        E.assert_ulp(dh, rdh, 0, "%s den_h k=%d" % (norm, k))
+        if norm == "fro":
+            E.assert_ulp(nw, rnw, 0, "fro num_w k=%d" % k)
+            E.assert_ulp(nh, rnh, 0, "fro num_h k=%d" % k)
+        else:
+            one_r, one_c = ref["row_obs"] == 1, ref["col_obs"] == 1
+            assert one_r.sum() >= 3 and one_c.sum() >= 1
+            E.assert_ulp(nw[one_r], rnw[one_r], 5, "kl num_w (single-observation rows) k=%d" % k)
+            E.assert_ulp(nh[:, one_c], rnh[:, one_c], 5, "kl num_h (single-observation columns) k=%d" % k)
+            for g, r_ in ((nw, rnw), (nh, rnh)):                                    # the rest: test 1's bound
+                assert np.linalg.norm(g - r_) <= 1e-5 * np.linalg.norm(r_), (norm, k)
+        assert not nw[ref["row_obs"] == 0].any() and not dw[ref["row_obs"] == 0].any()
+        assert not nh[:, ref["col_obs"] == 0].any() and not dh[:, ref["col_obs"] == 0].any()
+    _operands_not_written(Ap, Wp, Hp)
+    return Ap, Wp, Hp, blk, got
+
+
+def _operands_not_written(Ap, Wp, Hp):
+    for p_, what in ((Ap, "A"), (Wp, "W"), (Hp, "H")):
+        b = p_.buf.cpu().numpy()
+        assert np.isnan(b[~p_.mask]).all(), what
+
+
 @pytest.mark.parametrize("shape", D.EXACT_SHAPES, ids=lambda s: "%dx%d" % s)
 def test_masked_dense_exact_operands(shape):
     """tests/_exact.py::products under a 50 % mask written as NaN (tests/test_masked_dense_cpu.py proves every masked sum an integer
@@ -122,41 +174,112 @@ def test_masked_dense_exact_operands(shape):
     MFMA's multiply-add round once each (2^-24 each): at most 5 * 2^-24 relative in all, and one ulp of the result is at least 2^-24
     of it -- hence 5 ulp.  Elsewhere the numerators fall under test 1's bound.  (132, 96) adds the 16-byte vector paths on padded
     views to the issue's two shapes, whose widths are no multiple of 4.)"""
-    ops = _ops()
     m, n = shape
     for k in D.EXACT_KS:
-        A, mask, W, H, ref = D.exact_problem(m, n, k)
-        Ap = E.Poisoned(torch, D.nan_marked(A, mask))
-        Wp, Hp = E.Poisoned(torch, W), E.Poisoned(torch, H)
-        assert Ap.ld > n and Wp.ld > k and Hp.ld > n and not Ap.view.is_contiguous()
-        from pydnmfk_amd.masked import MaskedDenseBlock
+        _exact_pair_checks(*D.exact_problem(m, n, k))
+
+
+# ---- 3b. the same where a workgroup walks several tiles, a wave several row blocks, the reduce a second trip
+def _takes_vector_kernels(Ap, Wp, Hp, k):
+    """the library's own condition for its FAST kernels (csrc/dnmf_masked.hip::masked_fast), on the views handed over"""
+    n = Ap.cols
+    return all(p_.view.data_ptr() % 16 == 0 and p_.ld % 4 == 0 for p_ in (Ap, Wp, Hp)) and n % 4 == 0 and k % 4 == 0
+
+
+def _assert_within_an_ulp(got, exp, what):
+    from tests.test_gpu_masked import _ulp_apart
+    ok = _ulp_apart(got, exp)
+    if not ok.all():
+        idx = tuple(int(i) for i in np.argwhere(~ok)[0])
+        raise AssertionError("%s: %d of %d elements more than an ulp from x * (num / (den + eps)); first at %s: got %r, expected %r"
+                             % (what, int((~ok).sum()), ok.size, idx, got[idx].item(), exp[idx].item()))
+
+
+@pytest.mark.parametrize("shape", D.EXACT_LOOP_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_masked_dense_exact_operands_in_the_loops(shape):
+    """The checks of test_masked_dense_exact_operands at the shapes of tests/_masked_dense.py::EXACT_LOOP_CASES -- the smallest at
+    which dnmf_masked_plan (asserted in tests/test_capi_masked.py) gives a workgroup of masked_uht_kernel three tiles (both LDS
+    buffers, the prefetch, a ragged last tile that is not the first), a wave of masked_wtu_kernel two row blocks (and the last chunk
+    one), and masked_reduce_kernel a second grid-stride trip -- generic and 16-byte vector kernels.  Then each pair form once more on
+    the same inputs: bit-identical (partials are added in a fixed order, no float atomics)."""
+    case = D.loop_case(shape)
+    m, n = shape
+    for k in case["ks"]:
+        A, mask, W, H, ref = D.loop_problem(m, n, k)
+        Ap, Wp, Hp, blk, got = _exact_pair_checks(A, mask, W, H, ref)
+        assert _takes_vector_kernels(Ap, Wp, Hp, k) == (case["fast"] and k % 4 == 0), (shape, k)
+        for norm in ("fro", "kl"):
+            again = _pairs_on_views(blk, Wp, Hp, k, norm)
+            for a, b, what in zip(got[norm], again, ("num_w", "den_w", "num_h", "den_h")):
+                assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (shape, k, norm, what, "second call differs")
+
+
+@pytest.mark.parametrize("shape", [(70, 2085), (2130, 70)], ids=lambda s: "%dx%d" % s)
+def test_masked_dense_exact_operands_in_the_loops_at_odd_base_and_pitch(shape):
+    """The tile loop (70 x 2085) and the row-block loop (2130 x 70) once more with every operand and output view starting three
+    elements into its buffer at a pitch of its width + 3: no view is 16-byte aligned and rows fall at every 4-byte offset, at any
+    rank -- the per-element loads and stores of the generic kernels inside the loops, whatever k.  The same checks, the same bounds."""
+    case = D.loop_case(shape)
+    m, n = shape
+    for k in case["ks"]:
+        A, mask, W, H, ref = D.loop_problem(m, n, k)
+        Ap, Wp, Hp, _, _ = _exact_pair_checks(A, mask, W, H, ref, aligned=False)
+        assert all(p_.view.data_ptr() % 16 and p_.ld == p_.cols + 3 for p_ in (Ap, Wp, Hp)) and not _takes_vector_kernels(Ap, Wp, Hp, k)
+
+
+@pytest.mark.parametrize("shape", D.EXACT_LOOP_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_masked_dense_fused_endings_on_padded_views_in_the_loops(shape):
+    """masked_update_w, masked_update_h (clamp off and on) at the same shapes with the updated factor, the other factor and A all
+    poisoned, pitched views: each result within an ulp of x * (num / (den + eps)) evaluated in float32 from the pair the pair-writing
+    ending just wrote on the same views (the helper and bound of tests/test_gpu_masked.py, as test 1 has them on contiguous tensors);
+    nothing outside the view changes, no NaN comes through."""
+    from pydnmfk_amd.masked import MaskedDenseBlock
+    ops = _ops()
+    case = D.loop_case(shape)
+    m, n = shape
+    e = np.float32(EPS)
+    for k in case["ks"]:
+        A, mask, W, H, _ = D.loop_problem(m, n, k)
+        Ap, Wp, Hp = E.Poisoned(torch, D.nan_marked(A, mask)), E.Poisoned(torch, W), E.Poisoned(torch, H)
         blk = MaskedDenseBlock(Ap.view)
         for norm in ("fro", "kl"):
-            outs = {}
-            for side, (r, c) in (("w", (m, k)), ("h", (k, n))):
-                num, den = E.Poisoned.out(torch, r, c, torch.float32), E.Poisoned.out(torch, r, c, torch.float32)
-                assert num.ld == den.ld > c
-                ops.masked_pair_into(side, blk, Wp.view, Hp.view, EPS, norm, num.view, den.view)
-                outs[side] = (num.check("%s %s num k=%d" % (norm, side, k)), den.check("%s %s den k=%d" % (norm, side, k)))   # nothing outside, no NaN
-            (nw, dw), (nh, dh) = outs["w"], outs["h"]
-            rnw, rdw, rnh, rdh = ref[norm]
-            E.assert_ulp(dw, rdw, 0, "%s den_w k=%d" % (norm, k))
-            E.assert_ulp(dh, rdh, 0, "%s den_h k=%d" % (norm, k))
-            if norm == "fro":
-                E.assert_ulp(nw, rnw, 0, "fro num_w k=%d" % k)
-                E.assert_ulp(nh, rnh, 0, "fro num_h k=%d" % k)
-            else:
-                one_r, one_c = ref["row_obs"] == 1, ref["col_obs"] == 1
-                assert one_r.sum() >= 3 and one_c.sum() >= 1
-                E.assert_ulp(nw[one_r], rnw[one_r], 5, "kl num_w (single-observation rows) k=%d" % k)
-                E.assert_ulp(nh[:, one_c], rnh[:, one_c], 5, "kl num_h (single-observation columns) k=%d" % k)
-                for g, r_ in ((nw, rnw), (nh, rnh)):                                    # the rest: test 1's bound
-                    assert np.linalg.norm(g - r_) <= 1e-5 * np.linalg.norm(r_), (norm, k)
-            assert not nw[ref["row_obs"] == 0].any() and not dw[ref["row_obs"] == 0].any()
-            assert not nh[:, ref["col_obs"] == 0].any() and not dh[:, ref["col_obs"] == 0].any()
-        for p_, what in ((Ap, "A"), (Wp, "W"), (Hp, "H")):                            # the operands were not written
-            b = p_.buf.cpu().numpy()
-            assert np.isnan(b[~p_.mask]).all(), what
+            nw, dw, nh, dh = _pairs_on_views(blk, Wp, Hp, k, norm)
+            expW, expH = W * (nw / (dw + e)), H * (nh / (dh + e))
+            W1, H1, H2 = E.Poisoned(torch, W), E.Poisoned(torch, H), E.Poisoned(torch, H)
+            ops.masked_update_w(blk, W1.view, Hp.view, EPS, norm)
+            ops.masked_update_h(blk, Wp.view, H1.view, EPS, norm)
+            ops.masked_update_h(blk, Wp.view, H2.view, EPS, norm, clamp=True)
+            tag = "%dx%d %s k=%d " % (m, n, norm, k)
+            _assert_within_an_ulp(W1.check(tag + "fused W"), expW, tag + "fused W")
+            _assert_within_an_ulp(H1.check(tag + "fused H"), expH, tag + "fused H")
+            _assert_within_an_ulp(H2.check(tag + "fused H, clamped"), np.maximum(expH, e), tag + "fused H, clamped")
+        _operands_not_written(Ap, Wp, Hp)
+
+
+@pytest.mark.parametrize("shape", D.EXACT_LOOP_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_masked_dense_exact_residual_in_the_loops(shape):
+    """The block W H + r, r in {0, 1, 2} at the observed positions (tests/test_masked_dense_cpu.py proves the per-lane float32
+    partials exact): the masked residual equals sum(mask * r^2) as a float64, on poisoned views.  The sum of squares of the exact
+    problem's own block equals the integer sum, and the kernel's count of observed entries the mask's."""
+    from pydnmfk_amd.masked import MaskedDenseBlock
+    ops = _ops()
+    case = D.loop_case(shape)
+    m, n = shape
+    for k in case["ks"]:
+        A, mask, W, H, _ = D.loop_problem(m, n, k)
+        Rn, r = D.exact_resid_block(A, mask, W, H)
+        Rp, Wp, Hp = E.Poisoned(torch, Rn), E.Poisoned(torch, W), E.Poisoned(torch, H)
+        got = float(ops.resid_sqnorm(MaskedDenseBlock(Rp.view), Wp.view, Hp.view).cpu())
+        want = float((mask * r ** 2).sum())
+        assert got == want, (shape, k, got, want)
+        _operands_not_written(Rp, Wp, Hp)
+    A, mask, _, _, _ = D.loop_problem(m, n, case["ks"][-1])
+    Ap = E.Poisoned(torch, D.nan_marked(A, mask))
+    blk = MaskedDenseBlock(Ap.view)
+    sq = float(ops.sqnorm(blk).cpu())
+    assert sq == float((A.astype(np.int64) ** 2)[mask].sum()), (shape, sq)
+    assert float(blk._sqnorm[1].cpu()) == float(mask.sum()) == blk.n_observed
+    assert np.isnan(Ap.buf.cpu().numpy()[~Ap.mask]).all()
 
 
 # ---- 4. single steps along a float64 trajectory, through PyNMF

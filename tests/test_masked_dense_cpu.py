@@ -231,14 +231,23 @@ def test_main_accepts_missing_nan_for_dense_file_types_and_refuses_spnpz(tmp_pat
 
 
 # ---- 4. the exact operands of the GPU test stay exact under a mask (float64 proof)
-@pytest.mark.parametrize("shape", D.EXACT_SHAPES, ids=lambda s: "%dx%d" % s)
+def _exact_case(shape):
+    """(ranks, problem builder) of a shape of EXACT_SHAPES or EXACT_LOOP_SHAPES"""
+    if shape in D.EXACT_SHAPES:
+        return D.EXACT_KS, D.exact_problem
+    return D.loop_case(shape)["ks"], D.loop_problem
+
+
+@pytest.mark.parametrize("shape", D.EXACT_SHAPES + D.EXACT_LOOP_SHAPES, ids=lambda s: "%dx%d" % s)
 def test_masked_exact_operands_are_integers_below_2_24(shape):
-    """all terms are non-negative, so a masked sum is at most the unmasked sum tests/_exact.py::products already bounds -- asserted
-    here, not assumed: every masked `fro` numerator and denominator (and the `kl` denominators) is an integer below 2^24, hence exact
-    in float32 in any summation order"""
+    """all terms are non-negative, so a masked sum is at most the unmasked sum the generator already bounds -- asserted here, not
+    assumed: every masked `fro` numerator and denominator (and the `kl` denominators) is an integer below 2^24, hence exact in float32
+    in any summation order.  The shapes of EXACT_LOOP_CASES (more tiles per split, more row blocks per chunk: longer partial sums in
+    one accumulator) and the 0 / 1 generator of the tall one included."""
     m, n = shape
-    for k in D.EXACT_KS:
-        A, mask, W, H, ref = D.exact_problem(m, n, k)
+    ks, problem = _exact_case(shape)
+    for k in ks:
+        A, mask, W, H, ref = problem(m, n, k)
         assert (A >= 0).all() and (W >= 0).all() and (H >= 0).all()
         assert 0.4 < mask.mean() < 0.6
         assert (ref["row_obs"] == 0).any() and (ref["col_obs"] == 0).any() and (ref["row_obs"] == 1).sum() >= 3 and (ref["col_obs"] == 1).sum() >= 1
@@ -252,3 +261,27 @@ def test_masked_exact_operands_are_integers_below_2_24(shape):
         # every model value <W_r, H_c> is an integer of at most 9 k: the first product is exact as well
         Dm = W.astype(np.float64) @ H.astype(np.float64)
         assert np.array_equal(Dm, np.round(Dm)) and Dm.max() <= 9 * k
+        if problem is D.loop_problem and D.loop_case(shape)["gen"] == "01":
+            assert set(np.unique(W)) <= {0.0, 1.0} and set(np.unique(H)) <= {0.0, 1.0} and 1 <= Dm.min() and Dm.max() <= k
+        print("exact operands %dx%d k=%d: largest unmasked sum %d, largest masked sum %d" % (m, n, k, max(x.max() for x in ref["unmasked_fro"]),
+                                                                                         max(x.max() for x in ref["fro"])))
+
+
+@pytest.mark.parametrize("case", D.EXACT_LOOP_CASES, ids=lambda c: "%dx%d" % c["shape"])
+def test_exact_residual_block_has_exact_per_lane_partials(case):
+    """The block W H + r, r in {0, 1, 2}, NaN where not observed: its entries are integers below 2^24 (exact in float32), the model
+    value the kernel forms is the same integer (the proof above), so every difference is exactly r and every squared difference at
+    most 4.  A lane of masked_resid_kernel adds 64 of them in float32 (16 rows x 4 columns of its tile): at most 256, far below
+    2^24, whatever the order.  From there on the sums are float64: the total, an integer of at most 4 m n, is below 2^53.  The sum of
+    squares of the data block itself (`sqnorm`) is an integer of at most 49 m n in float64 throughout."""
+    m, n = case["shape"]
+    for k in case["ks"]:
+        A, mask, W, H, _ = D.loop_problem(m, n, k)
+        blk, r = D.exact_resid_block(A, mask, W, H)
+        assert set(np.unique(r)) == {0, 1, 2} and np.array_equal(np.isnan(blk), ~mask)
+        Dm = W.astype(np.float64) @ H.astype(np.float64)
+        assert np.array_equal(blk[mask].astype(np.float64), (Dm + r)[mask]) and (Dm + r).max() < 2.0 ** 24      # stored without rounding
+        d2 = (blk[mask].astype(np.float64) - Dm[mask]) ** 2
+        assert d2.max() <= 4 and 64 * d2.max() < 2.0 ** 24
+        assert float(d2.sum()) == float((mask * r ** 2).sum()) <= 4.0 * m * n < 2.0 ** 53
+        assert 49.0 * m * n < 2.0 ** 53 and float((A.astype(np.float64) ** 2)[mask].sum()) == float(np.sum((mask * A.astype(np.int64) ** 2)))
