@@ -281,6 +281,22 @@ int dnmf_mu_fit_persistent(long m, long n, int k);
 /* != 0: dnmf_hals_fro_fit[_bf16a] with w_update != 0 and column_sweep == 0 runs fits of this shape on the persistent kernel too (A streamed
  * from the L2, fp32 or bf16-stored; the k column norms of a W sweep cross the problem's workgroups through value-as-flag slots) */
 int dnmf_hals_fit_persistent(long m, long n, int k);
+/* Which persistent kernel a whole fit of this shape takes and with what geometry, host arithmetic only (nothing is launched; the switch
+ * dnmf_set_persistent is not consulted), from the functions the launches call.  method: 0 MU/FRO, 1 MU/KL, 2 HALS/FRO; bf16 != 0: A stored
+ * as bfloat16 (the *_bf16a fits; refused for MU/KL); w_update as passed to the fit.
+ * out = {route, KP, NW, ALDS, P, ns, cw, bf16_resident}.  route 0: none (the launch chain); 1: the barrier kernel of the method
+ * (small_kl_fit_kernel / small_fro_fit_kernel, with W fixed the former at w_update = 0); 2: the W-fixed MU/KL kernel (small_kl_hfit_kernel:
+ * all of W fits the LDS; no barrier); 3: the HALS kernel.  KP = 16 or 32 (k padded); NW = waves of a workgroup (slabs of 16 NW rows); ALDS != 0:
+ * the slab of A lives in LDS, else it is streamed; P = workgroups per problem (slabs; route 2: 16-column tiles); ns = n rounded up to 16;
+ * cw = columns of H a workgroup of the HALS kernel sweeps; bf16_resident != 0: the HALS kernel keeps the bf16 slab in LDS.  All zero behind
+ * route 0.  Route 3 is what dnmf_hals_fro_fit[_bf16a] takes with column_sweep == 0; with column_sweep != 0 the fit takes the launch chain
+ * whatever the query says.  Non-zero for an unknown method, bf16 with MU/KL, m or n < 1, k outside 1..32 or a null `out`. */
+int dnmf_small_fit_plan(int method, int bf16, int w_update, long m, long n, int k, int out[8]);
+/* Kernel launches of the persistent small fits since the library was loaded, counted on the host where a fit call has TAKEN the kernel
+ * (a grid that the occupancy query finds not resident takes the launch chain instead and counts nothing): out = {small_kl_fit_kernel,
+ * small_fro_fit_kernel (fp32 and bf16-stored A), small_kl_hfit_kernel, small_hals_fit_kernel}.  A batch that runs as several launches
+ * counts each. */
+int dnmf_small_fit_launches(unsigned long long out[4]);
 /* seconds a barrier of the persistent small fit may wait before it gives up (default 2; process-wide, read at the next fit call) */
 int dnmf_fit_set_timeout(double seconds);
 int dnmf_mu_fro_fit(const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int w_update,

@@ -7,6 +7,7 @@
 #include "dnmf_common.h"
 #include "dnmf_host.h"
 #include "dnmf_small.h"
+#include <atomic>
 
 // csrc/dnmf.hip: offsets of the step workspace {G, S, x, partials, total}
 __attribute__((visibility("hidden"))) void dnmf_ws_offsets_(long m, long n, int k, size_t out[5]);
@@ -94,6 +95,47 @@ FroBfPlan small_fro_bf16_plan(long m, long n, int k) {
     return s;
 }
 
+// The W-fixed MU/KL kernel (small_kl_hfit_kernel) keeps ALL of W in LDS: taken when that fits, else the barrier kernel runs with w_update = 0
+constexpr int HFIT_NW = 8;
+inline bool small_kl_wfixed_fits(int kp, long m) { return small_kl_hfit_lds(kp, HFIT_NW, m) <= 160 * 1024; }
+
+// Which persistent kernel a whole fit takes, from the shape alone: what fit_impl dispatches on and what dnmf_small_fit_plan reports.
+enum { ROUTE_NONE = 0, ROUTE_BARRIER = 1, ROUTE_WFIXED = 2, ROUTE_HALS = 3 };
+enum { FAM_KL = 0, FAM_FRO = 1, FAM_WFIXED = 2, FAM_HALS = 3 };             // the launch counters (dnmf_small_fit_launches)
+struct SmallRoute { int route, kp, nw, P, cw; bool alds, bf16_resident; long ns; size_t bytes; };
+SmallRoute small_route(int method, bool bf, int w_update, long m, long n, int k) {
+    SmallRoute r{};
+    if (m < 1 || n < 1) return r;
+    if (method == FIT_HALS_FRO) {                          // (W fixed: the hoisted H-only loop of fit_impl is the better path)
+        const HalsPlan hp = small_hals_plan(m, n, k);
+        if (!hp.ok || !w_update) return r;
+        r.route = ROUTE_HALS; r.kp = hp.kp; r.nw = hp.nw; r.P = hp.P; r.cw = hp.cw; r.ns = hp.ns; r.bytes = hp.bytes;
+        r.bf16_resident = bf && hp.lds_bf16_resident <= 160 * 1024;
+        r.alds = r.bf16_resident;
+        return r;
+    }
+    if (method == FIT_MU_FRO && bf) {
+        const FroBfPlan sp = small_fro_bf16_plan(m, n, k);
+        if (!sp.ok || !w_update) return r;
+        r.route = ROUTE_BARRIER; r.kp = sp.kp; r.nw = sp.nw; r.P = sp.P; r.alds = sp.alds; r.ns = sp.ns; r.bytes = sp.bytes;
+        return r;
+    }
+    if (bf || (method != FIT_MU_KL && method != FIT_MU_FRO)) return r;
+    if (method == FIT_MU_FRO && !w_update) return r;       // (Frobenius MU with W fixed: the hoisted H-only loop beats the barrier kernel)
+    const SmallPlan sp = small_kl_plan(m, n, k);
+    if (!sp.ok) return r;
+    r.kp = sp.kp; r.ns = sp.ns; r.bytes = sp.bytes;
+    if (method == FIT_MU_KL && !w_update && small_kl_wfixed_fits(sp.kp, m)) {
+        r.route = ROUTE_WFIXED; r.nw = HFIT_NW; r.P = (int)(sp.ns / 16);     // a workgroup per 16 columns, A streamed
+        return r;
+    }
+    r.route = ROUTE_BARRIER; r.nw = sp.nw; r.P = sp.P; r.alds = sp.alds;
+    return r;
+}
+
+// kernel launches of the persistent small fits that were TAKEN, per family (host side; dnmf_small_fit_launches)
+std::atomic<unsigned long long> g_small_launches[4];
+
 // per-problem workspace: [ step workspace | s: KP floats (column sums of W) | ss2: KP doubles | sq: 2 doubles | small-fit partials ]
 struct FitWs { size_t g_off, s_off, part_off, step_total, cs_off, ss2_off, sq_off, small_off, total; };
 
@@ -145,7 +187,7 @@ int hals_step(const void* A, long m, long n, long lda, float* W, long ldw, float
 unsigned long long g_small_patience = 200000000ull;
 
 // a launch (or as few as keep every workgroup resident) of a persistent small-fit kernel
-int resident_launch(void (*kern)(SmallKlArgs), int threads, size_t lds, int P, SmallKlArgs a, int batch, hipStream_t st, bool* taken, const char* what) {
+int resident_launch(void (*kern)(SmallKlArgs), int threads, size_t lds, int P, SmallKlArgs a, int batch, hipStream_t st, bool* taken, const char* what, int family) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
         return fail(DNMF_EHIP, "small fit: cannot raise the dynamic LDS limit");
     int nb = 0, dev = 0, cus = 0;
@@ -156,12 +198,15 @@ int resident_launch(void (*kern)(SmallKlArgs), int threads, size_t lds, int P, S
     if (cap < P) return DNMF_OK;
     const int per_launch = (int)std::min<long>(batch, cap / P);
     const int each = (int)cdiv(batch, cdiv(batch, per_launch));
+    unsigned long long launches = 0;
     for (int z0 = 0; z0 < batch; z0 += each) {
         a.z0 = z0;
         hipLaunchKernelGGL(kern, dim3((unsigned)P, 1, (unsigned)std::min(each, batch - z0)), dim3(threads), lds, st, a);
         const int rc = check_launch(what);
         if (rc) return rc;
+        ++launches;
     }
+    g_small_launches[family] += launches;
     *taken = true;
     return DNMF_OK;
 }
@@ -170,10 +215,10 @@ int resident_launch(void (*kern)(SmallKlArgs), int threads, size_t lds, int P, S
 template <int KP, int NW, bool ALDS, bool FRO>
 int small_kl_launch(const SmallPlan& sp, SmallKlArgs a, int batch, hipStream_t st, bool* taken) {
     return resident_launch(FRO ? small_fro_fit_kernel<KP, NW, ALDS, float> : small_kl_fit_kernel<KP, NW, ALDS>, 64 * NW, sp.lds, sp.P, a, batch, st, taken,
-                           FRO ? "small_fro_fit_kernel" : "small_kl_fit_kernel");
+                           FRO ? "small_fro_fit_kernel" : "small_kl_fit_kernel", FRO ? FAM_FRO : FAM_KL);
 }
 
-int small_fit(bool fro, const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int w_update, int itr,
+int small_fit(const SmallRoute& rt, bool fro, const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int w_update, int itr,
                  int batch, long a_stride, long w_stride, long h_stride, char* ws, const FitWs& f, void* stream, bool* taken) {
     *taken = false;
     const SmallPlan sp = small_kl_plan(m, n, k);
@@ -187,19 +232,20 @@ int small_fit(bool fro, const float* A, long m, long n, long lda, float* W, long
     a.hg = a.part + sp.part_floats; a.hg_stride = a.part_stride;                       // [kp][ns] granules {H element, step}: zeroed below
     a.patience = g_small_patience;                                     // ticks of the 100 MHz wall clock (2 s unless dnmf_fit_set_timeout)
     if (batch == 1) { a.a_stride = a.w_stride = a.h_stride = 0; }
-    if (!fro && !w_update) {
-        // W fixed: the columns of H are independent -- a workgroup per 16 columns, no barrier, nothing to keep resident (small_kl_hfit_kernel)
-        constexpr int NW = 8;
-        const size_t lds = small_kl_hfit_lds(sp.kp, NW, m);
-        if (lds <= 160 * 1024) {
-            const dim3 grid((unsigned)(sp.ns / 16), 1, (unsigned)batch);
+    if (rt.route == ROUTE_WFIXED) {
+        // W fixed: the columns of H are independent -- a workgroup per 16 columns, no barrier, nothing to keep resident (small_kl_hfit_kernel);
+        // small_route has decided that all of W fits the LDS and how many workgroups that makes
+        constexpr int NW = HFIT_NW;
+        {
+            const size_t lds = small_kl_hfit_lds(rt.kp, NW, m);
+            const dim3 grid((unsigned)rt.P, 1, (unsigned)batch);
             a.z0 = 0;
-            const auto kern = sp.kp == 16 ? small_kl_hfit_kernel<16, NW> : small_kl_hfit_kernel<32, NW>;
+            const auto kern = rt.kp == 16 ? small_kl_hfit_kernel<16, NW> : small_kl_hfit_kernel<32, NW>;
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
                 return fail(DNMF_EHIP, "small fit: cannot raise the dynamic LDS limit");
             hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, st, a);
             const int rc = check_launch("small_kl_hfit_kernel");
-            if (!rc) *taken = true;
+            if (!rc) { ++g_small_launches[FAM_WFIXED]; *taken = true; }
             return rc;
         }
     }
@@ -218,10 +264,10 @@ int small_fit(bool fro, const float* A, long m, long n, long lda, float* W, long
 // the better path)
 template <int KP, int NW, typename TA, bool ALDS>
 int small_hals_launch(const HalsPlan& hp, SmallKlArgs a, int batch, hipStream_t st, bool* taken) {
-    return resident_launch(small_hals_fit_kernel<KP, NW, TA, ALDS>, 64 * NW, ALDS ? hp.lds_bf16_resident : hp.lds, hp.P, a, batch, st, taken, "small_hals_fit_kernel");
+    return resident_launch(small_hals_fit_kernel<KP, NW, TA, ALDS>, 64 * NW, ALDS ? hp.lds_bf16_resident : hp.lds, hp.P, a, batch, st, taken, "small_hals_fit_kernel", FAM_HALS);
 }
 
-int small_hals_fit(bool bf, const void* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int itr, int batch,
+int small_hals_fit(const SmallRoute& rt, bool bf, const void* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int itr, int batch,
                    long a_stride, long w_stride, long h_stride, char* ws, const FitWs& f, void* stream, bool* taken) {
     *taken = false;
     const HalsPlan hp = small_hals_plan(m, n, k);
@@ -243,7 +289,7 @@ int small_hals_fit(bool bf, const void* A, long m, long n, long lda, float* W, l
 #define HALS_CASE(KP_, NW_)                                                                                                       \
     if (hp.kp == KP_ && hp.nw == NW_)                                                                                             \
         return !bf ? small_hals_launch<KP_, NW_, float, false>(hp, a, batch, st, taken)                                           \
-                   : (hp.lds_bf16_resident <= 160 * 1024 ? small_hals_launch<KP_, NW_, bf16_t, true>(hp, a, batch, st, taken)         \
+                   : (rt.bf16_resident ? small_hals_launch<KP_, NW_, bf16_t, true>(hp, a, batch, st, taken)         /* (small_route's test) */ \
                                                          : small_hals_launch<KP_, NW_, bf16_t, false>(hp, a, batch, st, taken))
     HALS_CASE(16, 8); HALS_CASE(16, 4); HALS_CASE(32, 8); HALS_CASE(32, 4);
 #undef HALS_CASE
@@ -268,7 +314,7 @@ int small_fro_bf16_fit(const void* A, long m, long n, long lda, float* W, long l
     if (hipMemset2DAsync(a.hg, f.total, 0, 2 * (size_t)sp.kp * sp.ns * sizeof(float), (size_t)batch, st) != hipSuccess) return fail(DNMF_EHIP, "small fit: memset failed");
 #define FROBF_CASE(KP_, NW_, AL_)                                                                                                 \
     if (sp.kp == KP_ && sp.nw == NW_ && sp.alds == AL_)                                                                           \
-        return resident_launch(small_fro_fit_kernel<KP_, NW_, AL_, bf16_t>, 64 * NW_, sp.lds, sp.P, a, batch, st, taken, "small_fro_fit_kernel(bf16)")
+        return resident_launch(small_fro_fit_kernel<KP_, NW_, AL_, bf16_t>, 64 * NW_, sp.lds, sp.P, a, batch, st, taken, "small_fro_fit_kernel(bf16)", FAM_FRO)
     FROBF_CASE(16, 8, true); FROBF_CASE(16, 8, false); FROBF_CASE(16, 4, true); FROBF_CASE(16, 4, false);
     FROBF_CASE(32, 8, true); FROBF_CASE(32, 8, false); FROBF_CASE(32, 4, true); FROBF_CASE(32, 4, false);
 #undef FROBF_CASE
@@ -295,26 +341,26 @@ int fit_impl(int method, bool bf, const void* A, long m, long n, long lda, float
     bool small = false;
     const bool pers = dnmf_persistent_on_() != 0;
     if (!pers) column_sweep = 1;                                       // (the HALS steps below take the column launches)
-    if (pers && method == FIT_HALS_FRO && w_update && !column_sweep) {
+    const SmallRoute route = pers ? small_route(method, bf, w_update, m, n, k) : SmallRoute{};
+    if (route.route == ROUTE_HALS && !column_sweep) {
         const int B = ctx->B;
         ctx->B = 1;
-        rc = small_hals_fit(bf, A, m, n, lda, W, ldw, H, ldh, k, eps, itr, batch, a_stride, w_stride, h_stride, base, f, stream, &small);
+        rc = small_hals_fit(route, bf, A, m, n, lda, W, ldw, H, ldh, k, eps, itr, batch, a_stride, w_stride, h_stride, base, f, stream, &small);
         ctx->B = B;
         if (rc) return rc;
     }
-    if (pers && method == FIT_MU_FRO && bf && w_update) {
+    if (route.route == ROUTE_BARRIER && bf) {              // (MU/FRO on bf16-stored data)
         const int B = ctx->B;
         ctx->B = 1;
         rc = small_fro_bf16_fit(A, m, n, lda, W, ldw, H, ldh, k, eps, itr, batch, a_stride, w_stride, h_stride, base, f, stream, &small);
         ctx->B = B;
         if (rc) return rc;
     }
-    // (Frobenius MU with W fixed: the hoisted H-only loop below beats the barrier kernel)
-    if (pers && (method == FIT_MU_KL || (method == FIT_MU_FRO && w_update)) && !bf) {
+    if ((route.route == ROUTE_BARRIER || route.route == ROUTE_WFIXED) && !bf) {
         // small fp32 problems: the whole loop as one persistent kernel per batch (csrc/dnmf_small.h); launched unbatched -- it indexes the problems itself
         const int B = ctx->B;
         ctx->B = 1;
-        rc = small_fit(method == FIT_MU_FRO, (const float*)A, m, n, lda, W, ldw, H, ldh, k, eps, w_update, itr, batch, a_stride, w_stride, h_stride, base, f, stream, &small);
+        rc = small_fit(route, method == FIT_MU_FRO, (const float*)A, m, n, lda, W, ldw, H, ldh, k, eps, w_update, itr, batch, a_stride, w_stride, h_stride, base, f, stream, &small);
         ctx->B = B;
         if (rc) return rc;
         // (the W-fixed KL kernel leaves W alone; the clamp of pyDNMF.py:155 after step 0 is this launch)
@@ -395,6 +441,21 @@ int dnmf_hals_fit_persistent(long m, long n, int k) {
 
 int dnmf_mu_fit_persistent(long m, long n, int k) {
     return (dnmf_persistent_on_() && m >= 1 && n >= 1 && small_kl_plan(m, n, k).ok) ? 1 : 0;
+}
+
+int dnmf_small_fit_plan(int method, int bf16, int w_update, long m, long n, int k, int out[8]) {
+    if (method != FIT_MU_FRO && method != FIT_MU_KL && method != FIT_HALS_FRO) return fail(DNMF_EINVAL, "small_fit_plan: method %d (0 mu-fro, 1 mu-kl, 2 hals-fro)", method);
+    if (bf16 && method == FIT_MU_KL) return fail(DNMF_EINVAL, "small_fit_plan: bfloat16 storage of A is for the Frobenius updates");
+    if (!out || m < 1 || n < 1 || k < 1 || k > 32) return fail(DNMF_EINVAL, "small_fit_plan: null pointer or bad shape (m=%ld n=%ld k=%d; 1 <= k <= 32)", m, n, k);
+    const SmallRoute r = small_route(method, bf16 != 0, w_update, m, n, k);
+    out[0] = r.route; out[1] = r.kp; out[2] = r.nw; out[3] = r.alds ? 1 : 0; out[4] = r.P; out[5] = (int)r.ns; out[6] = r.cw; out[7] = r.bf16_resident ? 1 : 0;
+    return DNMF_OK;
+}
+
+int dnmf_small_fit_launches(unsigned long long out[4]) {
+    if (!out) return fail(DNMF_EINVAL, "small_fit_launches: null pointer");
+    for (int i = 0; i < 4; ++i) out[i] = g_small_launches[i].load();
+    return DNMF_OK;
 }
 
 size_t dnmf_ws_bytes_fit(long m, long n, int k, int batch) {

@@ -114,6 +114,184 @@ def kl(m, n, k, dtype=np.float32, seed=0, qmax=3):
     return A.astype(dtype), W.astype(dtype), H.astype(dtype), U
 
 
+# ---------------------------------------------------------------------------------------------------------- fixed points of a whole MU step
+# Operands at which ONE whole MU step -- both phases, the clamp, any number of times -- returns its input bit for bit in fp32 (the small
+# whole-fit kernels of csrc/dnmf_small.h over several steps: tests/test_gpu_small_exact.py; proofs: tests/test_exact_cpu.py).
+#   W[r][j] = 2^a_r g_j,  H[j][c] = h_j 2^q_c,  g_j, h_j and g_j h_j powers of two with sum_j g_j h_j = 2^s,  A = W H = 2^(a_r + q_c + s).
+# Every sum a step forms has terms that are multiples of one power of two with fewer than 2^24 of them in total (exact in any order), and
+# every divisor is a power of two >= 2 (eps is absorbed; the kernels divide by multiplying with v_rcp_f32, which is exact there:
+# test_rcp_is_exact_at_powers_of_two).  All entries are positive powers of two: the clamp is a no-op, bf16 storage is exact.
+def _rank_split(k, rs):
+    """g, h (k powers of two each, g >= 2, h >= 1) with sum g h a power of two: 2^S ones (2^S >= 4 k) merged pairwise, two equal values
+    into their sum, until k values are left -- the sum stays 2^S --, each value split at random between g and h; g doubled"""
+    S = max(0, int(np.ceil(np.log2(k)))) + 2
+    vals = [0] * (1 << S)                                       # exponents
+    while len(vals) > k:
+        dup = [v for v in set(vals) if vals.count(v) >= 2]      # (distinct powers of two never add up to a power of two: there is one)
+        v = dup[rs.randint(len(dup))]
+        vals.remove(v); vals.remove(v); vals.append(v + 1)
+    e = np.array(vals)[rs.permutation(k)]
+    u = np.array([rs.randint(0, x + 1) for x in e])
+    g, h = 2.0 ** (u + 1), 2.0 ** (e - u)
+    assert np.sum(g * h) == 2.0 ** (S + 1)
+    return g, h, S + 1
+
+
+def _pow2_total(L, base, rs):
+    """L exponents in {0, 1}, at random places, with sum base^e a power of two (base 2: a total in [L, 2 L]; base 4: one in [L, 4 L],
+    which exists when 3 does not divide L, since 4^e = 1 mod 3 and the powers of two alternate between 1 and 2 mod 3)"""
+    assert base in (2, 4)
+    if base == 4:
+        assert L % 3 != 0, "no set of %d powers of four sums to a power of two: a Frobenius fixed point needs m and n not divisible by 3" % L
+    for p in range(0, 64):
+        t, rem = divmod(2 ** p - L, base - 1)                   # t entries of `base`, L - t of 1
+        if 2 ** p >= L and rem == 0 and t <= L:
+            break
+    e = np.zeros(L, dtype=np.int64)
+    e[rs.permutation(L)[:t]] = 1
+    tot = float(np.sum(float(base) ** e))
+    assert tot == 2.0 ** p
+    return e
+
+
+def _fixed(m, n, k, base, qlo, seed):
+    rs = np.random.RandomState(seed + 1013 * m + 19 * n + 7 * k + base)
+    g, h, s = _rank_split(k, rs)
+    a, q = _pow2_total(m, base, rs), _pow2_total(n, base, rs) + qlo
+    W = 2.0 ** a[:, None] * g[None, :]
+    H = h[:, None] * 2.0 ** q[None, :]
+    A = W @ H
+    assert np.array_equal(A, 2.0 ** (a[:, None] + q[None, :] + s))
+    # the terms of a sum over j are multiples of the smallest one, min g h >= 2 times the common factor, and add up to 2^s of it
+    _bound(2.0 ** s / np.min(g * h), 1.0, np.float32, "a sum over the rank")
+    return A, W, H, g, h, a, q
+
+
+def kl_fixed(m, n, k, dtype=np.float32, seed=0):
+    """A fixed point of the MU/KL step: q_c in {1, 2} with sum_c 2^q_c a power of two, a_r in {0, 1} with sum_r 2^a_r one.  W H is a
+    power of two >= 2, so U = A / (W H + eps) = 1; U H^T = rowsum(H) = h_j sum 2^q and W^T U = colsum(W) = g_j sum 2^a are what the
+    updates divide by, powers of two >= 2: both factors stay; the closing normalisation divides by colsum(W), a power of two."""
+    A, W, H, g, h, a, q = _fixed(m, n, k, 2, 1, seed)
+    _bound(np.sum(2.0 ** q), 2.0, np.float32, "rowsum(H) = U H^T in units of 2 h_j")
+    _bound(np.sum(2.0 ** a), 1.0, np.float32, "colsum(W) = W^T U in units of g_j")
+    for d, what in ((A, "W H"), (H.sum(1), "rowsum(H)"), (W.sum(0), "colsum(W)")):
+        assert np.all(d >= 2) and np.array_equal(np.log2(d), np.round(np.log2(d))), "%s is not a power of two >= 2" % what
+    return A.astype(dtype), W.astype(dtype), H.astype(dtype)
+
+
+def kl_moved(m, n, k, dtype=np.float32, seed=0):
+    """`kl_fixed` with A doubled, for fits with W FIXED: U = 2, so step 0 gives exactly 2 H, where W (2 H) = A: a fixed point from
+    step 1 on.  The H of step 1 is the first that is not the caller's array -- a workgroup that reads the caller's H instead of the
+    published one doubles it again.  Returns A, W, H; the fit must end at H_out = 2 H."""
+    A, W, H = kl_fixed(m, n, k, dtype, seed)
+    return (2 * A).astype(dtype), W, H
+
+
+def fro_fixed(m, n, k, dtype=np.float32, seed=0):
+    """A fixed point of the MU/Frobenius step: q_c, a_r in {0, 1} with sum_c 4^q_c and sum_r 4^a_r powers of two (m, n not divisible
+    by 3).  A H^T = W (H H^T) and W^T A = (W^T W) H term for term -- 2^(a_r + s) h_j sum 4^q and g_j 2^(q_c + s) sum 4^a --, powers of
+    two >= 2 with every partial sum exact.  colsum(W) = g_j sum 2^a_r is an integer >= 2, in general not a power of two: the
+    normalisation rounds once per element (the step itself does not)."""
+    A, W, H, g, h, a, q = _fixed(m, n, k, 4, 0, seed)
+    G, GW = H @ H.T, W.T @ W
+    _bound(np.sum(4.0 ** q), 1.0, np.float32, "A H^T in units of 2^(a_r + s) h_j, H H^T in units of h_j h_l")
+    _bound(np.sum(4.0 ** a), 1.0, np.float32, "W^T A in units of g_j 2^(q_c + s), W^T W in units of g_j g_l")
+    _bound(W.sum(0) / g, 0.25, np.float32, "colsum(W) in units of g_j")                             # below 2^22: s + eps rounds to s
+    for d, what in ((W @ G, "W (H H^T)"), (GW @ H, "(W^T W) H")):
+        assert np.all(d >= 2) and np.array_equal(np.log2(d), np.round(np.log2(d))), "%s is not a power of two >= 2" % what
+    assert np.array_equal(A @ H.T, W @ G) and np.array_equal(W.T @ A, GW @ H) and np.all(W.sum(0) >= 2)
+    return A.astype(dtype), W.astype(dtype), H.astype(dtype)
+
+
+# The reach table of the small whole-fit kernels (csrc/dnmf_small.h; the dispatch of csrc/dnmf_fit.hip): one shape, about the smallest there
+# is, for every instantiation the plans can choose, with the plan dnmf_small_fit_plan must report for it -- {route, KP, NW, ALDS, P, ns,
+# cw, bf16_resident}; route 1: the barrier kernel, 2: the W-fixed MU/KL kernel, 3: the HALS kernel.  tests/test_capi_small.py asserts every
+# entry without a GPU; tests/test_gpu_small_exact.py runs every one.  The Frobenius shapes have m and n not divisible by 3 (`fro_fixed`).
+# Between them the barrier-kernel entries of every family hold a single slab (P = 1, NW = 4), the maximum P = 64, a ragged last slab,
+# n % 16 != 0 and k = 1, 16, 17, 32; n = 353, 497, ... give the W phase whole groups of four column tiles and a tail, n = 37 a tail alone.
+SMALL_FAMILIES = {"kl": (1, 0, 1), "fro": (0, 0, 1), "fro_bf16": (0, 1, 1), "kl_wfixed": (1, 0, 0), "hals": (2, 0, 1), "hals_bf16": (2, 1, 1)}   # method, bf16, w_update
+SMALL_REACH = [
+    ("kl", 130, 37, 5, (1, 16, 8, 1, 2, 48, 0, 0)),
+    ("kl", 100, 20, 16, (1, 16, 6, 1, 2, 32, 0, 0)),
+    ("kl", 130, 353, 1, (1, 16, 8, 0, 2, 368, 0, 0)),
+    ("kl", 17, 5, 1, (1, 16, 4, 1, 1, 16, 0, 0)),
+    ("kl", 50, 497, 7, (1, 16, 4, 0, 1, 512, 0, 0)),
+    ("kl", 130, 37, 17, (1, 32, 8, 1, 2, 48, 0, 0)),
+    ("kl", 100, 20, 32, (1, 32, 6, 1, 2, 32, 0, 0)),
+    ("kl", 130, 305, 20, (1, 32, 8, 0, 2, 320, 0, 0)),
+    ("kl", 40, 50, 31, (1, 32, 4, 1, 1, 64, 0, 0)),
+    ("kl", 50, 401, 17, (1, 32, 4, 0, 1, 416, 0, 0)),
+    ("kl", 8191, 20, 3, (1, 16, 8, 1, 64, 32, 0, 0)),
+    ("fro", 130, 37, 5, (1, 16, 8, 1, 2, 48, 0, 0)),
+    ("fro", 100, 20, 16, (1, 16, 6, 1, 2, 32, 0, 0)),
+    ("fro", 130, 353, 1, (1, 16, 8, 0, 2, 368, 0, 0)),
+    ("fro", 17, 5, 1, (1, 16, 4, 1, 1, 16, 0, 0)),
+    ("fro", 50, 497, 7, (1, 16, 4, 0, 1, 512, 0, 0)),
+    ("fro", 130, 37, 17, (1, 32, 8, 1, 2, 48, 0, 0)),
+    ("fro", 100, 20, 32, (1, 32, 6, 1, 2, 32, 0, 0)),
+    ("fro", 130, 305, 20, (1, 32, 8, 0, 2, 320, 0, 0)),
+    ("fro", 40, 50, 31, (1, 32, 4, 1, 1, 64, 0, 0)),
+    ("fro", 50, 401, 17, (1, 32, 4, 0, 1, 416, 0, 0)),
+    ("fro", 8191, 20, 3, (1, 16, 8, 1, 64, 32, 0, 0)),
+    ("fro_bf16", 130, 37, 5, (1, 16, 8, 1, 2, 48, 0, 0)),
+    ("fro_bf16", 130, 497, 5, (1, 16, 8, 0, 2, 512, 0, 0)),
+    ("fro_bf16", 17, 5, 1, (1, 16, 4, 1, 1, 16, 0, 0)),
+    ("fro_bf16", 50, 833, 7, (1, 16, 4, 0, 1, 848, 0, 0)),
+    ("fro_bf16", 130, 37, 17, (1, 32, 8, 1, 2, 48, 0, 0)),
+    ("fro_bf16", 130, 370, 20, (1, 32, 8, 0, 2, 384, 0, 0)),
+    ("fro_bf16", 40, 50, 31, (1, 32, 4, 1, 1, 64, 0, 0)),
+    ("fro_bf16", 50, 593, 17, (1, 32, 4, 0, 1, 608, 0, 0)),
+    ("fro_bf16", 8191, 20, 3, (1, 16, 8, 1, 64, 32, 0, 0)),
+    ("fro_bf16", 100, 20, 16, (1, 16, 4, 1, 2, 32, 0, 0)),
+    ("fro_bf16", 100, 20, 32, (1, 32, 4, 1, 2, 32, 0, 0)),
+    ("kl_wfixed", 530, 21, 5, (2, 16, 8, 0, 2, 32, 0, 0)),
+    ("kl_wfixed", 530, 21, 17, (2, 32, 8, 0, 2, 32, 0, 0)),
+    ("kl_wfixed", 2270, 20, 5, (1, 16, 8, 1, 18, 32, 0, 0)),
+    ("kl_wfixed", 1102, 20, 17, (1, 32, 8, 1, 9, 32, 0, 0)),
+    ("hals", 50, 37, 5, (3, 16, 4, 0, 1, 48, 48, 0)),
+    ("hals", 130, 37, 5, (3, 16, 8, 0, 2, 48, 24, 0)),
+    ("hals", 50, 37, 17, (3, 32, 4, 0, 1, 48, 48, 0)),
+    ("hals", 130, 37, 17, (3, 32, 8, 0, 2, 48, 24, 0)),
+    ("hals", 8191, 20, 3, (3, 16, 8, 0, 64, 32, 1, 0)),
+    ("hals", 17, 5, 1, (3, 16, 4, 0, 1, 16, 16, 0)),
+    ("hals", 100, 20, 16, (3, 16, 4, 0, 2, 32, 16, 0)),
+    ("hals", 40, 50, 32, (3, 32, 4, 0, 1, 64, 64, 0)),
+    ("hals_bf16", 50, 37, 5, (3, 16, 4, 1, 1, 48, 48, 1)),
+    ("hals_bf16", 130, 37, 5, (3, 16, 8, 1, 2, 48, 24, 1)),
+    ("hals_bf16", 50, 37, 17, (3, 32, 4, 1, 1, 48, 48, 1)),
+    ("hals_bf16", 130, 37, 17, (3, 32, 8, 1, 2, 48, 24, 1)),
+    ("hals_bf16", 50, 610, 5, (3, 16, 4, 0, 1, 624, 624, 0)),
+    ("hals_bf16", 130, 417, 5, (3, 16, 8, 0, 2, 432, 216, 0)),
+    ("hals_bf16", 50, 370, 17, (3, 32, 4, 0, 1, 384, 384, 0)),
+    ("hals_bf16", 130, 290, 17, (3, 32, 8, 0, 2, 304, 152, 0)),
+    ("hals_bf16", 8191, 20, 3, (3, 16, 8, 1, 64, 32, 1, 1)),
+    ("hals_bf16", 17, 5, 1, (3, 16, 4, 1, 1, 16, 16, 1)),
+    ("hals_bf16", 100, 20, 16, (3, 16, 4, 1, 2, 32, 16, 1)),
+    ("hals_bf16", 40, 50, 32, (3, 32, 4, 1, 1, 64, 64, 1)),
+]
+
+
+# The data of the HALS rows of the table (tests/test_gpu_small_exact.py compares with the float64 loop of the checker): the random data of
+# tests/test_gpu_fit.py -- A uniform in [0.01, 1.01) with every seventh column zero at odd seeds, factors uniform in [0, 1) -- wherever
+# that loop is well-conditioned.  At the four shapes below it is not: with k close to n or above m / 3 on full-rank data components die
+# at the clamp or survive depending on the last bits, and the checker's OWN loop run in numpy float32 ends 0.6 to 1.2 of the largest
+# entry away from its float64 run after 11 steps (tests/test_exact_cpu.py asserts that, and that it stays within 5e-4 on the data used
+# here at every shape and seed); there the data has rank k plus 1 % noise.
+HALS_RANK_K = {(50, 37, 17), (40, 50, 32), (50, 370, 17), (100, 20, 16)}
+HALS_SEEDS = (10, 11, 12)
+
+
+def hals_problem(m, n, k, seed, rank_k=None):
+    rs = np.random.RandomState(seed + m + 7 * n + k)
+    if (m, n, k) in HALS_RANK_K if rank_k is None else rank_k:
+        A = (rs.rand(m, k) + 0.1) @ (rs.rand(k, n) + 0.1) + 0.01 * rs.rand(m, n)
+    else:
+        A = rs.rand(m, n) + 0.01
+        if seed % 2:
+            A[:, ::7] = 0.0
+    return A.astype(np.float32), rs.rand(m, k).astype(np.float32), rs.rand(k, n).astype(np.float32)
+
+
 # ---------------------------------------------------------------------------------------------------------- sparse (CSR) blocks
 # Row lengths on both sides of every structural boundary of csrc/dnmf_csr.h: the lane-group counts NG = 256 / KPAD = 16, 8, 4, 2, 1,
 # the 64 (col, val) pairs a wave reads per step, and the segment length 1024 of a long row (one, two and three segments, a ragged
@@ -259,17 +437,18 @@ SENTINEL = -12345.6875
 class Poisoned:
     """A rows x cols view -- or a stack [B][rows][cols] of them, problem b at b rows ld -- inside a buffer: `lead` elements before it,
     pitch ld >= cols, `guard` elements after it; everything outside the view holds `fill` (NaN for operands, SENTINEL for outputs).
-    aligned: lead and ld multiples of 4 (the vector paths); otherwise an odd start and pitch (the generic paths).  packed: ld = cols
-    (a contiguous view, for the entry points that require one)."""
+    aligned: lead and ld multiples of 4 (the vector paths; `quantum` elements instead of 4: 8 puts the members of a bf16 stack 16 bytes
+    apart whatever the row count); otherwise an odd start and pitch (the generic paths).  packed: ld = cols (a contiguous view, for the
+    entry points that require one)."""
 
-    def __init__(self, torch, x, dtype=None, fill=float("nan"), aligned=True, guard=67, device="cuda", packed=False):
+    def __init__(self, torch, x, dtype=None, fill=float("nan"), aligned=True, guard=67, device="cuda", packed=False, quantum=4):
         x = np.asarray(x)
         x3 = x if x.ndim == 3 else x[None]
         B, rows, cols = x3.shape
         self.torch = torch
         self.dtype = dtype or {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}[x.dtype]
         self.lead = 8 if aligned else 3
-        self.ld = cols if packed else (-(-cols // 4) * 4 + 4) if aligned else cols + 3
+        self.ld = cols if packed else (-(-cols // quantum) * quantum + quantum) if aligned else cols + 3
         self.rows, self.cols, self.fill = rows, cols, fill
         bs = rows * self.ld
         self.buf = torch.full((self.lead + B * bs + guard,), fill, dtype=self.dtype, device=device)

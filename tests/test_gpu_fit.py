@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 CASES = [  # m, n, k, method, norm, precision, itr
     (1000, 250, 9, "mu", "kl", "float32", 31),        # persistent small-fit kernel: ragged slab, ragged columns, 128-row slabs
-    (4100, 400, 20, "mu", "kl", "float32", 12),       # ... 64-row slabs, k padded to 32, more slabs than fit one launch with 5 problems
+    (4100, 400, 20, "mu", "kl", "float32", 12),       # ... 33 streamed 128-row slabs, k padded to 32 (the plans: tests/test_capi_small.py)
     (70, 33, 3, "mu", "kl", "float32", 23),           # ... one or two slabs
     (1000, 250, 9, "mu", "fro", "float32", 31),       # the Frobenius twin of the persistent kernel
     (4100, 400, 20, "mu", "fro", "float32", 12),
