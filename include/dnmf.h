@@ -129,6 +129,15 @@ int dnmf_hals_update_w(float* W, long m, int k, long ldw, const float* AH, long 
  * resources the other's remaining workgroups need.  One process per GPU and one stream, the product's model, is safe. */
 int dnmf_hals_sweep_w(float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, float eps,
                       void* ws, size_t ws_bytes, void* stream);
+/* What dnmf_hals_sweep_w would run for an m x k factor with these pitches on the current device (nothing is launched; the decision is
+ * the one the sweep itself takes).  w_aligned16 / ah_aligned16 != 0: W / AH start on a 16-byte boundary.  out = {route, KP, grid,
+ * transform, vec, cap}: route 1 = the persistent sweep, 0 = k column launches (always for a wide rank, k > 128); KP = dnmf_kp(k); grid =
+ * workgroups of the sweep kernel (512 rows each) or of one column launch (256 rows each, at most 2048: beyond that they stride);
+ * transform = the variant of the sweep's first pass (0: 16-byte row access and whole tiles, 1: 16-byte row access with guards, 2: scalar
+ * row access; -1 on route 0); vec = 1: the sweep kernel loads and stores its rows 16 bytes at a time; cap = workgroups of that
+ * instantiation the device holds resident (0 for a wide rank).  It assumes a workspace of dnmf_ws_bytes(m, k, k), a single problem
+ * (no batch) and reads the process-wide dnmf_set_persistent switch.  Refused: a null `out`, k outside 1..256, m < 1, a pitch below k. */
+int dnmf_hals_sweep_plan(long m, int k, long ldw, long ldah, int w_aligned16, int ah_aligned16, int out[6]);
 /* Did a persistent W sweep on the current device give up waiting for its other workgroups since the last call?  (Its
  * workgroups were not co-resident -- see above; the sweep then ends after about a second with NaN column norms instead of
  * hanging the GPU, and sets a sticky per-device word.)  *timed_out = 0 / 1; the word is cleared.  This call SYNCHRONISES

@@ -11,6 +11,9 @@
 __attribute__((visibility("hidden"))) int dnmf_wide_hals_update_h_(float* H, int k, long n, long ldh, const float* AtW, long ldatw, const float* G,
                                                                    long ldg, float eps, void* stream);
 
+// workgroups of the column kernels (hals_w_col_kernel, hals_w_scale_kernel): 256 rows each, grid-stride beyond 2048
+static inline unsigned hals_col_grid(long m) { return (unsigned)std::min<long>(cdiv(m, 256), 2048); }
+
 extern "C" {
 
 static int hals_w_col_launch(float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, int kk,
@@ -19,7 +22,7 @@ static int hals_w_col_launch(float* W, long m, int k, long ldw, const float* AH,
     REQUIRE(kpg > 0 && W && AH && G && ss2_out && m >= 1 && ldw >= k && ldah >= k && kk >= 0 && kk < k, "hals_w_col: bad arguments");
     hipStream_t st = S(stream);
     if (zero && batch_memset(ss2_out, 0, sizeof(double), st) != hipSuccess) return fail(DNMF_EHIP, "hals_w_col: memset failed");
-    const unsigned grid = (unsigned)std::min<long>(cdiv(m, 256), 2048);
+    const unsigned grid = hals_col_grid(m);
     DNMF_LAUNCH(hals_w_col_kernel, dim3(grid), dim3(256), 0, st, W, m, k, ldw, AH, ldah, G, kpg, kk, prev_ss2,
                        eps, ss2_out);
     return check_launch("hals_w_col");
@@ -32,7 +35,7 @@ int dnmf_hals_w_col(float* W, long m, int k, long ldw, const float* AH, long lda
 
 int dnmf_hals_w_scale(float* W, long m, long ldw, int col, const double* ss2, void* stream) {
     REQUIRE(W && ss2 && m >= 1 && col >= 0 && ldw > col, "hals_w_scale: bad arguments");
-    const unsigned grid = (unsigned)std::min<long>(cdiv(m, 256), 2048);
+    const unsigned grid = hals_col_grid(m);
     DNMF_LAUNCH(hals_w_scale_kernel, dim3(grid), dim3(256), 0, S(stream), W, m, ldw, col, ss2);
     return check_launch("hals_w_scale");
 }
@@ -61,20 +64,22 @@ long resident_workgroups(K kernel, int threads, size_t lds) {
     return (long)cus * per_cu;
 }
 
-// pe != nullptr: the cross-rank sweep (HalsPeers, dnmf_common.h) -- the slot slabs are the peers' exported ones (pe->slab), this
-// rank's slab of the sweep's parity is reset AFTER the kernel (see dnmf_comm.hip).  check_only: no launch, 0 = the sweep applies
+// What launch_hals_sweep decides for one shape (dnmf_hals_sweep_plan reports it): persistent = the sweep kernel applies on this device;
+// tvar = the update_w_seq_kernel<.., UW_HALS_T> variant of pass 1 (0: 16-byte rows and whole tiles, 1: 16-byte rows with guards, 2: scalar
+// rows); vec = the sweep kernel's 16-byte row load / store; cap = resident workgroups of that instantiation; per = problems of a batch per launch
+struct HalsPlan { bool persistent; int tvar; bool vec; long grid, cap; int per; };
+
+// w16 / ah16: W / AH start on a 16-byte boundary.  peers: the cross-rank sweep.  B: problems of the batch the launch is part of (1: a
+// single problem).  Non-zero: the device could not be queried.
 template <int KT>
-int launch_hals_sweep(float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, float eps,
-                      unsigned long long* slab, double* ss2, float* T, hipStream_t st, const HalsPeers* pe = nullptr,
-                      bool check_only = false) {
+int hals_sweep_decide(long m, int k, long ldw, long ldah, bool w16, bool ah16, bool peers, int B, HalsPlan* p) {
     constexpr int KP = 32 * KT;
-    const long ldt = KP;
-    const bool vecw = aligned16(W) && aligned16(AH) && ldw % 4 == 0 && ldah % 4 == 0 && k % 4 == 0;   // pass 1 reads W, AH
+    const bool vecw = w16 && ah16 && ldw % 4 == 0 && ldah % 4 == 0 && k % 4 == 0;   // pass 1 reads W, AH
     // pass 2: T rows are aligned.  Only KP = 64 has a 16-byte variant of the row load / store (once per sweep): hipcc
     // register-allocates the KP = 32 one pathologically (the whole row in scratch, 20000 spills), and every variant of the
     // fully expanded KP = 128 sweep costs a minute of build time.
     constexpr bool HASVEC = KT == 2;
-    const bool vec = HASVEC && aligned16(W) && ldw % 4 == 0 && k % 4 == 0;
+    const bool vec = HASVEC && w16 && ldw % 4 == 0 && k % 4 == 0;
     const long grid = cdiv(m, HALS_WG);
     constexpr size_t lds = (size_t)KP * KP * sizeof(float);          // G staged per workgroup
     // co-residency capacity per DEVICE (a process may drive several GPUs, or a CU-masked one), filled once per device under a
@@ -96,12 +101,37 @@ int launch_hals_sweep(float* W, long m, int k, long ldw, const float* AH, long l
     // a batch whose workgroups do not all fit the device runs the sweep kernel on as many problems at a time as do (round 5: it took the
     // column launches instead -- 20 problems of 65536 rows, BASELINE config 5: 41 us x k per step -- and a batched fit then differed
     // from single fits, which do fit)
+    const long cap = vec ? cap_v[dev] : cap_s[dev];
+    p->vec = vec;
+    p->tvar = vecw ? (k == KP && m % 32 == 0 ? 0 : 1) : 2;
+    p->grid = grid;
+    p->cap = cap;
+    p->per = 0;
+    p->persistent = false;
+    if (grid > HALS_MAX_WG || grid > cap || (peers && B > 1) || !dnmf_persistent_on_()) return 0;   // not applicable (or switched off): the caller takes the column path
+    if (ldw >= (1L << 23) || ldah >= (1L << 23)) return 0;                        // beyond the 32-bit tile offsets of pass 1: column path
+    p->per = (int)std::min<long>(B, cap / grid);
+    p->persistent = true;
+    return 0;
+}
+
+// pe != nullptr: the cross-rank sweep (HalsPeers, dnmf_common.h) -- the slot slabs are the peers' exported ones (pe->slab), this
+// rank's slab of the sweep's parity is reset AFTER the kernel (see dnmf_comm.hip).  check_only: no launch, 0 = the sweep applies
+template <int KT>
+int launch_hals_sweep(float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, float eps,
+                      unsigned long long* slab, double* ss2, float* T, hipStream_t st, const HalsPeers* pe = nullptr,
+                      bool check_only = false) {
+    constexpr int KP = 32 * KT;
+    const long ldt = KP;
+    constexpr bool HASVEC = KT == 2;
+    constexpr size_t lds = (size_t)KP * KP * sizeof(float);          // G staged per workgroup
+    HalsPlan plan;
     BatchCtx* bc = dnmf_batch_();
     const int B = bc->B;
-    const long cap = vec ? cap_v[dev] : cap_s[dev];
-    if (grid > HALS_MAX_WG || grid > cap || (pe && B > 1) || !dnmf_persistent_on_()) return 1;   // not applicable (or switched off): the caller takes the column path
-    const int per = (int)std::min<long>(B, cap / grid);
-    if (ldw >= (1L << 23) || ldah >= (1L << 23)) return 1;                        // beyond the 32-bit tile offsets of pass 1: column path
+    if (hals_sweep_decide<KT>(m, k, ldw, ldah, aligned16(W), aligned16(AH), pe != nullptr, B, &plan) || !plan.persistent) return 1;
+    const bool vec = plan.vec;
+    const long grid = plan.grid;
+    const int per = plan.per;
     if (check_only) return 0;
     if (!pe && batch_memset(slab, 0xff, (size_t)k * HALS_MAX_WG * sizeof(unsigned long long), st) != hipSuccess)
         return fail(DNMF_EHIP, "hals_sweep_w: memset failed");
@@ -118,9 +148,9 @@ int launch_hals_sweep(float* W, long m, int k, long ldw, const float* AH, long l
         }
         const unsigned g1 = upd_grid(cdiv(m, 32), KT);
         constexpr unsigned T1 = 64 * upd_waves(KT);
-        if (vecw && k == KP && m % 32 == 0)
+        if (plan.tvar == 0)
             DNMF_LAUNCH((update_w_seq_kernel<KT, 4, OCC, false, UW_HALS_T>), dim3(g1), dim3(T1), lds1, st, W, m, k, ldw, AH, ldah, G, eps, T, ldt);
-        else if (vecw)
+        else if (plan.tvar == 1)
             DNMF_LAUNCH((update_w_seq_kernel<KT, 4, OCC, true, UW_HALS_T>), dim3(g1), dim3(T1), lds1, st, W, m, k, ldw, AH, ldah, G, eps, T, ldt);
         else
             DNMF_LAUNCH((update_w_seq_kernel<KT, 1, OCC, true, UW_HALS_T>), dim3(g1), dim3(T1), lds1, st, W, m, k, ldw, AH, ldah, G, eps, T, ldt);
@@ -167,6 +197,25 @@ int dnmf_hals_sweep_w(float* W, long m, int k, long ldw, const float* AH, long l
     }
     if (rc != 1) return rc;
     return dnmf_hals_update_w(W, m, k, ldw, AH, ldah, G, eps, ss2, stream);   // too many rows to keep resident: one launch per column
+}
+
+int dnmf_hals_sweep_plan(long m, int k, long ldw, long ldah, int w_aligned16, int ah_aligned16, int out[6]) {
+    const int kt = kt_of(k);                                        // (-1 for a wide rank: column launches)
+    const int kp = kp_of(k);
+    REQUIRE(out && kp > 0 && m >= 1 && ldw >= k && ldah >= k, "hals_sweep_plan: bad arguments");
+    HalsPlan p{false, -1, false, 0, 0, 0};
+    int rc = 0;
+    if (kt == 1) rc = hals_sweep_decide<1>(m, k, ldw, ldah, w_aligned16 != 0, ah_aligned16 != 0, false, 1, &p);
+    else if (kt == 2) rc = hals_sweep_decide<2>(m, k, ldw, ldah, w_aligned16 != 0, ah_aligned16 != 0, false, 1, &p);
+    else if (kt == 4) rc = hals_sweep_decide<4>(m, k, ldw, ldah, w_aligned16 != 0, ah_aligned16 != 0, false, 1, &p);
+    if (rc) return fail(DNMF_EHIP, "hals_sweep_plan: the device could not be queried");
+    out[0] = p.persistent ? 1 : 0;
+    out[1] = kp;
+    out[2] = p.persistent ? (int)p.grid : (int)hals_col_grid(m);
+    out[3] = p.persistent ? p.tvar : -1;
+    out[4] = p.persistent && p.vec ? 1 : 0;
+    out[5] = (int)p.cap;
+    return DNMF_OK;
 }
 
 }  // extern "C"

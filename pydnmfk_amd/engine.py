@@ -121,6 +121,9 @@ def stack_alloc(B, rows, cols, dtype, device):
     return torch.empty(B * stride, dtype=dtype, device=device).as_strided((B, rows, cols), (stride, cols, 1))
 
 
+_HALS_MAX_WG = 1024                      # slots per column of the persistent HALS W sweep (csrc/dnmf_common.h)
+
+
 def new_gram(k, device):
     return torch.zeros(kp(k), kp(k), dtype=torch.float32, device=device)
 
@@ -270,12 +273,24 @@ class HipOps:
 
     def hals_update_w(self, W, AH, G, eps):
         """The whole W sweep of a rank with local column norms: one persistent launch when the rows fit on the device at
-        once, else one launch per column (decided inside the library)."""
+        once, else one launch per column (decided inside the library).  Returns the k column sums of squares (device doubles)."""
         _req(W, "W"); _req(AH, "AH"); _req(G, "G")
         m, k = W.shape
         ws = workspace(m, k, k, W.device)
         check(lib.dnmf_hals_sweep_w(W.data_ptr(), m, k, _ld(W), AH.data_ptr(), _ld(AH), G.data_ptr(), float(eps),
                                     ws.data_ptr(), ws.numel(), _stream()))
+        # the k column sums of squares: the library keeps them behind the slot slab of its workspace (dnmf_hals_sweep_w, csrc/dnmf_hals.hip:
+        # KP x HALS_MAX_WG slots of 8 bytes)
+        off = kp(k) * _HALS_MAX_WG * 8
+        return ws[off:off + 8 * k].view(torch.float64).clone()
+
+    def hals_sweep_plan(self, W, AH):
+        """What `hals_update_w` runs for these views on this device (dnmf_hals_sweep_plan): (route, KP, grid, transform, vec, cap) --
+        route 1 = the persistent sweep, 0 = column launches; see include/dnmf.h."""
+        import ctypes
+        out = (ctypes.c_int * 6)()
+        check(lib.dnmf_hals_sweep_plan(W.shape[0], W.shape[1], _ld(W), _ld(AH), int(W.data_ptr() % 16 == 0), int(AH.data_ptr() % 16 == 0), out))
+        return tuple(out)
 
     def hals_check(self):
         """Raise if a persistent W sweep on this device gave up waiting for its other workgroups (they were not co-resident:
@@ -291,12 +306,14 @@ class HipOps:
                                     "dnmf_set_persistent(0), or hals_sweep = 'columns' / fit_loop = 'python' per fit.")
 
     def hals_update_w_columns(self, W, AH, G, eps):
-        """The same sweep as k column launches (what the persistent kernel falls back to; kept callable for A/B tests)."""
+        """The same sweep as k column launches (what the persistent kernel falls back to; kept callable for A/B tests).  Returns the k
+        column sums of squares (device doubles)."""
         _req(W, "W"); _req(AH, "AH"); _req(G, "G")
         m, k = W.shape
         ss2 = self.hals_ss2(k, W)
         check(lib.dnmf_hals_update_w(W.data_ptr(), m, k, _ld(W), AH.data_ptr(), _ld(AH), G.data_ptr(), float(eps),
                                      ss2.data_ptr(), _stream()))
+        return ss2
 
     def hals_update_h(self, H, AtW, G, eps):
         _req(H, "H"); _req(AtW, "AtW"); _req(G, "G")
@@ -1199,6 +1216,7 @@ class HipOpsF64:
         for kk in range(k):
             self.hals_w_col(W, AH, G, kk, ss2, eps)
         self.hals_w_scale(W, k - 1, ss2)
+        return ss2
 
     hals_update_w_columns = hals_update_w
 

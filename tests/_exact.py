@@ -292,6 +292,396 @@ def hals_problem(m, n, k, seed, rank_k=None):
     return A.astype(np.float32), rs.rand(m, k).astype(np.float32), rs.rand(k, n).astype(np.float32)
 
 
+# ---------------------------------------------------------------------------------------------------------- one exact HALS sweep
+# HALS has no exact fixed point, but ONE sweep from a chosen state is exact: the generators below work backwards from the answer
+# (tests/test_exact_cpu.py proves them in every order, tests/test_gpu_exact_hals.py holds the kernels of csrc/dnmf_hals.h to them).
+# Two values of the clamp go through the entry points' `eps` argument:
+#   HALS_EPS_A = 2^-3   a clamped entry is an ordinary dyadic number: every sum of the sweep is exact in fp32 in any order;
+#   HALS_EPS_B = 2^-23  the library's eps.  A clamped w = eps / 2^p reaches a later t[j] as a term below a quarter ulp of its integer value
+#                       (|t| >= 1), which the single rounding of each fmaf absorbs -- the generator keeps the sum of those terms along
+#                       every row below 2^-25 --, so the fp32 results are the integers of the construction again.
+HALS_EPS_A = 2.0 ** -3
+HALS_EPS_B = 2.0 ** -23
+HALS_ROWS = 512                                                   # rows per workgroup of the persistent sweep (HALS_WG, csrc/dnmf_common.h)
+
+
+def _sym_gram(k, rs):
+    """symmetric, off-diagonals in {1, 2} (no zero a mutation could hide behind), diagonal in 2..5"""
+    G = np.triu(rs.randint(1, 3, size=(k, k)), 1)
+    return (G + G.T + np.diag(rs.randint(2, 6, size=k))).astype(np.float64)
+
+
+def _squares_to(total, n, rs):
+    """n values in {1, 2, 3}, at random places, whose squares add up to `total`: n + 3 a + 8 b = total with a twos and b threes (the
+    threes are what frees n from any condition modulo 3).  None if there is no such split."""
+    X = total - n
+    if X < 0:
+        return None
+    b = np.arange(0, min(n, X // 8) + 1)
+    a3 = X - 8 * b
+    ok = (a3 % 3 == 0) & (a3 // 3 + b <= n)
+    if not ok.any():
+        return None
+    b = int(rs.choice(b[ok]))
+    a = (X - 8 * b) // 3
+    v = np.ones(n)
+    v[:a] = 2
+    v[a:a + b] = 3
+    return v[rs.permutation(n)]
+
+
+def hals_w_exact(W_old, AH, G, eps, dtype=np.float32):
+    """The W sweep in exact arithmetic, each value rounded ONCE to `dtype`: for every column kk, t = AH[:, kk] - sum_{l > kk} W_old[:, l]
+    G[l][kk] - sum_{l < kk} W_new[:, l] G[l][kk]; u = max(t, eps); ss2 = sum u^2; W_new[:, kk] = u / dtype(sqrt(ss2)).  The float64 sums
+    here are exact on the generators' operands (multiples of 2^-(23 + p) below 2^12: `hals_w_problem` asserts the range).  Returns the
+    pre-clamp values t, W_new and ss2 (float64)."""
+    W_old, AH, G = (np.asarray(x, dtype=np.float64) for x in (W_old, AH, G))
+    m, k = W_old.shape
+    T, Wn, ss2 = np.zeros((m, k)), np.zeros((m, k)), np.zeros(k)
+    for kk in range(k):
+        t = AH[:, kk] - W_old[:, kk + 1:] @ G[kk + 1:k, kk] - Wn[:, :kk] @ G[:kk, kk]
+        T[:, kk] = t.astype(dtype)
+        u = np.maximum(T[:, kk], eps)
+        ss2[kk] = np.sum(u * u)
+        ss = float(dtype(np.sqrt(ss2[kk])))
+        Wn[:, kk] = (u / ss).astype(dtype) if ss > 0 else u
+    return T, Wn, ss2
+
+
+def hals_w_problem(m, k, eps, seed=0, dtype=np.float32):
+    """One exact W sweep (csrc/dnmf_hals.h), built backwards from the answer.  Returns a dict: W_old, AH (m x k), G (k x k), the
+    expected pre-clamp values T_final (column kk at its own turn), W_new, ss2 (k float64), p (ss2 = 4^p up to the eps terms), ss2_tol
+    (0 for HALS_EPS_A) and `clamped` (m x k bool).
+
+    G: `_sym_gram`.  W_old in 0..3.  Column kk of the clamped pre-normalisation U: eps in its clamped rows, values of {1, 2, 3} elsewhere
+    with sum U^2 = 4^p_kk exactly (`_squares_to`; with eps = 2^-3 the 64 clamped rows add 64 eps^2 = 1 to it, with eps = 2^-23 their
+    2^-46 each vanish in float(sqrt(ss2)) and ss2 is held to ss2_tol = the eps terms plus one float64 rounding per addition).  So
+    (float)sqrt(ss2) = 2^p_kk and W_new = U / 2^p_kk is exact.  The pre-clamp target is U where not clamped and an integer in -3..-1
+    where clamped; AH[i][kk] = target + sum_{l > kk} W_old[i][l] G[l][kk] + sum_{l < kk} W_new[i][l] G[l][kk] (eps = 2^-23: without the
+    clamped W_new terms, so AH is an integer and the exact sweep ends a hair below the target, rounded once: the target).
+    Clamped rows: the last row in even columns, the first row of the last workgroup in odd ones (eps = 2^-23: in columns 0 and 1 only),
+    the others at random (eps = 2^-3: 64 per column, m >= 130; eps = 2^-23: two per column, dealt round so that no row clamps often,
+    m >= 16).  Smaller m: no row clamps (m = 1 cannot have both kinds).
+
+    ss2_tol, eps = 2^-23: the integer squares and all their partial sums are exact in float64; only a partial sum that carries one of the
+    n_c terms of 2^-46 can round, by at most half a spacing of 4^p, and along its way to the total it does so where it merges with
+    another such partial or crosses a binade (at most 2 p + 2 of them; between those it stays on the grid it was rounded to, the
+    integers added to it are multiples of that grid).  So |ss2 - 4^p| <= n_c (2^-46 + (2 p + 5) spacing(4^p) / 2).
+
+    dtype = float64 with eps = 2^-23: float64 does NOT absorb the clamped terms, so AH carries them (exact: multiples of 2^-(23 + p)
+    below 2^12) and the pre-clamp values are the integers again, exactly; ss2 = 4^p + n_c 2^-46 is then no float64 number, its square root
+    rounds and every later column sees a W_new that is off in the last bits.  `W_rel` bounds that per column (R = 2^-53, M the largest
+    sum of magnitudes of a row): tau_j = sum_{l < j} G[l][j] 3 / 2^p_l c_l + (k + 2) R M bounds the error of t (|t| >= 1 where it does not
+    clamp, <= -1 + tau where it does: no clamp flips while tau < 1/2), the sum of squares is within 2 tau_j + 2200 R of its value,
+    relatively (at most 2200 additions on any path to the total: two trips, the trees, a chain of 2048 workgroups), its root within half
+    of that plus ss2_tol / (2 4^p) + R, and c_j = 1.01 (tau_j + that + R) bounds |w - W_new| / W_new in column j (column 0: exact inputs,
+    only ss2_tol and the two roundings)."""
+    assert eps in (HALS_EPS_A, HALS_EPS_B), "the construction is proved for eps = 2^-3 and 2^-23"
+    mode_a = eps == HALS_EPS_A
+    rs = np.random.RandomState(seed + 1013 * m + 7 * k + (0 if mode_a else 3))
+    G = _sym_gram(k, rs)
+    W_old = rs.randint(0, 4, size=(m, k)).astype(np.float64)
+    last, wg0 = m - 1, HALS_ROWS * ((m - 1) // HALS_ROWS)
+    clamped = np.zeros((m, k), dtype=bool)
+    deal = rs.permutation(m)
+    for kk in range(k):
+        if mode_a and m >= 130:
+            forced = last if kk % 2 == 0 else wg0
+            rest = np.setdiff1d(np.arange(m), [forced])
+            clamped[rs.choice(rest, size=63, replace=False), kk] = True
+            clamped[forced, kk] = True
+        elif not mode_a and m >= 16:
+            clamped[deal[[(2 * kk) % m, (2 * kk + 1) % m]], kk] = True
+            if kk < 2:
+                clamped[last if kk == 0 else wg0, kk] = True
+    U = np.zeros((m, k))
+    p = np.zeros(k, dtype=np.int64)
+    for kk in range(k):
+        free = np.flatnonzero(~clamped[:, kk])
+        nc = m - free.size
+        for pk in range(0, 16):
+            v = _squares_to(4 ** pk - (nc // 64 if mode_a else 0), free.size, rs)
+            if v is not None:
+                break
+        assert v is not None, "no column of %d values in {1, 2, 3} has a power of four as its sum of squares" % free.size
+        U[free, kk], U[clamped[:, kk], kk], p[kk] = v, eps, pk
+    Wn = U / 2.0 ** p[None, :]
+    target = np.where(clamped, -rs.randint(1, 4, size=(m, k)).astype(np.float64), U)
+    f64b = not mode_a and np.dtype(dtype) == np.float64
+    Wn_seen = Wn if mode_a or f64b else np.where(clamped, 0.0, Wn)
+    AH = target + W_old @ np.tril(G, -1) + Wn_seen @ np.triu(G, 1)
+    # range: every value of the sweep is a multiple of `unit`; the sum of the magnitudes of all terms of a row bounds every partial sum
+    unit = (eps if mode_a else 1.0) / 2.0 ** p.max()
+    top = np.max(np.abs(AH) + 3 + (W_old + Wn) @ G + W_old * np.diag(G)[None, :])
+    assert top < unit * 2.0 ** 24 if mode_a else top * 2.0 ** (23 + p.max()) < 2.0 ** 52, "m = %d, k = %d: the sweep leaves the exact range" % (m, k)
+    if not mode_a:                                                  # the clamped terms a row collects stay below a quarter ulp of 1
+        tiny = np.where(clamped, eps / 2.0 ** p[None, :], 0.0) @ np.triu(G, 1)
+        assert tiny.max(initial=0.0) < 2.0 ** -25, "m = %d, k = %d: a row clamps too often for eps = 2^-23" % (m, k)
+    nc = clamped.sum(0)
+    ss2_tol = np.zeros(k) if mode_a else nc * (eps * eps + (2 * p + 5) * np.spacing(4.0 ** p) / 2)
+    W_rel = np.zeros(k)
+    if f64b:                                                        # the exact sweep with the exact W_new: the integers, and 4^p + n_c eps^2
+        T = AH - W_old @ np.tril(G, -1) - Wn @ np.triu(G, 1)
+        W_new, ss2 = Wn, 4.0 ** p + nc * eps * eps
+        R = 2.0 ** -53
+        for j in range(k):
+            tau = (G[:j, j] * 3 / 2.0 ** p[:j]) @ W_rel[:j] + (k + 2) * R * top if j else 0.0
+            root = ((2 * tau + 2200 * R) / 2 if j else 0.0) + ss2_tol[j] / (2 * 4.0 ** p[j]) + R
+            W_rel[j] = 1.01 * (tau + root + R)
+            assert tau < 0.5, "m = %d, k = %d: the float64 bound with eps = 2^-23 reaches a clamp decision at column %d" % (m, k, j)
+            ss2_tol[j] += (2 * tau + 2200 * R) * 4.0 ** p[j] if j else 0.0
+    else:
+        T, W_new, ss2 = hals_w_exact(W_old, AH, G, eps)
+    assert np.array_equal(T, target) and np.array_equal(W_new, Wn), "the exact sweep does not end at the constructed answer"
+    if mode_a:
+        assert np.array_equal(ss2, 4.0 ** p)
+    for s in (ss2 - ss2_tol, ss2 + ss2_tol):
+        assert np.array_equal(np.sqrt(s).astype(np.float32), 2.0 ** p)
+    if not f64b:
+        assert np.all(np.abs(ss2 - 4.0 ** p) <= ss2_tol)
+    if m >= (130 if mode_a else 16):
+        assert clamped.any(0).all() and (~clamped).any(0).all() and clamped[last].any() and clamped[wg0:].any()
+    cast = lambda x: x.astype(dtype)
+    for x in (W_old, AH, G, W_new):
+        assert np.array_equal(cast(x).astype(np.float64), x)
+    return dict(W_old=cast(W_old), AH=cast(AH), G=cast(G), T_final=target, W_new=W_new, ss2=ss2, p=p, ss2_tol=ss2_tol, W_rel=W_rel, clamped=clamped)
+
+
+def hals_h_exact(H_old, AtW, G2, eps, dtype=np.float32):
+    """The H sweep in exact arithmetic, each row rounded once: H[kk] = max(H[kk] + AtW[kk] - G2[kk] . H, eps) with the rows above kk
+    already updated (float64 sums, exact on the generator's operands)."""
+    H = np.array(H_old, dtype=np.float64)
+    AtW, G2 = np.asarray(AtW, dtype=np.float64), np.asarray(G2, dtype=np.float64)
+    for kk in range(H.shape[0]):
+        H[kk] = np.maximum((H[kk] + AtW[kk] - G2[kk] @ H).astype(dtype), eps)
+    return H
+
+
+def hals_h_problem(k, n, eps, seed=0):
+    """One exact H sweep: H_old in 0..3, G2 = `_sym_gram`, the new H chosen first -- eps where it clamps (from a pre-clamp integer in
+    -3..-1), 1..3 elsewhere -- and AtW solved for: AtW[kk] = pre-clamp - H_old[kk] + sum_{j >= kk} G2[kk][j] H_old[j] + sum_{j < kk}
+    G2[kk][j] H_new[j].  eps = 2^-3: any entry may clamp (each with probability 0.3); every value is a multiple of 2^-3 below 2^21.
+    eps = 2^-23: a clamped eps is not absorbed by the integers it meets, so the clamped rows of a column are its LAST ones, from a row
+    s_c that runs over 0..k with c: the rows above them never see an eps and those below clamp whatever it does to their pre-clamp
+    value (<= -1 + k 2^-21); AtW leaves the eps terms out.  Every row (k > 1) has clamped and unclamped columns for n >= k + 1.
+    Returns H_old, AtW, G2 and the expected new H (float64)."""
+    assert eps in (HALS_EPS_A, HALS_EPS_B)
+    mode_a = eps == HALS_EPS_A
+    rs = np.random.RandomState(seed + 101 * k + 3 * n + (0 if mode_a else 1))
+    G2 = _sym_gram(k, rs)
+    H_old = rs.randint(0, 4, size=(k, n)).astype(np.float64)
+    if mode_a:
+        clamped = rs.rand(k, n) < 0.3
+        clamped[rs.randint(k, size=n), np.arange(n)] |= n > 1       # (and at least one per column)
+    else:
+        clamped = np.arange(k)[:, None] >= ((np.arange(n) + 1) % (k + 1))[None, :]
+    Hn = np.where(clamped, eps, rs.randint(1, 4, size=(k, n)).astype(np.float64))
+    pre = np.where(clamped, -rs.randint(1, 4, size=(k, n)).astype(np.float64), Hn)
+    seen = Hn if mode_a else np.where(clamped, 0.0, Hn)
+    AtW = pre - H_old + np.triu(G2) @ H_old + np.tril(G2, -1) @ seen
+    _bound(np.abs(AtW) + 3 + G2 @ (H_old + Hn) + H_old, eps if mode_a else 2.0 ** -3, np.float32, "the H sweep")
+    assert np.array_equal(hals_h_exact(H_old, AtW, G2, eps), Hn), "the exact H sweep does not end at the constructed answer"
+    f32 = lambda x: x.astype(np.float32)
+    for x in (H_old, AtW, G2, Hn):
+        assert np.array_equal(f32(x).astype(np.float64), x)
+    return f32(H_old), f32(AtW), f32(G2), Hn
+
+
+def is_bf16(x):
+    """element-wise: the float32 value has no bits below bfloat16's 8-bit significand"""
+    return (np.ascontiguousarray(x, dtype=np.float32).view(np.uint32) & 0xFFFF) == 0
+
+
+def _column_mix(m):
+    """(p, n1, n2, n3, a, b): a column of m rows -- n1 ones, n2 twos, n3 threes, a entries of 1/2, b of 1/4, the rest eps = 1/8 -- whose
+    squares add up to 4^p: m + 3 b + 15 a + 63 n1 + 255 n2 + 575 n3 = 64 4^p (n3 = 2 (1 - m) mod 3 leaves a multiple of 3 for a and b)"""
+    n3 = (2 * (1 - m)) % 3
+    for p in range(0, 12):
+        r = 64 * 4 ** p - m - 575 * n3
+        if r < 0:
+            continue
+        n2 = min(r // 255, 40)
+        r -= 255 * n2
+        n1 = min(r // 63, 6)
+        r -= 63 * n1
+        a, b = (r // 3) // 5, (r // 3) % 5
+        if r % 3 == 0 and a <= 6 and 1 <= n1 + n2 + n3 and n1 + n2 + n3 + a + b <= m - 2:
+            return p, n1, n2, n3, a, b
+    raise AssertionError("no column of %d rows with these values has a power of four as its sum of squares" % m)
+
+
+def _step_design_bf16(m, n, k, rs):
+    """The W phase of `hals_step_problem` with every entry of A representable in bfloat16 (8 significant bits).  What costs bits in
+    AH = pre-clamp + sum_{l > kk} W_old G + sum_{l < kk} W_new G is the last sum, so: ONE p for all columns (`_column_mix`: a few rows of
+    1/4, 1/2, 1, 2, 3, all others clamped), every off-diagonal of G equal to g = 2^(3 + p) (H2: one column of 2^((3 + p) / 2), or two of
+    2^((2 + p) / 2)), so W_new g = 8 U is 1 for a clamped entry and 2, 4, 8, 16, 24 for the others; W_old one-hot with a 1 (or a zero
+    row).  AH is then a small integer (plus 1/4 or 1/2 in a row that takes a fraction: those go to the rows with the smallest sums),
+    the unclamped values of a column go to the rows that carry least so far.  The columns of A that meet zeros of H_old are free (0..7)."""
+    eps = HALS_EPS_A
+    nh = n - k
+    assert nh >= 2, "the bf16 construction needs n >= k + 2"
+    p, n1, n2, n3, a, b = _column_mix(m)
+    g = 2.0 ** (3 + p)
+    H2 = np.zeros((k, nh))
+    nz = 1 if p % 2 else 2
+    H2[:, :nz] = 2.0 ** ((3 + p) // 2 if p % 2 else (2 + p) // 2)
+    D = 2.0 ** rs.randint(0, 2, size=k)
+    H_old = np.hstack([np.diag(D), H2])
+    G = H_old @ H_old.T
+    assert np.all(G[~np.eye(k, dtype=bool)] == g)
+    W_old = np.zeros((m, k))
+    hot = rs.randint(0, k + 1, size=m)                              # (k: a zero row)
+    W_old[np.arange(m)[hot < k], hot[hot < k]] = 1
+    U, clamped, S, load = np.full((m, k), eps), np.ones((m, k), dtype=bool), np.zeros((m, k)), np.zeros(m)
+    vals = np.concatenate([np.full(b, 0.25), np.full(a, 0.5), np.full(n1, 1.0), np.full(n2, 2.0), np.full(n3, 3.0)])
+    for kk in range(k):
+        S[:, kk] = W_old[:, kk + 1:] @ G[kk + 1:, kk] + (U[:, :kk] / 2.0 ** p) @ G[:kk, kk]
+        forced = m - 1 if kk % 2 == 0 else 0
+        order = np.argsort(S[:, kk] + load + rs.rand(m), kind="stable")
+        order = order[order != forced][:vals.size]
+        U[order, kk], clamped[order, kk] = vals, False
+        load[order] += 8 * vals
+    target = np.where(clamped, -np.minimum(rs.randint(0, 4, size=(m, k)), np.floor(S)), U)
+    AH = target + S
+    A2 = np.zeros((m, nh))
+    A2[:, nz:] = rs.randint(0, 8, size=(m, nh - nz))
+    A2[:, 0] = rs.rand(m) < 0.5
+    A2[((AH - A2 @ H2.T) < 0).any(1), 0] = 0
+    A = np.hstack([(AH - A2 @ H2.T) / D[None, :], A2])
+    return A, W_old, H_old, G, U, clamped, np.full(k, p), target, AH
+
+
+def hals_step_problem(m, n, k, seed=0, bf16=False):
+    """ONE whole HALS step (W sweep, then the H sweep on the new W) with an exact W phase, eps = 2^-3.  H_old = [D | H2]: D a k x k
+    diagonal of 1s and 2s, H2 0/1 with a first column of ones, so G = H_old H_old^T = D^2 + H2 H2^T has off-diagonals >= 1.  The W
+    phase is built as in `hals_w_problem` for that G, for any m >= 11: per column 4 clamped rows (the last row in even columns, row 0
+    in odd ones), 3 rows of 1/4 and 3 of 1/2 -- together 4/64 + 3/16 + 3/4 = 1 -- and values of {1, 2, 3} whose squares add up to
+    4^p - 1.  A clamped pre-clamp value is 0, -1, -2 or -3, as low as A >= 0 allows (with every sum exact nothing can flip a clamp).
+    A = [A1 | A2]: A2 0/1, sparse, kept in the rows where A1 = (AH - A2 H2^T) D^-1 stays >= 0, so A H_old^T = AH term for term,
+    non-negative multiples of 2^-(3 + p) below 2^24 of them.
+    The H phase is NOT exact and cannot be made so: every entry of the new W is >= eps / 2^p > 0, so G2 = W^T W has off-diagonals of
+    many bits, each row of the H sweep multiplies them with the rows above it and the bits add up row by row; W^T A itself leaves 24
+    bits from m of about a hundred on.  A forward error bound is no substitute: the columns of this W are far from orthogonal (G2
+    off-diagonals up to 0.8), the bound of row kk carries those of the rows above it with these weights and passes the values
+    themselves from k = 16 on.  It is derived and asserted all the same -- it holds a few 1e-6 of the entries at k = 1, a few per cent
+    at k = 5 and k = 12 -- and the H sweep kernels have `hals_h_problem` for every element.  H_err, with u = 2^-24 and g(c) = c u / (1 - c u):
+    W^T A and W^T W are sums of m exact non-negative products, within g(m) of their values in any order; row kk of the sweep forms k
+    products, their sum and two more additions, in any order within g(2 k + 2) of the sum of the magnitudes, and carries the errors E_j
+    of the rows above it with weights G2[kk][j]; the clamp is 1-Lipschitz; magnitudes are enlarged by their own bounds.
+    bf16=True: the construction of `_step_design_bf16` instead, every entry of A a bfloat16 number (asserted; a shape it cannot serve
+    raises AssertionError and belongs in HALS_STEP_BF16_LEFT).
+    Returns a dict: A, W_old, H_old (float32), W_new (the exact new W, float64), H_new (the float64 sweep), H_err, AH, G and `clamped`."""
+    eps = HALS_EPS_A
+    nh = n - k
+    assert nh >= 1 and m >= 11, "the construction needs n > k and m >= 11"
+    rs = np.random.RandomState(seed + 31 * m + 7 * n + k + (5 if bf16 else 0))
+    if bf16:
+        A, W_old, H_old, G, U, clamped, p, target, AH = _step_design_bf16(m, n, k, rs)
+        assert is_bf16(A).all(), "%d x %d, k = %d: an entry of A needs more than 8 significant bits" % (m, n, k)
+        return _step_finish(m, n, k, eps, A, W_old, H_old, G, U, clamped, p, target, AH)
+    D = 2.0 ** rs.randint(0, 2, size=k)
+    H2 = (rs.rand(k, nh) < 0.3).astype(np.float64)
+    H2[:, 0] = 1
+    H_old = np.hstack([np.diag(D), H2])
+    G = H_old @ H_old.T
+    W_old = rs.randint(0, 4, size=(m, k)).astype(np.float64)
+    U, clamped, p = np.zeros((m, k)), np.zeros((m, k), dtype=bool), np.zeros(k, dtype=np.int64)
+    for kk in range(k):
+        forced = m - 1 if kk % 2 == 0 else 0
+        rows = np.concatenate([[forced], rs.permutation(np.setdiff1d(np.arange(m), [forced]))])
+        for pk in range(0, 16):
+            v = _squares_to(4 ** pk - 1, m - 10, rs)
+            if v is not None:
+                break
+        assert v is not None
+        U[rows[:4], kk], U[rows[4:7], kk], U[rows[7:10], kk], U[rows[10:], kk] = eps, 0.25, 0.5, v
+        clamped[rows[:4], kk], p[kk] = True, pk
+    Wn = U / 2.0 ** p[None, :]
+    S = W_old @ np.tril(G, -1) + Wn @ np.triu(G, 1)
+    target = np.where(clamped, -np.minimum(rs.randint(0, 4, size=(m, k)), np.floor(S)), U)
+    AH = target + S
+    A2 = (rs.rand(m, nh) < 0.15).astype(np.float64)
+    A2[((AH - A2 @ H2.T) < 0).any(1)] = 0
+    A = np.hstack([(AH - A2 @ H2.T) / D[None, :], A2])
+    return _step_finish(m, n, k, eps, A, W_old, H_old, G, U, clamped, p, target, AH)
+
+
+def _step_finish(m, n, k, eps, A, W_old, H_old, G, U, clamped, p, target, AH):
+    """the checks of `hals_step_problem` and the float64 H sweep with its bound"""
+    Wn = U / 2.0 ** p[None, :]
+    unit = eps / 2.0 ** p.max()
+    assert A.min() >= 0 and np.array_equal(A @ H_old.T, AH)
+    _bound(AH + 3 + (W_old + Wn) @ G + W_old * np.diag(G)[None, :], unit, np.float32, "the W phase of the step")
+    _bound(G, 1.0, np.float32, "H H^T")
+    T, W_new, ss2 = hals_w_exact(W_old, AH, G, eps)
+    assert np.array_equal(T, target) and np.array_equal(W_new, Wn) and np.array_equal(ss2, 4.0 ** p)
+    u = 2.0 ** -24
+    g = lambda cnt: cnt * u / (1 - cnt * u)
+    AtW, G2 = Wn.T @ A, Wn.T @ Wn
+    eA, eG = g(m) * AtW, g(m) * G2
+    H, E = H_old.copy(), np.zeros((k, n))
+    for kk in range(k):
+        Hm = np.abs(H) + E
+        mag = Hm[kk] + AtW[kk] + eA[kk] + (G2[kk] + eG[kk]) @ Hm
+        E[kk] = (eA[kk] + eG[kk] @ Hm + G2[kk] @ E + g(2 * k + 2) * mag) * (1 + 2.0 ** -20)      # (and the float64 evaluation of this reference)
+        H[kk] = np.maximum(H[kk] + AtW[kk] - G2[kk] @ H, eps)
+    f32 = lambda x: x.astype(np.float32)
+    for x in (A, W_old, H_old):
+        assert np.array_equal(f32(x).astype(np.float64), x)
+    return dict(A=f32(A), W_old=f32(W_old), H_old=f32(H_old), W_new=Wn, H_new=H, H_err=E, AH=AH, G=G, clamped=clamped)
+
+
+# bf16-A rows of the reach table that `hals_step_problem(bf16=True)` cannot serve (they keep the checks of test_hals_reach only)
+HALS_STEP_BF16_LEFT = []
+
+
+# one step on the big path (no small whole-fit kernel applies): the one-rank route of nmf_algorithms_1D
+HALS_STEP_BIG = [(3000, 300, 12), (2100, 260, 40)]
+
+
+# The shapes of tests/test_gpu_exact_hals.py with what dnmf_hals_sweep_plan must report for each -- (route, KP, grid, transform, vec):
+# route 1 = the persistent sweep (grid = ceil(m / 512)), 0 = column launches (grid = min(ceil(m / 256), 2048)); transform 0 = whole
+# tiles, 1 = 16-byte rows with guards, 2 = scalar rows.  aligned: 16-byte aligned starts and pitches (`Poisoned`), else odd ones.
+def _slots(nwg):
+    """m whose last workgroup (of nwg) holds ONE live row"""
+    return HALS_ROWS * nwg - (HALS_ROWS - 1)
+
+
+HALS_W_CASES = [
+    # KP = 32
+    ("700x5", 700, 5, True, (1, 32, 2, 2, 0)),
+    ("1024x32-full-tiles", 1024, 32, True, (1, 32, 2, 0, 0)),
+    ("1000x12-guarded", 1000, 12, True, (1, 32, 2, 1, 0)),
+    ("1000x12-odd", 1000, 12, False, (1, 32, 2, 2, 0)),
+    ("1x1", 1, 1, True, (1, 32, 1, 2, 0)),
+    ("513x1", 513, 1, True, (1, 32, 2, 2, 0)),
+    # KP = 64
+    ("900x33", 900, 33, True, (1, 64, 2, 2, 0)),
+    ("1024x64-vec-full", 1024, 64, True, (1, 64, 2, 0, 1)),
+    ("1030x36-vec-guarded", 1030, 36, True, (1, 64, 3, 1, 1)),
+    ("1030x36-odd", 1030, 36, False, (1, 64, 3, 2, 0)),
+    # KP = 128
+    ("1500x65", 1500, 65, True, (1, 128, 3, 2, 0)),
+    ("1536x128-full-tiles", 1536, 128, True, (1, 128, 3, 0, 0)),
+    ("1100x100-guarded", 1100, 100, True, (1, 128, 3, 1, 0)),
+    # wide ranks: column launches only
+    ("600x129-wide", 600, 129, True, (0, 256, 3, -1, 0)),
+    ("300x256-wide", 300, 256, False, (0, 256, 2, -1, 0)),
+    # the column kernels' grid-stride loop: a second trip of the 2048 x 256 grid (and more workgroups than the slot slab holds)
+    ("524588x2-stride", 524588, 2, True, (0, 32, 2048, -1, 0)),
+    # slot polling (hals_poll<NQ> per polling wave of 256 slots), the last workgroup holding one live row
+    ("poll-kp128-129wg", _slots(129), 65, True, (1, 128, 129, 2, 0)),
+] + [("poll-%dwg" % nwg, _slots(nwg), 3, True, (1, 32, nwg, 2, 0)) for nwg in (64, 65, 128, 129, 256, 257, 330, 400)]
+HALS_CAPS = (512, 1024)                                           # resident workgroups of the KP = 32 sweep the proofs cover (an MI355X holds 512)
+HALS_POLL_K = 3                                                   # the rank of the two cases at nwg = cap and cap + 1 (read from the plan)
+HALS_W_F64 = [(300, 7), (1000, 33), (513, 128)]
+HALS_W_F64_B = HALS_W_F64[:2]                                     # eps = 2^-23 in float64: the derived bound W_rel grows like 1.4^k and means nothing at k = 128
+HALS_H_CASES = ([(k, n) for k in (1, 5, 32, 33, 64) for n in (1, 255, 256, 257, 600)]          # hals_h_kernel<32>, <64>: 256 columns per workgroup
+                + [(k, n) for k in (65, 100, 128) for n in (1, 63, 64, 65, 200)]                # hals_h_kernel_lds: 64 columns per workgroup
+                + [(k, n) for k in (129, 192, 256) for n in (70, 300)])                         # the wide kernel
+HALS_H_F64 = [(7, 200), (64, 257), (128, 65)]
+
+
 # ---------------------------------------------------------------------------------------------------------- sparse (CSR) blocks
 # Row lengths on both sides of every structural boundary of csrc/dnmf_csr.h: the lane-group counts NG = 256 / KPAD = 16, 8, 4, 2, 1,
 # the 64 (col, val) pairs a wave reads per step, and the segment length 1024 of a long row (one, two and three segments, a ragged

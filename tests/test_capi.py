@@ -62,6 +62,12 @@ def test_argument_validation_without_gpu():
     assert lib.dnmf_mu_fro_step_2d_bf16a(None, 8, 8, 8, None, 8, 4, None, 8, 8, 4, 1e-7, 1, 0, None, 0, None, None) == -1
     assert lib.dnmf_wta_gram(None, 8, 8, 8, None, 4, 4, None, 8, None, None, 0, None) == -1
     assert lib.dnmf_clock_probe(None, 4, 1, None) == -1
+    # the plan query of the HALS W sweep: its refusals come before the device is asked
+    plan = (ctypes.c_int * 6)()
+    for bad in ((8, 4, 4, 4, 1, 1, None), (8, 0, 4, 4, 1, 1, plan), (8, 257, 300, 300, 1, 1, plan), (0, 4, 4, 4, 1, 1, plan), (8, 4, 3, 4, 1, 1, plan),
+                (8, 4, 4, 3, 1, 1, plan)):
+        assert lib.dnmf_hals_sweep_plan(*bad) == -1 and b"hals_sweep_plan:" in lib.dnmf_last_error(), bad
+    assert lib.dnmf_hals_sweep_plan(600, 129, 129, 129, 1, 1, plan) == 0 and list(plan) == [0, 256, 3, -1, 0, 0]     # a wide rank: column launches, no device needed
     assert lib.dnmf_comm_destroy(None) == 0
 
 

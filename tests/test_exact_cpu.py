@@ -314,3 +314,217 @@ def test_sparse_kl_is_exact(lens_mask, k):
         _exact_in_all_orders(mask, Mf, H.T, ng, ref["klden_w"], "stored-position sums of H rows")
         _exact_in_all_orders(mask.T, U32.T, W, ng, ref["wtu"].T, "W^T U")
         _exact_in_all_orders(mask.T, Mf.T, W, ng, ref["klden_h"].T, "stored-position sums of W columns")
+
+
+# ---------------------------------------------------------------------------------------------------------- one exact HALS sweep
+# `hals_w_problem` / `hals_h_problem`: the sweeps of csrc/dnmf_hals.h evaluated in numpy float32 in the forms the kernels use, each with
+# its sums taken forward, reversed and in one random order, end at the constructed answer bit for bit -- with eps = 2^-3 (every sum
+# exact) and with the library's eps = 2^-23 (the clamped terms absorbed by the single rounding of each fmaf).
+F32 = np.float32
+
+
+def _fma(a, b, c):
+    """fmaf on float32 arrays: the float64 product and sum are exact on these operands (`hals_w_problem` asserts the range), so
+    rounding them once is the fused operation"""
+    return (np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64) + np.asarray(c, dtype=np.float64)).astype(F32)
+
+
+def _orders(n, seed=0):
+    return (("forward", np.arange(n)), ("reversed", np.arange(n)[::-1]), ("random", np.random.RandomState(seed + n).permutation(n)))
+
+
+def _ss2(u, rows):
+    """sum of squares in float64, one row after the other in the order `rows`"""
+    u = u.astype(np.float64)[rows]
+    return float(np.cumsum(u * u)[-1])
+
+
+def _w_persistent(W, AH, G, eps, order, rows, lagged):
+    """the two-launch form: T[i][j] = AH[i][j] - sum_{l > j} W[i][l] G[l][j] (the products summed in `order`, then one subtraction: the
+    MFMA pass), then per column u, ss2 in float64, w = u / (float)sqrt(ss2) and t[j] = fmaf(-w, G[kk][j], t[j]) for j > kk -- at once, or
+    lagged as hals_col_step does it: j = kk + 1 first, the others at the start of the next column's turn"""
+    m, k = W.shape
+    acc = np.zeros((m, k), dtype=F32)
+    for l in order:
+        acc[:, :l] = _fma(W[:, l:l + 1], G[l:l + 1, :l], acc[:, :l])
+    t = AH - acc
+    T0 = t.copy()
+    ss2 = np.zeros(k)
+    for kk in range(k):
+        if lagged and kk > 0:
+            t[:, kk + 1:] = _fma(-t[:, kk - 1:kk], G[kk - 1:kk, kk + 1:], t[:, kk + 1:])
+        u = np.maximum(t[:, kk], F32(eps))
+        ss2[kk] = _ss2(u, rows)
+        ss = F32(np.sqrt(ss2[kk]))
+        t[:, kk] = u / ss if ss > 0 else u
+        hi = kk + 2 if lagged else k
+        t[:, kk + 1:hi] = _fma(-t[:, kk:kk + 1], G[kk:kk + 1, kk + 1:hi], t[:, kk + 1:hi])
+    return T0, t, ss2
+
+
+def _w_columns(W, AH, G, eps, order, rows):
+    """hals_w_col_kernel: the pending normalisation of column kk - 1, dot = sum_j fmaf(row[j], g[j], dot) over ALL j, t = row[kk] g[kk] +
+    AH - dot; then hals_w_scale_kernel on the last column"""
+    W = W.copy()
+    m, k = W.shape
+    ss2 = np.zeros(k)
+    for kk in range(k):
+        if kk > 0:
+            den = F32(np.sqrt(ss2[kk - 1]))
+            if den > 0:
+                W[:, kk - 1] = W[:, kk - 1] / den
+        dot = np.zeros(m, dtype=F32)
+        for j in order:
+            dot = _fma(W[:, j], G[j, kk], dot)
+        t = (W[:, kk] * G[kk, kk] + AH[:, kk]) - dot
+        W[:, kk] = np.maximum(t, F32(eps))
+        ss2[kk] = _ss2(W[:, kk], rows)
+    den = F32(np.sqrt(ss2[k - 1]))
+    if den > 0:
+        W[:, k - 1] = W[:, k - 1] / den
+    return W, ss2
+
+
+def _check_w(got, ss2, P, how):
+    assert got.dtype == F32 and np.array_equal(got.astype(np.float64), P["W_new"]), "W sweep, %s: not the constructed answer" % how
+    assert np.all(np.abs(ss2 - P["ss2"]) <= P["ss2_tol"]), "W sweep, %s: ss2 off by %g" % (how, np.max(np.abs(ss2 - P["ss2"]) - P["ss2_tol"]))
+    assert np.array_equal(np.sqrt(ss2).astype(F32), 2.0 ** P["p"])
+
+
+HALS_W_PROOF = sorted({(m, k) for _, m, k, _, _ in ex.HALS_W_CASES} | set(ex.HALS_W_F64)
+                      | {(ex._slots(c + over), ex.HALS_POLL_K) for c in ex.HALS_CAPS for over in (0, 1)})
+
+
+@pytest.mark.parametrize("eps", [ex.HALS_EPS_A, ex.HALS_EPS_B], ids=["eps2^-3", "eps2^-23"])
+@pytest.mark.parametrize("m,k", HALS_W_PROOF)
+def test_hals_w_problem_is_exact_in_every_form(m, k, eps):
+    P = ex.hals_w_problem(m, k, eps)
+    W, AH, G = P["W_old"], P["AH"], P["G"]
+    T0_exact = AH.astype(np.float64) - W.astype(np.float64) @ np.tril(G.astype(np.float64), -1)
+    for (how, order), (_, rows) in zip(_orders(k), _orders(m, 1)):
+        for lagged in (False, True):
+            T0, got, ss2 = _w_persistent(W, AH, G, eps, order, rows, lagged)
+            assert np.array_equal(T0.astype(np.float64), T0_exact), "the transform pass is not exact (%s)" % how
+            _check_w(got, ss2, P, "persistent form%s, %s" % (", lagged" if lagged else "", how))
+        got, ss2 = _w_columns(W, AH, G, eps, order, rows)
+        _check_w(got, ss2, P, "column form, %s" % how)
+    if eps == ex.HALS_EPS_A:
+        assert not P["ss2_tol"].any() and np.array_equal(P["ss2"], 4.0 ** P["p"])
+    if m >= 130:
+        c = P["clamped"]
+        assert c.any(0).all() and (~c).any(0).all() and c[m - 1].any() and c[ex.HALS_ROWS * ((m - 1) // ex.HALS_ROWS):].any()
+        assert np.all(P["G"][~np.eye(k, dtype=bool)] > 0)
+
+
+def test_hals_w_problem_is_free_of_the_row_count_modulo_three():
+    """entries of 3 (9 = 0 mod 3) lift the condition pure powers of four would put on m"""
+    for m in (130, 131, 132, 513, 514, 515):
+        for eps in (ex.HALS_EPS_A, ex.HALS_EPS_B):
+            ex.hals_w_problem(m, 4, eps)
+
+
+@pytest.mark.parametrize("eps", [ex.HALS_EPS_A, ex.HALS_EPS_B], ids=["eps2^-3", "eps2^-23"])
+@pytest.mark.parametrize("k,n", sorted(set(ex.HALS_H_CASES) | set(ex.HALS_H_F64)))
+def test_hals_h_problem_is_exact_in_every_order(k, n, eps):
+    H0, AtW, G2, Hn = ex.hals_h_problem(k, n, eps)
+    for how, order in _orders(k):
+        H = H0.copy()
+        for kk in range(k):
+            dot = np.zeros(n, dtype=F32)
+            for j in order:
+                dot = _fma(G2[kk, j], H[j], dot)
+            H[kk] = np.maximum((H[kk] + AtW[kk]) - dot, F32(eps))
+        assert H.dtype == F32 and np.array_equal(H.astype(np.float64), Hn), "H sweep, %s: not the constructed answer" % how
+    clamped = Hn == eps
+    if k > 1 and n > k:
+        assert clamped.any(1).all() and (~clamped).any(1).all(), "a row without both kinds of column"
+
+
+HALS_STEP_PROOF = [e[1:4] for e in ex.SMALL_REACH if e[0] == "hals"] + ex.HALS_STEP_BIG
+HALS_STEP_BF16 = [e[1:4] for e in ex.SMALL_REACH if e[0] == "hals_bf16"]
+
+
+def test_hals_step_bf16_rows_left_out_stay_few():
+    """at most 3 bf16-A rows may be left to the old checks, each must really be out of the generator's reach, every other row has a
+    problem whose A is bf16 in every entry"""
+    left = set(ex.HALS_STEP_BF16_LEFT)
+    assert len(left) <= 3 and left <= set(HALS_STEP_BF16)
+    for m, n, k in HALS_STEP_BF16:
+        if (m, n, k) in left:
+            with pytest.raises(AssertionError):
+                ex.hals_step_problem(m, n, k, bf16=True)
+        else:
+            for seed in range(3):
+                P = ex.hals_step_problem(m, n, k, seed, bf16=True)
+                assert ex.is_bf16(P["A"]).all() and P["A"].min() >= 0
+
+
+@pytest.mark.parametrize("m,n,k,bf16", [s + (False,) for s in HALS_STEP_PROOF] + [s + (True,) for s in HALS_STEP_BF16 if s not in ex.HALS_STEP_BF16_LEFT])
+def test_hals_step_problem_has_an_exact_w_phase(m, n, k, bf16):
+    """A H^T and H H^T in every order, then the W sweep in every form: the constructed W_new bit for bit; A >= 0"""
+    for seed in range(3 if m * n * k < 1e6 else 1):
+        P = ex.hals_step_problem(m, n, k, seed, bf16)
+        A, W, H = P["A"], P["W_old"], P["H_old"]
+        assert A.min() >= 0 and P["clamped"].any(0).all() and P["clamped"][m - 1].any()
+        small = m * n * k <= 4e6
+        AH = _all_orders(A, H.T, "A H^T") if small else A.astype(np.float64) @ H.astype(np.float64).T
+        G = _all_orders(H, H.T, "H H^T")
+        assert np.array_equal(AH, P["AH"]) and np.array_equal(G, P["G"]) and np.all(G[~np.eye(k, dtype=bool)] >= 1)
+        assert P["clamped"].any(0).all() and (~P["clamped"]).any(0).all()
+        AH32, G32 = AH.astype(F32), G.astype(F32)
+        for (how, order), (_, rows) in zip(_orders(k), _orders(m, 1)):
+            for lagged in (False, True):
+                _, got, ss2 = _w_persistent(W, AH32, G32, ex.HALS_EPS_A, order, rows, lagged)
+                assert np.array_equal(got.astype(np.float64), P["W_new"]) and np.all(np.log2(ss2) % 2 == 0), how
+            got, ss2 = _w_columns(W, AH32, G32, ex.HALS_EPS_A, order, rows)
+            assert np.array_equal(got.astype(np.float64), P["W_new"]) and np.all(np.log2(ss2) % 2 == 0), how
+            # the small whole-fit kernel sums the squares in float32: exact too (multiples of 2^-6 below 2^18 of them)
+            u = np.maximum(P["W_new"] * np.sqrt(ss2)[None, :], 0).astype(F32)
+            assert np.array_equal(np.cumsum((u * u)[rows], axis=0, dtype=F32)[-1].astype(np.float64), ss2)
+        Wc = np.maximum(P["W_new"], ex.HALS_EPS_A)
+        s = Wc.sum(0)
+        for order in (np.arange(m), np.arange(m)[::-1]):
+            assert np.array_equal(np.cumsum(Wc.astype(F32)[order], axis=0, dtype=F32)[-1].astype(np.float64), s), "colsum(W) is not exact"
+        assert np.array_equal((s + ex.HALS_EPS_A).astype(F32).astype(np.float64), s + ex.HALS_EPS_A)
+
+
+@pytest.mark.parametrize("m,k", ex.HALS_W_F64_B)
+def test_hals_w_problem_float64_with_the_library_eps_stays_within_its_bound(m, k):
+    """float64, eps = 2^-23: the column form in numpy float64 (fma replaced by two roundings: within the (k + 2) R M the bound allows), its
+    sums forward, reversed and in a random order, ends within W_rel of the exact answer and within ss2_tol of the exact sums of squares"""
+    P = ex.hals_w_problem(m, k, ex.HALS_EPS_B, dtype=np.float64)
+    assert P["AH"].dtype == np.float64 and P["W_rel"].max() < 1e-8 and P["W_rel"][0] < 1e-14
+    for (how, order), (_, rows) in zip(_orders(k), _orders(m, 1)):
+        W = P["W_old"].copy()
+        ss2 = np.zeros(k)
+        for kk in range(k):
+            if kk > 0:
+                W[:, kk - 1] /= np.sqrt(ss2[kk - 1])
+            dot = np.zeros(m)
+            for j in order:
+                dot = dot + W[:, j] * P["G"][j, kk]
+            W[:, kk] = np.maximum((W[:, kk] * P["G"][kk, kk] + P["AH"][:, kk]) - dot, ex.HALS_EPS_B)
+            ss2[kk] = np.cumsum((W[:, kk] ** 2)[rows])[-1]
+        W[:, k - 1] /= np.sqrt(ss2[k - 1])
+        assert np.all(np.abs(W - P["W_new"]) <= P["W_rel"][None, :] * P["W_new"]), how
+        assert np.all(np.abs(ss2 - P["ss2"]) <= P["ss2_tol"]), how
+
+
+@pytest.mark.parametrize("m,n,k,bf16", [s + (False,) for s in HALS_STEP_PROOF] + [s + (True,) for s in HALS_STEP_BF16 if s not in ex.HALS_STEP_BF16_LEFT])
+def test_hals_step_problem_h_bound_holds_in_float32(m, n, k, bf16):
+    """the H phase of the step in numpy float32 -- W^T A and W^T W through BLAS and as sequential sums from either end, the sweep's dot
+    products forward, reversed and in a random order -- stays within the derived bound H_err of the float64 sweep"""
+    P = ex.hals_step_problem(m, n, k, bf16=bf16)
+    A, H0, Wn = P["A"], P["H_old"], P["W_new"].astype(F32)
+    small = m * n * k <= 4e6
+    prods = [(Wn.T @ A, Wn.T @ Wn)] + ([(_seq(Wn.T, A, r), _seq(Wn.T, Wn, r)) for r in (False, True)] if small else [])
+    for (AtW, G2), (how, order) in zip(prods * 3, _orders(k)):
+        H = H0.copy()
+        for kk in range(k):
+            dot = np.zeros(n, dtype=F32)
+            for j in order:
+                dot = dot + G2[kk, j] * H[j]
+            H[kk] = np.maximum((H[kk] + AtW[kk]) - dot, F32(ex.HALS_EPS_A))
+        assert H.dtype == F32 and np.all(np.abs(H - P["H_new"]) <= P["H_err"]), how
+    if k == 1 and not bf16:
+        assert np.max(P["H_err"] / np.abs(P["H_new"])) < 1e-5
