@@ -786,6 +786,76 @@ def transposed(A, mask, W, H):
     return tuple(np.ascontiguousarray(x) for x in (A.T, mask.T, H.T, W.T))
 
 
+# ---------------------------------------------------------------------------------------------------------- the BCD projected-gradient step
+# out = max(0, Xm - (S - P) / L), S = Xm G on the W side (Xm, P, out [R x k]) and G Xm on the H side ([k x R]); csrc/dnmf_bcd.h.  Proofs:
+# tests/test_exact_cpu.py; the kernels: tests/test_gpu_exact_bcd.py.
+BCD_L = 64.0                                                      # the power-of-two step bound of the exact family
+BCD_PG_PROOF = [(131, 1), (131, 17), (203, 33), (16500, 3), (520, 256), (300, 100)]      # (R, k) proved in every order, both sides
+BCD_PG_R = (1, 63, 64, 65, 131)                                   # rows of a workgroup: 64 (BCD_ROWS)
+BCD_PG_K = (1, 2, 15, 16, 17, 32, 33, 63, 64, 65, 100, 128, 129, 255, 256)
+BCD_COLSUM = [(19137, 17), (40001, 4)]                            # 300 and 626 workgroup partials: two and three trips of bcd_colsum_kernel
+
+
+def bcd_pg_problem(R, k, seed=0, L=BCD_L, side="w", shift=True):
+    """Operands of one projected-gradient step whose result is known exactly.  Xm holds integers 0..3 and G integers 0..2 (not
+    symmetric for k > 1, G[0][0] >= 1), so every term of S is a non-negative integer and S <= 6 k <= 1536: exact in float32 in any
+    order, fused or not.  P = max(0, S + u), u an integer in [-200, 200]: gr = S - P is an integer with |gr| <= 200 (the elements `shift`
+    forces below zero: up to 6 ceil(L), and they end at 0).
+
+    L = 2^p (the default 2^6): gr / L is a multiple of 1 / L with few bits, y = Xm - gr / L <= 3 + 200 / 64 = 6.125 is exact, and so
+    is the clamp -- the float32 result IS the float64 one (`expected`, compared with assert_ulp(..., 0)).  The column sums (W side):
+    a workgroup's partial adds 64 values <= 6.125 that are multiples of 2^-6, at most 64 * 6.125 * 2^6 < 2^15 units: exact in float32
+    in any butterfly order; the float64 sum of the partials is exact (below 2^53 units); the one rounding left is the final
+    conversion, so s == float32(exact sum) (`s`).
+    L = None: L = float32(||G||_F), what a fit would hold.  S and gr are exact as before; the quotient, the subtraction and the clamp
+    are one IEEE float32 operation each, so the result must equal the numpy float32 evaluation bit for bit (`expected` is that
+    evaluation, held in float64); s depends on the summation order here and keeps a relative bound.
+
+    shift: the random design alone clamps 11-26 % of the elements and none at k = 1, so every seventh element (in storage order) is
+    forced below zero -- P = S - ceil(L) (Xm + c), c in 1..3: y <= -c -- and every seventh is an exact zero: P = S - L Xm where L is a
+    power of two (y = Xm - Xm), and Xm = 0, P = S elsewhere (y = 0 - 0 / L).  P is negative at some of those.  The shares of clamped,
+    exactly-zero and positive elements are in `shares`; callers assert them.
+    Returns a dict: Xm, P, G (float32), L (a float that is a float32), expected (float64), s (float32 column sums, W side), shares."""
+    assert side in ("w", "h")
+    rs = np.random.RandomState(seed + 7919 * R + 31 * k + (side == "h"))
+    shape = (R, k) if side == "w" else (k, R)
+    Xm = rs.randint(0, 4, size=shape).astype(np.float64)
+    G = rs.randint(0, 3, size=(k, k)).astype(np.float64)
+    G[0, 0] = max(G[0, 0], 1.0)
+    if k > 1 and np.array_equal(G, G.T):
+        G[0, 1], G[1, 0] = 2.0, 0.0
+    pow2 = L is not None
+    Lf = np.float32(L if pow2 else np.sqrt((G * G).sum()))
+    if pow2:
+        assert np.frexp(Lf)[0] == 0.5 and Lf >= 1, "L must be a power of two >= 1 (or None)"
+    flat = np.arange(Xm.size).reshape(shape)
+    forced_neg, forced_zero = (flat % 7 == 2) & shift, (flat % 7 == 5) & shift
+    if R * k < 7 and shift:                                      # (too few elements for all three kinds: keep what fits, in this order)
+        forced_neg, forced_zero = flat == 1, flat == 2
+    if not pow2:
+        Xm[forced_zero] = 0.0
+    S = Xm @ G if side == "w" else G @ Xm
+    _bound(S, 1.0, np.float32, "Xm G")
+    P = np.maximum(0.0, np.rint(S + rs.randint(-200, 201, size=shape)))
+    P[forced_neg] = (S - np.ceil(float(Lf)) * (Xm + rs.randint(1, 4, size=shape)))[forced_neg]
+    P[forced_zero] = (S - float(Lf) * Xm)[forced_zero] if pow2 else S[forced_zero]
+    gr = S - P
+    assert np.abs(P).max() < 2 ** 22 and np.abs(gr).max() < 2 ** 22
+    if pow2:
+        y = Xm - gr / float(Lf)
+        assert np.array_equal(y.astype(np.float32).astype(np.float64), y) and (Lf < 64 or y.max() <= 6.125)
+        assert np.array_equal(y * float(Lf), np.rint(y * float(Lf))), "y is not a multiple of 1 / L"
+        _bound(64 * max(y.max(), 0.0), 1.0 / float(Lf), np.float32, "a workgroup's column-sum partial")
+    else:
+        y = (Xm.astype(np.float32) - gr.astype(np.float32) / Lf).astype(np.float64)
+    assert (y[forced_neg] < 0).all() and (y[forced_zero] == 0).all()
+    out = np.where(y < 0, 0.0, y)
+    shares = {"clamped": float((y < 0).mean()), "zero": float((y == 0).mean()), "positive": float((y > 0).mean())}
+    s = out.sum(0).astype(np.float32) if side == "w" else None
+    return {"Xm": Xm.astype(np.float32), "P": P.astype(np.float32), "G": G.astype(np.float32), "L": float(Lf), "expected": out, "s": s,
+            "shares": shares, "pow2": pow2}
+
+
 # ---------------------------------------------------------------------------------------------------------- per-element comparison
 def assert_ulp(got, q, c, what="", tile=(16, 32), q_hi=None):
     """|got - q| <= c * spacing(q in got's type) per element, q the float64 reference; q == 0 must be exactly 0 and c == 0 means
@@ -854,8 +924,8 @@ class Poisoned:
         npd = {torch.float32: np.float32, torch.float64: np.float64}[dtype]
         return cls(torch, np.full((rows, cols), SENTINEL, dtype=npd), dtype, fill=SENTINEL, aligned=aligned)
 
-    def check(self, what=""):
-        """nothing outside the view changed; no NaN inside it.  Returns the view as numpy."""
+    def check(self, what="", allow_nan=False):
+        """nothing outside the view changed; no NaN inside it (unless the case expects some: allow_nan).  Returns the view as numpy."""
         b = self.buf.float().cpu().numpy() if self.dtype == self.torch.bfloat16 else self.buf.cpu().numpy()
         out = b[~self.mask]
         ok = np.isnan(out) if np.isnan(self.fill) else out == np.asarray(self.fill, dtype=b.dtype)
@@ -864,5 +934,5 @@ class Poisoned:
             raise AssertionError("%s: element %d of the buffer outside the view (view starts at %d, pitch %d) was written: %r"
                                  % (what, i, self.lead, self.ld, b[i]))
         v = self.view.cpu().numpy() if self.dtype != self.torch.bfloat16 else self.view.float().cpu().numpy()
-        assert not np.isnan(v).any(), "%s: NaN inside the view at %s" % (what, tuple(np.argwhere(np.isnan(v))[0]))
+        assert allow_nan or not np.isnan(v).any(), "%s: NaN inside the view at %s" % (what, tuple(np.argwhere(np.isnan(v))[0]))
         return v

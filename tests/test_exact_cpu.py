@@ -528,3 +528,83 @@ def test_hals_step_problem_h_bound_holds_in_float32(m, n, k, bf16):
         assert H.dtype == F32 and np.all(np.abs(H - P["H_new"]) <= P["H_err"]), how
     if k == 1 and not bf16:
         assert np.max(P["H_err"] / np.abs(P["H_new"])) < 1e-5
+
+
+# ---------------------------------------------------------------------------------------------------------- the BCD projected-gradient step
+# `bcd_pg_problem`: out = max(0, Xm - (S - P) / L) evaluated in numpy float32 with the terms of S forward, reversed and in a random
+# order, each with fused and with separately rounded multiply-adds, on both sides, ends at the constructed answer bit for bit -- with
+# L = 2^6 (the float64 answer) and with L = float32(||G||_F) (the float32 expression); the checker of tests/_bcd.py gives the same bits.
+def _pg32(P, side, order, fused):
+    Xm, G = P["Xm"], P["G"]
+    X, Y = (Xm, G) if side == "w" else (G, Xm)
+    acc = np.zeros(Xm.shape, dtype=F32)
+    for t in order:
+        acc = _fma(X[:, t:t + 1], Y[t:t + 1], acc) if fused else acc + X[:, t:t + 1] * Y[t:t + 1]
+    assert acc.dtype == F32
+    y = Xm - (acc - P["P"]) / F32(P["L"])
+    return np.where(y < 0, F32(0), y)
+
+
+def _butterfly(v):
+    """the xor butterfly of a 64-lane wave over axis 0 in float32: every lane ends with the total"""
+    lanes = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[lanes ^ o]
+    assert v.dtype == F32 and np.array_equal(v[0], v[63])
+    return v[0]
+
+
+@pytest.mark.parametrize("L", [ex.BCD_L, None], ids=["L2^6", "Lnorm"])
+@pytest.mark.parametrize("R,k", ex.BCD_PG_PROOF + ex.BCD_COLSUM)
+def test_bcd_pg_problem_is_exact_in_every_order(R, k, L):
+    import torch
+    from tests._bcd import LH, LW, BcdOracleOps
+    for side in ("w", "h"):
+        P = ex.bcd_pg_problem(R, k, seed=1, L=L, side=side)
+        assert P["Xm"].dtype == P["P"].dtype == P["G"].dtype == F32 and P["L"] == float(F32(P["L"]))
+        assert k == 1 or not np.array_equal(P["G"], P["G"].T)
+        sh = P["shares"]
+        assert sh["clamped"] >= 0.1 and sh["zero"] >= 0.1 and sh["positive"] >= 0.3, sh
+        if L is None:
+            assert P["L"] == float(F32(np.linalg.norm(P["G"].astype(np.float64)))) and np.frexp(P["L"])[0] != 0.5 or k == 1
+        else:                                                    # the float64 answer, from the operands alone
+            X64, P64, G64 = (P[x].astype(np.float64) for x in ("Xm", "P", "G"))
+            S = X64 @ G64 if side == "w" else G64 @ X64
+            assert np.array_equal(np.maximum(0, X64 - (S - P64) / L), P["expected"])
+        for how, order in _orders(k):
+            for fused in (True, False):
+                got = _pg32(P, side, order, fused)
+                assert got.dtype == F32 and np.array_equal(got.astype(np.float64), P["expected"]), (side, how, fused)
+        st = torch.zeros(16, dtype=torch.float64)
+        st[LW if side == "w" else LH] = P["L"]
+        out = torch.full(P["Xm"].shape, -1.0)
+        t = {x: torch.from_numpy(P[x]) for x in ("Xm", "P", "G")}
+        if side == "w":
+            s = torch.full((k,), -1.0)
+            BcdOracleOps().bcd_update_w(t["Xm"], t["P"], t["G"], st, out, s)
+            assert np.array_equal(_bits(s.numpy()), _bits(P["s"]))
+        else:
+            BcdOracleOps().bcd_update_h(t["Xm"], t["P"], t["G"], st, out)
+        assert np.array_equal(_bits(out.numpy()), _bits(P["expected"].astype(F32))), "the checker disagrees (%s side)" % side
+
+
+@pytest.mark.parametrize("R,k", ex.BCD_PG_PROOF + ex.BCD_COLSUM)
+def test_bcd_pg_problem_column_sums_round_once(R, k):
+    """L = 2^6, W side: the partial of every 64-row workgroup is exact in float32 in the butterfly order and as a sequential sum from either
+    end; the float64 sum of the partials is exact in any order; so s is float32(exact sum) -- one rounding"""
+    P = ex.bcd_pg_problem(R, k, seed=1, side="w")
+    y = P["expected"].astype(F32)
+    nb = -(-R // 64)
+    y = np.concatenate([y, np.zeros((nb * 64 - R, k), dtype=F32)]).reshape(nb, 64, k).transpose(1, 0, 2)      # [lane][workgroup][column]
+    exact = y.astype(np.float64).sum(0)
+    for got, how in ((_butterfly(y), "butterfly"), (np.cumsum(y, axis=0, dtype=F32)[-1], "forward"),
+                     (np.cumsum(y[::-1], axis=0, dtype=F32)[-1], "reversed")):
+        assert got.dtype == F32 and np.array_equal(got.astype(np.float64), exact), how
+    total = int(np.rint(exact * 64).astype(np.int64).sum(0).max())
+    assert np.array_equal(exact * 64, np.rint(exact * 64)) and total < 2 ** 53
+    for order in (np.arange(nb), np.arange(nb)[::-1], np.random.RandomState(nb).permutation(nb)):
+        tot = np.cumsum(exact[order], axis=0)[-1]
+        assert np.array_equal(tot, P["expected"].sum(0)) and np.array_equal(_bits(tot.astype(F32)), _bits(P["s"]))
+    if R > 2 ** 14:
+        assert nb > 256 and np.any(exact[256:].sum(0) > 0), "no partial beyond the first 256 carries weight"
+        assert not np.array_equal(exact[:256].sum(0).astype(F32), P["s"])
