@@ -487,6 +487,62 @@ def hals_h_problem(k, n, eps, seed=0):
     return f32(H_old), f32(AtW), f32(G2), Hn
 
 
+def hals_h_step_problem(m, n, k, seed=0):
+    """The H phase of ONE HALS step with W FIXED, exact from a real A and W (eps = 2^-3): where `hals_h_problem` hands the sweep kernel
+    a made-up AtW and G2, here they are W^T A and W^T W of small integers, so on a grid they are what crosses the ranks.  Most rows of
+    W hold one entry in {1, 2}, about 15 % a second entry, a 1, in another column (the off-diagonals of G2), about 3 % are zero;
+    Ht in 0..3; A = W Ht + (a 0/1 noise at 10 %) with 5 % of the entries zeroed; H_old = max(Ht + {-1, 0, 1}, 0) (-1 at 10 %, 0 and 1 at 45 %
+    each) with 5 % zero columns.
+    W^T A and W^T W are non-negative integers, H_old is one, and every row of H[kk] = max(H[kk] + AtW[kk] - G2[kk] . H, eps) is a sum of
+    multiples of 2^-3 whose magnitudes add up to less than 2^21 (asserted): exact in float32 in any order, however AtW and G2 were
+    summed over the ranks.  Asserted as well, so that a shape the design cannot serve raises: every row of the new H has at least
+    10 % unclamped entries, at least 10 % of all entries clamp, every operand is a float32 number, G2 has a nonzero off-diagonal (k >= 2).
+    Returns A, W, H_old (float32) and the expected new H (float64, `hals_h_exact`)."""
+    eps = HALS_EPS_A
+    rs = np.random.RandomState(seed + 31 * m + 7 * n + k + 11)
+    W = np.zeros((m, k))
+    j1 = rs.randint(0, k, size=m)
+    W[np.arange(m), j1] = rs.randint(1, 3, size=m)
+    if k >= 2:
+        second = np.flatnonzero(rs.rand(m) < 0.15)
+        W[second, (j1[second] + 1 + rs.randint(0, k - 1, size=second.size)) % k] = 1
+    W[rs.rand(m) < 0.03] = 0
+    Ht = rs.randint(0, 4, size=(k, n)).astype(np.float64)
+    A = W @ Ht + (rs.rand(m, n) < 0.1)
+    A[rs.rand(m, n) < 0.05] = 0
+    # (an entry that starts BELOW Ht gains about G2[kk][kk] and every later row coupled to it loses G2[kk][j] times that in the same column:
+    #  with -1 as likely as 0 and +1 whole rows clamp at m / k of 30 and more, so -1 is the rare offset)
+    H_old = np.maximum(Ht + rs.choice([-1, 0, 1], size=(k, n), p=[0.1, 0.45, 0.45]), 0.0)
+    H_old[:, rs.rand(n) < 0.05] = 0
+    AtW, G2 = W.T @ A, W.T @ W
+    Hn = hals_h_exact(H_old, AtW, G2, eps)
+    # every value of a row update is a multiple of eps; the sum of the magnitudes of its terms, with the largest |H| the sweep holds
+    Hmax = np.maximum(H_old, Hn)
+    _bound(Hmax + AtW + G2 @ Hmax, eps, np.float32, "the H phase of a W-fixed HALS step")
+    _bound(A.sum(0)[None, :] * W.max(), 1.0, np.float32, "W^T A")
+    clamped = Hn == eps                                             # (the rows below a clamped entry hold multiples of eps, not integers)
+    assert np.array_equal(Hn / eps, np.rint(Hn / eps)) and Hn.min() >= eps
+    assert (1 - clamped.mean(1)).min() >= 0.1, "%d x %d, k = %d: a row of the new H has fewer than 10 %% unclamped entries" % (m, n, k)
+    assert clamped.mean() >= 0.1, "%d x %d, k = %d: fewer than 10 %% of the new H clamp" % (m, n, k)
+    assert k < 2 or G2[~np.eye(k, dtype=bool)].any(), "%d x %d, k = %d: W^T W is diagonal" % (m, n, k)
+    f32 = lambda x: x.astype(np.float32)
+    for x in (A, W, H_old, AtW, G2, Hn):
+        assert np.array_equal(f32(x).astype(np.float64), x)
+    return f32(A), f32(W), f32(H_old), Hn
+
+
+def kl_refs(A, W, H, U):
+    """float64 answers of one MU/KL step on `kl` operands: U H^T, W^T U, rowsum(H), colsum(W), and the quotients of the new W and of
+    the new H with W fixed (the divisors as the kernels form them: one fp32 addition of eps)"""
+    W64, H64 = W.astype(np.float64), H.astype(np.float64)
+    eps32 = np.float32(np.finfo(np.float32).eps)
+    UHt, WtU = U @ H64.T, W64.T @ U
+    rs, cs = H64.sum(1), W64.sum(0)
+    dw = (rs.astype(np.float32) + eps32).astype(np.float64)             # one fp32 addition, as the kernels do
+    dh = (cs.astype(np.float32) + eps32).astype(np.float64)
+    return UHt, WtU, rs, cs, W64 * UHt / dw[None, :], H64 * WtU / dh[:, None]
+
+
 def is_bf16(x):
     """element-wise: the float32 value has no bits below bfloat16's 8-bit significand"""
     return (np.ascontiguousarray(x, dtype=np.float32).view(np.uint32) & 0xFFFF) == 0
@@ -854,6 +910,41 @@ def bcd_pg_problem(R, k, seed=0, L=BCD_L, side="w", shift=True):
     s = out.sum(0).astype(np.float32) if side == "w" else None
     return {"Xm": Xm.astype(np.float32), "P": P.astype(np.float32), "G": G.astype(np.float32), "L": float(Lf), "expected": out, "s": s,
             "shares": shares, "pow2": pow2}
+
+
+# ---------------------------------------------------------------------------------------------------------- exact operands on a grid
+# One update() of nmf_algorithms_1D / _2D per kind on more than one rank (tests/_mp.py run_exact_cases; tests/test_exact_grid_cpu.py with
+# the checker back end, tests/test_gpu_exact_grid.py with the HIP kernels).  GRID_EXACT: (id, grid, shapes, modes, long tier) -- every
+# kind at every shape in every mode, the overlapped H phase for the MU/Frobenius kinds only.  The branch of dist_nmf.py each shape is
+# named after is asserted by tests/test_exact_cpu.py::test_grid_shapes_reach_their_branches.
+GRID_KINDS = ("fro", "fro_bf16", "kl_wfixed", "kl_w", "kl_fixed", "hals", "hals_bf16", "hals_wfixed")
+GRID_OVERLAP_KINDS = ("fro", "fro_bf16")
+_ROW = ("choreography", "overlap4", "native-hosted", "overlap4-native", "direct")
+_COL = ("choreography", "native-hosted", "direct")
+_2D = ("choreography", "native-hosted")
+GRID_EXACT = [
+    ("3x1", (3, 1), [(301, 262, 5), (301, 262, 17)], _ROW, False),          # row blocks 101, 100, 100; chunks of 128, 128, 6 columns
+    ("1x3", (1, 3), [(301, 262, 5), (301, 262, 17)], _COL, False),          # column blocks 88, 87, 87
+    ("2x2-blockable", (2, 2), [(512, 256, 16)], _2D, False),                # h = 64, 64: the [p_r][k][n_h] stack as it is; equal w
+    ("2x2-sliceable", (2, 2), [(515, 272, 33)], _2D, False),                # h = 68, 68: sliced products, no stack; ragged w
+    ("2x2-ragged", (2, 2), [(515, 263, 33)], _2D, False),                   # h = 66, 66 | 66, 65: the transposing route
+    ("2x3", (2, 3), [(241, 199, 33)], _2D, False),                          # ragged, three-member row groups
+    ("3x2", (3, 2), [(301, 197, 5)], _2D, True),
+    ("4x2", (4, 2), [(203, 259, 64)], _2D, True),                           # eight ranks
+    ("4x1", (4, 1), [(1024, 520, 64)], _COL, True),                         # the default overlap settings (one packed exchange at n = 520) and direct
+]
+GRID_CPU_MODES = ("choreography", "overlap4")                               # the modes that need no library
+
+
+def grid_exact_cases(entry, cpu=False, kinds=GRID_KINDS):
+    """[(kind, shape, modes), ...] of an entry of GRID_EXACT; cpu: the modes of the checker back end only"""
+    _, grid, shapes, modes, _ = entry
+    out = []
+    for shape in shapes:
+        for kind in kinds:
+            ms = tuple(mo for mo in modes if (kind in GRID_OVERLAP_KINDS or not mo.startswith("overlap4")) and (not cpu or mo in GRID_CPU_MODES))
+            out.append((kind, shape, ms))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------- per-element comparison

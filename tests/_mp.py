@@ -440,3 +440,210 @@ def run_exact(grid, shape, exchange=None, timeout=240):
     res = collect(procs, q, timeout)
     for rank, err in res:
         assert err is None, "rank %d failed:\n%s" % (rank, err)
+
+
+# ---------------------------------------------------------------------------------------------------------- exact operands on a grid
+# Modes of one exact case: what is set on the params bag before the step (tests/_exact.py, GRID_EXACT lists the modes of every grid)
+EXACT_MODES = {
+    "choreography": {},
+    "overlap4": {"overlap_chunks": 4, "overlap_min_cols": 64},
+    "native-hosted": {"exchange": "native-hosted"},
+    "overlap4-native": {"exchange": "native-hosted", "overlap_chunks": 4, "overlap_min_cols": 64},
+    "direct": {"exchange": "native-hosted", "direct_allreduce": True},
+}
+
+
+_EXACT_CLAMPS = {"fro": (False, True), "fro_bf16": (False, True)}      # the kinds that run with and without the clamp
+
+
+def _exact_problem(kind, shape):
+    """-> (A, W0, H0, w_update, variants, expected): the operands of a case kind on the WHOLE matrix and what the step must give;
+    `variants`: the values of `clamp` the step runs with"""
+    from tests import _exact as ex
+    m, n, k = shape
+    if kind in ("fro", "fro_bf16"):
+        A, W, H, Wn, Hq = ex.fro_step(m, n, k)
+        assert ex.is_bf16(A).all(), "%s: an entry of A is no bfloat16 number" % (shape,)
+        return A, W, H, True, _EXACT_CLAMPS[kind], {"Wn": Wn, "Hq": Hq}
+    if kind in ("kl_wfixed", "kl_w"):
+        A, W, H, U = ex.kl(m, n, k)
+        _, _, _, _, Wq, Hq = ex.kl_refs(A, W, H, U)
+        return A, W, H, kind == "kl_w", (False,), {"Wq": Wq, "Hq": Hq}
+    if kind == "kl_fixed":
+        A, W, H = ex.kl_fixed(m, n, k)
+        return A, W, H, True, (False,), {}
+    if kind in ("hals", "hals_bf16"):
+        P = ex.hals_step_problem(m, n, k, bf16=(kind == "hals_bf16"))
+        if kind == "hals_bf16":
+            assert ex.is_bf16(P["A"]).all()
+        return P["A"], P["W_old"], P["H_old"], True, (False,), P
+    if kind == "hals_wfixed":
+        A, W, H, Hn = ex.hals_h_step_problem(m, n, k)
+        return A, W, H, False, (False,), {"Hn": Hn}
+    raise ValueError("unknown exact case kind %r" % (kind,))
+
+
+def _exact_check(kind, clamp, exp, W0, H0, A, W1, H1, w, h, gathered, what):
+    """the assertions of a case kind on this rank's slices (rows w[0]:w[1] of W, columns h[0]:h[1] of H); `gathered` (kl_w): every rank's
+    (first row, last row + 1, new W slice)"""
+    import numpy as np
+    from tests import _exact as ex
+    eps32 = np.float32(np.finfo(np.float32).eps)
+    (w0, w1), (h0, h1) = w, h
+    ws, hs = "%s: W rows %d:%d" % (what, w0, w1), "%s: H columns %d:%d" % (what, h0, h1)
+    if kind in ("fro", "fro_bf16"):
+        Wn, Hq = (np.maximum(exp["Wn"], eps32), np.maximum(exp["Hq"], eps32)) if clamp else (exp["Wn"], exp["Hq"])
+        ex.assert_ulp(W1, Wn[w0:w1], 0, ws + " (exact)")
+        ex.assert_ulp(H1, Hq[:, h0:h1], 3, hs)
+    elif kind == "kl_wfixed":
+        ex.assert_ulp(W1, W0[w0:w1].astype(np.float64), 0, ws + " (W fixed)")
+        ex.assert_ulp(H1, exp["Hq"][:, h0:h1], 2, hs)                      # kl_update_h: one IEEE division and one product
+    elif kind == "kl_w":
+        ex.assert_ulp(W1, exp["Wq"][w0:w1], 2, ws)                         # kl_update_w: the same
+        # H after W moved: its quotient U is no longer exact -- 1e-5 of each element against the float64 step from the gathered new W
+        Wn = np.zeros(W0.shape)
+        for a, b, blk in gathered:
+            Wn[a:b] = blk
+        H64 = H0.astype(np.float64)
+        Un = A.astype(np.float64) / (Wn @ H64 + float(eps32))
+        Hn = (H64 * (Wn.T @ Un) / (Wn.sum(0) + float(eps32))[:, None])[:, h0:h1]
+        bad = ~(np.abs(H1 - Hn) <= 1e-5 * np.abs(Hn))
+        assert not bad.any(), "%s: off by more than 1e-5 first at %s: got %r, float64 %r" % (
+            hs, tuple(np.argwhere(bad)[0]), H1[tuple(np.argwhere(bad)[0])], Hn[tuple(np.argwhere(bad)[0])])
+    elif kind == "kl_fixed":
+        ex.assert_ulp(W1, W0[w0:w1].astype(np.float64), 0, ws + " (fixed point)")
+        ex.assert_ulp(H1, H0[:, h0:h1].astype(np.float64), 0, hs + " (fixed point)")
+    elif kind in ("hals", "hals_bf16"):
+        ex.assert_ulp(W1, exp["W_new"][w0:w1], 0, ws + " (exact)", tile=(ex.HALS_ROWS, 4))
+        # the H sweep on the new W cannot be exact: the derived forward bound of the generator, which its docstring calls loose from k of about 16 on
+        Hn, He = exp["H_new"][:, h0:h1], exp["H_err"][:, h0:h1]
+        assert np.isfinite(H1).all() and (H1 >= ex.HALS_EPS_A).all(), hs + ": not finite or below eps"
+        bad = np.abs(H1 - Hn) > He
+        assert not bad.any(), "%s: at %s got %r, expected %r within %g" % (
+            hs, tuple(np.argwhere(bad)[0]), H1[tuple(np.argwhere(bad)[0])], Hn[tuple(np.argwhere(bad)[0])], He[tuple(np.argwhere(bad)[0])])
+    elif kind == "hals_wfixed":
+        ex.assert_ulp(W1, W0[w0:w1].astype(np.float64), 0, ws + " (W fixed)")
+        ex.assert_ulp(H1, exp["Hn"][:, h0:h1], 0, hs + " (exact)")
+
+
+def run_exact_cases_rank(rank, world, port, grid, cases, q, use_hip):
+    """Every case of `cases` = [(kind, (m, n, k), modes), ...] in every one of its modes on this rank of ONE process group: one update()
+    of nmf_algorithms_1D / _2D through PyNMF per (case, mode, clamp), this rank's slices against the whole-matrix answer (`_exact_check`).
+    A failed assertion is recorded with rank, case and mode and the loop goes on (the ranks stay in step); anything else ends the rank."""
+    try:
+        import numpy as np
+        import torch.distributed as dist
+        from oracle import nmf_oracle as orc
+        from pydnmfk_amd.dist_comm import MPI_comm
+        from pydnmfk_amd.dist_nmf import nmf_algorithms_1D, nmf_algorithms_2D
+        from pydnmfk_amd.pyDNMF import PyNMF
+        from pydnmfk_amd.utils import determine_block_params, parse
+        from tests import _exact as ex
+
+        torch.set_num_threads(1)
+        if use_hip:
+            torch.cuda.set_device(0)
+            ops = None
+        else:
+            from tests._ops_double import OracleOps
+            ops = OracleOps()
+        os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        p_r, p_c = grid
+        comms = MPI_comm(None, p_r, p_c)
+        kmax = max(shape[2] for _, shape, _ in cases)
+        shared = {}                         # the library's communicators of this process: one hosted, one with the peer regions on top
+        failures = []
+        done = {"steps": 0, "library": 0, "direct": 0, "xsweeps": 0, "downgraded": False}     # what really ran, for the parent to count
+        for kind, shape, modes in cases:
+            m, n, k = shape
+            A, W0, H0, w_update, variants, exp = _exact_problem(kind, shape)
+            hals = kind.startswith("hals")
+            s, e = determine_block_params(rank, (p_r, p_c), A.shape).determine_block_index_range_asymm()
+            w, h = orc.factor_ranges(rank, p_r, p_c, m, n)
+            for mode in modes:
+                extra = EXACT_MODES[mode]
+                if extra and not use_hip and "exchange" in extra:
+                    raise ValueError("mode %r needs the library: not a mode of the CPU tier" % mode)
+                for clamp in variants:
+                    what = "rank %d, %s %d x %d k = %d on %d x %d, mode %s%s" % (rank, kind, m, n, k, p_r, p_c, mode, ", clamp" if clamp else "")
+                    args = parse()
+                    args.comm1, args.comm, args.p_r, args.p_c, args.k = comms.comm, comms, p_r, p_c, k
+                    args.row_comm, args.col_comm = comms.cart_1d_row(), comms.cart_1d_column()
+                    args.itr, args.init, args.verbose, args.prune = 1, "rand", False, False
+                    args.norm, args.method, args.W_update = ("kl" if kind.startswith("kl") else "fro"), ("hals" if hals else "mu"), w_update
+                    if kind.endswith("bf16"):
+                        args.precision = "bfloat16"
+                    for key, val in extra.items():
+                        setattr(args, key, val)
+                    native, direct = "exchange" in extra, bool(extra.get("direct_allreduce"))
+                    if direct:
+                        args.end_k = kmax           # the peer regions are sized once per process: for the largest rank of the list, as an NMFk sweep sizes them
+                    if native and shared.get(direct) is not None:
+                        args._native_comm = shared[direct]
+                    nmf = PyNMF(A[s[0]:e[0] + 1, s[1]:e[1] + 1], factors=[W0[w[0]:w[1]], H0[:, h[0]:h[1]]], params=args, ops=ops)
+                    assert nmf.A_ij.dtype == (torch.bfloat16 if kind.endswith("bf16") else torch.float32), what
+                    if hals:
+                        nmf.params.eps = ex.HALS_EPS_A
+                    nc = shared.get(direct) if native else None
+                    steps0 = nc.steps if nc is not None else 0
+                    sweeps0 = nc.hals_xsweeps() if nc is not None and direct else 0
+                    if nc is not None:
+                        nc.fit_begin()              # (what PyNMF.fit does on every rank before the first step on new data)
+                    if nmf.topo == "2d":
+                        W1, H1 = nmf_algorithms_2D(nmf.A_ij, nmf.W_ij, nmf.H_ij, params=nmf.params, ops=nmf._ops()).update(clamp=clamp)
+                    else:
+                        W1, H1 = nmf_algorithms_1D(nmf.A_ij, nmf.W_i, nmf.H_j, params=nmf.params, ops=nmf._ops()).update(clamp=clamp)
+                    W1, H1 = W1.cpu().numpy(), H1.cpu().numpy()
+                    done["steps"] += 1
+                    gathered = comms.comm.allgather((w[0], w[1], W1)) if kind == "kl_w" else None    # (a collective: before anything can raise)
+                    try:
+                        if native:
+                            import pydnmfk_amd.engine as _eng
+                            nc = shared[direct] = getattr(args, "_native_comm", None)
+                            done["downgraded"] = bool(getattr(_eng, "_downgraded", False))
+                            done["library"] += int(nc is not None and nc.steps == steps0 + 1)
+                            if not getattr(_eng, "_downgraded", False):     # the step really ran inside the library
+                                assert nc is not None and nc.steps == steps0 + 1, "the library's step was not taken (%r)" % (nc,)
+                            if direct:                                      # ... with its world allreduce over the peer regions
+                                assert nc is not None and getattr(nc, "direct_ready", False) and not nc.direct_timed_out(), "no direct allreduce"
+                                done["direct"] += 1
+                                done["xsweeps"] += nc.hals_xsweeps() - sweeps0
+                                if kind in ("hals", "hals_bf16") and p_r > 1 and p_c == 1 and not getattr(_eng, "_downgraded", False):
+                                    # ... and the W sweep as ONE persistent launch across the ranks (csrc/dnmf_hals.h, HalsPeers)
+                                    assert nc.hals_xsweeps() == sweeps0 + 1, "%d cross-rank sweeps" % (nc.hals_xsweeps() - sweeps0)
+                        _exact_check(kind, clamp, exp, W0, H0, A, W1, H1, w, h, gathered, what)
+                    except AssertionError:
+                        failures.append("%s\n%s" % (what, traceback.format_exc()))
+        q.put((rank, done, "\n".join(failures) or None))
+        dist.barrier()
+        for nc in shared.values():
+            if nc is not None:
+                nc.close()
+        dist.destroy_process_group()
+    except Exception:  # noqa: BLE001
+        q.put((rank, None, traceback.format_exc()))
+
+
+def run_exact_cases(grid, cases, use_hip=True, timeout=240):
+    """All of `cases` = [(kind, (m, n, k), modes), ...] on ONE process group of grid[0] x grid[1] ranks (gloo; with `use_hip` every rank on
+    cuda:0 and the HIP kernels, without it the checker back end of tests/_ops_double.py and no GPU): a GPU process takes seconds to
+    start, a step milliseconds.  kinds: `_exact_problem`; modes: EXACT_MODES; what each rank's slice must satisfy: `_exact_check`."""
+    world = grid[0] * grid[1]
+    assert 1 < world <= 8, "at most 8 ranks"
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = free_port()
+    procs = [ctx.Process(target=run_exact_cases_rank, args=(r, world, port, grid, cases, q, use_hip)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = collect(procs, q, timeout)
+    bad = ["rank %d failed:\n%s" % (rank, err) for rank, _, err in sorted(res, key=lambda r: r[0]) if err is not None]
+    assert not bad, "\n".join(bad)
+    # every rank ran every (case, mode, clamp), and every mode that names the library ran inside it (unless the engine fell back
+    # to its launch chains on a shared GPU: run_case_rank)
+    steps = sum(len(modes) * len(_EXACT_CLAMPS.get(kind, (False,))) for kind, _, modes in cases)
+    lib = sum(len([mo for mo in modes if "exchange" in EXACT_MODES[mo]]) * len(_EXACT_CLAMPS.get(kind, (False,))) for kind, _, modes in cases)
+    for rank, done, _ in res:
+        assert done["steps"] == steps and (done["library"] == lib or done["downgraded"]), (rank, done, steps, lib)
+    return [done for _, done, _ in sorted(res, key=lambda r: r[0])]

@@ -68,7 +68,9 @@ class OracleOps:
             w[:, kk - 1] /= np.float32(np.sqrt(float(ss2[kk - 1])))
         t = w[:, kk] * g[kk, kk] + _n(AH)[:, kk] - w.dot(g[:, kk])
         w[:, kk] = np.maximum(t, np.float32(eps))
-        ss2[kk] = float(np.linalg.norm(w[:, kk], ord=2)) ** 2
+        # the float64 sum of squares, as the HIP column kernel forms it (the reference squares a rank's float32 norm again, utils.py:388-391:
+        # a rounding per rank that the exact operands of tests/_exact.py would see on a grid)
+        ss2[kk] = float(np.sum(w[:, kk].astype(np.float64) ** 2))
 
     def hals_w_scale(self, W, col, ss2):
         if float(ss2[col]) > 0:

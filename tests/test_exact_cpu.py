@@ -608,3 +608,117 @@ def test_bcd_pg_problem_column_sums_round_once(R, k):
     if R > 2 ** 14:
         assert nb > 256 and np.any(exact[256:].sum(0) > 0), "no partial beyond the first 256 carries weight"
         assert not np.array_equal(exact[:256].sum(0).astype(F32), P["s"])
+
+
+# ---------------------------------------------------------------------------------------------------------- exact operands on a grid
+GRID_SHAPES = sorted({shape for e in ex.GRID_EXACT for shape in e[2]})
+
+
+def _part(total, p):
+    """the partition rule (utils.py:36-41): the first total % p members hold one item more"""
+    return [total // p + (1 if q < total % p else 0) for q in range(p)]
+
+
+def _sum32(terms, order):
+    """the float32 sum of a list of equally shaped float32 arrays, one after the other in the given order"""
+    idx = {"forward": np.arange(len(terms)), "reversed": np.arange(len(terms))[::-1]}.get(order)
+    if idx is None:
+        idx = np.random.RandomState(order).permutation(len(terms))
+    acc = np.zeros_like(terms[0])
+    for t in idx:
+        acc = (acc + terms[t]).astype(np.float32)
+    return acc
+
+
+@pytest.mark.parametrize("m,n,k", GRID_SHAPES)
+def test_hals_h_step_problem_is_exact_in_any_order(m, n, k):
+    """`hals_h_step_problem` at every shape of the grid tier: W^T A and W^T W summed in float32 as p partial sums over row blocks (p = 1..4,
+    the partition rule), the partials and the terms of every row update forward, reversed and in two random orders -- every evaluation
+    equals the float64 sweep bit for bit"""
+    A, W, H_old, Hn = ex.hals_h_step_problem(m, n, k)
+    eps = np.float32(ex.HALS_EPS_A)
+    assert A.dtype == W.dtype == H_old.dtype == np.float32 and A.min() >= 0 and W.min() >= 0 and H_old.min() >= 0
+    assert np.array_equal(ex.hals_h_exact(H_old, W.T.astype(np.float64) @ A, W.T.astype(np.float64) @ W, ex.HALS_EPS_A), Hn)
+    for p in (1, 2, 3, 4):
+        cuts = np.cumsum([0] + _part(m, p))
+        for order in ORDERS:
+            AtW = _sum32([_mm(W[a:b].T.copy(), A[a:b], order) for a, b in zip(cuts[:-1], cuts[1:])], order)
+            G2 = _sum32([_mm(W[a:b].T.copy(), W[a:b], order) for a, b in zip(cuts[:-1], cuts[1:])], order)
+            H = H_old.copy()
+            for kk in range(k):
+                t = _sum32([H[kk], AtW[kk]] + [(-G2[kk, j] * H[j]).astype(np.float32) for j in range(k)], order)
+                H[kk] = np.maximum(t, eps)
+            assert np.array_equal(H.astype(np.float64), Hn), "p = %d, order %s: the float32 H phase is not the float64 sweep" % (p, order)
+
+
+class _Rank:
+    def __init__(self, rank):
+        self.rank, self.size = rank, 1
+
+
+def _grid_branches(grid, shape, extra=None):
+    """per rank of the grid: what the choreography of pydnmfk_amd/dist_nmf.py decides for the shape -- its own objects, built on empty blocks"""
+    import torch
+    from pydnmfk_amd.dist_nmf import nmf_algorithms_1D, nmf_algorithms_2D
+    from pydnmfk_amd.utils import determine_block_params, parse
+    from tests._ops_double import OracleOps
+    (p_r, p_c), (m, n, k) = grid, shape
+    out = []
+    for rank in range(p_r * p_c):
+        s, e = determine_block_params(rank, (p_r, p_c), (m, n)).determine_block_index_range_asymm()
+        m_l, n_l = e[0] + 1 - s[0], e[1] + 1 - s[1]
+        p = parse()
+        p.m, p.n, p.p_r, p.p_c, p.k, p.eps, p.W_update, p.norm, p.method = m, n, p_r, p_c, k, 1e-7, True, "fro", "mu"
+        p.comm1 = p.row_comm = p.col_comm = p.comm = _Rank(rank)
+        for key, val in (extra or {}).items():
+            setattr(p, key, val)
+        A = torch.empty(m_l, n_l)
+        if p_r > 1 and p_c > 1:
+            alg = nmf_algorithms_2D(A, torch.empty(1, k), torch.empty(k, 1), params=p, ops=OracleOps())
+            hc, wc = alg.h_counts, alg.w_counts
+            assert hc == _part(n_l, p_r) and wc == _part(m_l, p_c)
+            blockable = alg._h_blockable("aht_hblocks") and alg._h_blockable("kl_uht_hblocks")
+            sliceable = len(set(hc)) == 1 and hc[0] % 4 == 0                # (_product_scattered_to_H, the fp32 operator set)
+            out.append(dict(m_l=m_l, n_l=n_l, h=hc, w=wc, blockable=blockable, sliceable=sliceable, w_equal=len(set(wc)) == 1))
+        else:
+            alg = nmf_algorithms_1D(A, torch.empty(m_l if p_c == 1 else m, k), torch.empty(k, n_l if p_r == 1 else n), params=p, ops=OracleOps())
+            nch = alg._overlap_chunks(n_l)
+            cw = -(-(-(-n_l // nch)) // 64) * 64
+            out.append(dict(m_l=m_l, n_l=n_l, nch=nch, chunks=[min(cw, n_l - c0) for c0 in range(0, n_l, cw)] if nch > 1 else [n_l]))
+    return out
+
+
+def test_grid_shapes_reach_their_branches():
+    """every (grid, shape) of GRID_EXACT takes the branch of the choreography it is named after: the stacked [p_r][k][n_h] blocks with
+    the KL re-blocking copies, the sliced products without the stack, the transposing route; equal and ragged row counts of gather_W;
+    the chunk widths of the overlapped H phase"""
+    from tests._mp import EXACT_MODES
+    table = {e[0]: e for e in ex.GRID_EXACT}
+    b = _grid_branches((2, 2), (512, 256, 16))
+    assert all(r["blockable"] and r["sliceable"] and r["w_equal"] and r["h"] == [64, 64] for r in b)
+    b = _grid_branches((2, 2), (515, 272, 33))
+    assert all(r["sliceable"] and not r["blockable"] and r["h"] == [68, 68] for r in b) and not all(r["w_equal"] for r in b)
+    b = _grid_branches((2, 2), (515, 263, 33))
+    assert not any(r["sliceable"] or r["blockable"] for r in b) and sorted(r["h"] for r in b) == [[66, 65], [66, 65], [66, 66], [66, 66]]
+    b = _grid_branches((2, 3), (241, 199, 33))
+    assert not any(r["sliceable"] for r in b) and [67, 66, 66] == [b[j]["n_l"] for j in range(3)] and {tuple(r["w"]) for r in b} == {(41, 40, 40), (40, 40, 40)}
+    assert {tuple(r["h"]) for r in b} == {(34, 33), (33, 33)}
+    for gid in ("3x2", "4x2"):
+        _, grid, (shape,), _, _ = table[gid]
+        b = _grid_branches(grid, shape)
+        assert not any(r["sliceable"] for r in b) and any(len(set(r["h"])) > 1 for r in b) and any(not r["w_equal"] for r in b)
+    # row grids: 101, 100, 100 rows; with overlap_chunks = 4 from 64 columns on, n = 262 goes out as chunks of 128, 128 and 6 columns
+    b = _grid_branches((3, 1), (301, 262, 5), EXACT_MODES["overlap4"])
+    assert [r["m_l"] for r in b] == [101, 100, 100] and all(r["nch"] == 4 and r["chunks"] == [128, 128, 6] for r in b)
+    assert all(r["chunks"] == [262] for r in _grid_branches((3, 1), (301, 262, 5)))           # the default: one packed exchange
+    b = _grid_branches((4, 1), (1024, 520, 64))
+    assert [r["m_l"] for r in b] == [256] * 4 and all(r["chunks"] == [520] for r in b)
+    b = _grid_branches((1, 3), (301, 262, 17))
+    assert [r["n_l"] for r in b] == [88, 87, 87] and all(r["chunks"] == [r["n_l"]] for r in b)
+    # every kind of every grid has its modes, the overlapped H phase only where it exists
+    for e in ex.GRID_EXACT:
+        cases = ex.grid_exact_cases(e)
+        assert len(cases) == len(e[2]) * len(ex.GRID_KINDS) and e[1][0] * e[1][1] <= 8
+        for kind, shape, modes in cases:
+            assert modes and all(mo in EXACT_MODES for mo in modes)
+            assert any(mo.startswith("overlap4") for mo in modes) == (e[1][1] == 1 and e[0] != "4x1" and kind in ex.GRID_OVERLAP_KINDS)

@@ -190,15 +190,6 @@ def test_mu_updates(env, m, n, k, aligned):
 
 
 # ------------------------------------------------------------------------------------------------------------- KL
-def _kl_refs(A, W, H, U):
-    W64, H64 = W.astype(np.float64), H.astype(np.float64)
-    UHt, WtU = U @ H64.T, W64.T @ U
-    rs, cs = H64.sum(1), W64.sum(0)
-    dw = (rs.astype(np.float32) + EPS32).astype(np.float64)             # one fp32 addition, as the kernels do
-    dh = (cs.astype(np.float32) + EPS32).astype(np.float64)
-    return UHt, WtU, rs, cs, W64 * UHt / dw[None, :], H64 * WtU / dh[:, None]
-
-
 @pytest.mark.parametrize("m,n,k,aligned", PRIM)
 def test_kl(env, m, n, k, aligned):
     """kl_uht, kl_wtu, rowsum, colsum: exact; kl_update_w / kl_update_h: c = 2; mu_kl_step: W c = 3, H (from the kernel's new W,
@@ -206,7 +197,7 @@ def test_kl(env, m, n, k, aligned):
     engine, _ = env
     ops = engine.HIP_OPS
     A, W, H, U = ex.kl(m, n, k)
-    UHt, WtU, rs, cs, Wq, Hq = _kl_refs(A, W, H, U)
+    UHt, WtU, rs, cs, Wq, Hq = ex.kl_refs(A, W, H, U)
     Av, Wv, Hv = _P(A, aligned), _P(W, aligned), _P(H, aligned)
     o = _out(m, k, aligned)
     ops.kl_uht(Av.view, Wv.view, Hv.view, EPS, o.view)
@@ -434,7 +425,7 @@ def test_fit_itr1(env, m, n, k, B):
     Ap.check("A")
     w3, h3 = Wp.check("fit W"), Hp.check("fit H")
     for b, (A, W, H, U) in enumerate(probs):
-        Hq = _kl_refs(A, W, H, U)[5]
+        Hq = ex.kl_refs(A, W, H, U)[5]
         _assert_normalized(w3[b], h3[b], np.maximum(W.astype(np.float64), EPS32), np.maximum(Hq, EPS32), 6, "mu-kl fit [%d]" % b)
 
 
@@ -462,7 +453,7 @@ def test_bf16x6_products(env, m, n, k, aligned):
         ops.aht_update_w(Av.view, _P(H, aligned).view, G, Wv.view, EPS)
         ex.assert_ulp(Wv.check("bf16x6 aht_update_w"), _mu_ref(W64, A64 @ H64.T, W64 @ (H64 @ H64.T)), 3, "bf16x6 aht_update_w %s" % adt)
     A, W, H, U = ex.kl(m, n, k)
-    UHt, WtU, _, _, _, Hq = _kl_refs(A, W, H, U)
+    UHt, WtU, _, _, _, Hq = ex.kl_refs(A, W, H, U)
     Av, Wv, Hv = _P(A, aligned), _P(W, aligned), _P(H, aligned)
     o = _out(m, k, aligned)
     ops.kl_uht(Av.view, Wv.view, Hv.view, EPS, o.view)
