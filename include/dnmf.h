@@ -734,6 +734,26 @@ int dnmf_masked_resid_sqnorm(const float* A, long m, long n, long lda, const flo
                              double* sq, void* stream);
 /* out[0] = ||P_Omega(A)||_F^2, out[1] = |Omega| (the count of observed entries), both float64 */
 int dnmf_masked_sqnorm(const float* A, long m, long n, long lda, double* out, void* stream);
+/* num[c] = sum_{i: (i,c) in Omega} (a - S)^2, den[c] = sum_{i: (i,c) in Omega} a^2 (float64, c < n) over this rank's rows: the pieces of
+ * PyNMF.column_err (pyDNMF.py:221-239) with both sums over the observed positions.  The S tile stays in MFMA accumulators; fp32 per
+ * 16-row tile, float64 from there on.  Every row chunk leaves one float64 pair per column in `ws`; an ending adds them in chunk order
+ * and STORES num, den (nothing is accumulated into them, no atomics: two calls are bit-identical).  A column without an observation
+ * gives exactly (0, 0).  1 <= k <= DNMF_TUNED_MAX_K; any shape and any leading dimensions.
+ * `ws`: dnmf_masked_column_err_ws_bytes(m, n, k) bytes, 16-byte aligned (0: bad shape or rank). */
+size_t dnmf_masked_column_err_ws_bytes(long m, long n, int k);
+/* Its launch plan, host arithmetic only: out = {rowblks_per_chunk, nchunks, ncolblk} -- nchunks chunks of rowblks_per_chunk 32-row
+ * blocks (the last chunk holds the rest), ncolblk blocks of 128 columns; the slab takes nchunks * 2 * ncolblk * 128 doubles. */
+int dnmf_masked_column_err_plan(long m, long n, int k, long out[3]);
+int dnmf_masked_column_err(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, double* num,
+                           double* den, void* ws, size_t ws_bytes, void* stream);
+/* A whole masked MU fit on one rank as ONE call (pyDNMF.py:138-182 over the observed positions): `itr` steps of dnmf_masked_update_w
+ * (iff w_update) and dnmf_masked_update_h with the clamp of H and then of W at the steps i % 10 == 0 (:155-157, :170-172),
+ * normalize_features (:185-194) and sq_out = {||P_Omega(A - W H)||^2, ||P_Omega(A)||^2} (:205-218; the caller takes the square roots,
+ * as after dnmf_mu_fro_fit).  Host sequencing of the launches above on `stream`: no host synchronisation inside.  One problem per call.
+ * `ws`: dnmf_masked_ws_bytes_fit(m, n, k) bytes, 16-byte aligned (0: bad shape or rank). */
+size_t dnmf_masked_ws_bytes_fit(long m, long n, int k);
+int dnmf_masked_mu_fit(const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int kl,
+                       int w_update, int itr, double* sq_out, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- measurement aid (no counterpart in the reference) ----
  * Which shader clock does the GPU hold right now?  Launches ONE wave on `stream` that writes `n` pairs {s_memtime (shader

@@ -285,6 +285,68 @@ __global__ __launch_bounds__(256) void masked_resid_kernel(NnArgs p) {
     block_atomic_sum(total, p.out);
 }
 
+// ---- per-column error over Omega (PyNMF.column_err, pyDNMF.py:221-239 with both sums over the observed positions): colerr_kernel of
+// csrc/dnmf_nn.h with the select above.  A wave owns a 128-column block and a chunk of 32-row blocks; fp32 per 16-row tile, float64 from
+// there on.  The chunk's pair goes to its own slab row, P[chunk][half][ldc] with ldc = ncolblk * 128 (every store is inside the slab);
+// masked_colerr_reduce_kernel adds the rows in chunk order and STORES num[c], den[c]: no atomics, nothing accumulated into the outputs.
+template <int KT, bool FAST>
+__global__ __launch_bounds__(256) void masked_colerr_kernel(NnArgs p, double* __restrict__ P, long ldc, long rowblks_per_chunk) {
+    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long gw = (long)blockIdx.x * 4 + wid;
+    const long nchunks = cdiv(p.nrowblk, rowblks_per_chunk);
+    if (gw >= nchunks * p.ncolblk) return;
+    const long chunk = gw / p.ncolblk, colblk = gw % p.ncolblk;
+    const long col0 = colblk * 128;
+    double dn[4] = {0.0, 0.0, 0.0, 0.0}, dd[4] = {0.0, 0.0, 0.0, 0.0};
+    long rb1 = (chunk + 1) * rowblks_per_chunk;
+    if (rb1 > p.nrowblk) rb1 = p.nrowblk;
+    for (long rb = chunk * rowblks_per_chunk; rb < rb1; ++rb) {
+        const long row0 = rb * 32;
+        f32x16 acc[4];
+        nn_tile<KT, 4, FAST, false>(acc, p.W, p.ldw, p.m, p.k, p.H, p.ldh, p.n, row0, col0, li, h);
+        float pn[4] = {0.f, 0.f, 0.f, 0.f}, pd[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const long row = row0 + crow(r, h);
+            float a[4];
+            load_vec<4, FAST>(a, p.A + row * p.lda, col0 + 4 * li, p.n, row < p.m);
+#pragma unroll
+            for (int ne = 0; ne < 4; ++ne) {
+                // outside the block a = 0 and acc = 0 (zero-filled operands): an observed zero that is reproduced exactly
+                const bool obs = a[ne] == a[ne];
+                const float d = obs ? a[ne] - acc[ne][r] : 0.f;
+                const float ao = obs ? a[ne] : 0.f;
+                pn[ne] = fmaf(d, d, pn[ne]);
+                pd[ne] = fmaf(ao, ao, pd[ne]);
+            }
+        }
+#pragma unroll
+        for (int ne = 0; ne < 4; ++ne) { dn[ne] += (double)pn[ne]; dd[ne] += (double)pd[ne]; }
+    }
+    double* Pn = P + chunk * 2 * ldc + col0 + 4 * li;
+    double* Pd = Pn + ldc;
+#pragma unroll
+    for (int ne = 0; ne < 4; ++ne) {
+        dn[ne] += __shfl_xor(dn[ne], 32, 64);
+        dd[ne] += __shfl_xor(dd[ne], 32, 64);
+        if (h == 0) { Pn[ne] = dn[ne]; Pd[ne] = dd[ne]; }
+    }
+}
+
+__global__ __launch_bounds__(256) void masked_colerr_reduce_kernel(const double* __restrict__ P, long ldc, long nchunks, long n,
+                                                                   double* __restrict__ num, double* __restrict__ den) {
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long)gridDim.x * 256) {
+        double a = P[c], b = P[ldc + c];
+        for (long s = 1; s < nchunks; ++s) {
+            a += P[s * 2 * ldc + c];
+            b += P[s * 2 * ldc + ldc + c];
+        }
+        num[c] = a;
+        den[c] = b;
+    }
+}
+
 // out[0] = sum over Omega of a^2, out[1] = |Omega| (both float64; the count is exact below 2^53)
 __global__ __launch_bounds__(256) void masked_sqnorm_kernel(const float* __restrict__ A, long m, long n, long lda, double* __restrict__ out) {
     double s = 0.0, cnt = 0.0;

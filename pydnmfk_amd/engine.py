@@ -951,9 +951,10 @@ class HipMaskedOps(HipOps):
     'nan'`): the operations that touch A are the masked ones of csrc/dnmf_masked.h (`dnmf_masked_*`: S = W H tiles in MFMA accumulators,
     one compare and two selects per element, two second products) -- `masked_aht_pair` / `masked_wta_pair` (numerator and denominator
     over the observed positions as one contiguous [num | den] buffer for ONE allreduce), `ratio_update` after it, `masked_update_w` /
-    `masked_update_h` where nothing crosses ranks, `resid_sqnorm` and `sqnorm` over the observed positions.  Everything that never
-    sees A -- clamps, normalisation, scaling -- is the fp32 code of HipOps.  Every dense operation that would read A as numbers (the
-    fused local steps, the whole fits, the plain products) refuses the block: those kernels would consume the NaNs."""
+    `masked_update_h` where nothing crosses ranks, `resid_sqnorm` and `sqnorm` over the observed positions, `column_err_sums` (the per-column
+    error of an NMFk sweep, `masked_nmfk`) and `fit` (a whole fit on one rank as one library call).  Everything that never sees A --
+    clamps, normalisation, scaling -- is the fp32 code of HipOps.  Every dense operation that would read A as numbers (the fused local
+    steps, the plain products) refuses the block: those kernels would consume the NaNs."""
 
     name = "hip-masked"
     kl_uht_hblocks = None
@@ -1044,6 +1045,52 @@ class HipMaskedOps(HipOps):
                                            int(W.shape[1]), out.data_ptr(), _stream()))
         return out
 
+    # ---- NMFk on a NaN-marked block: the per-column error (the perturbed copy is HipOps.perturb_uniform on the raw tensor: NaN stays NaN)
+    masked_nmfk = True
+
+    def column_err_sums(self, A, W, H):
+        """(num, den) per column over this rank's rows, float64 [n]: sum (A - W H)^2 and sum A^2 over the OBSERVED positions of a
+        MaskedDenseBlock (dnmf_masked_column_err: stored, not accumulated -- two calls are bit-identical; a column without an observation
+        gives (0, 0)).  A plain tensor takes the dense kernel."""
+        if not self._blk(A):
+            return super().column_err_sums(A, W, H)
+        T = _req(A.tensor, "A"); _req(W, "W"); _req(H, "H")
+        m, n = T.shape
+        k = W.shape[1]
+        if tuple(W.shape) != (m, k) or tuple(H.shape) != (k, n):
+            raise ValueError("masked column_err_sums: shapes A %s, W %s, H %s do not match" % (tuple(T.shape), tuple(W.shape), tuple(H.shape)))
+        nbytes = lib.dnmf_masked_column_err_ws_bytes(int(m), int(n), int(k))
+        if nbytes == 0:
+            raise NotImplementedError("missing='nan' with k = %d: the masked dense kernels serve 1 <= k <= 128" % k)
+        ws = _scratch(nbytes, T.device)
+        out = torch.empty(2, n, dtype=torch.float64, device=T.device)
+        check(lib.dnmf_masked_column_err(T.data_ptr(), m, n, _ld(T), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), int(k), out[0].data_ptr(),
+                                         out[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        return out[0], out[1]
+
+    def fit(self, method, norm, A, W, H, eps, w_update, itr, column_sweep=False):
+        """A MaskedDenseBlock: `itr` masked MU steps (clamps after the steps i % 10 == 0), normalize_features and the squared norms of
+        relative_err over the observed positions in ONE library call (dnmf_masked_mu_fit: the launches of the step loop in its order).
+        One problem; W, H are updated in place; returns the device tensor [1][2].  A plain tensor takes the inherited whole fits."""
+        if not self._blk(A):
+            return super().fit(method, norm, A, W, H, eps, w_update, itr, column_sweep=column_sweep)
+        method, norm = str(method).lower(), str(norm).lower()
+        if method != "mu" or norm not in ("fro", "kl"):
+            raise NotImplementedError("missing='nan' is provided for method 'mu' (fro / kl) only, not for '%s' / '%s'" % (method, norm))
+        T = _req(A.tensor, "A"); _req(W, "W"); _req(H, "H")
+        m, n = T.shape
+        k = W.shape[1]
+        if tuple(W.shape) != (m, k) or tuple(H.shape) != (k, n):
+            raise ValueError("masked fit: shapes A %s, W %s, H %s do not match" % (tuple(T.shape), tuple(W.shape), tuple(H.shape)))
+        nbytes = lib.dnmf_masked_ws_bytes_fit(int(m), int(n), int(k))
+        if nbytes == 0:
+            raise NotImplementedError("missing='nan' with k = %d: the masked dense kernels serve 1 <= k <= 128" % k)
+        ws = _scratch(nbytes, T.device)
+        sq = torch.empty(1, 2, dtype=torch.float64, device=T.device)
+        check(lib.dnmf_masked_mu_fit(T.data_ptr(), m, n, _ld(T), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), int(k), float(eps),
+                                     int(norm == "kl"), int(bool(w_update)), int(itr), sq.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        return sq
+
     def _refuse(self, what, A):
         if self._blk(A):
             raise NotImplementedError("%s is not provided under missing='nan': it would read the NaNs of the block as data (the "
@@ -1061,16 +1108,10 @@ def _masked_refusal(name, what):
 for _name, _what in (("aht", "the product A H^T"), ("wta", "the product W^T A"), ("wta_gram", "the product W^T A"),
                      ("aht_update_w", "the fused A H^T update"), ("mu_fro_step", "the fused local MU/FRO step"),
                      ("mu_kl_step", "the fused local MU/KL step"), ("kl_uht", "the dense KL product U H^T"),
-                     ("kl_wtu", "the dense KL product W^T U"), ("column_err_sums", "the per-column error (NMFk)")):
+                     ("kl_wtu", "the dense KL product W^T U")):
     setattr(HipMaskedOps, _name, _masked_refusal(_name, _what))
 
 
-def _masked_fit(self, method, norm, A, *args, **kwargs):
-    self._refuse("a whole-fit entry point", A)
-    return HipOps.fit(self, method, norm, A, *args, **kwargs)
-
-
-HipMaskedOps.fit = _masked_fit
 HIP_MASKED_OPS = HipMaskedOps()
 
 

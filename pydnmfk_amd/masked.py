@@ -7,7 +7,8 @@ update choreography (dist_nmf.py) dispatches on the block: `dist_nmf._is_masked`
 `engine.ops_for` hands out the `hip-masked` operator set, whose operations that touch A are the masked ones.
 
 Objective, MU rules (fro / kl) and the reported error run over the observed positions only ("Dense data with
-missing entries"): method 'mu', one rank and the two 1D grids, 1 <= k <= 128.
+missing entries"): method 'mu', one rank and the two 1D grids, 1 <= k <= 128.  `PyNMFk` sweeps such data too: it keeps the raw array,
+perturbs it (NaN stays NaN) and lets every `PyNMF` wrap its copy in a block ("NMFk over a NaN-marked block").
 """
 import torch
 

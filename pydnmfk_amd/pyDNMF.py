@@ -18,7 +18,8 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
   * sparse data (pydnmfk_amd.sparse) with `params.missing = 'unstored'`: an unstored entry is NOT OBSERVED instead of zero -- objective,
     MU rules (fro / kl) and the reported error run over the stored positions only (1D grids, method 'mu'; DESIGN.md "Sparse data");
   * dense float32 data with `params.missing = 'nan'`: an entry is observed iff it is not NaN (a zero is an observation) -- the same
-    masked objective, rules and error on the matrix cores (pydnmfk_amd.masked, csrc/dnmf_masked.h; method 'mu', 1D grids, k <= 128).
+    masked objective, rules and error on the matrix cores (pydnmfk_amd.masked, csrc/dnmf_masked.h; method 'mu', 1D grids, k <= 128;
+    on one rank the whole fit is one library call, dnmf_masked_mu_fit; `column_err` runs over the observed positions).
     Without `params.missing` dense data are not scanned for NaN;
   * `prune=True` (the reference's default when the attribute is absent) drops all-zero rows / columns before the
     iterations and scatters the factors back afterwards.  numpy callers get float64 factors back in that case, exactly
@@ -357,8 +358,13 @@ class PyNMF:
     def _whole_fit_ok(self, ops):
         """One rank, the product's own fp32-MFMA operator set, a method / norm pair the library has a whole-fit entry point for
         (anything else keeps the step loop, which raises the reference's messages for invalid pairs).  `params.fit_loop =
-        'python'` keeps the step loop (A/B runs, tests of the per-step API)."""
-        return (not self._sparse and not self._masked_dense and self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") in ("hip", "hip-f64") and hasattr(ops, "fit")
+        'python'` keeps the step loop (A/B runs, tests of the per-step API).  A NaN-marked block (missing='nan') has one with the
+        'hip-masked' set: dnmf_masked_mu_fit, the launches of the step loop in its order (one problem per call: never batched)."""
+        if self._masked_dense:
+            return (self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") == "hip-masked" and hasattr(ops, "fit")
+                    and str(self.method).lower() == "mu" and str(self.norm).lower() in ("fro", "kl")
+                    and getattr(self.params, "fit_loop", None) != "python" and not getattr(self.params, "native_always", False))
+        return (not self._sparse and self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") in ("hip", "hip-f64") and hasattr(ops, "fit")
                 and not (getattr(ops, "name", "") == "hip-f64" and self.k > 128)
                 and (str(self.method).lower(), str(self.norm).lower()) in _NATIVE_FITS
                 and not (str(self.method).lower() == "bcd" and (getattr(ops, "name", "") != "hip" or self.a_dtype != torch.float32))
@@ -417,7 +423,7 @@ class PyNMF:
         f0 = fits[0] if fits else None
 
         def same(f):
-            return (f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
+            return (not f._masked_dense and f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
                     and f.A_ij.dtype == f0.A_ij.dtype and f.A_ij.device == f0.A_ij.device and f.W_i.shape == f0.W_i.shape
                     and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k) ==
                     (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k))

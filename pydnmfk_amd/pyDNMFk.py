@@ -11,6 +11,8 @@ Differences: statistics are kept in memory for the p-value analysis (and written
 h5py exists, else npz); no plots are drawn (plot_results is out of scope).  `params.hall_layout = 'aligned'` (not the
 default) stacks the perturbations' H matrices as Hall[:, :, p] = H_p; the default 'reference' reproduces the reference's
 vstack + C-order reshape (pyDNMFk.py:236-237), whose fibres mix perturbations -- it only seeds the regression fit.
+Sparse input is swept as a SparseBlock (`SparseSweep`); dense float32 input with `params.missing = 'nan'` is swept as it is, NaN = not
+observed: the raw array is kept, every perturbed copy keeps its NaNs, and the per-column error runs over the observed positions.
 """
 import os
 
@@ -29,10 +31,16 @@ class sample:
     'poisson': Poisson(X) (:47-49).  numpy input uses the process-global numpy RNG seeded with `seed`, i.e. the
     reference's exact stream (and the `PyNMF` rand init that follows continues that stream, as in the reference);
     CUDA tensors are perturbed on the device with a torch generator seeded the same way (same distribution,
-    different stream)."""
+    different stream).
 
-    def __init__(self, data, noise_var, method, seed=None, out=None, sparse=None):
+    A NaN-marked array (`missing='nan'`): a NaN entry stays NaN and an observed entry gets exactly the value the zero-filled array
+    gets.  'uniform' needs nothing for that -- the multiplication keeps NaN, on the host and in dnmf_perturb_uniform (both of its
+    kernels only multiply) --; 'poisson' draws from the zero-filled rates and puts NaN back, so no NaN rate reaches a generator, the
+    generators are consumed as on the dense path, and a draw of 0 at an observed position is an observed zero."""
+
+    def __init__(self, data, noise_var, method, seed=None, out=None, sparse=None, missing=None):
         self.X = data
+        self.missing = missing
         self.out = out          # optional destination of the perturbed copy (a slice of the stack an NMFk batch is fitted from)
         # a SparseBlock: what the sweep keeps about it between the perturbations (SparseSweep; built here when the caller has none)
         self.sparse = sparse if sparse is not None or not getattr(data, "is_sparse_block", False) else SparseSweep(data)
@@ -67,10 +75,19 @@ class sample:
         if self.sparse is not None:
             self.X_per = self.sparse.poisson(self.seed)
             return
+        nan = self.missing == "nan"
         if isinstance(self.X, torch.Tensor):
             g = torch.Generator(device=self.X.device)
             g.manual_seed(0 if self.seed is None else int(self.seed))
-            self.X_per = torch.poisson(self.X.float(), generator=g).to(self.X.dtype)
+            gaps = torch.isnan(self.X) if nan else None
+            rates = torch.where(gaps, torch.zeros_like(self.X), self.X) if nan else self.X
+            self.X_per = torch.poisson(rates.float(), generator=g).to(self.X.dtype)
+            if nan:
+                self.X_per[gaps] = float("nan")
+        elif nan:
+            gaps = np.isnan(self.X)
+            self.X_per = np.random.poisson(np.where(gaps, 0, self.X)).astype(self.X.dtype)
+            self.X_per[gaps] = np.nan
         else:
             self.X_per = np.random.poisson(self.X).astype(self.X.dtype)
 
@@ -154,9 +171,18 @@ class PyNMFk:
     def __init__(self, A_ij, factors=None, params=None, ops=None):
         from .sparse import is_sparse_input
         self._sparse = is_sparse_input(A_ij)
-        if getattr(params, "missing", None) == "nan" and not self._sparse:
-            raise NotImplementedError("PyNMFk with missing='nan' is not provided: rank estimation over NaN-marked data needs a masked "
-                                      "per-column error (PyNMF factorises such data at a given k)")
+        self._masked = getattr(params, "missing", None) == "nan" and not self._sparse
+        if self._masked:
+            # as for a sparse block, the sweep touches A outside PyNMF.fit in the perturbed copy (NaN stays NaN through the
+            # multiplication) and in the per-column error, which must run over the observed positions
+            if ops is None:
+                from .engine import HIP_MASKED_OPS as opset
+            else:
+                opset = ops
+            if not (getattr(opset, "masked_nmfk", False) and hasattr(opset, "column_err_sums")):
+                raise NotImplementedError("PyNMFk with missing='nan' is not provided by operator set %r: rank estimation over NaN-marked "
+                                          "data needs a masked per-column error (PyNMF factorises such data at a given k)"
+                                          % (getattr(opset, "name", type(opset).__name__),))
         if self._sparse:
             # the sweep touches A outside PyNMF.fit in two operations: the perturbed copy and the per-column error
             if ops is None:
@@ -224,6 +250,24 @@ class PyNMFk:
         self.sweep = None
         if self._sparse:
             self._sparse_setup(A_ij)
+        if self._masked:
+            self._masked_setup(A_ij)
+
+    def _masked_setup(self, A_ij):
+        """missing='nan': the raw array stays `self.A_ij` (every PyNMF wraps its perturbed copy in a MaskedDenseBlock itself); what PyNMF
+        refuses under missing='nan' is refused here, at construction, in its words."""
+        PyNMF._missing_checks(A_ij, self.params, False)          # method, storage and data type, gemm, 2D grid, nnsvd
+        if var_init(self.params, 'prune', default=True):
+            raise NotImplementedError("missing='nan' with prune=True is not provided (pruning drops all-ZERO rows and columns; under "
+                                      "missing='nan' a row without an observation keeps its place and its factor row goes to zero): set "
+                                      "params.prune = False")
+        if int(self.end_k) > 128:
+            raise NotImplementedError("missing='nan' with k = %d is not provided: the masked dense kernels serve 1 <= k <= 128" % int(self.end_k))
+        if self.ops is None:
+            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda:
+                raise TypeError("PyNMFk: A_ij is a CPU tensor; pass a CUDA tensor or a numpy array (no CPU fallback)")
+            if not torch.cuda.is_available():
+                raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
 
     def _sparse_setup(self, A_ij):
         """The SparseBlock of the sweep, built ONCE (keep_zeros and the meaning of an unstored entry from params.missing) and handed
@@ -295,7 +339,8 @@ class PyNMFk:
                     stack = stack_alloc(len(chunk), self.A_ij.shape[0], self.A_ij.shape[1], self.A_ij.dtype,
                                         self.A_ij.device)            # the perturbed copies are written straight into it
                 data = sample(data=self.A_ij, noise_var=self.noise_var, method=self.sampling, seed=perturbation * 1000,
-                              out=None if stack is None else stack[b], sparse=self.sweep).fit()
+                              out=None if stack is None else stack[b], sparse=self.sweep,
+                              missing="nan" if self._masked else None).fit()
                 self.params.W_update = True
                 if getattr(self.params, "rng", None) == "device":       # device-drawn init: one seed per (perturbation, k)
                     self.params.init_seed = perturbation * 1000 + self.k
@@ -356,7 +401,7 @@ class PyNMFk:
         self.AvgW, self.AvgH, self.L_errDist = regressH.fit()                                           # :246-247
         self.col_err = regressH.column_err()                                                            # :248
         self.avgErr = float(np.mean(self.recon_err))
-        mn = self.params.m * self.params.n      # (sparse data too, under both meanings of an unstored entry: DESIGN.md "Sparse data")
+        mn = self.params.m * self.params.n      # (sparse data too, under both meanings of an unstored entry, and NaN-marked data: DESIGN.md section 7)
         self.AIC = 2 * self.k + mn * np.log(self.avgErr / mn)                                           # :250
         cluster_stats = {'clusterSilhouetteCoefficients': self.clusterSilhouetteCoefficients,
                          'avgSilhouetteCoefficients': self.avgSilhouetteCoefficients, 'L_errDist': self.L_errDist,
@@ -408,7 +453,7 @@ class PyNMFk:
         operators -- as many as fit next to each other in the GPU's free memory (each holds its perturbed copy of the data) --
         else 1.  `params.nmfk_batch` = False / 0 / 1 keeps the one-by-one fits, an integer caps the batch."""
         want = getattr(self.params, "nmfk_batch", True)
-        if self._sparse:          # no batched sparse entry point: the fits run one by one and no stack is allocated
+        if self._sparse or self._masked:          # no batched sparse or masked entry point: the fits run one by one, no stack is allocated
             return 1
         if want is False or self.p != 1 or self.ops is not None or not torch.cuda.is_available():
             return 1
