@@ -89,6 +89,37 @@ int dnmf_mu_update_h(float* H, int k, long n, long ldh, const float* AtW, long l
 int dnmf_aht_update_w(const float* A, long m, long n, long lda, const float* H, int k, long ldh,
                       const float* G, float* W, long ldw, float eps, void* stream);
 
+/* ---- The W phase from a transposed image of A (csrc/dnmf_timg.hip; fp32 A, 32 < k <= 64) ----
+ * A is constant for a whole fit.  With At[c][i] = A[i][c] (n x m, leading dimension ldat = m rounded up to 4) in device memory,
+ * A H^T becomes a product whose contraction index runs down the rows of both operands: it streams At from global memory
+ * straight into the matrix cores (no LDS round trip, a higher held clock) and then applies the same fused update.  Every output
+ * element runs the SAME chain of MFMA steps as in the kernel behind dnmf_aht_update_w, so results are BIT-EQUAL with and
+ * without the image: which path ran never shows in the numbers.
+ *   dnmf_wimage_bytes(m, n)   bytes of the image buffer of an m x n block (the image + room for H^T, rebuilt every W phase)
+ *   dnmf_wimage_build         writes the image (one read and one write of A; m, n, lda, ldat multiples of 4, 16-byte aligned)
+ *   dnmf_wimage_bind/unbind   names the image of (A, m, n, lda) to the CALLING THREAD.  While bound, dnmf_aht_update_w,
+ *                             dnmf_mu_fro_step and dnmf_mu_fro_fit on exactly that (A, m, n, lda) -- one problem, no batch --
+ *                             take the image where the plan below takes it and the kernel of dnmf_aht_update_w otherwise,
+ *                             silently.  THE CALLER KEEPS THE IMAGE CURRENT: after any write to A, rebuild or unbind -- a stale
+ *                             image gives silently wrong factors.  Unbind before freeing either buffer.
+ *   dnmf_set_wimage(mode)     process-wide: 0 off, 1 auto (default: where a sweep measured a gain -- m a multiple of 131072, i.e. the
+ *                             128-row blocks fill whole half-rounds of 1024 waves, and m * n >= 2^27), 2 forced (any size the
+ *                             conditions admit; up to 2 x slower than the other kernel on small or ragged row counts).  Returns the previous setting; other values only query.
+ *   dnmf_wimage_plan          out = {taken, reason, R, grid, KT, launches} for a bound image under the current mode, answered
+ *                             by the function the launch decides with; launches = W phases the calling thread has run from an
+ *                             image so far (the only way to tell: the results do not show it).  a_aligned: A, the image and H are 16-byte aligned and ldh % 4 == 0;
+ *                             w_aligned: W and G are 16-byte aligned, ldw % 4 == 0, 128 rows of W lie within 2 GiB.  Conditions:
+ *                             n % 32 == 0, m % 4 == 0, lda % 4 == 0, 32 < k <= 64, k % 4 == 0, rows of the image short enough for
+ *                             descriptor windows of R >= 8 rows ((R + 8) * ldat * 4 < 2^31; R a power of two).  reason: 0 taken,
+ *                             1 mode off, 2 shape, 3 alignment of A / image / H, 4 alignment of W / k % 4, 5 rank, 6 auto mode and
+ *                             a shape where it does not pay, 7 descriptor windows. */
+size_t dnmf_wimage_bytes(long m, long n);
+int dnmf_wimage_build(const float* A, long m, long n, long lda, float* At, long ldat, void* stream);
+int dnmf_wimage_bind(const float* A, long m, long n, long lda, float* At, long ldat);
+void dnmf_wimage_unbind(void);
+int dnmf_set_wimage(int mode);
+int dnmf_wimage_plan(long m, long n, int k, long lda, int a_aligned, int w_aligned, int out[6]);
+
 /* ---- One whole local MU/Frobenius step on one rank (dist_nmf.py:755-771 with p_r = p_c = 1),
  * W first then H with the new W; clamp!=0 applies pyDNMF.py:155-157 after the step. ---- */
 /* k <= 32 on fp32 A with n a multiple of 4 up to 4096 (8192 at k <= 16; by default from 2048), m >= 4096, 16-byte aligned rows (and w_update != 0): the step reads A

@@ -30,6 +30,9 @@
 HID int dnmf_wide_mu_update_w_(float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, long ldg, float eps, void* stream);
 HID int dnmf_wide_mu_update_h_(float* H, int k, long n, long ldh, const float* AtW, long ldatw, const float* G, long ldg, float eps, int clamp,
                                void* stream);
+// csrc/dnmf_timg.hip: the W phase from a bound transposed image of A (1 = not applicable)
+HID int dnmf_wimage_try_(const float* A, long m, long n, long lda, const float* H, int k, long ldh, const float* G, float* W, long ldw, float eps,
+                         void* stream);
 #undef HID
 
 char* dnmf_errbuf_() {
@@ -424,6 +427,10 @@ int aht_update_w_impl(const TA* A, long m, long n, long lda, const float* H, int
     REQUIRE(!wide_k(k), "aht_update_w: the fused form takes k <= %d (dnmf_aht followed by dnmf_mu_update_w beyond it)", DNMF_TUNED_MAX_K);
     const int kt = kt_of(k);
     REQUIRE(kt > 0 && A && H && G && W && m >= 1 && n >= 1 && lda >= n && ldh >= n && ldw >= k, "aht_update_w: bad arguments");
+    // a transposed image of this very block bound to the calling thread (dnmf_wimage_bind): the TN-form W phase of
+    // csrc/dnmf_timg.hip where its plan takes it -- bit-equal to the kernel below, so the choice never shows in the results
+    if constexpr (std::is_same<TA, float>::value)
+        if (int rci = dnmf_wimage_try_(A, m, n, lda, H, k, ldh, G, W, ldw, eps, stream); rci != 1) return rci;
     NtArgs a{};
     a.X = A; a.ldx = lda; a.nrows = m; a.ncols = n;
     a.Y = H; a.ldy = ldh; a.yrows = k;

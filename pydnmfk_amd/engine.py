@@ -6,6 +6,10 @@ row-major with unit inner stride; anything else raises (no silent host fallback)
 exception is the data matrix A of the Frobenius paths, which may be STORED as bfloat16 (the
 `*_bf16a` entry points: half the HBM bytes, fp32 arithmetic).
 """
+import ctypes
+import os
+import weakref
+
 import torch
 
 from ._lib import DnmfError, PersistentTimeout, check, lib
@@ -128,6 +132,127 @@ def new_gram(k, device):
     return torch.zeros(kp(k), kp(k), dtype=torch.float32, device=device)
 
 
+# ---- the transposed image of A (csrc/dnmf_timg.hip): the W phase of MU/Frobenius at 32 < k <= 64 streams
+# At = A^T instead of A.  Results are bit-equal with and without it, so everything here only decides WHEN an image exists.
+# One slot per device.  A slot belongs to ONE tensor object (weak reference; its death frees the image) in ONE state: the key
+# is (A._version, data_ptr, shape, strides), and any mismatch throws the slot away -- an image never outlives a change of A
+# that torch can see.  Writes torch cannot see (library calls that write through data_ptr()) call _wimage_forget.
+WIMAGE_RESERVE = 2 << 30        # device memory that must stay free after an image is allocated (else the step stays on A)
+_wimage_slots = {}
+
+
+def wimage_mode_from_env(environ):
+    """DNMF_WIMAGE=0|1|2 -> the mode to set at import (None: leave the library's default, 1 = auto)"""
+    v = environ.get("DNMF_WIMAGE", "").strip()
+    return int(v) if v in ("0", "1", "2") else None
+
+
+def set_wimage(mode):
+    """0 off, 1 auto (blocks whose shape the library's sweep found to gain, from their second consecutive call), 2 forced (built on first sight).
+    Returns the previous mode; switching off frees every image."""
+    was = lib.dnmf_set_wimage(int(mode))
+    if int(mode) == 0:
+        _wimage_slots.clear()
+    return was
+
+
+def _wimage_mode():
+    return lib.dnmf_set_wimage(-1)                    # (values outside 0..2 only query)
+
+
+class _WimageSlot:
+    __slots__ = ("ref", "key", "buf", "ldat", "event", "refused")
+
+
+def _wimage_key(A):
+    return (A._version, A.data_ptr(), tuple(A.shape), tuple(A.stride()))
+
+
+def _wimage_forget(t):
+    """`t` is about to be written behind torch's back: drop the image of whatever tensor shares its storage"""
+    dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
+    slot = _wimage_slots.get(dev)
+    if slot is None:
+        return
+    A = slot.ref()
+    if A is None or A.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+        _wimage_slots.pop(dev, None)
+
+
+def _wimage_reaper(dev):
+    def dead(r):                                      # the imaged tensor has been collected: free its image
+        slot = _wimage_slots.get(dev)
+        if slot is not None and slot.ref is r:
+            _wimage_slots.pop(dev, None)
+    return dead
+
+
+def _wimage_lookup(A, H, W, G=None):
+    """The slot whose image the next library call on (A, H, W) may use, or None.  Builds the image when it is due."""
+    mode = _wimage_mode()
+    if mode == 0 or A.dtype != torch.float32 or A.dim() != 2 or A._base is not None or not A.is_cuda:
+        return None
+    m, n = A.shape
+    k = H.shape[0]
+    lda = _ld(A)
+    plan = (ctypes.c_int * 6)()
+    a_ok = A.data_ptr() % 16 == 0 and H.data_ptr() % 16 == 0 and _ld(H) % 4 == 0
+    w_ok = W.data_ptr() % 16 == 0 and _ld(W) % 4 == 0 and (G is None or G.data_ptr() % 16 == 0) and (128 * _ld(W) + 64) * 4 < 2**31 - 1
+    lib.dnmf_wimage_plan(m, n, k, lda, int(a_ok), int(w_ok), plan)
+    if not plan[0]:
+        return None                                   # (the slot of another tensor, if any, stays: this call never binds)
+    dev = A.device.index if A.device.index is not None else torch.cuda.current_device()
+    key = _wimage_key(A)
+    slot = _wimage_slots.get(dev)
+    if slot is None or slot.ref() is not A or slot.key != key:
+        _wimage_slots.pop(dev, None)                  # frees the old image before a new one is asked for
+        slot = _WimageSlot()
+        slot.ref = weakref.ref(A, _wimage_reaper(dev))
+        slot.key, slot.buf, slot.ldat, slot.event, slot.refused = key, None, 0, None, False
+        _wimage_slots[dev] = slot
+        if mode != 2:
+            return None                               # auto: first sight -- the image is built on the second consecutive call
+    if slot.buf is None:
+        if slot.refused:
+            return None
+        nbytes = lib.dnmf_wimage_bytes(m, n)
+        free, _ = torch.cuda.mem_get_info(A.device)
+        if free - nbytes < WIMAGE_RESERVE:
+            slot.refused = True
+            return None
+        try:
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
+        except torch.cuda.OutOfMemoryError:
+            slot.refused = True
+            return None
+        ldat = -(-m // 4) * 4
+        check(lib.dnmf_wimage_build(A.data_ptr(), m, n, lda, buf.data_ptr(), ldat, _stream()))
+        slot.buf, slot.ldat = buf, ldat
+        slot.event = torch.cuda.current_stream().record_event()
+    else:
+        torch.cuda.current_stream().wait_event(slot.event)      # (a no-op on the stream that built it)
+    return slot
+
+
+class _wimage_bound:
+    """with _wimage_bound(A, H, W): the library call inside sees A's image, if there is one; unbound on every exit path"""
+
+    def __init__(self, A, H, W, G=None):
+        self.slot = _wimage_lookup(A, H, W, G)
+        self.A = A
+
+    def __enter__(self):
+        if self.slot is not None:
+            A = self.A
+            check(lib.dnmf_wimage_bind(A.data_ptr(), A.shape[0], A.shape[1], _ld(A), self.slot.buf.data_ptr(), self.slot.ldat))
+        return self
+
+    def __exit__(self, *exc):
+        if self.slot is not None:
+            lib.dnmf_wimage_unbind()
+        return False
+
+
 class ClockProbe:
     """The shader clock the GPU holds while other work runs (dnmf_clock_probe; a measurement aid, bench.py / tools).
 
@@ -243,17 +368,19 @@ class HipOps:
             AH = torch.empty(m, k, dtype=torch.float32, device=W.device)
             self.aht(A, H, AH)
             return self.mu_update_w(W, AH, G, eps)
-        check(_fn("aht_update_w", sfx)(A.data_ptr(), m, n, _ld(A), H.data_ptr(), k, _ld(H), G.data_ptr(), W.data_ptr(),
-                                    _ld(W), float(eps), _stream()))
+        with _wimage_bound(A, H, W, G):
+            check(_fn("aht_update_w", sfx)(A.data_ptr(), m, n, _ld(A), H.data_ptr(), k, _ld(H), G.data_ptr(), W.data_ptr(),
+                                        _ld(W), float(eps), _stream()))
 
     def mu_fro_step(self, A, W, H, eps, w_update=True, clamp=False):
         sfx = _req_a(A); _req(W, "W"); _req(H, "H")
         m, n = A.shape
         k = W.shape[1]
         ws = workspace(m, n, k, A.device)
-        check(_fn("mu_fro_step", sfx)(A.data_ptr(), m, n, _ld(A), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), k,
-                                   float(eps), int(bool(w_update)), int(bool(clamp)), ws.data_ptr(), ws.numel(),
-                                   _stream()))
+        with _wimage_bound(A, H, W):
+            check(_fn("mu_fro_step", sfx)(A.data_ptr(), m, n, _ld(A), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), k,
+                                       float(eps), int(bool(w_update)), int(bool(clamp)), ws.data_ptr(), ws.numel(),
+                                       _stream()))
 
     # ---- HALS sweeps
     def hals_ss2(self, k, like):
@@ -414,6 +541,7 @@ class HipOps:
         ld = _ld(X)
         if out is None or out.shape != X.shape or out.dtype != X.dtype or not out.is_contiguous():
             out = torch.empty(rows, cols, dtype=X.dtype, device=X.device)
+        _wimage_forget(out)          # written through its raw pointer: torch's version counter does not see it
         check(lib.dnmf_perturb_uniform(X.data_ptr(), out.data_ptr(), rows, cols, ld, cols, float(noise_var), int(seed) & (2**64 - 1),
                                        int(X.dtype == torch.bfloat16), _stream()))
         return out
@@ -544,9 +672,15 @@ class HipOps:
         for t, name in ((A3, "A"), (W3, "W"), (H3, "H")):
             if t.stride(2) != 1 and t.numel():
                 raise ValueError("fit: %s must have unit inner stride" % name)
-        check(fn(A3.data_ptr(), m, n, _ld(A3[0]), W3.data_ptr(), _ld(W3[0]), H3.data_ptr(), _ld(H3[0]), k, float(eps),
-                 int(bool(w_update)), int(itr), *extra, int(B), A3.stride(0), W3.stride(0), H3.stride(0), sq.data_ptr(),
-                 ws.data_ptr(), ws.numel(), _stream()))
+        if batched or (norm, method) != ("fro", "mu"):
+            check(fn(A3.data_ptr(), m, n, _ld(A3[0]), W3.data_ptr(), _ld(W3[0]), H3.data_ptr(), _ld(H3[0]), k, float(eps),
+                     int(bool(w_update)), int(itr), *extra, int(B), A3.stride(0), W3.stride(0), H3.stride(0), sq.data_ptr(),
+                     ws.data_ptr(), ws.numel(), _stream()))
+            return sq
+        with _wimage_bound(A, H, W):                  # one MU/Frobenius problem: every step of the fit may stream A's image
+            check(fn(A3.data_ptr(), m, n, _ld(A3[0]), W3.data_ptr(), _ld(W3[0]), H3.data_ptr(), _ld(H3[0]), k, float(eps),
+                     int(bool(w_update)), int(itr), *extra, int(B), A3.stride(0), W3.stride(0), H3.stride(0), sq.data_ptr(),
+                     ws.data_ptr(), ws.numel(), _stream()))
         return sq
 
     def _bcd_fit(self, A3, W3, H3, eps, w_update, itr, sfx, batched):
@@ -579,6 +713,8 @@ class HipOps:
 
 
 HIP_OPS = HipOps()
+if wimage_mode_from_env(os.environ) is not None:
+    lib.dnmf_set_wimage(wimage_mode_from_env(os.environ))
 
 
 class HipOpsBf16x6(HipOps):
