@@ -295,6 +295,15 @@ int dnmf_kl_wtu_bf16x6(const float* A, long m, long n, long lda, const float* W,
                        int k, float eps, float* WTU, long ldo, void* ws, size_t ws_bytes, void* stream);
 int dnmf_mu_kl_step_bf16x6(const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh,
                            int k, float eps, int w_update, int clamp, void* ws, size_t ws_bytes, void* stream);
+/* Which kernels and loop trip counts the bf16x6 entry points choose for a shape: host only, launches nothing, answered by the
+ * functions the entry points decide with.  lda in elements of A; a_bf16: A stored as bfloat16; a_aligned16: A starts on a 16-byte
+ * boundary.  out = {0 the Frobenius entry points take the split kernels (else they forward to the fp32 twins),
+ *   1 the KL entry points do (fp32 A only), 2 KT (32-wide tiles of the padded rank),
+ *   3 tiles in flight in the interior A H^T main loop, 4 W^T A row chunks, 5 rows per chunk,
+ *   6 KL W^T U row chunks, 7 32-row blocks per chunk, 8 KL U H^T column splits, 9 columns per split,
+ *   10 / 11 the A H^T / W^T A kernels stream A past the caches (A of 256 MiB and more)}.
+ * Fields 3-5, 10, 11 are 0 unless out[0], fields 6-9 unless out[1]; all are 0 when neither holds. */
+int dnmf_bf16x6_plan(long m, long n, int k, long lda, int a_bf16, int a_aligned16, long out[12]);
 
 /* ---- Whole fits on one rank (PyNMF.fit, pyDNMF.py:138-182 with p_r = p_c = 1): `itr` update steps with the clamp to eps
  * after the steps i % 10 == 0 (:155-157, :170-172), then normalize_features (:185-194) and the two squared norms of

@@ -85,6 +85,7 @@ for _n in ("aht", "wta", "aht_update_w", "mu_fro_step"):
 SIGNATURES["dnmf_kl_uht_bf16x6"] = SIGNATURES["dnmf_kl_uht"]
 SIGNATURES["dnmf_kl_wtu_bf16x6"] = SIGNATURES["dnmf_kl_wtu"]
 SIGNATURES["dnmf_mu_kl_step_bf16x6"] = SIGNATURES["dnmf_mu_kl_step"]
+SIGNATURES["dnmf_bf16x6_plan"] = [c_long, c_long, c_int, c_long, c_int, c_int, c_void_p]      # m n k lda a_bf16 a_aligned16 out: long[12]
 # grid exchanges inside the library (csrc/dnmf_comm.hip); the communicator handle is an opaque pointer
 SIGNATURES["dnmf_comm_unique_id"] = [c_void_p]
 SIGNATURES["dnmf_comm_create"] = [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]

@@ -301,11 +301,13 @@ __device__ __forceinline__ void ntx_mainloop(f32x16 (&acc)[1][KT], const TX* __r
 // (A second main loop -- A cut before LDS into wave-private piece tiles, two tiles in flight, 182 registers -- gave the same bits, 3 %
 // faster timed alone and 1 % slower inside the iteration: the pass is bound by the power limit, not by its schedule.  Measured in
 // rounds 3 / 4 (profiles/r03d_ntxproto.txt) and removed.)
+constexpr int ntx_nset(int kt, bool b16) { return (kt == 2 && !b16) ? 4 : 2; }   // (of the interior instantiation; dnmf_bf16x6_plan reports it)
+
 template <int KT, int MODE, int AUX, typename TX = float>
 __global__ __launch_bounds__(256, (KT == 4 && std::is_same<TX, bf16_t>::value) ? 1 : 2) void ntx_kernel(NtArgs p, SplitOperand ys) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NW = 4, BM = 32 * NW;
-    constexpr int NSET = (KT == 2 && std::is_same<TX, float>::value) ? 4 : 2;
+    constexpr int NSET = ntx_nset(KT, std::is_same<TX, bf16_t>::value);
     const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long row0 = (long)blockIdx.x * BM;

@@ -13,16 +13,23 @@ namespace {
 // The split kernels exist for 32 < k <= 128 (below that the fp32 kernels are already bound by the HBM, not by the matrix
 // cores) and take A in whole 128-byte lines: 16-byte aligned rows, n a multiple of 128.  Every other shape runs the fp32
 // kernels of dnmf.hip -- the caller gets the exact products instead.
-template <typename TA>
-bool split_shape(const TA* A, long m, long n, long lda, int k) {
-    constexpr long V = 16 / sizeof(TA);                              // elements per 16 bytes
+// (alignment as a flag: dnmf_bf16x6_plan answers with this function, without a pointer)
+bool split_shape(bool a_bf16, bool a_aligned16, long m, long n, long lda, int k) {
+    const long V = a_bf16 ? 8 : 4;                                   // elements per 16 bytes
     // fp32 A at k <= 32 streams at the HBM rate on the fp32 kernels already.  bf16-stored A is matrix-pipe bound on them from
     // k = 17 on (the 32-wide kernels; iteration at 262144 x 8192, k = 32: 2.39 ms, three-product kernels 1.48 ms); at k <= 16 the
     // 16-wide fp32 kernels are as fast (1.39-1.43 ms vs 1.43-1.46 ms) and stay.
-    const int kmin = std::is_same<TA, bf16_t>::value ? 17 : 33;
-    return k >= kmin && k <= DNMF_TUNED_MAX_K && n % 128 == 0 && lda % V == 0 && aligned16(A) && lda >= n && lda <= 4 * n && m >= 1 &&
+    const int kmin = a_bf16 ? 17 : 33;
+    return k >= kmin && k <= DNMF_TUNED_MAX_K && n % 128 == 0 && lda % V == 0 && a_aligned16 && lda >= n && lda <= 4 * n && m >= 1 &&
            n < (1L << 19);
 }
+template <typename TA>
+bool split_shape(const TA* A, long m, long n, long lda, int k) {
+    return split_shape(std::is_same<TA, bf16_t>::value, aligned16(A), m, n, lda, k);
+}
+
+// A is touched once: stream it past the caches when it cannot stay in them anyway (the AUX = 2 instantiations of ntx / tnx)
+bool streams_past_cache(long rows, long cols, size_t elem_bytes) { return (double)rows * cols * elem_bytes >= 256.0 * (1 << 20); }
 
 struct TnxPlan { int nt, ncolblk, nchunks; long rows_per_chunk, ldp, chunk_stride; };
 
@@ -76,8 +83,7 @@ int launch_ntx_kt(const NtArgs& a, const SplitOperand& ys, hipStream_t st) {
     // two stages [A tile, 32 NW rows x 128 bytes | H tile bf16 pieces (32 indices per row for fp32 A, 64 for bf16 A)]; >= the W.G loop's LDS
     constexpr size_t lds = 2 * (32 * NW * 128 + 3 * 32 * KT * (std::is_same<TX, bf16_t>::value ? 128 : 64));
     static bool once = false;
-    // A is touched once: stream it past the caches when it cannot stay in them anyway
-    const bool nt = (double)a.nrows * a.ncols * sizeof(TX) >= 256.0 * (1 << 20);
+    const bool nt = streams_past_cache(a.nrows, a.ncols, sizeof(TX));
     if (!once) { allow_lds(ntx_kernel<KT, MODE, 0, TX>, lds); allow_lds(ntx_kernel<KT, MODE, 2, TX>, lds); once = true; }
     const dim3 grid((unsigned)cdiv(a.nrows, 32 * NW), 1);
     if (nt) hipLaunchKernelGGL((ntx_kernel<KT, MODE, 2, TX>), grid, dim3(64 * NW), lds, st, a, ys);
@@ -98,7 +104,7 @@ int launch_tnx(const TnArgs& a, const SplitOperand& wsplit, const TnxPlan& p, lo
     constexpr size_t lds = 2 * 3 * 32 * KT * (XKT / 8) * 16;
     static bool once = false;
     if (!once) { allow_lds(tnx_kernel<KT, NT, XKT, 0, TX>, lds); allow_lds(tnx_kernel<KT, NT, XKT, 2, TX>, lds); once = true; }
-    const bool nt = (double)m * n * sizeof(TX) >= 256.0 * (1 << 20);
+    const bool nt = streams_past_cache(m, n, sizeof(TX));
     const dim3 grid((unsigned)(cdiv(p.ncolblk, 4) * p.nchunks));
     if (nt) hipLaunchKernelGGL((tnx_kernel<KT, NT, XKT, 2, TX>), grid, dim3(256), lds, st, a, wsplit);
     else hipLaunchKernelGGL((tnx_kernel<KT, NT, XKT, 0, TX>), grid, dim3(256), lds, st, a, wsplit);
@@ -184,10 +190,11 @@ int wta_x6(const TA* A, long m, long n, long lda, const float* W, int k, long ld
 
 // ---------------------------------------------------------------------------------------------- KL products
 // whole 128-column blocks, 16-byte aligned rows of A; other shapes run the fp32 kernels.
-bool klx_shape(const float* A, long m, long n, long lda, int k) {
-    return k >= 1 && k <= DNMF_TUNED_MAX_K && n % 128 == 0 && lda % 4 == 0 && aligned16(A) && lda >= n && lda <= 4 * n && m >= 1 &&
+bool klx_shape(bool a_aligned16, long m, long n, long lda, int k) {
+    return k >= 1 && k <= DNMF_TUNED_MAX_K && n % 128 == 0 && lda % 4 == 0 && a_aligned16 && lda >= n && lda <= 4 * n && m >= 1 &&
            n < (1L << 19);
 }
+bool klx_shape(const float* A, long m, long n, long lda, int k) { return klx_shape(aligned16(A), m, n, lda, k); }
 
 struct KlxImages { SplitOperand wp, ht; };
 long klx_mpad(long m) { return round_up(m, 128); }
@@ -260,6 +267,30 @@ size_t dnmf_ws_bytes_bf16x6(long m, long n, int k) {
     if (n % 128 == 0) extra = h_image_bytes(n, 32 * kt_of(k)) + wta_need(m, n, k);      // (k <= 32: bf16-stored A only)
     if (n % 128 == 0) extra = std::max(extra, klx_need(m, n, k));
     return align256(base) + extra;
+}
+
+int dnmf_bf16x6_plan(long m, long n, int k, long lda, int a_bf16, int a_aligned16, long out[12]) {
+    REQUIRE(out, "bf16x6_plan: null output");
+    for (int i = 0; i < 12; ++i) out[i] = 0;
+    const bool fro = split_shape(a_bf16 != 0, a_aligned16 != 0, m, n, lda, k);
+    const bool kl = !a_bf16 && klx_shape(a_aligned16 != 0, m, n, lda, k);      // (the KL products take fp32 A only)
+    if (!fro && !kl) return DNMF_OK;
+    const int kt = kt_of(k);
+    out[0] = fro; out[1] = kl; out[2] = kt;
+    if (fro) {
+        const size_t eb = a_bf16 ? sizeof(bf16_t) : sizeof(float);
+        const TnxPlan p = plan_tnx(m, n, kt);
+        out[3] = ntx_nset(kt, a_bf16 != 0);
+        out[4] = p.nchunks; out[5] = p.rows_per_chunk;
+        out[10] = out[11] = streams_past_cache(m, n, eb);
+    }
+    if (kl) {
+        const WtuxPlan w = plan_wtux(m, n, kt);
+        const UhtxPlan u = plan_uhtx(m, n);
+        out[6] = w.nchunks; out[7] = w.rowblks_per_chunk;
+        out[8] = u.nsplit; out[9] = u.cols_per_split;
+    }
+    return DNMF_OK;
 }
 
 int dnmf_aht_update_w_bf16x6(const float* A, long m, long n, long lda, const float* H, int k, long ldh, const float* G,

@@ -947,6 +947,300 @@ def grid_exact_cases(entry, cpu=False, kinds=GRID_KINDS):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------- bf16x6: operands with pieces
+# The arithmetic of csrc/dnmf_split.h as its header states it, in numpy, and operands on which it is EXACT although second and third
+# pieces are not zero (tests/test_exact_cpu.py proves the families and that a model with a term deleted, two pieces swapped or a piece
+# plane zeroed differs in every 32 x 32 output tile; tests/test_gpu_exact_split.py holds the six kernels to them).  The integer
+# families above have at most 3 significant bits: x2 = x3 = 0, and five of the six piece products are multiplied by zero.
+#   cut3(x): x1 = rne_bf16(x), x2 = rne_bf16(x - x1), x3 = rne_bf16(x - x1 - x2)
+#   fp32 A:        x y ~ x1 y1 + (x1 y2 + x2 y1) + (x1 y3 + x2 y2 + x3 y1)     (X6_TERMS; dropped: x2 y3, x3 y2, x3 y3)
+#   bf16-stored A: x y = x y1 + x y2 + x y3                                    (X3_TERMS)
+# Values: one piece {1, 2}; two pieces 1 + i 2^-8, i odd (x2 = +-2^-8); three pieces 1 + a 2^-17 with a residual of nine bits
+# after x1 (a = 257: x2 = 2^-9, x3 = 2^-17; a = 767: x1 = 1 + 2^-7, x2 = -2^-9, x3 = -2^-17), all positive, pieces of both signs.  A multiplied pair is two x two pieces, three x
+# one or one x three, so the dropped terms are zero and every piece product is a multiple of 2^-17 (2^-8 2^-8, 2^-17 1); a contraction
+# line may hold 2^24 of those units = 128 in magnitudes, i.e. about 60 products of values near 1 and 2: A is sparse.
+X6_TERMS = ((1, 1), (1, 2), (2, 1), (1, 3), (2, 2), (3, 1))
+X6_DROPPED = ((2, 3), (3, 2), (3, 3))
+X3_TERMS = ((1, 1), (1, 2), (1, 3))                              # (piece of A, piece of the fp32 factor)
+X6_UNIT = 2.0 ** -17
+
+
+def bf16_rne(x):
+    """float32 -> the nearest bfloat16, ties to even, as float32"""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return ((u + (((u >> 16) & 1) + np.uint32(0x7FFF))) & np.uint32(0xFFFF0000)).view(np.float32)
+
+
+def cut3(x, check=True):
+    """the three bf16 pieces of float32 values (float32 arrays; both subtractions are exact in fp32, asserted through the sum)"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    x1 = bf16_rne(x)
+    r1 = x - x1
+    x2 = bf16_rne(r1)
+    r2 = r1 - x2
+    x3 = bf16_rne(r2)
+    assert not check or np.array_equal(x1.astype(np.float64) + x2 + x3, x.astype(np.float64)), "a value needs more than three bf16 pieces"
+    return [x1, x2, x3]
+
+
+def npieces(x):
+    """how many of the three pieces are nonzero (1 for zero itself)"""
+    p = cut3(x)
+    return 1 + (p[1] != 0) + (p[2] != 0)
+
+
+X6_P1 = np.array([1.0, 2.0])
+X6_P2 = np.array([1 + i * 2.0 ** -8 for i in (1, 3, 5, 7)])
+X6_P3 = np.array([1 + a * 2.0 ** -17 for a in (257, 259, 261, 763, 765, 767)])      # (x2, x3) 2^17 = (256, 1), (260, -1), ..., (-256, -1)
+X6_POOLS = (X6_P1, X6_P2, X6_P3)
+assert np.all(npieces(X6_P3) == 3) and np.all(npieces(X6_P2) == 2) and np.all(npieces(X6_P1) == 1)
+
+
+def _mm(X, Y, side):
+    """float64 X Y^T ('aht': X m x n, Y k x n) or Y^T X ('wta': X m x n, Y m x k) of float32 operands (a large X: as a sparse matrix;
+    on the operands here every float64 sum is exact, so the order does not matter)"""
+    Y = Y.astype(np.float64)
+    if X.size > 1 << 22:
+        import scipy.sparse as sp
+        Xs = sp.csr_matrix(X).astype(np.float64)
+        return np.asarray(Xs @ Y.T) if side == "aht" else np.ascontiguousarray(np.asarray(Xs.T @ Y).T)
+    X = X.astype(np.float64)
+    return X @ Y.T if side == "aht" else Y.T @ X
+
+
+def x6_pieces_products(A, F, side):
+    """T[(a, b)] = (piece a of A)(piece b of the factor) for all nine pairs, float64"""
+    Ap, Fp = cut3(A), cut3(F)
+    return {(a, b): _mm(Ap[a - 1], Fp[b - 1], side) for a in (1, 2, 3) for b in (1, 2, 3)}
+
+
+def x6_model(A, F, side, terms=X6_TERMS, a_planes=(1, 2, 3), f_planes=(1, 2, 3), T=None):
+    """the product as the kernels form it: sum over `terms` (a, b) of (plane a of A) (plane b of the factor), in float64 (exact on
+    the families here).  side 'aht': A F^T with F = H (k x n); 'wta': F^T A with F = W (m x k).  a_planes / f_planes: which cut lies
+    in which plane of the operand (0: that plane is zero), to model swapped or lost planes.  T: x6_pieces_products, if at hand."""
+    T = x6_pieces_products(A, F, side) if T is None else T
+    out = np.zeros_like(T[(1, 1)])
+    for a, b in terms:
+        if a_planes[a - 1] and f_planes[b - 1]:
+            out = out + T[(a_planes[a - 1], f_planes[b - 1])]
+    return out
+
+
+def _signs_both(pieces, what, third=True):
+    for s in (1, 2) if third else (1,):
+        v = np.concatenate([p[s].ravel() for p in pieces])
+        assert (v > 0).any() and (v < 0).any(), "%s: piece %d has one sign only" % (what, s + 1)
+
+
+def pieces_product(m, n, k, side, bf16a=False, seed=0, rot=0, nnz=20):
+    """A (m x n, sparse) and the factor F -- side 'aht': F = H (k x n), the product A H^T contracts over the columns of A; 'wta':
+    F = W (m x k), W^T A contracts over its rows.  Contraction index i has type (i + rot) % 3:
+      0  A two pieces,   F two pieces      x1 y1, x1 y2, x2 y1, x2 y2
+      1  A three pieces, F one piece       x1 y1, x2 y1, x3 y1
+      2  A one piece,    F three pieces    x1 y1, x1 y2, x1 y3
+    (rot: with a contraction of fewer than three indices one call cannot hold every type; the callers run rot = 0, 1, 2.)
+    bf16a: every A one piece (a bf16 number), F two and three pieces: the three-term path.  About `nnz` nonzeros of A per
+    contraction line.  Asserted: the three dropped terms are zero for every multiplied pair, second and third pieces of both signs
+    occur, every piece is a multiple of the unit that makes all piece products multiples of 2^-17, and the sum of the magnitudes of
+    the piece products along every contraction line is below 2^24 of those units: exact in fp32 in any order."""
+    assert side in ("aht", "wta")
+    rs = np.random.RandomState(seed + 7919 * m + 31 * n + 3 * k + 101 * rot + (1 if side == "wta" else 0) + (2 if bf16a else 0))
+    L = n if side == "aht" else m
+    typ = (np.arange(L) + rot) % 3
+    ta = np.zeros(L, dtype=int) if bf16a else np.array([1, 2, 0])[typ]                       # index into X6_POOLS
+    tf = (1 + rs.randint(0, 2, size=L)) if bf16a else np.array([1, 0, 2])[typ]
+    draw = lambda t: np.choose(t, [P[rs.randint(0, len(P), size=t.shape)] for P in X6_POOLS])
+    F = draw(np.broadcast_to(tf[None, :], (k, n)) if side == "aht" else np.broadcast_to(tf[:, None], (m, k))).astype(np.float32)
+    flat = np.unique(rs.randint(0, m * n, size=int(round(min(0.5, nnz / L) * m * n))))       # the nonzeros of A
+    rows, cols = flat // n, flat % n
+    line = cols if side == "aht" else rows                            # their contraction index
+    vals = draw(ta[line]).astype(np.float32)
+    A = np.zeros((m, n), dtype=np.float32)
+    A[rows, cols] = vals
+    Vp, Fp = cut3(vals), cut3(F)                                      # (the pieces of A, at its nonzeros only)
+    a_on = [np.bincount(line[P != 0], minlength=L) > 0 for P in Vp]   # per contraction index
+    f_on = [(P != 0).any(axis=0 if side == "aht" else 1) for P in Fp]
+    for a, b in X6_DROPPED:
+        assert not (a_on[a - 1] & f_on[b - 1]).any(), "a multiplied pair has a nonzero dropped term x%d y%d" % (a, b)
+    if bf16a:
+        assert is_bf16(vals).all()
+    if L >= 3:                                                        # (a shorter contraction does not hold every type)
+        _signs_both([Fp] if bf16a else [Vp, Fp], "pieces_product")
+    ua = np.array([1.0, 2.0 ** -8, 2.0 ** -17])
+    for q in Vp:                                                      # every piece a multiple of the unit of its type
+        v = q / ua[ta[line]]
+        assert np.array_equal(v, np.rint(v)), "a piece of A is no multiple of its unit"
+    for q in Fp:
+        v = q / (ua[tf][None, :] if side == "aht" else ua[tf][:, None])
+        assert np.array_equal(v, np.rint(v)), "a piece of the factor is no multiple of its unit"
+    import scipy.sparse as sp
+    Am = sp.csr_matrix((sum(np.abs(P.astype(np.float64)) for P in Vp), (rows, cols)), shape=(m, n))
+    Fm = sum(np.abs(P.astype(np.float64)) for P in Fp)
+    mag = Am @ Fm.T if side == "aht" else Am.T @ Fm                   # >= the magnitudes of the kept terms
+    _bound(mag, X6_UNIT, np.float32, "bf16x6 piece products along a contraction line (%s, %d x %d, k = %d)" % (side, m, n, k))
+    return A, F
+
+
+def _pow2(x):
+    with np.errstate(divide="ignore"):
+        return np.array_equal(np.log2(x), np.round(np.log2(x)))
+
+
+KLX_KINDS = ("w", "h", "wh")
+
+
+def kl_pieces(m, n, k, kind, seed=0, rot=0, nnz=20):
+    """KL operands for the bf16x6 kernels (csrc/dnmf_split_kl.h): S = W H is a power of two >= 4 -- so eps is absorbed and U = A / (S + eps)
+    is exact -- but a sum in which second and third pieces take part and cancel.  A row of W is nonzero in a window of 2 ('w', 'h') or
+    4 ('wh') consecutive rank columns that starts anywhere (m < 32: in up to 32 adjacent windows, so that few rows still reach every
+    column; the magnitudes of S keep an 18-bit value to 64 columns):
+      'w'   W[r][j] = 2^p (1 +- d) alternating along the window, H[j][c] = 2^q for every j: S = 2^(p + q) times the width.  d by row type
+            (r + rot) % 3: 0: 1 + d has three pieces, U of that row one piece; 1: d an odd multiple of 2^-8 of either sign (two
+            pieces and one), U two pieces; 2: d = 0, U three pieces.  W^T U sees every kept term, S = W H the terms x1 y1, x2 y1, x3 y1.
+      'h'   the mirror image: W[r][j] = 2^p in the window, H[j][c] = 2^q (1 + (-1)^j d_c), d and the pieces of U by COLUMN type:
+            U H^T sees every kept term, S the terms x1 y1, x1 y2, x1 y3.
+      'wh'  W[r][j] = 2^p (1 + (-1)^j a_r), H[j][c] = 2^q (1 + s_j b_c) with s = + + - - along j, a and b odd multiples of 2^-8 of
+            either sign: over four consecutive j the sums of (-1)^j, s_j and (-1)^j s_j vanish, S = 2^(p + q + 2) with x2 y2 among
+            its terms; U one and two pieces.
+    k below the window (k = 1; k < 4 for 'wh'): W and H are powers of two, U one to three pieces.  U = A / S is sparse (about `nnz` per
+    row and column).  Asserted: S, the dropped terms of all three products, both signs, and the magnitudes of the piece products of
+    S (per line, in units of 2^(p + q - 17)), U H^T (unit 2^-16: q >= 1) and W^T U (unit 2^-17) below 2^24 units.
+    Returns A, W, H (float32), U (float64)."""
+    assert kind in KLX_KINDS
+    rs = np.random.RandomState(seed + 4099 * m + 37 * n + 5 * k + 11 * rot + KLX_KINDS.index(kind))
+    gs = 4 if kind == "wh" else 2
+    p, q = rs.randint(0, 2, size=m), rs.randint(1, 3, size=n)
+    tr, tc = (np.arange(m) + rot) % 3, (np.arange(n) + rot) % 3
+    d3, d2 = X6_P3 - 1.0, X6_P2 - 1.0
+    sgn = lambda size: rs.choice([-1.0, 1.0], size=size)
+    j = np.arange(k)
+    alt = (-1.0) ** j
+    W = np.zeros((m, k))
+    H = np.ones((k, 1)) * 2.0 ** q[None, :]
+    upool = np.zeros((m, n), dtype=int)                               # index into X6_POOLS of U's entries
+    if k < gs:
+        W[:, 0] = 2.0 ** p
+        upool[:] = (tr[:, None] + tc[None, :]) % 3
+        width = 1
+    else:
+        nw = 1
+        while m < 32 and nw < 32 and 2 * nw * gs <= k:
+            nw *= 2
+        width = nw * gs
+        o = rs.randint(0, k - width + 1, size=m)
+        inwin = (j[None, :] >= o[:, None]) & (j[None, :] < o[:, None] + width)
+        if kind == "w":
+            d = np.choose(tr, [d3[rs.randint(0, len(d3), size=m)], sgn(m) * d2[rs.randint(0, len(d2), size=m)], np.zeros(m)])
+            W = np.where(inwin, 2.0 ** p[:, None] * (1 + alt[None, :] * d[:, None]), 0.0)
+            upool[:] = np.array([0, 1, 2])[tr][:, None]
+        elif kind == "h":
+            d = np.choose(tc, [d3[rs.randint(0, len(d3), size=n)], sgn(n) * d2[rs.randint(0, len(d2), size=n)], np.zeros(n)])
+            H = 2.0 ** q[None, :] * (1 + alt[:, None] * d[None, :])
+            W = np.where(inwin, 2.0 ** p[:, None] * np.ones((1, k)), 0.0)
+            upool[:] = np.array([0, 1, 2])[tc][None, :]
+        else:
+            a = sgn(m) * d2[rs.randint(0, len(d2), size=m)]
+            b = sgn(n) * d2[rs.randint(0, len(d2), size=n)]
+            s4 = np.array([1.0, 1.0, -1.0, -1.0])[j % 4]
+            W = np.where(inwin, 2.0 ** p[:, None] * (1 + alt[None, :] * a[:, None]), 0.0)
+            H = 2.0 ** q[None, :] * (1 + s4[:, None] * b[None, :])
+            upool[:] = rs.randint(0, 2, size=(m, n))
+    S = W @ H
+    assert np.array_equal(S, width * 2.0 ** (p[:, None] + q[None, :])) and S.min() >= 2 and _pow2(S), "W H is not the power of two of the design"
+    Uv = np.choose(upool, [P[rs.randint(0, len(P), size=(m, n))] for P in X6_POOLS])
+    U = np.where(rs.rand(m, n) < min(0.5, nnz / n, nnz / m), Uv, 0.0)
+    A = U * S
+    f32 = lambda x: x.astype(np.float32)
+    for x in (A, W, H, U):
+        assert np.array_equal(f32(x).astype(np.float64), x)
+    Wp, Hp, Up = cut3(W), cut3(H), cut3(U)
+    nz = lambda P: P != 0
+    for a, b in X6_DROPPED:
+        # S: W[r][j] meets H[j][c] for every r, c with W[r][j] != 0; U H^T: U[r][c] meets H[j][c] for every j; W^T U: W[r][j] meets U[r][c]
+        assert not (nz(Wp[a - 1]).any(0) & nz(Hp[b - 1]).any(1)).any(), "S = W H has a nonzero dropped term"
+        assert not (nz(Up[a - 1]).any(0) & nz(Hp[b - 1]).any(0)).any(), "U H^T has a nonzero dropped term"
+        assert not (nz(Up[a - 1]).any(1) & nz(Wp[b - 1]).any(1)).any(), "W^T U has a nonzero dropped term"
+    if k >= gs and min(m, n) >= 3:
+        _signs_both([Wp, Up] if kind == "w" else [Hp, Up] if kind == "h" else [Wp, Hp, Up], "kl_pieces", third=kind != "wh")
+    absum = lambda P: sum(np.abs(x.astype(np.float64)) for x in P)
+    _bound(absum(Up) @ absum(Hp).T, 2.0 ** -16, np.float32, "U H^T piece products along a row")
+    _bound(absum(Wp).T @ absum(Up), 2.0 ** -17, np.float32, "W^T U piece products along a column")
+    _bound((absum(Wp) / 2.0 ** p[:, None]) @ (absum(Hp) / 2.0 ** q[None, :]), 2.0 ** (-16 if kind == "wh" else -17), np.float32, "W H piece products")
+    return f32(A), f32(W), f32(H), U
+
+
+def klx_model(A, W, H, which, s_terms=X6_TERMS, p_terms=X6_TERMS, eps=float(np.finfo(np.float32).eps)):
+    """the KL products as the kernels form them: S = sum over s_terms (a, b) of (piece a of W)(piece b of H); U = A / (S + eps) in fp32;
+    `which` 'uht': sum over p_terms (a, b) of (piece a of U)(piece b of H)^T, 'wtu': (piece b of W)^T (piece a of U).  float64 sums."""
+    Wp, Hp = ([x.astype(np.float64) for x in cut3(X)] for X in (W, H))
+    S = sum(Wp[a - 1] @ Hp[b - 1] for a, b in s_terms)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        U = (A.astype(np.float32) / (S.astype(np.float32) + np.float32(eps))).astype(np.float32)
+    U = np.where(np.isfinite(U), U, 0).astype(np.float32)
+    Up = [x.astype(np.float64) for x in cut3(U, check=False)]          # (with a term of S deleted U is no value of the design)
+    if which == "uht":
+        return sum(Up[a - 1] @ Hp[b - 1].T for a, b in p_terms)
+    return sum(Wp[b - 1].T @ Up[a - 1] for a, b in p_terms)
+
+
+def x6_rots(L):
+    """the rotations of the pair types a caller of `pieces_product` runs: all three where the contraction is shorter than three"""
+    return (0, 1, 2) if L < 3 else (0,)
+
+
+def klx_rots(m):
+    """... of `kl_pieces`: kind 'w' types the ROWS, and a last 32-row tile of one or two rows holds one or two types per call
+    (and fewer than 32 rows leave some tile of W^T U without an entry of the type a term needs: three independent draws)"""
+    return (0, 1, 2) if m % 32 in (1, 2) or m < 32 else (0,)
+
+
+def tiles_differ(X, Y, tile=32):
+    """per 32 x 32 tile of two equal-shaped matrices: does any element differ (a boolean matrix over the tiles, ragged last tiles kept)"""
+    D = ~(np.asarray(X) == np.asarray(Y))
+    r, c = -(-D.shape[0] // tile), -(-D.shape[1] // tile)
+    P = np.zeros((r * tile, c * tile), dtype=bool)
+    P[:D.shape[0], :D.shape[1]] = D
+    return P.reshape(r, tile, c, tile).any(axis=(1, 3))
+
+
+# The shapes of tests/test_gpu_exact_split.py, named after the boundary they sit on, with the plan dnmf_bf16x6_plan must report
+# (tests/test_bf16x6_plan.py, without a GPU): (id, m, n, k, lda, factors aligned, (KT, tiles in flight, tnx chunks, rows per chunk)).
+# lda = 0: the pitch Poisoned gives an aligned view (n + 4 for fp32, n + 8 for bf16).  tnx: cdiv(m, 256) chunks of cdiv(m, chunks) rows
+# rounded up to 64.
+X6_F32 = [
+    ("k33-kmin-m1-edge-only-n128-one-trip", 1, 128, 33, 0, True, (2, 4, 1, 64)),
+    ("k40-below-kp-m31-edge-only-n256", 31, 256, 40, 0, True, (2, 4, 1, 64)),
+    ("k63-m100-edge-only-n384-odd-multiple-unaligned", 100, 384, 63, 0, False, (2, 4, 1, 128)),
+    ("k64-nset4-m128-interior-only-n128-lda2n", 128, 128, 64, 256, True, (2, 4, 1, 128)),
+    ("k65-kt4-m129-both-n256-unaligned", 129, 256, 65, 0, False, (4, 2, 1, 192)),
+    ("k64-nset4-m257-both-two-chunks-n1152-rotation", 257, 1152, 64, 0, True, (2, 4, 2, 192)),
+    ("k128-m640-three-chunks-n384-lda4n", 640, 384, 128, 1536, True, (4, 2, 3, 256)),
+    ("k97-kt4-m1000-ragged-chunk-n1152-rotation-unaligned", 1000, 1152, 97, 0, False, (4, 2, 4, 256)),
+    ("k40-m129-n128-lda4n-unaligned", 129, 128, 40, 512, False, (2, 4, 1, 192)),
+]
+X6_BF16 = [
+    ("k17-kmin-kt1-m1-n128-two-tiles", 1, 128, 17, 0, True, (1, 2, 1, 64)),
+    ("k20-kt1-m100-n256-unaligned", 100, 256, 20, 0, False, (1, 2, 1, 128)),
+    ("k32-kt1-m129-both-n384", 129, 384, 32, 0, True, (1, 2, 1, 192)),
+    ("k48-kt2-m257-n1152-rotation-unaligned", 257, 1152, 48, 0, False, (2, 2, 2, 192)),
+    ("k100-kt4-m1000-ragged-chunk-n128", 1000, 128, 100, 0, True, (4, 2, 4, 256)),
+    ("k64-kt2-m640-n256-lda4n", 640, 256, 64, 1024, True, (2, 2, 3, 256)),
+]
+X6_FALLBACK = [("k32-f32", 129, 256, 32, False), ("k16-bf16", 129, 256, 16, True)]       # (id, m, n, k, bf16-stored A): the fp32 route
+# KL: (id, m, n, k, lda, factors aligned, (KT, wtux chunks, 32-row blocks per chunk, uhtx splits, columns per split))
+X6_KL = [
+    ("k1-n128-one-split-m100", 100, 128, 1, 0, True, (1, 1, 4, 1, 128)),
+    ("k5-n128-m640-five-chunks-one-live-wave-unaligned", 640, 128, 5, 0, False, (1, 5, 4, 1, 128)),
+    ("k32-n512-two-splits-m129", 129, 512, 32, 0, True, (1, 1, 5, 2, 256)),
+    ("k33-kt2-n512-m257-lda2n-unaligned", 257, 512, 33, 1024, False, (2, 2, 5, 2, 256)),
+    ("k64-n896-three-splits-m1000", 1000, 896, 64, 0, True, (2, 8, 4, 3, 320)),
+    ("k128-kt4-n896-m31-unaligned", 31, 896, 128, 0, False, (4, 1, 1, 3, 320)),
+    ("k64-m1-n128", 1, 128, 64, 0, True, (2, 1, 1, 1, 128)),
+]
+# A of 256 MiB: the instantiations that stream A past the caches (id, m, n, k, bf16-stored A, plan)
+X6_STREAMED = [("f32-32768x2048-k40", 32768, 2048, 40, False, (2, 4, 128, 256)), ("bf16-65536x2048-k40", 65536, 2048, 40, True, (2, 2, 128, 512))]
+
+
 # ---------------------------------------------------------------------------------------------------------- per-element comparison
 def assert_ulp(got, q, c, what="", tile=(16, 32), q_hi=None):
     """|got - q| <= c * spacing(q in got's type) per element, q the float64 reference; q == 0 must be exactly 0 and c == 0 means
@@ -990,9 +1284,9 @@ class Poisoned:
     pitch ld >= cols, `guard` elements after it; everything outside the view holds `fill` (NaN for operands, SENTINEL for outputs).
     aligned: lead and ld multiples of 4 (the vector paths; `quantum` elements instead of 4: 8 puts the members of a bf16 stack 16 bytes
     apart whatever the row count); otherwise an odd start and pitch (the generic paths).  packed: ld = cols (a contiguous view, for the
-    entry points that require one)."""
+    entry points that require one).  ld: that pitch instead."""
 
-    def __init__(self, torch, x, dtype=None, fill=float("nan"), aligned=True, guard=67, device="cuda", packed=False, quantum=4):
+    def __init__(self, torch, x, dtype=None, fill=float("nan"), aligned=True, guard=67, device="cuda", packed=False, quantum=4, ld=None):
         x = np.asarray(x)
         x3 = x if x.ndim == 3 else x[None]
         B, rows, cols = x3.shape
@@ -1000,6 +1294,9 @@ class Poisoned:
         self.dtype = dtype or {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}[x.dtype]
         self.lead = 8 if aligned else 3
         self.ld = cols if packed else (-(-cols // quantum) * quantum + quantum) if aligned else cols + 3
+        if ld is not None:                                          # a pitch of the caller's (a column slice of a wider matrix)
+            assert ld >= cols
+            self.ld = ld
         self.rows, self.cols, self.fill = rows, cols, fill
         bs = rows * self.ld
         self.buf = torch.full((self.lead + B * bs + guard,), fill, dtype=self.dtype, device=device)

@@ -722,3 +722,114 @@ def test_grid_shapes_reach_their_branches():
         for kind, shape, modes in cases:
             assert modes and all(mo in EXACT_MODES for mo in modes)
             assert any(mo.startswith("overlap4") for mo in modes) == (e[1][1] == 1 and e[0] != "4x1" and kind in ex.GRID_OVERLAP_KINDS)
+
+
+# ---------------------------------------------------------------------------------------------------------- bf16x6: operands with pieces
+X6_CASES = [pytest.param(c, False, id="f32-" + c[0]) for c in ex.X6_F32] + [pytest.param(c, True, id="bf16-" + c[0]) for c in ex.X6_BF16]
+
+
+def test_cut3_is_the_split_of_the_header():
+    """x1 = rne_bf16(x), x2 = rne_bf16(x - x1), x3 = rne_bf16(x - x1 - x2): ties go to even, the pieces are bf16 numbers, their sum is
+    x, and the example of the design -- 1 + 3 2^-9 cuts to 1 + 2^-7 and -2^-9"""
+    x = np.float32([1 + 3 * 2.0 ** -9, 1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, 1 + 257 * 2.0 ** -17, 1 + 767 * 2.0 ** -17, 3.0, 0.0, -1 - 2.0 ** -8])
+    p = ex.cut3(x)
+    assert all(ex.is_bf16(q).all() for q in p)
+    assert [float(q[0]) for q in p] == [1 + 2.0 ** -7, -2.0 ** -9, 0.0]
+    assert [float(q[1]) for q in p] == [1.0, 2.0 ** -8, 0.0] and [float(q[2]) for q in p] == [1 + 2.0 ** -6, -2.0 ** -8, 0.0]
+    assert [float(q[3]) for q in p] == [1.0, 2.0 ** -9, 2.0 ** -17] and [float(q[4]) for q in p] == [1 + 2.0 ** -7, -2.0 ** -9, -2.0 ** -17]
+    assert [float(q[7]) for q in p] == [-1.0, -2.0 ** -8, 0.0]
+    rs = np.random.RandomState(3)
+    y = (rs.rand(4096).astype(np.float32) + np.float32(0.5)) * np.float32(2.0) ** rs.randint(-20, 20, size=4096)
+    q = ex.cut3(y)                                                          # (asserts x1 + x2 + x3 == x)
+    assert np.all(np.abs(q[1]) <= 2.0 ** -8 * np.abs(y)) and np.all(np.abs(q[2]) <= 2.0 ** -16 * np.abs(y))
+    for i, pool in enumerate(ex.X6_POOLS):
+        assert np.all(ex.npieces(pool) == i + 1) and np.all(pool > 0)
+
+
+def _x6_mutations(bf16):
+    """(name, keyword arguments of x6_model): each kept term deleted, a piece plane zeroed, the second and third planes swapped (bf16-
+    stored A: all three terms are kept, so a swap of the factor's planes is the same sum and only deletions can show)"""
+    terms = ex.X3_TERMS if bf16 else ex.X6_TERMS
+    muts = [("without x%d y%d" % t, dict(terms=tuple(u for u in terms if u != t))) for t in terms]
+    muts += [("plane %d of the factor zero" % (i + 1), dict(terms=terms, f_planes=tuple(0 if j == i else j + 1 for j in range(3)))) for i in range(3)]
+    if not bf16:
+        muts += [("plane %d of A zero" % (i + 1), dict(terms=terms, a_planes=tuple(0 if j == i else j + 1 for j in range(3)))) for i in range(3)]
+        muts += [("planes 2 and 3 of the factor swapped", dict(terms=terms, f_planes=(1, 3, 2))),
+                 ("planes 2 and 3 of A swapped", dict(terms=terms, a_planes=(1, 3, 2)))]
+    return terms, muts
+
+
+def _f32_any_order(T, terms, seed):
+    """the kept piece products added in float32, term by term in a random order"""
+    acc = np.zeros_like(T[(1, 1)], dtype=np.float32)
+    for i in np.random.RandomState(seed).permutation(len(terms)):
+        acc = acc + T[terms[i]].astype(np.float32)
+    return acc.astype(np.float64)
+
+
+@pytest.mark.parametrize("side", ["aht", "wta"])
+@pytest.mark.parametrize("case,bf16", X6_CASES)
+def test_pieces_products_are_exact_and_every_term_counts(case, bf16, side):
+    """on `pieces_product` operands the model of the kernels' arithmetic EQUALS the float64 product, in float32 too, and the model with
+    any one kept term deleted, a plane zeroed or two planes swapped differs from it in every 32 x 32 tile of the output: the GPU
+    assertion can fail.  (A contraction of fewer than three indices holds one type of pair per call: the three rotations between them.)"""
+    _, m, n, k = case[:4]
+    terms, muts = _x6_mutations(bf16)
+    seen = {}
+    for rot in ex.x6_rots(n if side == "aht" else m):
+        A, F = ex.pieces_product(m, n, k, side, bf16a=bf16, rot=rot)
+        ref = ex._mm(A, F, side)
+        T = ex.x6_pieces_products(A, F, side)
+        assert np.array_equal(ex.x6_model(A, F, side, terms, T=T), ref), "the model is not the float64 product"
+        assert np.array_equal(_f32_any_order(T, terms, rot), ref)
+        assert all(np.array_equal(T[t].astype(np.float32), T[t]) for t in terms), "a sum of piece products is no float32 number"
+        assert not any(T[t].any() for t in ex.X6_DROPPED)
+        for name, kw in muts:
+            seen[name] = seen.get(name, False) | ex.tiles_differ(ex.x6_model(A, F, side, T=T, **kw), ref)
+    for name, d in seen.items():
+        assert d.all(), "%s: the model equals float64 in tile %s of %s" % (name, tuple(np.argwhere(~d)[0]), d.shape)
+
+
+@pytest.mark.parametrize("case", [pytest.param(c, id=c[0]) for c in ex.X6_KL])
+def test_kl_pieces_are_exact_and_every_term_counts(case):
+    """`kl_pieces`: the model of klx_uht_kernel / klx_wtu_kernel equals the float64 U H^T and W^T U for every kind; a term deleted
+    from S = W H, or from the second product, changes every 32 x 32 output tile in at least one of the kinds (k >= 4: every kept
+    term of both products; k = 1: W and H are single powers of two, only the pieces of U take part)"""
+    _, m, n, k = case[:4]
+    s_need = ex.X6_TERMS if k >= 4 else ((1, 1),)
+    p_need = ex.X6_TERMS if k >= 4 else ((1, 1), (2, 1), (3, 1))
+    for which in ("uht", "wtu"):
+        seen = {}
+        for kind in ex.KLX_KINDS:
+            for rot in ex.klx_rots(m):
+                A, W, H, U = ex.kl_pieces(m, n, k, kind, rot=rot)
+                W64, H64 = W.astype(np.float64), H.astype(np.float64)
+                ref = U @ H64.T if which == "uht" else W64.T @ U
+                assert np.array_equal(ex.klx_model(A, W, H, which), ref), "%s, kind %s: the model is not the float64 product" % (which, kind)
+                assert np.array_equal(ref.astype(np.float32), ref)
+                for t in s_need:
+                    d = ex.tiles_differ(ex.klx_model(A, W, H, which, s_terms=tuple(u for u in ex.X6_TERMS if u != t)), ref)
+                    seen[("S", t)] = seen.get(("S", t), False) | d
+                for t in p_need:
+                    d = ex.tiles_differ(ex.klx_model(A, W, H, which, p_terms=tuple(u for u in ex.X6_TERMS if u != t)), ref)
+                    seen[(which, t)] = seen.get((which, t), False) | d
+        for key, d in seen.items():
+            assert d.all(), "%s without x%d y%d: the model equals float64 in tile %s of %s" % (key[0], key[1][0], key[1][1], tuple(np.argwhere(~d)[0]), d.shape)
+
+
+@pytest.mark.parametrize("case", [pytest.param(c, id=c[0]) for c in ex.X6_STREAMED])
+def test_pieces_products_fit_the_streamed_shapes(case):
+    """the 256 MiB shapes: the generator's own assertions -- the dropped terms are zero for every pair, every piece product is a multiple of
+    2^-17, the magnitudes along every line stay below 2^24 units -- which with x = x1 + x2 + x3 (cut3 asserts it) make the kept terms
+    add up to the product exactly; every output tile holds every kept term.  (The model itself and the mutations: the smaller shapes.)"""
+    _, m, n, k, bf16, _ = case
+    terms = ex.X3_TERMS if bf16 else ex.X6_TERMS
+    for side in ("aht", "wta"):
+        A, F = ex.pieces_product(m, n, k, side, bf16a=bf16)
+        import scipy.sparse as sp
+        rows, cols = np.nonzero(A)
+        Vp, Fp = ex.cut3(A[rows, cols]), [x.astype(np.float64) for x in ex.cut3(F)]
+        for a, b in terms:
+            X = sp.csr_matrix((Vp[a - 1].astype(np.float64), (rows, cols)), shape=A.shape)
+            T = X @ Fp[b - 1].T if side == "aht" else (X.T @ Fp[b - 1]).T
+            assert ex.tiles_differ(T, 0.0).all(), "x%d y%d is zero in a whole output tile" % (a, b)

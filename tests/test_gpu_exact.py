@@ -299,7 +299,9 @@ def _fro_step(ops, A, W, H, clamp, aligned=True, adt=torch.float32):
 
 @pytest.mark.parametrize("m,n,k,aligned", FRO)
 def test_mu_fro_step_two_pass(env, m, n, k, aligned):
-    """mu_fro_step on the two-pass route: the new W exact, the new H c = 3; fp32 and bf16-stored A, fp32 and bf16x6 products"""
+    """mu_fro_step on the two-pass route: the new W exact, the new H c = 3; fp32 and bf16-stored A, through HIP_OPS and through
+    HIP_OPS_BF16X6 -- whose entry points forward every shape of FRO to the fp32 kernels (n % 128 != 0), so the second round covers the
+    forwarding; the step on the split kernels: tests/test_gpu_exact_split.py::test_mu_fro_step"""
     engine, lib = env
     A, W, H, Wn, Hq = ex.fro_step(m, n, k)
     was = lib.dnmf_set_onepass(0)
@@ -432,8 +434,9 @@ def test_fit_itr1(env, m, n, k, B):
 # ------------------------------------------------------------------------------------------------------------- bf16x6 and float64
 @pytest.mark.parametrize("m,n,k,aligned", SUB)
 def test_bf16x6_products(env, m, n, k, aligned):
-    """the six-piece bf16 products (csrc/dnmf_split.h) split small integers and dyadic quotients exactly: aht, wta, kl_uht, kl_wtu
-    EQUAL float64, fp32 and bf16-stored A; aht_update_w c = 3"""
+    """the bf16x6 entry points on shapes WITHOUT a split kernel (no n of SUB is a multiple of 128: tests/test_bf16x6_plan.py asserts it):
+    the forwarding to the fp32 kernels -- aht, wta, kl_uht, kl_wtu EQUAL float64, fp32 and bf16-stored A; aht_update_w c = 3.  The split
+    kernels themselves (csrc/dnmf_split.h, dnmf_split_kl.h) are held to exact operands in tests/test_gpu_exact_split.py"""
     engine, _ = env
     ops = engine.HIP_OPS_BF16X6
     A, W, H = ex.products(m, n, k)
@@ -626,8 +629,10 @@ def _scratch_runs(engine, fn):
             and not torch.isnan(a).any(), "the result depends on what the scratch held before the call"
 
 
-@pytest.mark.parametrize("m,n,k", [(1000, 515, 17), (4096, 2048, 32), (300, 130, 5)])
+@pytest.mark.parametrize("m,n,k", [(1000, 515, 17), (4096, 2048, 32), (300, 130, 5), (257, 256, 40)])
 def test_scratch_holds_no_state(env, m, n, k):
+    """(257, 256, 40) is a split shape of the bf16x6 entry points (n % 128 == 0, k > 32: the images and partial sums of ntx, tnx,
+    klx_uht and klx_wtu live in the scratch); at (4096, 2048, 32) only the KL ones are"""
     engine, lib = env
     ops, o6, f64 = engine.HIP_OPS, engine.HIP_OPS_BF16X6, engine.HIP_OPS_F64
     A, W, H = (_dev(x) for x in ex.products(m, n, k))
@@ -652,7 +657,8 @@ def test_scratch_holds_no_state(env, m, n, k):
              lambda: [ops.colsum(W, torch.empty(k, device="cuda")), ops.resid_sqnorm(A, W, H)],
              lambda: [o6.aht(A, H, torch.empty(m, k, device="cuda")), o6.wta(A, W, torch.empty(k, n, device="cuda"))],
              lambda: [o6.kl_uht(Ak, Wk, Hk, EPS, torch.empty(m, k, device="cuda"))],
-             step(ops, True), step(ops, False), step(o6, True)]
+             lambda: [o6.kl_wtu(Ak, Wk, Hk, EPS, torch.empty(k, n, device="cuda"))],
+             step(ops, True), step(ops, False), step(o6, True), step(o6, False)]
     if lib.dnmf_mu_fro_onepass(m, n, k) or m >= 4096:
         cases.append(step(ops, True, 2))
     Ad, Wd, Hd = (x.double() for x in (A, W, H))
