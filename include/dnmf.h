@@ -486,6 +486,41 @@ int dnmf_f64_hals_w_col(double* W, long m, int k, long ldw, const double* AH, lo
 int dnmf_f64_hals_w_scale(double* W, long m, long ldw, int col, const double* ss2, void* stream);
 int dnmf_f64_hals_update_h(double* H, int k, long n, long ldh, const double* AtW, long ldatw, const double* G, long ldg, double eps,
                            void* stream);
+/* Which kernel a float64 entry point launches for a shape, host arithmetic only (no GPU, nothing is launched): answered by the plan
+ * functions the entry points themselves launch from (csrc/dnmf_f64.hip "launch plans"), so a test can assert the variant a shape reaches.
+ * op (DNMF_F64_OP_*) and what m, n, k mean for it:
+ *   AHT          X m x n, Y k x n (a Gram H H^T: m = k)       ld = {ldx, ldy}
+ *   WTA          A m x n, W m x k (a Gram W^T W: n = k)       ld = {lda, ldw}
+ *   KL_UHT, KL_WTU   A m x n at rank k                        ld = {lda, ldw, ldh}
+ *   KL_QUOT, SQDIFF  the m x n image at rank k                ld = {lda, ldw, ldh, ldo}
+ *   MU_UPDATE_W  W m x k (n ignored)     MU_UPDATE_H  H k x n (m ignored)
+ *   SUM, COLSUM, EW  a matrix of m rows and n columns (k ignored)
+ *   FIT          dnmf_f64_fit at m x n, rank k, `method` (itr >= 1)
+ * `ld`: the row pitches that enter the 2 GiB descriptor-window checks, in elements; NULL or an entry <= 0: the packed pitch.  The
+ * workspace is taken to be 16-byte aligned (the reduce width depends on it).  out (DNMF_F64_PLAN_*):
+ *   FAMILY  DNMF_F64_FAM_*: NT = f64_nt_kernel, TN = f64_tn_kernel, KL_UHT / KL_WTU = the fused kernels of csrc/dnmf_f64_kl.h, NN_COLS =
+ *           f64_nn_cols_kernel, NN_ROWS = f64_nn_rows_kernel (the W update), UPD_H = f64_upd_h_kernel, SUM / COLSUM / EW = the streaming
+ *           kernels, FIT_TINY = the one-workgroup fit, FIT_CHAIN = the chain of primitives, IMAGE = a KL product that goes through the
+ *           m x n image (k > 64: query KL_QUOT and AHT / WTA for its two launches), NONE = the entry point refuses the pitches
+ *   NT      the template's NT (16-wide tiles of k), or KS (contraction steps of 4) for NN_COLS / NN_ROWS / UPD_H
+ *   RT      row tiles per wave (NT, KL_UHT); the template's CT, column tiles per wave, for TN, KL_WTU, NN_COLS
+ *   VEC, FULL  the template's flags (FULL: KL_UHT only)      D  register sets of operand loads in flight
+ *   COUNT   column splits (NT, KL_UHT), row chunks (TN, KL_WTU, NN_COLS, COLSUM) or block partials (SUM)
+ *   PER     columns per split / rows per chunk (the last one holds the rest)
+ *   V       columns per thread of the ordered reduction that follows (2 or 1); 0: no reduction is launched
+ *   GRID_X, GRID_Y  the grid of the main launch, in workgroups of 256 threads (SUM, EW: the grid-stride loop takes more than one
+ *           trip when m n > 256 GRID_X); FIT: 1 x 1 for the tiny kernel, 0 for the chain
+ *   WAVES   waves with work (TN, KL_WTU, NN_COLS: below 4 GRID_X the last workgroup has idle waves), else 4 GRID_X
+ * Returns DNMF_EINVAL for a bad op, shape, rank, method or a null `out`. */
+enum { DNMF_F64_OP_AHT = 0, DNMF_F64_OP_WTA, DNMF_F64_OP_KL_UHT, DNMF_F64_OP_KL_WTU, DNMF_F64_OP_KL_QUOT, DNMF_F64_OP_SQDIFF,
+       DNMF_F64_OP_MU_UPDATE_W, DNMF_F64_OP_MU_UPDATE_H, DNMF_F64_OP_SUM, DNMF_F64_OP_COLSUM, DNMF_F64_OP_EW, DNMF_F64_OP_FIT };
+enum { DNMF_F64_FAM_NONE = 0, DNMF_F64_FAM_NT, DNMF_F64_FAM_TN, DNMF_F64_FAM_KL_UHT, DNMF_F64_FAM_KL_WTU, DNMF_F64_FAM_NN_COLS,
+       DNMF_F64_FAM_NN_ROWS, DNMF_F64_FAM_UPD_H, DNMF_F64_FAM_SUM, DNMF_F64_FAM_COLSUM, DNMF_F64_FAM_EW, DNMF_F64_FAM_FIT_TINY,
+       DNMF_F64_FAM_FIT_CHAIN, DNMF_F64_FAM_IMAGE };
+enum { DNMF_F64_PLAN_FAMILY = 0, DNMF_F64_PLAN_NT, DNMF_F64_PLAN_RT, DNMF_F64_PLAN_VEC, DNMF_F64_PLAN_FULL, DNMF_F64_PLAN_D,
+       DNMF_F64_PLAN_COUNT, DNMF_F64_PLAN_PER, DNMF_F64_PLAN_V, DNMF_F64_PLAN_GRID_X, DNMF_F64_PLAN_GRID_Y, DNMF_F64_PLAN_WAVES,
+       DNMF_F64_PLAN_LEN };
+int dnmf_f64_plan(int op, long m, long n, int k, const long* ld, int method, long out[DNMF_F64_PLAN_LEN]);
 
 /* ---- Grid exchanges inside the library (RCCL over xGMI; replaces MPI_comm, dist_comm.py:16-56, and the mpi4py calls of
  * global_gram / global_mm, dist_nmf.py:681,707).  RCCL is bound at run time (dlopen; an RCCL already in the process -- the

@@ -160,6 +160,11 @@ SIGNATURES["dnmf_f64_hals_w_col"] = [c_void_p, c_long, c_int, c_long, c_void_p, 
                                      c_void_p, c_size_t, c_void_p]
 SIGNATURES["dnmf_f64_hals_w_scale"] = [c_void_p, c_long, c_long, c_int, c_void_p, c_void_p]
 SIGNATURES["dnmf_f64_hals_update_h"] = [c_void_p, c_int, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_double, c_void_p]
+# host only: op m n k ld (long[4] or NULL) method out: long[12] (include/dnmf.h DNMF_F64_OP_*, DNMF_F64_FAM_*, DNMF_F64_PLAN_*)
+SIGNATURES["dnmf_f64_plan"] = [c_int, c_long, c_long, c_int, c_void_p, c_int, c_void_p]
+F64_OPS = ("aht", "wta", "kl_uht", "kl_wtu", "kl_quot", "sqdiff", "mu_update_w", "mu_update_h", "sum", "colsum", "ew", "fit")
+F64_FAMILIES = ("none", "nt", "tn", "kl_uht", "kl_wtu", "nn_cols", "nn_rows", "upd_h", "sum", "colsum", "ew", "fit_tiny", "fit_chain", "image")
+F64_PLAN_FIELDS = ("family", "nt", "rt", "vec", "full", "d", "count", "per", "v", "grid_x", "grid_y", "waves")
 # BCD (csrc/dnmf_bcd.hip)
 SIGNATURES["dnmf_bcd_state_init"] = [c_void_p, c_void_p, c_void_p]
 SIGNATURES["dnmf_bcd_init_factor"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_void_p]
@@ -261,3 +266,14 @@ class PersistentTimeout(DnmfError):
 def check(rc):
     if rc != 0:
         raise DnmfError("libdnmf_hip: %s (code %d)" % (lib.dnmf_last_error().decode(), rc))
+
+
+def f64_plan(op, m, n, k, ld=(), method=0):
+    """dnmf_f64_plan as a dict: which kernel the float64 entry point `op` (a name of F64_OPS) launches for the shape -- `family` by
+    name, the other F64_PLAN_FIELDS as integers.  ld: the pitches in the order of the entry point's arguments (missing: packed)."""
+    pitches = (c_long * 4)(*(list(ld) + [0] * (4 - len(ld))))
+    out = (c_long * len(F64_PLAN_FIELDS))()
+    check(lib.dnmf_f64_plan(F64_OPS.index(op), int(m), int(n), int(k), pitches, int(method), out))
+    p = dict(zip(F64_PLAN_FIELDS, out))
+    p["family"] = F64_FAMILIES[p["family"]]
+    return p

@@ -275,9 +275,12 @@ __global__ __launch_bounds__(256) void f64_reduce_kernel(const double* __restric
 #pragma unroll
     for (int e = 0; e < V; ++e) out[r * ldo + c + e] = s[e];
 }
+// the reduce width the slabs allow: two consecutive columns per thread (16-byte accesses) or one
+inline int reduce_v(long cols, long ldp, long stride, const void* P) {
+    return (cols % 2 == 0 && ldp % 2 == 0 && stride % 2 == 0 && ((uintptr_t)P & 15) == 0) ? 2 : 1;
+}
 inline void launch_reduce64(const double* P, long stride, long ldp, int nsplit, double* out, long ldo, long rows, long cols, hipStream_t st) {
-    const bool v2 = cols % 2 == 0 && ldp % 2 == 0 && stride % 2 == 0 && ((uintptr_t)P & 15) == 0;
-    if (v2) hipLaunchKernelGGL(f64_reduce_kernel<2>, dim3((unsigned)cdiv(rows * (cols / 2), 256)), dim3(256), 0, st, P, stride, ldp, nsplit, out, ldo, rows, cols);
+    if (reduce_v(cols, ldp, stride, P) == 2) hipLaunchKernelGGL(f64_reduce_kernel<2>, dim3((unsigned)cdiv(rows * (cols / 2), 256)), dim3(256), 0, st, P, stride, ldp, nsplit, out, ldo, rows, cols);
     else hipLaunchKernelGGL(f64_reduce_kernel<1>, dim3((unsigned)cdiv(rows * cols, 256)), dim3(256), 0, st, P, stride, ldp, nsplit, out, ldo, rows, cols);
 }
 
@@ -579,8 +582,88 @@ long nt_splits(long m, long n) {
     return m <= 1024 ? std::max<long>(1, std::min<long>(256, n / 512)) : 1;
 }
 
+// ---- launch plans: one struct per kernel family holds every decision its entry point takes before it launches -- the template
+// arguments, the splits / chunks, the grid.  The entry points launch from these structs and dnmf_f64_plan reports them, so the query
+// cannot drift from the dispatch.  `ok`: every pitch stays inside the 2 GiB descriptor window (the entry point refuses otherwise).
+// `ws` only enters through its 16-byte alignment (the reduce width); the query passes nullptr, i.e. an aligned workspace.
+struct NtLaunch64 { bool ok, vec; int rt, nt, d, kp, v; long nsplit, cps; unsigned gx; };
+NtLaunch64 plan_nt64(long m, long n, int kc, long ldx, long ldy, const void* ws) {
+    NtLaunch64 p;
+    const long ns = nt_splits(m, n);
+    p.cps = ns > 1 ? round_up(cdiv(n, ns), 16) : round_up(n, 16);
+    p.nsplit = cdiv(n, p.cps);
+    p.kp = 16 * tiles16(kc);
+    p.ok = buf_ok(ldx, 16) && buf_ok(ldy, kc);
+    p.vec = n % 4 == 0;
+    const int nt = tiles16(kc);
+    p.nt = nt <= 1 ? 1 : nt <= 2 ? 2 : nt <= 4 ? 4 : 8;
+    p.rt = (m >= 16 * 4 * 256 && nt <= 4) ? 4 : (m >= 16 * 2 * 256 ? 2 : 1);       // row tiles per wave: 16 accumulators at most
+    while (p.rt > 1 && !buf_ok(ldx, 16 * p.rt)) p.rt >>= 1;
+    p.d = p.nt == 1 ? 3 : 2;      // (three register sets in flight for k <= 16, where the kernel is a stream of A: 0.565 -> 0.509 ms at 65536 x 4096; two beyond)
+    p.gx = (unsigned)cdiv(cdiv(m, 16 * p.rt), 4);
+    p.v = p.nsplit > 1 ? reduce_v(kc, p.kp, m * p.kp, ws) : 0;
+    return p;
+}
+
+struct TnLaunch64 { TnPlan64 c; bool ok, vec; int nt, ct, kp, v; long ldp, nwaves; unsigned gx; };
+TnLaunch64 plan_tn_launch64(long m, long n, int kc, long ldy, long ldx, const void* ws) {
+    TnLaunch64 p;
+    p.c = plan_tn64(m, n, kc);
+    p.kp = 16 * tiles16(kc);
+    p.ldp = round_up(n, 16);
+    p.nwaves = p.c.nchunks * p.c.ncolblk;
+    p.gx = (unsigned)cdiv(p.nwaves, 4);
+    p.ok = buf_ok(ldx, 16) && buf_ok(ldy, 16);
+    const int nt = tiles16(kc);
+    p.nt = nt <= 1 ? 1 : nt <= 2 ? 2 : nt <= 4 ? 4 : 8;
+    p.ct = tn_ct(p.nt);
+    p.vec = n % p.ct == 0 && kc % std::min(p.nt, 4) == 0;
+    p.v = reduce_v(n, p.ldp, (long)p.kp * p.ldp, ws);
+    return p;
+}
+
+// the two m x n images (quotient, squared residual): f64_nn_cols_kernel
+struct NnColsLaunch64 { bool ok, vec; int ks, ct, ncolblk; long nchunks, rpw, nwaves; unsigned gx; };
+NnColsLaunch64 plan_nn_cols64(long m, long n, int kc, long ldx, long ldy, long lda, long ldo) {
+    NnColsLaunch64 p;
+    p.ks = kc <= 16 ? 4 : kc <= 32 ? 8 : kc <= 64 ? 16 : 32;
+    p.ct = nn_ct(p.ks);
+    p.ncolblk = (int)cdiv(n, 16 * p.ct);
+    long nch = std::max<long>(1, 2048 / p.ncolblk);
+    nch = std::min<long>(nch, std::max<long>(1, cdiv(m, 64)));
+    p.rpw = round_up(cdiv(m, nch), 16);
+    p.nchunks = cdiv(m, p.rpw);
+    p.nwaves = p.nchunks * p.ncolblk;
+    p.gx = (unsigned)cdiv(p.nwaves, 4);
+    p.ok = buf_ok(ldx, 16) && buf_ok(ldy, kc) && buf_ok(lda, 16) && buf_ok(ldo, 16);
+    p.vec = n % p.ct == 0 && kc % 4 == 0;
+    return p;
+}
+
+// the two MU updates: a wave owns 16 rows of W (all its columns) / 16 columns of H (all its rows)
+struct UpdLaunch64 { int ks; unsigned gx; };
+UpdLaunch64 plan_upd64(long len, int k) {
+    UpdLaunch64 p;
+    p.ks = k <= 16 ? 4 : k <= 32 ? 8 : k <= 64 ? 16 : 32;
+    p.gx = (unsigned)cdiv(cdiv(len, 16), 4);
+    return p;
+}
+
+struct ColsumLaunch64 { long slabs, rpc, chunks; unsigned gx; int v; };      // slabs: what the workspace is sized for (>= chunks)
+ColsumLaunch64 plan_colsum64(long m, long n, const void* ws) {
+    ColsumLaunch64 p;
+    p.slabs = std::max<long>(1, std::min<long>(cdiv(m, 64), 2048 / std::max<long>(1, cdiv(n, 256))));
+    p.rpc = cdiv(m, p.slabs);
+    p.chunks = cdiv(m, p.rpc);
+    p.gx = (unsigned)cdiv(n, 256);
+    p.v = reduce_v(n, n, n, ws);
+    return p;
+}
+inline int sum_parts64(long rows, long cols) { return (int)std::min<long>(1024, cdiv(rows * cols, 256 * 8)); }
+inline unsigned ew_grid64(long rows, long cols) { return (unsigned)std::min<long>(cdiv(rows * cols, 256), 8192); }
+
 int sum_all(bool sq, const double* X, long rows, long cols, long ldx, double* out, void* ws, size_t ws_bytes, hipStream_t st) {
-    const int nparts = (int)std::min<long>(1024, cdiv(rows * cols, 256 * 8));
+    const int nparts = sum_parts64(rows, cols);
     if (ws_bytes < (size_t)nparts * sizeof(double)) return fail(DNMF_EWS, "f64 sum: workspace too small");
     if (sq) hipLaunchKernelGGL(f64_sum_partial_kernel<true>, dim3(nparts), dim3(256), 0, st, X, rows, cols, ldx, (double*)ws);
     else hipLaunchKernelGGL(f64_sum_partial_kernel<false>, dim3(nparts), dim3(256), 0, st, X, rows, cols, ldx, (double*)ws);
@@ -589,53 +672,74 @@ int sum_all(bool sq, const double* X, long rows, long cols, long ldx, double* ou
 }
 
 int colsum_any(bool sq, const double* X, long m, long n, long ldx, double* x, void* ws, size_t ws_bytes, hipStream_t st) {
-    const long nch = std::max<long>(1, std::min<long>(cdiv(m, 64), 2048 / std::max<long>(1, cdiv(n, 256))));
-    const long rpc = cdiv(m, nch);
-    const long chunks = cdiv(m, rpc);
-    if (ws_bytes < (size_t)chunks * n * sizeof(double)) return fail(DNMF_EWS, "f64 colsum: workspace too small");
-    const dim3 grid((unsigned)cdiv(n, 256), (unsigned)chunks);
-    if (sq) hipLaunchKernelGGL(f64_colsum_partial_kernel<true>, grid, dim3(256), 0, st, X, m, n, ldx, rpc, (double*)ws);
-    else hipLaunchKernelGGL(f64_colsum_partial_kernel<false>, grid, dim3(256), 0, st, X, m, n, ldx, rpc, (double*)ws);
-    launch_reduce64((const double*)ws, n, n, (int)chunks, x, n, 1L, n, st);
+    const ColsumLaunch64 p = plan_colsum64(m, n, ws);
+    if (ws_bytes < (size_t)p.chunks * n * sizeof(double)) return fail(DNMF_EWS, "f64 colsum: workspace too small");
+    const dim3 grid(p.gx, (unsigned)p.chunks);
+    if (sq) hipLaunchKernelGGL(f64_colsum_partial_kernel<true>, grid, dim3(256), 0, st, X, m, n, ldx, p.rpc, (double*)ws);
+    else hipLaunchKernelGGL(f64_colsum_partial_kernel<false>, grid, dim3(256), 0, st, X, m, n, ldx, p.rpc, (double*)ws);
+    launch_reduce64((const double*)ws, n, n, (int)p.chunks, x, n, 1L, n, st);
     return check_launch("f64 colsum");
 }
 
+// the quotient / squared-residual image (MODE = NN_QUOT, NN_SQDIFF), column-resident
 template <int MODE>
-int launch_nn_rows(const double* X, long ldx, long m, int kc, const double* Y, long ldy, long n, const double* A, long lda, double* O, long ldo,
+int launch_nn_cols(const double* X, long ldx, long m, int kc, const double* Y, long ldy, long n, const double* A, long lda, double* O, long ldo,
                    double eps, hipStream_t st) {
-    if constexpr (MODE != NN_UPD_W) {
-        const int ks = kc <= 16 ? 4 : kc <= 32 ? 8 : kc <= 64 ? 16 : 32;
-        const int ncolblk = (int)cdiv(n, 16 * nn_ct(ks));
-        long nch = std::max<long>(1, 2048 / ncolblk);
-        nch = std::min<long>(nch, std::max<long>(1, cdiv(m, 64)));
-        const long rpw = round_up(cdiv(m, nch), 16);
-        const long nwaves = cdiv(m, rpw) * ncolblk;
-        if (!(buf_ok(ldx, 16) && buf_ok(ldy, kc) && buf_ok(lda, 16) && buf_ok(ldo, 16))) return fail(DNMF_EINVAL, "f64 nn(cols): a row pitch beyond the 2 GiB window of the float64 operand loads");
-        const bool vec = n % nn_ct(ks) == 0 && kc % 4 == 0;
-#define NNC_CASE(KS_) do { if (vec) hipLaunchKernelGGL((f64_nn_cols_kernel<KS_, MODE, true>), dim3((unsigned)cdiv(nwaves, 4)), dim3(256), 0, st, X, ldx, m, kc, Y, ldy, n, \
-                                                       A, lda, O, ldo, eps, rpw, ncolblk, nwaves); \
-                           else hipLaunchKernelGGL((f64_nn_cols_kernel<KS_, MODE, false>), dim3((unsigned)cdiv(nwaves, 4)), dim3(256), 0, st, X, ldx, m, kc, Y, ldy, n, \
-                                                   A, lda, O, ldo, eps, rpw, ncolblk, nwaves); } while (0)
-        if (ks == 4) NNC_CASE(4); else if (ks == 8) NNC_CASE(8); else if (ks == 16) NNC_CASE(16); else NNC_CASE(32);
+    static_assert(MODE == NN_QUOT || MODE == NN_SQDIFF, "the in-place W update runs on row strips");
+    const NnColsLaunch64 p = plan_nn_cols64(m, n, kc, ldx, ldy, lda, ldo);
+    if (!p.ok) return fail(DNMF_EINVAL, "f64 nn(cols): a row pitch beyond the 2 GiB window of the float64 operand loads");
+#define NNC_CASE(KS_) do { if (p.vec) hipLaunchKernelGGL((f64_nn_cols_kernel<KS_, MODE, true>), dim3(p.gx), dim3(256), 0, st, X, ldx, m, kc, Y, ldy, n, \
+                                                         A, lda, O, ldo, eps, p.rpw, p.ncolblk, p.nwaves); \
+                           else hipLaunchKernelGGL((f64_nn_cols_kernel<KS_, MODE, false>), dim3(p.gx), dim3(256), 0, st, X, ldx, m, kc, Y, ldy, n, \
+                                                   A, lda, O, ldo, eps, p.rpw, p.ncolblk, p.nwaves); } while (0)
+    if (p.ks == 4) NNC_CASE(4); else if (p.ks == 8) NNC_CASE(8); else if (p.ks == 16) NNC_CASE(16); else NNC_CASE(32);
 #undef NNC_CASE
-        return check_launch("f64 nn(cols)");
-    }
-    // column range per wave: the whole width for the in-place W update (the wave owns its rows), else about 8192 waves in all
-    long cpw = n;
-    if (MODE != NN_UPD_W) {
-        const long rowtiles = cdiv(m, 16);
-        const long want = std::max<long>(1, 8192 / rowtiles);
-        cpw = std::max<long>(64, round_up(cdiv(n, want), 16));
-    }
-    const dim3 grid((unsigned)cdiv(cdiv(m, 16), 4), (unsigned)cdiv(n, cpw));
-#define NN_CASE(KS_) hipLaunchKernelGGL((f64_nn_rows_kernel<KS_, MODE>), grid, dim3(256), 0, st, X, ldx, m, kc, Y, ldy, n, A, lda, O, ldo, eps, cpw)
-    if (kc <= 16) NN_CASE(4); else if (kc <= 32) NN_CASE(8); else if (kc <= 64) NN_CASE(16); else NN_CASE(32);
+    return check_launch("f64 nn(cols)");
+}
+
+// the in-place W update: a wave owns its rows over the whole width
+int launch_upd_w(double* W, long ldw, long m, int k, const double* G, long ldg, const double* AH, long ldah, double eps, hipStream_t st) {
+    const UpdLaunch64 p = plan_upd64(m, k);
+    const dim3 grid(p.gx, 1);
+#define NN_CASE(KS_) hipLaunchKernelGGL((f64_nn_rows_kernel<KS_, NN_UPD_W>), grid, dim3(256), 0, st, W, ldw, m, k, G, ldg, (long)k, AH, ldah, W, ldw, eps, (long)k)
+    if (p.ks == 4) NN_CASE(4); else if (p.ks == 8) NN_CASE(8); else if (p.ks == 16) NN_CASE(16); else NN_CASE(32);
 #undef NN_CASE
     return check_launch("f64 nn");
 }
 
 #include "dnmf_f64_kl.h"
 inline bool kl64_buf_ok(long lda, long ldw, long ldh, int k) { return buf_ok(lda, 16) && buf_ok(ldw, 16) && buf_ok(ldh, k); }
+// fused: the one-pass kernels of dnmf_f64_kl.h; otherwise the products go through the m x n image (dnmf_f64_kl_quot, then the NT / TN form)
+inline bool kl64_fused(long lda, long ldw, long ldh, int k) { return k <= KL64_MAX_K && kl64_buf_ok(lda, ldw, ldh, k); }
+
+struct KlUhtLaunch64 { KlUhtPlan c; bool vec, full; int nt, kp, v; unsigned gx; };      // c.rt: after the window fallback
+KlUhtLaunch64 plan_kl_uht_launch(long m, long n, int k, long lda, long ldw, const void* ws) {
+    KlUhtLaunch64 p;
+    p.c = plan_kl_uht(m, n, k);
+    p.kp = 16 * tiles16(k);
+    p.vec = n % 4 == 0;
+    while (p.c.rt > 1 && !(buf_ok(lda, 16 * p.c.rt) && buf_ok(ldw, 16 * p.c.rt))) p.c.rt >>= 1;
+    p.full = n % p.c.cps == 0 && p.c.cps % 64 == 0;          // every split a whole number of groups of four tiles: the mask-free kernel
+    const int nt = tiles16(k);
+    p.nt = nt <= 1 ? 1 : nt <= 2 ? 2 : 4;
+    p.gx = (unsigned)cdiv(cdiv(m, 16 * p.c.rt), 4);
+    p.v = p.c.nsplit > 1 ? reduce_v(k, p.kp, m * p.kp, ws) : 0;
+    return p;
+}
+struct KlWtuLaunch64 { KlWtuPlan c; bool vec; int nt, kp, v; long ldp, nwaves; unsigned gx; };
+KlWtuLaunch64 plan_kl_wtu_launch(long m, long n, int k, const void* ws) {
+    KlWtuLaunch64 p;
+    p.c = plan_kl_wtu(m, n, k);
+    p.kp = 16 * tiles16(k);
+    p.ldp = round_up(n, 16);
+    p.nwaves = p.c.nchunks * p.c.ncolblk;
+    p.gx = (unsigned)cdiv(p.nwaves, 4);
+    const int nt = tiles16(k);
+    p.nt = nt <= 1 ? 1 : nt <= 2 ? 2 : 4;
+    p.vec = n % p.c.ct == 0 && k % 4 == 0;
+    p.v = reduce_v(n, p.ldp, (long)p.kp * p.ldp, ws);
+    return p;
+}
 
 }  // namespace
 
@@ -646,9 +750,7 @@ extern "C" {
 size_t dnmf_f64_ws_bytes(long m, long n, int k) {
     if (k < 1 || k > DNMF_TUNED_MAX_K || m < 1 || n < 1) return 0;
     const size_t kp = 16 * tiles16(k), D = sizeof(double);
-    auto colsum_slabs = [](long rows, long cols) {
-        return (size_t)std::max<long>(1, std::min<long>(cdiv(rows, 64), 2048 / std::max<long>(1, cdiv(cols, 256)))) * cols;
-    };
+    auto colsum_slabs = [](long rows, long cols) { return (size_t)plan_colsum64(rows, cols, nullptr).slabs * cols; };
     size_t b = 2048 * D;                                                               // block partials of the sums
     b = std::max(b, (size_t)plan_tn64(m, n, k).nchunks * kp * round_up(n, 16) * D);       // W^T A
     b = std::max(b, (size_t)plan_tn64(m, k, k).nchunks * kp * round_up(k, 16) * D);       // W^T W
@@ -665,32 +767,24 @@ int dnmf_f64_aht(const double* X, long m, long n, long ldx, const double* Y, int
                  void* stream) {
     REQ(X && Y && C && m >= 1 && n >= 1 && kc >= 1 && kc <= DNMF_TUNED_MAX_K && ldx >= n && ldy >= n && ldc >= kc, "f64 aht: bad arguments");
     hipStream_t st = ST(stream);
-    const long ns = nt_splits(m, n);
-    const long cps = ns > 1 ? round_up(cdiv(n, ns), 16) : round_up(n, 16);
-    const long nsplit = cdiv(n, cps);
-    const int kp = 16 * tiles16(kc);
+    const NtLaunch64 p = plan_nt64(m, n, kc, ldx, ldy, ws);
     double* out = C; long ldo = ldc, sstride = 0;
-    if (nsplit > 1) {
-        if (!ws || ws_bytes < (size_t)nsplit * m * kp * sizeof(double)) return fail(DNMF_EWS, "f64 aht: workspace too small");
-        out = (double*)ws; ldo = kp; sstride = m * kp;
+    if (p.nsplit > 1) {
+        if (!ws || ws_bytes < (size_t)p.nsplit * m * p.kp * sizeof(double)) return fail(DNMF_EWS, "f64 aht: workspace too small");
+        out = (double*)ws; ldo = p.kp; sstride = m * p.kp;
     }
-    REQ(buf_ok(ldx, 16) && buf_ok(ldy, kc), "f64 aht: a row pitch beyond the 2 GiB window of the float64 operand loads");
-    const bool vec = n % 4 == 0;
-    const int nt = tiles16(kc);
-    int rt = (m >= 16 * 4 * 256 && nt <= 4) ? 4 : (m >= 16 * 2 * 256 ? 2 : 1);     // row tiles per wave: 16 accumulators at most
-    while (rt > 1 && !buf_ok(ldx, 16 * rt)) rt >>= 1;
-// (three register sets in flight for k <= 16, where the kernel is a stream of A: 0.565 -> 0.509 ms at 65536 x 4096; two beyond)
-#define NT_LAUNCH(RT_, NT_, VEC_) hipLaunchKernelGGL((f64_nt_kernel<RT_, NT_, VEC_, (NT_ == 1 ? 3 : 2)>), dim3((unsigned)cdiv(cdiv(m, 16 * RT_), 4), (unsigned)nsplit), dim3(256), 0, st, \
-                                                     X, ldx, m, n, Y, ldy, kc, out, ldo, sstride, cps)
-#define NT_CASE(RT_, NT_) do { if (vec) NT_LAUNCH(RT_, NT_, true); else NT_LAUNCH(RT_, NT_, false); } while (0)
-#define NT_ROWS(NT_) do { if (rt == 4) NT_CASE(4, NT_); else if (rt == 2) NT_CASE(2, NT_); else NT_CASE(1, NT_); } while (0)
-    if (nt <= 1) NT_ROWS(1); else if (nt <= 2) NT_ROWS(2); else if (nt <= 4) NT_ROWS(4); else if (rt >= 2) NT_CASE(2, 8); else NT_CASE(1, 8);
+    REQ(p.ok, "f64 aht: a row pitch beyond the 2 GiB window of the float64 operand loads");
+#define NT_LAUNCH(RT_, NT_, VEC_) hipLaunchKernelGGL((f64_nt_kernel<RT_, NT_, VEC_, (NT_ == 1 ? 3 : 2)>), dim3(p.gx, (unsigned)p.nsplit), dim3(256), 0, st, \
+                                                     X, ldx, m, n, Y, ldy, kc, out, ldo, sstride, p.cps)
+#define NT_CASE(RT_, NT_) do { if (p.vec) NT_LAUNCH(RT_, NT_, true); else NT_LAUNCH(RT_, NT_, false); } while (0)
+#define NT_ROWS(NT_) do { if (p.rt == 4) NT_CASE(4, NT_); else if (p.rt == 2) NT_CASE(2, NT_); else NT_CASE(1, NT_); } while (0)
+    if (p.nt == 1) NT_ROWS(1); else if (p.nt == 2) NT_ROWS(2); else if (p.nt == 4) NT_ROWS(4); else if (p.rt == 2) NT_CASE(2, 8); else NT_CASE(1, 8);
 #undef NT_ROWS
 #undef NT_CASE
 #undef NT_LAUNCH
     int rc = check_launch("f64 aht");
-    if (rc || nsplit == 1) return rc;
-    launch_reduce64((const double*)ws, sstride, ldo, (int)nsplit, C, ldc, m, (long)kc, st);
+    if (rc || p.nsplit == 1) return rc;
+    launch_reduce64((const double*)ws, sstride, ldo, (int)p.nsplit, C, ldc, m, (long)kc, st);
     return check_launch("f64 aht(reduce)");
 }
 
@@ -699,32 +793,26 @@ int dnmf_f64_wta(const double* Y, long m, long n, long ldy, const double* X, int
                  void* stream) {
     REQ(X && Y && C && ws && m >= 1 && n >= 1 && kc >= 1 && kc <= DNMF_TUNED_MAX_K && ldy >= n && ldx >= kc && ldc >= n, "f64 wta: bad arguments");
     hipStream_t st = ST(stream);
-    const TnPlan64 p = plan_tn64(m, n, kc);
-    const int kp = 16 * tiles16(kc);
-    const long ldp = round_up(n, 16);
-    if (ws_bytes < (size_t)p.nchunks * kp * ldp * sizeof(double)) return fail(DNMF_EWS, "f64 wta: workspace too small");
-    const long nwaves = p.nchunks * p.ncolblk;
-    const dim3 grid((unsigned)cdiv(nwaves, 4));
-    REQ(buf_ok(ldx, 16) && buf_ok(ldy, 16), "f64 wta: a row pitch beyond the 2 GiB window of the float64 operand loads");
-    const int nt = tiles16(kc);
-    const int ntk = nt <= 1 ? 1 : nt <= 2 ? 2 : nt <= 4 ? 4 : 8;                    // the instantiation below
-    const bool vec = n % tn_ct(ntk) == 0 && kc % std::min(ntk, 4) == 0;
-#define TN_CASE(NT_) do { if (vec) hipLaunchKernelGGL((f64_tn_kernel<NT_, true>), grid, dim3(256), 0, st, X, ldx, kc, Y, ldy, n, m, p.rows_per_chunk, p.ncolblk, nwaves, \
-                                                      (double*)ws, (long)kp * ldp, ldp); \
-                          else hipLaunchKernelGGL((f64_tn_kernel<NT_, false>), grid, dim3(256), 0, st, X, ldx, kc, Y, ldy, n, m, p.rows_per_chunk, p.ncolblk, nwaves, \
-                                                  (double*)ws, (long)kp * ldp, ldp); } while (0)
-    if (nt <= 1) TN_CASE(1); else if (nt <= 2) TN_CASE(2); else if (nt <= 4) TN_CASE(4); else TN_CASE(8);
+    const TnLaunch64 p = plan_tn_launch64(m, n, kc, ldy, ldx, ws);
+    if (ws_bytes < (size_t)p.c.nchunks * p.kp * p.ldp * sizeof(double)) return fail(DNMF_EWS, "f64 wta: workspace too small");
+    const dim3 grid(p.gx);
+    REQ(p.ok, "f64 wta: a row pitch beyond the 2 GiB window of the float64 operand loads");
+#define TN_CASE(NT_) do { if (p.vec) hipLaunchKernelGGL((f64_tn_kernel<NT_, true>), grid, dim3(256), 0, st, X, ldx, kc, Y, ldy, n, m, p.c.rows_per_chunk, p.c.ncolblk, p.nwaves, \
+                                                        (double*)ws, (long)p.kp * p.ldp, p.ldp); \
+                          else hipLaunchKernelGGL((f64_tn_kernel<NT_, false>), grid, dim3(256), 0, st, X, ldx, kc, Y, ldy, n, m, p.c.rows_per_chunk, p.c.ncolblk, p.nwaves, \
+                                                  (double*)ws, (long)p.kp * p.ldp, p.ldp); } while (0)
+    if (p.nt == 1) TN_CASE(1); else if (p.nt == 2) TN_CASE(2); else if (p.nt == 4) TN_CASE(4); else TN_CASE(8);
 #undef TN_CASE
     int rc = check_launch("f64 wta");
     if (rc) return rc;
-    launch_reduce64((const double*)ws, (long)kp * ldp, ldp, (int)p.nchunks, C, ldc, (long)kc, n, st);
+    launch_reduce64((const double*)ws, (long)p.kp * p.ldp, p.ldp, (int)p.c.nchunks, C, ldc, (long)kc, n, st);
     return check_launch("f64 wta(reduce)");
 }
 
 // W *= AH / (W G + eps)  (dist_nmf.py:731-732, :244-245)
 int dnmf_f64_mu_update_w(double* W, long m, int k, long ldw, const double* AH, long ldah, const double* G, long ldg, double eps, void* stream) {
     REQ(W && AH && G && m >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K && ldw >= k && ldah >= k && ldg >= k, "f64 mu_update_w: bad arguments");
-    return launch_nn_rows<NN_UPD_W>(W, ldw, m, k, G, ldg, k, AH, ldah, W, ldw, eps, ST(stream));
+    return launch_upd_w(W, ldw, m, k, G, ldg, AH, ldah, eps, ST(stream));
 }
 
 // H *= AtW / (G H + eps), clamp: H = max(H, eps) afterwards  (dist_nmf.py:750-751, :224-225; pyDNMF.py:156)
@@ -732,9 +820,10 @@ int dnmf_f64_mu_update_h(double* H, int k, long n, long ldh, const double* AtW, 
                          void* stream) {
     REQ(H && AtW && G && n >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K && ldh >= n && ldatw >= n && ldg >= k, "f64 mu_update_h: bad arguments");
     hipStream_t st = ST(stream);
-    const dim3 grid((unsigned)cdiv(cdiv(n, 16), 4));
+    const UpdLaunch64 p = plan_upd64(n, k);
+    const dim3 grid(p.gx);
 #define UH_CASE(KS_) hipLaunchKernelGGL((f64_upd_h_kernel<KS_>), grid, dim3(256), 0, st, H, k, n, ldh, AtW, ldatw, G, ldg, eps, clamp)
-    if (k <= 16) UH_CASE(4); else if (k <= 32) UH_CASE(8); else if (k <= 64) UH_CASE(16); else UH_CASE(32);
+    if (p.ks == 4) UH_CASE(4); else if (p.ks == 8) UH_CASE(8); else if (p.ks == 16) UH_CASE(16); else UH_CASE(32);
 #undef UH_CASE
     return check_launch("f64 mu_update_h");
 }
@@ -743,7 +832,7 @@ int dnmf_f64_mu_update_h(double* H, int k, long n, long ldh, const double* AtW, 
 int dnmf_f64_kl_quot(const double* A, long m, long n, long lda, const double* W, long ldw, const double* H, long ldh, int k, double eps,
                      double* U, long ldu, void* stream) {
     REQ(A && W && H && U && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K && lda >= n && ldw >= k && ldh >= n && ldu >= n, "f64 kl_quot: bad arguments");
-    return launch_nn_rows<NN_QUOT>(W, ldw, m, k, H, ldh, n, A, lda, U, ldu, eps, ST(stream));
+    return launch_nn_cols<NN_QUOT>(W, ldw, m, k, H, ldh, n, A, lda, U, ldu, eps, ST(stream));
 }
 
 // S[m x k] = (A / (W H + eps)) H^T  (dist_nmf.py:806, :810) -- k <= 64: one pass over A, the quotient never leaves the registers
@@ -751,34 +840,29 @@ int dnmf_f64_kl_quot(const double* A, long m, long n, long lda, const double* W,
 int dnmf_f64_kl_uht(const double* A, long m, long n, long lda, const double* W, long ldw, const double* H, long ldh, int k, double eps,
                     double* S, long lds_, double* U, void* ws, size_t ws_bytes, void* stream) {
     REQ(A && W && H && S && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K && lda >= n && ldw >= k && ldh >= n && lds_ >= k, "f64 kl_uht: bad arguments");
-    if (k > KL64_MAX_K || !kl64_buf_ok(lda, ldw, ldh, k)) {
+    if (!kl64_fused(lda, ldw, ldh, k)) {
         REQ(U, "f64 kl_uht: k = %d > %d needs the m x n image U", k, KL64_MAX_K);
         int rc = dnmf_f64_kl_quot(A, m, n, lda, W, ldw, H, ldh, k, eps, U, n, stream);
         return rc ? rc : dnmf_f64_aht(U, m, n, n, H, k, ldh, S, lds_, ws, ws_bytes, stream);
     }
     hipStream_t st = ST(stream);
-    KlUhtPlan p = plan_kl_uht(m, n, k);
-    const int kp = 16 * tiles16(k);
+    const KlUhtLaunch64 p = plan_kl_uht_launch(m, n, k, lda, ldw, ws);
     double* out = S; long ldo = lds_, sstride = 0;
-    if (p.nsplit > 1) {
-        if (!ws || ws_bytes < (size_t)p.nsplit * m * kp * sizeof(double)) return fail(DNMF_EWS, "f64 kl_uht: workspace too small");
-        out = (double*)ws; ldo = kp; sstride = m * kp;
+    if (p.c.nsplit > 1) {
+        if (!ws || ws_bytes < (size_t)p.c.nsplit * m * p.kp * sizeof(double)) return fail(DNMF_EWS, "f64 kl_uht: workspace too small");
+        out = (double*)ws; ldo = p.kp; sstride = m * p.kp;
     }
-    const bool vec = n % 4 == 0;
-    while (p.rt > 1 && !(buf_ok(lda, 16 * p.rt) && buf_ok(ldw, 16 * p.rt))) p.rt >>= 1;
-    const bool full = n % p.cps == 0 && p.cps % 64 == 0;          // every split a whole number of groups of four tiles: the mask-free kernel
-#define UHT_LAUNCH(NT_, RT_, VEC_, FULL_) hipLaunchKernelGGL((f64_kl_uht_kernel<NT_, RT_, VEC_, FULL_>), dim3((unsigned)cdiv(cdiv(m, 16 * RT_), 4), (unsigned)p.nsplit), dim3(256), 0, st, \
-                                                             A, lda, m, n, W, ldw, H, ldh, k, eps, out, ldo, sstride, p.cps)
-#define UHT_CASE(NT_, RT_) do { if (full) UHT_LAUNCH(NT_, RT_, true, true); else if (vec) UHT_LAUNCH(NT_, RT_, true, false); else UHT_LAUNCH(NT_, RT_, false, false); } while (0)
-    const int nt = tiles16(k);
-    if (nt <= 2 && p.rt >= 4) { if (nt <= 1) UHT_CASE(1, 4); else UHT_CASE(2, 4); }
-    else if (p.rt >= 2) { if (nt <= 1) UHT_CASE(1, 2); else if (nt <= 2) UHT_CASE(2, 2); else UHT_CASE(4, 2); }
-    else { if (nt <= 1) UHT_CASE(1, 1); else if (nt <= 2) UHT_CASE(2, 1); else UHT_CASE(4, 1); }
+#define UHT_LAUNCH(NT_, RT_, VEC_, FULL_) hipLaunchKernelGGL((f64_kl_uht_kernel<NT_, RT_, VEC_, FULL_>), dim3(p.gx, (unsigned)p.c.nsplit), dim3(256), 0, st, \
+                                                             A, lda, m, n, W, ldw, H, ldh, k, eps, out, ldo, sstride, p.c.cps)
+#define UHT_CASE(NT_, RT_) do { if (p.full) UHT_LAUNCH(NT_, RT_, true, true); else if (p.vec) UHT_LAUNCH(NT_, RT_, true, false); else UHT_LAUNCH(NT_, RT_, false, false); } while (0)
+    if (p.c.rt == 4) { if (p.nt == 1) UHT_CASE(1, 4); else UHT_CASE(2, 4); }
+    else if (p.c.rt == 2) { if (p.nt == 1) UHT_CASE(1, 2); else if (p.nt == 2) UHT_CASE(2, 2); else UHT_CASE(4, 2); }
+    else { if (p.nt == 1) UHT_CASE(1, 1); else if (p.nt == 2) UHT_CASE(2, 1); else UHT_CASE(4, 1); }
 #undef UHT_LAUNCH
 #undef UHT_CASE
     int rc = check_launch("f64 kl_uht");
-    if (rc || p.nsplit == 1) return rc;
-    launch_reduce64((const double*)ws, sstride, ldo, (int)p.nsplit, S, lds_, m, (long)k, st);
+    if (rc || p.c.nsplit == 1) return rc;
+    launch_reduce64((const double*)ws, sstride, ldo, (int)p.c.nsplit, S, lds_, m, (long)k, st);
     return check_launch("f64 kl_uht(reduce)");
 }
 
@@ -786,29 +870,24 @@ int dnmf_f64_kl_uht(const double* A, long m, long n, long lda, const double* W, 
 int dnmf_f64_kl_wtu(const double* A, long m, long n, long lda, const double* W, long ldw, const double* H, long ldh, int k, double eps,
                     double* S, long lds_, double* U, void* ws, size_t ws_bytes, void* stream) {
     REQ(A && W && H && S && ws && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K && lda >= n && ldw >= k && ldh >= n && lds_ >= n, "f64 kl_wtu: bad arguments");
-    if (k > KL64_MAX_K || !kl64_buf_ok(lda, ldw, ldh, k)) {
+    if (!kl64_fused(lda, ldw, ldh, k)) {
         REQ(U, "f64 kl_wtu: k = %d > %d needs the m x n image U", k, KL64_MAX_K);
         int rc = dnmf_f64_kl_quot(A, m, n, lda, W, ldw, H, ldh, k, eps, U, n, stream);
         return rc ? rc : dnmf_f64_wta(U, m, n, n, W, k, ldw, S, lds_, ws, ws_bytes, stream);
     }
     hipStream_t st = ST(stream);
-    const KlWtuPlan p = plan_kl_wtu(m, n, k);
-    const int kp = 16 * tiles16(k);
-    const long ldp = round_up(n, 16);
-    if (ws_bytes < (size_t)p.nchunks * kp * ldp * sizeof(double)) return fail(DNMF_EWS, "f64 kl_wtu: workspace too small");
-    const long nwaves = p.nchunks * p.ncolblk;
-    const dim3 grid((unsigned)cdiv(nwaves, 4));
-    const int nt = tiles16(k);
-    const bool vec = n % p.ct == 0 && k % 4 == 0;
-#define WTU_CASE(NT_) do { if (vec) hipLaunchKernelGGL((f64_kl_wtu_kernel<NT_, kl_ct(NT_), true>), grid, dim3(256), 0, st, A, lda, m, n, W, ldw, H, ldh, k, eps, \
-                                                       p.rows_per_chunk, p.ncolblk, nwaves, (double*)ws, (long)kp * ldp, ldp); \
+    const KlWtuLaunch64 p = plan_kl_wtu_launch(m, n, k, ws);
+    if (ws_bytes < (size_t)p.c.nchunks * p.kp * p.ldp * sizeof(double)) return fail(DNMF_EWS, "f64 kl_wtu: workspace too small");
+    const dim3 grid(p.gx);
+#define WTU_CASE(NT_) do { if (p.vec) hipLaunchKernelGGL((f64_kl_wtu_kernel<NT_, kl_ct(NT_), true>), grid, dim3(256), 0, st, A, lda, m, n, W, ldw, H, ldh, k, eps, \
+                                                         p.c.rows_per_chunk, p.c.ncolblk, p.nwaves, (double*)ws, (long)p.kp * p.ldp, p.ldp); \
                            else hipLaunchKernelGGL((f64_kl_wtu_kernel<NT_, kl_ct(NT_), false>), grid, dim3(256), 0, st, A, lda, m, n, W, ldw, H, ldh, k, eps, \
-                                                   p.rows_per_chunk, p.ncolblk, nwaves, (double*)ws, (long)kp * ldp, ldp); } while (0)
-    if (nt <= 1) WTU_CASE(1); else if (nt <= 2) WTU_CASE(2); else WTU_CASE(4);
+                                                   p.c.rows_per_chunk, p.c.ncolblk, p.nwaves, (double*)ws, (long)p.kp * p.ldp, p.ldp); } while (0)
+    if (p.nt == 1) WTU_CASE(1); else if (p.nt == 2) WTU_CASE(2); else WTU_CASE(4);
 #undef WTU_CASE
     int rc = check_launch("f64 kl_wtu");
     if (rc) return rc;
-    launch_reduce64((const double*)ws, (long)kp * ldp, ldp, (int)p.nchunks, S, lds_, (long)k, n, st);
+    launch_reduce64((const double*)ws, (long)p.kp * p.ldp, p.ldp, (int)p.c.nchunks, S, lds_, (long)k, n, st);
     return check_launch("f64 kl_wtu(reduce)");
 }
 
@@ -816,7 +895,7 @@ int dnmf_f64_kl_wtu(const double* A, long m, long n, long lda, const double* W, 
 int dnmf_f64_sqdiff(const double* A, long m, long n, long lda, const double* W, long ldw, const double* H, long ldh, int k, double* R, long ldr,
                     void* stream) {
     REQ(A && W && H && R && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K && lda >= n && ldw >= k && ldh >= n && ldr >= n, "f64 sqdiff: bad arguments");
-    return launch_nn_rows<NN_SQDIFF>(W, ldw, m, k, H, ldh, n, A, lda, R, ldr, 0.0, ST(stream));
+    return launch_nn_cols<NN_SQDIFF>(W, ldw, m, k, H, ldh, n, A, lda, R, ldr, 0.0, ST(stream));
 }
 
 // *out = sum X (sq == 0) or sum X^2 (sq != 0) over a rows x cols matrix, fixed summation order
@@ -844,7 +923,7 @@ int dnmf_f64_ew(int op, double* X, long rows, long cols, long ldx, const double*
                 void* stream) {
     REQ(X && rows >= 1 && cols >= 1 && ldx >= cols && op >= 0 && op <= 4 && (op == E_CLAMP || x) && (op < E_KL_BYROW || (Sm && lds_ >= cols)),
         "f64 ew: bad arguments");
-    const unsigned grid = (unsigned)std::min<long>(cdiv(rows * cols, 256), 8192);
+    const unsigned grid = ew_grid64(rows, cols);
     hipLaunchKernelGGL(f64_ew_kernel, dim3(grid), dim3(256), 0, ST(stream), op, X, rows, cols, ldx, Sm, lds_, x, eps, clamp);
     return check_launch("f64 ew");
 }
@@ -961,6 +1040,63 @@ int dnmf_f64_fit(int method, const double* A, long m, long n, long lda, double* 
     F64(dnmf_f64_sum(A, m, n, lda, 1, sq + 1, prim, prim_bytes, stream));
 #undef F64
     if (hipMemcpyAsync(sq_out, sq, 2 * D, hipMemcpyDeviceToDevice, ST(stream)) != hipSuccess) return fail(DNMF_EHIP, "f64 fit: copy of the squared norms failed");
+    return DNMF_OK;
+}
+
+// Which kernel an entry point launches for a shape, host arithmetic only: the plan structs the entry points launch from (include/dnmf.h
+// lists the fields).  ld: the pitches that enter the 2 GiB window checks, in the order of the entry point's own arguments (NULL: packed)
+int dnmf_f64_plan(int op, long m, long n, int k, const long* ld, int method, long out[DNMF_F64_PLAN_LEN]) {
+    REQ(out && op >= DNMF_F64_OP_AHT && op <= DNMF_F64_OP_FIT && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K, "f64 plan: bad arguments");
+    for (int i = 0; i < DNMF_F64_PLAN_LEN; ++i) out[i] = 0;
+    auto L = [&](int i, long packed) { return ld && ld[i] > 0 ? ld[i] : packed; };
+    auto set = [&](long fam, long nt, long rt, long vec, long full, long d, long count, long per, long v, long gx, long gy, long nwaves) {
+        const long f[DNMF_F64_PLAN_LEN] = {fam, nt, rt, vec, full, d, count, per, v, gx, gy, nwaves};
+        for (int i = 0; i < DNMF_F64_PLAN_LEN; ++i) out[i] = f[i];
+    };
+    auto nt_form = [&](long ldx, long ldy) {
+        const NtLaunch64 p = plan_nt64(m, n, k, ldx, ldy, nullptr);
+        if (p.ok) set(DNMF_F64_FAM_NT, p.nt, p.rt, p.vec, 0, p.d, p.nsplit, p.cps, p.v, p.gx, p.nsplit, 4L * p.gx);
+    };
+    auto tn_form = [&](long ldy, long ldx) {
+        const TnLaunch64 p = plan_tn_launch64(m, n, k, ldy, ldx, nullptr);
+        if (p.ok) set(DNMF_F64_FAM_TN, p.nt, p.ct, p.vec, 0, 2, p.c.nchunks, p.c.rows_per_chunk, p.v, p.gx, 1, p.nwaves);
+    };
+    switch (op) {
+    case DNMF_F64_OP_AHT: nt_form(L(0, n), L(1, n)); break;
+    case DNMF_F64_OP_WTA: tn_form(L(0, n), L(1, k)); break;
+    case DNMF_F64_OP_KL_UHT: {
+        if (!kl64_fused(L(0, n), L(1, k), L(2, n), k)) { set(DNMF_F64_FAM_IMAGE, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0); break; }
+        const KlUhtLaunch64 p = plan_kl_uht_launch(m, n, k, L(0, n), L(1, k), nullptr);
+        set(DNMF_F64_FAM_KL_UHT, p.nt, p.c.rt, p.full || p.vec, p.full, 2, p.c.nsplit, p.c.cps, p.v, p.gx, p.c.nsplit, 4L * p.gx);
+        break;
+    }
+    case DNMF_F64_OP_KL_WTU: {
+        if (!kl64_fused(L(0, n), L(1, k), L(2, n), k)) { set(DNMF_F64_FAM_IMAGE, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0); break; }
+        const KlWtuLaunch64 p = plan_kl_wtu_launch(m, n, k, nullptr);
+        set(DNMF_F64_FAM_KL_WTU, p.nt, p.c.ct, p.vec, 0, 2, p.c.nchunks, p.c.rows_per_chunk, p.v, p.gx, 1, p.nwaves);
+        break;
+    }
+    case DNMF_F64_OP_KL_QUOT:
+    case DNMF_F64_OP_SQDIFF: {
+        const NnColsLaunch64 p = plan_nn_cols64(m, n, k, L(1, k), L(2, n), L(0, n), L(3, n));
+        if (p.ok) set(DNMF_F64_FAM_NN_COLS, p.ks, p.ct, p.vec, 0, 2, p.nchunks, p.rpw, 0, p.gx, 1, p.nwaves);
+        break;
+    }
+    case DNMF_F64_OP_MU_UPDATE_W: { const UpdLaunch64 p = plan_upd64(m, k); set(DNMF_F64_FAM_NN_ROWS, p.ks, 1, 0, 0, 1, 1, k, 0, p.gx, 1, 4L * p.gx); break; }
+    case DNMF_F64_OP_MU_UPDATE_H: { const UpdLaunch64 p = plan_upd64(n, k); set(DNMF_F64_FAM_UPD_H, p.ks, 1, 0, 0, 1, 1, k, 0, p.gx, 1, 4L * p.gx); break; }
+    case DNMF_F64_OP_SUM: { const int parts = sum_parts64(m, n); set(DNMF_F64_FAM_SUM, 0, 0, 0, 0, 0, parts, 0, 0, parts, 1, 0); break; }
+    case DNMF_F64_OP_COLSUM: {
+        const ColsumLaunch64 p = plan_colsum64(m, n, nullptr);
+        set(DNMF_F64_FAM_COLSUM, 0, 0, 0, 0, 0, p.chunks, p.rpc, p.v, p.gx, p.chunks, 0);
+        break;
+    }
+    case DNMF_F64_OP_EW: set(DNMF_F64_FAM_EW, 0, 0, 0, 0, 0, 1, 0, 0, ew_grid64(m, n), 1, 0); break;
+    default: {
+        REQ(method >= 0 && method <= 2, "f64 plan: bad method");
+        const bool tiny = dnmf_f64_fit_tiny(m, n, k, method) != 0;
+        set(tiny ? DNMF_F64_FAM_FIT_TINY : DNMF_F64_FAM_FIT_CHAIN, 0, 0, 0, 0, 0, 1, 0, 0, tiny ? 1 : 0, tiny ? 1 : 0, 0);
+    }
+    }
     return DNMF_OK;
 }
 

@@ -32,6 +32,12 @@ __host__ __device__ inline size_t f64_tiny_lds_doubles(long m, long n, int k, in
     return (size_t)m * n * (method == 1 ? 2 : 1) + (size_t)(m + n) * k + (size_t)std::max<long>(m * k, (long)k * n) + (size_t)k * k + k + TINY_T;
 }
 
+// the shapes the kernel takes (dnmf_f64_fit_tiny reports it, dnmf_f64_tiny_fit_ launches by it)
+inline bool f64_tiny_takes(long m, long n, int k, int method) {
+    return m >= 1 && n >= 1 && k >= 1 && k <= 16 && m <= 4096 && n <= 4096 && method >= 0 && method <= 2 &&
+           f64_tiny_lds_doubles(m, n, k, method) * sizeof(double) <= 160 * 1024 - 64;
+}
+
 // sum of v over the workgroup's threads, the same value in all of them (fixed tree)
 __device__ __forceinline__ double tiny_sum(double v, double* red) {
     __syncthreads();
@@ -233,9 +239,8 @@ __global__ __launch_bounds__(TINY_T) void f64_tiny_fit_kernel(TinyArgs a) {
 __attribute__((visibility("hidden"))) int dnmf_f64_tiny_fit_(int method, const double* A, long m, long n, long lda, long a_stride, double* W, long ldw,
                                                               long w_stride, double* H, long ldh, long h_stride, int k, double eps, int w_update, int itr,
                                                               int batch, double* sq_out, long sq_stride, void* stream) {
-    if (k > 16 || m > 4096 || n > 4096 || itr < 1 || batch < 1) return 1;
+    if (!f64_tiny_takes(m, n, k, method) || itr < 1 || batch < 1) return 1;
     const size_t lds = f64_tiny_lds_doubles(m, n, k, method) * sizeof(double);
-    if (lds > 160 * 1024 - 64) return 1;
     static bool once = false;
     if (!once) { allow_lds(f64_tiny_fit_kernel, 160 * 1024); once = true; }
     TinyArgs a{};
@@ -249,8 +254,7 @@ __attribute__((visibility("hidden"))) int dnmf_f64_tiny_fit_(int method, const d
 extern "C" {
 
 int dnmf_f64_fit_tiny(long m, long n, int k, int method) {
-    return (m >= 1 && n >= 1 && k >= 1 && k <= 16 && m <= 4096 && n <= 4096 && method >= 0 && method <= 2 &&
-            f64_tiny_lds_doubles(m, n, k, method) * sizeof(double) <= 160 * 1024 - 64) ? 1 : 0;
+    return f64_tiny_takes(m, n, k, method) ? 1 : 0;
 }
 
 }  // extern "C"

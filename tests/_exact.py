@@ -24,7 +24,9 @@ def _bound(total, unit, dtype, what):
 def products(m, n, k, dtype=np.float32, seed=0):
     """A in 0..7, W and H in 1..3 with some zero rows / columns: A H^T, W^T A, the Grams, and the MU denominators W (H H^T),
     (W^T W) H are integers.  The denominators are 0 (a zero row of W / column of H: that factor element stays 0) or >= 2 and
-    below 2^22, so eps is absorbed in every order (an integer below 2^22 is an even number of its own ulps)."""
+    below 2^22, so eps is absorbed in every order (an integer below 2^22 is an even number of its own ulps).  float64: below 2^51,
+    where an integer >= 2 absorbs eps = 2^-52 the same way (it is at most half an ulp, and at 2 and 3, where it is exactly half, the
+    integer's last bit is even)."""
     rs = np.random.RandomState(seed + 1009 * m + 17 * n + k)
     A = rs.randint(0, 8, size=(m, n)).astype(dtype)
     A[rs.rand(m, n) < 0.2] = 0
@@ -38,7 +40,7 @@ def products(m, n, k, dtype=np.float32, seed=0):
     for tot, what in ((A64 @ H64.T, "A H^T"), (W64.T @ A64, "W^T A"), (G, "H H^T"), (GW, "W^T W")):
         _bound(tot, 1.0, dtype, what)
     for d, what in ((dw, "W HH^T"), (dh, "W^TW H")):
-        _bound(d, 0.25, np.float32, what)           # below 2^22
+        _bound(d, 0.25, dtype, what)                # below 2^22 (float64: 2^51 -- an integer in [2, 2^51) absorbs 2^-52 as well)
         assert np.all((d == 0) | (d >= 2)), what
     return A, W, H
 
@@ -85,7 +87,7 @@ def fro_step(m, n, k, dtype=np.float32, seed=0, tmax=6):
     cnt = AH / 2.0 ** a * 2.0 ** np.array(t)                     # nonzeros of A per row and group
     assert np.array_equal(Wn, 2.0 ** a * cnt)
     num, den = Wn.T @ A, (Wn.T @ Wn) @ H
-    _bound(cnt.T @ cnt, 0.25, np.float32, "H-phase denominators")                 # below 2^22 units of 2^(2a - t_g) >= 2
+    _bound(cnt.T @ cnt, 0.25, dtype, "H-phase denominators")                      # below 2^22 (float64: 2^51) units of 2^(2a - t_g) >= 2
     _bound(num, 2.0 ** (2 * a), dtype, "W_new^T A")
     assert np.all((den == 0) | (den >= 2)), "an H-phase denominator in (0, 2): raise a"
     Hq = np.where(den > 0, H * num / np.where(den > 0, den, 1.0), 0.0)
@@ -1239,6 +1241,63 @@ X6_KL = [
 ]
 # A of 256 MiB: the instantiations that stream A past the caches (id, m, n, k, bf16-stored A, plan)
 X6_STREAMED = [("f32-32768x2048-k40", 32768, 2048, 40, False, (2, 4, 128, 256)), ("bf16-65536x2048-k40", 65536, 2048, 40, True, (2, 2, 128, 512))]
+
+
+# ---------------------------------------------------------------------------------------------------------- float64 shape table
+# The shapes of tests/test_gpu_exact_f64.py, each with the kernel variant it is there for, stated here and not asked of the library: tests/test_f64_plan.py
+# asserts on the CPU, through dnmf_f64_plan, that every shape reaches its variant and that the table covers every instantiation the
+# dispatch of csrc/dnmf_f64.hip can launch and both sides of its host branches; the GPU test asserts it again before it launches.
+# Pitches beyond the 2 GiB descriptor window (buf_ok false: the `rt >>= 1` fallbacks and the refusals) need operands of hundreds of GB
+# and are not covered.
+# f64_nt_kernel<RT, NT, VEC> (aht; gram_hht is the same entry point at m = k): (m, n, k, RT, NT, VEC, splits, V)
+F64_AHT = (
+    [(40, n, 9, 1, 1, n % 4 == 0, 1, 0) for n in (70, 100, 130)]                 # NT = 1 is a ring of three: 3, 4, 5 trips of 32 columns
+    + [(40, n, k, 1, nt, n % 4 == 0, 1, 0) for k, nt in ((9, 1), (20, 2), (40, 4), (100, 8)) for n in (70, 72) if (k, n) != (9, 70)]
+    + [(600, 70, 20, 1, 2, False, 1, 0)]                                          # ten workgroups, the last wave ragged
+    + [(8200, n, k, 2, nt, n % 4 == 0, 1, 0) for k, nt in ((9, 1), (20, 2), (40, 4), (100, 8)) for n in (70, 72)]
+    + [(16400, n, k, 4, nt, n % 4 == 0, 1, 0) for k, nt in ((9, 1), (20, 2), (40, 4)) for n in (70, 72)]      # 16400 % 64 = 16: a ragged last wave
+    + [(600, 1100, 9, 1, 1, True, 2, 1), (600, 1100, 20, 1, 2, True, 2, 2), (600, 1100, 40, 1, 4, True, 2, 2),      # splits of 560 + 540 columns
+       (600, 1100, 100, 1, 8, True, 2, 2), (700, 1502, 33, 1, 4, False, 2, 1)])
+# f64_tn_kernel<NT, VEC> (wta; gram_wtw is the same entry point at n = k): (m, n, k, NT, CT, VEC, chunks, rows per chunk, V).
+# m = 40: one chunk; 130: chunks of 48 rows (the two-set ring ends on a half step); 600: ten chunks of 64, the last of 24
+F64_WTA = [(m, n, k, nt, ct, vec, ch, rpc, 2 - n % 2)
+           for m, ch, rpc in ((40, 1, 48), (130, 3, 48), (600, 10, 64))
+           for n, k, nt, ct, vec in ((72, 9, 1, 4, True), (70, 9, 1, 4, False), (71, 9, 1, 4, False), (72, 20, 2, 4, True), (72, 21, 2, 4, False),
+                                     (72, 40, 4, 4, True), (71, 40, 4, 4, False), (70, 100, 8, 2, True), (71, 100, 8, 2, False))]
+# f64_kl_uht_kernel<NT, RT, VEC, FULL>: (m, n, k, NT, RT, VEC, FULL, splits, V); n = 64 / 68 / 70: mask-free / vector / generic
+F64_KL_UHT = (
+    [(m, n, k, nt, rt, n % 4 == 0, n == 64, 1, 0)
+     for m, rt, ks in ((40, 1, ((9, 1), (20, 2), (40, 4))), (32800, 2, ((9, 1), (30, 2), (64, 4))), (65500, 4, ((9, 1), (20, 2))))
+     for k, nt in ks for n in (64, 68, 70)]
+    + [(1000, 2048, k, nt, 1, True, True, 4, 2 - k % 2) for k, nt in ((9, 1), (20, 2), (40, 4))]             # four whole splits of 512
+    + [(700, 1500, k, nt, 1, True, False, 2, 2 - k % 2) for k, nt in ((9, 1), (20, 2), (40, 4))]             # 768 + 732 columns
+    + [(700, 1502, 9, 1, 1, False, False, 2, 1)])
+# RT > 1 together with a column split, A of 0.27 and 0.5 GB built on the device: (m, n, k, NT, RT, splits, V)
+F64_KL_UHT_BIG = [(32768, 1024, 9, 1, 2, 2, 1), (65536, 1024, 16, 1, 4, 2, 2)]
+# f64_kl_wtu_kernel<NT, CT, VEC>: (m, n, k, NT, CT, VEC, chunks, V)
+F64_KL_WTU = [(m, n, k, nt, ct, vec, ch, 2 - n % 2)
+              for m, ch in ((40, 1), (130, 3), (600, 10))
+              for n, k, nt, ct, vec in ((72, 12, 1, 4, True), (72, 9, 1, 4, False), (72, 20, 2, 4, True), (70, 20, 2, 4, False),
+                                        (72, 40, 4, 2, True), (71, 40, 4, 2, False))]
+# f64_nn_cols_kernel<KS, MODE, VEC>, both images: (m, n, k, KS, CT, VEC, chunks).  k > 64 is the image path of the KL products.
+# 16400 x 132 has more than 2^21 elements: the grid-stride loops of the sums and of the element-wise kernel take more than one trip
+F64_IMAGE = [(130, 72, 8, 4, 4, True, 3), (130, 70, 9, 4, 4, False, 3), (130, 72, 20, 8, 4, True, 3), (130, 70, 21, 8, 4, False, 3),
+             (130, 72, 40, 16, 4, True, 3), (130, 71, 41, 16, 4, False, 3), (130, 72, 100, 32, 2, True, 3), (130, 71, 99, 32, 2, False, 3),
+             (40, 72, 65, 32, 2, False, 1), (16400, 132, 20, 8, 4, True, 257)]
+F64_IMAGE_K = [c for c in F64_IMAGE if c[2] > 64]
+# f64_nn_rows_kernel<KS, NN_UPD_W> and f64_upd_h_kernel<KS>: (m, n, k, KS); k % 4 != 0, m and n ragged at 16
+F64_MU = [(130, 70, 9, 4), (130, 70, 21, 8), (130, 70, 41, 16), (130, 70, 99, 32)]
+# dnmf_f64_fit, itr = 1: (m, n, k, family).  The tiny kernel takes what fits 160 KiB - 64 bytes of LDS at k <= 16: 20 x 300 at k = 16 has
+# m k, k n and n above 256 (every strided loop takes a second trip); 119 x 119 (88 x 89 with the quotient image of KL) is the largest such
+# shape, one more row or column leaves it to the chain
+F64_FIT_FRO = [(20, 300, 16, "fit_tiny"), (40, 300, 1, "fit_tiny"), (119, 119, 16, "fit_tiny"), (120, 119, 16, "fit_chain"), (130, 72, 20, "fit_chain")]
+F64_FIT_KL = [(24, 260, 12, "fit_tiny"), (30, 280, 1, "fit_tiny"), (88, 89, 16, "fit_tiny"), (89, 89, 16, "fit_chain"), (130, 72, 20, "fit_chain")]
+F64_FIT_STACK = (20, 300, 16)
+
+
+def f64_pitch(cols, aligned):
+    """the pitch of a `Poisoned` view of `cols` float64 columns"""
+    return -(-cols // 4) * 4 + 4 if aligned else cols + 3
 
 
 # ---------------------------------------------------------------------------------------------------------- per-element comparison

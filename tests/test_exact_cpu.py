@@ -75,6 +75,88 @@ def test_kl_quotient_is_exact(m, n, k):
     assert np.array_equal(H.sum(1, dtype=np.float32).astype(np.float64), H.astype(np.float64).sum(1))
 
 
+# ---------------------------------------------------------------------------------------------------------- the float64 shapes
+# The shapes of tests/test_gpu_exact_f64.py are far larger than the fp32 ones (65500 rows): the generators' bounds follow the dtype, and
+# the claims are proved here in float64 arithmetic against exact integers (int64 holds every sum: the totals are below 2^53).
+F64_EPS = 2.220446049250313e-16
+
+
+def _orders64(X, Y, scale, what):
+    """X @ Y in float64 in four orders -- BLAS, the contraction index reversed, sequential slabs of 48 and of 1000 terms added in slab
+    order -- all equal to the exact product of the integers X scale[0], Y scale[1]; returns that product over the scales, as float64"""
+    Xi, Yi = np.rint(X * scale[0]).astype(np.int64), np.rint(Y * scale[1]).astype(np.int64)
+    assert np.array_equal(Xi / scale[0], X) and np.array_equal(Yi / scale[1], Y), "%s: the operands are not multiples of the stated units" % what
+    exact = Xi @ Yi
+    assert np.abs(exact).max() < 2 ** 53
+    ref = exact.astype(np.float64) / (scale[0] * scale[1])
+    L = X.shape[1]
+    got = {"BLAS": X @ Y, "reversed": X[:, ::-1] @ Y[::-1]}
+    for step in (48, 1000):
+        acc = np.zeros_like(ref)
+        for t in range(0, L, step):
+            acc += X[:, t:t + step] @ Y[t:t + step]
+        got["slabs of %d" % step] = acc
+    for how, g in got.items():
+        assert np.array_equal(g, ref), "%s (%s) is not exact in float64" % (what, how)
+    return ref
+
+
+F64_PRODUCT_PROOF = sorted({c[:3] for c in ex.F64_AHT if c[0] >= 8200 and c[1] == 70} | {c[:3] for c in ex.F64_AHT if c[6] > 1}
+                           | {c[:3] for c in ex.F64_WTA if c[0] == 600 and c[1] == 71} | {c[:3] for c in ex.F64_MU} | {ex.F64_IMAGE[-1][:3]})
+F64_KL_PROOF = sorted({c[:3] for c in ex.F64_KL_UHT if c[1] == 70 or c[7] > 1} | {c[:3] for c in ex.F64_KL_WTU if c[0] == 600}
+                      | {c[:3] for c in ex.F64_IMAGE_K})
+
+
+@pytest.mark.parametrize("m,n,k", F64_PRODUCT_PROOF, ids=str)
+def test_float64_products_are_exact(m, n, k):
+    """`products` in float64: the four products and the two MU denominators are integers, equal in every order; a positive
+    denominator is in [2, 2^51) and absorbs eps = 2^-52"""
+    A, W, H = ex.products(m, n, k, np.float64)
+    assert A.dtype == W.dtype == H.dtype == np.float64
+    one = (1, 1)
+    _orders64(A, H.T, one, "A H^T")
+    _orders64(W.T, A, one, "W^T A")
+    G, GW = _orders64(H, H.T, one, "H H^T"), _orders64(W.T, W, one, "W^T W")
+    for d, what in ((_orders64(W, G, one, "W G"), "W G"), (_orders64(GW, H, one, "G H"), "G H")):
+        assert np.all((d == 0) | ((d >= 2) & (d < 2.0 ** 51))), what
+        assert np.array_equal(d[d > 0] + F64_EPS, d[d > 0]), "%s + eps is not absorbed in float64" % what
+    S = _orders64(W, H, one, "W H")                                            # the residual operands of sqdiff: A = W H + (0..2)
+    assert (S.max() + 2) ** 2 * m * n < 2 ** 53                                # (so is the sum of the squares of A, whatever its order)
+
+
+@pytest.mark.parametrize("m,n,k", F64_KL_PROOF, ids=str)
+def test_float64_kl_quotient_is_exact(m, n, k):
+    """`kl` in float64: W H is a power of two >= 2 that absorbs eps, U = A / (W H + eps) is A times a power of two (exactly), and
+    U H^T, W^T U (multiples of 2^-5), rowsum(H), colsum(W) are equal in every order"""
+    A, W, H, U = ex.kl(m, n, k, np.float64)
+    assert A.dtype == W.dtype == H.dtype == np.float64
+    WH = _orders64(W, H, (1, 1), "W H")
+    assert np.array_equal(WH + F64_EPS, WH), "W H + eps is not absorbed in float64"
+    U64 = A / (WH + F64_EPS)
+    assert np.array_equal(U64, U)
+    e = np.log2(WH)
+    assert np.array_equal(e, np.round(e)) and e.min() >= 1 and np.array_equal(U * WH, A) and np.array_equal(np.ldexp(A, -e.astype(int)), U)
+    _orders64(U, H.T, (32, 1), "U H^T")
+    _orders64(W.T, U, (1, 32), "W^T U")
+    ones = np.ones((1, n)), np.ones((m, 1))
+    assert np.array_equal(_orders64(ones[0], H.T, (1, 1), "rowsum(H)")[0], H.sum(1))
+    assert np.array_equal(_orders64(W.T, ones[1], (1, 1), "colsum(W)")[:, 0], W.sum(0))
+
+
+@pytest.mark.parametrize("m,n,k", sorted({c[:3] for c in ex.F64_FIT_FRO} | {ex.F64_FIT_STACK}), ids=str)
+def test_float64_fro_step_is_exact(m, n, k):
+    """`fro_step` in float64: the W phase is exact (W G a power of two >= 2), the H phase has exact numerators and denominators >= 2"""
+    A, W, H, Wn, Hq = ex.fro_step(m, n, k, np.float64)
+    G, AH = H @ H.T, A @ H.T
+    WG = W @ G
+    assert np.array_equal(np.log2(WG), np.round(np.log2(WG))) and WG.min() >= 2
+    assert np.array_equal(W * (AH / (WG + F64_EPS)), Wn)
+    num, den = Wn.T @ A, (Wn.T @ Wn) @ H
+    assert np.array_equal(num, Wn[::-1].T @ A[::-1]) and np.array_equal(den, (Wn[::-1].T @ Wn[::-1]) @ H)
+    assert np.all((den == 0) | (den >= 2)) and np.array_equal(den[den > 0] + F64_EPS, den[den > 0])
+    ex.assert_ulp(H * (num / (den + F64_EPS)), Hq, 1, "H phase in float64")
+
+
 # ---------------------------------------------------------------------------------------------------------- fixed points of a whole MU step
 F32_EPS = np.float32(np.finfo(np.float32).eps)
 ORDERS = ("forward", "reversed", 11, 12)                                    # (a number: that seed's random permutation of the terms)

@@ -392,12 +392,16 @@ FIT = [pytest.param(300, 130, 5, 1, id="small-k5"), pytest.param(1000, 260, 16, 
        pytest.param(257, 600, 32, 3, id="small-k32-batched"), pytest.param(1030, 515, 17, 2, id="small-k17-batched-n%4")]
 
 
-def _assert_normalized(w, h, Wc, Hc, c, what):
+def _assert_normalized(w, h, Wc, Hc, c, what, eps=EPS):
     """normalize_features on the clamped step: s = column sums of W, W / (s + eps), H s.  The clamped zeros of W add eps terms to
     s that an fp32 sum absorbs or keeps depending on its order, so s lies between the sum without them and the float64 sum with
-    them; each element is held to c ulps of the interval that spans"""
-    s_lo, s_hi = np.where(Wc > EPS32, Wc, 0).sum(0), Wc.sum(0)
-    ex.assert_ulp(w, Wc / (s_lo + EPS)[None, :], c, what + " W", q_hi=Wc / (s_hi + EPS)[None, :])
+    them; each element is held to c ulps of the interval that spans.  eps: the clamp of the operator set (float64: 2^-52, where the
+    same holds for its float64 sums -- tests/test_gpu_exact_f64.py; there numpy's own float64 sum of Wc would absorb eps terms too,
+    so the upper end is formed as s_lo + count eps: exact for the fp32 operands, within half an ulp of s for the float64 ones)"""
+    clamped = Wc <= eps
+    s_lo = np.where(clamped, 0, Wc).sum(0)
+    s_hi = s_lo + clamped.sum(0) * eps
+    ex.assert_ulp(w, Wc / (s_lo + eps)[None, :], c, what + " W", q_hi=Wc / (s_hi + eps)[None, :])
     ex.assert_ulp(h, Hc * s_lo[:, None], c, what + " H", q_hi=Hc * s_hi[:, None])
 
 
