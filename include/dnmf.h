@@ -331,7 +331,7 @@ int dnmf_mu_fit_persistent(long m, long n, int k);
  * from the L2, fp32 or bf16-stored; the k column norms of a W sweep cross the problem's workgroups through value-as-flag slots) */
 int dnmf_hals_fit_persistent(long m, long n, int k);
 /* Which persistent kernel a whole fit of this shape takes and with what geometry, host arithmetic only (nothing is launched; the switch
- * dnmf_set_persistent is not consulted), from the functions the launches call.  method: 0 MU/FRO, 1 MU/KL, 2 HALS/FRO; bf16 != 0: A stored
+ * dnmf_set_persistent is not consulted): the plan that a fit computes once and launches from (small_plan, csrc/dnmf_fit.hip).  method: 0 MU/FRO, 1 MU/KL, 2 HALS/FRO; bf16 != 0: A stored
  * as bfloat16 (the *_bf16a fits; refused for MU/KL); w_update as passed to the fit.
  * out = {route, KP, NW, ALDS, P, ns, cw, bf16_resident}.  route 0: none (the launch chain); 1: the barrier kernel of the method
  * (small_kl_fit_kernel / small_fro_fit_kernel, with W fixed the former at w_update = 0); 2: the W-fixed MU/KL kernel (small_kl_hfit_kernel:

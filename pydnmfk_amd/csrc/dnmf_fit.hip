@@ -18,119 +18,92 @@ enum { FIT_MU_FRO = 0, FIT_MU_KL = 1, FIT_HALS_FRO = 2 };
 
 inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 
-// The persistent small-problem MU/KL fit (csrc/dnmf_small.h): which shapes take it and with what geometry.  fp32 A, k <= 32, the slab of A +
-// all of H + the slab's W in the 160 KiB of LDS of a CU (8-wave workgroups = 128-row slabs when that fits, else 4-wave = 64-row), at
-// most 64 slabs per problem -- in practice n up to ~500 columns and m up to 8192 rows: the reference's example sizes.
-struct SmallPlan { int kp, nw, P; bool alds; long ns; size_t lds, part_floats, bytes; bool ok; };
-SmallPlan small_kl_plan(long m, long n, int k) {
-    SmallPlan s{};
-    if (k < 1 || k > 32 || n > 4096) return s;
-    s.kp = k <= 16 ? 16 : 32;
-    s.ns = round_up(n, 16);
-    // geometry by shape alone (a batched fit must equal single fits bit for bit): 128-row slabs with A in LDS when that fits; else 96-row
-    // slabs with A in LDS (round 6: at 16 < k <= 32 the 1024 x 256 examples keep A on chip this way, and 20 problems x 11 slabs cover 220
-    // of the 256 CUs where 8 slabs covered 160); else 128-row slabs with A streamed from the L2 (H and the slab's W in LDS); else 64-row
-    // slabs with A in LDS, or streamed (short, wide problems)
-    struct Try { int nw; bool alds; };
-    const Try tries[5] = {{8, true}, {6, true}, {8, false}, {4, true}, {4, false}};
-    for (const auto& t : tries) {
-        const size_t lds = small_kl_lds(s.kp, t.nw, n, t.alds);
-        const long P = cdiv(m, 16L * t.nw);
-        if (lds <= 160 * 1024 && P <= 64 && (t.nw == 4 || P >= 2)) { s.nw = t.nw; s.alds = t.alds; s.P = (int)P; s.lds = lds; break; }
-    }
-    if (!s.nw) return s;
-    s.part_floats = (size_t)s.P * s.kp * s.ns + (size_t)s.P * s.kp * s.kp;       // W^T U / W^T A partials + (KL) column sums or (FRO) W^T W per slab
-    s.part_floats = (s.part_floats + 3) & ~size_t(3);                                // ... + the granules {element, step} of H, 16-byte aligned
-    s.bytes = (((s.part_floats + 2 * (size_t)s.kp * s.ns) * sizeof(float) + 255) & ~size_t(255)) + 256;      // ... + the arrival counter
-    s.ok = true;
-    return s;
-}
-
-// HALS on the persistent kernel (small_hals_fit_kernel): A always streamed, so LDS holds H, the slab's W, the Gram matrix and the
-// workgroup's share of W^T A; fp32 or bf16-stored A
-struct HalsPlan { int kp, nw, P, cw; long ns; size_t lds, lds_bf16_resident, part_floats, slot_words, bytes; bool ok; };
-HalsPlan small_hals_plan(long m, long n, int k) {
-    HalsPlan s{};
-    if (k < 1 || k > 32 || n > 4096) return s;
-    s.kp = k <= 16 ? 16 : 32;
-    s.ns = round_up(n, 16);
-    for (int nw : {8, 4}) {
-        const long P = cdiv(m, 16L * nw);
-        const int cw = (int)cdiv(s.ns, P);
-        const size_t lds = small_hals_lds(s.kp, nw, n, cw, 0);
-        if (lds <= 160 * 1024 && P <= 64 && (nw == 4 || P >= 2)) {
-            s.nw = nw; s.P = (int)P; s.cw = cw; s.lds = lds;
-            s.lds_bf16_resident = small_hals_lds(s.kp, nw, n, cw, 2);       // (the geometry never depends on the storage: only where A is read from)
-            break;
-        }
-    }
-    if (!s.nw) return s;
-    s.part_floats = (size_t)s.P * s.kp * s.ns + (size_t)s.P * s.kp * s.kp;
-    s.slot_words = (((size_t)2 * s.kp * s.P) + 3) & ~size_t(3);
-    s.part_floats = (s.part_floats + 3) & ~size_t(3);
-    s.bytes = (((s.part_floats + s.slot_words + 2 * (size_t)s.kp * s.ns) * 4 + 255) & ~size_t(255)) + 256;      // partials | slots | granules of H | counter
-    s.ok = true;
-    return s;
-}
-
-// MU/FRO on bf16-stored data (params.precision = 'bfloat16'): the Frobenius kernel with TA = bf16_t, its own plan (the slab is half the
-// size: it fits LDS where the fp32 one streams)
-struct FroBfPlan { int kp, nw, P; bool alds; long ns; size_t lds, part_floats, bytes; bool ok; };
-FroBfPlan small_fro_bf16_plan(long m, long n, int k) {
-    FroBfPlan s{};
-    if (k < 1 || k > 32 || n > 4096) return s;
-    s.kp = k <= 16 ? 16 : 32;
-    s.ns = round_up(n, 16);
-    const struct { int nw; bool alds; } tries[4] = {{8, true}, {8, false}, {4, true}, {4, false}};
-    for (const auto& t : tries) {
-        const size_t lds = small_fro_lds(s.kp, t.nw, n, t.alds, 2);
-        const long P = cdiv(m, 16L * t.nw);
-        if (lds <= 160 * 1024 && P <= 64 && (t.nw == 4 || P >= 2)) { s.nw = t.nw; s.alds = t.alds; s.P = (int)P; s.lds = lds; break; }
-    }
-    if (!s.nw) return s;
-    s.part_floats = (size_t)s.P * s.kp * s.ns + (size_t)s.P * s.kp * s.kp;
-    s.part_floats = (s.part_floats + 3) & ~size_t(3);                                  // (the granules of H behind it: 16-byte aligned)
-    s.bytes = (((s.part_floats + 2 * (size_t)s.kp * s.ns) * sizeof(float) + 255) & ~size_t(255)) + 256;
-    s.ok = true;
-    return s;
-}
-
-// The W-fixed MU/KL kernel (small_kl_hfit_kernel) keeps ALL of W in LDS: taken when that fits, else the barrier kernel runs with w_update = 0
-constexpr int HFIT_NW = 8;
-inline bool small_kl_wfixed_fits(int kp, long m) { return small_kl_hfit_lds(kp, HFIT_NW, m) <= 160 * 1024; }
-
-// Which persistent kernel a whole fit takes, from the shape alone: what fit_impl dispatches on and what dnmf_small_fit_plan reports.
+// The persistent small-problem fits (csrc/dnmf_small.h): which shapes take them, with what geometry and workspace.  k <= 32, n <= 4096;
+// all of H + the slab's W (+ the slab of A when that fits) in the 160 KiB of LDS of a CU, 8-wave workgroups = 128-row slabs when that fits,
+// else 4-wave = 64-row, at most 64 slabs per problem -- in practice n up to ~500 columns and m up to 8192 rows: the reference's example sizes.
 enum { ROUTE_NONE = 0, ROUTE_BARRIER = 1, ROUTE_WFIXED = 2, ROUTE_HALS = 3 };
 enum { FAM_KL = 0, FAM_FRO = 1, FAM_WFIXED = 2, FAM_HALS = 3 };             // the launch counters (dnmf_small_fit_launches)
-struct SmallRoute { int route, kp, nw, P, cw; bool alds, bf16_resident; long ns; size_t bytes; };
-SmallRoute small_route(int method, bool bf, int w_update, long m, long n, int k) {
-    SmallRoute r{};
-    if (m < 1 || n < 1) return r;
-    if (method == FIT_HALS_FRO) {                          // (W fixed: the hoisted H-only loop of fit_impl is the better path)
-        const HalsPlan hp = small_hals_plan(m, n, k);
-        if (!hp.ok || !w_update) return r;
-        r.route = ROUTE_HALS; r.kp = hp.kp; r.nw = hp.nw; r.P = hp.P; r.cw = hp.cw; r.ns = hp.ns; r.bytes = hp.bytes;
-        r.bf16_resident = bf && hp.lds_bf16_resident <= 160 * 1024;
-        r.alds = r.bf16_resident;
-        return r;
+constexpr size_t SMALL_LDS_MAX = 160 * 1024;
+constexpr int HFIT_NW = 8;                                                  // waves of the W-fixed MU/KL kernel (small_kl_hfit_kernel)
+
+// What a whole fit takes, from the shape alone: everything dnmf_small_fit_plan reports and everything small_launch needs.  All zero: route 0.
+struct SmallPlan {
+    int route, family, kp, nw, P, cw;
+    bool alds, bf16_resident;
+    long ns;
+    size_t lds;                                  // dynamic LDS of the kernel chosen
+    size_t part_floats, slot_words, bytes;       // workspace: partials | slots (HALS) | granules of H | arrival counter
+};
+
+// The geometry families: their {NW, A in LDS} tries in order of preference, their LDS function, and whether they have the slots and the
+// column share cw = ceil(ns / P) of the HALS sweep.
+//   MU on fp32 A (KL and FRO alike: FRO takes the KL geometry and the KL size): 128-row slabs with A in LDS when that fits; else 96-row
+//     slabs with A in LDS (round 6: at 16 < k <= 32 the 1024 x 256 examples keep A on chip this way, and 20 problems x 11 slabs cover 220
+//     of the 256 CUs where 8 slabs covered 160); else 128-row slabs with A streamed from the L2; else 64-row slabs with A in LDS, or
+//     streamed (short, wide problems)
+//   MU/FRO on bf16-stored A (params.precision = 'bfloat16'): the slab is half the size, it fits LDS where the fp32 one streams
+//   HALS: A streamed, LDS holds H, the slab's W, the Gram matrix and the workgroup's share of W^T A; the geometry never depends on the
+//     storage of A, only where A is read from (small_plan)
+struct SmallTry { int nw; bool alds; };
+struct SmallGeometry { SmallTry tries[5]; int ntries; size_t (*lds)(int kp, int nw, long n, bool alds, int cw); bool slots; };
+enum { GEO_MU = 0, GEO_MU_BF16 = 1, GEO_HALS = 2 };
+const SmallGeometry SMALL_GEOMETRIES[3] = {
+    {{{8, true}, {6, true}, {8, false}, {4, true}, {4, false}}, 5, [](int kp, int nw, long n, bool alds, int) { return small_kl_lds(kp, nw, n, alds); }, false},
+    {{{8, true}, {8, false}, {4, true}, {4, false}}, 4, [](int kp, int nw, long n, bool alds, int) { return small_fro_lds(kp, nw, n, alds, 2); }, false},
+    {{{8, false}, {4, false}}, 2, [](int kp, int nw, long n, bool, int cw) { return small_hals_lds(kp, nw, n, cw, 0); }, true},
+};
+
+// geometry by shape alone (a batched fit must equal single fits bit for bit): the first try that fits the LDS in at most 64 slabs -- 8- and
+// 6-wave workgroups only where that makes two slabs or more -- and the workspace layout that goes with it.  nw == 0: none
+SmallPlan small_geometry(int geo, long m, long n, int k) {
+    SmallPlan s{};
+    if (m < 1 || n < 1 || k < 1 || k > 32 || n > 4096) return s;
+    const SmallGeometry& g = SMALL_GEOMETRIES[geo];
+    const int kp = k <= 16 ? 16 : 32;
+    const long ns = round_up(n, 16);
+    for (int i = 0; i < g.ntries; ++i) {
+        const SmallTry t = g.tries[i];
+        const long P = cdiv(m, 16L * t.nw);
+        const int cw = g.slots ? (int)cdiv(ns, P) : 0;
+        const size_t lds = g.lds(kp, t.nw, n, t.alds, cw);
+        if (lds > SMALL_LDS_MAX || P > 64 || (t.nw != 4 && P < 2)) continue;
+        s.kp = kp; s.nw = t.nw; s.P = (int)P; s.cw = cw; s.alds = t.alds; s.ns = ns; s.lds = lds;
+        // W^T U / W^T A partials + (KL) column sums or (FRO, HALS) W^T W per slab; the slots and the granules {element, step} of H behind
+        // them 16-byte aligned; the arrival counter in a 256-byte block of its own
+        s.part_floats = ((size_t)P * kp * ns + (size_t)P * kp * kp + 3) & ~size_t(3);
+        s.slot_words = g.slots ? ((size_t)2 * kp * P + 3) & ~size_t(3) : 0;
+        s.bytes = al256((s.part_floats + s.slot_words + 2 * (size_t)kp * ns) * sizeof(float)) + 256;
+        break;
     }
-    if (method == FIT_MU_FRO && bf) {
-        const FroBfPlan sp = small_fro_bf16_plan(m, n, k);
-        if (!sp.ok || !w_update) return r;
-        r.route = ROUTE_BARRIER; r.kp = sp.kp; r.nw = sp.nw; r.P = sp.P; r.alds = sp.alds; r.ns = sp.ns; r.bytes = sp.bytes;
-        return r;
+    return s;
+}
+
+// the small area of the fit workspace serves whichever family the fit call turns out to be
+size_t small_area_bytes(long m, long n, int k) {
+    return std::max(std::max(small_geometry(GEO_MU, m, n, k).bytes, small_geometry(GEO_HALS, m, n, k).bytes), small_geometry(GEO_MU_BF16, m, n, k).bytes);
+}
+
+// Which persistent kernel a whole fit takes: computed once per fit by fit_impl, and what dnmf_small_fit_plan reports.
+SmallPlan small_plan(int method, bool bf, int w_update, long m, long n, int k) {
+    if (method != FIT_MU_KL && method != FIT_MU_FRO && method != FIT_HALS_FRO) return SmallPlan{};
+    // MU/KL reads fp32 A only; the Frobenius updates with W fixed: the hoisted H-only loop of fit_impl is the better path
+    if (method == FIT_MU_KL ? bf : !w_update) return SmallPlan{};
+    SmallPlan p = small_geometry(method == FIT_HALS_FRO ? GEO_HALS : bf ? GEO_MU_BF16 : GEO_MU, m, n, k);
+    if (!p.nw) return SmallPlan{};
+    if (method == FIT_HALS_FRO) {
+        const size_t resident = small_hals_lds(p.kp, p.nw, n, p.cw, 2);         // with the bf16 slab of A in LDS
+        p.route = ROUTE_HALS; p.family = FAM_HALS;
+        p.alds = p.bf16_resident = bf && resident <= SMALL_LDS_MAX;
+        if (p.bf16_resident) p.lds = resident;
+    } else if (method == FIT_MU_KL && !w_update && small_kl_hfit_lds(p.kp, HFIT_NW, m) <= SMALL_LDS_MAX) {
+        // the W-fixed MU/KL kernel keeps ALL of W in LDS: taken when that fits (else the barrier kernel runs with w_update = 0); a workgroup
+        // per 16 columns, A streamed.  The workspace layout stays that of the barrier geometry: the kernel touches none of it
+        p.route = ROUTE_WFIXED; p.family = FAM_WFIXED;
+        p.nw = HFIT_NW; p.P = (int)(p.ns / 16); p.alds = false; p.lds = small_kl_hfit_lds(p.kp, HFIT_NW, m);
+    } else {
+        p.route = ROUTE_BARRIER; p.family = method == FIT_MU_FRO ? FAM_FRO : FAM_KL;
     }
-    if (bf || (method != FIT_MU_KL && method != FIT_MU_FRO)) return r;
-    if (method == FIT_MU_FRO && !w_update) return r;       // (Frobenius MU with W fixed: the hoisted H-only loop beats the barrier kernel)
-    const SmallPlan sp = small_kl_plan(m, n, k);
-    if (!sp.ok) return r;
-    r.kp = sp.kp; r.ns = sp.ns; r.bytes = sp.bytes;
-    if (method == FIT_MU_KL && !w_update && small_kl_wfixed_fits(sp.kp, m)) {
-        r.route = ROUTE_WFIXED; r.nw = HFIT_NW; r.P = (int)(sp.ns / 16);     // a workgroup per 16 columns, A streamed
-        return r;
-    }
-    r.route = ROUTE_BARRIER; r.nw = sp.nw; r.P = sp.P; r.alds = sp.alds;
-    return r;
+    return p;
 }
 
 // kernel launches of the persistent small fits that were TAKEN, per family (host side; dnmf_small_fit_launches)
@@ -152,7 +125,7 @@ FitWs fit_layout(long m, long n, int k) {
     f.ss2_off = f.cs_off + al256((size_t)kp * sizeof(float));
     f.sq_off = f.ss2_off + al256((size_t)kp * sizeof(double));
     f.small_off = f.sq_off + 256;
-    f.total = f.small_off + std::max(std::max(small_kl_plan(m, n, k).bytes, small_hals_plan(m, n, k).bytes), small_fro_bf16_plan(m, n, k).bytes);
+    f.total = f.small_off + small_area_bytes(m, n, k);
     return f;
 }
 
@@ -211,114 +184,66 @@ int resident_launch(void (*kern)(SmallKlArgs), int threads, size_t lds, int P, S
     return DNMF_OK;
 }
 
-// all `itr` MU/KL steps of `batch` small problems: as few launches as keep every workgroup of a launch resident at once
-template <int KP, int NW, bool ALDS, bool FRO>
-int small_kl_launch(const SmallPlan& sp, SmallKlArgs a, int batch, hipStream_t st, bool* taken) {
-    return resident_launch(FRO ? small_fro_fit_kernel<KP, NW, ALDS, float> : small_kl_fit_kernel<KP, NW, ALDS>, 64 * NW, sp.lds, sp.P, a, batch, st, taken,
-                           FRO ? "small_fro_fit_kernel" : "small_kl_fit_kernel", FRO ? FAM_FRO : FAM_KL);
-}
-
-int small_fit(const SmallRoute& rt, bool fro, const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int w_update, int itr,
-                 int batch, long a_stride, long w_stride, long h_stride, char* ws, const FitWs& f, void* stream, bool* taken) {
-    *taken = false;
-    const SmallPlan sp = small_kl_plan(m, n, k);
-    if (!sp.ok || itr < 1) return DNMF_OK;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    SmallKlArgs a{};
-    a.A = A; a.lda = lda; a.a_stride = a_stride; a.W = W; a.ldw = ldw; a.w_stride = w_stride; a.H = H; a.ldh = ldh; a.h_stride = h_stride;
-    a.m = (int)m; a.n = (int)n; a.k = k; a.eps = eps; a.itr = itr; a.w_update = w_update;
-    a.part = (float*)(ws + f.small_off); a.part_stride = (long)(f.total / sizeof(float));
-    a.bar = (unsigned*)(ws + f.small_off + sp.bytes - 256); a.bar_stride = (long)(f.total / sizeof(unsigned));
-    a.hg = a.part + sp.part_floats; a.hg_stride = a.part_stride;                       // [kp][ns] granules {H element, step}: zeroed below
-    a.patience = g_small_patience;                                     // ticks of the 100 MHz wall clock (2 s unless dnmf_fit_set_timeout)
-    if (batch == 1) { a.a_stride = a.w_stride = a.h_stride = 0; }
-    if (rt.route == ROUTE_WFIXED) {
-        // W fixed: the columns of H are independent -- a workgroup per 16 columns, no barrier, nothing to keep resident (small_kl_hfit_kernel);
-        // small_route has decided that all of W fits the LDS and how many workgroups that makes
-        constexpr int NW = HFIT_NW;
-        {
-            const size_t lds = small_kl_hfit_lds(rt.kp, NW, m);
-            const dim3 grid((unsigned)rt.P, 1, (unsigned)batch);
-            a.z0 = 0;
-            const auto kern = rt.kp == 16 ? small_kl_hfit_kernel<16, NW> : small_kl_hfit_kernel<32, NW>;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return fail(DNMF_EHIP, "small fit: cannot raise the dynamic LDS limit");
-            hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, st, a);
-            const int rc = check_launch("small_kl_hfit_kernel");
-            if (!rc) { ++g_small_launches[FAM_WFIXED]; *taken = true; }
-            return rc;
+// the kernel of a plan: the ONE place that names the 42 instantiations
+struct SmallKernel { void (*fn)(SmallKlArgs); const char* name; };
+template <int KP, int NW, bool ALDS>
+SmallKernel small_kernel_at(int family, bool bf) {
+    if (family == FAM_KL) return {small_kl_fit_kernel<KP, NW, ALDS>, "small_kl_fit_kernel"};
+    if (family == FAM_FRO && !bf) return {small_fro_fit_kernel<KP, NW, ALDS, float>, "small_fro_fit_kernel"};
+    if constexpr (NW != 6) {                               // (96-row slabs: MU on fp32 A only)
+        if (family == FAM_FRO) return {small_fro_fit_kernel<KP, NW, ALDS, bf16_t>, "small_fro_fit_kernel(bf16)"};
+        if constexpr (ALDS) {                              // HALS: ALDS == bf16_resident, fp32 A is always streamed
+            if (family == FAM_HALS) return {small_hals_fit_kernel<KP, NW, bf16_t, true>, "small_hals_fit_kernel"};
+        } else {
+            if (family == FAM_HALS) return {bf ? small_hals_fit_kernel<KP, NW, bf16_t, false> : small_hals_fit_kernel<KP, NW, float, false>, "small_hals_fit_kernel"};
+            if constexpr (NW == HFIT_NW)
+                if (family == FAM_WFIXED) return {small_kl_hfit_kernel<KP, NW>, "small_kl_hfit_kernel"};
         }
     }
-    if (hipMemset2DAsync(a.bar, f.total, 0, 2 * sizeof(unsigned), (size_t)batch, st) != hipSuccess) return fail(DNMF_EHIP, "small fit: memset failed");
-    if (hipMemset2DAsync(a.hg, f.total, 0, 2 * (size_t)sp.kp * sp.ns * sizeof(float), (size_t)batch, st) != hipSuccess) return fail(DNMF_EHIP, "small fit: memset failed");
-#define SMALL_CASE(KP_, NW_, AL_)                                                                                                 \
-    if (sp.kp == KP_ && sp.nw == NW_ && sp.alds == AL_)                                                                           \
-        return fro ? small_kl_launch<KP_, NW_, AL_, true>(sp, a, batch, st, taken) : small_kl_launch<KP_, NW_, AL_, false>(sp, a, batch, st, taken)
+    return {nullptr, nullptr};
+}
+SmallKernel small_kernel(const SmallPlan& p, bool bf) {
+#define SMALL_CASE(KP_, NW_, AL_) \
+    if (p.kp == KP_ && p.nw == NW_ && p.alds == AL_) return small_kernel_at<KP_, NW_, AL_>(p.family, bf)
     SMALL_CASE(16, 8, true); SMALL_CASE(16, 6, true); SMALL_CASE(16, 8, false); SMALL_CASE(16, 4, true); SMALL_CASE(16, 4, false);
     SMALL_CASE(32, 8, true); SMALL_CASE(32, 6, true); SMALL_CASE(32, 8, false); SMALL_CASE(32, 4, true); SMALL_CASE(32, 4, false);
 #undef SMALL_CASE
-    return DNMF_OK;
+    return {nullptr, nullptr};
 }
 
-// all `itr` HALS steps of `batch` small problems on the persistent kernel (W updated: with W fixed the hoisted H-only loop of fit_impl is
-// the better path)
-template <int KP, int NW, typename TA, bool ALDS>
-int small_hals_launch(const HalsPlan& hp, SmallKlArgs a, int batch, hipStream_t st, bool* taken) {
-    return resident_launch(small_hals_fit_kernel<KP, NW, TA, ALDS>, 64 * NW, ALDS ? hp.lds_bf16_resident : hp.lds, hp.P, a, batch, st, taken, "small_hals_fit_kernel", FAM_HALS);
-}
-
-int small_hals_fit(const SmallRoute& rt, bool bf, const void* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int itr, int batch,
-                   long a_stride, long w_stride, long h_stride, char* ws, const FitWs& f, void* stream, bool* taken) {
+// all `itr` steps of `batch` small problems on the persistent kernel of the plan (csrc/dnmf_small.h): the barrier and HALS kernels as few
+// launches as keep every workgroup of a launch resident at once
+int small_launch(const SmallPlan& p, bool bf, const void* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int w_update,
+                 int itr, int batch, long a_stride, long w_stride, long h_stride, char* ws, const FitWs& f, void* stream, bool* taken) {
     *taken = false;
-    const HalsPlan hp = small_hals_plan(m, n, k);
-    if (!hp.ok || itr < 1) return DNMF_OK;
+    const SmallKernel kern = small_kernel(p, bf);
+    if (!p.route || !kern.fn || itr < 1) return DNMF_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     SmallKlArgs a{};
     a.A = (const float*)A; a.lda = lda; a.a_stride = a_stride; a.W = W; a.ldw = ldw; a.w_stride = w_stride; a.H = H; a.ldh = ldh; a.h_stride = h_stride;
-    a.m = (int)m; a.n = (int)n; a.k = k; a.eps = eps; a.itr = itr; a.w_update = 1; a.cw = hp.cw;
+    a.m = (int)m; a.n = (int)n; a.k = k; a.eps = eps; a.itr = itr; a.w_update = w_update; a.cw = p.cw;
     a.part = (float*)(ws + f.small_off); a.part_stride = (long)(f.total / sizeof(float));
-    a.slots = (unsigned*)(ws + f.small_off) + hp.part_floats; a.slots_stride = (long)(f.total / sizeof(unsigned));
-    a.bar = (unsigned*)(ws + f.small_off + hp.bytes - 256); a.bar_stride = (long)(f.total / sizeof(unsigned));
-    a.hg = a.part + hp.part_floats + hp.slot_words; a.hg_stride = a.part_stride;          // [kp][ns] granules {H element, step}
-    a.patience = g_small_patience;
+    a.bar = (unsigned*)(ws + f.small_off + p.bytes - 256); a.bar_stride = (long)(f.total / sizeof(unsigned));
+    a.hg = a.part + p.part_floats + p.slot_words; a.hg_stride = a.part_stride;      // [kp][ns] granules {H element, step}: zeroed below
+    a.patience = g_small_patience;                                     // ticks of the 100 MHz wall clock (2 s unless dnmf_fit_set_timeout)
     if (batch == 1) { a.a_stride = a.w_stride = a.h_stride = 0; }
-    if (hipMemset2DAsync(a.hg, f.total, 0, 2 * (size_t)hp.kp * hp.ns * sizeof(float), (size_t)batch, st) != hipSuccess ||
-        hipMemset2DAsync(a.slots, f.total, 0xff, hp.slot_words * sizeof(unsigned), (size_t)batch, st) != hipSuccess ||
-        hipMemset2DAsync(a.bar, f.total, 0, 2 * sizeof(unsigned), (size_t)batch, st) != hipSuccess)
-        return fail(DNMF_EHIP, "small fit: memset failed");
-#define HALS_CASE(KP_, NW_)                                                                                                       \
-    if (hp.kp == KP_ && hp.nw == NW_)                                                                                             \
-        return !bf ? small_hals_launch<KP_, NW_, float, false>(hp, a, batch, st, taken)                                           \
-                   : (rt.bf16_resident ? small_hals_launch<KP_, NW_, bf16_t, true>(hp, a, batch, st, taken)         /* (small_route's test) */ \
-                                                         : small_hals_launch<KP_, NW_, bf16_t, false>(hp, a, batch, st, taken))
-    HALS_CASE(16, 8); HALS_CASE(16, 4); HALS_CASE(32, 8); HALS_CASE(32, 4);
-#undef HALS_CASE
-    return DNMF_OK;
-}
-
-int small_fro_bf16_fit(const void* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int itr, int batch,
-                       long a_stride, long w_stride, long h_stride, char* ws, const FitWs& f, void* stream, bool* taken) {
-    *taken = false;
-    const FroBfPlan sp = small_fro_bf16_plan(m, n, k);
-    if (!sp.ok || itr < 1) return DNMF_OK;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    SmallKlArgs a{};
-    a.A = (const float*)A; a.lda = lda; a.a_stride = a_stride; a.W = W; a.ldw = ldw; a.w_stride = w_stride; a.H = H; a.ldh = ldh; a.h_stride = h_stride;
-    a.m = (int)m; a.n = (int)n; a.k = k; a.eps = eps; a.itr = itr; a.w_update = 1;
-    a.part = (float*)(ws + f.small_off); a.part_stride = (long)(f.total / sizeof(float));
-    a.bar = (unsigned*)(ws + f.small_off + sp.bytes - 256); a.bar_stride = (long)(f.total / sizeof(unsigned));
-    a.hg = a.part + sp.part_floats; a.hg_stride = a.part_stride;
-    a.patience = g_small_patience;
-    if (batch == 1) { a.a_stride = a.w_stride = a.h_stride = 0; }
-    if (hipMemset2DAsync(a.bar, f.total, 0, 2 * sizeof(unsigned), (size_t)batch, st) != hipSuccess) return fail(DNMF_EHIP, "small fit: memset failed");
-    if (hipMemset2DAsync(a.hg, f.total, 0, 2 * (size_t)sp.kp * sp.ns * sizeof(float), (size_t)batch, st) != hipSuccess) return fail(DNMF_EHIP, "small fit: memset failed");
-#define FROBF_CASE(KP_, NW_, AL_)                                                                                                 \
-    if (sp.kp == KP_ && sp.nw == NW_ && sp.alds == AL_)                                                                           \
-        return resident_launch(small_fro_fit_kernel<KP_, NW_, AL_, bf16_t>, 64 * NW_, sp.lds, sp.P, a, batch, st, taken, "small_fro_fit_kernel(bf16)", FAM_FRO)
-    FROBF_CASE(16, 8, true); FROBF_CASE(16, 8, false); FROBF_CASE(16, 4, true); FROBF_CASE(16, 4, false);
-    FROBF_CASE(32, 8, true); FROBF_CASE(32, 8, false); FROBF_CASE(32, 4, true); FROBF_CASE(32, 4, false);
-#undef FROBF_CASE
-    return DNMF_OK;
+    if (p.route == ROUTE_WFIXED) {
+        // W fixed: the columns of H are independent -- a workgroup per 16 columns, no barrier, nothing to keep resident and nothing to zero
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+            return fail(DNMF_EHIP, "small fit: cannot raise the dynamic LDS limit");
+        hipLaunchKernelGGL(kern.fn, dim3((unsigned)p.P, 1, (unsigned)batch), dim3(64 * p.nw), p.lds, st, a);
+        const int rc = check_launch(kern.name);
+        if (!rc) { ++g_small_launches[p.family]; *taken = true; }
+        return rc;
+    }
+    bool zeroed = hipMemset2DAsync(a.bar, f.total, 0, 2 * sizeof(unsigned), (size_t)batch, st) == hipSuccess &&
+                  hipMemset2DAsync(a.hg, f.total, 0, 2 * (size_t)p.kp * p.ns * sizeof(float), (size_t)batch, st) == hipSuccess;
+    if (p.route == ROUTE_HALS) {                                       // the column-norm slots of the W sweep, all SLOT_EMPTY
+        a.slots = (unsigned*)a.part + p.part_floats; a.slots_stride = a.bar_stride;
+        zeroed = zeroed && hipMemset2DAsync(a.slots, f.total, 0xff, p.slot_words * sizeof(unsigned), (size_t)batch, st) == hipSuccess;
+    }
+    if (!zeroed) return fail(DNMF_EHIP, "small fit: memset failed");
+    return resident_launch(kern.fn, 64 * p.nw, p.lds, p.P, a, batch, st, taken, kern.name, p.family);
 }
 
 int fit_impl(int method, bool bf, const void* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps,
@@ -341,26 +266,13 @@ int fit_impl(int method, bool bf, const void* A, long m, long n, long lda, float
     bool small = false;
     const bool pers = dnmf_persistent_on_() != 0;
     if (!pers) column_sweep = 1;                                       // (the HALS steps below take the column launches)
-    const SmallRoute route = pers ? small_route(method, bf, w_update, m, n, k) : SmallRoute{};
-    if (route.route == ROUTE_HALS && !column_sweep) {
+    // (column_sweep != 0, also set just above: the HALS fit takes the launch chain; the MU entry points pass 0)
+    const SmallPlan plan = pers && !column_sweep ? small_plan(method, bf, w_update, m, n, k) : SmallPlan{};
+    if (plan.route) {
+        // small problems: the whole loop as one persistent kernel per batch (csrc/dnmf_small.h); launched unbatched -- it indexes the problems itself
         const int B = ctx->B;
         ctx->B = 1;
-        rc = small_hals_fit(route, bf, A, m, n, lda, W, ldw, H, ldh, k, eps, itr, batch, a_stride, w_stride, h_stride, base, f, stream, &small);
-        ctx->B = B;
-        if (rc) return rc;
-    }
-    if (route.route == ROUTE_BARRIER && bf) {              // (MU/FRO on bf16-stored data)
-        const int B = ctx->B;
-        ctx->B = 1;
-        rc = small_fro_bf16_fit(A, m, n, lda, W, ldw, H, ldh, k, eps, itr, batch, a_stride, w_stride, h_stride, base, f, stream, &small);
-        ctx->B = B;
-        if (rc) return rc;
-    }
-    if ((route.route == ROUTE_BARRIER || route.route == ROUTE_WFIXED) && !bf) {
-        // small fp32 problems: the whole loop as one persistent kernel per batch (csrc/dnmf_small.h); launched unbatched -- it indexes the problems itself
-        const int B = ctx->B;
-        ctx->B = 1;
-        rc = small_fit(route, method == FIT_MU_FRO, (const float*)A, m, n, lda, W, ldw, H, ldh, k, eps, w_update, itr, batch, a_stride, w_stride, h_stride, base, f, stream, &small);
+        rc = small_launch(plan, bf, A, m, n, lda, W, ldw, H, ldh, k, eps, w_update, itr, batch, a_stride, w_stride, h_stride, base, f, stream, &small);
         ctx->B = B;
         if (rc) return rc;
         // (the W-fixed KL kernel leaves W alone; the clamp of pyDNMF.py:155 after step 0 is this launch)
@@ -436,18 +348,18 @@ int dnmf_fit_set_timeout(double seconds) {
 }
 
 int dnmf_hals_fit_persistent(long m, long n, int k) {
-    return (dnmf_persistent_on_() && m >= 1 && n >= 1 && small_hals_plan(m, n, k).ok) ? 1 : 0;
+    return (dnmf_persistent_on_() && small_geometry(GEO_HALS, m, n, k).nw) ? 1 : 0;
 }
 
 int dnmf_mu_fit_persistent(long m, long n, int k) {
-    return (dnmf_persistent_on_() && m >= 1 && n >= 1 && small_kl_plan(m, n, k).ok) ? 1 : 0;
+    return (dnmf_persistent_on_() && small_geometry(GEO_MU, m, n, k).nw) ? 1 : 0;
 }
 
 int dnmf_small_fit_plan(int method, int bf16, int w_update, long m, long n, int k, int out[8]) {
     if (method != FIT_MU_FRO && method != FIT_MU_KL && method != FIT_HALS_FRO) return fail(DNMF_EINVAL, "small_fit_plan: method %d (0 mu-fro, 1 mu-kl, 2 hals-fro)", method);
     if (bf16 && method == FIT_MU_KL) return fail(DNMF_EINVAL, "small_fit_plan: bfloat16 storage of A is for the Frobenius updates");
     if (!out || m < 1 || n < 1 || k < 1 || k > 32) return fail(DNMF_EINVAL, "small_fit_plan: null pointer or bad shape (m=%ld n=%ld k=%d; 1 <= k <= 32)", m, n, k);
-    const SmallRoute r = small_route(method, bf16 != 0, w_update, m, n, k);
+    const SmallPlan r = small_plan(method, bf16 != 0, w_update, m, n, k);
     out[0] = r.route; out[1] = r.kp; out[2] = r.nw; out[3] = r.alds ? 1 : 0; out[4] = r.P; out[5] = (int)r.ns; out[6] = r.cw; out[7] = r.bf16_resident ? 1 : 0;
     return DNMF_OK;
 }

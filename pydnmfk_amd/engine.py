@@ -6,6 +6,7 @@ row-major with unit inner stride; anything else raises (no silent host fallback)
 exception is the data matrix A of the Frobenius paths, which may be STORED as bfloat16 (the
 `*_bf16a` entry points: half the HBM bytes, fp32 arithmetic).
 """
+import contextlib
 import ctypes
 import os
 import weakref
@@ -672,12 +673,8 @@ class HipOps:
         for t, name in ((A3, "A"), (W3, "W"), (H3, "H")):
             if t.stride(2) != 1 and t.numel():
                 raise ValueError("fit: %s must have unit inner stride" % name)
-        if batched or (norm, method) != ("fro", "mu"):
-            check(fn(A3.data_ptr(), m, n, _ld(A3[0]), W3.data_ptr(), _ld(W3[0]), H3.data_ptr(), _ld(H3[0]), k, float(eps),
-                     int(bool(w_update)), int(itr), *extra, int(B), A3.stride(0), W3.stride(0), H3.stride(0), sq.data_ptr(),
-                     ws.data_ptr(), ws.numel(), _stream()))
-            return sq
-        with _wimage_bound(A, H, W):                  # one MU/Frobenius problem: every step of the fit may stream A's image
+        # one MU/Frobenius problem: every step of the fit may stream A's image
+        with _wimage_bound(A, H, W) if not batched and (norm, method) == ("fro", "mu") else contextlib.nullcontext():
             check(fn(A3.data_ptr(), m, n, _ld(A3[0]), W3.data_ptr(), _ld(W3[0]), H3.data_ptr(), _ld(H3[0]), k, float(eps),
                      int(bool(w_update)), int(itr), *extra, int(B), A3.stride(0), W3.stride(0), H3.stride(0), sq.data_ptr(),
                      ws.data_ptr(), ws.numel(), _stream()))

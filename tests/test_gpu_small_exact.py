@@ -79,10 +79,15 @@ def _cus():
     return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
 
 
-def _expected_launches(plan, B):
+def _expected_launches(plan, B, split=False):
     """launches of one fit call: the W-fixed kernel needs no residency (one launch); a barrier or HALS kernel runs as one launch when
     the B x P workgroups of the batch fit the device at one workgroup per CU (resident_launch, csrc/dnmf_fit.hip) -- asserted, so a
-    smaller device says so here instead of failing a count"""
+    smaller device says so here instead of failing a count.  split: a batch that cannot be resident at once -- a CU holds at most 32
+    waves, four 8-wave workgroups, whatever occupancy the compiler reaches -- so at least 2 launches (asserted too: a larger device says so)"""
+    if split:
+        assert plan[0] != 2 and plan[2] == 8 and B * plan[4] > 4 * _cus(), \
+            "%d problems x %d workgroups fit the %d CUs of this device at four 8-wave workgroups each: the batch may be one launch" % (B, plan[4], _cus())
+        return 2
     if plan[0] != 2:
         assert B * plan[4] <= _cus(), "%d problems x %d workgroups exceed the %d CUs of this device: the batch takes several launches" % (B, plan[4], _cus())
     return 1
@@ -92,8 +97,9 @@ def _counter(family, plan):
     return FAMILY_COUNTER[family] if family != "kl_wfixed" else (2 if plan[0] == 2 else 0)
 
 
-def _run_fixed(env, family, m, n, k, plan, itr, B, persistent=True):
-    """one fit of B fixed-point problems (different seeds); every check of the module docstring"""
+def _run_fixed(env, family, m, n, k, plan, itr, B, persistent=True, split=False):
+    """one fit of B fixed-point problems (different seeds); every check of the module docstring.  split: the batch takes several
+    launches (_expected_launches gives their least number, not their number)"""
     engine, lib = env
     ops = engine.HIP_OPS
     what = "%s %dx%d k=%d itr=%d batch=%d%s" % (family, m, n, k, itr, B, "" if persistent else " (launch chain)")
@@ -105,7 +111,11 @@ def _run_fixed(env, family, m, n, k, plan, itr, B, persistent=True):
     ops.hals_check()
     want = list(before)
     if persistent:
-        want[_counter(family, plan)] += _expected_launches(plan, B)
+        want[_counter(family, plan)] += _expected_launches(plan, B, split)
+    if split:
+        c = _counter(family, plan)
+        print("%s: %d launches" % (what, after[c] - before[c]))
+        want[c] = max(want[c], after[c])
     assert after == want, "%s: launches %s -> %s, expected %s {kl, fro, W-fixed, hals} (%d CUs)" % (what, before, after, want, _cus())
     Ap.check(what + " A")
     w3, h3 = Wp.check(what + " W"), Hp.check(what + " H")
@@ -203,3 +213,41 @@ def test_hals_reach(env, entry):
             print("%s %dx%d k=%d [%d] %s: max |x - f64| = %.3e of max %.3e" % (family, m, n, k, b, name, float((X.double() - Y).abs().max()), float(Y.abs().max())))
             assert _close(X, Y, 1e-3), (b, name, float((X.double() - Y).abs().max()), float(Y.abs().max()))
     assert not np.array_equal(w3[0], w3[1])
+
+
+@pytest.mark.parametrize("family", ["kl", "hals"])
+def test_batch_split_over_several_launches(env, family):
+    """a batch that resident_launch cannot keep resident at once runs as several launches, the later ones with z0 > 0: 17 problems of
+    8191 x 20, k = 3 (P = 64 workgroups of 8 waves each; 11 MB of data).  MU/KL: every problem is held to its fixed point; HALS: every
+    problem of the batch equals its single fit bit for bit.  The family's counter grows by at least 2, no other counter moves."""
+    engine, lib = env
+    ops = engine.HIP_OPS
+    m, n, k, B = 8191, 20, 3, 17
+    plan, = [e[4] for e in ex.SMALL_REACH if e[:4] == (family, m, n, k)]
+    assert plan[2] == 8 and plan[4] == 64 and _plan(lib, family, m, n, k) == plan
+    assert B * 64 > 4 * _cus(), "17 problems x 64 workgroups fit the %d CUs of this device at four 8-wave workgroups each: no split to test" % _cus()
+    if family == "kl":
+        for itr in (1, 3):
+            _run_fixed(env, family, m, n, k, plan, itr, B, split=True)
+        return
+    itr = 3
+    probs = [ex.hals_problem(m, n, k, seed) for seed in range(10, 10 + B)]
+    before = _launches(lib)
+    (Ap, Wp, Hp), args = _stacks(probs, B, torch.float32)
+    ops.fit("hals", "fro", *args, EPS, True, itr)
+    ops.hals_check()
+    after = _launches(lib)
+    print("hals %dx%d k=%d itr=%d batch=%d: %d launches" % (m, n, k, itr, B, after[3] - before[3]))
+    assert after[3] - before[3] >= _expected_launches(plan, B, split=True) and after[:3] == before[:3], "launches %s -> %s" % (before, after)
+    Ap.check("A")
+    w3, h3 = Wp.check("W"), Hp.check("H")
+    assert np.isfinite(w3).all() and np.isfinite(h3).all()
+    for b in range(B):
+        P1, a1 = _stacks(probs[b:b + 1], 1, torch.float32)
+        ops.fit("hals", "fro", *a1, EPS, True, itr)
+        ops.hals_check()
+        w1, h1 = P1[1].check("single W"), P1[2].check("single H")
+        assert np.array_equal(w3[b].view(np.uint32), w1.view(np.uint32)) and np.array_equal(h3[b].view(np.uint32), h1.view(np.uint32)), \
+            "problem %d of the batch differs from its single fit" % b
+    assert _launches(lib)[3] == after[3] + B
+    assert not np.array_equal(w3[0], w3[16])
