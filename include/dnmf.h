@@ -522,6 +522,71 @@ enum { DNMF_F64_PLAN_FAMILY = 0, DNMF_F64_PLAN_NT, DNMF_F64_PLAN_RT, DNMF_F64_PL
        DNMF_F64_PLAN_LEN };
 int dnmf_f64_plan(int op, long m, long n, int k, const long* ld, int method, long out[DNMF_F64_PLAN_LEN]);
 
+/* Which kernel a float32 entry point of the MU/Frobenius path launches for a shape, host arithmetic only (no GPU, nothing is launched):
+ * answered by the selectors the entry points themselves launch from (csrc/dnmf.hip "selectors", select_reduce of csrc/dnmf_host.h), so a
+ * test can assert the variant and the loop trips a shape reaches.  bf16a != 0: the _bf16a form of the entry point (A stored as bfloat16).
+ * op (DNMF_DENSE_OP_*), what m, n, k mean for it, and the operands whose pitch (`ld`, in elements; NULL or an entry <= 0: packed) and
+ * address modulo 16 (`align`, in bytes; NULL: all 0) enter the choice, four entries each, in this order:
+ *   AHT, AHT_HBLOCKS  A m x n, H k x n                 {A, H}       (AHT_HBLOCKS: ld[1] is the block width nh)
+ *   AHT_UPDATE_W      A m x n, H k x n, W m x k        {A, H, W}    (without a bound transposed image: dnmf_wimage_plan answers for that)
+ *   WTA, WTA_GRAM     A m x n, W m x k, AtW k x n      {A, W, AtW}  ws_bytes: the caller's workspace
+ *   GRAM_HHT          H k x n (m ignored)              {H}
+ *   GRAM_WTW          W m x k (n ignored)              {W}          ws_bytes as above
+ *   MU_UPDATE_W       W, AH m x k (n ignored)          {W, AH}
+ *   MU_UPDATE_H       H, AtW k x n (m ignored)         {H, AtW}
+ *   EW                X m rows x n columns (k ignored) {X, S, x}    ew_op: 0 clamp_min, 1 scale_cols_div, 2 scale_rows_mul,
+ *                                                                   3 kl_update_h, 4 kl_update_w
+ *   KL_UHT, KL_UHT_HBLOCKS, KL_WTU   A m x n at rank k (float32)   {A, W, H, out}   ws_bytes as above (KL_UHT_HBLOCKS: ld[2] is the
+ *                     block width nh)
+ *   RESID_SQNORM, COLUMN_ERR   A m x n, W, H at rank k   {A, W, H}   ws_bytes (RESID_SQNORM): the workspace of the _ws form, 0 without
+ *   SQNORM            A m x n (k ignored)              {A}
+ * The workspace and the Gram buffers are taken to be 16-byte aligned.  out (DNMF_DENSE_PLAN_*):
+ *   (KL and residual families) KL_UHT_PIPE = kl_uht_pipe_kernel on GRID_X whole 128-row tiles, EDGE = 1: kl_uht_kernel follows on the AUX
+ *           ragged ones; KL_UHT = kl_uht_kernel alone; KL_WTU = kl_wtu_kernel (B0 / BL: 32-row blocks and rows left of the first / last
+ *           chunk); RESID_LDS / RESID, COLERR (COUNT row chunks of PER rows per 128-column block), SQNORM (AUX: grid-stride trips);
+ *           MODE = 1: the factors are first copied into zero-padded images in the workspace (pad_factors);
+ *           KL16_UHT = kl_uht16_kernel (k <= 16; EDGE = 1: one split stored directly, no slabs; AUX: rows of the ragged last row tile),
+ *           KL16_WTU = kl_wtu16_kernel (B0 / BL: 16-row blocks, two per trip, and rows left of the first / last chunk)
+ *   FAMILY  DNMF_DENSE_FAM_*: NT16 = nt16_kernel, NT = nt_kernel, TN16 / TN16_GRAM = tn16_kernel without / with the riding Gram, TN =
+ *           tn_kernel, UPDATE_W16 / UPDATE_W_SEQ / UPDATE_H_SEQ = the kernels of csrc/dnmf_update.h, EW = ew_kernel, WIDE = 128 < k <= 256: the
+ *           entry point runs COUNT panel calls of PER columns of the factor (query them at k = 128 and k - 128), NONE = it refuses
+ *           (workspace too small, a pitch beyond the 32-bit tile offsets, a shape that is neither a long-row nor a patch one)
+ *   KT, FAST, MODE, PF, NT, V, EDGE, OCC   the template arguments of that name (MODE: 0 NT_STORE, 1 NT_FUSED_W; EW: 1 = the long-row form,
+ *           V = 4 or 1; TN16: V = columns per lane; UPDATE_W16: the template's NWV is BLOCK / 64)
+ *   NTEMP   the nontemporal flag: NTY of tn_kernel, the <.., 2, 2> form of update_h_seq_kernel, the streaming form of ew_kernel
+ *   WFAST   NT_FUSED_W: W allows the vector path of the kernel's second product
+ *   GRID_X, GRID_Y, BLOCK   the launch
+ *   COUNT, PER   column splits and columns per split (NT), row chunks and rows per chunk (TN, TN16), tiles and rows / columns per tile
+ *           (the updates)
+ *   REDUCE  the reduction that follows: 0 none, 1 single stage, 2 the wide single stage, 3 two stages of SLICES slices, then one
+ *   NK      NT, NT16: contraction tiles (32 columns; bf16 A: 64) of the first split; AUX: of the last split
+ *   INTERIOR  NT: (row tile, split) workgroups whose tiles are all in bounds, i.e. that take an interior loop;  ELIGIBLE: those of them
+ *           that take the descriptor loop of PF 10 / 13 (interior and inside the 2 GiB windows)
+ *   B0_FULL, B0_TAIL, BL_FULL, BL_TAIL   TN, TN16: full register batches (8 rows; TN16: 16) of the pipelined loop and rows left to the
+ *           predicated tail loop, for the first and for the last row chunk (a tn_kernel that is not FAST has no batches)
+ *   AUX     the updates: trips of the grid-stride tile loop of the busiest wave; EW patch form: log2 of the threads along a row
+ * Returns DNMF_EINVAL for a bad op, shape, rank, H layout or a null `out`. */
+enum { DNMF_DENSE_OP_AHT = 0, DNMF_DENSE_OP_AHT_HBLOCKS, DNMF_DENSE_OP_AHT_UPDATE_W, DNMF_DENSE_OP_WTA, DNMF_DENSE_OP_WTA_GRAM,
+       DNMF_DENSE_OP_GRAM_HHT, DNMF_DENSE_OP_GRAM_WTW, DNMF_DENSE_OP_MU_UPDATE_W, DNMF_DENSE_OP_MU_UPDATE_H, DNMF_DENSE_OP_EW,
+       DNMF_DENSE_OP_KL_UHT, DNMF_DENSE_OP_KL_UHT_HBLOCKS, DNMF_DENSE_OP_KL_WTU, DNMF_DENSE_OP_RESID_SQNORM, DNMF_DENSE_OP_COLUMN_ERR,
+       DNMF_DENSE_OP_SQNORM };
+enum { DNMF_DENSE_FAM_NONE = 0, DNMF_DENSE_FAM_NT16, DNMF_DENSE_FAM_NT, DNMF_DENSE_FAM_TN16, DNMF_DENSE_FAM_TN16_GRAM, DNMF_DENSE_FAM_TN,
+       DNMF_DENSE_FAM_UPDATE_W16, DNMF_DENSE_FAM_UPDATE_W_SEQ, DNMF_DENSE_FAM_UPDATE_H_SEQ, DNMF_DENSE_FAM_EW, DNMF_DENSE_FAM_WIDE,
+       DNMF_DENSE_FAM_KL_UHT_PIPE, DNMF_DENSE_FAM_KL_UHT, DNMF_DENSE_FAM_KL_WTU, DNMF_DENSE_FAM_RESID_LDS, DNMF_DENSE_FAM_RESID,
+       DNMF_DENSE_FAM_COLERR, DNMF_DENSE_FAM_SQNORM, DNMF_DENSE_FAM_KL16_UHT, DNMF_DENSE_FAM_KL16_WTU };
+enum { DNMF_DENSE_PLAN_FAMILY = 0, DNMF_DENSE_PLAN_KT, DNMF_DENSE_PLAN_FAST, DNMF_DENSE_PLAN_MODE, DNMF_DENSE_PLAN_PF, DNMF_DENSE_PLAN_NT,
+       DNMF_DENSE_PLAN_V, DNMF_DENSE_PLAN_EDGE, DNMF_DENSE_PLAN_OCC, DNMF_DENSE_PLAN_NTEMP, DNMF_DENSE_PLAN_WFAST, DNMF_DENSE_PLAN_GRID_X,
+       DNMF_DENSE_PLAN_GRID_Y, DNMF_DENSE_PLAN_BLOCK, DNMF_DENSE_PLAN_COUNT, DNMF_DENSE_PLAN_PER, DNMF_DENSE_PLAN_REDUCE,
+       DNMF_DENSE_PLAN_SLICES, DNMF_DENSE_PLAN_NK, DNMF_DENSE_PLAN_INTERIOR, DNMF_DENSE_PLAN_ELIGIBLE, DNMF_DENSE_PLAN_B0_FULL,
+       DNMF_DENSE_PLAN_B0_TAIL, DNMF_DENSE_PLAN_BL_FULL, DNMF_DENSE_PLAN_BL_TAIL, DNMF_DENSE_PLAN_AUX, DNMF_DENSE_PLAN_LEN };
+int dnmf_dense_plan(int op, int bf16a, long m, long n, int k, const long* ld, const int* align, size_t ws_bytes, int ew_op,
+                    long out[DNMF_DENSE_PLAN_LEN]);
+/* Every variant those selectors can return, from the selectors themselves (each is called over its whole discrete input domain): rows of
+ * DNMF_DENSE_VARIANT_LEN values {FAMILY, KT, FAST, MODE, PF, NT, V, EDGE, NTEMP, bf16a} as dnmf_dense_plan reports them; rows repeat.
+ * Returns the number of rows; at most `cap` of them are written to `rows` (NULL: count only). */
+enum { DNMF_DENSE_VARIANT_LEN = 10 };
+int dnmf_dense_plan_variants(long* rows, int cap);
+
 /* ---- Grid exchanges inside the library (RCCL over xGMI; replaces MPI_comm, dist_comm.py:16-56, and the mpi4py calls of
  * global_gram / global_mm, dist_nmf.py:681,707).  RCCL is bound at run time (dlopen; an RCCL already in the process -- the
  * PyTorch host's -- is preferred), so the library loads without it; these entry points then return DNMF_ECOMM.

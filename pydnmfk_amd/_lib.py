@@ -165,6 +165,18 @@ SIGNATURES["dnmf_f64_plan"] = [c_int, c_long, c_long, c_int, c_void_p, c_int, c_
 F64_OPS = ("aht", "wta", "kl_uht", "kl_wtu", "kl_quot", "sqdiff", "mu_update_w", "mu_update_h", "sum", "colsum", "ew", "fit")
 F64_FAMILIES = ("none", "nt", "tn", "kl_uht", "kl_wtu", "nn_cols", "nn_rows", "upd_h", "sum", "colsum", "ew", "fit_tiny", "fit_chain", "image")
 F64_PLAN_FIELDS = ("family", "nt", "rt", "vec", "full", "d", "count", "per", "v", "grid_x", "grid_y", "waves")
+# host only: op bf16a m n k ld (long[4] or NULL) align (int[4] or NULL) ws_bytes ew_op out: long[26] (include/dnmf.h DNMF_DENSE_*)
+SIGNATURES["dnmf_dense_plan"] = [c_int, c_int, c_long, c_long, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+SIGNATURES["dnmf_dense_plan_variants"] = [c_void_p, c_int]      # rows: long[cap][10] or NULL; returns the number of rows
+DENSE_VARIANT_FIELDS = ("family", "kt", "fast", "mode", "pf", "nt", "v", "edge", "ntemp", "bf16a")
+DENSE_OPS = ("aht", "aht_hblocks", "aht_update_w", "wta", "wta_gram", "gram_hht", "gram_wtw", "mu_update_w", "mu_update_h", "ew",
+             "kl_uht", "kl_uht_hblocks", "kl_wtu", "resid_sqnorm", "column_err", "sqnorm")
+DENSE_FAMILIES = ("none", "nt16", "nt", "tn16", "tn16_gram", "tn", "update_w16", "update_w_seq", "update_h_seq", "ew", "wide",
+                  "kl_uht_pipe", "kl_uht", "kl_wtu", "resid_lds", "resid", "colerr", "sqnorm", "kl16_uht", "kl16_wtu")
+DENSE_PLAN_FIELDS = ("family", "kt", "fast", "mode", "pf", "nt", "v", "edge", "occ", "ntemp", "wfast", "grid_x", "grid_y", "block", "count", "per",
+                     "reduce", "slices", "nk", "interior", "eligible", "b0_full", "b0_tail", "bl_full", "bl_tail", "aux")
+DENSE_REDUCE = ("none", "single", "wide", "two_stage")
+DENSE_EW_OPS = ("clamp_min", "scale_cols_div", "scale_rows_mul", "kl_update_h", "kl_update_w")
 # BCD (csrc/dnmf_bcd.hip)
 SIGNATURES["dnmf_bcd_state_init"] = [c_void_p, c_void_p, c_void_p]
 SIGNATURES["dnmf_bcd_init_factor"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_void_p]
@@ -277,3 +289,29 @@ def f64_plan(op, m, n, k, ld=(), method=0):
     p = dict(zip(F64_PLAN_FIELDS, out))
     p["family"] = F64_FAMILIES[p["family"]]
     return p
+
+
+def dense_plan(op, m, n, k, ld=(), align=(), bf16a=False, ws_bytes=None, ew_op="clamp_min"):
+    """dnmf_dense_plan as a dict: which kernel the float32 entry point `op` (a name of DENSE_OPS) launches for the shape -- `family` and
+    `reduce` by name, the other DENSE_PLAN_FIELDS as integers.  ld / align: the pitches (elements) and the addresses modulo 16 (bytes) of
+    the operands in the order include/dnmf.h gives for the op (missing: packed / aligned).  ws_bytes: None = dnmf_ws_bytes(m, n, k)."""
+    pitches = (c_long * 4)(*(list(ld) + [0] * (4 - len(ld))))
+    offs = (c_int * 4)(*(list(align) + [0] * (4 - len(align))))
+    out = (c_long * len(DENSE_PLAN_FIELDS))()
+    if ws_bytes is None:
+        ws_bytes = lib.dnmf_ws_bytes(int(m), int(n), int(k)) if op != "ew" else 0
+    check(lib.dnmf_dense_plan(DENSE_OPS.index(op), int(bool(bf16a)), int(m), int(n), int(k), pitches, offs, int(ws_bytes),
+                              DENSE_EW_OPS.index(ew_op), out))
+    p = dict(zip(DENSE_PLAN_FIELDS, out))
+    p["family"] = DENSE_FAMILIES[p["family"]]
+    p["reduce"] = DENSE_REDUCE[p["reduce"]]
+    return p
+
+
+def dense_plan_variants():
+    """dnmf_dense_plan_variants as a set of tuples in the order of DENSE_VARIANT_FIELDS (family by name)"""
+    n = lib.dnmf_dense_plan_variants(None, 0)
+    rows = (c_long * (n * len(DENSE_VARIANT_FIELDS)))()
+    assert lib.dnmf_dense_plan_variants(rows, n) == n
+    w = len(DENSE_VARIANT_FIELDS)
+    return {(DENSE_FAMILIES[rows[i * w]],) + tuple(rows[i * w + 1:(i + 1) * w]) for i in range(n)}

@@ -30,6 +30,9 @@
 HID int dnmf_wide_mu_update_w_(float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, long ldg, float eps, void* stream);
 HID int dnmf_wide_mu_update_h_(float* H, int k, long n, long ldh, const float* AtW, long ldatw, const float* G, long ldg, float eps, int clamp,
                                void* stream);
+// csrc/dnmf_kl.hip: its part of the launch-plan query
+HID int dnmf_dense_plan_kl_(int op, int bf16a, long m, long n, int k, const long* ld, const unsigned* off, size_t ws_bytes, long* out);
+HID int dnmf_dense_variants_kl_(long* rows, int cap, int nrows);
 // csrc/dnmf_timg.hip: the W phase from a bound transposed image of A (1 = not applicable)
 HID int dnmf_wimage_try_(const float* A, long m, long n, long lda, const float* H, int k, long ldh, const float* G, float* W, long ldw, float eps,
                          void* stream);
@@ -47,6 +50,162 @@ BatchCtx* dnmf_batch_() {
 
 namespace {
 
+// ---- selectors: every choice an entry point of this file makes between kernels, template arguments and grids, as a function of the
+// shape, the pitches and the operands' addresses modulo 16 (off16).  The launchers below launch from these and dnmf_dense_plan reports
+// them, so the query cannot drift from the dispatch.  `ea`: bytes per element of A (4: float, 2: bfloat16).
+constexpr int DENSE_BM = 128;                                        // rows of an nt_kernel / nt16_kernel workgroup, every rank
+inline unsigned nt_grid_x(long nrows) { return (unsigned)cdiv(nrows, DENSE_BM); }                           // row tiles of the NT kernels
+inline unsigned tn_grid(long nchunks, long ncolblk) { return (unsigned)cdiv(nchunks * ncolblk, 4); }         // a wave per (chunk, column block), 4 per workgroup
+// 32-bit tile offsets of the updates' buffer accesses: the entry points refuse pitches beyond these
+inline bool update_w_pitch_ok(long ldw, long ldah) { return ldw < (1L << 23) && ldah < (1L << 23); }
+// (27 + 4) rows of a 32-row block plus the column part stay below 2 GiB
+inline bool update_h_pitch_ok(long ldh, long ldatw) { return ldh < (1L << 24) && ldatw < (1L << 24); }
+inline bool rows16(unsigned off, long ld, size_t ea) { return off == 0 && (ld * ea) % 16 == 0; }             // = a_rows16
+inline bool vec4(unsigned off, long ld, long cols) { return off == 0 && ld % 4 == 0 && cols % 4 == 0; }
+// NT form: 16-byte loads from A and H
+inline bool nt_fast(unsigned offa, long lda, size_t ea, unsigned offh, long ldh, long n) { return rows16(offa, lda, ea) && vec4(offh, ldh, n); }
+inline bool nt16_applies(int k, bool fast, long n, bool b16) { return k <= 16 && fast && n % (b16 ? 64 : 32) == 0; }
+// PF code of nt_kernel (launch_nt_inst explains the codes); wgs: workgroups of the launch
+inline int nt_pf(bool fast_ks1, int mode, bool store_all, bool f32, long wgs) {
+    if (!(fast_ks1 && (mode == NT_FUSED_W || !store_all))) return 1;
+    if (!f32) return 5;                                              // bf16 X: one 64-wide tile in flight
+    // 13 = 10 with three tiles in flight: chosen when the grid has at most one workgroup per CU (a 32768-row
+    // shard = the per-GPU work of the 8-GPU configuration), where a single wave per SIMD has to cover the HBM latency
+    return wgs <= 256 ? 13 : 10;
+}
+
+// TN form (W^T A): the 16-wide kernel, its riding Gram, or the 32-wide kernel; fam < 0: the workspace is too small
+enum { WTA_TN16 = 0, WTA_TN = 1, WTA_EWS = -1 };
+struct WtaSel { int fam; bool fast, ride; int nt; Tn16Plan q; TnPlan p; size_t pb, need; };
+inline WtaSel select_wta(long m, long n, int k, int kt, size_t ea, unsigned offa, long lda, unsigned offw, long ldw, size_t ws_bytes, bool gram) {
+    WtaSel s{};
+    const int V = ea == 2 ? 8 : 4;
+    if (k <= 16 && rows16(offa, lda, ea) && n % (16 * V) == 0) {     // rank k <= 16: 16-byte aligned rows of A, whole column blocks, workspace permitting
+        s.q = plan_tn16(m, n, V);
+        s.pb = (size_t)s.q.nchunks * 16 * n * sizeof(float);
+        if (s.pb + reduce_scratch_bytes(s.q.nchunks, k, n) <= ws_bytes) {
+            const size_t gb = (size_t)s.q.nchunks * 256 * sizeof(float);            // partial Gram tiles behind the slabs
+            s.fam = WTA_TN16;
+            s.fast = true;
+            s.ride = gram && reduce_slices(s.q.nchunks) == 1 && s.pb + gb <= ws_bytes;
+            s.need = s.pb + reduce_scratch_bytes(s.q.nchunks, k, n);
+            return s;
+        }
+    }
+    s.nt = tn_nt(kt);
+    s.p = plan_tn(m, n, kt, s.nt, 256, wta_waves(m, n, kt, ea));
+    s.pb = (size_t)s.p.nchunks * s.p.chunk_stride * sizeof(float);
+    s.need = s.pb + reduce_scratch_bytes(s.p.nchunks, k, n);
+    s.fam = ws_bytes < s.need ? WTA_EWS : WTA_TN;
+    // the streamed A is read 4 elements per lane, W only KT per lane (1 float for k <= 32): W's alignment need is KT-wide
+    s.fast = offa % (4 * ea) == 0 && lda % 4 == 0 && n % 4 == 0 && offw % (4 * kt) == 0 && ldw % kt == 0 && k % kt == 0;
+    return s;
+}
+// W^T W streams only W (m x k): with 256-row chunks a 32768-row shard gives 128 waves on 32 CUs and the launch is one long
+// latency chain; 128-row chunks spread it over the chip (28.8 -> 21.5 us at 32768 rows, 30.2 -> 22.2 us at 65536, k = 64)
+// but cost a second reduction stage on tall matrices (34 -> 42 us at 262144 rows), which keep 256.
+inline long gram_min_rows(long m) { return m <= 131072 ? 128 : 256; }
+struct GramWtwSel { bool fast, ews; int nt; TnPlan p; size_t pb, need; };
+inline GramWtwSel select_gram_wtw(long m, int k, int kt, unsigned offw, long ldw, size_t ws_bytes) {
+    GramWtwSel s;
+    s.nt = kt == 4 ? 2 : kt;        // NT column sets per wave (KT = 4 uses 2 column blocks of 64 to bound registers)
+    s.p = plan_tn(m, 32 * kt, kt, s.nt, gram_min_rows(m));
+    s.pb = (size_t)s.p.nchunks * s.p.chunk_stride * sizeof(float);
+    s.need = s.pb + reduce_scratch_bytes(s.p.nchunks, 32 * kt, 32 * kt);
+    s.ews = ws_bytes < s.need;
+    s.fast = vec4(offw, ldw, k);
+    return s;
+}
+
+// the reductions of this file's entry points: a Gram's partial tiles ([nsplit] of `stride` floats, pitch ldp -> KP x KP, zero padded);
+// the 16-row slabs of tn16_kernel; the chunk slabs of tn_kernel
+inline ReduceShape reduce_shape_gram(long stride, long ldp, int nsplit, int k, int kp) { return ReduceShape{stride, ldp, nsplit, k, k, kp, kp}; }
+inline ReduceShape reduce_shape_wta16(const Tn16Plan& q, int k, long n) { return ReduceShape{16 * n, n, q.nchunks, k, n, k, n}; }
+inline ReduceShape reduce_shape_wta(const TnPlan& p, int k, long n) { return ReduceShape{p.chunk_stride, p.ldp, p.nchunks, k, n, k, n}; }
+
+// the W update: 16-row wave tiles (update_w16_kernel; dnmf_mu_update_w explains when) or 32-row tiles (update_w_seq_kernel<KT, V, OCC, EDGE>)
+// waves per workgroup and waves per SIMD of update_w16_kernel<KT, NWV, OCC>: the selector reports them and the launcher instantiates with them
+constexpr int w16_nwv(int kt) { return kt == 4 ? 8 : 4; }
+constexpr int w16_occ(int kt) { return kt == 4 ? 4 : 8; }
+struct UpdWSel { bool w16, edge; int kt, v, occ, nwv; unsigned grid; long tiles; };
+inline UpdWSel select_update_w(long m, int k, int kt, unsigned offw, long ldw, unsigned offah, long ldah) {
+    UpdWSel s;
+    const bool fast = offw == 0 && offah == 0 && ldw % 4 == 0 && ldah % 4 == 0 && k % 4 == 0;
+    s.kt = kt;
+    s.v = fast ? 4 : 1;
+    s.w16 = fast && k == 32 * kt && m % 16 == 0 && 16 * ldw * 4 + k * 4 < 0x7fffffffL && 16 * ldah * 4 + k * 4 < 0x7fffffffL;
+    if (s.w16) {
+        s.nwv = w16_nwv(kt);
+        s.occ = w16_occ(kt);
+        s.tiles = m / 16;
+        s.edge = false;
+        s.grid = (unsigned)std::min<long>(cdiv(s.tiles, s.nwv), kt == 1 ? (1L << 30) : 1024L);
+    } else {
+        // waves per SIMD requested from the compiler (3.2 GB pass, k = 64: 3 / 4 / 5 / 6 -> 4.68 / 4.72 / 4.76 / 4.67 TB/s;
+        // k = 128 holds 120 registers: 4)
+        s.nwv = upd_waves(kt);
+        s.occ = kt == 4 ? 4 : 5;
+        s.tiles = cdiv(m, 32);
+        s.edge = !(k == 32 * kt && m % 32 == 0);
+        s.grid = upd_grid(s.tiles, kt);
+    }
+    return s;
+}
+
+// the H update: update_h_seq_kernel<KT, NT, OCC, EDGE> and its nontemporal form <KT, 2, OCC, false, 2, 2> (dnmf_mu_update_h explains)
+struct UpdHSel { bool edge, nontemporal; int kt, nt, occ; unsigned grid; long tiles; };
+inline UpdHSel select_update_h(int k, long n, int kt, unsigned offh, long ldh, unsigned offs, long ldatw) {
+    UpdHSel s;
+    const bool even = offh % 8 == 0 && offs % 8 == 0 && ldh % 2 == 0 && ldatw % 2 == 0 && n % 2 == 0;
+    s.kt = kt;
+    s.nt = (even && k == 32 * kt && n % 64 == 0 && n / 64 >= 1024) ? 2 : 1;
+    s.occ = s.nt == 2 ? (kt == 4 ? 2 : 3) : 4;
+    s.tiles = cdiv(n, 32 * s.nt);
+    s.grid = upd_grid(s.tiles, kt);
+    s.edge = !(k == 32 * kt && n % (32 * s.nt) == 0);
+    // a long H that cannot stay cached (>= 64 MiB) streams with nontemporal loads and stores: 4.87 -> 5.07 TB/s at
+    // 64 x 2^22 (each line is touched by exactly one instruction here; the W-side kernel touches a line four times
+    // and loses a factor of two with the same hint, so it keeps the default policy)
+    s.nontemporal = s.nt == 2 && !s.edge && (double)k * n * sizeof(float) >= 64.0 * (1 << 20);
+    return s;
+}
+
+// element-wise pass (dnmf_stream.h): 16-byte vectors when X (and S) allow it; a long-row or a patch launch; `stream`: a matrix that
+// cannot stay in the caches until it is touched again (>= 256 MiB) is streamed with nontemporal loads and stores: 5.5 -> 6.1 TB/s on
+// the 1 GiB operands of the isolation pass; smaller factors (the W and H of a step are re-read by the next kernel) keep the default
+// policy.  bad: neither a long-row nor a patch shape.
+struct EwSel { bool vec, longrow, stream, bad; int txs; unsigned gx, gy; };
+inline EwSel select_ew(int op, long rows, long cols, unsigned offx, long ldx, bool has_s, unsigned offs, long lds_, bool has_x, unsigned offv) {
+    constexpr int U = 4;
+    EwSel s{};
+    s.vec = vec4(offx, ldx, cols) && (!has_s || (offs == 0 && lds_ % 4 == 0)) &&
+            (!has_x || op == EW_ROWS_MUL || op == EW_KL_BYROW || offv == 0);
+    const long cvecs = s.vec ? cols / 4 : cols;
+    s.stream = s.vec && (double)rows * cols * sizeof(float) >= 256.0 * (1 << 20);
+    if (cvecs > 256 && rows <= 65535) {
+        s.longrow = true;
+        s.gx = (unsigned)cdiv(cvecs, 256 * U);
+        s.gy = (unsigned)rows;
+        return s;
+    }
+    if (cvecs > 256) { s.bad = true; return s; }
+    while (s.txs < 8 && (1L << s.txs) < cvecs) ++s.txs;
+    s.gx = (unsigned)cdiv(rows, (256 >> s.txs) * U);
+    s.gy = 1;
+    return s;
+}
+
+// the squared norm: sqnorm_kernel<FAST, TA>, a grid-stride loop over 4-element vectors (FAST) or elements, at most 2048 workgroups
+struct SqnormSel { bool fast; unsigned grid; long trips; };
+inline SqnormSel select_sqnorm(long m, long n, size_t ea, unsigned offa, long lda) {
+    SqnormSel s;
+    s.fast = offa % (4 * ea) == 0 && lda % 4 == 0 && n % 4 == 0;
+    const long work = s.fast ? m * (n / 4) : m * n;
+    s.grid = (unsigned)std::min<long>(cdiv(work, 256), 2048);
+    s.trips = cdiv(work, 256L * s.grid);
+    return s;
+}
+
 template <int KT, int MT, int NW, int KS, bool FAST, int MODE, int PF, typename TX>
 int launch_nt_pf(const NtArgs& a, int nsplit, hipStream_t st) {
     constexpr int BM = 32 * MT * (NW / KS);
@@ -55,7 +214,8 @@ int launch_nt_pf(const NtArgs& a, int nsplit, hipStream_t st) {
     constexpr size_t lds = std::is_same<TX, bf16_t>::value ? (lds16 > lds32 ? lds16 : lds32) : lds32;
     static bool once = false;
     if (!once) { allow_lds(nt_kernel<KT, MT, NW, KS, FAST, MODE, PF, TX>, lds); once = true; }
-    DNMF_LAUNCH((nt_kernel<KT, MT, NW, KS, FAST, MODE, PF, TX>), dim3((unsigned)cdiv(a.nrows, BM), (unsigned)nsplit),
+    static_assert(BM == DENSE_BM, "the plan query reports 128-row workgroups");
+    DNMF_LAUNCH((nt_kernel<KT, MT, NW, KS, FAST, MODE, PF, TX>), dim3(nt_grid_x(a.nrows), (unsigned)nsplit),
                        dim3(64 * NW), lds, st, a);
     return check_launch("nt_kernel");
 }
@@ -84,15 +244,15 @@ int launch_nt_inst(const NtArgs& a, int nsplit, hipStream_t st) {
     // kernel reaches 103 / 118 / 128 TFLOP/s at 32768 / 65536 / 262144 rows against 82-89 / 91 / 113 from HBM -- with
     // IDENTICAL cycle counts (PMC): the difference is the core clock the chip holds (1.8-2.0 GHz with the HBM stream,
     // 2.2-2.4 GHz without), i.e. power, not the instruction schedule (measured ceilings).
-    if constexpr (FAST && KS == 1) if (MODE == NT_FUSED_W || !a.store_all) {
-        if constexpr (std::is_same<TX, float>::value) {
-            // 13 = 10 with three tiles in flight: chosen when the grid has at most one workgroup per CU (a 32768-row
-            // shard = the per-GPU work of the 8-GPU configuration), where a single wave per SIMD has to cover the HBM latency
-            constexpr int BM = 32 * MT * (NW / KS);
-            if (cdiv(a.nrows, BM) * nsplit <= 256) return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 13, TX>(a, nsplit, st);
-            return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 10, TX>(a, nsplit, st);
+    constexpr int BM = 32 * MT * (NW / KS);
+    constexpr bool F32 = std::is_same<TX, float>::value;
+    const int pf = nt_pf(FAST && KS == 1, MODE, a.store_all != 0, F32, cdiv(a.nrows, BM) * nsplit);
+    if constexpr (FAST && KS == 1) {
+        if constexpr (F32) {
+            if (pf == 13) return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 13, TX>(a, nsplit, st);
+            if (pf == 10) return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 10, TX>(a, nsplit, st);
         } else {
-            return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 5, TX>(a, nsplit, st);   // bf16 X: one 64-wide tile in flight
+            if (pf == 5) return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 5, TX>(a, nsplit, st);
         }
     }
     return launch_nt_pf<KT, MT, NW, KS, FAST, MODE, 1, TX>(a, nsplit, st);
@@ -119,8 +279,7 @@ inline int nt_rows_per_tile(int) { return 128; }
 
 template <int MODE, typename TY = float>
 int launch_tn(int kt, bool fast, const TnArgs& a, hipStream_t st) {
-    const long waves = (long)a.nchunks * a.ncolblk;
-    const dim3 grid((unsigned)cdiv(waves, 4)), block(256);
+    const dim3 grid(tn_grid(a.nchunks, a.ncolblk)), block(256);
     // nontemporal loads of the streamed operand (A): +2 % at 262144 rows, +7 % at 65536 rows, slightly less HBM
     // traffic (the reused W rows stay in L2).
 #define TN_CASE(KT_, NT_)                                                                                \
@@ -135,11 +294,6 @@ int launch_tn(int kt, bool fast, const TnArgs& a, hipStream_t st) {
 #undef TN_CASE
     return fail(DNMF_EINVAL, "unsupported k tile %d", kt);
 }
-
-// W^T W streams only W (m x k): with 256-row chunks a 32768-row shard gives 128 waves on 32 CUs and the launch is one long
-// latency chain; 128-row chunks spread it over the chip (28.8 -> 21.5 us at 32768 rows, 30.2 -> 22.2 us at 65536, k = 64)
-// but cost a second reduction stage on tall matrices (34 -> 42 us at 262144 rows), which keep 256.
-inline long gram_min_rows(long m) { return m <= 131072 ? 128 : 256; }
 
 struct SplitPlan { int nsplit; long cols_per_split; };
 
@@ -158,16 +312,11 @@ SplitPlan plan_gram_nt(long n) {
 template <int OP>
 int launch_ew(float* X, long rows, long cols, long ldx, const float* Sm, long lds_, const float* x, float eps, int clamp,
               const char* what, hipStream_t st) {
-    const bool vec = aligned16(X) && ldx % 4 == 0 && cols % 4 == 0 && (!Sm || (aligned16(Sm) && lds_ % 4 == 0)) &&
-                     (!x || OP == EW_ROWS_MUL || OP == EW_KL_BYROW || aligned16(x));
-    const long cvecs = vec ? cols / 4 : cols;
-    constexpr int U = 4;
-    if (cvecs > 256 && rows <= 65535) {                       // long rows
-        const dim3 grid((unsigned)cdiv(cvecs, 256 * U), (unsigned)rows);
-        // a matrix that cannot stay in the caches until it is touched again (>= 256 MiB) is streamed with nontemporal
-        // loads and stores: 5.5 -> 6.1 TB/s on the 1 GiB operands of the isolation pass; smaller factors (the W and H of a
-        // step are re-read by the next kernel) keep the default policy.
-        if (vec && (double)rows * cols * sizeof(float) >= 256.0 * (1 << 20)) {
+    const EwSel sel = select_ew(OP, rows, cols, off16(X), ldx, Sm != nullptr, off16(Sm), lds_, x != nullptr, off16(x));
+    const bool vec = sel.vec;
+    if (sel.longrow) {                                        // long rows
+        const dim3 grid(sel.gx, sel.gy);
+        if (sel.stream) {
             DNMF_LAUNCH((ew_kernel<OP, 4, true, true>), grid, dim3(256), 0, st, X, rows, cols, ldx, Sm, lds_, x, eps, clamp, 0);
             return check_launch(what);
         }
@@ -175,12 +324,10 @@ int launch_ew(float* X, long rows, long cols, long ldx, const float* Sm, long ld
         else DNMF_LAUNCH((ew_kernel<OP, 1, true>), grid, dim3(256), 0, st, X, rows, cols, ldx, Sm, lds_, x, eps, clamp, 0);
         return check_launch(what);
     }
-    if (cvecs > 256) return fail(DNMF_EINVAL, "%s: %ld rows x %ld columns: neither a long-row nor a patch shape", what, rows, cols);
-    int txs = 0;
-    while (txs < 8 && (1L << txs) < cvecs) ++txs;
-    const long TY = 256 >> txs;
-    const dim3 grid((unsigned)cdiv(rows, TY * U));
-    if (vec && (double)rows * cols * sizeof(float) >= 256.0 * (1 << 20)) {
+    if (sel.bad) return fail(DNMF_EINVAL, "%s: %ld rows x %ld columns: neither a long-row nor a patch shape", what, rows, cols);
+    const int txs = sel.txs;
+    const dim3 grid(sel.gx);
+    if (sel.stream) {
         DNMF_LAUNCH((ew_kernel<OP, 4, false, true>), grid, dim3(256), 0, st, X, rows, cols, ldx, Sm, lds_, x, eps, clamp, txs);
         return check_launch(what);
     }
@@ -338,11 +485,10 @@ int dnmf_gram_hht(const float* H, int k, long n, long ldh, float* G, void* ws, s
     a.Y = H; a.ldy = ldh; a.yrows = k;
     a.cols_per_split = sp.cols_per_split;
     a.out = (float*)ws; a.ldo = kp; a.split_stride = tile_rows * kp; a.store_all = 1;
-    const bool fast = aligned16(H) && ldh % 4 == 0 && n % 4 == 0;
+    const bool fast = nt_fast(off16(H), ldh, sizeof(float), off16(H), ldh, n);
     int rc = launch_nt<NT_STORE>(kt, fast, a, sp.nsplit, S(stream));
     if (rc) return rc;
-    return launch_reduce((const float*)ws, tile_rows * kp, kp, sp.nsplit, G, kp, k, k, kp, kp,
-                         (float*)((char*)ws + pbytes), S(stream));
+    return launch_reduce((const float*)ws, reduce_shape_gram(tile_rows * kp, kp, sp.nsplit, k, kp), G, kp, (float*)((char*)ws + pbytes), S(stream));
 }
 
 int dnmf_gram_wtw(const float* W, long m, int k, long ldw, float* G, void* ws, size_t ws_bytes, void* stream) {
@@ -353,19 +499,17 @@ int dnmf_gram_wtw(const float* W, long m, int k, long ldw, float* G, void* ws, s
     const int kt = kt_of(k);
     REQUIRE(kt > 0 && W && G && ws && m >= 1 && ldw >= k, "gram_wtw: bad arguments (k=%d m=%ld)", k, m);
     const int kp = 32 * kt;
-    // TN form with X = Y = W; NT column sets per wave (KT = 4 uses 2 column blocks of 64 to bound registers)
-    const int nt = kt == 4 ? 2 : kt;
-    TnPlan p = plan_tn(m, kp, kt, nt, gram_min_rows(m));
-    const size_t pbytes = (size_t)p.nchunks * p.chunk_stride * sizeof(float);
-    const size_t need = pbytes + reduce_scratch_bytes(p.nchunks, kp, kp);
-    if (ws_bytes < need) return fail(DNMF_EWS, "gram_wtw: workspace %zu < %zu", ws_bytes, need);
+    // TN form with X = Y = W
+    const GramWtwSel sel = select_gram_wtw(m, k, kt, off16(W), ldw, ws_bytes);
+    const TnPlan& p = sel.p;
+    const size_t pbytes = sel.pb, need = sel.need;
+    if (sel.ews) return fail(DNMF_EWS, "gram_wtw: workspace %zu < %zu", ws_bytes, need);
     TnArgs a{};
     a.X = W; a.ldx = ldw; a.xcols = k; a.Y = W; a.ldy = ldw; a.ycols = k;
     a.nrows = m; a.rows_per_chunk = p.rows_per_chunk; a.nchunks = p.nchunks; a.ncolblk = p.ncolblk;
     a.P = (float*)ws; a.chunk_stride = p.chunk_stride; a.ldp = p.ldp;
-    const bool fast = aligned16(W) && ldw % 4 == 0 && k % 4 == 0;
-    const long waves = (long)a.nchunks * a.ncolblk;
-    const dim3 grid((unsigned)cdiv(waves, 4)), block(256);
+    const bool fast = sel.fast;
+    const dim3 grid(tn_grid(a.nchunks, a.ncolblk)), block(256);
     hipStream_t st = S(stream);
 #define GRAM_CASE(KT_, NT_)                                                                          \
     if (kt == KT_) {                                                                                 \
@@ -376,8 +520,7 @@ int dnmf_gram_wtw(const float* W, long m, int k, long ldw, float* G, void* ws, s
 #undef GRAM_CASE
     int rc = check_launch("gram_wtw");
     if (rc) return rc;
-    return launch_reduce((const float*)ws, p.chunk_stride, p.ldp, p.nchunks, G, kp, k, k, kp, kp,
-                         (float*)((char*)ws + pbytes), st);
+    return launch_reduce((const float*)ws, reduce_shape_gram(p.chunk_stride, p.ldp, p.nchunks, k, kp), G, kp, (float*)((char*)ws + pbytes), st);
 }
 
 }  // extern "C"  (typed implementations shared by the fp32 and the bf16-A entry points)
@@ -389,8 +532,8 @@ namespace {
 template <int MODE, typename TA>
 int try_nt16(const NtArgs& a, bool fast, long n, int k, hipStream_t st) {
     constexpr bool b16 = std::is_same<TA, bf16_t>::value;
-    if (!(k <= 16 && fast && n % (b16 ? BKH : BK) == 0)) return 1;
-    DNMF_LAUNCH((nt16_kernel<TA, MODE>), dim3((unsigned)cdiv(a.nrows, 128)), dim3(256), nt16_lds_bytes(b16), st, a);
+    if (!nt16_applies(k, fast, n, b16)) return 1;
+    DNMF_LAUNCH((nt16_kernel<TA, MODE>), dim3(nt_grid_x(a.nrows)), dim3(256), nt16_lds_bytes(b16), st, a);
     return check_launch("nt16_kernel");
 }
 
@@ -416,7 +559,7 @@ int aht_impl(const TA* A, long m, long n, long lda, const float* H, int k, long 
     }
     a.cols_per_split = round_up(n, BK);
     a.out = AH; a.ldo = ldah; a.split_stride = 0; a.store_all = 0;
-    const bool fast = a_rows16(A, lda) && aligned16(H) && ldh % 4 == 0 && n % 4 == 0;
+    const bool fast = nt_fast(off16(A), lda, sizeof(TA), off16(H), ldh, n);
     if (int rc16 = try_nt16<NT_STORE, TA>(a, fast, n, k, S(stream)); rc16 != 1) return rc16;
     return launch_nt<NT_STORE, TA>(kt, fast, a, 1, S(stream));
 }
@@ -436,8 +579,8 @@ int aht_update_w_impl(const TA* A, long m, long n, long lda, const float* H, int
     a.Y = H; a.ldy = ldh; a.yrows = k;
     a.cols_per_split = round_up(n, BK);
     a.W = W; a.ldw = ldw; a.G = G; a.eps = eps; a.k = k;
-    const bool fast = a_rows16(A, lda) && aligned16(H) && ldh % 4 == 0 && n % 4 == 0;
-    a.wfast = aligned16(W) && ldw % 4 == 0 && k % 4 == 0;
+    const bool fast = nt_fast(off16(A), lda, sizeof(TA), off16(H), ldh, n);
+    a.wfast = vec4(off16(W), ldw, k);
     if (int rc16 = try_nt16<NT_FUSED_W, TA>(a, fast, n, k, S(stream)); rc16 != 1) return rc16;
     return launch_nt<NT_FUSED_W, TA>(kt, fast, a, 1, S(stream));
 }
@@ -469,15 +612,15 @@ int dnmf_aht_update_w_bf16a(const void* A, long m, long n, long lda, const float
 }  // extern "C"
 namespace {
 template <int KT, int V, int OCC>
-int launch_update_w_seq(float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, float eps, hipStream_t st) {
+int launch_update_w_seq(const UpdWSel& sel, float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, float eps, hipStream_t st) {
     constexpr size_t lds = (size_t)(32 * KT) * (32 * KT + 4) * sizeof(float);
     static bool once = false;
     if (!once) { allow_lds(update_w_seq_kernel<KT, V, OCC, false>, lds); allow_lds(update_w_seq_kernel<KT, V, OCC, true>, lds); once = true; }
     // one tile per wave (the kernel's tile loop only matters beyond 2^31 workgroups): measured on the 3.2 GB pass at
     // k = 64, workgroups that loop over tiles (256 x OCC of them, G staged once each) 4.5 TB/s, one tile per wave 4.75
-    const unsigned grid = upd_grid(cdiv(m, 32), KT);
+    const unsigned grid = sel.grid;
     constexpr unsigned T = 64 * upd_waves(KT);
-    if (k == 32 * KT && m % 32 == 0)
+    if (!sel.edge)
         DNMF_LAUNCH((update_w_seq_kernel<KT, V, OCC, false>), dim3(grid), dim3(T), lds, st, W, m, k, ldw, AH, ldah, G, eps, (float*)nullptr, 0L);
     else
         DNMF_LAUNCH((update_w_seq_kernel<KT, V, OCC, true>), dim3(grid), dim3(T), lds, st, W, m, k, ldw, AH, ldah, G, eps, (float*)nullptr, 0L);
@@ -494,37 +637,32 @@ int dnmf_mu_update_w(float* W, long m, int k, long ldw, const float* AH, long ld
     }
     const int kt = kt_of(k);
     REQUIRE(kt > 0 && W && AH && G && m >= 1 && ldw >= k && ldah >= k, "mu_update_w: bad arguments");
-    REQUIRE(ldw < (1L << 23) && ldah < (1L << 23), "mu_update_w: leading dimension beyond the 32-bit tile offsets");
-    const bool fast = aligned16(W) && aligned16(AH) && ldw % 4 == 0 && ldah % 4 == 0 && k % 4 == 0;
+    REQUIRE(update_w_pitch_ok(ldw, ldah), "mu_update_w: leading dimension beyond the 32-bit tile offsets");
+    const UpdWSel sel = select_update_w(m, k, kt, off16(W), ldw, off16(AH), ldah);
     hipStream_t st = S(stream);
-    {   // 16-row wave tiles (update_w16_kernel; round 5): full ranks, whole tiles, aligned rows, 2 GiB descriptor windows.  Measured on
-        // the isolation pass (k x 2^22): k = 32: 0.346 -> 0.310 ms (0.58 -> 0.65 of HBM), k = 64: 0.759 -> 0.632
-        // (0.53 -> 0.64), k = 128: 1.49 -> 1.40 (0.54 -> 0.58: the matrix work of 2 n k^2 flops bounds that one).  Workgroups walk
-        // their tiles grid-stride; capped at 1024 workgroups from k = 64 on (G staged once per several tiles: 0.648 -> 0.632 at
-        // k = 64), one tile per wave at k = 32.
-        if (fast && k == 32 * kt && m % 16 == 0 && 16 * ldw * 4 + k * 4 < 0x7fffffffL && 16 * ldah * 4 + k * 4 < 0x7fffffffL) {
-            const long tiles = m / 16;
-            auto run = [&](auto kt_c, auto nwv_c, auto occ_c) {
-                constexpr int KT_ = decltype(kt_c)::value, NWV_ = decltype(nwv_c)::value, OCC_ = decltype(occ_c)::value;
-                constexpr size_t lds = (size_t)(32 * KT_) * (32 * KT_ + 4) * sizeof(float);
-                static bool once = false;
-                if (!once) { allow_lds(update_w16_kernel<KT_, NWV_, OCC_>, lds); once = true; }
-                const long cap = KT_ == 1 ? (1L << 30) : 1024L;
-                const unsigned grid = (unsigned)std::min<long>(cdiv(tiles, NWV_), cap);
-                DNMF_LAUNCH((update_w16_kernel<KT_, NWV_, OCC_>), dim3(grid), dim3(64 * NWV_), lds, st, W, m, ldw, AH, ldah, G, eps);
-                return check_launch("mu_update_w(16)");
-            };
-            using std::integral_constant;
-            if (kt == 1) return run(integral_constant<int, 1>{}, integral_constant<int, 4>{}, integral_constant<int, 8>{});
-            if (kt == 2) return run(integral_constant<int, 2>{}, integral_constant<int, 4>{}, integral_constant<int, 8>{});
-            return run(integral_constant<int, 4>{}, integral_constant<int, 8>{}, integral_constant<int, 4>{});
-        }
+    // 16-row wave tiles (update_w16_kernel; round 5): full ranks, whole tiles, aligned rows, 2 GiB descriptor windows.  Measured on
+    // the isolation pass (k x 2^22): k = 32: 0.346 -> 0.310 ms (0.58 -> 0.65 of HBM), k = 64: 0.759 -> 0.632
+    // (0.53 -> 0.64), k = 128: 1.49 -> 1.40 (0.54 -> 0.58: the matrix work of 2 n k^2 flops bounds that one).  Workgroups walk
+    // their tiles grid-stride; capped at 1024 workgroups from k = 64 on (G staged once per several tiles: 0.648 -> 0.632 at
+    // k = 64), one tile per wave at k = 32.
+    if (sel.w16) {
+        auto run = [&](auto kt_c) {
+            constexpr int KT_ = decltype(kt_c)::value, NWV_ = w16_nwv(KT_), OCC_ = w16_occ(KT_);
+            constexpr size_t lds = (size_t)(32 * KT_) * (32 * KT_ + 4) * sizeof(float);
+            static bool once = false;
+            if (!once) { allow_lds(update_w16_kernel<KT_, NWV_, OCC_>, lds); once = true; }
+            DNMF_LAUNCH((update_w16_kernel<KT_, NWV_, OCC_>), dim3(sel.grid), dim3(64 * NWV_), lds, st, W, m, ldw, AH, ldah, G, eps);
+            return check_launch("mu_update_w(16)");
+        };
+        using std::integral_constant;
+        if (kt == 1) return run(integral_constant<int, 1>{});
+        if (kt == 2) return run(integral_constant<int, 2>{});
+        return run(integral_constant<int, 4>{});
     }
-    // waves per SIMD requested from the compiler (3.2 GB pass, k = 64: 3 / 4 / 5 / 6 -> 4.68 / 4.72 / 4.76 / 4.67 TB/s;
-    // k = 128 holds 120 registers: 4)
-    if (kt == 1) return fast ? launch_update_w_seq<1, 4, 5>(W, m, k, ldw, AH, ldah, G, eps, st) : launch_update_w_seq<1, 1, 5>(W, m, k, ldw, AH, ldah, G, eps, st);
-    if (kt == 2) return fast ? launch_update_w_seq<2, 4, 5>(W, m, k, ldw, AH, ldah, G, eps, st) : launch_update_w_seq<2, 1, 5>(W, m, k, ldw, AH, ldah, G, eps, st);
-    return fast ? launch_update_w_seq<4, 4, 4>(W, m, k, ldw, AH, ldah, G, eps, st) : launch_update_w_seq<4, 1, 4>(W, m, k, ldw, AH, ldah, G, eps, st);
+    const bool fast = sel.v == 4;
+    if (kt == 1) return fast ? launch_update_w_seq<1, 4, 5>(sel, W, m, k, ldw, AH, ldah, G, eps, st) : launch_update_w_seq<1, 1, 5>(sel, W, m, k, ldw, AH, ldah, G, eps, st);
+    if (kt == 2) return fast ? launch_update_w_seq<2, 4, 5>(sel, W, m, k, ldw, AH, ldah, G, eps, st) : launch_update_w_seq<2, 1, 5>(sel, W, m, k, ldw, AH, ldah, G, eps, st);
+    return fast ? launch_update_w_seq<4, 4, 4>(sel, W, m, k, ldw, AH, ldah, G, eps, st) : launch_update_w_seq<4, 1, 4>(sel, W, m, k, ldw, AH, ldah, G, eps, st);
 }
 
 }  // extern "C"
@@ -544,54 +682,42 @@ int wta_impl(const TA* A, long m, long n, long lda, const float* W, int k, long 
     REQUIRE(kt > 0 && A && W && AtW && ws && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldatw >= n, "wta: bad arguments");
     const int kp = 32 * kt;
     auto gram_first = [&]() { return G ? dnmf_gram_wtw(W, m, k, ldw, G, ws, ws_bytes, stream) : DNMF_OK; };
-    {   // rank k <= 16: 16-wide kernel (16-byte aligned rows of A, whole column blocks, workspace permitting)
-        constexpr int V = std::is_same<TA, bf16_t>::value ? 8 : 4;
-        if (k <= 16 && a_rows16(A, lda) && n % (16 * V) == 0) {
-            const Tn16Plan q = plan_tn16(m, n, V);
-            const size_t pb = (size_t)q.nchunks * 16 * n * sizeof(float);
-            if (pb + reduce_scratch_bytes(q.nchunks, k, n) <= ws_bytes) {
-                TnArgs a{};
-                a.X = W; a.ldx = ldw; a.xcols = k; a.Y = A; a.ldy = lda; a.ycols = n;
-                a.nrows = m; a.rows_per_chunk = q.rows_per_chunk; a.nchunks = q.nchunks; a.ncolblk = q.ncolblk;
-                a.P = (float*)ws; a.chunk_stride = 16 * n; a.ldp = n;
-                const size_t gb = (size_t)q.nchunks * 256 * sizeof(float);            // partial Gram tiles behind the slabs
-                const bool ride = G && reduce_slices(q.nchunks) == 1 && pb + gb <= ws_bytes;
-                int rc;
-                if (!ride && (rc = gram_first())) return rc;
-                hipStream_t st = S(stream);
-                const dim3 grid16((unsigned)cdiv((long)q.nchunks * q.ncolblk, 4));
-                if (ride) {
-                    a.Pg = (float*)((char*)ws + pb);
-                    DNMF_LAUNCH((tn16_kernel<TA, true>), grid16, dim3(256), 0, st, a);
-                } else {
-                    DNMF_LAUNCH((tn16_kernel<TA>), grid16, dim3(256), 0, st, a);
-                }
-                if ((rc = check_launch("tn16_kernel"))) return rc;
-                const GramTail gt{a.Pg, G, 16, k, kp, q.nchunks};
-                return launch_reduce((const float*)ws, 16 * n, n, q.nchunks, AtW, ldatw, k, n, k, n, (float*)((char*)ws + pb), st,
-                                     ride ? &gt : nullptr);
-            }
+    const WtaSel sel = select_wta(m, n, k, kt, sizeof(TA), off16(A), lda, off16(W), ldw, ws_bytes, G != nullptr);
+    if (sel.fam == WTA_TN16) {   // rank k <= 16: 16-wide kernel (16-byte aligned rows of A, whole column blocks, workspace permitting)
+        const Tn16Plan& q = sel.q;
+        const size_t pb = sel.pb;
+        TnArgs a{};
+        a.X = W; a.ldx = ldw; a.xcols = k; a.Y = A; a.ldy = lda; a.ycols = n;
+        a.nrows = m; a.rows_per_chunk = q.rows_per_chunk; a.nchunks = q.nchunks; a.ncolblk = q.ncolblk;
+        a.P = (float*)ws; a.chunk_stride = 16 * n; a.ldp = n;
+        const bool ride = sel.ride;
+        int rc;
+        if (!ride && (rc = gram_first())) return rc;
+        hipStream_t st = S(stream);
+        const dim3 grid16(tn_grid(q.nchunks, q.ncolblk));
+        if (ride) {
+            a.Pg = (float*)((char*)ws + pb);
+            DNMF_LAUNCH((tn16_kernel<TA, true>), grid16, dim3(256), 0, st, a);
+        } else {
+            DNMF_LAUNCH((tn16_kernel<TA>), grid16, dim3(256), 0, st, a);
         }
+        if ((rc = check_launch("tn16_kernel"))) return rc;
+        const GramTail gt{a.Pg, G, 16, k, kp, q.nchunks};
+        return launch_reduce((const float*)ws, reduce_shape_wta16(q, k, n), AtW, ldatw, (float*)((char*)ws + pb), st, ride ? &gt : nullptr);
     }
-    const int nt = tn_nt(kt);
-    TnPlan p = plan_tn(m, n, kt, nt, 256, wta_waves(m, n, kt, sizeof(TA)));
-    const size_t pbytes = (size_t)p.nchunks * p.chunk_stride * sizeof(float);
-    const size_t need = pbytes + reduce_scratch_bytes(p.nchunks, k, n);
-    if (ws_bytes < need) return fail(DNMF_EWS, "wta: workspace %zu < %zu", ws_bytes, need);
+    const TnPlan& p = sel.p;
+    const size_t pbytes = sel.pb, need = sel.need;
+    if (sel.fam == WTA_EWS) return fail(DNMF_EWS, "wta: workspace %zu < %zu", ws_bytes, need);
     TnArgs a{};
     a.X = W; a.ldx = ldw; a.xcols = k; a.Y = A; a.ldy = lda; a.ycols = n;
     a.nrows = m; a.rows_per_chunk = p.rows_per_chunk; a.nchunks = p.nchunks; a.ncolblk = p.ncolblk;
     a.P = (float*)ws; a.chunk_stride = p.chunk_stride; a.ldp = p.ldp;
-    // the streamed A is read 4 elements per lane, W only KT per lane (1 float for k <= 32): W's alignment need is KT-wide
-    const bool fast = a_aligned(A) && lda % 4 == 0 && n % 4 == 0 &&
-                      ((uintptr_t)W % (4 * kt)) == 0 && ldw % kt == 0 && k % kt == 0;
     // (the riding Gram was also built for the 32-wide kernel at 16 < k <= 32: no gain -- 0.3707 vs 0.3706 ms per iteration at
     // 65536 x 4096, k = 32, where the two launches it saves cost 6 us -- so these ranks keep dnmf_gram_wtw)
     int rc;
     if ((rc = gram_first())) return rc;
-    if ((rc = launch_tn<TN_PARTIAL, TA>(kt, fast, a, S(stream)))) return rc;
-    return launch_reduce((const float*)ws, p.chunk_stride, p.ldp, p.nchunks, AtW, ldatw, k, n, k, n,
-                         (float*)((char*)ws + pbytes), S(stream));
+    if ((rc = launch_tn<TN_PARTIAL, TA>(kt, sel.fast, a, S(stream)))) return rc;
+    return launch_reduce((const float*)ws, reduce_shape_wta(p, k, n), AtW, ldatw, (float*)((char*)ws + pbytes), S(stream));
 }
 }  // namespace
 extern "C" {
@@ -619,25 +745,22 @@ int dnmf_wta_gram_bf16a(const void* A, long m, long n, long lda, const float* W,
 }  // extern "C"
 namespace {
 template <int KT, int NT, int OCC>
-int launch_update_h_seq(float* H, int k, long n, long ldh, const float* AtW, long ldatw, const float* G, float eps, int clamp,
+int launch_update_h_seq(const UpdHSel& sel, float* H, int k, long n, long ldh, const float* AtW, long ldatw, const float* G, float eps, int clamp,
                         hipStream_t st) {
     constexpr size_t lds = (size_t)(32 * KT) * (32 * KT + 4) * sizeof(float);
     static bool once = false;
     if (!once) { allow_lds(update_h_seq_kernel<KT, NT, OCC, false>, lds); allow_lds(update_h_seq_kernel<KT, NT, OCC, true>, lds); once = true; }
-    const unsigned grid = upd_grid(cdiv(n, 32 * NT), KT);
+    const unsigned grid = sel.grid;
     constexpr unsigned T = 64 * upd_waves(KT);
     if constexpr (NT == 2) {
-        // a long H that cannot stay cached (>= 64 MiB) streams with nontemporal loads and stores: 4.87 -> 5.07 TB/s at
-        // 64 x 2^22 (each line is touched by exactly one instruction here; the W-side kernel touches a line four times
-        // and loses a factor of two with the same hint, so it keeps the default policy)
-        if (k == 32 * KT && n % (32 * NT) == 0 && (double)k * n * sizeof(float) >= 64.0 * (1 << 20)) {
+        if (sel.nontemporal) {
             static bool once2 = false;
             if (!once2) { allow_lds(update_h_seq_kernel<KT, NT, OCC, false, 2, 2>, lds); once2 = true; }
             DNMF_LAUNCH((update_h_seq_kernel<KT, NT, OCC, false, 2, 2>), dim3(grid), dim3(T), lds, st, H, k, n, ldh, AtW, ldatw, G, eps, clamp);
             return check_launch("mu_update_h");
         }
     }
-    if (k == 32 * KT && n % (32 * NT) == 0)
+    if (!sel.edge)
         DNMF_LAUNCH((update_h_seq_kernel<KT, NT, OCC, false>), dim3(grid), dim3(T), lds, st, H, k, n, ldh, AtW, ldatw, G, eps, clamp);
     else
         DNMF_LAUNCH((update_h_seq_kernel<KT, NT, OCC, true>), dim3(grid), dim3(T), lds, st, H, k, n, ldh, AtW, ldatw, G, eps, clamp);
@@ -654,9 +777,8 @@ int dnmf_mu_update_h(float* H, int k, long n, long ldh, const float* AtW, long l
     }
     const int kt = kt_of(k);
     REQUIRE(kt > 0 && H && AtW && G && n >= 1 && ldh >= n && ldatw >= n, "mu_update_h: bad arguments");
-    // 32-bit tile offsets of the buffer accesses: (27 + 4) rows of a 32-row block plus the column part stay below 2 GiB
-    REQUIRE(ldh < (1L << 24) && ldatw < (1L << 24), "mu_update_h: leading dimension beyond the 32-bit tile offsets");
-    const bool even = ((uintptr_t)H % 8 == 0) && ((uintptr_t)AtW % 8 == 0) && ldh % 2 == 0 && ldatw % 2 == 0 && n % 2 == 0;
+    REQUIRE(update_h_pitch_ok(ldh, ldatw), "mu_update_h: leading dimension beyond the 32-bit tile offsets");
+    const UpdHSel sel = select_update_h(k, n, kt, off16(H), ldh, off16(AtW), ldatw);
     hipStream_t st = S(stream);
     // variant code = 10 * NT (columns per lane) + waves per SIMD requested from the compiler.  Measured on the 3.2 GB pass
     // (k x 2^22): k = 64: 14 / 16 -> 4.76 / 4.78 TB/s, 23 -> 4.97, 24 (spills) -> 4.0; k = 32: 14 -> 4.93, 23 -> 5.26;
@@ -665,14 +787,14 @@ int dnmf_mu_update_h(float* H, int k, long n, long ldh, const float* AtW, long l
     // k = 128 (round 4): LDS holds two workgroups per CU there whatever the registers allow (66 KiB of G each), so the two-column
     // tile at TWO waves per SIMD (200 registers, no spills) costs no occupancy and halves the accesses per byte: 4.25 -> 4.5 TB/s on
     // the 6.4 GB pass (variant 23 spills there: 2.4 TB/s)
-    if (even && k == 32 * kt && n % 64 == 0 && n / 64 >= 1024) {
-        if (kt == 1) return launch_update_h_seq<1, 2, 3>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
-        if (kt == 2) return launch_update_h_seq<2, 2, 3>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
-        return launch_update_h_seq<4, 2, 2>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
+    if (sel.nt == 2) {
+        if (kt == 1) return launch_update_h_seq<1, 2, 3>(sel, H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
+        if (kt == 2) return launch_update_h_seq<2, 2, 3>(sel, H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
+        return launch_update_h_seq<4, 2, 2>(sel, H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
     }
-    if (kt == 1) return launch_update_h_seq<1, 1, 4>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
-    if (kt == 2) return launch_update_h_seq<2, 1, 4>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
-    return launch_update_h_seq<4, 1, 4>(H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
+    if (kt == 1) return launch_update_h_seq<1, 1, 4>(sel, H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
+    if (kt == 2) return launch_update_h_seq<2, 1, 4>(sel, H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
+    return launch_update_h_seq<4, 1, 4>(sel, H, k, n, ldh, AtW, ldatw, G, eps, clamp, st);
 }
 
 int dnmf_clamp_min(float* X, long rows, long cols, long ldx, float eps, void* stream) {
@@ -708,9 +830,9 @@ int sqnorm_impl(const TA* A, long m, long n, long lda, double* out, void* stream
     REQUIRE(A && out && m >= 1 && n >= 1 && lda >= n, "sqnorm: bad arguments");
     hipStream_t st = S(stream);
     if (batch_memset(out, 0, sizeof(double), st) != hipSuccess) return fail(DNMF_EHIP, "sqnorm: memset failed");
-    const bool fast = a_aligned(A) && lda % 4 == 0 && n % 4 == 0;
-    const long work = fast ? m * (n / 4) : m * n;
-    const unsigned grid = (unsigned)std::min<long>(cdiv(work, 256), 2048);
+    const SqnormSel sel = select_sqnorm(m, n, sizeof(TA), off16(A), lda);
+    const bool fast = sel.fast;
+    const unsigned grid = sel.grid;
     if (fast) DNMF_LAUNCH((sqnorm_kernel<true, TA>), dim3(grid), dim3(256), 0, st, A, m, n, lda, out);
     else DNMF_LAUNCH((sqnorm_kernel<false, TA>), dim3(grid), dim3(256), 0, st, A, m, n, lda, out);
     return check_launch("sqnorm");
@@ -869,3 +991,233 @@ int dnmf_mu_kl_step(const float* A, long m, long n, long lda, float* W, long ldw
 }
 
 }  // extern "C"
+
+// =============================================================================================== the launch-plan query
+namespace {
+// full register batches and rows left to the predicated tail loop of a row chunk of `rows` rows (tn_mainloop: batches of 8 rows on the
+// FAST path only; tn16_body: batches of 16 rows)
+inline void chunk_trips(long rows, int batch, bool pipelined, long* full, long* tail) {
+    *full = pipelined ? rows / batch : 0;
+    *tail = rows - *full * batch;
+}
+inline void report_chunks(long* out, long m, long rpc, int nchunks, int batch, bool pipelined) {
+    out[DNMF_DENSE_PLAN_COUNT] = nchunks;
+    out[DNMF_DENSE_PLAN_PER] = rpc;
+    chunk_trips(std::min(rpc, m), batch, pipelined, &out[DNMF_DENSE_PLAN_B0_FULL], &out[DNMF_DENSE_PLAN_B0_TAIL]);
+    chunk_trips(m - (long)(nchunks - 1) * rpc, batch, pipelined, &out[DNMF_DENSE_PLAN_BL_FULL], &out[DNMF_DENSE_PLAN_BL_TAIL]);
+}
+inline void report_reduce(long* out, const ReduceSel& r) {
+    out[DNMF_DENSE_PLAN_REDUCE] = r.kind;
+    out[DNMF_DENSE_PLAN_SLICES] = r.kind == REDUCE_TWO_STAGE ? r.ny : 0;
+}
+// the NT form: X nrows x ncols against Y yrows x ncols in `nsplit` column splits of `cps`.  The interior / window tests are the ones
+// nt_mainloop and nt_mainloop_b16 (csrc/dnmf_nt.h) make per workgroup on the device, repeated here for every (row tile, split).
+void report_nt(long* out, int mode, bool store_all, bool b16, bool fast, bool wfast, int k, long nrows, long ncols, long ldx, long ldy, long cps,
+               int nsplit, long hblk) {
+    const int tile = b16 ? 64 : 32;
+    if (nt16_applies(k, fast, ncols, b16)) {
+        out[DNMF_DENSE_PLAN_FAMILY] = DNMF_DENSE_FAM_NT16;
+        out[DNMF_DENSE_PLAN_KT] = 1; out[DNMF_DENSE_PLAN_FAST] = 1; out[DNMF_DENSE_PLAN_MODE] = mode;
+        out[DNMF_DENSE_PLAN_GRID_X] = nt_grid_x(nrows); out[DNMF_DENSE_PLAN_GRID_Y] = 1; out[DNMF_DENSE_PLAN_BLOCK] = 256;
+        out[DNMF_DENSE_PLAN_COUNT] = 1; out[DNMF_DENSE_PLAN_PER] = cps;
+        out[DNMF_DENSE_PLAN_NK] = out[DNMF_DENSE_PLAN_AUX] = ncols / tile;
+        out[DNMF_DENSE_PLAN_WFAST] = wfast;
+        return;
+    }
+    const int kt = kt_of(k), kp = 32 * kt;
+    const long rowtiles = nt_grid_x(nrows);
+    const int pf = nt_pf(fast, mode, store_all, !b16, rowtiles * nsplit);
+    out[DNMF_DENSE_PLAN_FAMILY] = DNMF_DENSE_FAM_NT;
+    out[DNMF_DENSE_PLAN_KT] = kt; out[DNMF_DENSE_PLAN_FAST] = fast; out[DNMF_DENSE_PLAN_MODE] = mode; out[DNMF_DENSE_PLAN_PF] = pf;
+    out[DNMF_DENSE_PLAN_GRID_X] = rowtiles; out[DNMF_DENSE_PLAN_GRID_Y] = nsplit; out[DNMF_DENSE_PLAN_BLOCK] = 256;
+    out[DNMF_DENSE_PLAN_COUNT] = nsplit; out[DNMF_DENSE_PLAN_PER] = cps;
+    out[DNMF_DENSE_PLAN_WFAST] = wfast;
+    long interior = 0, eligible = 0;
+    for (int s = 0; s < nsplit; ++s) {
+        const long cbeg = (long)s * cps, cend = std::min(cbeg + cps, ncols), w = cend - cbeg;
+        if (s == 0) out[DNMF_DENSE_PLAN_NK] = cdiv(w, tile);
+        if (s == nsplit - 1) out[DNMF_DENSE_PLAN_AUX] = cdiv(w, tile);
+        if (!(fast && w % tile == 0 && (b16 || k >= kp))) continue;
+        interior += nrows / nt_rows_per_tile(kt);
+        const long yoff = hblk ? (cend - 1) / hblk * ((long)(k - 1) * hblk) : 0;
+        const bool bufok = (nt_rows_per_tile(kt) * ldx + w) * 4 < 0x7fffffffL && ((long)kp * ldy + w + yoff) * 4 < 0x7fffffffL;
+        if (bufok && (pf == 10 || pf == 13)) eligible += nrows / nt_rows_per_tile(kt);
+    }
+    out[DNMF_DENSE_PLAN_INTERIOR] = interior;
+    out[DNMF_DENSE_PLAN_ELIGIBLE] = eligible;
+}
+}  // namespace
+
+extern "C" int dnmf_dense_plan(int op, int bf16a, long m, long n, int k, const long* ld, const int* align, size_t ws_bytes, int ew_op,
+                               long out[DNMF_DENSE_PLAN_LEN]) {
+    REQUIRE(out && op >= DNMF_DENSE_OP_AHT && op <= DNMF_DENSE_OP_SQNORM && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_MAX_K,
+            "dense_plan: null output, unknown op or bad shape (op=%d m=%ld n=%ld k=%d)", op, m, n, k);
+    for (int i = 0; i < DNMF_DENSE_PLAN_LEN; ++i) out[i] = 0;
+    auto L = [&](int i, long packed) { return ld && ld[i] > 0 ? ld[i] : packed; };
+    auto O = [&](int i) { return align ? (unsigned)(align[i] & 15) : 0u; };
+    const size_t ea = bf16a ? 2 : 4;
+    if (op == DNMF_DENSE_OP_EW) {                                    // a matrix of m rows and n columns; operands X, S, x
+        REQUIRE(ew_op >= EW_CLAMP && ew_op <= EW_KL_BYCOL, "dense_plan: bad element-wise op %d", ew_op);
+        const bool has_s = ew_op == EW_KL_BYROW || ew_op == EW_KL_BYCOL, has_x = ew_op != EW_CLAMP;
+        const EwSel s = select_ew(ew_op, m, n, O(0), L(0, n), has_s, O(1), L(1, n), has_x, O(2));
+        if (s.bad) return DNMF_OK;                                   // family NONE: the entry point refuses the shape
+        out[DNMF_DENSE_PLAN_FAMILY] = DNMF_DENSE_FAM_EW;
+        out[DNMF_DENSE_PLAN_V] = s.vec ? 4 : 1; out[DNMF_DENSE_PLAN_MODE] = s.longrow; out[DNMF_DENSE_PLAN_NTEMP] = s.stream;
+        out[DNMF_DENSE_PLAN_GRID_X] = s.gx; out[DNMF_DENSE_PLAN_GRID_Y] = s.gy; out[DNMF_DENSE_PLAN_BLOCK] = 256;
+        out[DNMF_DENSE_PLAN_AUX] = s.txs;
+        return DNMF_OK;
+    }
+    if (op == DNMF_DENSE_OP_SQNORM) {                                // operand A
+        const SqnormSel s = select_sqnorm(m, n, ea, O(0), L(0, n));
+        out[DNMF_DENSE_PLAN_FAMILY] = DNMF_DENSE_FAM_SQNORM;
+        out[DNMF_DENSE_PLAN_FAST] = s.fast; out[DNMF_DENSE_PLAN_GRID_X] = s.grid; out[DNMF_DENSE_PLAN_GRID_Y] = 1; out[DNMF_DENSE_PLAN_BLOCK] = 256;
+        out[DNMF_DENSE_PLAN_AUX] = s.trips;
+        return DNMF_OK;
+    }
+    if (wide_k(k)) {       // 128 < k <= 256: two panels of the tuned kernels (query k = 128 and k - 128) and the plain kernels of csrc/dnmf_wide.hip
+        REQUIRE(op != DNMF_DENSE_OP_AHT_HBLOCKS && op != DNMF_DENSE_OP_AHT_UPDATE_W, "dense_plan: this entry point takes k <= %d", DNMF_TUNED_MAX_K);
+        out[DNMF_DENSE_PLAN_FAMILY] = DNMF_DENSE_FAM_WIDE;
+        out[DNMF_DENSE_PLAN_COUNT] = (op == DNMF_DENSE_OP_GRAM_HHT || op == DNMF_DENSE_OP_GRAM_WTW) ? 4 : 2;
+        out[DNMF_DENSE_PLAN_PER] = WIDE_PANEL;
+        return DNMF_OK;
+    }
+    const int kt = kt_of(k), kp = 32 * kt;
+    if (op >= DNMF_DENSE_OP_KL_UHT) {                                // operands A, W, H, out: csrc/dnmf_kl.hip answers
+        const long lds4[4] = {L(0, n), L(1, k), L(2, n), L(3, op == DNMF_DENSE_OP_KL_WTU ? n : k)};
+        const unsigned offs4[4] = {O(0), O(1), O(2), O(3)};
+        return dnmf_dense_plan_kl_(op, bf16a, m, n, k, lds4, offs4, ws_bytes, out);
+    }
+    switch (op) {
+    case DNMF_DENSE_OP_AHT: case DNMF_DENSE_OP_AHT_HBLOCKS: case DNMF_DENSE_OP_AHT_UPDATE_W: {      // operands A, H, W (the fused form)
+        const bool blocks = op == DNMF_DENSE_OP_AHT_HBLOCKS;
+        REQUIRE(!(blocks && bf16a), "dense_plan: aht_hblocks takes float32 data");
+        const long lda = L(0, n), ldh = L(1, n), hblk = blocks ? ldh : 0;
+        REQUIRE(!blocks || (n % hblk == 0 && hblk % BK == 0), "dense_plan: bad H layout (block %ld, n %ld)", hblk, n);
+        const bool fused = op == DNMF_DENSE_OP_AHT_UPDATE_W;
+        report_nt(out, fused ? NT_FUSED_W : NT_STORE, false, bf16a != 0, nt_fast(O(0), lda, ea, O(1), ldh, n), fused && vec4(O(2), L(2, k), k), k, m, n,
+                  lda, ldh, round_up(n, BK), 1, hblk);
+        break;
+    }
+    case DNMF_DENSE_OP_GRAM_HHT: {                                   // operand H (k x n)
+        const long ldh = L(0, n);
+        const SplitPlan sp = plan_gram_nt(n);
+        report_nt(out, NT_STORE, true, false, nt_fast(O(0), ldh, sizeof(float), O(0), ldh, n), false, k, k, n, ldh, ldh, sp.cols_per_split, sp.nsplit, 0);
+        report_reduce(out, select_reduce(reduce_shape_gram(nt_rows_per_tile(kt) * kp, kp, sp.nsplit, k, kp), 0, 0, kp));
+        break;
+    }
+    case DNMF_DENSE_OP_GRAM_WTW: {                                   // operand W (m x k)
+        const GramWtwSel s = select_gram_wtw(m, k, kt, O(0), L(0, k), ws_bytes);
+        if (s.ews) break;
+        out[DNMF_DENSE_PLAN_FAMILY] = DNMF_DENSE_FAM_TN;
+        out[DNMF_DENSE_PLAN_KT] = kt; out[DNMF_DENSE_PLAN_FAST] = s.fast; out[DNMF_DENSE_PLAN_NT] = s.nt; out[DNMF_DENSE_PLAN_NTEMP] = 0;
+        out[DNMF_DENSE_PLAN_GRID_X] = tn_grid(s.p.nchunks, s.p.ncolblk); out[DNMF_DENSE_PLAN_GRID_Y] = 1; out[DNMF_DENSE_PLAN_BLOCK] = 256;
+        report_chunks(out, m, s.p.rows_per_chunk, s.p.nchunks, 8, s.fast);
+        report_reduce(out, select_reduce(reduce_shape_gram(s.p.chunk_stride, s.p.ldp, s.p.nchunks, k, kp), 0, 0, kp));
+        break;
+    }
+    case DNMF_DENSE_OP_WTA: case DNMF_DENSE_OP_WTA_GRAM: {           // operands A, W, AtW
+        const WtaSel s = select_wta(m, n, k, kt, ea, O(0), L(0, n), O(1), L(1, k), ws_bytes, op == DNMF_DENSE_OP_WTA_GRAM);
+        if (s.fam == WTA_EWS) break;
+        const long ldatw = L(2, n);
+        if (s.fam == WTA_TN16) {
+            out[DNMF_DENSE_PLAN_FAMILY] = s.ride ? DNMF_DENSE_FAM_TN16_GRAM : DNMF_DENSE_FAM_TN16;
+            out[DNMF_DENSE_PLAN_KT] = 1; out[DNMF_DENSE_PLAN_FAST] = 1; out[DNMF_DENSE_PLAN_V] = bf16a ? 8 : 4; out[DNMF_DENSE_PLAN_NTEMP] = 1;
+            out[DNMF_DENSE_PLAN_GRID_X] = tn_grid(s.q.nchunks, s.q.ncolblk); out[DNMF_DENSE_PLAN_GRID_Y] = 1; out[DNMF_DENSE_PLAN_BLOCK] = 256;
+            report_chunks(out, m, s.q.rows_per_chunk, s.q.nchunks, 16, true);
+            report_reduce(out, select_reduce(reduce_shape_wta16(s.q, k, n), 0, O(2), ldatw));
+        } else {
+            out[DNMF_DENSE_PLAN_FAMILY] = DNMF_DENSE_FAM_TN;
+            out[DNMF_DENSE_PLAN_KT] = kt; out[DNMF_DENSE_PLAN_FAST] = s.fast; out[DNMF_DENSE_PLAN_NT] = s.nt; out[DNMF_DENSE_PLAN_NTEMP] = s.fast;
+            out[DNMF_DENSE_PLAN_GRID_X] = tn_grid(s.p.nchunks, s.p.ncolblk); out[DNMF_DENSE_PLAN_GRID_Y] = 1; out[DNMF_DENSE_PLAN_BLOCK] = 256;
+            report_chunks(out, m, s.p.rows_per_chunk, s.p.nchunks, 8, s.fast);
+            report_reduce(out, select_reduce(reduce_shape_wta(s.p, k, n), 0, O(2), ldatw));
+        }
+        break;
+    }
+    case DNMF_DENSE_OP_MU_UPDATE_W: {                                // operands W, AH (m x k; n ignored)
+        const long ldw = L(0, k), ldah = L(1, k);
+        if (!update_w_pitch_ok(ldw, ldah)) break;
+        const UpdWSel s = select_update_w(m, k, kt, O(0), ldw, O(1), ldah);
+        out[DNMF_DENSE_PLAN_FAMILY] = s.w16 ? DNMF_DENSE_FAM_UPDATE_W16 : DNMF_DENSE_FAM_UPDATE_W_SEQ;
+        out[DNMF_DENSE_PLAN_KT] = kt; out[DNMF_DENSE_PLAN_FAST] = s.v == 4; out[DNMF_DENSE_PLAN_V] = s.v; out[DNMF_DENSE_PLAN_EDGE] = s.edge;
+        out[DNMF_DENSE_PLAN_OCC] = s.occ;
+        out[DNMF_DENSE_PLAN_GRID_X] = s.grid; out[DNMF_DENSE_PLAN_GRID_Y] = 1; out[DNMF_DENSE_PLAN_BLOCK] = 64 * s.nwv;
+        out[DNMF_DENSE_PLAN_COUNT] = s.tiles; out[DNMF_DENSE_PLAN_PER] = s.w16 ? 16 : 32;
+        out[DNMF_DENSE_PLAN_AUX] = cdiv(s.tiles, (long)s.grid * s.nwv);
+        break;
+    }
+    case DNMF_DENSE_OP_MU_UPDATE_H: {                                // operands H, AtW (k x n; m ignored)
+        const long ldh = L(0, n), ldatw = L(1, n);
+        if (!update_h_pitch_ok(ldh, ldatw)) break;
+        const UpdHSel s = select_update_h(k, n, kt, O(0), ldh, O(1), ldatw);
+        out[DNMF_DENSE_PLAN_FAMILY] = DNMF_DENSE_FAM_UPDATE_H_SEQ;
+        out[DNMF_DENSE_PLAN_KT] = kt; out[DNMF_DENSE_PLAN_NT] = s.nt; out[DNMF_DENSE_PLAN_EDGE] = s.edge; out[DNMF_DENSE_PLAN_NTEMP] = s.nontemporal;
+        out[DNMF_DENSE_PLAN_OCC] = s.occ;
+        out[DNMF_DENSE_PLAN_GRID_X] = s.grid; out[DNMF_DENSE_PLAN_GRID_Y] = 1; out[DNMF_DENSE_PLAN_BLOCK] = 64 * upd_waves(kt);
+        out[DNMF_DENSE_PLAN_COUNT] = s.tiles; out[DNMF_DENSE_PLAN_PER] = 32 * s.nt;
+        out[DNMF_DENSE_PLAN_AUX] = cdiv(s.tiles, (long)s.grid * upd_waves(kt));
+        break;
+    }
+    default: break;
+    }
+    return DNMF_OK;
+}
+
+// Every variant the selectors can return: each selector is called over its whole discrete input domain (every rank tile, both
+// alignments, both sides of each of its thresholds) and what it answers is written as one row {family, KT, FAST, MODE, PF, NT, V, EDGE,
+// NTEMP, bf16 A}; rows repeat.  Returns the number of rows (at most `cap` are written).  tests/test_dense_plan.py holds the reach table
+// of the exact tests against this list.
+extern "C" int dnmf_dense_plan_variants(long* rows, int cap) {
+    int nrows = 0;
+    auto emit = [&](long fam, long kt, long fast, long mode, long pf, long nt, long v, long edge, long ntemp, long b16) {
+        const long r[DNMF_DENSE_VARIANT_LEN] = {fam, kt, fast, mode, pf, nt, v, edge, ntemp, b16};
+        if (rows && nrows < cap) for (int i = 0; i < DNMF_DENSE_VARIANT_LEN; ++i) rows[(long)nrows * DNMF_DENSE_VARIANT_LEN + i] = r[i];
+        ++nrows;
+    };
+    for (int b16 = 0; b16 < 2; ++b16)                                 // k = 16: the 16-wide kernels where their predicates take them
+        for (int fast = 0; fast < 2; ++fast) {
+            for (int mode = NT_STORE; mode <= NT_FUSED_W; ++mode)
+                for (long n : {128L, 100L})
+                    if (nt16_applies(16, fast != 0, n, b16 != 0)) emit(DNMF_DENSE_FAM_NT16, 1, 1, mode, 0, 0, 0, 0, 0, b16);
+            for (int gram = 0; gram < 2; ++gram)
+                for (size_t wsb : {(size_t)2 * 16 * 128 * 4, ~size_t(0)}) {            // the slabs alone; room for the riding Gram
+                    const WtaSel s = select_wta(300, 128, 16, 1, b16 ? 2 : 4, fast ? 0 : 4, 136, 0, 20, wsb, gram != 0);
+                    if (s.fam == WTA_TN16) emit(s.ride ? DNMF_DENSE_FAM_TN16_GRAM : DNMF_DENSE_FAM_TN16, 1, 1, 0, 0, 0, b16 ? 8 : 4, 0, 1, b16);
+                }
+        }
+    for (int kt : {1, 2, 4}) {
+        const int kp = 32 * kt;
+        for (int fast = 0; fast < 2; ++fast) {
+            for (int b16 = 0; b16 < 2; ++b16)
+                for (int mode = NT_STORE; mode <= NT_FUSED_W; ++mode)
+                    for (int store_all = 0; store_all < (mode == NT_STORE && !b16 ? 2 : 1); ++store_all)       // (store_all: H H^T, float32)
+                        for (long wgs : {256L, 257L}) emit(DNMF_DENSE_FAM_NT, kt, fast, mode, nt_pf(fast, mode, store_all, !b16, wgs), 0, 0, 0, 0, b16);
+            const unsigned off = fast ? 0 : 4;
+            for (size_t ea : {(size_t)4, (size_t)2}) {
+                const WtaSel s = select_wta(300, 132, kp, kt, ea, off, 136, off, kp + 4, ~size_t(0), false);
+                emit(DNMF_DENSE_FAM_TN, kt, s.fast, 0, 0, s.nt, 0, 0, s.fast, ea == 2);
+            }
+            const GramWtwSel g = select_gram_wtw(300, kp, kt, off, kp + 4, ~size_t(0));
+            emit(DNMF_DENSE_FAM_TN, kt, g.fast, 0, 0, g.nt, 0, 0, 0, 0);
+            for (int k : {kp, kp - 4})
+                for (long m : {64L, 48L, 40L}) {                      // whole 32-row tiles, whole 16-row tiles, neither
+                    const UpdWSel s = select_update_w(m, k, kt, off, kp + 4, off, kp + 4);
+                    emit(s.w16 ? DNMF_DENSE_FAM_UPDATE_W16 : DNMF_DENSE_FAM_UPDATE_W_SEQ, kt, s.v == 4, 0, 0, 0, s.v, s.edge, 0, 0);
+                }
+            for (int k : {kp, kp - 4})
+                for (long n : {96L, 100L, 65536L, 65536L + 32, (long)(64.0 * (1 << 20) / (4 * kp))}) {      // NT = 1 whole / ragged; NT = 2; 64 MiB
+                    const UpdHSel s = select_update_h(k, n, kt, off, n + 4, off, n + 4);
+                    emit(DNMF_DENSE_FAM_UPDATE_H_SEQ, kt, 0, 0, 0, s.nt, 0, s.edge, s.nontemporal, 0);
+                }
+        }
+    }
+    for (unsigned off : {0u, 4u})
+        for (long rows_ : {10L, 1000L, 16384L, 65536L})
+            for (long cols : {2000L, 40L, 4096L, 1024L}) {
+                const EwSel s = select_ew(EW_CLAMP, rows_, cols, off, cols + 4, false, 0, 0, false, 0);
+                if (!s.bad) emit(DNMF_DENSE_FAM_EW, 0, 0, s.longrow, 0, 0, s.vec ? 4 : 1, 0, s.stream, 0);
+            }
+    for (int b16 = 0; b16 < 2; ++b16)
+        for (unsigned off : {0u, 4u}) emit(DNMF_DENSE_FAM_SQNORM, 0, select_sqnorm(100, 64, b16 ? 2 : 4, off, 68).fast, 0, 0, 0, 0, 0, 0, b16);
+    return dnmf_dense_variants_kl_(rows, cap, nrows);                 // the KL products, the residual, the per-column error
+}

@@ -77,23 +77,43 @@ inline size_t reduce_scratch_bytes(int nsplit, int rows_out, long cols_out) {
 // room behind the partial slabs of W^T A for the partial Gram tiles of dnmf_wta_gram (<= 64 chunks x 16 x 16 floats)
 constexpr size_t GRAM_RIDE_BYTES = 2 * REDUCE_SLICE * 256 * sizeof(float);
 
+// Which of its three forms a reduction takes (launch_reduce launches from this; dnmf_dense_plan reports it).  off_*: the operand's
+// address modulo 16.  gx: workgroups along x of the main launch (without the Gram tail's); ny: slices of the first of two stages.
+inline unsigned off16(const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15); }
+enum { REDUCE_NONE = 0, REDUCE_SINGLE = 1, REDUCE_WIDE = 2, REDUCE_TWO_STAGE = 3 };
+struct ReduceSel { int kind; int ny; unsigned gx; };
+inline ReduceSel select_reduce(unsigned off_p, long stride, long ldp, int nsplit, unsigned off_out, long ldo, int rows, long cols,
+                               int rows_out, long cols_out) {
+    const long total = (long)rows_out * cdiv(cols_out, 4);
+    ReduceSel r;
+    r.ny = reduce_slices(nsplit);
+    if (r.ny == 1 && rows == rows_out && cols == cols_out && cols % 4 == 0 && cols >= 4096 && ldo % 4 == 0 &&
+        off_out == 0 && off_p == 0 && ldp % 4 == 0 && stride % 4 == 0) {
+        r.kind = REDUCE_WIDE;
+        r.gx = (unsigned)cdiv(total, 256);
+    } else {
+        r.kind = r.ny == 1 ? REDUCE_SINGLE : REDUCE_TWO_STAGE;
+        r.gx = (unsigned)cdiv(total, 64);
+    }
+    return r;
+}
+
 // `gram` (optional, single-stage reductions only): the partial Gram tiles of a GRAM kernel are summed by one extra workgroup of
 // the same launch (dnmf_tn.h: GramTail)
 int launch_reduce(const float* P, long stride, long ldp, int nsplit, float* out, long ldo, int rows, long cols,
                   int rows_out, long cols_out, float* scratch, hipStream_t st, const GramTail* gram = nullptr) {
-    const long total = (long)rows_out * cdiv(cols_out, 4);
-    const unsigned gx = (unsigned)cdiv(total, 64);
-    const int ny = reduce_slices(nsplit);
+    const ReduceSel sel = select_reduce(off16(P), stride, ldp, nsplit, off16(out), ldo, rows, cols, rows_out, cols_out);
+    const unsigned gx = sel.gx;
+    const int ny = sel.ny;
     const GramTail gt = gram ? *gram : GramTail{nullptr, nullptr, 0, 0, 0, 0};
     const unsigned extra = gram ? (unsigned)gram_tail_blocks(gram->k) : 0u;
     if (gram && ny != 1) return fail(DNMF_EINVAL, "reduce: a Gram tail needs a single-stage reduction (%d partials)", nsplit);
-    if (ny == 1 && rows == rows_out && cols == cols_out && cols % 4 == 0 && cols >= 4096 && ldo % 4 == 0 &&
-        aligned16(out) && aligned16(P) && ldp % 4 == 0 && stride % 4 == 0) {
-        DNMF_LAUNCH(reduce_partials_wide_kernel, dim3((unsigned)cdiv(total, 256) + extra), dim3(256), 0, st, P, stride, ldp,
+    if (sel.kind == REDUCE_WIDE) {
+        DNMF_LAUNCH(reduce_partials_wide_kernel, dim3(gx + extra), dim3(256), 0, st, P, stride, ldp,
                            nsplit, out, ldo, rows, cols, gt);
         return check_launch("reduce_partials_wide");
     }
-    if (ny == 1) {
+    if (sel.kind == REDUCE_SINGLE) {
         DNMF_LAUNCH(reduce_partials_kernel, dim3(gx + extra, 1), dim3(256), 0, st, P, stride, ldp, nsplit, nsplit, out, ldo,
                            0L, rows, cols, rows_out, cols_out, gt);
     } else {
@@ -104,6 +124,16 @@ int launch_reduce(const float* P, long stride, long ldp, int nsplit, float* out,
                            ldo, 0L, rows_out, cols_out, rows_out, cols_out, gt);
     }
     return check_launch("reduce_partials");
+}
+
+// What an entry point hands to its reduction: built once per entry point (the reduce_shape_* helpers beside the selectors) and used by
+// both its launcher and the plan query.
+struct ReduceShape { long stride, ldp; int nsplit; int rows; long cols; int rows_out; long cols_out; };
+inline ReduceSel select_reduce(const ReduceShape& r, unsigned off_p, unsigned off_out, long ldo) {
+    return select_reduce(off_p, r.stride, r.ldp, r.nsplit, off_out, ldo, r.rows, r.cols, r.rows_out, r.cols_out);
+}
+inline int launch_reduce(const float* P, const ReduceShape& r, float* out, long ldo, float* scratch, hipStream_t st, const GramTail* gram = nullptr) {
+    return launch_reduce(P, r.stride, r.ldp, r.nsplit, out, ldo, r.rows, r.cols, r.rows_out, r.cols_out, scratch, st, gram);
 }
 
 // ---- plans and predicates shared by csrc/dnmf.hip and csrc/dnmf_kl.hip

@@ -1300,6 +1300,428 @@ def f64_pitch(cols, aligned):
     return -(-cols // 4) * 4 + 4 if aligned else cols + 3
 
 
+# ---------------------------------------------------------------------------------------------------------- the fp32 dense MU/Frobenius path
+# The shapes of tests/test_gpu_exact_dense.py, each named after the kernel variant or loop-trip class it is there for, with the fields
+# dnmf_dense_plan must report for it (tests/test_dense_plan.py asserts them, and that the table reaches every instantiation the
+# selectors of csrc/dnmf.hip can return, without a GPU).  (id, op, m, n, k, aligned, bf16-stored A, plan fields).  `aligned`: the
+# operands are `Poisoned` views with 16-byte aligned rows (bf16: quantum 8); otherwise an odd start and pitch.
+def _nt(pf, kt, nk, mode=0, **kw):
+    return dict(family="nt", fast=1, pf=pf, kt=kt, nk=nk, mode=mode, **kw)
+
+
+P2_M = 128 * 257 + 4             # 257 interior row tiles and a ragged one: 258 workgroups, more than the 256 below which PF 13 is chosen
+P3_M = 2 * 128 + 44              # two interior tiles and a ragged one
+DENSE_NT = (
+    # nt_mainloop_p2 (PF 10): nk = 1 (prologue clamps, tail only), 2 (one trip, no tail), 3 (trip + tail), 4 (even), 5 (odd), every KT
+    [("p2-k%d-nk%d" % (k, nk), "aht", P2_M, 32 * nk, k, True, False, _nt(10, k // 32, nk, interior=257, eligible=257, grid_x=258))
+     for k in (32, 64, 128) for nk in (1, 2, 3, 4, 5)]
+    + [("p2-fused-k%d-nk%d" % (k, nk), "aht_update_w", P2_M, 32 * nk, k, True, False, _nt(10, k // 32, nk, 1, wfast=1, eligible=257))
+       for k, nk in ((32, 3), (64, 4), (128, 5), (64, 1), (128, 2))]
+    + [("p2-hblocks-k64-nk4", "aht_hblocks", P2_M, 128, 64, True, False, _nt(10, 2, 4, eligible=257))]
+    # nt_mainloop_p3t (PF 13): nk = 1, 2 (the prologue's prefetches clamp to the last tile) and every residue nk mod 6 behind a whole trip
+    + [("p3t-k%d-nk%d" % (k, nk), "aht", P3_M + 128 * (nk % 2), 32 * nk, k, True, False,
+        _nt(13, k // 32, nk, interior=2 + nk % 2, eligible=2 + nk % 2)) for k in (32, 64, 128) for nk in (1, 2, 6, 7, 8, 9, 10, 11)]
+    + [("p3t-fused-k%d-nk%d" % (k, nk), "aht_update_w", P3_M, 32 * nk, k, True, False, _nt(13, k // 32, nk, 1, wfast=1, eligible=2))
+       for k, nk in ((32, 7), (64, 11), (128, 8))]
+    + [("p3t-hblocks-k32-nk8", "aht_hblocks", P3_M, 256, 32, True, False, _nt(13, 1, 8, eligible=2))]
+    # the descriptor loops' other side: W of the fused form off the vector path; an unaligned A (the generic loop, PF 1); k < KP keeps
+    # the fast kernel off its interior loop
+    + [("fused-w-unaligned-k32", "aht_update_w", P3_M, 96, 32, "W", False, _nt(13, 1, 3, 1, wfast=0, eligible=2)),
+       ("fast-edge-k%KP-k40", "aht", P3_M, 96, 40, True, False, _nt(13, 2, 3, interior=0, eligible=0)),
+       ("fast-edge-n%32-k64", "aht", P3_M, 100, 64, True, False, _nt(13, 2, 4, interior=0, eligible=0)),
+       ("fast-edge-k%KP-fused-k100", "aht_update_w", P3_M, 96, 100, True, False, _nt(13, 4, 3, 1, wfast=1, interior=0, eligible=0))]
+    # bf16-stored A (PF 5): 64-wide tiles, nk = 1, 2 and odd
+    + [("bf16-k%d-nk%d" % (k, nk), "aht", P3_M, 64 * nk, k, True, True, _nt(5, k // 32, nk, interior=2, eligible=0))
+       for k in (32, 64, 128) for nk in (1, 2, 3)]
+    + [("bf16-fused-k%d-nk%d" % (k, nk), "aht_update_w", P3_M, 64 * nk, k, True, True, _nt(5, k // 32, nk, 1, wfast=1, interior=2))
+       for k, nk in ((32, 2), (64, 3), (128, 1))]
+    + [("bf16-edge-n%64-k32", "aht", P3_M, 96, 32, True, True, _nt(5, 1, 2, interior=0))]
+    # the generic kernels (FAST = false): unaligned operands, every KT, both modes, both storage types of A
+    + [("generic-%s-k%d%s" % (op, k, "-bf16" if b else ""), op, P3_M, 96, k, False, b,
+        dict(family="nt", fast=0, pf=1, kt=kt, mode=int(op != "aht"), wfast=0, interior=0, eligible=0))
+       for op in ("aht", "aht_update_w") for k, kt in ((20, 1), (64, 2), (128, 4)) for b in (False, True)]
+    # the 16-wide kernel: its pair loop with and without the odd tile
+    + [("nt16-k16-nk3", "aht", P3_M, 96, 16, True, False, dict(family="nt16", nk=3)),
+       ("nt16-fused-k9-nk2", "aht_update_w", P3_M, 64, 9, True, False, dict(family="nt16", nk=2, mode=1)),
+       ("nt16-bf16-k8-nk1", "aht", P3_M, 64, 8, True, True, dict(family="nt16", nk=1)),
+       ("nt16-bf16-fused-k12-nk2", "aht_update_w", P3_M, 128, 12, True, True, dict(family="nt16", nk=2, mode=1)),
+       ("nt16-not-taken-n%32-k16", "aht", P3_M, 100, 16, True, False, _nt(13, 1, 4, interior=0))]
+)
+# H H^T: the store_all form (PF 1) in column splits; single-stage and two-stage reductions of the split tiles, ragged last split
+DENSE_HHT = [
+    ("hht-k64-1-split", "gram_hht", 0, 100, 64, True, False, dict(family="nt", pf=1, fast=1, count=1, reduce="single")),
+    ("hht-k32-ragged-split", "gram_hht", 0, 300, 32, True, False, dict(family="nt", pf=1, fast=1, count=3, nk=4, aux=2, reduce="single")),
+    ("hht-k128-unaligned", "gram_hht", 0, 301, 128, False, False, dict(family="nt", pf=1, fast=0, count=3, reduce="single")),
+    ("hht-k64-34-splits", "gram_hht", 0, 66 * 128 + 36, 64, True, False,
+     dict(family="nt", pf=1, fast=1, count=34, per=256, reduce="single")),
+    ("hht-k20-two-stage-ragged-slice", "gram_hht", 0, 65 * 256 + 4, 20, True, False, dict(family="nt", pf=1, count=66, reduce="two_stage", slices=3)),
+    ("hht-k128-two-stage", "gram_hht", 0, 64 * 256 + 32, 128, True, False, dict(family="nt", pf=1, count=65, reduce="two_stage", slices=3)),
+]
+
+
+def _tn(kt, nt, b0, bl, fast=1, **kw):
+    return dict(family="tn", kt=kt, nt=nt, fast=fast, b0_full=b0[0], b0_tail=b0[1], bl_full=bl[0], bl_tail=bl[1], **kw)
+
+
+# tn_kernel's row-batch pipeline (two batches of 8 rows per trip): the last chunk with 0, 1, an odd and an even number of full batches and
+# tails of 1..7 rows; n and k short of the column tile (clamped lanes); the reductions
+DENSE_TN = (
+    [("tn-k%d-b%d-t%d" % (k, b, t), "wta", 8 * b + t, n, k, True, False, _tn(kt, nt, (b, t), (b, t), count=1, reduce="single"))
+     for k, kt, nt, n, b, t in ((32, 1, 4, 128, 0, 5), (30, 1, 4, 100, 1, 1), (64, 2, 4, 132, 3, 2), (62, 2, 4, 128, 4, 3), (128, 4, 2, 68, 5, 4),
+                                (100, 4, 2, 64, 6, 5), (32, 1, 4, 260, 7, 6), (64, 2, 4, 128, 8, 7), (128, 4, 2, 64, 2, 0))]
+    + [("tn-k32-2-chunks-ragged", "wta", 300, 132, 32, True, False, _tn(1, 4, (20, 0), (17, 4), count=2, reduce="single")),
+       ("tn-k64-gram-first", "wta_gram", 300, 128, 64, True, False, _tn(2, 4, (20, 0), (17, 4), count=2)),
+       ("tn-k32-bf16", "wta", 301, 128, 32, True, True, _tn(1, 4, (20, 0), (17, 5), count=2, ntemp=1)),
+       ("tn-k64-bf16", "wta_gram", 301, 128, 64, True, True, _tn(2, 4, (20, 0), (17, 5), count=2, ntemp=1)),
+       ("tn-k128-bf16", "wta", 301, 136, 128, True, True, _tn(4, 2, (20, 0), (17, 5), count=2, ntemp=1))]
+    + [("tn-generic-k%d%s" % (k, "-bf16" if b else ""), "wta", 301, 130, k, False, b, _tn(kt, nt, (0, 160), (0, 141), fast=0, count=2, ntemp=0))
+       for k, kt, nt in ((32, 1, 4), (64, 2, 4), (128, 4, 2)) for b in (False, True)]
+    + [
+       ("tn-k33-odd-rank-at-kt2", "wta", 300, 128, 33, True, False, dict(family="tn", kt=2, fast=0)),
+       ("tn-k32-wide-reduce", "wta", 300, 4096, 32, True, False, dict(family="tn", kt=1, count=2, reduce="wide")),
+       ("tn-k32-two-stage-ragged-slice", "wta", 78 * 256 + 40, 64, 32, True, False,
+        dict(family="tn", kt=1, count=79, per=256, reduce="two_stage", slices=3, bl_full=5, bl_tail=0))]
+    # the 16-wide kernel (batches of 16 rows), alone and with the riding Gram; the workspace too small for its slabs falls to tn_kernel
+    + [("tn16-k16-b0-t12", "wta", 12, 64, 16, True, False, dict(family="tn16", v=4, b0_full=0, b0_tail=12, reduce="single")),
+       ("tn16-k9-b1-t3", "wta", 19, 128, 9, True, False, dict(family="tn16", v=4, bl_full=1, bl_tail=3)),
+       ("tn16-k16-bf16-b2-t1", "wta", 33, 128, 16, True, True, dict(family="tn16", v=8, bl_full=2, bl_tail=1)),
+       ("tn16-k16-gram-ragged", "wta_gram", 300, 128, 16, True, False, dict(family="tn16_gram", count=2, b0_full=10, bl_full=8, bl_tail=12)),
+       ("tn16-k5-bf16-gram", "wta_gram", 301, 256, 5, True, True, dict(family="tn16_gram", v=8, bl_full=8, bl_tail=13)),
+       ("tn16-k16-two-stage-gram-first", "wta_gram", 65 * 256 + 16, 64, 16, True, False,
+        dict(family="tn16", count=66, reduce="two_stage", slices=3, bl_full=1)),
+       ("tn16-n%64-falls-to-tn", "wta", 300, 100, 16, True, False, dict(family="tn", kt=1))]
+)
+# W^T W: tn_kernel<KT, NT = KT (2 at KT = 4)> on 128-row chunks; the two-stage reduction at more than 64 chunks, ragged last slice
+DENSE_WTW = [
+    ("wtw-k32-b3-t1", "gram_wtw", 25, 0, 32, True, False, _tn(1, 1, (3, 1), (3, 1), count=1, reduce="single")),
+    ("wtw-k64-b1-t7", "gram_wtw", 15, 0, 64, True, False, _tn(2, 2, (1, 7), (1, 7), count=1, reduce="single")),
+    ("wtw-k64-ragged", "gram_wtw", 300, 0, 64, True, False, _tn(2, 2, (14, 0), (9, 4), count=3, per=112, reduce="single")),
+    ("wtw-k100-clamped", "gram_wtw", 301, 0, 100, True, False, _tn(4, 2, (14, 0), (9, 5), count=3, reduce="single")),
+    ("wtw-k64-generic", "gram_wtw", 301, 0, 64, False, False, _tn(2, 2, (0, 112), (0, 77), fast=0, count=3)),
+    ("wtw-k32-generic", "gram_wtw", 301, 0, 32, False, False, _tn(1, 1, (0, 112), (0, 77), fast=0, count=3)),
+    ("wtw-k128-generic", "gram_wtw", 301, 0, 128, False, False, _tn(4, 2, (0, 112), (0, 77), fast=0, count=3)),
+    ("wtw-k64-two-stage-ragged-slice", "gram_wtw", 8336, 0, 64, True, False,
+     _tn(2, 2, (16, 0), (2, 0), count=66, per=128, reduce="two_stage", slices=3)),
+    ("wtw-k128-two-stage-tail", "gram_wtw", 8325, 0, 128, True, False, _tn(4, 2, (16, 0), (0, 5), count=66, reduce="two_stage", slices=3)),
+]
+# the W update.  update_w16_kernel: the grid-stride loop's second, ragged trip behind the 1024-workgroup cap of KT >= 2; update_w_seq_kernel:
+# V = 4 only with EDGE (an aligned W with whole ranks and whole 32-row tiles goes to update_w16_kernel), V = 1 in both
+DENSE_UPD_W = [
+    ("w16-k32-one-tile-per-wave", "mu_update_w", 65536 + 16, 0, 32, True, False,
+     dict(family="update_w16", kt=1, block=256, occ=8, grid_x=1025, aux=1)),
+    ("w16-k64-second-trip", "mu_update_w", 65536 + 16, 0, 64, True, False,
+     dict(family="update_w16", kt=2, block=256, occ=8, grid_x=1024, count=4097, aux=2)),
+    ("w16-k128-second-trip", "mu_update_w", 131072 + 48, 0, 128, True, False,
+     dict(family="update_w16", kt=4, block=512, occ=4, grid_x=1024, count=8195, aux=2)),
+    ("w16-k64-short-grid", "mu_update_w", 48, 0, 64, True, False, dict(family="update_w16", kt=2, grid_x=1, count=3, aux=1)),
+] + [("wseq-k%d-v%d-edge%d" % (k, v, e), "mu_update_w", m, 0, k, v == 4, False,
+      dict(family="update_w_seq", kt=kt, v=v, edge=e, occ=4 if kt == 4 else 5))
+     for k, kt, m, v, e in ((32, 1, 100, 4, 1), (20, 1, 96, 4, 1), (64, 2, 72, 4, 1), (128, 4, 40, 4, 1), (32, 1, 96, 1, 0), (31, 1, 96, 1, 1),
+                            (64, 2, 64, 1, 0), (64, 2, 70, 1, 1), (128, 4, 32, 1, 0), (100, 4, 33, 1, 1))
+] + [("wseq-k128-second-trip", "mu_update_w", 131072 + 40, 0, 128, True, False,
+      dict(family="update_w_seq", kt=4, v=4, edge=1, grid_x=1024, aux=2))]
+# the H update.  Two columns per lane from 1024 tiles of 64 columns on; its nontemporal form from 64 MiB on; one column per lane in both
+# EDGE values; the second trip behind the 1024-workgroup cap of KT = 4
+DENSE_UPD_H = [
+    ("h2-k32-n65536", "mu_update_h", 0, 65536, 32, True, False, dict(family="update_h_seq", kt=1, nt=2, occ=3, edge=0, ntemp=0)),
+    ("h2-k64-n65536", "mu_update_h", 0, 65536, 64, True, False, dict(family="update_h_seq", kt=2, nt=2, occ=3, edge=0, ntemp=0)),
+    ("h2-k128-n65536", "mu_update_h", 0, 65536, 128, True, False, dict(family="update_h_seq", kt=4, nt=2, occ=2, edge=0, ntemp=0)),
+    ("h2-nontemporal-k128-n131072", "mu_update_h", 0, 131072, 128, True, False, dict(family="update_h_seq", kt=4, nt=2, occ=2, ntemp=1)),
+    ("h2-nontemporal-k64-n262144", "mu_update_h", 0, 262144, 64, True, False, dict(family="update_h_seq", kt=2, nt=2, occ=3, ntemp=1)),
+    ("h2-nontemporal-k32-n524288", "mu_update_h", 0, 524288, 32, True, False, dict(family="update_h_seq", kt=1, nt=2, occ=3, ntemp=1)),
+    ("h1-k32-odd-pitch-n65536", "mu_update_h", 0, 65536, 32, False, False, dict(family="update_h_seq", kt=1, nt=1, edge=0)),
+    ("h1-k128-second-trip", "mu_update_h", 0, 131072 + 36, 128, True, False,
+     dict(family="update_h_seq", kt=4, nt=1, edge=1, grid_x=1024, aux=2)),
+] + [("h1-k%d-n%d-edge%d" % (k, n, e), "mu_update_h", 0, n, k, al, False, dict(family="update_h_seq", kt=kt, nt=1, occ=4, edge=e))
+     for k, kt, n, al, e in ((32, 1, 96, True, 0), (20, 1, 96, True, 1), (64, 2, 64, False, 0), (64, 2, 70, True, 1), (128, 4, 32, True, 0),
+                             (65, 4, 33, False, 1))]
+# the element-wise passes: (id, pass, rows, cols, aligned, plan fields) -- the long-row and the patch form, vector and scalar; the
+# streaming form (>= 256 MiB) once
+DENSE_EW = [
+    ("ew-long-vec", "clamp_min", 10, 2000, True, dict(family="ew", mode=1, v=4, ntemp=0, grid_x=1, grid_y=10)),
+    ("ew-long-vec-2-blocks", "kl_update_h", 3, 4100, True, dict(family="ew", mode=1, v=4, grid_x=2, grid_y=3)),
+    ("ew-long-scalar", "scale_rows_mul", 10, 1030, False, dict(family="ew", mode=1, v=1, grid_x=2, grid_y=10)),
+    ("ew-patch-vec", "scale_cols_div", 1000, 40, True, dict(family="ew", mode=0, v=4, aux=4, grid_x=16)),
+    ("ew-patch-scalar", "kl_update_w", 1000, 37, False, dict(family="ew", mode=0, v=1, aux=6, grid_x=63)),
+    ("ew-patch-vec-x-unaligned", "scale_cols_div", 100, 40, "x", dict(family="ew", mode=0, v=1)),
+    ("ew-long-stream", "clamp_min", 16384, 4096, True, dict(family="ew", mode=1, v=4, ntemp=1)),
+    ("ew-patch-stream", "clamp_min", 1 << 20, 64, True, dict(family="ew", mode=0, v=4, ntemp=1)),
+]
+# the KL products at 16 < k (csrc/dnmf_kl.hip).  U H^T: the pipelined kernel on the whole 128-row tiles of every KT with kl_uht_kernel on the
+# ragged last one (both write into one output), alone on whole tiles, through column splits and their reduction, on H as column blocks
+# (65 blocks: a two-stage reduction), on padded images of a ragged rank; kl_uht_kernel alone below one tile and on unaligned operands.
+# W^T U: every KT fast and generic, a ragged last chunk, more than 64 chunks
+KL_M = 2 * 128 + 44
+DENSE_KL = (
+    [("klpipe-k%d-ragged-tile" % k, "kl_uht", KL_M, 96, k, True, False,
+      dict(family="kl_uht_pipe", kt=k // 32, fast=1, mode=0, edge=1, grid_x=2, aux=1, count=1, nk=3, reduce="none")) for k in (32, 64, 128)]
+    + [("klpipe-k%d-whole-tiles" % k, "kl_uht", 256, 64, k, True, False, dict(family="kl_uht_pipe", kt=k // 32, mode=0, edge=0, grid_x=2, aux=0))
+       for k in (32, 64, 128)]
+    + [("klpipe-k%d-padded-m%d" % (k, m), "kl_uht", m, 1024, k, True, False,
+        dict(family="kl_uht_pipe", kt=kt, fast=1, mode=1, edge=int(m % 128 > 0), count=4, reduce="single"))
+       for k, kt in ((20, 1), (40, 2), (100, 4)) for m in (256, KL_M)]
+    + [("kluht-k%d-padded-unsplit" % k, "kl_uht", KL_M, 96, k, True, False, dict(family="kl_uht", kt=kt, fast=1, mode=1, grid_x=3))
+       for k, kt in ((20, 1), (40, 2), (100, 4))]
+    + [("kluht-k%d-below-one-tile" % k, "kl_uht", 100, 96, k, True, False, dict(family="kl_uht", kt=k // 32, fast=1, mode=0, grid_x=1))
+       for k in (32, 64, 128)]
+    + [
+       ("klpipe-k64-4-splits", "kl_uht", KL_M, 1024, 64, True, False, dict(family="kl_uht_pipe", kt=2, edge=1, count=4, per=256, reduce="single")),
+       ("klpipe-k32-factors-unaligned-padded", "kl_uht", KL_M, 96, 32, "W,H", False, dict(family="kl_uht_pipe", kt=1, fast=1, mode=1)),
+       ("klpipe-hblocks-k32", "kl_uht_hblocks", KL_M, 128, 32, True, False, dict(family="kl_uht_pipe", kt=1, edge=1, count=4, per=32, reduce="single")),
+       ("klpipe-hblocks-k64-two-stage", "kl_uht_hblocks", KL_M, 65 * 32, 64, True, False,
+        dict(family="kl_uht_pipe", kt=2, count=65, per=32, reduce="two_stage", slices=3)),
+       ("kluht-k64-n%32", "kl_uht", KL_M, 100, 64, True, False, dict(family="kl_uht", kt=2, fast=1, grid_x=3))]
+    + [("kluht-k%d-generic" % k, "kl_uht", KL_M, 97, k, False, False, dict(family="kl_uht", kt=kt, fast=0, mode=0, grid_x=3))
+       for k, kt in ((20, 1), (64, 2), (128, 4))]
+    + [("klwtu-k%d-ragged-chunk" % k, "kl_wtu", KL_M, 132, k, True, False,
+        dict(family="kl_wtu", kt=kt, nt=nt, fast=1, mode=0, count=2, per=160, b0_full=5, bl_full=4, bl_tail=12, reduce="single"))
+       for k, kt, nt in ((32, 1, 4), (64, 2, 2), (128, 4, 2))]
+    + [("klwtu-k%d-generic" % k, "kl_wtu", KL_M, 131, k, False, False, dict(family="kl_wtu", kt=kt, fast=0, mode=0, count=2))
+       for k, kt in ((20, 1), (64, 2), (100, 4))]
+    + [("klwtu-k%d-padded" % k, "kl_wtu", KL_M, 132, k, True, False, dict(family="kl_wtu", kt=kt, fast=1, mode=1))
+       for k, kt in ((20, 1), (40, 2), (100, 4))]
+    + [
+       ("klwtu-k32-two-stage-ragged-slice", "kl_wtu", 65 * 256 + 40, 64, 32, True, False,
+        dict(family="kl_wtu", kt=1, fast=1, count=66, per=256, reduce="two_stage", slices=3, bl_full=1, bl_tail=8)),
+       ("klwtu-k32-wide-reduce", "kl_wtu", KL_M, 4096, 32, True, False, dict(family="kl_wtu", kt=1, fast=1, reduce="wide"))]
+)
+# the 16-wide KL kernels of k <= 16 (csrc/dnmf_kl16.hip).  kl_uht16_kernel: friendly factors (k = 16, aligned) and factors padded to 16, one
+# split stored directly and several splits through slabs, whole and ragged row tiles, an odd and an even number of k-tiles, H as column
+# blocks (65 of them: a two-stage reduction); kl_wtu16_kernel: chunks of 16-row blocks taken two per trip (an even and an odd count, a
+# ragged tail), more than 64 chunks, the wide reduction; and the shapes that keep the 32-wide kernels at k <= 16
+def _k16(fam, mode, **kw):
+    return dict(family=fam, kt=1, fast=1, mode=mode, **kw)
+
+
+DENSE_KL16 = [
+    ("kl16uht-k16-direct", "kl_uht", KL_M, 96, 16, True, False, _k16("kl16_uht", 0, edge=1, count=1, nk=3, grid_x=3, aux=44, reduce="none")),
+    ("kl16uht-k16-direct-whole-tiles", "kl_uht", 256, 64, 16, True, False, _k16("kl16_uht", 0, edge=1, nk=2, grid_x=2, aux=0)),
+    ("kl16uht-k16-4-splits", "kl_uht", KL_M, 1024, 16, True, False, _k16("kl16_uht", 0, edge=0, count=4, per=256, nk=8, reduce="single")),
+    ("kl16uht-k16-out-unaligned", "kl_uht", KL_M, 96, 16, "UHT", False, _k16("kl16_uht", 0, edge=0, count=1, reduce="single")),
+    ("kl16uht-k9-padded", "kl_uht", KL_M, 96, 9, True, False, _k16("kl16_uht", 1, edge=0, count=1, nk=3, reduce="single")),
+    ("kl16uht-k1-padded-4-splits", "kl_uht", KL_M, 1024, 1, True, False, _k16("kl16_uht", 1, edge=0, count=4, reduce="single")),
+    ("kl16uht-k16-factors-unaligned-padded", "kl_uht", KL_M, 32, 16, "W,H", False, _k16("kl16_uht", 1, edge=1, nk=1)),
+    ("kl16uht-hblocks-k16", "kl_uht_hblocks", KL_M, 128, 16, True, False, _k16("kl16_uht", 0, edge=0, count=4, per=32, nk=1, reduce="single")),
+    ("kl16uht-hblocks-k16-two-stage", "kl_uht_hblocks", KL_M, 65 * 32, 16, True, False,
+     _k16("kl16_uht", 0, count=65, per=32, reduce="two_stage", slices=3)),
+    ("kl16uht-not-taken-n%32", "kl_uht", KL_M, 100, 16, True, False, dict(family="kl_uht", kt=1, fast=1, mode=1)),
+    ("kl16uht-not-taken-a-unaligned-k9", "kl_uht", KL_M, 97, 9, False, False, dict(family="kl_uht", kt=1, fast=0, mode=0)),
+    ("kl16wtu-k16-odd-blocks-tail", "kl_wtu", 316, 128, 16, True, False,
+     _k16("kl16_wtu", 0, count=5, per=64, b0_full=4, bl_full=3, bl_tail=12, reduce="single")),
+    ("kl16wtu-k16-whole-chunks", "kl_wtu", 256, 64, 16, True, False, _k16("kl16_wtu", 0, count=4, per=64, bl_full=4, bl_tail=0)),
+    ("kl16wtu-k9-padded", "kl_wtu", KL_M, 128, 9, True, False, _k16("kl16_wtu", 1, count=5, bl_full=2, bl_tail=12)),
+    ("kl16wtu-k16-two-stage-ragged-slice", "kl_wtu", 65 * 64 + 20, 64, 16, True, False,
+     _k16("kl16_wtu", 0, count=66, per=64, reduce="two_stage", slices=3, bl_full=1, bl_tail=4)),
+    ("kl16wtu-k5-wide-reduce", "kl_wtu", KL_M, 4096, 5, True, False, _k16("kl16_wtu", 1, reduce="wide")),
+    ("kl16wtu-not-taken-n%64", "kl_wtu", KL_M, 96, 16, True, False, dict(family="kl_wtu", kt=1, fast=1, mode=1)),
+]
+# the residual, the per-column error and the squared norm: resid_lds_kernel for every KT and both storage types at m = 4096 plus a ragged
+# remainder (and on padded images of a ragged rank), resid_kernel below that size and on unaligned operands; colerr_kernel for every KT,
+# FAST and storage type and with several row blocks per wave; sqnorm_kernel in both forms with a second grid-stride trip
+RL_M = 4096 + 36
+DENSE_RESID = (
+    [("residlds-k%d%s" % (k, "-bf16" if b else ""), "resid_sqnorm", RL_M, 128, k, True, b, dict(family="resid_lds", kt=k // 32, fast=1, mode=0))
+     for k in (32, 64, 128) for b in (False, True)]
+    + [("residlds-k%d-padded%s" % (k, "-bf16" if b else ""), "resid_sqnorm", RL_M, 136, k, True, b, dict(family="resid_lds", kt=kt, fast=1, mode=1))
+       for k, kt in ((20, 1), (40, 2), (100, 4)) for b in (False, True)]
+    + [
+       ("resid-k32-n-below-128", "resid_sqnorm", RL_M, 124, 32, True, False, dict(family="resid", kt=1, fast=1)),
+       ("resid-k64-m-below-4096", "resid_sqnorm", 4095, 128, 64, True, True, dict(family="resid", kt=2, fast=1))]
+    + [("resid-k%d-generic%s" % (k, "-bf16" if b else ""), "resid_sqnorm", KL_M, 130, k, False, b, dict(family="resid", kt=kt, fast=0, mode=0))
+       for k, kt in ((20, 1), (64, 2), (128, 4)) for b in (False, True)]
+    + [("resid-k%d-fast%s" % (k, "-bf16" if b else ""), "resid_sqnorm", KL_M, 132, k, True, b, dict(family="resid", kt=k // 32, fast=1, mode=0))
+       for k in (32, 64, 128) for b in (False, True)]
+    + [("colerr-k%d-%s%s" % (k, "fast" if al else "generic", "-bf16" if b else ""), "column_err", KL_M, 132 if al else 130, k, al, b,
+        dict(family="colerr", kt=kt, fast=int(al), per=32)) for k, kt in ((32, 1), (64, 2), (128, 4)) for al in (True, False) for b in (False, True)]
+    + [("colerr-k32-2-row-blocks-per-wave", "column_err", 8192 + 40, 4096, 32, True, False, dict(family="colerr", kt=1, fast=1, per=64, count=129))]
+    + [("sqnorm-fast-2-trips", "sqnorm", 600, 4000, 1, True, False, dict(family="sqnorm", fast=1, grid_x=2048, aux=2)),
+       ("sqnorm-fast-bf16", "sqnorm", 300, 136, 1, True, True, dict(family="sqnorm", fast=1, aux=1)),
+       ("sqnorm-generic-2-trips", "sqnorm", 600, 1001, 1, False, False, dict(family="sqnorm", fast=0, grid_x=2048, aux=2)),
+       ("sqnorm-generic-bf16", "sqnorm", 300, 130, 1, False, True, dict(family="sqnorm", fast=0))]
+)
+DENSE_REACH = DENSE_NT + DENSE_HHT + DENSE_TN + DENSE_WTW + DENSE_UPD_W + DENSE_UPD_H + DENSE_KL + DENSE_KL16 + DENSE_RESID
+# What the table leaves out: only branches whose condition needs an operand above 1 GiB -- the 2 GiB descriptor-window fallbacks -- each
+# with the test that keeps it, and what the selectors cannot return at all.  (The streaming element-wise forms, 256 MiB each, are run for
+# one pass, clamp_min, in both the long-row and the patch form: the template's OP does not enter the choice.)
+DENSE_EXEMPT = {
+    "nt: interior, not eligible (a tile beyond the 2 GiB window of the PF 10 / 13 loops)": "test_gpu_kernels::test_a_beyond_2_and_4_gib, test_column_slice_leaves_the_window",
+    "tn: a chunk beyond the 2 GiB window (the pointer form of the pipeline)": "test_gpu_kernels::test_a_beyond_2_and_4_gib",
+    "kl_uht: a tile beyond the 2 GiB windows keeps kl_uht_kernel; kl_wtu: the chunk cap of plan_kl_wtu": "test_gpu_kernels::test_a_beyond_2_and_4_gib",
+    "update_w16: a 16-row tile beyond the 2 GiB window -- not reachable: mu_update_w refuses pitches from 2^23 on": "tests/test_dense_plan.py::test_unreachable",
+    "update_w_seq<KT, 4, OCC, false>: needs the window test above to fail -- not reachable": "tests/test_dense_plan.py::test_unreachable",
+}
+
+
+# (row chunks or column splits, rows or columns per chunk) of the cases whose CPU proofs walk the partition -- tests/test_exact_cpu.py stays
+# free of the library; tests/test_dense_plan.py holds these to dnmf_dense_plan
+DENSE_CHUNKS = {
+    "hht-k64-1-split": (1, 128),
+    "hht-k32-ragged-split": (3, 128),
+    "hht-k128-unaligned": (3, 128),
+    "hht-k64-34-splits": (34, 256),
+    "hht-k20-two-stage-ragged-slice": (66, 256),
+    "hht-k128-two-stage": (65, 256),
+    "tn-k32-b0-t5": (1, 16),
+    "tn-k30-b1-t1": (1, 16),
+    "tn-k64-b3-t2": (1, 32),
+    "tn-k62-b4-t3": (1, 48),
+    "tn-k128-b5-t4": (1, 48),
+    "tn-k100-b6-t5": (1, 64),
+    "tn-k32-b7-t6": (1, 64),
+    "tn-k64-b8-t7": (1, 80),
+    "tn-k128-b2-t0": (1, 16),
+    "tn-k32-2-chunks-ragged": (2, 160),
+    "tn-k64-gram-first": (2, 160),
+    "tn-k32-bf16": (2, 160),
+    "tn-k64-bf16": (2, 160),
+    "tn-k128-bf16": (2, 160),
+    "tn-generic-k32": (2, 160),
+    "tn-generic-k32-bf16": (2, 160),
+    "tn-generic-k64": (2, 160),
+    "tn-generic-k64-bf16": (2, 160),
+    "tn-generic-k128": (2, 160),
+    "tn-generic-k128-bf16": (2, 160),
+    "tn-k33-odd-rank-at-kt2": (2, 160),
+    "tn-k32-wide-reduce": (2, 160),
+    "tn-k32-two-stage-ragged-slice": (79, 256),
+    "tn16-k16-b0-t12": (1, 16),
+    "tn16-k9-b1-t3": (1, 32),
+    "tn16-k16-bf16-b2-t1": (1, 48),
+    "tn16-k16-gram-ragged": (2, 160),
+    "tn16-k5-bf16-gram": (2, 160),
+    "tn16-k16-two-stage-gram-first": (66, 256),
+    "tn16-n%64-falls-to-tn": (2, 160),
+    "wtw-k32-b3-t1": (1, 32),
+    "wtw-k64-b1-t7": (1, 16),
+    "wtw-k64-ragged": (3, 112),
+    "wtw-k100-clamped": (3, 112),
+    "wtw-k64-generic": (3, 112),
+    "wtw-k32-generic": (3, 112),
+    "wtw-k128-generic": (3, 112),
+    "wtw-k64-two-stage-ragged-slice": (66, 128),
+    "wtw-k128-two-stage-tail": (66, 128),
+    "klwtu-k32-ragged-chunk": (2, 160),
+    "klwtu-k64-ragged-chunk": (2, 160),
+    "klwtu-k128-ragged-chunk": (2, 160),
+    "klwtu-k20-generic": (2, 160),
+    "klwtu-k64-generic": (2, 160),
+    "klwtu-k100-generic": (2, 160),
+    "klwtu-k20-padded": (2, 160),
+    "klwtu-k40-padded": (2, 160),
+    "klwtu-k100-padded": (2, 160),
+    "klwtu-k32-two-stage-ragged-slice": (66, 256),
+    "klwtu-k32-wide-reduce": (2, 160),
+    "kl16wtu-k16-odd-blocks-tail": (5, 64),
+    "kl16wtu-k16-whole-chunks": (4, 64),
+    "kl16wtu-k9-padded": (5, 64),
+    "kl16wtu-k16-two-stage-ragged-slice": (66, 64),
+    "kl16wtu-k5-wide-reduce": (5, 64),
+    "kl16wtu-not-taken-n%64": (2, 160),
+}
+
+
+def dense_pitch(cols, aligned, bf16=False):
+    """the pitch and the start (in elements) of a `Poisoned` view as tests/test_gpu_exact_dense.py makes them"""
+    if not aligned:
+        return cols + 3, 3
+    q = 8 if bf16 else 4
+    return -(-cols // q) * q + q, 8
+
+
+DENSE_OPERANDS = {"aht": ("A", "H"), "aht_hblocks": ("A", "Hs"), "aht_update_w": ("A", "H", "W"), "wta": ("A", "W", "AtW"),
+                  "wta_gram": ("A", "W", "AtW"), "gram_hht": ("H",), "gram_wtw": ("W",), "mu_update_w": ("W", "AH"), "mu_update_h": ("H", "AtW"),
+                  "kl_uht": ("A", "W", "H", "UHT"), "kl_uht_hblocks": ("A", "W", "Hs", "UHT"), "kl_wtu": ("A", "W", "H", "WTU"),
+                  "resid_sqnorm": ("A", "W", "H"), "column_err": ("A", "W", "H"), "sqnorm": ("A",)}
+DENSE_HBLK = 32                                                    # the block width of the aht_hblocks cases
+
+
+def dense_is_aligned(aligned, name):
+    """`aligned` of a case: True, False, or the names of the operands that are not (comma separated)"""
+    return aligned is True or (isinstance(aligned, str) and name not in aligned.split(","))
+
+
+def dense_plan_args(op, m, n, k, aligned, bf16, quantum8=True):
+    """the pitches and the addresses modulo 16 dnmf_dense_plan takes for a case, in the order of its operands (include/dnmf.h);
+    quantum8=False: bf16 views as tests/test_gpu_exact.py makes them (pitches in steps of 4 elements)"""
+    cols = {"A": n, "H": n, "W": k, "AtW": n, "AH": k, "UHT": k, "WTU": n}
+    ld, off = [], []
+    for name in DENSE_OPERANDS[op]:
+        if name == "Hs":
+            ld.append(DENSE_HBLK); off.append(0)
+            continue
+        b = bool(bf16) and name == "A"
+        pitch, lead = dense_pitch(cols[name], dense_is_aligned(aligned, name), b and quantum8)
+        ld.append(pitch); off.append(lead * (2 if b else 4) % 16)
+    return ld, off
+
+
+def dense_nt_operands(m, n, k, seed=0):
+    """A in 0..7, H and W in 1..3 (some zero rows of W, zero columns of H), G = H H^T: the operands of `products` without its H-phase
+    denominators (W^T W) H, which outgrow 2^22 at the tall shapes of the descriptor loops.  A H^T is an integer below 2^24 and W G is 0
+    or an integer in [2, 2^22) that absorbs eps.  Every 32-column tile of every 128-row block of A has a nonzero product with H."""
+    rs = np.random.RandomState(seed + 1009 * m + 17 * n + k)
+    A = rs.randint(0, 8, size=(m, n)).astype(np.float32)
+    A[rs.rand(m, n) < 0.2] = 0
+    H = rs.randint(1, 4, size=(k, n)).astype(np.float32)
+    W = rs.randint(1, 4, size=(m, k)).astype(np.float32)
+    W[rs.rand(m) < 0.05] = 0
+    if n > 8:
+        H[:, rs.rand(n) < 0.05] = 0
+    A64, W64, H64 = (x.astype(np.float64) for x in (A, W, H))
+    G = H64 @ H64.T
+    _bound(A64 @ H64.T, 1.0, np.float32, "A H^T")
+    _bound(G, 1.0, np.float32, "H H^T")
+    d = W64 @ G
+    _bound(d, 0.25, np.float32, "W HH^T")
+    assert np.all((d == 0) | (d >= 2))
+    return A, W, H, G
+
+
+def dense_tn_operands(m, n, k, seed=0):
+    """A in 0..7 and W in 1..3 with some zero rows: W^T A and W^T W are integers below 2^24 in any order"""
+    rs = np.random.RandomState(seed + 1013 * m + 19 * n + k)
+    A = rs.randint(0, 8, size=(m, max(n, 1))).astype(np.float32)
+    A[rs.rand(m, max(n, 1)) < 0.2] = 0
+    W = rs.randint(1, 4, size=(m, k)).astype(np.float32)
+    if m > 16:
+        W[rs.rand(m) < 0.05] = 0
+    _bound(W.astype(np.float64).T @ A.astype(np.float64), 1.0, np.float32, "W^T A")
+    _bound(W.astype(np.float64).T @ W.astype(np.float64), 1.0, np.float32, "W^T W")
+    return A, W
+
+
+def dense_resid_operands(m, n, k, seed=0, whole=True):
+    """W and H in {0, 1}, A = W H + R with R in 0..2: W H <= k <= 128 and A <= 130 are integers (exact in bfloat16 too), every residual
+    square is at most 4 and every fp32 partial sum of squares -- of a row chunk, a column, the whole block -- stays an integer below
+    2^24.  Every 32-row block of every 128-column block holds a nonzero residual.  Returns A, W, H and R (float64)."""
+    rs = np.random.RandomState(seed + 1019 * m + 23 * n + k)
+    W = (rs.rand(m, k) < 0.5).astype(np.float32)
+    H = (rs.rand(k, n) < 0.5).astype(np.float32)
+    R = rs.randint(0, 3, size=(m, n)).astype(np.float64)
+    A = W.astype(np.float64) @ H.astype(np.float64) + R
+    _bound((A ** 2).sum(0), 1.0, np.float32, "column sums of A^2")
+    if whole:                                                       # (the per-column error sums columns only)
+        _bound((R ** 2).sum(), 1.0, np.float32, "the residual sum")
+    assert A.max() <= 256
+    return A.astype(np.float32), W, H, R
+
+
+def dense_update_operands(rows, k, seed=0):
+    """X (rows x k) in 1..3 with some zero rows, S in 0..63, G symmetric in 2..3: the denominators X G are 0 (a zero row: the element
+    stays 0) or integers in [2, 2^22) that absorb eps, the numerators are exact; transposed for the H update.  S differs from X G somewhere
+    in every 16 rows, so an update that skips a tile leaves a wrong value there."""
+    rs = np.random.RandomState(seed + 7 * rows + k)
+    X = rs.randint(1, 4, size=(rows, k)).astype(np.float32)
+    X[rs.rand(rows) < 0.05] = 0
+    S = rs.randint(0, 64, size=(rows, k)).astype(np.float32)
+    G = rs.randint(2, 4, size=(k, k))
+    G = np.maximum(G, G.T).astype(np.float64)
+    d = X.astype(np.float64) @ G
+    _bound(d, 0.25, np.float32, "X G")
+    assert np.all((d == 0) | (d >= 2))
+    return X, S, G
+
+
 # ---------------------------------------------------------------------------------------------------------- per-element comparison
 def assert_ulp(got, q, c, what="", tile=(16, 32), q_hi=None):
     """|got - q| <= c * spacing(q in got's type) per element, q the float64 reference; q == 0 must be exactly 0 and c == 0 means

@@ -915,3 +915,168 @@ def test_pieces_products_fit_the_streamed_shapes(case):
             X = sp.csr_matrix((Vp[a - 1].astype(np.float64), (rows, cols)), shape=A.shape)
             T = X @ Fp[b - 1].T if side == "aht" else (X.T @ Fp[b - 1]).T
             assert ex.tiles_differ(T, 0.0).all(), "x%d y%d is zero in a whole output tile" % (a, b)
+
+
+# ---------------------------------------------------------------------------------------------------------- the fp32 dense reach table
+# The operands of tests/test_gpu_exact_dense.py at the shapes of ex.DENSE_REACH: exact in fp32 in forward, reversed and tile-rotated
+# order, and able to see what the tier is for -- every unit of work a loop iteration owns (a 32-column k-tile of a 128-row block, an
+# 8-row batch of a row chunk, a partial slab, a slice of 32 slabs, a 16-row tile of an update trip) contributes a nonzero term to its
+# output tile, so deleting or doubling it changes the float64 answer there.
+def _rotated_sums(X, Yt, tile, rows, shift):
+    """X[rows] @ Yt.T in float32, k-tile by k-tile from tile `shift` on (wrapping), then the same from the back"""
+    X, Yt = X[rows].astype(np.float32), Yt.astype(np.float32)
+    nk = -(-X.shape[1] // tile)
+    out = []
+    for order in ([(shift + t) % nk for t in range(nk)], [(shift - t) % nk for t in range(nk)]):
+        acc = np.zeros((X.shape[0], Yt.shape[0]), dtype=np.float32)
+        for t in order:
+            for c in range(t * tile, min((t + 1) * tile, X.shape[1])):
+                acc += np.outer(X[:, c], Yt[:, c])
+        out.append(acc)
+    return out
+
+
+def _nt_proof(A, H, tile, cid):
+    m, n = A.shape
+    A64, H64 = A.astype(np.float64), H.astype(np.float64)
+    ref = A64 @ H64.T
+    nk = -(-n // tile)
+    blocks = sorted({0, min(1, (m - 1) // 128), (m - 1) // 128, max(0, m // 128 - 1)})
+    for b in blocks:
+        rows = slice(128 * b, min(128 * b + 32, m))                                  # the first wave's rows of the block
+        for got in _rotated_sums(A, H, tile, rows, b * 37 % nk) + _rotated_sums(A, H, tile, rows, 0):
+            assert np.array_equal(got.astype(np.float64), ref[rows]), "%s: A H^T is not exact in float32 (block %d)" % (cid, b)
+    nblk = -(-m // 128)
+    pad = np.zeros((nblk * 128 - m, H.shape[0]))
+    for t in range(nk):
+        P = A64[:, t * tile:(t + 1) * tile] @ H64[:, t * tile:(t + 1) * tile].T       # what k-tile t adds, every block at once
+        per_block = np.abs(np.vstack([P, pad])).reshape(nblk, -1).max(1)
+        assert per_block.min() > 0, "%s: k-tile %d adds nothing to row block %d" % (cid, t, int(per_block.argmin()))
+
+
+@pytest.mark.parametrize("case", [c for c in ex.DENSE_REACH if c[1] in ("aht", "aht_hblocks", "aht_update_w")], ids=lambda c: c[0])
+def test_dense_nt_operands_are_exact_and_see_every_tile(case):
+    cid, op, m, n, k, aligned, bf16, _ = case
+    tile = 64 if bf16 else 32
+    A, W, H, G = ex.dense_nt_operands(m, n, k)
+    _nt_proof(A, H, tile, cid)
+    for x in (A, W, H):                                                              # bf16 storage is exact
+        assert ex.is_bf16(x).all()
+    if op == "aht_update_w":
+        d = W.astype(np.float32) @ G.astype(np.float32)
+        assert np.array_equal(d.astype(np.float64), W.astype(np.float64) @ G)
+        eps = np.float32(np.finfo(np.float32).eps)
+        assert np.array_equal(d[d > 0] + eps, d[d > 0]), "W G + eps is not absorbed"
+        if n >= k:
+            A2, W2, H2, Wn, _ = ex.fro_step(m, n, k)
+            _nt_proof(A2, H2, tile, cid + " (fro_step)")
+            assert ex.is_bf16(A2).all() and ex.tiles_differ(Wn, W2.astype(np.float64), 32).all()
+
+
+def _col_blocks(P, width=32):
+    """per block of `width` columns: does P hold a nonzero there?"""
+    pad = np.zeros((P.shape[0], -P.shape[1] % width))
+    return np.abs(np.hstack([P, pad])).reshape(P.shape[0], -1, width).max(axis=(0, 2)) > 0
+
+
+def _chunk_batches(m, rpc, batch):
+    """(first row, end row) of every `batch`-row step of every row chunk"""
+    return [(r, min(r + batch, e)) for b in range(0, m, rpc) for e in (min(b + rpc, m),) for r in range(b, e, batch)]
+
+
+@pytest.mark.parametrize("case", [c for c in ex.DENSE_REACH if c[1] in ("wta", "wta_gram", "gram_wtw", "gram_hht")], ids=lambda c: c[0])
+def test_dense_tn_operands_are_exact_and_see_every_batch(case):
+    cid, op, m, n, k, aligned, bf16, want = case
+    count, per = ex.DENSE_CHUNKS[cid]
+    if op == "gram_hht":                                                             # H H^T in column splits of `per` columns
+        H = np.ascontiguousarray(ex.dense_tn_operands(n, 1, k)[1].T)
+        ref = _all_orders(H, H.T, "H H^T") if n * k * k <= 4e6 else H.astype(np.float64) @ H.astype(np.float64).T
+        slabs = [H[:, c:c + per].astype(np.float64) for c in range(0, n, per)]
+        parts = [s @ s.T for s in slabs]
+        for s in slabs:
+            for t in range(0, s.shape[1], 32):
+                assert (s[:, t:t + 32] @ s[:, t:t + 32].T).any(), "%s: a k-tile of a split adds nothing" % cid
+    else:
+        A, W = ex.dense_tn_operands(m, n, k)
+        Y = W if op == "gram_wtw" else A
+        assert ex.is_bf16(A).all() and ex.is_bf16(W).all()
+        W64, Y64 = W.astype(np.float64), Y.astype(np.float64)
+        ref = W64.T @ Y64
+        if m * k * Y.shape[1] <= 4e6:
+            _all_orders(W.T, Y, "W^T Y")
+        batch = 16 if want["family"].startswith("tn16") else 8
+        for r0, r1 in _chunk_batches(m, per, batch):                                 # in every 32-column block of the output: every wave's tile
+            assert _col_blocks(W64[r0:r1].T @ Y64[r0:r1]).all(), "%s: the batch of rows %d..%d adds nothing to a column block" % (cid, r0, r1)
+            if op == "wta_gram":
+                assert (W64[r0:r1].T @ W64[r0:r1]).any()
+        parts = [W64[b:b + per].T @ Y64[b:b + per] for b in range(0, m, per)]
+    assert len(parts) == count and np.array_equal(sum(parts), ref)
+    acc32 = np.zeros(ref.shape, dtype=np.float32)
+    for q in reversed(parts):                                                        # the slabs summed in fp32, last first
+        acc32 += q.astype(np.float32)
+    assert np.array_equal(acc32.astype(np.float64), ref)
+    assert all(_col_blocks(q).all() for q in parts), "%s: a partial slab with an all-zero column block" % cid
+    if want.get("reduce") == "two_stage":
+        assert all(_col_blocks(sum(parts[s:s + 32])).all() for s in range(0, len(parts), 32))
+
+
+@pytest.mark.parametrize("case", [c for c in ex.DENSE_REACH if c[1] in ("mu_update_w", "mu_update_h")], ids=lambda c: c[0])
+def test_dense_update_operands_are_exact_and_see_every_tile(case):
+    cid, op, m, n, k, aligned, bf16, _ = case
+    rows = m if op == "mu_update_w" else n
+    X, S, G = ex.dense_update_operands(rows, k)
+    X64 = X.astype(np.float64)
+    d = X64 @ G
+    d32 = X.astype(np.float32) @ G.astype(np.float32)
+    assert np.array_equal(d32.astype(np.float64), d)
+    if rows * k * k <= 4e6:
+        _all_orders(X, G, "X G")
+    eps = np.float32(np.finfo(np.float32).eps)
+    assert np.array_equal(d32[d32 > 0] + eps, d32[d32 > 0]), "X G + eps is not absorbed"
+    q = np.where(d > 0, X64 * S / np.where(d > 0, d, 1.0), 0.0)
+    far = np.abs(q - X64) > 4 * np.spacing(np.maximum(np.abs(q), np.abs(X64)).astype(np.float32))      # a skipped tile is not within c = 3
+    pad = np.zeros((-rows % 16, k), dtype=bool)
+    assert np.vstack([far, pad]).reshape(-1, 16 * k).any(1).all(), "%s: a 16-row tile the update leaves as it was" % cid
+
+
+@pytest.mark.parametrize("case", ex.DENSE_KL + ex.DENSE_KL16, ids=lambda c: c[0])
+def test_dense_kl_operands_are_exact_and_see_every_tile(case):
+    """ex.kl at the shapes of the KL cases: both products exact in float32, every 32-column k-tile of every 128-row tile adds a nonzero
+    term to U H^T, every 32-row block adds one to every 32-column block of W^T U, and so does every chunk slab and slice"""
+    cid, op, m, n, k, aligned, bf16, want = case
+    A, W, H, U = ex.kl(m, n, k)
+    W64, H64 = W.astype(np.float64), H.astype(np.float64)
+    U32 = (A / (W @ H + np.float32(np.finfo(np.float32).eps))).astype(np.float32)
+    assert np.array_equal(U32.astype(np.float64), U), "the quotient is not exact in float32"
+    if op == "kl_wtu":
+        ref = W64.T @ U
+        assert np.array_equal((W.T @ U32).astype(np.float64), ref)
+        count, per = ex.DENSE_CHUNKS[cid]
+        rb = 16 if want["family"] == "kl16_wtu" else 32                              # the rows a loop iteration owns
+        for r0 in range(0, m, rb):
+            assert _col_blocks(W64[r0:r0 + rb].T @ U[r0:r0 + rb]).all(), "%s: row block %d adds nothing to a column block" % (cid, r0 // rb)
+        parts = [W64[b:b + per].T @ U[b:b + per] for b in range(0, m, per)]
+        assert len(parts) == count and np.array_equal(sum(parts), ref)
+        if want.get("reduce") == "two_stage":
+            assert all(_col_blocks(sum(parts[s:s + 32])).all() for s in range(0, len(parts), 32))
+    else:
+        ref = U @ H64.T
+        assert np.array_equal((U32 @ H.T).astype(np.float64), ref)
+        nblk = -(-m // 128)
+        pad = np.zeros((nblk * 128 - m, k))
+        for t in range(0, n, 32):
+            P = U[:, t:t + 32] @ H64[:, t:t + 32].T
+            assert np.abs(np.vstack([P, pad])).reshape(nblk, -1).max(1).min() > 0, "%s: k-tile %d adds nothing to a row tile" % (cid, t // 32)
+
+
+@pytest.mark.parametrize("case", [c for c in ex.DENSE_RESID if c[1] != "sqnorm"], ids=lambda c: c[0])
+def test_dense_resid_operands_are_exact_and_see_every_block(case):
+    cid, op, m, n, k, aligned, bf16, want = case
+    A, W, H, R = ex.dense_resid_operands(m, n, k, whole=op == "resid_sqnorm")
+    assert ex.is_bf16(A).all()
+    WH = W @ H                                                                       # float32
+    assert np.array_equal(WH.astype(np.float64), W.astype(np.float64) @ H.astype(np.float64))
+    assert np.array_equal(((A - WH) ** 2).astype(np.float64), R ** 2)
+    padr, padc = -m % 32, -n % 128
+    blocks = np.pad(R, ((0, padr), (0, padc))).reshape((m + padr) // 32, 32, (n + padc) // 128, 128).max(axis=(1, 3))
+    assert (blocks > 0).all(), "%s: a 32-row block of a 128-column block without a residual" % cid
