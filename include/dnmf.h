@@ -895,6 +895,57 @@ size_t dnmf_masked_ws_bytes_fit(long m, long n, int k);
 int dnmf_masked_mu_fit(const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int kl,
                        int w_update, int itr, double* sq_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the Itakura-Saito objective (beta = 0) on dense strictly positive float32 data (csrc/dnmf_is.h) ----
+ * No counterpart in the reference, whose objectives are fro and kl; the rule is the majorisation-minimisation MU of Fevotte & Idier
+ * (2011), scikit-learn's for beta_loss='itakura-saito'.  With S = W H, R = 1 / (S + eps) element-wise and F = H^T (W side) or W (H side):
+ *     num = (A . R . R) F,   den = R F,   X <- X . sqrt(num / (den + eps))
+ * which never increases D_IS(A | S + eps) = sum (q - log q - 1), q = A . R.  The pairs have the structure of the masked ones above
+ * (a tile of S in MFMA accumulators, one element-wise step, two second products that share their F fragments -- the same kernels in
+ * a third mode, with dnmf_masked_plan's launch geometry but for the two choices dnmf_is_plan names) and parallel the reference's KL products (dist_nmf.py:806-810: the quotient;
+ * :827-849: the rules); the element-wise step is one v_rcp_f32 and two multiplies, and there is no mask: a NaN of A is not skipped,
+ * a zero of A sends the divergence to infinity (callers check A > 0).  1 <= k <= DNMF_TUNED_MAX_K; any shape and any leading dimensions
+ * (padding is never read as data and adds exactly nothing: csrc/dnmf_is.h).  Partial sums are added in a fixed order, no float
+ * atomics: bit-reproducible.  Bad arguments return DNMF_EINVAL with a dnmf_last_error text; the *_bytes functions return 0.
+ * `ws`: dnmf_is_ws_bytes(m, n, k) bytes, 16-byte aligned, serves every entry point below but the whole fit. */
+size_t dnmf_is_ws_bytes(long m, long n, int k);
+/* The launch plans, host arithmetic only (nothing is launched): out[0..5] = {tiles_per_split, nsplit, zdim, rowblks_per_chunk,
+ * nchunks, nrowblk} with the meaning of dnmf_masked_plan and its values, except that the H side never asks for fewer than four row
+ * chunks (a workgroup is four waves, a wave per chunk; the masked plan asks for 1024 / column blocks, which is below four beyond 256
+ * column blocks of 4096 / KP columns) and that zdim is 1 at KP = 128 as well (a workgroup of the W side holds all four tiles of output
+ * columns, so S is formed once; the column splits are sized for 512 / rowtiles workgroups accordingly); out[6] / out[7] = workgroups of the W side's / H side's ending (256 outputs each per
+ * grid-stride trip: dnmf_masked_reduce_grid(m, k) / (k, n)). */
+int dnmf_is_plan(long m, long n, int k, long out[8]);
+/* the pair stored: num = (A . R . R) F, den = R F, [m x k] (W side) or [k x n] (H side) with the same leading dimension ldo -- the two
+ * halves of one contiguous buffer where the sums cross ranks (one allreduce, then dnmf_is_ratio_update); parallels
+ * dist_nmf.py:806,810 (W side) and :806,808 (H side) */
+int dnmf_is_aht_pair(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,
+                     float* num, float* den, long ldo, void* ws, size_t ws_bytes, void* stream);
+int dnmf_is_wta_pair(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,
+                     float* num, float* den, long ldo, void* ws, size_t ws_bytes, void* stream);
+/* the pair applied where nothing crosses ranks: W <- W * sqrt(num / (den + eps)) in place after the pass has read it (parallels
+ * dist_nmf.py:828-830), H alike with max(., eps) if clamp != 0 (:847-849, pyDNMF.py:170-172) */
+int dnmf_is_update_w(const float* A, long m, long n, long lda, float* W, long ldw, const float* H, long ldh, int k, float eps, void* ws,
+                     size_t ws_bytes, void* stream);
+int dnmf_is_update_h(const float* A, long m, long n, long lda, const float* W, long ldw, float* H, long ldh, int k, float eps, int clamp,
+                     void* ws, size_t ws_bytes, void* stream);
+/* X[r][c] <- X[r][c] * sqrt(num[r][c] / (den[r][c] + eps)), max(., eps) if clamp != 0: the rule on a stored pair (ldo: the leading
+ * dimension of num and den) -- the same expression as the endings above */
+int dnmf_is_ratio_update(float* X, long rows, long cols, long ldx, const float* num, const float* den, long ldo, float eps, int clamp,
+                         void* stream);
+/* *out (double, device) = D_IS(A | W H + eps) = sum (q - log q - 1), q = a / (s + eps), over the block.  S tiles stay in MFMA
+ * accumulators (as in dnmf_masked_resid_sqnorm); fp32 per 32 x 128 tile and lane, float64 from there on, every tile's sum in its own
+ * slot of `ws` and the slots added in a fixed order: two calls are bit-identical.  Parallels the residual of pyDNMF.py:205-218. */
+int dnmf_is_divergence(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,
+                       double* out, void* ws, size_t ws_bytes, void* stream);
+/* A whole Itakura-Saito MU fit on one rank as ONE call (pyDNMF.py:138-182): `itr` steps of dnmf_is_update_w (iff w_update) and
+ * dnmf_is_update_h with the clamp of H and then of W at the steps i % 10 == 0 (:155-157, :170-172), normalize_features (:185-194) and
+ * sq_out = {||A - W H||^2, ||A||^2} (:205-218: the Frobenius pair, as after dnmf_mu_kl_fit; the caller takes the square roots).  Host
+ * sequencing of the launches above on `stream`: no host synchronisation inside.  One problem per call.
+ * `ws`: dnmf_is_ws_bytes_fit(m, n, k) bytes, 16-byte aligned (0: bad shape or rank). */
+size_t dnmf_is_ws_bytes_fit(long m, long n, int k);
+int dnmf_is_mu_fit(const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int w_update,
+                   int itr, double* sq_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- measurement aid (no counterpart in the reference) ----
  * Which shader clock does the GPU hold right now?  Launches ONE wave on `stream` that writes `n` pairs {s_memtime (shader
  * cycles), wall_clock64 (the constant 100 MHz reference)} into samples[2 n], sleeping `naps` x ~4 us between two pairs, and

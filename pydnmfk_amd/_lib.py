@@ -238,6 +238,21 @@ SIGNATURES["dnmf_masked_column_err"] = [c_void_p, c_long, c_long, c_long, c_void
 SIGNATURES["dnmf_masked_ws_bytes_fit"] = [c_long, c_long, c_int]
 SIGNATURES["dnmf_masked_mu_fit"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_int, c_int, c_int,
                                     c_void_p, c_void_p, c_size_t, c_void_p]
+# the Itakura-Saito rule (csrc/dnmf_is.hip): A m n lda W ldw H ldh k eps [clamp] [num den ldo] ws ws_bytes stream
+SIGNATURES["dnmf_is_ws_bytes"] = [c_long, c_long, c_int]
+SIGNATURES["dnmf_is_ws_bytes_fit"] = [c_long, c_long, c_int]
+SIGNATURES["dnmf_is_plan"] = [c_long, c_long, c_int, c_void_p]      # out: long[8]
+SIGNATURES["dnmf_is_aht_pair"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_void_p, c_void_p, c_long,
+                                  c_void_p, c_size_t, c_void_p]
+SIGNATURES["dnmf_is_wta_pair"] = SIGNATURES["dnmf_is_aht_pair"]
+SIGNATURES["dnmf_is_update_w"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_void_p, c_size_t, c_void_p]
+SIGNATURES["dnmf_is_update_h"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_int, c_void_p, c_size_t,
+                                  c_void_p]
+SIGNATURES["dnmf_is_ratio_update"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_void_p, c_long, c_float, c_int, c_void_p]
+SIGNATURES["dnmf_is_divergence"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_void_p, c_void_p, c_size_t,
+                                    c_void_p]
+SIGNATURES["dnmf_is_mu_fit"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_int, c_int, c_void_p, c_void_p,
+                                c_size_t, c_void_p]
 # the W phase from a transposed image of A (csrc/dnmf_timg.hip): build A m n lda At ldat stream; bind the same without the stream
 SIGNATURES["dnmf_wimage_bytes"] = [c_long, c_long]
 SIGNATURES["dnmf_wimage_build"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]
@@ -245,7 +260,7 @@ SIGNATURES["dnmf_wimage_bind"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_
 SIGNATURES["dnmf_wimage_unbind"] = []
 SIGNATURES["dnmf_set_wimage"] = [c_int]
 SIGNATURES["dnmf_wimage_plan"] = [c_long, c_long, c_int, c_long, c_int, c_int, c_void_p]      # out: int[6]
-_RESTYPES = {"dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
+_RESTYPES = {"dnmf_is_ws_bytes": c_size_t, "dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
              "dnmf_ws_bytes_1d": c_size_t, "dnmf_ws_bytes_hblocks": c_size_t, "dnmf_ws_bytes_2d": c_size_t,
              "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t, "dnmf_bcd_ws_bytes_fit": c_size_t}
 

@@ -1,0 +1,115 @@
+// dnmf_is.h -- the Itakura-Saito objective (beta = 0): the MU rule in its majorisation-minimisation form on the matrix cores.
+// Part of libdnmf_hip.so (kernels live in anonymous namespaces of the headers; the translation units csrc/*.hip include what they launch).
+//
+// With S = W H, R = 1 / (S + eps) element-wise (eps the float32 machine epsilon) and F = H^T on the W side, F = W on the H side:
+//     num = (A . R . R) F,   den = R F,   X <- X . sqrt(num / (den + eps))            (Fevotte & Idier 2011; the exponent 1/2 keeps
+//     D_IS(A | S + eps) = sum (q - log q - 1), q = A . R, from increasing; scikit-learn's rule for beta_loss='itakura-saito')
+// This is the structure of the masked pairs (csrc/dnmf_masked.h: a tile of S in MFMA accumulators, one element-wise step against A, TWO
+// second products that share their F fragments) with another step -- one v_rcp_f32 and two multiplies per element, no compare: there
+// is no mask.  The pair kernels ARE masked_uht_kernel / masked_wtu_kernel in their third mode (PAIR_IS), launched with the masked
+// launch plans but for two choices at wide shapes and KP = 128 (plan_is_uht / plan_is_wtu in csrc/dnmf_is.hip); this file adds the
+// endings (the square-root form of the ratio) and the divergence.
+//
+// Padding adds exactly nothing, without inf or 0 * inf.  An A load outside the block returns 0, so u_n = a r r = 0 * r * r there.  A
+// padded column c >= n is a zero column of the staged H tile and a padded row r >= m a zero row of W (the predicated loads), so S = 0,
+// r = 1 / eps = 2^23 and r^2 = 2^46 ~ 7e13 there: both finite in fp32, hence u_n = 0 * 2^46 = 0 exactly, and u_d = 2^23 meets an exact
+// zero of F in the second product where that product contracts over the padded index (W side: over the columns c, and H[:, c] = 0;
+// H side: over the rows r, and W[r, :] = 0).  Where the padded index is an OUTPUT index (a row >= m of the W side, a column >= n of
+// the H side) the sums are finite and go nowhere: the W side does not store such a row, the H side stores such a column into the
+// slab's own padding (ldp), which the ending never reads.  Inside the block S >= 0 (non-negative factors), so S + eps >= eps and
+// r <= 2^23 likewise; a padded contraction index j >= k is a zero row of H and a zero column of W.  eps added to the finished
+// accumulator (here) or taken as its initial value (the dense KL kernels) differ by rounding only: the sum is >= eps > 0 either way.
+//
+// Data must be strictly positive (PyNMF checks once per fit): a zero of A is legal for the pair (u_n = 0) but sends the divergence to
+// infinity, a NaN would reach an MFMA operand.
+#pragma once
+#include "dnmf_masked.h"
+
+namespace {
+
+__device__ __forceinline__ float is_ratio(float x, float a, float b, float eps, int clamp) {
+    const float y = x * sqrtf(a / (b + eps));
+    return clamp ? fmaxf(y, eps) : y;
+}
+
+// ---- the endings of the pair kernels: the partial slabs added in part order (masked_reduce_kernel's loop), then either the pair
+// stored (num, den with leading dimension ldo: the two halves of one contiguous buffer where the sums cross ranks) or the rule
+// applied in place, X <- X * sqrt(num / (den + eps)), max(., eps) with clamp
+__global__ __launch_bounds__(256) void is_reduce_kernel(const float* __restrict__ P, long part_stride, long half_stride, long ldp, int nparts,
+                                                        long rows, long cols, float* __restrict__ num, float* __restrict__ den, long ldo,
+                                                        float* __restrict__ X, long ldx, float eps, int clamp) {
+    const long total = rows * cols;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long r = idx / cols, c = idx % cols;
+        const float* q = P + r * ldp + c;
+        float a = q[0], b = q[half_stride];
+        for (int s = 1; s < nparts; ++s) {
+            a += q[s * part_stride];
+            b += q[s * part_stride + half_stride];
+        }
+        if (X) {
+            X[r * ldx + c] = is_ratio(X[r * ldx + c], a, b, eps, clamp);
+        } else {
+            num[r * ldo + c] = a;
+            den[r * ldo + c] = b;
+        }
+    }
+}
+
+// the same rule on a stored pair (after its allreduce on a 1D grid)
+__global__ __launch_bounds__(256) void is_ratio_kernel(float* __restrict__ X, long rows, long cols, long ldx, const float* __restrict__ num,
+                                                       const float* __restrict__ den, long ldo, float eps, int clamp) {
+    const long total = rows * cols;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long r = idx / cols, c = idx % cols;
+        X[r * ldx + c] = is_ratio(X[r * ldx + c], num[r * ldo + c], den[r * ldo + c], eps, clamp);
+    }
+}
+
+// ---- D_IS(A | W H + eps) = sum (q - log q - 1), q = a / (s + eps): masked_resid_kernel's tiles (a wave per 32 x 128 tile of S in
+// accumulators) with another term.  fp32 per tile and lane (64 terms), float64 from there on; a wave leaves ONE double in its own slot
+// of P (lanes added by a fixed shuffle tree) and is_div_sum_kernel adds the slots in a fixed order: no atomics, bit-reproducible.
+// Outside the block a = 0 and s = 0 give q = 0 and log q = -inf: the term is SELECTED away, never multiplied.
+template <int KT, bool FAST>
+__global__ __launch_bounds__(256) void is_div_kernel(NnArgs p, double* __restrict__ P) {
+    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long gw = (long)blockIdx.x * 4 + wid;
+    if (gw >= p.nrowblk * p.ncolblk) return;
+    const long row0 = (gw / p.ncolblk) * 32, col0 = (gw % p.ncolblk) * 128;
+    f32x16 acc[4];
+    nn_tile<KT, 4, FAST, false>(acc, p.W, p.ldw, p.m, p.k, p.H, p.ldh, p.n, row0, col0, li, h);
+    float part = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const long row = row0 + crow(r, h);
+        float a[4];
+        load_vec<4, FAST>(a, p.A + row * p.lda, col0 + 4 * li, p.n, row < p.m);
+#pragma unroll
+        for (int ne = 0; ne < 4; ++ne) {
+            const float q = kl_quot(a[ne], acc[ne][r] + p.eps);
+            const float t = (q - 1.f) - logf(q);
+            part += (row < p.m && col0 + 4 * li + ne < p.n) ? t : 0.f;
+        }
+    }
+    double total = (double)part;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) total += __shfl_xor(total, off, 64);
+    if (lane == 0) P[gw] = total;
+}
+
+// one workgroup: thread t adds the slots t, t + 256, ... in that order, then a fixed tree over the 256 sums
+__global__ __launch_bounds__(256) void is_div_sum_kernel(const double* __restrict__ P, long nparts, double* __restrict__ out) {
+    __shared__ double sh[256];
+    double s = 0.0;
+    for (long i = threadIdx.x; i < nparts; i += 256) s += P[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = sh[0];
+}
+
+}  // namespace

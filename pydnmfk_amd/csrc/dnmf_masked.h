@@ -26,24 +26,32 @@
 
 namespace {
 
-// the element-wise step: (u_n, u_d) of one element from its datum `a` and its model value s = <W[r], H[:, c]>
-template <bool KL>
+// the element-wise step: (u_n, u_d) of one element from its datum `a` and its model value s = <W[r], H[:, c]>.  MODE: the two masked
+// rules above, or the Itakura-Saito pair of csrc/dnmf_is.h, which has no mask (its padding argument is written there)
+enum { PAIR_FRO = 0, PAIR_KL = 1, PAIR_IS = 2 };
+template <int MODE>
 __device__ __forceinline__ void masked_pair(float a, float s, float eps, float& un, float& ud) {
-    const bool obs = a == a;
-    if constexpr (KL) {
-        un = obs ? kl_quot(a, s + eps) : 0.f;
-        ud = obs ? 1.f : 0.f;
+    if constexpr (MODE == PAIR_IS) {
+        ud = __builtin_amdgcn_rcpf(s + eps);       // r = 1 / (S + eps): v_rcp_f32, the form of kl_quot
+        un = a * ud * ud;                          // a r^2
     } else {
-        un = obs ? a : 0.f;
-        ud = obs ? s : 0.f;
+        const bool obs = a == a;
+        if constexpr (MODE == PAIR_KL) {
+            un = obs ? kl_quot(a, s + eps) : 0.f;
+            ud = obs ? 1.f : 0.f;
+        } else {
+            un = obs ? a : 0.f;
+            ud = obs ? s : 0.f;
+        }
     }
 }
 
 // ---- W side: P[split][half][m][KP], half 0 = num, 1 = den, over the columns of this split (row tiling of kl_uht_kernel: a workgroup
 // owns 128 rows, a lane the W row of its A row; S is formed transposed so that the contraction index of the second products is in
 // registers).  Two output accumulator sets do not fit next to the W row at KP = 128, so a workgroup owns JT of the KT 32-wide tiles of
-// output columns (blockIdx.z picks them; JT = KT up to KP = 64, JT = 2 at KP = 128 where S is formed twice).
-template <int KT, int JT, bool FAST, bool KL>
+// output columns (blockIdx.z picks them; JT = KT up to KP = 64, JT = 2 at KP = 128 where S is formed twice).  (Both sets DO fit at
+// KP = 128 once the accumulators may live in AGPRs -- 254 + 156 registers, no scratch --: csrc/dnmf_is.hip launches JT = 4 there.)
+template <int KT, int JT, bool FAST, int MODE>
 __global__ __launch_bounds__(256, KT == 4 ? 1 : 2) void masked_uht_kernel(NnArgs p, float* __restrict__ P, long split_stride,
                                                                           long half_stride, long cols_per_split) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -93,7 +101,7 @@ __global__ __launch_bounds__(256, KT == 4 ? 1 : 2) void masked_uht_kernel(NnArgs
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float x, y;
-                masked_pair<KL>(a_cur[g][e], st[4 * g + e], p.eps, x, y);
+                masked_pair<MODE>(a_cur[g][e], st[4 * g + e], p.eps, x, y);
                 un[4 * g + e] = x;
                 ud[4 * g + e] = y;
             }
@@ -135,7 +143,7 @@ __global__ __launch_bounds__(256, KT == 4 ? 1 : 2) void masked_uht_kernel(NnArgs
 // ---- H side: P[chunk][half][KP][ldp] over the rows of this chunk (the scheme of kl_wtu_kernel: a workgroup = 4 waves that share one
 // block of CW = 32 NT columns, whose KP x CW block of H is staged once; a wave walks a chunk of 32-row blocks, forms S, turns it into
 // (u_n, u_d) in place and feeds both as B operands of W^T u with the same W fragments).  ldp = ncolblk * CW: every store is in the slab.
-template <int KT, int NT, bool FAST, bool KL>
+template <int KT, int NT, bool FAST, int MODE>
 __global__ __launch_bounds__(256, 1) void masked_wtu_kernel(NnArgs p, long half_stride, long rowblks_per_chunk) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int KP = 32 * KT, CW = 32 * NT;
@@ -195,7 +203,7 @@ __global__ __launch_bounds__(256, 1) void masked_wtu_kernel(NnArgs p, long half_
 #pragma unroll
             for (int ne = 0; ne < NT; ++ne) {
                 float x, y;
-                masked_pair<KL>(areg[r][ne], acc[ne][r], p.eps, x, y);
+                masked_pair<MODE>(areg[r][ne], acc[ne][r], p.eps, x, y);
                 areg[r][ne] = x;
                 acc[ne][r] = y;
             }
@@ -359,5 +367,54 @@ __global__ __launch_bounds__(256) void masked_sqnorm_kernel(const float* __restr
     __syncthreads();                       // (block_atomic_sum's shared slots are read by thread 0 after its barrier)
     block_atomic_sum(cnt, out + 1);
 }
+
+// ================================================================================================ host side
+// The launch plans and predicates of the pair kernels above, shared by the translation units that launch them (csrc/dnmf_masked.hip,
+// csrc/dnmf_is.hip).
+// W side: 128-row tiles x column splits (x zdim128 = KT / JT parts of the output columns at KP = 128: 2 with JT = 2); splits are whole
+// 32-column tiles
+struct MaskedUhtPlan { long rowtiles; int zdim; long cols_per_split; int nsplit; size_t bytes; };
+MaskedUhtPlan plan_masked_uht(long m, long n, int kt, int zdim128 = 2) {
+    MaskedUhtPlan u{};
+    u.rowtiles = cdiv(m, 128);
+    u.zdim = kt == 4 ? zdim128 : 1;
+    const long tiles = cdiv(n, BK);
+    long ns = std::max<long>(1, 512 / (u.rowtiles * u.zdim));       // about two workgroups per CU
+    ns = std::min<long>(std::min<long>(ns, tiles), 32);
+    u.cols_per_split = cdiv(tiles, ns) * BK;
+    u.nsplit = (int)cdiv(n, u.cols_per_split);
+    u.bytes = (size_t)u.nsplit * 2 * m * (32 * kt) * sizeof(float);
+    return u;
+}
+
+// H side: column blocks of CW = 32 NT columns x row chunks (a wave per chunk).  min_chunks: the fewest chunks to ask for (a workgroup
+// is four chunks: with fewer, waves of every workgroup idle -- csrc/dnmf_is.hip asks for four)
+struct MaskedWtuPlan { int nt; int ncolblk; long ldp; long nrowblk; long rowblks_per_chunk; long nchunks; size_t bytes; };
+MaskedWtuPlan plan_masked_wtu(long m, long n, int kt, long min_chunks = 1) {
+    MaskedWtuPlan w{};
+    w.nt = kt == 1 ? 4 : (kt == 2 ? 2 : 1);
+    w.ncolblk = (int)cdiv(n, 32 * w.nt);
+    w.ldp = (long)w.ncolblk * 32 * w.nt;
+    w.nrowblk = cdiv(m, 32);
+    const long want = std::min<long>(std::max<long>(min_chunks, 1024 / w.ncolblk), 64);   // about a wave per SIMD
+    w.rowblks_per_chunk = std::max<long>(1, cdiv(w.nrowblk, want));
+    w.nchunks = cdiv(w.nrowblk, w.rowblks_per_chunk);
+    w.bytes = (size_t)w.nchunks * 2 * (32 * kt) * w.ldp * sizeof(float);
+    return w;
+}
+
+NnArgs masked_args(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps) {
+    NnArgs a{};
+    a.A = A; a.lda = lda; a.m = m; a.n = n; a.W = W; a.ldw = ldw; a.H = H; a.ldh = ldh; a.k = k; a.eps = eps; a.kreal = k;
+    a.nrowblk = cdiv(m, 32); a.ncolblk = (int)cdiv(n, 128);
+    return a;
+}
+
+bool masked_fast(const float* A, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k) {
+    return aligned16(A) && aligned16(W) && aligned16(H) && lda % 4 == 0 && n % 4 == 0 && ldw % 4 == 0 && k % 4 == 0 && ldh % 4 == 0;
+}
+
+// workgroups of masked_reduce_kernel (256 output elements each per grid-stride trip) for rows x cols outputs
+long masked_reduce_grid(long rows, long cols) { return std::min<long>(cdiv(rows * cols, 256), 8192); }
 
 }  // namespace

@@ -6,36 +6,6 @@
 
 namespace {
 
-// W side: 128-row tiles x column splits (x 2 halves of the output columns at KP = 128); splits are whole 32-column tiles
-struct MaskedUhtPlan { long rowtiles; int zdim; long cols_per_split; int nsplit; size_t bytes; };
-MaskedUhtPlan plan_masked_uht(long m, long n, int kt) {
-    MaskedUhtPlan u{};
-    u.rowtiles = cdiv(m, 128);
-    u.zdim = kt == 4 ? 2 : 1;
-    const long tiles = cdiv(n, BK);
-    long ns = std::max<long>(1, 512 / (u.rowtiles * u.zdim));       // about two workgroups per CU
-    ns = std::min<long>(std::min<long>(ns, tiles), 32);
-    u.cols_per_split = cdiv(tiles, ns) * BK;
-    u.nsplit = (int)cdiv(n, u.cols_per_split);
-    u.bytes = (size_t)u.nsplit * 2 * m * (32 * kt) * sizeof(float);
-    return u;
-}
-
-// H side: column blocks of CW = 32 NT columns x row chunks (a wave per chunk)
-struct MaskedWtuPlan { int nt; int ncolblk; long ldp; long nrowblk; long rowblks_per_chunk; long nchunks; size_t bytes; };
-MaskedWtuPlan plan_masked_wtu(long m, long n, int kt) {
-    MaskedWtuPlan w{};
-    w.nt = kt == 1 ? 4 : (kt == 2 ? 2 : 1);
-    w.ncolblk = (int)cdiv(n, 32 * w.nt);
-    w.ldp = (long)w.ncolblk * 32 * w.nt;
-    w.nrowblk = cdiv(m, 32);
-    const long want = std::min<long>(std::max<long>(1, 1024 / w.ncolblk), 64);   // about a wave per SIMD
-    w.rowblks_per_chunk = std::max<long>(1, cdiv(w.nrowblk, want));
-    w.nchunks = cdiv(w.nrowblk, w.rowblks_per_chunk);
-    w.bytes = (size_t)w.nchunks * 2 * (32 * kt) * w.ldp * sizeof(float);
-    return w;
-}
-
 // per-column error: 128-column blocks x row chunks (a wave per chunk and column block).  About two waves per SIMD, and at most 256
 // chunks: the ending adds a column's chunk pairs one after another
 struct MaskedColerrPlan { long ncolblk; long ldc; long nrowblk; long rowblks_per_chunk; long nchunks; size_t bytes; };
@@ -66,20 +36,6 @@ MaskedFitWs masked_fit_layout(long m, long n, int k) {
     f.total = f.sq_off + 256;
     return f;
 }
-
-NnArgs masked_args(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps) {
-    NnArgs a{};
-    a.A = A; a.lda = lda; a.m = m; a.n = n; a.W = W; a.ldw = ldw; a.H = H; a.ldh = ldh; a.k = k; a.eps = eps; a.kreal = k;
-    a.nrowblk = cdiv(m, 32); a.ncolblk = (int)cdiv(n, 128);
-    return a;
-}
-
-bool masked_fast(const float* A, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k) {
-    return aligned16(A) && aligned16(W) && aligned16(H) && lda % 4 == 0 && n % 4 == 0 && ldw % 4 == 0 && k % 4 == 0 && ldh % 4 == 0;
-}
-
-// workgroups of masked_reduce_kernel (256 output elements each per grid-stride trip) for rows x cols outputs
-long masked_reduce_grid(long rows, long cols) { return std::min<long>(cdiv(rows * cols, 256), 8192); }
 
 int masked_reduce(const float* P, long part_stride, long half_stride, long ldp, int nparts, long rows, long cols, float* num, float* den,
                   long ldo, float* X, long ldx, float eps, int clamp, hipStream_t st, const char* who) {

@@ -96,8 +96,47 @@ class _Base:
                 self.KL_MU_update(self.W_update, clamp)
             else:
                 raise Exception('Not a valid method: Choose (mu)')             # dist_nmf.py:89,657
+        elif norm == 'IS':                                                     # (no counterpart in the reference: csrc/dnmf_is.h)
+            if method == 'MU':
+                self.IS_MU_update(self.W_update, clamp)
+            else:
+                raise NotImplementedError("norm='is' is provided for method 'mu' only, not for '%s': HALS and BCD are Frobenius "
+                                          "methods" % self.method)
         else:
             raise Exception('Not a valid norm: Choose (fro/kl)')               # dist_nmf.py:91,659
+
+    # ---- Itakura-Saito, MU in its majorisation-minimisation form (1D grids).  With S = W H, R = 1 / (S + eps) and F = H^T / W:
+    #     num = (A . R . R) F,  den = R F,  X <- X * sqrt(num / (den + eps))
+    # Numerator AND denominator depend on the data, so what crosses ranks is the pair [num | den]: the shape of _masked_MU_update
+    def IS_MU_update(self, W_update=True, clamp=False):
+        ops, A, eps, k = self.ops, self.A_ij, self.eps, self.k
+        if self.p_r != 1 and self.p_c != 1:
+            raise NotImplementedError("norm='is' on a 2D grid (p_r = %d, p_c = %d) is not provided: use a 1D grid" % (self.p_r, self.p_c))
+        if _is_sparse(A) or _is_masked(A):
+            raise NotImplementedError("norm='is' is provided for dense data without missing entries, not for %s"
+                                      % ("sparse data" if _is_sparse(A) else "missing='%s'" % A.missing))
+        if not hasattr(ops, "is_update_w") or A.dtype not in getattr(ops, "is_dtypes", ()):
+            raise NotImplementedError("norm='is' runs on float32 data with the product's fp32 operator set; not provided for %s data with "
+                                      "the '%s' operator set" % (str(A.dtype).replace("torch.", ""), getattr(ops, "name", "?")))
+        W, H = self.W_i, self.H_j
+        m_l, n_l = A.shape
+        if W_update:
+            if self.p_c == 1:                                      # this rank's W rows see all their columns: the pass writes W
+                ops.is_update_w(A, W, H, eps)
+            else:
+                buf = _buf(("isnd_w", m_l, k), 2 * m_l * k, A)[: 2 * m_l * k]
+                num, den = ops.is_aht_pair(A, W, H, eps, buf)
+                self.comm1.allreduce_(buf)
+                ops.is_ratio_update(W, num, den, eps)
+        if self.p_r == 1:
+            ops.is_update_h(A, W, H, eps, clamp)
+        else:
+            buf = _buf(("isnd_h", k, n_l), 2 * k * n_l, A)[: 2 * k * n_l]
+            num, den = ops.is_wta_pair(A, W, H, eps, buf)
+            self.comm1.allreduce_(buf)
+            ops.is_ratio_update(H, num, den, eps, clamp)
+        if clamp:
+            ops.clamp_min(W, eps)
 
 
     # ---- BCD / Frobenius (dist_nmf.py:940-1047 in 1D, :474-579 in 2D).  The grid-specific pieces are the `_bcd_*` hooks of each

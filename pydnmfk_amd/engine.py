@@ -642,11 +642,16 @@ class HipOps:
         ONE library call (dnmf_{mu_fro,mu_kl,hals_fro}_fit; pyDNMF.py:138-182 on one rank).  A, W, H are matrices -- one
         problem -- or stacks [B][m][n], [B][m][k], [B][k][n] of B same-shape problems that every launch then covers together
         (blockIdx.z = problem; bit-identical to B single fits).  W, H are updated in place; returns the device tensor
-        [B][2] of {sum (A - W H)^2, sum A^2}."""
+        [B][2] of {sum (A - W H)^2, sum A^2}.  norm 'is' (method 'mu', one problem): `is_fit`, dnmf_is_mu_fit."""
         method, norm = method.lower(), norm.lower()
         batched = A.dim() == 3
         if W.dim() != A.dim() or H.dim() != A.dim():
             raise ValueError("fit: A, W, H must all be matrices or all be stacks")
+        if norm == "is":                                   # dnmf_is_mu_fit: one problem per call
+            if method != "mu" or batched:
+                raise NotImplementedError("norm='is' is provided for method 'mu' on one problem per call, not for '%s'%s"
+                                          % (method, " on a stack" if batched else ""))
+            return self.is_fit(A, W, H, eps, w_update, itr)
         A3, W3, H3 = (A, W, H) if batched else (A[None], W[None], H[None])
         sfx = _req_a(A3[0]); _req(W3[0], "W"); _req(H3[0], "H")
         B, m, n = A3.shape
@@ -678,6 +683,92 @@ class HipOps:
             check(fn(A3.data_ptr(), m, n, _ld(A3[0]), W3.data_ptr(), _ld(W3[0]), H3.data_ptr(), _ld(H3[0]), k, float(eps),
                      int(bool(w_update)), int(itr), *extra, int(B), A3.stride(0), W3.stride(0), H3.stride(0), sq.data_ptr(),
                      ws.data_ptr(), ws.numel(), _stream()))
+        return sq
+
+    # ---- the Itakura-Saito objective (csrc/dnmf_is.h, dnmf_is_*): dense strictly positive float32 data, 1 <= k <= 128.  With S = W H
+    # and R = 1 / (S + eps): num = (A . R . R) F, den = R F (F = H^T / W), X <- X * sqrt(num / (den + eps))
+    is_dtypes = (torch.float32,)       # the data types these operations take (PyNMF and the choreography refuse any other by name)
+
+    def _is(self, what, A, W, H, eps, nbytes_fn=None):
+        """the arguments every dnmf_is_* entry point starts with, and the scratch it ends with"""
+        _req(A, "A"); _req(W, "W"); _req(H, "H")
+        m, n = A.shape
+        k = W.shape[1]
+        if tuple(W.shape) != (m, k) or tuple(H.shape) != (k, n):
+            raise ValueError("%s: shapes A %s, W %s, H %s do not match" % (what, tuple(A.shape), tuple(W.shape), tuple(H.shape)))
+        nbytes = (nbytes_fn or lib.dnmf_is_ws_bytes)(int(m), int(n), int(k))
+        if nbytes == 0:
+            raise NotImplementedError("norm='is' with k = %d: the Itakura-Saito kernels serve 1 <= k <= 128" % k)
+        ws = _scratch(nbytes, A.device)
+        head = (A.data_ptr(), m, n, _ld(A), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), int(k), float(eps))
+        return head, (ws.data_ptr(), ws.numel(), _stream())
+
+    def _is_pair(self, side, A, W, H, eps, num, den):
+        head, tail = self._is("is pair", A, W, H, eps)
+        _req(num, "num"); _req(den, "den")
+        want = tuple(W.shape) if side == "w" else tuple(H.shape)
+        if tuple(num.shape) != want or tuple(den.shape) != want or _ld(num) != _ld(den):
+            raise ValueError("is pair: num %s and den %s must both be %s with one leading dimension" % (tuple(num.shape), tuple(den.shape), want))
+        fn = lib.dnmf_is_aht_pair if side == "w" else lib.dnmf_is_wta_pair
+        check(fn(*head, num.data_ptr(), den.data_ptr(), _ld(num), *tail))
+        return num, den
+
+    @staticmethod
+    def _is_halves(buf, shape):
+        r, c = shape
+        if buf.numel() < 2 * r * c or not buf.is_contiguous() or buf.dtype != torch.float32:
+            raise ValueError("is pair: a contiguous float32 buffer of 2 x %d x %d elements is expected" % (r, c))
+        return buf[: r * c].view(r, c), buf[r * c: 2 * r * c].view(r, c)
+
+    def is_aht_pair(self, A, W, H, eps, buf):
+        """buf = [num | den], each m x k: (A . R . R) H^T and R H^T"""
+        return self._is_pair("w", A, W, H, eps, *self._is_halves(buf, tuple(W.shape)))
+
+    def is_wta_pair(self, A, W, H, eps, buf):
+        """buf = [num | den], each k x n: W^T (A . R . R) and W^T R"""
+        return self._is_pair("h", A, W, H, eps, *self._is_halves(buf, tuple(H.shape)))
+
+    def is_pair_into(self, side, A, W, H, eps, num, den):
+        """the same pair into two views of the caller's (one leading dimension, any pitch): side 'w' (m x k) or 'h' (k x n)"""
+        return self._is_pair(side, A, W, H, eps, num, den)
+
+    def is_update_w(self, A, W, H, eps):
+        """W <- W * sqrt(num / (den + eps)): the pass, then the rule on its partial sums (this rank's W rows see all their columns)"""
+        head, tail = self._is("is_update_w", A, W, H, eps)
+        check(lib.dnmf_is_update_w(*head, *tail))
+        return W
+
+    def is_update_h(self, A, W, H, eps, clamp=False):
+        """H <- H * sqrt(num / (den + eps)), max(., eps) with `clamp` (this rank's H columns see all their rows)"""
+        head, tail = self._is("is_update_h", A, W, H, eps)
+        check(lib.dnmf_is_update_h(*head, int(bool(clamp)), *tail))
+        return H
+
+    def is_ratio_update(self, X, num, den, eps, clamp=False):
+        """X <- X * sqrt(num / (den + eps)), max(., eps) with `clamp`: the rule on a pair that was summed over the ranks"""
+        _req(X, "X"); _req(num, "num"); _req(den, "den")
+        if tuple(num.shape) != tuple(X.shape) or tuple(den.shape) != tuple(X.shape) or _ld(num) != _ld(den):
+            raise ValueError("is_ratio_update: X %s, num %s, den %s" % (tuple(X.shape), tuple(num.shape), tuple(den.shape)))
+        r, c = X.shape
+        check(lib.dnmf_is_ratio_update(X.data_ptr(), r, c, _ld(X), num.data_ptr(), den.data_ptr(), _ld(num), float(eps), int(bool(clamp)),
+                                       _stream()))
+        return X
+
+    def is_divergence(self, A, W, H, eps):
+        """D_IS(A | W H + eps) = sum (q - log q - 1), q = A / (W H + eps), over this block: one device double (stored, not
+        accumulated: two calls are bit-identical)"""
+        head, tail = self._is("is_divergence", A, W, H, eps)
+        out = torch.empty(1, dtype=torch.float64, device=A.device)
+        check(lib.dnmf_is_divergence(*head, out.data_ptr(), *tail))
+        return out
+
+    def is_fit(self, A, W, H, eps, w_update, itr):
+        """`itr` Itakura-Saito MU steps (clamps after the steps i % 10 == 0), normalize_features and the squared norms of relative_err in
+        ONE library call (dnmf_is_mu_fit: the launches of the step loop in its order).  One problem; W, H are updated in place; returns
+        the device tensor [1][2] of {sum (A - W H)^2, sum A^2}."""
+        head, tail = self._is("is_fit", A, W, H, eps, lib.dnmf_is_ws_bytes_fit)
+        sq = torch.empty(1, 2, dtype=torch.float64, device=A.device)
+        check(lib.dnmf_is_mu_fit(*head, int(bool(w_update)), int(itr), sq.data_ptr(), *tail))
         return sq
 
     def _bcd_fit(self, A3, W3, H3, eps, w_update, itr, sfx, batched):
@@ -722,6 +813,7 @@ class HipOpsBf16x6(HipOps):
     fp32 code either way."""
 
     name = "hip-bf16x6"
+    is_dtypes = ()                 # (no split form of the Itakura-Saito pairs)
     kl_uht_hblocks = None          # (no block-column variant of the split kernels: the 2D step concatenates H for them)
     aht_hblocks = None
 

@@ -21,6 +21,9 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
     masked objective, rules and error on the matrix cores (pydnmfk_amd.masked, csrc/dnmf_masked.h; method 'mu', 1D grids, k <= 128;
     on one rank the whole fit is one library call, dnmf_masked_mu_fit; `column_err` runs over the observed positions).
     Without `params.missing` dense data are not scanned for NaN;
+  * `params.norm = 'is'` (or 'itakura-saito'): the Itakura-Saito divergence by the majorisation-minimisation MU rule (csrc/dnmf_is.h;
+    no counterpart in the reference) -- strictly positive dense float32 data, method 'mu', 1D grids, k <= 128; on one rank the whole fit
+    is one library call, dnmf_is_mu_fit; `fit()` still returns the Frobenius relative error, `is_divergence()` reports the objective;
   * `prune=True` (the reference's default when the attribute is absent) drops all-zero rows / columns before the
     iterations and scatters the factors back afterwards.  numpy callers get float64 factors back in that case, exactly
     as from the reference (its unprune scatters into np.zeros, utils.py:195,198); tensor callers keep float32 on the GPU.
@@ -59,7 +62,7 @@ def storage_dtype(A_ij, params):
 
 
 _MASKS = ("row_zero_idx_x", "col_zero_idx_x", "row_zero_idx_w", "col_zero_idx_h")
-_NATIVE_FITS = (("mu", "fro"), ("mu", "kl"), ("hals", "fro"), ("bcd", "fro"))
+_NATIVE_FITS = (("mu", "fro"), ("mu", "kl"), ("hals", "fro"), ("bcd", "fro"), ("mu", "is"))
 
 
 class PyNMF:
@@ -119,6 +122,11 @@ class PyNMF:
         self.params.eps = self.eps
         self.norm = var_init(self.params, 'norm', default='kl')     # :70
         self.method = var_init(self.params, 'method', default='mu')
+        if str(self.norm).lower() in ('is', 'itakura-saito'):
+            self.norm = self.params.norm = 'is'
+        self._is = (self.norm == 'is')
+        if self._is:
+            self._is_checks(A_ij, missing)
         if self.a_dtype == torch.bfloat16 and str(self.norm).lower() == 'kl':
             raise TypeError("PyNMF: bfloat16 storage of A is provided for the Frobenius updates (mu / hals) only")
         self.prune = var_init(self.params, 'prune', default=True)
@@ -212,6 +220,39 @@ class PyNMF:
             raise NotImplementedError("missing='nan' on a 2D grid (%d x %d) is not provided: use a 1D grid (p_r = 1 or p_c = 1)" % (grid[0], grid[1]))
         if getattr(params, "init", None) == "nnsvd":
             raise NotImplementedError("missing='nan' with init='nnsvd' is not provided (the SVD would read the NaNs): init='rand' or factors=...")
+
+    def _is_checks(self, A_ij, missing):
+        """What is refused under norm='is', each by name (dense float32 data without missing entries, fp32 arithmetic, method 'mu', 1D
+        grids, k <= 128), and the one thing the data must be: strictly positive.  The ranks agree on that verdict through comm1 BEFORE
+        any of them raises, so none is left alone in a later collective."""
+        params = self.params
+        if missing is not None:
+            raise NotImplementedError("norm='is' with missing='%s' is not provided (dense data without missing entries only)" % missing)
+        if self._sparse:
+            raise NotImplementedError("norm='is' is not provided for sparse data: the Itakura-Saito divergence is infinite at a zero "
+                                      "entry (dense strictly positive float32 data only)")
+        if self.a_dtype == torch.bfloat16:
+            raise NotImplementedError("norm='is' with bfloat16 storage of the data is not provided (float32 data only)")
+        if (getattr(params, "gemm", None) or "fp32") != "fp32":
+            raise NotImplementedError("norm='is' with --gemm %s is not provided (fp32 arithmetic only)" % params.gemm)
+        # (an operator set names the data types its Itakura-Saito operations take, `is_dtypes`: the HIP kernels are float32)
+        if self.a_dtype not in (getattr(self.ops, "is_dtypes", ()) if self.ops is not None else (torch.float32,)):
+            raise NotImplementedError("norm='is' with %s data is not provided (float32 data only); cast the block to float32"
+                                      % str(self.a_dtype).replace("torch.", ""))
+        method = str(self.method).lower()
+        if method != "mu":
+            raise NotImplementedError("norm='is' is provided for method 'mu' only, not for '%s': HALS and BCD are Frobenius methods" % method)
+        if self.p_r != 1 and self.p_c != 1:
+            raise NotImplementedError("norm='is' on a 2D grid (%d x %d) is not provided: use a 1D grid (p_r = 1 or p_c = 1)"
+                                      % (self.p_r, self.p_c))
+        if self.params.k > 128:
+            raise NotImplementedError("norm='is' with k = %d is not provided: the Itakura-Saito kernels serve 1 <= k <= 128" % self.params.k)
+        lo = float(self.A_ij.min()) if self.A_ij.numel() else 1.0
+        bad = not lo > 0.0                                          # (a NaN minimum is refused as well)
+        nbad = int(self.comm1.allreduce(1 if bad else 0))
+        if nbad:
+            raise ValueError("norm='is' needs strictly positive data: the smallest entry of this rank's block is %g (%d of %d ranks hold "
+                             "an entry <= 0); the Itakura-Saito divergence is infinite there" % (lo, nbad, self.p_r * self.p_c))
 
     @staticmethod
     def _sparse_checks(A_ij, params):
@@ -360,6 +401,8 @@ class PyNMF:
         (anything else keeps the step loop, which raises the reference's messages for invalid pairs).  `params.fit_loop =
         'python'` keeps the step loop (A/B runs, tests of the per-step API).  A NaN-marked block (missing='nan') has one with the
         'hip-masked' set: dnmf_masked_mu_fit, the launches of the step loop in its order (one problem per call: never batched)."""
+        if self._is and getattr(ops, "name", "") != "hip":
+            return False                                            # (dnmf_is_mu_fit lives in the fp32 operator set only)
         if self._masked_dense:
             return (self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") == "hip-masked" and hasattr(ops, "fit")
                     and str(self.method).lower() == "mu" and str(self.norm).lower() in ("fro", "kl")
@@ -423,7 +466,7 @@ class PyNMF:
         f0 = fits[0] if fits else None
 
         def same(f):
-            return (not f._masked_dense and f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
+            return (not f._masked_dense and not f._is and f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
                     and f.A_ij.dtype == f0.A_ij.dtype and f.A_ij.device == f0.A_ij.device and f.W_i.shape == f0.W_i.shape
                     and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k) ==
                     (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k))
@@ -504,6 +547,20 @@ class PyNMF:
         self.glob_norm_err, self.glob_norm_A = float(np.sqrt(num)), float(np.sqrt(den))
         self.recon_err = self.glob_norm_err / self.glob_norm_A
         return self.recon_err
+
+    def is_divergence(self):
+        """D_IS(A | W H + eps) = sum (q - log q - 1), q = A / (W H + eps), of the CURRENT factors, summed over the grid (norm='is':
+        1D grids, where every rank's block meets its own W rows and H columns).  The objective the Itakura-Saito rule does not
+        increase; `fit()` keeps returning the Frobenius relative error, as it does for norm='kl'."""
+        if not self._is:
+            raise ValueError("is_divergence: this fit runs norm='%s'; the divergence is reported under norm='is'" % self.norm)
+        W, H = self.W_i, self.H_j
+        if W.shape[0] != self.A_ij.shape[0] or H.shape[1] != self.A_ij.shape[1]:   # (held factors are the pruned ones; see column_err)
+            W = W[self.params.row_zero_idx_x] if W.shape[0] != self.A_ij.shape[0] else W
+            H = H[:, self.params.col_zero_idx_x] if H.shape[1] != self.A_ij.shape[1] else H
+        d = self._ops().is_divergence(self.A_ij, W.contiguous(), H.contiguous(), self.eps)
+        self.comm1.allreduce_(d)
+        return float(d.cpu())
 
     def column_err(self):
         """pyDNMF.py:221-239: per-column relative error sqrt(sum_i (A - W H)^2 / sum_i A^2) over the GLOBAL n columns

@@ -171,6 +171,9 @@ class PyNMFk:
     def __init__(self, A_ij, factors=None, params=None, ops=None):
         from .sparse import is_sparse_input
         self._sparse = is_sparse_input(A_ij)
+        if str(getattr(params, "norm", None)).lower() in ("is", "itakura-saito"):
+            raise NotImplementedError("PyNMFk with norm='is' is not provided: rank estimation under the Itakura-Saito objective (a "
+                                      "perturbation model and a per-column error for it) is not built (PyNMF factorises at a given k)")
         self._masked = getattr(params, "missing", None) == "nan" and not self._sparse
         if self._masked:
             # as for a sparse block, the sweep touches A outside PyNMF.fit in the perturbed copy (NaN stays NaN through the
