@@ -27,42 +27,30 @@
 
 namespace {
 
-__device__ __forceinline__ float is_ratio(float x, float a, float b, float eps, int clamp) {
-    const float y = x * sqrtf(a / (b + eps));
-    return clamp ? fmaxf(y, eps) : y;
-}
+// ---- what the Itakura-Saito mode chooses on the launch path of csrc/dnmf_masked.h
+template <>
+struct PairMode<PAIR_IS> {
+    // The W side's plan: the masked one with ONE part of the output columns at KP = 128 (JT = KT = 4).  masked_uht_kernel<4, 2> forms
+    // every S tile twice, once per half of the output columns: 8 m n k flop for an IS side's 6 m n k.  With all four output tiles of
+    // both halves in one workgroup (128 accumulator registers, which the compiler keeps in AGPRs: 254 VGPRs + 156 AGPRs, no scratch,
+    // one wave per SIMD as before) S is formed once.  Up to KP = 64 nothing changes.
+    static constexpr int zdim128 = 1;
+    // The H side's plan: the masked one, but never fewer than four row chunks.  masked_wtu_kernel's workgroup is four waves = four
+    // chunks; the masked plan asks for 1024 / ncolblk of them, which is TWO at n = 16384, KP = 128 (512 column blocks of 32): half the
+    // waves of every workgroup returned at once and the pass ran on half the SIMDs (measured, 32768 x 16384, k = 128: 10.8 ms).
+    // Shapes with at most 256 column blocks -- every shape of the masked suite -- get the masked plan unchanged.
+    static constexpr long min_chunks = 4;
+    static constexpr bool sqrt_rule = true;     // X <- X * sqrt(num / (den + eps))
+    static constexpr const char* serves = "the Itakura-Saito kernels";
+};
 
-// ---- the endings of the pair kernels: the partial slabs added in part order (masked_reduce_kernel's loop), then either the pair
-// stored (num, den with leading dimension ldo: the two halves of one contiguous buffer where the sums cross ranks) or the rule
-// applied in place, X <- X * sqrt(num / (den + eps)), max(., eps) with clamp
-__global__ __launch_bounds__(256) void is_reduce_kernel(const float* __restrict__ P, long part_stride, long half_stride, long ldp, int nparts,
-                                                        long rows, long cols, float* __restrict__ num, float* __restrict__ den, long ldo,
-                                                        float* __restrict__ X, long ldx, float eps, int clamp) {
-    const long total = rows * cols;
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const long r = idx / cols, c = idx % cols;
-        const float* q = P + r * ldp + c;
-        float a = q[0], b = q[half_stride];
-        for (int s = 1; s < nparts; ++s) {
-            a += q[s * part_stride];
-            b += q[s * part_stride + half_stride];
-        }
-        if (X) {
-            X[r * ldx + c] = is_ratio(X[r * ldx + c], a, b, eps, clamp);
-        } else {
-            num[r * ldo + c] = a;
-            den[r * ldo + c] = b;
-        }
-    }
-}
-
-// the same rule on a stored pair (after its allreduce on a 1D grid)
+// ---- the rule on a stored pair (after its allreduce on a 1D grid): pair_rule's square-root form, as in the ending
 __global__ __launch_bounds__(256) void is_ratio_kernel(float* __restrict__ X, long rows, long cols, long ldx, const float* __restrict__ num,
                                                        const float* __restrict__ den, long ldo, float eps, int clamp) {
     const long total = rows * cols;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const long r = idx / cols, c = idx % cols;
-        X[r * ldx + c] = is_ratio(X[r * ldx + c], num[r * ldo + c], den[r * ldo + c], eps, clamp);
+        X[r * ldx + c] = pair_rule<true>(X[r * ldx + c], num[r * ldo + c], den[r * ldo + c], eps, clamp);
     }
 }
 

@@ -18,8 +18,12 @@
 // Every kernel here is generic: bounds by predication, any shape, any leading dimension (FAST = 16-byte rows, vector loads).  Sums
 // over column splits (W side) and row chunks (H side) are left as partials and added in split / chunk order by masked_reduce_kernel --
 // no float atomics, so a fit's factors are bit-reproducible.  Plain launch chains: no workgroup waits for another one.
+//
+// The pair kernels serve a third rule, Itakura-Saito (MODE = PAIR_IS, csrc/dnmf_is.h).  Everything around them exists once, in the
+// host part at the end of this file: plans, the launcher of each side, the ending, the plan report and the chain of a whole fit.
 #pragma once
 #include "dnmf_common.h"
+#include "dnmf_host.h"
 #include "dnmf_nt.h"
 #include "dnmf_stream.h"
 #include "dnmf_nn.h"
@@ -50,7 +54,7 @@ __device__ __forceinline__ void masked_pair(float a, float s, float eps, float& 
 // owns 128 rows, a lane the W row of its A row; S is formed transposed so that the contraction index of the second products is in
 // registers).  Two output accumulator sets do not fit next to the W row at KP = 128, so a workgroup owns JT of the KT 32-wide tiles of
 // output columns (blockIdx.z picks them; JT = KT up to KP = 64, JT = 2 at KP = 128 where S is formed twice).  (Both sets DO fit at
-// KP = 128 once the accumulators may live in AGPRs -- 254 + 156 registers, no scratch --: csrc/dnmf_is.hip launches JT = 4 there.)
+// KP = 128 once the accumulators may live in AGPRs -- 254 + 156 registers, no scratch --: the Itakura-Saito mode launches JT = 4 there, csrc/dnmf_is.h.)
 template <int KT, int JT, bool FAST, int MODE>
 __global__ __launch_bounds__(256, KT == 4 ? 1 : 2) void masked_uht_kernel(NnArgs p, float* __restrict__ P, long split_stride,
                                                                           long half_stride, long cols_per_split) {
@@ -238,12 +242,21 @@ __global__ __launch_bounds__(256, 1) void masked_wtu_kernel(NnArgs p, long half_
 }
 
 // ---- the endings: the partials added in part order, then either the pair stored (num, den with leading dimension ldo: the two halves
-// of one contiguous buffer where the sums cross ranks) or the rule applied, X <- X * (num / (den + eps)), max(., eps) with clamp
-// (the expression of dnmf_csr_ratio_update, which follows an allreduce of the stored pair)
+// of one contiguous buffer where the sums cross ranks) or the rule applied in place, max(., eps) with clamp.  The rule: the ratio,
+// X <- X * (num / (den + eps)) (the masked rules; the expression of dnmf_csr_ratio_update, which follows an allreduce of the stored
+// pair), or with SQRT its square root, X <- X * sqrt(num / (den + eps)) (the Itakura-Saito rule, csrc/dnmf_is.h)
+template <bool SQRT>
+__device__ __forceinline__ float pair_rule(float x, float a, float b, float eps, int clamp) {
+    const float q = a / (b + eps);
+    const float y = x * (SQRT ? sqrtf(q) : q);
+    return clamp ? fmaxf(y, eps) : y;
+}
+
+template <bool SQRT>
 __global__ __launch_bounds__(256) void masked_reduce_kernel(const float* __restrict__ P, long part_stride, long half_stride, long ldp,
-                                                            int nparts, long rows, long cols, float* __restrict__ num,
-                                                            float* __restrict__ den, long ldo, float* __restrict__ X, long ldx, float eps,
-                                                            int clamp) {
+                                                          int nparts, long rows, long cols, float* __restrict__ num,
+                                                          float* __restrict__ den, long ldo, float* __restrict__ X, long ldx, float eps,
+                                                          int clamp) {
     const long total = rows * cols;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const long r = idx / cols, c = idx % cols;
@@ -254,8 +267,7 @@ __global__ __launch_bounds__(256) void masked_reduce_kernel(const float* __restr
             b += q[s * part_stride + half_stride];
         }
         if (X) {
-            const float y = X[r * ldx + c] * (a / (b + eps));
-            X[r * ldx + c] = clamp ? fmaxf(y, eps) : y;
+            X[r * ldx + c] = pair_rule<SQRT>(X[r * ldx + c], a, b, eps, clamp);
         } else {
             num[r * ldo + c] = a;
             den[r * ldo + c] = b;
@@ -369,12 +381,24 @@ __global__ __launch_bounds__(256) void masked_sqnorm_kernel(const float* __restr
 }
 
 // ================================================================================================ host side
-// The launch plans and predicates of the pair kernels above, shared by the translation units that launch them (csrc/dnmf_masked.hip,
-// csrc/dnmf_is.hip).
+// The ONE launch path of the pair kernels above: plans, launchers of both sides, the ending, the plan report and the chain of a whole
+// fit, templated on MODE so that a translation unit instantiates only the kernels of the modes it launches (csrc/dnmf_masked.hip:
+// PAIR_FRO and PAIR_KL; csrc/dnmf_is.hip: PAIR_IS).
+
+// What a mode chooses: its two plan parameters (below), the form of its rule, and how the messages name its kernels.  The masked
+// modes take these; csrc/dnmf_is.h states the Itakura-Saito ones.
+template <int MODE>
+struct PairMode {
+    static constexpr int zdim128 = 2;           // parts of the output columns at KP = 128: JT = KT / zdim128 tiles per workgroup
+    static constexpr long min_chunks = 1;       // the fewest row chunks the H side asks for
+    static constexpr bool sqrt_rule = false;    // pair_rule's SQRT
+    static constexpr const char* serves = "masked dense data";
+};
+
 // W side: 128-row tiles x column splits (x zdim128 = KT / JT parts of the output columns at KP = 128: 2 with JT = 2); splits are whole
 // 32-column tiles
 struct MaskedUhtPlan { long rowtiles; int zdim; long cols_per_split; int nsplit; size_t bytes; };
-MaskedUhtPlan plan_masked_uht(long m, long n, int kt, int zdim128 = 2) {
+MaskedUhtPlan plan_masked_uht(long m, long n, int kt, int zdim128) {
     MaskedUhtPlan u{};
     u.rowtiles = cdiv(m, 128);
     u.zdim = kt == 4 ? zdim128 : 1;
@@ -388,9 +412,9 @@ MaskedUhtPlan plan_masked_uht(long m, long n, int kt, int zdim128 = 2) {
 }
 
 // H side: column blocks of CW = 32 NT columns x row chunks (a wave per chunk).  min_chunks: the fewest chunks to ask for (a workgroup
-// is four chunks: with fewer, waves of every workgroup idle -- csrc/dnmf_is.hip asks for four)
+// is four chunks: with fewer, waves of every workgroup idle)
 struct MaskedWtuPlan { int nt; int ncolblk; long ldp; long nrowblk; long rowblks_per_chunk; long nchunks; size_t bytes; };
-MaskedWtuPlan plan_masked_wtu(long m, long n, int kt, long min_chunks = 1) {
+MaskedWtuPlan plan_masked_wtu(long m, long n, int kt, long min_chunks) {
     MaskedWtuPlan w{};
     w.nt = kt == 1 ? 4 : (kt == 2 ? 2 : 1);
     w.ncolblk = (int)cdiv(n, 32 * w.nt);
@@ -401,6 +425,15 @@ MaskedWtuPlan plan_masked_wtu(long m, long n, int kt, long min_chunks = 1) {
     w.nchunks = cdiv(w.nrowblk, w.rowblks_per_chunk);
     w.bytes = (size_t)w.nchunks * 2 * (32 * kt) * w.ldp * sizeof(float);
     return w;
+}
+
+template <int MODE> MaskedUhtPlan pair_uht_plan(long m, long n, int kt) { return plan_masked_uht(m, n, kt, PairMode<MODE>::zdim128); }
+template <int MODE> MaskedWtuPlan pair_wtu_plan(long m, long n, int kt) { return plan_masked_wtu(m, n, kt, PairMode<MODE>::min_chunks); }
+
+// the slabs of one step: the larger side's
+template <int MODE>
+size_t pair_step_bytes(long m, long n, int kt) {
+    return align256(std::max(pair_uht_plan<MODE>(m, n, kt).bytes, pair_wtu_plan<MODE>(m, n, kt).bytes));
 }
 
 NnArgs masked_args(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps) {
@@ -416,5 +449,140 @@ bool masked_fast(const float* A, long n, long lda, const float* W, long ldw, con
 
 // workgroups of masked_reduce_kernel (256 output elements each per grid-stride trip) for rows x cols outputs
 long masked_reduce_grid(long rows, long cols) { return std::min<long>(cdiv(rows * cols, 256), 8192); }
+
+template <int MODE>
+int pair_reduce(const float* P, long part_stride, long half_stride, long ldp, int nparts, long rows, long cols, float* num, float* den,
+                long ldo, float* X, long ldx, float eps, int clamp, hipStream_t st, const char* who) {
+    const unsigned grid = (unsigned)masked_reduce_grid(rows, cols);
+    hipLaunchKernelGGL(masked_reduce_kernel<PairMode<MODE>::sqrt_rule>, dim3(grid), dim3(256), 0, st, P, part_stride, half_stride, ldp, nparts,
+                       rows, cols, num, den, ldo, X, ldx, eps, clamp);
+    return check_launch(who);
+}
+
+// the W side into partial slabs, then the ending: (num, den) stored, or X = W updated in place
+template <int MODE>
+int pair_w_side(const char* who, const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
+                float eps, float* num, float* den, long ldo, float* X, void* ws, size_t ws_bytes, void* stream) {
+    const int kt = kt_of(k);
+    REQUIRE(kt > 0, "%s: rank k=%d unsupported (1 <= k <= %d for %s)", who, k, DNMF_TUNED_MAX_K, PairMode<MODE>::serves);
+    REQUIRE(A && W && H && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n && (X || (num && den && ldo >= k)),
+            "%s: null pointer or bad shape", who);
+    const MaskedUhtPlan u = pair_uht_plan<MODE>(m, n, kt);
+    if (!ws || ws_bytes < u.bytes || !aligned16(ws)) return fail(DNMF_EWS, "%s: workspace %zu < %zu bytes", who, ws_bytes, u.bytes);
+    const int kp = 32 * kt;
+    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
+    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
+    const long half = m * kp, split = 2 * half;
+    const dim3 grid((unsigned)u.rowtiles, (unsigned)u.nsplit, (unsigned)u.zdim), block(256);
+    const size_t lds = 2ul * kp * BK * sizeof(float);
+    hipStream_t st = S(stream);
+    float* P = (float*)ws;
+#define PW_CASE(KT_, JT_)                                                                                                              \
+    if (kt == KT_) {                                                                                                                   \
+        if (fast) hipLaunchKernelGGL((masked_uht_kernel<KT_, JT_, true, MODE>), grid, block, lds, st, a, P, split, half, u.cols_per_split);  \
+        else hipLaunchKernelGGL((masked_uht_kernel<KT_, JT_, false, MODE>), grid, block, lds, st, a, P, split, half, u.cols_per_split);      \
+    }
+    PW_CASE(1, 1) PW_CASE(2, 2) PW_CASE(4, 4 / PairMode<MODE>::zdim128)
+#undef PW_CASE
+    if (int rc = check_launch(who)) return rc;
+    return pair_reduce<MODE>(P, split, half, kp, u.nsplit, m, k, num, den, ldo, X, ldw, eps, 0, st, who);
+}
+
+template <int MODE>
+int pair_h_side(const char* who, const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
+                float eps, float* num, float* den, long ldo, float* X, int clamp, void* ws, size_t ws_bytes, void* stream) {
+    const int kt = kt_of(k);
+    REQUIRE(kt > 0, "%s: rank k=%d unsupported (1 <= k <= %d for %s)", who, k, DNMF_TUNED_MAX_K, PairMode<MODE>::serves);
+    REQUIRE(A && W && H && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n && (X || (num && den && ldo >= n)),
+            "%s: null pointer or bad shape", who);
+    const MaskedWtuPlan w = pair_wtu_plan<MODE>(m, n, kt);
+    if (!ws || ws_bytes < w.bytes || !aligned16(ws)) return fail(DNMF_EWS, "%s: workspace %zu < %zu bytes", who, ws_bytes, w.bytes);
+    const int kp = 32 * kt;
+    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
+    a.ncolblk = w.ncolblk;
+    const long half = (long)kp * w.ldp;
+    a.P = (float*)ws; a.ldp = w.ldp; a.chunk_stride = 2 * half;
+    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
+    const dim3 grid((unsigned)(cdiv(w.nchunks, 4) * w.ncolblk)), block(256);     // 4 row chunks (waves) per workgroup
+    const size_t lds = (size_t)kp * 32 * w.nt * sizeof(float);
+    hipStream_t st = S(stream);
+#define PH_CASE(KT_, NT_)                                                                                                         \
+    if (kt == KT_) {                                                                                                              \
+        if (fast) hipLaunchKernelGGL((masked_wtu_kernel<KT_, NT_, true, MODE>), grid, block, lds, st, a, half, w.rowblks_per_chunk);    \
+        else hipLaunchKernelGGL((masked_wtu_kernel<KT_, NT_, false, MODE>), grid, block, lds, st, a, half, w.rowblks_per_chunk);        \
+    }
+    PH_CASE(1, 4) PH_CASE(2, 2) PH_CASE(4, 1)
+#undef PH_CASE
+    if (int rc = check_launch(who)) return rc;
+    return pair_reduce<MODE>(a.P, a.chunk_stride, half, w.ldp, (int)w.nchunks, k, n, num, den, ldo, X, ldh, eps, clamp, st, who);
+}
+
+// the launch plans of both sides as numbers (host arithmetic, no GPU): what the launches above use, for callers and tests that must
+// know which loops of the kernels a shape enters
+template <int MODE>
+int pair_plan_report(const char* who, long m, long n, int k, long* out) {
+    const int kt = kt_of(k);
+    REQUIRE(kt > 0, "%s: rank k=%d unsupported (1 <= k <= %d for %s)", who, k, DNMF_TUNED_MAX_K, PairMode<MODE>::serves);
+    REQUIRE(out && m >= 1 && n >= 1, "%s: null pointer or bad shape", who);
+    const MaskedUhtPlan u = pair_uht_plan<MODE>(m, n, kt);
+    const MaskedWtuPlan w = pair_wtu_plan<MODE>(m, n, kt);
+    out[0] = u.cols_per_split / BK;     // 32-column tiles a workgroup of the W side walks (the last split may hold fewer)
+    out[1] = u.nsplit;
+    out[2] = u.zdim;
+    out[3] = w.rowblks_per_chunk;       // 32-row blocks a wave of the H side walks (the last chunk may hold fewer)
+    out[4] = w.nchunks;
+    out[5] = w.nrowblk;
+    return DNMF_OK;
+}
+
+// workspace of a whole fit: the step's slabs, the partials of the column sums of W (dnmf_colsum: at most 1024 slabs of KP floats), the
+// sums themselves, and 256 bytes for the doubles of the error ({resid, ||A||^2}; masked: {resid, ||P(A)||^2, |Omega|})
+struct PairFitWs { size_t step; size_t part_off; size_t part_bytes; size_t cs_off; size_t sq_off; size_t total; };
+PairFitWs pair_fit_layout(size_t step, int k) {
+    PairFitWs f{};
+    const size_t kp = 32 * (size_t)kt_of(k);
+    f.step = step;
+    f.part_off = f.step;
+    f.part_bytes = align256(1024 * kp * sizeof(float));
+    f.cs_off = f.part_off + f.part_bytes;
+    f.sq_off = f.cs_off + align256(kp * sizeof(float));
+    f.total = f.sq_off + 256;
+    return f;
+}
+
+// pyDNMF.py:138-182 under a pair rule on one rank: the launches the step loop makes, in its order, with nothing in between.  The rule
+// is its two step calls (step_w(bytes), step_h(clamp, bytes), on the first `bytes` = step_bytes(m, n, kt) of the workspace) and the two
+// squared norms of its error (resid(sq), sqnorm(sq + 1))
+template <int MODE, class StepW, class StepH, class Resid, class Sqnorm>
+int pair_mu_fit(const char* who, size_t (*step_bytes)(long, long, int), const float* A, long m, long n, long lda, float* W, long ldw,
+                float* H, long ldh, int k, float eps, int w_update, int itr, double* sq_out, void* ws, size_t ws_bytes, void* stream,
+                StepW step_w, StepH step_h, Resid resid, Sqnorm sqnorm) {
+    const int kt = kt_of(k);
+    REQUIRE(kt > 0, "%s: rank k=%d unsupported (1 <= k <= %d for %s)", who, k, DNMF_TUNED_MAX_K, PairMode<MODE>::serves);
+    REQUIRE(A && W && H && sq_out && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n && itr >= 0,
+            "%s: null pointer or bad shape (m=%ld n=%ld k=%d itr=%d)", who, m, n, k, itr);
+    const PairFitWs f = pair_fit_layout(step_bytes(m, n, kt), k);
+    if (!ws || ws_bytes < f.total || !aligned16(ws)) return fail(DNMF_EWS, "%s: workspace %zu < %zu bytes", who, ws_bytes, f.total);
+    char* base = (char*)ws;
+    int rc = DNMF_OK;
+    for (int i = 0; i < itr; ++i) {                                                                   // pyDNMF.py:151-172
+        const int clamp = (i % 10 == 0);
+        if (w_update && (rc = step_w(f.step))) return rc;
+        if ((rc = step_h(clamp, f.step))) return rc;
+        if (clamp && (rc = dnmf_clamp_min(W, m, k, ldw, eps, stream))) return rc;
+    }
+    // normalize_features (pyDNMF.py:185-194): s = column sums of W; W /= s + eps; H *= s^T
+    float* s = (float*)(base + f.cs_off);
+    if ((rc = dnmf_colsum(W, m, k, ldw, s, base + f.part_off, f.part_bytes, stream))) return rc;
+    if ((rc = dnmf_scale_cols_div(W, m, k, ldw, s, eps, stream))) return rc;
+    if ((rc = dnmf_scale_rows_mul(H, k, n, ldh, s, stream))) return rc;
+    // relative_err (pyDNMF.py:205-218); the caller takes the square roots
+    double* sq = (double*)(base + f.sq_off);
+    if ((rc = resid(sq))) return rc;
+    if ((rc = sqnorm(sq + 1))) return rc;
+    if (hipMemcpyAsync(sq_out, sq, 2 * sizeof(double), hipMemcpyDeviceToDevice, S(stream)) != hipSuccess)
+        return fail(DNMF_EHIP, "%s: copy of the squared norms failed", who);
+    return DNMF_OK;
+}
 
 }  // namespace

@@ -1,4 +1,5 @@
-// dnmf_masked.hip -- C ABI of the masked MU rules on DENSE data whose missing entries are NaN (csrc/dnmf_masked.h).  A translation unit
+// dnmf_masked.hip -- C ABI of the masked MU rules on DENSE data whose missing entries are NaN: the masked modes of the pair launch
+// path of csrc/dnmf_masked.h behind their ABI names, and the error kernels of a masked block with their plans.  A translation unit
 // of its own (see csrc/dnmf_kl.hip).  Plain launch chains: no workgroup waits for another one; no float atomics in the products.
 #include "dnmf_common.h"
 #include "dnmf_host.h"
@@ -21,88 +22,17 @@ MaskedColerrPlan plan_masked_colerr(long m, long n) {
     return c;
 }
 
-// workspace of a whole fit: the step's slabs, the partials of the column sums of W (dnmf_colsum: at most 1024 slabs of KP floats), the
-// sums themselves, and three doubles {resid, ||P(A)||^2, |Omega|}
-struct MaskedFitWs { size_t step; size_t part_off; size_t part_bytes; size_t cs_off; size_t sq_off; size_t total; };
-MaskedFitWs masked_fit_layout(long m, long n, int k) {
-    MaskedFitWs f{};
-    const int kt = kt_of(k);
-    const size_t kp = 32 * (size_t)kt;
-    f.step = align256(std::max(plan_masked_uht(m, n, kt).bytes, plan_masked_wtu(m, n, kt).bytes));
-    f.part_off = f.step;
-    f.part_bytes = align256(1024 * kp * sizeof(float));
-    f.cs_off = f.part_off + f.part_bytes;
-    f.sq_off = f.cs_off + align256(kp * sizeof(float));
-    f.total = f.sq_off + 256;
-    return f;
-}
-
-int masked_reduce(const float* P, long part_stride, long half_stride, long ldp, int nparts, long rows, long cols, float* num, float* den,
-                  long ldo, float* X, long ldx, float eps, int clamp, hipStream_t st, const char* who) {
-    const unsigned grid = (unsigned)masked_reduce_grid(rows, cols);
-    hipLaunchKernelGGL(masked_reduce_kernel, dim3(grid), dim3(256), 0, st, P, part_stride, half_stride, ldp, nparts, rows, cols, num, den, ldo,
-                       X, ldx, eps, clamp);
-    return check_launch(who);
-}
-
-// the W side into partial slabs, then the ending: (num, den) stored, or X = W updated in place
+// the two masked modes of the one launch path (csrc/dnmf_masked.h), picked by the ABI's `kl`
 int masked_w_side(const char* who, const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
                   float eps, int kl, float* num, float* den, long ldo, float* X, void* ws, size_t ws_bytes, void* stream) {
-    const int kt = kt_of(k);
-    REQUIRE(kt > 0, "%s: rank k=%d unsupported (1 <= k <= %d for masked dense data)", who, k, DNMF_TUNED_MAX_K);
-    REQUIRE(A && W && H && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n && (X || (num && den && ldo >= k)),
-            "%s: null pointer or bad shape", who);
-    const MaskedUhtPlan u = plan_masked_uht(m, n, kt);
-    if (!ws || ws_bytes < u.bytes || !aligned16(ws)) return fail(DNMF_EWS, "%s: workspace %zu < %zu bytes", who, ws_bytes, u.bytes);
-    const int kp = 32 * kt;
-    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
-    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
-    const long half = m * kp, split = 2 * half;
-    const dim3 grid((unsigned)u.rowtiles, (unsigned)u.nsplit, (unsigned)u.zdim), block(256);
-    const size_t lds = 2ul * kp * BK * sizeof(float);
-    hipStream_t st = S(stream);
-    float* P = (float*)ws;
-#define MU_CASE(KT_, JT_)                                                                                                    \
-    if (kt == KT_) {                                                                                                         \
-        if (fast && kl) hipLaunchKernelGGL((masked_uht_kernel<KT_, JT_, true, true>), grid, block, lds, st, a, P, split, half, u.cols_per_split);   \
-        else if (fast) hipLaunchKernelGGL((masked_uht_kernel<KT_, JT_, true, false>), grid, block, lds, st, a, P, split, half, u.cols_per_split);   \
-        else if (kl) hipLaunchKernelGGL((masked_uht_kernel<KT_, JT_, false, true>), grid, block, lds, st, a, P, split, half, u.cols_per_split);     \
-        else hipLaunchKernelGGL((masked_uht_kernel<KT_, JT_, false, false>), grid, block, lds, st, a, P, split, half, u.cols_per_split);            \
-    }
-    MU_CASE(1, 1) MU_CASE(2, 2) MU_CASE(4, 2)
-#undef MU_CASE
-    if (int rc = check_launch(who)) return rc;
-    return masked_reduce(P, split, half, kp, u.nsplit, m, k, num, den, ldo, X, ldw, eps, 0, st, who);
+    return kl ? pair_w_side<PAIR_KL>(who, A, m, n, lda, W, ldw, H, ldh, k, eps, num, den, ldo, X, ws, ws_bytes, stream)
+              : pair_w_side<PAIR_FRO>(who, A, m, n, lda, W, ldw, H, ldh, k, eps, num, den, ldo, X, ws, ws_bytes, stream);
 }
 
 int masked_h_side(const char* who, const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
                   float eps, int kl, float* num, float* den, long ldo, float* X, int clamp, void* ws, size_t ws_bytes, void* stream) {
-    const int kt = kt_of(k);
-    REQUIRE(kt > 0, "%s: rank k=%d unsupported (1 <= k <= %d for masked dense data)", who, k, DNMF_TUNED_MAX_K);
-    REQUIRE(A && W && H && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n && (X || (num && den && ldo >= n)),
-            "%s: null pointer or bad shape", who);
-    const MaskedWtuPlan w = plan_masked_wtu(m, n, kt);
-    if (!ws || ws_bytes < w.bytes || !aligned16(ws)) return fail(DNMF_EWS, "%s: workspace %zu < %zu bytes", who, ws_bytes, w.bytes);
-    const int kp = 32 * kt;
-    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
-    a.ncolblk = w.ncolblk;
-    const long half = (long)kp * w.ldp;
-    a.P = (float*)ws; a.ldp = w.ldp; a.chunk_stride = 2 * half;
-    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
-    const dim3 grid((unsigned)(cdiv(w.nchunks, 4) * w.ncolblk)), block(256);     // 4 row chunks (waves) per workgroup
-    const size_t lds = (size_t)kp * 32 * w.nt * sizeof(float);
-    hipStream_t st = S(stream);
-#define MH_CASE(KT_, NT_)                                                                                                    \
-    if (kt == KT_) {                                                                                                         \
-        if (fast && kl) hipLaunchKernelGGL((masked_wtu_kernel<KT_, NT_, true, true>), grid, block, lds, st, a, half, w.rowblks_per_chunk);    \
-        else if (fast) hipLaunchKernelGGL((masked_wtu_kernel<KT_, NT_, true, false>), grid, block, lds, st, a, half, w.rowblks_per_chunk);    \
-        else if (kl) hipLaunchKernelGGL((masked_wtu_kernel<KT_, NT_, false, true>), grid, block, lds, st, a, half, w.rowblks_per_chunk);      \
-        else hipLaunchKernelGGL((masked_wtu_kernel<KT_, NT_, false, false>), grid, block, lds, st, a, half, w.rowblks_per_chunk);             \
-    }
-    MH_CASE(1, 4) MH_CASE(2, 2) MH_CASE(4, 1)
-#undef MH_CASE
-    if (int rc = check_launch(who)) return rc;
-    return masked_reduce(a.P, a.chunk_stride, half, w.ldp, (int)w.nchunks, k, n, num, den, ldo, X, ldh, eps, clamp, st, who);
+    return kl ? pair_h_side<PAIR_KL>(who, A, m, n, lda, W, ldw, H, ldh, k, eps, num, den, ldo, X, clamp, ws, ws_bytes, stream)
+              : pair_h_side<PAIR_FRO>(who, A, m, n, lda, W, ldw, H, ldh, k, eps, num, den, ldo, X, clamp, ws, ws_bytes, stream);
 }
 
 }  // namespace
@@ -112,25 +42,10 @@ extern "C" {
 size_t dnmf_masked_ws_bytes(long m, long n, int k) {
     const int kt = kt_of(k);
     if (kt < 0 || m < 1 || n < 1) return 0;
-    return align256(std::max(plan_masked_uht(m, n, kt).bytes, plan_masked_wtu(m, n, kt).bytes));
+    return pair_step_bytes<PAIR_FRO>(m, n, kt);
 }
 
-// the launch plans of both sides as numbers (host arithmetic, no GPU): what the launches above use, for callers and tests that must
-// know which loops of the kernels a shape enters
-int dnmf_masked_plan(long m, long n, int k, long out[6]) {
-    const int kt = kt_of(k);
-    REQUIRE(kt > 0, "masked_plan: rank k=%d unsupported (1 <= k <= %d for masked dense data)", k, DNMF_TUNED_MAX_K);
-    REQUIRE(out && m >= 1 && n >= 1, "masked_plan: null pointer or bad shape");
-    const MaskedUhtPlan u = plan_masked_uht(m, n, kt);
-    const MaskedWtuPlan w = plan_masked_wtu(m, n, kt);
-    out[0] = u.cols_per_split / BK;     // 32-column tiles a workgroup of the W side walks (the last split may hold fewer)
-    out[1] = u.nsplit;
-    out[2] = u.zdim;
-    out[3] = w.rowblks_per_chunk;       // 32-row blocks a wave of the H side walks (the last chunk may hold fewer)
-    out[4] = w.nchunks;
-    out[5] = w.nrowblk;
-    return DNMF_OK;
-}
+int dnmf_masked_plan(long m, long n, int k, long out[6]) { return pair_plan_report<PAIR_FRO>("masked_plan", m, n, k, out); }
 
 // the grid of the ending (masked_reduce_kernel) for a rows x cols output, as the launches size it: rows x cols = m x k on the W side,
 // k x n on the H side; the kernel takes cdiv(rows * cols, 256 * grid) grid-stride trips.  0 for rows or cols < 1.
@@ -233,39 +148,20 @@ int dnmf_masked_column_err(const float* A, long m, long n, long lda, const float
 }
 
 size_t dnmf_masked_ws_bytes_fit(long m, long n, int k) {
-    if (kt_of(k) < 0 || m < 1 || n < 1) return 0;
-    return masked_fit_layout(m, n, k).total;
+    const int kt = kt_of(k);
+    if (kt < 0 || m < 1 || n < 1) return 0;
+    return pair_fit_layout(pair_step_bytes<PAIR_FRO>(m, n, kt), k).total;
 }
 
-// pyDNMF.py:138-182 for a masked block on one rank: the launches the step loop makes, in its order, with nothing in between
+// a whole masked fit: the chain of csrc/dnmf_masked.h with the masked steps and the error over the observed positions
 int dnmf_masked_mu_fit(const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps, int kl,
                        int w_update, int itr, double* sq_out, void* ws, size_t ws_bytes, void* stream) {
-    const int kt = kt_of(k);
-    REQUIRE(kt > 0, "masked_mu_fit: rank k=%d unsupported (1 <= k <= %d for masked dense data)", k, DNMF_TUNED_MAX_K);
-    REQUIRE(A && W && H && sq_out && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n && itr >= 0,
-            "masked_mu_fit: null pointer or bad shape (m=%ld n=%ld k=%d itr=%d)", m, n, k, itr);
-    const MaskedFitWs f = masked_fit_layout(m, n, k);
-    if (!ws || ws_bytes < f.total || !aligned16(ws)) return fail(DNMF_EWS, "masked_mu_fit: workspace %zu < %zu bytes", ws_bytes, f.total);
-    char* base = (char*)ws;
-    int rc = DNMF_OK;
-    for (int i = 0; i < itr; ++i) {                                                                   // pyDNMF.py:151-172
-        const int clamp = (i % 10 == 0);
-        if (w_update && (rc = dnmf_masked_update_w(A, m, n, lda, W, ldw, H, ldh, k, eps, kl, ws, f.step, stream))) return rc;
-        if ((rc = dnmf_masked_update_h(A, m, n, lda, W, ldw, H, ldh, k, eps, kl, clamp, ws, f.step, stream))) return rc;
-        if (clamp && (rc = dnmf_clamp_min(W, m, k, ldw, eps, stream))) return rc;
-    }
-    // normalize_features (pyDNMF.py:185-194): s = column sums of W; W /= s + eps; H *= s^T
-    float* s = (float*)(base + f.cs_off);
-    if ((rc = dnmf_colsum(W, m, k, ldw, s, base + f.part_off, f.part_bytes, stream))) return rc;
-    if ((rc = dnmf_scale_cols_div(W, m, k, ldw, s, eps, stream))) return rc;
-    if ((rc = dnmf_scale_rows_mul(H, k, n, ldh, s, stream))) return rc;
-    // relative_err (pyDNMF.py:205-218) over the observed positions; the caller takes the square roots
-    double* sq = (double*)(base + f.sq_off);
-    if ((rc = dnmf_masked_resid_sqnorm(A, m, n, lda, W, ldw, H, ldh, k, sq, stream))) return rc;
-    if ((rc = dnmf_masked_sqnorm(A, m, n, lda, sq + 1, stream))) return rc;
-    if (hipMemcpyAsync(sq_out, sq, 2 * sizeof(double), hipMemcpyDeviceToDevice, S(stream)) != hipSuccess)
-        return fail(DNMF_EHIP, "masked_mu_fit: copy of the squared norms failed");
-    return DNMF_OK;
+    return pair_mu_fit<PAIR_FRO>(
+        "masked_mu_fit", pair_step_bytes<PAIR_FRO>, A, m, n, lda, W, ldw, H, ldh, k, eps, w_update, itr, sq_out, ws, ws_bytes, stream,
+        [&](size_t step) { return dnmf_masked_update_w(A, m, n, lda, W, ldw, H, ldh, k, eps, kl, ws, step, stream); },
+        [&](int clamp, size_t step) { return dnmf_masked_update_h(A, m, n, lda, W, ldw, H, ldh, k, eps, kl, clamp, ws, step, stream); },
+        [&](double* sq) { return dnmf_masked_resid_sqnorm(A, m, n, lda, W, ldw, H, ldh, k, sq, stream); },
+        [&](double* sq) { return dnmf_masked_sqnorm(A, m, n, lda, sq, stream); });
 }
 
 }  // extern "C"

@@ -105,11 +105,34 @@ class _Base:
         else:
             raise Exception('Not a valid norm: Choose (fro/kl)')               # dist_nmf.py:91,659
 
+    # ---- MU by a pair rule (1D grids): numerator AND denominator of the rule depend on the data (on its pattern, or through S = W H),
+    # so what crosses ranks is the pair [num | den] in one contiguous buffer -- one allreduce per side -- and the ratio rule follows it.
+    # A rule is its five operations; `role` keeps its buffers apart from another rule's (an NMFk sweep reuses them per rule).
+    def _pair_MU_update(self, role, update_w, update_h, aht_pair, wta_pair, ratio_update, W_update, clamp):
+        ops, A, W, H, eps, k = self.ops, self.A_ij, self.W_i, self.H_j, self.eps, self.k
+        m_l, n_l = A.shape
+        if W_update:
+            if self.p_c == 1:                                      # this rank's W rows see all their columns: the pass writes W
+                update_w(A, W, H, eps)
+            else:
+                buf = _buf((role + "_w", m_l, k), 2 * m_l * k, A)[: 2 * m_l * k]
+                num, den = aht_pair(A, W, H, eps, buf)
+                self.comm1.allreduce_(buf)                         # (masked: where :707 sums A H^T (fro) / :797 sums U H^T (kl))
+                ratio_update(W, num, den, eps)
+        if self.p_r == 1:
+            update_h(A, W, H, eps, clamp)
+        else:
+            buf = _buf((role + "_h", k, n_l), 2 * k * n_l, A)[: 2 * k * n_l]
+            num, den = wta_pair(A, W, H, eps, buf)
+            self.comm1.allreduce_(buf)
+            ratio_update(H, num, den, eps, clamp)
+        if clamp:
+            ops.clamp_min(W, eps)
+
     # ---- Itakura-Saito, MU in its majorisation-minimisation form (1D grids).  With S = W H, R = 1 / (S + eps) and F = H^T / W:
     #     num = (A . R . R) F,  den = R F,  X <- X * sqrt(num / (den + eps))
-    # Numerator AND denominator depend on the data, so what crosses ranks is the pair [num | den]: the shape of _masked_MU_update
     def IS_MU_update(self, W_update=True, clamp=False):
-        ops, A, eps, k = self.ops, self.A_ij, self.eps, self.k
+        ops, A = self.ops, self.A_ij
         if self.p_r != 1 and self.p_c != 1:
             raise NotImplementedError("norm='is' on a 2D grid (p_r = %d, p_c = %d) is not provided: use a 1D grid" % (self.p_r, self.p_c))
         if _is_sparse(A) or _is_masked(A):
@@ -118,26 +141,7 @@ class _Base:
         if not hasattr(ops, "is_update_w") or A.dtype not in getattr(ops, "is_dtypes", ()):
             raise NotImplementedError("norm='is' runs on float32 data with the product's fp32 operator set; not provided for %s data with "
                                       "the '%s' operator set" % (str(A.dtype).replace("torch.", ""), getattr(ops, "name", "?")))
-        W, H = self.W_i, self.H_j
-        m_l, n_l = A.shape
-        if W_update:
-            if self.p_c == 1:                                      # this rank's W rows see all their columns: the pass writes W
-                ops.is_update_w(A, W, H, eps)
-            else:
-                buf = _buf(("isnd_w", m_l, k), 2 * m_l * k, A)[: 2 * m_l * k]
-                num, den = ops.is_aht_pair(A, W, H, eps, buf)
-                self.comm1.allreduce_(buf)
-                ops.is_ratio_update(W, num, den, eps)
-        if self.p_r == 1:
-            ops.is_update_h(A, W, H, eps, clamp)
-        else:
-            buf = _buf(("isnd_h", k, n_l), 2 * k * n_l, A)[: 2 * k * n_l]
-            num, den = ops.is_wta_pair(A, W, H, eps, buf)
-            self.comm1.allreduce_(buf)
-            ops.is_ratio_update(H, num, den, eps, clamp)
-        if clamp:
-            ops.clamp_min(W, eps)
-
+        self._pair_MU_update("isnd", ops.is_update_w, ops.is_update_h, ops.is_aht_pair, ops.is_wta_pair, ops.is_ratio_update, W_update, clamp)
 
     # ---- BCD / Frobenius (dist_nmf.py:940-1047 in 1D, :474-579 in 2D).  The grid-specific pieces are the `_bcd_*` hooks of each
     # class: the exchanges sit exactly where the reference allreduces / gathers.  Every scalar of the method stays in the device state
@@ -305,29 +309,17 @@ class nmf_algorithms_1D(_Base):
         return r
 
     # ---- a block whose unstored entries are missing: the rules of :716-751 (fro) and :806-849 (kl) with every sum over the stored
-    # positions.  Numerator AND denominator then depend on the pattern, so what crosses ranks is the pair [num | den]
+    # positions, as a pair rule (_pair_MU_update) whose operations take `norm`
     def _masked_MU_update(self, norm, W_update=True, clamp=False):
-        ops, A, W, H, eps, k = self.ops, self.A_ij, self.W_i, self.H_j, self.eps, self.k
+        ops = self.ops
         if not hasattr(ops, "masked_update_w"):
-            raise NotImplementedError("missing='%s': the '%s' operator set has no masked operations" % (A.missing, getattr(ops, "name", "?")))
-        m_l, n_l = A.shape
-        if W_update:
-            if self.p_c == 1:                                      # the reference exchanges nothing here: the pass writes W
-                ops.masked_update_w(A, W, H, eps, norm)
-            else:
-                buf = _buf(("mnd_w", m_l, k), 2 * m_l * k, A)[: 2 * m_l * k]
-                num, den = ops.masked_aht_pair(A, W, H, eps, norm, buf)
-                self.comm1.allreduce_(buf)                         # where :707 sums A H^T (fro) / :797 sums U H^T (kl)
-                ops.ratio_update(W, num, den, eps)
-        if self.p_r == 1:
-            ops.masked_update_h(A, W, H, eps, norm, clamp)
-        else:
-            buf = _buf(("mnd_h", k, n_l), 2 * k * n_l, A)[: 2 * k * n_l]
-            num, den = ops.masked_wta_pair(A, W, H, eps, norm, buf)
-            self.comm1.allreduce_(buf)
-            ops.ratio_update(H, num, den, eps, clamp)
-        if clamp:
-            ops.clamp_min(W, eps)
+            raise NotImplementedError("missing='%s': the '%s' operator set has no masked operations" % (self.A_ij.missing, getattr(ops, "name", "?")))
+        self._pair_MU_update("mnd",
+                             lambda A, W, H, eps: ops.masked_update_w(A, W, H, eps, norm),
+                             lambda A, W, H, eps, clamp: ops.masked_update_h(A, W, H, eps, norm, clamp),
+                             lambda A, W, H, eps, buf: ops.masked_aht_pair(A, W, H, eps, norm, buf),
+                             lambda A, W, H, eps, buf: ops.masked_wta_pair(A, W, H, eps, norm, buf),
+                             ops.ratio_update, W_update, clamp)
 
     # ---- Frobenius (dist_nmf.py:716-771)
     def Fro_MU_update(self, W_update=True, clamp=False):

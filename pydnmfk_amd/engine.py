@@ -689,44 +689,72 @@ class HipOps:
     # and R = 1 / (S + eps): num = (A . R . R) F, den = R F (F = H^T / W), X <- X * sqrt(num / (den + eps))
     is_dtypes = (torch.float32,)       # the data types these operations take (PyNMF and the choreography refuse any other by name)
 
-    def _is(self, what, A, W, H, eps, nbytes_fn=None):
-        """the arguments every dnmf_is_* entry point starts with, and the scratch it ends with"""
-        _req(A, "A"); _req(W, "W"); _req(H, "H")
-        m, n = A.shape
+    _is_ranks = "norm='is' with k = %d: the Itakura-Saito kernels serve 1 <= k <= 128"
+
+    # ---- what the dense pair rules share (dnmf_is_* here, dnmf_masked_* in HipMaskedOps; the sparse set uses the last two)
+    @staticmethod
+    def _pair_args(what, T, W, H, eps, nbytes_fn, ranks, mode=(), pair=None):
+        """(A, W, H) checked against each other, the scratch `nbytes_fn` sizes (0: the rank is refused with `ranks`), and the
+        arguments every entry point of a dense pair rule starts with (`mode`: the masked rules' kl) and ends with.  pair = (side,
+        num, den): two views of the side's shape with one leading dimension, appended to the head."""
+        _req(T, "A"); _req(W, "W"); _req(H, "H")
+        m, n = T.shape
         k = W.shape[1]
         if tuple(W.shape) != (m, k) or tuple(H.shape) != (k, n):
-            raise ValueError("%s: shapes A %s, W %s, H %s do not match" % (what, tuple(A.shape), tuple(W.shape), tuple(H.shape)))
-        nbytes = (nbytes_fn or lib.dnmf_is_ws_bytes)(int(m), int(n), int(k))
+            raise ValueError("%s: shapes A %s, W %s, H %s do not match" % (what, tuple(T.shape), tuple(W.shape), tuple(H.shape)))
+        nbytes = nbytes_fn(int(m), int(n), int(k))
         if nbytes == 0:
-            raise NotImplementedError("norm='is' with k = %d: the Itakura-Saito kernels serve 1 <= k <= 128" % k)
-        ws = _scratch(nbytes, A.device)
-        head = (A.data_ptr(), m, n, _ld(A), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), int(k), float(eps))
+            raise NotImplementedError(ranks % k)
+        ws = _scratch(nbytes, T.device)
+        head = (T.data_ptr(), m, n, _ld(T), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), int(k), float(eps)) + tuple(mode)
+        if pair is not None:
+            side, num, den = pair
+            _req(num, "num"); _req(den, "den")
+            want = (m, k) if side == "w" else (k, n)
+            if tuple(num.shape) != want or tuple(den.shape) != want or _ld(num) != _ld(den):
+                raise ValueError("%s: num %s and den %s must both be %s with one leading dimension" % (what, tuple(num.shape), tuple(den.shape), want))
+            head += (num.data_ptr(), den.data_ptr(), _ld(num))
         return head, (ws.data_ptr(), ws.numel(), _stream())
 
-    def _is_pair(self, side, A, W, H, eps, num, den):
-        head, tail = self._is("is pair", A, W, H, eps)
-        _req(num, "num"); _req(den, "den")
-        want = tuple(W.shape) if side == "w" else tuple(H.shape)
-        if tuple(num.shape) != want or tuple(den.shape) != want or _ld(num) != _ld(den):
-            raise ValueError("is pair: num %s and den %s must both be %s with one leading dimension" % (tuple(num.shape), tuple(den.shape), want))
-        fn = lib.dnmf_is_aht_pair if side == "w" else lib.dnmf_is_wta_pair
-        check(fn(*head, num.data_ptr(), den.data_ptr(), _ld(num), *tail))
-        return num, den
+    def _pair_fit(self, what, fit_fn, T, W, H, eps, nbytes_fn, ranks, mode, w_update, itr):
+        """a whole fit under a dense pair rule as one library call: returns the device tensor [1][2] of its two squared norms"""
+        head, tail = self._pair_args(what, T, W, H, eps, nbytes_fn, ranks, mode)
+        sq = torch.empty(1, 2, dtype=torch.float64, device=T.device)
+        check(fit_fn(*head, int(bool(w_update)), int(itr), sq.data_ptr(), *tail))
+        return sq
 
     @staticmethod
-    def _is_halves(buf, shape):
+    def _halves(buf, shape):
+        """[num | den]: the halves of one contiguous buffer (what ONE allreduce carries) as two views of `shape`"""
         r, c = shape
         if buf.numel() < 2 * r * c or not buf.is_contiguous() or buf.dtype != torch.float32:
-            raise ValueError("is pair: a contiguous float32 buffer of 2 x %d x %d elements is expected" % (r, c))
+            raise ValueError("pair buffer: a contiguous float32 buffer of 2 x %d x %d elements is expected" % (r, c))
         return buf[: r * c].view(r, c), buf[r * c: 2 * r * c].view(r, c)
+
+    @staticmethod
+    def _ratio_args(what, X, num, den, eps, clamp):
+        """the arguments of a rule on a stored pair (dnmf_csr_ratio_update, dnmf_is_ratio_update)"""
+        _req(X, "X"); _req(num, "num"); _req(den, "den")
+        if tuple(num.shape) != tuple(X.shape) or tuple(den.shape) != tuple(X.shape) or _ld(num) != _ld(den):
+            raise ValueError("%s: X %s, num %s, den %s" % (what, tuple(X.shape), tuple(num.shape), tuple(den.shape)))
+        r, c = X.shape
+        return X.data_ptr(), r, c, _ld(X), num.data_ptr(), den.data_ptr(), _ld(num), float(eps), int(bool(clamp)), _stream()
+
+    def _is(self, what, A, W, H, eps, pair=None):
+        return self._pair_args(what, A, W, H, eps, lib.dnmf_is_ws_bytes, self._is_ranks, pair=pair)
+
+    def _is_pair(self, side, A, W, H, eps, num, den):
+        head, tail = self._is("is pair", A, W, H, eps, pair=(side, num, den))
+        check((lib.dnmf_is_aht_pair if side == "w" else lib.dnmf_is_wta_pair)(*head, *tail))
+        return num, den
 
     def is_aht_pair(self, A, W, H, eps, buf):
         """buf = [num | den], each m x k: (A . R . R) H^T and R H^T"""
-        return self._is_pair("w", A, W, H, eps, *self._is_halves(buf, tuple(W.shape)))
+        return self._is_pair("w", A, W, H, eps, *self._halves(buf, tuple(W.shape)))
 
     def is_wta_pair(self, A, W, H, eps, buf):
         """buf = [num | den], each k x n: W^T (A . R . R) and W^T R"""
-        return self._is_pair("h", A, W, H, eps, *self._is_halves(buf, tuple(H.shape)))
+        return self._is_pair("h", A, W, H, eps, *self._halves(buf, tuple(H.shape)))
 
     def is_pair_into(self, side, A, W, H, eps, num, den):
         """the same pair into two views of the caller's (one leading dimension, any pitch): side 'w' (m x k) or 'h' (k x n)"""
@@ -746,12 +774,7 @@ class HipOps:
 
     def is_ratio_update(self, X, num, den, eps, clamp=False):
         """X <- X * sqrt(num / (den + eps)), max(., eps) with `clamp`: the rule on a pair that was summed over the ranks"""
-        _req(X, "X"); _req(num, "num"); _req(den, "den")
-        if tuple(num.shape) != tuple(X.shape) or tuple(den.shape) != tuple(X.shape) or _ld(num) != _ld(den):
-            raise ValueError("is_ratio_update: X %s, num %s, den %s" % (tuple(X.shape), tuple(num.shape), tuple(den.shape)))
-        r, c = X.shape
-        check(lib.dnmf_is_ratio_update(X.data_ptr(), r, c, _ld(X), num.data_ptr(), den.data_ptr(), _ld(num), float(eps), int(bool(clamp)),
-                                       _stream()))
+        check(lib.dnmf_is_ratio_update(*self._ratio_args("is_ratio_update", X, num, den, eps, clamp)))
         return X
 
     def is_divergence(self, A, W, H, eps):
@@ -766,10 +789,7 @@ class HipOps:
         """`itr` Itakura-Saito MU steps (clamps after the steps i % 10 == 0), normalize_features and the squared norms of relative_err in
         ONE library call (dnmf_is_mu_fit: the launches of the step loop in its order).  One problem; W, H are updated in place; returns
         the device tensor [1][2] of {sum (A - W H)^2, sum A^2}."""
-        head, tail = self._is("is_fit", A, W, H, eps, lib.dnmf_is_ws_bytes_fit)
-        sq = torch.empty(1, 2, dtype=torch.float64, device=A.device)
-        check(lib.dnmf_is_mu_fit(*head, int(bool(w_update)), int(itr), sq.data_ptr(), *tail))
-        return sq
+        return self._pair_fit("is_fit", lib.dnmf_is_mu_fit, A, W, H, eps, lib.dnmf_is_ws_bytes_fit, self._is_ranks, (), w_update, itr)
 
     def _bcd_fit(self, A3, W3, H3, eps, w_update, itr, sfx, batched):
         """method 'bcd' (dnmf_bcd_fro_fit): float32 data; a stack of B problems is ONE library call in which every launch
@@ -1006,13 +1026,6 @@ class HipCsrOps(HipOps):
         check(lib.dnmf_csr_masked_update(*head, int(bool(clamp)), X.data_ptr(), _ld(X), int(transposed), *tail))
         return X
 
-    @staticmethod
-    def _halves(buf, shape):
-        r, c = shape
-        if buf.numel() < 2 * r * c or not buf.is_contiguous() or buf.dtype != torch.float32:
-            raise ValueError("masked pair: a contiguous float32 buffer of 2 x %d x %d elements is expected" % (r, c))
-        return buf[: r * c].view(r, c), buf[r * c: 2 * r * c].view(r, c)
-
     def masked_aht_pair(self, A, W, H, eps, norm, buf):
         """buf = [num | den], each m x k: A H^T and P(W H) H^T ('fro'), or U H^T and the stored-position row sums of H ('kl')"""
         return self._masked(A, False, W, H, eps, norm, pair=self._halves(buf, tuple(W.shape)))
@@ -1031,14 +1044,7 @@ class HipCsrOps(HipOps):
 
     def ratio_update(self, X, num, den, eps, clamp=False):
         """X <- X * num / (den + eps), max(., eps) with `clamp`: the rule on a pair that was summed over the ranks"""
-        _req(X, "X")
-        _req(num, "num")
-        _req(den, "den")
-        if tuple(num.shape) != tuple(X.shape) or tuple(den.shape) != tuple(X.shape) or _ld(num) != _ld(den):
-            raise ValueError("ratio_update: X %s, num %s, den %s" % (tuple(X.shape), tuple(num.shape), tuple(den.shape)))
-        r, c = X.shape
-        check(lib.dnmf_csr_ratio_update(X.data_ptr(), r, c, _ld(X), num.data_ptr(), den.data_ptr(), _ld(num), float(eps), int(bool(clamp)),
-                                        _stream()))
+        check(lib.dnmf_csr_ratio_update(*self._ratio_args("ratio_update", X, num, den, eps, clamp)))
         return X
 
     def aht(self, A, H, out):
@@ -1184,8 +1190,8 @@ class HipMaskedOps(HipOps):
     name = "hip-masked"
     kl_uht_hblocks = None
     aht_hblocks = None
-    _halves = staticmethod(HipCsrOps._halves)
     ratio_update = HipCsrOps.ratio_update
+    _masked_ranks = "missing='nan' with k = %d: the masked dense kernels serve 1 <= k <= 128"
 
     @staticmethod
     def _blk(A):
@@ -1197,29 +1203,11 @@ class HipMaskedOps(HipOps):
         if str(norm).lower() not in ("fro", "kl"):
             raise ValueError("masked update: norm %r (fro / kl)" % (norm,))
         kl = int(str(norm).lower() == "kl")
-        T = _req(A.tensor, "A")
-        _req(W, "W")
-        _req(H, "H")
-        m, n = T.shape
-        k = W.shape[1]
-        if tuple(W.shape) != (m, k) or tuple(H.shape) != (k, n):
-            raise ValueError("masked update: shapes A %s, W %s, H %s do not match" % (tuple(T.shape), tuple(W.shape), tuple(H.shape)))
-        nbytes = lib.dnmf_masked_ws_bytes(int(m), int(n), int(k))
-        if nbytes == 0:
-            raise NotImplementedError("missing='nan' with k = %d: the masked dense kernels serve 1 <= k <= 128" % k)
-        ws = _scratch(nbytes, T.device)
-        head = (T.data_ptr(), m, n, _ld(T), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), int(k), float(eps), kl)
-        tail = (ws.data_ptr(), ws.numel(), _stream())
-        if X is None:
-            num, den = pair
-            _req(num, "num")
-            _req(den, "den")
-            want = (m, k) if side == "w" else (k, n)
-            if tuple(num.shape) != want or tuple(den.shape) != want or _ld(num) != _ld(den):
-                raise ValueError("masked pair: num %s and den %s must both be %s with one leading dimension" % (tuple(num.shape), tuple(den.shape), want))
-            fn = lib.dnmf_masked_aht_pair if side == "w" else lib.dnmf_masked_wta_pair
-            check(fn(*head, num.data_ptr(), den.data_ptr(), _ld(num), *tail))
-            return num, den
+        head, tail = self._pair_args("masked update" if pair is None else "masked pair", A.tensor, W, H, eps, lib.dnmf_masked_ws_bytes,
+                                     self._masked_ranks, (kl,), pair=None if pair is None else (side,) + tuple(pair))
+        if pair is not None:
+            check((lib.dnmf_masked_aht_pair if side == "w" else lib.dnmf_masked_wta_pair)(*head, *tail))
+            return pair
         if side == "w":
             check(lib.dnmf_masked_update_w(*head, *tail))
         else:
@@ -1279,18 +1267,9 @@ class HipMaskedOps(HipOps):
         gives (0, 0)).  A plain tensor takes the dense kernel."""
         if not self._blk(A):
             return super().column_err_sums(A, W, H)
-        T = _req(A.tensor, "A"); _req(W, "W"); _req(H, "H")
-        m, n = T.shape
-        k = W.shape[1]
-        if tuple(W.shape) != (m, k) or tuple(H.shape) != (k, n):
-            raise ValueError("masked column_err_sums: shapes A %s, W %s, H %s do not match" % (tuple(T.shape), tuple(W.shape), tuple(H.shape)))
-        nbytes = lib.dnmf_masked_column_err_ws_bytes(int(m), int(n), int(k))
-        if nbytes == 0:
-            raise NotImplementedError("missing='nan' with k = %d: the masked dense kernels serve 1 <= k <= 128" % k)
-        ws = _scratch(nbytes, T.device)
-        out = torch.empty(2, n, dtype=torch.float64, device=T.device)
-        check(lib.dnmf_masked_column_err(T.data_ptr(), m, n, _ld(T), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), int(k), out[0].data_ptr(),
-                                         out[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        head, tail = self._pair_args("masked column_err_sums", A.tensor, W, H, 0.0, lib.dnmf_masked_column_err_ws_bytes, self._masked_ranks)
+        out = torch.empty(2, A.tensor.shape[1], dtype=torch.float64, device=A.tensor.device)
+        check(lib.dnmf_masked_column_err(*head[:-1], out[0].data_ptr(), out[1].data_ptr(), *tail))      # (this entry point takes no eps)
         return out[0], out[1]
 
     def fit(self, method, norm, A, W, H, eps, w_update, itr, column_sweep=False):
@@ -1302,19 +1281,8 @@ class HipMaskedOps(HipOps):
         method, norm = str(method).lower(), str(norm).lower()
         if method != "mu" or norm not in ("fro", "kl"):
             raise NotImplementedError("missing='nan' is provided for method 'mu' (fro / kl) only, not for '%s' / '%s'" % (method, norm))
-        T = _req(A.tensor, "A"); _req(W, "W"); _req(H, "H")
-        m, n = T.shape
-        k = W.shape[1]
-        if tuple(W.shape) != (m, k) or tuple(H.shape) != (k, n):
-            raise ValueError("masked fit: shapes A %s, W %s, H %s do not match" % (tuple(T.shape), tuple(W.shape), tuple(H.shape)))
-        nbytes = lib.dnmf_masked_ws_bytes_fit(int(m), int(n), int(k))
-        if nbytes == 0:
-            raise NotImplementedError("missing='nan' with k = %d: the masked dense kernels serve 1 <= k <= 128" % k)
-        ws = _scratch(nbytes, T.device)
-        sq = torch.empty(1, 2, dtype=torch.float64, device=T.device)
-        check(lib.dnmf_masked_mu_fit(T.data_ptr(), m, n, _ld(T), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), int(k), float(eps),
-                                     int(norm == "kl"), int(bool(w_update)), int(itr), sq.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
-        return sq
+        return self._pair_fit("masked fit", lib.dnmf_masked_mu_fit, A.tensor, W, H, eps, lib.dnmf_masked_ws_bytes_fit, self._masked_ranks,
+                              (int(norm == "kl"),), w_update, itr)
 
     def _refuse(self, what, A):
         if self._blk(A):
