@@ -937,6 +937,19 @@ int dnmf_is_ratio_update(float* X, long rows, long cols, long ldx, const float* 
  * slot of `ws` and the slots added in a fixed order: two calls are bit-identical.  Parallels the residual of pyDNMF.py:205-218. */
 int dnmf_is_divergence(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,
                        double* out, void* ws, size_t ws_bytes, void* stream);
+/* div[c] (float64, c < n) = sum_i (q - log q - 1), q = a / (s + eps), over this rank's rows: the divergence above column by column.
+ * No counterpart in the reference; it stands where PyNMF.column_err (pyDNMF.py:221-239) stands in an NMFk sweep (pyDNMFk.py:248) when
+ * the objective is Itakura-Saito -- divided by the global row count it is a mean per entry, scale-invariant across columns.  The
+ * structure of dnmf_masked_column_err: S tiles in MFMA accumulators, fp32 over the 16 rows a lane holds of a 32-row block, float64
+ * from there on; every row chunk leaves one float64 per column in `ws`, an ending adds them in chunk order and STORES div (nothing
+ * is accumulated into it, no atomics: two calls are bit-identical).  1 <= k <= DNMF_TUNED_MAX_K; any shape and leading dimensions.
+ * `ws`: dnmf_is_column_div_ws_bytes(m, n, k) bytes, 16-byte aligned (0: bad shape or rank). */
+size_t dnmf_is_column_div_ws_bytes(long m, long n, int k);
+/* Its launch plan, host arithmetic only: out = {rowblks_per_chunk, nchunks, ncolblk} with the values of dnmf_masked_column_err_plan;
+ * the slab takes nchunks * ncolblk * 128 doubles (one per chunk and column, not a pair). */
+int dnmf_is_column_div_plan(long m, long n, int k, long out[3]);
+int dnmf_is_column_div(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,
+                       double* div, void* ws, size_t ws_bytes, void* stream);
 /* A whole Itakura-Saito MU fit on one rank as ONE call (pyDNMF.py:138-182): `itr` steps of dnmf_is_update_w (iff w_update) and
  * dnmf_is_update_h with the clamp of H and then of W at the steps i % 10 == 0 (:155-157, :170-172), normalize_features (:185-194) and
  * sq_out = {||A - W H||^2, ||A||^2} (:205-218: the Frobenius pair, as after dnmf_mu_kl_fit; the caller takes the square roots).  Host

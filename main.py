@@ -40,7 +40,7 @@ FLAGS = [
     ('fname', str, 'swim', False, 'input file name without extension'),
     ('init', str, 'rand', False, 'factor initialisation: rand / nnsvd'),
     ('itr', int, 5000, False, 'update iterations'),
-    ('norm', str, 'kl', False, 'objective: kl / fro / is (Itakura-Saito: strictly positive float32 data, method mu, 1D grids, k <= 128)'),
+    ('norm', str, 'kl', False, 'objective: kl / fro / is (Itakura-Saito: strictly positive float32 data, method mu, 1D grids, k <= 128; with --process pyDNMFk: uniform sampling, the per-column statistic is the mean divergence per entry)'),
     ('method', str, 'mu', False, 'update rule: mu / hals / bcd (bcd: Frobenius, float32 data)'),
     ('verbose', _flag, False, False, 'print the relative error of every fit'),
     ('results_path', str, 'results/', False, 'output directory'),

@@ -253,6 +253,10 @@ SIGNATURES["dnmf_is_divergence"] = [c_void_p, c_long, c_long, c_long, c_void_p, 
                                     c_void_p]
 SIGNATURES["dnmf_is_mu_fit"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_int, c_int, c_void_p, c_void_p,
                                 c_size_t, c_void_p]
+# the per-column Itakura-Saito divergence (NMFk under norm='is'): A m n lda W ldw H ldh k eps div ws ws_bytes stream
+SIGNATURES["dnmf_is_column_div_ws_bytes"] = [c_long, c_long, c_int]
+SIGNATURES["dnmf_is_column_div_plan"] = [c_long, c_long, c_int, c_void_p]      # out: long[3]
+SIGNATURES["dnmf_is_column_div"] = SIGNATURES["dnmf_is_divergence"]
 # the W phase from a transposed image of A (csrc/dnmf_timg.hip): build A m n lda At ldat stream; bind the same without the stream
 SIGNATURES["dnmf_wimage_bytes"] = [c_long, c_long]
 SIGNATURES["dnmf_wimage_build"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]
@@ -260,7 +264,7 @@ SIGNATURES["dnmf_wimage_bind"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_
 SIGNATURES["dnmf_wimage_unbind"] = []
 SIGNATURES["dnmf_set_wimage"] = [c_int]
 SIGNATURES["dnmf_wimage_plan"] = [c_long, c_long, c_int, c_long, c_int, c_int, c_void_p]      # out: int[6]
-_RESTYPES = {"dnmf_is_ws_bytes": c_size_t, "dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
+_RESTYPES = {"dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
              "dnmf_ws_bytes_1d": c_size_t, "dnmf_ws_bytes_hblocks": c_size_t, "dnmf_ws_bytes_2d": c_size_t,
              "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t, "dnmf_bcd_ws_bytes_fit": c_size_t}
 

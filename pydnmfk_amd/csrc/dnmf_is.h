@@ -8,7 +8,7 @@
 // second products that share their F fragments) with another step -- one v_rcp_f32 and two multiplies per element, no compare: there
 // is no mask.  The pair kernels ARE masked_uht_kernel / masked_wtu_kernel in their third mode (PAIR_IS), launched with the masked
 // launch plans but for two choices at wide shapes and KP = 128 (plan_is_uht / plan_is_wtu in csrc/dnmf_is.hip); this file adds the
-// endings (the square-root form of the ratio) and the divergence.
+// endings (the square-root form of the ratio), the divergence and the divergence per column (what an NMFk sweep compares across k).
 //
 // Padding adds exactly nothing, without inf or 0 * inf.  An A load outside the block returns 0, so u_n = a r r = 0 * r * r there.  A
 // padded column c >= n is a zero column of the staged H tile and a padded row r >= m a zero row of W (the predicated loads), so S = 0,
@@ -98,6 +98,61 @@ __global__ __launch_bounds__(256) void is_div_sum_kernel(const double* __restric
         __syncthreads();
     }
     if (threadIdx.x == 0) out[0] = sh[0];
+}
+
+// ---- per-column divergence, div[c] = sum_i (q - log q - 1) over this block's rows (PyNMF.is_column_divergence: the per-column statistic
+// of an NMFk sweep under norm='is'): masked_colerr_kernel's structure (csrc/dnmf_masked.h) with is_div_kernel's term.  A wave owns a
+// 128-column block and a chunk of 32-row blocks; fp32 over the 16 rows a lane holds of one row block, float64 from there on, one shuffle
+// joins the lane halves.  The chunk's sums go to its own slab row, P[chunk][ldc] with ldc = ncolblk * 128 (every store is inside the
+// slab); is_coldiv_reduce_kernel adds the rows in chunk order and STORES div[c]: no atomics, nothing accumulated into the output.
+// Outside the block the term is SELECTED away (q = 0, log q = -inf there), never multiplied.
+template <int KT, bool FAST>
+__global__ __launch_bounds__(256) void is_coldiv_kernel(NnArgs p, double* __restrict__ P, long ldc, long rowblks_per_chunk) {
+    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long gw = (long)blockIdx.x * 4 + wid;
+    const long nchunks = cdiv(p.nrowblk, rowblks_per_chunk);
+    if (gw >= nchunks * p.ncolblk) return;
+    const long chunk = gw / p.ncolblk, colblk = gw % p.ncolblk;
+    const long col0 = colblk * 128;
+    double dv[4] = {0.0, 0.0, 0.0, 0.0};
+    long rb1 = (chunk + 1) * rowblks_per_chunk;
+    if (rb1 > p.nrowblk) rb1 = p.nrowblk;
+    for (long rb = chunk * rowblks_per_chunk; rb < rb1; ++rb) {
+        const long row0 = rb * 32;
+        f32x16 acc[4];
+        nn_tile<KT, 4, FAST, false>(acc, p.W, p.ldw, p.m, p.k, p.H, p.ldh, p.n, row0, col0, li, h);
+        float pv[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const long row = row0 + crow(r, h);
+            float a[4];
+            load_vec<4, FAST>(a, p.A + row * p.lda, col0 + 4 * li, p.n, row < p.m);
+#pragma unroll
+            for (int ne = 0; ne < 4; ++ne) {
+                const float q = kl_quot(a[ne], acc[ne][r] + p.eps);
+                const float t = (q - 1.f) - logf(q);
+                pv[ne] += (row < p.m && col0 + 4 * li + ne < p.n) ? t : 0.f;
+            }
+        }
+#pragma unroll
+        for (int ne = 0; ne < 4; ++ne) dv[ne] += (double)pv[ne];
+    }
+    double* Pc = P + chunk * ldc + col0 + 4 * li;
+#pragma unroll
+    for (int ne = 0; ne < 4; ++ne) {
+        dv[ne] += __shfl_xor(dv[ne], 32, 64);
+        if (h == 0) Pc[ne] = dv[ne];
+    }
+}
+
+__global__ __launch_bounds__(256) void is_coldiv_reduce_kernel(const double* __restrict__ P, long ldc, long nchunks, long n,
+                                                               double* __restrict__ div) {
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long)gridDim.x * 256) {
+        double a = P[c];
+        for (long s = 1; s < nchunks; ++s) a += P[s * ldc + c];
+        div[c] = a;
+    }
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 // dnmf_is.hip -- C ABI of the Itakura-Saito MU rule on dense strictly positive data: the PAIR_IS mode of the pair launch path of
-// csrc/dnmf_masked.h behind its ABI names, the rule on a stored pair and the divergence (csrc/dnmf_is.h).  A translation unit of its own
+// csrc/dnmf_masked.h behind its ABI names, the rule on a stored pair, the divergence and its per-column form (csrc/dnmf_is.h).  A translation unit of its own
 // (see csrc/dnmf_kl.hip).  Plain launch chains: no workgroup waits for another one; no float atomics in the products or the divergence.
 #include "dnmf_common.h"
 #include "dnmf_host.h"
@@ -90,6 +90,47 @@ int dnmf_is_divergence(const float* A, long m, long n, long lda, const float* W,
     if (int rc = check_launch("is_divergence")) return rc;
     hipLaunchKernelGGL(is_div_sum_kernel, dim3(1), dim3(256), 0, st, (const double*)P, tiles, out);
     return check_launch("is_divergence");
+}
+
+size_t dnmf_is_column_div_ws_bytes(long m, long n, int k) {
+    if (kt_of(k) < 0 || m < 1 || n < 1) return 0;
+    return align256(plan_masked_colerr(m, n, 1).bytes);
+}
+
+// the launch plan of dnmf_is_column_div as numbers (host arithmetic, no GPU): the masked per-column plan
+int dnmf_is_column_div_plan(long m, long n, int k, long out[3]) {
+    REQUIRE(kt_of(k) > 0, "is_column_div_plan: rank k=%d unsupported (1 <= k <= %d for the Itakura-Saito kernels)", k, DNMF_TUNED_MAX_K);
+    REQUIRE(out && m >= 1 && n >= 1, "is_column_div_plan: null pointer or bad shape");
+    const MaskedColerrPlan c = plan_masked_colerr(m, n, 1);
+    out[0] = c.rowblks_per_chunk;       // 32-row blocks a wave walks (the last chunk may hold fewer)
+    out[1] = c.nchunks;
+    out[2] = c.ncolblk;                 // 128-column blocks (the last may be ragged)
+    return DNMF_OK;
+}
+
+int dnmf_is_column_div(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,
+                       double* div, void* ws, size_t ws_bytes, void* stream) {
+    const int kt = kt_of(k);
+    REQUIRE(kt > 0, "is_column_div: rank k=%d unsupported (1 <= k <= %d for the Itakura-Saito kernels)", k, DNMF_TUNED_MAX_K);
+    REQUIRE(A && W && H && div && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n, "is_column_div: null pointer or bad shape");
+    const MaskedColerrPlan c = plan_masked_colerr(m, n, 1);
+    if (!ws || ws_bytes < c.bytes || !aligned16(ws)) return fail(DNMF_EWS, "is_column_div: workspace %zu < %zu bytes", ws_bytes, c.bytes);
+    hipStream_t st = S(stream);
+    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
+    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
+    double* P = (double*)ws;
+    const dim3 grid((unsigned)cdiv(c.nchunks * c.ncolblk, 4)), block(256);
+#define IC_CASE(KT_)                                                                                                         \
+    if (kt == KT_) {                                                                                                         \
+        if (fast) hipLaunchKernelGGL((is_coldiv_kernel<KT_, true>), grid, block, 0, st, a, P, c.ldc, c.rowblks_per_chunk);   \
+        else hipLaunchKernelGGL((is_coldiv_kernel<KT_, false>), grid, block, 0, st, a, P, c.ldc, c.rowblks_per_chunk);       \
+    }
+    IC_CASE(1) IC_CASE(2) IC_CASE(4)
+#undef IC_CASE
+    if (int rc = check_launch("is_column_div")) return rc;
+    hipLaunchKernelGGL(is_coldiv_reduce_kernel, dim3((unsigned)std::min<long>(cdiv(n, 256), 4096)), dim3(256), 0, st, (const double*)P, c.ldc,
+                       c.nchunks, n, div);
+    return check_launch("is_column_div");
 }
 
 // a whole Itakura-Saito fit: the chain of csrc/dnmf_masked.h with the IS steps; its error is the Frobenius pair, as after dnmf_mu_kl_fit

@@ -427,6 +427,22 @@ MaskedWtuPlan plan_masked_wtu(long m, long n, int kt, long min_chunks) {
     return w;
 }
 
+// per-column error: 128-column blocks x row chunks (a wave per chunk and column block).  About two waves per SIMD, and at most 256
+// chunks: the ending adds a column's chunk sums one after another.  `per_col`: float64 sums a chunk leaves per column (the masked
+// error's pair: 2; the Itakura-Saito per-column divergence of csrc/dnmf_is.h: 1)
+struct MaskedColerrPlan { long ncolblk; long ldc; long nrowblk; long rowblks_per_chunk; long nchunks; size_t bytes; };
+MaskedColerrPlan plan_masked_colerr(long m, long n, int per_col = 2) {
+    MaskedColerrPlan c{};
+    c.ncolblk = cdiv(n, 128);
+    c.ldc = c.ncolblk * 128;
+    c.nrowblk = cdiv(m, 32);
+    const long want = std::min<long>(std::max<long>(1, 2048 / c.ncolblk), 256);
+    c.rowblks_per_chunk = std::max<long>(1, cdiv(c.nrowblk, want));
+    c.nchunks = cdiv(c.nrowblk, c.rowblks_per_chunk);
+    c.bytes = (size_t)c.nchunks * per_col * c.ldc * sizeof(double);
+    return c;
+}
+
 template <int MODE> MaskedUhtPlan pair_uht_plan(long m, long n, int kt) { return plan_masked_uht(m, n, kt, PairMode<MODE>::zdim128); }
 template <int MODE> MaskedWtuPlan pair_wtu_plan(long m, long n, int kt) { return plan_masked_wtu(m, n, kt, PairMode<MODE>::min_chunks); }
 

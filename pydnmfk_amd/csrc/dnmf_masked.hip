@@ -7,21 +7,6 @@
 
 namespace {
 
-// per-column error: 128-column blocks x row chunks (a wave per chunk and column block).  About two waves per SIMD, and at most 256
-// chunks: the ending adds a column's chunk pairs one after another
-struct MaskedColerrPlan { long ncolblk; long ldc; long nrowblk; long rowblks_per_chunk; long nchunks; size_t bytes; };
-MaskedColerrPlan plan_masked_colerr(long m, long n) {
-    MaskedColerrPlan c{};
-    c.ncolblk = cdiv(n, 128);
-    c.ldc = c.ncolblk * 128;
-    c.nrowblk = cdiv(m, 32);
-    const long want = std::min<long>(std::max<long>(1, 2048 / c.ncolblk), 256);
-    c.rowblks_per_chunk = std::max<long>(1, cdiv(c.nrowblk, want));
-    c.nchunks = cdiv(c.nrowblk, c.rowblks_per_chunk);
-    c.bytes = (size_t)c.nchunks * 2 * c.ldc * sizeof(double);
-    return c;
-}
-
 // the two masked modes of the one launch path (csrc/dnmf_masked.h), picked by the ABI's `kl`
 int masked_w_side(const char* who, const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
                   float eps, int kl, float* num, float* den, long ldo, float* X, void* ws, size_t ws_bytes, void* stream) {

@@ -785,6 +785,16 @@ class HipOps:
         check(lib.dnmf_is_divergence(*head, out.data_ptr(), *tail))
         return out
 
+    is_nmfk = True                     # PyNMFk looks for this and `is_column_div`: the per-column statistic of a sweep under norm='is'
+
+    def is_column_div(self, A, W, H, eps):
+        """div[c] = sum_i (q - log q - 1), q = A / (W H + eps), over this block's rows: n device doubles, column SUMS (dnmf_is_column_div:
+        stored, not accumulated -- two calls are bit-identical)"""
+        head, tail = self._pair_args("is_column_div", A, W, H, eps, lib.dnmf_is_column_div_ws_bytes, self._is_ranks)
+        out = torch.empty(A.shape[1], dtype=torch.float64, device=A.device)
+        check(lib.dnmf_is_column_div(*head, out.data_ptr(), *tail))
+        return out
+
     def is_fit(self, A, W, H, eps, w_update, itr):
         """`itr` Itakura-Saito MU steps (clamps after the steps i % 10 == 0), normalize_features and the squared norms of relative_err in
         ONE library call (dnmf_is_mu_fit: the launches of the step loop in its order).  One problem; W, H are updated in place; returns
@@ -834,6 +844,7 @@ class HipOpsBf16x6(HipOps):
 
     name = "hip-bf16x6"
     is_dtypes = ()                 # (no split form of the Itakura-Saito pairs)
+    is_nmfk = False                # (nor an NMFk sweep under norm='is')
     kl_uht_hblocks = None          # (no block-column variant of the split kernels: the 2D step concatenates H for them)
     aht_hblocks = None
 

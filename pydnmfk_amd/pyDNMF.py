@@ -23,7 +23,8 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
     Without `params.missing` dense data are not scanned for NaN;
   * `params.norm = 'is'` (or 'itakura-saito'): the Itakura-Saito divergence by the majorisation-minimisation MU rule (csrc/dnmf_is.h;
     no counterpart in the reference) -- strictly positive dense float32 data, method 'mu', 1D grids, k <= 128; on one rank the whole fit
-    is one library call, dnmf_is_mu_fit; `fit()` still returns the Frobenius relative error, `is_divergence()` reports the objective;
+    is one library call, dnmf_is_mu_fit; `fit()` still returns the Frobenius relative error, `is_divergence()` reports the objective and
+    `is_column_divergence()` its mean per entry column by column (the per-column statistic of PyNMFk under this norm);
   * `prune=True` (the reference's default when the attribute is absent) drops all-zero rows / columns before the
     iterations and scatters the factors back afterwards.  numpy callers get float64 factors back in that case, exactly
     as from the reference (its unprune scatters into np.zeros, utils.py:195,198); tensor callers keep float32 on the GPU.
@@ -225,34 +226,42 @@ class PyNMF:
         """What is refused under norm='is', each by name (dense float32 data without missing entries, fp32 arithmetic, method 'mu', 1D
         grids, k <= 128), and the one thing the data must be: strictly positive.  The ranks agree on that verdict through comm1 BEFORE
         any of them raises, so none is left alone in a later collective."""
-        params = self.params
+        self._is_refusals(self.params, self._sparse, missing, self.a_dtype, self.ops, self.method, self.p_r, self.p_c, self.params.k)
+        self._is_positive(float(self.A_ij.min()) if self.A_ij.numel() else 1.0, self.comm1, self.p_r * self.p_c)
+
+    @staticmethod
+    def _is_refusals(params, sparse, missing, a_dtype, ops, method, p_r, p_c, k):
+        """the refusals of norm='is' that need no look at the data (PyNMFk raises them at construction, with its largest rank as k)"""
         if missing is not None:
             raise NotImplementedError("norm='is' with missing='%s' is not provided (dense data without missing entries only)" % missing)
-        if self._sparse:
+        if sparse:
             raise NotImplementedError("norm='is' is not provided for sparse data: the Itakura-Saito divergence is infinite at a zero "
                                       "entry (dense strictly positive float32 data only)")
-        if self.a_dtype == torch.bfloat16:
+        if a_dtype == torch.bfloat16:
             raise NotImplementedError("norm='is' with bfloat16 storage of the data is not provided (float32 data only)")
         if (getattr(params, "gemm", None) or "fp32") != "fp32":
             raise NotImplementedError("norm='is' with --gemm %s is not provided (fp32 arithmetic only)" % params.gemm)
         # (an operator set names the data types its Itakura-Saito operations take, `is_dtypes`: the HIP kernels are float32)
-        if self.a_dtype not in (getattr(self.ops, "is_dtypes", ()) if self.ops is not None else (torch.float32,)):
+        if a_dtype not in (getattr(ops, "is_dtypes", ()) if ops is not None else (torch.float32,)):
             raise NotImplementedError("norm='is' with %s data is not provided (float32 data only); cast the block to float32"
-                                      % str(self.a_dtype).replace("torch.", ""))
-        method = str(self.method).lower()
+                                      % str(a_dtype).replace("torch.", ""))
+        method = str(method).lower()
         if method != "mu":
             raise NotImplementedError("norm='is' is provided for method 'mu' only, not for '%s': HALS and BCD are Frobenius methods" % method)
-        if self.p_r != 1 and self.p_c != 1:
+        if p_r != 1 and p_c != 1:
             raise NotImplementedError("norm='is' on a 2D grid (%d x %d) is not provided: use a 1D grid (p_r = 1 or p_c = 1)"
-                                      % (self.p_r, self.p_c))
-        if self.params.k > 128:
-            raise NotImplementedError("norm='is' with k = %d is not provided: the Itakura-Saito kernels serve 1 <= k <= 128" % self.params.k)
-        lo = float(self.A_ij.min()) if self.A_ij.numel() else 1.0
+                                      % (p_r, p_c))
+        if k > 128:
+            raise NotImplementedError("norm='is' with k = %d is not provided: the Itakura-Saito kernels serve 1 <= k <= 128" % k)
+
+    @staticmethod
+    def _is_positive(lo, comm1, nranks):
+        """`lo`: the smallest entry of this rank's block; every rank raises when any rank holds an entry <= 0"""
         bad = not lo > 0.0                                          # (a NaN minimum is refused as well)
-        nbad = int(self.comm1.allreduce(1 if bad else 0))
+        nbad = int(comm1.allreduce(1 if bad else 0))
         if nbad:
             raise ValueError("norm='is' needs strictly positive data: the smallest entry of this rank's block is %g (%d of %d ranks hold "
-                             "an entry <= 0); the Itakura-Saito divergence is infinite there" % (lo, nbad, self.p_r * self.p_c))
+                             "an entry <= 0); the Itakura-Saito divergence is infinite there" % (lo, nbad, nranks))
 
     @staticmethod
     def _sparse_checks(A_ij, params):
@@ -561,6 +570,32 @@ class PyNMF:
         d = self._ops().is_divergence(self.A_ij, W.contiguous(), H.contiguous(), self.eps)
         self.comm1.allreduce_(d)
         return float(d.cpu())
+
+    def is_column_divergence(self):
+        """The Itakura-Saito divergence of the CURRENT factors column by column, over the GLOBAL n columns, each divided by the global row
+        count `params.m`: a mean per entry, scale-invariant (a column's scale cancels in q = A / (W H + eps)) and comparable across k.
+        What an NMFk sweep under norm='is' takes where the Frobenius `column_err()` stands (which weights the columns by their scale);
+        `column_err()` itself is unchanged under every norm.  Its scheme: each rank fills its own column range with its sums over its own
+        rows, one float64 allreduce (row shards add partial sums, column shards fill disjoint ranges), then the division."""
+        if not self._is:
+            raise ValueError("is_column_divergence: this fit runs norm='%s'; the divergence is reported under norm='is'" % self.norm)
+        from .utils import determine_block_params
+        blk = determine_block_params(self.comm1, (self.p_r, self.p_c), (self.params.m, self.params.n))
+        c0 = blk.determine_block_index_range_asymm()[0][1]
+        ncol = blk.determine_block_shape_asymm()[1]
+        W, H = self.W_i, self.H_j
+        if W.shape[0] != self.A_ij.shape[0] or H.shape[1] != self.A_ij.shape[1]:   # factors were un-pruned by fit()
+            W = W[self.params.row_zero_idx_x] if W.shape[0] != self.A_ij.shape[0] else W
+            H = H[:, self.params.col_zero_idx_x] if H.shape[1] != self.A_ij.shape[1] else H
+        div = self._ops().is_column_div(self.A_ij, W.contiguous(), H.contiguous(), self.eps)
+        col = torch.zeros(self.params.n, dtype=torch.float64, device=div.device)
+        keep = getattr(self.params, "col_zero_idx_x", None) if self.prune else None
+        if keep is not None and int(keep.numel()) == ncol and div.numel() != ncol:
+            col[c0:c0 + ncol][keep] = div               # (strictly positive data leave nothing to prune: column_err's scheme all the same)
+        else:
+            col[c0:c0 + ncol] = div
+        self.comm1.allreduce_(col)
+        return (col / float(self.params.m)).cpu().numpy()
 
     def column_err(self):
         """pyDNMF.py:221-239: per-column relative error sqrt(sum_i (A - W H)^2 / sum_i A^2) over the GLOBAL n columns

@@ -13,6 +13,10 @@ default) stacks the perturbations' H matrices as Hall[:, :, p] = H_p; the defaul
 vstack + C-order reshape (pyDNMFk.py:236-237), whose fibres mix perturbations -- it only seeds the regression fit.
 Sparse input is swept as a SparseBlock (`SparseSweep`); dense float32 input with `params.missing = 'nan'` is swept as it is, NaN = not
 observed: the raw array is kept, every perturbed copy keeps its NaNs, and the per-column error runs over the observed positions.
+`params.norm = 'is'` (strictly positive dense float32 data, 'uniform' sampling -- multiplicative noise, the noise the Itakura-Saito
+divergence is the likelihood of --, what PyNMF refuses under the norm is refused at construction): the per-column statistic `L_err` is
+the mean divergence per entry of each column (PyNMF.is_column_divergence) instead of the scale-dependent Frobenius column error, and the
+statistics gain 'is_div' (per perturbation) and 'avgDiv'; recon_err, avgErr and AIC keep their Frobenius definitions.
 """
 import os
 
@@ -171,11 +175,21 @@ class PyNMFk:
     def __init__(self, A_ij, factors=None, params=None, ops=None):
         from .sparse import is_sparse_input
         self._sparse = is_sparse_input(A_ij)
-        if str(getattr(params, "norm", None)).lower() in ("is", "itakura-saito"):
-            raise NotImplementedError("PyNMFk with norm='is' is not provided: rank estimation under the Itakura-Saito objective (a "
-                                      "perturbation model and a per-column error for it) is not built (PyNMF factorises at a given k)")
+        self._is = str(getattr(params, "norm", None)).lower() in ("is", "itakura-saito")
+        if self._is:
+            # the sweep asks one operation beyond a fit: the per-column divergence (the 'uniform' perturbation is multiplicative noise,
+            # which is the noise the Itakura-Saito divergence is the likelihood of, and keeps positive data positive)
+            params.norm = 'is'
+            if ops is None:
+                from .engine import HIP_OPS as opset
+            else:
+                opset = ops
+            if not (getattr(opset, "is_nmfk", False) and hasattr(opset, "is_column_div")):
+                raise NotImplementedError("PyNMFk with norm='is' is not provided by operator set %r: rank estimation under the "
+                                          "Itakura-Saito objective needs a per-column divergence (PyNMF factorises at a given k)"
+                                          % (getattr(opset, "name", type(opset).__name__),))
         self._masked = getattr(params, "missing", None) == "nan" and not self._sparse
-        if self._masked:
+        if self._masked and not self._is:           # (norm='is' refuses missing= and sparse data by name in _is_setup)
             # as for a sparse block, the sweep touches A outside PyNMF.fit in the perturbed copy (NaN stays NaN through the
             # multiplication) and in the per-column error, which must run over the observed positions
             if ops is None:
@@ -186,7 +200,7 @@ class PyNMFk:
                 raise NotImplementedError("PyNMFk with missing='nan' is not provided by operator set %r: rank estimation over NaN-marked "
                                           "data needs a masked per-column error (PyNMF factorises such data at a given k)"
                                           % (getattr(opset, "name", type(opset).__name__),))
-        if self._sparse:
+        if self._sparse and not self._is:
             # the sweep touches A outside PyNMF.fit in two operations: the perturbed copy and the per-column error
             if ops is None:
                 from .engine import HIP_CSR_OPS as opset
@@ -251,10 +265,32 @@ class PyNMFk:
         self.cp = Checkpoint(checkpoint_save=self.params.checkpoint, params=self.params)
         self.stats = {}        # k -> cluster statistics (also written to disk per k)
         self.sweep = None
+        if self._is:
+            self._is_setup(A_ij)            # (first: sparse data and missing= are refused in the norm's words)
         if self._sparse:
             self._sparse_setup(A_ij)
         if self._masked:
             self._masked_setup(A_ij)
+
+    def _is_setup(self, A_ij):
+        """norm='is': what PyNMF refuses under it is refused here, at construction, in its words (the sweep's largest rank stands for
+        k), and the data are checked for strict positivity ONCE, before the first fit; every perturbed copy is positive then
+        (1 + nv + 2 nv U > 0).  'poisson' sampling is refused: a draw of 0 makes the divergence infinite."""
+        from .pyDNMF import storage_dtype
+        params = self.params
+        a_dtype = torch.float32 if self._sparse else storage_dtype(A_ij, params)
+        PyNMF._is_refusals(params, self._sparse, getattr(params, "missing", None), a_dtype, self.ops,
+                           var_init(params, 'method', default='mu'), self.p_r, self.p_c, int(self.end_k))
+        if self.sampling == 'poisson':
+            raise NotImplementedError("PyNMFk with norm='is' and sampling='poisson' is not provided: a Poisson draw of 0 makes the "
+                                      "Itakura-Saito divergence infinite (sampling='uniform', multiplicative noise, keeps the data positive)")
+        if self.ops is None:
+            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda:
+                raise TypeError("PyNMFk: A_ij is a CPU tensor; pass a CUDA tensor or a numpy array (no CPU fallback)")
+            if not torch.cuda.is_available():
+                raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
+        lo = float(A_ij.min()) if int(np.prod(A_ij.shape)) else 1.0
+        PyNMF._is_positive(lo, self.comm1, self.p)
 
     def _masked_setup(self, A_ij):
         """missing='nan': the raw array stays `self.A_ij` (every PyNMF wraps its perturbed copy in a MaskedDenseBlock itself); what PyNMF
@@ -321,6 +357,7 @@ class PyNMFk:
         if self.rank == 0:
             os.makedirs(self.params.results_paths, exist_ok=True)
         results = []
+        divs = []                    # norm='is': the total divergence of every perturbation's fit
         if self.rank == 0:
             print('*************Computing for k=', self.k, '************')
         perturbation = 0
@@ -357,11 +394,13 @@ class PyNMFk:
                 fits.append(f)
                 del data
             results.extend(PyNMF.fit_batch(fits))
+            if self._is:
+                divs.extend(f.is_divergence() for f in fits)
             for perturbation in chunk:
                 self.cp._save_checkpoint(self.params.flag, perturbation, self.k)
             del fits, stack
         if shared:
-            results = self._gather_fits(results, mine)
+            results, divs = self._gather_fits(results, mine, divs if self._is else None)
             perturbation = self.perturbations - 1
         self.params.flag = 1
         self.cp._save_checkpoint(self.params.flag, perturbation, self.k)
@@ -402,13 +441,18 @@ class PyNMFk:
         f0 = [_np(self.AvgW), _np(self.AvgH)] if numpy_io else [self.AvgW, self.AvgH]
         regressH = PyNMF(self.A_ij, factors=f0, params=self.params, ops=self.ops)
         self.AvgW, self.AvgH, self.L_errDist = regressH.fit()                                           # :246-247
-        self.col_err = regressH.column_err()                                                            # :248
+        # :248.  Under norm='is' the per-column statistic is the mean Itakura-Saito divergence per entry: the Frobenius column_err
+        # weights the columns by their scale, which is what a user who chose this norm wanted to avoid
+        self.col_err = regressH.is_column_divergence() if self._is else regressH.column_err()
         self.avgErr = float(np.mean(self.recon_err))
         mn = self.params.m * self.params.n      # (sparse data too, under both meanings of an unstored entry, and NaN-marked data: DESIGN.md section 7)
         self.AIC = 2 * self.k + mn * np.log(self.avgErr / mn)                                           # :250
         cluster_stats = {'clusterSilhouetteCoefficients': self.clusterSilhouetteCoefficients,
                          'avgSilhouetteCoefficients': self.avgSilhouetteCoefficients, 'L_errDist': self.L_errDist,
                          'L_err': self.col_err, 'avgErr': self.avgErr, 'recon_err': self.recon_err, 'AIC': self.AIC}
+        if self._is:                            # (recon_err, avgErr and AIC keep their Frobenius definitions)
+            self.is_div = [float(d) for d in divs]
+            cluster_stats['is_div'], cluster_stats['avgDiv'] = self.is_div, float(np.mean(self.is_div))
         self.stats[self.k] = cluster_stats
         if getattr(self.params, "ftype", None) is None:
             self.params.ftype = None
@@ -419,9 +463,10 @@ class PyNMFk:
         self.params.flag = 3
         self.cp._save_checkpoint(self.params.flag, perturbation, self.k)
 
-    def _gather_fits(self, results, mine):
+    def _gather_fits(self, results, mine, divs=None):
         """Perturbation-shared sweep: every rank has fitted its own perturbations; all ranks end with all (W, H, err) in
-        perturbation order.  One allgather of the stacked factors per k (ranks with one perturbation fewer pad their stack)."""
+        perturbation order.  One allgather of the stacked factors per k (ranks with one perturbation fewer pad their stack).
+        `divs` (norm='is'): this rank's divergences, carried as the errors are.  Returns (fits, divergences or None)."""
         world, P = self.world, self.perturbations
         numpy_io = bool(results) and not isinstance(results[0][0], torch.Tensor)
         dev = torch.device("cuda", torch.cuda.current_device()) if (self.ops is None and torch.cuda.is_available()) else torch.device("cpu")
@@ -444,19 +489,24 @@ class PyNMFk:
         allW = world.allgather_blocks(Ws, [tuple(Ws.shape)] * world.size)
         allH = world.allgather_blocks(Hs, [tuple(Hs.shape)] * world.size)
         allE = world.allgather_blocks(errs, [tuple(errs.shape)] * world.size)
+        if divs is not None:
+            dv = torch.zeros(per, dtype=torch.float64, device=dev)
+            for i, d in enumerate(divs):
+                dv[i] = float(d)
+            allD = world.allgather_blocks(dv, [tuple(dv.shape)] * world.size)
         out = []
         for p in range(P):
             r, i = p % world.size, p // world.size
             W, H, e = allW[r][i], allH[r][i], float(allE[r][i])
             out.append((W.cpu().numpy(), H.cpu().numpy(), e) if numpy_io else (W, H, e))
-        return out
+        return out, (None if divs is None else [float(allD[p % world.size][p // world.size]) for p in range(P)])
 
     def _batch_size(self):
         """How many perturbation fits run together (PyNMF.fit_batch): all of them on one rank with the product's own
         operators -- as many as fit next to each other in the GPU's free memory (each holds its perturbed copy of the data) --
         else 1.  `params.nmfk_batch` = False / 0 / 1 keeps the one-by-one fits, an integer caps the batch."""
         want = getattr(self.params, "nmfk_batch", True)
-        if self._sparse or self._masked:          # no batched sparse or masked entry point: the fits run one by one, no stack is allocated
+        if self._sparse or self._masked or self._is:          # no batched sparse, masked or Itakura-Saito entry point: the fits run one by one, no stack is allocated
             return 1
         if want is False or self.p != 1 or self.ops is not None or not torch.cuda.is_available():
             return 1

@@ -5,7 +5,8 @@
 One MI355X; 32768 x 16384 at k = 5, 32, 64, 128 and 65536 x 4096 at k = 64; A uniform in [0.05, 1.05), factors uniform.  A step is
 one `nmf_algorithms_1D(...).update()` on one rank (both factors, the fused endings).  The two steps are timed back to back -- IS,
 then KL, `--steps` times after `--warmup` of each -- every step with its own pair of HIP events; the figures are medians (min / max
-next to them).  The two sides of the IS step are timed on their own as well.  By arithmetic an IS side is 6 m n k flop against KL's
+next to them).  The two sides of the IS step, the divergence and the per-column divergence of an NMFk sweep (dnmf_is_column_div,
+once per k of a sweep) are timed on their own as well.  By arithmetic an IS side is 6 m n k flop against KL's
 4 m n k on the same bytes: the figure to hold the ratio against is 1.5 where the fp32 MFMA bounds the step and 1 at k <= 16.
 """
 import argparse
@@ -50,6 +51,7 @@ def bench(m, n, k, steps, warmup, seed=0):
         "is_update_w": lambda: HIP_OPS.is_update_w(A, W, H, EPS),
         "is_update_h": lambda: HIP_OPS.is_update_h(A, W, H, EPS),
         "is_divergence": lambda: HIP_OPS.is_divergence(A, W, H, EPS),
+        "is_column_div": lambda: HIP_OPS.is_column_div(A, W, H, EPS),
     }
     for _ in range(warmup):
         for fn in fns.values():
@@ -77,14 +79,14 @@ def main():
     torch.cuda.set_device(0)
     shapes = (tuple(int(x) for x in opt.only.split(",")),) if opt.only else SHAPES
     rows = [bench(m, n, k, opt.steps, opt.warmup) for m, n, k in shapes]
-    print("| m x n | k | IS step ms (min-max) | KL step ms (min-max) | IS / KL | IS W side ms | IS H side ms | divergence ms | "
+    print("| m x n | k | IS step ms (min-max) | KL step ms (min-max) | IS / KL | IS W side ms | IS H side ms | divergence ms | per-column divergence ms | "
           "IS step, padded-rank TFLOP/s |")
-    print("|---|---|---|---|---|---|---|---|---|")
+    print("|---|---|---|---|---|---|---|---|---|---|")
     for r in rows:
         t = lambda key: "%.3f (%.3f-%.3f)" % (r[key]["median_ms"], r[key]["min_ms"], r[key]["max_ms"])      # noqa: E731
-        print("| %d x %d | %d | %s | %s | %.2f | %.3f | %.3f | %.3f | %.1f |" % (
+        print("| %d x %d | %d | %s | %s | %.2f | %.3f | %.3f | %.3f | %.3f | %.1f |" % (
             r["m"], r["n"], r["k"], t("is_step"), t("kl_step"), r["ratio_is_over_kl"], r["is_update_w"]["median_ms"],
-            r["is_update_h"]["median_ms"], r["is_divergence"]["median_ms"], r["is_tflops"]))
+            r["is_update_h"]["median_ms"], r["is_divergence"]["median_ms"], r["is_column_div"]["median_ms"], r["is_tflops"]))
     if opt.json:
         os.makedirs(os.path.dirname(os.path.abspath(opt.json)), exist_ok=True)
         with open(opt.json, "w") as f:
