@@ -86,7 +86,7 @@ SIGNATURES["dnmf_kl_uht_bf16x6"] = SIGNATURES["dnmf_kl_uht"]
 SIGNATURES["dnmf_kl_wtu_bf16x6"] = SIGNATURES["dnmf_kl_wtu"]
 SIGNATURES["dnmf_mu_kl_step_bf16x6"] = SIGNATURES["dnmf_mu_kl_step"]
 SIGNATURES["dnmf_bf16x6_plan"] = [c_long, c_long, c_int, c_long, c_int, c_int, c_void_p]      # m n k lda a_bf16 a_aligned16 out: long[12]
-# grid exchanges inside the library (csrc/dnmf_comm.hip); the communicator handle is an opaque pointer
+# grid exchanges inside the library (csrc/dnmf_comm.hip; the whole steps: csrc/dnmf_grid.hip); the communicator handle is an opaque pointer
 SIGNATURES["dnmf_comm_unique_id"] = [c_void_p]
 SIGNATURES["dnmf_comm_create"] = [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]
 COLLECTIVE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p)   # dnmf_collective_fn

@@ -1,17 +1,13 @@
-// dnmf_comm.hip -- the grid exchanges INSIDE the library: RCCL communicators for the p_r x p_c grid (dist_comm.py:16-56) and
-// whole 1D steps that enqueue  kernels -> ncclAllReduce -> kernels  on the caller's stream with no host code in between
-// (dist_nmf.py:663-771 Frobenius, :776-869 KL).  A host that is not PyTorch (the reference's mpi4py driver)
-// gets the packed single allreduce and the overlapped H phase through these entry points; the PyTorch host can use them
-// instead of torch.distributed (params.exchange = 'native').
+// dnmf_comm.hip -- the grid exchanges INSIDE the library: RCCL communicators for the p_r x p_c grid (dist_comm.py:16-56), the direct
+// two-shot allreduce over IPC peer buffers, the collectives over the groups of the grid and the cross-rank HALS W sweep -- what the
+// library-sequenced steps of csrc/dnmf_grid.hip enqueue between their kernels (csrc/dnmf_comm.h) -- and the dnmf_comm_* entry points.
 //
 // RCCL is bound at run time (dlopen): the library loads and every compute entry point works on a host without RCCL; the
 // first dnmf_comm_* call looks for an RCCL that is ALREADY in the process (PyTorch's own copy: two RCCL / HIP runtime
 // instances in one process do not share device state) and only then loads librccl.so.1 by name.
 #include <dlfcn.h>
-#include <rccl/rccl.h>
 
-#include "dnmf_common.h"
-#include "dnmf_host.h"
+#include "dnmf_comm.h"
 
 // csrc/dnmf_hals.hip: the persistent W sweep with the column norms summed over the ranks of `pe` (nullptr: applicability check only)
 __attribute__((visibility("hidden"))) int dnmf_hals_sweep_w_peers_(float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G,
@@ -64,53 +60,15 @@ Rccl* rccl() {
     return inst;
 }
 
-constexpr int MAX_CHUNKS = 8;
-
-}  // namespace
-
-struct dnmf_comm {
-    ncclComm_t world = nullptr, row = nullptr, col = nullptr;   // row: the p_r ranks of one grid column; col: the p_c ranks of one grid row
-    int nranks = 1, rank = 0, p_r = 1, p_c = 1;
-    int overlap_chunks = 1;
-    int always = 0;                                              // testing: a one-rank communicator still issues its RCCL calls
-    int null_exchange = 0;                                       // measurement: the steps skip their RCCL calls (wrong results on > 1 rank)
-    dnmf_collective_fn hook = nullptr;                           // host-supplied collectives instead of RCCL (dnmf_comm_create_hosted)
-    void* hook_user = nullptr;
-    hipStream_t xstream = nullptr;                               // exchanges of the overlapped H phase run here
-    hipEvent_t ready[MAX_CHUNKS] = {}, done[MAX_CHUNKS] = {};
-    // direct (two-shot) allreduce over IPC peer buffers (dnmf_comm_direct_*): every rank's region as mapped into this process
-    int direct_on = 0;
-    size_t direct_cap = 0;                                       // floats per message
-    char* direct_peer[DNMF_DIRECT_MAX_RANKS] = {};               // [rank] = the own region
-    unsigned long long direct_seq = 0, direct_small_seq = 0;
-    unsigned long long direct_patience = 30ull * 100000000ull;   // 30 s of the 100 MHz wall clock (dnmf_comm_set_direct_timeout)
-    int emulated = 0;                                            // measurement: ONE member of a p_r x p_c grid, every collective on a one-rank RCCL communicator
-    // cross-rank persistent HALS W sweep over the peer regions (hals_sweep_exchanged): the ranks' agreement for the last shape seen
-    unsigned long long hals_seq = 0;                             // sweeps issued: its parity selects the slot slab
-    long xs_m = -1; int xs_k = -1, xs_ok = 0, xs_first = 0, xs_total = 0;
-    // WHEN the ranks agree again is a function of things every rank sees alike -- the fit counter (dnmf_comm_fit_begin: PyNMF calls it on
-    // every rank at the start of every fit), the rank k, the process-wide persistent switch -- never of a rank's LOCAL row count: with
-    // an asymmetric split two fits of different global m can change the row count on some ranks only, and an agreement
-    // that only those ranks enter is a collective mismatch
-    int xs_epoch = 0, xs_seen_epoch = -1, xs_pers = -1;
-    float* agree_buf = nullptr;                                  // DNMF_DIRECT_MAX_RANKS device floats of the comm's own (the caller's workspace may be absent)
-};
-
-namespace {
-
 int nccl_fail(const char* what, ncclResult_t e) {
     Rccl* r = rccl();
     return fail(DNMF_ECOMM, "%s: RCCL error %d (%s)", what, (int)e, r ? r->GetErrorString(e) : "?");
 }
 #define NCCL_OK(call, what) do { ncclResult_t e_ = (call); if (e_ != ncclSuccess) return nccl_fail(what, e_); } while (0)
-#define HIP_OK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(DNMF_EHIP, "%s: %s", what, hipGetErrorString(e_)); } while (0)
 
-inline size_t pad64(size_t x) { return (x + 63) / 64 * 64; }
-
-// The three collectives of the path over a GROUP of the grid: 0 = all ranks, 1 = cart_1d_row (the p_r ranks of a grid column),
-// 2 = cart_1d_column (the p_c ranks of a grid row) -- dist_comm.py:16-56.  A group of one member is the identity (unless `always`
-// asks a one-rank communicator to issue its calls anyway); a hosted communicator hands every call to the host's function.
-enum { G_WORLD = 0, G_ROW = 1, G_COL = 2 };
+// The three collectives of the path over a GROUP of the grid (G_WORLD / G_ROW / G_COL, csrc/dnmf_comm.h).  A group of one member is
+// the identity (unless `always` asks a one-rank communicator to issue its calls anyway); a hosted communicator hands every call to
+// the host's function.
 enum { OP_ALLREDUCE = DNMF_ALLREDUCE, OP_ALLGATHER = DNMF_ALLGATHER, OP_REDUCE_SCATTER = DNMF_REDUCE_SCATTER };
 
 int group_size(const dnmf_comm* cm, int g) { return g == G_WORLD ? cm->nranks : g == G_ROW ? cm->p_r : cm->p_c; }
@@ -279,8 +237,10 @@ int direct_allreduce_small_f64(dnmf_comm* cm, double* buf, size_t count, hipStre
     return check_launch("allreduce(direct, small)");
 }
 
-// in-place SUM over the group
-int allreduce_f32(dnmf_comm* cm, int g, float* buf, size_t count, hipStream_t st) {
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------- what csrc/dnmf_grid.hip calls (dnmf_comm.h)
+int dnmf_allreduce_f32_(dnmf_comm* cm, int g, float* buf, size_t count, hipStream_t st) {
     if (cm->direct_on && g == G_WORLD && cm->nranks > 1 && !cm->null_exchange && count <= cm->direct_cap && count % 2 == 0 &&
         ((uintptr_t)buf & 7) == 0)
         return direct_allreduce(cm, buf, count, st);
@@ -292,8 +252,7 @@ int allreduce_f32(dnmf_comm* cm, int g, float* buf, size_t count, hipStream_t st
     return DNMF_OK;
 }
 
-// in-place SUM of doubles (the column norms of the HALS W sweep, utils.py:388-391)
-int allreduce_f64(dnmf_comm* cm, int g, double* buf, size_t count, hipStream_t st) {
+int dnmf_allreduce_f64_(dnmf_comm* cm, int g, double* buf, size_t count, hipStream_t st) {
     if (cm->direct_on && g == G_WORLD && cm->nranks > 1 && !cm->null_exchange && count >= 1 && count <= DIRECT_SMALL_MAX)
         return direct_allreduce_small_f64(cm, buf, count, st);
     ncclComm_t c;
@@ -312,8 +271,8 @@ int allreduce_f64(dnmf_comm* cm, int g, double* buf, size_t count, hipStream_t s
 // contributes its workgroup count (0: the persistent sweep does not apply here -- too many rows to keep resident, workspace too
 // small) through a world allreduce; the sweep is on when every rank can and the slots fit a column of the slab.  The counts also
 // give each rank its first slot.  (Host-synchronous, once per shape.)
-int hals_xsweep_agree(dnmf_comm* cm, float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, float eps, void* ws,
-                      size_t ws_bytes, hipStream_t st) {
+static int hals_xsweep_agree(dnmf_comm* cm, float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, float eps, void* ws,
+                             size_t ws_bytes, hipStream_t st) {
     cm->xs_m = m; cm->xs_k = k; cm->xs_ok = 0; cm->xs_seen_epoch = cm->xs_epoch; cm->xs_pers = dnmf_persistent_on_();
     int nwg = 0;
     const bool mine = ws && ws_bytes >= 64 * sizeof(float) &&
@@ -325,7 +284,7 @@ int hals_xsweep_agree(dnmf_comm* cm, float* W, long m, int k, long ldw, const fl
     float* dev = cm->agree_buf;
     HIP_OK(hipMemcpyAsync(dev, host, sizeof(host), hipMemcpyHostToDevice, st), "hals sweep: agreement");
     HIP_OK(hipStreamSynchronize(st), "hals sweep: agreement");
-    if (int rc = allreduce_f32(cm, G_WORLD, dev, DNMF_DIRECT_MAX_RANKS, st)) return rc;
+    if (int rc = dnmf_allreduce_f32_(cm, G_WORLD, dev, DNMF_DIRECT_MAX_RANKS, st)) return rc;
     HIP_OK(hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, st), "hals sweep: agreement");
     HIP_OK(hipStreamSynchronize(st), "hals sweep: agreement");
     int total = 0, first = 0;
@@ -340,8 +299,8 @@ int hals_xsweep_agree(dnmf_comm* cm, float* W, long m, int k, long ldw, const fl
     return DNMF_OK;
 }
 
-int hals_sweep_exchanged(dnmf_comm* cm, float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, float eps,
-                         double* ss2, void* ws, size_t ws_bytes, void* stream, int column_sweep = 0) {
+int dnmf_hals_sweep_exchanged_(dnmf_comm* cm, float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, float eps,
+                               double* ss2, void* ws, size_t ws_bytes, void* stream, int column_sweep) {
     hipStream_t st = S(stream);
     // ONE persistent launch when the direct peer regions are up (dnmf_comm_set_direct) and every rank can keep its rows resident:
     // the column partials cross the ranks through the slot slabs in the exported regions (csrc/dnmf_hals.h, HalsPeers)
@@ -367,13 +326,13 @@ int hals_sweep_exchanged(dnmf_comm* cm, float* W, long m, int k, long ldw, const
     int rc;
     for (int kk = 0; kk < k; ++kk) {
         if ((rc = dnmf_hals_w_col(W, m, k, ldw, AH, ldah, G, kk, kk > 0 ? ss2 + kk - 1 : nullptr, eps, ss2 + kk, stream))) return rc;
-        if ((rc = allreduce_f64(cm, G_WORLD, ss2 + kk, 1, st))) return rc;
+        if ((rc = dnmf_allreduce_f64_(cm, G_WORLD, ss2 + kk, 1, st))) return rc;
     }
     return dnmf_hals_w_scale(W, m, ldw, k - 1, ss2 + k - 1, stream);
 }
 // ... and with local norms: the persistent sweep (or its column form on request)
-int hals_sweep_local(float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, float eps, int column_sweep,
-                     double* ss2, void* ws, size_t kws, void* stream) {
+int dnmf_hals_sweep_local_(float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, float eps, int column_sweep,
+                           double* ss2, void* ws, size_t kws, void* stream) {
     if (column_sweep) {
         HIP_OK(hipMemsetAsync(ss2, 0, (size_t)k * sizeof(double), S(stream)), "hals sweep: memset");
         return dnmf_hals_update_w(W, m, k, ldw, AH, ldah, G, eps, ss2, stream);
@@ -381,8 +340,7 @@ int hals_sweep_local(float* W, long m, int k, long ldw, const float* AH, long ld
     return dnmf_hals_sweep_w(W, m, k, ldw, AH, ldah, G, eps, ws, kws, stream);
 }
 
-// equal blocks of `count` floats: recv[q * count ...] = member q's send (MPI Allgather, dist_nmf.py:163-165, :195-197)
-int allgather_f32(dnmf_comm* cm, int g, const float* send, float* recv, size_t count, hipStream_t st) {
+int dnmf_allgather_f32_(dnmf_comm* cm, int g, const float* send, float* recv, size_t count, hipStream_t st) {
     ncclComm_t c;
     const int r = resolve(cm, g, &c, "allgather");
     if (r < 0) return r;
@@ -398,8 +356,7 @@ int allgather_f32(dnmf_comm* cm, int g, const float* send, float* recv, size_t c
     return DNMF_OK;
 }
 
-// SUM reduce-scatter of members x count floats: recv = this member's block of the sum (MPI Reduce_scatter, :169, :202)
-int reduce_scatter_f32(dnmf_comm* cm, int g, const float* send, float* recv, size_t count, int member, hipStream_t st) {
+int dnmf_reduce_scatter_f32_(dnmf_comm* cm, int g, const float* send, float* recv, size_t count, int member, hipStream_t st) {
     ncclComm_t c;
     const int r = resolve(cm, g, &c, "reduce_scatter");
     if (r < 0) return r;
@@ -412,200 +369,6 @@ int reduce_scatter_f32(dnmf_comm* cm, int g, const float* send, float* recv, siz
     NCCL_OK(rccl()->ReduceScatter(cm->emulated ? send + (size_t)member * count : send, recv, count, ncclFloat32, ncclSum, c, st), "reduce_scatter");
     return DNMF_OK;
 }
-
-// ---- 2D grids: slices of a block over the members of a sub-communicator follow the reference's partition rule (utils.py:36-41):
-// the first total % p members hold one item more
-struct Split {
-    int p; long base, rem;
-    long count(int q) const { return base + (q < rem ? 1 : 0); }
-    long start(int q) const { return (long)q * base + std::min<long>(q, rem); }
-    long maxc() const { return base + (rem > 0 ? 1 : 0); }
-    bool equal() const { return rem == 0; }
-};
-inline Split split_of(long total, int p) { return Split{p, total / p, total % p}; }
-
-// workspace of the 2D steps: kernel scratch | G | the exchange buffers (sized for the padded, ragged form)
-struct Ws2d { size_t g_off, hs_off, hj_off, v_off, vp_off, sw_off, wp_off, wg_off, wi_off, y_off, yb_off, sh_off, x_off, total; };
-Ws2d ws2d_layout(long m_l, long n_l, int k, int p_r, int p_c) {
-    const int kp = 32 * kt_of(k);
-    const Split ws = split_of(m_l, p_c), hs = split_of(n_l, p_r);
-    const long mw = ws.maxc(), nh = hs.maxc();
-    size_t kws = std::max(dnmf_ws_bytes(m_l, n_l, k), dnmf_ws_bytes(m_l, std::max<long>(1, hs.base), k));
-    kws = std::max(kws, dnmf_ws_bytes(ws.maxc(), k, k));            // (the HALS W sweep on the rank's slice)
-    if (hs.equal() && hs.base % 32 == 0) kws = std::max(kws, dnmf_ws_bytes_hblocks(m_l, n_l, k, hs.base));
-    Ws2d w;
-    size_t o = align256(kws);
-    auto take = [&](size_t floats) { const size_t at = o; o += align256(floats * sizeof(float)); return at; };
-    w.g_off = take((size_t)kp * kp);
-    w.hs_off = take((size_t)p_r * k * nh + (size_t)k * nh);     // gathered H slices [p_r][k nh] (+ this rank's padded send block)
-    w.hj_off = take((size_t)k * n_l);                           // H_j assembled (ragged / narrow slices)
-    w.v_off = take((size_t)m_l * k);                            // A H^T or U H^T of the block
-    w.vp_off = take((size_t)p_c * mw * k);                      // ... laid out at the pitch of the largest W slice
-    w.sw_off = take((size_t)mw * k);                            // this rank's slice of the reduced product
-    w.wp_off = take((size_t)mw * k);                            // this rank's W slice, padded
-    w.wg_off = take((size_t)p_c * mw * k);                      // gathered W slices
-    w.wi_off = take((size_t)m_l * k);                           // W_i assembled
-    w.y_off = take((size_t)k * n_l);                            // full-width H-phase product
-    w.yb_off = take((size_t)p_r * k * nh);                      // ... as member blocks
-    w.sh_off = take((size_t)k * nh);
-    w.x_off = take(128 + 2 * DNMF_MAX_K);                          // factor sums; k doubles for the HALS norms
-    w.total = o;
-    return w;
-}
-
-int check_2d(const char* what, const dnmf_comm* c, long m_l, long n_l, long m_w, long n_h, long ldw, long ldh, int k) {
-    if (c->p_r * c->p_c != c->nranks) return fail(DNMF_EINVAL, "%s: communicator grid %d x %d", what, c->p_r, c->p_c);
-    const int i = c->rank / c->p_c, j = c->rank % c->p_c;
-    const Split ws = split_of(m_l, c->p_c), hs = split_of(n_l, c->p_r);
-    if (m_l < c->p_c || n_l < c->p_r || m_w != ws.count(j) || n_h != hs.count(i) || ldw != k || ldh != n_h)
-        return fail(DNMF_EINVAL, "%s: factor slices off the partition rule or strided (A %ld x %ld on %d x %d at (%d, %d): W slice %ld x %d "
-                    "ld %ld, expected %ld rows; H slice %d x %ld ld %ld, expected %ld columns): use the host choreography",
-                    what, m_l, n_l, c->p_r, c->p_c, i, j, m_w, k, ldw, ws.count(j), k, n_h, ldh, hs.count(i));
-    return DNMF_OK;
-}
-
-#define COPY2D(dst, dpitch, src, spitch, width, height, what)                                                                   \
-    HIP_OK(hipMemcpy2DAsync((dst), (size_t)(dpitch) * sizeof(float), (src), (size_t)(spitch) * sizeof(float),                   \
-                            (size_t)(width) * sizeof(float), (size_t)(height), hipMemcpyDeviceToDevice, st), what)
-#define COPY1D(dst, src, count, what) \
-    HIP_OK(hipMemcpyAsync((dst), (src), (size_t)(count) * sizeof(float), hipMemcpyDeviceToDevice, st), what)
-
-// The exchanges of a 2D step, shared by the Frobenius and the KL form.  How H_j reaches the kernels mirrors gather_H /
-// _product_scattered_to_H of pydnmfk_amd/dist_nmf.py exactly (the same kernels on the same operand shapes: same bits):
-//   blocked  equal slices of whole 32-column tiles, p_r > 1: the allgather's receive buffer [p_r][k][n_h] IS the operand
-//   else     H_j (k x n_l) is assembled from the (padded) slices
-//   sliced   equal slices of whole 16-byte vectors: the H-phase product is formed slice by slice into the reduce-scatter's
-//            send buffer; else one full-width product, cut into member blocks at the pitch of the largest slice
-struct Grid2d {
-    dnmf_comm* c; hipStream_t st; int k, i, j; long m_l, n_l, m_w, n_h; Split ws, hs; bool blocked, sliced;
-    char* base; Ws2d L;
-    float* at(size_t off) const { return (float*)(base + off); }
-
-    // H_j from the row group: returns the operand pointer (*hb = leading dimension, or the block width when blocked)
-    int gather_h(const float* H, const float** Hop, long* hb) {
-        float* Hs = at(L.hs_off);
-        const long nh = hs.maxc();
-        int rc;
-        if (c->p_r == 1) { *Hop = H; *hb = n_l; return DNMF_OK; }                                        // (one member: its slice is H_j)
-        if (hs.equal()) {
-            if ((rc = allgather_f32(c, G_ROW, H, Hs, (size_t)k * n_h, st))) return rc;
-            if (blocked) { *Hop = Hs; *hb = n_h; return DNMF_OK; }
-        } else {                                                                                          // ragged: blocks padded to the largest
-            float* mine = Hs + (size_t)c->p_r * k * nh;
-            COPY1D(mine, H, (size_t)k * n_h, "gather_h: pad");
-            if ((rc = allgather_f32(c, G_ROW, mine, Hs, (size_t)k * nh, st))) return rc;
-        }
-        float* Hj = at(L.hj_off);
-        const size_t pitch = hs.equal() ? (size_t)k * n_h : (size_t)k * nh;
-        for (int q = 0; q < c->p_r; ++q)
-            COPY2D(Hj + hs.start(q), n_l, Hs + q * pitch, hs.count(q), hs.count(q), k, "gather_h: assemble");
-        *Hop = Hj; *hb = n_l;
-        return DNMF_OK;
-    }
-    // W_i (m_l x k) from the column group
-    int gather_w(const float* W, const float** Wi_out) {
-        int rc;
-        if (c->p_c == 1) { *Wi_out = W; return DNMF_OK; }
-        float* Wi = at(L.wi_off);
-        if (ws.equal()) {
-            if ((rc = allgather_f32(c, G_COL, W, Wi, (size_t)m_w * k, st))) return rc;
-        } else {
-            float *Wp = at(L.wp_off), *Wg = at(L.wg_off);
-            const size_t pitch = (size_t)ws.maxc() * k;
-            COPY1D(Wp, W, (size_t)m_w * k, "gather_w: pad");
-            if ((rc = allgather_f32(c, G_COL, Wp, Wg, pitch, st))) return rc;
-            for (int q = 0; q < c->p_c; ++q) COPY1D(Wi + ws.start(q) * k, Wg + q * pitch, (size_t)ws.count(q) * k, "gather_w: assemble");
-        }
-        *Wi_out = Wi;
-        return DNMF_OK;
-    }
-    // reduce-scatter of V (m_l x k) over the column group -> this rank's m_w x k slice
-    int scatter_to_w(const float* V, const float** out) {
-        int rc;
-        if (c->p_c == 1) { *out = V; return DNMF_OK; }
-        float* Sw = at(L.sw_off);
-        if (ws.equal()) {
-            if ((rc = reduce_scatter_f32(c, G_COL, V, Sw, (size_t)m_w * k, j, st))) return rc;
-        } else {
-            float* Vp = at(L.vp_off);
-            const size_t pitch = (size_t)ws.maxc() * k;
-            for (int q = 0; q < c->p_c; ++q) COPY1D(Vp + q * pitch, V + ws.start(q) * k, (size_t)ws.count(q) * k, "scatter_to_w: pad");
-            if ((rc = reduce_scatter_f32(c, G_COL, Vp, Sw, pitch, j, st))) return rc;
-        }
-        *out = Sw;
-        return DNMF_OK;
-    }
-    // reduce-scatter of the H-phase product over the row group -> this rank's k x n_h slice.  sliced: Yb holds the member
-    // blocks already; else Y (k x n_l) is cut into blocks at the pitch of the largest slice first.
-    int scatter_to_h(const float* Y, const float** out) {
-        int rc;
-        float *Yb = at(L.yb_off), *Sh = at(L.sh_off);
-        if (c->p_r == 1) { *out = sliced ? Yb : Y; return DNMF_OK; }
-        size_t pitch = (size_t)k * n_h;
-        if (!sliced) {
-            pitch = (size_t)k * hs.maxc();
-            for (int q = 0; q < c->p_r; ++q)
-                COPY2D(Yb + q * pitch, hs.count(q), Y + hs.start(q), n_l, hs.count(q), k, "scatter_to_h: blocks");
-        }
-        if ((rc = reduce_scatter_f32(c, G_ROW, Yb, Sh, pitch, i, st))) return rc;
-        *out = Sh;
-        return DNMF_OK;
-    }
-};
-
-// the entry points that touch A, for fp32 and for bf16-stored A (params.precision = 'bfloat16': Frobenius mu / hals)
-template <typename TA> struct AOps;
-template <> struct AOps<float> {
-    static constexpr bool f32 = true;
-    static int aht(const float* A, long m, long n, long lda, const float* H, int k, long ldh, float* o, long ldo, void* s) { return dnmf_aht(A, m, n, lda, H, k, ldh, o, ldo, s); }
-    static int wta(const float* A, long m, long n, long lda, const float* W, int k, long ldw, float* o, long ldo, void* ws, size_t wb, void* s) { return dnmf_wta(A, m, n, lda, W, k, ldw, o, ldo, ws, wb, s); }
-    static int wta_gram(const float* A, long m, long n, long lda, const float* W, int k, long ldw, float* o, long ldo, float* G, void* ws, size_t wb, void* s) { return dnmf_wta_gram(A, m, n, lda, W, k, ldw, o, ldo, G, ws, wb, s); }
-    static int ahtw(const float* A, long m, long n, long lda, const float* H, int k, long ldh, const float* G, float* W, long ldw, float eps, void* s) { return dnmf_aht_update_w(A, m, n, lda, H, k, ldh, G, W, ldw, eps, s); }
-};
-template <> struct AOps<bf16_t> {
-    static constexpr bool f32 = false;
-    static int aht(const bf16_t* A, long m, long n, long lda, const float* H, int k, long ldh, float* o, long ldo, void* s) { return dnmf_aht_bf16a(A, m, n, lda, H, k, ldh, o, ldo, s); }
-    static int wta(const bf16_t* A, long m, long n, long lda, const float* W, int k, long ldw, float* o, long ldo, void* ws, size_t wb, void* s) { return dnmf_wta_bf16a(A, m, n, lda, W, k, ldw, o, ldo, ws, wb, s); }
-    static int wta_gram(const bf16_t* A, long m, long n, long lda, const float* W, int k, long ldw, float* o, long ldo, float* G, void* ws, size_t wb, void* s) { return dnmf_wta_gram_bf16a(A, m, n, lda, W, k, ldw, o, ldo, G, ws, wb, s); }
-    static int ahtw(const bf16_t* A, long m, long n, long lda, const float* H, int k, long ldh, const float* G, float* W, long ldw, float eps, void* s) { return dnmf_aht_update_w_bf16a(A, m, n, lda, H, k, ldh, G, W, ldw, eps, s); }
-};
-
-int grid2d_init(Grid2d& g, const char* what, dnmf_comm* c, long m_l, long n_l, long m_w, long n_h, long ldw, long ldh, int k,
-                void* ws, size_t ws_bytes, void* stream, bool f32 = true) {
-    int rc;
-    if ((rc = check_2d(what, c, m_l, n_l, m_w, n_h, ldw, ldh, k))) return rc;
-    g.c = c; g.st = S(stream); g.k = k; g.i = c->rank / c->p_c; g.j = c->rank % c->p_c;
-    g.m_l = m_l; g.n_l = n_l; g.m_w = m_w; g.n_h = n_h;
-    g.ws = split_of(m_l, c->p_c); g.hs = split_of(n_l, c->p_r);
-    g.blocked = f32 && c->p_r > 1 && g.hs.equal() && n_h % 32 == 0;   // (bf16-stored A has no column-block form of A H^T)
-    g.sliced = g.hs.equal() && n_h % 4 == 0;
-    g.L = ws2d_layout(m_l, n_l, k, c->p_r, c->p_c);
-    if (ws_bytes < g.L.total) return fail(DNMF_EWS, "%s: workspace %zu < %zu", what, ws_bytes, g.L.total);
-    g.base = (char*)ws;
-    return DNMF_OK;
-}
-
-// workspace of the 1D steps: [kernel scratch of dnmf_ws_bytes | G (KP x KP) | packed exchange buffer]
-struct Ws1d { size_t g_off, x_off, total; };
-Ws1d ws1d_layout(long m_l, long n_l, int k) {
-    const int kp = 32 * kt_of(k);
-    Ws1d w;
-    size_t kws = std::max(dnmf_ws_bytes(m_l, n_l, k), dnmf_ws_bytes(m_l, k, k));   // kernel scratch: the whole block (and the HALS sweep's), every chunk width of the
-    for (int nch = 2; nch <= MAX_CHUNKS; ++nch) {                 // overlapped H phase (the chunking of W^T A depends on the width)
-        const long cw = (cdiv(n_l, nch) + 63) / 64 * 64;
-        if (cw >= n_l) continue;
-        kws = std::max(kws, dnmf_ws_bytes(m_l, cw, k));
-        if (n_l % cw) kws = std::max(kws, dnmf_ws_bytes(m_l, n_l % cw, k));
-    }
-    w.g_off = align256(kws);
-    w.x_off = w.g_off + align256((size_t)kp * kp * sizeof(float));
-    const size_t big = std::max((size_t)k * n_l, (size_t)m_l * k);
-    // one packed message [product | pad | KP x KP] or up to MAX_CHUNKS chunk messages, each padded to 64 floats
-    w.total = w.x_off + align256((pad64(big) + (size_t)MAX_CHUNKS * 64 + (size_t)kp * kp + 128 + 2 * DNMF_MAX_K) * sizeof(float));   // (+ k doubles: HALS norms)
-    return w;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -863,359 +626,7 @@ int dnmf_comm_info(const dnmf_comm_t* c, int* nranks, int* rank, int* p_r, int* 
 
 int dnmf_comm_allreduce(dnmf_comm_t* c, float* buf, size_t count, int group, void* stream) {
     REQUIRE(c && buf && group >= 0 && group <= 2, "comm_allreduce: bad arguments");
-    return allreduce_f32(c, group, buf, count, S(stream));
-}
-
-size_t dnmf_ws_bytes_1d(long m_l, long n_l, int k) {
-    if (kt_of(k) < 0 || m_l < 1 || n_l < 1) return 0;
-    return ws1d_layout(m_l, n_l, k).total;
-}
-
-// One MU / Frobenius step of a rank of a 1D grid (dist_nmf.py:716-771 with the exchanges of :681,:707).  p_c == 1: A and W
-// are row blocks, H is replicated -- the W phase is the fused local kernel, the H phase ONE allreduce of the packed
-// [W^T A (k x n_l) | pad | W^T W (KP x KP)] message (or `overlap_chunks` column chunks: W^T A of chunk c+1 is computed on
-// the caller's stream while chunk c is reduced on the communicator's stream; chunk 0 carries W^T W).  p_r == 1: the mirror
-// image (A and H column blocks, W replicated, [A H^T | H H^T] reduced).
-}  // extern "C"
-namespace {
-template <typename TA>
-int mu_fro_step_1d_impl(const TA* A, long m_l, long n_l, long lda, float* W, long ldw, float* H, long ldh, int k,
-                        float eps, int w_update, int clamp, void* ws, size_t ws_bytes, dnmf_comm_t* c, void* stream) {
-    const int kt = kt_of(k);
-    REQUIRE(kt > 0 && A && W && H && ws && c && m_l >= 1 && n_l >= 1, "mu_fro_step_1d: bad arguments");
-    REQUIRE(c->p_r == 1 || c->p_c == 1, "mu_fro_step_1d: a %d x %d grid is 2D", c->p_r, c->p_c);
-    const int kp = 32 * kt;
-    const Ws1d L = ws1d_layout(m_l, n_l, k);
-    if (ws_bytes < L.total) return fail(DNMF_EWS, "mu_fro_step_1d: workspace %zu < %zu", ws_bytes, L.total);
-    char* base = (char*)ws;
-    const size_t kws = L.g_off;                                   // kernel scratch: [0, g_off)
-    float* G = (float*)(base + L.g_off);
-    float* X = (float*)(base + L.x_off);
-    hipStream_t st = S(stream);
-    int rc;
-    if (w_update) {                                               // Fro_MU_update_W :716-732
-        if (c->p_c == 1) {
-            if ((rc = dnmf_gram_hht(H, k, n_l, ldh, G, ws, kws, stream))) return rc;
-            if ((rc = AOps<TA>::ahtw(A, m_l, n_l, lda, H, k, ldh, G, W, ldw, eps, stream))) return rc;
-        } else {
-            const size_t off = pad64((size_t)m_l * k);
-            float* AH = X; float* Gx = X + off;
-            if ((rc = dnmf_gram_hht(H, k, n_l, ldh, Gx, ws, kws, stream))) return rc;
-            if ((rc = AOps<TA>::aht(A, m_l, n_l, lda, H, k, ldh, AH, k, stream))) return rc;
-            if ((rc = allreduce_f32(c, G_WORLD, X, off + (size_t)kp * kp, st))) return rc;
-            if ((rc = dnmf_mu_update_w(W, m_l, k, ldw, AH, k, Gx, eps, stream))) return rc;
-        }
-    }
-    const bool xr = c->p_r != 1 || c->always;                                 // which axis exchanges (always: a 1 x 1 grid acts as a row grid)
-    int nch = (c->p_c == 1 && xr) ? c->overlap_chunks : 1;                     // Fro_MU_update_H :736-751
-    if (nch > 1 && n_l / 64 < nch) nch = (int)std::max<long>(1, n_l / 64);
-    if (nch <= 1) {
-        const size_t off = pad64((size_t)k * n_l);
-        float* AtW = X; float* Gx = X + off;
-        if ((rc = AOps<TA>::wta_gram(A, m_l, n_l, lda, W, k, ldw, AtW, n_l, Gx, ws, kws, stream))) return rc;
-        if (xr && (rc = allreduce_f32(c, G_WORLD, X, off + (size_t)kp * kp, st))) return rc;
-        if ((rc = dnmf_mu_update_h(H, k, n_l, ldh, AtW, n_l, Gx, eps, clamp, stream))) return rc;
-    } else {
-        const long cw = (cdiv(n_l, nch) + 63) / 64 * 64;          // chunk width: ceil(n_l / nch) rounded up to 64 columns
-        float* Gx = X + pad64((size_t)k * std::min(cw, n_l));
-        if ((rc = dnmf_gram_wtw(W, m_l, k, ldw, Gx, ws, kws, stream))) return rc;
-        size_t off = 0;
-        float* chunk_ptr[MAX_CHUNKS]; long c0s[MAX_CHUNKS], c1s[MAX_CHUNKS];
-        int nq = 0;
-        for (long c0 = 0; c0 < n_l; c0 += cw, ++nq) {
-            const long c1 = std::min(n_l, c0 + cw);
-            const size_t ne = pad64((size_t)k * (c1 - c0));
-            float* AtW = X + off;
-            if ((rc = AOps<TA>::wta(A + c0, m_l, c1 - c0, lda, W, k, ldw, AtW, c1 - c0, ws, kws, stream))) return rc;
-            const size_t span = ne + (nq == 0 ? (size_t)kp * kp : 0);          // chunk 0: [W^T A chunk | W^T W] in one message
-            HIP_OK(hipEventRecord(c->ready[nq], st), "mu_fro_step_1d: event record");
-            HIP_OK(hipStreamWaitEvent(c->xstream, c->ready[nq], 0), "mu_fro_step_1d: stream wait");
-            if ((rc = allreduce_f32(c, G_WORLD, X + off, span, c->xstream))) return rc;
-            HIP_OK(hipEventRecord(c->done[nq], c->xstream), "mu_fro_step_1d: event record");
-            chunk_ptr[nq] = AtW; c0s[nq] = c0; c1s[nq] = c1;
-            off += span;
-        }
-        for (int q = 0; q < nq; ++q) {
-            HIP_OK(hipStreamWaitEvent(st, c->done[q], 0), "mu_fro_step_1d: stream wait");
-            if ((rc = dnmf_mu_update_h(H + c0s[q], k, c1s[q] - c0s[q], ldh, chunk_ptr[q], c1s[q] - c0s[q], Gx, eps, clamp, stream))) return rc;
-        }
-    }
-    if (clamp) return dnmf_clamp_min(W, m_l, k, ldw, eps, stream);
-    return DNMF_OK;
-}
-}  // namespace
-extern "C" {
-int dnmf_mu_fro_step_1d(const float* A, long m_l, long n_l, long lda, float* W, long ldw, float* H, long ldh, int k,
-                        float eps, int w_update, int clamp, void* ws, size_t ws_bytes, dnmf_comm_t* c, void* stream) {
-    return mu_fro_step_1d_impl<float>(A, m_l, n_l, lda, W, ldw, H, ldh, k, eps, w_update, clamp, ws, ws_bytes, c, stream);
-}
-int dnmf_mu_fro_step_1d_bf16a(const void* A, long m_l, long n_l, long lda, float* W, long ldw, float* H, long ldh, int k,
-                              float eps, int w_update, int clamp, void* ws, size_t ws_bytes, dnmf_comm_t* c, void* stream) {
-    return mu_fro_step_1d_impl<bf16_t>((const bf16_t*)A, m_l, n_l, lda, W, ldw, H, ldh, k, eps, w_update, clamp, ws, ws_bytes, c, stream);
-}
-
-// One MU / KL step of a rank of a 1D grid (dist_nmf.py:813-869; exchanges :797,:707): [U H^T | rowsum(H)] is reduced when
-// W is replicated (p_r == 1), [W^T U | colsum(W)] when H is (p_c == 1).
-int dnmf_mu_kl_step_1d(const float* A, long m_l, long n_l, long lda, float* W, long ldw, float* H, long ldh, int k,
-                       float eps, int w_update, int clamp, void* ws, size_t ws_bytes, dnmf_comm_t* c, void* stream) {
-    const int kt = kt_of(k);
-    REQUIRE(kt > 0 && A && W && H && ws && c && m_l >= 1 && n_l >= 1, "mu_kl_step_1d: bad arguments");
-    REQUIRE(c->p_r == 1 || c->p_c == 1, "mu_kl_step_1d: a %d x %d grid is 2D", c->p_r, c->p_c);
-    const Ws1d L = ws1d_layout(m_l, n_l, k);
-    if (ws_bytes < L.total) return fail(DNMF_EWS, "mu_kl_step_1d: workspace %zu < %zu", ws_bytes, L.total);
-    char* base = (char*)ws;
-    const size_t kws = L.g_off;
-    float* X = (float*)(base + L.x_off);
-    hipStream_t st = S(stream);
-    int rc;
-    if (w_update) {                                               // KL_MU_update_W :813-830
-        const size_t off = pad64((size_t)m_l * k);
-        float* UHT = X; float* x2 = X + off;
-        if ((rc = dnmf_rowsum(H, k, n_l, ldh, x2, stream))) return rc;
-        if ((rc = dnmf_kl_uht(A, m_l, n_l, lda, W, ldw, H, ldh, k, eps, UHT, k, ws, kws, stream))) return rc;
-        if (c->p_c != 1 && (rc = allreduce_f32(c, G_WORLD, X, off + (size_t)k, st))) return rc;
-        if ((rc = dnmf_kl_update_w(W, m_l, k, ldw, UHT, k, x2, eps, stream))) return rc;
-    }
-    const size_t off = pad64((size_t)k * n_l);                    // KL_MU_update_H :832-849
-    float* WTU = X; float* x1 = X + off;
-    if ((rc = dnmf_colsum(W, m_l, k, ldw, x1, ws, kws, stream))) return rc;
-    if ((rc = dnmf_kl_wtu(A, m_l, n_l, lda, W, ldw, H, ldh, k, eps, WTU, n_l, ws, kws, stream))) return rc;
-    if ((c->p_r != 1 || c->always) && (rc = allreduce_f32(c, G_WORLD, X, off + (size_t)k, st))) return rc;
-    if ((rc = dnmf_kl_update_h(H, k, n_l, ldh, WTU, n_l, x1, eps, clamp, stream))) return rc;
-    if (clamp) return dnmf_clamp_min(W, m_l, k, ldw, eps, stream);
-    return DNMF_OK;
-}
-
-size_t dnmf_ws_bytes_2d(long m_l, long n_l, int k, int p_r, int p_c) {
-    if (kt_of(k) < 0 || p_r < 1 || p_c < 1 || m_l < p_c || n_l < p_r) return 0;
-    return ws2d_layout(m_l, n_l, k, p_r, p_c).total;
-}
-
-// One MU / Frobenius step of a rank of a p_r x p_c grid (nmf_algorithms_2D.update, dist_nmf.py:207-263 with global_gram :107-117,
-// AH_glob :186-205, ATW_glob :154-172): the rank holds A_ij (m_l x n_l), its slice W_ij (m_w x k) of the grid row's W_i and its
-// slice H_ij (k x n_h) of the grid column's H_j.  Row group = the p_r ranks of its grid column (they share H_j's columns), column
-// group = the p_c ranks of its grid row (they share W_i's rows).
-}  // extern "C"
-namespace {
-template <typename TA>
-int mu_fro_step_2d_impl(const TA* A, long m_l, long n_l, long lda, float* W, long m_w, long ldw, float* H, long n_h, long ldh,
-                        int k, float eps, int w_update, int clamp, void* ws, size_t ws_bytes, dnmf_comm_t* c, void* stream) {
-    const int kt = kt_of(k);
-    REQUIRE(kt > 0 && A && W && H && ws && c && m_l >= 1 && n_l >= 1 && lda >= n_l, "mu_fro_step_2d: bad arguments");
-    Grid2d g;
-    int rc;
-    if ((rc = grid2d_init(g, "mu_fro_step_2d", c, m_l, n_l, m_w, n_h, ldw, ldh, k, ws, ws_bytes, stream, AOps<TA>::f32))) return rc;
-    const int kp = 32 * kt;
-    const size_t kws = g.L.g_off;
-    float *G = g.at(g.L.g_off), *V = g.at(g.L.v_off), *Y = g.at(g.L.y_off), *Yb = g.at(g.L.yb_off);
-    hipStream_t st = g.st;
-    if (w_update) {                                                // Fro_MU_update_W :227-245
-        if ((rc = dnmf_gram_hht(H, k, n_h, ldh, G, ws, kws, stream))) return rc;
-        if ((rc = allreduce_f32(c, G_WORLD, G, (size_t)kp * kp, st))) return rc;                          // global_gram :114
-        const float* Hop; long hb;
-        if ((rc = g.gather_h(H, &Hop, &hb))) return rc;                                                   // AH_glob :195-197
-        if constexpr (AOps<TA>::f32) { if (g.blocked) rc = dnmf_aht_hblocks(A, m_l, n_l, lda, Hop, hb, k, V, k, stream); else rc = AOps<TA>::aht(A, m_l, n_l, lda, Hop, k, hb, V, k, stream); }                 // :198, H as received
-        else rc = AOps<TA>::aht(A, m_l, n_l, lda, Hop, k, hb, V, k, stream);
-        if (rc) return rc;
-        const float* AH;
-        if ((rc = g.scatter_to_w(V, &AH))) return rc;                                                     // :202
-        if ((rc = dnmf_mu_update_w(W, m_w, k, ldw, AH, k, G, eps, stream))) return rc;                    // :244-245
-    }
-    if ((rc = dnmf_gram_wtw(W, m_w, k, ldw, G, ws, kws, stream))) return rc;                              // Fro_MU_update_H :207-225
-    if ((rc = allreduce_f32(c, G_WORLD, G, (size_t)kp * kp, st))) return rc;
-    const float* Wi;
-    if ((rc = g.gather_w(W, &Wi))) return rc;                                                             // ATW_glob :163-165
-    if (g.sliced) {                                                // :166 slice by slice: member q's k x n_h block is contiguous
-        for (int q = 0; q < c->p_r; ++q)
-            if ((rc = AOps<TA>::wta(A + q * n_h, m_l, n_h, lda, Wi, k, k, Yb + (size_t)q * k * n_h, n_h, ws, kws, stream))) return rc;
-    } else if ((rc = AOps<TA>::wta(A, m_l, n_l, lda, Wi, k, k, Y, n_l, ws, kws, stream))) return rc;
-    const float* AtW;
-    if ((rc = g.scatter_to_h(Y, &AtW))) return rc;                                                        // :169-171
-    const long ldatw = (c->p_r == 1 && !g.sliced) ? n_l : n_h;
-    if ((rc = dnmf_mu_update_h(H, k, n_h, ldh, AtW, ldatw, G, eps, clamp, stream))) return rc;            // :224-225
-    if (clamp) return dnmf_clamp_min(W, m_w, k, ldw, eps, stream);
-    return DNMF_OK;
-}
-}  // namespace
-extern "C" {
-int dnmf_mu_fro_step_2d(const float* A, long m_l, long n_l, long lda, float* W, long m_w, long ldw, float* H, long n_h, long ldh,
-                        int k, float eps, int w_update, int clamp, void* ws, size_t ws_bytes, dnmf_comm_t* c, void* stream) {
-    return mu_fro_step_2d_impl<float>(A, m_l, n_l, lda, W, m_w, ldw, H, n_h, ldh, k, eps, w_update, clamp, ws, ws_bytes, c, stream);
-}
-int dnmf_mu_fro_step_2d_bf16a(const void* A, long m_l, long n_l, long lda, float* W, long m_w, long ldw, float* H, long n_h, long ldh,
-                              int k, float eps, int w_update, int clamp, void* ws, size_t ws_bytes, dnmf_comm_t* c, void* stream) {
-    return mu_fro_step_2d_impl<bf16_t>((const bf16_t*)A, m_l, n_l, lda, W, m_w, ldw, H, n_h, ldh, k, eps, w_update, clamp, ws, ws_bytes, c, stream);
-}
-
-// The same for MU / KL (dist_nmf.py:351-407 with sum_axis :346-349, gather_W_H :268-291, UHT_glob :330-343, WTU_glob :294-318)
-int dnmf_mu_kl_step_2d(const float* A, long m_l, long n_l, long lda, float* W, long m_w, long ldw, float* H, long n_h, long ldh,
-                       int k, float eps, int w_update, int clamp, void* ws, size_t ws_bytes, dnmf_comm_t* c, void* stream) {
-    const int kt = kt_of(k);
-    REQUIRE(kt > 0 && A && W && H && ws && c && m_l >= 1 && n_l >= 1 && lda >= n_l, "mu_kl_step_2d: bad arguments");
-    Grid2d g;
-    int rc;
-    if ((rc = grid2d_init(g, "mu_kl_step_2d", c, m_l, n_l, m_w, n_h, ldw, ldh, k, ws, ws_bytes, stream))) return rc;
-    const size_t kws = g.L.g_off;
-    float *V = g.at(g.L.v_off), *Y = g.at(g.L.y_off), *Yb = g.at(g.L.yb_off), *x = g.at(g.L.x_off);
-    hipStream_t st = g.st;
-    // H_j: gathered once per step (the W phase changes W, not H)
-    const float* Hop; long hb;
-    if ((rc = g.gather_h(H, &Hop, &hb))) return rc;                                                       // gather_W_H :283-287
-    const float* Wi;
-    if (w_update) {                                                // KL_MU_update_W :351-369
-        if ((rc = dnmf_rowsum(H, k, n_h, ldh, x, stream))) return rc;
-        if ((rc = allreduce_f32(c, G_WORLD, x, (size_t)k, st))) return rc;                                // sum_axis :346-349
-        if ((rc = g.gather_w(W, &Wi))) return rc;                                                         // :276-280
-        if (g.blocked) rc = dnmf_kl_uht_hblocks(A, m_l, n_l, lda, Wi, k, Hop, hb, k, eps, V, k, ws, kws, stream);   // :337-338
-        else rc = dnmf_kl_uht(A, m_l, n_l, lda, Wi, k, Hop, hb, k, eps, V, k, ws, kws, stream);
-        if (rc) return rc;
-        const float* UHT;
-        if ((rc = g.scatter_to_w(V, &UHT))) return rc;                                                    // :340
-        if ((rc = dnmf_kl_update_w(W, m_w, k, ldw, UHT, k, x, eps, stream))) return rc;                   // :369
-    }
-    if ((rc = dnmf_colsum(W, m_w, k, ldw, x, ws, kws, stream))) return rc;                                // KL_MU_update_H :371-389
-    if ((rc = allreduce_f32(c, G_WORLD, x, (size_t)k, st))) return rc;
-    if ((rc = g.gather_w(W, &Wi))) return rc;                                                             // :387
-    if (g.sliced && c->p_r > 1) {
-        // WTU_glob :311-312.  Round 5: ONE full-width product, then the k x n_l result is cut into the reduce-scatter's member blocks
-        // (scatter_to_h) -- p_r sliced launches that wrote the blocks directly cost 4.19 ms against 3.97 + 0.04 ms on the config-4
-        // block (each slice pays its own partial slabs and tail; tools/dbg/kl_slices.py).  The product wants H_j as one matrix:
-        // assembled from the gathered blocks (k x n_l floats, one copy per member).
-        if (g.blocked) {
-            float* Hj = g.at(g.L.hj_off);
-            for (int q = 0; q < c->p_r; ++q)
-                COPY2D(Hj + (size_t)q * n_h, n_l, Hop + (size_t)q * k * n_h, n_h, n_h, k, "mu_kl_step_2d: assemble H_j");
-            Hop = Hj; hb = n_l;
-        }
-        if ((rc = dnmf_kl_wtu(A, m_l, n_l, lda, Wi, k, Hop, hb, k, eps, Y, n_l, ws, kws, stream))) return rc;
-        g.sliced = false;                                          // (scatter_to_h cuts Y into the member blocks)
-    } else if (g.sliced) {                                         // one member: its "slice" is the whole width, written where the update reads it
-        if ((rc = dnmf_kl_wtu(A, m_l, n_h, lda, Wi, k, Hop, g.blocked ? n_h : hb, k, eps, Yb, n_h, ws, kws, stream))) return rc;
-    } else if ((rc = dnmf_kl_wtu(A, m_l, n_l, lda, Wi, k, Hop, hb, k, eps, Y, n_l, ws, kws, stream))) return rc;
-    const float* WTU;
-    if ((rc = g.scatter_to_h(Y, &WTU))) return rc;                                                        // :314-316
-    const long ldwtu = (c->p_r == 1 && !g.sliced) ? n_l : n_h;
-    if ((rc = dnmf_kl_update_h(H, k, n_h, ldh, WTU, ldwtu, x, eps, clamp, stream))) return rc;            // :389
-    if (clamp) return dnmf_clamp_min(W, m_w, k, ldw, eps, stream);
-    return DNMF_OK;
-}
-
-// One HALS / Frobenius step of a rank of a 1D grid (FRO_HALS_update, dist_nmf.py:873-934): products and Gram matrices as in the
-// MU step (one packed allreduce per phase along the split axis), the W sweep column by column -- with row-sharded W (p_r > 1)
-// the 8-byte sum of squares of every column is allreduced between the column kernels (utils.py:388-391), with local norms
-// (p_r == 1) it is the persistent sweep, or k column launches when `column_sweep` != 0 -- then the H sweep.  `clamp`:
-// H = max(H, eps), W = max(W, eps) afterwards (pyDNMF.py:170-172).
-}  // extern "C"
-namespace {
-template <typename TA>
-int hals_fro_step_1d_impl(const TA* A, long m_l, long n_l, long lda, float* W, long ldw, float* H, long ldh, int k,
-                          float eps, int w_update, int clamp, int column_sweep, void* ws, size_t ws_bytes, dnmf_comm_t* c,
-                          void* stream) {
-    const int kt = kt_of(k);
-    REQUIRE(kt > 0 && A && W && H && ws && c && m_l >= 1 && n_l >= 1, "hals_fro_step_1d: bad arguments");
-    REQUIRE(c->p_r == 1 || c->p_c == 1, "hals_fro_step_1d: a %d x %d grid is 2D", c->p_r, c->p_c);
-    const int kp = 32 * kt;
-    const Ws1d L = ws1d_layout(m_l, n_l, k);
-    if (ws_bytes < L.total) return fail(DNMF_EWS, "hals_fro_step_1d: workspace %zu < %zu", ws_bytes, L.total);
-    char* base = (char*)ws;
-    const size_t kws = L.g_off;
-    float* X = (float*)(base + L.x_off);
-    const size_t big = std::max((size_t)k * n_l, (size_t)m_l * k);
-    double* ss2 = reinterpret_cast<double*>(X + pad64(big) + (size_t)MAX_CHUNKS * 64 + (size_t)kp * kp + 128);
-    hipStream_t st = S(stream);
-    int rc;
-    if (w_update) {                                               // FRO_HALS_update_W :873-891
-        const size_t off = pad64((size_t)m_l * k);
-        float* AH = X; float* Gx = X + off;
-        if ((rc = dnmf_gram_hht(H, k, n_l, ldh, Gx, ws, kws, stream))) return rc;                 // :882
-        if ((rc = AOps<TA>::aht(A, m_l, n_l, lda, H, k, ldh, AH, k, stream))) return rc;               // :883
-        if (c->p_c != 1 && (rc = allreduce_f32(c, G_WORLD, X, off + (size_t)kp * kp, st))) return rc;
-        if ((c->p_r != 1 && c->nranks > 1) || c->always) rc = hals_sweep_exchanged(c, W, m_l, k, ldw, AH, k, Gx, eps, ss2, ws, kws, stream, column_sweep);   // :884-891
-        else rc = hals_sweep_local(W, m_l, k, ldw, AH, k, Gx, eps, column_sweep, ss2, ws, kws, stream);
-        if (rc) return rc;
-    }
-    const size_t off = pad64((size_t)k * n_l);                    // FRO_HALS_update_H :893-909
-    float* AtW = X; float* Gx = X + off;
-    if ((rc = AOps<TA>::wta_gram(A, m_l, n_l, lda, W, k, ldw, AtW, n_l, Gx, ws, kws, stream))) return rc;   // :902-903
-    if ((c->p_r != 1 || c->always) && (rc = allreduce_f32(c, G_WORLD, X, off + (size_t)kp * kp, st))) return rc;
-    if ((rc = dnmf_hals_update_h(H, k, n_l, ldh, AtW, n_l, Gx, eps, stream))) return rc;           // :905-909
-    if (clamp) {
-        if ((rc = dnmf_clamp_min(H, k, n_l, ldh, eps, stream))) return rc;
-        return dnmf_clamp_min(W, m_l, k, ldw, eps, stream);
-    }
-    return DNMF_OK;
-}
-}  // namespace
-extern "C" {
-int dnmf_hals_fro_step_1d(const float* A, long m_l, long n_l, long lda, float* W, long ldw, float* H, long ldh, int k,
-                          float eps, int w_update, int clamp, int column_sweep, void* ws, size_t ws_bytes, dnmf_comm_t* c,
-                          void* stream) {
-    return hals_fro_step_1d_impl<float>(A, m_l, n_l, lda, W, ldw, H, ldh, k, eps, w_update, clamp, column_sweep, ws, ws_bytes, c, stream);
-}
-int dnmf_hals_fro_step_1d_bf16a(const void* A, long m_l, long n_l, long lda, float* W, long ldw, float* H, long ldh, int k,
-                                float eps, int w_update, int clamp, int column_sweep, void* ws, size_t ws_bytes, dnmf_comm_t* c,
-                                void* stream) {
-    return hals_fro_step_1d_impl<bf16_t>((const bf16_t*)A, m_l, n_l, lda, W, ldw, H, ldh, k, eps, w_update, clamp, column_sweep, ws, ws_bytes, c, stream);
-}
-
-// The same on the 2D grid (FRO_HALS_update, dist_nmf.py:411-470): exchanges as dnmf_mu_fro_step_2d; the column norms of the W
-// sweep are summed over ALL ranks (every rank holds other rows of W).
-}  // extern "C"
-namespace {
-template <typename TA>
-int hals_fro_step_2d_impl(const TA* A, long m_l, long n_l, long lda, float* W, long m_w, long ldw, float* H, long n_h, long ldh,
-                          int k, float eps, int w_update, int clamp, void* ws, size_t ws_bytes, dnmf_comm_t* c, void* stream) {
-    const int kt = kt_of(k);
-    REQUIRE(kt > 0 && A && W && H && ws && c && m_l >= 1 && n_l >= 1 && lda >= n_l, "hals_fro_step_2d: bad arguments");
-    Grid2d g;
-    int rc;
-    if ((rc = grid2d_init(g, "hals_fro_step_2d", c, m_l, n_l, m_w, n_h, ldw, ldh, k, ws, ws_bytes, stream, AOps<TA>::f32))) return rc;
-    const int kp = 32 * kt;
-    const size_t kws = g.L.g_off;
-    float *G = g.at(g.L.g_off), *V = g.at(g.L.v_off), *Y = g.at(g.L.y_off), *Yb = g.at(g.L.yb_off);
-    double* ss2 = reinterpret_cast<double*>(g.at(g.L.x_off) + 128);
-    hipStream_t st = g.st;
-    if (w_update) {                                                // FRO_HALS_update_W :411-434
-        if ((rc = dnmf_gram_hht(H, k, n_h, ldh, G, ws, kws, stream))) return rc;
-        if ((rc = allreduce_f32(c, G_WORLD, G, (size_t)kp * kp, st))) return rc;                          // :426
-        const float* Hop; long hb;
-        if ((rc = g.gather_h(H, &Hop, &hb))) return rc;
-        if constexpr (AOps<TA>::f32) { if (g.blocked) rc = dnmf_aht_hblocks(A, m_l, n_l, lda, Hop, hb, k, V, k, stream); else rc = AOps<TA>::aht(A, m_l, n_l, lda, Hop, k, hb, V, k, stream); }                 // AH_glob :427
-        else rc = AOps<TA>::aht(A, m_l, n_l, lda, Hop, k, hb, V, k, stream);
-        if (rc) return rc;
-        const float* AH;
-        if ((rc = g.scatter_to_w(V, &AH))) return rc;
-        if (c->nranks > 1) rc = hals_sweep_exchanged(c, W, m_w, k, ldw, AH, k, G, eps, ss2, ws, kws, stream);      // :428-434
-        else rc = hals_sweep_local(W, m_w, k, ldw, AH, k, G, eps, 0, ss2, ws, kws, stream);
-        if (rc) return rc;
-    }
-    if ((rc = dnmf_gram_wtw(W, m_w, k, ldw, G, ws, kws, stream))) return rc;                              // FRO_HALS_update_H :436-452
-    if ((rc = allreduce_f32(c, G_WORLD, G, (size_t)kp * kp, st))) return rc;
-    const float* Wi;
-    if ((rc = g.gather_w(W, &Wi))) return rc;
-    if (g.sliced) {
-        for (int q = 0; q < c->p_r; ++q)
-            if ((rc = AOps<TA>::wta(A + q * n_h, m_l, n_h, lda, Wi, k, k, Yb + (size_t)q * k * n_h, n_h, ws, kws, stream))) return rc;
-    } else if ((rc = AOps<TA>::wta(A, m_l, n_l, lda, Wi, k, k, Y, n_l, ws, kws, stream))) return rc;          // ATW_glob :448
-    const float* AtW;
-    if ((rc = g.scatter_to_h(Y, &AtW))) return rc;
-    const long ldatw = (c->p_r == 1 && !g.sliced) ? n_l : n_h;
-    if ((rc = dnmf_hals_update_h(H, k, n_h, ldh, AtW, ldatw, G, eps, stream))) return rc;                 // :449-452
-    if (clamp) {
-        if ((rc = dnmf_clamp_min(H, k, n_h, ldh, eps, stream))) return rc;
-        return dnmf_clamp_min(W, m_w, k, ldw, eps, stream);
-    }
-    return DNMF_OK;
-}
-}  // namespace
-extern "C" {
-int dnmf_hals_fro_step_2d(const float* A, long m_l, long n_l, long lda, float* W, long m_w, long ldw, float* H, long n_h, long ldh,
-                          int k, float eps, int w_update, int clamp, void* ws, size_t ws_bytes, dnmf_comm_t* c, void* stream) {
-    return hals_fro_step_2d_impl<float>(A, m_l, n_l, lda, W, m_w, ldw, H, n_h, ldh, k, eps, w_update, clamp, ws, ws_bytes, c, stream);
-}
-int dnmf_hals_fro_step_2d_bf16a(const void* A, long m_l, long n_l, long lda, float* W, long m_w, long ldw, float* H, long n_h, long ldh,
-                                int k, float eps, int w_update, int clamp, void* ws, size_t ws_bytes, dnmf_comm_t* c, void* stream) {
-    return hals_fro_step_2d_impl<bf16_t>((const bf16_t*)A, m_l, n_l, lda, W, m_w, ldw, H, n_h, ldh, k, eps, w_update, clamp, ws, ws_bytes, c, stream);
+    return dnmf_allreduce_f32_(c, group, buf, count, S(stream));
 }
 
 }  // extern "C"

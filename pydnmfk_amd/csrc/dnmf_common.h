@@ -118,6 +118,15 @@ int check_launch(const char* what) {
     return DNMF_OK;
 }
 
+// an entry point's stream argument (clears the sticky error first: what check_launch reports afterwards is the entry point's own)
+hipStream_t S(void* s) {
+    clear_hip_error();
+    return reinterpret_cast<hipStream_t>(s);
+}
+
+#define REQUIRE(cond, ...) \
+    do { if (!(cond)) return fail(DNMF_EINVAL, __VA_ARGS__); } while (0)
+
 // host twins of `rebase`: problem z's copy of a pointer laid out for problem 0, and a memset of every problem's copy
 inline void* batch_ptr(const void* p, int z) {
     const BatchCtx* bc = dnmf_batch_();

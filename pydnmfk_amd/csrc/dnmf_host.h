@@ -16,20 +16,12 @@ inline bool wide_k(int k) { return k > DNMF_TUNED_MAX_K && k <= DNMF_MAX_K; }
 inline int kp_of(int k) { return wide_k(k) ? 256 : (kt_of(k) < 0 ? -1 : 32 * kt_of(k)); }
 constexpr int WIDE_PANEL = 128;          // the panels a wide rank is cut into
 
-hipStream_t S(void* s) {
-    clear_hip_error();
-    return reinterpret_cast<hipStream_t>(s);
-}
-
 template <typename K>
 void allow_lds(K kernel, size_t bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
-#define REQUIRE(cond, ...) \
-    do { if (!(cond)) return fail(DNMF_EINVAL, __VA_ARGS__); } while (0)
 
 // ---- the batch state of a whole fit (csrc/dnmf_fit.hip, csrc/dnmf_bcd.hip; csrc/dnmf_common.h "batched launches")
 struct BatchGuard {      // the batch state of this thread is set for the duration of one fit call, whatever the exit path

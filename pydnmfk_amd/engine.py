@@ -1582,9 +1582,9 @@ HIP_OPS_F64 = HipOpsF64()
 
 class NativeComm:
     """The grid's RCCL communicators INSIDE libdnmf_hip.so (csrc/dnmf_comm.hip) and the whole-step entry points on top of
-    them: one library call enqueues kernels -> allreduce -> kernels, no Python between the launches.  Built from the host's
-    existing communicator (`comm`: a dist_comm.TorchComm over all ranks), which only carries the 128-byte RCCL id from rank 0
-    to the others.  `params.exchange = 'native'` makes nmf_algorithms_1D / _2D use it for MU (Frobenius, KL) and HALS steps, fp32
+    them (csrc/dnmf_grid.hip): one library call enqueues kernels -> allreduce -> kernels, no Python between the launches.  Built
+    from the host's existing communicator (`comm`: a dist_comm.TorchComm over all ranks), which only carries the 128-byte RCCL id
+    from rank 0 to the others.  `params.exchange = 'native'` makes nmf_algorithms_1D / _2D use it for MU (Frobenius, KL) and HALS steps, fp32
     and bf16-stored data (created on first use; `NativeComm.hosted` builds one whose collectives the host performs)."""
 
     def __init__(self, comm, p_r, p_c):
@@ -1810,10 +1810,10 @@ class NativeComm:
         check(lib.dnmf_comm_allreduce(self.handle, t.data_ptr(), t.numel(), int(group), _stream()))
         return t
 
-    def _workspace(self, m, n, k, device):
-        nbytes = lib.dnmf_ws_bytes_1d(int(m), int(n), int(k))
+    def _workspace(self, nbytes, device):
+        """the communicator's one workspace, grown to `nbytes` (what dnmf_ws_bytes_1d / _2d asked for; 0: the shape is refused)"""
         if nbytes == 0:
-            raise ValueError("bad problem shape m=%d n=%d k=%d" % (m, n, k))
+            raise ValueError("bad problem shape for the steps of a %d x %d grid" % (self.p_r, self.p_c))
         if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
         return self._ws
@@ -1823,7 +1823,7 @@ class NativeComm:
         _req(W, "W"); _req(H, "H")
         m, n = A.shape
         k = W.shape[1]
-        ws = self._workspace(m, n, k, A.device)
+        ws = self._workspace(lib.dnmf_ws_bytes_1d(int(m), int(n), int(k)), A.device)
         if norm.lower() == "fro":
             fn = _fn("mu_fro_step_1d", _req_a(A))                      # fp32 or bf16-stored A
         else:
@@ -1837,11 +1837,10 @@ class NativeComm:
         sfx = _req_a(A); _req(W, "W"); _req(H, "H")
         m, n = A.shape
         k = W.shape[1]
-        ws = self._workspace(m, n, k, A.device)
+        ws = self._workspace(lib.dnmf_ws_bytes_1d(int(m), int(n), int(k)), A.device)
         check(_fn("hals_fro_step_1d", sfx)(A.data_ptr(), m, n, _ld(A), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), k, float(eps),
                                         int(bool(w_update)), int(bool(clamp)), int(bool(column_sweep)), ws.data_ptr(), ws.numel(),
                                         self.handle, _stream()))
-
 
     def step_2d(self, norm, A, W, H, eps, w_update=True, clamp=False):
         """One step of this rank of a 2D grid, exchanges included -- MU (norm 'fro' / 'kl': dnmf_mu_{fro,kl}_step_2d) or HALS /
@@ -1851,17 +1850,13 @@ class NativeComm:
         _req(W, "W"); _req(H, "H")
         m, n = A.shape
         k = W.shape[1]
-        nbytes = lib.dnmf_ws_bytes_2d(int(m), int(n), int(k), self.p_r, self.p_c)
-        if nbytes == 0:
-            raise ValueError("step_2d: bad problem shape m=%d n=%d k=%d on %d x %d" % (m, n, k, self.p_r, self.p_c))
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != A.device:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
+        ws = self._workspace(lib.dnmf_ws_bytes_2d(int(m), int(n), int(k), self.p_r, self.p_c), A.device)
         sfx = _req_a(A)
         if norm.lower() == "kl" and sfx:
             raise ValueError("step_2d: KL needs float32 data")
         fn = {"fro": _fn("mu_fro_step_2d", sfx), "kl": lib.dnmf_mu_kl_step_2d, "hals": _fn("hals_fro_step_2d", sfx)}[norm.lower()]
         check(fn(A.data_ptr(), m, n, _ld(A), W.data_ptr(), W.shape[0], _ld(W), H.data_ptr(), H.shape[1], _ld(H), k, float(eps),
-                 int(bool(w_update)), int(bool(clamp)), self._ws.data_ptr(), self._ws.numel(), self.handle, _stream()))
+                 int(bool(w_update)), int(bool(clamp)), ws.data_ptr(), ws.numel(), self.handle, _stream()))
 
     def step_2d_ok(self, A, W, H):
         """What the 2D entry points take (include/dnmf.h): contiguous factor slices whose sizes follow the partition rule of

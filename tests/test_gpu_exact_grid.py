@@ -1,6 +1,6 @@
 """The grid steps on exact operands, element by element: one update() of nmf_algorithms_1D / _2D per kind of tests/_exact.py GRID_KINDS on
 every grid and shape of GRID_EXACT, through the Python choreography and through the library-sequenced step (dnmf_*_step_{1d,2d},
-csrc/dnmf_comm.hip; on 1D grids also with the direct allreduce over the peer regions, on row grids also with the H phase cut into
+csrc/dnmf_grid.hip; on 1D grids also with the direct allreduce over the peer regions, on row grids also with the H phase cut into
 chunks).  Every sum that crosses ranks is exact in any order, so a ragged 2 x 3 grid must give the bits of one rank: each rank's slice
 is held to the whole-matrix answer (tests/_mp.py `_exact_check`):
   fro, fro_bf16   new W equal; new H within 3 ulps of the float64 quotient (mu_quot, then the factor); also with the clamp

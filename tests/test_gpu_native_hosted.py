@@ -1,4 +1,4 @@
-"""The C step entry points (dnmf_mu_{fro,kl}_step_{1d,2d}, csrc/dnmf_comm.hip) on MORE THAN ONE RANK: a hosted communicator
+"""The C step entry points (dnmf_mu_{fro,kl}_step_{1d,2d}, csrc/dnmf_grid.hip) on MORE THAN ONE RANK: a hosted communicator
 (dnmf_comm_create_hosted) hands every collective of a step to the host, which runs it over gloo -- world_size 2..8 processes
 stacked on the one GPU, the real kernels, the library's own sequencing of kernels and exchanges, its group / member / block
 order.  Each rank must end with the factors the Python choreography (pinned by the reference's goldens on the same grids,
