@@ -11,7 +11,14 @@
  *     stream-ordered, no entry point synchronises the device or allocates memory; the library
  *     reads no environment variables;
  *   - every leading dimension must be >= the logical row length (lda >= n, ...);
- *   - `ws` is caller-provided device scratch of at least dnmf_ws_bytes(m, n, k) bytes;
+ *   - `ws` is caller-provided device scratch of at least dnmf_ws_bytes(m, n, k) bytes -- or of the size query its section names
+ *     (dnmf_ws_bytes_hblocks, _bf16x6, _fit, _1d / _2d, dnmf_f64_ws_bytes, dnmf_bcd_ws_bytes_w, dnmf_csr_ws_bytes, ...).  EVERY `ws`
+ *     starts on a 16-byte boundary: the partial slabs are read and written as 16-byte vectors, and the padded factor images, the
+ *     slots of the waiting kernels and the float64 sums sit at multiples of 256 bytes from it.  No kernel needs more than that; a
+ *     workspace at any other address is refused with DNMF_EWS before anything else is looked at (float32, bf16x6, float64, whole fits,
+ *     BCD, HALS and the grid steps: first of all checks; CSR, masked dense and Itakura-Saito: together with the size).  The
+ *     workspace holds no state: what it contains before a call never shows in a result, and a result does not depend on ws_bytes
+ *     once that reaches the query (tests/test_gpu_workspace.py holds every entry point to both);
  *   - return value: 0 on success, negative DNMF_E* on error (dnmf_last_error() has text);
  *   - k <= DNMF_MAX_K.  Internally k is padded to KP = 32/64/128/256; "gram" buffers G are
  *     always KP x KP, ld = KP, zero padded (dnmf_kp(k) returns KP).

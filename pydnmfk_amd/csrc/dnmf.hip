@@ -468,6 +468,7 @@ int wide_gram(bool hht, const float* F, long len, int k, long ld, float* G, void
 extern "C" {
 
 int dnmf_gram_hht(const float* H, int k, long n, long ldh, float* G, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "gram_hht");
     if (wide_k(k)) {
         REQUIRE(H && G && n >= 1 && ldh >= n, "gram_hht: bad arguments (k=%d n=%ld)", k, n);
         return wide_gram(true, H, n, k, ldh, G, ws, ws_bytes, stream);
@@ -492,6 +493,7 @@ int dnmf_gram_hht(const float* H, int k, long n, long ldh, float* G, void* ws, s
 }
 
 int dnmf_gram_wtw(const float* W, long m, int k, long ldw, float* G, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "gram_wtw");
     if (wide_k(k)) {
         REQUIRE(W && G && ws && m >= 1 && ldw >= k, "gram_wtw: bad arguments (k=%d m=%ld)", k, m);
         return wide_gram(false, W, m, k, ldw, G, ws, ws_bytes, stream);
@@ -672,6 +674,7 @@ namespace {
 template <typename TA>
 int wta_impl(const TA* A, long m, long n, long lda, const float* W, int k, long ldw, float* AtW, long ldatw,
              void* ws, size_t ws_bytes, void* stream, float* G) {
+    REQUIRE_WS16(ws, "wta");
     if (wide_k(k)) {                                               // W^T A splits exactly along the columns of W: two passes over A
         REQUIRE(W && AtW && ws && ldw >= k && ldatw >= n, "wta: bad arguments (k = %d)", k);
         if (G) if (int rc = dnmf_gram_wtw(W, m, k, ldw, G, ws, ws_bytes, stream)) return rc;
@@ -879,6 +882,7 @@ int dnmf_rowsum(const float* H, int k, long n, long ldh, float* x, void* stream)
 }
 
 int dnmf_colsum(const float* W, long m, int k, long ldw, float* x, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "colsum");
     const int kp = kp_of(k);
     REQUIRE(kp > 0 && W && x && ws && m >= 1 && ldw >= k, "colsum: bad arguments");
     // slabs of 128 rows (a 32768-row shard gives 256 workgroups; 1024-row slabs left it on 32 CUs: 116 us for 16 MiB),
@@ -908,6 +912,7 @@ namespace {
 template <typename TA>
 int mu_fro_step_impl(const TA* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k,
                      float eps, int w_update, int clamp, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "mu_fro_step");
     REQUIRE(kp_of(k) > 0 && A && W && H && ws && m >= 1 && n >= 1, "mu_fro_step: bad arguments");
     const WsLayout L = ws_layout(m, n, k);
     if (ws_bytes < L.total) return fail(DNMF_EWS, "mu_fro_step: workspace %zu < %zu", ws_bytes, L.total);
@@ -967,6 +972,7 @@ int dnmf_mu_fro_step_bf16a(const void* A, long m, long n, long lda, float* W, lo
 
 int dnmf_mu_kl_step(const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps,
                     int w_update, int clamp, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "mu_kl_step");
     REQUIRE(kp_of(k) > 0 && A && W && H && ws && m >= 1 && n >= 1, "mu_kl_step: bad arguments");
     const WsLayout L = ws_layout(m, n, k);
     if (ws_bytes < L.total) return fail(DNMF_EWS, "mu_kl_step: workspace %zu < %zu", ws_bytes, L.total);

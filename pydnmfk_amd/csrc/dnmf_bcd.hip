@@ -91,6 +91,7 @@ int dnmf_bcd_lipschitz(const float* G, int k, double* st, int which, void* strea
 
 int dnmf_bcd_update_w(const float* Wm, long ldwm, const float* AHT, long ldaht, const float* G, long m, int k, const double* st, float* W,
                       long ldw, float* s, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "bcd_update_w");
     REQUIRE(Wm && AHT && G && st && W && s && ws && m >= 1 && k >= 1 && k <= DNMF_MAX_K && ldwm >= k && ldaht >= k && ldw >= k,
             "bcd_update_w: bad arguments (m %ld, k %d)", m, k);
     REQUIRE(W != Wm, "bcd_update_w: W must not alias Wm (the step reads Wm rows other workgroups write)");
@@ -149,6 +150,7 @@ int dnmf_bcd_fro_fit(const float* A, long m, long n, long lda, float* W, long ld
                      int itr, int batch, long a_stride, long w_stride, long h_stride, double* sq_out, void* ws, size_t ws_bytes,
                      void* stream) {
     (void)w_update;                                                          // (W is always updated: dist_nmf.py:967 ignores W_update)
+    REQUIRE_WS16(ws, "bcd_fro_fit");
     REQUIRE(A && W && H && sq_out && ws && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_MAX_K && lda >= n && ldw >= k && ldh >= n && itr >= 1 &&
             batch >= 1, "bcd_fro_fit: bad arguments (m %ld, n %ld, k %d, itr %d, batch %d)", m, n, k, itr, batch);
     const size_t need = dnmf_bcd_ws_bytes(m, n, k);

@@ -152,6 +152,11 @@ inline hipError_t batch_memset(void* p, int value, size_t bytes, hipStream_t st)
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// include/dnmf.h: every `ws` starts on a 16-byte boundary -- the partial slabs are read and written as 16-byte vectors, and the padded
+// factor images, the slots and the doubles behind them sit at multiples of 256 bytes from it.  The first statement of an entry point
+// that takes (ws, ws_bytes): refused before any other argument is looked at (a NULL workspace is the entry point's own matter).
+#define REQUIRE_WS16(wsptr, who) \
+    do { if ((wsptr) && !aligned16(wsptr)) return fail(DNMF_EWS, "%s: the workspace must start on a 16-byte boundary", who); } while (0)
 __host__ __device__ inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 inline long round_up(long a, long b) { return cdiv(a, b) * b; }
 

@@ -765,6 +765,7 @@ size_t dnmf_f64_ws_bytes(long m, long n, int k) {
 // C[m x kc] = X[m x n] Y[kc x n]^T  (A H^T: global_mm(A, H.T), dist_nmf.py:730; H H^T: global_gram(H.T), :729 -- X = Y = H)
 int dnmf_f64_aht(const double* X, long m, long n, long ldx, const double* Y, int kc, long ldy, double* C, long ldc, void* ws, size_t ws_bytes,
                  void* stream) {
+    REQUIRE_WS16(ws, "f64 aht");
     REQ(X && Y && C && m >= 1 && n >= 1 && kc >= 1 && kc <= DNMF_TUNED_MAX_K && ldx >= n && ldy >= n && ldc >= kc, "f64 aht: bad arguments");
     hipStream_t st = ST(stream);
     const NtLaunch64 p = plan_nt64(m, n, kc, ldx, ldy, ws);
@@ -791,6 +792,7 @@ int dnmf_f64_aht(const double* X, long m, long n, long ldx, const double* Y, int
 // C[kc x n] = X[m x kc]^T Y[m x n]  (W^T A: global_mm(W.T, A), dist_nmf.py:749; W^T W: global_gram(W), :748 -- Y = X = W)
 int dnmf_f64_wta(const double* Y, long m, long n, long ldy, const double* X, int kc, long ldx, double* C, long ldc, void* ws, size_t ws_bytes,
                  void* stream) {
+    REQUIRE_WS16(ws, "f64 wta");
     REQ(X && Y && C && ws && m >= 1 && n >= 1 && kc >= 1 && kc <= DNMF_TUNED_MAX_K && ldy >= n && ldx >= kc && ldc >= n, "f64 wta: bad arguments");
     hipStream_t st = ST(stream);
     const TnLaunch64 p = plan_tn_launch64(m, n, kc, ldy, ldx, ws);
@@ -839,6 +841,7 @@ int dnmf_f64_kl_quot(const double* A, long m, long n, long lda, const double* W,
 // (csrc/dnmf_f64_kl.h); beyond: through the image U (m x n, the caller's; DNMF_EINVAL without one)
 int dnmf_f64_kl_uht(const double* A, long m, long n, long lda, const double* W, long ldw, const double* H, long ldh, int k, double eps,
                     double* S, long lds_, double* U, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "f64 kl_uht");
     REQ(A && W && H && S && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K && lda >= n && ldw >= k && ldh >= n && lds_ >= k, "f64 kl_uht: bad arguments");
     if (!kl64_fused(lda, ldw, ldh, k)) {
         REQ(U, "f64 kl_uht: k = %d > %d needs the m x n image U", k, KL64_MAX_K);
@@ -869,6 +872,7 @@ int dnmf_f64_kl_uht(const double* A, long m, long n, long lda, const double* W, 
 // S[k x n] = W^T (A / (W H + eps))  (dist_nmf.py:806, :808) -- as dnmf_f64_kl_uht
 int dnmf_f64_kl_wtu(const double* A, long m, long n, long lda, const double* W, long ldw, const double* H, long ldh, int k, double eps,
                     double* S, long lds_, double* U, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "f64 kl_wtu");
     REQ(A && W && H && S && ws && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K && lda >= n && ldw >= k && ldh >= n && lds_ >= n, "f64 kl_wtu: bad arguments");
     if (!kl64_fused(lda, ldw, ldh, k)) {
         REQ(U, "f64 kl_wtu: k = %d > %d needs the m x n image U", k, KL64_MAX_K);
@@ -900,12 +904,14 @@ int dnmf_f64_sqdiff(const double* A, long m, long n, long lda, const double* W, 
 
 // *out = sum X (sq == 0) or sum X^2 (sq != 0) over a rows x cols matrix, fixed summation order
 int dnmf_f64_sum(const double* X, long rows, long cols, long ldx, int sq, double* out, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "f64 sum");
     REQ(X && out && ws && rows >= 1 && cols >= 1 && ldx >= cols, "f64 sum: bad arguments");
     return sum_all(sq != 0, X, rows, cols, ldx, out, ws, ws_bytes, ST(stream));
 }
 
 // x[c] = sum_r X[r][c] (or of squares): sum_along_axis(W, axis=0), dist_nmf.py:793; the per-column sums of column_err, pyDNMF.py:229
 int dnmf_f64_colsum(const double* X, long m, long n, long ldx, int sq, double* x, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "f64 colsum");
     REQ(X && x && ws && m >= 1 && n >= 1 && ldx >= n, "f64 colsum: bad arguments");
     return colsum_any(sq != 0, X, m, n, ldx, x, ws, ws_bytes, ST(stream));
 }
@@ -931,6 +937,7 @@ int dnmf_f64_ew(int op, double* X, long rows, long cols, long ldx, const double*
 // one column of the HALS W sweep (dist_nmf.py:886-887): see dnmf_hals_w_col; *ss2_out = sum of squares of the new column
 int dnmf_f64_hals_w_col(double* W, long m, int k, long ldw, const double* AH, long ldah, const double* G, long ldg, int kk,
                         const double* prev_ss2, double eps, double* ss2_out, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "f64 hals_w_col");
     REQ(W && AH && G && ss2_out && ws && m >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K && kk >= 0 && kk < k && ldw >= k && ldah >= k && ldg >= k,
         "f64 hals_w_col: bad arguments");
     hipStream_t st = ST(stream);
@@ -972,6 +979,7 @@ size_t dnmf_f64_ws_bytes_fit(long m, long n, int k) {
 
 int dnmf_f64_fit(int method, const double* A, long m, long n, long lda, double* W, long ldw, double* H, long ldh, int k, double eps, int w_update,
                  int itr, double* sq_out, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "f64 fit");
     REQ(method >= 0 && method <= 2 && A && W && H && sq_out && ws && m >= 1 && n >= 1 && k >= 1 && k <= DNMF_TUNED_MAX_K && itr >= 0 && lda >= n &&
             ldw >= k && ldh >= n, "f64 fit: bad arguments");
     const size_t need = dnmf_f64_ws_bytes_fit(m, n, k);

@@ -249,6 +249,7 @@ int small_launch(const SmallPlan& p, bool bf, const void* A, long m, long n, lon
 int fit_impl(int method, bool bf, const void* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps,
              int w_update, int itr, int column_sweep, int batch, long a_stride, long w_stride, long h_stride, double* sq_out,
              void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "fit");
     const int kp = dnmf_kp(k);
     if (kp < 0 || !A || !W || !H || !sq_out || !ws || m < 1 || n < 1 || itr < 0 || batch < 1 || lda < n || ldw < k || ldh < n)
         return fail(DNMF_EINVAL, "fit: bad arguments (m=%ld n=%ld k=%d itr=%d batch=%d)", m, n, k, itr, batch);

@@ -54,6 +54,7 @@ struct Step1d {
 
     int init(const char* what, const void* A, long m_l, long n_l, const float* W, const float* H, int k, void* ws, size_t ws_bytes,
              dnmf_comm* comm, void* stream) {
+        REQUIRE_WS16(ws, what);
         const int kt = kt_of(k);
         REQUIRE(kt > 0 && A && W && H && ws && comm && m_l >= 1 && n_l >= 1, "%s: bad arguments", what);
         REQUIRE(comm->p_r == 1 || comm->p_c == 1, "%s: a %d x %d grid is 2D", what, comm->p_r, comm->p_c);
@@ -263,6 +264,7 @@ struct Grid2d {
     // `f32`: bf16-stored A has no column-block form of A H^T
     int init(const char* what, const void* A, long m_l_, long n_l_, long lda, const float* W, long m_w_, long ldw, const float* H,
              long n_h_, long ldh, int k_, void* wsp, size_t ws_bytes, dnmf_comm* comm, void* stream, bool f32) {
+        REQUIRE_WS16(wsp, what);
         REQUIRE(kt_of(k_) > 0 && A && W && H && wsp && comm && m_l_ >= 1 && n_l_ >= 1 && lda >= n_l_, "%s: bad arguments", what);
         if (int rc = check_2d(what, comm, m_l_, n_l_, m_w_, n_h_, ldw, ldh, k_)) return rc;
         c = comm; st = S(stream); k = k_; i = c->rank / c->p_c; j = c->rank % c->p_c;

@@ -179,6 +179,7 @@ extern "C" {
 
 int dnmf_hals_sweep_w(float* W, long m, int k, long ldw, const float* AH, long ldah, const float* G, float eps, void* ws,
                       size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "hals_sweep_w");
     const int kt = kt_of(k);                                        // (-1 for a wide rank: the column launches below)
     const int kp = kp_of(k);
     REQUIRE(kp > 0 && W && AH && G && ws && m >= 1 && ldw >= k && ldah >= k, "hals_sweep_w: bad arguments");

@@ -182,6 +182,7 @@ namespace {
 template <typename TA>
 int resid_sqnorm_impl(const TA* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh,
                       int k, double* out, void* stream, void* ws = nullptr, size_t ws_bytes = 0) {
+    REQUIRE_WS16(ws, "resid_sqnorm");
     if (wide_k(k)) {
         REQUIRE((std::is_same<TA, float>::value) && A && W && H && out && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n,
                 "resid_sqnorm: bad arguments (k = %d: float32 data)", k);
@@ -310,6 +311,7 @@ bool pad_factors_hblocks(const float*& W, long& ldw, const float*& H, long& ldh,
 // hblk = 0: H is one k x n matrix (ldh).  hblk > 0: H is the stack of n / hblk column blocks [q][k][hblk] (ldh = hblk).
 int kl_uht_impl(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, long hblk, int k,
                 float eps, float* UHT, long ldo, void* ws, size_t ws_bytes, void* stream) {   // (W, ldw, H, ldh, k may be re-pointed at padded copies)
+    REQUIRE_WS16(ws, "kl_uht");
     if (wide_k(k)) {
         REQUIRE(!hblk && A && W && H && UHT && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n && ldo >= k,
                 "kl_uht: bad arguments (k = %d; H as column blocks: k <= %d)", k, DNMF_TUNED_MAX_K);
@@ -393,6 +395,7 @@ int dnmf_kl_uht_hblocks(const float* A, long m, long n, long lda, const float* W
 
 int dnmf_kl_wtu(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
                 float eps, float* WTU, long ldo, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "kl_wtu");
     if (wide_k(k)) {
         REQUIRE(A && W && H && WTU && ws && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n && ldo >= n, "kl_wtu: bad arguments");
         return wide_kl_product(false, A, m, n, lda, W, ldw, H, ldh, k, eps, WTU, ldo, ws, ws_bytes, stream);

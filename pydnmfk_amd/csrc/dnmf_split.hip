@@ -129,6 +129,7 @@ template <> struct Fp32Twin<bf16_t> {
 template <typename TA>
 int ahtw_x6(const TA* A, long m, long n, long lda, const float* H, int k, long ldh, const float* G, float* W, long ldw, float eps,
             void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "aht_update_w_bf16x6");
     if (!split_shape(A, m, n, lda, k)) return Fp32Twin<TA>::ahtw(A, m, n, lda, H, k, ldh, G, W, ldw, eps, stream);
     REQUIRE(H && G && W && ws && ldh >= n && ldw >= k, "aht_update_w_bf16x6: bad arguments");
     const int kt = kt_of(k), kp = 32 * kt;
@@ -147,6 +148,7 @@ int ahtw_x6(const TA* A, long m, long n, long lda, const float* H, int k, long l
 template <typename TA>
 int aht_x6(const TA* A, long m, long n, long lda, const float* H, int k, long ldh, float* AH, long ldah, void* ws, size_t ws_bytes,
            void* stream) {
+    REQUIRE_WS16(ws, "aht_bf16x6");
     if (!split_shape(A, m, n, lda, k)) return Fp32Twin<TA>::aht(A, m, n, lda, H, k, ldh, AH, ldah, stream);
     REQUIRE(H && AH && ws && ldh >= n && ldah >= k, "aht_bf16x6: bad arguments");
     const int kt = kt_of(k), kp = 32 * kt;
@@ -164,6 +166,7 @@ int aht_x6(const TA* A, long m, long n, long lda, const float* H, int k, long ld
 template <typename TA>
 int wta_x6(const TA* A, long m, long n, long lda, const float* W, int k, long ldw, float* AtW, long ldatw, void* ws, size_t ws_bytes,
            void* stream) {
+    REQUIRE_WS16(ws, "wta_bf16x6");
     if (!split_shape(A, m, n, lda, k)) return Fp32Twin<TA>::wta(A, m, n, lda, W, k, ldw, AtW, ldatw, ws, ws_bytes, stream);
     REQUIRE(W && AtW && ws && ldw >= k && ldatw >= n, "wta_bf16x6: bad arguments");
     const size_t need = wta_need(m, n, k);
@@ -325,6 +328,7 @@ namespace {
 template <typename TA>
 int step_x6(const TA* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k,
             float eps, int w_update, int clamp, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "mu_fro_step_bf16x6");
     if (!split_shape(A, m, n, lda, k)) return Fp32Twin<TA>::step(A, m, n, lda, W, ldw, H, ldh, k, eps, w_update, clamp, ws, ws_bytes, stream);
     REQUIRE(W && H && ws, "mu_fro_step_bf16x6: bad arguments");
     const size_t total = dnmf_ws_bytes_bf16x6(m, n, k);
@@ -365,6 +369,7 @@ int dnmf_mu_fro_step_bf16a_bf16x6(const void* A, long m, long n, long lda, float
 
 int dnmf_kl_wtu_bf16x6(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
                        float eps, float* WTU, long ldo, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "kl_wtu_bf16x6");
     if (!klx_shape(A, m, n, lda, k)) return dnmf_kl_wtu(A, m, n, lda, W, ldw, H, ldh, k, eps, WTU, ldo, ws, ws_bytes, stream);
     REQUIRE(W && H && WTU && ws && ldw >= k && ldh >= n && ldo >= n, "kl_wtu_bf16x6: bad arguments");
     const int kt = kt_of(k), kp = 32 * kt;
@@ -398,6 +403,7 @@ int dnmf_kl_wtu_bf16x6(const float* A, long m, long n, long lda, const float* W,
 
 int dnmf_kl_uht_bf16x6(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
                        float eps, float* UHT, long ldo, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "kl_uht_bf16x6");
     if (!klx_shape(A, m, n, lda, k)) return dnmf_kl_uht(A, m, n, lda, W, ldw, H, ldh, k, eps, UHT, ldo, ws, ws_bytes, stream);
     REQUIRE(W && H && UHT && ws && ldw >= k && ldh >= n && ldo >= k, "kl_uht_bf16x6: bad arguments");
     const int kt = kt_of(k), kp = 32 * kt;
@@ -431,6 +437,7 @@ int dnmf_kl_uht_bf16x6(const float* A, long m, long n, long lda, const float* W,
 
 int dnmf_mu_kl_step_bf16x6(const float* A, long m, long n, long lda, float* W, long ldw, float* H, long ldh, int k, float eps,
                            int w_update, int clamp, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "mu_kl_step_bf16x6");
     if (!klx_shape(A, m, n, lda, k)) return dnmf_mu_kl_step(A, m, n, lda, W, ldw, H, ldh, k, eps, w_update, clamp, ws, ws_bytes, stream);
     REQUIRE(W && H && ws, "mu_kl_step_bf16x6: bad arguments");
     const size_t total = dnmf_ws_bytes_bf16x6(m, n, k);

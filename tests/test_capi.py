@@ -187,3 +187,32 @@ def test_csr_pack_and_ratio_validation_without_gpu():
     ratio = dict(X=P16, rows=8, cols=4, ldx=4, num=P16, den=P16, ldp=4, eps=1e-7, clamp=0, stream=None)
     for bad in (dict(X=None), dict(num=None), dict(den=None), dict(rows=0), dict(cols=0), dict(ldx=3), dict(ldp=3)):
         _refused(lib, "dnmf_csr_ratio_update", "csr_ratio_update", ratio, **bad)
+
+
+# ---- the alignment of `ws` (include/dnmf.h: every workspace starts on a 16-byte boundary).  The float32, bf16x6, float64, whole-fit,
+# BCD, HALS and grid-step entry points refuse any other address with DNMF_EWS as the FIRST of their checks -- every other argument below
+# is made up (a pointer nothing may dereference, 8 for every integer), so a refusal that came later would be another one, or a fault.
+# The CSR, masked dense and Itakura-Saito entry points check the alignment together with the size: test_csr_argument_validation_without_gpu
+# above, tests/test_capi_masked.py, tests/test_capi_is.py.
+WS_CHECKED_WITH_THE_SIZE = ("dnmf_csr_", "dnmf_masked_", "dnmf_is_")
+
+
+def test_a_misaligned_workspace_is_refused_before_anything_else_without_gpu():
+    from pydnmfk_amd import _lib
+    lib = _lib.lib
+    seen = []
+    for name, args in _lib.SIGNATURES.items():
+        if name.startswith("dnmf_comm_") or name.startswith(WS_CHECKED_WITH_THE_SIZE) or name == "dnmf_dense_plan":
+            continue
+        at = next((i for i in range(len(args) - 1) if args[i] is ctypes.c_void_p and args[i + 1] is ctypes.c_size_t), None)
+        if at is None:
+            continue
+        call = [P16 if a is ctypes.c_void_p else 1 << 20 if a is ctypes.c_size_t else 1e-7 if a in (ctypes.c_float, ctypes.c_double) else 8
+                for a in args]
+        for odd in (ODD, P16 + 8, P16 + 1):
+            call[at] = odd
+            rc = getattr(lib, name)(*call)
+            err = lib.dnmf_last_error()
+            assert rc == EWS and b"16-byte boundary" in err, "%s with ws at %#x returned %d (%r)" % (name, odd, rc, err)
+        seen.append(name)
+    assert len(seen) == 52, (len(seen), seen)                    # 72 launching entry points take a workspace; 20 check it with the size
