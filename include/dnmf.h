@@ -978,4 +978,8 @@ int dnmf_clock_probe(unsigned long long* samples, int n, int naps, void* stream)
 #ifdef __cplusplus
 }
 #endif
+
+/* the beta-divergence family (dnmf_beta_*): part of this ABI, declared in a header of its own */
+#include "dnmf_beta_api.h"
+
 #endif /* DNMF_H */

@@ -257,6 +257,18 @@ SIGNATURES["dnmf_is_mu_fit"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_lo
 SIGNATURES["dnmf_is_column_div_ws_bytes"] = [c_long, c_long, c_int]
 SIGNATURES["dnmf_is_column_div_plan"] = [c_long, c_long, c_int, c_void_p]      # out: long[3]
 SIGNATURES["dnmf_is_column_div"] = SIGNATURES["dnmf_is_divergence"]
+# the beta-divergence rule (csrc/dnmf_beta.hip): the Itakura-Saito signatures with `float beta` after eps.  A table of its own: the
+# core table above is held, entry point by entry point, to the workspace contract by tests/test_workspace_cpu.py, tests/test_capi.py and
+# tests/test_gpu_workspace.py; this family's entries are held to the same contract by tests/test_beta_workspace_cpu.py and
+# tests/test_gpu_beta_workspace.py
+BETA_SIGNATURES = {}
+BETA_SIGNATURES["dnmf_beta_ws_bytes"] = [c_long, c_long, c_int]
+BETA_SIGNATURES["dnmf_beta_ws_bytes_fit"] = [c_long, c_long, c_int]
+BETA_SIGNATURES["dnmf_beta_plan"] = [c_long, c_long, c_int, c_void_p]      # out: long[8]
+for _name in ("aht_pair", "wta_pair", "update_w", "update_h", "divergence", "mu_fit"):
+    _sig = SIGNATURES["dnmf_is_" + _name]
+    BETA_SIGNATURES["dnmf_beta_" + _name] = _sig[:10] + [c_float] + _sig[10:]
+BETA_SIGNATURES["dnmf_beta_ratio_update"] = SIGNATURES["dnmf_is_ratio_update"][:8] + [c_float] + SIGNATURES["dnmf_is_ratio_update"][8:]
 # the W phase from a transposed image of A (csrc/dnmf_timg.hip): build A m n lda At ldat stream; bind the same without the stream
 SIGNATURES["dnmf_wimage_bytes"] = [c_long, c_long]
 SIGNATURES["dnmf_wimage_build"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]
@@ -264,7 +276,7 @@ SIGNATURES["dnmf_wimage_bind"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_
 SIGNATURES["dnmf_wimage_unbind"] = []
 SIGNATURES["dnmf_set_wimage"] = [c_int]
 SIGNATURES["dnmf_wimage_plan"] = [c_long, c_long, c_int, c_long, c_int, c_int, c_void_p]      # out: int[6]
-_RESTYPES = {"dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
+_RESTYPES = {"dnmf_beta_ws_bytes": c_size_t, "dnmf_beta_ws_bytes_fit": c_size_t, "dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
              "dnmf_ws_bytes_1d": c_size_t, "dnmf_ws_bytes_hblocks": c_size_t, "dnmf_ws_bytes_2d": c_size_t,
              "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t, "dnmf_bcd_ws_bytes_fit": c_size_t}
 
@@ -275,7 +287,7 @@ def load():
             "pydnmfk_amd: %s not found. Build it with `python -m pydnmfk_amd.build` (hipcc, gfx950). "
             "There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, args in SIGNATURES.items():
+    for name, args in list(SIGNATURES.items()) + list(BETA_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI drifted from include/dnmf.h
         fn.argtypes = args
         fn.restype = _RESTYPES.get(name, c_int)

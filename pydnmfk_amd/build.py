@@ -21,7 +21,7 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     import glob
-    deps = glob.glob(os.path.join(HERE, "csrc", "*")) + [os.path.join(ROOT, "include", "dnmf.h")]
+    deps = glob.glob(os.path.join(HERE, "csrc", "*")) + glob.glob(os.path.join(ROOT, "include", "*.h"))
     return any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps)
 
 

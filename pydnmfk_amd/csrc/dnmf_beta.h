@@ -1,0 +1,142 @@
+// dnmf_beta.h -- the beta-divergence for any beta in [-2, 4]: the MU rule in its majorisation-minimisation form on the matrix cores.
+// Part of libdnmf_hip.so (kernels live in anonymous namespaces of the headers; the translation units csrc/*.hip include what they launch).
+//
+//     d_beta(a | s) = (a^beta + (beta - 1) s^beta - beta a s^(beta - 1)) / (beta (beta - 1))
+// (beta = 2: half the squared error; beta -> 1: Kullback-Leibler; beta -> 0: Itakura-Saito).  With S' = W H + eps (eps the float32 machine
+// epsilon, placed as in csrc/dnmf_is.h), P = S'^(beta - 2) element-wise and F = H^T on the W side, F = W on the H side (with the new W):
+//     u_n = A . P,   u_d = S' . P,   num = u_n F,   den = u_d F,   X <- X . (num / (den + eps))^gamma(beta)
+//     gamma = 1 / (2 - beta) for beta < 1,   1 for 1 <= beta <= 2,   1 / (beta - 1) for beta > 2
+// (Fevotte & Idier 2011, the majorisation-minimisation rule: D_beta(A | W H + eps) never increases).  This is the structure of the masked
+// pairs (csrc/dnmf_masked.h) with a fourth element-wise step, MODE = PAIR_BETA, and ONE runtime scalar e = beta - 2 that the host
+// computes once (NnArgs::pexp).  The pair kernels ARE masked_uht_kernel / masked_wtu_kernel; this file adds the mode's choices, the
+// rule on a stored pair (pair_rule's RULE_POW form, the same function as in the reduce ending) and the divergence.
+//
+// The element-wise step.  p = exp2(e * log2(s + eps)) with the ONE-INSTRUCTION forms v_log_f32 and v_exp_f32 (__builtin_amdgcn_logf /
+// __builtin_amdgcn_exp2f), not the library log2f / exp2f: the library forms add a range scaling for denormal arguments and results
+// (three to four more vector instructions each), and neither can occur -- s + eps >= 2^-23 and, inside the accepted range of beta,
+// p of a padded position is within [2^-46, 2^92]; a p that underflows inside the block (a model value of 1e10 under beta = -2) is a zero
+// weight, which is what the limit is.  Both instructions are accurate to 1 ulp of their result, so the absolute error of e * log2 s is
+// about (1 + |e|) ulp(log2 s) + ulp(e log2 s) / 2 and the relative error of p is ln 2 times that: for S in [0.05, 200] and |e| <= 4
+// below 2e-6 per element, before the averaging of the second products.  Per element: v_add_f32 (s + eps), v_log_f32, v_mul_f32 (e .),
+// v_exp_f32, v_mul_f32 (a p), v_mul_f32 (s' p) -- SIX vector instructions where the Itakura-Saito step has four (v_add, v_rcp, two
+// v_mul).  On gfx950 a vector instruction beside the MFMAs costs about 3.3 matrix-pipe cycles (README, round 3): two more per element
+// is what this mode pays over IS, about 6.6 cycles per element on each side, next to the 6 KP / 8 cycles per element of a side's three
+// 32x32x2 products (24 / 48 / 96 at KP = 32 / 64 / 128).  Measured (tools/betabench.py, profiles/beta_step_times.md, one MI355X,
+// 32768 x 16384): a beta step takes 1.04 / 1.01 / 1.00 times the Itakura-Saito step at k = 32 / 64 / 128 -- the pair kernels are plain
+// loops that wait for their loads, and the two additional instructions issue under those waits.
+// Measured accuracy against float64 (tests/test_gpu_beta.py, bound 1e-5): pairs 6.5e-7 (largest at beta = -2), updates 1.6e-7;
+// v_exp_f32 of an exact zero is exactly 1, so at beta = 2 the pairs of exact operands are exact.
+//
+// Padding adds exactly nothing, without inf or 0 * inf.  An A load outside the block returns 0.  A padded column c >= n is a zero
+// column of the staged H tile and a padded row r >= m a zero row of W (the predicated loads), so S = 0 there and s + eps = 2^-23
+// exactly: log2 is -23, p = 2^(-23 (beta - 2)).  That must be FINITE so that u_n = 0 * p = 0 exactly and u_d = 2^-23 p meets an exact zero
+// of F in the second product where that product contracts over the padded index (W side: over the columns c, and H[:, c] = 0; H side:
+// over the rows r, and W[r, :] = 0).  Finite in fp32 means 23 |beta - 2| < 128, |beta - 2| < 5.5; the accepted range is -2 <= beta <= 4,
+// |beta - 2| <= 4 < 5.5: p <= 2^92 (beta = -2), u_d <= 2^69, and p >= 2^-46 (beta = 4), u_d >= 2^-69, a normal number.  Outside that range
+// the entry points return DNMF_EINVAL (beta_ok below) and Python raises ValueError naming the range.  Where the padded index is an
+// OUTPUT index (a row >= m of the W side, a column >= n of the H side) the sums are finite and go nowhere: the W side does not store
+// such a row, the H side stores such a column into the slab's own padding (ldp), which the ending never reads.  Inside the block
+// S >= 0 (non-negative factors), so s + eps >= 2^-23 and the bounds on p hold likewise; a padded contraction index j >= k is a zero row of
+// H and a zero column of W.
+//
+// Data: strictly positive for beta <= 0 (a zero sends the divergence to infinity), non-negative for beta > 0 (a zero gives u_n = 0 and
+// a^beta = 0).  PyNMF checks once per fit.  A NaN would reach an MFMA operand.
+//
+// Registers (hipcc --offload-arch=gfx950 -O3, kernel-resource-usage remarks; every PAIR_BETA instantiation, none uses scratch):
+//   masked_uht_kernel<KT, JT, FAST, PAIR_BETA>   VGPR  AGPR  scratch  waves/SIMD     masked_wtu_kernel<KT, NT, FAST, PAIR_BETA>   VGPR  AGPR  scratch  waves/SIMD
+//   <1, 1, true>                                  158     0     0        3           <1, 4, true>                                  256   160     0        1
+//   <1, 1, false>                                 156     0     0        3           <1, 4, false>                                 256   228     0        1
+//   <2, 2, true>                                  236     0     0        2           <2, 2, true>                                  238   132     0        1
+//   <2, 2, false>                                 236     0     0        2           <2, 2, false>                                 240   132     0        1
+//   <4, 4, true>                                  254   156     0        1           <4, 1, true>                                  193   128     0        1
+//   <4, 4, false>                                 256   157     0        1           <4, 1, false>                                 197   128     0        1
+// (the waves per SIMD are those of the launch bounds, as for the other modes).  JT = 4 at KP = 128 does not spill, so the W side takes
+// the Itakura-Saito plan there (one pass over S), not the masked plan's JT = 2.  masked_reduce_kernel<RULE_POW>: 33 VGPRs;
+// beta_ratio_kernel: 29; beta_div_kernel: 91 to 166 VGPRs + 64 AGPRs; none uses scratch.
+#pragma once
+#include "dnmf_masked.h"
+#include "dnmf_is.h"        // is_div_sum_kernel: the fixed-order sum of the divergence's slots
+
+namespace {
+
+// -2 <= beta <= 4 (the padding argument above); a NaN compares false
+inline bool beta_ok(float beta) { return beta >= -2.f && beta <= 4.f; }
+
+// the exponent of the rule
+inline float beta_gamma(float beta) { return beta < 1.f ? 1.f / (2.f - beta) : (beta <= 2.f ? 1.f : 1.f / (beta - 1.f)); }
+
+inline PairExp beta_exp(float beta) { return PairExp{beta - 2.f, beta_gamma(beta)}; }
+
+// ---- what the mode chooses on the launch path of csrc/dnmf_masked.h: the Itakura-Saito plans (csrc/dnmf_is.h: one part of the output
+// columns at KP = 128 -- JT = 4 holds next to the two transcendentals without scratch, see the table above -- and at least four row
+// chunks on the H side), the rule with a runtime exponent
+template <>
+struct PairMode<PAIR_BETA> {
+    static constexpr int zdim128 = 1;
+    static constexpr long min_chunks = 4;
+    static constexpr int rule = RULE_POW;       // X <- X * (num / (den + eps))^gamma
+    static constexpr const char* serves = "the beta-divergence kernels";
+};
+
+// ---- the rule on a stored pair (after its allreduce on a 1D grid): pair_rule's RULE_POW form, as in the ending
+__global__ __launch_bounds__(256) void beta_ratio_kernel(float* __restrict__ X, long rows, long cols, long ldx, const float* __restrict__ num,
+                                                         const float* __restrict__ den, long ldo, float eps, int clamp, float gamma) {
+    const long total = rows * cols;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long r = idx / cols, c = idx % cols;
+        X[r * ldx + c] = pair_rule<RULE_POW>(X[r * ldx + c], num[r * ldo + c], den[r * ldo + c], eps, clamp, gamma);
+    }
+}
+
+// ---- D_beta(A | W H + eps): is_div_kernel's structure (csrc/dnmf_is.h: a wave per 32 x 128 tile of S in accumulators, fp32 per tile
+// and lane (64 terms), float64 from there on, ONE double per wave in its own slot of P, the slots added in a fixed order by
+// is_div_sum_kernel: no atomics, bit-reproducible) with another term.  FORM picks it:
+//   BETA_DIV_GEN  (a^beta + (beta - 1) s'^beta - beta a s'^(beta - 1)) / (beta (beta - 1)), as s'^(beta - 1) ((beta - 1) s' - beta a) + a^beta
+//                 times c = 1 / (beta (beta - 1)) from the host; a^beta at a = 0 is SELECTED to 0 (beta > 0; log2 0 = -inf never meets it)
+//   BETA_DIV_KL   beta = 1, where that form is singular: a log(a / s') - a + s', and s' where a = 0
+//   BETA_DIV_IS   beta = 0, singular as well: q - log q - 1, q = a / s' (is_div_kernel's term)
+// The library log2f / exp2f / logf here (not the one-instruction forms of the pair): this kernel runs once per report, not per step.
+// Outside the block the term is SELECTED away, never multiplied.
+enum { BETA_DIV_GEN = 0, BETA_DIV_KL = 1, BETA_DIV_IS = 2 };
+template <int FORM>
+__device__ __forceinline__ float beta_div_term(float a, float sp, float beta, float c) {
+    if constexpr (FORM == BETA_DIV_KL) {
+        return a > 0.f ? a * logf(a / sp) - a + sp : sp;
+    } else if constexpr (FORM == BETA_DIV_IS) {
+        const float q = kl_quot(a, sp);
+        return (q - 1.f) - logf(q);
+    } else {
+        const float sb1 = exp2f((beta - 1.f) * log2f(sp));          // s'^(beta - 1)
+        const float ab = a > 0.f ? exp2f(beta * log2f(a)) : 0.f;    // a^beta, 0 at a = 0
+        return (ab + sb1 * ((beta - 1.f) * sp - beta * a)) * c;
+    }
+}
+
+template <int KT, bool FAST, int FORM>
+__global__ __launch_bounds__(256) void beta_div_kernel(NnArgs p, double* __restrict__ P, float beta, float c) {
+    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long gw = (long)blockIdx.x * 4 + wid;
+    if (gw >= p.nrowblk * p.ncolblk) return;
+    const long row0 = (gw / p.ncolblk) * 32, col0 = (gw % p.ncolblk) * 128;
+    f32x16 acc[4];
+    nn_tile<KT, 4, FAST, false>(acc, p.W, p.ldw, p.m, p.k, p.H, p.ldh, p.n, row0, col0, li, h);
+    float part = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const long row = row0 + crow(r, h);
+        float a[4];
+        load_vec<4, FAST>(a, p.A + row * p.lda, col0 + 4 * li, p.n, row < p.m);
+#pragma unroll
+        for (int ne = 0; ne < 4; ++ne) {
+            const float t = beta_div_term<FORM>(a[ne], acc[ne][r] + p.eps, beta, c);
+            part += (row < p.m && col0 + 4 * li + ne < p.n) ? t : 0.f;
+        }
+    }
+    double total = (double)part;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) total += __shfl_xor(total, off, 64);
+    if (lane == 0) P[gw] = total;
+}
+
+}  // namespace

@@ -40,7 +40,7 @@ struct PairMode<PAIR_IS> {
     // waves of every workgroup returned at once and the pass ran on half the SIMDs (measured, 32768 x 16384, k = 128: 10.8 ms).
     // Shapes with at most 256 column blocks -- every shape of the masked suite -- get the masked plan unchanged.
     static constexpr long min_chunks = 4;
-    static constexpr bool sqrt_rule = true;     // X <- X * sqrt(num / (den + eps))
+    static constexpr int rule = RULE_SQRT;      // X <- X * sqrt(num / (den + eps))
     static constexpr const char* serves = "the Itakura-Saito kernels";
 };
 
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void is_ratio_kernel(float* __restrict__ X, lo
     const long total = rows * cols;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const long r = idx / cols, c = idx % cols;
-        X[r * ldx + c] = pair_rule<true>(X[r * ldx + c], num[r * ldo + c], den[r * ldo + c], eps, clamp);
+        X[r * ldx + c] = pair_rule<RULE_SQRT>(X[r * ldx + c], num[r * ldo + c], den[r * ldo + c], eps, clamp);
     }
 }
 

@@ -19,7 +19,8 @@
 // over column splits (W side) and row chunks (H side) are left as partials and added in split / chunk order by masked_reduce_kernel --
 // no float atomics, so a fit's factors are bit-reproducible.  Plain launch chains: no workgroup waits for another one.
 //
-// The pair kernels serve a third rule, Itakura-Saito (MODE = PAIR_IS, csrc/dnmf_is.h).  Everything around them exists once, in the
+// The pair kernels serve a third rule, Itakura-Saito (MODE = PAIR_IS, csrc/dnmf_is.h), and a fourth, the beta-divergence for a runtime
+// beta (MODE = PAIR_BETA, csrc/dnmf_beta.h).  Everything around them exists once, in the
 // host part at the end of this file: plans, the launcher of each side, the ending, the plan report and the chain of a whole fit.
 #pragma once
 #include "dnmf_common.h"
@@ -31,11 +32,17 @@
 namespace {
 
 // the element-wise step: (u_n, u_d) of one element from its datum `a` and its model value s = <W[r], H[:, c]>.  MODE: the two masked
-// rules above, or the Itakura-Saito pair of csrc/dnmf_is.h, which has no mask (its padding argument is written there)
-enum { PAIR_FRO = 0, PAIR_KL = 1, PAIR_IS = 2 };
+// rules above, or the Itakura-Saito pair of csrc/dnmf_is.h, which has no mask (its padding argument is written there), or the pair of
+// a general beta-divergence (csrc/dnmf_beta.h: no mask either; `e` = beta - 2 is NnArgs::pexp, which the other modes never read)
+enum { PAIR_FRO = 0, PAIR_KL = 1, PAIR_IS = 2, PAIR_BETA = 3 };
 template <int MODE>
-__device__ __forceinline__ void masked_pair(float a, float s, float eps, float& un, float& ud) {
-    if constexpr (MODE == PAIR_IS) {
+__device__ __forceinline__ void masked_pair(float a, float s, float eps, float e, float& un, float& ud) {
+    if constexpr (MODE == PAIR_BETA) {
+        const float sp = s + eps;                  // S' = S + eps >= 2^-23
+        const float p = __builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf(sp));   // P = S'^e: v_log_f32, v_mul_f32, v_exp_f32
+        un = a * p;                                // A . P
+        ud = sp * p;                               // S' . P
+    } else if constexpr (MODE == PAIR_IS) {
         ud = __builtin_amdgcn_rcpf(s + eps);       // r = 1 / (S + eps): v_rcp_f32, the form of kl_quot
         un = a * ud * ud;                          // a r^2
     } else {
@@ -105,7 +112,7 @@ __global__ __launch_bounds__(256, KT == 4 ? 1 : 2) void masked_uht_kernel(NnArgs
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float x, y;
-                masked_pair<MODE>(a_cur[g][e], st[4 * g + e], p.eps, x, y);
+                masked_pair<MODE>(a_cur[g][e], st[4 * g + e], p.eps, p.pexp, x, y);
                 un[4 * g + e] = x;
                 ud[4 * g + e] = y;
             }
@@ -207,7 +214,7 @@ __global__ __launch_bounds__(256, 1) void masked_wtu_kernel(NnArgs p, long half_
 #pragma unroll
             for (int ne = 0; ne < NT; ++ne) {
                 float x, y;
-                masked_pair<MODE>(areg[r][ne], acc[ne][r], p.eps, x, y);
+                masked_pair<MODE>(areg[r][ne], acc[ne][r], p.eps, p.pexp, x, y);
                 areg[r][ne] = x;
                 acc[ne][r] = y;
             }
@@ -244,19 +251,25 @@ __global__ __launch_bounds__(256, 1) void masked_wtu_kernel(NnArgs p, long half_
 // ---- the endings: the partials added in part order, then either the pair stored (num, den with leading dimension ldo: the two halves
 // of one contiguous buffer where the sums cross ranks) or the rule applied in place, max(., eps) with clamp.  The rule: the ratio,
 // X <- X * (num / (den + eps)) (the masked rules; the expression of dnmf_csr_ratio_update, which follows an allreduce of the stored
-// pair), or with SQRT its square root, X <- X * sqrt(num / (den + eps)) (the Itakura-Saito rule, csrc/dnmf_is.h)
-template <bool SQRT>
-__device__ __forceinline__ float pair_rule(float x, float a, float b, float eps, int clamp) {
+// pair), or with RULE_SQRT its square root, X <- X * sqrt(num / (den + eps)) (the Itakura-Saito rule, csrc/dnmf_is.h), or with
+// RULE_POW its power with a runtime exponent, X <- X * (num / (den + eps))^gamma (the beta-divergence rule, csrc/dnmf_beta.h: gamma = 1
+// takes the plain ratio; powf(0, gamma) is 0 for gamma > 0, so a quotient of 0 gives 0, not NaN).  `gamma` is read by RULE_POW alone
+enum { RULE_RATIO = 0, RULE_SQRT = 1, RULE_POW = 2 };
+template <int RULE>
+__device__ __forceinline__ float pair_rule(float x, float a, float b, float eps, int clamp, float gamma = 1.f) {
     const float q = a / (b + eps);
-    const float y = x * (SQRT ? sqrtf(q) : q);
+    float f;
+    if constexpr (RULE == RULE_POW) f = gamma == 1.f ? q : powf(q, gamma);
+    else f = RULE == RULE_SQRT ? sqrtf(q) : q;
+    const float y = x * f;
     return clamp ? fmaxf(y, eps) : y;
 }
 
-template <bool SQRT>
+template <int RULE>
 __global__ __launch_bounds__(256) void masked_reduce_kernel(const float* __restrict__ P, long part_stride, long half_stride, long ldp,
                                                           int nparts, long rows, long cols, float* __restrict__ num,
                                                           float* __restrict__ den, long ldo, float* __restrict__ X, long ldx, float eps,
-                                                          int clamp) {
+                                                          int clamp, float gamma) {
     const long total = rows * cols;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const long r = idx / cols, c = idx % cols;
@@ -267,7 +280,7 @@ __global__ __launch_bounds__(256) void masked_reduce_kernel(const float* __restr
             b += q[s * part_stride + half_stride];
         }
         if (X) {
-            X[r * ldx + c] = pair_rule<SQRT>(X[r * ldx + c], a, b, eps, clamp);
+            X[r * ldx + c] = pair_rule<RULE>(X[r * ldx + c], a, b, eps, clamp, gamma);
         } else {
             num[r * ldo + c] = a;
             den[r * ldo + c] = b;
@@ -383,15 +396,15 @@ __global__ __launch_bounds__(256) void masked_sqnorm_kernel(const float* __restr
 // ================================================================================================ host side
 // The ONE launch path of the pair kernels above: plans, launchers of both sides, the ending, the plan report and the chain of a whole
 // fit, templated on MODE so that a translation unit instantiates only the kernels of the modes it launches (csrc/dnmf_masked.hip:
-// PAIR_FRO and PAIR_KL; csrc/dnmf_is.hip: PAIR_IS).
+// PAIR_FRO and PAIR_KL; csrc/dnmf_is.hip: PAIR_IS; csrc/dnmf_beta.hip: PAIR_BETA).
 
 // What a mode chooses: its two plan parameters (below), the form of its rule, and how the messages name its kernels.  The masked
-// modes take these; csrc/dnmf_is.h states the Itakura-Saito ones.
+// modes take these; csrc/dnmf_is.h states the Itakura-Saito ones, csrc/dnmf_beta.h those of a general beta.
 template <int MODE>
 struct PairMode {
     static constexpr int zdim128 = 2;           // parts of the output columns at KP = 128: JT = KT / zdim128 tiles per workgroup
     static constexpr long min_chunks = 1;       // the fewest row chunks the H side asks for
-    static constexpr bool sqrt_rule = false;    // pair_rule's SQRT
+    static constexpr int rule = RULE_RATIO;     // pair_rule's RULE
     static constexpr const char* serves = "masked dense data";
 };
 
@@ -452,8 +465,12 @@ size_t pair_step_bytes(long m, long n, int kt) {
     return align256(std::max(pair_uht_plan<MODE>(m, n, kt).bytes, pair_wtu_plan<MODE>(m, n, kt).bytes));
 }
 
+// the two runtime scalars of a mode whose step and rule take one each (PAIR_BETA: e = beta - 2 and gamma(beta)); every other mode
+// leaves them at what changes nothing
+struct PairExp { float e = 0.f; float gamma = 1.f; };
+
 NnArgs masked_args(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps) {
-    NnArgs a{};
+    NnArgs a{};                                 // (pexp = 0: the caller of a PAIR_BETA launch sets it)
     a.A = A; a.lda = lda; a.m = m; a.n = n; a.W = W; a.ldw = ldw; a.H = H; a.ldh = ldh; a.k = k; a.eps = eps; a.kreal = k;
     a.nrowblk = cdiv(m, 32); a.ncolblk = (int)cdiv(n, 128);
     return a;
@@ -468,17 +485,17 @@ long masked_reduce_grid(long rows, long cols) { return std::min<long>(cdiv(rows 
 
 template <int MODE>
 int pair_reduce(const float* P, long part_stride, long half_stride, long ldp, int nparts, long rows, long cols, float* num, float* den,
-                long ldo, float* X, long ldx, float eps, int clamp, hipStream_t st, const char* who) {
+                long ldo, float* X, long ldx, float eps, int clamp, hipStream_t st, const char* who, float gamma = 1.f) {
     const unsigned grid = (unsigned)masked_reduce_grid(rows, cols);
-    hipLaunchKernelGGL(masked_reduce_kernel<PairMode<MODE>::sqrt_rule>, dim3(grid), dim3(256), 0, st, P, part_stride, half_stride, ldp, nparts,
-                       rows, cols, num, den, ldo, X, ldx, eps, clamp);
+    hipLaunchKernelGGL(masked_reduce_kernel<PairMode<MODE>::rule>, dim3(grid), dim3(256), 0, st, P, part_stride, half_stride, ldp, nparts,
+                       rows, cols, num, den, ldo, X, ldx, eps, clamp, gamma);
     return check_launch(who);
 }
 
 // the W side into partial slabs, then the ending: (num, den) stored, or X = W updated in place
 template <int MODE>
 int pair_w_side(const char* who, const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
-                float eps, float* num, float* den, long ldo, float* X, void* ws, size_t ws_bytes, void* stream) {
+                float eps, float* num, float* den, long ldo, float* X, void* ws, size_t ws_bytes, void* stream, PairExp px = {}) {
     const int kt = kt_of(k);
     REQUIRE(kt > 0, "%s: rank k=%d unsupported (1 <= k <= %d for %s)", who, k, DNMF_TUNED_MAX_K, PairMode<MODE>::serves);
     REQUIRE(A && W && H && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n && (X || (num && den && ldo >= k)),
@@ -487,6 +504,7 @@ int pair_w_side(const char* who, const float* A, long m, long n, long lda, const
     if (!ws || ws_bytes < u.bytes || !aligned16(ws)) return fail(DNMF_EWS, "%s: workspace %zu < %zu bytes", who, ws_bytes, u.bytes);
     const int kp = 32 * kt;
     NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
+    a.pexp = px.e;
     const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
     const long half = m * kp, split = 2 * half;
     const dim3 grid((unsigned)u.rowtiles, (unsigned)u.nsplit, (unsigned)u.zdim), block(256);
@@ -501,12 +519,13 @@ int pair_w_side(const char* who, const float* A, long m, long n, long lda, const
     PW_CASE(1, 1) PW_CASE(2, 2) PW_CASE(4, 4 / PairMode<MODE>::zdim128)
 #undef PW_CASE
     if (int rc = check_launch(who)) return rc;
-    return pair_reduce<MODE>(P, split, half, kp, u.nsplit, m, k, num, den, ldo, X, ldw, eps, 0, st, who);
+    return pair_reduce<MODE>(P, split, half, kp, u.nsplit, m, k, num, den, ldo, X, ldw, eps, 0, st, who, px.gamma);
 }
 
 template <int MODE>
 int pair_h_side(const char* who, const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
-                float eps, float* num, float* den, long ldo, float* X, int clamp, void* ws, size_t ws_bytes, void* stream) {
+                float eps, float* num, float* den, long ldo, float* X, int clamp, void* ws, size_t ws_bytes, void* stream,
+                PairExp px = {}) {
     const int kt = kt_of(k);
     REQUIRE(kt > 0, "%s: rank k=%d unsupported (1 <= k <= %d for %s)", who, k, DNMF_TUNED_MAX_K, PairMode<MODE>::serves);
     REQUIRE(A && W && H && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n && (X || (num && den && ldo >= n)),
@@ -516,6 +535,7 @@ int pair_h_side(const char* who, const float* A, long m, long n, long lda, const
     const int kp = 32 * kt;
     NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
     a.ncolblk = w.ncolblk;
+    a.pexp = px.e;
     const long half = (long)kp * w.ldp;
     a.P = (float*)ws; a.ldp = w.ldp; a.chunk_stride = 2 * half;
     const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
@@ -530,7 +550,7 @@ int pair_h_side(const char* who, const float* A, long m, long n, long lda, const
     PH_CASE(1, 4) PH_CASE(2, 2) PH_CASE(4, 1)
 #undef PH_CASE
     if (int rc = check_launch(who)) return rc;
-    return pair_reduce<MODE>(a.P, a.chunk_stride, half, w.ldp, (int)w.nchunks, k, n, num, den, ldo, X, ldh, eps, clamp, st, who);
+    return pair_reduce<MODE>(a.P, a.chunk_stride, half, w.ldp, (int)w.nchunks, k, n, num, den, ldo, X, ldh, eps, clamp, st, who, px.gamma);
 }
 
 // the launch plans of both sides as numbers (host arithmetic, no GPU): what the launches above use, for callers and tests that must

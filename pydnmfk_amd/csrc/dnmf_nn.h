@@ -26,6 +26,8 @@ struct NnArgs {
                                                      // contraction indices are all padding (k <= 16: half of that product's matrix work)
     long rowtile0;                                   // kl_uht: first 128-row tile of this launch (the full tiles below it went to
                                                      // kl_uht_pipe_kernel, csrc/dnmf_kluht.h)
+    float pexp;                                      // the pair kernels' PAIR_BETA mode (csrc/dnmf_beta.h): e = beta - 2, the exponent of
+                                                     // P = (S + eps)^e; zero everywhere else (last: no other field moves)
 };
 __device__ __forceinline__ void rebase_args(NnArgs& p, const BatchTab& bt) {
     rebase(p.A, bt); rebase(p.W, bt); rebase(p.H, bt); rebase(p.out, bt); rebase(p.P, bt);

@@ -102,6 +102,12 @@ class _Base:
             else:
                 raise NotImplementedError("norm='is' is provided for method 'mu' only, not for '%s': HALS and BCD are Frobenius "
                                           "methods" % self.method)
+        elif norm == 'BETA':                                                   # (no counterpart in the reference: csrc/dnmf_beta.h)
+            if method == 'MU':
+                self.BETA_MU_update(self.W_update, clamp)
+            else:
+                raise NotImplementedError("norm='beta' is provided for method 'mu' only, not for '%s': HALS and BCD are Frobenius "
+                                          "methods" % self.method)
         else:
             raise Exception('Not a valid norm: Choose (fro/kl)')               # dist_nmf.py:91,659
 
@@ -142,6 +148,29 @@ class _Base:
             raise NotImplementedError("norm='is' runs on float32 data with the product's fp32 operator set; not provided for %s data with "
                                       "the '%s' operator set" % (str(A.dtype).replace("torch.", ""), getattr(ops, "name", "?")))
         self._pair_MU_update("isnd", ops.is_update_w, ops.is_update_h, ops.is_aht_pair, ops.is_wta_pair, ops.is_ratio_update, W_update, clamp)
+
+    # ---- the beta-divergence, -2 <= beta <= 4, MU in its majorisation-minimisation form (1D grids).  With S' = W H + eps, P = S'^(beta - 2)
+    # and F = H^T / W:  num = (A . P) F,  den = (S' . P) F,  X <- X * (num / (den + eps))^gamma(beta)   (params.beta; csrc/dnmf_beta.h)
+    def BETA_MU_update(self, W_update=True, clamp=False):
+        ops, A = self.ops, self.A_ij
+        if self.p_r != 1 and self.p_c != 1:
+            raise NotImplementedError("norm='beta' on a 2D grid (p_r = %d, p_c = %d) is not provided: use a 1D grid" % (self.p_r, self.p_c))
+        if _is_sparse(A) or _is_masked(A):
+            raise NotImplementedError("norm='beta' is provided for dense data without missing entries, not for %s"
+                                      % ("sparse data" if _is_sparse(A) else "missing='%s'" % A.missing))
+        if not hasattr(ops, "beta_update_w") or A.dtype not in getattr(ops, "beta_dtypes", ()):
+            raise NotImplementedError("norm='beta' runs on float32 data with the product's fp32 operator set; not provided for %s data with "
+                                      "the '%s' operator set" % (str(A.dtype).replace("torch.", ""), getattr(ops, "name", "?")))
+        beta = getattr(self.params, "beta", None)
+        if beta is None:
+            raise ValueError("norm='beta' needs params.beta (a float in -2 <= beta <= 4)")
+        beta = float(beta)
+        self._pair_MU_update("betand",
+                             lambda A, W, H, eps: ops.beta_update_w(A, W, H, eps, beta),
+                             lambda A, W, H, eps, clamp: ops.beta_update_h(A, W, H, eps, beta, clamp),
+                             lambda A, W, H, eps, buf: ops.beta_aht_pair(A, W, H, eps, beta, buf),
+                             lambda A, W, H, eps, buf: ops.beta_wta_pair(A, W, H, eps, beta, buf),
+                             lambda X, num, den, eps, clamp=False: ops.beta_ratio_update(X, num, den, eps, beta, clamp), W_update, clamp)
 
     # ---- BCD / Frobenius (dist_nmf.py:940-1047 in 1D, :474-579 in 2D).  The grid-specific pieces are the `_bcd_*` hooks of each
     # class: the exchanges sit exactly where the reference allreduces / gathers.  Every scalar of the method stays in the device state

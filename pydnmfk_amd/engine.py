@@ -801,6 +801,72 @@ class HipOps:
         the device tensor [1][2] of {sum (A - W H)^2, sum A^2}."""
         return self._pair_fit("is_fit", lib.dnmf_is_mu_fit, A, W, H, eps, lib.dnmf_is_ws_bytes_fit, self._is_ranks, (), w_update, itr)
 
+    # ---- the beta-divergence, -2 <= beta <= 4 (csrc/dnmf_beta.h, dnmf_beta_*): dense float32 data, 1 <= k <= 128.  With S' = W H + eps and
+    # P = S'^(beta - 2): num = (A . P) F, den = (S' . P) F (F = H^T / W), X <- X * (num / (den + eps))^gamma(beta).  `beta` follows `eps`
+    beta_dtypes = (torch.float32,)     # the data types these operations take (PyNMF and the choreography refuse any other by name)
+    BETA_RANGE = (-2.0, 4.0)
+
+    _beta_ranks = "norm='beta' with k = %d: the beta-divergence kernels serve 1 <= k <= 128"
+
+    @classmethod
+    def _beta_mode(cls, beta):
+        beta = float(beta)
+        if not cls.BETA_RANGE[0] <= beta <= cls.BETA_RANGE[1]:
+            raise ValueError("beta = %r is outside the accepted range %g <= beta <= %g" % ((beta,) + cls.BETA_RANGE))
+        return (beta,)
+
+    def _beta(self, what, A, W, H, eps, beta, pair=None):
+        return self._pair_args(what, A, W, H, eps, lib.dnmf_beta_ws_bytes, self._beta_ranks, mode=self._beta_mode(beta), pair=pair)
+
+    def _beta_pair(self, side, A, W, H, eps, beta, num, den):
+        head, tail = self._beta("beta pair", A, W, H, eps, beta, pair=(side, num, den))
+        check((lib.dnmf_beta_aht_pair if side == "w" else lib.dnmf_beta_wta_pair)(*head, *tail))
+        return num, den
+
+    def beta_aht_pair(self, A, W, H, eps, beta, buf):
+        """buf = [num | den], each m x k: (A . P) H^T and (S' . P) H^T"""
+        return self._beta_pair("w", A, W, H, eps, beta, *self._halves(buf, tuple(W.shape)))
+
+    def beta_wta_pair(self, A, W, H, eps, beta, buf):
+        """buf = [num | den], each k x n: W^T (A . P) and W^T (S' . P)"""
+        return self._beta_pair("h", A, W, H, eps, beta, *self._halves(buf, tuple(H.shape)))
+
+    def beta_pair_into(self, side, A, W, H, eps, beta, num, den):
+        """the same pair into two views of the caller's (one leading dimension, any pitch): side 'w' (m x k) or 'h' (k x n)"""
+        return self._beta_pair(side, A, W, H, eps, beta, num, den)
+
+    def beta_update_w(self, A, W, H, eps, beta):
+        """W <- W * (num / (den + eps))^gamma: the pass, then the rule on its partial sums (this rank's W rows see all their columns)"""
+        head, tail = self._beta("beta_update_w", A, W, H, eps, beta)
+        check(lib.dnmf_beta_update_w(*head, *tail))
+        return W
+
+    def beta_update_h(self, A, W, H, eps, beta, clamp=False):
+        """H <- H * (num / (den + eps))^gamma, max(., eps) with `clamp` (this rank's H columns see all their rows)"""
+        head, tail = self._beta("beta_update_h", A, W, H, eps, beta)
+        check(lib.dnmf_beta_update_h(*head, int(bool(clamp)), *tail))
+        return H
+
+    def beta_ratio_update(self, X, num, den, eps, beta, clamp=False):
+        """X <- X * (num / (den + eps))^gamma, max(., eps) with `clamp`: the rule on a pair that was summed over the ranks"""
+        a = self._ratio_args("beta_ratio_update", X, num, den, eps, clamp)
+        check(lib.dnmf_beta_ratio_update(*a[:8], *self._beta_mode(beta), *a[8:]))
+        return X
+
+    def beta_divergence(self, A, W, H, eps, beta):
+        """D_beta(A | W H + eps) over this block: one device double (stored, not accumulated: two calls are bit-identical)"""
+        head, tail = self._beta("beta_divergence", A, W, H, eps, beta)
+        out = torch.empty(1, dtype=torch.float64, device=A.device)
+        check(lib.dnmf_beta_divergence(*head, out.data_ptr(), *tail))
+        return out
+
+    def beta_fit(self, A, W, H, eps, beta, w_update, itr):
+        """`itr` beta-divergence MU steps (clamps after the steps i % 10 == 0), normalize_features and the squared norms of relative_err in
+        ONE library call (dnmf_beta_mu_fit: the launches of the step loop in its order).  One problem; W, H are updated in place; returns
+        the device tensor [1][2] of {sum (A - W H)^2, sum A^2}."""
+        return self._pair_fit("beta_fit", lib.dnmf_beta_mu_fit, A, W, H, eps, lib.dnmf_beta_ws_bytes_fit, self._beta_ranks,
+                              self._beta_mode(beta), w_update, itr)
+
     def _bcd_fit(self, A3, W3, H3, eps, w_update, itr, sfx, batched):
         """method 'bcd' (dnmf_bcd_fro_fit): float32 data; a stack of B problems is ONE library call in which every launch
         covers all of them.  Each problem keeps its own state block in its workspace slice, so the problems accept or restart
@@ -845,6 +911,7 @@ class HipOpsBf16x6(HipOps):
     name = "hip-bf16x6"
     is_dtypes = ()                 # (no split form of the Itakura-Saito pairs)
     is_nmfk = False                # (nor an NMFk sweep under norm='is')
+    beta_dtypes = ()               # (nor of the beta-divergence pairs)
     kl_uht_hblocks = None          # (no block-column variant of the split kernels: the 2D step concatenates H for them)
     aht_hblocks = None
 

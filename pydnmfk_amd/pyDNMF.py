@@ -25,6 +25,10 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
     no counterpart in the reference) -- strictly positive dense float32 data, method 'mu', 1D grids, k <= 128; on one rank the whole fit
     is one library call, dnmf_is_mu_fit; `fit()` still returns the Frobenius relative error, `is_divergence()` reports the objective and
     `is_column_divergence()` its mean per entry column by column (the per-column statistic of PyNMFk under this norm);
+  * `params.norm = 'beta'` with `params.beta` in [-2, 4]: the beta-divergence by the same kind of rule (csrc/dnmf_beta.h; scikit-learn's
+    beta_loss=<float>) under the same restrictions; data strictly positive for beta <= 0, non-negative for beta > 0; beta = 0 IS norm='is'
+    (the same bits), beta = 1 and 2 are the KL and Frobenius objectives under this family's rule, not the reference's; one library call
+    per fit on one rank (dnmf_beta_mu_fit); `beta_divergence()` reports the objective;
   * `prune=True` (the reference's default when the attribute is absent) drops all-zero rows / columns before the
     iterations and scatters the factors back afterwards.  numpy callers get float64 factors back in that case, exactly
     as from the reference (its unprune scatters into np.zeros, utils.py:195,198); tensor callers keep float32 on the GPU.
@@ -63,7 +67,8 @@ def storage_dtype(A_ij, params):
 
 
 _MASKS = ("row_zero_idx_x", "col_zero_idx_x", "row_zero_idx_w", "col_zero_idx_h")
-_NATIVE_FITS = (("mu", "fro"), ("mu", "kl"), ("hals", "fro"), ("bcd", "fro"), ("mu", "is"))
+_NATIVE_FITS = (("mu", "fro"), ("mu", "kl"), ("hals", "fro"), ("bcd", "fro"), ("mu", "is"), ("mu", "beta"))
+BETA_RANGE = (-2.0, 4.0)             # where the value of (W H + eps)^(beta - 2) at a padded position is finite in float32 (csrc/dnmf_beta.h)
 
 
 class PyNMF:
@@ -123,11 +128,19 @@ class PyNMF:
         self.params.eps = self.eps
         self.norm = var_init(self.params, 'norm', default='kl')     # :70
         self.method = var_init(self.params, 'method', default='mu')
+        self.beta = None
+        if str(self.norm).lower() == 'beta':
+            self.beta = self._beta_value(self.params)
+            # beta = 0 IS Itakura-Saito: handed to that path (its kernels, its bits), the way 'itakura-saito' is renamed
+            self.norm = self.params.norm = 'is' if self.beta == 0.0 else 'beta'
         if str(self.norm).lower() in ('is', 'itakura-saito'):
             self.norm = self.params.norm = 'is'
         self._is = (self.norm == 'is')
+        self._beta = (self.norm == 'beta')
         if self._is:
             self._is_checks(A_ij, missing)
+        if self._beta:
+            self._beta_checks(missing)
         if self.a_dtype == torch.bfloat16 and str(self.norm).lower() == 'kl':
             raise TypeError("PyNMF: bfloat16 storage of A is provided for the Frobenius updates (mu / hals) only")
         self.prune = var_init(self.params, 'prune', default=True)
@@ -253,6 +266,55 @@ class PyNMF:
                                       % (p_r, p_c))
         if k > 128:
             raise NotImplementedError("norm='is' with k = %d is not provided: the Itakura-Saito kernels serve 1 <= k <= 128" % k)
+
+    @staticmethod
+    def _beta_value(params):
+        """`params.beta` as a float inside BETA_RANGE; a missing or an out-of-range value is a ValueError"""
+        beta = getattr(params, "beta", None)
+        if beta is None:
+            raise ValueError("norm='beta' needs params.beta: a float in %g <= beta <= %g (main.py --beta)" % BETA_RANGE)
+        beta = float(beta)
+        if not BETA_RANGE[0] <= beta <= BETA_RANGE[1]:
+            raise ValueError("norm='beta' with beta = %g is outside the accepted range %g <= beta <= %g" % ((beta,) + BETA_RANGE))
+        return beta
+
+    def _beta_checks(self, missing):
+        """What is refused under norm='beta', each by name (what norm='is' refuses), and what the data must be: strictly positive for
+        beta <= 0, non-negative for beta > 0.  The ranks agree on that verdict through comm1 BEFORE any of them raises."""
+        self._beta_refusals(self.params, self._sparse, missing, self.a_dtype, self.ops, self.method, self.p_r, self.p_c, self.params.k)
+        lo = float(self.A_ij.min()) if self.A_ij.numel() else 1.0
+        bad = not (lo > 0.0 if self.beta <= 0.0 else lo >= 0.0)     # (a NaN minimum is refused as well)
+        nranks = self.p_r * self.p_c
+        nbad = int(self.comm1.allreduce(1 if bad else 0))
+        if nbad:
+            raise ValueError("norm='beta' with beta = %g needs %s data: the smallest entry of this rank's block is %g (%d of %d ranks hold "
+                             "an entry %s 0)%s" % (self.beta, "strictly positive" if self.beta <= 0.0 else "non-negative", lo, nbad, nranks,
+                                                   "<=" if self.beta <= 0.0 else "<",
+                                                   "; the divergence is infinite at a zero for beta <= 0" if self.beta <= 0.0 else ""))
+
+    @staticmethod
+    def _beta_refusals(params, sparse, missing, a_dtype, ops, method, p_r, p_c, k):
+        """the refusals of norm='beta' that need no look at the data: those of norm='is', in this norm's words"""
+        if missing is not None:
+            raise NotImplementedError("norm='beta' with missing='%s' is not provided (dense data without missing entries only)" % missing)
+        if sparse:
+            raise NotImplementedError("norm='beta' is not provided for sparse data (dense float32 data only)")
+        if a_dtype == torch.bfloat16:
+            raise NotImplementedError("norm='beta' with bfloat16 storage of the data is not provided (float32 data only)")
+        if (getattr(params, "gemm", None) or "fp32") != "fp32":
+            raise NotImplementedError("norm='beta' with --gemm %s is not provided (fp32 arithmetic only)" % params.gemm)
+        # (an operator set names the data types its beta-divergence operations take, `beta_dtypes`: the HIP kernels are float32)
+        if a_dtype not in (getattr(ops, "beta_dtypes", ()) if ops is not None else (torch.float32,)):
+            raise NotImplementedError("norm='beta' with %s data is not provided (float32 data only); cast the block to float32"
+                                      % str(a_dtype).replace("torch.", ""))
+        method = str(method).lower()
+        if method != "mu":
+            raise NotImplementedError("norm='beta' is provided for method 'mu' only, not for '%s': HALS and BCD are Frobenius methods" % method)
+        if p_r != 1 and p_c != 1:
+            raise NotImplementedError("norm='beta' on a 2D grid (%d x %d) is not provided: use a 1D grid (p_r = 1 or p_c = 1)"
+                                      % (p_r, p_c))
+        if k > 128:
+            raise NotImplementedError("norm='beta' with k = %d is not provided: the beta-divergence kernels serve 1 <= k <= 128" % k)
 
     @staticmethod
     def _is_positive(lo, comm1, nranks):
@@ -385,8 +447,11 @@ class PyNMF:
         if self._whole_fit_ok(ops):
             # one rank: the whole loop below -- steps, clamps, normalisation, both squared norms -- is ONE library call
             # (dnmf_*_fit, csrc/dnmf_fit.hip): no Python, no ctypes call and no host synchronisation inside the fit
-            sq = ops.fit(self.method, self.norm, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr,
-                         column_sweep=(getattr(self.params, "hals_sweep", None) == "columns"))
+            if self._beta:                                          # dnmf_beta_mu_fit
+                sq = ops.beta_fit(self.A_ij, self.W_i, self.H_j, self.eps, self.beta, self.W_update, self.itr)
+            else:
+                sq = ops.fit(self.method, self.norm, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr,
+                             column_sweep=(getattr(self.params, "hals_sweep", None) == "columns"))
             return self._finish(sq[0])
         # bcd: ONE trip with i = itr - 1 (pyDNMF.py:152) -- its update() runs all itr iterations (dist_nmf.py:83, params.itr)
         trips = range(self.itr - 1, self.itr) if self.method.lower() == 'bcd' else range(self.itr)
@@ -410,8 +475,8 @@ class PyNMF:
         (anything else keeps the step loop, which raises the reference's messages for invalid pairs).  `params.fit_loop =
         'python'` keeps the step loop (A/B runs, tests of the per-step API).  A NaN-marked block (missing='nan') has one with the
         'hip-masked' set: dnmf_masked_mu_fit, the launches of the step loop in its order (one problem per call: never batched)."""
-        if self._is and getattr(ops, "name", "") != "hip":
-            return False                                            # (dnmf_is_mu_fit lives in the fp32 operator set only)
+        if (self._is or self._beta) and getattr(ops, "name", "") != "hip":
+            return False                                            # (dnmf_is_mu_fit / dnmf_beta_mu_fit live in the fp32 operator set only)
         if self._masked_dense:
             return (self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") == "hip-masked" and hasattr(ops, "fit")
                     and str(self.method).lower() == "mu" and str(self.norm).lower() in ("fro", "kl")
@@ -475,7 +540,7 @@ class PyNMF:
         f0 = fits[0] if fits else None
 
         def same(f):
-            return (not f._masked_dense and not f._is and f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
+            return (not f._masked_dense and not f._is and not f._beta and f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
                     and f.A_ij.dtype == f0.A_ij.dtype and f.A_ij.device == f0.A_ij.device and f.W_i.shape == f0.W_i.shape
                     and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k) ==
                     (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k))
@@ -568,6 +633,20 @@ class PyNMF:
             W = W[self.params.row_zero_idx_x] if W.shape[0] != self.A_ij.shape[0] else W
             H = H[:, self.params.col_zero_idx_x] if H.shape[1] != self.A_ij.shape[1] else H
         d = self._ops().is_divergence(self.A_ij, W.contiguous(), H.contiguous(), self.eps)
+        self.comm1.allreduce_(d)
+        return float(d.cpu())
+
+    def beta_divergence(self):
+        """D_beta(A | W H + eps) of the CURRENT factors, summed over the grid (norm='beta': 1D grids, where every rank's block meets its own
+        W rows and H columns).  The objective the rule does not increase; `fit()` keeps returning the Frobenius relative error."""
+        if not self._beta:
+            raise ValueError("beta_divergence: this fit runs norm='%s'; the divergence is reported under norm='beta'%s"
+                             % (self.norm, " (beta = 0 is norm='is': is_divergence())" if self._is else ""))
+        W, H = self.W_i, self.H_j
+        if W.shape[0] != self.A_ij.shape[0] or H.shape[1] != self.A_ij.shape[1]:   # (held factors are the pruned ones; see column_err)
+            W = W[self.params.row_zero_idx_x] if W.shape[0] != self.A_ij.shape[0] else W
+            H = H[:, self.params.col_zero_idx_x] if H.shape[1] != self.A_ij.shape[1] else H
+        d = self._ops().beta_divergence(self.A_ij, W.contiguous(), H.contiguous(), self.eps, self.beta)
         self.comm1.allreduce_(d)
         return float(d.cpu())
 

@@ -176,6 +176,9 @@ class PyNMFk:
         from .sparse import is_sparse_input
         self._sparse = is_sparse_input(A_ij)
         self._is = str(getattr(params, "norm", None)).lower() in ("is", "itakura-saito")
+        if str(getattr(params, "norm", None)).lower() == "beta":
+            raise NotImplementedError("PyNMFk with norm='beta' is not provided: rank estimation needs a per-column statistic, which exists for "
+                                      "the Itakura-Saito member of the family alone (norm='is'); PyNMF factorises under any beta at a given k")
         if self._is:
             # the sweep asks one operation beyond a fit: the per-column divergence (the 'uniform' perturbation is multiplicative noise,
             # which is the noise the Itakura-Saito divergence is the likelihood of, and keeps positive data positive)
