@@ -66,8 +66,12 @@ def iterate(A, W, H, beta, itr, eps=EPS, W_update=True):
 def _terms(A, W, H, beta, eps):
     """the three terms of every element's divergence, already divided by beta (beta - 1): their sum is the divergence, the sum of
     their magnitudes is what its rounding error scales with"""
-    A = np.asarray(A, dtype=np.float64)
-    S = np.asarray(W, dtype=np.float64) @ np.asarray(H, dtype=np.float64) + eps
+    return terms_of(A, np.asarray(W, dtype=np.float64) @ np.asarray(H, dtype=np.float64) + eps, beta)
+
+
+def terms_of(A, S, beta):
+    """the same three terms from the model values S = s' themselves (any shape)"""
+    A, S = np.asarray(A, dtype=np.float64), np.asarray(S, dtype=np.float64)
     if beta == 1:
         pos = A > 0
         return np.where(pos, A * np.log(np.where(pos, A, 1.0) / S), 0.0), -A, S

@@ -293,6 +293,19 @@ def reference_fits(shape_k=(50, 39, 3), eps=EPS, dtype=np.float64):
 
 
 # ---- exact operands: both pairs exact in fp32, element by element, in any summation order
+def exact_factors(rs, m, n, k, qmax=3):
+    """(W, H, S = W H) in float64 from the stream `rs`: W has one nonzero per row, 2^(0..2) in a random column j(r); H = 2^(1..qmax).
+    Every S is a power of two in [2, 2^(2 + qmax)] whose float32 image absorbs eps (asserted).  No bound on any sum: the shape is free."""
+    jr = rs.randint(0, k, size=m)
+    W = np.zeros((m, k))
+    W[np.arange(m), jr] = 2.0 ** rs.randint(0, 3, size=m)
+    H = 2.0 ** rs.randint(1, qmax + 1, size=(k, n))
+    S = W @ H
+    assert np.all(S >= 2) and np.array_equal(np.log2(S), np.round(np.log2(S)))
+    assert np.array_equal((S.astype(np.float32) + np.float32(EPS)), S.astype(np.float32))          # eps is absorbed
+    return W, H, S
+
+
 def exact(m, n, k, seed=0, qmax=3):
     """The operands of tests/_exact.py::kl with A in 1..7: W has one nonzero per row, 2^(0..2) in a random column j(r); H = 2^(1..qmax).
     Every S = W[r][j(r)] H[j(r)][c] is then a power of two in [2, 2^(2 + qmax)]: eps is absorbed (it is at most half an ulp of 2, whose
@@ -302,13 +315,7 @@ def exact(m, n, k, seed=0, qmax=3):
     {"w": (num, den), "h": (num, den)}."""
     rs = np.random.RandomState(seed + 13 * m + 5 * n + 3 * k + 1)
     A = rs.randint(1, 8, size=(m, n)).astype(np.float64)
-    jr = rs.randint(0, k, size=m)
-    W = np.zeros((m, k))
-    W[np.arange(m), jr] = 2.0 ** rs.randint(0, 3, size=m)
-    H = 2.0 ** rs.randint(1, qmax + 1, size=(k, n))
-    S = W @ H
-    assert np.all(S >= 2) and np.array_equal(np.log2(S), np.round(np.log2(S)))
-    assert np.array_equal((S.astype(np.float32) + np.float32(EPS)), S.astype(np.float32))          # eps is absorbed
+    W, H, S = exact_factors(rs, m, n, k, qmax)
     R = 1.0 / S
     U = A * R * R
     ref = {"w": (U @ H.T, R @ H.T), "h": (W.T @ U, W.T @ R)}
