@@ -981,5 +981,7 @@ int dnmf_clock_probe(unsigned long long* samples, int n, int naps, void* stream)
 
 /* the beta-divergence family (dnmf_beta_*): part of this ABI, declared in a header of its own */
 #include "dnmf_beta_api.h"
+/* and its per-column statistic for rank estimation (dnmf_beta_column_div*), likewise */
+#include "dnmf_beta_nmfk_api.h"
 
 #endif /* DNMF_H */

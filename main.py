@@ -40,8 +40,8 @@ FLAGS = [
     ('fname', str, 'swim', False, 'input file name without extension'),
     ('init', str, 'rand', False, 'factor initialisation: rand / nnsvd'),
     ('itr', int, 5000, False, 'update iterations'),
-    ('norm', str, 'kl', False, 'objective: kl / fro / is / beta (is = Itakura-Saito: strictly positive float32 data, method mu, 1D grids, k <= 128; with --process pyDNMFk: uniform sampling, the per-column statistic is the mean divergence per entry; beta = the beta-divergence of --beta under the same restrictions, pyDNMF only)'),
-    ('beta', float, None, False, 'with --norm beta: the beta of the divergence, -2 <= beta <= 4 (2 = Frobenius, 1 = KL, 0 = Itakura-Saito and runs as --norm is, 0.5 is common for audio); data strictly positive for beta <= 0, non-negative for beta > 0'),
+    ('norm', str, 'kl', False, 'objective: kl / fro / is / beta (is = Itakura-Saito: strictly positive float32 data, method mu, 1D grids, k <= 128; with --process pyDNMFk: uniform sampling, the per-column statistic is the mean divergence per entry; beta = the beta-divergence of --beta under the same restrictions; with --process pyDNMFk the per-column statistic is the divergence of each column over its sum of a^beta)'),
+    ('beta', float, None, False, 'with --norm beta: the beta of the divergence, -2 <= beta <= 4 (2 = Frobenius, 1 = KL, 0 = Itakura-Saito and runs as --norm is, 0.5 is common for audio); data strictly positive for beta <= 0, non-negative for beta > 0; with --process pyDNMFk --sampling poisson needs beta > 0'),
     ('method', str, 'mu', False, 'update rule: mu / hals / bcd (bcd: Frobenius, float32 data)'),
     ('verbose', _flag, False, False, 'print the relative error of every fit'),
     ('results_path', str, 'results/', False, 'output directory'),

@@ -269,6 +269,12 @@ for _name in ("aht_pair", "wta_pair", "update_w", "update_h", "divergence", "mu_
     _sig = SIGNATURES["dnmf_is_" + _name]
     BETA_SIGNATURES["dnmf_beta_" + _name] = _sig[:10] + [c_float] + _sig[10:]
 BETA_SIGNATURES["dnmf_beta_ratio_update"] = SIGNATURES["dnmf_is_ratio_update"][:8] + [c_float] + SIGNATURES["dnmf_is_ratio_update"][8:]
+# the per-column statistic of an NMFk sweep under norm='beta' (include/dnmf_beta_nmfk_api.h), a table of its own as well (the table above
+# is pinned to the ten functions of include/dnmf_beta_api.h): A m n lda W ldw H ldh k eps beta div pw ws ws_bytes stream
+BETA_NMFK_SIGNATURES = {}
+BETA_NMFK_SIGNATURES["dnmf_beta_column_div_ws_bytes"] = [c_long, c_long, c_int]
+BETA_NMFK_SIGNATURES["dnmf_beta_column_div_plan"] = [c_long, c_long, c_int, c_void_p]      # out: long[3]
+BETA_NMFK_SIGNATURES["dnmf_beta_column_div"] = BETA_SIGNATURES["dnmf_beta_divergence"][:12] + [c_void_p] + BETA_SIGNATURES["dnmf_beta_divergence"][12:]
 # the W phase from a transposed image of A (csrc/dnmf_timg.hip): build A m n lda At ldat stream; bind the same without the stream
 SIGNATURES["dnmf_wimage_bytes"] = [c_long, c_long]
 SIGNATURES["dnmf_wimage_build"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]
@@ -276,7 +282,7 @@ SIGNATURES["dnmf_wimage_bind"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_
 SIGNATURES["dnmf_wimage_unbind"] = []
 SIGNATURES["dnmf_set_wimage"] = [c_int]
 SIGNATURES["dnmf_wimage_plan"] = [c_long, c_long, c_int, c_long, c_int, c_int, c_void_p]      # out: int[6]
-_RESTYPES = {"dnmf_beta_ws_bytes": c_size_t, "dnmf_beta_ws_bytes_fit": c_size_t, "dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
+_RESTYPES = {"dnmf_beta_column_div_ws_bytes": c_size_t, "dnmf_beta_ws_bytes": c_size_t, "dnmf_beta_ws_bytes_fit": c_size_t, "dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
              "dnmf_ws_bytes_1d": c_size_t, "dnmf_ws_bytes_hblocks": c_size_t, "dnmf_ws_bytes_2d": c_size_t,
              "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t, "dnmf_bcd_ws_bytes_fit": c_size_t}
 
@@ -287,7 +293,7 @@ def load():
             "pydnmfk_amd: %s not found. Build it with `python -m pydnmfk_amd.build` (hipcc, gfx950). "
             "There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, args in list(SIGNATURES.items()) + list(BETA_SIGNATURES.items()):
+    for name, args in list(SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BETA_NMFK_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI drifted from include/dnmf.h
         fn.argtypes = args
         fn.restype = _RESTYPES.get(name, c_int)

@@ -1,5 +1,5 @@
 // dnmf_beta.hip -- C ABI of the beta-divergence MU rule on dense data, -2 <= beta <= 4: the PAIR_BETA mode of the pair launch path of
-// csrc/dnmf_masked.h behind its ABI names, the rule on a stored pair and the divergence (csrc/dnmf_beta.h).  A translation unit of its own
+// csrc/dnmf_masked.h behind its ABI names, the rule on a stored pair, the divergence and its per-column sums (csrc/dnmf_beta.h).  A translation unit of its own
 // (see csrc/dnmf_kl.hip).  Plain launch chains: no workgroup waits for another one; no float atomics in the products or the divergence.
 #include "dnmf_common.h"
 #include "dnmf_host.h"
@@ -119,6 +119,62 @@ int dnmf_beta_divergence(const float* A, long m, long n, long lda, const float* 
     if (int rc = check_launch("beta_divergence")) return rc;
     hipLaunchKernelGGL(is_div_sum_kernel, dim3(1), dim3(256), 0, st, (const double*)P, tiles, out);
     return check_launch("beta_divergence");
+}
+
+// ---- the per-column statistic of an NMFk sweep under norm='beta' (include/dnmf_beta_nmfk_api.h): the masked per-column error's plan
+// and pair slab as they are
+size_t dnmf_beta_column_div_ws_bytes(long m, long n, int k) {
+    if (kt_of(k) < 0 || m < 1 || n < 1) return 0;
+    return align256(plan_masked_colerr(m, n, 2).bytes);
+}
+
+int dnmf_beta_column_div_plan(long m, long n, int k, long out[3]) {
+    REQUIRE(kt_of(k) > 0, "beta_column_div_plan: rank k=%d unsupported (1 <= k <= %d for the beta-divergence kernels)", k, DNMF_TUNED_MAX_K);
+    REQUIRE(out && m >= 1 && n >= 1, "beta_column_div_plan: null pointer or bad shape");
+    const MaskedColerrPlan c = plan_masked_colerr(m, n, 2);
+    out[0] = c.rowblks_per_chunk;       // 32-row blocks a wave walks (the last chunk may hold fewer)
+    out[1] = c.nchunks;
+    out[2] = c.ncolblk;                 // 128-column blocks (the last may be ragged)
+    return DNMF_OK;
+}
+
+int dnmf_beta_column_div(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps,
+                         float beta, double* div, double* pw, void* ws, size_t ws_bytes, void* stream) {
+    REQUIRE_WS16(ws, "beta_column_div");
+    const int kt = kt_of(k);
+    REQUIRE_BETA("beta_column_div");
+    REQUIRE(kt > 0, "beta_column_div: rank k=%d unsupported (1 <= k <= %d for the beta-divergence kernels)", k, DNMF_TUNED_MAX_K);
+    REQUIRE(A && W && H && div && pw && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n, "beta_column_div: null pointer or bad shape");
+    const MaskedColerrPlan cp = plan_masked_colerr(m, n, 2);
+    if (!ws || ws_bytes < cp.bytes || !aligned16(ws)) return fail(DNMF_EWS, "beta_column_div: workspace %zu < %zu bytes", ws_bytes, cp.bytes);
+    hipStream_t st = S(stream);
+    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
+    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
+    double* P = (double*)ws;
+    const dim3 grid((unsigned)cdiv(cp.nchunks * cp.ncolblk, 4)), block(256);
+    const int form = beta == 1.f ? BETA_DIV_KL : (beta == 0.f ? BETA_DIV_IS : BETA_DIV_GEN);
+    const float c = form == BETA_DIV_GEN ? (float)(1.0 / ((double)beta * ((double)beta - 1.0))) : 1.f;
+#define BC_LAUNCH(KT_, FAST_, FORM_) \
+    hipLaunchKernelGGL((beta_coldiv_kernel<KT_, FAST_, FORM_>), grid, block, 0, st, a, P, cp.ldc, cp.rowblks_per_chunk, beta, c)
+#define BC_FORM(KT_, FAST_)                                            \
+    {                                                                  \
+        if (form == BETA_DIV_KL) BC_LAUNCH(KT_, FAST_, BETA_DIV_KL);   \
+        else if (form == BETA_DIV_IS) BC_LAUNCH(KT_, FAST_, BETA_DIV_IS); \
+        else BC_LAUNCH(KT_, FAST_, BETA_DIV_GEN);                      \
+    }
+#define BC_CASE(KT_)                  \
+    if (kt == KT_) {                  \
+        if (fast) BC_FORM(KT_, true)  \
+        else BC_FORM(KT_, false)      \
+    }
+    BC_CASE(1) BC_CASE(2) BC_CASE(4)
+#undef BC_CASE
+#undef BC_FORM
+#undef BC_LAUNCH
+    if (int rc = check_launch("beta_column_div")) return rc;
+    hipLaunchKernelGGL(masked_colerr_reduce_kernel, dim3((unsigned)std::min<long>(cdiv(n, 256), 4096)), dim3(256), 0, st, (const double*)P,
+                       cp.ldc, cp.nchunks, n, div, pw);
+    return check_launch("beta_column_div");
 }
 
 // a whole beta-divergence fit: the chain of csrc/dnmf_masked.h with the beta steps; its error is the Frobenius pair, as after dnmf_is_mu_fit

@@ -141,7 +141,7 @@ class data_write:
                 'L_err': np.asarray(params['L_err']), 'L_errDist': np.asarray(params['L_errDist']),
                 'avgErr': np.asarray(params['avgErr']), 'ErrTol': np.asarray(params['recon_err']),
                 'AIC': np.asarray(params['AIC'])}
-        for key in ('is_div', 'avgDiv'):        # a sweep under norm='is' (no counterpart in the reference): other norms' files stay as they are
+        for key in ('is_div', 'beta_div', 'avgDiv', 'beta'):        # a sweep under norm='is' / 'beta' (no counterpart in the reference): other norms' files stay as they are
             if key in params:
                 data[key] = np.asarray(params[key])
         try:

@@ -860,6 +860,18 @@ class HipOps:
         check(lib.dnmf_beta_divergence(*head, out.data_ptr(), *tail))
         return out
 
+    beta_nmfk = True                   # PyNMFk looks for this and `beta_column_div`: the per-column statistic of a sweep under norm='beta'
+
+    def beta_column_div(self, A, W, H, eps, beta):
+        """(div, pw): div[c] = sum_i d_beta(A | W H + eps) and pw[c] = sum_i A^beta over this block's rows, n device doubles each, column
+        SUMS (dnmf_beta_column_div: stored, not accumulated -- two calls are bit-identical).  div / pw, after the sums have crossed the
+        ranks, is the scale-invariant per-column statistic (PyNMF.beta_column_divergence)."""
+        head, tail = self._pair_args("beta_column_div", A, W, H, eps, lib.dnmf_beta_column_div_ws_bytes, self._beta_ranks,
+                                     mode=self._beta_mode(beta))
+        out = torch.empty(2, A.shape[1], dtype=torch.float64, device=A.device)
+        check(lib.dnmf_beta_column_div(*head, out[0].data_ptr(), out[1].data_ptr(), *tail))
+        return out[0], out[1]
+
     def beta_fit(self, A, W, H, eps, beta, w_update, itr):
         """`itr` beta-divergence MU steps (clamps after the steps i % 10 == 0), normalize_features and the squared norms of relative_err in
         ONE library call (dnmf_beta_mu_fit: the launches of the step loop in its order).  One problem; W, H are updated in place; returns
@@ -912,6 +924,7 @@ class HipOpsBf16x6(HipOps):
     is_dtypes = ()                 # (no split form of the Itakura-Saito pairs)
     is_nmfk = False                # (nor an NMFk sweep under norm='is')
     beta_dtypes = ()               # (nor of the beta-divergence pairs)
+    beta_nmfk = False              # (nor an NMFk sweep under norm='beta')
     kl_uht_hblocks = None          # (no block-column variant of the split kernels: the 2D step concatenates H for them)
     aht_hblocks = None
 

@@ -28,7 +28,8 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
   * `params.norm = 'beta'` with `params.beta` in [-2, 4]: the beta-divergence by the same kind of rule (csrc/dnmf_beta.h; scikit-learn's
     beta_loss=<float>) under the same restrictions; data strictly positive for beta <= 0, non-negative for beta > 0; beta = 0 IS norm='is'
     (the same bits), beta = 1 and 2 are the KL and Frobenius objectives under this family's rule, not the reference's; one library call
-    per fit on one rank (dnmf_beta_mu_fit); `beta_divergence()` reports the objective;
+    per fit on one rank (dnmf_beta_mu_fit); `beta_divergence()` reports the objective and `beta_column_divergence()` each column's
+    divergence over its sum of a^beta (scale-invariant for every beta: the per-column statistic of PyNMFk under this norm);
   * `prune=True` (the reference's default when the attribute is absent) drops all-zero rows / columns before the
     iterations and scatters the factors back afterwards.  numpy callers get float64 factors back in that case, exactly
     as from the reference (its unprune scatters into np.zeros, utils.py:195,198); tensor callers keep float32 on the GPU.
@@ -675,6 +676,40 @@ class PyNMF:
             col[c0:c0 + ncol] = div
         self.comm1.allreduce_(col)
         return (col / float(self.params.m)).cpu().numpy()
+
+    def beta_column_divergence(self):
+        """The beta-divergence of the CURRENT factors column by column, over the GLOBAL n columns, each divided by the column's sum of
+        a^beta:  stat[c] = sum_i d_beta(a_ic | s'_ic) / sum_i a_ic^beta,  s' = W H + eps,  a^beta := 0 at a = 0 (beta > 0).  Both sums
+        scale as lambda^beta when a column is scaled by lambda, so the ratio is scale-invariant for every beta and comparable across k:
+        what an NMFk sweep under norm='beta' takes where the Frobenius `column_err()` stands.  At beta = 0 the denominator is the global
+        row count and this is `is_column_divergence()`; at beta = 2 it is column_err()^2 / 2.  A column without a positive entry has
+        no scale to divide by: nan, as from `column_err()`.  The scheme of `is_column_divergence()`: each rank fills its own column
+        range of both arrays with its sums over its own rows, one float64 allreduce (row shards add partial sums, column shards fill
+        disjoint ranges), then the ratio."""
+        if not self._beta:
+            raise ValueError("beta_column_divergence: this fit runs norm='%s'; the divergence is reported under norm='beta'%s"
+                             % (self.norm, " (beta = 0 is norm='is': is_column_divergence())" if self._is else ""))
+        from .utils import determine_block_params
+        blk = determine_block_params(self.comm1, (self.p_r, self.p_c), (self.params.m, self.params.n))
+        c0 = blk.determine_block_index_range_asymm()[0][1]
+        ncol = blk.determine_block_shape_asymm()[1]
+        W, H = self.W_i, self.H_j
+        if W.shape[0] != self.A_ij.shape[0] or H.shape[1] != self.A_ij.shape[1]:   # factors were un-pruned by fit()
+            W = W[self.params.row_zero_idx_x] if W.shape[0] != self.A_ij.shape[0] else W
+            H = H[:, self.params.col_zero_idx_x] if H.shape[1] != self.A_ij.shape[1] else H
+        div, pw = self._ops().beta_column_div(self.A_ij, W.contiguous(), H.contiguous(), self.eps, self.beta)
+        col = torch.zeros(2, self.params.n, dtype=torch.float64, device=div.device)        # [div | pw]: ONE allreduce carries both
+        keep = getattr(self.params, "col_zero_idx_x", None) if self.prune else None
+        if keep is not None and int(keep.numel()) == ncol and div.numel() != ncol:
+            col[0, c0:c0 + ncol][keep] = div            # (a pruned all-zero column keeps 0 / 0)
+            col[1, c0:c0 + ncol][keep] = pw
+        else:
+            col[0, c0:c0 + ncol] = div
+            col[1, c0:c0 + ncol] = pw
+        self.comm1.allreduce_(col)
+        col = col.cpu().numpy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(col[1] > 0.0, col[0] / col[1], np.nan)
 
     def column_err(self):
         """pyDNMF.py:221-239: per-column relative error sqrt(sum_i (A - W H)^2 / sum_i A^2) over the GLOBAL n columns

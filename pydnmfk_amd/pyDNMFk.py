@@ -17,6 +17,10 @@ observed: the raw array is kept, every perturbed copy keeps its NaNs, and the pe
 divergence is the likelihood of --, what PyNMF refuses under the norm is refused at construction): the per-column statistic `L_err` is
 the mean divergence per entry of each column (PyNMF.is_column_divergence) instead of the scale-dependent Frobenius column error, and the
 statistics gain 'is_div' (per perturbation) and 'avgDiv'; recon_err, avgErr and AIC keep their Frobenius definitions.
+`params.norm = 'beta'` with `params.beta` in [-2, 4] is swept likewise (beta = 0 IS norm='is' and takes that path): data strictly positive
+for beta <= 0 and non-negative for beta > 0, checked once; 'poisson' sampling for beta > 0 only; `L_err` is the divergence of each column
+over the column's sum of a^beta (PyNMF.beta_column_divergence: scale-invariant for every beta; the Itakura-Saito statistic at beta = 0,
+half the squared Frobenius column error at beta = 2); the statistics gain 'beta_div' (per perturbation), 'avgDiv' and 'beta'.
 """
 import os
 
@@ -176,9 +180,21 @@ class PyNMFk:
         from .sparse import is_sparse_input
         self._sparse = is_sparse_input(A_ij)
         self._is = str(getattr(params, "norm", None)).lower() in ("is", "itakura-saito")
+        self._beta, self.beta = False, None
         if str(getattr(params, "norm", None)).lower() == "beta":
-            raise NotImplementedError("PyNMFk with norm='beta' is not provided: rank estimation needs a per-column statistic, which exists for "
-                                      "the Itakura-Saito member of the family alone (norm='is'); PyNMF factorises under any beta at a given k")
+            # first of all: the sweep asks one operation beyond a fit, the per-column divergence with the column's sum of a^beta
+            if ops is None:
+                from .engine import HIP_OPS as opset
+            else:
+                opset = ops
+            if not (getattr(opset, "beta_nmfk", False) and hasattr(opset, "beta_column_div")):
+                raise NotImplementedError("PyNMFk with norm='beta' is not provided by operator set %r: rank estimation under a "
+                                          "beta-divergence needs a per-column divergence (PyNMF factorises at a given k)"
+                                          % (getattr(opset, "name", type(opset).__name__),))
+            self.beta = PyNMF._beta_value(params)
+            # beta = 0 IS Itakura-Saito: renamed, as PyNMF renames it, and swept on that path unchanged
+            self._is, self._beta = self.beta == 0.0, self.beta != 0.0
+            params.norm = 'is' if self._is else 'beta'
         if self._is:
             # the sweep asks one operation beyond a fit: the per-column divergence (the 'uniform' perturbation is multiplicative noise,
             # which is the noise the Itakura-Saito divergence is the likelihood of, and keeps positive data positive)
@@ -192,7 +208,7 @@ class PyNMFk:
                                           "Itakura-Saito objective needs a per-column divergence (PyNMF factorises at a given k)"
                                           % (getattr(opset, "name", type(opset).__name__),))
         self._masked = getattr(params, "missing", None) == "nan" and not self._sparse
-        if self._masked and not self._is:           # (norm='is' refuses missing= and sparse data by name in _is_setup)
+        if self._masked and not (self._is or self._beta):           # (norm='is' and norm='beta' refuse missing= and sparse data by name in their setup)
             # as for a sparse block, the sweep touches A outside PyNMF.fit in the perturbed copy (NaN stays NaN through the
             # multiplication) and in the per-column error, which must run over the observed positions
             if ops is None:
@@ -203,7 +219,7 @@ class PyNMFk:
                 raise NotImplementedError("PyNMFk with missing='nan' is not provided by operator set %r: rank estimation over NaN-marked "
                                           "data needs a masked per-column error (PyNMF factorises such data at a given k)"
                                           % (getattr(opset, "name", type(opset).__name__),))
-        if self._sparse and not self._is:
+        if self._sparse and not (self._is or self._beta):
             # the sweep touches A outside PyNMF.fit in two operations: the perturbed copy and the per-column error
             if ops is None:
                 from .engine import HIP_CSR_OPS as opset
@@ -270,6 +286,8 @@ class PyNMFk:
         self.sweep = None
         if self._is:
             self._is_setup(A_ij)            # (first: sparse data and missing= are refused in the norm's words)
+        if self._beta:
+            self._beta_setup(A_ij)
         if self._sparse:
             self._sparse_setup(A_ij)
         if self._masked:
@@ -294,6 +312,35 @@ class PyNMFk:
                 raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
         lo = float(A_ij.min()) if int(np.prod(A_ij.shape)) else 1.0
         PyNMF._is_positive(lo, self.comm1, self.p)
+
+    def _beta_setup(self, A_ij):
+        """norm='beta' (beta != 0): what PyNMF refuses under it is refused here, at construction, in its words (the sweep's largest rank
+        stands for k), and the data's sign is checked ONCE, before the first fit -- strictly positive for beta <= 0, non-negative for
+        beta > 0; the ranks agree on the verdict before any of them raises.  The 'uniform' perturbation keeps either property
+        (1 + nv + 2 nv U > 0).  'poisson' sampling is refused for beta <= 0, where a draw of 0 makes the divergence infinite; for
+        beta > 0 a zero is legal data and the sampling is allowed."""
+        from .pyDNMF import storage_dtype
+        params, beta = self.params, self.beta
+        a_dtype = torch.float32 if self._sparse else storage_dtype(A_ij, params)
+        PyNMF._beta_refusals(params, self._sparse, getattr(params, "missing", None), a_dtype, self.ops,
+                             var_init(params, 'method', default='mu'), self.p_r, self.p_c, int(self.end_k))
+        if self.sampling == 'poisson' and beta <= 0.0:
+            raise NotImplementedError("PyNMFk with norm='beta', beta = %g and sampling='poisson' is not provided: a Poisson draw of 0 makes "
+                                      "the divergence infinite for beta <= 0 (sampling='uniform', multiplicative noise, keeps the data "
+                                      "positive; 'poisson' is accepted for beta > 0)" % beta)
+        if self.ops is None:
+            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda:
+                raise TypeError("PyNMFk: A_ij is a CPU tensor; pass a CUDA tensor or a numpy array (no CPU fallback)")
+            if not torch.cuda.is_available():
+                raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
+        lo = float(A_ij.min()) if int(np.prod(A_ij.shape)) else 1.0
+        bad = not (lo > 0.0 if beta <= 0.0 else lo >= 0.0)          # (a NaN minimum is refused as well)
+        nbad = int(self.comm1.allreduce(1 if bad else 0))
+        if nbad:
+            raise ValueError("norm='beta' with beta = %g needs %s data: the smallest entry of this rank's block is %g (%d of %d ranks hold "
+                             "an entry %s 0)%s" % (beta, "strictly positive" if beta <= 0.0 else "non-negative", lo, nbad, self.p,
+                                                   "<=" if beta <= 0.0 else "<",
+                                                   "; the divergence is infinite at a zero for beta <= 0" if beta <= 0.0 else ""))
 
     def _masked_setup(self, A_ij):
         """missing='nan': the raw array stays `self.A_ij` (every PyNMF wraps its perturbed copy in a MaskedDenseBlock itself); what PyNMF
@@ -360,7 +407,7 @@ class PyNMFk:
         if self.rank == 0:
             os.makedirs(self.params.results_paths, exist_ok=True)
         results = []
-        divs = []                    # norm='is': the total divergence of every perturbation's fit
+        divs = []                    # norm='is' / 'beta': the total divergence of every perturbation's fit
         if self.rank == 0:
             print('*************Computing for k=', self.k, '************')
         perturbation = 0
@@ -399,11 +446,13 @@ class PyNMFk:
             results.extend(PyNMF.fit_batch(fits))
             if self._is:
                 divs.extend(f.is_divergence() for f in fits)
+            elif self._beta:
+                divs.extend(f.beta_divergence() for f in fits)
             for perturbation in chunk:
                 self.cp._save_checkpoint(self.params.flag, perturbation, self.k)
             del fits, stack
         if shared:
-            results, divs = self._gather_fits(results, mine, divs if self._is else None)
+            results, divs = self._gather_fits(results, mine, divs if (self._is or self._beta) else None)
             perturbation = self.perturbations - 1
         self.params.flag = 1
         self.cp._save_checkpoint(self.params.flag, perturbation, self.k)
@@ -446,7 +495,9 @@ class PyNMFk:
         self.AvgW, self.AvgH, self.L_errDist = regressH.fit()                                           # :246-247
         # :248.  Under norm='is' the per-column statistic is the mean Itakura-Saito divergence per entry: the Frobenius column_err
         # weights the columns by their scale, which is what a user who chose this norm wanted to avoid
-        self.col_err = regressH.is_column_divergence() if self._is else regressH.column_err()
+        # and under norm='beta' the divergence of each column over its sum of a^beta, scale-invariant for every beta
+        self.col_err = (regressH.is_column_divergence() if self._is else regressH.beta_column_divergence() if self._beta
+                        else regressH.column_err())
         self.avgErr = float(np.mean(self.recon_err))
         mn = self.params.m * self.params.n      # (sparse data too, under both meanings of an unstored entry, and NaN-marked data: DESIGN.md section 7)
         self.AIC = 2 * self.k + mn * np.log(self.avgErr / mn)                                           # :250
@@ -456,6 +507,9 @@ class PyNMFk:
         if self._is:                            # (recon_err, avgErr and AIC keep their Frobenius definitions)
             self.is_div = [float(d) for d in divs]
             cluster_stats['is_div'], cluster_stats['avgDiv'] = self.is_div, float(np.mean(self.is_div))
+        if self._beta:
+            self.beta_div = [float(d) for d in divs]
+            cluster_stats['beta_div'], cluster_stats['avgDiv'], cluster_stats['beta'] = self.beta_div, float(np.mean(self.beta_div)), self.beta
         self.stats[self.k] = cluster_stats
         if getattr(self.params, "ftype", None) is None:
             self.params.ftype = None
@@ -469,7 +523,7 @@ class PyNMFk:
     def _gather_fits(self, results, mine, divs=None):
         """Perturbation-shared sweep: every rank has fitted its own perturbations; all ranks end with all (W, H, err) in
         perturbation order.  One allgather of the stacked factors per k (ranks with one perturbation fewer pad their stack).
-        `divs` (norm='is'): this rank's divergences, carried as the errors are.  Returns (fits, divergences or None)."""
+        `divs` (norm='is', norm='beta'): this rank's divergences, carried as the errors are.  Returns (fits, divergences or None)."""
         world, P = self.world, self.perturbations
         numpy_io = bool(results) and not isinstance(results[0][0], torch.Tensor)
         dev = torch.device("cuda", torch.cuda.current_device()) if (self.ops is None and torch.cuda.is_available()) else torch.device("cpu")
@@ -509,7 +563,7 @@ class PyNMFk:
         operators -- as many as fit next to each other in the GPU's free memory (each holds its perturbed copy of the data) --
         else 1.  `params.nmfk_batch` = False / 0 / 1 keeps the one-by-one fits, an integer caps the batch."""
         want = getattr(self.params, "nmfk_batch", True)
-        if self._sparse or self._masked or self._is:          # no batched sparse, masked or Itakura-Saito entry point: the fits run one by one, no stack is allocated
+        if self._sparse or self._masked or self._is or self._beta:          # no batched sparse, masked, Itakura-Saito or beta-divergence entry point: the fits run one by one, no stack is allocated
             return 1
         if want is False or self.p != 1 or self.ops is not None or not torch.cuda.is_available():
             return 1

@@ -5,7 +5,8 @@
 One MI355X; 32768 x 16384 at k = 32, 64, 128 and 65536 x 4096 at k = 64; A uniform in [0.05, 1.05), factors uniform.  A step is one
 `nmf_algorithms_1D(...).update()` on one rank (both factors, the fused endings).  The two steps are timed back to back -- beta, then IS,
 `--steps` times after `--warmup` of each -- every step with its own pair of HIP events; the figures are medians (min / max next to
-them).  The two sides of both steps and the divergence are timed on their own as well.  Both steps run the same pair kernels with the
+them).  The two sides of both steps, the divergence and the per-column sums of an NMFk sweep (dnmf_beta_column_div next to
+dnmf_is_column_div, once per k of a sweep) are timed on their own as well.  Both steps run the same pair kernels with the
 same launch plans on the same bytes; the beta step's element-wise work is six vector instructions per element (v_add, v_log, v_mul,
 v_exp, two v_mul) where the IS step has four (v_add, v_rcp, two v_mul): the ratio shows what the extra transcendental pair costs.
 The cost does not depend on the value of beta (the ending's powf runs over m k + k n elements, and not at all for 1 <= beta <= 2).
@@ -44,6 +45,8 @@ def bench(m, n, k, beta, steps, warmup, seed=0):
         "is_update_h": lambda: HIP_OPS.is_update_h(A, W, H, EPS),
         "beta_divergence": lambda: HIP_OPS.beta_divergence(A, W, H, EPS, beta),
         "is_divergence": lambda: HIP_OPS.is_divergence(A, W, H, EPS),
+        "beta_column_div": lambda: HIP_OPS.beta_column_div(A, W, H, EPS, beta),
+        "is_column_div": lambda: HIP_OPS.is_column_div(A, W, H, EPS),
     }
     for _ in range(warmup):
         for fn in fns.values():
@@ -55,7 +58,7 @@ def bench(m, n, k, beta, steps, warmup, seed=0):
             ts[name].append(_event_ms(fn))
     out = {"m": m, "n": n, "k": k, "beta": beta}
     out.update({name: _stats(v) for name, v in ts.items()})
-    for what in ("step", "update_w", "update_h", "divergence"):
+    for what in ("step", "update_w", "update_h", "divergence", "column_div"):
         out["ratio_%s" % what] = out["beta_" + what]["median_ms"] / out["is_" + what]["median_ms"]
     assert torch.isfinite(W).all() and torch.isfinite(H).all()
     return out
@@ -73,14 +76,15 @@ def main():
     shapes = (tuple(int(x) for x in opt.only.split(",")),) if opt.only else SHAPES
     rows = [bench(m, n, k, opt.beta, opt.steps, opt.warmup) for m, n, k in shapes]
     print("| m x n | k | beta | beta step ms (min-max) | IS step ms (min-max) | beta / IS | W side: beta ms | IS ms | ratio | H side: beta ms | IS ms | ratio | "
-          "divergence: beta ms | IS ms |")
-    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+          "divergence: beta ms | IS ms | per-column: beta ms | IS ms | ratio |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
     for r in rows:
         t = lambda key: "%.3f (%.3f-%.3f)" % (r[key]["median_ms"], r[key]["min_ms"], r[key]["max_ms"])      # noqa: E731
         md = lambda key: r[key]["median_ms"]                                                                 # noqa: E731
-        print("| %d x %d | %d | %g | %s | %s | %.2f | %.3f | %.3f | %.2f | %.3f | %.3f | %.2f | %.3f | %.3f |" % (
+        print("| %d x %d | %d | %g | %s | %s | %.2f | %.3f | %.3f | %.2f | %.3f | %.3f | %.2f | %.3f | %.3f | %.3f | %.3f | %.2f |" % (
             r["m"], r["n"], r["k"], r["beta"], t("beta_step"), t("is_step"), r["ratio_step"], md("beta_update_w"), md("is_update_w"),
-            r["ratio_update_w"], md("beta_update_h"), md("is_update_h"), r["ratio_update_h"], md("beta_divergence"), md("is_divergence")))
+            r["ratio_update_w"], md("beta_update_h"), md("is_update_h"), r["ratio_update_h"], md("beta_divergence"), md("is_divergence"),
+            md("beta_column_div"), md("is_column_div"), r["ratio_column_div"]))
     if opt.json:
         os.makedirs(os.path.dirname(os.path.abspath(opt.json)), exist_ok=True)
         with open(opt.json, "w") as f:
