@@ -53,19 +53,21 @@
 //   <4, 4, false>                                 256   157     0        1           <4, 1, false>                                 197   128     0        1
 // (the waves per SIMD are those of the launch bounds, as for the other modes).  JT = 4 at KP = 128 does not spill, so the W side takes
 // the Itakura-Saito plan there (one pass over S), not the masked plan's JT = 2.  masked_reduce_kernel<RULE_POW>: 33 VGPRs;
-// beta_ratio_kernel: 29; beta_div_kernel: 91 to 166 VGPRs + 64 AGPRs; none uses scratch.
-//   beta_coldiv_kernel<KT, FAST, FORM>   GEN: VGPR  AGPR  scratch    KL: VGPR  AGPR  scratch    IS: VGPR  AGPR  scratch    (one wave per SIMD)
-//   <1, true>                                  229    64     0           226    64     0           222    64     0
-//   <1, false>                                 230    64     0           228    64     0           224    64     0
-//   <2, true>                                  256    70     0           256    67     0           255    64     0
-//   <2, false>                                 256    72     0           256    70     0           256    67     0
-//   <4, true>                                  256   136     0           256   132     0           256   128     0
-//   <4, false>                                 256   140     0           256   136     0           256   134     0
-// (the launch bounds of 256 allow 512 registers per lane; no instantiation spills).  masked_colerr_reduce_kernel (csrc/dnmf_masked.h),
-// the ending, is launched as it is.
+// pair_ratio_kernel<RULE_POW>: 29; tile_sum_kernel<KT, FAST, BetaDivTerm<FORM, 1>> (csrc/dnmf_sums.h): 91 to 166 VGPRs + 64 AGPRs (KL
+// 94 / 91 at three waves per SIMD, IS 136 / 134 and GEN 138 / 166 at two, FAST / generic, the same at every KT); none uses scratch.
+// The per-column walk with two sums (csrc/dnmf_sums.h; one wave per SIMD):
+//   <KT, FAST>    GEN, beta_coldiv_kernel: VGPR  AGPR  scratch    KL, col_sums_kernel: VGPR  AGPR  scratch    IS, col_sums_kernel: VGPR  AGPR  scratch
+//   <1, true>                               229    64     0                             226    64     0                             222    64     0
+//   <1, false>                              230    64     0                             228    64     0                             224    64     0
+//   <2, true>                               256    70     0                             256    67     0                             255    64     0
+//   <2, false>                              256    72     0                             256    70     0                             256    67     0
+//   <4, true>                               256   136     0                             256   132     0                             256   128     0
+//   <4, false>                              256   140     0                             256   136     0                             256   134     0
+// (the launch bounds of 256 allow 512 registers per lane; no instantiation spills; KL and IS are col_sums_kernel<KT, FAST,
+// BetaDivTerm<FORM, 2>>, the general form keeps its own kernel for the reason written there).  col_sums_reduce_kernel<2>, the ending:
+// 18 VGPRs.
 #pragma once
 #include "dnmf_masked.h"
-#include "dnmf_is.h"        // is_div_sum_kernel: the fixed-order sum of the divergence's slots
 
 namespace {
 
@@ -88,130 +90,30 @@ struct PairMode<PAIR_BETA> {
     static constexpr const char* serves = "the beta-divergence kernels";
 };
 
-// ---- the rule on a stored pair (after its allreduce on a 1D grid): pair_rule's RULE_POW form, as in the ending
-__global__ __launch_bounds__(256) void beta_ratio_kernel(float* __restrict__ X, long rows, long cols, long ldx, const float* __restrict__ num,
-                                                         const float* __restrict__ den, long ldo, float eps, int clamp, float gamma) {
-    const long total = rows * cols;
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const long r = idx / cols, c = idx % cols;
-        X[r * ldx + c] = pair_rule<RULE_POW>(X[r * ldx + c], num[r * ldo + c], den[r * ldo + c], eps, clamp, gamma);
-    }
-}
-
-// ---- D_beta(A | W H + eps): is_div_kernel's structure (csrc/dnmf_is.h: a wave per 32 x 128 tile of S in accumulators, fp32 per tile
-// and lane (64 terms), float64 from there on, ONE double per wave in its own slot of P, the slots added in a fixed order by
-// is_div_sum_kernel: no atomics, bit-reproducible) with another term.  FORM picks it:
-//   BETA_DIV_GEN  (a^beta + (beta - 1) s'^beta - beta a s'^(beta - 1)) / (beta (beta - 1)), as s'^(beta - 1) ((beta - 1) s' - beta a) + a^beta
-//                 times c = 1 / (beta (beta - 1)) from the host; a^beta at a = 0 is SELECTED to 0 (beta > 0; log2 0 = -inf never meets it)
-//   BETA_DIV_KL   beta = 1, where that form is singular: a log(a / s') - a + s', and s' where a = 0
-//   BETA_DIV_IS   beta = 0, singular as well: q - log q - 1, q = a / s' (is_div_kernel's term)
-// The library log2f / exp2f / logf here (not the one-instruction forms of the pair): this kernel runs once per report, not per step.
-// Outside the block the term is SELECTED away, never multiplied.
-enum { BETA_DIV_GEN = 0, BETA_DIV_KL = 1, BETA_DIV_IS = 2 };
-// the term and, in `pw`, a^beta of the same element (the general form computes it anyway; a at beta = 1, 1 at beta = 0): what the
-// per-column statistic below divides by.  beta_div_kernel drops it; its term is the same expression as before.
-template <int FORM>
-__device__ __forceinline__ float beta_div_term_pw(float a, float sp, float beta, float c, float& pw) {
-    if constexpr (FORM == BETA_DIV_KL) {
-        pw = a;
-        return a > 0.f ? a * logf(a / sp) - a + sp : sp;
-    } else if constexpr (FORM == BETA_DIV_IS) {
-        pw = 1.f;
-        const float q = kl_quot(a, sp);
-        return (q - 1.f) - logf(q);
-    } else {
-        const float sb1 = exp2f((beta - 1.f) * log2f(sp));          // s'^(beta - 1)
-        const float ab = a > 0.f ? exp2f(beta * log2f(a)) : 0.f;    // a^beta, 0 at a = 0
-        pw = ab;
-        return (ab + sb1 * ((beta - 1.f) * sp - beta * a)) * c;
-    }
-}
-template <int FORM>
-__device__ __forceinline__ float beta_div_term(float a, float sp, float beta, float c) {
-    float pw;
-    return beta_div_term_pw<FORM>(a, sp, beta, c, pw);
-}
-
-template <int KT, bool FAST, int FORM>
-__global__ __launch_bounds__(256) void beta_div_kernel(NnArgs p, double* __restrict__ P, float beta, float c) {
-    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
-    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long gw = (long)blockIdx.x * 4 + wid;
-    if (gw >= p.nrowblk * p.ncolblk) return;
-    const long row0 = (gw / p.ncolblk) * 32, col0 = (gw % p.ncolblk) * 128;
-    f32x16 acc[4];
-    nn_tile<KT, 4, FAST, false>(acc, p.W, p.ldw, p.m, p.k, p.H, p.ldh, p.n, row0, col0, li, h);
-    float part = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const long row = row0 + crow(r, h);
-        float a[4];
-        load_vec<4, FAST>(a, p.A + row * p.lda, col0 + 4 * li, p.n, row < p.m);
-#pragma unroll
-        for (int ne = 0; ne < 4; ++ne) {
-            const float t = beta_div_term<FORM>(a[ne], acc[ne][r] + p.eps, beta, c);
-            part += (row < p.m && col0 + 4 * li + ne < p.n) ? t : 0.f;
-        }
-    }
-    double total = (double)part;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) total += __shfl_xor(total, off, 64);
-    if (lane == 0) P[gw] = total;
-}
-
-// ---- the divergence column by column, with the column's sum of a^beta next to it: div[c] = sum_i d_beta(a_ic | s'_ic) and
+// ---- the rule on a stored pair is pair_ratio_kernel<RULE_POW> (csrc/dnmf_masked.h).  The divergence D_beta(A | W H + eps) is
+// tile_sum_kernel of csrc/dnmf_sums.h with the term BetaDivTerm<FORM, 1>, FORM and the constant c from beta_form below.
+//
+// The divergence column by column, with the column's sum of a^beta next to it: div[c] = sum_i d_beta(a_ic | s'_ic) and
 // pw[c] = sum_i a_ic^beta over this block's rows (PyNMF.beta_column_divergence divides the one by the other after the sums have crossed
 // the ranks: both scale as lambda^beta with a column's scale, so the ratio is the scale-invariant per-column statistic of an NMFk sweep
-// under norm='beta'; at beta = 0 pw is the row count and the ratio is_coldiv_kernel's mean per entry).  is_coldiv_kernel's structure
-// (csrc/dnmf_is.h) with beta_div_kernel's term: a wave owns a 128-column block and a chunk of 32-row blocks; fp32 over the 16 rows a
-// lane holds of one row block, float64 from there on, one shuffle joins the lane halves.  The chunk's pair goes to its own slab row in
-// the masked per-column error's layout, P[chunk][half][ldc] with ldc = ncolblk * 128 (plan_masked_colerr(m, n, 2); every store is
-// inside the slab), and masked_colerr_reduce_kernel adds the rows in chunk order and STORES div[c], pw[c]: no atomics, nothing
-// accumulated into the outputs.  Outside the block BOTH terms are SELECTED away, never multiplied (for beta <= 0 the padded a = 0 gives
-// log2 0 = -inf and a^beta = inf there).
-template <int KT, bool FAST, int FORM>
-__global__ __launch_bounds__(256) void beta_coldiv_kernel(NnArgs p, double* __restrict__ P, long ldc, long rowblks_per_chunk, float beta,
-                                                          float c) {
-    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
-    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long gw = (long)blockIdx.x * 4 + wid;
-    const long nchunks = cdiv(p.nrowblk, rowblks_per_chunk);
-    if (gw >= nchunks * p.ncolblk) return;
-    const long chunk = gw / p.ncolblk, colblk = gw % p.ncolblk;
-    const long col0 = colblk * 128;
-    double dv[4] = {0.0, 0.0, 0.0, 0.0}, dp[4] = {0.0, 0.0, 0.0, 0.0};
-    long rb1 = (chunk + 1) * rowblks_per_chunk;
-    if (rb1 > p.nrowblk) rb1 = p.nrowblk;
-    for (long rb = chunk * rowblks_per_chunk; rb < rb1; ++rb) {
-        const long row0 = rb * 32;
-        f32x16 acc[4];
-        nn_tile<KT, 4, FAST, false>(acc, p.W, p.ldw, p.m, p.k, p.H, p.ldh, p.n, row0, col0, li, h);
-        float pv[4] = {0.f, 0.f, 0.f, 0.f}, pp[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const long row = row0 + crow(r, h);
-            float a[4];
-            load_vec<4, FAST>(a, p.A + row * p.lda, col0 + 4 * li, p.n, row < p.m);
-#pragma unroll
-            for (int ne = 0; ne < 4; ++ne) {
-                float w;
-                const float t = beta_div_term_pw<FORM>(a[ne], acc[ne][r] + p.eps, beta, c, w);
-                const bool in = row < p.m && col0 + 4 * li + ne < p.n;
-                pv[ne] += in ? t : 0.f;
-                pp[ne] += in ? w : 0.f;
-            }
-        }
-#pragma unroll
-        for (int ne = 0; ne < 4; ++ne) { dv[ne] += (double)pv[ne]; dp[ne] += (double)pp[ne]; }
-    }
-    double* Pv = P + chunk * 2 * ldc + col0 + 4 * li;
-    double* Pp = Pv + ldc;
-#pragma unroll
-    for (int ne = 0; ne < 4; ++ne) {
-        dv[ne] += __shfl_xor(dv[ne], 32, 64);
-        dp[ne] += __shfl_xor(dp[ne], 32, 64);
-        if (h == 0) { Pv[ne] = dv[ne]; Pp[ne] = dp[ne]; }
-    }
+// under norm='beta'; at beta = 0 pw is the row count and the ratio the Itakura-Saito mean per entry).  It is col_sums_kernel with the
+// term BetaDivTerm<FORM, 2> (the general form: beta_coldiv_kernel, the same walk kept as first written, see csrc/dnmf_sums.h): the chunk's
+// pair goes to its own slab rows in the masked per-column error's layout, P[chunk][half][ldc].
+
+// which expression serves this beta, and its constant: the general form is singular at beta = 1 and beta = 0
+struct BetaForm { int form; float c; };
+inline BetaForm beta_form(float beta) {
+    const int form = beta == 1.f ? BETA_DIV_KL : (beta == 0.f ? BETA_DIV_IS : BETA_DIV_GEN);
+    return BetaForm{form, form == BETA_DIV_GEN ? (float)(1.0 / ((double)beta * ((double)beta - 1.0))) : 1.f};
+}
+
+// f(term) with the BetaDivTerm<FORM, NSUM> of this beta
+template <int NSUM, class F>
+int with_beta_term(float beta, F f) {
+    const BetaForm bf = beta_form(beta);
+    if (bf.form == BETA_DIV_KL) return f(BetaDivTerm<BETA_DIV_KL, NSUM>{beta, bf.c});
+    if (bf.form == BETA_DIV_IS) return f(BetaDivTerm<BETA_DIV_IS, NSUM>{beta, bf.c});
+    return f(BetaDivTerm<BETA_DIV_GEN, NSUM>{beta, bf.c});
 }
 
 }  // namespace

@@ -44,115 +44,11 @@ struct PairMode<PAIR_IS> {
     static constexpr const char* serves = "the Itakura-Saito kernels";
 };
 
-// ---- the rule on a stored pair (after its allreduce on a 1D grid): pair_rule's square-root form, as in the ending
-__global__ __launch_bounds__(256) void is_ratio_kernel(float* __restrict__ X, long rows, long cols, long ldx, const float* __restrict__ num,
-                                                       const float* __restrict__ den, long ldo, float eps, int clamp) {
-    const long total = rows * cols;
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const long r = idx / cols, c = idx % cols;
-        X[r * ldx + c] = pair_rule<RULE_SQRT>(X[r * ldx + c], num[r * ldo + c], den[r * ldo + c], eps, clamp);
-    }
-}
-
-// ---- D_IS(A | W H + eps) = sum (q - log q - 1), q = a / (s + eps): masked_resid_kernel's tiles (a wave per 32 x 128 tile of S in
-// accumulators) with another term.  fp32 per tile and lane (64 terms), float64 from there on; a wave leaves ONE double in its own slot
-// of P (lanes added by a fixed shuffle tree) and is_div_sum_kernel adds the slots in a fixed order: no atomics, bit-reproducible.
-// Outside the block a = 0 and s = 0 give q = 0 and log q = -inf: the term is SELECTED away, never multiplied.
-template <int KT, bool FAST>
-__global__ __launch_bounds__(256) void is_div_kernel(NnArgs p, double* __restrict__ P) {
-    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
-    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long gw = (long)blockIdx.x * 4 + wid;
-    if (gw >= p.nrowblk * p.ncolblk) return;
-    const long row0 = (gw / p.ncolblk) * 32, col0 = (gw % p.ncolblk) * 128;
-    f32x16 acc[4];
-    nn_tile<KT, 4, FAST, false>(acc, p.W, p.ldw, p.m, p.k, p.H, p.ldh, p.n, row0, col0, li, h);
-    float part = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const long row = row0 + crow(r, h);
-        float a[4];
-        load_vec<4, FAST>(a, p.A + row * p.lda, col0 + 4 * li, p.n, row < p.m);
-#pragma unroll
-        for (int ne = 0; ne < 4; ++ne) {
-            const float q = kl_quot(a[ne], acc[ne][r] + p.eps);
-            const float t = (q - 1.f) - logf(q);
-            part += (row < p.m && col0 + 4 * li + ne < p.n) ? t : 0.f;
-        }
-    }
-    double total = (double)part;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) total += __shfl_xor(total, off, 64);
-    if (lane == 0) P[gw] = total;
-}
-
-// one workgroup: thread t adds the slots t, t + 256, ... in that order, then a fixed tree over the 256 sums
-__global__ __launch_bounds__(256) void is_div_sum_kernel(const double* __restrict__ P, long nparts, double* __restrict__ out) {
-    __shared__ double sh[256];
-    double s = 0.0;
-    for (long i = threadIdx.x; i < nparts; i += 256) s += P[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = sh[0];
-}
-
-// ---- per-column divergence, div[c] = sum_i (q - log q - 1) over this block's rows (PyNMF.is_column_divergence: the per-column statistic
-// of an NMFk sweep under norm='is'): masked_colerr_kernel's structure (csrc/dnmf_masked.h) with is_div_kernel's term.  A wave owns a
-// 128-column block and a chunk of 32-row blocks; fp32 over the 16 rows a lane holds of one row block, float64 from there on, one shuffle
-// joins the lane halves.  The chunk's sums go to its own slab row, P[chunk][ldc] with ldc = ncolblk * 128 (every store is inside the
-// slab); is_coldiv_reduce_kernel adds the rows in chunk order and STORES div[c]: no atomics, nothing accumulated into the output.
-// Outside the block the term is SELECTED away (q = 0, log q = -inf there), never multiplied.
-template <int KT, bool FAST>
-__global__ __launch_bounds__(256) void is_coldiv_kernel(NnArgs p, double* __restrict__ P, long ldc, long rowblks_per_chunk) {
-    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
-    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long gw = (long)blockIdx.x * 4 + wid;
-    const long nchunks = cdiv(p.nrowblk, rowblks_per_chunk);
-    if (gw >= nchunks * p.ncolblk) return;
-    const long chunk = gw / p.ncolblk, colblk = gw % p.ncolblk;
-    const long col0 = colblk * 128;
-    double dv[4] = {0.0, 0.0, 0.0, 0.0};
-    long rb1 = (chunk + 1) * rowblks_per_chunk;
-    if (rb1 > p.nrowblk) rb1 = p.nrowblk;
-    for (long rb = chunk * rowblks_per_chunk; rb < rb1; ++rb) {
-        const long row0 = rb * 32;
-        f32x16 acc[4];
-        nn_tile<KT, 4, FAST, false>(acc, p.W, p.ldw, p.m, p.k, p.H, p.ldh, p.n, row0, col0, li, h);
-        float pv[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const long row = row0 + crow(r, h);
-            float a[4];
-            load_vec<4, FAST>(a, p.A + row * p.lda, col0 + 4 * li, p.n, row < p.m);
-#pragma unroll
-            for (int ne = 0; ne < 4; ++ne) {
-                const float q = kl_quot(a[ne], acc[ne][r] + p.eps);
-                const float t = (q - 1.f) - logf(q);
-                pv[ne] += (row < p.m && col0 + 4 * li + ne < p.n) ? t : 0.f;
-            }
-        }
-#pragma unroll
-        for (int ne = 0; ne < 4; ++ne) dv[ne] += (double)pv[ne];
-    }
-    double* Pc = P + chunk * ldc + col0 + 4 * li;
-#pragma unroll
-    for (int ne = 0; ne < 4; ++ne) {
-        dv[ne] += __shfl_xor(dv[ne], 32, 64);
-        if (h == 0) Pc[ne] = dv[ne];
-    }
-}
-
-__global__ __launch_bounds__(256) void is_coldiv_reduce_kernel(const double* __restrict__ P, long ldc, long nchunks, long n,
-                                                               double* __restrict__ div) {
-    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long)gridDim.x * 256) {
-        double a = P[c];
-        for (long s = 1; s < nchunks; ++s) a += P[s * ldc + c];
-        div[c] = a;
-    }
-}
+// ---- the rule on a stored pair is pair_ratio_kernel<RULE_SQRT> (csrc/dnmf_masked.h).  The divergence
+//     D_IS(A | W H + eps) = sum (q - log q - 1), q = a / (s + eps)
+// and its per-column form, div[c] = the same sum over this block's rows (PyNMF.is_column_divergence: the per-column statistic of an
+// NMFk sweep under norm='is'), are the two walks of csrc/dnmf_sums.h with the term BetaDivTerm<BETA_DIV_IS, 1>: tile_sum_kernel leaves
+// one double per 32 x 128 tile, col_sums_kernel one double per column and chunk of row blocks.
+using IsDivTerm = BetaDivTerm<BETA_DIV_IS, 1>;
 
 }  // namespace

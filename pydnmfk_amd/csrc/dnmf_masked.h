@@ -28,6 +28,7 @@
 #include "dnmf_nt.h"
 #include "dnmf_stream.h"
 #include "dnmf_nn.h"
+#include "dnmf_sums.h"
 
 namespace {
 
@@ -288,6 +289,17 @@ __global__ __launch_bounds__(256) void masked_reduce_kernel(const float* __restr
     }
 }
 
+// ---- the rule on a stored pair (after its allreduce on a 1D grid): pair_rule as in the ending above
+template <int RULE>
+__global__ __launch_bounds__(256) void pair_ratio_kernel(float* __restrict__ X, long rows, long cols, long ldx, const float* __restrict__ num,
+                                                         const float* __restrict__ den, long ldo, float eps, int clamp, float gamma) {
+    const long total = rows * cols;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long r = idx / cols, c = idx % cols;
+        X[r * ldx + c] = pair_rule<RULE>(X[r * ldx + c], num[r * ldo + c], den[r * ldo + c], eps, clamp, gamma);
+    }
+}
+
 // ---- sum over Omega of (a - d)^2 (pyDNMF.py:205-218 over the observed positions): resid_kernel's tiles with the select; fp32 per tile
 // and lane (64 terms), float64 from there on, ending the way the dense residual does
 template <int KT, bool FAST>
@@ -319,66 +331,8 @@ __global__ __launch_bounds__(256) void masked_resid_kernel(NnArgs p) {
 }
 
 // ---- per-column error over Omega (PyNMF.column_err, pyDNMF.py:221-239 with both sums over the observed positions): colerr_kernel of
-// csrc/dnmf_nn.h with the select above.  A wave owns a 128-column block and a chunk of 32-row blocks; fp32 per 16-row tile, float64 from
-// there on.  The chunk's pair goes to its own slab row, P[chunk][half][ldc] with ldc = ncolblk * 128 (every store is inside the slab);
-// masked_colerr_reduce_kernel adds the rows in chunk order and STORES num[c], den[c]: no atomics, nothing accumulated into the outputs.
-template <int KT, bool FAST>
-__global__ __launch_bounds__(256) void masked_colerr_kernel(NnArgs p, double* __restrict__ P, long ldc, long rowblks_per_chunk) {
-    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
-    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long gw = (long)blockIdx.x * 4 + wid;
-    const long nchunks = cdiv(p.nrowblk, rowblks_per_chunk);
-    if (gw >= nchunks * p.ncolblk) return;
-    const long chunk = gw / p.ncolblk, colblk = gw % p.ncolblk;
-    const long col0 = colblk * 128;
-    double dn[4] = {0.0, 0.0, 0.0, 0.0}, dd[4] = {0.0, 0.0, 0.0, 0.0};
-    long rb1 = (chunk + 1) * rowblks_per_chunk;
-    if (rb1 > p.nrowblk) rb1 = p.nrowblk;
-    for (long rb = chunk * rowblks_per_chunk; rb < rb1; ++rb) {
-        const long row0 = rb * 32;
-        f32x16 acc[4];
-        nn_tile<KT, 4, FAST, false>(acc, p.W, p.ldw, p.m, p.k, p.H, p.ldh, p.n, row0, col0, li, h);
-        float pn[4] = {0.f, 0.f, 0.f, 0.f}, pd[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const long row = row0 + crow(r, h);
-            float a[4];
-            load_vec<4, FAST>(a, p.A + row * p.lda, col0 + 4 * li, p.n, row < p.m);
-#pragma unroll
-            for (int ne = 0; ne < 4; ++ne) {
-                // outside the block a = 0 and acc = 0 (zero-filled operands): an observed zero that is reproduced exactly
-                const bool obs = a[ne] == a[ne];
-                const float d = obs ? a[ne] - acc[ne][r] : 0.f;
-                const float ao = obs ? a[ne] : 0.f;
-                pn[ne] = fmaf(d, d, pn[ne]);
-                pd[ne] = fmaf(ao, ao, pd[ne]);
-            }
-        }
-#pragma unroll
-        for (int ne = 0; ne < 4; ++ne) { dn[ne] += (double)pn[ne]; dd[ne] += (double)pd[ne]; }
-    }
-    double* Pn = P + chunk * 2 * ldc + col0 + 4 * li;
-    double* Pd = Pn + ldc;
-#pragma unroll
-    for (int ne = 0; ne < 4; ++ne) {
-        dn[ne] += __shfl_xor(dn[ne], 32, 64);
-        dd[ne] += __shfl_xor(dd[ne], 32, 64);
-        if (h == 0) { Pn[ne] = dn[ne]; Pd[ne] = dd[ne]; }
-    }
-}
-
-__global__ __launch_bounds__(256) void masked_colerr_reduce_kernel(const double* __restrict__ P, long ldc, long nchunks, long n,
-                                                                   double* __restrict__ num, double* __restrict__ den) {
-    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long)gridDim.x * 256) {
-        double a = P[c], b = P[ldc + c];
-        for (long s = 1; s < nchunks; ++s) {
-            a += P[s * 2 * ldc + c];
-            b += P[s * 2 * ldc + ldc + c];
-        }
-        num[c] = a;
-        den[c] = b;
-    }
-}
+// csrc/dnmf_nn.h with the select above and without atomics -- col_sums_kernel<KT, FAST, MaskedErrTerm> of csrc/dnmf_sums.h, launched by
+// col_sums below.
 
 // out[0] = sum over Omega of a^2, out[1] = |Omega| (both float64; the count is exact below 2^53)
 __global__ __launch_bounds__(256) void masked_sqnorm_kernel(const float* __restrict__ A, long m, long n, long lda, double* __restrict__ out) {
@@ -492,6 +446,92 @@ int pair_reduce(const float* P, long part_stride, long half_stride, long ldp, in
     return check_launch(who);
 }
 
+// the rule of MODE on a stored pair
+template <int MODE>
+int pair_ratio_update(const char* who, float* X, long rows, long cols, long ldx, const float* num, const float* den, long ldo, float eps,
+                      int clamp, void* stream, float gamma = 1.f) {
+    REQUIRE(X && num && den && rows >= 1 && cols >= 1 && ldx >= cols && ldo >= cols, "%s: null pointer or bad shape", who);
+    const unsigned grid = (unsigned)masked_reduce_grid(rows, cols);
+    hipLaunchKernelGGL(pair_ratio_kernel<PairMode<MODE>::rule>, dim3(grid), dim3(256), 0, S(stream), X, rows, cols, ldx, num, den, ldo, eps,
+                       clamp != 0, gamma);
+    return check_launch(who);
+}
+
+// ---- the sums of csrc/dnmf_sums.h.  `serves` names the kernels in the rank message, as PairMode<MODE>::serves does for the pairs.
+#define SUMS_CHECKS(who, serves, outs_ok)                                                                                  \
+    const int kt = kt_of(k);                                                                                               \
+    REQUIRE(kt > 0, "%s: rank k=%d unsupported (1 <= k <= %d for %s)", who, k, DNMF_TUNED_MAX_K, serves);                  \
+    REQUIRE(A && W && H && (outs_ok) && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n, "%s: null pointer or bad shape", who)
+// f(KtFast<KT, FAST>{}) for the rank's KT and the operands' alignment
+template <int KT_, bool FAST_> struct KtFast { static constexpr int KT = KT_; static constexpr bool FAST = FAST_; };
+template <class F>
+void with_kt_fast(int kt, bool fast, F f) {
+    if (kt == 1) { if (fast) f(KtFast<1, true>{}); else f(KtFast<1, false>{}); }
+    else if (kt == 2) { if (fast) f(KtFast<2, true>{}); else f(KtFast<2, false>{}); }
+    else { if (fast) f(KtFast<4, true>{}); else f(KtFast<4, false>{}); }
+}
+
+// per column: out0[c] (and out1[c] where the Term has two sums) over the block's rows
+template <class Term>
+int col_sums(const char* who, const char* serves, const float* A, long m, long n, long lda, const float* W, long ldw, const float* H,
+             long ldh, int k, float eps, Term term, double* out0, double* out1, void* ws, size_t ws_bytes, void* stream) {
+    SUMS_CHECKS(who, serves, out0 && (Term::NSUM == 1 || out1));
+    const MaskedColerrPlan c = plan_masked_colerr(m, n, Term::NSUM);
+    if (!ws || ws_bytes < c.bytes || !aligned16(ws)) return fail(DNMF_EWS, "%s: workspace %zu < %zu bytes", who, ws_bytes, c.bytes);
+    hipStream_t st = S(stream);
+    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
+    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
+    double* P = (double*)ws;
+    const dim3 grid((unsigned)cdiv(c.nchunks * c.ncolblk, 4)), block(256);
+    with_kt_fast(kt, fast, [&](auto v) { col_sums_launch<v.KT, v.FAST>(grid, block, st, a, P, c.ldc, c.rowblks_per_chunk, term); });
+    if (int rc = check_launch(who)) return rc;
+    hipLaunchKernelGGL(col_sums_reduce_kernel<Term::NSUM>, dim3((unsigned)std::min<long>(cdiv(n, 256), 4096)), dim3(256), 0, st,
+                       (const double*)P, c.ldc, c.nchunks, n, out0, out1);
+    return check_launch(who);
+}
+
+size_t col_sums_ws_bytes(long m, long n, int k, int per_col) {
+    if (kt_of(k) < 0 || m < 1 || n < 1) return 0;
+    return align256(plan_masked_colerr(m, n, per_col).bytes);
+}
+
+// the launch plan of col_sums as numbers (host arithmetic, no GPU)
+int col_sums_plan_report(const char* who, const char* serves, long m, long n, int k, int per_col, long* out) {
+    REQUIRE(kt_of(k) > 0, "%s: rank k=%d unsupported (1 <= k <= %d for %s)", who, k, DNMF_TUNED_MAX_K, serves);
+    REQUIRE(out && m >= 1 && n >= 1, "%s: null pointer or bad shape", who);
+    const MaskedColerrPlan c = plan_masked_colerr(m, n, per_col);
+    out[0] = c.rowblks_per_chunk;       // 32-row blocks a wave walks (the last chunk may hold fewer)
+    out[1] = c.nchunks;
+    out[2] = c.ncolblk;                 // 128-column blocks (the last may be ragged)
+    return DNMF_OK;
+}
+
+// one scalar: the divergence leaves one double per 32 x 128 tile
+size_t div_bytes(long m, long n) { return (size_t)cdiv(m, 32) * cdiv(n, 128) * sizeof(double); }
+
+template <class Term>
+int tile_sum(const char* who, const char* serves, const float* A, long m, long n, long lda, const float* W, long ldw, const float* H,
+             long ldh, int k, float eps, Term term, double* out, void* ws, size_t ws_bytes, void* stream) {
+    SUMS_CHECKS(who, serves, out);
+    const size_t need = div_bytes(m, n);
+    if (!ws || ws_bytes < need || !aligned16(ws)) return fail(DNMF_EWS, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    hipStream_t st = S(stream);
+    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
+    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
+    const long tiles = a.nrowblk * a.ncolblk;
+    double* P = (double*)ws;
+    const dim3 grid((unsigned)cdiv(tiles, 4)), block(256);
+    with_kt_fast(kt, fast, [&](auto v) { hipLaunchKernelGGL((tile_sum_kernel<v.KT, v.FAST, Term>), grid, block, 0, st, a, P, term); });
+    if (int rc = check_launch(who)) return rc;
+    hipLaunchKernelGGL(slot_sum_kernel, dim3(1), dim3(256), 0, st, (const double*)P, tiles, out);
+    return check_launch(who);
+}
+#undef SUMS_CHECKS
+
+// ---- what the modes with a divergence (PAIR_IS, PAIR_BETA) share beyond the pairs: one workspace serves a step and the divergence
+template <int MODE>
+size_t div_step_bytes(long m, long n, int kt) { return align256(std::max(pair_step_bytes<MODE>(m, n, kt), div_bytes(m, n))); }
+
 // the W side into partial slabs, then the ending: (num, den) stored, or X = W updated in place
 template <int MODE>
 int pair_w_side(const char* who, const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k,
@@ -584,6 +624,24 @@ PairFitWs pair_fit_layout(size_t step, int k) {
     f.sq_off = f.cs_off + align256(kp * sizeof(float));
     f.total = f.sq_off + 256;
     return f;
+}
+
+// workspace of a step, or of a whole fit, of a mode with a divergence; 0 for a rank or a shape its kernels do not serve
+template <int MODE>
+size_t div_ws_bytes(long m, long n, int k, bool fit) {
+    const int kt = kt_of(k);
+    if (kt < 0 || m < 1 || n < 1) return 0;
+    const size_t step = div_step_bytes<MODE>(m, n, kt);
+    return fit ? pair_fit_layout(step, k).total : step;
+}
+
+// the launch plans of both sides and of their endings as numbers (host arithmetic, no GPU)
+template <int MODE>
+int div_plan_report(const char* who, long m, long n, int k, long* out) {
+    if (int rc = pair_plan_report<MODE>(who, m, n, k, out)) return rc;
+    out[6] = masked_reduce_grid(m, k);  // workgroups (256 outputs each per grid-stride trip) of the W side's ending
+    out[7] = masked_reduce_grid(k, n);  // and of the H side's
+    return DNMF_OK;
 }
 
 // pyDNMF.py:138-182 under a pair rule on one rank: the launches the step loop makes, in its order, with nothing in between.  The rule

@@ -91,45 +91,16 @@ int dnmf_masked_sqnorm(const float* A, long m, long n, long lda, double* out, vo
     return check_launch("masked_sqnorm");
 }
 
-size_t dnmf_masked_column_err_ws_bytes(long m, long n, int k) {
-    if (kt_of(k) < 0 || m < 1 || n < 1) return 0;
-    return align256(plan_masked_colerr(m, n).bytes);
-}
+size_t dnmf_masked_column_err_ws_bytes(long m, long n, int k) { return col_sums_ws_bytes(m, n, k, MaskedErrTerm::NSUM); }
 
-// the launch plan of dnmf_masked_column_err as numbers (host arithmetic, no GPU)
 int dnmf_masked_column_err_plan(long m, long n, int k, long out[3]) {
-    REQUIRE(kt_of(k) > 0, "masked_column_err_plan: rank k=%d unsupported (1 <= k <= %d for masked dense data)", k, DNMF_TUNED_MAX_K);
-    REQUIRE(out && m >= 1 && n >= 1, "masked_column_err_plan: null pointer or bad shape");
-    const MaskedColerrPlan c = plan_masked_colerr(m, n);
-    out[0] = c.rowblks_per_chunk;       // 32-row blocks a wave walks (the last chunk may hold fewer)
-    out[1] = c.nchunks;
-    out[2] = c.ncolblk;                 // 128-column blocks (the last may be ragged)
-    return DNMF_OK;
+    return col_sums_plan_report("masked_column_err_plan", PairMode<PAIR_FRO>::serves, m, n, k, MaskedErrTerm::NSUM, out);
 }
 
 int dnmf_masked_column_err(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, double* num,
                            double* den, void* ws, size_t ws_bytes, void* stream) {
-    const int kt = kt_of(k);
-    REQUIRE(kt > 0, "masked_column_err: rank k=%d unsupported (1 <= k <= %d for masked dense data)", k, DNMF_TUNED_MAX_K);
-    REQUIRE(A && W && H && num && den && m >= 1 && n >= 1 && lda >= n && ldw >= k && ldh >= n, "masked_column_err: null pointer or bad shape");
-    const MaskedColerrPlan c = plan_masked_colerr(m, n);
-    if (!ws || ws_bytes < c.bytes || !aligned16(ws)) return fail(DNMF_EWS, "masked_column_err: workspace %zu < %zu bytes", ws_bytes, c.bytes);
-    hipStream_t st = S(stream);
-    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, 0.f);
-    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k);
-    double* P = (double*)ws;
-    const dim3 grid((unsigned)cdiv(c.nchunks * c.ncolblk, 4)), block(256);
-#define MC_CASE(KT_)                                                                                                            \
-    if (kt == KT_) {                                                                                                            \
-        if (fast) hipLaunchKernelGGL((masked_colerr_kernel<KT_, true>), grid, block, 0, st, a, P, c.ldc, c.rowblks_per_chunk);  \
-        else hipLaunchKernelGGL((masked_colerr_kernel<KT_, false>), grid, block, 0, st, a, P, c.ldc, c.rowblks_per_chunk);      \
-    }
-    MC_CASE(1) MC_CASE(2) MC_CASE(4)
-#undef MC_CASE
-    if (int rc = check_launch("masked_column_err")) return rc;
-    hipLaunchKernelGGL(masked_colerr_reduce_kernel, dim3((unsigned)std::min<long>(cdiv(n, 256), 4096)), dim3(256), 0, st, (const double*)P, c.ldc,
-                       c.nchunks, n, num, den);
-    return check_launch("masked_column_err");
+    return col_sums("masked_column_err", PairMode<PAIR_FRO>::serves, A, m, n, lda, W, ldw, H, ldh, k, 0.f, MaskedErrTerm{}, num, den, ws,
+                    ws_bytes, stream);
 }
 
 size_t dnmf_masked_ws_bytes_fit(long m, long n, int k) {

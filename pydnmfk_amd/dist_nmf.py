@@ -135,42 +135,36 @@ class _Base:
         if clamp:
             ops.clamp_min(W, eps)
 
-    # ---- Itakura-Saito, MU in its majorisation-minimisation form (1D grids).  With S = W H, R = 1 / (S + eps) and F = H^T / W:
-    #     num = (A . R . R) F,  den = R F,  X <- X * sqrt(num / (den + eps))
-    def IS_MU_update(self, W_update=True, clamp=False):
+    # ---- Itakura-Saito and the beta-divergence, -2 <= beta <= 4, MU in its majorisation-minimisation form (1D grids).  F = H^T / W:
+    #   'is':    S = W H, R = 1 / (S + eps):             num = (A . R . R) F,  den = R F,         X <- X * sqrt(num / (den + eps))
+    #   'beta':  S' = W H + eps, P = S'^(beta - 2):      num = (A . P) F,      den = (S' . P) F,  X <- X * (num / (den + eps))^gamma(beta)
+    # (csrc/dnmf_is.h, csrc/dnmf_beta.h).  One body: the operations ops.<norm>_*, which under 'beta' take params.beta after eps
+    def _div_MU_update(self, norm, W_update, clamp):
         ops, A = self.ops, self.A_ij
         if self.p_r != 1 and self.p_c != 1:
-            raise NotImplementedError("norm='is' on a 2D grid (p_r = %d, p_c = %d) is not provided: use a 1D grid" % (self.p_r, self.p_c))
+            raise NotImplementedError("norm='%s' on a 2D grid (p_r = %d, p_c = %d) is not provided: use a 1D grid" % (norm, self.p_r, self.p_c))
         if _is_sparse(A) or _is_masked(A):
-            raise NotImplementedError("norm='is' is provided for dense data without missing entries, not for %s"
-                                      % ("sparse data" if _is_sparse(A) else "missing='%s'" % A.missing))
-        if not hasattr(ops, "is_update_w") or A.dtype not in getattr(ops, "is_dtypes", ()):
-            raise NotImplementedError("norm='is' runs on float32 data with the product's fp32 operator set; not provided for %s data with "
-                                      "the '%s' operator set" % (str(A.dtype).replace("torch.", ""), getattr(ops, "name", "?")))
-        self._pair_MU_update("isnd", ops.is_update_w, ops.is_update_h, ops.is_aht_pair, ops.is_wta_pair, ops.is_ratio_update, W_update, clamp)
+            raise NotImplementedError("norm='%s' is provided for dense data without missing entries, not for %s"
+                                      % (norm, "sparse data" if _is_sparse(A) else "missing='%s'" % A.missing))
+        if not hasattr(ops, norm + "_update_w") or A.dtype not in getattr(ops, norm + "_dtypes", ()):
+            raise NotImplementedError("norm='%s' runs on float32 data with the product's fp32 operator set; not provided for %s data with "
+                                      "the '%s' operator set" % (norm, str(A.dtype).replace("torch.", ""), getattr(ops, "name", "?")))
+        mode = ()
+        if norm == "beta":
+            if getattr(self.params, "beta", None) is None:
+                raise ValueError("norm='beta' needs params.beta (a float in -2 <= beta <= 4)")
+            mode = (float(self.params.beta),)
 
-    # ---- the beta-divergence, -2 <= beta <= 4, MU in its majorisation-minimisation form (1D grids).  With S' = W H + eps, P = S'^(beta - 2)
-    # and F = H^T / W:  num = (A . P) F,  den = (S' . P) F,  X <- X * (num / (den + eps))^gamma(beta)   (params.beta; csrc/dnmf_beta.h)
+        def op(name):      # ops.<norm>_<name>(..., eps, [beta,] ...): eps is the fourth argument of every one
+            fn = getattr(ops, "%s_%s" % (norm, name))
+            return lambda *a: fn(*a[:4], *mode, *a[4:])
+        self._pair_MU_update(norm + "nd", op("update_w"), op("update_h"), op("aht_pair"), op("wta_pair"), op("ratio_update"), W_update, clamp)
+
+    def IS_MU_update(self, W_update=True, clamp=False):
+        self._div_MU_update("is", W_update, clamp)
+
     def BETA_MU_update(self, W_update=True, clamp=False):
-        ops, A = self.ops, self.A_ij
-        if self.p_r != 1 and self.p_c != 1:
-            raise NotImplementedError("norm='beta' on a 2D grid (p_r = %d, p_c = %d) is not provided: use a 1D grid" % (self.p_r, self.p_c))
-        if _is_sparse(A) or _is_masked(A):
-            raise NotImplementedError("norm='beta' is provided for dense data without missing entries, not for %s"
-                                      % ("sparse data" if _is_sparse(A) else "missing='%s'" % A.missing))
-        if not hasattr(ops, "beta_update_w") or A.dtype not in getattr(ops, "beta_dtypes", ()):
-            raise NotImplementedError("norm='beta' runs on float32 data with the product's fp32 operator set; not provided for %s data with "
-                                      "the '%s' operator set" % (str(A.dtype).replace("torch.", ""), getattr(ops, "name", "?")))
-        beta = getattr(self.params, "beta", None)
-        if beta is None:
-            raise ValueError("norm='beta' needs params.beta (a float in -2 <= beta <= 4)")
-        beta = float(beta)
-        self._pair_MU_update("betand",
-                             lambda A, W, H, eps: ops.beta_update_w(A, W, H, eps, beta),
-                             lambda A, W, H, eps, clamp: ops.beta_update_h(A, W, H, eps, beta, clamp),
-                             lambda A, W, H, eps, buf: ops.beta_aht_pair(A, W, H, eps, beta, buf),
-                             lambda A, W, H, eps, buf: ops.beta_wta_pair(A, W, H, eps, beta, buf),
-                             lambda X, num, den, eps, clamp=False: ops.beta_ratio_update(X, num, den, eps, beta, clamp), W_update, clamp)
+        self._div_MU_update("beta", W_update, clamp)
 
     # ---- BCD / Frobenius (dist_nmf.py:940-1047 in 1D, :474-579 in 2D).  The grid-specific pieces are the `_bcd_*` hooks of each
     # class: the exchanges sit exactly where the reference allreduces / gathers.  Every scalar of the method stays in the device state

@@ -740,66 +740,84 @@ class HipOps:
         r, c = X.shape
         return X.data_ptr(), r, c, _ld(X), num.data_ptr(), den.data_ptr(), _ld(num), float(eps), int(bool(clamp)), _stream()
 
-    def _is(self, what, A, W, H, eps, pair=None):
-        return self._pair_args(what, A, W, H, eps, lib.dnmf_is_ws_bytes, self._is_ranks, pair=pair)
+    # ---- ONE implementation of both families.  `p` is the library prefix ('is' or 'beta'), `mode` what follows `eps` in every call
+    # (() or (beta,)); the rank message is _is_ranks / _beta_ranks.  The public is_* and beta_* methods below are its callers.
+    def _fam(self, p, what, A, W, H, eps, mode, pair=None, ws="ws_bytes"):
+        return self._pair_args(what, A, W, H, eps, _fn(p + "_" + ws, ""), getattr(self, "_%s_ranks" % p), mode=mode, pair=pair)
 
-    def _is_pair(self, side, A, W, H, eps, num, den):
-        head, tail = self._is("is pair", A, W, H, eps, pair=(side, num, den))
-        check((lib.dnmf_is_aht_pair if side == "w" else lib.dnmf_is_wta_pair)(*head, *tail))
+    def _fam_pair(self, p, mode, side, A, W, H, eps, num, den):
+        head, tail = self._fam(p, p + " pair", A, W, H, eps, mode, pair=(side, num, den))
+        check(_fn(p + ("_aht_pair" if side == "w" else "_wta_pair"), "")(*head, *tail))
         return num, den
+
+    def _fam_update(self, p, mode, side, A, W, H, eps, *clamp):
+        what = "%s_update_%s" % (p, side)
+        head, tail = self._fam(p, what, A, W, H, eps, mode)
+        check(_fn(what, "")(*head, *clamp, *tail))
+        return W if side == "w" else H
+
+    def _fam_ratio_update(self, p, mode_of, X, num, den, eps, clamp):
+        a = self._ratio_args(p + "_ratio_update", X, num, den, eps, clamp)
+        check(_fn(p + "_ratio_update", "")(*a[:8], *mode_of(), *a[8:]))
+        return X
+
+    def _fam_divergence(self, p, mode, A, W, H, eps):
+        head, tail = self._fam(p, p + "_divergence", A, W, H, eps, mode)
+        out = torch.empty(1, dtype=torch.float64, device=A.device)
+        check(_fn(p + "_divergence", "")(*head, out.data_ptr(), *tail))
+        return out
+
+    def _fam_column_div(self, p, mode, nout, A, W, H, eps):
+        head, tail = self._fam(p, p + "_column_div", A, W, H, eps, mode, ws="column_div_ws_bytes")
+        out = torch.empty(nout, A.shape[1], dtype=torch.float64, device=A.device)
+        check(_fn(p + "_column_div", "")(*head, *(o.data_ptr() for o in out), *tail))
+        return out
+
+    def _fam_fit(self, p, mode, A, W, H, eps, w_update, itr):
+        return self._pair_fit(p + "_fit", _fn(p + "_mu_fit", ""), A, W, H, eps, _fn(p + "_ws_bytes_fit", ""),
+                              getattr(self, "_%s_ranks" % p), mode, w_update, itr)
 
     def is_aht_pair(self, A, W, H, eps, buf):
         """buf = [num | den], each m x k: (A . R . R) H^T and R H^T"""
-        return self._is_pair("w", A, W, H, eps, *self._halves(buf, tuple(W.shape)))
+        return self._fam_pair("is", (), "w", A, W, H, eps, *self._halves(buf, tuple(W.shape)))
 
     def is_wta_pair(self, A, W, H, eps, buf):
         """buf = [num | den], each k x n: W^T (A . R . R) and W^T R"""
-        return self._is_pair("h", A, W, H, eps, *self._halves(buf, tuple(H.shape)))
+        return self._fam_pair("is", (), "h", A, W, H, eps, *self._halves(buf, tuple(H.shape)))
 
     def is_pair_into(self, side, A, W, H, eps, num, den):
         """the same pair into two views of the caller's (one leading dimension, any pitch): side 'w' (m x k) or 'h' (k x n)"""
-        return self._is_pair(side, A, W, H, eps, num, den)
+        return self._fam_pair("is", (), side, A, W, H, eps, num, den)
 
     def is_update_w(self, A, W, H, eps):
         """W <- W * sqrt(num / (den + eps)): the pass, then the rule on its partial sums (this rank's W rows see all their columns)"""
-        head, tail = self._is("is_update_w", A, W, H, eps)
-        check(lib.dnmf_is_update_w(*head, *tail))
-        return W
+        return self._fam_update("is", (), "w", A, W, H, eps)
 
     def is_update_h(self, A, W, H, eps, clamp=False):
         """H <- H * sqrt(num / (den + eps)), max(., eps) with `clamp` (this rank's H columns see all their rows)"""
-        head, tail = self._is("is_update_h", A, W, H, eps)
-        check(lib.dnmf_is_update_h(*head, int(bool(clamp)), *tail))
-        return H
+        return self._fam_update("is", (), "h", A, W, H, eps, int(bool(clamp)))
 
     def is_ratio_update(self, X, num, den, eps, clamp=False):
         """X <- X * sqrt(num / (den + eps)), max(., eps) with `clamp`: the rule on a pair that was summed over the ranks"""
-        check(lib.dnmf_is_ratio_update(*self._ratio_args("is_ratio_update", X, num, den, eps, clamp)))
-        return X
+        return self._fam_ratio_update("is", tuple, X, num, den, eps, clamp)
 
     def is_divergence(self, A, W, H, eps):
         """D_IS(A | W H + eps) = sum (q - log q - 1), q = A / (W H + eps), over this block: one device double (stored, not
         accumulated: two calls are bit-identical)"""
-        head, tail = self._is("is_divergence", A, W, H, eps)
-        out = torch.empty(1, dtype=torch.float64, device=A.device)
-        check(lib.dnmf_is_divergence(*head, out.data_ptr(), *tail))
-        return out
+        return self._fam_divergence("is", (), A, W, H, eps)
 
     is_nmfk = True                     # PyNMFk looks for this and `is_column_div`: the per-column statistic of a sweep under norm='is'
 
     def is_column_div(self, A, W, H, eps):
         """div[c] = sum_i (q - log q - 1), q = A / (W H + eps), over this block's rows: n device doubles, column SUMS (dnmf_is_column_div:
         stored, not accumulated -- two calls are bit-identical)"""
-        head, tail = self._pair_args("is_column_div", A, W, H, eps, lib.dnmf_is_column_div_ws_bytes, self._is_ranks)
-        out = torch.empty(A.shape[1], dtype=torch.float64, device=A.device)
-        check(lib.dnmf_is_column_div(*head, out.data_ptr(), *tail))
-        return out
+        return self._fam_column_div("is", (), 1, A, W, H, eps)[0]
 
     def is_fit(self, A, W, H, eps, w_update, itr):
         """`itr` Itakura-Saito MU steps (clamps after the steps i % 10 == 0), normalize_features and the squared norms of relative_err in
         ONE library call (dnmf_is_mu_fit: the launches of the step loop in its order).  One problem; W, H are updated in place; returns
         the device tensor [1][2] of {sum (A - W H)^2, sum A^2}."""
-        return self._pair_fit("is_fit", lib.dnmf_is_mu_fit, A, W, H, eps, lib.dnmf_is_ws_bytes_fit, self._is_ranks, (), w_update, itr)
+        return self._fam_fit("is", (), A, W, H, eps, w_update, itr)
 
     # ---- the beta-divergence, -2 <= beta <= 4 (csrc/dnmf_beta.h, dnmf_beta_*): dense float32 data, 1 <= k <= 128.  With S' = W H + eps and
     # P = S'^(beta - 2): num = (A . P) F, den = (S' . P) F (F = H^T / W), X <- X * (num / (den + eps))^gamma(beta).  `beta` follows `eps`
@@ -815,50 +833,33 @@ class HipOps:
             raise ValueError("beta = %r is outside the accepted range %g <= beta <= %g" % ((beta,) + cls.BETA_RANGE))
         return (beta,)
 
-    def _beta(self, what, A, W, H, eps, beta, pair=None):
-        return self._pair_args(what, A, W, H, eps, lib.dnmf_beta_ws_bytes, self._beta_ranks, mode=self._beta_mode(beta), pair=pair)
-
-    def _beta_pair(self, side, A, W, H, eps, beta, num, den):
-        head, tail = self._beta("beta pair", A, W, H, eps, beta, pair=(side, num, den))
-        check((lib.dnmf_beta_aht_pair if side == "w" else lib.dnmf_beta_wta_pair)(*head, *tail))
-        return num, den
-
     def beta_aht_pair(self, A, W, H, eps, beta, buf):
         """buf = [num | den], each m x k: (A . P) H^T and (S' . P) H^T"""
-        return self._beta_pair("w", A, W, H, eps, beta, *self._halves(buf, tuple(W.shape)))
+        return self._fam_pair("beta", self._beta_mode(beta), "w", A, W, H, eps, *self._halves(buf, tuple(W.shape)))
 
     def beta_wta_pair(self, A, W, H, eps, beta, buf):
         """buf = [num | den], each k x n: W^T (A . P) and W^T (S' . P)"""
-        return self._beta_pair("h", A, W, H, eps, beta, *self._halves(buf, tuple(H.shape)))
+        return self._fam_pair("beta", self._beta_mode(beta), "h", A, W, H, eps, *self._halves(buf, tuple(H.shape)))
 
     def beta_pair_into(self, side, A, W, H, eps, beta, num, den):
         """the same pair into two views of the caller's (one leading dimension, any pitch): side 'w' (m x k) or 'h' (k x n)"""
-        return self._beta_pair(side, A, W, H, eps, beta, num, den)
+        return self._fam_pair("beta", self._beta_mode(beta), side, A, W, H, eps, num, den)
 
     def beta_update_w(self, A, W, H, eps, beta):
         """W <- W * (num / (den + eps))^gamma: the pass, then the rule on its partial sums (this rank's W rows see all their columns)"""
-        head, tail = self._beta("beta_update_w", A, W, H, eps, beta)
-        check(lib.dnmf_beta_update_w(*head, *tail))
-        return W
+        return self._fam_update("beta", self._beta_mode(beta), "w", A, W, H, eps)
 
     def beta_update_h(self, A, W, H, eps, beta, clamp=False):
         """H <- H * (num / (den + eps))^gamma, max(., eps) with `clamp` (this rank's H columns see all their rows)"""
-        head, tail = self._beta("beta_update_h", A, W, H, eps, beta)
-        check(lib.dnmf_beta_update_h(*head, int(bool(clamp)), *tail))
-        return H
+        return self._fam_update("beta", self._beta_mode(beta), "h", A, W, H, eps, int(bool(clamp)))
 
     def beta_ratio_update(self, X, num, den, eps, beta, clamp=False):
         """X <- X * (num / (den + eps))^gamma, max(., eps) with `clamp`: the rule on a pair that was summed over the ranks"""
-        a = self._ratio_args("beta_ratio_update", X, num, den, eps, clamp)
-        check(lib.dnmf_beta_ratio_update(*a[:8], *self._beta_mode(beta), *a[8:]))
-        return X
+        return self._fam_ratio_update("beta", lambda: self._beta_mode(beta), X, num, den, eps, clamp)
 
     def beta_divergence(self, A, W, H, eps, beta):
         """D_beta(A | W H + eps) over this block: one device double (stored, not accumulated: two calls are bit-identical)"""
-        head, tail = self._beta("beta_divergence", A, W, H, eps, beta)
-        out = torch.empty(1, dtype=torch.float64, device=A.device)
-        check(lib.dnmf_beta_divergence(*head, out.data_ptr(), *tail))
-        return out
+        return self._fam_divergence("beta", self._beta_mode(beta), A, W, H, eps)
 
     beta_nmfk = True                   # PyNMFk looks for this and `beta_column_div`: the per-column statistic of a sweep under norm='beta'
 
@@ -866,18 +867,14 @@ class HipOps:
         """(div, pw): div[c] = sum_i d_beta(A | W H + eps) and pw[c] = sum_i A^beta over this block's rows, n device doubles each, column
         SUMS (dnmf_beta_column_div: stored, not accumulated -- two calls are bit-identical).  div / pw, after the sums have crossed the
         ranks, is the scale-invariant per-column statistic (PyNMF.beta_column_divergence)."""
-        head, tail = self._pair_args("beta_column_div", A, W, H, eps, lib.dnmf_beta_column_div_ws_bytes, self._beta_ranks,
-                                     mode=self._beta_mode(beta))
-        out = torch.empty(2, A.shape[1], dtype=torch.float64, device=A.device)
-        check(lib.dnmf_beta_column_div(*head, out[0].data_ptr(), out[1].data_ptr(), *tail))
+        out = self._fam_column_div("beta", self._beta_mode(beta), 2, A, W, H, eps)
         return out[0], out[1]
 
     def beta_fit(self, A, W, H, eps, beta, w_update, itr):
         """`itr` beta-divergence MU steps (clamps after the steps i % 10 == 0), normalize_features and the squared norms of relative_err in
         ONE library call (dnmf_beta_mu_fit: the launches of the step loop in its order).  One problem; W, H are updated in place; returns
         the device tensor [1][2] of {sum (A - W H)^2, sum A^2}."""
-        return self._pair_fit("beta_fit", lib.dnmf_beta_mu_fit, A, W, H, eps, lib.dnmf_beta_ws_bytes_fit, self._beta_ranks,
-                              self._beta_mode(beta), w_update, itr)
+        return self._fam_fit("beta", self._beta_mode(beta), A, W, H, eps, w_update, itr)
 
     def _bcd_fit(self, A3, W3, H3, eps, w_update, itr, sfx, batched):
         """method 'bcd' (dnmf_bcd_fro_fit): float32 data; a stack of B problems is ONE library call in which every launch

@@ -138,10 +138,8 @@ class PyNMF:
             self.norm = self.params.norm = 'is'
         self._is = (self.norm == 'is')
         self._beta = (self.norm == 'beta')
-        if self._is:
-            self._is_checks(A_ij, missing)
-        if self._beta:
-            self._beta_checks(missing)
+        if self._is or self._beta:
+            self._div_checks(missing)
         if self.a_dtype == torch.bfloat16 and str(self.norm).lower() == 'kl':
             raise TypeError("PyNMF: bfloat16 storage of A is provided for the Frobenius updates (mu / hals) only")
         self.prune = var_init(self.params, 'prune', default=True)
@@ -236,37 +234,44 @@ class PyNMF:
         if getattr(params, "init", None) == "nnsvd":
             raise NotImplementedError("missing='nan' with init='nnsvd' is not provided (the SVD would read the NaNs): init='rand' or factors=...")
 
-    def _is_checks(self, A_ij, missing):
-        """What is refused under norm='is', each by name (dense float32 data without missing entries, fp32 arithmetic, method 'mu', 1D
-        grids, k <= 128), and the one thing the data must be: strictly positive.  The ranks agree on that verdict through comm1 BEFORE
-        any of them raises, so none is left alone in a later collective."""
-        self._is_refusals(self.params, self._sparse, missing, self.a_dtype, self.ops, self.method, self.p_r, self.p_c, self.params.k)
-        self._is_positive(float(self.A_ij.min()) if self.A_ij.numel() else 1.0, self.comm1, self.p_r * self.p_c)
+    # the phrases in which the refusals of the two divergence norms differ: (its kernels' name, the end of the sparse refusal)
+    _DIV_WORDS = {"is": ("Itakura-Saito", ": the Itakura-Saito divergence is infinite at a zero entry (dense strictly positive float32 data only)"),
+                  "beta": ("beta-divergence", " (dense float32 data only)")}
+
+    def _div_checks(self, missing):
+        """What is refused under norm='is' and norm='beta', each by name (dense float32 data without missing entries, fp32 arithmetic,
+        method 'mu', 1D grids, k <= 128), and what the data must be: strictly positive under 'is' and for beta <= 0, non-negative for
+        beta > 0.  The ranks agree on that verdict through comm1 BEFORE any of them raises, so none is left alone in a later collective."""
+        self._div_refusals(self.norm, self.params, self._sparse, missing, self.a_dtype, self.ops, self.method, self.p_r, self.p_c, self.params.k)
+        self._sign_check(self.beta if self._beta else None, float(self.A_ij.min()) if self.A_ij.numel() else 1.0, self.comm1,
+                         self.p_r * self.p_c)
 
     @staticmethod
-    def _is_refusals(params, sparse, missing, a_dtype, ops, method, p_r, p_c, k):
-        """the refusals of norm='is' that need no look at the data (PyNMFk raises them at construction, with its largest rank as k)"""
+    def _div_refusals(norm, params, sparse, missing, a_dtype, ops, method, p_r, p_c, k):
+        """the refusals of `norm` ('is' or 'beta') that need no look at the data (PyNMFk raises them at construction, with its largest
+        rank as k)"""
+        kernels, sparse_why = PyNMF._DIV_WORDS[norm]
         if missing is not None:
-            raise NotImplementedError("norm='is' with missing='%s' is not provided (dense data without missing entries only)" % missing)
+            raise NotImplementedError("norm='%s' with missing='%s' is not provided (dense data without missing entries only)" % (norm, missing))
         if sparse:
-            raise NotImplementedError("norm='is' is not provided for sparse data: the Itakura-Saito divergence is infinite at a zero "
-                                      "entry (dense strictly positive float32 data only)")
+            raise NotImplementedError("norm='%s' is not provided for sparse data%s" % (norm, sparse_why))
         if a_dtype == torch.bfloat16:
-            raise NotImplementedError("norm='is' with bfloat16 storage of the data is not provided (float32 data only)")
+            raise NotImplementedError("norm='%s' with bfloat16 storage of the data is not provided (float32 data only)" % norm)
         if (getattr(params, "gemm", None) or "fp32") != "fp32":
-            raise NotImplementedError("norm='is' with --gemm %s is not provided (fp32 arithmetic only)" % params.gemm)
-        # (an operator set names the data types its Itakura-Saito operations take, `is_dtypes`: the HIP kernels are float32)
-        if a_dtype not in (getattr(ops, "is_dtypes", ()) if ops is not None else (torch.float32,)):
-            raise NotImplementedError("norm='is' with %s data is not provided (float32 data only); cast the block to float32"
-                                      % str(a_dtype).replace("torch.", ""))
+            raise NotImplementedError("norm='%s' with --gemm %s is not provided (fp32 arithmetic only)" % (norm, params.gemm))
+        # (an operator set names the data types its operations under the norm take, `is_dtypes` / `beta_dtypes`: the HIP kernels are float32)
+        if a_dtype not in (getattr(ops, norm + "_dtypes", ()) if ops is not None else (torch.float32,)):
+            raise NotImplementedError("norm='%s' with %s data is not provided (float32 data only); cast the block to float32"
+                                      % (norm, str(a_dtype).replace("torch.", "")))
         method = str(method).lower()
         if method != "mu":
-            raise NotImplementedError("norm='is' is provided for method 'mu' only, not for '%s': HALS and BCD are Frobenius methods" % method)
+            raise NotImplementedError("norm='%s' is provided for method 'mu' only, not for '%s': HALS and BCD are Frobenius methods"
+                                      % (norm, method))
         if p_r != 1 and p_c != 1:
-            raise NotImplementedError("norm='is' on a 2D grid (%d x %d) is not provided: use a 1D grid (p_r = 1 or p_c = 1)"
-                                      % (p_r, p_c))
+            raise NotImplementedError("norm='%s' on a 2D grid (%d x %d) is not provided: use a 1D grid (p_r = 1 or p_c = 1)"
+                                      % (norm, p_r, p_c))
         if k > 128:
-            raise NotImplementedError("norm='is' with k = %d is not provided: the Itakura-Saito kernels serve 1 <= k <= 128" % k)
+            raise NotImplementedError("norm='%s' with k = %d is not provided: the %s kernels serve 1 <= k <= 128" % (norm, k, kernels))
 
     @staticmethod
     def _beta_value(params):
@@ -279,52 +284,21 @@ class PyNMF:
             raise ValueError("norm='beta' with beta = %g is outside the accepted range %g <= beta <= %g" % ((beta,) + BETA_RANGE))
         return beta
 
-    def _beta_checks(self, missing):
-        """What is refused under norm='beta', each by name (what norm='is' refuses), and what the data must be: strictly positive for
-        beta <= 0, non-negative for beta > 0.  The ranks agree on that verdict through comm1 BEFORE any of them raises."""
-        self._beta_refusals(self.params, self._sparse, missing, self.a_dtype, self.ops, self.method, self.p_r, self.p_c, self.params.k)
-        lo = float(self.A_ij.min()) if self.A_ij.numel() else 1.0
-        bad = not (lo > 0.0 if self.beta <= 0.0 else lo >= 0.0)     # (a NaN minimum is refused as well)
-        nranks = self.p_r * self.p_c
-        nbad = int(self.comm1.allreduce(1 if bad else 0))
-        if nbad:
-            raise ValueError("norm='beta' with beta = %g needs %s data: the smallest entry of this rank's block is %g (%d of %d ranks hold "
-                             "an entry %s 0)%s" % (self.beta, "strictly positive" if self.beta <= 0.0 else "non-negative", lo, nbad, nranks,
-                                                   "<=" if self.beta <= 0.0 else "<",
-                                                   "; the divergence is infinite at a zero for beta <= 0" if self.beta <= 0.0 else ""))
-
     @staticmethod
-    def _beta_refusals(params, sparse, missing, a_dtype, ops, method, p_r, p_c, k):
-        """the refusals of norm='beta' that need no look at the data: those of norm='is', in this norm's words"""
-        if missing is not None:
-            raise NotImplementedError("norm='beta' with missing='%s' is not provided (dense data without missing entries only)" % missing)
-        if sparse:
-            raise NotImplementedError("norm='beta' is not provided for sparse data (dense float32 data only)")
-        if a_dtype == torch.bfloat16:
-            raise NotImplementedError("norm='beta' with bfloat16 storage of the data is not provided (float32 data only)")
-        if (getattr(params, "gemm", None) or "fp32") != "fp32":
-            raise NotImplementedError("norm='beta' with --gemm %s is not provided (fp32 arithmetic only)" % params.gemm)
-        # (an operator set names the data types its beta-divergence operations take, `beta_dtypes`: the HIP kernels are float32)
-        if a_dtype not in (getattr(ops, "beta_dtypes", ()) if ops is not None else (torch.float32,)):
-            raise NotImplementedError("norm='beta' with %s data is not provided (float32 data only); cast the block to float32"
-                                      % str(a_dtype).replace("torch.", ""))
-        method = str(method).lower()
-        if method != "mu":
-            raise NotImplementedError("norm='beta' is provided for method 'mu' only, not for '%s': HALS and BCD are Frobenius methods" % method)
-        if p_r != 1 and p_c != 1:
-            raise NotImplementedError("norm='beta' on a 2D grid (%d x %d) is not provided: use a 1D grid (p_r = 1 or p_c = 1)"
-                                      % (p_r, p_c))
-        if k > 128:
-            raise NotImplementedError("norm='beta' with k = %d is not provided: the beta-divergence kernels serve 1 <= k <= 128" % k)
-
-    @staticmethod
-    def _is_positive(lo, comm1, nranks):
-        """`lo`: the smallest entry of this rank's block; every rank raises when any rank holds an entry <= 0"""
-        bad = not lo > 0.0                                          # (a NaN minimum is refused as well)
+    def _sign_check(beta, lo, comm1, nranks):
+        """`lo`: the smallest entry of this rank's block; `beta`: None under norm='is'.  Every rank raises when any rank holds an entry
+        that the norm does not take: <= 0 under 'is' and for beta <= 0, < 0 for beta > 0"""
+        strict = beta is None or beta <= 0.0
+        bad = not (lo > 0.0 if strict else lo >= 0.0)               # (a NaN minimum is refused as well)
         nbad = int(comm1.allreduce(1 if bad else 0))
-        if nbad:
+        if nbad and beta is None:
             raise ValueError("norm='is' needs strictly positive data: the smallest entry of this rank's block is %g (%d of %d ranks hold "
                              "an entry <= 0); the Itakura-Saito divergence is infinite there" % (lo, nbad, nranks))
+        if nbad:
+            raise ValueError("norm='beta' with beta = %g needs %s data: the smallest entry of this rank's block is %g (%d of %d ranks hold "
+                             "an entry %s 0)%s" % (beta, "strictly positive" if strict else "non-negative", lo, nbad, nranks,
+                                                   "<=" if strict else "<",
+                                                   "; the divergence is infinite at a zero for beta <= 0" if strict else ""))
 
     @staticmethod
     def _sparse_checks(A_ij, params):
@@ -623,33 +597,57 @@ class PyNMF:
         self.recon_err = self.glob_norm_err / self.glob_norm_A
         return self.recon_err
 
+    def _block_factors(self):
+        """(W, H) of this rank's block as the kernels take them: where fit() has un-pruned the held factors, the rows and columns that
+        the pruned block kept"""
+        W, H = self.W_i, self.H_j
+        if W.shape[0] != self.A_ij.shape[0]:
+            W = W[self.params.row_zero_idx_x]
+        if H.shape[1] != self.A_ij.shape[1]:
+            H = H[:, self.params.col_zero_idx_x]
+        return W.contiguous(), H.contiguous()
+
+    def _global_columns(self, *sums):
+        """[len(sums)][params.n] float64 zeros with this rank's column range filled from `sums`, each one value per column of this
+        block; the sums of a pruned block go to the columns it kept (`col_zero_idx_x`), the pruned ones stay 0"""
+        from .utils import determine_block_params
+        blk = determine_block_params(self.comm1, (self.p_r, self.p_c), (self.params.m, self.params.n))
+        c0 = blk.determine_block_index_range_asymm()[0][1]
+        ncol = blk.determine_block_shape_asymm()[1]
+        col = torch.zeros(len(sums), self.params.n, dtype=torch.float64, device=sums[0].device)
+        keep = getattr(self.params, "col_zero_idx_x", None) if self.prune else None
+        for row, x in zip(col, sums):
+            if keep is not None and int(keep.numel()) == ncol and x.numel() != ncol:
+                row[c0:c0 + ncol][keep] = x
+            else:
+                row[c0:c0 + ncol] = x
+        return col
+
+    def _norm_op(self, norm, op, caller):
+        """ops.<norm>_<op>(A, W, H, eps[, beta]) on this block and its current factors, for the norm this fit runs ('is' or 'beta'); a
+        fit under another norm is refused in `caller`'s name"""
+        if not (self._is if norm == 'is' else self._beta):
+            raise ValueError("%s: this fit runs norm='%s'; the divergence is reported under norm='%s'%s"
+                             % (caller, self.norm, norm,
+                                " (beta = 0 is norm='is': %s())" % caller.replace("beta_", "is_") if norm == 'beta' and self._is else ""))
+        W, H = self._block_factors()
+        return getattr(self._ops(), "%s_%s" % (norm, op))(self.A_ij, W, H, self.eps, *((self.beta,) if norm == 'beta' else ()))
+
+    def _divergence(self, norm):
+        d = self._norm_op(norm, "divergence", norm + "_divergence")
+        self.comm1.allreduce_(d)
+        return float(d.cpu())
+
     def is_divergence(self):
         """D_IS(A | W H + eps) = sum (q - log q - 1), q = A / (W H + eps), of the CURRENT factors, summed over the grid (norm='is':
         1D grids, where every rank's block meets its own W rows and H columns).  The objective the Itakura-Saito rule does not
         increase; `fit()` keeps returning the Frobenius relative error, as it does for norm='kl'."""
-        if not self._is:
-            raise ValueError("is_divergence: this fit runs norm='%s'; the divergence is reported under norm='is'" % self.norm)
-        W, H = self.W_i, self.H_j
-        if W.shape[0] != self.A_ij.shape[0] or H.shape[1] != self.A_ij.shape[1]:   # (held factors are the pruned ones; see column_err)
-            W = W[self.params.row_zero_idx_x] if W.shape[0] != self.A_ij.shape[0] else W
-            H = H[:, self.params.col_zero_idx_x] if H.shape[1] != self.A_ij.shape[1] else H
-        d = self._ops().is_divergence(self.A_ij, W.contiguous(), H.contiguous(), self.eps)
-        self.comm1.allreduce_(d)
-        return float(d.cpu())
+        return self._divergence('is')
 
     def beta_divergence(self):
         """D_beta(A | W H + eps) of the CURRENT factors, summed over the grid (norm='beta': 1D grids, where every rank's block meets its own
         W rows and H columns).  The objective the rule does not increase; `fit()` keeps returning the Frobenius relative error."""
-        if not self._beta:
-            raise ValueError("beta_divergence: this fit runs norm='%s'; the divergence is reported under norm='beta'%s"
-                             % (self.norm, " (beta = 0 is norm='is': is_divergence())" if self._is else ""))
-        W, H = self.W_i, self.H_j
-        if W.shape[0] != self.A_ij.shape[0] or H.shape[1] != self.A_ij.shape[1]:   # (held factors are the pruned ones; see column_err)
-            W = W[self.params.row_zero_idx_x] if W.shape[0] != self.A_ij.shape[0] else W
-            H = H[:, self.params.col_zero_idx_x] if H.shape[1] != self.A_ij.shape[1] else H
-        d = self._ops().beta_divergence(self.A_ij, W.contiguous(), H.contiguous(), self.eps, self.beta)
-        self.comm1.allreduce_(d)
-        return float(d.cpu())
+        return self._divergence('beta')
 
     def is_column_divergence(self):
         """The Itakura-Saito divergence of the CURRENT factors column by column, over the GLOBAL n columns, each divided by the global row
@@ -657,23 +655,7 @@ class PyNMF:
         What an NMFk sweep under norm='is' takes where the Frobenius `column_err()` stands (which weights the columns by their scale);
         `column_err()` itself is unchanged under every norm.  Its scheme: each rank fills its own column range with its sums over its own
         rows, one float64 allreduce (row shards add partial sums, column shards fill disjoint ranges), then the division."""
-        if not self._is:
-            raise ValueError("is_column_divergence: this fit runs norm='%s'; the divergence is reported under norm='is'" % self.norm)
-        from .utils import determine_block_params
-        blk = determine_block_params(self.comm1, (self.p_r, self.p_c), (self.params.m, self.params.n))
-        c0 = blk.determine_block_index_range_asymm()[0][1]
-        ncol = blk.determine_block_shape_asymm()[1]
-        W, H = self.W_i, self.H_j
-        if W.shape[0] != self.A_ij.shape[0] or H.shape[1] != self.A_ij.shape[1]:   # factors were un-pruned by fit()
-            W = W[self.params.row_zero_idx_x] if W.shape[0] != self.A_ij.shape[0] else W
-            H = H[:, self.params.col_zero_idx_x] if H.shape[1] != self.A_ij.shape[1] else H
-        div = self._ops().is_column_div(self.A_ij, W.contiguous(), H.contiguous(), self.eps)
-        col = torch.zeros(self.params.n, dtype=torch.float64, device=div.device)
-        keep = getattr(self.params, "col_zero_idx_x", None) if self.prune else None
-        if keep is not None and int(keep.numel()) == ncol and div.numel() != ncol:
-            col[c0:c0 + ncol][keep] = div               # (strictly positive data leave nothing to prune: column_err's scheme all the same)
-        else:
-            col[c0:c0 + ncol] = div
+        col = self._global_columns(self._norm_op('is', "column_div", "is_column_divergence"))[0]
         self.comm1.allreduce_(col)
         return (col / float(self.params.m)).cpu().numpy()
 
@@ -686,26 +668,7 @@ class PyNMF:
         no scale to divide by: nan, as from `column_err()`.  The scheme of `is_column_divergence()`: each rank fills its own column
         range of both arrays with its sums over its own rows, one float64 allreduce (row shards add partial sums, column shards fill
         disjoint ranges), then the ratio."""
-        if not self._beta:
-            raise ValueError("beta_column_divergence: this fit runs norm='%s'; the divergence is reported under norm='beta'%s"
-                             % (self.norm, " (beta = 0 is norm='is': is_column_divergence())" if self._is else ""))
-        from .utils import determine_block_params
-        blk = determine_block_params(self.comm1, (self.p_r, self.p_c), (self.params.m, self.params.n))
-        c0 = blk.determine_block_index_range_asymm()[0][1]
-        ncol = blk.determine_block_shape_asymm()[1]
-        W, H = self.W_i, self.H_j
-        if W.shape[0] != self.A_ij.shape[0] or H.shape[1] != self.A_ij.shape[1]:   # factors were un-pruned by fit()
-            W = W[self.params.row_zero_idx_x] if W.shape[0] != self.A_ij.shape[0] else W
-            H = H[:, self.params.col_zero_idx_x] if H.shape[1] != self.A_ij.shape[1] else H
-        div, pw = self._ops().beta_column_div(self.A_ij, W.contiguous(), H.contiguous(), self.eps, self.beta)
-        col = torch.zeros(2, self.params.n, dtype=torch.float64, device=div.device)        # [div | pw]: ONE allreduce carries both
-        keep = getattr(self.params, "col_zero_idx_x", None) if self.prune else None
-        if keep is not None and int(keep.numel()) == ncol and div.numel() != ncol:
-            col[0, c0:c0 + ncol][keep] = div            # (a pruned all-zero column keeps 0 / 0)
-            col[1, c0:c0 + ncol][keep] = pw
-        else:
-            col[0, c0:c0 + ncol] = div
-            col[1, c0:c0 + ncol] = pw
+        col = self._global_columns(*self._norm_op('beta', "column_div", "beta_column_divergence"))   # [div | pw]: ONE allreduce carries both
         self.comm1.allreduce_(col)
         col = col.cpu().numpy()
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -715,26 +678,10 @@ class PyNMF:
         """pyDNMF.py:221-239: per-column relative error sqrt(sum_i (A - W H)^2 / sum_i A^2) over the GLOBAL n columns
         (each rank fills its own column range, float64 allreduce).  Used once per k by NMFk; the per-column sums come
         from one kernel pass over A (dnmf_column_err: the residual tile stays in accumulators)."""
-        from .utils import determine_block_params
-        blk = determine_block_params(self.comm1, (self.p_r, self.p_c), (self.params.m, self.params.n))
-        c0 = blk.determine_block_index_range_asymm()[0][1]
-        ncol = blk.determine_block_shape_asymm()[1]
         if self.topo == '2d' and not hasattr(self, "W_i"):
             self.cart_2d_collect_factors()
-        W, H = self.W_i, self.H_j
-        if W.shape[0] != self.A_ij.shape[0] or H.shape[1] != self.A_ij.shape[1]:   # factors were un-pruned by fit()
-            W = W[self.params.row_zero_idx_x] if W.shape[0] != self.A_ij.shape[0] else W
-            H = H[:, self.params.col_zero_idx_x] if H.shape[1] != self.A_ij.shape[1] else H
-        num, den = self._ops().column_err_sums(self.A_ij, W.contiguous(), H.contiguous())   # one pass over A, no temporaries
-        col_num = torch.zeros(self.params.n, dtype=torch.float64, device=num.device)
-        col_den = torch.zeros(self.params.n, dtype=torch.float64, device=num.device)
-        keep = getattr(self.params, "col_zero_idx_x", None) if self.prune else None
-        if keep is not None and int(keep.numel()) == ncol and num.numel() != ncol:
-            col_num[c0:c0 + ncol][keep] = num           # pruned (all-zero) columns stay 0 / 0 -> nan, as in numpy
-            col_den[c0:c0 + ncol][keep] = den
-        else:
-            col_num[c0:c0 + ncol] = num
-            col_den[c0:c0 + ncol] = den
-        self.comm1.allreduce_(col_num)
+        W, H = self._block_factors()
+        col_num, col_den = self._global_columns(*self._ops().column_err_sums(self.A_ij, W, H))   # one pass over A, no temporaries
+        self.comm1.allreduce_(col_num)                  # (pruned all-zero columns stay 0 / 0 -> nan, as in numpy)
         self.comm1.allreduce_(col_den)
         return torch.sqrt(col_num / col_den).cpu().numpy()

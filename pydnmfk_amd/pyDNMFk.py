@@ -180,33 +180,27 @@ class PyNMFk:
         from .sparse import is_sparse_input
         self._sparse = is_sparse_input(A_ij)
         self._is = str(getattr(params, "norm", None)).lower() in ("is", "itakura-saito")
-        self._beta, self.beta = False, None
-        if str(getattr(params, "norm", None)).lower() == "beta":
-            # first of all: the sweep asks one operation beyond a fit, the per-column divergence with the column's sum of a^beta
+        self._beta, self.beta = str(getattr(params, "norm", None)).lower() == "beta", None
+        for norm in ("beta", "is"):         # ('beta' first: beta = 0 IS Itakura-Saito and is then held to that norm's check as well)
+            if not (self._beta if norm == "beta" else self._is):
+                continue
+            # first of all: the sweep asks one operation beyond a fit, the per-column divergence (under norm='beta' with the column's sum
+            # of a^beta).  (The 'uniform' perturbation is multiplicative noise, which is the noise the Itakura-Saito divergence is the
+            # likelihood of, and keeps positive data positive)
             if ops is None:
                 from .engine import HIP_OPS as opset
             else:
                 opset = ops
-            if not (getattr(opset, "beta_nmfk", False) and hasattr(opset, "beta_column_div")):
-                raise NotImplementedError("PyNMFk with norm='beta' is not provided by operator set %r: rank estimation under a "
-                                          "beta-divergence needs a per-column divergence (PyNMF factorises at a given k)"
-                                          % (getattr(opset, "name", type(opset).__name__),))
-            self.beta = PyNMF._beta_value(params)
-            # beta = 0 IS Itakura-Saito: renamed, as PyNMF renames it, and swept on that path unchanged
-            self._is, self._beta = self.beta == 0.0, self.beta != 0.0
+            if not (getattr(opset, norm + "_nmfk", False) and hasattr(opset, norm + "_column_div")):
+                raise NotImplementedError("PyNMFk with norm='%s' is not provided by operator set %r: rank estimation under %s needs a "
+                                          "per-column divergence (PyNMF factorises at a given k)"
+                                          % (norm, getattr(opset, "name", type(opset).__name__),
+                                             "a beta-divergence" if norm == "beta" else "the Itakura-Saito objective"))
+            if norm == "beta":
+                self.beta = PyNMF._beta_value(params)
+                # renamed, as PyNMF renames it, and swept on that path unchanged
+                self._is, self._beta = self.beta == 0.0, self.beta != 0.0
             params.norm = 'is' if self._is else 'beta'
-        if self._is:
-            # the sweep asks one operation beyond a fit: the per-column divergence (the 'uniform' perturbation is multiplicative noise,
-            # which is the noise the Itakura-Saito divergence is the likelihood of, and keeps positive data positive)
-            params.norm = 'is'
-            if ops is None:
-                from .engine import HIP_OPS as opset
-            else:
-                opset = ops
-            if not (getattr(opset, "is_nmfk", False) and hasattr(opset, "is_column_div")):
-                raise NotImplementedError("PyNMFk with norm='is' is not provided by operator set %r: rank estimation under the "
-                                          "Itakura-Saito objective needs a per-column divergence (PyNMF factorises at a given k)"
-                                          % (getattr(opset, "name", type(opset).__name__),))
         self._masked = getattr(params, "missing", None) == "nan" and not self._sparse
         if self._masked and not (self._is or self._beta):           # (norm='is' and norm='beta' refuse missing= and sparse data by name in their setup)
             # as for a sparse block, the sweep touches A outside PyNMF.fit in the perturbed copy (NaN stays NaN through the
@@ -284,46 +278,27 @@ class PyNMFk:
         self.cp = Checkpoint(checkpoint_save=self.params.checkpoint, params=self.params)
         self.stats = {}        # k -> cluster statistics (also written to disk per k)
         self.sweep = None
-        if self._is:
-            self._is_setup(A_ij)            # (first: sparse data and missing= are refused in the norm's words)
-        if self._beta:
-            self._beta_setup(A_ij)
+        if self._is or self._beta:
+            self._div_setup(A_ij)           # (first: sparse data and missing= are refused in the norm's words)
         if self._sparse:
             self._sparse_setup(A_ij)
         if self._masked:
             self._masked_setup(A_ij)
 
-    def _is_setup(self, A_ij):
-        """norm='is': what PyNMF refuses under it is refused here, at construction, in its words (the sweep's largest rank stands for
-        k), and the data are checked for strict positivity ONCE, before the first fit; every perturbed copy is positive then
-        (1 + nv + 2 nv U > 0).  'poisson' sampling is refused: a draw of 0 makes the divergence infinite."""
+    def _div_setup(self, A_ij):
+        """norm='is' and norm='beta' (beta != 0): what PyNMF refuses under the norm is refused here, at construction, in its words (the
+        sweep's largest rank stands for k), and the data's sign is checked ONCE, before the first fit -- strictly positive under 'is' and
+        for beta <= 0, non-negative for beta > 0; the ranks agree on the verdict before any of them raises.  The 'uniform' perturbation
+        keeps either property (1 + nv + 2 nv U > 0).  'poisson' sampling is refused where a draw of 0 makes the divergence infinite:
+        under 'is' and for beta <= 0; for beta > 0 a zero is legal data and the sampling is allowed."""
         from .pyDNMF import storage_dtype
-        params = self.params
+        params, beta = self.params, (self.beta if self._beta else None)
         a_dtype = torch.float32 if self._sparse else storage_dtype(A_ij, params)
-        PyNMF._is_refusals(params, self._sparse, getattr(params, "missing", None), a_dtype, self.ops,
-                           var_init(params, 'method', default='mu'), self.p_r, self.p_c, int(self.end_k))
-        if self.sampling == 'poisson':
+        PyNMF._div_refusals('beta' if self._beta else 'is', params, self._sparse, getattr(params, "missing", None), a_dtype, self.ops,
+                            var_init(params, 'method', default='mu'), self.p_r, self.p_c, int(self.end_k))
+        if self.sampling == 'poisson' and beta is None:
             raise NotImplementedError("PyNMFk with norm='is' and sampling='poisson' is not provided: a Poisson draw of 0 makes the "
                                       "Itakura-Saito divergence infinite (sampling='uniform', multiplicative noise, keeps the data positive)")
-        if self.ops is None:
-            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda:
-                raise TypeError("PyNMFk: A_ij is a CPU tensor; pass a CUDA tensor or a numpy array (no CPU fallback)")
-            if not torch.cuda.is_available():
-                raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
-        lo = float(A_ij.min()) if int(np.prod(A_ij.shape)) else 1.0
-        PyNMF._is_positive(lo, self.comm1, self.p)
-
-    def _beta_setup(self, A_ij):
-        """norm='beta' (beta != 0): what PyNMF refuses under it is refused here, at construction, in its words (the sweep's largest rank
-        stands for k), and the data's sign is checked ONCE, before the first fit -- strictly positive for beta <= 0, non-negative for
-        beta > 0; the ranks agree on the verdict before any of them raises.  The 'uniform' perturbation keeps either property
-        (1 + nv + 2 nv U > 0).  'poisson' sampling is refused for beta <= 0, where a draw of 0 makes the divergence infinite; for
-        beta > 0 a zero is legal data and the sampling is allowed."""
-        from .pyDNMF import storage_dtype
-        params, beta = self.params, self.beta
-        a_dtype = torch.float32 if self._sparse else storage_dtype(A_ij, params)
-        PyNMF._beta_refusals(params, self._sparse, getattr(params, "missing", None), a_dtype, self.ops,
-                             var_init(params, 'method', default='mu'), self.p_r, self.p_c, int(self.end_k))
         if self.sampling == 'poisson' and beta <= 0.0:
             raise NotImplementedError("PyNMFk with norm='beta', beta = %g and sampling='poisson' is not provided: a Poisson draw of 0 makes "
                                       "the divergence infinite for beta <= 0 (sampling='uniform', multiplicative noise, keeps the data "
@@ -333,14 +308,7 @@ class PyNMFk:
                 raise TypeError("PyNMFk: A_ij is a CPU tensor; pass a CUDA tensor or a numpy array (no CPU fallback)")
             if not torch.cuda.is_available():
                 raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
-        lo = float(A_ij.min()) if int(np.prod(A_ij.shape)) else 1.0
-        bad = not (lo > 0.0 if beta <= 0.0 else lo >= 0.0)          # (a NaN minimum is refused as well)
-        nbad = int(self.comm1.allreduce(1 if bad else 0))
-        if nbad:
-            raise ValueError("norm='beta' with beta = %g needs %s data: the smallest entry of this rank's block is %g (%d of %d ranks hold "
-                             "an entry %s 0)%s" % (beta, "strictly positive" if beta <= 0.0 else "non-negative", lo, nbad, self.p,
-                                                   "<=" if beta <= 0.0 else "<",
-                                                   "; the divergence is infinite at a zero for beta <= 0" if beta <= 0.0 else ""))
+        PyNMF._sign_check(beta, float(A_ij.min()) if int(np.prod(A_ij.shape)) else 1.0, self.comm1, self.p)
 
     def _masked_setup(self, A_ij):
         """missing='nan': the raw array stays `self.A_ij` (every PyNMF wraps its perturbed copy in a MaskedDenseBlock itself); what PyNMF

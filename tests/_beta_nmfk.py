@@ -175,7 +175,7 @@ def assert_split_equals_one_rank(outs):
                 assert np.allclose(np.asarray(o[1][k][key]), np.asarray(val), rtol=1e-9, atol=0, equal_nan=True), (k, key)
 
 
-# ---- exact operands of the per-column kernel (csrc/dnmf_beta.h: beta_coldiv_kernel)
+# ---- exact operands of the per-column kernel (csrc/dnmf_sums.h: col_sums_kernel with the terms BetaDivTerm<FORM, 2>; the general form: beta_coldiv_kernel)
 _COLDIV = {}
 
 

@@ -1,5 +1,5 @@
-"""Operands for the two scalar divergence reductions, is_div_kernel (csrc/dnmf_is.h) and beta_div_kernel (csrc/dnmf_beta.h), which share
-is_div_sum_kernel (TEST INFRASTRUCTURE, lives under tests/ only).
+"""Operands for the two scalar divergence reductions, tile_sum_kernel (csrc/dnmf_sums.h) behind dnmf_is_divergence and dnmf_beta_divergence, which share
+slot_sum_kernel (TEST INFRASTRUCTURE, lives under tests/ only).
 
 Both give a wave one 32 x 128 tile of the block (tile gw = row block * ncolblk + column block, its sum in slot gw of the workspace); a
 lane adds the terms of 16 rows by 4 contiguous columns in fp32; everything after that is float64.  Nothing here encodes which rows a
@@ -243,7 +243,7 @@ def with_fault(form, A, S, L, fault, fma=False):
 def emulate(T, seed=0):
     """{order: total} of the float32 terms T: a fp32 partial per cell (its 128 positions added forwards, backwards or in a random
     order; padding adds nothing), a tile's 32 cell partials and then the slots in float64 -- the slots forwards, backwards, in a random
-    order, and as is_div_sum_kernel does (thread t adds the slots t, t + 256, ..., then a tree over the 256 sums)"""
+    order, and as slot_sum_kernel does (thread t adds the slots t, t + 256, ..., then a tree over the 256 sums)"""
     m, n = T.shape
     g = geometry(m, n)
     nrb, ncb = g["nrowblk"], g["ncolblk"]

@@ -178,7 +178,7 @@ def assert_split_equals_one_rank(outs):
                 assert np.allclose(np.asarray(o[1][k][key]), np.asarray(val), rtol=1e-9, atol=0, equal_nan=True), (k, key)
 
 
-# ---- exact operands of the per-column divergence kernel (csrc/dnmf_is.h: is_coldiv_kernel)
+# ---- exact operands of the per-column divergence kernel (csrc/dnmf_sums.h: col_sums_kernel with the term BetaDivTerm<BETA_DIV_IS, 1>)
 _COLDIV = {}
 
 

@@ -120,7 +120,7 @@ def run_nmfk_golden_nan(fixture, use_hip=False, timeout=600, extra=None):
     return [out for _, out, _ in sorted(res, key=lambda r: r[0])]
 
 
-# ---- exact operands of the per-column error kernel (csrc/dnmf_masked.h: masked_colerr_kernel)
+# ---- exact operands of the per-column error kernel (csrc/dnmf_sums.h: col_sums_kernel<KT, FAST, MaskedErrTerm>)
 # EXACT_SHAPES of tests/_masked_dense.py stay at one 128-column block and one 32-row block per chunk.  COLERR_LOOP_CASES are the
 # smallest shapes whose plan (dnmf_masked_column_err_plan: {rowblks_per_chunk, nchunks, ncolblk}) leaves one trip of each loop; what
 # tests/test_capi_masked_nmfk.py must find in the plan at EVERY rank:
@@ -170,7 +170,7 @@ def colerr_ref(A, mask, W, H):
 
 
 def tile_partials(A, mask, W, H):
-    """the largest fp32 partial of masked_colerr_kernel: per column, per 32-row block and per lane half h, the sums of (a - S)^2 and
+    """the largest fp32 partial of col_sums_kernel<KT, FAST, MaskedErrTerm>: per column, per 32-row block and per lane half h, the sums of (a - S)^2 and
     of a^2 over the observed ones of the 16 rows crow(r, h) = (r & 3) + 8 (r >> 2) + 4 h"""
     m, n = A.shape
     A64, Dm = A.astype(np.float64), W.astype(np.float64) @ H.astype(np.float64)

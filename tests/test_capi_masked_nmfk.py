@@ -2,7 +2,7 @@
 dnmf_masked_{ws_bytes_fit,mu_fit}) without a GPU: every bad argument is refused by the host-side checks before any launch -- the
 pointers are made-up addresses that nothing may dereference (the pattern of tests/test_capi.py) --, the workspace query equals the
 slab recomputed from the plan, and the plan shows which shapes of tests/test_gpu_masked_nmfk.py enter which loop of
-masked_colerr_kernel (tests/_masked_nmfk.py::COLERR_LOOP_CASES)."""
+col_sums_kernel (tests/_masked_nmfk.py::COLERR_LOOP_CASES)."""
 import ctypes
 
 import pytest

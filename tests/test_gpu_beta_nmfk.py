@@ -1,4 +1,4 @@
-"""NMFk under a beta-divergence (`params.norm = 'beta'`) on the GPU: the per-column kernel (csrc/dnmf_beta.h: beta_coldiv_kernel) on
+"""NMFk under a beta-divergence (`params.norm = 'beta'`) on the GPU: the per-column kernels (csrc/dnmf_sums.h: col_sums_kernel, beta_coldiv_kernel) on
 exact operands bit for bit at beta = 1 and on random data against float64 over the accepted range, its workspace contract,
 PyNMF.beta_column_divergence() on one rank and on both 1D grids, the planted sweep through pydnmfk_amd.pyDNMFk from numpy and from
 device input against the float64 checker set's estimate of the same array, and main.py --process pyDNMFk --norm beta.
@@ -271,3 +271,34 @@ def test_main_pydnmfk_norm_beta_end_to_end(tmp_path):
             assert np.asarray(z["L_err"]).shape == (90,)
             found += 1
     assert found == 2, (found, out.stdout[-1000:])
+
+
+# ------------------------------------------------------------------------------------- one walk, one term: 'is' and beta = 0 agree
+@pytest.mark.parametrize("k", [3, 40, 100], ids=lambda k: "k=%d" % k)
+def test_is_and_beta_zero_share_their_bits(k):
+    """The Itakura-Saito entry points and the beta ones at beta = 0 run the same tile walks (csrc/dnmf_sums.h: tile_sum_kernel and
+    col_sums_kernel) with the same term, BetaDivTerm<BETA_DIV_IS, .> -- the per-column walk once with one sum per column and once with
+    two.  On strictly positive random operands, 70 x 300 (three column blocks, the last ragged; three 32-row blocks, the last ragged; a
+    partly filled last workgroup), KT = 1, 2, 4, on contiguous tensors and on views at an odd base with an odd pitch (the generic
+    loads): is_divergence == beta_divergence(., 0.0) and is_column_div == beta_column_div(., 0.0)[0] bit for bit, and the second
+    output, the column's sum of a^0, is the row count.  No tolerance."""
+    m, n = 70, 300
+    rs = np.random.RandomState(1000 + k)
+    A, W, H = (rs.uniform(0.25, 2.0, s).astype(np.float32) for s in ((m, n), (m, k), (k, n)))
+    ops = _ops()
+    for aligned in (True, False):
+        if aligned:
+            Ad, Wd, Hd = (torch.from_numpy(x).cuda() for x in (A, W, H))
+        else:
+            Ad, Wd, Hd = (E.Poisoned(torch, x, aligned=False, fill=float("nan"), ld=x.shape[1] + 3 + x.shape[1] % 2).view for x in (A, W, H))
+            assert all(t.data_ptr() % 16 and t.stride(0) % 2 == 1 for t in (Ad, Wd, Hd))
+        d_is = ops.is_divergence(Ad, Wd, Hd, EPS).cpu().numpy()
+        d_b0 = ops.beta_divergence(Ad, Wd, Hd, EPS, 0.0).cpu().numpy()
+        c_is = ops.is_column_div(Ad, Wd, Hd, EPS).cpu().numpy()
+        c_b0, pw = (x.cpu().numpy() for x in ops.beta_column_div(Ad, Wd, Hd, EPS, 0.0))
+        tag = "k=%d %s" % (k, "contiguous" if aligned else "odd views")
+        print("%s: divergence %r / %r, column sums differ in %d of %d" % (tag, d_is[0], d_b0[0], int((_bits(c_is) != _bits(c_b0)).sum()), n))
+        assert np.isfinite(d_is).all() and d_is[0] > 0.0 and np.isfinite(c_is).all() and (c_is > 0.0).all(), tag
+        assert np.array_equal(_bits(d_is), _bits(d_b0)), (tag, d_is, d_b0)
+        assert c_is.shape == (n,) and np.array_equal(_bits(c_is), _bits(c_b0)), (tag, np.flatnonzero(c_is != c_b0)[:4])
+        assert np.array_equal(pw, np.full(n, float(m))), (tag, np.flatnonzero(pw != m)[:4])

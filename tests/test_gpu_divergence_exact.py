@@ -1,5 +1,5 @@
-"""The two scalar divergence reductions on the GPU -- is_div_kernel (csrc/dnmf_is.h) and beta_div_kernel<KT, FAST, FORM>
-(csrc/dnmf_beta.h), both ended by is_div_sum_kernel -- through HIP_OPS.is_divergence and HIP_OPS.beta_divergence on planted exact
+"""The two scalar divergence reductions on the GPU -- tile_sum_kernel<KT, FAST, BetaDivTerm<FORM, 1>>
+(csrc/dnmf_sums.h) behind both entry points, ended by slot_sum_kernel -- through HIP_OPS.is_divergence and HIP_OPS.beta_divergence on planted exact
 operands (tests/_div.py; tests/test_divergence_cases_cpu.py shows that the answers are exact in every order and that one faulty
 position breaks them), tile by tile:
 

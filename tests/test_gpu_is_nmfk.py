@@ -1,5 +1,5 @@
-"""NMFk under the Itakura-Saito objective (`params.norm = 'is'`) on the GPU: the per-column divergence (csrc/dnmf_is.h:
-is_coldiv_kernel) on exact operands bit for bit and on random data against float64, PyNMF.is_column_divergence() on one rank and on
+"""NMFk under the Itakura-Saito objective (`params.norm = 'is'`) on the GPU: the per-column divergence (csrc/dnmf_sums.h:
+col_sums_kernel with the term BetaDivTerm<BETA_DIV_IS, 1>) on exact operands bit for bit and on random data against float64, PyNMF.is_column_divergence() on one rank and on
 both 1D grids, the planted sweep through pydnmfk_amd.pyDNMFk from numpy and from device input, and the perturbation split."""
 import ctypes
 import time

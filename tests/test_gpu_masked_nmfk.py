@@ -1,5 +1,5 @@
 """NMFk over dense data with NaN-marked gaps (`params.missing = 'nan'`) on the GPU: the masked per-column error
-(csrc/dnmf_masked.h: masked_colerr_kernel) on exact operands element by element and on random data against float64, the perturbation
+(csrc/dnmf_sums.h: col_sums_kernel<KT, FAST, MaskedErrTerm>) on exact operands element by element and on random data against float64, the perturbation
 of a NaN-marked tensor, the whole masked fit as one library call (dnmf_masked_mu_fit) against the step loop, and the sweeps through
 pydnmfk_amd.pyDNMFk."""
 import ctypes

@@ -175,7 +175,7 @@ def test_oracle_column_err_runs_over_the_observed_positions():
 
 @pytest.mark.parametrize("shape", N.COLERR_SHAPES, ids=lambda s: "%dx%d" % s)
 def test_colerr_exact_operands_keep_every_partial_an_integer_below_2_24(shape):
-    """masked_colerr_kernel adds, per column and lane half, the (a - S)^2 and a^2 of the observed ones of 16 rows in float32 (fmaf on
+    """col_sums_kernel<KT, FAST, MaskedErrTerm> adds, per column and lane half, the (a - S)^2 and a^2 of the observed ones of 16 rows in float32 (fmaf on
     integers: exact while every intermediate stays below 2^24), and float64 from there on.  Asserted here for the operands the GPU test
     uses: the model values are integers (so every difference is), the largest 16-row partial is below 2^24, the column sums are
     integers below 2^53, and at least two columns have no observation."""
