@@ -556,7 +556,12 @@ int dnmf_f64_plan(int op, long m, long n, int k, const long* ld, int method, lon
  *           KL16_WTU = kl_wtu16_kernel (B0 / BL: 16-row blocks, two per trip, and rows left of the first / last chunk)
  *   FAMILY  DNMF_DENSE_FAM_*: NT16 = nt16_kernel, NT = nt_kernel, TN16 / TN16_GRAM = tn16_kernel without / with the riding Gram, TN =
  *           tn_kernel, UPDATE_W16 / UPDATE_W_SEQ / UPDATE_H_SEQ = the kernels of csrc/dnmf_update.h, EW = ew_kernel, WIDE = 128 < k <= 256: the
- *           entry point runs COUNT panel calls of PER columns of the factor (query them at k = 128 and k - 128), NONE = it refuses
+ *           entry point runs COUNT panel calls of PER columns of the factor (query them at k = 128 and k - 128, with the second panel's
+ *           pitches and addresses: H + PER ldh, W + PER); for the ops that launch a plain kernel of csrc/dnmf_wide.hip, GRID_X, GRID_Y and
+ *           BLOCK are that launch -- MU_UPDATE_W, KL_UHT, KL_WTU (the quotient U), RESID_SQNORM, COLUMN_ERR: wide_nn_rows_kernel, a wave per
+ *           16-row strip, GRID_Y column ranges, AUX = 16-column tiles of a full range (the last range may have fewer, its last tile may be
+ *           ragged; MU_UPDATE_W: one range over the k columns); MU_UPDATE_H: wide_upd_h_kernel, a wave per 16 columns, AUX = 16-row tiles
+ *           of k; NONE = it refuses
  *           (workspace too small, a pitch beyond the 32-bit tile offsets, a shape that is neither a long-row nor a patch one)
  *   KT, FAST, MODE, PF, NT, V, EDGE, OCC   the template arguments of that name (MODE: 0 NT_STORE, 1 NT_FUSED_W; EW: 1 = the long-row form,
  *           V = 4 or 1; TN16: V = columns per lane; UPDATE_W16: the template's NWV is BLOCK / 64)

@@ -1085,6 +1085,17 @@ extern "C" int dnmf_dense_plan(int op, int bf16a, long m, long n, int k, const l
         out[DNMF_DENSE_PLAN_FAMILY] = DNMF_DENSE_FAM_WIDE;
         out[DNMF_DENSE_PLAN_COUNT] = (op == DNMF_DENSE_OP_GRAM_HHT || op == DNMF_DENSE_OP_GRAM_WTW) ? 4 : 2;
         out[DNMF_DENSE_PLAN_PER] = WIDE_PANEL;
+        // the launch of the plain kernel the op runs besides (or, for the updates, instead of) its panel calls
+        const bool rows_w = op == DNMF_DENSE_OP_MU_UPDATE_W;
+        if (rows_w || op == DNMF_DENSE_OP_KL_UHT || op == DNMF_DENSE_OP_KL_WTU || op == DNMF_DENSE_OP_RESID_SQNORM ||
+            op == DNMF_DENSE_OP_COLUMN_ERR) {                       // wide_nn_rows_kernel: W G over the k columns, or W H over the n columns of A
+            const WideRowsGrid g = wide_rows_grid(rows_w, m, rows_w ? k : n);
+            out[DNMF_DENSE_PLAN_GRID_X] = g.gx; out[DNMF_DENSE_PLAN_GRID_Y] = g.gy; out[DNMF_DENSE_PLAN_BLOCK] = 256;
+            out[DNMF_DENSE_PLAN_AUX] = cdiv(g.cpw, 16);
+        } else if (op == DNMF_DENSE_OP_MU_UPDATE_H) {               // wide_upd_h_kernel
+            out[DNMF_DENSE_PLAN_GRID_X] = wide_upd_h_grid(n); out[DNMF_DENSE_PLAN_GRID_Y] = 1; out[DNMF_DENSE_PLAN_BLOCK] = 256;
+            out[DNMF_DENSE_PLAN_AUX] = cdiv(k, 16);
+        }
         return DNMF_OK;
     }
     const int kt = kt_of(k), kp = 32 * kt;

@@ -15,6 +15,21 @@ int kt_of(int k) {      // 32-wide tiles of the TUNED kernels' padded rank; -1 b
 inline bool wide_k(int k) { return k > DNMF_TUNED_MAX_K && k <= DNMF_MAX_K; }
 inline int kp_of(int k) { return wide_k(k) ? 256 : (kt_of(k) < 0 ? -1 : 32 * kt_of(k)); }
 constexpr int WIDE_PANEL = 128;          // the panels a wide rank is cut into
+// The launches of the plain wide kernels (csrc/dnmf_wide.hip launches from these; dnmf_dense_plan reports them).
+// wide_nn_rows_kernel: a wave per 16-row strip, 4 per workgroup, grid.y column ranges of cpw columns each (the last may be shorter).
+// whole_width (W_UPD_W: the wave owns its rows across the whole width): one range.  Otherwise about 8192 (strip, range) waves, a
+// range never below 64 columns.
+struct WideRowsGrid { long cpw; unsigned gx, gy; };
+inline WideRowsGrid wide_rows_grid(bool whole_width, long m, long n) {
+    long cpw = n;
+    if (!whole_width) {
+        const long want = std::max<long>(1, 8192 / cdiv(m, 16));
+        cpw = std::max<long>(64, round_up(cdiv(n, want), 16));
+    }
+    return WideRowsGrid{cpw, (unsigned)cdiv(cdiv(m, 16), 4), (unsigned)cdiv(n, cpw)};
+}
+// wide_upd_h_kernel: a wave per 16 columns of H, 4 per workgroup
+inline unsigned wide_upd_h_grid(long n) { return (unsigned)cdiv(cdiv(n, 16), 4); }
 
 template <typename K>
 void allow_lds(K kernel, size_t bytes) {

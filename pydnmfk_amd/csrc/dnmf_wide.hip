@@ -132,13 +132,8 @@ __global__ __launch_bounds__(256) void wide_hals_h_kernel(float* H, int k, long 
 template <int MODE>
 int launch_rows(const float* X, long ldx, long m, int kc, const float* Y, long ldy, long n, const float* A, long lda, float* O, long ldo,
                 float eps, double* dsum, double* den, hipStream_t st) {
-    long cpw = n;                                                   // W_UPD_W: the wave owns its rows across the whole width
-    if (MODE != W_UPD_W) {
-        const long want = std::max<long>(1, 8192 / cdiv(m, 16));
-        cpw = std::max<long>(64, round_up(cdiv(n, want), 16));
-    }
-    const dim3 grid((unsigned)cdiv(cdiv(m, 16), 4), (unsigned)cdiv(n, cpw));
-    DNMF_LAUNCH((wide_nn_rows_kernel<MODE>), grid, dim3(256), 0, st, X, ldx, m, kc, Y, ldy, n, A, lda, O, ldo, eps, cpw, dsum, den);
+    const WideRowsGrid g = wide_rows_grid(MODE == W_UPD_W, m, n);   // W_UPD_W: the wave owns its rows across the whole width
+    DNMF_LAUNCH((wide_nn_rows_kernel<MODE>), dim3(g.gx, g.gy), dim3(256), 0, st, X, ldx, m, kc, Y, ldy, n, A, lda, O, ldo, eps, g.cpw, dsum, den);
     return check_launch("wide nn");
 }
 
@@ -162,7 +157,7 @@ int dnmf_wide_mu_update_w_(float* W, long m, int k, long ldw, const float* AH, l
 }
 int dnmf_wide_mu_update_h_(float* H, int k, long n, long ldh, const float* AtW, long ldatw, const float* G, long ldg, float eps, int clamp,
                            void* stream) {
-    DNMF_LAUNCH(wide_upd_h_kernel, dim3((unsigned)cdiv(cdiv(n, 16), 4)), dim3(256), 0, S(stream), H, k, n, ldh, AtW, ldatw, G, ldg, eps, clamp);
+    DNMF_LAUNCH(wide_upd_h_kernel, dim3(wide_upd_h_grid(n)), dim3(256), 0, S(stream), H, k, n, ldh, AtW, ldatw, G, ldg, eps, clamp);
     return check_launch("wide mu_update_h");
 }
 int dnmf_wide_quot_(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps, float* U,

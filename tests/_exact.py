@@ -1655,6 +1655,174 @@ def dense_plan_args(op, m, n, k, aligned, bf16, quantum8=True):
     return ld, off
 
 
+# ---------------------------------------------------------------------------------------------------------- ranks 128 < k <= 256
+# The shapes of tests/test_gpu_exact_wide.py, in the layout of DENSE_REACH: (id, op, m, n, k, aligned, bf16-stored A, plan fields).  A wide
+# rank is served by composition (csrc/dnmf_wide.hip): two panel calls of the tuned kernels, the second at r = k - 128 on sub-views, four
+# block calls for a Gram, and the plain kernels wide_nn_rows_kernel / wide_upd_h_kernel.  The plan fields of a case:
+#   panel     (family, kt, fast) of the LAST tuned call the entry point issues (`wide_panel_plans`): the second panel, block (1, 1) of a Gram
+#   gram10    the family of block (1, 0) of W^T W, r x 128: the 16-wide kernel when W's rows are 16-byte aligned and r <= 16
+#   grid_x, grid_y, aux   the launch of the plain kernel as dnmf_dense_plan reports it at the wide rank (aux: 16-column tiles of a full
+#             column range; mu_update_h: 16-row tiles of k)
+# tests/test_dense_plan.py asserts every entry and what the union covers without a GPU; tests/test_exact_cpu.py proves the operands.
+_N16, _T16 = ("nt16", 1, 1), ("tn16", 1, 1)
+# (class, m, n, k, aligned, second panel of the NT form, of the TN form, block (1, 1) of W^T W, family of block (1, 0) of W^T W)
+WIDE_PANEL_CLASSES = [
+    # r <= 16 on the 16-wide kernels: 16-byte aligned rows, n a multiple of 64
+    ("r4-16wide", 300, 256, 132, True, _N16, _T16, ("tn", 1, 1), "tn16"),
+    ("r16-16wide", 300, 256, 144, True, _N16, _T16, ("tn", 1, 1), "tn16"),
+    # r <= 16 where they do not apply: 32-wide at KT = 1 -- an unaligned view, n % 32 != 0, k % 4 = 2 and 3
+    ("r4-unaligned", 300, 256, 132, False, ("nt", 1, 0), ("tn", 1, 0), ("tn", 1, 0), "tn"),
+    ("r16-n%32", 261, 332, 144, True, ("nt", 1, 1), ("tn", 1, 1), ("tn", 1, 1), "tn16"),
+    ("r2-k%4=2", 261, 331, 130, True, ("nt", 1, 0), ("tn", 1, 0), ("tn", 1, 0), "tn16"),
+    ("r3-k%4=3-unaligned", 261, 331, 131, False, ("nt", 1, 0), ("tn", 1, 0), ("tn", 1, 0), "tn"),
+    # the two sides of the KT boundaries
+    ("r17", 300, 256, 145, True, ("nt", 1, 1), ("tn", 1, 1), ("tn", 1, 0), "tn"),
+    ("r32-unaligned", 261, 331, 160, False, ("nt", 1, 0), ("tn", 1, 0), ("tn", 1, 0), "tn"),
+    ("r33", 300, 256, 161, True, ("nt", 2, 1), ("tn", 2, 0), ("tn", 2, 0), "tn"),
+    ("r33-unaligned", 261, 331, 161, False, ("nt", 2, 0), ("tn", 2, 0), ("tn", 2, 0), "tn"),
+    ("r64", 300, 256, 192, True, ("nt", 2, 1), ("tn", 2, 1), ("tn", 2, 1), "tn"),
+    ("r65-unaligned", 261, 331, 193, False, ("nt", 4, 0), ("tn", 4, 0), ("tn", 4, 0), "tn"),
+    ("r127", 300, 256, 255, True, ("nt", 4, 1), ("tn", 4, 0), ("tn", 4, 0), "tn"),
+    ("r128", 300, 256, 256, True, ("nt", 4, 1), ("tn", 4, 1), ("tn", 4, 1), "tn"),
+]
+WIDE_BF16_CLASSES = ("r4-16wide", "r16-16wide", "r33", "r65-unaligned", "r127")      # bf16-stored A for the products: the same kernels
+# the quotient image U of the KL products is 16-byte aligned whatever the caller's views are: W^T U of an unaligned case with whole
+# 64-column blocks stays on the 16-wide kernel
+WIDE_KLWTU_PANEL = {"r4-unaligned": _T16}
+
+
+def _wpanel(p, **kw):
+    return dict(panel=dict(family=p[0], kt=p[1], fast=p[2]), **kw)
+
+
+def _wide_panel_cases():
+    out = []
+    for name, m, n, k, al, ntp, tnp, w11, w10 in WIDE_PANEL_CLASSES:
+        gy, gx = -(-n // 64), -(-(-(-m // 16)) // 4)                # (these shapes: ranges of the minimum 64 columns, 4 tiles)
+        out += [("aht-" + name, "aht", m, n, k, al, False, _wpanel(ntp)),
+                ("wta-" + name, "wta", m, n, k, al, False, _wpanel(tnp)),
+                ("wtagram-" + name, "wta_gram", m, n, k, al, False, _wpanel(tnp, gram10=w10)),
+                ("hht-" + name, "gram_hht", 0, n, k, al, False, _wpanel(ntp)),
+                ("wtw-" + name, "gram_wtw", m, 0, k, al, False, _wpanel(w11, gram10=w10)),
+                ("kluht-" + name, "kl_uht", m, n, k, al, False, _wpanel(ntp, grid_x=gx, grid_y=gy, aux=4)),
+                ("klwtu-" + name, "kl_wtu", m, n, k, al, False, _wpanel(WIDE_KLWTU_PANEL.get(name, tnp), grid_x=gx, grid_y=gy, aux=4))]
+        if name in WIDE_BF16_CLASSES:
+            out += [("aht-%s-bf16" % name, "aht", m, n, k, al, True, _wpanel(ntp)),
+                    ("wta-%s-bf16" % name, "wta", m, n, k, al, True, _wpanel(tnp)),
+                    ("wtagram-%s-bf16" % name, "wta_gram", m, n, k, al, True, _wpanel(tnp, gram10=w10))]
+    return out
+
+
+# The plain kernels.  wide_nn_rows_kernel<W_QUOT | W_SQSUM | W_COLERR> (through kl_uht / kl_wtu, resid_sqnorm, column_err): a wave per
+# 16-row strip, grid_y column ranges of 16 aux columns.  BIG: 513 strips, ranges of 5 tiles, 13 of them, the last of 40 columns with a
+# ragged last tile.  TALL: more than 8192 strips, where the launcher asks for ONE range whatever n is -- 5 tiles, the last ragged -- and
+# the last of 2049 workgroups has one live wave (W alone is 64.5 MiB there: no m above 131072 keeps a wide W below 64 MiB).
+WIDE_BIG, WIDE_TALL = (8200, 1000), (131088, 70)
+WIDE_PLAIN = (
+    [("%s-5-tile-ranges-ragged" % s, op, WIDE_BIG[0], WIDE_BIG[1], 130, al, False, dict(grid_x=129, grid_y=13, aux=5))
+     for s, op, al in (("kluht", "kl_uht", True), ("klwtu-unaligned", "kl_wtu", False), ("resid", "resid_sqnorm", True),
+                       ("colerr-unaligned", "column_err", False))]
+    + [("%s-one-range-of-5-tiles" % s, op, WIDE_TALL[0], WIDE_TALL[1], 130, True, False, dict(grid_x=2049, grid_y=1, aux=5))
+       for s, op in (("kluht", "kl_uht"), ("resid", "resid_sqnorm"), ("colerr", "column_err"))]
+    # n < 16 and n = 1 (one ragged tile); m % 16 != 0; 17 strips: the last workgroup has one live wave; ranges of 4 tiles with a ragged last
+    # range at k % 4 = 3 and at k = 256
+    + [("%s-n9-k131" % s, op, 300, 9, 131, al, False, dict(grid_x=5, grid_y=1, aux=4))
+       for s, op, al in (("kluht", "kl_uht", False), ("klwtu", "kl_wtu", True), ("resid", "resid_sqnorm", False), ("colerr", "column_err", True))]
+    + [("%s-n1-k130" % s, op, 261, 1, 130, al, False, dict(grid_x=5, grid_y=1, aux=4))
+       for s, op, al in (("kluht", "kl_uht", True), ("klwtu", "kl_wtu", False), ("resid", "resid_sqnorm", True), ("colerr", "column_err", False))]
+    + [("%s-6-ranges-k%d%s" % (s, k, "" if al else "-unaligned"), op, 261, 331, k, al, False, dict(grid_x=5, grid_y=6, aux=4))
+       for s, op in (("resid", "resid_sqnorm"), ("colerr", "column_err")) for k, al in ((131, False), (256, True))]
+    # wide_nn_rows_kernel<W_UPD_W>: one range over the k columns of W -- k % 16 != 0 (a ragged last tile; k % 4 = 2, 3: the lane mask),
+    # k = 255 and k = 256
+    + [("updw-k%d%s" % (k, "" if al else "-unaligned"), "mu_update_w", m, 0, k, al, False, dict(grid_x=5, grid_y=1, aux=-(-k // 16)))
+       for m, k, al in ((261, 130, True), (300, 131, False), (261, 255, False), (300, 256, True))]
+    # wide_upd_h_kernel: a wave per 16 columns, a loop over the 16-row tiles of k -- a ragged last row tile, a ragged last column tile, a
+    # partly filled last workgroup (21 tiles: 6 workgroups, the last with one wave), n = 1 and n = 9, whole tiles throughout at k = 256
+    + [("updh-k%d-n%d%s" % (k, n, "" if al else "-unaligned"), "mu_update_h", 0, n, k, al, False,
+        dict(grid_x=-(-(-(-n // 16)) // 4), grid_y=1, aux=-(-k // 16)))
+       for n, k, al in ((331, 131, True), (1, 130, False), (9, 255, True), (331, 193, False), (256, 256, True))]
+)
+WIDE_REACH = _wide_panel_cases() + list(WIDE_PLAIN)
+WIDE_ROWS_OPS = ("kl_uht", "kl_wtu", "resid_sqnorm", "column_err")      # the ops that launch wide_nn_rows_kernel over the columns of A
+# whole fits on fixed points (tests/test_gpu_exact_wide.py): `fro_fixed`, `kl_fixed`, `kl_moved` at one shape (m, n not divisible by 3)
+WIDE_FIT_SHAPE = (260, 334)
+WIDE_FIT_KS = (130, 161, 255)
+WIDE_FIT_STEPS = (1, 11, 12)                                        # the clamp step is i % 10 == 0: steps 0 and 10
+
+
+def wide_panel_plans(op, m, n, k, ld, off, bf16=False, ws_bytes=None):
+    """The tuned-kernel calls an entry point issues at a wide rank (128 < k <= 256; csrc/dnmf.hip: aht_impl, wta_impl, wide_gram;
+    csrc/dnmf_kl.hip: wide_kl_product), as dnmf_dense_plan answers each one at the call's own rank, pitches and addresses modulo 16.
+    ld / off: the pitches (elements) and addresses modulo 16 (bytes) of the op's operands in the order of include/dnmf.h; ws_bytes: the
+    caller's workspace (None: dnmf_ws_bytes).  Returns (the wide plan, the calls' plans in the order they are issued): the products
+    issue two -- rows of H, columns of W --, the Grams four blocks (p, q) = (0, 0), (0, 1), (1, 0), (1, 1), wta_gram the four of W^T W and
+    then its two panels; the KL products run theirs on the quotient image U (pitch n rounded up to 4, in the workspace)."""
+    from pydnmfk_amd import _lib as L
+    m, n = max(m, 1), max(n, 1)
+    if ws_bytes is None:
+        ws_bytes = L.lib.dnmf_ws_bytes(m, n, k)
+    wide = L.dense_plan(op, m, n, k, ld, off, bf16a=bf16, ws_bytes=ws_bytes)
+    assert wide["family"] == "wide", (op, k, wide)
+    per = wide["per"]
+    ks = (per, k - per)
+    assert 0 < ks[1] <= per and wide["count"] == (4 if op.startswith("gram") else 2)
+    adv = lambda o, elems: (o + 4 * elems) % 16                      # a float32 operand advanced by `elems` elements
+
+    def gram_wtw(ldw, offw):                                         # W_p^T W_q = "W^T A" with A = W_q, into the 256-pitch Gram buffer
+        return [L.dense_plan("wta", m, ks[q], ks[p], [ldw, ldw, 256], [adv(offw, q * per), adv(offw, p * per), 0], ws_bytes=ws_bytes)
+                for p in (0, 1) for q in (0, 1)]
+    if op == "aht":
+        plans = [L.dense_plan("aht", m, n, ks[j], ld[:2], [off[0], adv(off[1], j * per * ld[1])], bf16a=bf16) for j in (0, 1)]
+    elif op in ("wta", "wta_gram"):
+        plans = gram_wtw(ld[1], off[1]) if op == "wta_gram" else []
+        plans += [L.dense_plan("wta", m, n, ks[j], ld[:3], [off[0], adv(off[1], j * per), adv(off[2], j * per * ld[2])], bf16a=bf16,
+                               ws_bytes=ws_bytes) for j in (0, 1)]
+    elif op == "gram_hht":                                           # H_p H_q^T = "A H^T" with A = H_p
+        plans = [L.dense_plan("aht", ks[p], n, ks[q], [ld[0], ld[0]], [adv(off[0], p * per * ld[0]), adv(off[0], q * per * ld[0])])
+                 for p in (0, 1) for q in (0, 1)]
+    elif op == "gram_wtw":
+        plans = gram_wtw(ld[0], off[0])
+    elif op in ("kl_uht", "kl_wtu"):
+        ldu = -(-n // 4) * 4
+        ub = -(-m * ldu * 4 // 256) * 256
+        assert ws_bytes >= ub
+        inner = (ws_bytes - ub) // 256 * 256                         # what is left in front of U for the panel calls
+        if op == "kl_uht":
+            plans = [L.dense_plan("aht", m, n, ks[j], [ldu, ld[2]], [0, adv(off[2], j * per * ld[2])]) for j in (0, 1)]
+        else:
+            plans = [L.dense_plan("wta", m, n, ks[j], [ldu, ld[1], ld[3]], [0, adv(off[1], j * per), adv(off[3], j * per * ld[3])],
+                                  ws_bytes=inner) for j in (0, 1)]
+    else:
+        raise ValueError("%s issues no panel calls" % op)
+    assert all(p["family"] not in ("none", "wide") for p in plans), (op, m, n, k, plans)
+    return wide, plans
+
+
+def wide_case_plans(case, ws_bytes=None, ld=None, off=None):
+    """(the wide plan, the tuned calls' plans) of a WIDE_REACH case -- at the pitches and addresses `dense_plan_args` derives for it, or
+    at those of the views a test is about to pass (ld, off)"""
+    from pydnmfk_amd import _lib as L
+    cid, op, m, n, k, aligned, bf16, _ = case
+    if ld is None:
+        ld, off = dense_plan_args(op, m, n, k, aligned, bf16)
+    if op in ("mu_update_w", "mu_update_h", "resid_sqnorm", "column_err"):            # the plain kernel alone
+        return L.dense_plan(op, max(m, 1), max(n, 1), k, ld, off, bf16a=bf16, ws_bytes=ws_bytes), []
+    return wide_panel_plans(op, m, n, k, ld, off, bf16, ws_bytes)
+
+
+def wide_assert_plans(case, wide, plans):
+    """a WIDE_REACH case reports the fields it is listed with"""
+    cid, op, want = case[0], case[1], case[-1]
+    assert wide["family"] == "wide" and wide["count"] == (4 if op.startswith("gram") else 2) and wide["per"] == 128, (cid, wide)
+    if "panel" in want:
+        assert {f: plans[-1][f] for f in ("family", "kt", "fast")} == want["panel"], (cid, plans[-1])
+    if "gram10" in want:                                            # (the Gram's blocks come first: (0, 0), (0, 1), (1, 0), (1, 1))
+        assert plans[2]["family"] == want["gram10"], (cid, plans[2])
+    got = {f: wide[f] for f in ("grid_x", "grid_y", "aux") if f in want}
+    assert got == {f: want[f] for f in got}, (cid, wide)
+    assert wide["block"] == (256 if got else 0), (cid, wide)
+
+
 def dense_nt_operands(m, n, k, seed=0):
     """A in 0..7, H and W in 1..3 (some zero rows of W, zero columns of H), G = H H^T: the operands of `products` without its H-phase
     denominators (W^T W) H, which outgrow 2^22 at the tall shapes of the descriptor loops.  A H^T is an integer below 2^24 and W G is 0
@@ -1690,18 +1858,20 @@ def dense_tn_operands(m, n, k, seed=0):
     return A, W
 
 
-def dense_resid_operands(m, n, k, seed=0, whole=True):
+def dense_resid_operands(m, n, k, seed=0, whole=True, sum_dtype=np.float32):
     """W and H in {0, 1}, A = W H + R with R in 0..2: W H <= k <= 128 and A <= 130 are integers (exact in bfloat16 too), every residual
     square is at most 4 and every fp32 partial sum of squares -- of a row chunk, a column, the whole block -- stays an integer below
-    2^24.  Every 32-row block of every 128-column block holds a nonzero residual.  Returns A, W, H and R (float64)."""
+    2^24.  Every 32-row block of every 128-column block holds a nonzero residual.  Returns A, W, H and R (float64).
+    sum_dtype: the type the kernel under test sums the squares in -- float64 for the plain kernels of csrc/dnmf_wide.hip, which square
+    float32 differences (integers up to 258: exact) in float64 and add them there, so their sums stay exact up to 2^53."""
     rs = np.random.RandomState(seed + 1019 * m + 23 * n + k)
     W = (rs.rand(m, k) < 0.5).astype(np.float32)
     H = (rs.rand(k, n) < 0.5).astype(np.float32)
     R = rs.randint(0, 3, size=(m, n)).astype(np.float64)
     A = W.astype(np.float64) @ H.astype(np.float64) + R
-    _bound((A ** 2).sum(0), 1.0, np.float32, "column sums of A^2")
+    _bound((A ** 2).sum(0), 1.0, sum_dtype, "column sums of A^2")
     if whole:                                                       # (the per-column error sums columns only)
-        _bound((R ** 2).sum(), 1.0, np.float32, "the residual sum")
+        _bound((R ** 2).sum(), 1.0, sum_dtype, "the residual sum")
     assert A.max() <= 256
     return A.astype(np.float32), W, H, R
 

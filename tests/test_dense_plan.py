@@ -326,5 +326,161 @@ def test_old_shapes_reach_and_design_table():
         assert line in design, "DESIGN.md lacks the reach-table line (python -m tests.test_dense_plan prints the table):\n" + line
 
 
+# ------------------------------------------------------------------------------------------ ranks 128 < k <= 256
+# WIDE_REACH (tests/_exact.py: the cases of tests/test_gpu_exact_wide.py).  At a wide rank dnmf_dense_plan answers family = wide and, for
+# the ops that launch a plain kernel of csrc/dnmf_wide.hip, that launch; the tuned calls are queried as the entry point issues them
+# (ex.wide_panel_plans).
+WIDE_PLANS = [(c, ex.wide_case_plans(c)) for c in ex.WIDE_REACH]
+
+
+@pytest.mark.parametrize("case", ex.WIDE_REACH, ids=lambda c: c[0])
+def test_wide_case_plan(case):
+    ex.wide_assert_plans(case, *ex.wide_case_plans(case))
+
+
+def test_wide_ids_are_unique_and_operands_stay_small():
+    ids = [c[0] for c in ex.WIDE_REACH]
+    assert len(ids) == len(set(ids))
+    for cid, op, m, n, k, aligned, bf16, _ in ex.WIDE_REACH:
+        assert 128 < k <= 256 and max(m, 1) * max(n, 1) * 4 < 64 << 20 and max(n, 1) * k * 4 < 64 << 20, cid
+        # W: below 64 MiB except at the one-range shape, which needs m > 131072 rows of more than 128 columns
+        assert max(m, 1) * k * 4 < 64 << 20 or (m, n) == ex.WIDE_TALL, cid
+
+
+def _second_panels():
+    return [(c, pl[-1]) for c, (w, pl) in WIDE_PLANS if pl]
+
+
+def test_wide_second_panels_cover_the_tuned_kernels():
+    """the union of the second-panel plans: nt16, nt at KT 1 / 2 / 4, tn16 and tn at KT 1 / 2 / 4, FAST and not at every KT, for every
+    op that issues panels -- and the classes the cases are named after, per op"""
+    sp = _second_panels()
+    got = {(p["family"], p["kt"]) for c, p in sp}
+    assert got == {("nt16", 1), ("nt", 1), ("nt", 2), ("nt", 4), ("tn16", 1), ("tn", 1), ("tn", 2), ("tn", 4)}, sorted(got)
+    for fam in ("nt", "tn"):
+        for kt in (1, 2, 4):
+            _both([p["fast"] for c, p in sp if (p["family"], p["kt"]) == (fam, kt)], "second panel %s FAST, KT %d" % (fam, kt))
+    for op in ("aht", "wta", "wta_gram", "gram_hht", "gram_wtw", "kl_uht", "kl_wtu"):
+        mine = [(c, p) for c, p in sp if c[1] == op]
+        r = {c[4] - 128 for c, p in mine}
+        assert {2, 3, 4, 16, 17, 32, 33, 65, 127} <= r, (op, sorted(r))
+        assert {c[4] % 4 for c, p in mine} == {0, 1, 2, 3}, op
+        assert {c[5] for c, p in mine} == {True, False}, op         # aligned views, and views at an odd base with pitch = width + 3
+        small = [(c, p) for c, p in mine if c[4] - 128 <= 16]
+        if op != "gram_wtw":                                        # (block (1, 1) of W^T W has n = r columns: never whole 64-column blocks)
+            _both([int(p["family"] in ("nt16", "tn16")) for c, p in small], "%s: a 16-wide second panel at r <= 16" % op)
+            assert {c[4] for c, p in small if p["family"] in ("nt16", "tn16")} == {132, 144}, op
+        assert all(p["kt"] == 1 for c, p in small), op
+        # r <= 16 off the 16-wide kernels through an unaligned view, through n % 32 != 0, and at k = 130, 131
+        off16 = {(c[4], c[5], c[3] % 32 == 0) for c, p in small if p["family"] in ("nt", "tn")}
+        assert {k for k, al, whole in off16} >= {130, 131}, op
+        if op not in ("gram_wtw", "kl_wtu"):                         # (kl_wtu: U is aligned whatever the views are)
+            assert [1 for k, al, whole in off16 if not al and whole and k % 4 == 0], op
+        if op != "gram_wtw":
+            assert [1 for k, al, whole in off16 if al and not whole and k % 4 == 0], op
+    for op in ("aht", "wta", "wta_gram"):
+        b = {p["family"] for c, p in sp if c[1] == op and c[6]}
+        assert b == ({"nt16", "nt"} if op == "aht" else {"tn16", "tn"}), (op, b)
+    # the r x 128 block of W^T W on the 16-wide kernel, and off it
+    g10 = {(c[1], pl[2]["family"]) for c, (w, pl) in WIDE_PLANS if c[1] in ("gram_wtw", "wta_gram")}
+    assert g10 == {(op, f) for op in ("gram_wtw", "wta_gram") for f in ("tn16", "tn")}
+
+
+def test_wide_plain_kernel_classes():
+    """wide_nn_rows_kernel: both sides of "more than 4 tiles per range" and of "one range", ragged last ranges and tiles, n < 16, n = 1,
+    m % 16 != 0, a last workgroup with one live wave; W_UPD_W at k % 16 != 0 and at k = 256; wide_upd_h_kernel with ragged last row and
+    column tiles and a partly filled last workgroup"""
+    rows = [(c, w) for c, (w, pl) in WIDE_PLANS if c[1] in ex.WIDE_ROWS_OPS]
+    for op in ("kl_uht", "resid_sqnorm", "column_err"):             # (kl_wtu launches the same W_QUOT kernel)
+        mine = [(c, w) for c, w in rows if c[1] == op]
+        _both([int(w["aux"] > 4) for c, w in mine], "%s: more than 4 tiles per range" % op)
+        _both([int(w["grid_y"] == 1) for c, w in mine], "%s: one range" % op)
+        big = [(c, w) for c, w in mine if w["aux"] > 4]
+        # several ranges of more than 4 tiles, the last range shorter, its last tile ragged
+        assert [1 for c, w in big if w["grid_y"] > 1 and 0 < c[3] - (w["grid_y"] - 1) * 16 * w["aux"] < 16 * w["aux"] and c[3] % 16], op
+        # the one range of want = 1: more than 8192 strips, n above the 64-column minimum, a ragged last tile, one live wave at the end
+        assert [1 for c, w in big if w["grid_y"] == 1 and -(-c[2] // 16) > 8192 and c[3] > 64 and c[3] % 16 and -(-c[2] // 16) % 4 == 1], op
+        assert {1, 9} <= {c[3] for c, w in mine}, op
+        assert [1 for c, w in mine if c[2] % 16] and [1 for c, w in mine if -(-c[2] // 16) % 4 == 1], op
+        assert {c[4] % 4 for c, w in mine} >= {2, 3} or op == "kl_uht", op
+    assert {c[4] % 4 for c, w in rows if c[1].startswith("kl")} == {0, 1, 2, 3}
+    for c, w in rows:
+        m, n = c[2], c[3]
+        assert w["grid_x"] == -(-(-(-m // 16)) // 4) and (w["grid_y"] - 1) * 16 * w["aux"] < n <= w["grid_y"] * 16 * w["aux"], c[0]
+    upw = [(c, w) for c, (w, pl) in WIDE_PLANS if c[1] == "mu_update_w"]
+    assert {c[4] for c, w in upw} >= {130, 131, 255, 256} and all(w["grid_y"] == 1 and w["aux"] == -(-c[4] // 16) for c, w in upw)
+    assert {c[5] for c, w in upw} == {True, False} and [1 for c, w in upw if c[2] % 16] and [1 for c, w in upw if -(-c[2] // 16) % 4 == 1]
+    uph = [(c, w) for c, (w, pl) in WIDE_PLANS if c[1] == "mu_update_h"]
+    assert [1 for c, w in uph if c[4] % 16 and c[3] % 16 and -(-c[3] // 16) % 4] and [1 for c, w in uph if c[4] == 256 and c[3] % 64 == 0]
+    assert {1, 9} <= {c[3] for c, w in uph} and {c[5] for c, w in uph} == {True, False} and {c[4] % 4 for c, w in uph} >= {1, 2, 3, 0}
+    assert all(w["grid_x"] == -(-(-(-c[3] // 16)) // 4) and w["aux"] == -(-c[4] // 16) for c, w in uph)
+
+
+def _old_wide_cases():
+    """the calls tests/test_gpu_exact.py makes at a wide rank: PRIM (test_products, test_mu_updates, test_kl, SUB: the residual sums) and
+    FRO (the two-pass step: gram_hht, aht, mu_update_w, wta_gram, mu_update_h)"""
+    from tests import test_gpu_exact as old
+    out = []
+    for prm in old.PRIM + old.FRO:
+        m, n, k, aligned = prm.values
+        if k <= 128:
+            continue
+        ops = ["aht", "wta_gram", "gram_hht", "mu_update_w", "mu_update_h"]
+        if prm in old.PRIM:
+            ops += ["wta", "gram_wtw", "kl_uht", "kl_wtu"] + (["resid_sqnorm", "column_err"] if prm in old.SUB else [])
+        out += [("%s-%s" % (op, prm.id), op, m if op != "gram_hht" else 0, n if op != "gram_wtw" else 0, k, aligned, False, None) for op in ops]
+    return out
+
+
+def _wide_classes(plans):
+    d = {}
+
+    def add(name, v):
+        d.setdefault(name, set()).add(v)
+    for c, (w, pl) in plans:
+        op, m, n, k = c[1:5]
+        if pl:
+            p = pl[-1]
+            add("second panel of %s: (family, KT)" % op, (p["family"], p["kt"]))
+            add("second panel: r = k - 128", k - 128)
+        if op in ("gram_wtw", "wta_gram"):
+            add("r x 128 block of W^T W: family", pl[2]["family"])
+        add("k % 4", k % 4)
+        if op in ex.WIDE_ROWS_OPS:
+            add("wide_nn_rows_kernel: (ranges, tiles of a full range)", (w["grid_y"], w["aux"]))
+            add("wide_nn_rows_kernel: n", n)
+        if op == "mu_update_w":
+            add("wide_nn_rows_kernel<W_UPD_W>: (k % 16, m % 16)", (k % 16, m % 16))
+        if op == "mu_update_h":
+            add("wide_upd_h_kernel: (k % 16, n % 16, waves of the last workgroup)", (k % 16, n % 16, (-(-n // 16) - 1) % 4 + 1))
+    return {k: sorted(v) for k, v in d.items()}
+
+
+def wide_reach_table():
+    """the table of DESIGN.md: class | what PRIM / FRO reach at a wide rank | what WIDE_REACH reaches"""
+    old = _wide_classes([(c, ex.wide_case_plans(c)) for c in _old_wide_cases()])
+    new = _wide_classes(WIDE_PLANS)
+    fmt = lambda v: ", ".join(str(x).replace("'", "") for x in v) if v else "--"
+    return ["| %s | %s | %s |" % (name, fmt(old.get(name, [])), fmt(new[name])) for name in sorted(new)]
+
+
+def test_old_wide_shapes_do_not_reach_the_new_classes():
+    old = [(c, ex.wide_case_plans(c)) for c in _old_wide_cases()]
+    assert {c[4] for c, _ in old} == {129, 192, 256}
+    sp = [(c, pl[-1]) for c, (w, pl) in old if pl]
+    assert not [c for c, p in sp if p["family"] in ("nt16", "tn16")], "an older shape has a 16-wide second panel after all"
+    assert {c[4] - 128 for c, p in sp} == {1, 64, 128} and {c[4] % 4 for c, _ in old} == {0, 1}
+    assert {(p["family"], p["kt"]) for c, p in sp if c[4] - 128 <= 16} == {("nt", 1), ("tn", 1)}
+    rows = [(c, w) for c, (w, pl) in old if c[1] in ex.WIDE_ROWS_OPS]
+    assert rows and all(w["aux"] == 4 and w["grid_y"] > 1 and c[3] >= 16 for c, w in rows), "an older shape has a long or a single range"
+    assert all(c[4] % 16 in (0, 1) for c, _ in old if c[1] == "mu_update_w")
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "DESIGN.md")) as f:
+        design = f.read()
+    for line in wide_reach_table():
+        assert line in design, "DESIGN.md lacks the wide reach-table line (python -m tests.test_dense_plan prints the table):\n" + line
+
+
 if __name__ == "__main__":
     print("\n".join(reach_table()))
+    print()
+    print("\n".join(wide_reach_table()))

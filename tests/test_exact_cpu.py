@@ -1080,3 +1080,121 @@ def test_dense_resid_operands_are_exact_and_see_every_block(case):
     padr, padc = -m % 32, -n % 128
     blocks = np.pad(R, ((0, padr), (0, padc))).reshape((m + padr) // 32, 32, (n + padc) // 128, 128).max(axis=(1, 3))
     assert (blocks > 0).all(), "%s: a 32-row block of a 128-column block without a residual" % cid
+
+
+# ---------------------------------------------------------------------------------------------------------- ranks 128 < k <= 256
+# The operands of tests/test_gpu_exact_wide.py at the shapes of ex.WIDE_REACH: exact in fp32 forward and reversed, and every unit of work
+# a loop iteration of the wide path owns -- a 16 x 16 tile of a row strip of wide_nn_rows_kernel, a 16-row tile of k of wide_upd_h_kernel, a
+# panel of the composition -- adds a nonzero term to its output (all terms are non-negative), so dropping or doubling it changes the
+# float64 answer there.
+def _both_ways(X, Y, what):
+    """X @ Y exact in float32 from the front and from the back: term by term where that is affordable, else BLAS on the operands and on
+    the operands with the contraction index reversed"""
+    if X.shape[0] * X.shape[1] * Y.shape[1] <= 5e7:
+        return _all_orders(X, Y, what)
+    ref = X.astype(np.float64) @ Y.astype(np.float64)
+    X32, Y32 = X.astype(np.float32), Y.astype(np.float32)
+    for got, how in ((X32 @ Y32, "BLAS"), (np.ascontiguousarray(X32[:, ::-1]) @ np.ascontiguousarray(Y32[::-1]), "BLAS, reversed")):
+        assert np.array_equal(got.astype(np.float64), ref), "%s (%s) is not exact in float32" % (what, how)
+    return ref
+
+
+def _tiles16(X):
+    """per 16 x 16 tile of X (ragged edge tiles included): does it hold a nonzero?"""
+    r, c = X.shape
+    P = np.pad(np.abs(X), ((0, -r % 16), (0, -c % 16)))
+    return P.reshape(P.shape[0] // 16, 16, P.shape[1] // 16, 16).max(axis=(1, 3)) > 0
+
+
+def _panels(ref, axis, per=128):
+    """the blocks a wide entry point writes, one per panel call, along `axis` (2: both -- the four blocks of a Gram)"""
+    cut = lambda X, ax: [X[:per], X[per:]] if ax == 0 else [X[:, :per], X[:, per:]]
+    return [b for half in cut(ref, 0) for b in cut(half, 1)] if axis == 2 else cut(ref, axis)
+
+
+@pytest.mark.parametrize("case", [c for c in ex.WIDE_REACH if c[1] in ("aht", "wta", "wta_gram", "gram_hht", "gram_wtw")], ids=lambda c: c[0])
+def test_wide_product_operands_are_exact_and_every_panel_counts(case):
+    cid, op, m, n, k, aligned, bf16, _ = case
+    if op == "aht":
+        A, W, H, G = ex.dense_nt_operands(m, n, k)
+        blocks = _panels(_both_ways(A, H.T, "A H^T"), 1)
+        assert ex.is_bf16(A).all()
+    elif op == "gram_hht":
+        H = np.ascontiguousarray(ex.dense_tn_operands(n, 1, k)[1].T)
+        blocks = _panels(_both_ways(H, H.T, "H H^T"), 2)
+    else:
+        A, W = ex.dense_tn_operands(m, max(n, 1), k)
+        assert ex.is_bf16(A).all()
+        blocks = _panels(_both_ways(W.T, A, "W^T A"), 0) if op != "gram_wtw" else []
+        if op != "wta":
+            blocks += _panels(_both_ways(W.T, W, "W^T W"), 2)
+    assert len(blocks) == {"aht": 2, "wta": 2, "wta_gram": 6, "gram_hht": 4, "gram_wtw": 4}[op]
+    for b in blocks:
+        assert b.size and _tiles16(b).all(), "%s: a panel's block with an all-zero 16 x 16 tile" % cid
+
+
+@pytest.mark.parametrize("case", [c for c in ex.WIDE_REACH if c[1] in ("kl_uht", "kl_wtu")], ids=lambda c: c[0])
+def test_wide_kl_operands_are_exact_and_every_tile_counts(case):
+    cid, op, m, n, k, aligned, bf16, _ = case
+    A, W, H, U = ex.kl(m, n, k)
+    U32 = (A / (W @ H + np.float32(np.finfo(np.float32).eps))).astype(np.float32)
+    assert np.array_equal(U32.astype(np.float64), U), "the quotient is not exact in float32"
+    _both_ways(W, H, "W H")
+    # a tile of the quotient image that wide_nn_rows_kernel<W_QUOT> leaves out: H > 0 and every row of W has one nonzero, so a nonzero
+    # U[r][c] is a term of row r of U H^T and of column c of W^T U
+    assert _tiles16(U).all(), "%s: a 16 x 16 tile of U without a nonzero" % cid
+    assert (H > 0).all() and ((W > 0).sum(1) == 1).all()
+    ref = _both_ways(U32, H.T, "U H^T") if op == "kl_uht" else _both_ways(W.T, U32, "W^T U")
+    for b in _panels(ref, 1 if op == "kl_uht" else 0):
+        assert b.any(), "%s: a panel that adds nothing" % cid
+
+
+@pytest.mark.parametrize("case", [c for c in ex.WIDE_REACH if c[1] in ("resid_sqnorm", "column_err")], ids=lambda c: c[0])
+def test_wide_resid_operands_are_exact_and_every_tile_counts(case):
+    cid, op, m, n, k, aligned, bf16, _ = case
+    A, W, H, R = ex.dense_resid_operands(m, n, k, whole=op == "resid_sqnorm", sum_dtype=np.float64)
+    WH = _both_ways(W, H, "W H")
+    d = A - (W @ H)                                                                    # float32, as the kernel forms it
+    assert np.array_equal(d.astype(np.float64), R) and np.array_equal(A.astype(np.float64) - WH, R)
+    assert float((R ** 2).sum()) < 2.0 ** 53 and float((A.astype(np.float64) ** 2).sum()) < 2.0 ** 53
+    assert _tiles16(R).all(), "%s: a 16 x 16 tile without a residual" % cid
+    if op == "column_err":                                                             # every column of every strip's tile: num and den
+        P = np.pad(R, ((0, -m % 16), (0, 0))).reshape(-1, 16, n)
+        assert (np.abs(P).max(1) > 0).mean() > 0.99 and _tiles16(A).all()
+
+
+@pytest.mark.parametrize("case", [c for c in ex.WIDE_REACH if c[1] in ("mu_update_w", "mu_update_h")], ids=lambda c: c[0])
+def test_wide_update_operands_are_exact_and_every_tile_counts(case):
+    """X G exact and absorbing eps; the update moves an element by more than the c = 3 of the comparison in every 16 x 16 tile of W (a
+    trip of the column loop of wide_nn_rows_kernel<W_UPD_W>) and of H (a 16-row tile of k of a wave's 16 columns in wide_upd_h_kernel)"""
+    cid, op, m, n, k, aligned, bf16, _ = case
+    rows = m if op == "mu_update_w" else n
+    X, S, G = ex.dense_update_operands(rows, k)
+    X64 = X.astype(np.float64)
+    d = _both_ways(X, G, "X G")
+    d32 = d.astype(np.float32)
+    eps = np.float32(np.finfo(np.float32).eps)
+    assert np.array_equal(d32[d32 > 0] + eps, d32[d32 > 0]), "X G + eps is not absorbed"
+    q = np.where(d > 0, X64 * S / np.where(d > 0, d, 1.0), 0.0)
+    far = np.abs(q - X64) > 4 * np.spacing(np.maximum(np.abs(q), np.abs(X64)).astype(np.float32))
+    assert _tiles16(far if op == "mu_update_w" else far.T).all(), "%s: a 16 x 16 tile the update leaves as it was" % cid
+
+
+@pytest.mark.parametrize("k", ex.WIDE_FIT_KS)
+def test_wide_fit_operands_are_fixed_points(k):
+    """`fro_fixed`, `kl_fixed` and `kl_moved` accept the wide ranks at the shape of the whole-fit cases, and one step of the float32 model
+    (any order of the sums) returns its input"""
+    m, n = ex.WIDE_FIT_SHAPE
+    for seed in (0, 1):
+        for order in ("forward", "reversed"):
+            A, W, H = ex.fro_fixed(m, n, k, seed=seed)
+            W1, H1 = _fro_step32(A, W, H, order, True)
+            assert np.array_equal(_bits(W1), _bits(W)) and np.array_equal(_bits(H1), _bits(H))
+            A, W, H = ex.kl_fixed(m, n, k, seed=seed)
+            W1, H1 = _kl_step32(A, W, H, order, True, True)
+            assert np.array_equal(_bits(W1), _bits(W)) and np.array_equal(_bits(H1), _bits(H))
+            A, W, H = ex.kl_moved(m, n, k, seed=seed)
+            W1, H1 = _kl_step32(A, W, H, order, False, True)
+            assert np.array_equal(_bits(W1), _bits(W)) and np.array_equal(_bits(H1), _bits(2 * H))
+            W2, H2 = _kl_step32(A, W1, H1, order, False, False)
+            assert np.array_equal(_bits(H2), _bits(H1))

@@ -36,7 +36,8 @@ def test_wide_rank_primitives_match_float64(m, n, k):
     G2 = torch.full((KP, KP), 3.0, device=dev)
     AtW = torch.empty(k, n, device=dev)
     ops.wta_gram(A, W, AtW, G2)
-    assert rel(G2[:k, :k], Wd.t() @ Wd) < tol and (k == KP or float(G2[k:].abs().max()) == 0.0) and rel(AtW, Wd.t() @ Ad) < tol
+    assert rel(G2[:k, :k], Wd.t() @ Wd) < tol and rel(AtW, Wd.t() @ Ad) < tol
+    assert k == KP or (float(G2[k:].abs().max()) == 0.0 and float(G2[:, k:].abs().max()) == 0.0), "the zero padding of the wta_gram Gram"
     # updates (dist_nmf.py:731-732, :750-751) with exact inputs
     AH = (Ad @ Hd.t()).float()
     Gd = G.double()[:k, :k]
