@@ -75,6 +75,8 @@ def _pad64(x):
 class _Base:
     def _dispatch(self, clamp):
         norm, method = self.norm.upper(), self.method.upper()
+        if self._weights() is not None:                                        # (no counterpart in the reference: csrc/dnmf_weighted.h)
+            return self.WEIGHTED_MU_update(self.W_update, clamp)
         if _is_masked(self.A_ij) and method in ('HALS', 'BCD'):
             raise NotImplementedError("missing='%s' is provided for method 'mu' (fro / kl) only, not for '%s': HALS and BCD "
                                       "contract with Gram matrices, which count every position" % (self.A_ij.missing, self.method))
@@ -165,6 +167,44 @@ class _Base:
 
     def BETA_MU_update(self, W_update=True, clamp=False):
         self._div_MU_update("beta", W_update, clamp)
+
+    # ---- per-entry weights V >= 0 of A's shape, sharded like A (`params.weights_block`: this rank's block on the device): the pair of
+    # the norm with both halves scaled by V and selected to 0 where v = 0, num = (V . u_n) F, den = (V . u_d) F, then the norm's own rule
+    # (csrc/dnmf_weighted.h).  The stored pair crosses the ranks like any other pair; the weights are inside it.
+    def _weights(self):
+        return getattr(self.params, "weights_block", None)
+
+    def WEIGHTED_MU_update(self, W_update=True, clamp=False):
+        ops, A, V = self.ops, self.A_ij, self._weights()
+        norm, method = str(self.norm).lower(), str(self.method).lower()
+        if method != "mu":
+            raise NotImplementedError("weights are provided for method 'mu' only, not for '%s': HALS and BCD contract with Gram matrices, "
+                                      "which weigh every position alike" % self.method)
+        if self.p_r != 1 and self.p_c != 1:
+            raise NotImplementedError("weights on a 2D grid (p_r = %d, p_c = %d) are not provided: use a 1D grid" % (self.p_r, self.p_c))
+        if _is_sparse(A) or _is_masked(A):
+            raise NotImplementedError("weights are provided for dense data without params.missing, not for %s"
+                                      % ("sparse data" if _is_sparse(A) else "missing='%s' (give weight 0 instead)" % A.missing))
+        if norm not in ("fro", "kl", "is", "beta"):
+            raise NotImplementedError("weights are provided for the norms fro / kl / is / beta, not for '%s'" % self.norm)
+        if not hasattr(ops, "weighted_update_w") or A.dtype not in getattr(ops, "weighted_dtypes", ()):
+            raise NotImplementedError("weights run on float32 data with the product's fp32 operator set; not provided for %s data with "
+                                      "the '%s' operator set" % (str(A.dtype).replace("torch.", ""), getattr(ops, "name", "?")))
+        if self.k > 128:
+            raise NotImplementedError("weights with k = %d are not provided: the weighted kernels serve 1 <= k <= 128" % self.k)
+        if tuple(V.shape) != tuple(A.shape):
+            raise ValueError("weights: this rank's block is %s, its weights are %s" % (tuple(A.shape), tuple(V.shape)))
+        beta = 0.0
+        if norm == "beta":
+            if getattr(self.params, "beta", None) is None:
+                raise ValueError("norm='beta' needs params.beta (a float in -2 <= beta <= 4)")
+            beta = float(self.params.beta)
+
+        def op(name):      # ops.weighted_<name>(A, V, W, H, eps, norm, beta, ...)
+            fn = getattr(ops, "weighted_" + name)
+            return lambda A_, W, H, eps, *a: fn(A_, V, W, H, eps, norm, beta, *a)
+        self._pair_MU_update("wnd", op("update_w"), op("update_h"), op("aht_pair"), op("wta_pair"),
+                             lambda X, num, den, eps, *a: ops.weighted_ratio_update(X, num, den, eps, norm, beta, *a), W_update, clamp)
 
     # ---- BCD / Frobenius (dist_nmf.py:940-1047 in 1D, :474-579 in 2D).  The grid-specific pieces are the `_bcd_*` hooks of each
     # class: the exchanges sit exactly where the reference allreduces / gathers.  Every scalar of the method stays in the device state
@@ -262,8 +302,8 @@ class nmf_algorithms_1D(_Base):
         the RCCL communicator inside libdnmf_hip.so) -- same kernels in the same order as the choreography below, no Python
         between the launches.  float32 data, the product's own operator set, more than one rank."""
         hals = self.method.upper() == 'HALS' and self.norm.upper() == 'FRO'
-        if _is_sparse(self.A_ij) or _is_masked_dense(self.A_ij):
-            return False            # (sparse data, NaN-marked dense data: the host sequences the primitives)
+        if _is_sparse(self.A_ij) or _is_masked_dense(self.A_ij) or self._weights() is not None:
+            return False            # (sparse data, NaN-marked dense data, weighted data: the host sequences the primitives)
         if (self.p == 1 and not getattr(self.params, "native_always", False)) or self.k > 128 or \
                 not (hals or (self.method.upper() == 'MU' and self.norm.upper() in ('FRO', 'KL'))):
             return False            # (k > 128: the library-sequenced steps stop at the tuned kernels' rank; the choreography below does not)
@@ -553,6 +593,8 @@ class nmf_algorithms_2D(_Base):
         keep the choreography."""
         if getattr(self.params, "exchange", None) not in ("native", "native-hosted") or getattr(self.ops, "name", "") != "hip" or self.k > 128:
             return False
+        if self._weights() is not None:
+            return False            # (weights: the choreography refuses the 2D grid by name)
         hals = self.method.upper() == 'HALS' and self.norm.upper() == 'FRO'
         if not (hals or (self.method.upper() == 'MU' and self.norm.upper() in ('FRO', 'KL'))):
             return False

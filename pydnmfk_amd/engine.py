@@ -876,6 +876,87 @@ class HipOps:
         the device tensor [1][2] of {sum (A - W H)^2, sum A^2}."""
         return self._fam_fit("beta", self._beta_mode(beta), A, W, H, eps, w_update, itr)
 
+    # ---- per-entry weights V >= 0 of A's shape under the four pair rules (csrc/dnmf_weighted.h, dnmf_weighted_*): dense float32 data,
+    # 1 <= k <= 128.  num = (V . u_n) F, den = (V . u_d) F with the norm's own pair and rule; v = 0 is "not observed" (A is not looked at
+    # there).  `V` follows `A`; `norm` ('fro' / 'kl' / 'is' / 'beta') and `beta` (read under 'beta' alone) follow `eps`
+    weighted_dtypes = (torch.float32,)  # the data types these operations take (PyNMF and the choreography refuse any other by name)
+    WEIGHTED_NORMS = ("fro", "kl", "is", "beta")
+
+    _weighted_ranks = "weights with k = %d: the weighted kernels serve 1 <= k <= 128"
+
+    @classmethod
+    def _weighted_mode(cls, norm, beta):
+        norm = str(norm).lower()
+        if norm not in cls.WEIGHTED_NORMS:
+            raise ValueError("weights: norm %r (fro / kl / is / beta)" % (norm,))
+        return (cls.WEIGHTED_NORMS.index(norm), cls._beta_mode(beta)[0] if norm == "beta" else 0.0)
+
+    def _weighted(self, what, A, V, W, H, eps, norm, beta, pair=None, ws=None):
+        """the arguments of a dnmf_weighted_* entry point: those of the norm's own family with (V, ldv) after lda"""
+        _req(V, "weights")
+        if tuple(V.shape) != tuple(A.shape):
+            raise ValueError("%s: weights %s must have the shape of A %s" % (what, tuple(V.shape), tuple(A.shape)))
+        head, tail = self._pair_args(what, A, W, H, eps, ws or lib.dnmf_weighted_ws_bytes, self._weighted_ranks, self._weighted_mode(norm, beta), pair=pair)
+        return head[:4] + (V.data_ptr(), _ld(V)) + head[4:], tail
+
+    def weighted_aht_pair(self, A, V, W, H, eps, norm, beta, buf):
+        """buf = [num | den], each m x k: (V . u_n) H^T and (V . u_d) H^T"""
+        return self.weighted_pair_into("w", A, V, W, H, eps, norm, beta, *self._halves(buf, tuple(W.shape)))
+
+    def weighted_wta_pair(self, A, V, W, H, eps, norm, beta, buf):
+        """buf = [num | den], each k x n: W^T (V . u_n) and W^T (V . u_d)"""
+        return self.weighted_pair_into("h", A, V, W, H, eps, norm, beta, *self._halves(buf, tuple(H.shape)))
+
+    def weighted_pair_into(self, side, A, V, W, H, eps, norm, beta, num, den):
+        """the same pair into two views of the caller's (one leading dimension, any pitch): side 'w' (m x k) or 'h' (k x n)"""
+        head, tail = self._weighted("weighted pair", A, V, W, H, eps, norm, beta, pair=(side, num, den))
+        check((lib.dnmf_weighted_aht_pair if side == "w" else lib.dnmf_weighted_wta_pair)(*head, *tail))
+        return num, den
+
+    def weighted_update_w(self, A, V, W, H, eps, norm, beta):
+        """W <- W * rule(num / (den + eps)): the pass, then the norm's rule on its partial sums"""
+        head, tail = self._weighted("weighted_update_w", A, V, W, H, eps, norm, beta)
+        check(lib.dnmf_weighted_update_w(*head, *tail))
+        return W
+
+    def weighted_update_h(self, A, V, W, H, eps, norm, beta, clamp=False):
+        """H <- H * rule(num / (den + eps)), max(., eps) with `clamp`"""
+        head, tail = self._weighted("weighted_update_h", A, V, W, H, eps, norm, beta)
+        check(lib.dnmf_weighted_update_h(*head, int(bool(clamp)), *tail))
+        return H
+
+    def weighted_ratio_update(self, X, num, den, eps, norm, beta, clamp=False):
+        """the norm's rule on a pair that was summed over the ranks: the unweighted rule (pair_ratio_kernel), the weights are in the pair"""
+        norm = self.WEIGHTED_NORMS[self._weighted_mode(norm, beta)[0]]
+        if norm == "is":
+            return self.is_ratio_update(X, num, den, eps, clamp)
+        if norm == "beta":
+            return self.beta_ratio_update(X, num, den, eps, beta, clamp)
+        check(lib.dnmf_csr_ratio_update(*self._ratio_args("weighted_ratio_update", X, num, den, eps, clamp)))
+        return X
+
+    def weighted_resid_sqnorm(self, A, V, W, H):
+        """{sum v (A - W H)^2, sum v A^2} over v > 0: two device doubles (stored, not accumulated: two calls are bit-identical)"""
+        head, tail = self._weighted("weighted_resid_sqnorm", A, V, W, H, 0.0, "fro", 0.0)
+        out = torch.empty(2, dtype=torch.float64, device=A.device)
+        check(lib.dnmf_weighted_resid_sqnorm(*head[:11], out.data_ptr(), *tail))
+        return out
+
+    def weighted_divergence(self, A, V, W, H, eps, norm, beta):
+        """sum v d(A | W H + eps) over v > 0 with d of the norm (fro: half of sum v (A - W H)^2): one device double"""
+        head, tail = self._weighted("weighted_divergence", A, V, W, H, eps, norm, beta)
+        out = torch.empty(1, dtype=torch.float64, device=A.device)
+        check(lib.dnmf_weighted_divergence(*head, out.data_ptr(), *tail))
+        return out
+
+    def weighted_fit(self, A, V, W, H, eps, norm, beta, w_update, itr):
+        """`itr` weighted MU steps (clamps after the steps i % 10 == 0), normalize_features and the weighted error pair in ONE library
+        call (dnmf_weighted_mu_fit).  One problem; W, H are updated in place; returns the device tensor [1][2] of weighted_resid_sqnorm."""
+        head, tail = self._weighted("weighted_fit", A, V, W, H, eps, norm, beta, ws=lib.dnmf_weighted_ws_bytes_fit)
+        sq = torch.empty(1, 2, dtype=torch.float64, device=A.device)
+        check(lib.dnmf_weighted_mu_fit(*head, int(bool(w_update)), int(itr), sq.data_ptr(), *tail))
+        return sq
+
     def _bcd_fit(self, A3, W3, H3, eps, w_update, itr, sfx, batched):
         """method 'bcd' (dnmf_bcd_fro_fit): float32 data; a stack of B problems is ONE library call in which every launch
         covers all of them.  Each problem keeps its own state block in its workspace slice, so the problems accept or restart
@@ -922,6 +1003,7 @@ class HipOpsBf16x6(HipOps):
     is_nmfk = False                # (nor an NMFk sweep under norm='is')
     beta_dtypes = ()               # (nor of the beta-divergence pairs)
     beta_nmfk = False              # (nor an NMFk sweep under norm='beta')
+    weighted_dtypes = ()           # (nor of the weighted pairs)
     kl_uht_hblocks = None          # (no block-column variant of the split kernels: the 2D step concatenates H for them)
     aht_hblocks = None
 

@@ -30,6 +30,11 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
     (the same bits), beta = 1 and 2 are the KL and Frobenius objectives under this family's rule, not the reference's; one library call
     per fit on one rank (dnmf_beta_mu_fit); `beta_divergence()` reports the objective and `beta_column_divergence()` each column's
     divergence over its sum of a^beta (scale-invariant for every beta: the per-column statistic of PyNMFk under this norm);
+  * `params.weights = V`: per-entry weights, a non-negative float32 array of the block's shape -- the objective is sum v d(a | W H) with d
+    of the norm (fro / kl / is / beta), the rule the norm's own with both halves of its pair scaled by V (csrc/dnmf_weighted.h; method
+    'mu', 1D grids, k <= 128, prune=False).  v = 0 means NOT OBSERVED: the data may hold anything there (NaN included), so
+    weights = ~isnan(A) is masked IS / beta.  `fit()` returns the weighted relative error sqrt(sum v (a - s)^2 / sum v a^2);
+    `weighted_divergence()` reports the objective; one library call per fit on one rank (dnmf_weighted_mu_fit);
   * `prune=True` (the reference's default when the attribute is absent) drops all-zero rows / columns before the
     iterations and scatters the factors back afterwards.  numpy callers get float64 factors back in that case, exactly
     as from the reference (its unprune scatters into np.zeros, utils.py:195,198); tensor callers keep float32 on the GPU.
@@ -138,8 +143,16 @@ class PyNMF:
             self.norm = self.params.norm = 'is'
         self._is = (self.norm == 'is')
         self._beta = (self.norm == 'beta')
+        self._weighted = getattr(self.params, "weights", None) is not None
+        self.V_ij = None
+        if hasattr(self.params, "weights_block"):                   # (the bag may have served a weighted fit before)
+            del self.params.weights_block
+        if self._weighted:
+            self._weighted_refusals(self.norm, self.params, self._sparse, missing, self.a_dtype, self.ops, self.method, self.p_r, self.p_c)
         if self._is or self._beta:
             self._div_checks(missing)
+        if self._weighted:
+            self.V_ij = self.params.weights_block = self._weights_block()
         if self.a_dtype == torch.bfloat16 and str(self.norm).lower() == 'kl':
             raise TypeError("PyNMF: bfloat16 storage of A is provided for the Frobenius updates (mu / hals) only")
         self.prune = var_init(self.params, 'prune', default=True)
@@ -243,6 +256,8 @@ class PyNMF:
         method 'mu', 1D grids, k <= 128), and what the data must be: strictly positive under 'is' and for beta <= 0, non-negative for
         beta > 0.  The ranks agree on that verdict through comm1 BEFORE any of them raises, so none is left alone in a later collective."""
         self._div_refusals(self.norm, self.params, self._sparse, missing, self.a_dtype, self.ops, self.method, self.p_r, self.p_c, self.params.k)
+        if self._weighted:
+            return                                                  # (the sign condition is tested where v > 0 only: _weights_block)
         self._sign_check(self.beta if self._beta else None, float(self.A_ij.min()) if self.A_ij.numel() else 1.0, self.comm1,
                          self.p_r * self.p_c)
 
@@ -272,6 +287,66 @@ class PyNMF:
                                       % (norm, p_r, p_c))
         if k > 128:
             raise NotImplementedError("norm='%s' with k = %d is not provided: the %s kernels serve 1 <= k <= 128" % (norm, k, kernels))
+
+    @staticmethod
+    def _weighted_refusals(norm, params, sparse, missing, a_dtype, ops, method, p_r, p_c):
+        """What is refused under `params.weights`, each by name (dense float32 data without params.missing, fp32 arithmetic, method 'mu',
+        norms fro / kl / is / beta, 1D grids, k <= 128, init='rand' or factors, prune=False); needs no look at the data"""
+        if missing is not None:
+            raise NotImplementedError("weights together with missing='%s' are not provided: give the missing entries the weight 0 instead "
+                                      "(a weight of 0 IS 'not observed', under every norm)" % missing)
+        if sparse:
+            raise NotImplementedError("weights are not provided for sparse data (dense float32 data only)")
+        # (an operator set names the data types its weighted operations take, `weighted_dtypes`: the HIP kernels are float32)
+        if a_dtype not in (getattr(ops, "weighted_dtypes", ()) if ops is not None else (torch.float32,)):
+            raise NotImplementedError("weights with %s data are not provided (float32 data only); cast the block to float32"
+                                      % str(a_dtype).replace("torch.", ""))
+        if (getattr(params, "gemm", None) or "fp32") != "fp32":
+            raise NotImplementedError("weights with --gemm %s are not provided (fp32 arithmetic only)" % params.gemm)
+        if str(method).lower() != "mu":
+            raise NotImplementedError("weights are provided for method 'mu' only, not for '%s': HALS and BCD contract with Gram matrices, "
+                                      "which weigh every position alike" % method)
+        if str(norm).lower() not in ("fro", "kl", "is", "beta"):
+            raise NotImplementedError("weights are provided for the norms fro / kl / is / beta, not for '%s'" % norm)
+        if p_r != 1 and p_c != 1:
+            raise NotImplementedError("weights on a 2D grid (%d x %d) are not provided: use a 1D grid (p_r = 1 or p_c = 1)" % (p_r, p_c))
+        if getattr(params, "prune", True):
+            raise NotImplementedError("weights with prune=True are not provided (pruning drops all-ZERO rows and columns of the data; under "
+                                      "weights a row keeps its place whatever it holds): set params.prune = False")
+        if getattr(params, "init", None) == "nnsvd":
+            raise NotImplementedError("weights with init='nnsvd' are not provided (the SVD would weigh every entry alike, and read what "
+                                      "lies under a zero weight): init='rand' or factors=...")
+        if params.k > 128:
+            raise NotImplementedError("weights with k = %d are not provided: the weighted kernels serve 1 <= k <= 128" % params.k)
+
+    def _weights_block(self):
+        """`params.weights` as this rank's float32 block on the device, after the data checks: finite, >= 0, at least one positive, the
+        block's shape, and the norm's sign condition on A where v > 0 only.  The ranks agree on the verdict through comm1 BEFORE any of
+        them raises, so none is left alone in a later collective."""
+        V = self.params.weights
+        why = None
+        if tuple(V.shape) != tuple(self.A_ij.shape):
+            why = "weights of shape %s for a block of shape %s" % (tuple(V.shape), tuple(self.A_ij.shape))
+            V = None
+        else:
+            V = _to_device(V, self.device, torch.float32, what="weights")
+            on = V > 0
+            strict = self._is or (self._beta and self.beta <= 0.0)
+            if not bool(torch.isfinite(V).all()) or bool((V < 0).any()):
+                why = "weights must be finite and >= 0"
+            else:
+                a = self.A_ij[on]
+                if not bool((a > 0).all() if strict else (a >= 0).all()):   # (a NaN under a positive weight is refused as well)
+                    why = "norm='%s'%s needs %s data where the weight is positive: the smallest such entry is %g" % (
+                        self.norm, " with beta = %g" % self.beta if self._beta else "",
+                        "strictly positive" if strict else "non-negative", float(a.min()))
+        nbad = int(self.comm1.allreduce(1 if why is not None else 0))
+        if nbad:
+            raise ValueError("params.weights: %s (%d of %d ranks refuse their block)"
+                             % (why if why is not None else "another rank's block is refused", nbad, self.p_r * self.p_c))
+        if not int(self.comm1.allreduce(int(bool((V > 0).any())))):
+            raise ValueError("params.weights: no positive weight on any rank (nothing is observed)")
+        return V
 
     @staticmethod
     def _beta_value(params):
@@ -422,7 +497,9 @@ class PyNMF:
         if self._whole_fit_ok(ops):
             # one rank: the whole loop below -- steps, clamps, normalisation, both squared norms -- is ONE library call
             # (dnmf_*_fit, csrc/dnmf_fit.hip): no Python, no ctypes call and no host synchronisation inside the fit
-            if self._beta:                                          # dnmf_beta_mu_fit
+            if self._weighted:                                      # dnmf_weighted_mu_fit
+                sq = ops.weighted_fit(self.A_ij, self.V_ij, self.W_i, self.H_j, self.eps, self.norm, self.beta or 0.0, self.W_update, self.itr)
+            elif self._beta:                                        # dnmf_beta_mu_fit
                 sq = ops.beta_fit(self.A_ij, self.W_i, self.H_j, self.eps, self.beta, self.W_update, self.itr)
             else:
                 sq = ops.fit(self.method, self.norm, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr,
@@ -450,8 +527,11 @@ class PyNMF:
         (anything else keeps the step loop, which raises the reference's messages for invalid pairs).  `params.fit_loop =
         'python'` keeps the step loop (A/B runs, tests of the per-step API).  A NaN-marked block (missing='nan') has one with the
         'hip-masked' set: dnmf_masked_mu_fit, the launches of the step loop in its order (one problem per call: never batched)."""
-        if (self._is or self._beta) and getattr(ops, "name", "") != "hip":
-            return False                                            # (dnmf_is_mu_fit / dnmf_beta_mu_fit live in the fp32 operator set only)
+        if (self._is or self._beta or self._weighted) and getattr(ops, "name", "") != "hip":
+            return False                                            # (dnmf_is_mu_fit / dnmf_beta_mu_fit / dnmf_weighted_mu_fit live in the fp32 operator set only)
+        if self._weighted:                                          # dnmf_weighted_mu_fit: one problem per call, every norm it serves
+            return (self.p == 1 and self.topo == '1d' and self.itr >= 1 and hasattr(ops, "weighted_fit")
+                    and getattr(self.params, "fit_loop", None) != "python" and not getattr(self.params, "native_always", False))
         if self._masked_dense:
             return (self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") == "hip-masked" and hasattr(ops, "fit")
                     and str(self.method).lower() == "mu" and str(self.norm).lower() in ("fro", "kl")
@@ -515,7 +595,7 @@ class PyNMF:
         f0 = fits[0] if fits else None
 
         def same(f):
-            return (not f._masked_dense and not f._is and not f._beta and f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
+            return (not f._masked_dense and not f._is and not f._beta and not f._weighted and f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
                     and f.A_ij.dtype == f0.A_ij.dtype and f.A_ij.device == f0.A_ij.device and f.W_i.shape == f0.W_i.shape
                     and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k) ==
                     (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k))
@@ -590,7 +670,10 @@ class PyNMF:
         if sq is None:
             if self.topo == '2d':
                 self.cart_2d_collect_factors()
-            sq = torch.cat([ops.resid_sqnorm(self.A_ij, self.W_i, self.H_j), ops.sqnorm(self.A_ij)])
+            if self._weighted:                          # sqrt(sum v (a - s)^2 / sum v a^2) over v > 0: at 0/1 weights the masked error
+                sq = ops.weighted_resid_sqnorm(self.A_ij, self.V_ij, self.W_i, self.H_j)
+            else:
+                sq = torch.cat([ops.resid_sqnorm(self.A_ij, self.W_i, self.H_j), ops.sqnorm(self.A_ij)])
             self.comm1.allreduce_(sq)
         num, den = (float(v) for v in sq.cpu())
         self.glob_norm_err, self.glob_norm_A = float(np.sqrt(num)), float(np.sqrt(den))
@@ -648,6 +731,16 @@ class PyNMF:
         """D_beta(A | W H + eps) of the CURRENT factors, summed over the grid (norm='beta': 1D grids, where every rank's block meets its own
         W rows and H columns).  The objective the rule does not increase; `fit()` keeps returning the Frobenius relative error."""
         return self._divergence('beta')
+
+    def weighted_divergence(self):
+        """The weighted objective sum v d(a | s') of the CURRENT factors over v > 0, summed over the grid: d of the fit's norm ('kl', 'is',
+        'beta' with params.beta; s' = W H + eps); under 'fro' half of sum v (a - W H)^2.  What the weighted rule does not increase."""
+        if not self._weighted:
+            raise ValueError("weighted_divergence: this fit has no params.weights")
+        W, H = self._block_factors()
+        d = self._ops().weighted_divergence(self.A_ij, self.V_ij, W, H, self.eps, self.norm, self.beta or 0.0)
+        self.comm1.allreduce_(d)
+        return float(d.cpu())
 
     def is_column_divergence(self):
         """The Itakura-Saito divergence of the CURRENT factors column by column, over the GLOBAL n columns, each divided by the global row

@@ -178,6 +178,9 @@ class PyNMFk:
 
     def __init__(self, A_ij, factors=None, params=None, ops=None):
         from .sparse import is_sparse_input
+        if getattr(params, "weights", None) is not None:
+            raise NotImplementedError("PyNMFk with params.weights is not provided: rank estimation under per-entry weights is a follow-up "
+                                      "(PyNMF takes the weights for one rank k)")
         self._sparse = is_sparse_input(A_ij)
         self._is = str(getattr(params, "norm", None)).lower() in ("is", "itakura-saito")
         self._beta, self.beta = str(getattr(params, "norm", None)).lower() == "beta", None
