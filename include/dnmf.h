@@ -990,5 +990,7 @@ int dnmf_clock_probe(unsigned long long* samples, int n, int naps, void* stream)
 #include "dnmf_beta_nmfk_api.h"
 /* the pair rules under per-entry weights (dnmf_weighted_*), likewise */
 #include "dnmf_weighted_api.h"
+/* and their per-column statistic for rank estimation (dnmf_weighted_column_div*), likewise */
+#include "dnmf_weighted_nmfk_api.h"
 
 #endif /* DNMF_H */

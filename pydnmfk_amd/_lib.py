@@ -286,6 +286,13 @@ for _name in ("aht_pair", "wta_pair", "update_w", "update_h", "divergence", "mu_
     WEIGHTED_SIGNATURES["dnmf_weighted_" + _name] = _sig[:4] + [c_void_p, c_long] + _sig[4:10] + [c_int] + _sig[10:]
 WEIGHTED_SIGNATURES["dnmf_weighted_resid_sqnorm"] = (SIGNATURES["dnmf_masked_resid_sqnorm"][:4] + [c_void_p, c_long]
                                                      + SIGNATURES["dnmf_masked_resid_sqnorm"][4:10] + [c_void_p, c_size_t, c_void_p])
+# the per-column statistic of an NMFk sweep under weights (include/dnmf_weighted_nmfk_api.h), a table of its own (the table above stays
+# as it is): A m n lda V ldv W ldw H ldh k eps norm beta num den ws ws_bytes stream
+WEIGHTED_NMFK_SIGNATURES = {}
+WEIGHTED_NMFK_SIGNATURES["dnmf_weighted_column_div_ws_bytes"] = [c_long, c_long, c_int]
+WEIGHTED_NMFK_SIGNATURES["dnmf_weighted_column_div_plan"] = [c_long, c_long, c_int, c_void_p]      # out: long[3]
+WEIGHTED_NMFK_SIGNATURES["dnmf_weighted_column_div"] = (WEIGHTED_SIGNATURES["dnmf_weighted_divergence"][:15] + [c_void_p]
+                                                        + WEIGHTED_SIGNATURES["dnmf_weighted_divergence"][15:])
 # the W phase from a transposed image of A (csrc/dnmf_timg.hip): build A m n lda At ldat stream; bind the same without the stream
 SIGNATURES["dnmf_wimage_bytes"] = [c_long, c_long]
 SIGNATURES["dnmf_wimage_build"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]
@@ -293,7 +300,7 @@ SIGNATURES["dnmf_wimage_bind"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_
 SIGNATURES["dnmf_wimage_unbind"] = []
 SIGNATURES["dnmf_set_wimage"] = [c_int]
 SIGNATURES["dnmf_wimage_plan"] = [c_long, c_long, c_int, c_long, c_int, c_int, c_void_p]      # out: int[6]
-_RESTYPES = {"dnmf_weighted_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes_fit": c_size_t, "dnmf_beta_column_div_ws_bytes": c_size_t, "dnmf_beta_ws_bytes": c_size_t, "dnmf_beta_ws_bytes_fit": c_size_t, "dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
+_RESTYPES = {"dnmf_weighted_column_div_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes_fit": c_size_t, "dnmf_beta_column_div_ws_bytes": c_size_t, "dnmf_beta_ws_bytes": c_size_t, "dnmf_beta_ws_bytes_fit": c_size_t, "dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
              "dnmf_ws_bytes_1d": c_size_t, "dnmf_ws_bytes_hblocks": c_size_t, "dnmf_ws_bytes_2d": c_size_t,
              "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t, "dnmf_bcd_ws_bytes_fit": c_size_t}
 
@@ -305,7 +312,7 @@ def load():
             "There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, args in list(SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BETA_NMFK_SIGNATURES.items()) \
-            + list(WEIGHTED_SIGNATURES.items()):
+            + list(WEIGHTED_SIGNATURES.items()) + list(WEIGHTED_NMFK_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI drifted from include/dnmf.h
         fn.argtypes = args
         fn.restype = _RESTYPES.get(name, c_int)

@@ -312,6 +312,118 @@ __global__ __launch_bounds__(256) void weighted_tile_sum_kernel(NnArgs p, const 
     }
 }
 
+// ---- the per-column pair of an NMFk sweep under weights: num[c] and den[c] over the block's rows, v > 0 only (DESIGN.md section 7,
+// "NMFk under weights").  add(t, a, s, v, eps) with t[0] the column's numerator and t[1] its scale.
+// v (a - s)^2 and v a^2 with the contraction STATED (fmaf): at v in {0, 1} the operations of MaskedErrTerm on A with NaN where v = 0
+struct WeightedColErrTerm {
+    __device__ __forceinline__ void add(float (&t)[2], float a, float s, float v, float) const {
+        const bool on = v > 0.f;
+        const float d = on ? a - s : 0.f;
+        const float ao = on ? a : 0.f;
+        t[0] = fmaf(on ? v * d : 0.f, d, t[0]);
+        t[1] = fmaf(on ? v * ao : 0.f, ao, t[1]);
+    }
+};
+
+// v d_beta(a | s + eps) and v a^beta (v a under kl, v under is: the column's weight sum)
+template <int FORM>
+struct WeightedColDivTerm {
+    float beta = 0.f, c = 1.f;
+    __device__ __forceinline__ void add(float (&t)[2], float a, float s, float v, float eps) const {
+        float pw;
+        const float d = beta_div_term_pw<FORM>(a, s + eps, beta, c, pw);
+        const bool on = v > 0.f;
+        t[0] += on ? v * d : 0.f;
+        t[1] += on ? v * pw : 0.f;
+    }
+};
+
+// The geometry, the plan (plan_masked_colerr(m, n, 2)), the slab and the ending (col_sums_reduce_kernel<2>) of col_sums_kernel
+// (csrc/dnmf_sums.h); its own is the second m x n operand.  KT <= 2 (HOLD): the lane's 16 x 4 weights of a row block live in vreg, one
+// buffer.  The chunk's first block requests them before its nn_tile products; from there on row r of the NEXT block is requested into
+// vreg[r] where row r of this block has just been consumed, next to the request for row r of A and ahead of the row's terms, so a
+// block's V is in flight under the previous block's terms and its own products.  Only a block whose 32 x 128 tile lies inside the
+// matrix (a wave-uniform test) is requested ahead, with plain vector loads; a ragged block is loaded predicated at its own top, where
+// a V load outside the block returns 0: a gap, with no bounds select.  KT = 4: the carried buffer spills (the products fill the
+// register file), so a row's V is requested with its A through predicated loads.  Forms tried and registers: DESIGN.md section 7.
+template <int KT, bool FAST, class Term>
+__global__ __launch_bounds__(256) void weighted_col_sums_kernel(NnArgs p, const float* __restrict__ V, long ldv, double* __restrict__ P,
+                                                                long ldc, long rowblks_per_chunk, Term term) {
+    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long gw = (long)blockIdx.x * 4 + wid;
+    const long nchunks = cdiv(p.nrowblk, rowblks_per_chunk);
+    if (gw >= nchunks * p.ncolblk) return;
+    const long chunk = gw / p.ncolblk, colblk = gw % p.ncolblk;
+    const long col0 = colblk * 128, col = col0 + 4 * li;
+    constexpr bool HOLD = KT < 4;                               // vreg is carried over the products (see above)
+    const bool cols_in = FAST && col0 + 128 <= p.n;             // wave-uniform: with rows_in(rb), the block's tile is interior
+    auto rows_in = [&](long rb) { return rb * 32 + 32 <= p.m; };
+    double dv[4][2];
+#pragma unroll
+    for (int ne = 0; ne < 4; ++ne) dv[ne][0] = dv[ne][1] = 0.0;
+    float vreg[16][4];
+    bool have = false;                                          // vreg holds this block's weights already (requested a block ago)
+    long rb1 = (chunk + 1) * rowblks_per_chunk;
+    if (rb1 > p.nrowblk) rb1 = p.nrowblk;
+    for (long rb = chunk * rowblks_per_chunk; rb < rb1; ++rb) {
+        const long row0 = rb * 32;
+        const bool in = cols_in && rows_in(rb);
+        const bool pre = HOLD && in && rb + 1 < rb1 && rows_in(rb + 1);  // the next block is interior: its V rows are requested in the walk
+        if (HOLD && !have) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const long row = row0 + crow(r, h);
+                if (in) load_tile_vec<4, FAST, true>(vreg[r], V + row * ldv, col, p.n, true);
+                else load_vec<4, FAST>(vreg[r], V + row * ldv, col, p.n, row < p.m);    // 0 outside the block: a gap
+            }
+        }
+        f32x16 acc[4];
+        nn_tile<KT, 4, FAST, false>(acc, p.W, p.ldw, p.m, p.k, p.H, p.ldh, p.n, row0, col0, li, h);
+        // (the rows of A stay behind the products: hoisted above them, an interior block's 64 registers of A are live next to the
+        // products' W and H operands and to vreg, and KT = 4 spills; behind them they take the registers those operands leave)
+        __builtin_amdgcn_sched_barrier(0);
+        float pv[4][2];
+#pragma unroll
+        for (int ne = 0; ne < 4; ++ne) pv[ne][0] = pv[ne][1] = 0.f;
+        auto walk = [&](auto interior) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const long row = row0 + crow(r, h);
+                float a[4], v[4];
+                load_tile_vec<4, FAST, interior.value>(a, p.A + row * p.lda, col, p.n, row < p.m);
+                if constexpr (HOLD) {
+#pragma unroll
+                    for (int ne = 0; ne < 4; ++ne) v[ne] = vreg[r][ne];
+                } else {
+                    load_tile_vec<4, FAST, interior.value>(v, V + row * ldv, col, p.n, row < p.m);
+                }
+                if constexpr (HOLD && interior.value)
+                    if (pre) load_tile_vec<4, FAST, true>(vreg[r], V + (row + 32) * ldv, col, p.n, true);
+#pragma unroll
+                for (int ne = 0; ne < 4; ++ne) term.add(pv[ne], a[ne], acc[ne][r], v[ne], p.eps);
+            }
+        };
+        if constexpr (HOLD) {
+            if (in) walk(std::true_type{});
+            else walk(std::false_type{});
+        } else {
+            walk(std::false_type{});
+        }
+        have = pre;
+#pragma unroll
+        for (int ne = 0; ne < 4; ++ne) { dv[ne][0] += (double)pv[ne][0]; dv[ne][1] += (double)pv[ne][1]; }
+    }
+    double* Pc = P + chunk * 2 * ldc + col;
+#pragma unroll
+    for (int ne = 0; ne < 4; ++ne)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            dv[ne][j] += __shfl_xor(dv[ne][j], 32, 64);
+            if (h == 0) Pc[j * ldc + ne] = dv[ne][j];
+        }
+}
+
 // ================================================================================================ host side
 // norm of the C ABI -> MODE: f(std::integral_constant<int, MODE>{})
 template <class F>
@@ -411,6 +523,29 @@ int weighted_tile_sum(const char* who, const float* A, long m, long n, long lda,
         if (int rc = check_launch(who)) return rc;
     }
     return DNMF_OK;
+}
+
+// num[0..n) and den[0..n): the walk into the chunks' slab rows, then col_sums_reduce_kernel<2>
+template <class Term>
+int weighted_col_sums(const char* who, const float* A, long m, long n, long lda, const float* V, long ldv, const float* W, long ldw,
+                      const float* H, long ldh, int k, float eps, Term term, double* num, double* den, void* ws, size_t ws_bytes,
+                      void* stream) {
+    WEIGHTED_CHECKS(who, num && den);
+    const MaskedColerrPlan c = plan_masked_colerr(m, n, 2);
+    if (!ws || ws_bytes < c.bytes || !aligned16(ws)) return fail(DNMF_EWS, "%s: workspace %zu < %zu bytes", who, ws_bytes, c.bytes);
+    hipStream_t st = S(stream);
+    NnArgs a = masked_args(A, m, n, lda, W, ldw, H, ldh, k, eps);
+    const bool fast = masked_fast(A, n, lda, W, ldw, H, ldh, k) && weighted_fast(V, ldv);
+    double* P = (double*)ws;
+    const dim3 grid((unsigned)cdiv(c.nchunks * c.ncolblk, 4)), block(256);
+    with_kt_fast(kt, fast, [&](auto v) {
+        hipLaunchKernelGGL((weighted_col_sums_kernel<v.KT, v.FAST, Term>), grid, block, 0, st, a, V, ldv, P, c.ldc, c.rowblks_per_chunk,
+                           term);
+    });
+    if (int rc = check_launch(who)) return rc;
+    hipLaunchKernelGGL(col_sums_reduce_kernel<2>, dim3((unsigned)std::min<long>(cdiv(n, 256), 4096)), dim3(256), 0, st, (const double*)P,
+                       c.ldc, c.nchunks, n, num, den);
+    return check_launch(who);
 }
 #undef WEIGHTED_CHECKS
 

@@ -104,6 +104,29 @@ int dnmf_weighted_divergence(const float* A, long m, long n, long lda, const flo
     return run(WeightedDivTerm<BETA_DIV_GEN>{beta, bf.c});
 }
 
+// ---- the per-column statistic of an NMFk sweep under weights (include/dnmf_weighted_nmfk_api.h): the masked per-column error's plan
+// and pair slab as they are, weighted_col_sums_kernel in the walk's place
+size_t dnmf_weighted_column_div_ws_bytes(long m, long n, int k) { return col_sums_ws_bytes(m, n, k, 2); }
+
+int dnmf_weighted_column_div_plan(long m, long n, int k, long out[3]) {
+    return col_sums_plan_report("weighted_column_div_plan", "the weighted kernels", m, n, k, 2, out);
+}
+
+int dnmf_weighted_column_div(const float* A, long m, long n, long lda, const float* V, long ldv, const float* W, long ldw, const float* H,
+                             long ldh, int k, float eps, int norm, float beta, double* num, double* den, void* ws, size_t ws_bytes,
+                             void* stream) {
+    REQUIRE_WS16(ws, "weighted_column_div");
+    REQUIRE_NORM("weighted_column_div");
+    auto run = [&](auto term) {
+        return weighted_col_sums("weighted_column_div", A, m, n, lda, V, ldv, W, ldw, H, ldh, k, eps, term, num, den, ws, ws_bytes, stream);
+    };
+    if (norm == 0) return run(WeightedColErrTerm{});
+    const BetaForm bf = norm == 3 ? beta_form(beta) : BetaForm{norm == 1 ? BETA_DIV_KL : BETA_DIV_IS, 1.f};
+    if (bf.form == BETA_DIV_KL) return run(WeightedColDivTerm<BETA_DIV_KL>{});
+    if (bf.form == BETA_DIV_IS) return run(WeightedColDivTerm<BETA_DIV_IS>{});
+    return run(WeightedColDivTerm<BETA_DIV_GEN>{beta, bf.c});
+}
+
 // a whole weighted fit: the chain of csrc/dnmf_masked.h with the weighted steps; sq_out is the weighted error pair
 int dnmf_weighted_mu_fit(const float* A, long m, long n, long lda, const float* V, long ldv, float* W, long ldw, float* H, long ldh, int k,
                          float eps, int norm, float beta, int w_update, int itr, double* sq_out, void* ws, size_t ws_bytes, void* stream) {

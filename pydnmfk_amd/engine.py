@@ -949,6 +949,18 @@ class HipOps:
         check(lib.dnmf_weighted_divergence(*head, out.data_ptr(), *tail))
         return out
 
+    weighted_nmfk = True               # PyNMFk looks for this and `weighted_column_div`: the per-column statistic of a sweep under weights
+
+    def weighted_column_div(self, A, V, W, H, eps, norm, beta):
+        """(num, den), n device doubles each, column SUMS over this block's rows where v > 0: sum v (A - W H)^2 and sum v A^2 under
+        'fro'; sum v d(A | W H + eps) and sum v A^beta under kl / is / beta (A under kl, 1 under is).  dnmf_weighted_column_div: stored,
+        not accumulated -- two calls are bit-identical.  The statistic is formed after the sums have crossed the ranks
+        (PyNMF.weighted_column_divergence)."""
+        head, tail = self._weighted("weighted_column_div", A, V, W, H, eps, norm, beta, ws=lib.dnmf_weighted_column_div_ws_bytes)
+        out = torch.empty(2, A.shape[1], dtype=torch.float64, device=A.device)
+        check(lib.dnmf_weighted_column_div(*head, out[0].data_ptr(), out[1].data_ptr(), *tail))
+        return out[0], out[1]
+
     def weighted_fit(self, A, V, W, H, eps, norm, beta, w_update, itr):
         """`itr` weighted MU steps (clamps after the steps i % 10 == 0), normalize_features and the weighted error pair in ONE library
         call (dnmf_weighted_mu_fit).  One problem; W, H are updated in place; returns the device tensor [1][2] of weighted_resid_sqnorm."""

@@ -742,6 +742,23 @@ class PyNMF:
         self.comm1.allreduce_(d)
         return float(d.cpu())
 
+    def weighted_column_divergence(self):
+        """The weighted objective of the CURRENT factors column by column, over the GLOBAL n columns and over v > 0 only, each divided by
+        the column's own weighted scale:  sqrt(sum_i v (a - s)^2 / sum_i v a^2) under 'fro' (at 0/1 weights the masked `column_err()`),
+        sum_i v d(a | s') / sum_i v a^beta under kl / is / beta (a^1 under kl; a^0 = 1 under is: the column's weight sum).  Invariant
+        under a column's scale and under the scale of its weights; what an NMFk sweep under weights takes where `column_err()` stands
+        (which reads the entries under zero weights).  A column without a positive weight, or without scale, gives nan.  The scheme of
+        `beta_column_divergence()`: each rank fills its own column range of [num | den], ONE float64 allreduce carries both."""
+        if not self._weighted:
+            raise ValueError("weighted_column_divergence: this fit has no params.weights")
+        W, H = self._block_factors()
+        col = self._global_columns(*self._ops().weighted_column_div(self.A_ij, self.V_ij, W, H, self.eps, self.norm, self.beta or 0.0))
+        self.comm1.allreduce_(col)
+        col = col.cpu().numpy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            stat = np.where(col[1] > 0.0, col[0] / col[1], np.nan)
+            return np.sqrt(stat) if str(self.norm).lower() == 'fro' else stat
+
     def is_column_divergence(self):
         """The Itakura-Saito divergence of the CURRENT factors column by column, over the GLOBAL n columns, each divided by the global row
         count `params.m`: a mean per entry, scale-invariant (a column's scale cancels in q = A / (W H + eps)) and comparable across k.

@@ -21,6 +21,13 @@ statistics gain 'is_div' (per perturbation) and 'avgDiv'; recon_err, avgErr and 
 for beta <= 0 and non-negative for beta > 0, checked once; 'poisson' sampling for beta > 0 only; `L_err` is the divergence of each column
 over the column's sum of a^beta (PyNMF.beta_column_divergence: scale-invariant for every beta; the Itakura-Saito statistic at beta = 0,
 half the squared Frobenius column error at beta = 2); the statistics gain 'beta_div' (per perturbation), 'avgDiv' and 'beta'.
+`params.weights` (per-entry weights V >= 0 of the block's shape, norms fro / kl / is / beta; what PyNMF refuses under weights is refused at
+construction): the weights stay fixed over the sweep and only the data are perturbed -- 'uniform' multiplies the array as it is, so what
+lies under a zero weight stays unread; 'poisson' draws from rates zeroed where v = 0 --, the sign condition of is / beta is checked where
+v > 0 only, the fits run one by one, `L_err` is PyNMF.weighted_column_divergence (each column's weighted error or divergence over its own
+weighted scale, v > 0 only), recon_err / avgErr are the weighted relative error, and the statistics gain 'weighted_div' (per
+perturbation, PyNMF.weighted_divergence) and 'avgDiv' in place of 'is_div' / 'beta_div'.  One rank, the two 1D grids (each rank's
+params.weights is its block) and nmfk_split='perturbations'.
 """
 import os
 
@@ -46,9 +53,10 @@ class sample:
     kernels only multiply) --; 'poisson' draws from the zero-filled rates and puts NaN back, so no NaN rate reaches a generator, the
     generators are consumed as on the dense path, and a draw of 0 at an observed position is an observed zero."""
 
-    def __init__(self, data, noise_var, method, seed=None, out=None, sparse=None, missing=None):
+    def __init__(self, data, noise_var, method, seed=None, out=None, sparse=None, missing=None, weights=None):
         self.X = data
         self.missing = missing
+        self.weights = weights  # per-entry weights: 'poisson' draws from rates zeroed where v = 0 ('uniform' only multiplies: nothing to do)
         self.out = out          # optional destination of the perturbed copy (a slice of the stack an NMFk batch is fitted from)
         # a SparseBlock: what the sweep keeps about it between the perturbations (SparseSweep; built here when the caller has none)
         self.sparse = sparse if sparse is not None or not getattr(data, "is_sparse_block", False) else SparseSweep(data)
@@ -84,18 +92,21 @@ class sample:
             self.X_per = self.sparse.poisson(self.seed)
             return
         nan = self.missing == "nan"
+        # (what lies under a zero weight is a gap as well, and no rate: the draw there is Poisson(0) = 0, never read, and no NaN is put back)
+        off = None if self.weights is None else ~(torch.as_tensor(self.weights) > 0)
         if isinstance(self.X, torch.Tensor):
             g = torch.Generator(device=self.X.device)
             g.manual_seed(0 if self.seed is None else int(self.seed))
-            gaps = torch.isnan(self.X) if nan else None
-            rates = torch.where(gaps, torch.zeros_like(self.X), self.X) if nan else self.X
+            gaps = torch.isnan(self.X) if nan else None if off is None else off.to(self.X.device)
+            rates = torch.where(gaps, torch.zeros_like(self.X), self.X) if gaps is not None else self.X
             self.X_per = torch.poisson(rates.float(), generator=g).to(self.X.dtype)
             if nan:
                 self.X_per[gaps] = float("nan")
-        elif nan:
-            gaps = np.isnan(self.X)
+        elif nan or off is not None:
+            gaps = np.isnan(self.X) if nan else off.cpu().numpy()
             self.X_per = np.random.poisson(np.where(gaps, 0, self.X)).astype(self.X.dtype)
-            self.X_per[gaps] = np.nan
+            if nan:
+                self.X_per[gaps] = np.nan
         else:
             self.X_per = np.random.poisson(self.X).astype(self.X.dtype)
 
@@ -178,9 +189,18 @@ class PyNMFk:
 
     def __init__(self, A_ij, factors=None, params=None, ops=None):
         from .sparse import is_sparse_input
-        if getattr(params, "weights", None) is not None:
-            raise NotImplementedError("PyNMFk with params.weights is not provided: rank estimation under per-entry weights is a follow-up "
-                                      "(PyNMF takes the weights for one rank k)")
+        self._weighted = getattr(params, "weights", None) is not None
+        if self._weighted:
+            # first of all: the sweep asks one operation beyond a weighted fit, the per-column pair over v > 0 (column_err and the
+            # per-column divergences read the entries under zero weights and know no V)
+            if ops is None:
+                from .engine import HIP_OPS as opset
+            else:
+                opset = ops
+            if not (getattr(opset, "weighted_nmfk", False) and hasattr(opset, "weighted_column_div")):
+                raise NotImplementedError("PyNMFk with params.weights is not provided by operator set %r: rank estimation under per-entry "
+                                          "weights needs a weighted per-column divergence (PyNMF takes the weights for one rank k)"
+                                          % (getattr(opset, "name", type(opset).__name__),))
         self._sparse = is_sparse_input(A_ij)
         self._is = str(getattr(params, "norm", None)).lower() in ("is", "itakura-saito")
         self._beta, self.beta = str(getattr(params, "norm", None)).lower() == "beta", None
@@ -194,7 +214,8 @@ class PyNMFk:
                 from .engine import HIP_OPS as opset
             else:
                 opset = ops
-            if not (getattr(opset, norm + "_nmfk", False) and hasattr(opset, norm + "_column_div")):
+            # (under weights the statistic is the weighted pair's, checked above: the norm's own per-column divergence is not asked for)
+            if not self._weighted and not (getattr(opset, norm + "_nmfk", False) and hasattr(opset, norm + "_column_div")):
                 raise NotImplementedError("PyNMFk with norm='%s' is not provided by operator set %r: rank estimation under %s needs a "
                                           "per-column divergence (PyNMF factorises at a given k)"
                                           % (norm, getattr(opset, "name", type(opset).__name__),
@@ -205,7 +226,7 @@ class PyNMFk:
                 self._is, self._beta = self.beta == 0.0, self.beta != 0.0
             params.norm = 'is' if self._is else 'beta'
         self._masked = getattr(params, "missing", None) == "nan" and not self._sparse
-        if self._masked and not (self._is or self._beta):           # (norm='is' and norm='beta' refuse missing= and sparse data by name in their setup)
+        if self._masked and not (self._is or self._beta or self._weighted):           # (norm='is' and norm='beta' refuse missing= and sparse data by name in their setup)
             # as for a sparse block, the sweep touches A outside PyNMF.fit in the perturbed copy (NaN stays NaN through the
             # multiplication) and in the per-column error, which must run over the observed positions
             if ops is None:
@@ -216,7 +237,7 @@ class PyNMFk:
                 raise NotImplementedError("PyNMFk with missing='nan' is not provided by operator set %r: rank estimation over NaN-marked "
                                           "data needs a masked per-column error (PyNMF factorises such data at a given k)"
                                           % (getattr(opset, "name", type(opset).__name__),))
-        if self._sparse and not (self._is or self._beta):
+        if self._sparse and not (self._is or self._beta or self._weighted):         # (weights refuse sparse data and missing= by name in their setup)
             # the sweep touches A outside PyNMF.fit in two operations: the perturbed copy and the per-column error
             if ops is None:
                 from .engine import HIP_CSR_OPS as opset
@@ -281,6 +302,8 @@ class PyNMFk:
         self.cp = Checkpoint(checkpoint_save=self.params.checkpoint, params=self.params)
         self.stats = {}        # k -> cluster statistics (also written to disk per k)
         self.sweep = None
+        if self._weighted:
+            self._weighted_setup(A_ij)      # (first, as in PyNMF: what it refuses under weights is refused in those words)
         if self._is or self._beta:
             self._div_setup(A_ij)           # (first: sparse data and missing= are refused in the norm's words)
         if self._sparse:
@@ -311,7 +334,35 @@ class PyNMFk:
                 raise TypeError("PyNMFk: A_ij is a CPU tensor; pass a CUDA tensor or a numpy array (no CPU fallback)")
             if not torch.cuda.is_available():
                 raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
-        PyNMF._sign_check(beta, float(A_ij.min()) if int(np.prod(A_ij.shape)) else 1.0, self.comm1, self.p)
+        lo = self._observed_min(A_ij, params.weights) if self._weighted else float(A_ij.min()) if int(np.prod(A_ij.shape)) else 1.0
+        PyNMF._sign_check(beta, lo, self.comm1, self.p)
+
+    @staticmethod
+    def _observed_min(A_ij, V):
+        """the smallest entry of the block where the weight is positive -- what lies under a zero weight is not looked at, as in
+        PyNMF._weights_block; a block whose weights PyNMF will refuse by name at the first fit (shape, no positive weight) passes here"""
+        a, v = torch.as_tensor(A_ij), torch.as_tensor(V)
+        if tuple(v.shape) != tuple(a.shape):
+            return 1.0
+        on = v.to(a.device) > 0
+        return float(a[on].min()) if bool(on.any()) else 1.0
+
+    def _weighted_setup(self, A_ij):
+        """params.weights: the weights stay fixed over the sweep (every fit, the regression fit included, reads the same params.weights;
+        only the data are perturbed); what PyNMF refuses under weights is refused here, at construction, in its words (the sweep's
+        largest rank stands for k)."""
+        import copy
+        from .pyDNMF import storage_dtype
+        probe = copy.copy(self.params)
+        probe.k = int(self.end_k)
+        a_dtype = torch.float32 if self._sparse else storage_dtype(A_ij, self.params)
+        PyNMF._weighted_refusals(var_init(self.params, 'norm', default='kl'), probe, self._sparse, getattr(self.params, "missing", None),
+                                 a_dtype, self.ops, var_init(self.params, 'method', default='mu'), self.p_r, self.p_c)
+        if self.ops is None:
+            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda:
+                raise TypeError("PyNMFk: A_ij is a CPU tensor; pass a CUDA tensor or a numpy array (no CPU fallback)")
+            if not torch.cuda.is_available():
+                raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
 
     def _masked_setup(self, A_ij):
         """missing='nan': the raw array stays `self.A_ij` (every PyNMF wraps its perturbed copy in a MaskedDenseBlock itself); what PyNMF
@@ -401,7 +452,8 @@ class PyNMFk:
                                         self.A_ij.device)            # the perturbed copies are written straight into it
                 data = sample(data=self.A_ij, noise_var=self.noise_var, method=self.sampling, seed=perturbation * 1000,
                               out=None if stack is None else stack[b], sparse=self.sweep,
-                              missing="nan" if self._masked else None).fit()
+                              missing="nan" if self._masked else None,
+                              weights=self.params.weights if self._weighted and self.sampling == 'poisson' else None).fit()
                 self.params.W_update = True
                 if getattr(self.params, "rng", None) == "device":       # device-drawn init: one seed per (perturbation, k)
                     self.params.init_seed = perturbation * 1000 + self.k
@@ -415,7 +467,9 @@ class PyNMFk:
                 fits.append(f)
                 del data
             results.extend(PyNMF.fit_batch(fits))
-            if self._is:
+            if self._weighted:              # (the norm's own divergence would read the entries under zero weights)
+                divs.extend(f.weighted_divergence() for f in fits)
+            elif self._is:
                 divs.extend(f.is_divergence() for f in fits)
             elif self._beta:
                 divs.extend(f.beta_divergence() for f in fits)
@@ -423,7 +477,7 @@ class PyNMFk:
                 self.cp._save_checkpoint(self.params.flag, perturbation, self.k)
             del fits, stack
         if shared:
-            results, divs = self._gather_fits(results, mine, divs if (self._is or self._beta) else None)
+            results, divs = self._gather_fits(results, mine, divs if (self._is or self._beta or self._weighted) else None)
             perturbation = self.perturbations - 1
         self.params.flag = 1
         self.cp._save_checkpoint(self.params.flag, perturbation, self.k)
@@ -467,18 +521,24 @@ class PyNMFk:
         # :248.  Under norm='is' the per-column statistic is the mean Itakura-Saito divergence per entry: the Frobenius column_err
         # weights the columns by their scale, which is what a user who chose this norm wanted to avoid
         # and under norm='beta' the divergence of each column over its sum of a^beta, scale-invariant for every beta
-        self.col_err = (regressH.is_column_divergence() if self._is else regressH.beta_column_divergence() if self._beta
-                        else regressH.column_err())
+        # and under weights the weighted pair's statistic of the norm, over v > 0 only
+        self.col_err = (regressH.weighted_column_divergence() if self._weighted else regressH.is_column_divergence() if self._is
+                        else regressH.beta_column_divergence() if self._beta else regressH.column_err())
         self.avgErr = float(np.mean(self.recon_err))
         mn = self.params.m * self.params.n      # (sparse data too, under both meanings of an unstored entry, and NaN-marked data: DESIGN.md section 7)
         self.AIC = 2 * self.k + mn * np.log(self.avgErr / mn)                                           # :250
         cluster_stats = {'clusterSilhouetteCoefficients': self.clusterSilhouetteCoefficients,
                          'avgSilhouetteCoefficients': self.avgSilhouetteCoefficients, 'L_errDist': self.L_errDist,
                          'L_err': self.col_err, 'avgErr': self.avgErr, 'recon_err': self.recon_err, 'AIC': self.AIC}
-        if self._is:                            # (recon_err, avgErr and AIC keep their Frobenius definitions)
+        if self._weighted:                      # (recon_err and avgErr are the weighted relative error fit() returns; AIC keeps m n)
+            self.weighted_div = [float(d) for d in divs]
+            cluster_stats['weighted_div'], cluster_stats['avgDiv'] = self.weighted_div, float(np.mean(self.weighted_div))
+            if self._beta:
+                cluster_stats['beta'] = self.beta
+        elif self._is:                          # (recon_err, avgErr and AIC keep their Frobenius definitions)
             self.is_div = [float(d) for d in divs]
             cluster_stats['is_div'], cluster_stats['avgDiv'] = self.is_div, float(np.mean(self.is_div))
-        if self._beta:
+        elif self._beta:
             self.beta_div = [float(d) for d in divs]
             cluster_stats['beta_div'], cluster_stats['avgDiv'], cluster_stats['beta'] = self.beta_div, float(np.mean(self.beta_div)), self.beta
         self.stats[self.k] = cluster_stats
@@ -534,7 +594,7 @@ class PyNMFk:
         operators -- as many as fit next to each other in the GPU's free memory (each holds its perturbed copy of the data) --
         else 1.  `params.nmfk_batch` = False / 0 / 1 keeps the one-by-one fits, an integer caps the batch."""
         want = getattr(self.params, "nmfk_batch", True)
-        if self._sparse or self._masked or self._is or self._beta:          # no batched sparse, masked, Itakura-Saito or beta-divergence entry point: the fits run one by one, no stack is allocated
+        if self._sparse or self._masked or self._is or self._beta or self._weighted:          # no batched sparse, masked, weighted, Itakura-Saito or beta-divergence entry point: the fits run one by one, no stack is allocated
             return 1
         if want is False or self.p != 1 or self.ops is not None or not torch.cuda.is_available():
             return 1

@@ -8,6 +8,7 @@ twin is the masked KL step, the PAIR_KL kernels, on the same NaN-free data) and 
 are timed back to back -- weighted, then unweighted, `--steps` times after `--warmup` of each -- every step with its own pair of HIP
 events; the figures are medians (min / max next to them).  Both run the mode's launch plan; the weighted step reads 4 m n more bytes
 per side (V beside A), so the byte ratio of a side is (2 A-sized reads) / (1): at most 2, reached only where a side is bound by HBM.
+A second table times dnmf_weighted_column_div (beta = 0.5) next to dnmf_beta_column_div on the same A, W, H, in the same rounds.
 """
 import argparse
 import json
@@ -50,6 +51,10 @@ def bench(m, n, k, steps, warmup, seed=0):
             w, h = make("w"), make("h")
             fns["%s_%s_step" % (norm, kind)] = lambda w=w, h=h: (w(), h())
             fns["%s_%s_w" % (norm, kind)], fns["%s_%s_h" % (norm, kind)] = w, h
+    # the per-column pair of an NMFk sweep under weights next to dnmf_beta_column_div of the same build on the same A, W, H (beta = 0.5:
+    # the general form): twice the A-sized bytes at the same flops
+    fns["coldiv_weighted"] = lambda: HIP_OPS.weighted_column_div(A, V, W, H, EPS, "beta", 0.5)
+    fns["coldiv_plain"] = lambda: HIP_OPS.beta_column_div(A, W, H, EPS, 0.5)
     for _ in range(warmup):
         for fn in fns.values():
             fn()
@@ -63,6 +68,7 @@ def bench(m, n, k, steps, warmup, seed=0):
     for norm, _ in MODES:
         for what in ("step", "w", "h"):
             out["ratio_%s_%s" % (norm, what)] = out["%s_weighted_%s" % (norm, what)]["median_ms"] / out["%s_plain_%s" % (norm, what)]["median_ms"]
+    out["ratio_coldiv"] = out["coldiv_weighted"]["median_ms"] / out["coldiv_plain"]["median_ms"]
     assert torch.isfinite(W).all() and torch.isfinite(H).all()
     return out
 
@@ -88,6 +94,10 @@ def main():
                 r["m"], r["n"], r["k"], norm if norm != "beta" else "beta=%g" % beta, t(norm + "_weighted_step"), t(norm + "_plain_step"),
                 r["ratio_%s_step" % norm], md(norm + "_weighted_w"), md(norm + "_plain_w"), r["ratio_%s_w" % norm], md(norm + "_weighted_h"),
                 md(norm + "_plain_h"), r["ratio_%s_h" % norm]))
+    lines += ["", "| m x n | k | dnmf_weighted_column_div ms (min-max) | dnmf_beta_column_div ms (min-max) | ratio |", "|---|---|---|---|---|"]
+    for r in rows:
+        t = lambda key: "%.3f (%.3f-%.3f)" % (r[key]["median_ms"], r[key]["min_ms"], r[key]["max_ms"])          # noqa: E731
+        lines.append("| %d x %d | %d | %s | %s | %.2f |" % (r["m"], r["n"], r["k"], t("coldiv_weighted"), t("coldiv_plain"), r["ratio_coldiv"]))
     print("\n".join(lines))
     for path, text in ((opt.md, "\n".join(lines) + "\n"), (opt.json, json.dumps({"rows": rows}, indent=1))):
         if path:
