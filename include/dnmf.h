@@ -992,5 +992,7 @@ int dnmf_clock_probe(unsigned long long* samples, int n, int naps, void* stream)
 #include "dnmf_weighted_api.h"
 /* and their per-column statistic for rank estimation (dnmf_weighted_column_div*), likewise */
 #include "dnmf_weighted_nmfk_api.h"
+/* Itakura-Saito and the beta-divergence on float64 data (dnmf_is_f64_*, dnmf_beta_f64_*), likewise */
+#include "dnmf_f64_div_api.h"
 
 #endif /* DNMF_H */

@@ -293,6 +293,14 @@ WEIGHTED_NMFK_SIGNATURES["dnmf_weighted_column_div_ws_bytes"] = [c_long, c_long,
 WEIGHTED_NMFK_SIGNATURES["dnmf_weighted_column_div_plan"] = [c_long, c_long, c_int, c_void_p]      # out: long[3]
 WEIGHTED_NMFK_SIGNATURES["dnmf_weighted_column_div"] = (WEIGHTED_SIGNATURES["dnmf_weighted_divergence"][:15] + [c_void_p]
                                                         + WEIGHTED_SIGNATURES["dnmf_weighted_divergence"][15:])
+# Itakura-Saito and the beta-divergence on float64 data (include/dnmf_f64_div_api.h, csrc/dnmf_f64_div.hip), a table of its own as well: the
+# dnmf_is_* / dnmf_beta_* signatures with `double eps` and `double beta`; no plan query, no whole fit
+F64_DIV_SIGNATURES = {"dnmf_is_f64_ws_bytes": [c_long, c_long, c_int], "dnmf_beta_f64_ws_bytes": [c_long, c_long, c_int]}
+for _name in ("aht_pair", "wta_pair", "update_w", "update_h", "divergence", "ratio_update"):
+    _e = 7 if _name == "ratio_update" else 9
+    _sig = SIGNATURES["dnmf_is_" + _name]
+    F64_DIV_SIGNATURES["dnmf_is_f64_" + _name] = _sig[:_e] + [c_double] + _sig[_e + 1:]
+    F64_DIV_SIGNATURES["dnmf_beta_f64_" + _name] = _sig[:_e] + [c_double, c_double] + _sig[_e + 1:]
 # the W phase from a transposed image of A (csrc/dnmf_timg.hip): build A m n lda At ldat stream; bind the same without the stream
 SIGNATURES["dnmf_wimage_bytes"] = [c_long, c_long]
 SIGNATURES["dnmf_wimage_build"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]
@@ -300,7 +308,7 @@ SIGNATURES["dnmf_wimage_bind"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_
 SIGNATURES["dnmf_wimage_unbind"] = []
 SIGNATURES["dnmf_set_wimage"] = [c_int]
 SIGNATURES["dnmf_wimage_plan"] = [c_long, c_long, c_int, c_long, c_int, c_int, c_void_p]      # out: int[6]
-_RESTYPES = {"dnmf_weighted_column_div_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes_fit": c_size_t, "dnmf_beta_column_div_ws_bytes": c_size_t, "dnmf_beta_ws_bytes": c_size_t, "dnmf_beta_ws_bytes_fit": c_size_t, "dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
+_RESTYPES = {"dnmf_is_f64_ws_bytes": c_size_t, "dnmf_beta_f64_ws_bytes": c_size_t, "dnmf_weighted_column_div_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes_fit": c_size_t, "dnmf_beta_column_div_ws_bytes": c_size_t, "dnmf_beta_ws_bytes": c_size_t, "dnmf_beta_ws_bytes_fit": c_size_t, "dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
              "dnmf_ws_bytes_1d": c_size_t, "dnmf_ws_bytes_hblocks": c_size_t, "dnmf_ws_bytes_2d": c_size_t,
              "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t, "dnmf_bcd_ws_bytes_fit": c_size_t}
 
@@ -312,7 +320,7 @@ def load():
             "There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, args in list(SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BETA_NMFK_SIGNATURES.items()) \
-            + list(WEIGHTED_SIGNATURES.items()) + list(WEIGHTED_NMFK_SIGNATURES.items()):
+            + list(WEIGHTED_SIGNATURES.items()) + list(WEIGHTED_NMFK_SIGNATURES.items()) + list(F64_DIV_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI drifted from include/dnmf.h
         fn.argtypes = args
         fn.restype = _RESTYPES.get(name, c_int)

@@ -11,18 +11,9 @@
 //   TN  C[j][c] = sum_r X[r][j] Y[r][c]      W^T A, W^T W      (contraction over the rows; partial slabs + ordered reduction)
 //   NN  S[r][c] = sum_j X[r][j] Y[j][c]      W H, W G, G H     (fused epilogues: quotient, squared residual, the MU updates)
 // The contraction order inside a tile is permuted freely (sums are order-agnostic up to rounding).
-#include "dnmf_common.h"
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-#define MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
+#include "dnmf_f64_ops.h"      // the fp64 MFMA, the MUBUF operand loads (rsrc64, ldq), block_sum: shared with csrc/dnmf_f64_div.hip
 
 namespace {
-
-#define REQ(cond, ...) do { if (!(cond)) return fail(DNMF_EINVAL, __VA_ARGS__); } while (0)
-inline hipStream_t ST(void* s) { clear_hip_error(); return reinterpret_cast<hipStream_t>(s); }
-inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
-inline int tiles16(int k) { return (k + 15) / 16; }
 
 // four consecutive doubles row[c .. c + 3]; zero outside [.., cend) or when !ok.  vec: the row pointer is 16-byte aligned and c is even
 __device__ __forceinline__ void ld4(double (&d)[4], const double* __restrict__ row, long c, long cend, bool ok, bool vec) {
@@ -44,40 +35,6 @@ __device__ __forceinline__ void ldn(double (&d)[N], const double* __restrict__ r
         else { d[0] = (ok && c < cend) ? row[c] : 0.0; d[1] = (ok && c + 1 < cend) ? row[c + 1] : 0.0; }
     } else d[0] = (ok && c < cend) ? row[c] : 0.0;
 }
-
-// ---- MUBUF operand loads (dnmf_common.h "buffer addressing").  Round 6: the flat loads above sit behind runtime branches (vector or
-// element-wise, in or out of range), and hipcc answers a load under a branch with s_waitcnt vmcnt(0) at the next use -- the "two
-// register sets" of the NT / TN kernels never overlapped anything (3 waits in f64_nt_kernel<4,4>, all vmcnt(0), behind 335 branches).
-// A buffer load needs no branch: a lane is switched off through its offset, rows beyond the operand fall outside the descriptor's
-// byte count (the hardware returns 0), a 16-byte access only needs 4-byte alignment.
-// descriptor over `bytes` bytes from `base` (both wave-uniform; at most 2 GiB: offsets are 31-bit, BUF_OOB is the off switch)
-__device__ __forceinline__ i32x4 rsrc64(const double* base, long bytes) {
-    i32x4 r = buf_rsrc(base);
-    const long b = bytes < 0 ? 0 : (bytes > 0x7fffffffL ? 0x7fffffffL : bytes);
-    r[2] = __builtin_amdgcn_readfirstlane((int)b);
-    return r;
-}
-// N consecutive doubles (N = 1, 2, 4) at byte offset vo + soff; `nvalid` of them are in range (the rest: zero).  VEC: nvalid is 0 or N
-// by construction of the caller (column counts divisible by N), so the lane moves as a whole
-template <int N, bool VEC>
-__device__ __forceinline__ void ldq(double (&d)[N], i32x4 rs, int vo, int soff, int nvalid) {
-    if constexpr (VEC) {
-        const int o = nvalid > 0 ? vo : BUF_OOB;
-        if constexpr (N == 4) {
-            const f32x4 a = buf_ld_f32x4(rs, o, soff, 0), b = buf_ld_f32x4(rs, o + 16, soff, 0);
-            const f64x2 x = __builtin_bit_cast(f64x2, a), y = __builtin_bit_cast(f64x2, b);
-            d[0] = x[0]; d[1] = x[1]; d[2] = y[0]; d[3] = y[1];
-        } else if constexpr (N == 2) {
-            const f64x2 x = __builtin_bit_cast(f64x2, buf_ld_f32x4(rs, o, soff, 0));
-            d[0] = x[0]; d[1] = x[1];
-        } else d[0] = __builtin_bit_cast(double, buf_ld_f32x2(rs, o, soff, 0));
-    } else {
-#pragma unroll
-        for (int e = 0; e < N; ++e) d[e] = __builtin_bit_cast(double, buf_ld_f32x2(rs, e < nvalid ? vo + 8 * e : BUF_OOB, soff, 0));
-    }
-}
-__device__ __forceinline__ int sgpr(long x) { return __builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ int clampi(long x, int hi) { return x < 0 ? 0 : (x > hi ? hi : (int)x); }
 
 // ================================================================================================ NT form
 // out[split][r][j] = sum_{c in split} X[r][c] Y[j][c];  one wave = RT 16-row tiles x NT 16-column tiles of the output.
@@ -467,18 +424,6 @@ __global__ __launch_bounds__(256) void f64_ew_kernel(int op, double* __restrict_
     }
 }
 
-__device__ __forceinline__ double block_sum(double v, double* red) {       // fixed-order tree: deterministic
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double out = red[0];
-    __syncthreads();
-    return out;
-}
-
 // part[blockIdx.x] = sum over the block's grid-stride share of f(X); SQ: squares
 template <bool SQ>
 __global__ __launch_bounds__(256) void f64_sum_partial_kernel(const double* __restrict__ X, long rows, long cols, long ldx, double* __restrict__ part) {
@@ -492,14 +437,6 @@ __global__ __launch_bounds__(256) void f64_sum_partial_kernel(const double* __re
     const double s = block_sum(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
-__global__ __launch_bounds__(256) void f64_sum_final_kernel(const double* __restrict__ part, int nparts, double* __restrict__ out) {
-    __shared__ double red[256];
-    double acc = 0.0;
-    for (int p = threadIdx.x; p < nparts; p += 256) acc += part[p];
-    const double s = block_sum(acc, red);
-    if (threadIdx.x == 0) *out = s;
-}
-
 // x[r] = sum_c H[r][c]: one workgroup per row
 __global__ __launch_bounds__(256) void f64_rowsum_kernel(const double* __restrict__ H, long n, long ldh, double* __restrict__ x) {
     __shared__ double red[256];
@@ -565,8 +502,6 @@ __global__ __launch_bounds__(256) void f64_hals_h_kernel(double* __restrict__ H,
 
 // ------------------------------------------------------------------------------------------------ host side
 bool vec_ok(const double* p, long ld) { return ((uintptr_t)p & 15) == 0 && ld % 2 == 0; }
-// `rows` rows of pitch ld (plus one more row of slack for the lane offsets inside a row) stay inside a descriptor's 31-bit offsets
-bool buf_ok(long ld, long rows) { return (rows + 1) * ld * 8 < 0x7fffffffL; }
 
 struct TnPlan64 { int ncolblk; long nchunks, rows_per_chunk; };
 TnPlan64 plan_tn64(long m, long n, int k) {

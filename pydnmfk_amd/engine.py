@@ -286,7 +286,172 @@ class ClockProbe:
         return float(x.median()) if x.numel() else None
 
 
-class HipOps:
+class _DivFamily:
+    """What the operator sets share under the dense pair rules: the argument checks and, for the Itakura-Saito and beta-divergence
+    families, ONE implementation of the pair, update, ratio and divergence operations over the library prefix -- dnmf_is_* / dnmf_beta_*
+    on float32 tensors (HipOps), dnmf_is_f64_* / dnmf_beta_f64_* on float64 tensors (HipOpsF64).  A set names its tensors' dtype
+    (`_fam_dtype`), their check (`_fam_req`), the infix of its entry points (`_fam_sfx`) and its rank messages."""
+
+    _fam_sfx = ""
+    _fam_dtype = torch.float32
+    _fam_req = staticmethod(_req)
+    BETA_RANGE = (-2.0, 4.0)
+
+    # ---- what the dense pair rules share (dnmf_is_* / dnmf_beta_* here, dnmf_masked_* in HipMaskedOps; the sparse set uses the last two)
+    @classmethod
+    def _pair_args(cls, what, T, W, H, eps, nbytes_fn, ranks, mode=(), pair=None):
+        """(A, W, H) checked against each other, the scratch `nbytes_fn` sizes (0: the rank is refused with `ranks`), and the
+        arguments every entry point of a dense pair rule starts with (`mode`: the masked rules' kl) and ends with.  pair = (side,
+        num, den): two views of the side's shape with one leading dimension, appended to the head."""
+        _req = cls._fam_req
+        _req(T, "A"); _req(W, "W"); _req(H, "H")
+        m, n = T.shape
+        k = W.shape[1]
+        if tuple(W.shape) != (m, k) or tuple(H.shape) != (k, n):
+            raise ValueError("%s: shapes A %s, W %s, H %s do not match" % (what, tuple(T.shape), tuple(W.shape), tuple(H.shape)))
+        nbytes = nbytes_fn(int(m), int(n), int(k))
+        if nbytes == 0:
+            raise NotImplementedError(ranks % k)
+        ws = _scratch(nbytes, T.device)
+        head = (T.data_ptr(), m, n, _ld(T), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), int(k), float(eps)) + tuple(mode)
+        if pair is not None:
+            side, num, den = pair
+            _req(num, "num"); _req(den, "den")
+            want = (m, k) if side == "w" else (k, n)
+            if tuple(num.shape) != want or tuple(den.shape) != want or _ld(num) != _ld(den):
+                raise ValueError("%s: num %s and den %s must both be %s with one leading dimension" % (what, tuple(num.shape), tuple(den.shape), want))
+            head += (num.data_ptr(), den.data_ptr(), _ld(num))
+        return head, (ws.data_ptr(), ws.numel(), _stream())
+
+    def _pair_fit(self, what, fit_fn, T, W, H, eps, nbytes_fn, ranks, mode, w_update, itr):
+        """a whole fit under a dense pair rule as one library call: returns the device tensor [1][2] of its two squared norms"""
+        head, tail = self._pair_args(what, T, W, H, eps, nbytes_fn, ranks, mode)
+        sq = torch.empty(1, 2, dtype=torch.float64, device=T.device)
+        check(fit_fn(*head, int(bool(w_update)), int(itr), sq.data_ptr(), *tail))
+        return sq
+
+    @classmethod
+    def _halves(cls, buf, shape):
+        """[num | den]: the halves of one contiguous buffer (what ONE allreduce carries) as two views of `shape`"""
+        r, c = shape
+        if buf.numel() < 2 * r * c or not buf.is_contiguous() or buf.dtype != cls._fam_dtype:
+            raise ValueError("pair buffer: a contiguous %s buffer of 2 x %d x %d elements is expected" % (str(cls._fam_dtype).replace("torch.", ""), r, c))
+        return buf[: r * c].view(r, c), buf[r * c: 2 * r * c].view(r, c)
+
+    @classmethod
+    def _ratio_args(cls, what, X, num, den, eps, clamp):
+        """the arguments of a rule on a stored pair (dnmf_csr_ratio_update, dnmf_is_ratio_update)"""
+        _req = cls._fam_req
+        _req(X, "X"); _req(num, "num"); _req(den, "den")
+        if tuple(num.shape) != tuple(X.shape) or tuple(den.shape) != tuple(X.shape) or _ld(num) != _ld(den):
+            raise ValueError("%s: X %s, num %s, den %s" % (what, tuple(X.shape), tuple(num.shape), tuple(den.shape)))
+        r, c = X.shape
+        return X.data_ptr(), r, c, _ld(X), num.data_ptr(), den.data_ptr(), _ld(num), float(eps), int(bool(clamp)), _stream()
+
+    # ---- ONE implementation of both families.  `p` is the family ('is' or 'beta'; the library prefix is p + _fam_sfx), `mode` what
+    # follows `eps` in every call (() or (beta,)); the rank message is _is_ranks / _beta_ranks.  The public is_* and beta_* methods below are
+    # its callers.
+    def _fam(self, p, what, A, W, H, eps, mode, pair=None, ws="ws_bytes"):
+        return self._pair_args(what, A, W, H, eps, _fn(p + self._fam_sfx + "_" + ws, ""), getattr(self, "_%s_ranks" % p), mode=mode, pair=pair)
+
+    def _fam_pair(self, p, mode, side, A, W, H, eps, num, den):
+        head, tail = self._fam(p, p + " pair", A, W, H, eps, mode, pair=(side, num, den))
+        check(_fn(p + self._fam_sfx + ("_aht_pair" if side == "w" else "_wta_pair"), "")(*head, *tail))
+        return num, den
+
+    def _fam_update(self, p, mode, side, A, W, H, eps, *clamp):
+        what = "%s%s_update_%s" % (p, self._fam_sfx, side)
+        head, tail = self._fam(p, what, A, W, H, eps, mode)
+        check(_fn(what, "")(*head, *clamp, *tail))
+        return W if side == "w" else H
+
+    def _fam_ratio_update(self, p, mode_of, X, num, den, eps, clamp):
+        a = self._ratio_args(p + "_ratio_update", X, num, den, eps, clamp)
+        check(_fn(p + self._fam_sfx + "_ratio_update", "")(*a[:8], *mode_of(), *a[8:]))
+        return X
+
+    def _fam_divergence(self, p, mode, A, W, H, eps):
+        head, tail = self._fam(p, p + "_divergence", A, W, H, eps, mode)
+        out = torch.empty(1, dtype=torch.float64, device=A.device)
+        check(_fn(p + self._fam_sfx + "_divergence", "")(*head, out.data_ptr(), *tail))
+        return out
+
+    def _fam_column_div(self, p, mode, nout, A, W, H, eps):
+        head, tail = self._fam(p, p + "_column_div", A, W, H, eps, mode, ws="column_div_ws_bytes")
+        out = torch.empty(nout, A.shape[1], dtype=torch.float64, device=A.device)
+        check(_fn(p + "_column_div", "")(*head, *(o.data_ptr() for o in out), *tail))
+        return out
+
+    def _fam_fit(self, p, mode, A, W, H, eps, w_update, itr):
+        return self._pair_fit(p + "_fit", _fn(p + "_mu_fit", ""), A, W, H, eps, _fn(p + "_ws_bytes_fit", ""),
+                              getattr(self, "_%s_ranks" % p), mode, w_update, itr)
+
+    @classmethod
+    def _beta_mode(cls, beta):
+        beta = float(beta)
+        if not cls.BETA_RANGE[0] <= beta <= cls.BETA_RANGE[1]:
+            raise ValueError("beta = %r is outside the accepted range %g <= beta <= %g" % ((beta,) + cls.BETA_RANGE))
+        return (beta,)
+
+    def is_aht_pair(self, A, W, H, eps, buf):
+        """buf = [num | den], each m x k: (A . R . R) H^T and R H^T"""
+        return self._fam_pair("is", (), "w", A, W, H, eps, *self._halves(buf, tuple(W.shape)))
+
+    def is_wta_pair(self, A, W, H, eps, buf):
+        """buf = [num | den], each k x n: W^T (A . R . R) and W^T R"""
+        return self._fam_pair("is", (), "h", A, W, H, eps, *self._halves(buf, tuple(H.shape)))
+
+    def is_pair_into(self, side, A, W, H, eps, num, den):
+        """the same pair into two views of the caller's (one leading dimension, any pitch): side 'w' (m x k) or 'h' (k x n)"""
+        return self._fam_pair("is", (), side, A, W, H, eps, num, den)
+
+    def is_update_w(self, A, W, H, eps):
+        """W <- W * sqrt(num / (den + eps)): the pass, then the rule on its partial sums (this rank's W rows see all their columns)"""
+        return self._fam_update("is", (), "w", A, W, H, eps)
+
+    def is_update_h(self, A, W, H, eps, clamp=False):
+        """H <- H * sqrt(num / (den + eps)), max(., eps) with `clamp` (this rank's H columns see all their rows)"""
+        return self._fam_update("is", (), "h", A, W, H, eps, int(bool(clamp)))
+
+    def is_ratio_update(self, X, num, den, eps, clamp=False):
+        """X <- X * sqrt(num / (den + eps)), max(., eps) with `clamp`: the rule on a pair that was summed over the ranks"""
+        return self._fam_ratio_update("is", tuple, X, num, den, eps, clamp)
+
+    def is_divergence(self, A, W, H, eps):
+        """D_IS(A | W H + eps) = sum (q - log q - 1), q = A / (W H + eps), over this block: one device double (stored, not
+        accumulated: two calls are bit-identical)"""
+        return self._fam_divergence("is", (), A, W, H, eps)
+
+    def beta_aht_pair(self, A, W, H, eps, beta, buf):
+        """buf = [num | den], each m x k: (A . P) H^T and (S' . P) H^T"""
+        return self._fam_pair("beta", self._beta_mode(beta), "w", A, W, H, eps, *self._halves(buf, tuple(W.shape)))
+
+    def beta_wta_pair(self, A, W, H, eps, beta, buf):
+        """buf = [num | den], each k x n: W^T (A . P) and W^T (S' . P)"""
+        return self._fam_pair("beta", self._beta_mode(beta), "h", A, W, H, eps, *self._halves(buf, tuple(H.shape)))
+
+    def beta_pair_into(self, side, A, W, H, eps, beta, num, den):
+        """the same pair into two views of the caller's (one leading dimension, any pitch): side 'w' (m x k) or 'h' (k x n)"""
+        return self._fam_pair("beta", self._beta_mode(beta), side, A, W, H, eps, num, den)
+
+    def beta_update_w(self, A, W, H, eps, beta):
+        """W <- W * (num / (den + eps))^gamma: the pass, then the rule on its partial sums (this rank's W rows see all their columns)"""
+        return self._fam_update("beta", self._beta_mode(beta), "w", A, W, H, eps)
+
+    def beta_update_h(self, A, W, H, eps, beta, clamp=False):
+        """H <- H * (num / (den + eps))^gamma, max(., eps) with `clamp` (this rank's H columns see all their rows)"""
+        return self._fam_update("beta", self._beta_mode(beta), "h", A, W, H, eps, int(bool(clamp)))
+
+    def beta_ratio_update(self, X, num, den, eps, beta, clamp=False):
+        """X <- X * (num / (den + eps))^gamma, max(., eps) with `clamp`: the rule on a pair that was summed over the ranks"""
+        return self._fam_ratio_update("beta", lambda: self._beta_mode(beta), X, num, den, eps, clamp)
+
+    def beta_divergence(self, A, W, H, eps, beta):
+        """D_beta(A | W H + eps) over this block: one device double (stored, not accumulated: two calls are bit-identical)"""
+        return self._fam_divergence("beta", self._beta_mode(beta), A, W, H, eps)
+
+
+class HipOps(_DivFamily):
     """The operator set the update choreography (dist_nmf.py) is written against."""
 
     name = "hip"
@@ -691,121 +856,6 @@ class HipOps:
 
     _is_ranks = "norm='is' with k = %d: the Itakura-Saito kernels serve 1 <= k <= 128"
 
-    # ---- what the dense pair rules share (dnmf_is_* here, dnmf_masked_* in HipMaskedOps; the sparse set uses the last two)
-    @staticmethod
-    def _pair_args(what, T, W, H, eps, nbytes_fn, ranks, mode=(), pair=None):
-        """(A, W, H) checked against each other, the scratch `nbytes_fn` sizes (0: the rank is refused with `ranks`), and the
-        arguments every entry point of a dense pair rule starts with (`mode`: the masked rules' kl) and ends with.  pair = (side,
-        num, den): two views of the side's shape with one leading dimension, appended to the head."""
-        _req(T, "A"); _req(W, "W"); _req(H, "H")
-        m, n = T.shape
-        k = W.shape[1]
-        if tuple(W.shape) != (m, k) or tuple(H.shape) != (k, n):
-            raise ValueError("%s: shapes A %s, W %s, H %s do not match" % (what, tuple(T.shape), tuple(W.shape), tuple(H.shape)))
-        nbytes = nbytes_fn(int(m), int(n), int(k))
-        if nbytes == 0:
-            raise NotImplementedError(ranks % k)
-        ws = _scratch(nbytes, T.device)
-        head = (T.data_ptr(), m, n, _ld(T), W.data_ptr(), _ld(W), H.data_ptr(), _ld(H), int(k), float(eps)) + tuple(mode)
-        if pair is not None:
-            side, num, den = pair
-            _req(num, "num"); _req(den, "den")
-            want = (m, k) if side == "w" else (k, n)
-            if tuple(num.shape) != want or tuple(den.shape) != want or _ld(num) != _ld(den):
-                raise ValueError("%s: num %s and den %s must both be %s with one leading dimension" % (what, tuple(num.shape), tuple(den.shape), want))
-            head += (num.data_ptr(), den.data_ptr(), _ld(num))
-        return head, (ws.data_ptr(), ws.numel(), _stream())
-
-    def _pair_fit(self, what, fit_fn, T, W, H, eps, nbytes_fn, ranks, mode, w_update, itr):
-        """a whole fit under a dense pair rule as one library call: returns the device tensor [1][2] of its two squared norms"""
-        head, tail = self._pair_args(what, T, W, H, eps, nbytes_fn, ranks, mode)
-        sq = torch.empty(1, 2, dtype=torch.float64, device=T.device)
-        check(fit_fn(*head, int(bool(w_update)), int(itr), sq.data_ptr(), *tail))
-        return sq
-
-    @staticmethod
-    def _halves(buf, shape):
-        """[num | den]: the halves of one contiguous buffer (what ONE allreduce carries) as two views of `shape`"""
-        r, c = shape
-        if buf.numel() < 2 * r * c or not buf.is_contiguous() or buf.dtype != torch.float32:
-            raise ValueError("pair buffer: a contiguous float32 buffer of 2 x %d x %d elements is expected" % (r, c))
-        return buf[: r * c].view(r, c), buf[r * c: 2 * r * c].view(r, c)
-
-    @staticmethod
-    def _ratio_args(what, X, num, den, eps, clamp):
-        """the arguments of a rule on a stored pair (dnmf_csr_ratio_update, dnmf_is_ratio_update)"""
-        _req(X, "X"); _req(num, "num"); _req(den, "den")
-        if tuple(num.shape) != tuple(X.shape) or tuple(den.shape) != tuple(X.shape) or _ld(num) != _ld(den):
-            raise ValueError("%s: X %s, num %s, den %s" % (what, tuple(X.shape), tuple(num.shape), tuple(den.shape)))
-        r, c = X.shape
-        return X.data_ptr(), r, c, _ld(X), num.data_ptr(), den.data_ptr(), _ld(num), float(eps), int(bool(clamp)), _stream()
-
-    # ---- ONE implementation of both families.  `p` is the library prefix ('is' or 'beta'), `mode` what follows `eps` in every call
-    # (() or (beta,)); the rank message is _is_ranks / _beta_ranks.  The public is_* and beta_* methods below are its callers.
-    def _fam(self, p, what, A, W, H, eps, mode, pair=None, ws="ws_bytes"):
-        return self._pair_args(what, A, W, H, eps, _fn(p + "_" + ws, ""), getattr(self, "_%s_ranks" % p), mode=mode, pair=pair)
-
-    def _fam_pair(self, p, mode, side, A, W, H, eps, num, den):
-        head, tail = self._fam(p, p + " pair", A, W, H, eps, mode, pair=(side, num, den))
-        check(_fn(p + ("_aht_pair" if side == "w" else "_wta_pair"), "")(*head, *tail))
-        return num, den
-
-    def _fam_update(self, p, mode, side, A, W, H, eps, *clamp):
-        what = "%s_update_%s" % (p, side)
-        head, tail = self._fam(p, what, A, W, H, eps, mode)
-        check(_fn(what, "")(*head, *clamp, *tail))
-        return W if side == "w" else H
-
-    def _fam_ratio_update(self, p, mode_of, X, num, den, eps, clamp):
-        a = self._ratio_args(p + "_ratio_update", X, num, den, eps, clamp)
-        check(_fn(p + "_ratio_update", "")(*a[:8], *mode_of(), *a[8:]))
-        return X
-
-    def _fam_divergence(self, p, mode, A, W, H, eps):
-        head, tail = self._fam(p, p + "_divergence", A, W, H, eps, mode)
-        out = torch.empty(1, dtype=torch.float64, device=A.device)
-        check(_fn(p + "_divergence", "")(*head, out.data_ptr(), *tail))
-        return out
-
-    def _fam_column_div(self, p, mode, nout, A, W, H, eps):
-        head, tail = self._fam(p, p + "_column_div", A, W, H, eps, mode, ws="column_div_ws_bytes")
-        out = torch.empty(nout, A.shape[1], dtype=torch.float64, device=A.device)
-        check(_fn(p + "_column_div", "")(*head, *(o.data_ptr() for o in out), *tail))
-        return out
-
-    def _fam_fit(self, p, mode, A, W, H, eps, w_update, itr):
-        return self._pair_fit(p + "_fit", _fn(p + "_mu_fit", ""), A, W, H, eps, _fn(p + "_ws_bytes_fit", ""),
-                              getattr(self, "_%s_ranks" % p), mode, w_update, itr)
-
-    def is_aht_pair(self, A, W, H, eps, buf):
-        """buf = [num | den], each m x k: (A . R . R) H^T and R H^T"""
-        return self._fam_pair("is", (), "w", A, W, H, eps, *self._halves(buf, tuple(W.shape)))
-
-    def is_wta_pair(self, A, W, H, eps, buf):
-        """buf = [num | den], each k x n: W^T (A . R . R) and W^T R"""
-        return self._fam_pair("is", (), "h", A, W, H, eps, *self._halves(buf, tuple(H.shape)))
-
-    def is_pair_into(self, side, A, W, H, eps, num, den):
-        """the same pair into two views of the caller's (one leading dimension, any pitch): side 'w' (m x k) or 'h' (k x n)"""
-        return self._fam_pair("is", (), side, A, W, H, eps, num, den)
-
-    def is_update_w(self, A, W, H, eps):
-        """W <- W * sqrt(num / (den + eps)): the pass, then the rule on its partial sums (this rank's W rows see all their columns)"""
-        return self._fam_update("is", (), "w", A, W, H, eps)
-
-    def is_update_h(self, A, W, H, eps, clamp=False):
-        """H <- H * sqrt(num / (den + eps)), max(., eps) with `clamp` (this rank's H columns see all their rows)"""
-        return self._fam_update("is", (), "h", A, W, H, eps, int(bool(clamp)))
-
-    def is_ratio_update(self, X, num, den, eps, clamp=False):
-        """X <- X * sqrt(num / (den + eps)), max(., eps) with `clamp`: the rule on a pair that was summed over the ranks"""
-        return self._fam_ratio_update("is", tuple, X, num, den, eps, clamp)
-
-    def is_divergence(self, A, W, H, eps):
-        """D_IS(A | W H + eps) = sum (q - log q - 1), q = A / (W H + eps), over this block: one device double (stored, not
-        accumulated: two calls are bit-identical)"""
-        return self._fam_divergence("is", (), A, W, H, eps)
-
     is_nmfk = True                     # PyNMFk looks for this and `is_column_div`: the per-column statistic of a sweep under norm='is'
 
     def is_column_div(self, A, W, H, eps):
@@ -822,44 +872,7 @@ class HipOps:
     # ---- the beta-divergence, -2 <= beta <= 4 (csrc/dnmf_beta.h, dnmf_beta_*): dense float32 data, 1 <= k <= 128.  With S' = W H + eps and
     # P = S'^(beta - 2): num = (A . P) F, den = (S' . P) F (F = H^T / W), X <- X * (num / (den + eps))^gamma(beta).  `beta` follows `eps`
     beta_dtypes = (torch.float32,)     # the data types these operations take (PyNMF and the choreography refuse any other by name)
-    BETA_RANGE = (-2.0, 4.0)
-
     _beta_ranks = "norm='beta' with k = %d: the beta-divergence kernels serve 1 <= k <= 128"
-
-    @classmethod
-    def _beta_mode(cls, beta):
-        beta = float(beta)
-        if not cls.BETA_RANGE[0] <= beta <= cls.BETA_RANGE[1]:
-            raise ValueError("beta = %r is outside the accepted range %g <= beta <= %g" % ((beta,) + cls.BETA_RANGE))
-        return (beta,)
-
-    def beta_aht_pair(self, A, W, H, eps, beta, buf):
-        """buf = [num | den], each m x k: (A . P) H^T and (S' . P) H^T"""
-        return self._fam_pair("beta", self._beta_mode(beta), "w", A, W, H, eps, *self._halves(buf, tuple(W.shape)))
-
-    def beta_wta_pair(self, A, W, H, eps, beta, buf):
-        """buf = [num | den], each k x n: W^T (A . P) and W^T (S' . P)"""
-        return self._fam_pair("beta", self._beta_mode(beta), "h", A, W, H, eps, *self._halves(buf, tuple(H.shape)))
-
-    def beta_pair_into(self, side, A, W, H, eps, beta, num, den):
-        """the same pair into two views of the caller's (one leading dimension, any pitch): side 'w' (m x k) or 'h' (k x n)"""
-        return self._fam_pair("beta", self._beta_mode(beta), side, A, W, H, eps, num, den)
-
-    def beta_update_w(self, A, W, H, eps, beta):
-        """W <- W * (num / (den + eps))^gamma: the pass, then the rule on its partial sums (this rank's W rows see all their columns)"""
-        return self._fam_update("beta", self._beta_mode(beta), "w", A, W, H, eps)
-
-    def beta_update_h(self, A, W, H, eps, beta, clamp=False):
-        """H <- H * (num / (den + eps))^gamma, max(., eps) with `clamp` (this rank's H columns see all their rows)"""
-        return self._fam_update("beta", self._beta_mode(beta), "h", A, W, H, eps, int(bool(clamp)))
-
-    def beta_ratio_update(self, X, num, den, eps, beta, clamp=False):
-        """X <- X * (num / (den + eps))^gamma, max(., eps) with `clamp`: the rule on a pair that was summed over the ranks"""
-        return self._fam_ratio_update("beta", lambda: self._beta_mode(beta), X, num, den, eps, clamp)
-
-    def beta_divergence(self, A, W, H, eps, beta):
-        """D_beta(A | W H + eps) over this block: one device double (stored, not accumulated: two calls are bit-identical)"""
-        return self._fam_divergence("beta", self._beta_mode(beta), A, W, H, eps)
 
     beta_nmfk = True                   # PyNMFk looks for this and `beta_column_div`: the per-column statistic of a sweep under norm='beta'
 
@@ -1490,7 +1503,7 @@ for _name, _what in (("aht", "the product A H^T"), ("wta", "the product W^T A"),
 HIP_MASKED_OPS = HipMaskedOps()
 
 
-class HipOpsF64:
+class HipOpsF64(_DivFamily):
     """The operator set in float64 (csrc/dnmf_f64.hip: the fp64 matrix cores, one plain tile shape per kernel family).  The
     reference computes in the dtype of A_ij (pyDNMF.py:68): float64 data are factorised in float64, eps = 2.22e-16.  The same
     method surface as HipOps for the primitives the choreography (dist_nmf.py) sequences, plus the whole one-rank fit (`fit`); no
@@ -1511,6 +1524,18 @@ class HipOpsF64:
         if t.dim() != ndim or (t.numel() and t.stride(-1) != 1):
             raise ValueError("%s: must be %d-D row-major with unit inner stride" % (name, ndim))
         return t
+
+    # ---- Itakura-Saito and the beta-divergence, -2 <= beta <= 4, on float64 data (csrc/dnmf_f64_div.h, dnmf_is_f64_* / dnmf_beta_f64_*):
+    # the operations of _DivFamily -- is_ / beta_ {aht_pair, wta_pair, pair_into, update_w, update_h, ratio_update, divergence} with the
+    # signatures HipOps has -- on the fp64 matrix cores, 1 <= k <= 64.  No whole fit and no per-column statistic: the step loop runs, and
+    # PyNMFk under these norms stays with float32 data.
+    is_dtypes = beta_dtypes = (torch.float64,)
+    is_max_k = beta_max_k = 64         # the rank bound under these norms: PyNMF refuses beyond it before any kernel runs
+    _fam_sfx = "_f64"
+    _fam_dtype = torch.float64
+    _fam_req = _r
+    _is_ranks = "norm='is' with k = %d: the float64 Itakura-Saito kernels serve 1 <= k <= 64"
+    _beta_ranks = "norm='beta' with k = %d: the float64 beta-divergence kernels serve 1 <= k <= 64"
 
     @staticmethod
     def _ws(m, n, k, device):

@@ -274,8 +274,10 @@ class PyNMF:
             raise NotImplementedError("norm='%s' with bfloat16 storage of the data is not provided (float32 data only)" % norm)
         if (getattr(params, "gemm", None) or "fp32") != "fp32":
             raise NotImplementedError("norm='%s' with --gemm %s is not provided (fp32 arithmetic only)" % (norm, params.gemm))
-        # (an operator set names the data types its operations under the norm take, `is_dtypes` / `beta_dtypes`: the HIP kernels are float32)
-        if a_dtype not in (getattr(ops, norm + "_dtypes", ()) if ops is not None else (torch.float32,)):
+        # (an operator set names the data types its operations under the norm take, `is_dtypes` / `beta_dtypes`: float32 in the fp32 set,
+        #  float64 in the float64 set, none in the split set)
+        #  (ops None: the product's own sets, engine.ops_for -- the fp32 set for float32 data, the float64 set for float64 data)
+        if a_dtype not in (getattr(ops, norm + "_dtypes", ()) if ops is not None else (torch.float32, torch.float64)):
             raise NotImplementedError("norm='%s' with %s data is not provided (float32 data only); cast the block to float32"
                                       % (norm, str(a_dtype).replace("torch.", "")))
         method = str(method).lower()
@@ -285,8 +287,11 @@ class PyNMF:
         if p_r != 1 and p_c != 1:
             raise NotImplementedError("norm='%s' on a 2D grid (%d x %d) is not provided: use a 1D grid (p_r = 1 or p_c = 1)"
                                       % (norm, p_r, p_c))
-        if k > 128:
-            raise NotImplementedError("norm='%s' with k = %d is not provided: the %s kernels serve 1 <= k <= 128" % (norm, k, kernels))
+        # the rank bound is the operator set's, `<norm>_max_k` (the float64 pairs hold two accumulator sets: 64); float32 keeps 128
+        kmax = 128 if a_dtype != torch.float64 else (64 if ops is None else int(getattr(ops, norm + "_max_k", 128)))
+        if k > kmax:
+            raise NotImplementedError("norm='%s' with k = %d is not provided: the %s%s kernels serve 1 <= k <= %d"
+                                      % (norm, k, "float64 " if a_dtype == torch.float64 else "", kernels, kmax))
 
     @staticmethod
     def _weighted_refusals(norm, params, sparse, missing, a_dtype, ops, method, p_r, p_c):

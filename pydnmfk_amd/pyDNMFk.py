@@ -210,8 +210,10 @@ class PyNMFk:
             # first of all: the sweep asks one operation beyond a fit, the per-column divergence (under norm='beta' with the column's sum
             # of a^beta).  (The 'uniform' perturbation is multiplicative noise, which is the noise the Itakura-Saito divergence is the
             # likelihood of, and keeps positive data positive)
-            if ops is None:
-                from .engine import HIP_OPS as opset
+            if ops is None:                 # (the set PyNMF will take: float64 data run on the float64 set, which factorises under these norms but has no per-column divergence)
+                from .engine import HIP_OPS, HIP_OPS_F64
+                from .pyDNMF import storage_dtype
+                opset = HIP_OPS_F64 if not self._sparse and storage_dtype(A_ij, params) == torch.float64 else HIP_OPS
             else:
                 opset = ops
             # (under weights the statistic is the weighted pair's, checked above: the norm's own per-column divergence is not asked for)
