@@ -8,6 +8,12 @@ eps when i % 10 == 0 (after that step's update), and on the last step column-nor
 (copied to the current GPU; numpy arrays come back) or torch CUDA tensors (torch tensors come back).
 Everything numeric runs in libdnmf_hip.so; there is no CPU path.
 
+What kind of problem a fit is -- dense, sparse (pydnmfk_amd.sparse) or NaN-marked dense data (`params.missing`), the norm ('fro', 'kl',
+'is', 'beta' with `params.beta`), per-entry weights (`params.weights`) -- is decided ONCE, by `fit_kind()` below; PyNMF and PyNMFk both
+read that record (pyDNMFk.SWEEP_KINDS is keyed by it).  What each kind refuses is said, in its own words, by the `_*_checks` /
+`_*_refusals` methods; what each kind computes is described in DESIGN.md (its sections on sparse data, on missing entries, on the
+Itakura-Saito and beta-divergence norms and on per-entry weights) and on the methods `is_divergence` ... `weighted_column_divergence`.
+
 Differences from the reference, all deliberate and documented in DESIGN.md:
   * compute dtype follows the data, as in the reference (pyDNMF.py:68): float32 (the tuned path) or float64 (the fp64 matrix
     cores, engine.HipOpsF64: correctness first, one plain tile shape); `params.precision = 'bfloat16'` (or a
@@ -15,30 +21,15 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
     product in float32: the fit equals the float32 fit of the bf16-rounded data (BASELINE config 5);
   * method is 'mu' (fro / kl), 'hals' (fro) or 'bcd' (fro; float32 data with the fp32 operator set -- float64, bf16-stored A and
     --gemm bf16x6 raise NotImplementedError); init is 'rand' or 'nnsvd' (1D grids);
-  * sparse data (pydnmfk_amd.sparse) with `params.missing = 'unstored'`: an unstored entry is NOT OBSERVED instead of zero -- objective,
-    MU rules (fro / kl) and the reported error run over the stored positions only (1D grids, method 'mu'; DESIGN.md "Sparse data");
-  * dense float32 data with `params.missing = 'nan'`: an entry is observed iff it is not NaN (a zero is an observation) -- the same
-    masked objective, rules and error on the matrix cores (pydnmfk_amd.masked, csrc/dnmf_masked.h; method 'mu', 1D grids, k <= 128;
-    on one rank the whole fit is one library call, dnmf_masked_mu_fit; `column_err` runs over the observed positions).
-    Without `params.missing` dense data are not scanned for NaN;
-  * `params.norm = 'is'` (or 'itakura-saito'): the Itakura-Saito divergence by the majorisation-minimisation MU rule (csrc/dnmf_is.h;
-    no counterpart in the reference) -- strictly positive dense float32 data, method 'mu', 1D grids, k <= 128; on one rank the whole fit
-    is one library call, dnmf_is_mu_fit; `fit()` still returns the Frobenius relative error, `is_divergence()` reports the objective and
-    `is_column_divergence()` its mean per entry column by column (the per-column statistic of PyNMFk under this norm);
-  * `params.norm = 'beta'` with `params.beta` in [-2, 4]: the beta-divergence by the same kind of rule (csrc/dnmf_beta.h; scikit-learn's
-    beta_loss=<float>) under the same restrictions; data strictly positive for beta <= 0, non-negative for beta > 0; beta = 0 IS norm='is'
-    (the same bits), beta = 1 and 2 are the KL and Frobenius objectives under this family's rule, not the reference's; one library call
-    per fit on one rank (dnmf_beta_mu_fit); `beta_divergence()` reports the objective and `beta_column_divergence()` each column's
-    divergence over its sum of a^beta (scale-invariant for every beta: the per-column statistic of PyNMFk under this norm);
-  * `params.weights = V`: per-entry weights, a non-negative float32 array of the block's shape -- the objective is sum v d(a | W H) with d
-    of the norm (fro / kl / is / beta), the rule the norm's own with both halves of its pair scaled by V (csrc/dnmf_weighted.h; method
-    'mu', 1D grids, k <= 128, prune=False).  v = 0 means NOT OBSERVED: the data may hold anything there (NaN included), so
-    weights = ~isnan(A) is masked IS / beta.  `fit()` returns the weighted relative error sqrt(sum v (a - s)^2 / sum v a^2);
-    `weighted_divergence()` reports the objective; one library call per fit on one rank (dnmf_weighted_mu_fit);
+  * the kinds the reference does not have: sparse data, missing entries (`params.missing = 'unstored'` / 'nan'), the norms 'is' and
+    'beta', and `params.weights`; `fit()` returns the Frobenius relative error under every norm (the weighted one under weights), and
+    `divergence()` / `column_statistic()` report the objective and the per-column statistic of the fit's own family;
   * `prune=True` (the reference's default when the attribute is absent) drops all-zero rows / columns before the
     iterations and scatters the factors back afterwards.  numpy callers get float64 factors back in that case, exactly
     as from the reference (its unprune scatters into np.zeros, utils.py:195,198); tensor callers keep float32 on the GPU.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -76,21 +67,58 @@ _MASKS = ("row_zero_idx_x", "col_zero_idx_x", "row_zero_idx_w", "col_zero_idx_h"
 _NATIVE_FITS = (("mu", "fro"), ("mu", "kl"), ("hals", "fro"), ("bcd", "fro"), ("mu", "is"), ("mu", "beta"))
 BETA_RANGE = (-2.0, 4.0)             # where the value of (W H + eps)^(beta - 2) at a padded position is finite in float32 (csrc/dnmf_beta.h)
 
+# form: 'dense' | 'sparse' | 'nan' (dense data, NaN = not observed);  norm: as the fit runs it, after the renaming;  beta: params.beta when
+# the norm was handed over as 'beta' (0.0 where that was renamed to 'is'), else None;  weighted: params.weights is set;  family: whose
+# divergence and per-column statistic the fit reports -- 'weighted' before 'is' / 'beta' (the norm's own would read the entries under
+# zero weights), None for fro / kl;  batchable: whether fits of this kind may run as one batched whole-fit call (PyNMF.fit_batch)
+FitKind = namedtuple("FitKind", ("form", "norm", "beta", "weighted", "family", "batchable"))
+
+
+def fit_kind(A_ij, params):
+    """What kind of problem a fit of `A_ij` under `params` is, as a FitKind: decided once per fit, here, for PyNMF and PyNMFk alike.
+    Renames the norm on the bag (`params.norm`): 'itakura-saito' -> 'is', and 'beta' with params.beta = 0 -> 'is'.  Refuses nothing:
+    what a kind does not take is refused by the classes, in their order and their words -- a `params.beta` that is missing (nan here)
+    or out of range among it (`PyNMF._beta_value`, which PyNMFk calls only after it has told an operator set without the sweep's
+    operations so); such a value is not 0 and stays under norm 'beta'."""
+    from .sparse import is_sparse_input
+    form = "sparse" if is_sparse_input(A_ij) else "nan" if getattr(params, "missing", None) == "nan" else "dense"
+    norm, beta = var_init(params, 'norm', default='kl'), None        # :70
+    if str(norm).lower() == 'beta':
+        beta = float(getattr(params, "beta", None) if getattr(params, "beta", None) is not None else "nan")
+        # beta = 0 IS Itakura-Saito: handed to that path (its kernels, its bits), the way 'itakura-saito' is renamed
+        norm = params.norm = 'is' if beta == 0.0 else 'beta'
+    if str(norm).lower() in ('is', 'itakura-saito'):
+        norm = params.norm = 'is'
+    weighted = getattr(params, "weights", None) is not None
+    family = "weighted" if weighted else norm if norm in ("is", "beta") else None
+    # (no batched sparse, masked, weighted, Itakura-Saito or beta-divergence entry point: one problem per call)
+    return FitKind(form, norm, beta, weighted, family, form == "dense" and family is None)
+
+
+def _need_gpu(ops, A_ij, who, accepted="a numpy array"):
+    """No operator set was handed over (`ops` is None): the product's own run on the GPU, and there is no CPU path.  `who`: the class
+    the message names; `accepted`: what it takes next to a CUDA tensor."""
+    if ops is not None:
+        return
+    if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda:
+        raise TypeError("%s: A_ij is a CPU tensor; pass a CUDA tensor or %s (no CPU fallback)" % (who, accepted))
+    if not torch.cuda.is_available():
+        raise RuntimeError("%s: no GPU visible; the MI355X engine has no CPU fallback" % who)
+
 
 class PyNMF:
     """Reference pyDNMF.py:6-239 (the MU path of it)."""
 
     def __init__(self, A_ij, factors=None, save_factors=False, params=None, ops=None):
-        from .sparse import is_sparse_input
-        self._sparse = is_sparse_input(A_ij)
+        kind = self.kind = fit_kind(A_ij, params)
+        self._sparse, self._masked_dense = kind.form == "sparse", kind.form == "nan"
+        self.norm, self.beta, self._weighted = kind.norm, kind.beta, kind.weighted
+        self._is, self._beta = kind.norm == 'is', kind.norm == 'beta'
         # (sparse data: scipy input is numpy I/O, torch sparse tensors and SparseBlocks get CUDA tensors back)
         self._numpy_io = not (isinstance(A_ij, torch.Tensor) or getattr(A_ij, "is_sparse_block", False))
         self.ops = ops
+        _need_gpu(ops, None if self._sparse else A_ij, "PyNMF")     # (a sparse CPU tensor is taken: SparseBlock.from_any copies it over)
         if ops is None:
-            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda and not self._sparse:
-                raise TypeError("PyNMF: A_ij is a CPU tensor; pass a CUDA tensor or a numpy array (no CPU fallback)")
-            if not torch.cuda.is_available():
-                raise RuntimeError("PyNMF: no GPU visible; the MI355X engine has no CPU fallback")
             device = A_ij.device if isinstance(A_ij, torch.Tensor) and A_ij.is_cuda or getattr(A_ij, "is_sparse_block", False) \
                 else torch.device("cuda", torch.cuda.current_device())
         else:
@@ -107,7 +135,6 @@ class PyNMF:
         else:
             self.a_dtype = storage_dtype(A_ij, params)
         self.c_dtype = torch.float64 if self.a_dtype == torch.float64 else torch.float32      # factors, products, eps
-        self._masked_dense = (missing == "nan")
         if self._sparse:
             from .sparse import SparseBlock
             # (missing='unstored': a stored zero is an observation and stays stored; the block carries the meaning from here on)
@@ -132,18 +159,9 @@ class PyNMF:
         self.rank = self.comm1.rank
         self.eps = float(np.finfo(np.float64 if self.c_dtype == torch.float64 else np.float32).eps)   # pyDNMF.py:68
         self.params.eps = self.eps
-        self.norm = var_init(self.params, 'norm', default='kl')     # :70
         self.method = var_init(self.params, 'method', default='mu')
-        self.beta = None
-        if str(self.norm).lower() == 'beta':
-            self.beta = self._beta_value(self.params)
-            # beta = 0 IS Itakura-Saito: handed to that path (its kernels, its bits), the way 'itakura-saito' is renamed
-            self.norm = self.params.norm = 'is' if self.beta == 0.0 else 'beta'
-        if str(self.norm).lower() in ('is', 'itakura-saito'):
-            self.norm = self.params.norm = 'is'
-        self._is = (self.norm == 'is')
-        self._beta = (self.norm == 'beta')
-        self._weighted = getattr(self.params, "weights", None) is not None
+        if kind.beta is not None:
+            self._beta_value(self.params)
         self.V_ij = None
         if hasattr(self.params, "weights_block"):                   # (the bag may have served a weighted fit before)
             del self.params.weights_block
@@ -500,16 +518,7 @@ class PyNMF:
             raise NotImplementedError("method '%s' is not part of the MI355X engine (mu / hals / bcd)" % self.method)
         ops = self._ops()
         if self._whole_fit_ok(ops):
-            # one rank: the whole loop below -- steps, clamps, normalisation, both squared norms -- is ONE library call
-            # (dnmf_*_fit, csrc/dnmf_fit.hip): no Python, no ctypes call and no host synchronisation inside the fit
-            if self._weighted:                                      # dnmf_weighted_mu_fit
-                sq = ops.weighted_fit(self.A_ij, self.V_ij, self.W_i, self.H_j, self.eps, self.norm, self.beta or 0.0, self.W_update, self.itr)
-            elif self._beta:                                        # dnmf_beta_mu_fit
-                sq = ops.beta_fit(self.A_ij, self.W_i, self.H_j, self.eps, self.beta, self.W_update, self.itr)
-            else:
-                sq = ops.fit(self.method, self.norm, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr,
-                             column_sweep=(getattr(self.params, "hals_sweep", None) == "columns"))
-            return self._finish(sq[0])
+            return self._finish(self._whole_fit(ops)[0])
         # bcd: ONE trip with i = itr - 1 (pyDNMF.py:152) -- its update() runs all itr iterations (dist_nmf.py:83, params.itr)
         trips = range(self.itr - 1, self.itr) if self.method.lower() == 'bcd' else range(self.itr)
         for i in trips:
@@ -532,21 +541,29 @@ class PyNMF:
         (anything else keeps the step loop, which raises the reference's messages for invalid pairs).  `params.fit_loop =
         'python'` keeps the step loop (A/B runs, tests of the per-step API).  A NaN-marked block (missing='nan') has one with the
         'hip-masked' set: dnmf_masked_mu_fit, the launches of the step loop in its order (one problem per call: never batched)."""
-        if (self._is or self._beta or self._weighted) and getattr(ops, "name", "") != "hip":
+        if not (self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(self.params, "fit_loop", None) != "python"
+                and not getattr(self.params, "native_always", False)):
+            return False
+        name, method, norm = getattr(ops, "name", ""), str(self.method).lower(), str(self.norm).lower()
+        if self.kind.family is not None and name != "hip":
             return False                                            # (dnmf_is_mu_fit / dnmf_beta_mu_fit / dnmf_weighted_mu_fit live in the fp32 operator set only)
         if self._weighted:                                          # dnmf_weighted_mu_fit: one problem per call, every norm it serves
-            return (self.p == 1 and self.topo == '1d' and self.itr >= 1 and hasattr(ops, "weighted_fit")
-                    and getattr(self.params, "fit_loop", None) != "python" and not getattr(self.params, "native_always", False))
+            return hasattr(ops, "weighted_fit")
         if self._masked_dense:
-            return (self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") == "hip-masked" and hasattr(ops, "fit")
-                    and str(self.method).lower() == "mu" and str(self.norm).lower() in ("fro", "kl")
-                    and getattr(self.params, "fit_loop", None) != "python" and not getattr(self.params, "native_always", False))
-        return (not self._sparse and self.p == 1 and self.topo == '1d' and self.itr >= 1 and getattr(ops, "name", "") in ("hip", "hip-f64") and hasattr(ops, "fit")
-                and not (getattr(ops, "name", "") == "hip-f64" and self.k > 128)
-                and (str(self.method).lower(), str(self.norm).lower()) in _NATIVE_FITS
-                and not (str(self.method).lower() == "bcd" and (getattr(ops, "name", "") != "hip" or self.a_dtype != torch.float32))
-                and getattr(self.params, "fit_loop", None) != "python"
-                and not getattr(self.params, "native_always", False))
+            return name == "hip-masked" and hasattr(ops, "fit") and method == "mu" and norm in ("fro", "kl")
+        return (not self._sparse and name in ("hip", "hip-f64") and hasattr(ops, "fit") and not (name == "hip-f64" and self.k > 128)
+                and (method, norm) in _NATIVE_FITS and not (method == "bcd" and (name != "hip" or self.a_dtype != torch.float32)))
+
+    def _whole_fit(self, ops):
+        """What runs where `_whole_fit_ok`: the whole loop of `_fit_once` -- steps, clamps, normalisation, both squared norms -- as ONE
+        library call (dnmf_*_fit, csrc/dnmf_fit.hip): no Python, no ctypes call and no host synchronisation inside the fit.  Returns the
+        device pairs {sum (A - W H)^2, sum A^2}, one per problem."""
+        if self._weighted:                                          # dnmf_weighted_mu_fit
+            return ops.weighted_fit(self.A_ij, self.V_ij, self.W_i, self.H_j, self.eps, self.norm, self.beta or 0.0, self.W_update, self.itr)
+        if self._beta:                                              # dnmf_beta_mu_fit
+            return ops.beta_fit(self.A_ij, self.W_i, self.H_j, self.eps, self.beta, self.W_update, self.itr)
+        return ops.fit(self.method, self.norm, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr,
+                       column_sweep=(getattr(self.params, "hals_sweep", None) == "columns"))
 
     def _finish(self, sq):
         """The end of the last iteration (pyDNMF.py:158-166, :173-181): error, un-pruning, save.  `sq`: the device pair
@@ -600,7 +617,7 @@ class PyNMF:
         f0 = fits[0] if fits else None
 
         def same(f):
-            return (not f._masked_dense and not f._is and not f._beta and not f._weighted and f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
+            return (f.kind.batchable and f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
                     and f.A_ij.dtype == f0.A_ij.dtype and f.A_ij.device == f0.A_ij.device and f.W_i.shape == f0.W_i.shape
                     and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k) ==
                     (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k))
@@ -711,41 +728,73 @@ class PyNMF:
                 row[c0:c0 + ncol] = x
         return col
 
-    def _norm_op(self, norm, op, caller):
-        """ops.<norm>_<op>(A, W, H, eps[, beta]) on this block and its current factors, for the norm this fit runs ('is' or 'beta'); a
-        fit under another norm is refused in `caller`'s name"""
-        if not (self._is if norm == 'is' else self._beta):
+    def _family_op(self, family, op, caller):
+        """ops.<family>_<op> on this block and its CURRENT factors -- (A, W, H, eps[, beta]) for the norms 'is' and 'beta', (A, V, W, H,
+        eps, norm, beta) for 'weighted' --; a fit that does not run that norm, or has no weights, is refused in `caller`'s name"""
+        if family == 'weighted' and not self._weighted:
+            raise ValueError("%s: this fit has no params.weights" % caller)
+        if family != 'weighted' and not (self._is if family == 'is' else self._beta):
             raise ValueError("%s: this fit runs norm='%s'; the divergence is reported under norm='%s'%s"
-                             % (caller, self.norm, norm,
-                                " (beta = 0 is norm='is': %s())" % caller.replace("beta_", "is_") if norm == 'beta' and self._is else ""))
+                             % (caller, self.norm, family,
+                                " (beta = 0 is norm='is': %s())" % caller.replace("beta_", "is_") if family == 'beta' and self._is else ""))
         W, H = self._block_factors()
-        return getattr(self._ops(), "%s_%s" % (norm, op))(self.A_ij, W, H, self.eps, *((self.beta,) if norm == 'beta' else ()))
+        fn = getattr(self._ops(), "%s_%s" % (family, op))
+        if family == 'weighted':
+            return fn(self.A_ij, self.V_ij, W, H, self.eps, self.norm, self.beta or 0.0)
+        return fn(self.A_ij, W, H, self.eps, *((self.beta,) if family == 'beta' else ()))
 
-    def _divergence(self, norm):
-        d = self._norm_op(norm, "divergence", norm + "_divergence")
+    def _total(self, family, caller):
+        """the family's divergence of the current factors, summed over the grid"""
+        d = self._family_op(family, "divergence", caller)
         self.comm1.allreduce_(d)
         return float(d.cpu())
+
+    def _columns(self, family, caller):
+        """the family's per-column sums over the GLOBAL n columns, [div] or [num | den], float64 on the device: each rank fills its own
+        column range with its sums over its own rows, ONE allreduce carries all of them (row shards add partial sums, column shards fill
+        disjoint ranges)"""
+        sums = self._family_op(family, "column_div", caller)
+        col = self._global_columns(*(sums if isinstance(sums, (tuple, list)) else (sums,)))
+        self.comm1.allreduce_(col)
+        return col
+
+    @staticmethod
+    def _ratio(col):
+        """num / den of [num | den] on the host; nan where the column has no scale to divide by"""
+        col = col.cpu().numpy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(col[1] > 0.0, col[0] / col[1], np.nan)
+
+    def divergence(self):
+        """The objective of this fit's family (`fit_kind`): `weighted_divergence()` under params.weights, else `is_divergence()` /
+        `beta_divergence()` under those norms.  A fit under fro / kl without weights reports none: ValueError."""
+        if self.kind.family is None:
+            raise ValueError("divergence: this fit runs norm='%s' without params.weights; a divergence is reported under norm='is', "
+                             "norm='beta' and under params.weights" % self.norm)
+        return getattr(self, self.kind.family + "_divergence")()
+
+    def column_statistic(self):
+        """The per-column statistic of this fit's family, what an NMFk sweep takes as `L_err`: `weighted_column_divergence()` under
+        params.weights, else `is_column_divergence()` / `beta_column_divergence()` under those norms, else `column_err()`."""
+        if self.kind.family is None:
+            return self.column_err()
+        return getattr(self, self.kind.family + "_column_divergence")()
 
     def is_divergence(self):
         """D_IS(A | W H + eps) = sum (q - log q - 1), q = A / (W H + eps), of the CURRENT factors, summed over the grid (norm='is':
         1D grids, where every rank's block meets its own W rows and H columns).  The objective the Itakura-Saito rule does not
         increase; `fit()` keeps returning the Frobenius relative error, as it does for norm='kl'."""
-        return self._divergence('is')
+        return self._total('is', "is_divergence")
 
     def beta_divergence(self):
         """D_beta(A | W H + eps) of the CURRENT factors, summed over the grid (norm='beta': 1D grids, where every rank's block meets its own
         W rows and H columns).  The objective the rule does not increase; `fit()` keeps returning the Frobenius relative error."""
-        return self._divergence('beta')
+        return self._total('beta', "beta_divergence")
 
     def weighted_divergence(self):
         """The weighted objective sum v d(a | s') of the CURRENT factors over v > 0, summed over the grid: d of the fit's norm ('kl', 'is',
         'beta' with params.beta; s' = W H + eps); under 'fro' half of sum v (a - W H)^2.  What the weighted rule does not increase."""
-        if not self._weighted:
-            raise ValueError("weighted_divergence: this fit has no params.weights")
-        W, H = self._block_factors()
-        d = self._ops().weighted_divergence(self.A_ij, self.V_ij, W, H, self.eps, self.norm, self.beta or 0.0)
-        self.comm1.allreduce_(d)
-        return float(d.cpu())
+        return self._total('weighted', "weighted_divergence")
 
     def weighted_column_divergence(self):
         """The weighted objective of the CURRENT factors column by column, over the GLOBAL n columns and over v > 0 only, each divided by
@@ -754,15 +803,8 @@ class PyNMF:
         under a column's scale and under the scale of its weights; what an NMFk sweep under weights takes where `column_err()` stands
         (which reads the entries under zero weights).  A column without a positive weight, or without scale, gives nan.  The scheme of
         `beta_column_divergence()`: each rank fills its own column range of [num | den], ONE float64 allreduce carries both."""
-        if not self._weighted:
-            raise ValueError("weighted_column_divergence: this fit has no params.weights")
-        W, H = self._block_factors()
-        col = self._global_columns(*self._ops().weighted_column_div(self.A_ij, self.V_ij, W, H, self.eps, self.norm, self.beta or 0.0))
-        self.comm1.allreduce_(col)
-        col = col.cpu().numpy()
-        with np.errstate(divide="ignore", invalid="ignore"):
-            stat = np.where(col[1] > 0.0, col[0] / col[1], np.nan)
-            return np.sqrt(stat) if str(self.norm).lower() == 'fro' else stat
+        stat = self._ratio(self._columns('weighted', "weighted_column_divergence"))
+        return np.sqrt(stat) if str(self.norm).lower() == 'fro' else stat
 
     def is_column_divergence(self):
         """The Itakura-Saito divergence of the CURRENT factors column by column, over the GLOBAL n columns, each divided by the global row
@@ -770,9 +812,7 @@ class PyNMF:
         What an NMFk sweep under norm='is' takes where the Frobenius `column_err()` stands (which weights the columns by their scale);
         `column_err()` itself is unchanged under every norm.  Its scheme: each rank fills its own column range with its sums over its own
         rows, one float64 allreduce (row shards add partial sums, column shards fill disjoint ranges), then the division."""
-        col = self._global_columns(self._norm_op('is', "column_div", "is_column_divergence"))[0]
-        self.comm1.allreduce_(col)
-        return (col / float(self.params.m)).cpu().numpy()
+        return (self._columns('is', "is_column_divergence")[0] / float(self.params.m)).cpu().numpy()
 
     def beta_column_divergence(self):
         """The beta-divergence of the CURRENT factors column by column, over the GLOBAL n columns, each divided by the column's sum of
@@ -783,11 +823,7 @@ class PyNMF:
         no scale to divide by: nan, as from `column_err()`.  The scheme of `is_column_divergence()`: each rank fills its own column
         range of both arrays with its sums over its own rows, one float64 allreduce (row shards add partial sums, column shards fill
         disjoint ranges), then the ratio."""
-        col = self._global_columns(*self._norm_op('beta', "column_div", "beta_column_divergence"))   # [div | pw]: ONE allreduce carries both
-        self.comm1.allreduce_(col)
-        col = col.cpu().numpy()
-        with np.errstate(divide="ignore", invalid="ignore"):
-            return np.where(col[1] > 0.0, col[0] / col[1], np.nan)
+        return self._ratio(self._columns('beta', "beta_column_divergence"))   # [div | pw]
 
     def column_err(self):
         """pyDNMF.py:221-239: per-column relative error sqrt(sum_i (A - W H)^2 / sum_i A^2) over the GLOBAL n columns

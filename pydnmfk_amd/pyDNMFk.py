@@ -11,25 +11,16 @@ Differences: statistics are kept in memory for the p-value analysis (and written
 h5py exists, else npz); no plots are drawn (plot_results is out of scope).  `params.hall_layout = 'aligned'` (not the
 default) stacks the perturbations' H matrices as Hall[:, :, p] = H_p; the default 'reference' reproduces the reference's
 vstack + C-order reshape (pyDNMFk.py:236-237), whose fibres mix perturbations -- it only seeds the regression fit.
-Sparse input is swept as a SparseBlock (`SparseSweep`); dense float32 input with `params.missing = 'nan'` is swept as it is, NaN = not
-observed: the raw array is kept, every perturbed copy keeps its NaNs, and the per-column error runs over the observed positions.
-`params.norm = 'is'` (strictly positive dense float32 data, 'uniform' sampling -- multiplicative noise, the noise the Itakura-Saito
-divergence is the likelihood of --, what PyNMF refuses under the norm is refused at construction): the per-column statistic `L_err` is
-the mean divergence per entry of each column (PyNMF.is_column_divergence) instead of the scale-dependent Frobenius column error, and the
-statistics gain 'is_div' (per perturbation) and 'avgDiv'; recon_err, avgErr and AIC keep their Frobenius definitions.
-`params.norm = 'beta'` with `params.beta` in [-2, 4] is swept likewise (beta = 0 IS norm='is' and takes that path): data strictly positive
-for beta <= 0 and non-negative for beta > 0, checked once; 'poisson' sampling for beta > 0 only; `L_err` is the divergence of each column
-over the column's sum of a^beta (PyNMF.beta_column_divergence: scale-invariant for every beta; the Itakura-Saito statistic at beta = 0,
-half the squared Frobenius column error at beta = 2); the statistics gain 'beta_div' (per perturbation), 'avgDiv' and 'beta'.
-`params.weights` (per-entry weights V >= 0 of the block's shape, norms fro / kl / is / beta; what PyNMF refuses under weights is refused at
-construction): the weights stay fixed over the sweep and only the data are perturbed -- 'uniform' multiplies the array as it is, so what
-lies under a zero weight stays unread; 'poisson' draws from rates zeroed where v = 0 --, the sign condition of is / beta is checked where
-v > 0 only, the fits run one by one, `L_err` is PyNMF.weighted_column_divergence (each column's weighted error or divergence over its own
-weighted scale, v > 0 only), recon_err / avgErr are the weighted relative error, and the statistics gain 'weighted_div' (per
-perturbation, PyNMF.weighted_divergence) and 'avgDiv' in place of 'is_div' / 'beta_div'.  One rank, the two 1D grids (each rank's
-params.weights is its block) and nmfk_split='perturbations'.
+What kind of data and objective a sweep runs over is decided once, by pyDNMF.fit_kind -- the record every PyNMF of the sweep reads as
+well --, and what a sweep of each kind asks of an operator set, reports per perturbation and takes as `L_err` is the table SWEEP_KINDS
+below.  Under every kind the sweep touches the data outside PyNMF.fit in two places, the perturbed copy (`sample`: NaN stays NaN, what
+lies under a zero weight stays unread, a sparse copy shares its pattern) and the per-column statistic (PyNMF.column_statistic); what
+PyNMF refuses for a kind is refused at construction, in its words, with the sweep's largest rank standing for k.  recon_err, avgErr and
+AIC keep their Frobenius definitions under every norm (the weighted relative error under weights).  DESIGN.md section 7 has the
+reasons kind by kind.
 """
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -37,7 +28,7 @@ from scipy.stats import wilcoxon
 
 from .data_io import data_write
 from .dist_clustering import custom_clustering
-from .pyDNMF import PyNMF
+from .pyDNMF import PyNMF, _need_gpu, fit_kind, storage_dtype
 from .utils import Checkpoint, var_init
 
 
@@ -184,71 +175,71 @@ def _np(x):
     return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
+# What a sweep asks of an operator set beyond a fit, kind by kind.  The rows that apply to a fit_kind(), each held to its check in this
+# order: 'weights' alone under params.weights (the statistic is the weighted pair's: the norm's own per-column divergence is not asked
+# for); else 'beta' where the norm was handed over as 'beta', then 'is' under norm 'is' (beta = 0 IS Itakura-Saito and is held to both);
+# else 'nan' or 'sparse' by the data's form; a plain sweep (dense data, fro / kl) asks nothing and has no row.  The last row that applies
+# is the sweep's own:
+#   ops, ops_f64  the product's operator set where the caller hands none over (engine.<name>; ops_f64 for float64 arrays: the set
+#                 PyNMF will take, which factorises under these norms but has no per-column divergence)
+#   flag, method  what PyNMFk looks for on the set: the capability flag and the per-column operation behind `L_err`
+#   div           the statistics key (and attribute) of the per-perturbation divergences, PyNMF.divergence(); with it go 'avgDiv' and,
+#                 under norm 'beta', 'beta'.  None: `L_err` is PyNMF.column_err() and the statistics gain nothing
+#   refusal       what a set without flag or method is told (%r: its name)
+SweepKind = namedtuple("SweepKind", ("ops", "ops_f64", "flag", "method", "div", "refusal"))
+SWEEP_KINDS = {
+    # the sweep asks one operation beyond a weighted fit, the per-column pair over v > 0 (column_err and the per-column divergences
+    # read the entries under zero weights and know no V)
+    "weights": SweepKind("HIP_OPS", "HIP_OPS", "weighted_nmfk", "weighted_column_div", "weighted_div",
+                         "PyNMFk with params.weights is not provided by operator set %r: rank estimation under per-entry "
+                         "weights needs a weighted per-column divergence (PyNMF takes the weights for one rank k)"),
+    # the sweep asks one operation beyond a fit, the per-column divergence (under norm='beta' with the column's sum of a^beta).  (The
+    # 'uniform' perturbation is multiplicative noise, which is the noise the Itakura-Saito divergence is the likelihood of, and keeps
+    # positive data positive)
+    "beta": SweepKind("HIP_OPS", "HIP_OPS_F64", "beta_nmfk", "beta_column_div", "beta_div",
+                      "PyNMFk with norm='beta' is not provided by operator set %r: rank estimation under a beta-divergence needs a "
+                      "per-column divergence (PyNMF factorises at a given k)"),
+    "is": SweepKind("HIP_OPS", "HIP_OPS_F64", "is_nmfk", "is_column_div", "is_div",
+                    "PyNMFk with norm='is' is not provided by operator set %r: rank estimation under the Itakura-Saito objective needs a "
+                    "per-column divergence (PyNMF factorises at a given k)"),
+    # as for a sparse block, the sweep touches A outside PyNMF.fit in the perturbed copy (NaN stays NaN through the multiplication) and
+    # in the per-column error, which must run over the observed positions
+    "nan": SweepKind("HIP_MASKED_OPS", "HIP_MASKED_OPS", "masked_nmfk", "column_err_sums", None,
+                     "PyNMFk with missing='nan' is not provided by operator set %r: rank estimation over NaN-marked "
+                     "data needs a masked per-column error (PyNMF factorises such data at a given k)"),
+    # the sweep touches A outside PyNMF.fit in two operations: the perturbed copy and the per-column error
+    "sparse": SweepKind("HIP_CSR_OPS", "HIP_CSR_OPS", "sparse_nmfk", "column_err_sums", None,
+                        "PyNMFk on sparse data is not provided by operator set %r: it has no per-column error and no "
+                        "perturbed copy of a sparse block (PyNMF factorises sparse data at a given k)"),
+}
+
+
+def _sweep_rows(kind):
+    if kind.weighted:
+        return ["weights"]
+    if kind.family is not None:         # (norm='is' and norm='beta' refuse missing= and sparse data by name in their setup, as weights do)
+        return ["beta"] * (kind.beta is not None) + ["is"] * (kind.norm == "is")
+    return [kind.form] * (kind.form != "dense")
+
+
 class PyNMFk:
     """pyDNMFk.py:70-299."""
 
     def __init__(self, A_ij, factors=None, params=None, ops=None):
-        from .sparse import is_sparse_input
-        self._weighted = getattr(params, "weights", None) is not None
-        if self._weighted:
-            # first of all: the sweep asks one operation beyond a weighted fit, the per-column pair over v > 0 (column_err and the
-            # per-column divergences read the entries under zero weights and know no V)
-            if ops is None:
-                from .engine import HIP_OPS as opset
-            else:
-                opset = ops
-            if not (getattr(opset, "weighted_nmfk", False) and hasattr(opset, "weighted_column_div")):
-                raise NotImplementedError("PyNMFk with params.weights is not provided by operator set %r: rank estimation under per-entry "
-                                          "weights needs a weighted per-column divergence (PyNMF takes the weights for one rank k)"
-                                          % (getattr(opset, "name", type(opset).__name__),))
-        self._sparse = is_sparse_input(A_ij)
-        self._is = str(getattr(params, "norm", None)).lower() in ("is", "itakura-saito")
-        self._beta, self.beta = str(getattr(params, "norm", None)).lower() == "beta", None
-        for norm in ("beta", "is"):         # ('beta' first: beta = 0 IS Itakura-Saito and is then held to that norm's check as well)
-            if not (self._beta if norm == "beta" else self._is):
-                continue
-            # first of all: the sweep asks one operation beyond a fit, the per-column divergence (under norm='beta' with the column's sum
-            # of a^beta).  (The 'uniform' perturbation is multiplicative noise, which is the noise the Itakura-Saito divergence is the
-            # likelihood of, and keeps positive data positive)
-            if ops is None:                 # (the set PyNMF will take: float64 data run on the float64 set, which factorises under these norms but has no per-column divergence)
-                from .engine import HIP_OPS, HIP_OPS_F64
-                from .pyDNMF import storage_dtype
-                opset = HIP_OPS_F64 if not self._sparse and storage_dtype(A_ij, params) == torch.float64 else HIP_OPS
-            else:
-                opset = ops
-            # (under weights the statistic is the weighted pair's, checked above: the norm's own per-column divergence is not asked for)
-            if not self._weighted and not (getattr(opset, norm + "_nmfk", False) and hasattr(opset, norm + "_column_div")):
-                raise NotImplementedError("PyNMFk with norm='%s' is not provided by operator set %r: rank estimation under %s needs a "
-                                          "per-column divergence (PyNMF factorises at a given k)"
-                                          % (norm, getattr(opset, "name", type(opset).__name__),
-                                             "a beta-divergence" if norm == "beta" else "the Itakura-Saito objective"))
-            if norm == "beta":
-                self.beta = PyNMF._beta_value(params)
-                # renamed, as PyNMF renames it, and swept on that path unchanged
-                self._is, self._beta = self.beta == 0.0, self.beta != 0.0
-            params.norm = 'is' if self._is else 'beta'
-        self._masked = getattr(params, "missing", None) == "nan" and not self._sparse
-        if self._masked and not (self._is or self._beta or self._weighted):           # (norm='is' and norm='beta' refuse missing= and sparse data by name in their setup)
-            # as for a sparse block, the sweep touches A outside PyNMF.fit in the perturbed copy (NaN stays NaN through the
-            # multiplication) and in the per-column error, which must run over the observed positions
-            if ops is None:
-                from .engine import HIP_MASKED_OPS as opset
-            else:
-                opset = ops
-            if not (getattr(opset, "masked_nmfk", False) and hasattr(opset, "column_err_sums")):
-                raise NotImplementedError("PyNMFk with missing='nan' is not provided by operator set %r: rank estimation over NaN-marked "
-                                          "data needs a masked per-column error (PyNMF factorises such data at a given k)"
-                                          % (getattr(opset, "name", type(opset).__name__),))
-        if self._sparse and not (self._is or self._beta or self._weighted):         # (weights refuse sparse data and missing= by name in their setup)
-            # the sweep touches A outside PyNMF.fit in two operations: the perturbed copy and the per-column error
-            if ops is None:
-                from .engine import HIP_CSR_OPS as opset
-            else:
-                opset = ops
-            if not (getattr(opset, "sparse_nmfk", False) and hasattr(opset, "column_err_sums")):
-                raise NotImplementedError("PyNMFk on sparse data is not provided by operator set %r: it has no per-column error and no "
-                                          "perturbed copy of a sparse block (PyNMF factorises sparse data at a given k)"
-                                          % (getattr(opset, "name", type(opset).__name__),))
+        kind = self.kind = fit_kind(A_ij, params)
+        self._sparse, self._masked = kind.form == "sparse", kind.form == "nan"
+        self._is, self._beta, self._weighted, self.beta = kind.norm == "is", kind.norm == "beta", kind.weighted, kind.beta
+        self._row = None                    # the sweep's own row of SWEEP_KINDS (None: a plain sweep)
+        for name in _sweep_rows(kind):
+            self._row = row = SWEEP_KINDS[name]
+            opset = ops
+            if opset is None:
+                from . import engine
+                opset = getattr(engine, row.ops_f64 if kind.form != "sparse" and storage_dtype(A_ij, params) == torch.float64 else row.ops)
+            if not (getattr(opset, row.flag, False) and hasattr(opset, row.method)):
+                raise NotImplementedError(row.refusal % (getattr(opset, "name", type(opset).__name__),))
+        if kind.beta is not None:
+            PyNMF._beta_value(params)       # (after the rows: a missing or out-of-range beta is never 0, so no 'is' row waited behind it)
         self.A_ij = A_ij
         self.ops = ops
         self.local_m, self.local_n = self.A_ij.shape
@@ -319,10 +310,9 @@ class PyNMFk:
         for beta <= 0, non-negative for beta > 0; the ranks agree on the verdict before any of them raises.  The 'uniform' perturbation
         keeps either property (1 + nv + 2 nv U > 0).  'poisson' sampling is refused where a draw of 0 makes the divergence infinite:
         under 'is' and for beta <= 0; for beta > 0 a zero is legal data and the sampling is allowed."""
-        from .pyDNMF import storage_dtype
         params, beta = self.params, (self.beta if self._beta else None)
         a_dtype = torch.float32 if self._sparse else storage_dtype(A_ij, params)
-        PyNMF._div_refusals('beta' if self._beta else 'is', params, self._sparse, getattr(params, "missing", None), a_dtype, self.ops,
+        PyNMF._div_refusals(self.kind.norm, params, self._sparse, getattr(params, "missing", None), a_dtype, self.ops,
                             var_init(params, 'method', default='mu'), self.p_r, self.p_c, int(self.end_k))
         if self.sampling == 'poisson' and beta is None:
             raise NotImplementedError("PyNMFk with norm='is' and sampling='poisson' is not provided: a Poisson draw of 0 makes the "
@@ -331,11 +321,7 @@ class PyNMFk:
             raise NotImplementedError("PyNMFk with norm='beta', beta = %g and sampling='poisson' is not provided: a Poisson draw of 0 makes "
                                       "the divergence infinite for beta <= 0 (sampling='uniform', multiplicative noise, keeps the data "
                                       "positive; 'poisson' is accepted for beta > 0)" % beta)
-        if self.ops is None:
-            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda:
-                raise TypeError("PyNMFk: A_ij is a CPU tensor; pass a CUDA tensor or a numpy array (no CPU fallback)")
-            if not torch.cuda.is_available():
-                raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
+        _need_gpu(self.ops, A_ij, "PyNMFk")
         lo = self._observed_min(A_ij, params.weights) if self._weighted else float(A_ij.min()) if int(np.prod(A_ij.shape)) else 1.0
         PyNMF._sign_check(beta, lo, self.comm1, self.p)
 
@@ -354,17 +340,12 @@ class PyNMFk:
         only the data are perturbed); what PyNMF refuses under weights is refused here, at construction, in its words (the sweep's
         largest rank stands for k)."""
         import copy
-        from .pyDNMF import storage_dtype
         probe = copy.copy(self.params)
         probe.k = int(self.end_k)
         a_dtype = torch.float32 if self._sparse else storage_dtype(A_ij, self.params)
-        PyNMF._weighted_refusals(var_init(self.params, 'norm', default='kl'), probe, self._sparse, getattr(self.params, "missing", None),
+        PyNMF._weighted_refusals(self.kind.norm, probe, self._sparse, getattr(self.params, "missing", None),
                                  a_dtype, self.ops, var_init(self.params, 'method', default='mu'), self.p_r, self.p_c)
-        if self.ops is None:
-            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda:
-                raise TypeError("PyNMFk: A_ij is a CPU tensor; pass a CUDA tensor or a numpy array (no CPU fallback)")
-            if not torch.cuda.is_available():
-                raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
+        _need_gpu(self.ops, A_ij, "PyNMFk")
 
     def _masked_setup(self, A_ij):
         """missing='nan': the raw array stays `self.A_ij` (every PyNMF wraps its perturbed copy in a MaskedDenseBlock itself); what PyNMF
@@ -376,11 +357,7 @@ class PyNMFk:
                                       "params.prune = False")
         if int(self.end_k) > 128:
             raise NotImplementedError("missing='nan' with k = %d is not provided: the masked dense kernels serve 1 <= k <= 128" % int(self.end_k))
-        if self.ops is None:
-            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda:
-                raise TypeError("PyNMFk: A_ij is a CPU tensor; pass a CUDA tensor or a numpy array (no CPU fallback)")
-            if not torch.cuda.is_available():
-                raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
+        _need_gpu(self.ops, A_ij, "PyNMFk")
 
     def _sparse_setup(self, A_ij):
         """The SparseBlock of the sweep, built ONCE (keep_zeros and the meaning of an unstored entry from params.missing) and handed
@@ -389,14 +366,8 @@ class PyNMFk:
         missing = PyNMF._missing_checks(A_ij, self.params, True)
         PyNMF._sparse_checks(A_ij, self.params)
         on_dev = isinstance(A_ij, torch.Tensor) or getattr(A_ij, "is_sparse_block", False)
-        if self.ops is None:
-            if isinstance(A_ij, torch.Tensor) and not A_ij.is_cuda:
-                raise TypeError("PyNMFk: A_ij is a CPU tensor; pass a CUDA tensor or a scipy.sparse matrix (no CPU fallback)")
-            if not torch.cuda.is_available():
-                raise RuntimeError("PyNMFk: no GPU visible; the MI355X engine has no CPU fallback")
-            device = A_ij.device if on_dev else torch.device("cuda", torch.cuda.current_device())
-        else:
-            device = A_ij.device if on_dev else torch.device("cpu")
+        _need_gpu(self.ops, A_ij, "PyNMFk", "a scipy.sparse matrix")
+        device = A_ij.device if on_dev else torch.device("cuda", torch.cuda.current_device()) if self.ops is None else torch.device("cpu")
         self.A_ij = SparseBlock.from_any(A_ij, device, keep_zeros=(missing == "unstored"), missing=missing)
         self.sweep = SparseSweep(self.A_ij, numpy_io=not on_dev, ops=self.ops)
 
@@ -454,8 +425,8 @@ class PyNMFk:
                                         self.A_ij.device)            # the perturbed copies are written straight into it
                 data = sample(data=self.A_ij, noise_var=self.noise_var, method=self.sampling, seed=perturbation * 1000,
                               out=None if stack is None else stack[b], sparse=self.sweep,
-                              missing="nan" if self._masked else None,
-                              weights=self.params.weights if self._weighted and self.sampling == 'poisson' else None).fit()
+                              missing="nan" if self.kind.form == "nan" else None,
+                              weights=self.params.weights if self.kind.weighted and self.sampling == 'poisson' else None).fit()
                 self.params.W_update = True
                 if getattr(self.params, "rng", None) == "device":       # device-drawn init: one seed per (perturbation, k)
                     self.params.init_seed = perturbation * 1000 + self.k
@@ -469,17 +440,13 @@ class PyNMFk:
                 fits.append(f)
                 del data
             results.extend(PyNMF.fit_batch(fits))
-            if self._weighted:              # (the norm's own divergence would read the entries under zero weights)
-                divs.extend(f.weighted_divergence() for f in fits)
-            elif self._is:
-                divs.extend(f.is_divergence() for f in fits)
-            elif self._beta:
-                divs.extend(f.beta_divergence() for f in fits)
+            if self.kind.family is not None:
+                divs.extend(f.divergence() for f in fits)
             for perturbation in chunk:
                 self.cp._save_checkpoint(self.params.flag, perturbation, self.k)
             del fits, stack
         if shared:
-            results, divs = self._gather_fits(results, mine, divs if (self._is or self._beta or self._weighted) else None)
+            results, divs = self._gather_fits(results, mine, divs if self.kind.family is not None else None)
             perturbation = self.perturbations - 1
         self.params.flag = 1
         self.cp._save_checkpoint(self.params.flag, perturbation, self.k)
@@ -516,7 +483,7 @@ class PyNMFk:
         self.AvgW = centroids
         self.params.W_update = False                                                                    # :245
         self.params.init_seed = None
-        numpy_io = self.sweep.numpy_io if self._sparse else not isinstance(self.A_ij, torch.Tensor)
+        numpy_io = self.sweep.numpy_io if self.sweep is not None else not isinstance(self.A_ij, torch.Tensor)
         f0 = [_np(self.AvgW), _np(self.AvgH)] if numpy_io else [self.AvgW, self.AvgH]
         regressH = PyNMF(self.A_ij, factors=f0, params=self.params, ops=self.ops)
         self.AvgW, self.AvgH, self.L_errDist = regressH.fit()                                           # :246-247
@@ -524,25 +491,19 @@ class PyNMFk:
         # weights the columns by their scale, which is what a user who chose this norm wanted to avoid
         # and under norm='beta' the divergence of each column over its sum of a^beta, scale-invariant for every beta
         # and under weights the weighted pair's statistic of the norm, over v > 0 only
-        self.col_err = (regressH.weighted_column_divergence() if self._weighted else regressH.is_column_divergence() if self._is
-                        else regressH.beta_column_divergence() if self._beta else regressH.column_err())
+        self.col_err = regressH.column_statistic()
         self.avgErr = float(np.mean(self.recon_err))
         mn = self.params.m * self.params.n      # (sparse data too, under both meanings of an unstored entry, and NaN-marked data: DESIGN.md section 7)
         self.AIC = 2 * self.k + mn * np.log(self.avgErr / mn)                                           # :250
         cluster_stats = {'clusterSilhouetteCoefficients': self.clusterSilhouetteCoefficients,
                          'avgSilhouetteCoefficients': self.avgSilhouetteCoefficients, 'L_errDist': self.L_errDist,
                          'L_err': self.col_err, 'avgErr': self.avgErr, 'recon_err': self.recon_err, 'AIC': self.AIC}
-        if self._weighted:                      # (recon_err and avgErr are the weighted relative error fit() returns; AIC keeps m n)
-            self.weighted_div = [float(d) for d in divs]
-            cluster_stats['weighted_div'], cluster_stats['avgDiv'] = self.weighted_div, float(np.mean(self.weighted_div))
-            if self._beta:
+        if self.kind.family is not None:        # (recon_err and avgErr stay what fit() returns -- Frobenius; weighted under weights --, AIC keeps m n)
+            divs = [float(d) for d in divs]
+            setattr(self, self._row.div, divs)  # is_div / beta_div / weighted_div
+            cluster_stats[self._row.div], cluster_stats['avgDiv'] = divs, float(np.mean(divs))
+            if self.kind.norm == 'beta':
                 cluster_stats['beta'] = self.beta
-        elif self._is:                          # (recon_err, avgErr and AIC keep their Frobenius definitions)
-            self.is_div = [float(d) for d in divs]
-            cluster_stats['is_div'], cluster_stats['avgDiv'] = self.is_div, float(np.mean(self.is_div))
-        elif self._beta:
-            self.beta_div = [float(d) for d in divs]
-            cluster_stats['beta_div'], cluster_stats['avgDiv'], cluster_stats['beta'] = self.beta_div, float(np.mean(self.beta_div)), self.beta
         self.stats[self.k] = cluster_stats
         if getattr(self.params, "ftype", None) is None:
             self.params.ftype = None
@@ -596,7 +557,7 @@ class PyNMFk:
         operators -- as many as fit next to each other in the GPU's free memory (each holds its perturbed copy of the data) --
         else 1.  `params.nmfk_batch` = False / 0 / 1 keeps the one-by-one fits, an integer caps the batch."""
         want = getattr(self.params, "nmfk_batch", True)
-        if self._sparse or self._masked or self._is or self._beta or self._weighted:          # no batched sparse, masked, weighted, Itakura-Saito or beta-divergence entry point: the fits run one by one, no stack is allocated
+        if not self.kind.batchable:         # (the fits run one by one, no stack is allocated)
             return 1
         if want is False or self.p != 1 or self.ops is not None or not torch.cuda.is_available():
             return 1
