@@ -994,5 +994,7 @@ int dnmf_clock_probe(unsigned long long* samples, int n, int naps, void* stream)
 #include "dnmf_weighted_nmfk_api.h"
 /* Itakura-Saito and the beta-divergence on float64 data (dnmf_is_f64_*, dnmf_beta_f64_*), likewise */
 #include "dnmf_f64_div_api.h"
+/* whole Itakura-Saito / beta-divergence fits of small problems in one workgroup each (dnmf_pair_resident_*), likewise */
+#include "dnmf_resident_api.h"
 
 #endif /* DNMF_H */

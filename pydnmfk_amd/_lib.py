@@ -301,6 +301,16 @@ for _name in ("aht_pair", "wta_pair", "update_w", "update_h", "divergence", "rat
     _sig = SIGNATURES["dnmf_is_" + _name]
     F64_DIV_SIGNATURES["dnmf_is_f64_" + _name] = _sig[:_e] + [c_double] + _sig[_e + 1:]
     F64_DIV_SIGNATURES["dnmf_beta_f64_" + _name] = _sig[:_e] + [c_double, c_double] + _sig[_e + 1:]
+# whole Itakura-Saito / beta-divergence fits of small problems, one workgroup each (include/dnmf_resident_api.h, csrc/dnmf_resident.hip), a
+# table of its own as well: plan m n k out: long[8]; fit mode beta A a_stride lda W w_stride ldw H h_stride ldh m n k eps w_update itr batch
+# sq_out stream
+RESIDENT_SIGNATURES = {}
+RESIDENT_SIGNATURES["dnmf_pair_resident_plan"] = [c_long, c_long, c_int, c_void_p]
+RESIDENT_SIGNATURES["dnmf_pair_resident_fit_batch"] = [c_int, c_float, c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_long,
+                                                       c_long, c_long, c_int, c_float, c_int, c_int, c_int, c_void_p, c_void_p]
+RESIDENT_PLAN_FIELDS = ("eligible", "lds_bytes", "kp", "waves", "row_tiles_per_wave", "col_tiles_per_wave", "row_tiles", "col_tiles")
+RESIDENT_NOT_TAKEN = 1             # DNMF_RESIDENT_NOT_TAKEN
+RESIDENT_MAX_K, RESIDENT_LDS_MAX = 32, 160 * 1024
 # the W phase from a transposed image of A (csrc/dnmf_timg.hip): build A m n lda At ldat stream; bind the same without the stream
 SIGNATURES["dnmf_wimage_bytes"] = [c_long, c_long]
 SIGNATURES["dnmf_wimage_build"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]
@@ -320,7 +330,8 @@ def load():
             "There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, args in list(SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BETA_NMFK_SIGNATURES.items()) \
-            + list(WEIGHTED_SIGNATURES.items()) + list(WEIGHTED_NMFK_SIGNATURES.items()) + list(F64_DIV_SIGNATURES.items()):
+            + list(WEIGHTED_SIGNATURES.items()) + list(WEIGHTED_NMFK_SIGNATURES.items()) + list(F64_DIV_SIGNATURES.items()) \
+            + list(RESIDENT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI drifted from include/dnmf.h
         fn.argtypes = args
         fn.restype = _RESTYPES.get(name, c_int)
@@ -353,6 +364,14 @@ def f64_plan(op, m, n, k, ld=(), method=0):
     p = dict(zip(F64_PLAN_FIELDS, out))
     p["family"] = F64_FAMILIES[p["family"]]
     return p
+
+
+def resident_plan(m, n, k):
+    """dnmf_pair_resident_plan as a dict of RESIDENT_PLAN_FIELDS: whether one workgroup holds the whole Itakura-Saito / beta fit of an
+    m x n problem at rank k, its LDS bytes and KP, and how many tiles the busiest wave walks in each phase (host arithmetic, no GPU)"""
+    out = (c_long * len(RESIDENT_PLAN_FIELDS))()
+    check(lib.dnmf_pair_resident_plan(int(m), int(n), int(k), out))
+    return dict(zip(RESIDENT_PLAN_FIELDS, out))
 
 
 def dense_plan(op, m, n, k, ld=(), align=(), bf16a=False, ws_bytes=None, ew_op="clamp_min"):

@@ -889,6 +889,53 @@ class HipOps(_DivFamily):
         the device tensor [1][2] of {sum (A - W H)^2, sum A^2}."""
         return self._fam_fit("beta", self._beta_mode(beta), A, W, H, eps, w_update, itr)
 
+    # ---- the same two fits of SMALL problems inside one workgroup each (csrc/dnmf_resident.h, dnmf_pair_resident_*): k <= 32, W and H
+    # of a problem in LDS for the whole fit, a batch of same-shape problems in ONE launch.  `params.fit_loop = 'resident'` selects it
+    @staticmethod
+    def resident_refusal(m, n, k):
+        """None where one workgroup holds the whole fit of an m x n problem at rank k, else the sentence that names the limit"""
+        from ._lib import RESIDENT_LDS_MAX, RESIDENT_MAX_K, resident_plan
+        if not 1 <= k <= RESIDENT_MAX_K:
+            return "fit_loop='resident' with k = %d is not provided: the resident kernels serve 1 <= k <= %d" % (k, RESIDENT_MAX_K)
+        plan = resident_plan(m, n, k)
+        if not plan["eligible"]:
+            return ("fit_loop='resident' with a %d x %d block at k = %d is not provided: W and H need %d bytes of LDS, one workgroup holds "
+                    "%d" % (m, n, k, plan["lds_bytes"], RESIDENT_LDS_MAX))
+        return None
+
+    def resident_fit(self, norm, beta, A, W, H, eps, w_update, itr):
+        """The whole fit of `is_fit` (norm 'is') or `beta_fit` (norm 'beta') as ONE kernel launch, a workgroup per problem
+        (dnmf_pair_resident_fit_batch).  A, W, H are matrices -- one problem -- or stacks [B][m][n], [B][m][k], [B][k][n] of same-shape
+        problems with any row pitches and member distances; problem b of a stack has the bits of the same problem on its own.  W, H are
+        updated in place; returns the device tensor [B][2] of {sum (A - W H)^2, sum A^2}.  A shape that one workgroup does not hold is
+        refused by name (NotImplementedError): there is no other path behind this call."""
+        from ._lib import RESIDENT_NOT_TAKEN
+        norm = str(norm).lower()
+        if norm not in ("is", "beta"):
+            raise ValueError("resident_fit: norm %r ('is' or 'beta')" % (norm,))
+        mode = (1,) + self._beta_mode(beta) if norm == "beta" else (0, 0.0)
+        if W.dim() != A.dim() or H.dim() != A.dim() or A.dim() not in (2, 3):
+            raise ValueError("resident_fit: A, W, H must all be matrices or all be stacks")
+        A3, W3, H3 = (A, W, H) if A.dim() == 3 else (A[None], W[None], H[None])
+        for t, name in ((A3, "A"), (W3, "W"), (H3, "H")):
+            _req(t[0], name)
+        B, m, n = A3.shape
+        k = W3.shape[2]
+        if tuple(W3.shape) != (B, m, k) or tuple(H3.shape) != (B, k, n):
+            raise ValueError("resident_fit: shapes A %s, W %s, H %s do not match" % (tuple(A3.shape), tuple(W3.shape), tuple(H3.shape)))
+        why = self.resident_refusal(int(m), int(n), int(k))
+        if why:
+            raise NotImplementedError(why)
+        sq = torch.empty(B, 2, dtype=torch.float64, device=A.device)
+        rc = lib.dnmf_pair_resident_fit_batch(*mode, A3.data_ptr(), A3.stride(0), _ld(A3[0]), W3.data_ptr(), W3.stride(0), _ld(W3[0]),
+                                              H3.data_ptr(), H3.stride(0), _ld(H3[0]), m, n, int(k), float(eps), int(bool(w_update)),
+                                              int(itr), int(B), sq.data_ptr(), _stream())
+        if rc == RESIDENT_NOT_TAKEN:
+            raise NotImplementedError("fit_loop='resident': this device does not give one workgroup the LDS a %d x %d block at k = %d "
+                                      "needs" % (m, n, k))
+        check(rc)
+        return sq
+
     # ---- per-entry weights V >= 0 of A's shape under the four pair rules (csrc/dnmf_weighted.h, dnmf_weighted_*): dense float32 data,
     # 1 <= k <= 128.  num = (V . u_n) F, den = (V . u_d) F with the norm's own pair and rule; v = 0 is "not observed" (A is not looked at
     # there).  `V` follows `A`; `norm` ('fro' / 'kl' / 'is' / 'beta') and `beta` (read under 'beta' alone) follow `eps`

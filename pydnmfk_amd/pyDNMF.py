@@ -74,8 +74,19 @@ BETA_RANGE = (-2.0, 4.0)             # where the value of (W H + eps)^(beta - 2)
 FitKind = namedtuple("FitKind", ("form", "norm", "beta", "weighted", "family", "batchable"))
 
 
-def fit_kind(A_ij, params):
+def _resident_asked(form, norm, weighted, A_ij, params):
+    """`params.fit_loop = 'resident'` on a fit the resident kernels are written for (csrc/dnmf_resident.h): dense float32 data under
+    norm 'is' / 'beta', method 'mu', fp32 arithmetic, no weights, no `missing`, one rank.  Any other fit ignores the value."""
+    if getattr(params, "fit_loop", None) != "resident" or form != "dense" or norm not in ("is", "beta") or weighted:
+        return False
+    grid = getattr(params, "grid", None) or (getattr(params, "p_r", 1), getattr(params, "p_c", 1))
+    return (storage_dtype(A_ij, params) == torch.float32 and str(getattr(params, "method", None) or "mu").lower() == "mu"
+            and (getattr(params, "gemm", None) or "fp32") == "fp32" and grid[0] * grid[1] == 1)
+
+
+def fit_kind(A_ij, params, k=None):
     """What kind of problem a fit of `A_ij` under `params` is, as a FitKind: decided once per fit, here, for PyNMF and PyNMFk alike.
+    `k`: the rank that stands for the fit where `batchable` depends on it (PyNMF: params.k; PyNMFk: the largest rank of its sweep).
     Renames the norm on the bag (`params.norm`): 'itakura-saito' -> 'is', and 'beta' with params.beta = 0 -> 'is'.  Refuses nothing:
     what a kind does not take is refused by the classes, in their order and their words -- a `params.beta` that is missing (nan here)
     or out of range among it (`PyNMF._beta_value`, which PyNMFk calls only after it has told an operator set without the sweep's
@@ -91,8 +102,13 @@ def fit_kind(A_ij, params):
         norm = params.norm = 'is'
     weighted = getattr(params, "weights", None) is not None
     family = "weighted" if weighted else norm if norm in ("is", "beta") else None
-    # (no batched sparse, masked, weighted, Itakura-Saito or beta-divergence entry point: one problem per call)
-    return FitKind(form, norm, beta, weighted, family, form == "dense" and family is None)
+    # (no batched sparse, masked or weighted entry point, and the launch-chain Itakura-Saito / beta fits take one problem per call; the
+    #  resident ones take a batch of every shape one workgroup holds: ops.resident_fit, dnmf_pair_resident_fit_batch)
+    batchable = form == "dense" and family is None
+    if _resident_asked(form, norm, weighted, A_ij, params) and (k if k is not None else getattr(params, "k", None)) is not None:
+        from .engine import HipOps
+        batchable = HipOps.resident_refusal(int(A_ij.shape[0]), int(A_ij.shape[1]), int(k if k is not None else params.k)) is None
+    return FitKind(form, norm, beta, weighted, family, batchable)
 
 
 def _need_gpu(ops, A_ij, who, accepted="a numpy array"):
@@ -217,6 +233,13 @@ class PyNMF:
                     [int(c) for c in self.cart_1d_row.allgather(int(self.H_ij.shape[1]))])
         elif hasattr(self.params, "_slice_counts"):
             del self.params._slice_counts
+        # params.fit_loop = 'resident': the whole fit inside one workgroup (csrc/dnmf_resident.h); what it does not hold is refused by name
+        self._resident = _resident_asked(kind.form, kind.norm, kind.weighted, self.A_ij, self.params)
+        if self._resident:
+            from .engine import HipOps
+            why = HipOps.resident_refusal(int(self.m_loc), int(self.n_loc), int(self.k))
+            if why:
+                raise NotImplementedError(why)
 
     @staticmethod
     def _missing_checks(A_ij, params, sparse):
@@ -560,6 +583,8 @@ class PyNMF:
         device pairs {sum (A - W H)^2, sum A^2}, one per problem."""
         if self._weighted:                                          # dnmf_weighted_mu_fit
             return ops.weighted_fit(self.A_ij, self.V_ij, self.W_i, self.H_j, self.eps, self.norm, self.beta or 0.0, self.W_update, self.itr)
+        if self._resident:                                          # dnmf_pair_resident_fit_batch: one workgroup holds the whole fit
+            return ops.resident_fit(self.norm, self.beta or 0.0, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr)
         if self._beta:                                              # dnmf_beta_mu_fit
             return ops.beta_fit(self.A_ij, self.W_i, self.H_j, self.eps, self.beta, self.W_update, self.itr)
         return ops.fit(self.method, self.norm, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr,
@@ -619,8 +644,8 @@ class PyNMF:
         def same(f):
             return (f.kind.batchable and f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
                     and f.A_ij.dtype == f0.A_ij.dtype and f.A_ij.device == f0.A_ij.device and f.W_i.shape == f0.W_i.shape
-                    and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k) ==
-                    (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k))
+                    and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k, f.beta, f._resident) ==
+                    (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k, f0.beta, f0._resident))
         if len(fits) < 2 or not all(same(f) for f in fits):
             return [f.fit() for f in fits]
         if f0.method.lower() not in ('mu', 'hals', 'bcd'):
@@ -639,8 +664,11 @@ class PyNMF:
         from ._lib import PersistentTimeout
         ops = f0._ops()
         for attempt in (0, 1):
-            sq = ops.fit(f0.method, f0.norm, A, W, H, f0.eps, f0.W_update, f0.itr,
-                         column_sweep=(getattr(f0.params, "hals_sweep", None) == "columns"))
+            if f0._resident:                                # (a workgroup per problem: the same bits as the fits one by one)
+                sq = ops.resident_fit(f0.norm, f0.beta or 0.0, A, W, H, f0.eps, f0.W_update, f0.itr)
+            else:
+                sq = ops.fit(f0.method, f0.norm, A, W, H, f0.eps, f0.W_update, f0.itr,
+                             column_sweep=(getattr(f0.params, "hals_sweep", None) == "columns"))
             try:
                 if hasattr(ops, "hals_check"):
                     ops.hals_check()

@@ -226,7 +226,9 @@ class PyNMFk:
     """pyDNMFk.py:70-299."""
 
     def __init__(self, A_ij, factors=None, params=None, ops=None):
-        kind = self.kind = fit_kind(A_ij, params)
+        # (the sweep's largest rank stands for k: what one batched call takes there, it takes at every smaller rank)
+        k_range = getattr(params, "k_range", None) if getattr(params, "grid", None) else None
+        kind = self.kind = fit_kind(A_ij, params, k=k_range[1] if k_range else getattr(params, "end_k", None))
         self._sparse, self._masked = kind.form == "sparse", kind.form == "nan"
         self._is, self._beta, self._weighted, self.beta = kind.norm == "is", kind.norm == "beta", kind.weighted, kind.beta
         self._row = None                    # the sweep's own row of SWEEP_KINDS (None: a plain sweep)
