@@ -30,6 +30,16 @@ int dnmf_pair_resident_plan(long m, long n, int k, long out[8]);
 int dnmf_pair_resident_fit_batch(int mode, float beta, const float* A, long a_stride, long lda, float* W, long w_stride, long ldw, float* H,
                                  long h_stride, long ldh, long m, long n, int k, float eps, int w_update, int itr, int batch,
                                  double* sq_out, void* stream);
+/* The same whole fit under per-entry weights V >= 0 of A's shape (what dnmf_weighted_mu_fit computes, csrc/dnmf_weighted.h), for the four
+ * norms of dnmf_weighted_*: norm 0 fro, 1 kl, 2 is, 3 beta (`beta` is read under norm 3 alone, -2 <= beta <= 4; beta = 0 runs as is).
+ * Problem b reads its weights at V + b v_stride (leading dimension ldv); v_stride = 0 is legal: every problem of the batch reads the same
+ * V (an NMFk sweep perturbs the data and keeps the weights).  V is read from global memory every step beside A and takes no LDS: the
+ * plan is dnmf_pair_resident_plan's.  Where v > 0 fails the entry of A is not looked at (NaN, inf, 0, negative: anything).
+ * sq_out[b] = {sum v (A - W H)^2, sum v A^2} over v > 0, the pair of dnmf_weighted_resid_sqnorm.  With weights that are all 1 the
+ * factors and the pair under is / beta are those of dnmf_pair_resident_fit_batch bit for bit.  Return codes as above. */
+int dnmf_pair_resident_weighted_fit_batch(int norm, float beta, const float* A, long a_stride, long lda, const float* V, long v_stride,
+                                          long ldv, float* W, long w_stride, long ldw, float* H, long h_stride, long ldh, long m, long n,
+                                          int k, float eps, int w_update, int itr, int batch, double* sq_out, void* stream);
 
 #ifdef __cplusplus
 }

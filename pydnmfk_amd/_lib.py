@@ -308,6 +308,9 @@ RESIDENT_SIGNATURES = {}
 RESIDENT_SIGNATURES["dnmf_pair_resident_plan"] = [c_long, c_long, c_int, c_void_p]
 RESIDENT_SIGNATURES["dnmf_pair_resident_fit_batch"] = [c_int, c_float, c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_long,
                                                        c_long, c_long, c_int, c_float, c_int, c_int, c_int, c_void_p, c_void_p]
+# the same under per-entry weights: norm (0 fro, 1 kl, 2 is, 3 beta) in mode's place, (V, v_stride, ldv) after lda
+_sig = RESIDENT_SIGNATURES["dnmf_pair_resident_fit_batch"]
+RESIDENT_SIGNATURES["dnmf_pair_resident_weighted_fit_batch"] = _sig[:5] + [c_void_p, c_long, c_long] + _sig[5:]
 RESIDENT_PLAN_FIELDS = ("eligible", "lds_bytes", "kp", "waves", "row_tiles_per_wave", "col_tiles_per_wave", "row_tiles", "col_tiles")
 RESIDENT_NOT_TAKEN = 1             # DNMF_RESIDENT_NOT_TAKEN
 RESIDENT_MAX_K, RESIDENT_LDS_MAX = 32, 160 * 1024

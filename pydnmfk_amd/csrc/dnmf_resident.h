@@ -40,10 +40,14 @@
 // so problem b of a batch has the bits of the same problem fitted alone.  Against the launch-chain kernels the agreement is to fp32
 // rounding, NOT bit for bit (other tile shapes, other orders of the sums): the status csrc/dnmf_small.h has against its step kernels.
 //
-// Registers (hipcc --offload-arch=gfx950 -O3, kernel-resource-usage): see the table in DESIGN.md section 7; no instantiation uses scratch.
+// Per-entry weights (params.weights, the four modes of csrc/dnmf_weighted.h): pair_resident_weighted_kernel at the end of this file, a
+// sibling with V as a second m x n operand read the way A is read.
+//
+// Registers (hipcc --offload-arch=gfx950 -O3, kernel-resource-usage): see the tables in DESIGN.md section 7; no instantiation uses scratch.
 #pragma once
 #include "dnmf_is.h"
 #include "dnmf_beta.h"
+#include "dnmf_weighted.h"
 
 #define RS_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
@@ -289,6 +293,281 @@ __global__ __launch_bounds__(RS_T) void pair_resident_kernel(ResidentArgs p) {
                 const float d = a[r] - st[r];
                 part = fmaf(d, d, part);
                 dnorm += (double)a[r] * (double)a[r];
+            }
+            dres += (double)part;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        dres += __shfl_xor(dres, off);
+        dnorm += __shfl_xor(dnorm, off);
+    }
+    if (lane == 0) { wsum[2 * wave] = dres; wsum[2 * wave + 1] = dnorm; }
+    __syncthreads();
+    if (tid == 0) {
+        double a = 0.0, b = 0.0;
+        for (int w = 0; w < RS_NW; ++w) { a += wsum[2 * w]; b += wsum[2 * w + 1]; }
+        p.sq[2 * prob] = a;
+        p.sq[2 * prob + 1] = b;
+    }
+}
+
+// ================================================================================================ the same fit under per-entry weights
+// pair_resident_weighted_kernel: objective sum_ij v_ij d(a_ij | (W H)_ij) for the four modes of csrc/dnmf_weighted.h (PAIR_FRO, PAIR_KL,
+// PAIR_IS, PAIR_BETA).  A SIBLING of the kernel above, not a flag of it: with the two fits in one body (tried: a __forceinline__ body
+// with `if constexpr (WT)`) hipcc schedules and allocates the unweighted instantiations differently, and their code is to stay as it is,
+// instruction for instruction.  Geometry, LDS layout, barriers and the order in which every accumulator chain receives its products are
+// the kernel's above, line by line; what is new is V, a second m x n operand that goes the way A goes:
+//   W phase   the lane's four consecutive elements of its row of V (one 16-byte load when FAST, which now must hold for V's rows too),
+//             requested one tile ahead, beside a_nxt;
+//   H phase   four strided scalar loads beside A's four, requested one row tile ahead;
+//   step      masked_pair<MODE>, then weigh(v, un, ud): the select on v > 0 stands before the second products, so where it fails `a` is
+//             never looked at (NaN, inf, 0, negative) and no NaN reaches an MFMA operand;
+//   padding   a V load outside the block returns 0: a padded position is a gap, (u_n, u_d) = (0, 0), under all four modes -- the
+//             argument of csrc/dnmf_weighted.h.  (The unweighted u_d = 2^23 or eps^(beta - 1) met an exact zero there; 0 meets it now.)
+//   error     {sum v (a - s)^2, sum v a^2} over v > 0, BOTH terms selected, the float64 one included.
+// V is read from L2 every step and takes no LDS: plan_resident is the plan.  ResidentWeights is a second kernel argument; v_stride = 0
+// gives every problem of the batch the same V.  With V = 1 under PAIR_IS / PAIR_BETA every product by v is exact (x * 1) and the chains
+// receive what they receive above in the same order: the factors and the pair are the unweighted kernel's bit for bit.
+struct ResidentWeights { const float* V; long v_stride, ldv; };
+
+template <int KT, bool FAST, int MODE>
+__global__ __launch_bounds__(RS_T) void pair_resident_weighted_kernel(ResidentArgs p, ResidentWeights pv) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int KP = 16 * KT, LDW = KP + RS_PADW, RULE = PairMode<MODE>::rule;
+    const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, q = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const long prob = blockIdx.x;
+    const float* __restrict__ A = p.A + prob * p.a_stride;
+    const float* __restrict__ V = pv.V + prob * pv.v_stride;
+    float* __restrict__ Wg = p.W + prob * p.w_stride;
+    float* __restrict__ Hg = p.H + prob * p.h_stride;
+    const int m = p.m, n = p.n, k = p.k;
+    const int nrt = (m + 15) >> 4, nct = (n + 15) >> 4, MP = nrt * 16, LDH = nct * 16 + RS_PADH;
+    const float eps = p.eps;
+    float* red = smem;
+    float* cs = smem + RS_T;
+    double* wsum = reinterpret_cast<double*>(smem + RS_T + 32);
+    float* Ws = smem + RS_HDR;
+    float* Hs = Ws + MP * LDW;
+
+    for (int idx = tid; idx < MP * LDW; idx += RS_T) {
+        const int r = idx / LDW, j = idx - r * LDW;
+        Ws[idx] = (r < m && j < k) ? Wg[(long)r * p.ldw + j] : 0.f;
+    }
+    for (int idx = tid; idx < KP * LDH; idx += RS_T) {
+        const int j = idx / LDH, c = idx - j * LDH;
+        Hs[idx] = (j < k && c < n) ? Hg[(long)j * p.ldh + c] : 0.f;
+    }
+    __syncthreads();
+
+    for (int it = 0; it < p.itr; ++it) {
+        const int clamp = (it % 10 == 0);
+        if (p.w_update) {
+            for (int rt = wave; rt < nrt; rt += RS_NW) {                      // ---- W phase
+                const int r0 = rt * 16;
+                const bool rok = r0 + i < m;
+                const float* Ar = A + (long)(r0 + i) * p.lda;
+                const float* Vr = V + (long)(r0 + i) * pv.ldv;
+                float* wrow = Ws + (r0 + i) * LDW;
+                f32x4 wreg[KT], on[KT], od[KT];
+#pragma unroll
+                for (int t = 0; t < KT; ++t) {
+                    wreg[t] = *reinterpret_cast<const f32x4*>(wrow + 16 * t + 4 * q);
+                    on[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    od[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+                float a_cur[4], a_nxt[4] = {0.f, 0.f, 0.f, 0.f};
+                float v_cur[4], v_nxt[4] = {0.f, 0.f, 0.f, 0.f};
+                load_vec<4, FAST>(a_cur, Ar, 4 * q, n, rok);
+                load_vec<4, FAST>(v_cur, Vr, 4 * q, n, rok);                   // 0 outside the block: a gap
+                for (int ct = 0; ct < nct; ++ct) {
+                    const int c0 = ct * 16;
+                    if (ct + 1 < nct) {
+                        load_vec<4, FAST>(a_nxt, Ar, c0 + 16 + 4 * q, n, rok);
+                        load_vec<4, FAST>(v_nxt, Vr, c0 + 16 + 4 * q, n, rok);
+                    }
+                    f32x4 st = {0.f, 0.f, 0.f, 0.f};                           // S^T: lane (i, q) holds S[r0 + i][c0 + 4 q + reg]
+#pragma unroll
+                    for (int t = 0; t < KT; ++t)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) st = RS_MFMA(Hs[(16 * t + 4 * q + e) * LDH + c0 + i], wreg[t][e], st);
+                    f32x4 un, ud;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float x, y;
+                        masked_pair<MODE>(a_cur[r], st[r], eps, p.pexp, x, y);
+                        weigh(v_cur[r], x, y);                                 // the select: nothing of `a` passes where v > 0 fails
+                        un[r] = x;
+                        ud[r] = y;
+                    }
+#pragma unroll
+                    for (int jt = 0; jt < KT; ++jt) {                          // num^T, den^T: rows j = 16 jt + 4 q + reg, column r0 + i
+                        const f32x4 hh = *reinterpret_cast<const f32x4*>(Hs + (16 * jt + i) * LDH + c0 + 4 * q);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            on[jt] = RS_MFMA(hh[r], un[r], on[jt]);
+                            od[jt] = RS_MFMA(hh[r], ud[r], od[jt]);
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        a_cur[r] = a_nxt[r];
+                        v_cur[r] = v_nxt[r];
+                    }
+                }
+                if (rok) {
+#pragma unroll
+                    for (int jt = 0; jt < KT; ++jt)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int j = 16 * jt + 4 * q + r;
+                            if (j < k) wrow[j] = pair_rule<RULE>(wreg[jt][r], on[jt][r], od[jt][r], eps, 0, p.gamma);
+                        }
+                }
+            }
+            __syncthreads();
+        }
+        for (int ct = wave; ct < nct; ct += RS_NW) {                          // ---- H phase (with the new W)
+            const int c0 = ct * 16;
+            const bool cok = c0 + i < n;
+            const float* Ac = A + c0 + i;
+            const float* Vc = V + c0 + i;
+            f32x4 hb[KT], outn[KT], outd[KT];
+#pragma unroll
+            for (int t = 0; t < KT; ++t) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) hb[t][e] = Hs[(16 * t + 4 * q + e) * LDH + c0 + i];
+                outn[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+                outd[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            float a_cur[4], a_nxt[4] = {0.f, 0.f, 0.f, 0.f};
+            float v_cur[4], v_nxt[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const bool in = cok && 4 * q + r < m;
+                a_cur[r] = in ? Ac[(long)(4 * q + r) * p.lda] : 0.f;
+                v_cur[r] = in ? Vc[(long)(4 * q + r) * pv.ldv] : 0.f;
+            }
+            for (int rt = 0; rt < nrt; ++rt) {
+                const int r0 = rt * 16;
+                if (rt + 1 < nrt) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = r0 + 16 + 4 * q + r;
+                        const bool in = cok && row < m;
+                        a_nxt[r] = in ? Ac[(long)row * p.lda] : 0.f;
+                        v_nxt[r] = in ? Vc[(long)row * pv.ldv] : 0.f;
+                    }
+                }
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};                              // S: lane (i, q) holds S[r0 + 4 q + reg][c0 + i]
+#pragma unroll
+                for (int t = 0; t < KT; ++t) {
+                    const f32x4 w = *reinterpret_cast<const f32x4*>(Ws + (r0 + i) * LDW + 16 * t + 4 * q);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc = RS_MFMA(w[e], hb[t][e], acc);
+                }
+                f32x4 un, ud;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float x, y;
+                    masked_pair<MODE>(a_cur[r], acc[r], eps, p.pexp, x, y);
+                    weigh(v_cur[r], x, y);
+                    un[r] = x;
+                    ud[r] = y;
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int jt = 0; jt < KT; ++jt) {                          // num, den: rows j = 16 jt + 4 q + reg, column c0 + i
+                        const float w = Ws[(r0 + 4 * q + r) * LDW + 16 * jt + i];
+                        outn[jt] = RS_MFMA(w, un[r], outn[jt]);
+                        outd[jt] = RS_MFMA(w, ud[r], outd[jt]);
+                    }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    a_cur[r] = a_nxt[r];
+                    v_cur[r] = v_nxt[r];
+                }
+            }
+            if (cok) {
+#pragma unroll
+                for (int jt = 0; jt < KT; ++jt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int j = 16 * jt + 4 * q + r;
+                        if (j < k) Hs[j * LDH + c0 + i] = pair_rule<RULE>(hb[jt][r], outn[jt][r], outd[jt][r], eps, clamp, p.gamma);
+                    }
+            }
+        }
+        __syncthreads();
+        if (clamp) {                                                           // W = max(W, eps) after H's
+            for (int idx = tid; idx < m * k; idx += RS_T) {
+                float* w = Ws + (idx / k) * LDW + idx % k;
+                *w = fmaxf(*w, eps);
+            }
+            __syncthreads();
+        }
+    }
+
+    // ---- normalize_features: s = column sums of W in a fixed order; W /= s + eps; H *= s^T
+    {
+        constexpr int NPART = RS_T / KP;
+        const int j = tid % KP, part = tid / KP;
+        float s = 0.f;
+        for (int r = part; r < m; r += NPART) s += Ws[r * LDW + j];
+        red[part * KP + j] = s;
+        __syncthreads();
+        if (tid < KP) {
+            float t = 0.f;
+            for (int pp = 0; pp < NPART; ++pp) t += red[pp * KP + tid];
+            cs[tid] = t;
+        }
+        __syncthreads();
+    }
+    for (int idx = tid; idx < m * k; idx += RS_T) {
+        const int r = idx / k, j = idx - r * k;
+        const float v = Ws[r * LDW + j] / (cs[j] + eps);
+        Ws[r * LDW + j] = v;
+        Wg[(long)r * p.ldw + j] = v;
+    }
+    for (int idx = tid; idx < k * n; idx += RS_T) {
+        const int j = idx / n, c = idx - j * n;
+        const float v = Hs[j * LDH + c] * cs[j];
+        Hs[j * LDH + c] = v;
+        Hg[(long)j * p.ldh + c] = v;
+    }
+    __syncthreads();
+
+    // ---- the weighted error pair {sum v (A - W H)^2, sum v A^2} over v > 0 (dnmf_weighted_resid_sqnorm's); the tiles of the W phase
+    double dres = 0.0, dnorm = 0.0;
+    for (int rt = wave; rt < nrt; rt += RS_NW) {
+        const int r0 = rt * 16;
+        const bool rok = r0 + i < m;
+        const float* Ar = A + (long)(r0 + i) * p.lda;
+        const float* Vr = V + (long)(r0 + i) * pv.ldv;
+        f32x4 wreg[KT];
+#pragma unroll
+        for (int t = 0; t < KT; ++t) wreg[t] = *reinterpret_cast<const f32x4*>(Ws + (r0 + i) * LDW + 16 * t + 4 * q);
+        for (int ct = 0; ct < nct; ++ct) {
+            const int c0 = ct * 16;
+            float a[4], v[4];
+            load_vec<4, FAST>(a, Ar, c0 + 4 * q, n, rok);
+            load_vec<4, FAST>(v, Vr, c0 + 4 * q, n, rok);
+            f32x4 st = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < KT; ++t)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) st = RS_MFMA(Hs[(16 * t + 4 * q + e) * LDH + c0 + i], wreg[t][e], st);
+            float part = 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                // both terms selected: what lies under a zero weight, or outside the block (V loaded as 0), enters neither sum.  At
+                // v = 1 the products by v are exact and the terms are the unweighted kernel's, bit for bit
+                const bool obs = v[r] > 0.f;
+                const float d = obs ? a[r] - st[r] : 0.f;
+                part = fmaf(obs ? v[r] * d : 0.f, d, part);
+                dnorm += obs ? ((double)v[r] * (double)a[r]) * (double)a[r] : 0.0;
             }
             dres += (double)part;
         }

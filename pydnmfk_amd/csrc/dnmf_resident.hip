@@ -1,6 +1,7 @@
 // dnmf_resident.hip -- C ABI of the resident pair-rule fits (csrc/dnmf_resident.h, include/dnmf_resident_api.h): the plan of a shape as
-// numbers, and the launch of a batch of whole Itakura-Saito / beta-divergence MU fits, one workgroup per problem.  A translation unit of
-// its own (see csrc/dnmf_kl.hip).  One launch per call; no workgroup waits for another one; no workspace.
+// numbers, and the launch of a batch of whole Itakura-Saito / beta-divergence MU fits, one workgroup per problem -- or, under per-entry
+// weights, of whole fro / kl / is / beta fits (pair_resident_weighted_kernel).  A translation unit of its own (see csrc/dnmf_kl.hip).
+// One launch per call; no workgroup waits for another one; no workspace.
 #include "dnmf_common.h"
 #include "dnmf_host.h"
 #include "dnmf_resident.h"
@@ -21,6 +22,20 @@ ResidentKernel resident_kernel(int mode, int kp, bool fast) {
     return fast ? resident_kernel<2, true>(mode) : resident_kernel<2, false>(mode);
 }
 
+// the weighted kernels, by the norm of dnmf_weighted_* (0 fro, 1 kl, 2 is, 3 beta)
+typedef void (*ResidentWeightedKernel)(ResidentArgs, ResidentWeights);
+
+template <int KT, bool FAST>
+ResidentWeightedKernel resident_weighted_kernel(int norm) {
+    if (norm == 0) return pair_resident_weighted_kernel<KT, FAST, PAIR_FRO>;
+    if (norm == 1) return pair_resident_weighted_kernel<KT, FAST, PAIR_KL>;
+    return norm == 2 ? pair_resident_weighted_kernel<KT, FAST, PAIR_IS> : pair_resident_weighted_kernel<KT, FAST, PAIR_BETA>;
+}
+ResidentWeightedKernel resident_weighted_kernel(int norm, int kp, bool fast) {
+    if (kp == 16) return fast ? resident_weighted_kernel<1, true>(norm) : resident_weighted_kernel<1, false>(norm);
+    return fast ? resident_weighted_kernel<2, true>(norm) : resident_weighted_kernel<2, false>(norm);
+}
+
 size_t resident_lds_limit() {
     static size_t limit_of[RS_MAX_DEVICES];
     static bool have[RS_MAX_DEVICES] = {};
@@ -32,6 +47,9 @@ size_t resident_lds_limit() {
     for (int mode : {DNMF_RESIDENT_IS, DNMF_RESIDENT_BETA})
         for (int kp : {16, 32})
             for (bool fast : {false, true}) allow_lds(resident_kernel(mode, kp, fast), limit);
+    for (int norm = 0; norm < 4; ++norm)
+        for (int kp : {16, 32})
+            for (bool fast : {false, true}) allow_lds(resident_weighted_kernel(norm, kp, fast), limit);
     clear_hip_error();
     limit_of[dev] = limit;
     have[dev] = true;
@@ -85,6 +103,40 @@ int dnmf_pair_resident_fit_batch(int mode, float beta, const float* A, long a_st
     // A is fetched, never a sum: both forms give the same bits
     const bool fast = aligned16(A) && lda % 4 == 0 && n % 4 == 0 && a.a_stride % 4 == 0;
     hipLaunchKernelGGL(resident_kernel(mode, r.kp, fast), dim3((unsigned)batch), dim3(RS_T), r.lds, st, a);
+    return check_launch(who);
+}
+
+int dnmf_pair_resident_weighted_fit_batch(int norm, float beta, const float* A, long a_stride, long lda, const float* V, long v_stride,
+                                          long ldv, float* W, long w_stride, long ldw, float* H, long h_stride, long ldh, long m, long n,
+                                          int k, float eps, int w_update, int itr, int batch, double* sq_out, void* stream) {
+    const char* who = "pair_resident_weighted_fit_batch";
+    REQUIRE(norm >= 0 && norm <= 3, "%s: norm=%d is not known (0 fro, 1 kl, 2 is, 3 beta)", who, norm);
+    if (norm == 3) {
+        REQUIRE(beta_ok(beta), "%s: beta=%g is outside the accepted range -2 <= beta <= 4", who, (double)beta);
+        if (beta == 0.f) norm = 2;                         // beta = 0 IS Itakura-Saito: its kernels, its bits
+    }
+    REQUIRE(k >= 1 && k <= RS_MAX_K, "%s: rank k=%d unsupported (1 <= k <= %d for the resident fits)", who, k, RS_MAX_K);
+    REQUIRE(A && V && W && H && sq_out && m >= 1 && n >= 1 && lda >= n && ldv >= n && ldw >= k && ldh >= n && itr >= 0 && batch >= 1,
+            "%s: null pointer or bad shape (m=%ld n=%ld k=%d itr=%d batch=%d)", who, m, n, k, itr, batch);
+    // (v_stride = 0: every problem reads the one V -- a sweep perturbs the data and keeps the weights)
+    REQUIRE(batch == 1 || (a_stride >= (m - 1) * lda + n && w_stride >= (m - 1) * ldw + k && h_stride >= (long)(k - 1) * ldh + n &&
+                           (v_stride == 0 || v_stride >= (m - 1) * ldv + n)),
+            "%s: the problems of a batch overlap (strides %ld %ld %ld %ld)", who, a_stride, v_stride, w_stride, h_stride);
+    const ResidentPlan r = plan_resident(m, n, k);
+    if (!r.eligible) return DNMF_RESIDENT_NOT_TAKEN;
+    hipStream_t st = S(stream);
+    if (r.lds > resident_lds_limit()) return DNMF_RESIDENT_NOT_TAKEN;
+    ResidentArgs a{};
+    a.A = A; a.a_stride = batch == 1 ? 0 : a_stride; a.lda = lda;
+    a.W = W; a.w_stride = batch == 1 ? 0 : w_stride; a.ldw = ldw;
+    a.H = H; a.h_stride = batch == 1 ? 0 : h_stride; a.ldh = ldh;
+    a.m = (int)m; a.n = (int)n; a.k = k; a.eps = eps; a.w_update = w_update; a.itr = itr; a.sq = sq_out;
+    if (norm == 3) { const PairExp px = beta_exp(beta); a.pexp = px.e; a.gamma = px.gamma; }
+    else a.gamma = 1.f;
+    const ResidentWeights w{V, batch == 1 ? 0 : v_stride, ldv};
+    // the 16-byte loads: they must hold for the rows of V as for the rows of A (one FAST for both; the bits do not depend on it)
+    const bool fast = aligned16(A) && lda % 4 == 0 && n % 4 == 0 && a.a_stride % 4 == 0 && aligned16(V) && ldv % 4 == 0 && w.v_stride % 4 == 0;
+    hipLaunchKernelGGL(resident_weighted_kernel(norm, r.kp, fast), dim3((unsigned)batch), dim3(RS_T), r.lds, st, a, w);
     return check_launch(who);
 }
 

@@ -890,7 +890,8 @@ class HipOps(_DivFamily):
         return self._fam_fit("beta", self._beta_mode(beta), A, W, H, eps, w_update, itr)
 
     # ---- the same two fits of SMALL problems inside one workgroup each (csrc/dnmf_resident.h, dnmf_pair_resident_*): k <= 32, W and H
-    # of a problem in LDS for the whole fit, a batch of same-shape problems in ONE launch.  `params.fit_loop = 'resident'` selects it
+    # of a problem in LDS for the whole fit, a batch of same-shape problems in ONE launch.  `params.fit_loop = 'resident'` selects it;
+    # with weights V the weighted fit of any of the four weighted norms runs the same way (dnmf_pair_resident_weighted_fit_batch)
     @staticmethod
     def resident_refusal(m, n, k):
         """None where one workgroup holds the whole fit of an m x n problem at rank k, else the sentence that names the limit"""
@@ -903,17 +904,22 @@ class HipOps(_DivFamily):
                     "%d" % (m, n, k, plan["lds_bytes"], RESIDENT_LDS_MAX))
         return None
 
-    def resident_fit(self, norm, beta, A, W, H, eps, w_update, itr):
+    def resident_fit(self, norm, beta, A, W, H, eps, w_update, itr, V=None):
         """The whole fit of `is_fit` (norm 'is') or `beta_fit` (norm 'beta') as ONE kernel launch, a workgroup per problem
         (dnmf_pair_resident_fit_batch).  A, W, H are matrices -- one problem -- or stacks [B][m][n], [B][m][k], [B][k][n] of same-shape
         problems with any row pitches and member distances; problem b of a stack has the bits of the same problem on its own.  W, H are
         updated in place; returns the device tensor [B][2] of {sum (A - W H)^2, sum A^2}.  A shape that one workgroup does not hold is
-        refused by name (NotImplementedError): there is no other path behind this call."""
+        refused by name (NotImplementedError): there is no other path behind this call.
+        `V`: per-entry weights, the whole fit of `weighted_fit` under any of its four norms (dnmf_pair_resident_weighted_fit_batch) and
+        its pair {sum v (A - W H)^2, sum v A^2}: a matrix, or a stack [B][m][n]; a matrix next to stacks is shared by every problem."""
         from ._lib import RESIDENT_NOT_TAKEN
         norm = str(norm).lower()
-        if norm not in ("is", "beta"):
+        if V is not None:
+            mode = self._weighted_mode(norm, beta)
+        elif norm not in ("is", "beta"):
             raise ValueError("resident_fit: norm %r ('is' or 'beta')" % (norm,))
-        mode = (1,) + self._beta_mode(beta) if norm == "beta" else (0, 0.0)
+        else:
+            mode = (1,) + self._beta_mode(beta) if norm == "beta" else (0, 0.0)
         if W.dim() != A.dim() or H.dim() != A.dim() or A.dim() not in (2, 3):
             raise ValueError("resident_fit: A, W, H must all be matrices or all be stacks")
         A3, W3, H3 = (A, W, H) if A.dim() == 3 else (A[None], W[None], H[None])
@@ -927,9 +933,17 @@ class HipOps(_DivFamily):
         if why:
             raise NotImplementedError(why)
         sq = torch.empty(B, 2, dtype=torch.float64, device=A.device)
-        rc = lib.dnmf_pair_resident_fit_batch(*mode, A3.data_ptr(), A3.stride(0), _ld(A3[0]), W3.data_ptr(), W3.stride(0), _ld(W3[0]),
-                                              H3.data_ptr(), H3.stride(0), _ld(H3[0]), m, n, int(k), float(eps), int(bool(w_update)),
-                                              int(itr), int(B), sq.data_ptr(), _stream())
+        a_args = (A3.data_ptr(), A3.stride(0), _ld(A3[0]))
+        tail = (W3.data_ptr(), W3.stride(0), _ld(W3[0]), H3.data_ptr(), H3.stride(0), _ld(H3[0]), m, n, int(k), float(eps),
+                int(bool(w_update)), int(itr), int(B), sq.data_ptr(), _stream())
+        if V is not None:
+            if V.dim() not in (2, A.dim()) or tuple(V.shape[-2:]) != (m, n) or (V.dim() == 3 and V.shape[0] != B):
+                raise ValueError("resident_fit: weights %s must have the shape of A %s, or of one of its problems" % (tuple(V.shape), tuple(A.shape)))
+            _req(V if V.dim() == 2 else V[0], "weights")
+            v_args = (V.data_ptr(), V.stride(0) if V.dim() == 3 else 0, _ld(V if V.dim() == 2 else V[0]))     # a matrix: stride 0, shared
+            rc = lib.dnmf_pair_resident_weighted_fit_batch(*mode, *a_args, *v_args, *tail)
+        else:
+            rc = lib.dnmf_pair_resident_fit_batch(*mode, *a_args, *tail)
         if rc == RESIDENT_NOT_TAKEN:
             raise NotImplementedError("fit_loop='resident': this device does not give one workgroup the LDS a %d x %d block at k = %d "
                                       "needs" % (m, n, k))

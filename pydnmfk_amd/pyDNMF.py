@@ -76,8 +76,10 @@ FitKind = namedtuple("FitKind", ("form", "norm", "beta", "weighted", "family", "
 
 def _resident_asked(form, norm, weighted, A_ij, params):
     """`params.fit_loop = 'resident'` on a fit the resident kernels are written for (csrc/dnmf_resident.h): dense float32 data under
-    norm 'is' / 'beta', method 'mu', fp32 arithmetic, no weights, no `missing`, one rank.  Any other fit ignores the value."""
-    if getattr(params, "fit_loop", None) != "resident" or form != "dense" or norm not in ("is", "beta") or weighted:
+    norm 'is' / 'beta' -- with `params.weights` under fro / kl / is / beta --, method 'mu', fp32 arithmetic, no `missing`, one rank.  Any
+    other fit ignores the value (an unweighted fro / kl fit among them)."""
+    if getattr(params, "fit_loop", None) != "resident" or form != "dense" or str(norm).lower() not in (
+            ("fro", "kl", "is", "beta") if weighted else ("is", "beta")):
         return False
     grid = getattr(params, "grid", None) or (getattr(params, "p_r", 1), getattr(params, "p_c", 1))
     return (storage_dtype(A_ij, params) == torch.float32 and str(getattr(params, "method", None) or "mu").lower() == "mu"
@@ -103,7 +105,8 @@ def fit_kind(A_ij, params, k=None):
     weighted = getattr(params, "weights", None) is not None
     family = "weighted" if weighted else norm if norm in ("is", "beta") else None
     # (no batched sparse, masked or weighted entry point, and the launch-chain Itakura-Saito / beta fits take one problem per call; the
-    #  resident ones take a batch of every shape one workgroup holds: ops.resident_fit, dnmf_pair_resident_fit_batch)
+    #  resident ones take a batch of every shape one workgroup holds, weighted fits among them: ops.resident_fit,
+    #  dnmf_pair_resident_fit_batch / dnmf_pair_resident_weighted_fit_batch)
     batchable = form == "dense" and family is None
     if _resident_asked(form, norm, weighted, A_ij, params) and (k if k is not None else getattr(params, "k", None)) is not None:
         from .engine import HipOps
@@ -571,7 +574,7 @@ class PyNMF:
         if self.kind.family is not None and name != "hip":
             return False                                            # (dnmf_is_mu_fit / dnmf_beta_mu_fit / dnmf_weighted_mu_fit live in the fp32 operator set only)
         if self._weighted:                                          # dnmf_weighted_mu_fit: one problem per call, every norm it serves
-            return hasattr(ops, "weighted_fit")
+            return hasattr(ops, "resident_fit" if self._resident else "weighted_fit")   # (resident: a batch per call)
         if self._masked_dense:
             return name == "hip-masked" and hasattr(ops, "fit") and method == "mu" and norm in ("fro", "kl")
         return (not self._sparse and name in ("hip", "hip-f64") and hasattr(ops, "fit") and not (name == "hip-f64" and self.k > 128)
@@ -581,10 +584,10 @@ class PyNMF:
         """What runs where `_whole_fit_ok`: the whole loop of `_fit_once` -- steps, clamps, normalisation, both squared norms -- as ONE
         library call (dnmf_*_fit, csrc/dnmf_fit.hip): no Python, no ctypes call and no host synchronisation inside the fit.  Returns the
         device pairs {sum (A - W H)^2, sum A^2}, one per problem."""
+        if self._resident:                                          # dnmf_pair_resident_[weighted_]fit_batch: one workgroup holds the whole fit
+            return ops.resident_fit(self.norm, self.beta or 0.0, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr, V=self.V_ij)
         if self._weighted:                                          # dnmf_weighted_mu_fit
             return ops.weighted_fit(self.A_ij, self.V_ij, self.W_i, self.H_j, self.eps, self.norm, self.beta or 0.0, self.W_update, self.itr)
-        if self._resident:                                          # dnmf_pair_resident_fit_batch: one workgroup holds the whole fit
-            return ops.resident_fit(self.norm, self.beta or 0.0, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr)
         if self._beta:                                              # dnmf_beta_mu_fit
             return ops.beta_fit(self.A_ij, self.W_i, self.H_j, self.eps, self.beta, self.W_update, self.itr)
         return ops.fit(self.method, self.norm, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr,
@@ -644,8 +647,8 @@ class PyNMF:
         def same(f):
             return (f.kind.batchable and f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
                     and f.A_ij.dtype == f0.A_ij.dtype and f.A_ij.device == f0.A_ij.device and f.W_i.shape == f0.W_i.shape
-                    and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k, f.beta, f._resident) ==
-                    (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k, f0.beta, f0._resident))
+                    and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k, f.beta, f._resident, f._weighted) ==
+                    (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k, f0.beta, f0._resident, f0._weighted))
         if len(fits) < 2 or not all(same(f) for f in fits):
             return [f.fit() for f in fits]
         if f0.method.lower() not in ('mu', 'hals', 'bcd'):
@@ -661,11 +664,18 @@ class PyNMF:
         for b, f in enumerate(fits):
             W[b].copy_(f.W_i)
             H[b].copy_(f.H_j)
+        V = None
+        if f0._weighted:                                    # (batchable under weights: the resident kernels alone)
+            v0 = f0.V_ij                                    # one storage for every fit (a sweep keeps its weights): handed over once
+            if all(f.V_ij.data_ptr() == v0.data_ptr() and f.V_ij.shape == v0.shape and f.V_ij.stride() == v0.stride() for f in fits):
+                V = v0
+            else:
+                V = torch.stack([f.V_ij for f in fits])
         from ._lib import PersistentTimeout
         ops = f0._ops()
         for attempt in (0, 1):
             if f0._resident:                                # (a workgroup per problem: the same bits as the fits one by one)
-                sq = ops.resident_fit(f0.norm, f0.beta or 0.0, A, W, H, f0.eps, f0.W_update, f0.itr)
+                sq = ops.resident_fit(f0.norm, f0.beta or 0.0, A, W, H, f0.eps, f0.W_update, f0.itr, V=V)
             else:
                 sq = ops.fit(f0.method, f0.norm, A, W, H, f0.eps, f0.W_update, f0.itr,
                              column_sweep=(getattr(f0.params, "hals_sweep", None) == "columns"))

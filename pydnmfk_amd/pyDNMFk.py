@@ -348,6 +348,12 @@ class PyNMFk:
         PyNMF._weighted_refusals(self.kind.norm, probe, self._sparse, getattr(self.params, "missing", None),
                                  a_dtype, self.ops, var_init(self.params, 'method', default='mu'), self.p_r, self.p_c)
         _need_gpu(self.ops, A_ij, "PyNMFk")
+        if self.kind.batchable and self.ops is None:
+            # fits that run as one launch share the weights: the device block is built ONCE per sweep, here -- every PyNMF then takes
+            # this tensor as it is (the same storage), and PyNMF.fit_batch hands it over once, for all problems of the batch
+            from .pyDNMF import _to_device
+            dev = A_ij.device if isinstance(A_ij, torch.Tensor) and A_ij.is_cuda else torch.device("cuda", torch.cuda.current_device())
+            self.params.weights = _to_device(self.params.weights, dev, torch.float32, what="weights")
 
     def _masked_setup(self, A_ij):
         """missing='nan': the raw array stays `self.A_ij` (every PyNMF wraps its perturbed copy in a MaskedDenseBlock itself); what PyNMF
