@@ -996,5 +996,7 @@ int dnmf_clock_probe(unsigned long long* samples, int n, int naps, void* stream)
 #include "dnmf_f64_div_api.h"
 /* whole Itakura-Saito / beta-divergence fits of small problems in one workgroup each (dnmf_pair_resident_*), likewise */
 #include "dnmf_resident_api.h"
+/* whole MU fits of sparse blocks, batched over a shared pattern: dnmf_csr_fit_* and dnmf_csr_mu_fit_batch, likewise */
+#include "dnmf_csr_fit_api.h"
 
 #endif /* DNMF_H */

@@ -314,6 +314,16 @@ RESIDENT_SIGNATURES["dnmf_pair_resident_weighted_fit_batch"] = _sig[:5] + [c_voi
 RESIDENT_PLAN_FIELDS = ("eligible", "lds_bytes", "kp", "waves", "row_tiles_per_wave", "col_tiles_per_wave", "row_tiles", "col_tiles")
 RESIDENT_NOT_TAKEN = 1             # DNMF_RESIDENT_NOT_TAKEN
 RESIDENT_MAX_K, RESIDENT_LDS_MAX = 32, 160 * 1024
+# whole MU fits of sparse blocks, batched over a shared pattern (include/dnmf_csr_fit_api.h, csrc/dnmf_csr_fit.hip), a table of its own as
+# well: plan m n k batch out: long[6]; fit m n k batch nnz | crow col long_rows long_segptr n_long nseg | the same six of the transpose |
+# val t_val val_stride | W ldw w_stride | H ldh h_stride | norm missing eps w_update itr | ws ws_bytes sq_out stream
+CSR_FIT_SIGNATURES = {}
+CSR_FIT_SIGNATURES["dnmf_csr_fit_plan"] = [c_long, c_long, c_int, c_int, c_void_p]
+CSR_FIT_SIGNATURES["dnmf_csr_fit_ws_bytes"] = [c_long, c_long, c_int, c_int, c_int]
+CSR_FIT_SIGNATURES["dnmf_csr_mu_fit_batch"] = ([c_long, c_long, c_int, c_int, c_long] + 2 * [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int]
+                                               + [c_void_p, c_void_p, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_long,
+                                                  c_int, c_int, c_float, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p])
+CSR_FIT_PLAN_FIELDS = ("kpad", "g", "bt", "tiles", "w_image_bytes", "h_image_bytes")
 # the W phase from a transposed image of A (csrc/dnmf_timg.hip): build A m n lda At ldat stream; bind the same without the stream
 SIGNATURES["dnmf_wimage_bytes"] = [c_long, c_long]
 SIGNATURES["dnmf_wimage_build"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]
@@ -321,7 +331,7 @@ SIGNATURES["dnmf_wimage_bind"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_
 SIGNATURES["dnmf_wimage_unbind"] = []
 SIGNATURES["dnmf_set_wimage"] = [c_int]
 SIGNATURES["dnmf_wimage_plan"] = [c_long, c_long, c_int, c_long, c_int, c_int, c_void_p]      # out: int[6]
-_RESTYPES = {"dnmf_is_f64_ws_bytes": c_size_t, "dnmf_beta_f64_ws_bytes": c_size_t, "dnmf_weighted_column_div_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes_fit": c_size_t, "dnmf_beta_column_div_ws_bytes": c_size_t, "dnmf_beta_ws_bytes": c_size_t, "dnmf_beta_ws_bytes_fit": c_size_t, "dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
+_RESTYPES = {"dnmf_csr_fit_ws_bytes": c_size_t, "dnmf_is_f64_ws_bytes": c_size_t, "dnmf_beta_f64_ws_bytes": c_size_t, "dnmf_weighted_column_div_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes_fit": c_size_t, "dnmf_beta_column_div_ws_bytes": c_size_t, "dnmf_beta_ws_bytes": c_size_t, "dnmf_beta_ws_bytes_fit": c_size_t, "dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
              "dnmf_ws_bytes_1d": c_size_t, "dnmf_ws_bytes_hblocks": c_size_t, "dnmf_ws_bytes_2d": c_size_t,
              "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t, "dnmf_bcd_ws_bytes_fit": c_size_t}
 
@@ -334,7 +344,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, args in list(SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BETA_NMFK_SIGNATURES.items()) \
             + list(WEIGHTED_SIGNATURES.items()) + list(WEIGHTED_NMFK_SIGNATURES.items()) + list(F64_DIV_SIGNATURES.items()) \
-            + list(RESIDENT_SIGNATURES.items()):
+            + list(RESIDENT_SIGNATURES.items()) + list(CSR_FIT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI drifted from include/dnmf.h
         fn.argtypes = args
         fn.restype = _RESTYPES.get(name, c_int)
@@ -375,6 +385,14 @@ def resident_plan(m, n, k):
     out = (c_long * len(RESIDENT_PLAN_FIELDS))()
     check(lib.dnmf_pair_resident_plan(int(m), int(n), int(k), out))
     return dict(zip(RESIDENT_PLAN_FIELDS, out))
+
+
+def csr_fit_plan(m, n, k, batch=1):
+    """dnmf_csr_fit_plan as a dict of CSR_FIT_PLAN_FIELDS: KPAD, the lanes per stored entry, the problems per tile and the tiles of a batched
+    sparse fit, and the bytes of its two problem-interleaved images (host arithmetic, no GPU)"""
+    out = (c_long * len(CSR_FIT_PLAN_FIELDS))()
+    check(lib.dnmf_csr_fit_plan(int(m), int(n), int(k), int(batch), out))
+    return dict(zip(CSR_FIT_PLAN_FIELDS, out))
 
 
 def dense_plan(op, m, n, k, ld=(), align=(), bf16a=False, ws_bytes=None, ew_op="clamp_min"):

@@ -552,4 +552,18 @@ __global__ __launch_bounds__(256) void csr_gram_sum_kernel(const double* __restr
     Gm[e] = a;
 }
 
+// ---- host side: the plans that csrc/dnmf_csr.hip and csrc/dnmf_csr_fit.hip share (one definition: a batched fit must cut the sums
+// of the residual exactly as the single entry points do)
+inline int csr_kpad_of(int k) {
+    if (k < 1 || k > DNMF_MAX_K) return -1;
+    return k <= 16 ? 16 : (k <= 32 ? 32 : (k <= 64 ? 64 : (k <= 128 ? 128 : 256)));
+}
+
+inline int gram_chunks(long rows, int k) {
+    const long nt = cdiv(k, 16) * cdiv(k, 16);
+    return (int)std::max<long>(1, std::min<long>(cdiv(rows, 512), std::max<long>(8, 256 / nt)));
+}
+
+inline long resid_waves(long rows) { return std::min<long>(round_up(std::max<long>(rows, 1), 4), CSR_RESID_WAVES); }
+
 }  // namespace

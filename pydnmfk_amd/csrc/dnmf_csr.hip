@@ -9,18 +9,6 @@
 
 namespace {
 
-inline int csr_kpad_of(int k) {
-    if (k < 1 || k > DNMF_MAX_K) return -1;
-    return k <= 16 ? 16 : (k <= 32 ? 32 : (k <= 64 ? 64 : (k <= 128 ? 128 : 256)));
-}
-
-inline int gram_chunks(long rows, int k) {
-    const long nt = cdiv(k, 16) * cdiv(k, 16);
-    return (int)std::max<long>(1, std::min<long>(cdiv(rows, 512), std::max<long>(8, 256 / nt)));
-}
-
-inline long resid_waves(long rows) { return std::min<long>(round_up(std::max<long>(rows, 1), 4), CSR_RESID_WAVES); }
-
 struct ResidWs { size_t gw, gh, dpart, total; int ncw, nch; long nw; };
 
 ResidWs resid_layout(long rows, long cols, int k, long nseg) {

@@ -1173,8 +1173,9 @@ HIP_OPS_BF16X6 = HipOpsBf16x6()
 class HipCsrOps(HipOps):
     """The operator set for a SPARSE data block (pydnmfk_amd.sparse.SparseBlock): the eight operations that touch A run on its
     CSR images (csrc/dnmf_csr.h, `dnmf_csr_*`); everything else of a step -- update kernels, Gram matrices, clamps,
-    normalisation -- is the fp32 code of HipOps, which never sees A.  There is no fused local step and no whole fit for sparse
-    data (`mu_fro_step`, `mu_kl_step`, `fit` refuse it): the host's choreography sequences the primitives.  A dense tensor
+    normalisation -- is the fp32 code of HipOps, which never sees A.  There is no fused local step for sparse data (`mu_fro_step`,
+    `mu_kl_step` refuse it): the host's choreography sequences the primitives.  `fit` takes one block, or a list of blocks that share
+    one pattern, for method 'mu' (dnmf_csr_mu_fit_batch); sparse hals / bcd have no whole fit.  A dense tensor
     in A's place (BCD asks for the squared norms of W and H) takes the dense kernels.
     A block whose unstored entries are MISSING (`A.missing == 'unstored'`) takes the masked operations: `masked_aht_pair` /
     `masked_wta_pair` (numerator and denominator of the rule over the stored positions, as one contiguous [num | den] buffer for
@@ -1385,8 +1386,54 @@ class HipCsrOps(HipOps):
         return super().mu_kl_step(A, W, H, eps, w_update, clamp)
 
     def fit(self, method, norm, A, W, H, eps, w_update, itr, column_sweep=False):
-        self._dense_only("a whole-fit entry point", A)
-        return super().fit(method, norm, A, W, H, eps, w_update, itr, column_sweep=column_sweep)
+        """A SparseBlock with matrices W, H -- one problem -- or a list of B SparseBlocks that share ONE pattern (`sparse.same_pattern`:
+        the perturbed copies of an NMFk sweep) with stacks W [B][m][k], H [B][k][n]: `itr` MU steps (norm 'fro' / 'kl', under the block's
+        meaning of an unstored entry), normalize_features and the squared norms of relative_err in ONE library call
+        (dnmf_csr_mu_fit_batch: the index stream is read once per tile of problems; bit-identical to the step loop, problem by problem).
+        W, H are updated in place; returns the device tensor [B][2] of {sum (A - W H)^2, sum A^2}, both over the stored positions under
+        missing='unstored'.  Sparse hals / bcd have no whole fit.  Dense tensors: the inherited entry points."""
+        blocks = list(A) if isinstance(A, (list, tuple)) else [A]
+        if not all(self._sp(b) for b in blocks):
+            if len(blocks) != 1 or isinstance(A, (list, tuple)):
+                raise TypeError("fit: a list of data blocks must hold SparseBlocks only")
+            return super().fit(method, norm, A, W, H, eps, w_update, itr, column_sweep=column_sweep)
+        method, norm = str(method).lower(), str(norm).lower()
+        if method != "mu" or norm not in ("fro", "kl"):
+            self._dense_only("a whole-fit entry point", blocks[0])
+        from .sparse import same_pattern, value_stacks
+        A0, B = blocks[0], len(blocks)
+        self._req_sp(A0)
+        batched = W.dim() == 3
+        if H.dim() != W.dim() or (not batched and B != 1):
+            raise ValueError("fit: one SparseBlock takes matrices W, H; a list of B blocks takes stacks [B][m][k], [B][k][n]")
+        W3, H3 = (W, H) if batched else (W[None], H[None])
+        _req(W3[0], "W"); _req(H3[0], "H")
+        m, n = A0.shape
+        k = W3.shape[2]
+        if tuple(W3.shape) != (B, m, k) or tuple(H3.shape) != (B, k, n):
+            raise ValueError("fit: %d block(s) of shape %s, W %s, H %s do not match" % (B, (m, n), tuple(W3.shape), tuple(H3.shape)))
+        if any(not same_pattern(b, A0) or b.missing != A0.missing for b in blocks[1:]):
+            raise ValueError("fit: the blocks of a batch must share one pattern (SparseBlock.with_values) and one meaning of `missing`")
+        if A0.nnz < 1:
+            raise ValueError("fit: a block without stored entries has no whole fit")
+        val, t_val = value_stacks(blocks)
+        nseg = int(max(A0.nseg, A0.t_nseg))
+        nbytes = lib.dnmf_csr_fit_ws_bytes(int(m), int(n), int(k), B, nseg)
+        if nbytes == 0:
+            raise ValueError("fit: bad problem shape m=%d n=%d k=%d batch=%d" % (m, n, k, B))
+        ws = _scratch(nbytes, A0.device)
+        sq = torch.empty(B, 2, dtype=torch.float64, device=A0.device)
+
+        def lists(rows, segptr, n_long, nseg_):
+            return (rows.data_ptr() if n_long else None, segptr.data_ptr() if n_long else None, int(n_long), int(nseg_))
+        check(lib.dnmf_csr_mu_fit_batch(
+            int(m), int(n), int(k), B, int(A0.nnz),
+            A0.crow.data_ptr(), A0.col.data_ptr(), *lists(A0.long_rows, A0.long_segptr, A0.n_long, A0.nseg),
+            A0.t_crow.data_ptr(), A0.t_col.data_ptr(), *lists(A0.t_long_rows, A0.t_long_segptr, A0.t_n_long, A0.t_nseg),
+            val.data_ptr(), t_val.data_ptr(), val.stride(0), W3.data_ptr(), _ld(W3[0]), W3.stride(0), H3.data_ptr(), _ld(H3[0]), H3.stride(0),
+            int(norm == "kl"), int(A0.missing == "unstored"), float(eps), int(bool(w_update)), int(itr), ws.data_ptr(), ws.numel(),
+            sq.data_ptr(), _stream()))
+        return sq
 
     # ---- NMFk on a sparse block: the two operations of the sweep that touch A outside a fit
     sparse_nmfk = True
@@ -1394,12 +1441,13 @@ class HipCsrOps(HipOps):
     def perturb_uniform(self, X, noise_var, seed, out=None):
         """A SparseBlock: a NEW block with X's pattern (index arrays and long-row lists shared, `SparseBlock.with_values`) whose
         values are X's times (1 + nv + 2 nv U) -- U keyed by (seed, position in the dense block), so both images hold what
-        HipOps.perturb_uniform gives the densified block at the stored positions, bit for bit.  Dense tensors: the inherited path."""
+        HipOps.perturb_uniform gives the densified block at the stored positions, bit for bit.  `out`: the pair (val, t_val) the new
+        block's values are written to (rows of the stacks a batched fit reads).  Dense tensors: the inherited path."""
         if not self._sp(X):
             return super().perturb_uniform(X, noise_var, seed, out=out)
         self._req_sp(X)
         m, n = X.shape
-        val, t_val = torch.empty_like(X.val), torch.empty_like(X.t_val)
+        val, t_val = out if out is not None else (torch.empty_like(X.val), torch.empty_like(X.t_val))
         if X.nnz:
             sd = int(seed) & (2**64 - 1)
             check(lib.dnmf_csr_perturb_uniform(X.crow.data_ptr(), X.col.data_ptr(), X.val.data_ptr(), m, n, 0, float(noise_var), sd,

@@ -104,10 +104,11 @@ def fit_kind(A_ij, params, k=None):
         norm = params.norm = 'is'
     weighted = getattr(params, "weights", None) is not None
     family = "weighted" if weighted else norm if norm in ("is", "beta") else None
-    # (no batched sparse, masked or weighted entry point, and the launch-chain Itakura-Saito / beta fits take one problem per call; the
+    # (no batched masked or weighted entry point, and the launch-chain Itakura-Saito / beta fits take one problem per call; the
     #  resident ones take a batch of every shape one workgroup holds, weighted fits among them: ops.resident_fit,
-    #  dnmf_pair_resident_fit_batch / dnmf_pair_resident_weighted_fit_batch)
-    batchable = form == "dense" and family is None
+    #  dnmf_pair_resident_fit_batch / dnmf_pair_resident_weighted_fit_batch.  Sparse fits that share one pattern run together:
+    #  dnmf_csr_mu_fit_batch)
+    batchable = form in ("dense", "sparse") and family is None
     if _resident_asked(form, norm, weighted, A_ij, params) and (k if k is not None else getattr(params, "k", None)) is not None:
         from .engine import HipOps
         batchable = HipOps.resident_refusal(int(A_ij.shape[0]), int(A_ij.shape[1]), int(k if k is not None else params.k)) is None
@@ -577,6 +578,8 @@ class PyNMF:
             return hasattr(ops, "resident_fit" if self._resident else "weighted_fit")   # (resident: a batch per call)
         if self._masked_dense:
             return name == "hip-masked" and hasattr(ops, "fit") and method == "mu" and norm in ("fro", "kl")
+        if self._sparse:                                            # dnmf_csr_mu_fit_batch, under both meanings of an unstored entry
+            return name == "hip-csr" and hasattr(ops, "fit") and method == "mu" and norm in ("fro", "kl") and self.A_ij.nnz > 0
         return (not self._sparse and name in ("hip", "hip-f64") and hasattr(ops, "fit") and not (name == "hip-f64" and self.k > 128)
                 and (method, norm) in _NATIVE_FITS and not (method == "bcd" and (name != "hip" or self.a_dtype != torch.float32)))
 
@@ -649,13 +652,19 @@ class PyNMF:
                     and f.A_ij.dtype == f0.A_ij.dtype and f.A_ij.device == f0.A_ij.device and f.W_i.shape == f0.W_i.shape
                     and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k, f.beta, f._resident, f._weighted) ==
                     (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k, f0.beta, f0._resident, f0._weighted))
-        if len(fits) < 2 or not all(same(f) for f in fits):
+        sparse = f0 is not None and f0._sparse
+        if sparse:                                          # one pattern in memory (SparseBlock.with_values), one meaning of `missing`
+            from .sparse import same_pattern
+            shared = all(f._sparse and same_pattern(f.A_ij, f0.A_ij) and f.A_ij.missing == f0.A_ij.missing for f in fits)
+        if len(fits) < 2 or not all(same(f) for f in fits) or (sparse and not shared):
             return [f.fit() for f in fits]
         if f0.method.lower() not in ('mu', 'hals', 'bcd'):
             raise NotImplementedError("method '%s' is not part of the MI355X engine (mu / hals / bcd)" % f0.method)
         A = getattr(f0, "_stack", None)
-        if A is None or A.shape[0] != len(fits) or any(getattr(f, "_stack", None) is not A or f.A_ij.data_ptr() != A[b].data_ptr()
-                                                       for b, f in enumerate(fits)):
+        if sparse:
+            A = [f.A_ij for f in fits]                      # (ops.fit reads their values as stacks: sparse.value_stacks)
+        elif A is None or A.shape[0] != len(fits) or any(getattr(f, "_stack", None) is not A or f.A_ij.data_ptr() != A[b].data_ptr()
+                                                         for b, f in enumerate(fits)):
             A = stack_alloc(len(fits), f0.A_ij.shape[0], f0.A_ij.shape[1], f0.A_ij.dtype, f0.A_ij.device)
             for b, f in enumerate(fits):                    # (callers that adopt_stack() as they go never get here)
                 f.adopt_stack(A, b)

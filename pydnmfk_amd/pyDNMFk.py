@@ -61,7 +61,7 @@ class sample:
     def randM(self):
         nv = self.noise_var
         if self.sparse is not None:
-            self.X_per = self.sparse.uniform(nv, self.seed)
+            self.X_per = self.sparse.uniform(nv, self.seed) if self.out is None else self.sparse.uniform(nv, self.seed, out=self.out)
             return
         if isinstance(self.X, torch.Tensor):
             if self.X.is_cuda:      # one fused pass with a counter-based generator (dnmf_perturb_uniform): 1 GB of traffic per fit at
@@ -80,7 +80,7 @@ class sample:
 
     def poisson(self):
         if self.sparse is not None:
-            self.X_per = self.sparse.poisson(self.seed)
+            self.X_per = self.sparse.poisson(self.seed) if self.out is None else self.sparse.poisson(self.seed, out=self.out)
             return
         nan = self.missing == "nan"
         # (what lies under a zero weight is a gap as well, and no rate: the draw there is Poisson(0) = 0, never read, and no NaN is put back)
@@ -150,25 +150,40 @@ class SparseSweep:
             self._perm = self.blk.transpose_perm()
         return self._perm
 
-    def _with(self, val):
-        return self.blk.with_values(val, val[self.perm])
+    def new_stack(self, B):
+        """[(val, t_val)] * B: rows of two value stacks (sparse.alloc_value_stacks) for B perturbed copies that are fitted together"""
+        from .sparse import alloc_value_stacks
+        val, t_val = alloc_value_stacks(B, self.blk.nnz, self.blk.device)
+        return [(val[b], t_val[b]) for b in range(B)]
 
-    def uniform(self, nv, seed):
+    def _with(self, val, out=None):
+        """the copy with the values `val` (the block's order); `out`: the pair of rows its two value arrays are written to"""
+        if out is None:
+            return self.blk.with_values(val, val[self.perm])
+        out[0].copy_(val)
+        torch.index_select(out[0], 0, self.perm, out=out[1])
+        return self.blk.with_values(out[0], out[1])
+
+    def uniform(self, nv, seed, out=None):
         blk = self.blk
         if blk.device.type == "cuda" and not self.numpy_io:
             ops = self.ops
             if ops is None:
                 from .engine import HIP_CSR_OPS as ops
-            return ops.perturb_uniform(blk, nv, 0 if seed is None else int(seed))
+            if out is None:
+                return ops.perturb_uniform(blk, nv, 0 if seed is None else int(seed))
+            return ops.perturb_uniform(blk, nv, 0 if seed is None else int(seed), out=out)
         if self._host is None:
             self._host = tuple(t.cpu().numpy() for t in (blk.crow, blk.col, blk.val))
         val = host_uniform_values(*self._host, blk.shape, nv)
-        return self._with(torch.from_numpy(val).to(blk.device))
+        return self._with(torch.from_numpy(val).to(blk.device), out)
 
-    def poisson(self, seed):
+    def poisson(self, seed, out=None):
         g = torch.Generator(device=self.blk.device)
         g.manual_seed(0 if seed is None else int(seed))
-        return self._with(torch.poisson(self.blk.val, generator=g))
+        # (a draw of 0 stays stored: with_values keeps every position, so the copies of a sweep still share the source's pattern;
+        #  PyNMF.fit_batch asks sparse.same_pattern of every batch and fits copies that do not share one on their own)
+        return self._with(torch.poisson(self.blk.val, generator=g), out)
 
 
 def _np(x):
@@ -431,6 +446,8 @@ class PyNMFk:
                 if nb > 1 and stack is None and isinstance(self.A_ij, torch.Tensor) and self.A_ij.is_cuda and self.A_ij.dim() == 2:
                     stack = stack_alloc(len(chunk), self.A_ij.shape[0], self.A_ij.shape[1], self.A_ij.dtype,
                                         self.A_ij.device)            # the perturbed copies are written straight into it
+                if nb > 1 and stack is None and self._sparse:
+                    stack = self.sweep.new_stack(len(chunk))         # rows of the two value stacks the batched fit reads
                 data = sample(data=self.A_ij, noise_var=self.noise_var, method=self.sampling, seed=perturbation * 1000,
                               out=None if stack is None else stack[b], sparse=self.sweep,
                               missing="nan" if self.kind.form == "nan" else None,
@@ -439,7 +456,7 @@ class PyNMFk:
                 if getattr(self.params, "rng", None) == "device":       # device-drawn init: one seed per (perturbation, k)
                     self.params.init_seed = perturbation * 1000 + self.k
                 f = PyNMF(data, factors=None, params=self.params, ops=self.ops)                          # :230
-                if nb > 1:
+                if nb > 1 and not self._sparse:                     # (sparse copies share a pattern and hold rows of the value stacks)
                     if stack is None or tuple(stack.shape[1:]) != tuple(f.A_ij.shape) or stack.dtype != f.A_ij.dtype:
                         if b == 0:           # (host data, bf16 storage of fp32 input, pruned shapes: the stack takes the fit's block)
                             stack = stack_alloc(len(chunk), f.A_ij.shape[0], f.A_ij.shape[1], f.A_ij.dtype, f.A_ij.device)
@@ -575,6 +592,17 @@ class PyNMFk:
         except Exception:  # noqa: BLE001
             return 1
         m, n = self.A_ij.shape
+        if self._sparse:
+            # scipy input reproduces the reference's numpy stream on the host, O(m n) per copy: those sweeps keep their one-by-one fits
+            # (each still one library call); device input is the path that scales.  Per problem: both value arrays and its share of
+            # the batched fit's workspace at the largest rank
+            if self.sweep is None or self.sweep.numpy_io:
+                return 1
+            from ._lib import lib
+            blk = self.A_ij
+            per = 8 * blk.nnz * 1.25 + lib.dnmf_csr_fit_ws_bytes(int(m), int(n), max(int(self.end_k), 1), 8, int(max(blk.nseg, blk.t_nseg))) / 8 \
+                + (m + n) * max(int(self.end_k), 1) * 4 * 4 + (16 << 20)
+            return int(max(1, min(cap, self.perturbations, (0.6 * free) // per)))
         # per problem: its perturbed copy of the data in the data's own element size (float64 data are 8 bytes; fp32 data that the fit stores as
         # bf16 still pass through a full-size copy first), the float64 operator set's m x n quotient image (one per call, counted per problem to
         # stay on the safe side), the factors and their workspaces

@@ -74,6 +74,48 @@ def _check_dtype(dt):
         raise NotImplementedError("sparse data block: %s sparse data are not provided (float32 values only)" % (dt,))
 
 
+_PATTERN = ("crow", "col", "t_crow", "t_col", "long_rows", "long_segptr", "t_long_rows", "t_long_segptr")
+
+
+def same_pattern(a, b):
+    """a and b hold ONE pattern: the same index arrays and long-row lists in memory (SparseBlock.with_values shares them), not equal copies"""
+    return a.shape == b.shape and a.nnz == b.nnz and all(getattr(a, n_).data_ptr() == getattr(b, n_).data_ptr() for n_ in _PATTERN)
+
+
+def alloc_value_stacks(B, nnz, device):
+    """(val, t_val), each [B][nnz] float32 with rows a multiple of 16 bytes apart: the layout a batched sparse fit reads (include/
+    dnmf_csr_fit_api.h).  An NMFk sweep writes its perturbed copies straight into the rows."""
+    stride = max(4, -(-nnz // 4) * 4)
+    return tuple(torch.empty(B * stride, dtype=torch.float32, device=device).as_strided((B, nnz), (stride, 1)) for _ in range(2))
+
+
+def value_stacks(blocks):
+    """The value arrays of blocks that share one pattern as two stacks [B][nnz]: the blocks' own storage when their values already are
+    the rows of one stack (alloc_value_stacks), else a copy"""
+    b0, B = blocks[0], len(blocks)
+    if B == 1:
+        return b0.val.view(1, -1), b0.t_val.view(1, -1)
+    out = []
+    for name in ("val", "t_val"):
+        rows = [getattr(b, name) for b in blocks]
+        step = (rows[1].data_ptr() - rows[0].data_ptr()) // 4
+        if step >= b0.nnz and step % 4 == 0 and rows[0].data_ptr() % 16 == 0 and \
+                all(r.data_ptr() == rows[0].data_ptr() + 4 * step * i for i, r in enumerate(rows)) and \
+                rows[0].untyped_storage().data_ptr() == rows[-1].untyped_storage().data_ptr():
+            out.append(rows[0].as_strided((B, b0.nnz), (step, 1)))
+        else:
+            st = alloc_value_stacks(B, b0.nnz, b0.device)[0]
+            for i, r in enumerate(rows):
+                st[i].copy_(r)
+            out.append(st)
+    if out[0].stride(0) != out[1].stride(0):                       # (one stride serves both stacks)
+        st = alloc_value_stacks(B, b0.nnz, b0.device)
+        for dst, src in zip(st, out):
+            dst.copy_(src)
+        out = list(st)
+    return out[0], out[1]
+
+
 MISSING = (None, "unstored")
 
 
