@@ -998,5 +998,7 @@ int dnmf_clock_probe(unsigned long long* samples, int n, int naps, void* stream)
 #include "dnmf_resident_api.h"
 /* whole MU fits of sparse blocks, batched over a shared pattern: dnmf_csr_fit_* and dnmf_csr_mu_fit_batch, likewise */
 #include "dnmf_csr_fit_api.h"
+/* whole pair-rule fits of a batch of mid-size problems, two launches per step for all of them (dnmf_pair_slab_*), likewise */
+#include "dnmf_slab_api.h"
 
 #endif /* DNMF_H */

@@ -314,6 +314,11 @@ RESIDENT_SIGNATURES["dnmf_pair_resident_weighted_fit_batch"] = _sig[:5] + [c_voi
 RESIDENT_PLAN_FIELDS = ("eligible", "lds_bytes", "kp", "waves", "row_tiles_per_wave", "col_tiles_per_wave", "row_tiles", "col_tiles")
 RESIDENT_NOT_TAKEN = 1             # DNMF_RESIDENT_NOT_TAKEN
 RESIDENT_MAX_K, RESIDENT_LDS_MAX = 32, 160 * 1024
+# the same fits of a batch of mid-size problems, two launches per step for all of them (include/dnmf_slab_api.h, csrc/dnmf_slab.hip), a table
+# of its own as well: the three argument lists of the resident family
+SLAB_SIGNATURES = {"dnmf_pair_slab" + _name[len("dnmf_pair_resident"):]: list(_sig) for _name, _sig in RESIDENT_SIGNATURES.items()}
+SLAB_PLAN_FIELDS = ("eligible", "lds_bytes", "kp", "waves", "row_slabs", "col_slabs", "w_phase_panels", "h_phase_panels")
+SLAB_MAX_K = 64
 # whole MU fits of sparse blocks, batched over a shared pattern (include/dnmf_csr_fit_api.h, csrc/dnmf_csr_fit.hip), a table of its own as
 # well: plan m n k batch out: long[6]; fit m n k batch nnz | crow col long_rows long_segptr n_long nseg | the same six of the transpose |
 # val t_val val_stride | W ldw w_stride | H ldh h_stride | norm missing eps w_update itr | ws ws_bytes sq_out stream
@@ -344,7 +349,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, args in list(SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BETA_NMFK_SIGNATURES.items()) \
             + list(WEIGHTED_SIGNATURES.items()) + list(WEIGHTED_NMFK_SIGNATURES.items()) + list(F64_DIV_SIGNATURES.items()) \
-            + list(RESIDENT_SIGNATURES.items()) + list(CSR_FIT_SIGNATURES.items()):
+            + list(RESIDENT_SIGNATURES.items()) + list(CSR_FIT_SIGNATURES.items()) + list(SLAB_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI drifted from include/dnmf.h
         fn.argtypes = args
         fn.restype = _RESTYPES.get(name, c_int)
@@ -385,6 +390,14 @@ def resident_plan(m, n, k):
     out = (c_long * len(RESIDENT_PLAN_FIELDS))()
     check(lib.dnmf_pair_resident_plan(int(m), int(n), int(k), out))
     return dict(zip(RESIDENT_PLAN_FIELDS, out))
+
+
+def slab_plan(m, n, k):
+    """dnmf_pair_slab_plan as a dict of SLAB_PLAN_FIELDS: whether the slab kernels serve an m x n problem at rank k, KP, the LDS bytes of
+    a workgroup, the 64-row / 64-column slabs of the two phases and the panels a workgroup of each walks (host arithmetic, no GPU)"""
+    out = (c_long * len(SLAB_PLAN_FIELDS))()
+    check(lib.dnmf_pair_slab_plan(int(m), int(n), int(k), out))
+    return dict(zip(SLAB_PLAN_FIELDS, out))
 
 
 def csr_fit_plan(m, n, k, batch=1):

@@ -913,23 +913,34 @@ class HipOps(_DivFamily):
         `V`: per-entry weights, the whole fit of `weighted_fit` under any of its four norms (dnmf_pair_resident_weighted_fit_batch) and
         its pair {sum v (A - W H)^2, sum v A^2}: a matrix, or a stack [B][m][n]; a matrix next to stacks is shared by every problem."""
         from ._lib import RESIDENT_NOT_TAKEN
+        rc, sq, (m, n, k) = self._pair_stack_fit("resident", self.resident_refusal, norm, beta, A, W, H, eps, w_update, itr, V)
+        if rc == RESIDENT_NOT_TAKEN:
+            raise NotImplementedError("fit_loop='resident': this device does not give one workgroup the LDS a %d x %d block at k = %d "
+                                      "needs" % (m, n, k))
+        check(rc)
+        return sq
+
+    def _pair_stack_fit(self, family, refusal, norm, beta, A, W, H, eps, w_update, itr, V):
+        """`resident_fit` and `slab_fit` up to the return code: the checks of the operands, the refusal of the family by name, and the call
+        of dnmf_pair_<family>_fit_batch or, with weights, dnmf_pair_<family>_weighted_fit_batch.  Returns (rc, sq, (m, n, k))."""
+        who = family + "_fit"
         norm = str(norm).lower()
         if V is not None:
             mode = self._weighted_mode(norm, beta)
         elif norm not in ("is", "beta"):
-            raise ValueError("resident_fit: norm %r ('is' or 'beta')" % (norm,))
+            raise ValueError("%s: norm %r ('is' or 'beta')" % (who, norm))
         else:
             mode = (1,) + self._beta_mode(beta) if norm == "beta" else (0, 0.0)
         if W.dim() != A.dim() or H.dim() != A.dim() or A.dim() not in (2, 3):
-            raise ValueError("resident_fit: A, W, H must all be matrices or all be stacks")
+            raise ValueError("%s: A, W, H must all be matrices or all be stacks" % who)
         A3, W3, H3 = (A, W, H) if A.dim() == 3 else (A[None], W[None], H[None])
         for t, name in ((A3, "A"), (W3, "W"), (H3, "H")):
             _req(t[0], name)
         B, m, n = A3.shape
         k = W3.shape[2]
         if tuple(W3.shape) != (B, m, k) or tuple(H3.shape) != (B, k, n):
-            raise ValueError("resident_fit: shapes A %s, W %s, H %s do not match" % (tuple(A3.shape), tuple(W3.shape), tuple(H3.shape)))
-        why = self.resident_refusal(int(m), int(n), int(k))
+            raise ValueError("%s: shapes A %s, W %s, H %s do not match" % (who, tuple(A3.shape), tuple(W3.shape), tuple(H3.shape)))
+        why = refusal(int(m), int(n), int(k))
         if why:
             raise NotImplementedError(why)
         sq = torch.empty(B, 2, dtype=torch.float64, device=A.device)
@@ -938,15 +949,36 @@ class HipOps(_DivFamily):
                 int(bool(w_update)), int(itr), int(B), sq.data_ptr(), _stream())
         if V is not None:
             if V.dim() not in (2, A.dim()) or tuple(V.shape[-2:]) != (m, n) or (V.dim() == 3 and V.shape[0] != B):
-                raise ValueError("resident_fit: weights %s must have the shape of A %s, or of one of its problems" % (tuple(V.shape), tuple(A.shape)))
+                raise ValueError("%s: weights %s must have the shape of A %s, or of one of its problems" % (who, tuple(V.shape), tuple(A.shape)))
             _req(V if V.dim() == 2 else V[0], "weights")
             v_args = (V.data_ptr(), V.stride(0) if V.dim() == 3 else 0, _ld(V if V.dim() == 2 else V[0]))     # a matrix: stride 0, shared
-            rc = lib.dnmf_pair_resident_weighted_fit_batch(*mode, *a_args, *v_args, *tail)
+            rc = getattr(lib, "dnmf_pair_%s_weighted_fit_batch" % family)(*mode, *a_args, *v_args, *tail)
         else:
-            rc = lib.dnmf_pair_resident_fit_batch(*mode, *a_args, *tail)
-        if rc == RESIDENT_NOT_TAKEN:
-            raise NotImplementedError("fit_loop='resident': this device does not give one workgroup the LDS a %d x %d block at k = %d "
-                                      "needs" % (m, n, k))
+            rc = getattr(lib, "dnmf_pair_%s_fit_batch" % family)(*mode, *a_args, *tail)
+        return rc, sq, (m, n, k)
+
+    # ---- the same fits of a BATCH of mid-size problems, two launches per step for all of them (csrc/dnmf_slab.h, dnmf_pair_slab_*): k <= 64,
+    # a workgroup owns 64 rows (W phase) or 64 columns (H phase) of one problem and streams the other factor through its LDS.
+    # `params.fit_loop = 'slab'` selects it
+    @staticmethod
+    def slab_refusal(m, n, k):
+        """None where the slab kernels serve an m x n problem at rank k, else the sentence that names the limit"""
+        from ._lib import SLAB_MAX_K, slab_plan
+        if not 1 <= k <= SLAB_MAX_K:
+            return "fit_loop='slab' with k = %d is not provided: the slab kernels serve 1 <= k <= %d" % (k, SLAB_MAX_K)
+        if not slab_plan(m, n, k)["eligible"]:
+            return "fit_loop='slab' with a %d x %d block is not provided: the slab kernels serve up to 2^30 rows and columns" % (m, n)
+        return None
+
+    def slab_fit(self, norm, beta, A, W, H, eps, w_update, itr, V=None):
+        """The whole fit of `is_fit` (norm 'is') or `beta_fit` (norm 'beta') of one problem or of a stack of same-shape problems, every
+        step two kernel launches for ALL of them (dnmf_pair_slab_fit_batch).  A, W, H are matrices or stacks [B][m][n], [B][m][k],
+        [B][k][n] with any row pitches and member distances; problem b of a stack has the bits of the same problem on its own.  W, H are
+        updated in place; returns the device tensor [B][2] of {sum (A - W H)^2, sum A^2}.  A rank beyond 64 is refused by name
+        (NotImplementedError): there is no other path behind this call.
+        `V`: per-entry weights, the whole fit of `weighted_fit` under any of its four norms (dnmf_pair_slab_weighted_fit_batch) and its
+        pair {sum v (A - W H)^2, sum v A^2}: a matrix, or a stack [B][m][n]; a matrix next to stacks is shared by every problem."""
+        rc, sq, _ = self._pair_stack_fit("slab", self.slab_refusal, norm, beta, A, W, H, eps, w_update, itr, V)
         check(rc)
         return sq
 

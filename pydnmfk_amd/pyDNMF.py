@@ -78,7 +78,17 @@ def _resident_asked(form, norm, weighted, A_ij, params):
     """`params.fit_loop = 'resident'` on a fit the resident kernels are written for (csrc/dnmf_resident.h): dense float32 data under
     norm 'is' / 'beta' -- with `params.weights` under fro / kl / is / beta --, method 'mu', fp32 arithmetic, no `missing`, one rank.  Any
     other fit ignores the value (an unweighted fro / kl fit among them)."""
-    if getattr(params, "fit_loop", None) != "resident" or form != "dense" or str(norm).lower() not in (
+    return _pair_loop_asked("resident", form, norm, weighted, A_ij, params)
+
+
+def _slab_asked(form, norm, weighted, A_ij, params):
+    """`params.fit_loop = 'slab'` on a fit the slab kernels are written for (csrc/dnmf_slab.h): the conditions of `_resident_asked`, word
+    for word.  Any other fit ignores the value."""
+    return _pair_loop_asked("slab", form, norm, weighted, A_ij, params)
+
+
+def _pair_loop_asked(loop, form, norm, weighted, A_ij, params):
+    if getattr(params, "fit_loop", None) != loop or form != "dense" or str(norm).lower() not in (
             ("fro", "kl", "is", "beta") if weighted else ("is", "beta")):
         return False
     grid = getattr(params, "grid", None) or (getattr(params, "p_r", 1), getattr(params, "p_c", 1))
@@ -107,11 +117,15 @@ def fit_kind(A_ij, params, k=None):
     # (no batched masked or weighted entry point, and the launch-chain Itakura-Saito / beta fits take one problem per call; the
     #  resident ones take a batch of every shape one workgroup holds, weighted fits among them: ops.resident_fit,
     #  dnmf_pair_resident_fit_batch / dnmf_pair_resident_weighted_fit_batch.  Sparse fits that share one pattern run together:
-    #  dnmf_csr_mu_fit_batch)
+    #  dnmf_csr_mu_fit_batch.  fit_loop='slab': the same kinds of fit as the resident ones at any shape up to k = 64, every step two
+    #  launches for the whole batch: ops.slab_fit, dnmf_pair_slab_fit_batch / dnmf_pair_slab_weighted_fit_batch)
     batchable = form in ("dense", "sparse") and family is None
     if _resident_asked(form, norm, weighted, A_ij, params) and (k if k is not None else getattr(params, "k", None)) is not None:
         from .engine import HipOps
         batchable = HipOps.resident_refusal(int(A_ij.shape[0]), int(A_ij.shape[1]), int(k if k is not None else params.k)) is None
+    elif _slab_asked(form, norm, weighted, A_ij, params) and (k if k is not None else getattr(params, "k", None)) is not None:
+        from .engine import HipOps
+        batchable = HipOps.slab_refusal(int(A_ij.shape[0]), int(A_ij.shape[1]), int(k if k is not None else params.k)) is None
     return FitKind(form, norm, beta, weighted, family, batchable)
 
 
@@ -242,6 +256,13 @@ class PyNMF:
         if self._resident:
             from .engine import HipOps
             why = HipOps.resident_refusal(int(self.m_loc), int(self.n_loc), int(self.k))
+            if why:
+                raise NotImplementedError(why)
+        # params.fit_loop = 'slab': every step two launches for a whole batch (csrc/dnmf_slab.h); a rank beyond its limit is refused by name
+        self._slab = _slab_asked(kind.form, kind.norm, kind.weighted, self.A_ij, self.params)
+        if self._slab:
+            from .engine import HipOps
+            why = HipOps.slab_refusal(int(self.m_loc), int(self.n_loc), int(self.k))
             if why:
                 raise NotImplementedError(why)
 
@@ -575,7 +596,7 @@ class PyNMF:
         if self.kind.family is not None and name != "hip":
             return False                                            # (dnmf_is_mu_fit / dnmf_beta_mu_fit / dnmf_weighted_mu_fit live in the fp32 operator set only)
         if self._weighted:                                          # dnmf_weighted_mu_fit: one problem per call, every norm it serves
-            return hasattr(ops, "resident_fit" if self._resident else "weighted_fit")   # (resident: a batch per call)
+            return hasattr(ops, "resident_fit" if self._resident else "slab_fit" if self._slab else "weighted_fit")   # (resident, slab: a batch per call)
         if self._masked_dense:
             return name == "hip-masked" and hasattr(ops, "fit") and method == "mu" and norm in ("fro", "kl")
         if self._sparse:                                            # dnmf_csr_mu_fit_batch, under both meanings of an unstored entry
@@ -589,7 +610,9 @@ class PyNMF:
         device pairs {sum (A - W H)^2, sum A^2}, one per problem."""
         if self._resident:                                          # dnmf_pair_resident_[weighted_]fit_batch: one workgroup holds the whole fit
             return ops.resident_fit(self.norm, self.beta or 0.0, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr, V=self.V_ij)
-        if self._weighted:                                          # dnmf_weighted_mu_fit
+        if self._slab:                                              # dnmf_pair_slab_[weighted_]fit_batch: two launches per step
+            return ops.slab_fit(self.norm, self.beta or 0.0, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr, V=self.V_ij)
+        if self._weighted:                                         # dnmf_weighted_mu_fit
             return ops.weighted_fit(self.A_ij, self.V_ij, self.W_i, self.H_j, self.eps, self.norm, self.beta or 0.0, self.W_update, self.itr)
         if self._beta:                                              # dnmf_beta_mu_fit
             return ops.beta_fit(self.A_ij, self.W_i, self.H_j, self.eps, self.beta, self.W_update, self.itr)
@@ -650,8 +673,8 @@ class PyNMF:
         def same(f):
             return (f.kind.batchable and f._whole_fit_ok(f._ops()) and f._ops() is f0._ops() and f.A_ij.shape == f0.A_ij.shape
                     and f.A_ij.dtype == f0.A_ij.dtype and f.A_ij.device == f0.A_ij.device and f.W_i.shape == f0.W_i.shape
-                    and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k, f.beta, f._resident, f._weighted) ==
-                    (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k, f0.beta, f0._resident, f0._weighted))
+                    and f.H_j.shape == f0.H_j.shape and (f.method, f.norm, f.itr, f.W_update, f.eps, f.k, f.beta, f._resident, f._slab, f._weighted) ==
+                    (f0.method, f0.norm, f0.itr, f0.W_update, f0.eps, f0.k, f0.beta, f0._resident, f0._slab, f0._weighted))
         sparse = f0 is not None and f0._sparse
         if sparse:                                          # one pattern in memory (SparseBlock.with_values), one meaning of `missing`
             from .sparse import same_pattern
@@ -674,7 +697,7 @@ class PyNMF:
             W[b].copy_(f.W_i)
             H[b].copy_(f.H_j)
         V = None
-        if f0._weighted:                                    # (batchable under weights: the resident kernels alone)
+        if f0._weighted:                                    # (batchable under weights: the resident and the slab kernels)
             v0 = f0.V_ij                                    # one storage for every fit (a sweep keeps its weights): handed over once
             if all(f.V_ij.data_ptr() == v0.data_ptr() and f.V_ij.shape == v0.shape and f.V_ij.stride() == v0.stride() for f in fits):
                 V = v0
@@ -685,6 +708,8 @@ class PyNMF:
         for attempt in (0, 1):
             if f0._resident:                                # (a workgroup per problem: the same bits as the fits one by one)
                 sq = ops.resident_fit(f0.norm, f0.beta or 0.0, A, W, H, f0.eps, f0.W_update, f0.itr, V=V)
+            elif f0._slab:                                  # (a slab of one problem per workgroup: the same bits as well)
+                sq = ops.slab_fit(f0.norm, f0.beta or 0.0, A, W, H, f0.eps, f0.W_update, f0.itr, V=V)
             else:
                 sq = ops.fit(f0.method, f0.norm, A, W, H, f0.eps, f0.W_update, f0.itr,
                              column_sweep=(getattr(f0.params, "hals_sweep", None) == "columns"))
