@@ -1000,5 +1000,7 @@ int dnmf_clock_probe(unsigned long long* samples, int n, int naps, void* stream)
 #include "dnmf_csr_fit_api.h"
 /* whole pair-rule fits of a batch of mid-size problems, two launches per step for all of them (dnmf_pair_slab_*), likewise */
 #include "dnmf_slab_api.h"
+/* robust NMF under the Huber loss by reweighted MU (dnmf_huber_*), likewise */
+#include "dnmf_huber_api.h"
 
 #endif /* DNMF_H */

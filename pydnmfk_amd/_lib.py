@@ -329,6 +329,12 @@ CSR_FIT_SIGNATURES["dnmf_csr_mu_fit_batch"] = ([c_long, c_long, c_int, c_int, c_
                                                + [c_void_p, c_void_p, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_long,
                                                   c_int, c_int, c_float, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p])
 CSR_FIT_PLAN_FIELDS = ("kpad", "g", "bt", "tiles", "w_image_bytes", "h_image_bytes")
+# robust NMF under the Huber loss (include/dnmf_huber_api.h, csrc/dnmf_huber.hip), a table of its own as well: the beta signatures with
+# `float delta` where they take `float beta`; one workspace query serves every entry point, the whole fit included
+HUBER_SIGNATURES = {"dnmf_huber_ws_bytes": [c_long, c_long, c_int]}
+for _name, _twin in (("uht_pair", "aht_pair"), ("wtu_pair", "wta_pair"), ("update_w", "update_w"), ("update_h", "update_h"),
+                     ("loss", "divergence"), ("mu_fit", "mu_fit")):
+    HUBER_SIGNATURES["dnmf_huber_" + _name] = list(BETA_SIGNATURES["dnmf_beta_" + _twin])
 # the W phase from a transposed image of A (csrc/dnmf_timg.hip): build A m n lda At ldat stream; bind the same without the stream
 SIGNATURES["dnmf_wimage_bytes"] = [c_long, c_long]
 SIGNATURES["dnmf_wimage_build"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]
@@ -336,7 +342,7 @@ SIGNATURES["dnmf_wimage_bind"] = [c_void_p, c_long, c_long, c_long, c_void_p, c_
 SIGNATURES["dnmf_wimage_unbind"] = []
 SIGNATURES["dnmf_set_wimage"] = [c_int]
 SIGNATURES["dnmf_wimage_plan"] = [c_long, c_long, c_int, c_long, c_int, c_int, c_void_p]      # out: int[6]
-_RESTYPES = {"dnmf_csr_fit_ws_bytes": c_size_t, "dnmf_is_f64_ws_bytes": c_size_t, "dnmf_beta_f64_ws_bytes": c_size_t, "dnmf_weighted_column_div_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes_fit": c_size_t, "dnmf_beta_column_div_ws_bytes": c_size_t, "dnmf_beta_ws_bytes": c_size_t, "dnmf_beta_ws_bytes_fit": c_size_t, "dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
+_RESTYPES = {"dnmf_huber_ws_bytes": c_size_t, "dnmf_csr_fit_ws_bytes": c_size_t, "dnmf_is_f64_ws_bytes": c_size_t, "dnmf_beta_f64_ws_bytes": c_size_t, "dnmf_weighted_column_div_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes": c_size_t, "dnmf_weighted_ws_bytes_fit": c_size_t, "dnmf_beta_column_div_ws_bytes": c_size_t, "dnmf_beta_ws_bytes": c_size_t, "dnmf_beta_ws_bytes_fit": c_size_t, "dnmf_is_column_div_ws_bytes": c_size_t, "dnmf_is_ws_bytes": c_size_t,"dnmf_is_ws_bytes_fit": c_size_t, "dnmf_wimage_bytes": c_size_t, "dnmf_wimage_unbind": None, "dnmf_masked_column_err_ws_bytes": c_size_t, "dnmf_masked_ws_bytes_fit": c_size_t, "dnmf_masked_ws_bytes": c_size_t,"dnmf_masked_reduce_grid": c_long, "dnmf_csr_column_err_ws_bytes": c_size_t, "dnmf_csr_masked_ws_bytes": c_size_t, "dnmf_csr_ws_bytes": c_size_t, "dnmf_ws_bytes_fit": c_size_t, "dnmf_f64_ws_bytes": c_size_t, "dnmf_f64_ws_bytes_fit": c_size_t, "dnmf_last_error": ctypes.c_char_p, "dnmf_ws_bytes": c_size_t, "dnmf_ws_bytes_bf16x6": c_size_t,
              "dnmf_ws_bytes_1d": c_size_t, "dnmf_ws_bytes_hblocks": c_size_t, "dnmf_ws_bytes_2d": c_size_t,
              "dnmf_bcd_ws_bytes_w": c_size_t, "dnmf_bcd_ws_bytes": c_size_t, "dnmf_bcd_ws_bytes_fit": c_size_t}
 
@@ -349,7 +355,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, args in list(SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BETA_NMFK_SIGNATURES.items()) \
             + list(WEIGHTED_SIGNATURES.items()) + list(WEIGHTED_NMFK_SIGNATURES.items()) + list(F64_DIV_SIGNATURES.items()) \
-            + list(RESIDENT_SIGNATURES.items()) + list(CSR_FIT_SIGNATURES.items()) + list(SLAB_SIGNATURES.items()):
+            + list(RESIDENT_SIGNATURES.items()) + list(CSR_FIT_SIGNATURES.items()) + list(SLAB_SIGNATURES.items()) \
+            + list(HUBER_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI drifted from include/dnmf.h
         fn.argtypes = args
         fn.restype = _RESTYPES.get(name, c_int)

@@ -19,8 +19,9 @@
 // over column splits (W side) and row chunks (H side) are left as partials and added in split / chunk order by masked_reduce_kernel --
 // no float atomics, so a fit's factors are bit-reproducible.  Plain launch chains: no workgroup waits for another one.
 //
-// The pair kernels serve a third rule, Itakura-Saito (MODE = PAIR_IS, csrc/dnmf_is.h), and a fourth, the beta-divergence for a runtime
-// beta (MODE = PAIR_BETA, csrc/dnmf_beta.h).  Everything around them exists once, in the
+// The pair kernels serve a third rule, Itakura-Saito (MODE = PAIR_IS, csrc/dnmf_is.h), a fourth, the beta-divergence for a runtime
+// beta (MODE = PAIR_BETA, csrc/dnmf_beta.h), and a fifth, the Huber loss by reweighting for a runtime threshold delta (MODE =
+// PAIR_HUBER, csrc/dnmf_huber.h).  Everything around them exists once, in the
 // host part at the end of this file: plans, the launcher of each side, the ending, the plan report and the chain of a whole fit.
 #pragma once
 #include "dnmf_common.h"
@@ -34,11 +35,19 @@ namespace {
 
 // the element-wise step: (u_n, u_d) of one element from its datum `a` and its model value s = <W[r], H[:, c]>.  MODE: the two masked
 // rules above, or the Itakura-Saito pair of csrc/dnmf_is.h, which has no mask (its padding argument is written there), or the pair of
-// a general beta-divergence (csrc/dnmf_beta.h: no mask either; `e` = beta - 2 is NnArgs::pexp, which the other modes never read)
-enum { PAIR_FRO = 0, PAIR_KL = 1, PAIR_IS = 2, PAIR_BETA = 3 };
+// a general beta-divergence (csrc/dnmf_beta.h: no mask either; `e` = beta - 2 is NnArgs::pexp, which the other modes never read), or
+// the reweighted pair of the Huber loss (csrc/dnmf_huber.h: no mask; `e` is the threshold delta there, in the same NnArgs::pexp)
+enum { PAIR_FRO = 0, PAIR_KL = 1, PAIR_IS = 2, PAIR_BETA = 3, PAIR_HUBER = 4 };
 template <int MODE>
 __device__ __forceinline__ void masked_pair(float a, float s, float eps, float e, float& un, float& ud) {
-    if constexpr (MODE == PAIR_BETA) {
+    if constexpr (MODE == PAIR_HUBER) {
+        const float sp = s + eps;                  // S' = S + eps >= 2^-23
+        // P = min(1, delta / |A - S'|) as delta * rcp(|r|): v_sub_f32, v_rcp_f32 with the abs modifier, v_mul_f32, v_min_f32.  r = 0 gives
+        // rcp = inf and p = 1; delta = inf gives inf (or, at |r| >= 2^126 where rcp flushes to 0, a NaN that v_min_f32 drops) and p = 1
+        const float p = __builtin_fminf(1.f, e * __builtin_amdgcn_rcpf(__builtin_fabsf(a - sp)));
+        un = a * p;                                // A . P
+        ud = sp * p;                               // S' . P
+    } else if constexpr (MODE == PAIR_BETA) {
         const float sp = s + eps;                  // S' = S + eps >= 2^-23
         const float p = __builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf(sp));   // P = S'^e: v_log_f32, v_mul_f32, v_exp_f32
         un = a * p;                                // A . P
@@ -350,7 +359,7 @@ __global__ __launch_bounds__(256) void masked_sqnorm_kernel(const float* __restr
 // ================================================================================================ host side
 // The ONE launch path of the pair kernels above: plans, launchers of both sides, the ending, the plan report and the chain of a whole
 // fit, templated on MODE so that a translation unit instantiates only the kernels of the modes it launches (csrc/dnmf_masked.hip:
-// PAIR_FRO and PAIR_KL; csrc/dnmf_is.hip: PAIR_IS; csrc/dnmf_beta.hip: PAIR_BETA).
+// PAIR_FRO and PAIR_KL; csrc/dnmf_is.hip: PAIR_IS; csrc/dnmf_beta.hip: PAIR_BETA; csrc/dnmf_huber.hip: PAIR_HUBER).
 
 // What a mode chooses: its two plan parameters (below), the form of its rule, and how the messages name its kernels.  The masked
 // modes take these; csrc/dnmf_is.h states the Itakura-Saito ones, csrc/dnmf_beta.h those of a general beta.
@@ -419,8 +428,8 @@ size_t pair_step_bytes(long m, long n, int kt) {
     return align256(std::max(pair_uht_plan<MODE>(m, n, kt).bytes, pair_wtu_plan<MODE>(m, n, kt).bytes));
 }
 
-// the two runtime scalars of a mode whose step and rule take one each (PAIR_BETA: e = beta - 2 and gamma(beta)); every other mode
-// leaves them at what changes nothing
+// the two runtime scalars of a mode whose step and rule take one each (PAIR_BETA: e = beta - 2 and gamma(beta); PAIR_HUBER: e = delta,
+// gamma stays 1); every other mode leaves them at what changes nothing
 struct PairExp { float e = 0.f; float gamma = 1.f; };
 
 NnArgs masked_args(const float* A, long m, long n, long lda, const float* W, long ldw, const float* H, long ldh, int k, float eps) {

@@ -110,6 +110,12 @@ class _Base:
             else:
                 raise NotImplementedError("norm='beta' is provided for method 'mu' only, not for '%s': HALS and BCD are Frobenius "
                                           "methods" % self.method)
+        elif norm == 'HUBER':                                                  # (no counterpart in the reference: csrc/dnmf_huber.h)
+            if method == 'MU':
+                self.HUBER_MU_update(self.W_update, clamp)
+            else:
+                raise NotImplementedError("norm='huber' is provided for method 'mu' only, not for '%s': HALS and BCD are Frobenius "
+                                          "methods" % self.method)
         else:
             raise Exception('Not a valid norm: Choose (fro/kl)')               # dist_nmf.py:91,659
 
@@ -140,7 +146,9 @@ class _Base:
     # ---- Itakura-Saito and the beta-divergence, -2 <= beta <= 4, MU in its majorisation-minimisation form (1D grids).  F = H^T / W:
     #   'is':    S = W H, R = 1 / (S + eps):             num = (A . R . R) F,  den = R F,         X <- X * sqrt(num / (den + eps))
     #   'beta':  S' = W H + eps, P = S'^(beta - 2):      num = (A . P) F,      den = (S' . P) F,  X <- X * (num / (den + eps))^gamma(beta)
-    # (csrc/dnmf_is.h, csrc/dnmf_beta.h).  One body: the operations ops.<norm>_*, which under 'beta' take params.beta after eps
+    #   'huber': S' = W H + eps, P = min(1, delta / |A - S'|):  num = (A . P) F,  den = (S' . P) F,  X <- X * num / (den + eps)
+    # (csrc/dnmf_is.h, csrc/dnmf_beta.h, csrc/dnmf_huber.h).  One body: the operations ops.<norm>_*, which under 'beta' take params.beta
+    # after eps and under 'huber' params.delta
     def _div_MU_update(self, norm, W_update, clamp):
         ops, A = self.ops, self.A_ij
         if self.p_r != 1 and self.p_c != 1:
@@ -156,8 +164,12 @@ class _Base:
             if getattr(self.params, "beta", None) is None:
                 raise ValueError("norm='beta' needs params.beta (a float in -2 <= beta <= 4)")
             mode = (float(self.params.beta),)
+        if norm == "huber":
+            if getattr(self.params, "delta", None) is None:
+                raise ValueError("norm='huber' needs params.delta (a float > 0)")
+            mode = (float(self.params.delta),)
 
-        def op(name):      # ops.<norm>_<name>(..., eps, [beta,] ...): eps is the fourth argument of every one
+        def op(name):      # ops.<norm>_<name>(..., eps, [beta | delta,] ...): eps is the fourth argument of every one
             fn = getattr(ops, "%s_%s" % (norm, name))
             return lambda *a: fn(*a[:4], *mode, *a[4:])
         self._pair_MU_update(norm + "nd", op("update_w"), op("update_h"), op("aht_pair"), op("wta_pair"), op("ratio_update"), W_update, clamp)
@@ -167,6 +179,9 @@ class _Base:
 
     def BETA_MU_update(self, W_update=True, clamp=False):
         self._div_MU_update("beta", W_update, clamp)
+
+    def HUBER_MU_update(self, W_update=True, clamp=False):
+        self._div_MU_update("huber", W_update, clamp)
 
     # ---- per-entry weights V >= 0 of A's shape, sharded like A (`params.weights_block`: this rank's block on the device): the pair of
     # the norm with both halves scaled by V and selected to 0 where v = 0, num = (V . u_n) F, den = (V . u_d) F, then the norm's own rule

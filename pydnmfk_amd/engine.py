@@ -889,6 +889,70 @@ class HipOps(_DivFamily):
         the device tensor [1][2] of {sum (A - W H)^2, sum A^2}."""
         return self._fam_fit("beta", self._beta_mode(beta), A, W, H, eps, w_update, itr)
 
+    # ---- the Huber loss by reweighted MU, delta > 0 (csrc/dnmf_huber.h, dnmf_huber_*): dense non-negative float32 data, 1 <= k <= 128.
+    # With S' = W H + eps and P = min(1, delta / |A - S'|): num = (A . P) F, den = (S' . P) F (F = H^T / W), X <- X * num / (den + eps).
+    # `delta` follows `eps`; one workspace query serves every entry point
+    huber_dtypes = (torch.float32,)    # the data types these operations take (PyNMF and the choreography refuse any other by name)
+    _huber_ranks = "norm='huber' with k = %d: the Huber kernels serve 1 <= k <= 128"
+
+    @staticmethod
+    def _huber_mode(delta):
+        delta = float(delta)
+        if not delta > 0.0:
+            raise ValueError("delta = %r is not accepted: a float > 0 (inf is the Frobenius objective)" % (delta,))
+        return (delta,)
+
+    def _huber(self, what, A, W, H, eps, delta, pair=None):
+        return self._pair_args(what, A, W, H, eps, lib.dnmf_huber_ws_bytes, self._huber_ranks, self._huber_mode(delta), pair=pair)
+
+    def huber_pair_into(self, side, A, W, H, eps, delta, num, den):
+        """(num, den) = ((A . P) F, (S' . P) F) into two views of the caller's (one leading dimension, any pitch): side 'w' (m x k, F = H^T)
+        or 'h' (k x n, F = W)"""
+        head, tail = self._huber("huber pair", A, W, H, eps, delta, pair=(side, num, den))
+        check((lib.dnmf_huber_uht_pair if side == "w" else lib.dnmf_huber_wtu_pair)(*head, *tail))
+        return num, den
+
+    def huber_aht_pair(self, A, W, H, eps, delta, buf):
+        """buf = [num | den], each m x k: (A . P) H^T and (S' . P) H^T"""
+        return self.huber_pair_into("w", A, W, H, eps, delta, *self._halves(buf, tuple(W.shape)))
+
+    def huber_wta_pair(self, A, W, H, eps, delta, buf):
+        """buf = [num | den], each k x n: W^T (A . P) and W^T (S' . P)"""
+        return self.huber_pair_into("h", A, W, H, eps, delta, *self._halves(buf, tuple(H.shape)))
+
+    def huber_update_w(self, A, W, H, eps, delta):
+        """W <- W * num / (den + eps): the pass, then the rule on its partial sums (this rank's W rows see all their columns)"""
+        head, tail = self._huber("huber_update_w", A, W, H, eps, delta)
+        check(lib.dnmf_huber_update_w(*head, *tail))
+        return W
+
+    def huber_update_h(self, A, W, H, eps, delta, clamp=False):
+        """H <- H * num / (den + eps), max(., eps) with `clamp` (this rank's H columns see all their rows)"""
+        head, tail = self._huber("huber_update_h", A, W, H, eps, delta)
+        check(lib.dnmf_huber_update_h(*head, int(bool(clamp)), *tail))
+        return H
+
+    def huber_ratio_update(self, X, num, den, eps, delta, clamp=False):
+        """X <- X * num / (den + eps), max(., eps) with `clamp`: the rule on a pair that was summed over the ranks (the plain ratio:
+        `delta` is inside the pair)"""
+        self._huber_mode(delta)
+        check(lib.dnmf_csr_ratio_update(*self._ratio_args("huber_ratio_update", X, num, den, eps, clamp)))
+        return X
+
+    def huber_loss(self, A, W, H, eps, delta):
+        """sum rho_delta(A - (W H + eps)) over this block: one device double (stored, not accumulated: two calls are bit-identical)"""
+        head, tail = self._huber("huber_loss", A, W, H, eps, delta)
+        out = torch.empty(1, dtype=torch.float64, device=A.device)
+        check(lib.dnmf_huber_loss(*head, out.data_ptr(), *tail))
+        return out
+
+    def huber_fit(self, A, W, H, eps, delta, w_update, itr):
+        """`itr` Huber MU steps (clamps after the steps i % 10 == 0), normalize_features and the squared norms of relative_err in ONE
+        library call (dnmf_huber_mu_fit: the launches of the step loop in its order).  One problem; W, H are updated in place; returns
+        the device tensor [1][2] of {sum (A - W H)^2, sum A^2}."""
+        return self._pair_fit("huber_fit", lib.dnmf_huber_mu_fit, A, W, H, eps, lib.dnmf_huber_ws_bytes, self._huber_ranks,
+                              self._huber_mode(delta), w_update, itr)
+
     # ---- the same two fits of SMALL problems inside one workgroup each (csrc/dnmf_resident.h, dnmf_pair_resident_*): k <= 32, W and H
     # of a problem in LDS for the whole fit, a batch of same-shape problems in ONE launch.  `params.fit_loop = 'resident'` selects it;
     # with weights V the weighted fit of any of the four weighted norms runs the same way (dnmf_pair_resident_weighted_fit_batch)
@@ -1122,6 +1186,7 @@ class HipOpsBf16x6(HipOps):
     beta_dtypes = ()               # (nor of the beta-divergence pairs)
     beta_nmfk = False              # (nor an NMFk sweep under norm='beta')
     weighted_dtypes = ()           # (nor of the weighted pairs)
+    huber_dtypes = ()              # (nor of the Huber pairs)
     kl_uht_hblocks = None          # (no block-column variant of the split kernels: the 2D step concatenates H for them)
     aht_hblocks = None
 

@@ -9,10 +9,11 @@ eps when i % 10 == 0 (after that step's update), and on the last step column-nor
 Everything numeric runs in libdnmf_hip.so; there is no CPU path.
 
 What kind of problem a fit is -- dense, sparse (pydnmfk_amd.sparse) or NaN-marked dense data (`params.missing`), the norm ('fro', 'kl',
-'is', 'beta' with `params.beta`), per-entry weights (`params.weights`) -- is decided ONCE, by `fit_kind()` below; PyNMF and PyNMFk both
+'is', 'beta' with `params.beta`, 'huber' with `params.delta`), per-entry weights (`params.weights`) -- is decided ONCE, by `fit_kind()` below; PyNMF and PyNMFk both
 read that record (pyDNMFk.SWEEP_KINDS is keyed by it).  What each kind refuses is said, in its own words, by the `_*_checks` /
 `_*_refusals` methods; what each kind computes is described in DESIGN.md (its sections on sparse data, on missing entries, on the
-Itakura-Saito and beta-divergence norms and on per-entry weights) and on the methods `is_divergence` ... `weighted_column_divergence`.
+Itakura-Saito and beta-divergence norms, on the Huber loss and on per-entry weights) and on the methods `is_divergence` ...
+`weighted_column_divergence`, `huber_loss`.
 
 Differences from the reference, all deliberate and documented in DESIGN.md:
   * compute dtype follows the data, as in the reference (pyDNMF.py:68): float32 (the tuned path) or float64 (the fp64 matrix
@@ -21,8 +22,8 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
     product in float32: the fit equals the float32 fit of the bf16-rounded data (BASELINE config 5);
   * method is 'mu' (fro / kl), 'hals' (fro) or 'bcd' (fro; float32 data with the fp32 operator set -- float64, bf16-stored A and
     --gemm bf16x6 raise NotImplementedError); init is 'rand' or 'nnsvd' (1D grids);
-  * the kinds the reference does not have: sparse data, missing entries (`params.missing = 'unstored'` / 'nan'), the norms 'is' and
-    'beta', and `params.weights`; `fit()` returns the Frobenius relative error under every norm (the weighted one under weights), and
+  * the kinds the reference does not have: sparse data, missing entries (`params.missing = 'unstored'` / 'nan'), the norms 'is',
+    'beta' and 'huber', and `params.weights`; `fit()` returns the Frobenius relative error under every norm (the weighted one under weights), and
     `divergence()` / `column_statistic()` report the objective and the per-column statistic of the fit's own family;
   * `prune=True` (the reference's default when the attribute is absent) drops all-zero rows / columns before the
     iterations and scatters the factors back afterwards.  numpy callers get float64 factors back in that case, exactly
@@ -64,13 +65,13 @@ def storage_dtype(A_ij, params):
 
 
 _MASKS = ("row_zero_idx_x", "col_zero_idx_x", "row_zero_idx_w", "col_zero_idx_h")
-_NATIVE_FITS = (("mu", "fro"), ("mu", "kl"), ("hals", "fro"), ("bcd", "fro"), ("mu", "is"), ("mu", "beta"))
+_NATIVE_FITS = (("mu", "fro"), ("mu", "kl"), ("hals", "fro"), ("bcd", "fro"), ("mu", "is"), ("mu", "beta"), ("mu", "huber"))
 BETA_RANGE = (-2.0, 4.0)             # where the value of (W H + eps)^(beta - 2) at a padded position is finite in float32 (csrc/dnmf_beta.h)
 
 # form: 'dense' | 'sparse' | 'nan' (dense data, NaN = not observed);  norm: as the fit runs it, after the renaming;  beta: params.beta when
 # the norm was handed over as 'beta' (0.0 where that was renamed to 'is'), else None;  weighted: params.weights is set;  family: whose
 # divergence and per-column statistic the fit reports -- 'weighted' before 'is' / 'beta' (the norm's own would read the entries under
-# zero weights), None for fro / kl;  batchable: whether fits of this kind may run as one batched whole-fit call (PyNMF.fit_batch)
+# zero weights), 'huber' under that norm (its objective is `huber_loss()`; there is no per-column statistic), None for fro / kl;  batchable: whether fits of this kind may run as one batched whole-fit call (PyNMF.fit_batch)
 FitKind = namedtuple("FitKind", ("form", "norm", "beta", "weighted", "family", "batchable"))
 
 
@@ -113,8 +114,10 @@ def fit_kind(A_ij, params, k=None):
     if str(norm).lower() in ('is', 'itakura-saito'):
         norm = params.norm = 'is'
     weighted = getattr(params, "weights", None) is not None
-    family = "weighted" if weighted else norm if norm in ("is", "beta") else None
-    # (no batched masked or weighted entry point, and the launch-chain Itakura-Saito / beta fits take one problem per call; the
+    if str(norm).lower() == 'huber':
+        norm = params.norm = 'huber'
+    family = "weighted" if weighted else norm if norm in ("is", "beta", "huber") else None
+    # (no batched masked or weighted entry point, and the launch-chain Itakura-Saito / beta / Huber fits take one problem per call; the
     #  resident ones take a batch of every shape one workgroup holds, weighted fits among them: ops.resident_fit,
     #  dnmf_pair_resident_fit_batch / dnmf_pair_resident_weighted_fit_batch.  Sparse fits that share one pattern run together:
     #  dnmf_csr_mu_fit_batch.  fit_loop='slab': the same kinds of fit as the resident ones at any shape up to k = 64, every step two
@@ -147,7 +150,7 @@ class PyNMF:
         kind = self.kind = fit_kind(A_ij, params)
         self._sparse, self._masked_dense = kind.form == "sparse", kind.form == "nan"
         self.norm, self.beta, self._weighted = kind.norm, kind.beta, kind.weighted
-        self._is, self._beta = kind.norm == 'is', kind.norm == 'beta'
+        self._is, self._beta, self._huber = kind.norm == 'is', kind.norm == 'beta', kind.norm == 'huber'
         # (sparse data: scipy input is numpy I/O, torch sparse tensors and SparseBlocks get CUDA tensors back)
         self._numpy_io = not (isinstance(A_ij, torch.Tensor) or getattr(A_ij, "is_sparse_block", False))
         self.ops = ops
@@ -196,12 +199,13 @@ class PyNMF:
         self.method = var_init(self.params, 'method', default='mu')
         if kind.beta is not None:
             self._beta_value(self.params)
+        self.delta = self._delta_value(self.params) if self._huber else None
         self.V_ij = None
         if hasattr(self.params, "weights_block"):                   # (the bag may have served a weighted fit before)
             del self.params.weights_block
         if self._weighted:
             self._weighted_refusals(self.norm, self.params, self._sparse, missing, self.a_dtype, self.ops, self.method, self.p_r, self.p_c)
-        if self._is or self._beta:
+        if self._is or self._beta or self._huber:
             self._div_checks(missing)
         if self._weighted:
             self.V_ij = self.params.weights_block = self._weights_block()
@@ -315,22 +319,32 @@ class PyNMF:
 
     # the phrases in which the refusals of the two divergence norms differ: (its kernels' name, the end of the sparse refusal)
     _DIV_WORDS = {"is": ("Itakura-Saito", ": the Itakura-Saito divergence is infinite at a zero entry (dense strictly positive float32 data only)"),
-                  "beta": ("beta-divergence", " (dense float32 data only)")}
+                  "beta": ("beta-divergence", " (dense float32 data only)"),
+                  "huber": ("Huber", " (dense float32 data only)")}
 
     def _div_checks(self, missing):
-        """What is refused under norm='is' and norm='beta', each by name (dense float32 data without missing entries, fp32 arithmetic,
-        method 'mu', 1D grids, k <= 128), and what the data must be: strictly positive under 'is' and for beta <= 0, non-negative for
-        beta > 0.  The ranks agree on that verdict through comm1 BEFORE any of them raises, so none is left alone in a later collective."""
+        """What is refused under norm='is', norm='beta' and norm='huber', each by name (dense float32 data without missing entries, fp32
+        arithmetic, method 'mu', 1D grids, k <= 128; 'huber': float32 only), and what the data must be: strictly positive under 'is' and
+        for beta <= 0, non-negative for beta > 0, finite and non-negative under 'huber'.  The ranks agree on that verdict through comm1
+        BEFORE any of them raises, so none is left alone in a later collective."""
         self._div_refusals(self.norm, self.params, self._sparse, missing, self.a_dtype, self.ops, self.method, self.p_r, self.p_c, self.params.k)
         if self._weighted:
             return                                                  # (the sign condition is tested where v > 0 only: _weights_block)
+        if self._huber:
+            lo, hi = (float(self.A_ij.min()), float(self.A_ij.max())) if self.A_ij.numel() else (0.0, 0.0)
+            bad = not (lo >= 0.0 and hi < float("inf"))             # (a NaN extreme is refused as well)
+            nbad = int(self.comm1.allreduce(1 if bad else 0))
+            if nbad:
+                raise ValueError("norm='huber' needs finite non-negative data: the extreme entries of this rank's block are %g and %g (%d "
+                                 "of %d ranks hold an entry < 0 or not finite)" % (lo, hi, nbad, self.p_r * self.p_c))
+            return
         self._sign_check(self.beta if self._beta else None, float(self.A_ij.min()) if self.A_ij.numel() else 1.0, self.comm1,
                          self.p_r * self.p_c)
 
     @staticmethod
     def _div_refusals(norm, params, sparse, missing, a_dtype, ops, method, p_r, p_c, k):
-        """the refusals of `norm` ('is' or 'beta') that need no look at the data (PyNMFk raises them at construction, with its largest
-        rank as k)"""
+        """the refusals of `norm` ('is', 'beta' or 'huber') that need no look at the data (PyNMFk raises those of 'is' and 'beta' at
+        construction, with its largest rank as k)"""
         kernels, sparse_why = PyNMF._DIV_WORDS[norm]
         if missing is not None:
             raise NotImplementedError("norm='%s' with missing='%s' is not provided (dense data without missing entries only)" % (norm, missing))
@@ -342,8 +356,10 @@ class PyNMF:
             raise NotImplementedError("norm='%s' with --gemm %s is not provided (fp32 arithmetic only)" % (norm, params.gemm))
         # (an operator set names the data types its operations under the norm take, `is_dtypes` / `beta_dtypes`: float32 in the fp32 set,
         #  float64 in the float64 set, none in the split set)
-        #  (ops None: the product's own sets, engine.ops_for -- the fp32 set for float32 data, the float64 set for float64 data)
-        if a_dtype not in (getattr(ops, norm + "_dtypes", ()) if ops is not None else (torch.float32, torch.float64)):
+        #  (ops None: the product's own sets, engine.ops_for -- the fp32 set for float32 data, the float64 set for float64 data, which
+        #   has no Huber operations)
+        if a_dtype not in (getattr(ops, norm + "_dtypes", ()) if ops is not None
+                           else (torch.float32,) if norm == "huber" else (torch.float32, torch.float64)):
             raise NotImplementedError("norm='%s' with %s data is not provided (float32 data only); cast the block to float32"
                                       % (norm, str(a_dtype).replace("torch.", "")))
         method = str(method).lower()
@@ -429,6 +445,17 @@ class PyNMF:
         if not BETA_RANGE[0] <= beta <= BETA_RANGE[1]:
             raise ValueError("norm='beta' with beta = %g is outside the accepted range %g <= beta <= %g" % ((beta,) + BETA_RANGE))
         return beta
+
+    @staticmethod
+    def _delta_value(params):
+        """`params.delta` as a float > 0 (inf: the Frobenius objective under this rule); a missing or non-positive value is a ValueError"""
+        delta = getattr(params, "delta", None)
+        if delta is None:
+            raise ValueError("norm='huber' needs params.delta: a float > 0, the residual at which the loss turns linear (main.py --delta)")
+        delta = float(delta)
+        if not delta > 0.0:
+            raise ValueError("norm='huber' with delta = %g is not accepted: params.delta must be a float > 0 (main.py --delta)" % delta)
+        return delta
 
     @staticmethod
     def _sign_check(beta, lo, comm1, nranks):
@@ -594,7 +621,7 @@ class PyNMF:
             return False
         name, method, norm = getattr(ops, "name", ""), str(self.method).lower(), str(self.norm).lower()
         if self.kind.family is not None and name != "hip":
-            return False                                            # (dnmf_is_mu_fit / dnmf_beta_mu_fit / dnmf_weighted_mu_fit live in the fp32 operator set only)
+            return False                                            # (dnmf_is_mu_fit / dnmf_beta_mu_fit / dnmf_huber_mu_fit / dnmf_weighted_mu_fit live in the fp32 operator set only)
         if self._weighted:                                          # dnmf_weighted_mu_fit: one problem per call, every norm it serves
             return hasattr(ops, "resident_fit" if self._resident else "slab_fit" if self._slab else "weighted_fit")   # (resident, slab: a batch per call)
         if self._masked_dense:
@@ -616,6 +643,8 @@ class PyNMF:
             return ops.weighted_fit(self.A_ij, self.V_ij, self.W_i, self.H_j, self.eps, self.norm, self.beta or 0.0, self.W_update, self.itr)
         if self._beta:                                              # dnmf_beta_mu_fit
             return ops.beta_fit(self.A_ij, self.W_i, self.H_j, self.eps, self.beta, self.W_update, self.itr)
+        if self._huber:                                             # dnmf_huber_mu_fit
+            return ops.huber_fit(self.A_ij, self.W_i, self.H_j, self.eps, self.delta, self.W_update, self.itr)
         return ops.fit(self.method, self.norm, self.A_ij, self.W_i, self.H_j, self.eps, self.W_update, self.itr,
                        column_sweep=(getattr(self.params, "hals_sweep", None) == "columns"))
 
@@ -805,7 +834,7 @@ class PyNMF:
         eps, norm, beta) for 'weighted' --; a fit that does not run that norm, or has no weights, is refused in `caller`'s name"""
         if family == 'weighted' and not self._weighted:
             raise ValueError("%s: this fit has no params.weights" % caller)
-        if family != 'weighted' and not (self._is if family == 'is' else self._beta):
+        if family != 'weighted' and not {'is': self._is, 'beta': self._beta, 'huber': self._huber}[family]:
             raise ValueError("%s: this fit runs norm='%s'; the divergence is reported under norm='%s'%s"
                              % (caller, self.norm, family,
                                 " (beta = 0 is norm='is': %s())" % caller.replace("beta_", "is_") if family == 'beta' and self._is else ""))
@@ -813,11 +842,11 @@ class PyNMF:
         fn = getattr(self._ops(), "%s_%s" % (family, op))
         if family == 'weighted':
             return fn(self.A_ij, self.V_ij, W, H, self.eps, self.norm, self.beta or 0.0)
-        return fn(self.A_ij, W, H, self.eps, *((self.beta,) if family == 'beta' else ()))
+        return fn(self.A_ij, W, H, self.eps, *((self.beta,) if family == 'beta' else (self.delta,) if family == 'huber' else ()))
 
     def _total(self, family, caller):
-        """the family's divergence of the current factors, summed over the grid"""
-        d = self._family_op(family, "divergence", caller)
+        """the family's divergence (under 'huber': its loss) of the current factors, summed over the grid"""
+        d = self._family_op(family, "loss" if family == 'huber' else "divergence", caller)
         self.comm1.allreduce_(d)
         return float(d.cpu())
 
@@ -843,12 +872,12 @@ class PyNMF:
         if self.kind.family is None:
             raise ValueError("divergence: this fit runs norm='%s' without params.weights; a divergence is reported under norm='is', "
                              "norm='beta' and under params.weights" % self.norm)
-        return getattr(self, self.kind.family + "_divergence")()
+        return self.huber_loss() if self._huber else getattr(self, self.kind.family + "_divergence")()
 
     def column_statistic(self):
         """The per-column statistic of this fit's family, what an NMFk sweep takes as `L_err`: `weighted_column_divergence()` under
         params.weights, else `is_column_divergence()` / `beta_column_divergence()` under those norms, else `column_err()`."""
-        if self.kind.family is None:
+        if self.kind.family in (None, 'huber'):                     # (the Huber loss has no per-column statistic: PyNMFk refuses the norm)
             return self.column_err()
         return getattr(self, self.kind.family + "_column_divergence")()
 
@@ -862,6 +891,12 @@ class PyNMF:
         """D_beta(A | W H + eps) of the CURRENT factors, summed over the grid (norm='beta': 1D grids, where every rank's block meets its own
         W rows and H columns).  The objective the rule does not increase; `fit()` keeps returning the Frobenius relative error."""
         return self._total('beta', "beta_divergence")
+
+    def huber_loss(self):
+        """sum rho_delta(A - (W H + eps)) of the CURRENT factors, summed over the grid (norm='huber': 1D grids, where every rank's block meets
+        its own W rows and H columns); rho_delta(r) = r^2 / 2 for |r| <= delta, delta |r| - delta^2 / 2 otherwise.  The objective the
+        reweighted rule does not increase; `fit()` keeps returning the Frobenius relative error."""
+        return self._total('huber', "huber_loss")
 
     def weighted_divergence(self):
         """The weighted objective sum v d(a | s') of the CURRENT factors over v > 0, summed over the grid: d of the fit's norm ('kl', 'is',

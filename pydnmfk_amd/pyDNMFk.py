@@ -244,6 +244,9 @@ class PyNMFk:
         # (the sweep's largest rank stands for k: what one batched call takes there, it takes at every smaller rank)
         k_range = getattr(params, "k_range", None) if getattr(params, "grid", None) else None
         kind = self.kind = fit_kind(A_ij, params, k=k_range[1] if k_range else getattr(params, "end_k", None))
+        if kind.norm == "huber":
+            raise NotImplementedError("PyNMFk with norm='huber' is not provided: rank estimation under the Huber loss needs a per-column "
+                                      "statistic that does not let the outliers vote (PyNMF factorises under norm='huber' at a given k)")
         self._sparse, self._masked = kind.form == "sparse", kind.form == "nan"
         self._is, self._beta, self._weighted, self.beta = kind.norm == "is", kind.norm == "beta", kind.weighted, kind.beta
         self._row = None                    # the sweep's own row of SWEEP_KINDS (None: a plain sweep)
